@@ -1,7 +1,13 @@
 #!/usr/bin/env python3
 """bench.py -- registrations/sec of the MI355X-native TEASER++ solve() hot path.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up (every lane on every distinct batch, then W steps), times ONE region of exactly K steps,
+writes what the last of them computed when --dump-outputs is given (DIR/<name>.npy, float64: see dump_outputs) and
+prints the result line.  Everything else
+described below -- the median of `--repeats` regions, the correctness guard, the host-resident loop, K1's roofline,
+board power, latency, per-stage times, the other configurations and the CPU baselines -- runs with --full only.
 
 N > 1: the script re-launches ITSELF as N ranks (one process per GPU) under
 `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1`; when it is
@@ -11,8 +17,8 @@ Top-level line = BASELINE.json configs[1] (synthetic N = 10 000 correspondences,
 the largest single-GPU configuration the metric is quoted on).  One STEP = one batched pass of the whole hot
 path (TIM build + pruning -> adjacency bitmap -> max clique -> GNC-TLS rotation -> TLS translation) over
 `--batch` independent problems; EVERY step sees problems it has not seen before.  `value` is measured with the
-point arrays already resident in HBM when the timed region starts (the bench contract: the median of `--repeats`
-timed regions of exactly K steps each); the same loop fed from page-locked HOST memory, H2D inside the timer
+point arrays already resident in HBM when the timed region starts (one timed region of exactly K steps; with --full
+the median of `--repeats` such regions); the same loop fed from page-locked HOST memory, H2D inside the timer
 (SURVEY.md 8(d)'s timer scope), is reported at the top level as `value_host_resident` (+ its ratio to `value`) and
 in detail as config.host_resident.  Steps go through the library's asynchronous batch API (teaser_hip_submit_batch /
 teaser_hip_wait, `--depth` batches on the lanes, plus one staged host batch whose copy runs on the copy stream).
@@ -90,21 +96,31 @@ def parse(argv=None):
                          "the latency-bound tail of batch k (clique, GNC, TLS: one workgroup per problem) shares "
                          "the GPU with batch k+1's K1 (2 is that pattern exactly; more only adds contention).  "
                          "1 = strictly one batch at a time")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beyond the headline figure: --repeats timed regions, the "
+                         "correctness guard, K1's roofline, the host-resident loop, board power, latency, per-stage "
+                         "times, the CPU baseline and the other BASELINE configurations (--configs).  Without it the "
+                         "run sets up, warms up, times ONE region of exactly --steps steps and prints the result line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (the result records of its problems, and the index "
+                         "lists of rank 0's problems) as DIR/<name>.npy in float64")
     ap.add_argument("--configs", default="4,3,5,scale",
-                    help="other BASELINE configurations to run after the top-level one ('' = none)")
+                    help="--full: other BASELINE configurations to run after the top-level one ('' = none)")
     ap.add_argument("--config-depth", default="config3=6,config5=3,scale=3",
-                    help="batches in flight per `configs` line (default for the others: --depth).  The lines whose solves "
-                         "need the host-driven bound-closing stage (colouring bound / exact search) are latency-bound per "
-                         "lane, not K1-bound: more lanes overlap them (profiles/r5d, r5h)")
+                    help="--full: batches in flight per `configs` line (default for the others: --depth).  The lines "
+                         "whose solves need the host-driven bound-closing stage (colouring bound / exact search) are "
+                         "latency-bound per lane, not K1-bound: more lanes overlap them (profiles/r5d, r5h)")
     ap.add_argument("--repeats", type=int, default=9,
-                    help="timed regions (of --steps steps each at the top level) per line; the median is reported")
+                    help="--full: timed regions (of --steps steps each at the top level) per line; the median is "
+                         "reported")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-host-resident", action="store_true",
-                    help="skip the second timed loop fed from page-locked host memory")
+                    help="--full: skip the second timed loop fed from page-locked host memory")
     ap.add_argument("--no-power", action="store_true",
-                    help="skip the >= 1.5 s power region (board power / clock from the GPU's hwmon node)")
+                    help="--full: skip the >= 1.5 s power region (board power / clock from the GPU's hwmon node)")
     ap.add_argument("--no-latency", action="store_true",
-                    help="skip the single-problem latency probe (rocprofv3 runs: keeps every K1 launch the same size)")
+                    help="--full: skip the single-problem latency probe (profiler runs: keeps every K1 launch the "
+                         "same size)")
     ap.add_argument("--cpu-solves", type=int, default=16)
     ap.add_argument("--gather", choices=("auto", "rccl", "host"), default="auto",
                     help="N > 1: how the result records are gathered and the ranks synchronised.  auto = RCCL when a probe "
@@ -654,6 +670,32 @@ def stage_breakdown(solver, s_t, d_t, offsets, sizes, reps=3):
     return {k: round(float(v), 4) for k, v in zip(keep, med)}
 
 
+def dump_outputs(out_dir, tp, solver, records, B):
+    """--dump-outputs: what a caller of the timed path receives for the problems of the last timed step, one float64
+    DIR/<name>.npy each: the fields of the gathered result records (every rank's problems, P of them: rotation
+    [P, 3, 3], translation [P, 3], scale, valid, ... [P]) and the index lists of this rank's B problems (max clique,
+    rotation and translation inliers: [B, longest list], padded with -1)."""
+    bt = tp.batched
+    P = records.shape[0]
+    arrays = {name: records[:, f] for name, f in (
+        ("valid", bt.F_VALID), ("status", bt.F_STATUS), ("scale", bt.F_SCALE), ("n", bt.F_N),
+        ("clique_size", bt.F_CLIQUE), ("n_rotation_inliers", bt.F_NROT), ("n_translation_inliers", bt.F_NTRANS),
+        ("gnc_cost", bt.F_COST), ("gnc_iterations", bt.F_ITERS), ("clique_exact_run", bt.F_EXACT),
+        ("num_edges", bt.F_EDGES), ("problem_index", bt.F_INDEX))}
+    arrays["rotation"] = records[:, bt.F_R:bt.F_R + 9].reshape(P, 3, 3)
+    arrays["translation"] = records[:, bt.F_T:bt.F_T + 3]
+    for name, get in (("max_clique", solver.getInlierMaxClique), ("rotation_inliers", solver.getRotationInliers),
+                      ("translation_inliers", solver.getTranslationInliers)):
+        lists = [get(b) for b in range(B)]
+        a = np.full((B, max([len(x) for x in lists] + [1])), -1.0)
+        for b, x in enumerate(lists):
+            a[b, :len(x)] = x
+        arrays[name] = a
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+
+
 def run_config(tag, tp, torch, runner, args, dev, world, rank, make_workload, steps, want_cpu):
     """One `configs` line: median of args.repeats timed regions of `steps` steps each."""
     solver, wl = make_workload()
@@ -984,41 +1026,54 @@ def main():
     offsets = np.arange(B, dtype=np.int64) * n
     sizes = np.full(B, n, dtype=np.int32)
 
-    # warm-up (arenas of every lane sized, kernels loaded), then a correctness guard on a batch the timed
+    # warm-up (arenas of every lane sized, kernels loaded), then (--full) a correctness guard on a batch the timed
     # region will not see again: the work is not skipped and is right
     # (the guard comes FIRST and the warm-up steps directly in front of the timed region: the host-side check leaves the
     # GPU idle for a few milliseconds, and a region that starts on an idle, down-clocked GPU ran up to 20 % slower than
     # the ones behind it -- profiles/r5z)
+    # Every lane sees every distinct batch in the warm-up (lane j <- batch (o + j) mod n_batches, as in run_config): a
+    # timed region that was the first to meet the batches' inputs ran 3-4 % slower than the regions behind it.
     k_chk = args.warmup % n_batches
-    runner.run_steps(0, D, pool, offsets, sizes, False)
-    out = runner.run_steps(k_chk, 1, pool, offsets, sizes, False)
-    for b in range(B):
-        R, t, n_in = truth[k_chk][b]
-        o = out[b]
-        # an outlier consistent with every inlier legitimately enlarges the maximum clique
-        assert o.valid == 1 and n_in <= o.clique_size <= n_in + 3, (o.valid, o.clique_size, n_in)
-        assert np.linalg.norm(np.array(o.rotation[:]).reshape(3, 3) - R) < 0.05
-        assert np.linalg.norm(np.array(o.translation[:]) - t) < 0.05
+    for o in range(n_batches):
+        runner.run_steps(o, D, pool, offsets, sizes, False)
+    if args.full:
+        out = runner.run_steps(k_chk, 1, pool, offsets, sizes, False)
+        for b in range(B):
+            R, t, n_in = truth[k_chk][b]
+            o = out[b]
+            # an outlier consistent with every inlier legitimately enlarges the maximum clique
+            assert o.valid == 1 and n_in <= o.clique_size <= n_in + 3, (o.valid, o.clique_size, n_in)
+            assert np.linalg.norm(np.array(o.rotation[:]).reshape(3, 3) - R) < 0.05
+            assert np.linalg.norm(np.array(o.translation[:]) - t) < 0.05
     runner.run_steps(0, max(args.warmup, D), pool, offsets, sizes, False)  # the W warm-up steps
 
     # ---- timed region: EXACTLY args.steps steps, inputs resident in HBM -------------------------
-    solver.set_profiling(2)  # HIP events around the K1 kernel only (two per step), inside the timed region
-    acc = dict(ms=0.0, launches=0, bytes=0, pairs=0, aux=0.0)
+    # (--full: the median of --repeats such regions, with HIP events around the K1 kernel for the roofline)
+    acc = None
+    if args.full:
+        solver.set_profiling(2)  # HIP events around the K1 kernel only (two per step), inside the timed region
+        acc = dict(ms=0.0, launches=0, bytes=0, pairs=0, aux=0.0)
+    gathered = {}
 
     def gather_tail(last):
         # final gather of the fixed-size result records (256 B each; RCCL over xGMI when N > 1)
         rec = tp.batched.pack_records([last[b] for b in range(B)], first_index=rank * B)
         allrec = tp.batched.gather_records(rec, world * B, dist if world > 1 else None, device=gather_dev)
         assert allrec.shape[0] == world * B
+        gathered["records"] = allrec
 
+    regions = max(1, args.repeats) if args.full else 1
     elapsed_all = [runner.timed(args.warmup + 1 + r * args.steps, args.steps, pool, offsets, sizes, False, acc, gather_tail)[0]
-                   for r in range(max(1, args.repeats))]
+                   for r in range(regions)]
     elapsed = float(np.median(elapsed_all))  # every region times EXACTLY args.steps steps; the median region is reported
-    solver.set_profiling(0)
+    if args.full:
+        solver.set_profiling(0)
+    if args.dump_outputs and rank == 0:  # (before anything else runs on this solver: its getters address the last step)
+        dump_outputs(args.dump_outputs, tp, solver, gathered["records"], B)
 
     # ---- the same loop fed from page-locked HOST memory: H2D inside the timer ----
     host_line = None
-    if not args.no_host_resident:
+    if args.full and not args.no_host_resident:
         pinned = [(tp.PinnedArray(s), tp.PinnedArray(d)) for s, d in host_pool]  # (see run_config)
         runner.run_steps(0, D + 1, pinned, offsets, sizes, True)
         ths = [runner.timed(args.warmup + 1 + r * args.steps, args.steps, pinned, offsets, sizes, True, None, gather_tail)[0]
@@ -1040,7 +1095,7 @@ def main():
     # because its clock is what the power controller gives.  hwmon samples are ~10 ms apart and the controller's
     # filter is slower still, so the region here is >= 1.5 s of steps, not the 20-step timed regions above.
     power = None
-    if not args.no_power:  # (every rank runs the region -- its barriers are collective --, rank 0's GPU is the one reported)
+    if args.full and not args.no_power:  # (every rank runs the region -- its barriers are collective --, rank 0's GPU is the one reported)
         ps = PowerSampler(torch, dev)
         have = ps.available()
         if world > 1:  # the ranks must agree on whether the region runs
@@ -1067,13 +1122,13 @@ def main():
     lat = []
     s_t, d_t = pool[0]
     one_off, one_n = np.zeros(1, dtype=np.int64), np.array([n], dtype=np.int32)
-    for _ in range(0 if args.no_latency else 10):
+    for _ in range(10 if args.full and not args.no_latency else 0):
         torch.cuda.synchronize()
         a = time.perf_counter()
         solver.solve_batch_device(s_t.data_ptr(), d_t.data_ptr(), one_off, one_n)
         lat.append(time.perf_counter() - a)
     lat_ms = 1e3 * float(np.median(lat)) if lat else None
-    stages = stage_breakdown(solver, s_t, d_t, offsets, sizes)
+    stages = stage_breakdown(solver, s_t, d_t, offsets, sizes) if args.full else None
     del pool
     # the headline handle goes away before the other configurations create theirs: every handle owns a stream per lane
     # plus a copy stream, and streams beyond the device's hardware queues share them -- a second live handle put the
@@ -1083,12 +1138,12 @@ def main():
     del solver
 
     # ---- the other BASELINE configurations (their own solvers, pools and timed regions) -----------
-    want_cpu = world == 1 and not args.no_cpu_baseline
+    want_cpu = args.full and world == 1 and not args.no_cpu_baseline
     top_cpu = None
     if want_cpu and rank == 0:  # first: its thread sweep (on the headline workload) picks the thread count for all
         top_cpu = cpu_baseline(tp, n, args.outlier_ratio, args.noise_bound, args.seed, args.cpu_solves, 10.0)
     cfg_lines = {}
-    for tag in [c.strip() for c in args.configs.split(",") if c.strip()]:
+    for tag in [c.strip() for c in args.configs.split(",") if c.strip() and args.full]:
         if tag == "4":
             mk = lambda: synth_workload(tp, args, rank, "config4", 128, 5000, 0.90, 8, 24, 10.0)
             cfg_lines["config4"] = run_config("config4", tp, torch, runner, args, dev, world, rank, mk, 24, want_cpu)
@@ -1107,11 +1162,10 @@ def main():
     if rank == 0:
         total_regs = world * B * args.steps
         value = total_regs / elapsed
-        traffic, traffic_src = k1_traffic(B, n)
         line = {
             "metric": "registrations/sec at N=%d correspondences, %.0f%% outliers" % (n, 100 * args.outlier_ratio),
             "value": value, "unit": "registrations/s", "n_gpus": world, "steps": args.steps,
-            "warmup": args.warmup, "ms_per_step": 1e3 * elapsed / args.steps,
+            "warmup": args.warmup, "full": args.full, "ms_per_step": 1e3 * elapsed / args.steps,
             "ms_per_step_repeats": [round(1e3 * t / args.steps, 4) for t in elapsed_all],
             "repeat_spread": round((max(elapsed_all) - min(elapsed_all)) / elapsed, 4),
             "value_host_resident": host_line["value"] if host_line else None,
@@ -1143,13 +1197,17 @@ def main():
                        "gather_backend": gather_info["gather_backend"], "rccl_ranks": gather_info["rccl_ranks"],
                        "parallelism": "independent problems per GPU, one all_gather of result records (%s)"
                                       % gather_info["gather_backend"]},
-            # `limiter`: what bounds the STEP -- the board's power cap when the long region ran at >= 97 % of it (then the
-            # executed-pipe fractions above describe a kernel whose clock is set by the power controller), else the pipe
-            "roofline": dict(roofline_object(acc["ms"], acc["launches"], acc["bytes"], acc["pairs"], acc["aux"],
-                                             traffic, traffic_src, k1_issue()), power=power,
-                             limiter=("board power cap" if power and (power.get("frac_of_cap") or 0) >= 0.97 else "kernel pipes")),
+            "roofline": None,
             "configs": cfg_lines,
         }
+        if args.full:
+            # `limiter`: what bounds the STEP -- the board's power cap when the long region ran at >= 97 % of it (then the
+            # executed-pipe fractions above describe a kernel whose clock is set by the power controller), else the pipe
+            traffic, traffic_src = k1_traffic(B, n)
+            line["roofline"] = dict(roofline_object(acc["ms"], acc["launches"], acc["bytes"], acc["pairs"], acc["aux"],
+                                                    traffic, traffic_src, k1_issue()), power=power,
+                                    limiter=("board power cap" if power and (power.get("frac_of_cap") or 0) >= 0.97
+                                             else "kernel pipes"))
         if top_cpu is not None:
             line["cpu_baseline"] = top_cpu
         print(json.dumps(line))

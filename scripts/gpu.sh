@@ -7,7 +7,7 @@
 #   k1tests          the K1 / bitmap parity tests only
 #   tests:<expr>     pytest -m gpu -k <expr>
 #   suite            the whole GPU suite as the driver runs it
-#   bench            python bench.py (the default command)      benchq: headline only, no CPU baseline
+#   bench            python bench.py --full (every line)        benchq: headline only, no CPU baseline
 #   benchprof        the headline command under rocprofv3 --kernel-trace --stats (--no-latency)
 #   k1pmc            K1 probe under rocprofv3: kernel trace, SQ counter sets, FETCH_SIZE, WRITE_SIZE (separate runs)
 #   cliquepmc        LDS / VMEM counters of the clique-stage kernels on config 5 (single + batched) and config 3
@@ -17,7 +17,7 @@
 #   scalebench       the three problems of bench.py's `configs.scale` line: synchronous with every stage timed, then pipelined
 #   scaleprof        the same under rocprofv3 --kernel-trace --stats (kernel table of the scale line)
 #   benchenv         headline only, one run per environment group in $ENVS ("A=1 B=2;C=3"), $BENCH_EXTRA = extra bench.py flags
-#   bench4           bench.py --configs 4 (HBM-resident and host-resident rates of the headline and of config 4)
+#   bench4           bench.py --full --configs 4 (HBM-resident and host-resident rates of the headline and of config 4)
 #   cfgdepth         the `configs` lines in $CFGS at the depths in $DEPTHS, per environment group in $ENVS
 #   pipecfg          scripts/pipe_config.py (a synthetic workload through the asynchronous API, nothing else in the process) per
 #                    "n rho batch depth steps" in $PIPES x environment group in $ENVS
@@ -52,11 +52,11 @@ for task in "$@"; do
     k1tests) timeout 600 python -m pytest tests -m gpu -q -x -k "k1 or config2 or config3 or config4 or fixture" > $OUT/k1tests.txt 2>&1; echo "rc=$?"; tail -5 $OUT/k1tests.txt ;;
     tests:*) timeout ${TEST_TIMEOUT:-300} python -m pytest tests -m gpu -q -x -k "${task#tests:}" > $OUT/tests_sel.txt 2>&1; echo "rc=$?"; tail -8 $OUT/tests_sel.txt ;;
     suite) SECONDS=0; TEASER_CERT_DEBUG=$OUT/cert_warmup.txt timeout 1500 python -m pytest tests/ -x -q -m gpu --durations=12 > $OUT/gpu_tests.txt 2>&1; echo "suite rc=$? in ${SECONDS}s"; tail -22 $OUT/gpu_tests.txt ;;
-    bench) timeout 1200 python bench.py > $OUT/bench.json 2> $OUT/bench.err; echo "rc=$?"; cut -c1-700 $OUT/bench.json; tail -3 $OUT/bench.err ;;
-    benchq) timeout 400 python bench.py --configs '' --no-cpu-baseline > $OUT/benchq.json 2> $OUT/benchq.err; echo "rc=$?"; cut -c1-500 $OUT/benchq.json; tail -3 $OUT/benchq.err ;;
+    bench) timeout 1200 python bench.py --full > $OUT/bench.json 2> $OUT/bench.err; echo "rc=$?"; cut -c1-700 $OUT/bench.json; tail -3 $OUT/bench.err ;;
+    benchq) timeout 400 python bench.py --full --configs '' --no-cpu-baseline > $OUT/benchq.json 2> $OUT/benchq.err; echo "rc=$?"; cut -c1-500 $OUT/benchq.json; tail -3 $OUT/benchq.err ;;
     benchenv)  # headline only, one run per environment setting in $ENVS (semicolon-separated "A=1 B=2" groups)
       IFS=";" read -ra GRPS <<< "${ENVS}"
-      for g in "${GRPS[@]}"; do env $g timeout 300 python bench.py $BENCH_EXTRA --configs '' --no-cpu-baseline --no-latency --no-host-resident --steps 40 2>/dev/null | python -c "
+      for g in "${GRPS[@]}"; do env $g timeout 300 python bench.py --full $BENCH_EXTRA --configs '' --no-cpu-baseline --no-latency --no-host-resident --steps 40 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); r=d['roofline']
 print('$g: %.0f reg/s, %.4f ms/step, K1 %.4f ms, aux %.4f ms' % (d['value'], d['ms_per_step'], r['avg_launch_ms'], r['aux_ms_per_launch']))"; done | tee $OUT/bench_env.txt ;;
@@ -70,7 +70,7 @@ for l in sys.stdin:
     c5env)  # config 5 (single + batched) per environment setting in $ENVS
       IFS=";" read -ra GRPS <<< "${ENVS}"
       for g in "${GRPS[@]}"; do echo "# $g"; env $g timeout 200 python scripts/profile_config5.py batch 2>/dev/null | python scripts/pick.py config,exact_ms,heuristic_ms,colour_ms,rotation_ms,total_ms; done | tee $OUT/config5_env.txt ;;
-    bench4) timeout 600 python bench.py --configs 4 --no-cpu-baseline > $OUT/bench4.json 2> $OUT/bench4.err; echo "rc=$?"; python - <<PY
+    bench4) timeout 600 python bench.py --full --configs 4 --no-cpu-baseline > $OUT/bench4.json 2> $OUT/bench4.err; echo "rc=$?"; python - <<PY
 import json
 d=json.loads(open("$OUT/bench4.json").read().strip().splitlines()[-1])
 print("top", round(d["value"]), d["ms_per_step"], d["config"].get("host_resident",{}))
@@ -81,14 +81,14 @@ PY
       IFS=";" read -ra GRPS <<< "${ENVS:-X=0}"
       for g in "${GRPS[@]}"; do for d in ${DEPTHS:-2 3 4}; do
         cd_arg=$(for c in config3 config4 config5 scale; do printf "%s=%s," $c $d; done)
-        env $g timeout 400 python bench.py --configs "${CFGS:-3}" --config-depth "$cd_arg" --no-cpu-baseline --no-latency --no-host-resident --steps 20 --repeats 2 2>/dev/null | python -c "
+        env $g timeout 400 python bench.py --full --configs "${CFGS:-3}" --config-depth "$cd_arg" --no-cpu-baseline --no-latency --no-host-resident --steps 20 --repeats 2 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 for k,c in d['configs'].items():
     if isinstance(c,dict) and 'ms_per_step' in c: print('$g depth $d %s: %.1f reg/s, %.4f ms/step %s' % (k, c['value'], c['ms_per_step'], c['ms_per_step_repeats']))"
       done; done | tee $OUT/config_depths.txt ;;
     benchprof)
-      PROF_TIMEOUT=600 prof bench_prof --kernel-trace --stats --output-format csv -d $OUT/bench_prof -o t -- python $R/bench.py --configs '' --no-cpu-baseline --no-latency --no-host-resident
+      PROF_TIMEOUT=600 prof bench_prof --kernel-trace --stats --output-format csv -d $OUT/bench_prof -o t -- python $R/bench.py --full --configs '' --no-cpu-baseline --no-latency --no-host-resident
       grep '^{' $OUT/bench_prof.log | tail -1 > $OUT/bench_under_rocprof.json
       cp $(find $OUT/bench_prof -name "*kernel_stats.csv" | head -1) $OUT/bench_kernel_stats.csv; head -14 $OUT/bench_kernel_stats.csv | cut -c1-150 ;;
     k1pmc)
@@ -155,7 +155,7 @@ PY
       PROF_TIMEOUT=300 prof tl3 --kernel-trace --output-format csv -d $OUT/tl3 -o t -- python $R/scripts/pipe_config.py 50000 0.99 1 ${D3:-3} 12
       python scripts/trace_timeline.py $(find $OUT/tl3 -name "*kernel_trace.csv" | head -1) 30 > $OUT/timeline3.txt 2>&1; tail -150 $OUT/timeline3.txt | cut -c1-160 ;;
     timeline)
-      PROF_TIMEOUT=600 prof tl --kernel-trace --output-format csv -d $OUT/tl -o t -- python $R/bench.py --configs '' --no-cpu-baseline --no-latency --no-host-resident --steps 16 --warmup 2 --pool 6
+      PROF_TIMEOUT=600 prof tl --kernel-trace --output-format csv -d $OUT/tl -o t -- python $R/bench.py --full --configs '' --no-cpu-baseline --no-latency --no-host-resident --steps 16 --warmup 2 --pool 6
       python scripts/trace_timeline.py $(find $OUT/tl -name "*kernel_trace.csv" | head -1) > $OUT/timeline.txt 2>&1; tail -60 $OUT/timeline.txt | cut -c1-200 ;;
     *) echo "unknown task $task" ;;
   esac

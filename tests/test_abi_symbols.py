@@ -100,6 +100,39 @@ def test_bench_roofline_object():
     assert z["achieved"] == 0.0 and z["traffic"] is None
 
 
+def test_bench_dump_outputs_writes_the_last_steps_results(tmp_path):
+    """bench.py --dump-outputs: the gathered result records and the index lists of the last timed step become
+    float64 .npy files (rotation [P, 3, 3], translation [P, 3], per-problem scalars, -1-padded index lists)."""
+    import importlib.util
+    import types
+
+    import numpy as np
+    spec = importlib.util.spec_from_file_location("bench_mod3", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    assert bench.parse(["--full"]).full is True and bench.parse([]).full is False
+    assert bench.parse(["--dump-outputs", "d"]).dump_outputs == "d"
+    sols = []
+    for b in range(3):
+        s = tp.SolutionC()
+        s.valid, s.scale, s.n, s.clique_size, s.num_edges = 1, 1.0, 100 + b, 5 + b, 40 + b
+        s.rotation[:] = list(np.eye(3).ravel() * (b + 1))
+        s.translation[:] = [b, 2 * b, 3 * b]
+        sols.append(s)
+    rec = tp.batched.pack_records(sols)
+    lists = {0: [1, 2], 1: [], 2: [0, 4, 7]}
+    solver = types.SimpleNamespace(getInlierMaxClique=lambda b: lists[b], getRotationInliers=lambda b: lists[b][:1],
+                                   getTranslationInliers=lambda b: lists[b][::-1])
+    bench.dump_outputs(str(tmp_path / "out"), tp, solver, rec, 3)
+    got = {p.stem: np.load(p) for p in (tmp_path / "out").iterdir()}
+    assert all(a.dtype == np.float64 for a in got.values())
+    assert got["rotation"].shape == (3, 3, 3) and np.array_equal(got["rotation"][2], 3 * np.eye(3))
+    assert np.array_equal(got["translation"][1], [1, 2, 3]) and got["clique_size"].tolist() == [5, 6, 7]
+    assert got["num_edges"].tolist() == [40, 41, 42] and got["n"].tolist() == [100, 101, 102]
+    assert got["max_clique"].tolist() == [[1, 2, -1], [-1, -1, -1], [0, 4, 7]]
+    assert got["translation_inliers"][2].tolist() == [7, 4, 0]
+
+
 def test_roofline_flat_copies_and_measured_valu_peak():
     """A record that keeps scalars only must still carry the pipe fractions, the traffic ratio and BOTH VALU peaks:
     the assumed one (4 cycles per wave64 instruction at 2.4 GHz) and the one measured for K1's instruction mix

@@ -92,8 +92,8 @@ def test_bench_two_ranks_on_one_gpu():
     import json
     import subprocess
 
-    common = ["--steps", "6", "--warmup", "3", "--repeats", "3", "--batch", "16", "--n", "4000", "--configs", "",
-              "--no-cpu-baseline", "--no-latency", "--no-host-resident"]
+    common = ["--full", "--steps", "6", "--warmup", "3", "--repeats", "3", "--batch", "16", "--n", "4000",
+              "--configs", "", "--no-cpu-baseline", "--no-latency", "--no-host-resident"]
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
 
     def run(extra):

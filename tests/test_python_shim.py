@@ -1,15 +1,16 @@
 """`import teaserpp_python` is a drop-in for the reference's module: the names of
 python/teaserpp_python/__init__.py:4-57 and both constructors of teaserpp_python.cc:82-103 (no GPU needed:
-constructor-argument handling is checked up to the point a device would be opened).  When the reference tree is
-present (this container, not the GPU box), every attribute its own Python examples read from the module and
-from the solver object is checked to exist."""
-import ast
+constructor-argument handling is checked up to the point a device would be opened).  Every attribute the
+reference's own Python examples read from the module and from the solver object (the names recorded in
+tests/golden/reference_python_names.json by tests/golden/make_reference_python_names.py) is checked to exist."""
 import importlib
+import json
 import os
 
 import pytest
 
 import teaserpp_python as t
+from util import ROOT
 
 tp = importlib.import_module("teaser-plusplus_amd")
 S = t.RobustRegistrationSolver
@@ -91,28 +92,15 @@ REF_EXAMPLES = ["/root/reference/python/teaserpp_python/teaserpp_example.py",
                 "/root/reference/examples/teaser_python_3dsmooth/teaser_python_3dsmooth.py"]
 
 
-def _attribute_chains(tree):
-    """Dotted names read in the file: 'teaserpp_python.X.Y' and 'solver.attr' style chains."""
-    out = set()
-    for node in ast.walk(tree):
-        if isinstance(node, ast.Attribute):
-            parts, cur = [], node
-            while isinstance(cur, ast.Attribute):
-                parts.append(cur.attr)
-                cur = cur.value
-            if isinstance(cur, ast.Name):
-                out.add((cur.id,) + tuple(reversed(parts)))
-    return out
+REF_NAMES = json.load(open(os.path.join(ROOT, "tests", "golden", "reference_python_names.json")))
 
 
 @pytest.mark.parametrize("path", REF_EXAMPLES)
 def test_reference_python_examples_find_every_name_they_use(path):
-    if not os.path.exists(path):
-        pytest.skip("reference tree not present (GPU box)")
-    tree = ast.parse(open(path).read())
+    chains = REF_NAMES[path.split("/reference/", 1)[1]]  # (the ids stay those of the reference paths)
     solver_names = {"solver", "teaser_solver"}
     seen = 0
-    for chain in _attribute_chains(tree):
+    for chain in chains:
         if chain[0] == "teaserpp_python":
             obj = t
             for a in chain[1:]:
