@@ -1,9 +1,10 @@
 #!/usr/bin/env python3
 """The workflow of the reference's examples/teaser_python_fpfh_icp (helpers.py:9-60, without Open3D): two
 clouds -> FPFH features -> mutual nearest-neighbour correspondences -> TEASER++ registration -> optional DRS
-certificate, everything on the MI355X.  Usage:
+certificate -> optional ICP refinement (example.py:66-71: registration_icp seeded with the TEASER++ pose,
+max_correspondence_distance = voxel), everything on the MI355X.  Usage:
 
-    python examples/teaser_python_fpfh.py [src.ply dst.ply] [--voxel 0.05] [--certify]
+    python examples/teaser_python_fpfh.py [src.ply dst.ply] [--voxel 0.05] [--certify] [--icp [--icp-iterations 100]]
 
 Without file arguments it runs BASELINE config 5 from tests/golden/config5_clouds.npz (the 3DMatch pair
 cloud_bin_0 / cloud_bin_4 after a 0.05 voxel grid).  ASCII / binary little-endian PLY with float x y z."""
@@ -52,6 +53,8 @@ def main():
     ap.add_argument("clouds", nargs="*")
     ap.add_argument("--voxel", type=float, default=0.05)
     ap.add_argument("--certify", action="store_true")
+    ap.add_argument("--icp", action="store_true", help="refine the TEASER++ pose with point-to-point ICP")
+    ap.add_argument("--icp-iterations", type=int, default=100)
     a = ap.parse_args()
     if len(a.clouds) == 2:
         A = voxel_downsample(read_ply_xyz(a.clouds[0]), a.voxel)
@@ -86,6 +89,19 @@ def main():
         dst = B[c[:, 1]].astype(np.float64).T - sol.translation.reshape(3, 1)
         res = cert.certify(sol.rotation, src[:, inl], dst[:, inl], np.ones(int(inl.sum())))
         print(res)
+    if a.icp:
+        T = np.eye(4)
+        T[:3, :3], T[:3, 3] = sol.rotation, sol.translation
+        P, Q = np.asarray(A, dtype=np.float64), np.asarray(B, dtype=np.float64)
+        crit = tp.ICPConvergenceCriteria(max_iteration=a.icp_iterations)
+        before = tp.registration_icp(P, Q, vox, T, criteria=tp.ICPConvergenceCriteria(max_iteration=0))
+        t3 = time.perf_counter()
+        icp = tp.registration_icp(P, Q, vox, T, tp.TransformationEstimationPointToPoint(), crit)   # example.py:66-71
+        t4 = time.perf_counter()
+        print("ICP before: fitness %.6f rmse %.6f" % (before.fitness, before.inlier_rmse))
+        print("ICP after:  fitness %.6f rmse %.6f iterations %d (%.2f ms)" % (icp.fitness, icp.inlier_rmse,
+                                                                              icp.iterations, 1e3 * (t4 - t3)))
+        print("T_icp =\n%s" % icp.transformation)
 
 
 if __name__ == "__main__":

@@ -1,0 +1,137 @@
+// teaser/icp.h -- point-to-point ICP refinement (Open3D's RegistrationICP with
+// TransformationEstimationPointToPoint(with_scaling = false)) over the MI355X C ABI (include/teaser_hip.h,
+// "ICP refinement", where the contract is written out).  Header-only.
+//
+// Types follow teaser/registration.h: with Eigen the clouds are Matrix<double,3,Dynamic> and the transform is
+// Eigen::Matrix4d; without Eigen the same members are the header's small value types and teaser::Matrix4 below
+// (column-major, operator()(r, c)).  The ICP object holds one device handle and is reusable but not re-entrant (one
+// call at a time per object); its constructor throws teaser::ICPError with TEASER_HIP_ERR_NO_DEVICE when no MI355X is
+// visible (there is no CPU path), registrationICP throws teaser::ICPError on a failed call.
+#pragma once
+
+#include <stdexcept>
+#include <string>
+#include <utility>
+#include <vector>
+
+#include "teaser/registration.h"
+#include "teaser_hip.h"
+
+namespace teaser {
+
+#if TEASER_HIP_HAVE_EIGEN
+using Matrix4 = Eigen::Matrix4d;
+#else
+struct Matrix4 {  // column-major 4 x 4, like Eigen::Matrix4d
+  std::array<double, 16> v{{1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1}};
+  static Matrix4 Identity() { return Matrix4(); }
+  double& operator()(int r, int c) { return v[(size_t)(4 * c + r)]; }
+  double operator()(int r, int c) const { return v[(size_t)(4 * c + r)]; }
+};
+#endif
+
+// Open3D's ICPConvergenceCriteria (the stop rule compares ABSOLUTE changes of fitness and inlier RMSE).
+struct ICPConvergenceCriteria {
+  double relative_fitness = 1e-6;
+  double relative_rmse = 1e-6;
+  int max_iteration = 30;
+};
+
+// Open3D's RegistrationResult + the number of iterations run.
+struct ICPResult {
+  Matrix4 transformation;
+  double fitness = 0;
+  double inlier_rmse = 0;
+  std::vector<std::pair<int, int>> correspondence_set;  // (source, target), ascending source index
+  int iterations = 0;
+};
+
+// What teaser::ICP throws when a library call fails; status() is the teaser_hip_status
+// (TEASER_HIP_ERR_NO_DEVICE from the constructor: no MI355X visible).
+class ICPError : public std::runtime_error {
+ public:
+  ICPError(int32_t status, const std::string& what) : std::runtime_error(what), status_(status) {}
+  int32_t status() const { return status_; }
+
+ private:
+  int32_t status_;
+};
+
+class ICP {
+ public:
+  explicit ICP(int device = -1) {
+    const int32_t rc = teaser_hip_icp_create(device, &h_);
+    if (rc != TEASER_HIP_OK)
+      throw ICPError(rc, "teaser::ICP: teaser_hip_icp_create failed (status " + std::to_string(rc) +
+                             (rc == TEASER_HIP_ERR_NO_DEVICE ? ": no MI355X visible, there is no CPU path)" : ")"));
+  }
+  ~ICP() { teaser_hip_icp_destroy(h_); }
+  ICP(const ICP&) = delete;
+  ICP& operator=(const ICP&) = delete;
+
+  // Many independent problems in one launch sequence; result b is identical to problem b run alone.
+  std::vector<ICPResult> registrationICPBatch(const std::vector<Matrix3X>& src, const std::vector<Matrix3X>& dst,
+                                              const std::vector<double>& max_correspondence_distance,
+                                              const std::vector<Matrix4>& init,
+                                              const std::vector<ICPConvergenceCriteria>& criteria) {
+    const size_t b = src.size();
+    if (dst.size() != b || max_correspondence_distance.size() != b || init.size() != b || criteria.size() != b)
+      throw std::invalid_argument("teaser::ICP: one entry per problem in every argument");
+    std::vector<const double*> ps(b), pd(b);
+    std::vector<int32_t> ns(b), nd(b);
+    std::vector<double> T(16 * b);
+    std::vector<teaser_icp_params_c> params(b);
+    std::vector<std::vector<int32_t>> corr(b);
+    std::vector<int32_t*> pc(b);
+    for (size_t k = 0; k < b; ++k) {
+      ps[k] = src[k].data();
+      pd[k] = dst[k].data();
+      ns[k] = (int32_t)src[k].cols();
+      nd[k] = (int32_t)dst[k].cols();
+      for (int r = 0; r < 4; ++r)
+        for (int c = 0; c < 4; ++c) T[16 * k + (size_t)(4 * r + c)] = init[k](r, c);
+      params[k].max_correspondence_distance = max_correspondence_distance[k];
+      params[k].max_iteration = criteria[k].max_iteration;
+      params[k].relative_fitness = criteria[k].relative_fitness;
+      params[k].relative_rmse = criteria[k].relative_rmse;
+      corr[k].resize(2 * (size_t)(ns[k] > 0 ? ns[k] : 1));
+      pc[k] = corr[k].data();
+    }
+    std::vector<teaser_icp_result_c> out(b);
+    const int32_t rc = teaser_hip_icp_batch(h_, (int32_t)b, ps.data(), ns.data(), pd.data(), nd.data(), T.data(),
+                                            params.data(), out.data(), pc.data());
+    if (rc != TEASER_HIP_OK)
+      throw ICPError(rc, "teaser::ICP: status " + std::to_string(rc) + ": " + teaser_hip_icp_last_error(h_));
+    std::vector<ICPResult> res(b);
+    for (size_t k = 0; k < b; ++k) {
+      for (int r = 0; r < 4; ++r)
+        for (int c = 0; c < 4; ++c) res[k].transformation(r, c) = out[k].transformation[4 * r + c];
+      res[k].fitness = out[k].fitness;
+      res[k].inlier_rmse = out[k].inlier_rmse;
+      res[k].iterations = out[k].iterations;
+      for (int32_t i = 0; i < out[k].n_correspondences; ++i)
+        res[k].correspondence_set.emplace_back(corr[k][(size_t)(2 * i)], corr[k][(size_t)(2 * i + 1)]);
+    }
+    return res;
+  }
+
+  ICPResult registrationICP(const Matrix3X& src, const Matrix3X& dst, double max_correspondence_distance,
+                            const Matrix4& init = Matrix4::Identity(),
+                            const ICPConvergenceCriteria& criteria = ICPConvergenceCriteria()) {
+    return registrationICPBatch({src}, {dst}, {max_correspondence_distance}, {init}, {criteria})[0];
+  }
+
+ private:
+  teaser_hip_icp* h_ = nullptr;
+};
+
+// Open3D's free function (registration_icp), one problem; creates a handle per call -- keep a teaser::ICP object
+// for repeated calls.
+inline ICPResult registrationICP(const Matrix3X& src, const Matrix3X& dst, double max_correspondence_distance,
+                                 const Matrix4& init = Matrix4::Identity(),
+                                 const ICPConvergenceCriteria& criteria = ICPConvergenceCriteria()) {
+  ICP icp;
+  return icp.registrationICP(src, dst, max_correspondence_distance, init, criteria);
+}
+
+}  // namespace teaser

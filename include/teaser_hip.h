@@ -386,6 +386,63 @@ TEASER_HIP_API const char* teaser_hip_last_error(const teaser_hip_solver* h);
 TEASER_HIP_API int32_t teaser_hip_abi_version(void);
 TEASER_HIP_API int32_t teaser_hip_device_count(void);
 
+/* ICP refinement (the reference's 3DMatch tutorial, examples/teaser_python_fpfh_icp/example.py:66-71, refines the
+ * TEASER++ pose with Open3D's registration_icp + TransformationEstimationPointToPoint(with_scaling=False)): batched
+ * point-to-point ICP with Open3D's semantics, on its OWN handle (nothing is shared with teaser_hip_solver).
+ * Per problem: source P (n_s points) and target Q (n_t points), xyz interleaved doubles (the layout of solve()'s
+ * 3 x N column-major input); r = max_correspondence_distance; init 4 x 4 row-major, last row 0 0 0 1.
+ *   apply(T, p)_row = ((T[row][0] x + T[row][1] y) + T[row][2] z) + T[row][3]      (no fused operations)
+ *   corr(X): for each source point i, the lexicographic minimum of (d2, j) over the target points j with
+ *            d2 = ((dx dx + dy dy) + dz dz) < r r, dx = X.x - Q.x: ties go to the smaller target index, a point at
+ *            exactly r is not a match.  fitness = |C| / n_s, inlier_rmse = sqrt(sum d2 / |C|), both 0 when C = {}.
+ *   loop:    X = apply(init, P), T = init, res = corr(X); for it = 1 .. max_iteration:
+ *            U = umeyama(X[C.src], Q[C.dst]) (identity when C is empty), T = U T, X = apply(U, X), prev = res,
+ *            res = corr(X), stop when |prev.fitness - res.fitness| < relative_fitness AND
+ *            |prev.inlier_rmse - res.inlier_rmse| < relative_rmse -- ABSOLUTE differences, despite Open3D's names.
+ *   umeyama: R = V diag(1,1,s) U^T from the SVD U S V^T of H = sum (p - mu_P)(q - mu_Q)^T, s = -1 iff
+ *            det(U) det(V) < 0, t = mu_Q - R mu_P (no scaling).  The sums are centred on a fixed point of each
+ *            problem (its target's bounding-box centre), so clouds far from the origin keep their precision.
+ * Output: T, fitness and inlier_rmse of the final res, iterations = loop bodies executed (max_iteration = 0
+ * returns init and corr(apply(init, P))), and the correspondence set sorted by source index.  n_s = 0 or n_t = 0
+ * is valid (no correspondences, fitness 0, rmse 0).  TEASER_HIP_ERR_BAD_ARG (teaser_hip_icp_last_error names the
+ * argument) for a non-finite or non-positive r, a negative max_iteration, negative or non-finite criteria, a
+ * non-finite init or one whose last row is not 0 0 0 1, non-finite points, a NULL pointer where n > 0.
+ * Results are deterministic: the same bits run to run, and for a problem alone or inside any batch.  An ICP handle is
+ * not re-entrant (one call at a time; distinct handles are independent), like a solver handle. */
+typedef struct teaser_icp_params_c {
+  double max_correspondence_distance; /* r; no default (Open3D's argument is required) */
+  int32_t max_iteration;              /* 30 */
+  double relative_fitness;            /* 1e-6 */
+  double relative_rmse;               /* 1e-6 */
+} teaser_icp_params_c;
+typedef struct teaser_icp_result_c {
+  double transformation[16]; /* row-major 4 x 4 */
+  double fitness;
+  double inlier_rmse;
+  int32_t iterations;
+  int32_t n_correspondences;
+} teaser_icp_result_c;
+typedef struct teaser_hip_icp teaser_hip_icp;
+/* Open3D's ICPConvergenceCriteria defaults; max_correspondence_distance is set to 0 (invalid until given). */
+TEASER_HIP_API int32_t teaser_hip_icp_params_default(teaser_icp_params_c* params);
+/* device < 0: the current device.  TEASER_HIP_ERR_NO_DEVICE without a GPU: there is no CPU path. */
+TEASER_HIP_API int32_t teaser_hip_icp_create(int32_t device, teaser_hip_icp** out);
+TEASER_HIP_API int32_t teaser_hip_icp_destroy(teaser_hip_icp* icp);
+TEASER_HIP_API const char* teaser_hip_icp_last_error(const teaser_hip_icp* icp);
+/* `batch` independent problems, HOST pointers per problem, borrowed for the call.  init: batch x 16 row-major
+ * or NULL (identity for every problem); params: one per problem; out: [batch]; corr: NULL, or per problem NULL or
+ * room for n_src[b] x 2 int32 (source index, target index), ascending source index, out[b].n_correspondences
+ * pairs written.  Problems of mixed sizes share the launches. */
+TEASER_HIP_API int32_t teaser_hip_icp_batch(teaser_hip_icp* icp, int32_t batch, const double* const* src,
+                                            const int32_t* n_src, const double* const* dst, const int32_t* n_dst,
+                                            const double* init, const teaser_icp_params_c* params,
+                                            teaser_icp_result_c* out, int32_t* const* corr);
+/* One problem: teaser_hip_icp_batch with batch = 1.  init may be NULL (identity); corr NULL or room for n_src x 2. */
+TEASER_HIP_API int32_t teaser_hip_icp_solve(teaser_hip_icp* icp, const double* src, int32_t n_src,
+                                            const double* dst, int32_t n_dst, const double* init,
+                                            const teaser_icp_params_c* params, teaser_icp_result_c* out,
+                                            int32_t* corr);
+
 /* Page-locked host memory from the HIP runtime THIS library runs on.  teaser_hip_submit_batch(..., INPUT_HOST) moves
  * the points with one DMA copy per cloud, at PCIe speed only when the runtime knows the pages are locked.  A buffer
  * pinned by another HIP runtime instance in the same process (e.g. the one a Python framework bundles) is pageable

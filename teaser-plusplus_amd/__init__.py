@@ -129,6 +129,8 @@ EXPORTED_SYMBOLS = [
     "teaser_hip_certifier_params_default", "teaser_hip_certify", "teaser_hip_certifier_warmup",
     "teaser_hip_comm_shard", "teaser_hip_comm_unique_id", "teaser_hip_comm_create", "teaser_hip_comm_destroy",
     "teaser_hip_comm_gather_solutions", "teaser_hip_comm_gather_indices", "teaser_hip_comm_last_error",
+    "teaser_hip_icp_params_default", "teaser_hip_icp_create", "teaser_hip_icp_destroy", "teaser_hip_icp_last_error",
+    "teaser_hip_icp_batch", "teaser_hip_icp_solve",
 ]
 
 
@@ -208,6 +210,8 @@ def lib():
     L.teaser_hip_last_error.restype = C.c_char_p
     L.teaser_hip_synth_problem.argtypes = [C.c_uint64, C.c_int32, C.c_double, C.c_double, _dp, _dp,
                                            _dp, _dp, _u8p]
+    from . import icp as _icp
+    _icp.declare(L)
     _lib = L
     return L
 
@@ -979,7 +983,11 @@ class MultiDeviceSolver:
 
 
 from . import batched  # noqa: E402,F401  (sharding + record gather for the multi-GPU batched mode)
+from .icp import (ICPConvergenceCriteria, RegistrationResult, TransformationEstimationPointToPoint,  # noqa: E402
+                  registration_icp, registration_icp_batch)
 
 __all__ = ["batched", "FPFHEstimation", "Matcher", "MultiDeviceSolver", "RobustRegistrationSolver", "RegistrationSolution", "RotationEstimationAlgorithm",
            "InlierSelectionMode", "InlierGraphFormulation", "TeaserHipError", "synth_problem",
-           "device_count", "build", "lib", "LIB_PATH", "EXPORTED_SYMBOLS", "certifier_warmup", "PinnedArray"]
+           "device_count", "build", "lib", "LIB_PATH", "EXPORTED_SYMBOLS", "certifier_warmup", "PinnedArray",
+           "ICPConvergenceCriteria", "TransformationEstimationPointToPoint", "RegistrationResult", "registration_icp",
+           "registration_icp_batch"]

@@ -1,0 +1,343 @@
+// icp.hip -- host side of the batched point-to-point ICP (include/teaser_hip.h, "ICP refinement"): its own handle,
+// argument validation, the per-call target index and the iteration loop.  Kernels: kernels_icp.hip.
+//
+// The host enqueues iterations in groups of kIcpGroup (two launches each); after a group ONE small copy of the
+// number of unfinished problems decides whether another group follows.  There is no host round trip inside a group:
+// a problem that finishes mid-group makes its remaining launches return at once.
+#include <math.h>
+#include <string.h>
+
+#include <algorithm>
+#include <string>
+#include <vector>
+
+#include "icp_internal.h"
+#include "teaser_hip.h"
+
+using namespace thip;
+
+namespace {
+
+constexpr int kIcpGroup = 8;
+
+struct DevBuf {
+  void* p = nullptr;
+  size_t cap = 0;
+  bool ensure(size_t bytes) {
+    if (bytes <= cap) return true;
+    if (p) (void)hipFree(p);
+    p = nullptr;
+    cap = 0;
+    const size_t want = std::max<size_t>(bytes + bytes / 4, 256);
+    if (hipMalloc(&p, want) != hipSuccess) return false;
+    cap = want;
+    return true;
+  }
+  void release() {
+    if (p) (void)hipFree(p);
+    p = nullptr;
+    cap = 0;
+  }
+  template <typename T>
+  T* as() const { return static_cast<T*>(p); }
+};
+
+enum { B_DESC, B_STATE, B_BLK, B_TBLK, B_X, B_Q, B_TBUCKET, B_BCOUNT, B_BSTART, B_CURSOR, B_QS, B_QJ, B_MATCH,
+       B_PARTIALS, B_LIVE, B_COUNT };
+
+}  // namespace
+
+struct teaser_hip_icp {
+  int device = 0;
+  hipStream_t stream = nullptr;
+  int32_t* h_live = nullptr;  // page-locked: the one copy per iteration group
+  DevBuf buf[B_COUNT];
+  std::string err;
+  std::vector<double> stage;  // host packing of the points
+};
+
+namespace {
+
+int32_t fail(teaser_hip_icp* h, int32_t status, const std::string& msg) {
+  h->err = msg;
+  return status;
+}
+
+int32_t hip_fail(teaser_hip_icp* h, hipError_t e, const char* what) {
+  h->err = std::string(what) + ": " + hipGetErrorString(e);
+  return TEASER_HIP_ERR_HIP;
+}
+
+bool finite_points(const double* p, int64_t n) {
+  for (int64_t k = 0; k < 3 * n; ++k)
+    if (!std::isfinite(p[k])) return false;
+  return true;
+}
+
+std::string at(int b) { return " (problem " + std::to_string(b) + ")"; }
+
+int32_t validate(teaser_hip_icp* h, int32_t batch, const double* const* src, const int32_t* n_src,
+                 const double* const* dst, const int32_t* n_dst, const double* init,
+                 const teaser_icp_params_c* params, teaser_icp_result_c* out) {
+  if (batch < 0) return fail(h, TEASER_HIP_ERR_BAD_ARG, "batch must be >= 0");
+  if (batch == 0) return TEASER_HIP_OK;
+  if (!n_src || !n_dst) return fail(h, TEASER_HIP_ERR_BAD_ARG, "n_src / n_dst must not be NULL");
+  if (!params) return fail(h, TEASER_HIP_ERR_BAD_ARG, "params must not be NULL");
+  if (!out) return fail(h, TEASER_HIP_ERR_BAD_ARG, "out must not be NULL");
+  int64_t total_s = 0, total_t = 0;
+  for (int b = 0; b < batch; ++b) {
+    const teaser_icp_params_c& p = params[b];
+    const double r = p.max_correspondence_distance;
+    if (!std::isfinite(r) || !(r > 0))
+      return fail(h, TEASER_HIP_ERR_BAD_ARG, "max_correspondence_distance must be finite and > 0" + at(b));
+    if (!std::isfinite(r * r) || !(r * r > 0))
+      return fail(h, TEASER_HIP_ERR_BAD_ARG, "max_correspondence_distance squared must be finite and > 0" + at(b));
+    if (p.max_iteration < 0) return fail(h, TEASER_HIP_ERR_BAD_ARG, "max_iteration must be >= 0" + at(b));
+    if (!std::isfinite(p.relative_fitness) || p.relative_fitness < 0)
+      return fail(h, TEASER_HIP_ERR_BAD_ARG, "relative_fitness must be finite and >= 0" + at(b));
+    if (!std::isfinite(p.relative_rmse) || p.relative_rmse < 0)
+      return fail(h, TEASER_HIP_ERR_BAD_ARG, "relative_rmse must be finite and >= 0" + at(b));
+    if (n_src[b] < 0 || n_dst[b] < 0) return fail(h, TEASER_HIP_ERR_BAD_ARG, "n_src / n_dst must be >= 0" + at(b));
+    if (n_src[b] > 0 && (!src || !src[b])) return fail(h, TEASER_HIP_ERR_BAD_ARG, "src is NULL" + at(b));
+    if (n_dst[b] > 0 && (!dst || !dst[b])) return fail(h, TEASER_HIP_ERR_BAD_ARG, "dst is NULL" + at(b));
+    if (n_src[b] > 0 && !finite_points(src[b], n_src[b]))
+      return fail(h, TEASER_HIP_ERR_BAD_ARG, "src has a non-finite coordinate" + at(b));
+    if (n_dst[b] > 0 && !finite_points(dst[b], n_dst[b]))
+      return fail(h, TEASER_HIP_ERR_BAD_ARG, "dst has a non-finite coordinate" + at(b));
+    if (init) {
+      const double* T = init + 16 * (int64_t)b;
+      for (int k = 0; k < 16; ++k)
+        if (!std::isfinite(T[k])) return fail(h, TEASER_HIP_ERR_BAD_ARG, "init is not finite" + at(b));
+      if (T[12] != 0 || T[13] != 0 || T[14] != 0 || T[15] != 1)
+        return fail(h, TEASER_HIP_ERR_BAD_ARG, "init: last row must be 0 0 0 1" + at(b));
+    }
+    total_s += n_src[b];
+    total_t += n_dst[b];
+  }
+  if (total_s >= INT32_MAX || total_t >= INT32_MAX / 2)
+    return fail(h, TEASER_HIP_ERR_BAD_ARG, "too many points in one call");
+  return TEASER_HIP_OK;
+}
+
+int64_t next_pow2(int64_t v) {
+  int64_t p = 1;
+  while (p < v) p <<= 1;
+  return p;
+}
+
+}  // namespace
+
+extern "C" {
+
+int32_t teaser_hip_icp_params_default(teaser_icp_params_c* p) {
+  if (!p) return TEASER_HIP_ERR_BAD_ARG;
+  p->max_correspondence_distance = 0;  // required argument of registration_icp
+  p->max_iteration = 30;               // Open3D ICPConvergenceCriteria
+  p->relative_fitness = 1e-6;
+  p->relative_rmse = 1e-6;
+  return TEASER_HIP_OK;
+}
+
+int32_t teaser_hip_icp_create(int32_t device, teaser_hip_icp** out) {
+  if (!out) return TEASER_HIP_ERR_BAD_ARG;
+  *out = nullptr;
+  int count = 0;
+  if (hipGetDeviceCount(&count) != hipSuccess || count <= 0) return TEASER_HIP_ERR_NO_DEVICE;
+  if (device < 0 && hipGetDevice(&device) != hipSuccess) return TEASER_HIP_ERR_NO_DEVICE;
+  if (device >= count) return TEASER_HIP_ERR_BAD_ARG;
+  if (hipSetDevice(device) != hipSuccess) return TEASER_HIP_ERR_HIP;
+  teaser_hip_icp* h = new teaser_hip_icp();
+  h->device = device;
+  if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess) {
+    delete h;
+    return TEASER_HIP_ERR_HIP;
+  }
+  if (hipHostMalloc((void**)&h->h_live, sizeof(int32_t)) != hipSuccess) {
+    (void)hipStreamDestroy(h->stream);
+    delete h;
+    return TEASER_HIP_ERR_HIP;
+  }
+  *out = h;
+  return TEASER_HIP_OK;
+}
+
+int32_t teaser_hip_icp_destroy(teaser_hip_icp* h) {
+  if (!h) return TEASER_HIP_OK;
+  (void)hipSetDevice(h->device);
+  if (h->stream) (void)hipStreamSynchronize(h->stream);
+  for (DevBuf& b : h->buf) b.release();
+  if (h->h_live) (void)hipHostFree(h->h_live);
+  if (h->stream) (void)hipStreamDestroy(h->stream);
+  delete h;
+  return TEASER_HIP_OK;
+}
+
+const char* teaser_hip_icp_last_error(const teaser_hip_icp* h) { return h ? h->err.c_str() : ""; }
+
+int32_t teaser_hip_icp_batch(teaser_hip_icp* h, int32_t batch, const double* const* src, const int32_t* n_src,
+                             const double* const* dst, const int32_t* n_dst, const double* init,
+                             const teaser_icp_params_c* params, teaser_icp_result_c* out, int32_t* const* corr) {
+  if (!h) return TEASER_HIP_ERR_BAD_ARG;
+  h->err.clear();
+  int32_t rc = validate(h, batch, src, n_src, dst, n_dst, init, params, out);
+  if (rc != TEASER_HIP_OK || batch == 0) return rc;
+  hipError_t e = hipSetDevice(h->device);
+  if (e != hipSuccess) return hip_fail(h, e, "hipSetDevice");
+
+  // ---- descriptors, block maps and initial state (host) ----
+  std::vector<IcpDesc> desc((size_t)batch);
+  std::vector<IcpState> state((size_t)batch);
+  std::vector<int32_t> blk_prob, tblk_prob;
+  int64_t s_off = 0, t_off = 0, b_off = 0;
+  int max_iter = 0;
+  for (int b = 0; b < batch; ++b) {
+    IcpDesc& d = desc[(size_t)b];
+    memset(&d, 0, sizeof(d));
+    const teaser_icp_params_c& p = params[b];
+    const double r = p.max_correspondence_distance;
+    d.n_s = n_src[b];
+    d.n_t = n_dst[b];
+    d.s_off = s_off;
+    d.t_off = t_off;
+    d.b_off = b_off;
+    d.blk_off = (int32_t)blk_prob.size();
+    d.nblk = (d.n_s + kIcpBlock - 1) / kIcpBlock;
+    d.tblk_off = (int32_t)tblk_prob.size();
+    d.r2 = r * r;
+    d.rel_fitness = p.relative_fitness;
+    d.rel_rmse = p.relative_rmse;
+    d.max_iteration = p.max_iteration;
+    max_iter = std::max(max_iter, p.max_iteration);
+    if (d.n_t > 0) {
+      double lo[3], hi[3];
+      for (int c = 0; c < 3; ++c) lo[c] = hi[c] = dst[b][c];
+      for (int64_t j = 1; j < d.n_t; ++j)
+        for (int c = 0; c < 3; ++c) {
+          lo[c] = std::min(lo[c], dst[b][3 * j + c]);
+          hi[c] = std::max(hi[c], dst[b][3 * j + c]);
+        }
+      double mag = 0;
+      for (int c = 0; c < 3; ++c) mag = std::max(mag, std::max(fabs(lo[c]), fabs(hi[c])));
+      // cell edge slightly above r: two points closer than r then differ by at most one cell per axis although
+      // their cell coordinates are rounded (relative margin 1e-6; absolute 1e-12 of the coordinates' magnitude)
+      const double cell = r * (1 + 1e-6) + 1e-12 * mag;
+      d.inv_h = 1.0 / cell;
+      for (int c = 0; c < 3; ++c) {
+        d.origin[c] = lo[c];
+        d.centre[c] = 0.5 * (lo[c] + hi[c]);
+        d.cmax[c] = icp_cell(hi[c], lo[c], d.inv_h);
+      }
+      d.tb_mask = next_pow2(2 * (int64_t)d.n_t) - 1;
+      b_off += d.tb_mask + 2;  // tb + 1 starts
+    }
+    for (int k = 0; k < d.nblk; ++k) blk_prob.push_back(b);
+    for (int k = 0; k < (d.n_t + 255) / 256; ++k) tblk_prob.push_back(b);
+    s_off += d.n_s;
+    t_off += d.n_t;
+    IcpState& st = state[(size_t)b];
+    memset(&st, 0, sizeof(st));
+    static const double kEye[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
+    const double* T0 = init ? init + 16 * (int64_t)b : kEye;
+    for (int k = 0; k < 16; ++k) st.T[k] = T0[k];
+    for (int k = 0; k < 12; ++k) st.U[k] = T0[k];  // the first correspondence pass applies init to P
+  }
+  const int n_blk = (int)blk_prob.size(), n_tblk = (int)tblk_prob.size();
+
+  // ---- device buffers ----
+  const size_t bytes[B_COUNT] = {
+      sizeof(IcpDesc) * batch, sizeof(IcpState) * batch, sizeof(int32_t) * std::max(n_blk, 1),
+      sizeof(int32_t) * std::max(n_tblk, 1), sizeof(double) * 3 * std::max<int64_t>(s_off, 1),
+      sizeof(double) * 3 * std::max<int64_t>(t_off, 1), sizeof(int32_t) * std::max<int64_t>(t_off, 1),
+      sizeof(int32_t) * std::max<int64_t>(b_off, 1), sizeof(int32_t) * std::max<int64_t>(b_off, 1),
+      sizeof(int32_t) * std::max<int64_t>(b_off, 1), sizeof(double) * 3 * std::max<int64_t>(t_off, 1),
+      sizeof(int32_t) * std::max<int64_t>(t_off, 1), sizeof(int32_t) * std::max<int64_t>(s_off, 1),
+      sizeof(double) * kIcpSums * std::max(n_blk, 1), sizeof(int32_t)};
+  for (int k = 0; k < B_COUNT; ++k)
+    if (!h->buf[k].ensure(bytes[k])) return fail(h, TEASER_HIP_ERR_OOM, "hipMalloc failed (ICP buffers)");
+  hipStream_t s = h->stream;
+  DevBuf* B = h->buf;
+
+  h->stage.resize((size_t)(3 * (s_off + t_off)));
+  for (int b = 0; b < batch; ++b) {
+    if (desc[(size_t)b].n_s) memcpy(&h->stage[(size_t)(3 * desc[(size_t)b].s_off)], src[b], 24 * (size_t)n_src[b]);
+    if (desc[(size_t)b].n_t)
+      memcpy(&h->stage[(size_t)(3 * (s_off + desc[(size_t)b].t_off))], dst[b], 24 * (size_t)n_dst[b]);
+  }
+  struct Copy {
+    void* d;
+    const void* hsrc;
+    size_t n;
+  } copies[] = {{B[B_DESC].p, desc.data(), bytes[B_DESC]},
+                {B[B_STATE].p, state.data(), bytes[B_STATE]},
+                {B[B_BLK].p, blk_prob.data(), sizeof(int32_t) * n_blk},
+                {B[B_TBLK].p, tblk_prob.data(), sizeof(int32_t) * n_tblk},
+                {B[B_X].p, h->stage.data(), sizeof(double) * 3 * s_off},
+                {B[B_Q].p, h->stage.data() + 3 * s_off, sizeof(double) * 3 * t_off}};
+  for (const Copy& c : copies)
+    if (c.n && (e = hipMemcpyAsync(c.d, c.hsrc, c.n, hipMemcpyHostToDevice, s)) != hipSuccess)
+      return hip_fail(h, e, "hipMemcpyAsync (inputs)");
+  if (b_off && (e = hipMemsetAsync(B[B_BCOUNT].p, 0, sizeof(int32_t) * b_off, s)) != hipSuccess)
+    return hip_fail(h, e, "hipMemsetAsync");
+
+  // ---- target index, then the iteration groups ----
+  launch_icp_index(s, B[B_DESC].as<IcpDesc>(), B[B_TBLK].as<int32_t>(), n_tblk, batch, B[B_Q].as<double>(),
+                   B[B_TBUCKET].as<int32_t>(), B[B_BCOUNT].as<int32_t>(), B[B_BSTART].as<int32_t>(),
+                   B[B_CURSOR].as<int32_t>(), B[B_QS].as<double>(), B[B_QJ].as<int32_t>());
+  int64_t passes = 0;  // correspondence passes enqueued: the first one + one per iteration
+  for (;;) {
+    for (int g = 0; g < kIcpGroup && passes <= (int64_t)max_iter; ++g, ++passes)
+      launch_icp_iteration(s, B[B_DESC].as<IcpDesc>(), B[B_STATE].as<IcpState>(), B[B_BLK].as<int32_t>(), n_blk,
+                           batch, B[B_X].as<double>(), B[B_QS].as<double>(), B[B_QJ].as<int32_t>(),
+                           B[B_BSTART].as<int32_t>(), B[B_MATCH].as<int32_t>(), B[B_PARTIALS].as<double>());
+    launch_icp_live(s, B[B_STATE].as<IcpState>(), batch, B[B_LIVE].as<int32_t>());
+    if ((e = hipGetLastError()) != hipSuccess) return hip_fail(h, e, "ICP kernel launch");
+    if ((e = hipMemcpyAsync(h->h_live, B[B_LIVE].p, sizeof(int32_t), hipMemcpyDeviceToHost, s)) != hipSuccess)
+      return hip_fail(h, e, "hipMemcpyAsync (live count)");
+    if ((e = hipStreamSynchronize(s)) != hipSuccess) return hip_fail(h, e, "ICP iterations");
+    if (*h->h_live == 0) break;
+    if (passes > (int64_t)max_iter) return fail(h, TEASER_HIP_ERR_HIP, "ICP: problems left unfinished");
+  }
+
+  // ---- results ----
+  if ((e = hipMemcpyAsync(state.data(), B[B_STATE].p, bytes[B_STATE], hipMemcpyDeviceToHost, s)) != hipSuccess)
+    return hip_fail(h, e, "hipMemcpyAsync (state)");
+  bool want_corr = false;
+  for (int b = 0; corr && b < batch; ++b) want_corr |= corr[b] != nullptr && n_src[b] > 0;
+  std::vector<int32_t> match;
+  if (want_corr) {
+    match.resize((size_t)s_off);
+    if ((e = hipMemcpyAsync(match.data(), B[B_MATCH].p, sizeof(int32_t) * s_off, hipMemcpyDeviceToHost, s)) !=
+        hipSuccess)
+      return hip_fail(h, e, "hipMemcpyAsync (correspondences)");
+  }
+  if ((e = hipStreamSynchronize(s)) != hipSuccess) return hip_fail(h, e, "ICP results");
+  for (int b = 0; b < batch; ++b) {
+    const IcpState& st = state[(size_t)b];
+    teaser_icp_result_c& o = out[b];
+    for (int k = 0; k < 16; ++k) o.transformation[k] = st.T[k];
+    o.fitness = st.fitness;
+    o.inlier_rmse = st.rmse;
+    o.iterations = st.iterations;
+    o.n_correspondences = st.count;
+    if (want_corr && corr[b] && n_src[b] > 0) {
+      const int32_t* m = match.data() + desc[(size_t)b].s_off;
+      int32_t k = 0;
+      for (int32_t i = 0; i < n_src[b]; ++i)
+        if (m[i] >= 0) {
+          corr[b][2 * k] = i;
+          corr[b][2 * k + 1] = m[i];
+          ++k;
+        }
+    }
+  }
+  return TEASER_HIP_OK;
+}
+
+int32_t teaser_hip_icp_solve(teaser_hip_icp* h, const double* src, int32_t n_src, const double* dst, int32_t n_dst,
+                             const double* init, const teaser_icp_params_c* params, teaser_icp_result_c* out,
+                             int32_t* corr) {
+  int32_t* const corrs[1] = {corr};
+  return teaser_hip_icp_batch(h, 1, &src, &n_src, &dst, &n_dst, init, params, out, corrs);
+}
+
+}  // extern "C"

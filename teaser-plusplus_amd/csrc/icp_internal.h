@@ -1,0 +1,69 @@
+// icp_internal.h -- structures shared by the ICP host code (icp.hip) and its gfx950 kernels (kernels_icp.hip).
+// Kept apart from internal.h: the ICP handle shares nothing with teaser_hip_solver.
+#pragma once
+
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+namespace thip {
+
+constexpr int kIcpBlock = 256;   // source points per correspondence block (the chunking depends on n_s alone)
+constexpr int kIcpSums = 17;     // {count, sum d2, sum p' (3), sum q' (3), sum p' q'^T (9)} of one block
+constexpr int kIcpScanThreads = 1024;
+
+// One problem of a batch (host-built, read-only on the device).  Cell coordinates of a point x are
+// floor((x - origin) * inv_h) per axis, clamped to [-2, 2^40] (monotone, so neighbouring cells stay neighbours).
+struct IcpDesc {
+  int32_t n_s, n_t;
+  int64_t s_off;      // first source point in the packed X / match arrays
+  int64_t t_off;      // first target point in the packed target arrays
+  int64_t b_off;      // first entry of this problem's bucket-start table (tb + 1 entries)
+  int64_t tb_mask;    // bucket table size - 1 (power of two >= 2 n_t); unused when n_t = 0
+  int32_t blk_off;    // first correspondence block of this problem
+  int32_t nblk;       // ceil(n_s / kIcpBlock)
+  int64_t cmax[3];    // largest target cell coordinate per axis
+  double origin[3];   // target bounding-box minimum
+  double inv_h;       // 1 / cell edge (cell edge = r (1 + 1e-6) + 1e-12 max |bbox coordinate|)
+  double centre[3];   // target bounding-box centre: the fixed point the sums are centred on
+  double r2;          // r * r
+  double rel_fitness, rel_rmse;
+  int32_t max_iteration;
+  int32_t tblk_off;   // first target block of this problem (index build)
+};
+
+// Mutable per-problem state.
+struct IcpState {
+  double T[16];       // accumulated transform, row-major 4x4
+  double U[12];       // rows 0..2 of the transform the next correspondence launch applies to X
+  double fitness, rmse;
+  int32_t iterations; // loop bodies executed
+  int32_t count;      // |C| of the current result
+  int32_t phase;      // 0: the first correspondence pass has not been finalized yet
+  int32_t done;       // 1: converged or out of iterations -- every later launch returns at once
+};
+
+// Grid cell of one coordinate; host (descriptor set-up) and device (index build, search) run the same expression.
+__host__ __device__ inline int64_t icp_cell(double x, double origin, double inv_h) {
+  double v = floor((x - origin) * inv_h);
+  v = v < -2.0 ? -2.0 : (v > 1099511627776.0 ? 1099511627776.0 : v);
+  return (int64_t)v;
+}
+
+__host__ __device__ inline int64_t icp_bucket(int64_t cx, int64_t cy, int64_t cz, int64_t mask) {
+  uint64_t k = (uint64_t)cx * 0x9E3779B97F4A7C15ull ^ (uint64_t)cy * 0xC2B2AE3D27D4EB4Full ^
+               (uint64_t)cz * 0x165667B19E3779F9ull;
+  k ^= k >> 31;
+  k *= 0xD6E8FEB86659FD93ull;
+  k ^= k >> 32;
+  return (int64_t)(k & (uint64_t)mask);
+}
+
+void launch_icp_index(hipStream_t s, const IcpDesc* d_desc, const int32_t* d_tblk_prob, int n_tblk, int batch,
+                      const double* d_q, int32_t* d_tbucket, int32_t* d_bcount, int32_t* d_bstart,
+                      int32_t* d_cursor, double* d_qs, int32_t* d_qj);
+void launch_icp_iteration(hipStream_t s, const IcpDesc* d_desc, IcpState* d_state, const int32_t* d_blk_prob,
+                          int n_blk, int batch, double* d_x, const double* d_qs, const int32_t* d_qj,
+                          const int32_t* d_bstart, int32_t* d_match, double* d_partials);
+void launch_icp_live(hipStream_t s, const IcpState* d_state, int batch, int32_t* d_live);
+
+}  // namespace thip

@@ -1,0 +1,208 @@
+"""Point-to-point ICP refinement on the GPU with Open3D's interface (``o3d.pipelines.registration``):
+``registration_icp(source, target, max_correspondence_distance, init, estimation_method, criteria)`` and the batched
+``registration_icp_batch``.  The semantics are those of Open3D's RegistrationICP with
+TransformationEstimationPointToPoint(with_scaling=False), written out in include/teaser_hip.h ("ICP refinement").
+
+One library handle is kept per device between calls (no HIP context per call); calls from several threads are safe --
+each handle has a lock, so calls for one device run one after the other.  device=-1 means the calling thread's
+current HIP device at the time of the call.  Without a GPU the calls raise
+TeaserHipError (NO_DEVICE): there is no CPU path."""
+import atexit
+import ctypes as C
+import os
+import threading
+
+import numpy as np
+
+_vp, _ip, _dp = C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_double)
+
+
+class IcpParamsC(C.Structure):
+    _fields_ = [("max_correspondence_distance", C.c_double), ("max_iteration", C.c_int32),
+                ("relative_fitness", C.c_double), ("relative_rmse", C.c_double)]
+
+
+class IcpResultC(C.Structure):
+    _fields_ = [("transformation", C.c_double * 16), ("fitness", C.c_double), ("inlier_rmse", C.c_double),
+                ("iterations", C.c_int32), ("n_correspondences", C.c_int32)]
+
+
+def declare(L):
+    """ctypes signatures of the ICP entry points (called by the package's lib())."""
+    L.teaser_hip_icp_params_default.argtypes = [C.POINTER(IcpParamsC)]
+    L.teaser_hip_icp_create.argtypes = [C.c_int32, C.POINTER(_vp)]
+    L.teaser_hip_icp_destroy.argtypes = [_vp]
+    L.teaser_hip_icp_last_error.argtypes = [_vp]
+    L.teaser_hip_icp_last_error.restype = C.c_char_p
+    L.teaser_hip_icp_batch.argtypes = [_vp, C.c_int32, C.POINTER(_dp), _ip, C.POINTER(_dp), _ip, _dp,
+                                       C.POINTER(IcpParamsC), C.POINTER(IcpResultC), C.POINTER(_ip)]
+    L.teaser_hip_icp_solve.argtypes = [_vp, _dp, C.c_int32, _dp, C.c_int32, _dp, C.POINTER(IcpParamsC),
+                                       C.POINTER(IcpResultC), _ip]
+
+
+class ICPConvergenceCriteria:
+    """Open3D's ICPConvergenceCriteria: the loop stops when BOTH the fitness and the inlier RMSE changed by less
+    than these ABSOLUTE amounts in one iteration, or after max_iteration iterations."""
+
+    def __init__(self, relative_fitness=1e-6, relative_rmse=1e-6, max_iteration=30):
+        self.relative_fitness = float(relative_fitness)
+        self.relative_rmse = float(relative_rmse)
+        self.max_iteration = int(max_iteration)
+
+    def __repr__(self):
+        return "ICPConvergenceCriteria(relative_fitness=%g, relative_rmse=%g, max_iteration=%d)" % (
+            self.relative_fitness, self.relative_rmse, self.max_iteration)
+
+
+class TransformationEstimationPointToPoint:
+    """Open3D's point-to-point estimation; only with_scaling=False exists here."""
+
+    def __init__(self, with_scaling=False):
+        if with_scaling:
+            raise ValueError("TransformationEstimationPointToPoint(with_scaling=True) is not supported")
+        self.with_scaling = False
+
+
+class RegistrationResult:
+    """Open3D's RegistrationResult (transformation, fitness, inlier_rmse, correspondence_set) + iterations."""
+
+    def __init__(self, transformation, fitness, inlier_rmse, correspondence_set, iterations):
+        self.transformation = transformation
+        self.fitness = fitness
+        self.inlier_rmse = inlier_rmse
+        self.correspondence_set = correspondence_set
+        self.iterations = iterations
+
+    def __repr__(self):
+        return "RegistrationResult(fitness=%.6g, inlier_rmse=%.6g, correspondences=%d, iterations=%d)" % (
+            self.fitness, self.inlier_rmse, len(self.correspondence_set), self.iterations)
+
+
+# One C handle per device, shared by every thread of the process.  A handle is not re-entrant (its stream, device
+# buffers and staging memory serve one call at a time) and ctypes releases the GIL during the call, so each handle
+# has a lock held around every call on it; calls for different devices run concurrently.
+_handles = {}            # device ordinal -> (handle, lock)
+_handles_lock = threading.Lock()
+
+
+def _current_device():
+    """The calling thread's current HIP device, asked of the HIP runtime this package's library is linked against
+    (already loaded: RTLD_NOLOAD never loads a second runtime).  -1 when it cannot be asked."""
+    for name in ("libamdhip64.so.7", "libamdhip64.so.6", "libamdhip64.so"):
+        try:
+            rt = C.CDLL(name, mode=os.RTLD_NOLOAD | os.RTLD_GLOBAL)
+        except OSError:
+            continue
+        d = C.c_int(-1)
+        return d.value if rt.hipGetDevice(C.byref(d)) == 0 else -1
+    return -1
+
+
+def _handle(device):
+    """(handle, lock) for `device`; device < 0 is resolved to the calling thread's current device first."""
+    from . import TeaserHipError, lib
+    device = int(device)
+    L = lib()
+    if device < 0:
+        device = _current_device()
+    with _handles_lock:
+        entry = _handles.get(device)
+        if entry is not None:
+            return entry
+        h = _vp()
+        rc = L.teaser_hip_icp_create(device, C.byref(h))
+        if rc != 0:
+            raise TeaserHipError(rc, "(no MI355X visible: the product has no CPU path)" if rc == 3 else "")
+        entry = (h, threading.Lock())
+        _handles[device] = entry
+        return entry
+
+
+@atexit.register
+def _release():
+    with _handles_lock:
+        if not _handles:
+            return
+        from . import lib
+        L = lib()
+        for h, lock in _handles.values():
+            with lock:
+                L.teaser_hip_icp_destroy(h)
+        _handles.clear()
+
+
+def _cloud(a, what):
+    a = np.ascontiguousarray(np.asarray(a, dtype=np.float64))
+    if a.size == 0:
+        return np.zeros((0, 3))
+    if a.ndim != 2 or a.shape[1] != 3:
+        raise ValueError("%s must be an n x 3 array of points, got shape %s" % (what, a.shape))
+    return a
+
+
+def _init(T):
+    T = np.ascontiguousarray(np.asarray(T, dtype=np.float64))
+    if T.shape != (4, 4):
+        raise ValueError("init must be 4 x 4, got shape %s" % (T.shape,))
+    return T
+
+
+def _params(r, criteria):
+    c = criteria if criteria is not None else ICPConvergenceCriteria()
+    return IcpParamsC(float(r), int(c.max_iteration), float(c.relative_fitness), float(c.relative_rmse))
+
+
+def registration_icp_batch(sources, targets, max_correspondence_distance, inits=None, criteria=None, device=-1):
+    """One launch sequence for many independent problems (mixed sizes allowed).  max_correspondence_distance and
+    criteria: one value for all or one per problem; inits: None (identity), one 4 x 4 for all, or one per problem.
+    Returns a list of RegistrationResult, each identical to the same problem run alone."""
+    from . import TeaserHipError, lib
+    srcs = [_cloud(s, "source") for s in sources]
+    dsts = [_cloud(t, "target") for t in targets]
+    b = len(srcs)
+    if len(dsts) != b:
+        raise ValueError("sources and targets differ in length (%d vs %d)" % (b, len(dsts)))
+    rs = np.broadcast_to(np.asarray(max_correspondence_distance, dtype=np.float64), (b,))
+    crit = criteria if isinstance(criteria, (list, tuple)) else [criteria] * b
+    if len(crit) != b:
+        raise ValueError("criteria: one per problem or one for all")
+    params = (IcpParamsC * max(b, 1))(*[_params(rs[k], crit[k]) for k in range(b)])
+    if inits is None:
+        init = None
+    else:
+        a = np.asarray(inits, dtype=np.float64)
+        init = np.ascontiguousarray(np.broadcast_to(a, (b, 4, 4)) if a.shape == (4, 4) else a)
+        if init.shape != (b, 4, 4):
+            raise ValueError("inits: one 4 x 4 for all problems or b x 4 x 4")
+    h, lock = _handle(device)
+    L = lib()
+    n_s = np.array([len(s) for s in srcs], dtype=np.int32)
+    n_t = np.array([len(t) for t in dsts], dtype=np.int32)
+    sp = (_dp * max(b, 1))(*[s.ctypes.data_as(_dp) for s in srcs])
+    tp = (_dp * max(b, 1))(*[t.ctypes.data_as(_dp) for t in dsts])
+    corr = [np.zeros((max(int(n), 1), 2), dtype=np.int32) for n in n_s]
+    cp = (_ip * max(b, 1))(*[c.ctypes.data_as(_ip) for c in corr])
+    out = (IcpResultC * max(b, 1))()
+    with lock:  # the handle serves one call at a time
+        rc = L.teaser_hip_icp_batch(h, b, sp, n_s.ctypes.data_as(_ip), tp, n_t.ctypes.data_as(_ip),
+                                    None if init is None else init.ctypes.data_as(_dp), params, out, cp)
+        err = L.teaser_hip_icp_last_error(h).decode() if rc != 0 else ""
+    if rc != 0:
+        raise TeaserHipError(rc, err)
+    res = []
+    for k in range(b):
+        o = out[k]
+        res.append(RegistrationResult(np.array(o.transformation[:], dtype=np.float64).reshape(4, 4),
+                                      float(o.fitness), float(o.inlier_rmse),
+                                      corr[k][:o.n_correspondences].copy(), int(o.iterations)))
+    return res
+
+
+def registration_icp(source, target, max_correspondence_distance, init=np.eye(4), estimation_method=None,
+                     criteria=None, device=-1):
+    """Open3D's registration_icp (same argument order) for TransformationEstimationPointToPoint(False): refines
+    `init` so that it maps source onto target.  source / target: n x 3 points (np.asarray(pcd.points))."""
+    if estimation_method is not None and not isinstance(estimation_method, TransformationEstimationPointToPoint):
+        raise ValueError("only TransformationEstimationPointToPoint(with_scaling=False) is supported")
+    return registration_icp_batch([source], [target], max_correspondence_distance, inits=_init(init)[None],
+                                  criteria=[criteria], device=device)[0]

@@ -1,0 +1,197 @@
+"""The ICP contract (include/teaser_hip.h, "ICP refinement") as restated in numpy (tests/icp_reference.py), and the
+Python surface of the GPU implementation that needs no device: names, Open3D's defaults, loud failure without a GPU."""
+import importlib
+import os
+
+import numpy as np
+import pytest
+
+import icp_reference as R
+from util import ROOT
+
+tp = importlib.import_module("teaser-plusplus_amd")
+
+
+def rot(axis, deg):
+    a = np.asarray(axis, dtype=np.float64)
+    a /= np.linalg.norm(a)
+    K = np.array([[0, -a[2], a[1]], [a[2], 0, -a[0]], [-a[1], a[0], 0]])
+    th = np.deg2rad(deg)
+    return np.eye(3) + np.sin(th) * K + (1 - np.cos(th)) * K @ K
+
+
+def test_noiseless_rigid_transform_is_recovered():
+    rng = np.random.default_rng(7)
+    P = rng.uniform(-1, 1, size=(400, 3))
+    T_true = np.eye(4)
+    T_true[:3, :3] = rot([1, 2, 3], 4.0)
+    T_true[:3, 3] = [0.03, -0.02, 0.01]
+    Q = R.apply(T_true, P)
+    o = R.registration_icp(P, Q, 0.5, np.eye(4), max_iteration=100)
+    assert np.linalg.norm(o["transformation"] - T_true) < 1e-12
+    assert o["fitness"] == 1.0
+    assert o["inlier_rmse"] < 1e-12
+    assert np.array_equal(o["correspondence_set"], np.stack([np.arange(400), np.arange(400)], 1))
+
+
+def test_ties_go_to_the_smaller_target_index():
+    P = np.array([[0.0, 0.0, 0.0]])
+    Q = np.array([[5.0, 5.0, 5.0], [0.0, 0.25, 0.0], [0.0, -0.25, 0.0], [0.25, 0.0, 0.0]])
+    j, d2, fit, rmse = R.corr(P, Q, 0.5)
+    assert j[0] == 1 and d2[0] == 0.0625 and fit == 1.0 and rmse == 0.25
+
+
+def test_a_target_at_exactly_r_is_not_a_match():
+    P = np.array([[0.0, 0.0, 0.0], [1.0, 0.0, 0.0]])
+    Q = np.array([[0.5, 0.0, 0.0]])  # exactly r = 0.5 from both sources on an axis
+    j, _, fit, rmse = R.corr(P, Q, 0.5)
+    assert (j == -1).all() and fit == 0.0 and rmse == 0.0
+    j, _, fit, _ = R.corr(P, Q, np.nextafter(0.5, 1.0))
+    assert (j == 0).all() and fit == 1.0
+
+
+def test_max_iteration_zero_returns_init_and_its_correspondences():
+    P, Q, r, init = R.config5_problem()
+    o = R.registration_icp(P, Q, r, init, max_iteration=0)
+    j, _, fit, rmse = R.corr(R.apply(init, P), Q, r)
+    assert o["iterations"] == 0 and np.array_equal(o["transformation"], init)
+    assert o["fitness"] == fit and o["inlier_rmse"] == rmse
+    assert np.array_equal(o["correspondence_set"][:, 1], j[j >= 0])
+
+
+def test_stop_rule_uses_absolute_differences():
+    """A fitness change of 1e-3 on a fitness near 0.5 is far above relative 1e-6 but below absolute 2e-3: with
+    relative_fitness = relative_rmse = 2e-3 the loop must stop at the first iteration whose changes are both
+    below 2e-3 in absolute terms, which is earlier than with the defaults."""
+    P, Q, r, init = R.config5_problem()
+    ref = R.registration_icp(P, Q, r, init, max_iteration=100)
+    loose = R.registration_icp(P, Q, r, init, max_iteration=100, relative_fitness=2e-3, relative_rmse=2e-3)
+    assert loose["iterations"] < ref["iterations"]
+    # replay the loop and check that the stop is exactly the first absolute-difference hit
+    T, X = init.copy(), R.apply(init, P)
+    j, _, fit, rmse = R.corr(X, Q, r)
+    for it in range(1, 101):
+        m = j >= 0
+        U = R.umeyama(X[m], Q[j[m]])
+        T, X = R.compose(U, T), R.apply(U, X)
+        pf, pr = fit, rmse
+        j, _, fit, rmse = R.corr(X, Q, r)
+        if abs(pf - fit) < 2e-3 and abs(pr - rmse) < 2e-3:
+            break
+    assert it == loose["iterations"] and np.array_equal(T, loose["transformation"])
+
+
+def test_empty_clouds_are_valid():
+    P, Q, r, init = R.config5_problem()
+    for src, dst in ((P[:0], Q), (P, Q[:0])):
+        o = R.registration_icp(src, dst, r, init)
+        assert o["fitness"] == 0.0 and o["inlier_rmse"] == 0.0 and len(o["correspondence_set"]) == 0
+
+
+def test_golden_file_regenerates():
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("mk", os.path.join(ROOT, "tests", "golden", "make_icp_golden.py"))
+    mk = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mk)
+    d = mk.compute()
+    g = np.load(os.path.join(ROOT, "tests", "golden", "icp_golden.npz"))
+    assert int(g["iterations"]) == int(d["iterations"]) == 19
+    assert np.array_equal(g["correspondence_set"], d["correspondence_set"])
+    assert np.linalg.norm(g["transformation"] - d["transformation"]) < 1e-12
+    for k in ("fitness", "inlier_rmse", "init_fitness", "init_rmse"):
+        assert abs(float(g[k]) - float(d[k])) <= 1e-12 * abs(float(d[k])), k
+    assert float(g["fitness"]) > float(g["init_fitness"])
+
+
+def test_public_names_with_open3d_defaults():
+    for name in ("ICPConvergenceCriteria", "TransformationEstimationPointToPoint", "RegistrationResult",
+                 "registration_icp", "registration_icp_batch"):
+        assert name in tp.__all__ and hasattr(tp, name), name
+    c = tp.ICPConvergenceCriteria()
+    assert (c.relative_fitness, c.relative_rmse, c.max_iteration) == (1e-6, 1e-6, 30)
+    assert tp.TransformationEstimationPointToPoint().with_scaling is False
+    with pytest.raises(ValueError):
+        tp.TransformationEstimationPointToPoint(with_scaling=True)
+    import inspect
+    names = list(inspect.signature(tp.registration_icp).parameters)
+    assert names[:6] == ["source", "target", "max_correspondence_distance", "init", "estimation_method", "criteria"]
+    p = tp.icp.IcpParamsC()
+    assert tp.lib().teaser_hip_icp_params_default(p) == 0
+    assert (p.max_iteration, p.relative_fitness, p.relative_rmse) == (30, 1e-6, 1e-6)
+
+
+def test_no_device_is_a_loud_error():
+    if tp.device_count() > 0:
+        return  # the GPU suite covers the device path
+    P, Q, r, init = R.config5_problem()
+    with pytest.raises(tp.TeaserHipError) as e:
+        tp.registration_icp(P, Q, r, init)
+    assert "NO_DEVICE" in str(e.value)
+    import ctypes as C
+    h = C.c_void_p()
+    assert tp.lib().teaser_hip_icp_create(0, C.byref(h)) == 3 and not h
+
+
+def test_cxx_icp_example_exits_77_without_device():
+    from icp_cxx import build_icp_example
+    import subprocess
+    exe = build_icp_example()
+    rc = subprocess.call([exe], stdout=subprocess.DEVNULL)
+    assert rc == (0 if tp.device_count() > 0 else 77)
+
+
+def test_calls_on_one_handle_are_serialised(monkeypatch):
+    """The Python layer shares one C handle per device among threads; a handle is not re-entrant, so calls on it must
+    run one at a time (ctypes releases the GIL), and concurrent first calls must create ONE handle.  Checked with a
+    stand-in library that records how many calls overlap; device=-1 resolves to the current device's handle."""
+    import threading
+    import time
+    rec = dict(active=0, peak=0, calls=0, creates=0)
+    guard = threading.Lock()
+
+    class FakeLib:
+        def teaser_hip_icp_create(self, device, out):
+            with guard:
+                rec["creates"] += 1
+            time.sleep(0.01)
+            out._obj.value = 4096 + device
+            return 0
+
+        def teaser_hip_icp_batch(self, h, b, *args):
+            with guard:
+                rec["active"] += 1
+                rec["peak"] = max(rec["peak"], rec["active"])
+            time.sleep(0.01)
+            with guard:
+                rec["active"] -= 1
+                rec["calls"] += 1
+            return 0
+
+        def teaser_hip_icp_last_error(self, h):
+            return b""
+
+        def teaser_hip_icp_destroy(self, h):
+            return 0
+
+    fake = FakeLib()
+    monkeypatch.setattr(tp, "lib", lambda: fake)
+    monkeypatch.setattr(tp.icp, "_handles", {})
+    monkeypatch.setattr(tp.icp, "_current_device", lambda: 0)
+    P = np.zeros((4, 3))
+    errors = []
+
+    def worker(dev):
+        try:
+            for _ in range(3):
+                tp.registration_icp(P, P, 0.1, device=dev)
+        except Exception as e:  # pragma: no cover - reported below
+            errors.append(e)
+
+    threads = [threading.Thread(target=worker, args=(-1 if k % 2 else 0,)) for k in range(8)]
+    for t in threads:
+        t.start()
+    for t in threads:
+        t.join()
+    assert not errors, errors
+    assert rec["calls"] == 24 and rec["peak"] == 1 and rec["creates"] == 1
+    assert list(tp.icp._handles) == [0]
