@@ -22,6 +22,18 @@
  *
  * Errors: every call returns a teaser_hip_status; solve never throws.  A valid==0 solution with
  * status OK is the reference's soft failure (clique size <= 1, registration.cc:643-647).
+ *
+ * Problem-size limits.  The routes follow the largest problem of a
+ * batch (max_n): above 65536 correspondences the inlier graph is built by the all-FP64 K1 kernel
+ * and a separate degree pass instead of the matrix-core filter, the degree closure is off, and the
+ * colouring bound uses the vertex-centric rounds only; every problem of such a batch takes these
+ * routes, with the same results.  Refused with TEASER_HIP_ERR_UNSUPPORTED (the handle stays usable):
+ *   - inlier_selection_mode = KCORE_HEU when max_n > 65536 (solve and teaser_hip_max_clique;
+ *     before any work);
+ *   - estimate_scaling when n > 46341 (the reference's own `int` limit, registration.cc:47);
+ *   - rotation_tim_graph = COMPLETE when sum over the batch of n(n-1)/2 + 2 > 2^31 (before any
+ *     work).  This is stricter than the reference, which builds COMPLETE TIMs over the maximum
+ *     clique only (registration.cc:690-693); here they are sized for all n points.
  */
 #ifndef TEASER_HIP_H_
 #define TEASER_HIP_H_
@@ -379,6 +391,9 @@ TEASER_HIP_API int32_t teaser_hip_set_profiling(teaser_hip_solver* h, int32_t le
  * process; the library never calls getenv on a solve path and never modifies the environment.
  * Returns BAD_ARG for an unknown name. */
 TEASER_HIP_API int32_t teaser_hip_set_option(teaser_hip_solver* h, const char* name, int64_t value);
+/* The current value of a teaser_hip_set_option name (its default, the environment's value, or the last value set),
+ * so a caller can restore it.  Returns BAD_ARG for an unknown name or a NULL pointer. */
+TEASER_HIP_API int32_t teaser_hip_get_option(const char* name, int64_t* value);
 TEASER_HIP_API int32_t teaser_hip_get_profile(const teaser_hip_solver* h, teaser_profile_c* out);
 /* The HIP stream (hipStream_t) all kernels of this handle are launched on. */
 TEASER_HIP_API void* teaser_hip_get_stream(teaser_hip_solver* h);

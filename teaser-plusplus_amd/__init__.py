@@ -119,7 +119,7 @@ EXPORTED_SYMBOLS = [
     "teaser_hip_get_translation_inliers", "teaser_hip_get_input_ordered_translation_inliers",
     "teaser_hip_get_inlier_graph_bitmap", "teaser_hip_get_degrees", "teaser_hip_solve_for_rotation",
     "teaser_hip_solve_for_translation", "teaser_hip_scalar_tls", "teaser_hip_max_clique",
-    "teaser_hip_set_profiling", "teaser_hip_set_option", "teaser_hip_get_profile", "teaser_hip_get_stream",
+    "teaser_hip_set_profiling", "teaser_hip_set_option", "teaser_hip_get_option", "teaser_hip_get_profile", "teaser_hip_get_stream",
     "teaser_hip_last_error", "teaser_hip_abi_version", "teaser_hip_device_count", "teaser_hip_host_alloc",
     "teaser_hip_host_free",
     "teaser_hip_synth_problem", "teaser_hip_submit_batch", "teaser_hip_wait",
@@ -203,6 +203,7 @@ def lib():
     L.teaser_hip_multi_device_count.argtypes = [_vp]
     L.teaser_hip_set_profiling.argtypes = [_vp, C.c_int32]
     L.teaser_hip_set_option.argtypes = [_vp, C.c_char_p, C.c_int64]
+    L.teaser_hip_get_option.argtypes = [C.c_char_p, C.POINTER(C.c_int64)]
     L.teaser_hip_get_profile.argtypes = [_vp, C.POINTER(ProfileC)]
     L.teaser_hip_get_stream.argtypes = [_vp]
     L.teaser_hip_get_stream.restype = _vp
@@ -222,6 +223,15 @@ def set_option(name, value):
     rc = lib().teaser_hip_set_option(None, name.encode(), int(value))
     if rc != 0:
         raise TeaserHipError(rc, "unknown option %r" % name)
+
+
+def get_option(name):
+    """teaser_hip_get_option: the current value of a set_option name (to restore it afterwards)."""
+    v = C.c_int64()
+    rc = lib().teaser_hip_get_option(name.encode(), C.byref(v))
+    if rc != 0:
+        raise TeaserHipError(rc, "unknown option %r" % name)
+    return v.value
 
 
 # teaserpp_python.OMP_MAX_THREADS (python/teaserpp_python/teaserpp_python.cc:45): host threads

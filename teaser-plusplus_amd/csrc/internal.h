@@ -146,6 +146,7 @@ enum Setting {
 };
 int64_t setting(Setting id);
 bool set_setting(const char* name, int64_t value);  // name as in teaser_hip_set_option; false: unknown name
+bool get_setting(const char* name, int64_t* value);  // false: unknown name
 
 // ---- kernel launchers (implemented in the .hip files) -------------------------------------
 // K1: fused TIM norms + scale pruning + symmetric adjacency bitmap (kernels_graph.hip)

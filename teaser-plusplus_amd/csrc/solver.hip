@@ -124,6 +124,15 @@ bool set_setting(const char* name, int64_t value) {
     }
   return false;
 }
+bool get_setting(const char* name, int64_t* value) {
+  if (!name || !value) return false;
+  for (int i = 0; i < S_COUNT; ++i)
+    if (strcmp(name, kSettingRows[i].name) == 0) {
+      *value = setting_table().v[i].load(std::memory_order_relaxed);
+      return true;
+    }
+  return false;
+}
 }  // namespace thip
 
 using namespace thip;
@@ -1176,6 +1185,10 @@ int32_t solve_packed_enqueue(teaser_hip_solver* h, const double* d_src, const do
     h->err = "rotation_tim_graph = COMPLETE needs too many TIMs for this batch";
     return TEASER_HIP_ERR_UNSUPPORTED;
   }
+  if (mode == TEASER_INLIER_KCORE_HEU && max_n > 65536) {  // (refused before anything is enqueued)
+    h->err = "inlier_selection_mode = KCORE_HEU supports at most 65536 correspondences per problem";
+    return TEASER_HIP_ERR_UNSUPPORTED;
+  }
   h->max_n = max_n;
   h->max_W = (max_n + 63) / 64;
   h->total_n = maxpt;
@@ -1327,11 +1340,7 @@ int32_t solve_packed_enqueue(teaser_hip_solver* h, const double* d_src, const do
       int32_t rc = enqueue_heuristic_stage(h, batch, mode, mfma_k1);
       if (rc != TEASER_HIP_OK) return rc;
     }
-    if (mode == TEASER_INLIER_KCORE_HEU) {  // graph.cc:58-81
-      if (max_n > 65536) {
-        h->err = "inlier_selection_mode = KCORE_HEU supports at most 65536 correspondences per problem";
-        return TEASER_HIP_ERR_UNSUPPORTED;
-      }
+    if (mode == TEASER_INLIER_KCORE_HEU) {  // graph.cc:58-81 (max_n <= 65536: checked above)
       StageScope sc(h, ST_PEEL);
       HIPCHK(h, h->c_colour.ensure(4 * (size_t)total_n));
       HIPCHK(h, h->c_tent.ensure(4 * (size_t)total_n));
@@ -2436,6 +2445,10 @@ int32_t teaser_hip_max_clique(teaser_hip_solver* h, const uint64_t* bitmap, int3
   hipStream_t s = h->stream;
   const int W = (n + 63) / 64;
   const int mode = effective_mode(h->params);
+  if (mode == TEASER_INLIER_KCORE_HEU && n > 65536) {  // graph.cc:58-81 (refused before anything is enqueued)
+    h->err = "KCORE_HEU supports at most 65536 vertices";
+    return TEASER_HIP_ERR_UNSUPPORTED;
+  }
   // a one-problem "batch" whose graph is the caller's bitmap
   h->batch = 0;  // getters of a previous solve are invalidated
   h->descs.assign(1, ProbDesc());
@@ -2484,11 +2497,7 @@ int32_t teaser_hip_max_clique(teaser_hip_solver* h, const uint64_t* bitmap, int3
   }
   launch_select_best(s, dd, 1, W, h->d_deg.as<int32_t>(), ds, h->d_start_cliques.as<int32_t>(), n,
                      h->d_clique.as<int32_t>(), h->d_alive_a.as<uint64_t>(), exact ? 1 : 0, h->d_small.p, small_G);
-  if (mode == TEASER_INLIER_KCORE_HEU) {  // graph.cc:58-81
-    if (n > 65536) {
-      h->err = "KCORE_HEU supports at most 65536 vertices";
-      return TEASER_HIP_ERR_UNSUPPORTED;
-    }
+  if (mode == TEASER_INLIER_KCORE_HEU) {  // graph.cc:58-81 (n <= 65536: checked above)
     HIPCHK(h, h->c_colour.ensure(4 * (size_t)n));
     HIPCHK(h, h->c_tent.ensure(4 * (size_t)n));
     launch_kcore_heuristic(s, dd, 1, h->d_bitmap.as<uint64_t>(), h->d_deg.as<int32_t>(), ds,
@@ -2832,6 +2841,10 @@ int32_t teaser_hip_set_profiling(teaser_hip_solver* h, int32_t level) {
 
 int32_t teaser_hip_set_option(teaser_hip_solver*, const char* name, int64_t value) {
   return set_setting(name, value) ? TEASER_HIP_OK : TEASER_HIP_ERR_BAD_ARG;
+}
+
+int32_t teaser_hip_get_option(const char* name, int64_t* value) {
+  return get_setting(name, value) ? TEASER_HIP_OK : TEASER_HIP_ERR_BAD_ARG;
 }
 
 int32_t teaser_hip_get_profile(const teaser_hip_solver* h, teaser_profile_c* out) {

@@ -193,3 +193,21 @@ def test_every_documented_option_exists_with_its_default():
             seen.add(name)
     assert len(seen) >= 30 and {"colour_mis", "colour_mis_any", "colour_persistent", "deg_closure", "scale_hull"} <= seen, sorted(seen)
     assert L.teaser_hip_set_option(None, b"colour_mis", 65537) != 0 and L.teaser_hip_set_option(None, b"colour_mis_any", 2) != 0
+
+
+def test_get_option_reads_back_what_set_option_stored():
+    """teaser_hip_get_option (no device needed): the value set_option stored, BAD_ARG for an unknown name, and the
+    previous value restored."""
+    before = tp.get_option("colour_mis")
+    try:
+        tp.set_option("colour_mis", 4096)
+        assert tp.get_option("colour_mis") == 4096
+        tp.set_option("colour_mis", 0)
+        assert tp.get_option("colour_mis") == 0
+    finally:
+        tp.set_option("colour_mis", before)
+    assert tp.get_option("colour_mis") == before
+    with pytest.raises(tp.TeaserHipError):
+        tp.get_option("no_such_option")
+    v = C.c_int64(7)
+    assert tp.lib().teaser_hip_get_option(b"no_such_option", C.byref(v)) != 0 and v.value == 7

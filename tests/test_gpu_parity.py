@@ -11,15 +11,13 @@ import numpy as np
 import pytest
 
 from oracle import oracle
-from util import angular_error, golden, is_clique
+from util import (R_TOL, T_TOL, angular_error, check_against_fixture, config_golden, golden, is_clique,
+                  numpy_rows_predicate)
 
 pytestmark = pytest.mark.gpu
 
 tp = importlib.import_module("teaser-plusplus_amd")
 G = golden()
-
-R_TOL = 1e-4  # Frobenius, north_star
-T_TOL = 1e-4  # metres, north_star
 
 
 def make_solver(**kw):
@@ -895,20 +893,6 @@ def test_solve_parity_config2_10k():
     assert s.raw_solution().num_edges == o["num_edges"]
 
 
-def numpy_rows_predicate(src, dst, rows, beta):
-    """Rows of the adjacency matrix with the reference expression (registration.cc:434-442) in numpy:
-    individually rounded IEEE double products / sums / sqrt, sum order (x^2 + y^2) + z^2."""
-    out = np.zeros((len(rows), src.shape[1]), dtype=bool)
-    for k, i in enumerate(rows):
-        a = src - src[:, [i]]
-        b = dst - dst[:, [i]]
-        v1 = np.sqrt((a[0] * a[0] + a[1] * a[1]) + a[2] * a[2])
-        v2 = np.sqrt((b[0] * b[0] + b[1] * b[1]) + b[2] * b[2])
-        out[k] = np.abs(v1 - v2) <= beta
-        out[k, i] = False
-    return out
-
-
 def test_solve_config3_50k_properties():
     """BASELINE config 3: N = 50 000, 99 % outliers (1.25e9 pairs, 313 MB bitmap).  The oracle needs
     minutes here, so size-independent properties: sampled bitmap rows bit-exact against the reference
@@ -941,28 +925,6 @@ def test_solve_config3_50k_properties():
     assert (sub | np.eye(len(clique), dtype=bool)).all()
     assert angular_error(pr["R"], sol.rotation) < 0.01
     assert np.linalg.norm(sol.translation - pr["t"]) < 0.01
-
-
-def config_golden():
-    import json
-    import os
-    from util import ROOT
-    return json.load(open(os.path.join(ROOT, "tests", "golden", "config_golden.json")))
-
-
-def check_against_fixture(s, sol, fx, problem=0):
-    """Identity with the committed ORACLE result (tests/golden/make_config_golden.py): clique, rotation /
-    translation inlier lists, edge count, R and t to the north_star tolerances."""
-    assert bool(sol.valid) == fx["valid"]
-    assert s.raw_solution(problem).num_edges == fx["num_edges"]
-    clique = s.getInlierMaxClique(problem)
-    assert len(clique) == len(fx["max_clique"])
-    if fx["clique_unique"]:
-        assert clique == fx["max_clique"]
-        assert s.getRotationInliers(problem) == fx["rotation_inliers"]
-        assert s.getTranslationInliers(problem) == fx["translation_inliers"]
-        assert np.linalg.norm(np.asarray(sol.rotation).reshape(3, 3) - np.array(fx["rotation"]).reshape(3, 3)) <= R_TOL
-        assert np.linalg.norm(np.asarray(sol.translation) - np.array(fx["translation"])) <= T_TOL
 
 
 @pytest.mark.parametrize("case", ["config3", "config3_seed2"])

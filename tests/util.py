@@ -17,6 +17,80 @@ def angular_error(R_exp, R_est):
     return abs(np.arccos(min(max(c, -1.0), 1.0)))
 
 
+def numpy_rows_predicate(src, dst, rows, beta):
+    """Rows of the adjacency matrix with the reference expression (registration.cc:434-442) in numpy:
+    individually rounded IEEE double products / sums / sqrt, sum order (x^2 + y^2) + z^2."""
+    out = np.zeros((len(rows), src.shape[1]), dtype=bool)
+    for k, i in enumerate(rows):
+        a = src - src[:, [i]]
+        b = dst - dst[:, [i]]
+        v1 = np.sqrt((a[0] * a[0] + a[1] * a[1]) + a[2] * a[2])
+        v2 = np.sqrt((b[0] * b[0] + b[1] * b[1]) + b[2] * b[2])
+        out[k] = np.abs(v1 - v2) <= beta
+        out[k, i] = False
+    return out
+
+
+R_TOL = 1e-4  # Frobenius, north_star
+T_TOL = 1e-4  # metres, north_star
+
+
+def config_golden():
+    import json
+    return json.load(open(os.path.join(ROOT, "tests", "golden", "config_golden.json")))
+
+
+def check_against_fixture(s, sol, fx, problem=0):
+    """Identity with the committed ORACLE result (tests/golden/make_config_golden.py): clique, rotation /
+    translation inlier lists, edge count, R and t to the north_star tolerances."""
+    assert bool(sol.valid) == fx["valid"]
+    assert s.raw_solution(problem).num_edges == fx["num_edges"]
+    clique = s.getInlierMaxClique(problem)
+    assert len(clique) == len(fx["max_clique"])
+    if fx["clique_unique"]:
+        assert clique == fx["max_clique"]
+        assert s.getRotationInliers(problem) == fx["rotation_inliers"]
+        assert s.getTranslationInliers(problem) == fx["translation_inliers"]
+        assert np.linalg.norm(np.asarray(sol.rotation).reshape(3, 3) - np.array(fx["rotation"]).reshape(3, 3)) <= R_TOL
+        assert np.linalg.norm(np.asarray(sol.translation) - np.array(fx["translation"])) <= T_TOL
+
+
+# indices the long-N fixtures pin inside the planted inlier set: the first and the last 16-bit index, the first index
+# above them, and n - 1
+LONG_N_PINNED = (0, 65535, 65536)
+
+
+def long_n_permutation(inliers):
+    """The fixed column permutation of synth_problem's output used by the long-N fixtures
+    (tests/golden/make_config_golden.py, tests/test_gpu_long_n.py): for each index t in LONG_N_PINNED + (n - 1),
+    taken in increasing order, that is not an inlier, swap t with the lowest inlier that is not itself such an
+    index.  Correspondences 0 and n - 1 -- and 65 535 / 65 536 where n exceeds them -- then belong to the planted
+    inlier set.  Returns perm: the permuted problem's column j is the original column perm[j]."""
+    inliers = np.asarray(inliers, dtype=bool)
+    n = len(inliers)
+    perm = np.arange(n)
+    targets = sorted({t for t in LONG_N_PINNED + (n - 1,) if 0 <= t < n})
+    free = [int(i) for i in np.flatnonzero(inliers) if int(i) not in targets]
+    k = 0
+    for t in targets:
+        if not inliers[t]:
+            perm[t], perm[free[k]] = free[k], t
+            k += 1
+    return perm
+
+
+def long_n_problem(tp, seed, n, outlier_ratio, noise_bound):
+    """synth_problem(seed, n, outlier_ratio, noise_bound) with its columns permuted by long_n_permutation."""
+    pr = tp.synth_problem(seed, n, outlier_ratio, noise_bound)
+    perm = long_n_permutation(pr["inliers"])
+    out = dict(pr)
+    out["src"] = np.ascontiguousarray(pr["src"][:, perm])
+    out["dst"] = np.ascontiguousarray(pr["dst"][:, perm])
+    out["inliers"] = np.asarray(pr["inliers"])[perm]
+    out["perm"] = perm
+    return out
+
+
 def is_clique(dense_adj, members):
     m = np.asarray(members)
     sub = dense_adj[np.ix_(m, m)]
