@@ -381,15 +381,22 @@ TEASER_HIP_API int32_t teaser_hip_max_clique(teaser_hip_solver* h, const uint64_
 /* Profiling / diagnostics. */
 TEASER_HIP_API int32_t teaser_hip_set_profiling(teaser_hip_solver* h, int32_t level /* 0, 1, 2 */);
 /* Route switches among EQUIVALENT paths and tuning knobs of the implementation (no counterpart in the reference;
- * process-wide, `h` may be NULL).  No value changes a result: the GPU suite compares the routes with each other
- * and with the oracle.  Names (defaults): "k1_fp64" (0; 1 = the all-FP64 K1 instead of the matrix-core filter),
+ * process-wide, `h` may be NULL).  No value of a route option changes a result: the GPU suite compares the routes
+ * with each other and with the oracle (tests/test_gpu_route_switches.py).  Names (defaults; ranges and meanings in
+ * INTEGRATION.md's settings table): "k1_fp64" (0; 1 = the all-FP64 K1 instead of the matrix-core filter),
  * "fused_estimators" (1), "scale_sort64" (0), "scale_batch" (1), "scale_mid_batch" (1), "spec_bounds" (1),
  * "finisher" (1), "copy_stream" (0), "h2d_kernel" (0), "depth" (2; lanes of handles created afterwards), "stagger"
  * (1), "k1_stream" (0), "tail_cus" (0), "tail_cu_block" (0), "k4_lds_stack" (16384), "k4_donate" (1),
- * "k4_donate_after" / "k4_hungry" / "k4_expand" (-1 = built-in), "k4_debug" (0), "heu_blocks" (0 = built-in),
- * "greedy_threads" (0 = built-in), "fixup_wgs" (0 = built-in), "k4_waves" (0 = built-in: 4096).  Each also has an environment variable that is read ONCE per
- * process; the library never calls getenv on a solve path and never modifies the environment.
- * Returns BAD_ARG for an unknown name. */
+ * "k4_donate_after" / "k4_hungry" / "k4_expand" (-1 = built-in), "heu_blocks" (0 = built-in), "greedy_threads"
+ * (0 = built-in), "fixup_wgs" (0 = built-in), "k4_waves" (0 = built-in: 4096), "deg_closure" (1), "greedy_small"
+ * (1), "deg_closure_wgs" (0 = built-in), "scale_hull" (60), "scale_hull_sync" (1), "colour_persistent" (0),
+ * "heu_skip_closed" (0), "colour_mis" (8192), "colour_mis_any" (0).
+ * DIAGNOSTIC options, which may change results: "k4_debug" (0; stderr diagnostics), "k4_lb_bonus" (0; the exact
+ * search starts above the incumbent), "tail_skip" (0; timing probes: stages left out, results wrong by design),
+ * "reference_snapshot_semantics" (0; handles created or reset afterwards behave like the reference snapshot's
+ * binary).  Each option also has an environment variable that is read ONCE per process; the
+ * library never calls getenv on a solve path and never modifies the environment.
+ * Returns BAD_ARG for an unknown name or a value outside the option's range. */
 TEASER_HIP_API int32_t teaser_hip_set_option(teaser_hip_solver* h, const char* name, int64_t value);
 /* The current value of a teaser_hip_set_option name (its default, the environment's value, or the last value set),
  * so a caller can restore it.  Returns BAD_ARG for an unknown name or a NULL pointer. */

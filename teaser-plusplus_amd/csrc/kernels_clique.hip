@@ -902,9 +902,6 @@ void launch_exact_clique(hipStream_t s, ExactProb* d_probs, int nprob, int total
     if (room < qs.dcap) qs.dcap = room >= 1024 ? (int32_t)room : 0;
   }
   int64_t donate_bytes = (int64_t)qs.dcap * (qs.dslot_bytes + 4);
-  if (setting(S_K4_DEBUG))
-    fprintf(stderr, "[teaser_hip] exact search: donation queue %s (%d slots of %d B, max_W2 %d, pool %.1f MB)\n",
-            qs.dcap > 0 ? "active" : "OFF", (int)qs.dcap, (int)qs.dslot_bytes, max_W2, task_pool_bytes / 1048576.0);
   task_pool_bytes -= donate_bytes;
   qs.dpool = d_task_pool + task_pool_bytes;
   qs.dready = reinterpret_cast<int32_t*>(qs.dpool + (int64_t)qs.dcap * qs.dslot_bytes);
@@ -928,6 +925,12 @@ void launch_exact_clique(hipStream_t s, ExactProb* d_probs, int nprob, int total
     const int v = setting(S_K4_EXPAND) >= 0 ? (int)setting(S_K4_EXPAND) : kExactExpandPasses;
     return v > kTaskPrefix - 1 ? kTaskPrefix - 1 : v;
   }();
+  if (setting(S_K4_DEBUG))
+    fprintf(stderr,
+            "[teaser_hip] exact search: donation queue %s (%d slots of %d B, max_W2 %d, pool %.1f MB), LDS stack %d B, "
+            "%d expansion passes, %d waves\n",
+            qs.dcap > 0 ? "active" : "OFF", (int)qs.dcap, (int)qs.dslot_bytes, max_W2,
+            (task_pool_bytes + donate_bytes) / 1048576.0, lds_stack_bytes, passes, arena_waves);
   (void)hipMemsetAsync(d_counters, 0, (size_t)kExactCounterInts * sizeof(int32_t), s);
   if (qs.dcap > 0) (void)hipMemsetAsync(qs.dready, 0, (size_t)qs.dcap * sizeof(int32_t), s);
   const int w1 = std::min(total_waves, arena_waves);

@@ -719,6 +719,12 @@ int32_t scale_stage_batch(teaser_hip_solver* h, int batch, bool sort64) {
     mat += cnt;
     if (mid.size() - mat >= 1) HIPCHK(h, hipStreamSynchronize(s));  // (the next chunk reuses the scratch)
   }
+  if (setting(S_K4_DEBUG)) {  // diagnostics only: which route each problem of the batch took
+    int alone = 0;
+    for (int b = 0; b < batch; ++b) alone += done[(size_t)b] ? 0 : 1;
+    fprintf(stderr, "[teaser_hip] scale stage: %d batched, %d one at a time (scale_batch %d, scale_mid_batch %d)\n",
+            batch - alone, alone, (int)scale_batch, (int)mid_on);
+  }
   for (int b = 0; b < batch; ++b) {
     if (done[(size_t)b]) continue;
     const int32_t rc = scale_stage(h, b, sort64);
@@ -1618,6 +1624,11 @@ int32_t make_lane(teaser_hip_solver* h, teaser_hip_solver** out) {
     return TEASER_HIP_ERR_HIP;
   }
   lane->k1_stream = h->k1_stream;  // borrowed
+  if (setting(S_K4_DEBUG))  // diagnostics only
+    fprintf(stderr, "[teaser_hip] lane: depth %d, stagger %d (point %d), K1 stream %s%s, tail CUs %d (%s)\n", h->depth,
+            (int)h->stagger_k1, h->stagger_point, !h->k1_stream ? "none" : !mask_k1.empty() ? "CU mask" : "shared",
+            h->k1_kernel_only ? " (kernel only)" : "", mask_tail.empty() ? 0 : h->tail_cus,
+            h->tail_cu_block ? "block" : "spread");
   *out = lane;
   return TEASER_HIP_OK;
 }
@@ -1707,6 +1718,8 @@ int32_t ensure_input_sets(teaser_hip_solver* h) {
       (void)hipDeviceGetStreamPriorityRange(&lo, &hi);
       HIPCHK(h, hipStreamCreateWithPriority(&h->copy_stream, hipStreamNonBlocking, hi));
     }
+    if (setting(S_K4_DEBUG))  // diagnostics only
+      fprintf(stderr, "[teaser_hip] copy stream: %s\n", mode == 0 ? "parent" : mode == 1 ? "own" : "own, high priority");
   }
   while ((int)h->in_sets.size() < h->depth + 1) {
     h->in_sets.emplace_back();
@@ -1942,6 +1955,7 @@ int32_t submit_impl(teaser_hip_solver* h, const double* src, const double* dst,
         return a.type == hipMemoryTypeHost && a.devicePointer != nullptr;
       };
       const bool by_kernel = h2d_env != 1 && ((size_t)tot * 24) % 16 == 0 && device_readable(src) && device_readable(dst);
+      if (setting(S_K4_DEBUG)) fprintf(stderr, "[teaser_hip] host inputs: %s\n", by_kernel ? "kernel" : "copies");  // diagnostics
       if (by_kernel) {
         hipLaunchKernelGGL(host_inputs_kernel, dim3(64), dim3(256), 0, h->copy_stream, reinterpret_cast<const uint4*>(src),
                            reinterpret_cast<const uint4*>(dst), is.src.as<uint4>(), is.dst.as<uint4>(),
@@ -2451,6 +2465,7 @@ int32_t teaser_hip_max_clique(teaser_hip_solver* h, const uint64_t* bitmap, int3
   }
   // a one-problem "batch" whose graph is the caller's bitmap
   h->batch = 0;  // getters of a previous solve are invalidated
+  h->pend.spec_bounds = false;  // (a previous solve's speculative bound results are not this graph's)
   h->descs.assign(1, ProbDesc());
   h->states.assign(1, ProbState());
   h->exact_run.assign(1, 0);

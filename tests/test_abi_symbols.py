@@ -211,3 +211,95 @@ def test_get_option_reads_back_what_set_option_stored():
         tp.get_option("no_such_option")
     v = C.c_int64(7)
     assert tp.lib().teaser_hip_get_option(b"no_such_option", C.byref(v)) != 0 and v.value == 7
+
+
+def _integration_option_names():
+    text = open(os.path.join(ROOT, "INTEGRATION.md")).read()
+    table = text[text.index("| option | env | default | meaning |"):]
+    table = table[:table.index("\n\n")]
+    names = []
+    for line in table.splitlines()[2:]:
+        names += re.findall(r"`([a-z0-9_]+)`", line.strip().strip("|").split("|")[0])
+    return names
+
+
+def _header_option_comment():
+    text = open(os.path.join(ROOT, "include", "teaser_hip.h")).read()
+    end = text.index("TEASER_HIP_API int32_t teaser_hip_set_option(")
+    return text[text.rindex("/*", 0, end):end]
+
+
+def route_matrix_problems(rows, routes, combos, already, diagnostic, integration, header, test_sources):
+    """Every way in which the route matrix (tests/route_matrix.py) fails to cover the settings table: a list of
+    messages, empty when complete."""
+    bad = []
+    names = set(rows)
+    if set(integration) != names or len(integration) != len(set(integration)):
+        bad.append("INTEGRATION.md table %s != kSettingRows %s" % (sorted(set(integration) ^ names), sorted(names)))
+    parts = (set(routes), set(already), set(diagnostic))
+    for a, b in ((0, 1), (0, 2), (1, 2)):
+        if parts[a] & parts[b]:
+            bad.append("classified twice: %s" % sorted(parts[a] & parts[b]))
+    union = parts[0] | parts[1] | parts[2]
+    if union != names:
+        bad.append("not classified: %s; not an option: %s" % (sorted(names - union), sorted(union - names)))
+    for name, values in routes.items():
+        if name not in rows:
+            continue
+        lo, hi = rows[name][2], rows[name][3]
+        if not values or any(not lo <= v <= hi for v in values):
+            bad.append("%s: values %s outside [%d, %d]" % (name, values, lo, hi))
+        if lo not in values or hi not in values:
+            bad.append("%s: values %s miss lo %d or hi %d" % (name, values, lo, hi))
+    for combo, opts in combos.items():
+        for name, v in opts.items():
+            if name not in rows or not rows[name][2] <= v <= rows[name][3]:
+                bad.append("combo %s: %s = %s" % (combo, name, v))
+    for name, test in already.items():
+        module, func = test.split("::")
+        if not re.search(r"^def %s\(" % re.escape(func), test_sources.get(module, ""), flags=re.M):
+            bad.append("%s: no test %s" % (name, test))
+    for name in names:
+        if '"%s"' % name not in header:
+            bad.append("teaser_hip.h's set_option comment omits %s" % name)
+    for name in diagnostic:
+        if name in header and '"%s"' % name not in header[header.index("DIAGNOSTIC"):]:
+            bad.append("teaser_hip.h does not mark %s diagnostic" % name)
+    return bad
+
+
+def _route_matrix_inputs():
+    import route_matrix as rm
+    sources = {}
+    for test in rm.ALREADY_TESTED.values():
+        module = test.split("::")[0]
+        sources[module] = open(os.path.join(ROOT, "tests", module + ".py")).read()
+    return dict(rows=rm.setting_rows(), routes=rm.ROUTES, combos=rm.COMBOS, already=rm.ALREADY_TESTED,
+                diagnostic=rm.DIAGNOSTIC, integration=_integration_option_names(), header=_header_option_comment(),
+                test_sources=sources)
+
+
+def test_every_option_is_route_tested_or_diagnostic():
+    """The settings table of csrc/solver.hip, INTEGRATION.md's table, teaser_hip.h's set_option comment and the route
+    matrix (tests/route_matrix.py) name the same options; every option is route-tested (ROUTES, or a test named in
+    ALREADY_TESTED that exists) or classified DIAGNOSTIC, exactly once; every value under test is in range and the
+    ranges' ends are tested.  An option added without a route test fails here."""
+    inp = _route_matrix_inputs()
+    assert len(inp["rows"]) == 36
+    assert route_matrix_problems(**inp) == []
+
+
+def test_route_matrix_guard_catches_gaps(tmp_path):
+    """The guard above fails for a row added to a copy of the settings table and for an entry dropped from ROUTES."""
+    import route_matrix as rm
+    inp = _route_matrix_inputs()
+    src = open(rm.SOLVER_HIP).read()
+    fake = tmp_path / "solver.hip"
+    fake.write_text(src.replace('{"k1_fp64", ', '{"fake_route", "TEASER_FAKE_ROUTE", 0, 0, 1},\n    {"k1_fp64", ', 1))
+    assert "fake_route" in route_matrix_problems(**dict(inp, rows=rm.setting_rows(str(fake))))[0]
+    routes = dict(rm.ROUTES)
+    del routes["k4_hungry"]
+    assert any("k4_hungry" in m for m in route_matrix_problems(**dict(inp, routes=routes)))
+    routes = dict(rm.ROUTES, depth=[1, 17])
+    assert any(m.startswith("depth:") for m in route_matrix_problems(**dict(inp, routes=routes)))
+    assert any("no test" in m for m in route_matrix_problems(**dict(inp, already=dict(rm.ALREADY_TESTED, k1_fp64="test_gpu_parity::test_gone"))))
