@@ -465,6 +465,43 @@ TEASER_HIP_API int32_t teaser_hip_icp_solve(teaser_hip_icp* icp, const double* s
                                             const teaser_icp_params_c* params, teaser_icp_result_c* out,
                                             int32_t* corr);
 
+/* Voxel down-sampling (the reference's 3DMatch tutorial, examples/teaser_python_fpfh_icp/example.py:19-20, runs
+ * Open3D's pcd.voxel_down_sample(0.05) on the raw clouds): batched, with Open3D's arithmetic and a deterministic output
+ * order, on its OWN handle (nothing is shared with teaser_hip_solver or teaser_hip_icp).
+ * Per problem: n points p (xyz interleaved doubles, the layout ICP takes) and a voxel size v.  In FP64 per axis a:
+ *   lo_a = min_bound_a - 0.5 v,  hi_a = max_bound_a + 0.5 v      (min / max_bound: componentwise min / max of the points)
+ *   i_a  = floor((p_a - lo_a) / v)                                  (an IEEE division: no reciprocal, nothing fused)
+ * Every occupied voxel gives one output point: the FP64 sum of its points, added one at a time in input order
+ * starting from 0 (Open3D's AccumulatedPoint), divided by the voxel's count.
+ * Output order: ascending lexicographic (i_x, i_y, i_z).  This is the one deliberate difference from Open3D, which
+ * emits its hash map's (unspecified) order.  Normals and colours are not handled (the tutorial never reads them after
+ * down-sampling).
+ * Optional outputs per problem: counts[k] = number of points in output voxel k; voxel_of_point[i] = output index of
+ * input point i (maps keypoints back to the raw cloud).
+ * n = 0 is valid (0 outputs); n points of room per problem always suffice and n_out[b] returns the number written.
+ * TEASER_HIP_ERR_BAD_ARG (teaser_hip_voxel_last_error names the argument) for a voxel_size that is not finite or
+ * <= 0, a non-finite point, a NULL pointer where n > 0, and -- Open3D's guard -- v * INT_MAX < max_a (hi_a - lo_a):
+ * the voxel size is too small for 32-bit voxel indices.  The handle stays usable after a refusal.
+ * Results are deterministic (no floating-point atomics): the same bits run to run, and for a problem alone or inside
+ * any batch.  A voxel handle is not re-entrant (one call at a time; distinct handles are independent). */
+typedef struct teaser_hip_voxel teaser_hip_voxel;
+/* device < 0: the current device.  TEASER_HIP_ERR_NO_DEVICE without a GPU: there is no CPU path. */
+TEASER_HIP_API int32_t teaser_hip_voxel_create(int32_t device, teaser_hip_voxel** out);
+TEASER_HIP_API int32_t teaser_hip_voxel_destroy(teaser_hip_voxel* voxel);
+TEASER_HIP_API const char* teaser_hip_voxel_last_error(const teaser_hip_voxel* voxel);
+/* `batch` independent problems, HOST pointers per problem, borrowed for the call.  pts[b]: n[b] x 3 doubles;
+ * voxel_size[b]; out[b]: room for n[b] x 3 doubles; n_out[b] receives the number of voxels.  counts and
+ * voxel_of_point: NULL, or per problem NULL or room for n[b] int32.  Problems of mixed sizes share the launches. */
+TEASER_HIP_API int32_t teaser_hip_voxel_down_sample_batch(teaser_hip_voxel* voxel, int32_t batch,
+                                                          const double* const* pts, const int32_t* n,
+                                                          const double* voxel_size, double* const* out,
+                                                          int64_t* n_out, int32_t* const* counts,
+                                                          int32_t* const* voxel_of_point);
+/* One problem: teaser_hip_voxel_down_sample_batch with batch = 1; counts / voxel_of_point may be NULL. */
+TEASER_HIP_API int32_t teaser_hip_voxel_down_sample(teaser_hip_voxel* voxel, const double* pts, int32_t n,
+                                                    double voxel_size, double* out, int64_t* n_out, int32_t* counts,
+                                                    int32_t* voxel_of_point);
+
 /* Page-locked host memory from the HIP runtime THIS library runs on.  teaser_hip_submit_batch(..., INPUT_HOST) moves
  * the points with one DMA copy per cloud, at PCIe speed only when the runtime knows the pages are locked.  A buffer
  * pinned by another HIP runtime instance in the same process (e.g. the one a Python framework bundles) is pageable

@@ -131,6 +131,8 @@ EXPORTED_SYMBOLS = [
     "teaser_hip_comm_gather_solutions", "teaser_hip_comm_gather_indices", "teaser_hip_comm_last_error",
     "teaser_hip_icp_params_default", "teaser_hip_icp_create", "teaser_hip_icp_destroy", "teaser_hip_icp_last_error",
     "teaser_hip_icp_batch", "teaser_hip_icp_solve",
+    "teaser_hip_voxel_create", "teaser_hip_voxel_destroy", "teaser_hip_voxel_last_error",
+    "teaser_hip_voxel_down_sample_batch", "teaser_hip_voxel_down_sample",
 ]
 
 
@@ -213,6 +215,8 @@ def lib():
                                            _dp, _dp, _u8p]
     from . import icp as _icp
     _icp.declare(L)
+    from . import voxel as _voxel
+    _voxel.declare(L)
     _lib = L
     return L
 
@@ -995,9 +999,10 @@ class MultiDeviceSolver:
 from . import batched  # noqa: E402,F401  (sharding + record gather for the multi-GPU batched mode)
 from .icp import (ICPConvergenceCriteria, RegistrationResult, TransformationEstimationPointToPoint,  # noqa: E402
                   registration_icp, registration_icp_batch)
+from .voxel import voxel_down_sample, voxel_down_sample_batch  # noqa: E402
 
 __all__ = ["batched", "FPFHEstimation", "Matcher", "MultiDeviceSolver", "RobustRegistrationSolver", "RegistrationSolution", "RotationEstimationAlgorithm",
            "InlierSelectionMode", "InlierGraphFormulation", "TeaserHipError", "synth_problem",
            "device_count", "build", "lib", "LIB_PATH", "EXPORTED_SYMBOLS", "certifier_warmup", "PinnedArray",
            "ICPConvergenceCriteria", "TransformationEstimationPointToPoint", "RegistrationResult", "registration_icp",
-           "registration_icp_batch"]
+           "registration_icp_batch", "voxel_down_sample", "voxel_down_sample_batch"]

@@ -1,0 +1,161 @@
+"""The voxel down-sampling contract (include/teaser_hip.h, "Voxel down-sampling") as restated in numpy
+(tests/voxel_reference.py), its fixture, and the parts of the GPU implementation's surface that need no device:
+names, refusals, loud failure without a GPU, the C++ facade's build."""
+import importlib
+import importlib.util
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+import voxel_reference as R
+from util import ROOT
+
+tp = importlib.import_module("teaser-plusplus_amd")
+REF_DATA = "/root/reference/examples/teaser_python_fpfh_icp/data/"
+CROP = os.path.join(ROOT, "tests", "golden", "voxel_crop.npz")
+
+
+def sequential_mean(rows):
+    s = [0.0, 0.0, 0.0]
+    for r in rows:
+        for a in range(3):
+            s[a] += float(r[a])
+    return np.array(s) / float(len(rows))
+
+
+def load_example():
+    spec = importlib.util.spec_from_file_location("fpfh_example", os.path.join(ROOT, "examples",
+                                                                               "teaser_python_fpfh.py"))
+    ex = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(ex)
+    return ex
+
+
+@pytest.mark.skipif(not os.path.isdir(REF_DATA), reason="needs the tutorial's raw clouds (workstation only)")
+def test_restatement_reproduces_the_config5_fixture():
+    """config5_clouds.npz was made from the tutorial's raw PLYs; the restatement, cast to float32, gives its bits."""
+    c5 = np.load(os.path.join(ROOT, "tests", "golden", "config5_clouds.npz"))
+    read = load_example().read_ply_xyz
+    for name in ("cloud_bin_0", "cloud_bin_4"):
+        means, counts, trace = R.voxel_down_sample(read(REF_DATA + name + ".ply").astype(np.float64), 0.05)
+        assert means.astype(np.float32).tobytes() == c5[name].tobytes(), name
+
+
+def test_a_point_on_a_face_goes_to_the_upper_voxel():
+    # v = 1, min_bound 0 -> lo = -0.5: x = 0.5 gives (0.5 + 0.5) / 1 = 1 exactly, the face between voxels 0 and 1.
+    # The largest double below 0.5 lands on the face too ((p - lo) rounds to 1.0); 0.4999999999999999 stays below.
+    p = np.array([[0.0, 0.0, 0.0], [0.5, 0.0, 0.0], [0.49999999999999994, 0.0, 0.0], [0.4999999999999999, 0.0, 0.0]])
+    assert R.voxel_indices(p, 1.0)[:, 0].tolist() == [0, 1, 1, 0]
+    means, counts, trace = R.voxel_down_sample(p, 1.0)
+    assert counts.tolist() == [2, 2]
+    assert trace.tolist() == [0, 1, 1, 0]
+    assert means[1].tobytes() == sequential_mean(p[1:3]).tobytes()
+
+
+def test_negative_coordinates():
+    p = np.array([[-3.2, -1.1, -0.4], [-3.0, -1.0, -0.3], [-1.0, -1.0, -0.3]])
+    # lo = (-3.45, -1.35, -0.65): voxels (0, 0, 0), (0, 0, 0), (4, 0, 0)
+    assert R.voxel_indices(p, 0.5).tolist() == [[0, 0, 0], [0, 0, 0], [4, 0, 0]]
+    means, counts, trace = R.voxel_down_sample(p, 0.5)
+    assert counts.tolist() == [2, 1]
+    assert means[0].tobytes() == sequential_mean(p[:2]).tobytes()
+    assert means[1].tobytes() == p[2].tobytes()
+
+
+def test_a_single_point_returns_itself():
+    p = np.array([[1.2345678901234567, -9.87654321e-3, 4.5e7]])
+    means, counts, trace = R.voxel_down_sample(p, 0.05)
+    assert means.tobytes() == p.tobytes()
+    assert counts.tolist() == [1] and trace.tolist() == [0]
+
+
+def test_duplicate_points():
+    q = [0.1, 0.7, 0.3]
+    p = np.array([q] * 5 + [[3.0, 3.0, 3.0]] + [q] * 2)
+    means, counts, trace = R.voxel_down_sample(p, 0.5)
+    assert counts.tolist() == [7, 1]
+    assert trace.tolist() == [0, 0, 0, 0, 0, 1, 0, 0]
+    assert means[0].tobytes() == sequential_mean([q] * 7).tobytes()
+
+
+def test_summation_order_changes_the_bits():
+    """(0.1 + 0.2) + 0.3 != (0.3 + 0.2) + 0.1 in FP64: the input order of a voxel's points is part of the contract,
+    and a test comparing bits can tell the orders apart."""
+    fwd = np.array([[0.1, 0.0, 0.0], [0.2, 0.0, 0.0], [0.3, 0.0, 0.0]])
+    rev = fwd[::-1].copy()
+    mf, _, _ = R.voxel_down_sample(fwd, 1.0)
+    mr, _, _ = R.voxel_down_sample(rev, 1.0)
+    assert len(mf) == 1 and len(mr) == 1
+    assert mf[0, 0] == ((0.1 + 0.2) + 0.3) / 3 and mr[0, 0] == ((0.3 + 0.2) + 0.1) / 3
+    assert mf[0, 0] != mr[0, 0]
+
+
+def test_int_max_guard_on_both_sides_of_the_boundary():
+    # v = 1: hi - lo = X + 1 on x; refused iff 1 * INT_MAX < X + 1
+    ok = np.array([[0.0, 0.0, 0.0], [2147483646.0, 0.0, 0.0]])
+    bad = np.array([[0.0, 0.0, 0.0], [2147483647.0, 0.0, 0.0]])
+    means, counts, trace = R.voxel_down_sample(ok, 1.0)
+    assert means.tolist() == ok.tolist() and counts.tolist() == [1, 1]
+    with pytest.raises(ValueError, match="voxel_size is too small"):
+        R.voxel_down_sample(bad, 1.0)
+
+
+def test_refusals_name_their_argument():
+    p = np.zeros((3, 3))
+    for v in (0.0, -0.05, np.nan, np.inf):
+        with pytest.raises(ValueError, match="voxel_size"):
+            R.voxel_down_sample(p, v)
+    q = p.copy()
+    q[1, 2] = np.nan
+    with pytest.raises(ValueError, match="points"):
+        R.voxel_down_sample(q, 0.05)
+
+
+def test_empty_cloud_is_valid():
+    means, counts, trace = R.voxel_down_sample(np.zeros((0, 3)), 0.05)
+    assert means.shape == (0, 3) and len(counts) == 0 and len(trace) == 0
+
+
+def test_crop_fixture_is_consistent():
+    g = np.load(CROP)
+    pts = g["points"]
+    assert pts.dtype == np.float32 and 30000 <= len(pts) <= 50000
+    means, counts, trace = R.voxel_down_sample(pts.astype(np.float64), float(g["voxel_size"]))
+    assert means.tobytes() == g["means"].tobytes()
+    assert np.array_equal(counts, g["counts"]) and np.array_equal(trace, g["trace"])
+    assert counts.sum() == len(pts) and np.array_equal(np.bincount(trace), counts)
+    idx = R.voxel_indices(pts, float(g["voxel_size"]))
+    first = idx[np.unique(trace, return_index=True)[1]]
+    assert all(tuple(first[k]) < tuple(first[k + 1]) for k in range(len(first) - 1))  # ascending (i_x, i_y, i_z)
+
+
+def test_public_names():
+    assert "voxel_down_sample" in tp.__all__ and "voxel_down_sample_batch" in tp.__all__
+    for sym in ("teaser_hip_voxel_create", "teaser_hip_voxel_destroy", "teaser_hip_voxel_last_error",
+                "teaser_hip_voxel_down_sample_batch", "teaser_hip_voxel_down_sample"):
+        assert sym in tp.EXPORTED_SYMBOLS
+
+
+def test_example_has_no_host_down_sampling():
+    assert not hasattr(load_example(), "voxel_downsample")
+
+
+def test_no_device_is_a_loud_error():
+    if tp.device_count() > 0:
+        return  # the GPU suite covers the device path
+    with pytest.raises(tp.TeaserHipError) as e:
+        tp.voxel_down_sample(np.zeros((4, 3)), 0.05)
+    assert "NO_DEVICE" in str(e.value)
+    import ctypes as C
+    h = C.c_void_p()
+    assert tp.lib().teaser_hip_voxel_create(0, C.byref(h)) == 3 and not h
+
+
+@pytest.mark.parametrize("eigen", [False, True])
+def test_cxx_voxel_example_builds_and_fails_loudly_without_device(eigen):
+    from voxel_cxx import build_voxel_example
+    exe = build_voxel_example(eigen)
+    rc = subprocess.call([exe], stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
+    assert rc == (0 if tp.device_count() > 0 else 77)
