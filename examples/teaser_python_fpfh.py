@@ -6,6 +6,10 @@ nearest-neighbour correspondences -> TEASER++ registration -> optional DRS certi
 on the MI355X.  Usage:
 
     python examples/teaser_python_fpfh.py [src.ply dst.ply] [--voxel 0.05] [--certify] [--icp [--icp-iterations 100]]
+                                          [--icp-plane [--icp-kernel tukey --icp-kernel-k K]]
+
+--icp-plane refines with point-to-plane ICP instead, on the target normals the FPFH stage already computed
+(rows PCL leaves non-finite, below 3 neighbours, set to zero: they contribute nothing), optionally with a robust kernel.
 
 Without file arguments it runs BASELINE config 5 from tests/golden/config5_clouds.npz (the 3DMatch pair
 cloud_bin_0 / cloud_bin_4 after a 0.05 voxel grid); with two PLY files (ASCII or binary little-endian, float x y z)
@@ -48,6 +52,10 @@ def main():
     ap.add_argument("--certify", action="store_true")
     ap.add_argument("--icp", action="store_true", help="refine the TEASER++ pose with point-to-point ICP")
     ap.add_argument("--icp-iterations", type=int, default=100)
+    ap.add_argument("--icp-plane", action="store_true",
+                    help="refine the TEASER++ pose with point-to-plane ICP on the FPFH stage's target normals")
+    ap.add_argument("--icp-kernel", choices=["l2", "huber", "cauchy", "gm", "tukey"], default="l2")
+    ap.add_argument("--icp-kernel-k", type=float, default=None, help="kernel parameter (default: the voxel size)")
     a = ap.parse_args()
     t_ds = None
     if len(a.clouds) == 2:
@@ -65,6 +73,7 @@ def main():
     est = tp.FPFHEstimation()
     fa = est.computeFPFHFeatures(A, 2 * vox, 5 * vox)   # helpers.py:9-18: radii 2 and 5 voxels
     fb = est.computeFPFHFeatures(B, 2 * vox, 5 * vox)
+    nb = est.getNormals()   # the target's normals: point-to-plane ICP refines on them
     corr = tp.Matcher().calculateCorrespondences(A, B, fa, fb, False, True, False, 0)   # helpers.py:27-43
     t1 = time.perf_counter()
     params = tp.RobustRegistrationSolver.Params(noise_bound=vox, cbar2=1.0, estimate_scaling=False,
@@ -97,6 +106,26 @@ def main():
         t3 = time.perf_counter()
         icp = tp.registration_icp(P, Q, vox, T, tp.TransformationEstimationPointToPoint(), crit)   # example.py:66-71
         t4 = time.perf_counter()
+        print("ICP before: fitness %.6f rmse %.6f" % (before.fitness, before.inlier_rmse))
+        print("ICP after:  fitness %.6f rmse %.6f iterations %d (%.2f ms)" % (icp.fitness, icp.inlier_rmse,
+                                                                              icp.iterations, 1e3 * (t4 - t3)))
+        print("T_icp =\n%s" % icp.transformation)
+    if a.icp_plane:
+        T = np.eye(4)
+        T[:3, :3], T[:3, 3] = sol.rotation, sol.translation
+        P, Q = np.asarray(A, dtype=np.float64), np.asarray(B, dtype=np.float64)
+        N = np.asarray(nb, dtype=np.float64)
+        N[~np.isfinite(N).all(axis=1)] = 0.0
+        k = a.icp_kernel_k if a.icp_kernel_k is not None else vox
+        kernel = dict(l2=tp.L2Loss, huber=lambda: tp.HuberLoss(k), cauchy=lambda: tp.CauchyLoss(k),
+                      gm=lambda: tp.GMLoss(k), tukey=lambda: tp.TukeyLoss(k))[a.icp_kernel]()
+        crit = tp.ICPConvergenceCriteria(max_iteration=a.icp_iterations)
+        before = tp.registration_icp(P, Q, vox, T, criteria=tp.ICPConvergenceCriteria(max_iteration=0))
+        t3 = time.perf_counter()
+        icp = tp.registration_icp(P, Q, vox, T, tp.TransformationEstimationPointToPlane(kernel), crit,
+                                  target_normals=N)
+        t4 = time.perf_counter()
+        print("point-to-plane, kernel %r" % (kernel,))
         print("ICP before: fitness %.6f rmse %.6f" % (before.fitness, before.inlier_rmse))
         print("ICP after:  fitness %.6f rmse %.6f iterations %d (%.2f ms)" % (icp.fitness, icp.inlier_rmse,
                                                                               icp.iterations, 1e3 * (t4 - t3)))

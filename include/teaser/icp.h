@@ -1,6 +1,7 @@
-// teaser/icp.h -- point-to-point ICP refinement (Open3D's RegistrationICP with
-// TransformationEstimationPointToPoint(with_scaling = false)) over the MI355X C ABI (include/teaser_hip.h,
-// "ICP refinement", where the contract is written out).  Header-only.
+// teaser/icp.h -- ICP refinement (Open3D's RegistrationICP with TransformationEstimationPointToPoint(with_scaling =
+// false), or with TransformationEstimationPointToPlane and an optional robust kernel on caller-given target
+// normals) over the MI355X C ABI (include/teaser_hip.h, "ICP refinement", where the contracts are written out).
+// Header-only.
 //
 // Types follow teaser/registration.h: with Eigen the clouds are Matrix<double,3,Dynamic> and the transform is
 // Eigen::Matrix4d; without Eigen the same members are the header's small value types and teaser::Matrix4 below
@@ -35,6 +36,25 @@ struct ICPConvergenceCriteria {
   double relative_fitness = 1e-6;
   double relative_rmse = 1e-6;
   int max_iteration = 30;
+};
+
+// Open3D's RobustKernel: the weight of a point-to-plane residual (table in include/teaser_hip.h).  L1Loss is not
+// offered.
+struct RobustKernel {
+  int32_t kernel = 0;  // teaser_icp_estimation_c::kernel
+  double k = 1.0;
+};
+inline RobustKernel L2Loss() { return RobustKernel{0, 1.0}; }
+inline RobustKernel HuberLoss(double k = 1.0) { return RobustKernel{1, k}; }
+inline RobustKernel CauchyLoss(double k = 1.0) { return RobustKernel{2, k}; }
+inline RobustKernel GMLoss(double k = 1.0) { return RobustKernel{3, k}; }
+inline RobustKernel TukeyLoss(double k = 1.0) { return RobustKernel{4, k}; }
+
+// Open3D's TransformationEstimationPointToPlane(kernel); the target normals are an argument of registrationICP.
+struct TransformationEstimationPointToPlane {
+  RobustKernel kernel;
+  TransformationEstimationPointToPlane() = default;
+  explicit TransformationEstimationPointToPlane(const RobustKernel& k) : kernel(k) {}
 };
 
 // Open3D's RegistrationResult + the number of iterations run.
@@ -74,6 +94,51 @@ class ICP {
                                               const std::vector<double>& max_correspondence_distance,
                                               const std::vector<Matrix4>& init,
                                               const std::vector<ICPConvergenceCriteria>& criteria) {
+    return run(src, dst, max_correspondence_distance, init, criteria, nullptr, nullptr);
+  }
+
+  // The same with point-to-plane estimation: dst_normals[b] holds one normal per point of dst[b], used as given.
+  std::vector<ICPResult> registrationICPBatch(const std::vector<Matrix3X>& src, const std::vector<Matrix3X>& dst,
+                                              const std::vector<Matrix3X>& dst_normals,
+                                              const std::vector<double>& max_correspondence_distance,
+                                              const std::vector<Matrix4>& init,
+                                              const std::vector<TransformationEstimationPointToPlane>& estimation,
+                                              const std::vector<ICPConvergenceCriteria>& criteria) {
+    const size_t b = src.size();
+    if (dst.size() != b || dst_normals.size() != b || estimation.size() != b)
+      throw std::invalid_argument("teaser::ICP: one entry per problem in every argument");
+    std::vector<const double*> pn(b);
+    std::vector<teaser_icp_estimation_c> est(b);
+    for (size_t k = 0; k < b; ++k) {
+      if (dst_normals[k].cols() != dst[k].cols())
+        throw std::invalid_argument("teaser::ICP: one normal per target point");
+      pn[k] = dst_normals[k].data();
+      est[k].method = 1;
+      est[k].kernel = estimation[k].kernel.kernel;
+      est[k].kernel_k = estimation[k].kernel.k;
+    }
+    return run(src, dst, max_correspondence_distance, init, criteria, pn.data(), est.data());
+  }
+
+  ICPResult registrationICP(const Matrix3X& src, const Matrix3X& dst, double max_correspondence_distance,
+                            const Matrix4& init = Matrix4::Identity(),
+                            const ICPConvergenceCriteria& criteria = ICPConvergenceCriteria()) {
+    return registrationICPBatch({src}, {dst}, {max_correspondence_distance}, {init}, {criteria})[0];
+  }
+
+  ICPResult registrationICP(const Matrix3X& src, const Matrix3X& dst, const Matrix3X& dst_normals,
+                            double max_correspondence_distance, const Matrix4& init,
+                            const TransformationEstimationPointToPlane& estimation,
+                            const ICPConvergenceCriteria& criteria = ICPConvergenceCriteria()) {
+    return registrationICPBatch({src}, {dst}, {dst_normals}, {max_correspondence_distance}, {init}, {estimation},
+                                {criteria})[0];
+  }
+
+ private:
+  std::vector<ICPResult> run(const std::vector<Matrix3X>& src, const std::vector<Matrix3X>& dst,
+                             const std::vector<double>& max_correspondence_distance,
+                             const std::vector<Matrix4>& init, const std::vector<ICPConvergenceCriteria>& criteria,
+                             const double* const* normals, const teaser_icp_estimation_c* est) {
     const size_t b = src.size();
     if (dst.size() != b || max_correspondence_distance.size() != b || init.size() != b || criteria.size() != b)
       throw std::invalid_argument("teaser::ICP: one entry per problem in every argument");
@@ -98,8 +163,11 @@ class ICP {
       pc[k] = corr[k].data();
     }
     std::vector<teaser_icp_result_c> out(b);
-    const int32_t rc = teaser_hip_icp_batch(h_, (int32_t)b, ps.data(), ns.data(), pd.data(), nd.data(), T.data(),
-                                            params.data(), out.data(), pc.data());
+    const int32_t rc =
+        est ? teaser_hip_icp_batch_ex(h_, (int32_t)b, ps.data(), ns.data(), pd.data(), nd.data(), T.data(),
+                                      params.data(), out.data(), pc.data(), normals, est)
+            : teaser_hip_icp_batch(h_, (int32_t)b, ps.data(), ns.data(), pd.data(), nd.data(), T.data(),
+                                   params.data(), out.data(), pc.data());
     if (rc != TEASER_HIP_OK)
       throw ICPError(rc, "teaser::ICP: status " + std::to_string(rc) + ": " + teaser_hip_icp_last_error(h_));
     std::vector<ICPResult> res(b);
@@ -115,13 +183,6 @@ class ICP {
     return res;
   }
 
-  ICPResult registrationICP(const Matrix3X& src, const Matrix3X& dst, double max_correspondence_distance,
-                            const Matrix4& init = Matrix4::Identity(),
-                            const ICPConvergenceCriteria& criteria = ICPConvergenceCriteria()) {
-    return registrationICPBatch({src}, {dst}, {max_correspondence_distance}, {init}, {criteria})[0];
-  }
-
- private:
   teaser_hip_icp* h_ = nullptr;
 };
 
@@ -132,6 +193,15 @@ inline ICPResult registrationICP(const Matrix3X& src, const Matrix3X& dst, doubl
                                  const ICPConvergenceCriteria& criteria = ICPConvergenceCriteria()) {
   ICP icp;
   return icp.registrationICP(src, dst, max_correspondence_distance, init, criteria);
+}
+
+// Open3D's registration_icp with TransformationEstimationPointToPlane: dst_normals holds one normal per target point.
+inline ICPResult registrationICP(const Matrix3X& src, const Matrix3X& dst, const Matrix3X& dst_normals,
+                                 double max_correspondence_distance, const Matrix4& init,
+                                 const TransformationEstimationPointToPlane& estimation,
+                                 const ICPConvergenceCriteria& criteria = ICPConvergenceCriteria()) {
+  ICP icp;
+  return icp.registrationICP(src, dst, dst_normals, max_correspondence_distance, init, estimation, criteria);
 }
 
 }  // namespace teaser

@@ -465,6 +465,60 @@ TEASER_HIP_API int32_t teaser_hip_icp_solve(teaser_hip_icp* icp, const double* s
                                             const teaser_icp_params_c* params, teaser_icp_result_c* out,
                                             int32_t* corr);
 
+/* ICP refinement: point-to-plane (Open3D's TransformationEstimationPointToPlane with an optional RobustKernel), a
+ * second estimation method of the same batched ICP: same handle, search, stop rule and determinism guarantees,
+ * selectable per problem and mixed freely with point-to-point problems in one batch.
+ * Additional input per point-to-plane problem: the target normals N, n_t x 3 doubles, one per target point, used as
+ * given (not normalised, like Open3D).  A zero normal is legal and contributes nothing to the step.
+ * The loop, apply, corr, fitness, inlier_rmse (EUCLIDEAN, as above: Open3D's registration_icp reports that one for
+ * every estimation method), T = U T, the iteration count and the stop rule are exactly those written out above.
+ * Only U differs.  With c = the problem's target bounding-box centre and, for every correspondence (i, j) of C in
+ * ascending i, x = the current moved source point, q = Q[j], n = N[j]:
+ *   x' = x - c,  q' = q - c,  e = x' - q'
+ *   r  = (e0 n0 + e1 n1) + e2 n2                        residual, no fused operations
+ *   w  = kernel(r)                                      weight, table below
+ *   J  = [ x' x n ; n ]                                 6-vector (cross product, then the normal)
+ *   A  = sum w J J^T  (6 x 6, symmetric),  g = sum w r J
+ *   solve A xi = -g in FP64 by LDL^T without pivoting;  xi = (alpha, beta, gamma, t'x, t'y, t'z)
+ *   R  = Rz(gamma) Ry(beta) Rx(alpha)                   Open3D's TransformVector6dToMatrix4d
+ *   U  = [ R | t' + c - R c ]                           the step expressed in the problem's own coordinates
+ * U is the identity when C is empty, when the factorisation meets a pivot that is not finite or not positive, or when
+ * xi is not finite (Open3D returns the identity when its solve fails).  Solving in the frame centred on c is the ONE
+ * deliberate difference from Open3D, which linearises about the origin: the two steps differ at second order in the
+ * step's rotation and have the same fixed point, and the centred form makes the result independent of where the pair
+ * sits in space (up to the coordinates' own rounding), as the point-to-point sums already are.
+ * Robust kernels, Open3D's RobustKernel::Weight(r) with its parameter k:
+ *   L2 (default)  1
+ *   Huber         1 if |r| <= k, else k / |r|
+ *   Cauchy        1 / (1 + (r / k)^2)
+ *   GM            k / (k + r^2)^2
+ *   Tukey         (1 - (r / k)^2)^2 if |r| <= k, else 0
+ * Open3D's L1Loss (w = 1 / |r|, unbounded at r = 0) is not offered.  Open3D applies no kernel to point-to-point;
+ * neither does this.  TEASER_HIP_ERR_BAD_ARG (argument named) in addition to the list above: an unknown method or
+ * kernel, a kernel other than L2 with point-to-point, a kernel_k that is not finite and > 0 (ignored for L2),
+ * point-to-plane with n_t > 0 and no dst_normals, non-finite dst_normals.  Point-to-point problems give the same bits
+ * through the _ex entry points as through the ones above, alone or mixed with point-to-plane problems. */
+typedef struct teaser_icp_estimation_c {
+  int32_t method;  /* 0 point-to-point (default), 1 point-to-plane */
+  int32_t kernel;  /* 0 L2 (default), 1 Huber, 2 Cauchy, 3 GM, 4 Tukey */
+  double kernel_k; /* 1.0 (Open3D's default); ignored for L2 */
+} teaser_icp_estimation_c;
+TEASER_HIP_API int32_t teaser_hip_icp_estimation_default(teaser_icp_estimation_c* est);
+/* teaser_hip_icp_batch plus dst_normals (NULL, or per problem NULL for point-to-point, else n_dst[b] x 3 doubles,
+ * borrowed for the call) and est (NULL = every problem point-to-point, else one per problem). */
+TEASER_HIP_API int32_t teaser_hip_icp_batch_ex(teaser_hip_icp* icp, int32_t batch, const double* const* src,
+                                               const int32_t* n_src, const double* const* dst,
+                                               const int32_t* n_dst, const double* init,
+                                               const teaser_icp_params_c* params, teaser_icp_result_c* out,
+                                               int32_t* const* corr, const double* const* dst_normals,
+                                               const teaser_icp_estimation_c* est);
+/* One problem: teaser_hip_icp_batch_ex with batch = 1. */
+TEASER_HIP_API int32_t teaser_hip_icp_solve_ex(teaser_hip_icp* icp, const double* src, int32_t n_src,
+                                               const double* dst, int32_t n_dst, const double* init,
+                                               const teaser_icp_params_c* params, teaser_icp_result_c* out,
+                                               int32_t* corr, const double* dst_normals,
+                                               const teaser_icp_estimation_c* est);
+
 /* Voxel down-sampling (the reference's 3DMatch tutorial, examples/teaser_python_fpfh_icp/example.py:19-20, runs
  * Open3D's pcd.voxel_down_sample(0.05) on the raw clouds): batched, with Open3D's arithmetic and a deterministic output
  * order, on its OWN handle (nothing is shared with teaser_hip_solver or teaser_hip_icp).

@@ -130,7 +130,8 @@ EXPORTED_SYMBOLS = [
     "teaser_hip_comm_shard", "teaser_hip_comm_unique_id", "teaser_hip_comm_create", "teaser_hip_comm_destroy",
     "teaser_hip_comm_gather_solutions", "teaser_hip_comm_gather_indices", "teaser_hip_comm_last_error",
     "teaser_hip_icp_params_default", "teaser_hip_icp_create", "teaser_hip_icp_destroy", "teaser_hip_icp_last_error",
-    "teaser_hip_icp_batch", "teaser_hip_icp_solve",
+    "teaser_hip_icp_batch", "teaser_hip_icp_solve", "teaser_hip_icp_estimation_default", "teaser_hip_icp_batch_ex",
+    "teaser_hip_icp_solve_ex",
     "teaser_hip_voxel_create", "teaser_hip_voxel_destroy", "teaser_hip_voxel_last_error",
     "teaser_hip_voxel_down_sample_batch", "teaser_hip_voxel_down_sample",
 ]
@@ -997,7 +998,8 @@ class MultiDeviceSolver:
 
 
 from . import batched  # noqa: E402,F401  (sharding + record gather for the multi-GPU batched mode)
-from .icp import (ICPConvergenceCriteria, RegistrationResult, TransformationEstimationPointToPoint,  # noqa: E402
+from .icp import (CauchyLoss, GMLoss, HuberLoss, ICPConvergenceCriteria, L2Loss, RegistrationResult,  # noqa: E402
+                  TransformationEstimationPointToPlane, TransformationEstimationPointToPoint, TukeyLoss,
                   registration_icp, registration_icp_batch)
 from .voxel import voxel_down_sample, voxel_down_sample_batch  # noqa: E402
 
@@ -1005,4 +1007,5 @@ __all__ = ["batched", "FPFHEstimation", "Matcher", "MultiDeviceSolver", "RobustR
            "InlierSelectionMode", "InlierGraphFormulation", "TeaserHipError", "synth_problem",
            "device_count", "build", "lib", "LIB_PATH", "EXPORTED_SYMBOLS", "certifier_warmup", "PinnedArray",
            "ICPConvergenceCriteria", "TransformationEstimationPointToPoint", "RegistrationResult", "registration_icp",
-           "registration_icp_batch", "voxel_down_sample", "voxel_down_sample_batch"]
+           "registration_icp_batch", "voxel_down_sample", "voxel_down_sample_batch",
+           "TransformationEstimationPointToPlane", "L2Loss", "HuberLoss", "CauchyLoss", "GMLoss", "TukeyLoss"]

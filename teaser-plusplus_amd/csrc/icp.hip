@@ -1,5 +1,6 @@
-// icp.hip -- host side of the batched point-to-point ICP (include/teaser_hip.h, "ICP refinement"): its own handle,
-// argument validation, the per-call target index and the iteration loop.  Kernels: kernels_icp.hip.
+// icp.hip -- host side of the batched ICP (include/teaser_hip.h, "ICP refinement": point-to-point and point-to-plane
+// with robust kernels): its own handle, argument validation, the per-call target index and the iteration loop.
+// Kernels: kernels_icp.hip.
 //
 // The host enqueues iterations in groups of kIcpGroup (two launches each); after a group ONE small copy of the
 // number of unfinished problems decides whether another group follows.  There is no host round trip inside a group:
@@ -43,7 +44,7 @@ struct DevBuf {
 };
 
 enum { B_DESC, B_STATE, B_BLK, B_TBLK, B_X, B_Q, B_TBUCKET, B_BCOUNT, B_BSTART, B_CURSOR, B_QS, B_QJ, B_MATCH,
-       B_PARTIALS, B_LIVE, B_COUNT };
+       B_PARTIALS, B_LIVE, B_NORMALS, B_COUNT };
 
 }  // namespace
 
@@ -78,7 +79,8 @@ std::string at(int b) { return " (problem " + std::to_string(b) + ")"; }
 
 int32_t validate(teaser_hip_icp* h, int32_t batch, const double* const* src, const int32_t* n_src,
                  const double* const* dst, const int32_t* n_dst, const double* init,
-                 const teaser_icp_params_c* params, teaser_icp_result_c* out) {
+                 const teaser_icp_params_c* params, teaser_icp_result_c* out, const double* const* dst_normals,
+                 const teaser_icp_estimation_c* est) {
   if (batch < 0) return fail(h, TEASER_HIP_ERR_BAD_ARG, "batch must be >= 0");
   if (batch == 0) return TEASER_HIP_OK;
   if (!n_src || !n_dst) return fail(h, TEASER_HIP_ERR_BAD_ARG, "n_src / n_dst must not be NULL");
@@ -110,6 +112,24 @@ int32_t validate(teaser_hip_icp* h, int32_t batch, const double* const* src, con
         if (!std::isfinite(T[k])) return fail(h, TEASER_HIP_ERR_BAD_ARG, "init is not finite" + at(b));
       if (T[12] != 0 || T[13] != 0 || T[14] != 0 || T[15] != 1)
         return fail(h, TEASER_HIP_ERR_BAD_ARG, "init: last row must be 0 0 0 1" + at(b));
+    }
+    if (est) {
+      const teaser_icp_estimation_c& m = est[b];
+      if (m.method != kIcpMethodPoint && m.method != kIcpMethodPlane)
+        return fail(h, TEASER_HIP_ERR_BAD_ARG, "est: unknown method" + at(b));
+      if (m.kernel < kIcpKernelL2 || m.kernel > kIcpKernelTukey)
+        return fail(h, TEASER_HIP_ERR_BAD_ARG, "est: unknown kernel" + at(b));
+      if (m.method == kIcpMethodPoint && m.kernel != kIcpKernelL2)
+        return fail(h, TEASER_HIP_ERR_BAD_ARG,
+                    "est: a kernel other than L2 needs point-to-plane (kernel given with point-to-point)" + at(b));
+      if (m.kernel != kIcpKernelL2 && (!std::isfinite(m.kernel_k) || !(m.kernel_k > 0)))
+        return fail(h, TEASER_HIP_ERR_BAD_ARG, "est: kernel_k must be finite and > 0" + at(b));
+      if (m.method == kIcpMethodPlane && n_dst[b] > 0) {
+        if (!dst_normals || !dst_normals[b])
+          return fail(h, TEASER_HIP_ERR_BAD_ARG, "dst_normals is NULL for a point-to-plane problem" + at(b));
+        if (!finite_points(dst_normals[b], n_dst[b]))
+          return fail(h, TEASER_HIP_ERR_BAD_ARG, "dst_normals has a non-finite component" + at(b));
+      }
     }
     total_s += n_src[b];
     total_t += n_dst[b];
@@ -174,12 +194,27 @@ int32_t teaser_hip_icp_destroy(teaser_hip_icp* h) {
 
 const char* teaser_hip_icp_last_error(const teaser_hip_icp* h) { return h ? h->err.c_str() : ""; }
 
+int32_t teaser_hip_icp_estimation_default(teaser_icp_estimation_c* est) {
+  if (!est) return TEASER_HIP_ERR_BAD_ARG;
+  est->method = kIcpMethodPoint;
+  est->kernel = kIcpKernelL2;
+  est->kernel_k = 1.0;  // Open3D's default parameter of every robust kernel; ignored for L2
+  return TEASER_HIP_OK;
+}
+
 int32_t teaser_hip_icp_batch(teaser_hip_icp* h, int32_t batch, const double* const* src, const int32_t* n_src,
                              const double* const* dst, const int32_t* n_dst, const double* init,
                              const teaser_icp_params_c* params, teaser_icp_result_c* out, int32_t* const* corr) {
+  return teaser_hip_icp_batch_ex(h, batch, src, n_src, dst, n_dst, init, params, out, corr, nullptr, nullptr);
+}
+
+int32_t teaser_hip_icp_batch_ex(teaser_hip_icp* h, int32_t batch, const double* const* src, const int32_t* n_src,
+                                const double* const* dst, const int32_t* n_dst, const double* init,
+                                const teaser_icp_params_c* params, teaser_icp_result_c* out, int32_t* const* corr,
+                                const double* const* dst_normals, const teaser_icp_estimation_c* est) {
   if (!h) return TEASER_HIP_ERR_BAD_ARG;
   h->err.clear();
-  int32_t rc = validate(h, batch, src, n_src, dst, n_dst, init, params, out);
+  int32_t rc = validate(h, batch, src, n_src, dst, n_dst, init, params, out, dst_normals, est);
   if (rc != TEASER_HIP_OK || batch == 0) return rc;
   hipError_t e = hipSetDevice(h->device);
   if (e != hipSuccess) return hip_fail(h, e, "hipSetDevice");
@@ -190,6 +225,7 @@ int32_t teaser_hip_icp_batch(teaser_hip_icp* h, int32_t batch, const double* con
   std::vector<int32_t> blk_prob, tblk_prob;
   int64_t s_off = 0, t_off = 0, b_off = 0;
   int max_iter = 0;
+  bool plane = false;  // any point-to-plane problem: the launches with the wider partials
   for (int b = 0; b < batch; ++b) {
     IcpDesc& d = desc[(size_t)b];
     memset(&d, 0, sizeof(d));
@@ -208,6 +244,12 @@ int32_t teaser_hip_icp_batch(teaser_hip_icp* h, int32_t batch, const double* con
     d.rel_rmse = p.relative_rmse;
     d.max_iteration = p.max_iteration;
     max_iter = std::max(max_iter, p.max_iteration);
+    if (est) {
+      d.method = est[b].method;
+      d.kernel = est[b].kernel;
+      d.kernel_k = est[b].kernel == kIcpKernelL2 ? 0.0 : est[b].kernel_k;
+      plane |= d.method == kIcpMethodPlane;
+    }
     if (d.n_t > 0) {
       double lo[3], hi[3];
       for (int c = 0; c < 3; ++c) lo[c] = hi[c] = dst[b][c];
@@ -251,7 +293,8 @@ int32_t teaser_hip_icp_batch(teaser_hip_icp* h, int32_t batch, const double* con
       sizeof(int32_t) * std::max<int64_t>(b_off, 1), sizeof(int32_t) * std::max<int64_t>(b_off, 1),
       sizeof(int32_t) * std::max<int64_t>(b_off, 1), sizeof(double) * 3 * std::max<int64_t>(t_off, 1),
       sizeof(int32_t) * std::max<int64_t>(t_off, 1), sizeof(int32_t) * std::max<int64_t>(s_off, 1),
-      sizeof(double) * kIcpSums * std::max(n_blk, 1), sizeof(int32_t)};
+      sizeof(double) * (plane ? kIcpPlaneSums : kIcpSums) * std::max(n_blk, 1), sizeof(int32_t),
+      plane ? sizeof(double) * 3 * std::max<int64_t>(t_off, 1) : 0};
   for (int k = 0; k < B_COUNT; ++k)
     if (!h->buf[k].ensure(bytes[k])) return fail(h, TEASER_HIP_ERR_OOM, "hipMalloc failed (ICP buffers)");
   hipStream_t s = h->stream;
@@ -276,6 +319,13 @@ int32_t teaser_hip_icp_batch(teaser_hip_icp* h, int32_t batch, const double* con
   for (const Copy& c : copies)
     if (c.n && (e = hipMemcpyAsync(c.d, c.hsrc, c.n, hipMemcpyHostToDevice, s)) != hipSuccess)
       return hip_fail(h, e, "hipMemcpyAsync (inputs)");
+  for (int b = 0; b < batch; ++b) {  // one copy per point-to-plane problem, straight from the caller's normals
+    const IcpDesc& d = desc[(size_t)b];
+    if (d.method == kIcpMethodPlane && d.n_t > 0 &&
+        (e = hipMemcpyAsync(B[B_NORMALS].as<double>() + 3 * d.t_off, dst_normals[b], 24 * (size_t)d.n_t,
+                            hipMemcpyHostToDevice, s)) != hipSuccess)
+      return hip_fail(h, e, "hipMemcpyAsync (normals)");
+  }
   if (b_off && (e = hipMemsetAsync(B[B_BCOUNT].p, 0, sizeof(int32_t) * b_off, s)) != hipSuccess)
     return hip_fail(h, e, "hipMemsetAsync");
 
@@ -288,7 +338,8 @@ int32_t teaser_hip_icp_batch(teaser_hip_icp* h, int32_t batch, const double* con
     for (int g = 0; g < kIcpGroup && passes <= (int64_t)max_iter; ++g, ++passes)
       launch_icp_iteration(s, B[B_DESC].as<IcpDesc>(), B[B_STATE].as<IcpState>(), B[B_BLK].as<int32_t>(), n_blk,
                            batch, B[B_X].as<double>(), B[B_QS].as<double>(), B[B_QJ].as<int32_t>(),
-                           B[B_BSTART].as<int32_t>(), B[B_MATCH].as<int32_t>(), B[B_PARTIALS].as<double>());
+                           B[B_BSTART].as<int32_t>(), B[B_NORMALS].as<double>(), plane, B[B_MATCH].as<int32_t>(),
+                           B[B_PARTIALS].as<double>());
     launch_icp_live(s, B[B_STATE].as<IcpState>(), batch, B[B_LIVE].as<int32_t>());
     if ((e = hipGetLastError()) != hipSuccess) return hip_fail(h, e, "ICP kernel launch");
     if ((e = hipMemcpyAsync(h->h_live, B[B_LIVE].p, sizeof(int32_t), hipMemcpyDeviceToHost, s)) != hipSuccess)
@@ -336,8 +387,16 @@ int32_t teaser_hip_icp_batch(teaser_hip_icp* h, int32_t batch, const double* con
 int32_t teaser_hip_icp_solve(teaser_hip_icp* h, const double* src, int32_t n_src, const double* dst, int32_t n_dst,
                              const double* init, const teaser_icp_params_c* params, teaser_icp_result_c* out,
                              int32_t* corr) {
+  return teaser_hip_icp_solve_ex(h, src, n_src, dst, n_dst, init, params, out, corr, nullptr, nullptr);
+}
+
+int32_t teaser_hip_icp_solve_ex(teaser_hip_icp* h, const double* src, int32_t n_src, const double* dst,
+                                int32_t n_dst, const double* init, const teaser_icp_params_c* params,
+                                teaser_icp_result_c* out, int32_t* corr, const double* dst_normals,
+                                const teaser_icp_estimation_c* est) {
   int32_t* const corrs[1] = {corr};
-  return teaser_hip_icp_batch(h, 1, &src, &n_src, &dst, &n_dst, init, params, out, corrs);
+  return teaser_hip_icp_batch_ex(h, 1, &src, &n_src, &dst, &n_dst, init, params, out, corrs,
+                                 dst_normals ? &dst_normals : nullptr, est);
 }
 
 }  // extern "C"

@@ -9,7 +9,12 @@ namespace thip {
 
 constexpr int kIcpBlock = 256;   // source points per correspondence block (the chunking depends on n_s alone)
 constexpr int kIcpSums = 17;     // {count, sum d2, sum p' (3), sum q' (3), sum p' q'^T (9)} of one block
+constexpr int kIcpPlaneSums = 29;  // point-to-plane: {count, sum d2, upper triangle of A by rows (21), g (6)}
 constexpr int kIcpScanThreads = 1024;
+
+// IcpDesc::method / IcpDesc::kernel: the values of teaser_icp_estimation_c (include/teaser_hip.h)
+enum { kIcpMethodPoint = 0, kIcpMethodPlane = 1 };
+enum { kIcpKernelL2 = 0, kIcpKernelHuber = 1, kIcpKernelCauchy = 2, kIcpKernelGM = 3, kIcpKernelTukey = 4 };
 
 // One problem of a batch (host-built, read-only on the device).  Cell coordinates of a point x are
 // floor((x - origin) * inv_h) per axis, clamped to [-2, 2^40] (monotone, so neighbouring cells stay neighbours).
@@ -29,6 +34,9 @@ struct IcpDesc {
   double rel_fitness, rel_rmse;
   int32_t max_iteration;
   int32_t tblk_off;   // first target block of this problem (index build)
+  int32_t method;     // kIcpMethodPoint / kIcpMethodPlane
+  int32_t kernel;     // robust kernel of a point-to-plane problem (kIcpKernelL2 ...)
+  double kernel_k;    // its parameter; unused for L2
 };
 
 // Mutable per-problem state.
@@ -63,7 +71,8 @@ void launch_icp_index(hipStream_t s, const IcpDesc* d_desc, const int32_t* d_tbl
                       int32_t* d_cursor, double* d_qs, int32_t* d_qj);
 void launch_icp_iteration(hipStream_t s, const IcpDesc* d_desc, IcpState* d_state, const int32_t* d_blk_prob,
                           int n_blk, int batch, double* d_x, const double* d_qs, const int32_t* d_qj,
-                          const int32_t* d_bstart, int32_t* d_match, double* d_partials);
+                          const int32_t* d_bstart, const double* d_normals, bool plane, int32_t* d_match,
+                          double* d_partials);
 void launch_icp_live(hipStream_t s, const IcpState* d_state, int batch, int32_t* d_live);
 
 }  // namespace thip

@@ -15,6 +15,15 @@
 // the stop rule, and computes the next U (Umeyama via svd_rot3) and T = U T.  A finished problem's blocks return
 // at once.  No floating-point atomics: every sum has a fixed order, and the chunking depends on the problem alone,
 // so a problem gives the same bits alone and inside any batch.
+//
+// Point-to-plane (IcpDesc::method = 1; contract in include/teaser_hip.h, "ICP refinement: point-to-plane"): the same
+// search, then the target normal of the match is gathered ONCE per source point from the packed normals (the search
+// visits tens of candidates per point and uses one normal, so normals are not carried through the bucket order) and
+// the block's partial holds {count, sum d2, 21 upper-triangle entries of A = sum w J J^T, 6 entries of g = sum w r J}
+// = kIcpPlaneSums values.  The correspondence and finalize kernels are templates on kPlane: <false> is the
+// point-to-point code exactly as before, launched when a call has no point-to-plane problem; <true> has the wider
+// partial and branches per block on the problem's method (uniform over the block), its point-to-point branch
+// executing the same operations in the same order, so a point-to-point problem keeps its bits in a mixed batch.
 #include <math.h>
 
 #include "icp_internal.h"
@@ -28,18 +37,40 @@ __device__ __forceinline__ double icp_wave_sum(double v) {
   return v;
 }
 
-// Sums v[0..kIcpSums) over the 256 threads of the block in a fixed order; the result is valid in thread k < kIcpSums
-// as out (returned), for its own k.
-__device__ __forceinline__ double icp_block_sum(const double (&v)[kIcpSums], double (*s)[kIcpSums] /* LDS [4] */) {
+// Sums v[0..NS) over the 256 threads of the block in a fixed order; the result is valid in thread k < NS as out
+// (returned), for its own k.
+template <int NS>
+__device__ __forceinline__ double icp_block_sum(const double (&v)[NS], double (*s)[NS] /* LDS [4] */) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 #pragma unroll
-  for (int k = 0; k < kIcpSums; ++k) {
+  for (int k = 0; k < NS; ++k) {
     const double w = icp_wave_sum(v[k]);
     if (lane == 0) s[wave][k] = w;
   }
   __syncthreads();
   const int k = threadIdx.x;
-  return k < kIcpSums ? (s[0][k] + s[1][k]) + (s[2][k] + s[3][k]) : 0.0;
+  return k < NS ? (s[0][k] + s[1][k]) + (s[2][k] + s[3][k]) : 0.0;
+}
+
+// Open3D's RobustKernel::Weight(r); L2 never reaches this.
+__device__ __forceinline__ double icp_kernel_weight(int kernel, double k, double r) {
+  const double a = fabs(r);
+  switch (kernel) {
+    case kIcpKernelHuber: return a <= k ? 1.0 : k / a;
+    case kIcpKernelCauchy: {
+      const double q = r / k;
+      return 1.0 / (1.0 + q * q);
+    }
+    case kIcpKernelGM: {
+      const double s = k + r * r;
+      return k / (s * s);
+    }
+    case kIcpKernelTukey: {
+      const double q = r / k, u = 1.0 - q * q;
+      return a <= k ? u * u : 0.0;
+    }
+    default: return 1.0;
+  }
 }
 
 // ---- target index ---------------------------------------------------------------------------------------------
@@ -107,23 +138,26 @@ __global__ __launch_bounds__(256) void icp_fill_kernel(const IcpDesc* __restrict
 }
 
 // ---- one iteration ----------------------------------------------------------------------------------------------
+template <bool kPlane>
 __global__ __launch_bounds__(kIcpBlock) void icp_corr_kernel(const IcpDesc* __restrict__ descs,
                                                              const IcpState* __restrict__ state,
                                                              const int32_t* __restrict__ blk_prob,
                                                              double* __restrict__ X, const double* __restrict__ qs,
                                                              const int32_t* __restrict__ qj,
                                                              const int32_t* __restrict__ bstart,
+                                                             const double* __restrict__ normals,
                                                              int32_t* __restrict__ match,
                                                              double* __restrict__ partials) {
-  __shared__ double s[4][kIcpSums];
+  constexpr int NS = kPlane ? kIcpPlaneSums : kIcpSums;
+  __shared__ double s[4][NS];
   const int p = blk_prob[blockIdx.x];
   if (state[p].done) return;  // uniform over the block
   const IcpDesc& d = descs[p];
   const int chunk = (int)blockIdx.x - d.blk_off;
   const int64_t i = (int64_t)chunk * kIcpBlock + threadIdx.x;
-  double v[kIcpSums];
+  double v[NS];
 #pragma unroll
-  for (int k = 0; k < kIcpSums; ++k) v[k] = 0.0;
+  for (int k = 0; k < NS; ++k) v[k] = 0.0;
   if (i < d.n_s) {
     const double* U = state[p].U;
     double* xp = X + 3 * (d.s_off + i);
@@ -176,37 +210,112 @@ __global__ __launch_bounds__(kIcpBlock) void icp_corr_kernel(const IcpDesc* __re
       }
       v[0] = 1.0;
       v[1] = bd;
+      if (kPlane && d.method == kIcpMethodPlane) {  // uniform over the block
+        const double* np = normals + 3 * (d.t_off + bj);
+        const double n[3] = {np[0], np[1], np[2]};
+        const double e0 = pc[0] - qc[0], e1 = pc[1] - qc[1], e2 = pc[2] - qc[2];
+        const double res = (e0 * n[0] + e1 * n[1]) + e2 * n[2];
+        const double w = d.kernel == kIcpKernelL2 ? 1.0 : icp_kernel_weight(d.kernel, d.kernel_k, res);
+        double J[6];
+        J[0] = pc[1] * n[2] - pc[2] * n[1];
+        J[1] = pc[2] * n[0] - pc[0] * n[2];
+        J[2] = pc[0] * n[1] - pc[1] * n[0];
+        J[3] = n[0];
+        J[4] = n[1];
+        J[5] = n[2];
+        const double wr = w * res;
 #pragma unroll
-      for (int r = 0; r < 3; ++r) {
-        v[2 + r] = pc[r];
-        v[5 + r] = qc[r];
+        for (int r = 0; r < 6; ++r) {
+          const double wj = w * J[r];
 #pragma unroll
-        for (int c = 0; c < 3; ++c) v[8 + 3 * r + c] = pc[r] * qc[c];
+          for (int c = 0; c < 6; ++c)
+            if (c >= r) v[2 + 6 * r - r * (r - 1) / 2 + (c - r)] = wj * J[c];  // upper triangle by rows
+        }
+#pragma unroll
+        for (int r = 0; r < 6; ++r) v[23 + r] = wr * J[r];
+      } else {
+#pragma unroll
+        for (int r = 0; r < 3; ++r) {
+          v[2 + r] = pc[r];
+          v[5 + r] = qc[r];
+#pragma unroll
+          for (int c = 0; c < 3; ++c) v[8 + 3 * r + c] = pc[r] * qc[c];
+        }
       }
     }
   }
-  const double tot = icp_block_sum(v, s);
-  if (threadIdx.x < kIcpSums) partials[(int64_t)blockIdx.x * kIcpSums + threadIdx.x] = tot;
+  const double tot = icp_block_sum<NS>(v, s);
+  if (threadIdx.x < NS) partials[(int64_t)blockIdx.x * NS + threadIdx.x] = tot;
 }
 
+// The point-to-plane step from the summed normal equations (tot[2..22]: upper triangle of A by rows, tot[23..28]: g):
+// A xi = -g by LDL^T without pivoting, R = Rz(gamma) Ry(beta) Rx(alpha), U = [R | t' + c - R c].  U stays the
+// identity when a pivot is not finite or not positive or xi is not finite.
+__device__ void icp_plane_step(const double* tot, const double* c, double* U) {
+  double A[6][6], L[6][6], dd[6], y[6], xi[6];
+  int k = 2;
+  for (int r = 0; r < 6; ++r)
+    for (int q = r; q < 6; ++q) {
+      A[r][q] = tot[k];
+      A[q][r] = tot[k];
+      ++k;
+    }
+  for (int j = 0; j < 6; ++j) {
+    double sj = A[j][j];
+    for (int m = 0; m < j; ++m) sj -= L[j][m] * L[j][m] * dd[m];
+    if (!isfinite(sj) || !(sj > 0.0)) return;
+    dd[j] = sj;
+    for (int i = j + 1; i < 6; ++i) {
+      double t = A[i][j];
+      for (int m = 0; m < j; ++m) t -= L[i][m] * L[j][m] * dd[m];
+      L[i][j] = t / sj;
+    }
+  }
+  for (int i = 0; i < 6; ++i) {
+    double t = -tot[23 + i];
+    for (int m = 0; m < i; ++m) t -= L[i][m] * y[m];
+    y[i] = t;
+  }
+  for (int i = 0; i < 6; ++i) y[i] = y[i] / dd[i];
+  for (int i = 5; i >= 0; --i) {
+    double t = y[i];
+    for (int m = i + 1; m < 6; ++m) t -= L[m][i] * xi[m];
+    xi[i] = t;
+  }
+  for (int i = 0; i < 6; ++i)
+    if (!isfinite(xi[i])) return;
+  const double ca = cos(xi[0]), sa = sin(xi[0]), cb = cos(xi[1]), sb = sin(xi[1]), cg = cos(xi[2]), sg = sin(xi[2]);
+  const double R[9] = {cg * cb, cg * sb * sa - sg * ca, cg * sb * ca + sg * sa,
+                       sg * cb, sg * sb * sa + cg * ca, sg * sb * ca - cg * sa,
+                       -sb,     cb * sa,                cb * ca};
+  for (int r = 0; r < 3; ++r) {
+    U[4 * r] = R[3 * r];
+    U[4 * r + 1] = R[3 * r + 1];
+    U[4 * r + 2] = R[3 * r + 2];
+    U[4 * r + 3] = (xi[3 + r] + c[r]) - ((R[3 * r] * c[0] + R[3 * r + 1] * c[1]) + R[3 * r + 2] * c[2]);
+  }
+}
+
+template <bool kPlane>
 __global__ __launch_bounds__(256) void icp_finalize_kernel(const IcpDesc* __restrict__ descs,
                                                            IcpState* __restrict__ state,
                                                            const double* __restrict__ partials) {
-  __shared__ double s[4][kIcpSums];
-  __shared__ double tot[kIcpSums];
+  constexpr int NS = kPlane ? kIcpPlaneSums : kIcpSums;
+  __shared__ double s[4][NS];
+  __shared__ double tot[NS];
   const int p = blockIdx.x;
   if (state[p].done) return;
   const IcpDesc& d = descs[p];
-  double v[kIcpSums];
+  double v[NS];
 #pragma unroll
-  for (int k = 0; k < kIcpSums; ++k) v[k] = 0.0;
+  for (int k = 0; k < NS; ++k) v[k] = 0.0;
   for (int b = threadIdx.x; b < d.nblk; b += 256) {
-    const double* pb = partials + (int64_t)(d.blk_off + b) * kIcpSums;
+    const double* pb = partials + (int64_t)(d.blk_off + b) * NS;
 #pragma unroll
-    for (int k = 0; k < kIcpSums; ++k) v[k] += pb[k];
+    for (int k = 0; k < NS; ++k) v[k] += pb[k];
   }
-  const double t = icp_block_sum(v, s);
-  if (threadIdx.x < kIcpSums) tot[threadIdx.x] = t;
+  const double t = icp_block_sum<NS>(v, s);
+  if (threadIdx.x < NS) tot[threadIdx.x] = t;
   __syncthreads();
   if (threadIdx.x != 0) return;
   IcpState& st = state[p];
@@ -225,7 +334,9 @@ __global__ __launch_bounds__(256) void icp_finalize_kernel(const IcpDesc* __rest
   }
   // Umeyama without scaling on the sums centred on d.centre: H = sum p' q'^T - sum p' (sum q')^T / n
   double U[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
-  if (cnt > 0) {
+  if (kPlane && d.method == kIcpMethodPlane) {
+    if (cnt > 0) icp_plane_step(tot, d.centre, U);
+  } else if (cnt > 0) {
     double mp[3], mq[3], H[9], R[9];
     for (int r = 0; r < 3; ++r) {
       mp[r] = tot[2 + r] / cnt;
@@ -285,11 +396,19 @@ void launch_icp_index(hipStream_t s, const IcpDesc* d_desc, const int32_t* d_tbl
 
 void launch_icp_iteration(hipStream_t s, const IcpDesc* d_desc, IcpState* d_state, const int32_t* d_blk_prob,
                           int n_blk, int batch, double* d_x, const double* d_qs, const int32_t* d_qj,
-                          const int32_t* d_bstart, int32_t* d_match, double* d_partials) {
+                          const int32_t* d_bstart, const double* d_normals, bool plane, int32_t* d_match,
+                          double* d_partials) {
+  if (plane) {  // at least one point-to-plane problem: the wider partials, the method read per block
+    if (n_blk > 0)
+      hipLaunchKernelGGL(icp_corr_kernel<true>, dim3(n_blk), dim3(kIcpBlock), 0, s, d_desc, d_state, d_blk_prob,
+                         d_x, d_qs, d_qj, d_bstart, d_normals, d_match, d_partials);
+    hipLaunchKernelGGL(icp_finalize_kernel<true>, dim3(batch), dim3(256), 0, s, d_desc, d_state, d_partials);
+    return;
+  }
   if (n_blk > 0)
-    hipLaunchKernelGGL(icp_corr_kernel, dim3(n_blk), dim3(kIcpBlock), 0, s, d_desc, d_state, d_blk_prob, d_x, d_qs,
-                       d_qj, d_bstart, d_match, d_partials);
-  hipLaunchKernelGGL(icp_finalize_kernel, dim3(batch), dim3(256), 0, s, d_desc, d_state, d_partials);
+    hipLaunchKernelGGL(icp_corr_kernel<false>, dim3(n_blk), dim3(kIcpBlock), 0, s, d_desc, d_state, d_blk_prob, d_x,
+                       d_qs, d_qj, d_bstart, d_normals, d_match, d_partials);
+  hipLaunchKernelGGL(icp_finalize_kernel<false>, dim3(batch), dim3(256), 0, s, d_desc, d_state, d_partials);
 }
 
 void launch_icp_live(hipStream_t s, const IcpState* d_state, int batch, int32_t* d_live) {

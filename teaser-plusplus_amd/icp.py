@@ -1,7 +1,9 @@
-"""Point-to-point ICP refinement on the GPU with Open3D's interface (``o3d.pipelines.registration``):
+"""ICP refinement on the GPU with Open3D's interface (``o3d.pipelines.registration``):
 ``registration_icp(source, target, max_correspondence_distance, init, estimation_method, criteria)`` and the batched
 ``registration_icp_batch``.  The semantics are those of Open3D's RegistrationICP with
-TransformationEstimationPointToPoint(with_scaling=False), written out in include/teaser_hip.h ("ICP refinement").
+TransformationEstimationPointToPoint(with_scaling=False) or TransformationEstimationPointToPlane(kernel) (target
+normals given by the caller, robust kernels L2 / Huber / Cauchy / GM / Tukey), written out in include/teaser_hip.h
+("ICP refinement").
 
 One library handle is kept per device between calls (no HIP context per call); calls from several threads are safe --
 each handle has a lock, so calls for one device run one after the other.  device=-1 means the calling thread's
@@ -27,6 +29,10 @@ class IcpResultC(C.Structure):
                 ("iterations", C.c_int32), ("n_correspondences", C.c_int32)]
 
 
+class IcpEstimationC(C.Structure):
+    _fields_ = [("method", C.c_int32), ("kernel", C.c_int32), ("kernel_k", C.c_double)]
+
+
 def declare(L):
     """ctypes signatures of the ICP entry points (called by the package's lib())."""
     L.teaser_hip_icp_params_default.argtypes = [C.POINTER(IcpParamsC)]
@@ -38,6 +44,9 @@ def declare(L):
                                        C.POINTER(IcpParamsC), C.POINTER(IcpResultC), C.POINTER(_ip)]
     L.teaser_hip_icp_solve.argtypes = [_vp, _dp, C.c_int32, _dp, C.c_int32, _dp, C.POINTER(IcpParamsC),
                                        C.POINTER(IcpResultC), _ip]
+    L.teaser_hip_icp_estimation_default.argtypes = [C.POINTER(IcpEstimationC)]
+    L.teaser_hip_icp_batch_ex.argtypes = L.teaser_hip_icp_batch.argtypes + [C.POINTER(_dp), C.POINTER(IcpEstimationC)]
+    L.teaser_hip_icp_solve_ex.argtypes = L.teaser_hip_icp_solve.argtypes + [_dp, C.POINTER(IcpEstimationC)]
 
 
 class ICPConvergenceCriteria:
@@ -61,6 +70,58 @@ class TransformationEstimationPointToPoint:
         if with_scaling:
             raise ValueError("TransformationEstimationPointToPoint(with_scaling=True) is not supported")
         self.with_scaling = False
+
+
+class _RobustKernel:
+    """Open3D's RobustKernel: the weight w(r) a point-to-plane residual r enters the normal equations with."""
+    code = 0
+
+    def __init__(self, k=1.0):
+        self.k = float(k)
+
+    def __repr__(self):
+        return "%s(k=%g)" % (type(self).__name__, self.k)
+
+
+class L2Loss(_RobustKernel):
+    """w = 1 (no parameter)."""
+
+    def __init__(self):
+        super().__init__(1.0)
+
+    def __repr__(self):
+        return "L2Loss()"
+
+
+class HuberLoss(_RobustKernel):
+    """w = 1 if |r| <= k else k / |r|."""
+    code = 1
+
+
+class CauchyLoss(_RobustKernel):
+    """w = 1 / (1 + (r / k)^2)."""
+    code = 2
+
+
+class GMLoss(_RobustKernel):
+    """w = k / (k + r^2)^2."""
+    code = 3
+
+
+class TukeyLoss(_RobustKernel):
+    """w = (1 - (r / k)^2)^2 if |r| <= k else 0."""
+    code = 4
+
+
+class TransformationEstimationPointToPlane:
+    """Open3D's point-to-plane estimation with an optional robust kernel (default L2Loss).  The target normals are
+    given to registration_icp(..., target_normals=...)."""
+
+    def __init__(self, kernel=None):
+        kernel = L2Loss() if kernel is None else kernel
+        if not isinstance(kernel, _RobustKernel):
+            raise ValueError("kernel must be L2Loss, HuberLoss, CauchyLoss, GMLoss or TukeyLoss")
+        self.kernel = kernel
 
 
 class RegistrationResult:
@@ -152,9 +213,22 @@ def _params(r, criteria):
     return IcpParamsC(float(r), int(c.max_iteration), float(c.relative_fitness), float(c.relative_rmse))
 
 
-def registration_icp_batch(sources, targets, max_correspondence_distance, inits=None, criteria=None, device=-1):
+def _estimation(m):
+    """(method, kernel, k) codes of one estimation method; None is point-to-point."""
+    if m is None or isinstance(m, TransformationEstimationPointToPoint):
+        return 0, 0, 1.0
+    if isinstance(m, TransformationEstimationPointToPlane):
+        return 1, m.kernel.code, m.kernel.k
+    raise ValueError("estimation_method must be TransformationEstimationPointToPoint(with_scaling=False) or "
+                     "TransformationEstimationPointToPlane(kernel)")
+
+
+def registration_icp_batch(sources, targets, max_correspondence_distance, inits=None, criteria=None, device=-1,
+                           estimation_methods=None, target_normals=None):
     """One launch sequence for many independent problems (mixed sizes allowed).  max_correspondence_distance and
-    criteria: one value for all or one per problem; inits: None (identity), one 4 x 4 for all, or one per problem.
+    criteria: one value for all or one per problem; inits: None (identity), one 4 x 4 for all, or one per problem;
+    estimation_methods: None (point-to-point), one for all or one per problem; target_normals: None, or one entry per
+    problem (None for a point-to-point problem, else one normal per target point).
     Returns a list of RegistrationResult, each identical to the same problem run alone."""
     from . import TeaserHipError, lib
     srcs = [_cloud(s, "source") for s in sources]
@@ -162,6 +236,25 @@ def registration_icp_batch(sources, targets, max_correspondence_distance, inits=
     b = len(srcs)
     if len(dsts) != b:
         raise ValueError("sources and targets differ in length (%d vs %d)" % (b, len(dsts)))
+    ests = estimation_methods if isinstance(estimation_methods, (list, tuple)) else [estimation_methods] * b
+    if len(ests) != b:
+        raise ValueError("estimation_methods: one per problem or one for all")
+    ests = [_estimation(m) for m in ests]
+    plane = any(m[0] == 1 for m in ests)
+    normals = [None] * b
+    if plane:
+        if target_normals is None or len(target_normals) != b:
+            raise ValueError("point-to-plane needs target_normals: one entry per problem")
+        for k in range(b):
+            if ests[k][0] != 1:
+                continue
+            if target_normals[k] is None:
+                raise ValueError("point-to-plane needs target_normals (problem %d)" % k)
+            nv = _cloud(target_normals[k], "target_normals")
+            if nv.shape != dsts[k].shape:
+                raise ValueError("target_normals must have the target's shape %s, got %s (problem %d)"
+                                 % (dsts[k].shape, nv.shape, k))
+            normals[k] = nv
     rs = np.broadcast_to(np.asarray(max_correspondence_distance, dtype=np.float64), (b,))
     crit = criteria if isinstance(criteria, (list, tuple)) else [criteria] * b
     if len(crit) != b:
@@ -183,9 +276,15 @@ def registration_icp_batch(sources, targets, max_correspondence_distance, inits=
     corr = [np.zeros((max(int(n), 1), 2), dtype=np.int32) for n in n_s]
     cp = (_ip * max(b, 1))(*[c.ctypes.data_as(_ip) for c in corr])
     out = (IcpResultC * max(b, 1))()
+    args = (h, b, sp, n_s.ctypes.data_as(_ip), tp, n_t.ctypes.data_as(_ip),
+            None if init is None else init.ctypes.data_as(_dp), params, out, cp)
     with lock:  # the handle serves one call at a time
-        rc = L.teaser_hip_icp_batch(h, b, sp, n_s.ctypes.data_as(_ip), tp, n_t.ctypes.data_as(_ip),
-                                    None if init is None else init.ctypes.data_as(_dp), params, out, cp)
+        if plane:
+            nptr = (_dp * max(b, 1))(*[None if nv is None else nv.ctypes.data_as(_dp) for nv in normals])
+            est = (IcpEstimationC * max(b, 1))(*[IcpEstimationC(*m) for m in ests])
+            rc = L.teaser_hip_icp_batch_ex(*args, nptr, est)
+        else:  # point-to-point only: the original entry point
+            rc = L.teaser_hip_icp_batch(*args)
         err = L.teaser_hip_icp_last_error(h).decode() if rc != 0 else ""
     if rc != 0:
         raise TeaserHipError(rc, err)
@@ -199,10 +298,17 @@ def registration_icp_batch(sources, targets, max_correspondence_distance, inits=
 
 
 def registration_icp(source, target, max_correspondence_distance, init=np.eye(4), estimation_method=None,
-                     criteria=None, device=-1):
-    """Open3D's registration_icp (same argument order) for TransformationEstimationPointToPoint(False): refines
-    `init` so that it maps source onto target.  source / target: n x 3 points (np.asarray(pcd.points))."""
-    if estimation_method is not None and not isinstance(estimation_method, TransformationEstimationPointToPoint):
-        raise ValueError("only TransformationEstimationPointToPoint(with_scaling=False) is supported")
+                     criteria=None, device=-1, *, target_normals=None):
+    """Open3D's registration_icp (same argument order): refines `init` so that it maps source onto target.
+    source / target: n x 3 points (np.asarray(pcd.points)).  estimation_method: None or
+    TransformationEstimationPointToPoint() (with_scaling=False), or TransformationEstimationPointToPlane(kernel), which
+    needs target_normals (n_t x 3, np.asarray(target_pcd.normals))."""
+    if estimation_method is not None and not isinstance(
+            estimation_method, (TransformationEstimationPointToPoint, TransformationEstimationPointToPlane)):
+        raise ValueError("only TransformationEstimationPointToPoint(with_scaling=False) and "
+                         "TransformationEstimationPointToPlane(kernel) are supported")
+    if isinstance(estimation_method, TransformationEstimationPointToPlane) and target_normals is None:
+        raise ValueError("TransformationEstimationPointToPlane needs target_normals")
     return registration_icp_batch([source], [target], max_correspondence_distance, inits=_init(init)[None],
-                                  criteria=[criteria], device=device)[0]
+                                  criteria=[criteria], device=device, estimation_methods=[estimation_method],
+                                  target_normals=None if target_normals is None else [target_normals])[0]
