@@ -6,10 +6,14 @@ nearest-neighbour correspondences -> TEASER++ registration -> optional DRS certi
 on the MI355X.  Usage:
 
     python examples/teaser_python_fpfh.py [src.ply dst.ply] [--voxel 0.05] [--certify] [--icp [--icp-iterations 100]]
-                                          [--icp-plane [--icp-kernel tukey --icp-kernel-k K]]
+                                          [--icp-plane [--icp-kernel tukey --icp-kernel-k K]] [--batch K]
 
 --icp-plane refines with point-to-plane ICP instead, on the target normals the FPFH stage already computed
 (rows PCL leaves non-finite, below 3 neighbours, set to zero: they contribute nothing), optionally with a robust kernel.
+
+--batch K registers K perturbed copies of the pair (each moved by a seeded random rigid transform and jittered by a
+tenth of a voxel) through the four batched stages, one call each: voxel_down_sample_batch -> correspondences_batch ->
+solve_batch -> registration_icp_batch, and prints the wall time of every stage.
 
 Without file arguments it runs BASELINE config 5 from tests/golden/config5_clouds.npz (the 3DMatch pair
 cloud_bin_0 / cloud_bin_4 after a 0.05 voxel grid); with two PLY files (ASCII or binary little-endian, float x y z)
@@ -45,6 +49,50 @@ def read_ply_xyz(path):
         return np.stack([data["x"], data["y"], data["z"]], axis=1).astype(np.float32)
 
 
+def run_batch(A, B, vox, K, icp_iterations):
+    """K perturbed copies of the pair (A, B) through the batched stages, one call per stage."""
+    rng = np.random.default_rng(555)
+    srcs, dsts = [], []
+    for _ in range(K):
+        q = rng.standard_normal(4)
+        w, x, y, z = q / np.linalg.norm(q)
+        Rm = np.array([[1 - 2 * (y * y + z * z), 2 * (x * y - z * w), 2 * (x * z + y * w)],
+                       [2 * (x * y + z * w), 1 - 2 * (x * x + z * z), 2 * (y * z - x * w)],
+                       [2 * (x * z - y * w), 2 * (y * z + x * w), 1 - 2 * (x * x + y * y)]])
+        srcs.append((A + 0.1 * vox * rng.standard_normal(A.shape) - rng.uniform(-1, 1, 3)) @ Rm)
+        dsts.append(B + 0.1 * vox * rng.standard_normal(B.shape))
+    params = tp.RobustRegistrationSolver.Params(noise_bound=vox, cbar2=1.0, estimate_scaling=False,
+                                                rotation_gnc_factor=1.4, rotation_max_iterations=10000,
+                                                rotation_cost_threshold=1e-16)               # helpers.py:45-60
+    solver = tp.RobustRegistrationSolver(params)
+    crit = tp.ICPConvergenceCriteria(max_iteration=icp_iterations)
+    for timed in (False, True):  # the first pass creates the handles and grows the arenas
+        t0 = time.perf_counter()
+        down = tp.voxel_down_sample_batch(srcs + dsts, vox)
+        t1 = time.perf_counter()
+        sp, dp = down[:K], down[K:]
+        corr = tp.correspondences_batch(sp, dp, 2 * vox, 5 * vox)   # helpers.py:9-43 for every pair
+        t2 = time.perf_counter()
+        if min(map(len, corr)) < 3:
+            sys.exit("pair %d has %d correspondences: nothing to register" % (int(np.argmin([len(c) for c in corr])),
+                                                                              min(map(len, corr))))
+        sols = solver.solve_batch([sp[k][corr[k][:, 0]].T for k in range(K)], [dp[k][corr[k][:, 1]].T for k in range(K)])
+        t3 = time.perf_counter()
+        inits = []
+        for sol in sols:
+            T = np.eye(4)
+            T[:3, :3], T[:3, 3] = sol.rotation, sol.translation
+            inits.append(T)
+        icp = tp.registration_icp_batch(sp, dp, vox, inits, crit)
+        t4 = time.perf_counter()
+    print("%d pairs: %d .. %d points after down-sampling, %d .. %d correspondences"
+          % (K, min(map(len, down)), max(map(len, down)), min(map(len, corr)), max(map(len, corr))))
+    print("down-sampling %.1f ms, front-end %.1f ms, registration %.1f ms, ICP %.1f ms (one call each, second pass)"
+          % (1e3 * (t1 - t0), 1e3 * (t2 - t1), 1e3 * (t3 - t2), 1e3 * (t4 - t3)))
+    print("ICP fitness %.4f .. %.4f, rmse %.4f .. %.4f" % (min(r.fitness for r in icp), max(r.fitness for r in icp),
+                                                         min(r.inlier_rmse for r in icp), max(r.inlier_rmse for r in icp)))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("clouds", nargs="*")
@@ -56,7 +104,16 @@ def main():
                     help="refine the TEASER++ pose with point-to-plane ICP on the FPFH stage's target normals")
     ap.add_argument("--icp-kernel", choices=["l2", "huber", "cauchy", "gm", "tukey"], default="l2")
     ap.add_argument("--icp-kernel-k", type=float, default=None, help="kernel parameter (default: the voxel size)")
+    ap.add_argument("--batch", type=int, default=0, metavar="K",
+                    help="register K perturbed copies of the pair through the batched stages")
     a = ap.parse_args()
+    if a.batch > 0:
+        if len(a.clouds) == 2:
+            A, B = (read_ply_xyz(c).astype(np.float64) for c in a.clouds)
+        else:
+            c5 = np.load(os.path.join(ROOT, "tests", "golden", "config5_clouds.npz"))
+            A, B, a.voxel = c5["cloud_bin_0"].astype(np.float64), c5["cloud_bin_4"].astype(np.float64), float(c5["voxel_size"])
+        return run_batch(A, B, a.voxel, a.batch, a.icp_iterations)
     t_ds = None
     if len(a.clouds) == 2:
         raw = [read_ply_xyz(c).astype(np.float64) for c in a.clouds]

@@ -36,6 +36,7 @@ class FPFHEstimation {
   FPFHEstimation& operator=(const FPFHEstimation&) = delete;
   ~FPFHEstimation() {
     if (h_) teaser_hip_solver_destroy(h_);
+    if (fh_) teaser_hip_features_destroy(fh_);
   }
 
   // fpfh.h:40-42, fpfh.cc:15-43: normals with a radius search (viewpoint at the origin), then FPFH.
@@ -66,9 +67,50 @@ class FPFHEstimation {
   // fpfh.h:56: the normals used by the last computeFPFHFeatures
   NormalCloud getNormals() { return normals_; }
 
+  // computeFPFHFeatures for many clouds in one launch sequence (teaser_hip_features_fpfh_batch; no counterpart in
+  // the reference): one FPFHCloud per input cloud, each bit-identical to the single-cloud call.  Clouds of mixed
+  // sizes and empty clouds are allowed.
+  std::vector<FPFHCloud> computeFPFHFeaturesBatch(const std::vector<PointCloud>& input_clouds,
+                                                  double normal_search_radius = 0.03,
+                                                  double fpfh_search_radius = 0.05) {
+    if (!fh_) {
+      const int32_t rc = teaser_hip_features_create(/*device=*/-1, &fh_);
+      if (rc != TEASER_HIP_OK) {
+        fh_ = nullptr;
+        throw std::runtime_error("teaser::FPFHEstimation: teaser_hip_features_create failed (status " +
+                                 std::to_string(rc) + "; 3 = no HIP device)");
+      }
+    }
+    const size_t batch = input_clouds.size();
+    std::vector<FPFHCloud> out(batch);
+    batch_normals_.assign(batch, NormalCloud());
+    std::vector<const float*> pts(batch);
+    std::vector<float*> feat(batch), nrm(batch);
+    std::vector<int32_t> n(batch);
+    const std::vector<double> rn(batch, normal_search_radius), rf(batch, fpfh_search_radius);
+    for (size_t b = 0; b < batch; ++b) {
+      n[b] = (int32_t)input_clouds[b].size();
+      out[b].resize((size_t)n[b]);
+      batch_normals_[b].assign((size_t)n[b], Normal());
+      pts[b] = reinterpret_cast<const float*>(input_clouds[b].data());
+      feat[b] = reinterpret_cast<float*>(out[b].data());
+      nrm[b] = reinterpret_cast<float*>(batch_normals_[b].data());
+    }
+    const int32_t rc = teaser_hip_features_fpfh_batch(fh_, (int32_t)batch, pts.data(), n.data(), rn.data(), rf.data(),
+                                                      feat.data(), nrm.data());
+    if (rc != TEASER_HIP_OK)
+      throw std::runtime_error(std::string("teaser_hip_features_fpfh_batch status ") + std::to_string(rc) + ": " +
+                               teaser_hip_features_last_error(fh_));
+    return out;
+  }
+  // the normals used by the last computeFPFHFeaturesBatch, per cloud
+  const std::vector<NormalCloud>& getNormalsBatch() const { return batch_normals_; }
+
  private:
   teaser_hip_solver* h_ = nullptr;
+  teaser_hip_features* fh_ = nullptr;
   NormalCloud normals_;
+  std::vector<NormalCloud> batch_normals_;
 };
 
 }  // namespace teaser

@@ -27,6 +27,7 @@ class Matcher {
   Matcher& operator=(const Matcher&) = delete;
   ~Matcher() {
     if (h_) teaser_hip_solver_destroy(h_);
+    if (fh_) teaser_hip_features_destroy(fh_);
   }
 
   // matcher.h:40-44: (source index, target index) pairs, sorted, unique
@@ -67,8 +68,62 @@ class Matcher {
     return out;
   }
 
+  // calculateCorrespondences for many pairs in one launch sequence (teaser_hip_features_match_batch; no counterpart
+  // in the reference): per pair the list one call per pair returns.  The tuple test, when asked for, runs per pair
+  // through the same host routine.
+  std::vector<std::vector<std::pair<int, int>>> calculateCorrespondencesBatch(
+      const std::vector<PointCloud>& source_points, const std::vector<PointCloud>& target_points,
+      const std::vector<FPFHCloud>& source_features, const std::vector<FPFHCloud>& target_features,
+      bool use_absolute_scale = true, bool use_crosscheck = true, bool use_tuple_test = true, float tuple_scale = 0) {
+    (void)use_absolute_scale;
+    const size_t batch = source_features.size();
+    const bool tuple = use_tuple_test && tuple_scale != 0;
+    if (target_features.size() != batch || (tuple && (source_points.size() != batch || target_points.size() != batch)))
+      throw std::invalid_argument("teaser::Matcher::calculateCorrespondencesBatch: lists of different lengths");
+    if (!fh_) {
+      const int32_t rc = teaser_hip_features_create(/*device=*/-1, &fh_);
+      if (rc != TEASER_HIP_OK) {
+        fh_ = nullptr;
+        throw std::runtime_error("teaser::Matcher: teaser_hip_features_create failed (status " + std::to_string(rc) +
+                                 "; 3 = no HIP device)");
+      }
+    }
+    std::vector<std::vector<std::pair<int, int>>> out(batch);
+    std::vector<const float*> fs(batch), ft(batch);
+    std::vector<int32_t*> pairs(batch);
+    std::vector<int32_t> ns(batch), nt(batch);
+    std::vector<int64_t> cap(batch), cnt(batch, 0);
+    for (size_t b = 0; b < batch; ++b) {
+      ns[b] = (int32_t)source_features[b].size();
+      nt[b] = (int32_t)target_features[b].size();
+      out[b].resize((size_t)ns[b] + (size_t)nt[b] + 1);
+      cap[b] = (int64_t)out[b].size();
+      fs[b] = reinterpret_cast<const float*>(source_features[b].data());
+      ft[b] = reinterpret_cast<const float*>(target_features[b].data());
+      pairs[b] = reinterpret_cast<int32_t*>(out[b].data());
+    }
+    const int32_t rc = teaser_hip_features_match_batch(fh_, (int32_t)batch, fs.data(), ns.data(), ft.data(), nt.data(),
+                                                       33, use_crosscheck ? 1 : 0, pairs.data(), cap.data(),
+                                                       cnt.data());
+    if (rc != TEASER_HIP_OK)
+      throw std::runtime_error(std::string("teaser_hip_features_match_batch status ") + std::to_string(rc) + ": " +
+                               teaser_hip_features_last_error(fh_));
+    for (size_t b = 0; b < batch; ++b) {
+      if (tuple) {
+        const int32_t rt = teaser_hip_tuple_test(
+            nullptr, reinterpret_cast<const float*>(source_points[b].data()), (int32_t)source_points[b].size(),
+            reinterpret_cast<const float*>(target_points[b].data()), (int32_t)target_points[b].size(), tuple_scale,
+            /*seed=*/0, pairs[b], &cnt[b]);
+        if (rt != TEASER_HIP_OK) throw std::runtime_error("teaser_hip_tuple_test status " + std::to_string(rt));
+      }
+      out[b].resize((size_t)cnt[b]);
+    }
+    return out;
+  }
+
  private:
   teaser_hip_solver* h_ = nullptr;
+  teaser_hip_features* fh_ = nullptr;
 };
 
 }  // namespace teaser

@@ -556,6 +556,52 @@ TEASER_HIP_API int32_t teaser_hip_voxel_down_sample(teaser_hip_voxel* voxel, con
                                                     double voxel_size, double* out, int64_t* n_out, int32_t* counts,
                                                     int32_t* voxel_of_point);
 
+/* Batched correspondence front-end: teaser_hip_compute_fpfh and teaser_hip_match_features (see "Correspondence
+ * front-end" above for the arithmetic, which is theirs bit for bit) for a BATCH of clouds / pairs per call, on its OWN
+ * handle (nothing is shared with teaser_hip_solver).  Problems of mixed sizes share the launches; radii are given per
+ * problem.  A call waits for its stream (hipStreamSynchronize) a fixed number of times whatever the batch: twice where
+ * FPFH is computed, once for matching alone.  The copies of requested features / normals into the caller's arrays, and
+ * of the features match_batch reads from them, are one per problem and additional.  Neighbour lists that would exceed
+ * an internal budget (4 GiB per wave of clouds) are built in several waves inside the call, with the same results.
+ * n = 0 clouds, empty sides (zero pairs) and batch = 0 are valid.  TEASER_HIP_ERR_BAD_ARG
+ * (teaser_hip_features_last_error names the argument and the problem index) for a negative n, a NULL pointer where
+ * n > 0, a radius that is not finite and > 0, dim outside [1, 64], a pair_cap[b] that is too small (n_pairs[b] then
+ * holds the count needed, for every problem) and non-finite features that leave a query without a nearest neighbour.
+ * The handle stays usable after a refusal.  Results are deterministic: the same bits run to run, and for a problem
+ * alone or inside any batch.  A handle is not re-entrant (one call at a time; distinct handles are independent). */
+typedef struct teaser_hip_features teaser_hip_features;
+/* device < 0: the current HIP device.  TEASER_HIP_ERR_NO_DEVICE without a GPU. */
+TEASER_HIP_API int32_t teaser_hip_features_create(int32_t device, teaser_hip_features** out);
+TEASER_HIP_API int32_t teaser_hip_features_destroy(teaser_hip_features* features);
+TEASER_HIP_API const char* teaser_hip_features_last_error(const teaser_hip_features* features);
+/* DIAGNOSTIC (exists for the tests of the wave splitting; may be removed): the budgets of one wave in bytes, each
+ * <= 0 for its default -- list_bytes: neighbour lists of a wave of clouds (4 GiB); part_bytes: partial nearest-
+ * neighbour results of a wave of pairs (1 GiB).  Small values force a call into many waves; no value changes a result. */
+TEASER_HIP_API int32_t teaser_hip_features_set_budgets(teaser_hip_features* features, int64_t list_bytes,
+                                                       int64_t part_bytes);
+/* FPFH of `batch` clouds.  cloud[b]: n[b] x 3 floats; fpfh_out[b]: n[b] x 33 floats; normals_out: NULL, or per cloud
+ * NULL or n[b] x 3 floats. */
+TEASER_HIP_API int32_t teaser_hip_features_fpfh_batch(teaser_hip_features* features, int32_t batch,
+                                                      const float* const* cloud, const int32_t* n,
+                                                      const double* normal_radius, const double* fpfh_radius,
+                                                      float* const* fpfh_out, float* const* normals_out);
+/* Matching of `batch` feature pairs.  src_feat[b]: n_src[b] x dim floats, dst_feat[b] likewise; pairs[b]: room for
+ * pair_cap[b] (src, dst) pairs (n_src[b] + n_dst[b] always suffices); n_pairs[b] receives the count. */
+TEASER_HIP_API int32_t teaser_hip_features_match_batch(teaser_hip_features* features, int32_t batch,
+                                                       const float* const* src_feat, const int32_t* n_src,
+                                                       const float* const* dst_feat, const int32_t* n_dst,
+                                                       int32_t dim, int32_t use_crosscheck, int32_t* const* pairs,
+                                                       const int64_t* pair_cap, int64_t* n_pairs);
+/* Clouds in, correspondences out: FPFH of both clouds of every pair, then matching, the features staying on the
+ * device in between.  Optional outputs (each array NULL, or per pair NULL or room for the side's n x 33 features /
+ * n x 3 normals). */
+TEASER_HIP_API int32_t teaser_hip_features_correspondences_batch(
+    teaser_hip_features* features, int32_t batch, const float* const* src_xyz, const int32_t* n_src,
+    const float* const* dst_xyz, const int32_t* n_dst, const double* normal_radius, const double* fpfh_radius,
+    int32_t use_crosscheck, int32_t* const* pairs, const int64_t* pair_cap, int64_t* n_pairs,
+    float* const* src_feat_out, float* const* dst_feat_out, float* const* src_normals_out,
+    float* const* dst_normals_out);
+
 /* Page-locked host memory from the HIP runtime THIS library runs on.  teaser_hip_submit_batch(..., INPUT_HOST) moves
  * the points with one DMA copy per cloud, at PCIe speed only when the runtime knows the pages are locked.  A buffer
  * pinned by another HIP runtime instance in the same process (e.g. the one a Python framework bundles) is pageable

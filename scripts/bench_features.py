@@ -1,0 +1,124 @@
+#!/usr/bin/env python3
+"""Measures the batched correspondence front-end (teaser-plusplus_amd.correspondences_batch / compute_fpfh_batch /
+match_features_batch) against the single-call path in the same process and run, and prints ONE JSON object:
+  single_pair   one config-5 pair (tests/golden/config5_clouds.npz, radii 2 and 5 voxels): the single-call path
+                (FPFHEstimation.computeFPFHFeatures x 2 + Matcher.calculateCorrespondences) vs correspondences_batch
+                with batch = 1
+  batch64       64 perturbed config-5 pairs (the generator of bench.py's config-5 workload): correspondences_batch in
+                one call vs the same 64 pairs through the single-call path one after the other
+  stages64      compute_fpfh_batch (128 clouds) and match_features_batch (64 pairs) separately on the same 64
+  fixture       the object / scene pair of tests/golden/features_golden.npz (1 000 / 60 865 points, radii 0.02 and
+                0.04 as the reference's matcher test), both ways: two single-call pairs vs one call of two pairs
+The object also records the board's name, the ROCm version and the commit (None outside a git checkout).
+Wall-clock medians over --reps synchronous calls after --warmup calls; ms_min / ms_max give the spread.  Usage:
+    python scripts/bench_features.py [--reps 20] [--warmup 3]"""
+import argparse
+import ctypes
+import importlib
+import json
+import os
+import subprocess
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+from features_batch_cases import config5_pairs  # noqa: E402
+
+tp = importlib.import_module("teaser-plusplus_amd")
+
+
+def timed(fn, reps, warmup):
+    for _ in range(warmup):
+        fn()
+    ts = []
+    for _ in range(reps):
+        t0 = time.perf_counter()
+        fn()
+        ts.append(time.perf_counter() - t0)
+    return dict(ms=1e3 * float(np.median(ts)), ms_min=1e3 * min(ts), ms_max=1e3 * max(ts), reps=reps)
+
+
+def board_and_rocm():
+    """(device name and architecture as the HIP runtime reports them, ROCm version of the installation the runtime was loaded from)."""
+    name = ctypes.create_string_buffer(256)
+    try:
+        hip = ctypes.CDLL("libamdhip64.so")
+        board = name.value.decode() if hip.hipDeviceGetName(name, 256, 0) == 0 else ""
+    except OSError:
+        board = ""
+    try:  # (the marketing name is empty where the driver's id table is missing: the architecture then)
+        import torch
+        arch = torch.cuda.get_device_properties(0).gcnArchName.split(":")[0]
+        board = ("%s (%s)" % (board, arch)) if board else arch
+    except Exception:
+        pass
+    board = board or None
+    rocm = None
+    for line in open("/proc/self/maps"):
+        if "libamdhip64" in line:
+            root = os.path.dirname(os.path.dirname(os.path.realpath(line.split()[-1])))
+            try:
+                rocm = open(os.path.join(root, ".info", "version")).read().strip()
+            except OSError:
+                pass
+            break
+    return board, rocm
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reps", type=int, default=20)
+    ap.add_argument("--warmup", type=int, default=3)
+    a = ap.parse_args()
+    if tp.device_count() < 1:
+        sys.exit("bench_features.py needs an MI355X")
+    src, dst, vox = config5_pairs(64)
+    rn, rf = 2 * vox, 5 * vox
+    est, matcher = tp.FPFHEstimation(), tp.Matcher()
+
+    def single(s, d, rn=rn, rf=rf):
+        fa = est.computeFPFHFeatures(s, rn, rf)
+        fb = est.computeFPFHFeatures(d, rn, rf)
+        return matcher.calculateCorrespondences(s, d, fa, fb, False, True, False, 0)
+
+    C5 = np.load(os.path.join(ROOT, "tests", "golden", "config5_clouds.npz"))
+    A, B = C5["cloud_bin_0"], C5["cloud_bin_4"]
+    res = {"workload": "FPFH (radii 2 and 5 voxels) + mutual nearest neighbours, config-5 pairs (%d / %d points)"
+                       % (len(A), len(B))}
+    res["board"], res["rocm_version"] = board_and_rocm()
+    try:
+        res["commit"] = subprocess.run(["git", "-C", ROOT, "rev-parse", "--short", "HEAD"], capture_output=True,
+                                       text=True).stdout.strip() or None
+    except OSError:
+        res["commit"] = None
+    one = timed(lambda: single(A, B), a.reps, a.warmup)
+    b1 = timed(lambda: tp.correspondences_batch([A], [B], rn, rf), a.reps, a.warmup)
+    res["single_pair"] = dict(single_call=one, batch1=b1, batch1_over_single_call=b1["ms"] / one["ms"],
+                              batch1_minus_single_call_ms=b1["ms"] - one["ms"],
+                              single_call_spread_ms=one["ms_max"] - one["ms_min"])
+    seq = timed(lambda: [single(s, d) for s, d in zip(src, dst)], a.reps, a.warmup)
+    bat = timed(lambda: tp.correspondences_batch(src, dst, rn, rf), a.reps, a.warmup)
+    res["batch64"] = dict(sequential=seq, batched=bat, speedup=seq["ms"] / bat["ms"],
+                          saved_ms=seq["ms"] - bat["ms"], sequential_spread_ms=seq["ms_max"] - seq["ms_min"],
+                          sequential_ms_per_pair=seq["ms"] / 64, batched_ms_per_pair=bat["ms"] / 64)
+    feats = tp.compute_fpfh_batch(src + dst, rn, rf)
+    res["stages64"] = dict(fpfh_batch_128_clouds=timed(lambda: tp.compute_fpfh_batch(src + dst, rn, rf), a.reps, a.warmup),
+                           match_batch_64_pairs=timed(lambda: tp.match_features_batch(feats[:64], feats[64:]), a.reps,
+                                                      a.warmup))
+    G = np.load(os.path.join(ROOT, "tests", "golden", "features_golden.npz"))
+    obj, scene = G["matcher_object"], G["matcher_scene"]
+    reps = max(a.reps // 4, 3)
+    frn, frf = 0.02, 0.04
+    res["fixture"] = dict(points=[len(obj), len(scene)], radii=[frn, frf],
+                          single_call=timed(lambda: (single(obj, scene, frn, frf), single(scene, obj, frn, frf)), reps, 1),
+                          batched=timed(lambda: tp.correspondences_batch([obj, scene], [scene, obj], frn, frf), reps, 1))
+    res["fixture"]["speedup"] = res["fixture"]["single_call"]["ms"] / res["fixture"]["batched"]["ms"]
+    print(json.dumps(res))
+
+
+if __name__ == "__main__":
+    main()

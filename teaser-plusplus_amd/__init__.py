@@ -134,6 +134,9 @@ EXPORTED_SYMBOLS = [
     "teaser_hip_icp_solve_ex",
     "teaser_hip_voxel_create", "teaser_hip_voxel_destroy", "teaser_hip_voxel_last_error",
     "teaser_hip_voxel_down_sample_batch", "teaser_hip_voxel_down_sample",
+    "teaser_hip_features_create", "teaser_hip_features_destroy", "teaser_hip_features_last_error",
+    "teaser_hip_features_set_budgets", "teaser_hip_features_fpfh_batch", "teaser_hip_features_match_batch",
+    "teaser_hip_features_correspondences_batch",
 ]
 
 
@@ -218,6 +221,8 @@ def lib():
     _icp.declare(L)
     from . import voxel as _voxel
     _voxel.declare(L)
+    from . import features as _features
+    _features.declare(L)
     _lib = L
     return L
 
@@ -801,6 +806,7 @@ class FPFHEstimation:
 
     def __init__(self, device=-1):
         self._solver = RobustRegistrationSolver(device=device)
+        self._device = device
         self._normals = None
 
     def computeFPFHFeatures(self, input_cloud, normal_search_radius=0.03, fpfh_search_radius=0.05):
@@ -817,6 +823,15 @@ class FPFHEstimation:
     def getNormals(self):  # fpfh.h:56
         return self._normals
 
+    def computeFPFHFeaturesBatch(self, input_clouds, normal_search_radius=0.03, fpfh_search_radius=0.05):
+        """computeFPFHFeatures for a list of clouds in one launch sequence (features.compute_fpfh_batch): the list of
+        n_b x 33 float32 features, bit-identical to one call per cloud; getNormals() then returns the list of normals.
+        The radii: one value for all clouds or one per cloud."""
+        from . import features
+        out, self._normals = features.compute_fpfh_batch(input_clouds, normal_search_radius, fpfh_search_radius,
+                                                         device=self._device, return_normals=True)
+        return out
+
 
 class Matcher:
     """teaser::Matcher (reference teaser/include/teaser/matcher.h:20-61, teaser/src/matcher.cc:21-301) on
@@ -824,6 +839,7 @@ class Matcher:
 
     def __init__(self, device=-1):
         self._solver = RobustRegistrationSolver(device=device)
+        self._device = device
 
     def calculateCorrespondences(self, source_points, target_points, source_features, target_features,
                                  use_absolute_scale=True, use_crosscheck=True, use_tuple_test=True,
@@ -844,6 +860,21 @@ class Matcher:
         if use_tuple_test and tuple_scale != 0:
             return tuple_test(source_points, target_points, out[:cnt.value], tuple_scale, tuple_seed)
         return [tuple(int(v) for v in row) for row in out[:cnt.value]]
+
+    def calculateCorrespondencesBatch(self, source_points, target_points, source_features, target_features,
+                                      use_absolute_scale=True, use_crosscheck=True, use_tuple_test=True,
+                                      tuple_scale=0.0, tuple_seed=0):
+        """calculateCorrespondences for lists of clouds / feature arrays in one launch sequence
+        (features.match_features_batch): per pair the list of (src, dst) tuples one call per pair returns."""
+        from . import features
+        pairs = features.match_features_batch(source_features, target_features, use_crosscheck,
+                                              device=self._device)
+        if use_tuple_test and tuple_scale != 0:
+            features._same_length(source_points, pairs, "source_points", "source_features")
+            features._same_length(target_points, pairs, "target_points", "target_features")
+            return [tuple_test(source_points[k], target_points[k], pairs[k], tuple_scale, tuple_seed)
+                    for k in range(len(pairs))]
+        return [[tuple(int(v) for v in row) for row in p] for p in pairs]
 
 
 def tuple_test(source_points, target_points, pairs, tuple_scale, seed=0):
@@ -1002,10 +1033,12 @@ from .icp import (CauchyLoss, GMLoss, HuberLoss, ICPConvergenceCriteria, L2Loss,
                   TransformationEstimationPointToPlane, TransformationEstimationPointToPoint, TukeyLoss,
                   registration_icp, registration_icp_batch)
 from .voxel import voxel_down_sample, voxel_down_sample_batch  # noqa: E402
+from .features import compute_fpfh_batch, correspondences_batch, match_features_batch  # noqa: E402
 
 __all__ = ["batched", "FPFHEstimation", "Matcher", "MultiDeviceSolver", "RobustRegistrationSolver", "RegistrationSolution", "RotationEstimationAlgorithm",
            "InlierSelectionMode", "InlierGraphFormulation", "TeaserHipError", "synth_problem",
            "device_count", "build", "lib", "LIB_PATH", "EXPORTED_SYMBOLS", "certifier_warmup", "PinnedArray",
            "ICPConvergenceCriteria", "TransformationEstimationPointToPoint", "RegistrationResult", "registration_icp",
            "registration_icp_batch", "voxel_down_sample", "voxel_down_sample_batch",
+           "compute_fpfh_batch", "match_features_batch", "correspondences_batch",
            "TransformationEstimationPointToPlane", "L2Loss", "HuberLoss", "CauchyLoss", "GMLoss", "TukeyLoss"]

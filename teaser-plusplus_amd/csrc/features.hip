@@ -1,0 +1,585 @@
+// features.hip -- host side of the batched correspondence front-end (include/teaser_hip.h, "Batched correspondence
+// front-end"): its own handle, argument validation, the descriptor tables and the launch sequence of the segmented
+// kernels at the end of kernels_features.hip.
+//
+// FPFH of a batch of clouds.  The points of all clouds are packed one after the other; every radius block and every
+// point finds its cloud through a block -> cloud / point -> cloud map and the descriptor table.
+//   1. count pass for BOTH radii over the whole batch, one scan workgroup per cloud and radius, then ONE small copy of
+//      {list total, longest list} per cloud and radius and the first host synchronisation;
+//   2. the host cuts the clouds into waves whose lists fit the list budget (one wave, normally), sizes the list buffer
+//      once, uploads the list base of every cloud and turns the cloud-local offsets into 64-bit offsets into the
+//      wave's list;
+//   3. per wave, stream-ordered and without a host round trip: fill + sort of the normal-radius lists, normals; then
+//      per wave fill + sort of the FPFH-radius lists, SPFH, FPFH;
+//   4. the copies of the outputs and the second (last) synchronisation.
+// Matching a batch of feature pairs: two searches per pair in one launch, the results of all searches in one copy, one
+// synchronisation, then the O(n) index bookkeeping per pair on the host.  A call therefore waits for the stream
+// (hipStreamSynchronize) 2 times (FPFH, clouds -> correspondences) or once (matching), whatever the batch and the
+// number of waves.  Features and normals the caller asked for, and the features match_batch takes from the host, are
+// copied per problem between the device and the caller's own (pageable) arrays: those copies are additional.
+#include <math.h>
+#include <string.h>
+
+#include <algorithm>
+#include <climits>
+#include <string>
+#include <vector>
+
+#include "features_internal.h"
+#include "internal.h"
+#include "teaser_hip.h"
+
+using namespace thip;
+
+namespace {
+
+// Neighbour lists (8 bytes per neighbour) of one wave of clouds; a wave always holds at least one cloud.  The rank
+// sort of lists longer than the LDS sort's capacity needs a scratch copy of the same size when it is used.
+constexpr int64_t kFeatListBudgetBytes = (int64_t)4 << 30;
+// Partial results (8 bytes per query and data chunk) of one wave of pairs.
+constexpr int64_t kFeatPartBudgetBytes = (int64_t)1 << 30;
+
+struct DevBuf {
+  void* p = nullptr;
+  size_t cap = 0;
+  bool ensure(size_t bytes) {
+    if (bytes <= cap) return true;
+    if (p) (void)hipFree(p);
+    p = nullptr;
+    cap = 0;
+    const size_t want = std::max<size_t>(bytes + bytes / 4, 256);
+    if (hipMalloc(&p, want) != hipSuccess) return false;
+    cap = want;
+    return true;
+  }
+  void release() {
+    if (p) (void)hipFree(p);
+    p = nullptr;
+    cap = 0;
+  }
+  template <typename T>
+  T* as() const { return static_cast<T*>(p); }
+};
+
+// page-locked staging (the packed points going in, the small data-dependent results coming back)
+struct HostBuf {
+  void* p = nullptr;
+  size_t cap = 0;
+  bool ensure(size_t bytes) {
+    if (bytes <= cap) return true;
+    if (p) (void)hipHostFree(p);
+    p = nullptr;
+    cap = 0;
+    const size_t want = std::max<size_t>(bytes + bytes / 4, 256);
+    if (hipHostMalloc(&p, want, hipHostMallocDefault) != hipSuccess) return false;
+    cap = want;
+    return true;
+  }
+  void release() {
+    if (p) (void)hipHostFree(p);
+    p = nullptr;
+    cap = 0;
+  }
+  template <typename T>
+  T* as() const { return static_cast<T*>(p); }
+};
+
+enum { B_DESC, B_BLK, B_PT_CLOUD, B_PTS, B_COUNTS, B_OFFSETS, B_CURSOR, B_META, B_BASE, B_LIST, B_LIST2, B_NORMALS,
+       B_SPFH, B_FEAT, B_SEARCH, B_SBLK, B_PART_D, B_PART_I, B_NN, B_MFEAT, B_COUNT_OF_BUFS };
+enum { H_PTS, H_META, H_NN, H_COUNT_OF_BUFS };
+
+struct Wave {
+  int c0, c1;  // clouds (or pairs) [c0, c1)
+};
+
+}  // namespace
+
+struct teaser_hip_features {
+  int device = 0;
+  hipStream_t stream = nullptr;
+  DevBuf buf[B_COUNT_OF_BUFS];
+  HostBuf host[H_COUNT_OF_BUFS];
+  int64_t list_budget = kFeatListBudgetBytes;
+  int64_t part_budget = kFeatPartBudgetBytes;
+  std::string err;
+  // host tables of the call in flight (kept here so that they outlive their asynchronous uploads)
+  std::vector<FeatCloudDesc> desc;
+  std::vector<int32_t> blk_cloud, pt_cloud, blk_search;
+  std::vector<int64_t> base;
+  std::vector<FeatSearchDesc> search;
+};
+
+namespace {
+
+int32_t fail(teaser_hip_features* h, int32_t status, const std::string& msg) {
+  h->err = msg;
+  return status;
+}
+
+int32_t hip_fail(teaser_hip_features* h, hipError_t e, const char* what) {
+  h->err = std::string(what) + ": " + hipGetErrorString(e);
+  return TEASER_HIP_ERR_HIP;
+}
+
+std::string at(int b) { return " (problem " + std::to_string(b) + ")"; }
+
+#define FCHK(h, call, what)                                   \
+  do {                                                        \
+    const hipError_t e_ = (call);                             \
+    if (e_ != hipSuccess) return hip_fail((h), e_, (what));   \
+  } while (0)
+#define FENSURE(h, b, bytes) \
+  do {                       \
+    if (!(b).ensure(bytes)) return fail((h), TEASER_HIP_ERR_OOM, "allocation failed (front-end buffers)"); \
+  } while (0)
+
+int32_t check_radius(teaser_hip_features* h, const double* r, const char* name, int b) {
+  const double v = r[b];
+  const float r2 = (float)(v * v);
+  if (!std::isfinite(v) || !(v > 0) || !std::isfinite(r2) || !(r2 > 0))
+    return fail(h, TEASER_HIP_ERR_BAD_ARG, std::string(name) + " must be finite and > 0" + at(b));
+  return TEASER_HIP_OK;
+}
+
+// Checks `nc` clouds (problem index reported = c / per_problem) and builds the descriptor tables.
+int32_t validate_clouds(teaser_hip_features* h, int nc, int per_problem, const float* const* cloud, const char* const* names,
+                        const int32_t* const* n, const double* normal_radius, const double* fpfh_radius) {
+  h->desc.assign((size_t)nc, FeatCloudDesc{});
+  int64_t total = 0, blocks = 0;
+  const int chunk = feat_radius_chunk();
+  for (int c = 0; c < nc; ++c) {
+    const int b = c / per_problem, side = c % per_problem;
+    const int32_t nb = n[side][b];
+    int32_t rc = check_radius(h, normal_radius, "normal_radius", b);
+    if (rc == TEASER_HIP_OK) rc = check_radius(h, fpfh_radius, "fpfh_radius", b);
+    if (rc != TEASER_HIP_OK) return rc;
+    if (nb < 0) return fail(h, TEASER_HIP_ERR_BAD_ARG, std::string("n must be >= 0 for ") + names[side] + at(b));
+    if (nb > 0 && (!cloud || !cloud[c]))
+      return fail(h, TEASER_HIP_ERR_BAD_ARG, std::string(names[side]) + " is NULL" + at(b));
+    FeatCloudDesc& d = h->desc[(size_t)c];
+    d.off = total;
+    d.n = nb;
+    d.blk_off = (int32_t)blocks;
+    d.qblocks = (nb + 63) / 64;
+    d.r2[0] = (float)(normal_radius[b] * normal_radius[b]);  // pcl::KdTreeFLANN::radiusSearch: static_cast<float>(r * r)
+    d.r2[1] = (float)(fpfh_radius[b] * fpfh_radius[b]);
+    total += nb;
+    blocks += (int64_t)d.qblocks * ((nb + chunk - 1) / chunk);
+    if (total >= INT32_MAX || blocks >= INT32_MAX)
+      return fail(h, TEASER_HIP_ERR_UNSUPPORTED, "too many points in one call" + at(b));
+  }
+  return TEASER_HIP_OK;
+}
+
+int64_t cloud_blocks(const FeatCloudDesc& d) {
+  const int chunk = feat_radius_chunk();
+  return (int64_t)d.qblocks * ((d.n + chunk - 1) / chunk);
+}
+
+// FPFH of the clouds described by h->desc (cloud[c]: n x 3 floats): features in B_FEAT, normals in B_NORMALS, packed.
+// One host synchronisation; everything after it is only enqueued.
+int32_t run_fpfh(teaser_hip_features* h, const float* const* cloud) {
+  const int nc = (int)h->desc.size();
+  const int64_t T = nc ? h->desc.back().off + h->desc.back().n : 0;
+  if (T == 0) return TEASER_HIP_OK;
+  const int n_blk = (int)(h->desc.back().blk_off + cloud_blocks(h->desc.back()));
+  hipStream_t s = h->stream;
+  DevBuf* B = h->buf;
+
+  h->blk_cloud.resize((size_t)n_blk);
+  h->pt_cloud.resize((size_t)T);
+  for (int c = 0; c < nc; ++c) {
+    const FeatCloudDesc& d = h->desc[(size_t)c];
+    std::fill_n(h->blk_cloud.begin() + d.blk_off, cloud_blocks(d), c);
+    std::fill_n(h->pt_cloud.begin() + d.off, d.n, c);
+  }
+  FENSURE(h, B[B_DESC], sizeof(FeatCloudDesc) * (size_t)nc);
+  FENSURE(h, B[B_BLK], 4 * (size_t)n_blk);
+  FENSURE(h, B[B_PT_CLOUD], 4 * (size_t)T);
+  FENSURE(h, B[B_PTS], 12 * (size_t)T);
+  FENSURE(h, B[B_COUNTS], 2 * 4 * (size_t)T);
+  FENSURE(h, B[B_OFFSETS], 2 * 8 * (size_t)T);
+  FENSURE(h, B[B_CURSOR], 4 * (size_t)T);
+  FENSURE(h, B[B_META], 2 * 16 * (size_t)nc);
+  FENSURE(h, B[B_BASE], 2 * 8 * (size_t)nc);
+  FENSURE(h, B[B_NORMALS], 12 * (size_t)T);
+  FENSURE(h, B[B_SPFH], 33 * 4 * (size_t)T);
+  FENSURE(h, B[B_FEAT], 33 * 4 * (size_t)T);
+  FENSURE(h, h->host[H_PTS], 12 * (size_t)T);
+  FENSURE(h, h->host[H_META], 2 * 16 * (size_t)nc);
+
+  for (int c = 0; c < nc; ++c) {
+    const FeatCloudDesc& d = h->desc[(size_t)c];
+    if (d.n > 0) memcpy(h->host[H_PTS].as<float>() + 3 * d.off, cloud[c], 12 * (size_t)d.n);
+  }
+  const FeatCloudDesc* d_desc = B[B_DESC].as<FeatCloudDesc>();
+  const int32_t* d_blk = B[B_BLK].as<int32_t>();
+  const int32_t* d_ptc = B[B_PT_CLOUD].as<int32_t>();
+  const float* d_pts = B[B_PTS].as<float>();
+  FCHK(h, hipMemcpyAsync(B[B_DESC].p, h->desc.data(), sizeof(FeatCloudDesc) * (size_t)nc, hipMemcpyHostToDevice, s),
+       "hipMemcpyAsync (descriptors)");
+  FCHK(h, hipMemcpyAsync(B[B_BLK].p, h->blk_cloud.data(), 4 * (size_t)n_blk, hipMemcpyHostToDevice, s),
+       "hipMemcpyAsync (block map)");
+  FCHK(h, hipMemcpyAsync(B[B_PT_CLOUD].p, h->pt_cloud.data(), 4 * (size_t)T, hipMemcpyHostToDevice, s),
+       "hipMemcpyAsync (point map)");
+  FCHK(h, hipMemcpyAsync(B[B_PTS].p, h->host[H_PTS].p, 12 * (size_t)T, hipMemcpyHostToDevice, s),
+       "hipMemcpyAsync (points)");
+
+  // ---- 1. counts and scans for both radii, one copy of the totals ----
+  FCHK(h, hipMemsetAsync(B[B_COUNTS].p, 0, 2 * 4 * (size_t)T, s), "hipMemsetAsync (counts)");
+  for (int w = 0; w < 2; ++w) {
+    launch_feat_radius_count_batch(s, d_desc, d_blk, 0, n_blk, w, d_pts, B[B_COUNTS].as<int32_t>() + w * T);
+    launch_feat_scan_batch(s, d_desc, nc, B[B_COUNTS].as<int32_t>() + w * T, B[B_OFFSETS].as<int64_t>() + w * T,
+                           B[B_META].as<int64_t>() + (size_t)w * 2 * nc);
+  }
+  FCHK(h, hipGetLastError(), "front-end kernel launch (counts)");
+  const int64_t* meta = h->host[H_META].as<int64_t>();
+  FCHK(h, hipMemcpyAsync(h->host[H_META].p, B[B_META].p, 2 * 16 * (size_t)nc, hipMemcpyDeviceToHost, s),
+       "hipMemcpyAsync (list totals)");
+  FCHK(h, hipStreamSynchronize(s), "hipStreamSynchronize (list totals)");
+
+  // ---- 2. waves of clouds per radius, list bases, one allocation ----
+  const int64_t budget = h->list_budget / feat_nbr_bytes();
+  std::vector<Wave> waves[2];
+  std::vector<char> wave_long[2];
+  h->base.assign(2 * (size_t)nc, 0);
+  int64_t list_cap = 1;
+  bool any_long = false;
+  for (int w = 0; w < 2; ++w) {
+    int c0 = 0;
+    int64_t acc = 0;
+    bool lng = false;
+    for (int c = 0; c < nc; ++c) {
+      const int64_t tot = meta[(size_t)w * 2 * nc + 2 * c], mx = meta[(size_t)w * 2 * nc + 2 * c + 1];
+      if (c > c0 && acc + tot > budget) {
+        waves[w].push_back(Wave{c0, c});
+        wave_long[w].push_back(lng);
+        c0 = c;
+        acc = 0;
+        lng = false;
+      }
+      h->base[(size_t)w * nc + c] = acc;
+      acc += tot;
+      lng |= mx > feat_sort_capacity();
+      list_cap = std::max(list_cap, acc);
+    }
+    waves[w].push_back(Wave{c0, nc});
+    wave_long[w].push_back(lng);
+    for (char l : wave_long[w]) any_long |= l != 0;
+  }
+  FENSURE(h, B[B_LIST], (size_t)list_cap * (size_t)feat_nbr_bytes());
+  if (any_long) FENSURE(h, B[B_LIST2], (size_t)list_cap * (size_t)feat_nbr_bytes());
+  FCHK(h, hipMemcpyAsync(B[B_BASE].p, h->base.data(), 2 * 8 * (size_t)nc, hipMemcpyHostToDevice, s),
+       "hipMemcpyAsync (list bases)");
+  for (int w = 0; w < 2; ++w)
+    launch_feat_rebase(s, d_ptc, B[B_BASE].as<int64_t>() + (size_t)w * nc, T, B[B_OFFSETS].as<int64_t>() + w * T);
+
+  // ---- 3. per radius and wave: lists, then what consumes them ----
+  for (int w = 0; w < 2; ++w) {
+    FCHK(h, hipMemsetAsync(B[B_CURSOR].p, 0, 4 * (size_t)T, s), "hipMemsetAsync (cursor)");
+    const int32_t* counts = B[B_COUNTS].as<int32_t>() + w * T;
+    const int64_t* offsets = B[B_OFFSETS].as<int64_t>() + w * T;
+    for (size_t k = 0; k < waves[w].size(); ++k) {
+      const FeatCloudDesc& first = h->desc[(size_t)waves[w][k].c0];
+      const FeatCloudDesc& last = h->desc[(size_t)waves[w][k].c1 - 1];
+      const int blk0 = first.blk_off, blk1 = (int)(last.blk_off + cloud_blocks(last));
+      const int64_t pt0 = first.off, pt1 = last.off + last.n;
+      launch_feat_lists_batch(s, d_desc, d_blk, blk0, blk1 - blk0, w, pt0, pt1, d_pts, counts,
+                              B[B_CURSOR].as<int32_t>(), offsets, B[B_LIST].p,
+                              wave_long[w][k] ? B[B_LIST2].p : nullptr);
+      if (w == 0)
+        launch_feat_normals_batch(s, d_desc, d_ptc, pt0, pt1, d_pts, offsets, counts, B[B_LIST].p,
+                                  B[B_NORMALS].as<float>());
+      else
+        launch_feat_fpfh_batch(s, d_desc, d_ptc, pt0, pt1, d_pts, B[B_NORMALS].as<float>(), offsets, counts,
+                               B[B_LIST].p, B[B_SPFH].as<float>(), B[B_FEAT].as<float>());
+    }
+  }
+  FCHK(h, hipGetLastError(), "front-end kernel launch (features)");
+  return TEASER_HIP_OK;
+}
+
+// Enqueues the copy of a packed per-point device array (`width` floats per point) into the per-cloud host arrays.
+int32_t copy_out(teaser_hip_features* h, const float* d_packed, int width, float* const* out, int first, int stride) {
+  if (!out) return TEASER_HIP_OK;
+  for (size_t c = (size_t)first, b = 0; c < h->desc.size(); c += (size_t)stride, ++b) {
+    const FeatCloudDesc& d = h->desc[c];
+    if (d.n > 0 && out[b])
+      FCHK(h, hipMemcpyAsync(out[b], d_packed + (size_t)width * d.off, 4 * (size_t)width * d.n, hipMemcpyDeviceToHost,
+                             h->stream),
+           "hipMemcpyAsync (outputs)");
+  }
+  return TEASER_HIP_OK;
+}
+
+int32_t validate_match_outputs(teaser_hip_features* h, int32_t batch, int32_t* const* pairs, const int64_t* pair_cap,
+                               int64_t* n_pairs) {
+  if (!pair_cap) return fail(h, TEASER_HIP_ERR_BAD_ARG, "pair_cap must not be NULL");
+  if (!n_pairs) return fail(h, TEASER_HIP_ERR_BAD_ARG, "n_pairs must not be NULL");
+  for (int b = 0; b < batch; ++b) {
+    if (pair_cap[b] < 0) return fail(h, TEASER_HIP_ERR_BAD_ARG, "pair_cap must be >= 0" + at(b));
+    if (pair_cap[b] > 0 && (!pairs || !pairs[b])) return fail(h, TEASER_HIP_ERR_BAD_ARG, "pairs is NULL" + at(b));
+  }
+  return TEASER_HIP_OK;
+}
+
+// Matches `batch` pairs whose features are rows of d_feat (src_row[b], dst_row[b] = first row of each side), copies
+// the nearest-neighbour indices back, synchronises ONCE and writes the pair lists.
+int32_t run_match(teaser_hip_features* h, int32_t batch, const float* d_feat, const int64_t* src_row,
+                  const int64_t* dst_row, const int32_t* n_src, const int32_t* n_dst, int dim, bool use_crosscheck,
+                  int32_t* const* pairs, const int64_t* pair_cap, int64_t* n_pairs) {
+  hipStream_t s = h->stream;
+  DevBuf* B = h->buf;
+  for (int b = 0; b < batch; ++b) n_pairs[b] = 0;
+  // two searches per pair with both sides non-empty (matcher.cc:123-133: i = the larger cloud, j = the smaller one):
+  // search 2k: for every j its nearest i (:162);  search 2k + 1: for every i its nearest j (:165)
+  h->search.clear();
+  std::vector<int> pair_of;       // pair index of searches 2k, 2k + 1
+  std::vector<Wave> waves;        // in units of k
+  std::vector<int> wave_blk0;
+  int64_t nn_total = 0, blocks = 0, part_acc = 0, part_cap = 1;
+  const int64_t part_budget = h->part_budget / 8;
+  int k0 = 0;
+  for (int b = 0; b < batch; ++b) {
+    if (n_src[b] == 0 || n_dst[b] == 0) continue;
+    const bool swapped = n_dst[b] > n_src[b];
+    const int ni = swapped ? n_dst[b] : n_src[b], nj = swapped ? n_src[b] : n_dst[b];
+    const int64_t ri = swapped ? dst_row[b] : src_row[b], rj = swapped ? src_row[b] : dst_row[b];
+    const int64_t pa = (int64_t)feat_nn_chunks(ni) * nj, pb = (int64_t)feat_nn_chunks(nj) * ni;
+    const int k = (int)pair_of.size();
+    if (k > k0 && part_acc + pa + pb > part_budget) {
+      waves.push_back(Wave{k0, k});
+      k0 = k;
+      part_acc = 0;
+    }
+    if (k == k0) wave_blk0.push_back((int)blocks);
+    FeatSearchDesc a{ri, rj, part_acc, nn_total, ni, nj, (int32_t)blocks, (nj + 63) / 64};
+    blocks += (int64_t)a.qblocks * feat_nn_chunks(ni);
+    FeatSearchDesc c{rj, ri, part_acc + pa, nn_total + nj, nj, ni, (int32_t)blocks, (ni + 63) / 64};
+    blocks += (int64_t)c.qblocks * feat_nn_chunks(nj);
+    if (blocks >= INT32_MAX) return fail(h, TEASER_HIP_ERR_UNSUPPORTED, "too many features in one call" + at(b));
+    part_acc += pa + pb;
+    part_cap = std::max(part_cap, part_acc);
+    nn_total += (int64_t)ni + nj;
+    h->search.push_back(a);
+    h->search.push_back(c);
+    pair_of.push_back(b);
+  }
+  const int nk = (int)pair_of.size();
+  if (nk > 0) {
+    waves.push_back(Wave{k0, nk});
+    h->blk_search.resize((size_t)blocks);
+    for (size_t q = 0; q < h->search.size(); ++q) {
+      const int32_t end = q + 1 < h->search.size() ? h->search[q + 1].blk_off : (int32_t)blocks;
+      std::fill(h->blk_search.begin() + h->search[q].blk_off, h->blk_search.begin() + end, (int32_t)q);
+    }
+    FENSURE(h, B[B_SEARCH], sizeof(FeatSearchDesc) * h->search.size());
+    FENSURE(h, B[B_SBLK], 4 * (size_t)blocks);
+    FENSURE(h, B[B_PART_D], 4 * (size_t)part_cap);
+    FENSURE(h, B[B_PART_I], 4 * (size_t)part_cap);
+    FENSURE(h, B[B_NN], 4 * (size_t)nn_total);
+    FENSURE(h, h->host[H_NN], 4 * (size_t)nn_total);
+    FCHK(h, hipMemcpyAsync(B[B_SEARCH].p, h->search.data(), sizeof(FeatSearchDesc) * h->search.size(),
+                           hipMemcpyHostToDevice, s),
+         "hipMemcpyAsync (search descriptors)");
+    FCHK(h, hipMemcpyAsync(B[B_SBLK].p, h->blk_search.data(), 4 * (size_t)blocks, hipMemcpyHostToDevice, s),
+         "hipMemcpyAsync (search block map)");
+    for (size_t w = 0; w < waves.size(); ++w) {
+      const int s0 = 2 * waves[w].c0, s1 = 2 * waves[w].c1;
+      const int blk0 = wave_blk0[w], blk1 = s1 < (int)h->search.size() ? h->search[(size_t)s1].blk_off : (int)blocks;
+      int max_nq = 0;
+      for (int q = s0; q < s1; ++q) max_nq = std::max(max_nq, h->search[(size_t)q].nq);
+      launch_feat_nn1_batch(s, B[B_SEARCH].as<FeatSearchDesc>(), B[B_SBLK].as<int32_t>(), blk0, blk1 - blk0, s0, s1,
+                            max_nq, d_feat, dim, B[B_PART_D].as<float>(), B[B_PART_I].as<int32_t>(),
+                            B[B_NN].as<int32_t>());
+    }
+    FCHK(h, hipGetLastError(), "front-end kernel launch (matching)");
+    FCHK(h, hipMemcpyAsync(h->host[H_NN].p, B[B_NN].p, 4 * (size_t)nn_total, hipMemcpyDeviceToHost, s),
+         "hipMemcpyAsync (nearest neighbours)");
+  }
+  FCHK(h, hipStreamSynchronize(s), "hipStreamSynchronize (results)");
+
+  int too_small = -1;
+  for (int k = 0; k < nk; ++k) {
+    const int b = pair_of[(size_t)k];
+    const FeatSearchDesc& a = h->search[2 * (size_t)k];
+    const int ni = a.nd, nj = a.nq;
+    const int32_t* j_to_i = h->host[H_NN].as<int32_t>() + a.nn_off;
+    const int32_t* i_nn = j_to_i + nj;
+    // A query whose distances are all NaN / +inf (non-finite features) has no nearest neighbour: the kernel reports
+    // -1.  FLANN would return garbage there; an error is the honest answer.
+    bool ok = true;
+    for (int j = 0; j < nj; ++j) ok &= j_to_i[j] >= 0 && j_to_i[j] < ni;
+    for (int i = 0; i < ni; ++i) ok &= i_nn[i] >= 0 && i_nn[i] < nj;
+    if (!ok)
+      return fail(h, TEASER_HIP_ERR_BAD_ARG, "non-finite feature values (no nearest neighbour for a point)" + at(b));
+    const auto corres = feat_match_pairs(j_to_i, nj, i_nn, ni, n_dst[b] > n_src[b], use_crosscheck);
+    n_pairs[b] = (int64_t)corres.size();
+    if ((int64_t)corres.size() > pair_cap[b]) {
+      if (too_small < 0) too_small = b;
+      continue;
+    }
+    for (size_t q = 0; q < corres.size(); ++q) {
+      pairs[b][2 * q] = corres[q].first;
+      pairs[b][2 * q + 1] = corres[q].second;
+    }
+  }
+  if (too_small >= 0)
+    return fail(h, TEASER_HIP_ERR_BAD_ARG, "pair_cap is too small: " + std::to_string(n_pairs[too_small]) +
+                                               " pairs needed" + at(too_small));
+  return TEASER_HIP_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int32_t teaser_hip_features_create(int32_t device, teaser_hip_features** out) {
+  if (!out) return TEASER_HIP_ERR_BAD_ARG;
+  *out = nullptr;
+  int count = 0;
+  if (hipGetDeviceCount(&count) != hipSuccess || count <= 0) return TEASER_HIP_ERR_NO_DEVICE;
+  if (device < 0 && hipGetDevice(&device) != hipSuccess) return TEASER_HIP_ERR_NO_DEVICE;
+  if (device >= count) return TEASER_HIP_ERR_BAD_ARG;
+  if (hipSetDevice(device) != hipSuccess) return TEASER_HIP_ERR_HIP;
+  teaser_hip_features* h = new teaser_hip_features();
+  h->device = device;
+  if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess) {
+    delete h;
+    return TEASER_HIP_ERR_HIP;
+  }
+  *out = h;
+  return TEASER_HIP_OK;
+}
+
+int32_t teaser_hip_features_destroy(teaser_hip_features* h) {
+  if (!h) return TEASER_HIP_OK;
+  (void)hipSetDevice(h->device);
+  if (h->stream) (void)hipStreamSynchronize(h->stream);
+  for (DevBuf& b : h->buf) b.release();
+  for (HostBuf& b : h->host) b.release();
+  if (h->stream) (void)hipStreamDestroy(h->stream);
+  delete h;
+  return TEASER_HIP_OK;
+}
+
+const char* teaser_hip_features_last_error(const teaser_hip_features* h) { return h ? h->err.c_str() : ""; }
+
+int32_t teaser_hip_features_set_budgets(teaser_hip_features* h, int64_t list_bytes, int64_t part_bytes) {
+  if (!h) return TEASER_HIP_ERR_BAD_ARG;
+  h->list_budget = list_bytes > 0 ? list_bytes : kFeatListBudgetBytes;
+  h->part_budget = part_bytes > 0 ? part_bytes : kFeatPartBudgetBytes;
+  return TEASER_HIP_OK;
+}
+
+int32_t teaser_hip_features_fpfh_batch(teaser_hip_features* h, int32_t batch, const float* const* cloud,
+                                       const int32_t* n, const double* normal_radius, const double* fpfh_radius,
+                                       float* const* fpfh_out, float* const* normals_out) {
+  if (!h) return TEASER_HIP_ERR_BAD_ARG;
+  h->err.clear();
+  if (batch < 0) return fail(h, TEASER_HIP_ERR_BAD_ARG, "batch must be >= 0");
+  if (batch == 0) return TEASER_HIP_OK;
+  if (!n) return fail(h, TEASER_HIP_ERR_BAD_ARG, "n must not be NULL");
+  if (!normal_radius) return fail(h, TEASER_HIP_ERR_BAD_ARG, "normal_radius must not be NULL");
+  if (!fpfh_radius) return fail(h, TEASER_HIP_ERR_BAD_ARG, "fpfh_radius must not be NULL");
+  const char* names[1] = {"cloud"};
+  const int32_t* ns[1] = {n};
+  int32_t rc = validate_clouds(h, batch, 1, cloud, names, ns, normal_radius, fpfh_radius);
+  if (rc != TEASER_HIP_OK) return rc;
+  for (int b = 0; b < batch; ++b)
+    if (n[b] > 0 && (!fpfh_out || !fpfh_out[b])) return fail(h, TEASER_HIP_ERR_BAD_ARG, "fpfh_out is NULL" + at(b));
+  FCHK(h, hipSetDevice(h->device), "hipSetDevice");
+  if ((rc = run_fpfh(h, cloud)) != TEASER_HIP_OK) return rc;
+  if (h->desc.back().off + h->desc.back().n == 0) return TEASER_HIP_OK;
+  if ((rc = copy_out(h, h->buf[B_FEAT].as<float>(), 33, fpfh_out, 0, 1)) != TEASER_HIP_OK) return rc;
+  if ((rc = copy_out(h, h->buf[B_NORMALS].as<float>(), 3, normals_out, 0, 1)) != TEASER_HIP_OK) return rc;
+  FCHK(h, hipStreamSynchronize(h->stream), "hipStreamSynchronize (results)");
+  return TEASER_HIP_OK;
+}
+
+int32_t teaser_hip_features_match_batch(teaser_hip_features* h, int32_t batch, const float* const* src_feat,
+                                        const int32_t* n_src, const float* const* dst_feat, const int32_t* n_dst,
+                                        int32_t dim, int32_t use_crosscheck, int32_t* const* pairs,
+                                        const int64_t* pair_cap, int64_t* n_pairs) {
+  if (!h) return TEASER_HIP_ERR_BAD_ARG;
+  h->err.clear();
+  if (batch < 0) return fail(h, TEASER_HIP_ERR_BAD_ARG, "batch must be >= 0");
+  if (dim <= 0 || dim > feat_nn_max_dim())
+    return fail(h, TEASER_HIP_ERR_BAD_ARG, "dim must be in [1, " + std::to_string(feat_nn_max_dim()) + "]");
+  if (batch == 0) return TEASER_HIP_OK;
+  if (!n_src || !n_dst) return fail(h, TEASER_HIP_ERR_BAD_ARG, "n_src / n_dst must not be NULL");
+  int32_t rc = validate_match_outputs(h, batch, pairs, pair_cap, n_pairs);
+  if (rc != TEASER_HIP_OK) return rc;
+  std::vector<int64_t> src_row((size_t)batch), dst_row((size_t)batch);
+  int64_t rows = 0;
+  for (int b = 0; b < batch; ++b) {
+    if (n_src[b] < 0 || n_dst[b] < 0) return fail(h, TEASER_HIP_ERR_BAD_ARG, "n_src / n_dst must be >= 0" + at(b));
+    const bool both = n_src[b] > 0 && n_dst[b] > 0;  // (an empty side: zero pairs, the other side is not read)
+    if (both && (!src_feat || !src_feat[b])) return fail(h, TEASER_HIP_ERR_BAD_ARG, "src_feat is NULL" + at(b));
+    if (both && (!dst_feat || !dst_feat[b])) return fail(h, TEASER_HIP_ERR_BAD_ARG, "dst_feat is NULL" + at(b));
+    src_row[(size_t)b] = rows;
+    rows += both ? n_src[b] : 0;
+    dst_row[(size_t)b] = rows;
+    rows += both ? n_dst[b] : 0;
+    if (rows >= INT32_MAX) return fail(h, TEASER_HIP_ERR_UNSUPPORTED, "too many features in one call" + at(b));
+  }
+  FCHK(h, hipSetDevice(h->device), "hipSetDevice");
+  FENSURE(h, h->buf[B_MFEAT], 4 * (size_t)std::max<int64_t>(rows, 1) * (size_t)dim);
+  float* d_feat = h->buf[B_MFEAT].as<float>();
+  for (int b = 0; b < batch; ++b) {
+    if (n_src[b] == 0 || n_dst[b] == 0) continue;
+    FCHK(h, hipMemcpyAsync(d_feat + (size_t)src_row[(size_t)b] * dim, src_feat[b], 4 * (size_t)n_src[b] * dim,
+                           hipMemcpyHostToDevice, h->stream),
+         "hipMemcpyAsync (features)");
+    FCHK(h, hipMemcpyAsync(d_feat + (size_t)dst_row[(size_t)b] * dim, dst_feat[b], 4 * (size_t)n_dst[b] * dim,
+                           hipMemcpyHostToDevice, h->stream),
+         "hipMemcpyAsync (features)");
+  }
+  return run_match(h, batch, d_feat, src_row.data(), dst_row.data(), n_src, n_dst, dim, use_crosscheck != 0, pairs,
+                   pair_cap, n_pairs);
+}
+
+int32_t teaser_hip_features_correspondences_batch(teaser_hip_features* h, int32_t batch, const float* const* src_xyz,
+                                                  const int32_t* n_src, const float* const* dst_xyz,
+                                                  const int32_t* n_dst, const double* normal_radius,
+                                                  const double* fpfh_radius, int32_t use_crosscheck,
+                                                  int32_t* const* pairs, const int64_t* pair_cap, int64_t* n_pairs,
+                                                  float* const* src_feat_out, float* const* dst_feat_out,
+                                                  float* const* src_normals_out, float* const* dst_normals_out) {
+  if (!h) return TEASER_HIP_ERR_BAD_ARG;
+  h->err.clear();
+  if (batch < 0) return fail(h, TEASER_HIP_ERR_BAD_ARG, "batch must be >= 0");
+  if (batch == 0) return TEASER_HIP_OK;
+  if (!n_src || !n_dst) return fail(h, TEASER_HIP_ERR_BAD_ARG, "n_src / n_dst must not be NULL");
+  if (!normal_radius) return fail(h, TEASER_HIP_ERR_BAD_ARG, "normal_radius must not be NULL");
+  if (!fpfh_radius) return fail(h, TEASER_HIP_ERR_BAD_ARG, "fpfh_radius must not be NULL");
+  int32_t rc = validate_match_outputs(h, batch, pairs, pair_cap, n_pairs);
+  if (rc != TEASER_HIP_OK) return rc;
+  // the clouds of the call, interleaved: cloud 2 b = source of pair b, cloud 2 b + 1 = its target
+  std::vector<const float*> cloud(2 * (size_t)batch);
+  for (int b = 0; b < batch; ++b) {
+    cloud[2 * (size_t)b] = src_xyz ? src_xyz[b] : nullptr;
+    cloud[2 * (size_t)b + 1] = dst_xyz ? dst_xyz[b] : nullptr;
+  }
+  const char* names[2] = {"src_xyz", "dst_xyz"};
+  const int32_t* ns[2] = {n_src, n_dst};
+  rc = validate_clouds(h, 2 * batch, 2, cloud.data(), names, ns, normal_radius, fpfh_radius);
+  if (rc != TEASER_HIP_OK) return rc;
+  FCHK(h, hipSetDevice(h->device), "hipSetDevice");
+  if ((rc = run_fpfh(h, cloud.data())) != TEASER_HIP_OK) return rc;
+  if (h->desc.back().off + h->desc.back().n > 0) {  // (features leave the device only where the caller asked)
+    if ((rc = copy_out(h, h->buf[B_FEAT].as<float>(), 33, src_feat_out, 0, 2)) != TEASER_HIP_OK) return rc;
+    if ((rc = copy_out(h, h->buf[B_FEAT].as<float>(), 33, dst_feat_out, 1, 2)) != TEASER_HIP_OK) return rc;
+    if ((rc = copy_out(h, h->buf[B_NORMALS].as<float>(), 3, src_normals_out, 0, 2)) != TEASER_HIP_OK) return rc;
+    if ((rc = copy_out(h, h->buf[B_NORMALS].as<float>(), 3, dst_normals_out, 1, 2)) != TEASER_HIP_OK) return rc;
+  }
+  std::vector<int64_t> src_row((size_t)batch), dst_row((size_t)batch);
+  for (int b = 0; b < batch; ++b) {
+    src_row[(size_t)b] = h->desc[2 * (size_t)b].off;
+    dst_row[(size_t)b] = h->desc[2 * (size_t)b + 1].off;
+  }
+  return run_match(h, batch, h->buf[B_FEAT].as<float>(), src_row.data(), dst_row.data(), n_src, n_dst, 33,
+                   use_crosscheck != 0, pairs, pair_cap, n_pairs);
+}
+
+}  // extern "C"

@@ -24,6 +24,7 @@
 // with -ffp-contract=off like the rest of the library: no product-add is fused by the compiler; the ONE place where the
 // reference's fixtures need fused multiply-adds -- the covariance accumulators of the normals -- says so explicitly.
 #include "internal.h"
+#include "features_internal.h"
 
 namespace thip {
 
@@ -89,16 +90,17 @@ constexpr int kFeatChunk = 512;
 
 // FILL == 0: counts[q] += |{ i in chunk : d2(q, i) < r2 }| (counts zeroed by the launcher);
 // FILL == 1: the chunk's neighbours (d2, i) into list[offset[q] + cursor[q] ...] (cursor zeroed by the launcher)
+// (the body of one workgroup: query block `qblock`, data chunk `chunk` of ONE cloud -- shared by the single-cloud
+// kernel and the batched one, which hands it the cloud's own pointers)
 template <int FILL>
-__global__ __launch_bounds__(64) void feat_radius_kernel(const float* __restrict__ pts, int n, float r2,
-                                                         int32_t* __restrict__ counts,
-                                                         const int64_t* __restrict__ offsets,
-                                                         Nbr* __restrict__ list) {
+__device__ __forceinline__ void feat_radius_block(const float* __restrict__ pts, int n, float r2,
+                                                  int32_t* __restrict__ counts, const int64_t* __restrict__ offsets,
+                                                  Nbr* __restrict__ list, int qblock, int chunk) {
   __shared__ float tile[kFeatChunk * 3];
-  const int q = blockIdx.x * 64 + threadIdx.x;
+  const int q = qblock * 64 + threadIdx.x;
   const bool live = q < n;
   const float qx = live ? pts[3 * q] : 0.f, qy = live ? pts[3 * q + 1] : 0.f, qz = live ? pts[3 * q + 2] : 0.f;
-  const int base = blockIdx.y * kFeatChunk;
+  const int base = chunk * kFeatChunk;
   const int m = min(kFeatChunk, n - base);
   for (int k = threadIdx.x; k < 3 * m; k += 64) tile[k] = pts[3 * base + k];
   __syncthreads();
@@ -120,11 +122,20 @@ __global__ __launch_bounds__(64) void feat_radius_kernel(const float* __restrict
     }
   }
 }
+template <int FILL>
+__global__ __launch_bounds__(64) void feat_radius_kernel(const float* __restrict__ pts, int n, float r2,
+                                                         int32_t* __restrict__ counts,
+                                                         const int64_t* __restrict__ offsets,
+                                                         Nbr* __restrict__ list) {
+  feat_radius_block<FILL>(pts, n, r2, counts, offsets, list, blockIdx.x, blockIdx.y);
+}
 
 // exclusive scan of the counts (one workgroup; n <= a few million) + the largest count
-__global__ __launch_bounds__(1024) void feat_scan_kernel(const int32_t* __restrict__ counts, int n,
-                                                         int64_t* __restrict__ offsets,
-                                                         int64_t* __restrict__ total_and_max) {
+// (one workgroup's scan of one cloud; END: also offsets[n] = total, as the single-cloud launcher promises)
+template <bool END>
+__device__ __forceinline__ void feat_scan_block(const int32_t* __restrict__ counts, int n,
+                                                int64_t* __restrict__ offsets,
+                                                int64_t* __restrict__ total_and_max) {
   __shared__ long long part[1024];
   __shared__ int pmax[1024];
   const int t = threadIdx.x;
@@ -157,7 +168,12 @@ __global__ __launch_bounds__(1024) void feat_scan_kernel(const int32_t* __restri
     offsets[i] = acc;
     acc += counts[i];
   }
-  if (t == 1023) offsets[n] = part[1023] + s;
+  if (END && t == 1023) offsets[n] = part[1023] + s;
+}
+__global__ __launch_bounds__(1024) void feat_scan_kernel(const int32_t* __restrict__ counts, int n,
+                                                         int64_t* __restrict__ offsets,
+                                                         int64_t* __restrict__ total_and_max) {
+  feat_scan_block<true>(counts, n, offsets, total_and_max);
 }
 
 // per point: bitonic sort of its list by (d2, idx) in LDS (one 256-thread workgroup per point)
@@ -271,13 +287,11 @@ __device__ __forceinline__ void feat_cross(const float* a, const float* b, float
   c[2] = a[0] * b[1] - a[1] * b[0];
 }
 
-__global__ __launch_bounds__(128) void feat_normals_kernel(const float* __restrict__ pts, int n,
-                                                           const int64_t* __restrict__ offsets,
-                                                           const int32_t* __restrict__ counts,
-                                                           const Nbr* __restrict__ list,
-                                                           float* __restrict__ normals) {
-  const int q = blockIdx.x * 128 + threadIdx.x;
-  if (q >= n) return;
+// (the normal of point q of one cloud: one thread; every pointer is that cloud's own)
+__device__ __forceinline__ void feat_normal_point(const float* __restrict__ pts, int q,
+                                                  const int64_t* __restrict__ offsets,
+                                                  const int32_t* __restrict__ counts, const Nbr* __restrict__ list,
+                                                  float* __restrict__ normals) {
   const int k = counts[q];
   float* out = normals + 3 * q;
   if (k < 3) {  // computePointNormal: too few neighbours
@@ -346,6 +360,15 @@ __global__ __launch_bounds__(128) void feat_normals_kernel(const float* __restri
   out[1] = nv[1];
   out[2] = nv[2];
 }
+__global__ __launch_bounds__(128) void feat_normals_kernel(const float* __restrict__ pts, int n,
+                                                           const int64_t* __restrict__ offsets,
+                                                           const int32_t* __restrict__ counts,
+                                                           const Nbr* __restrict__ list,
+                                                           float* __restrict__ normals) {
+  const int q = blockIdx.x * 128 + threadIdx.x;
+  if (q >= n) return;
+  feat_normal_point(pts, q, offsets, counts, list, normals);
+}
 
 // ---- SPFH / FPFH -----------------------------------------------------------------------------------
 // Eigen::Vector4f dot with a zero 4th component, in the order Eigen's SSE reduction adds the lane products
@@ -398,18 +421,18 @@ __device__ __forceinline__ int feat_bin(double x) {
 // the SAME float (incr) to one bin of each of the three histograms, so a bin's value is incr added count times
 // in float -- whatever the order of the neighbours: the lanes count into LDS, then lane b replays the additions
 // of bin b.  (One thread per point, the first version, was 79 waves on 1 024 SIMDs and 1.98 ms at n = 5 000.)
-__global__ __launch_bounds__(256) void feat_spfh_kernel(const float* __restrict__ pts,
-                                                        const float* __restrict__ normals, int n,
-                                                        const int64_t* __restrict__ offsets,
-                                                        const int32_t* __restrict__ counts,
-                                                        const Nbr* __restrict__ list, float* __restrict__ spfh) {
+// (wave w of the workgroup computes point p of one cloud -- or nothing when !live; the four waves of a workgroup may
+// serve different clouds, each with that cloud's own pointers.  Every wave reaches both barriers.)
+__device__ __forceinline__ void feat_spfh_point(const float* __restrict__ pts, const float* __restrict__ normals,
+                                                bool live, int p, const int64_t* __restrict__ offsets,
+                                                const int32_t* __restrict__ counts, const Nbr* __restrict__ list,
+                                                float* __restrict__ spfh) {
   __shared__ int bins[4][33];
   const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
-  const int p = blockIdx.x * 4 + w;
   if (lane < 33) bins[w][lane] = 0;
   __syncthreads();
-  const int k = p < n ? counts[p] : 0;
-  if (p < n) {
+  const int k = live ? counts[p] : 0;
+  if (live) {
     const Nbr* nb = list + offsets[p];
     const float d_pi = 1.0f / (2.0f * 3.14159274101257324f);  // 1.0f / (2.0f * static_cast<float>(M_PI))
     const double pi = 3.14159265358979323846;
@@ -428,13 +451,21 @@ __global__ __launch_bounds__(256) void feat_spfh_kernel(const float* __restrict_
     }
   }
   __syncthreads();
-  if (p < n && lane < 33) {
+  if (live && lane < 33) {
     const float incr = 100.0f / (float)(k - 1);
     const int c = bins[w][lane];
     float h = 0.0f;
     for (int i = 0; i < c; ++i) h += incr;
     spfh[(size_t)p * 33 + lane] = h;
   }
+}
+__global__ __launch_bounds__(256) void feat_spfh_kernel(const float* __restrict__ pts,
+                                                        const float* __restrict__ normals, int n,
+                                                        const int64_t* __restrict__ offsets,
+                                                        const int32_t* __restrict__ counts,
+                                                        const Nbr* __restrict__ list, float* __restrict__ spfh) {
+  const int p = blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  feat_spfh_point(pts, normals, p < n, p, offsets, counts, list, spfh);
 }
 
 // weightPointSPFHSignature: one wave per point, lane b = bin b; the neighbours in order of increasing distance
@@ -444,13 +475,11 @@ __global__ __launch_bounds__(256) void feat_spfh_kernel(const float* __restrict_
 // contributes +0, which leaves the non-negative sums unchanged bit for bit.  Neighbour records are wave-uniform
 // (scalar loads), fetched one block of kFpfhBlock ahead of the rows they index.
 constexpr int kFpfhBlock = 8;
-__global__ __launch_bounds__(256) void feat_fpfh_kernel(int n, const int64_t* __restrict__ offsets,
-                                                        const int32_t* __restrict__ counts,
-                                                        const Nbr* __restrict__ list,
-                                                        const float* __restrict__ spfh, float* __restrict__ out) {
-  const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
-  const int p = blockIdx.x * 4 + w;
-  if (p >= n) return;
+// (one wave: point p of one cloud, with that cloud's own pointers)
+__device__ __forceinline__ void feat_fpfh_point(int p, const int64_t* __restrict__ offsets,
+                                                const int32_t* __restrict__ counts, const Nbr* __restrict__ list,
+                                                const float* __restrict__ spfh, float* __restrict__ out) {
+  const int lane = threadIdx.x & 63;
   const int k = counts[p];
   const Nbr* nb = list + offsets[p];
   const int b = lane < 33 ? lane : 32;  // (lanes 33 .. 63 shadow bin 32; they do not store)
@@ -487,6 +516,14 @@ __global__ __launch_bounds__(256) void feat_fpfh_kernel(int n, const int64_t* __
   if (sum != 0) sum = 100.0f / sum;
   if (lane < 33) out[(size_t)p * 33 + lane] = o * sum;
 }
+__global__ __launch_bounds__(256) void feat_fpfh_kernel(int n, const int64_t* __restrict__ offsets,
+                                                        const int32_t* __restrict__ counts,
+                                                        const Nbr* __restrict__ list,
+                                                        const float* __restrict__ spfh, float* __restrict__ out) {
+  const int p = blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  if (p >= n) return;
+  feat_fpfh_point(p, offsets, counts, list, spfh, out);
+}
 
 // ---- exact L2 1-NN in `dim` dimensions (the matcher's two searches) -------------------------------
 // grid (query blocks of 64, data chunks of kNnChunk): a thread owns one query (its `dim` values staged in
@@ -501,16 +538,17 @@ __global__ __launch_bounds__(256) void feat_fpfh_kernel(int n, const int64_t* __
 constexpr int kNnChunk = 256;
 constexpr int kNnTile = 64;
 constexpr int kNnMaxDim = 64;
+// (the body of one workgroup: query block `qblock` against data chunk `chunk` of ONE search)
 template <int DIM>
-__global__ __launch_bounds__(64) void feat_nn_partial_kernel(const float* __restrict__ data, int nd,
-                                                             const float* __restrict__ query, int nq, int dim_rt,
-                                                             float* __restrict__ part_d,
-                                                             int32_t* __restrict__ part_i) {
+__device__ __forceinline__ void feat_nn_partial_block(const float* __restrict__ data, int nd,
+                                                      const float* __restrict__ query, int nq, int dim_rt,
+                                                      float* __restrict__ part_d, int32_t* __restrict__ part_i,
+                                                      int qblock, int chunk) {
   constexpr int kPad = DIM > 0 ? ((DIM + 3) & ~3) : kNnMaxDim;  // floats per staged point (16-byte rows)
   __shared__ __attribute__((aligned(16))) float tile[kNnTile * kPad];
   __shared__ float qs[DIM > 0 ? 1 : 64 * (kNnMaxDim + 1)];
   const int dim = DIM > 0 ? DIM : dim_rt;
-  const int q = blockIdx.x * 64 + threadIdx.x;
+  const int q = qblock * 64 + threadIdx.x;
   const bool live = q < nq;
   float qr[DIM > 0 ? kPad : 1];
   if (DIM > 0) {
@@ -519,7 +557,7 @@ __global__ __launch_bounds__(64) void feat_nn_partial_kernel(const float* __rest
   } else {
     for (int c = 0; c < dim; ++c) qs[threadIdx.x * (kNnMaxDim + 1) + c] = live ? query[(size_t)q * dim + c] : 0.f;
   }
-  const int lo = blockIdx.y * kNnChunk, hi = min(nd, lo + kNnChunk);
+  const int lo = chunk * kNnChunk, hi = min(nd, lo + kNnChunk);
   float best = __builtin_inff();
   int bi = -1;
   for (int base = lo; base < hi; base += kNnTile) {
@@ -562,15 +600,20 @@ __global__ __launch_bounds__(64) void feat_nn_partial_kernel(const float* __rest
     }
   }
   if (live) {
-    part_d[(size_t)blockIdx.y * nq + q] = best;
-    part_i[(size_t)blockIdx.y * nq + q] = bi;
+    part_d[(size_t)chunk * nq + q] = best;
+    part_i[(size_t)chunk * nq + q] = bi;
   }
 }
-__global__ __launch_bounds__(256) void feat_nn_final_kernel(const float* __restrict__ part_d,
-                                                            const int32_t* __restrict__ part_i, int nq,
-                                                            int chunks, int32_t* __restrict__ nn) {
-  const int q = blockIdx.x * 256 + threadIdx.x;
-  if (q >= nq) return;
+template <int DIM>
+__global__ __launch_bounds__(64) void feat_nn_partial_kernel(const float* __restrict__ data, int nd,
+                                                             const float* __restrict__ query, int nq, int dim_rt,
+                                                             float* __restrict__ part_d,
+                                                             int32_t* __restrict__ part_i) {
+  feat_nn_partial_block<DIM>(data, nd, query, nq, dim_rt, part_d, part_i, blockIdx.x, blockIdx.y);
+}
+__device__ __forceinline__ void feat_nn_final_query(const float* __restrict__ part_d,
+                                                    const int32_t* __restrict__ part_i, int nq, int chunks,
+                                                    int32_t* __restrict__ nn, int q) {
   float best = __builtin_inff();
   int bi = -1;
   for (int c = 0; c < chunks; ++c) {  // chunks in index order + strict <: the first minimum overall
@@ -581,6 +624,13 @@ __global__ __launch_bounds__(256) void feat_nn_final_kernel(const float* __restr
     }
   }
   nn[q] = bi;
+}
+__global__ __launch_bounds__(256) void feat_nn_final_kernel(const float* __restrict__ part_d,
+                                                            const int32_t* __restrict__ part_i, int nq,
+                                                            int chunks, int32_t* __restrict__ nn) {
+  const int q = blockIdx.x * 256 + threadIdx.x;
+  if (q >= nq) return;
+  feat_nn_final_query(part_d, part_i, nq, chunks, nn, q);
 }
 
 }  // namespace
@@ -640,6 +690,175 @@ void launch_feat_nn1(hipStream_t s, const float* d_data, int nd, const float* d_
                        dim, d_part_d, d_part_i);
   hipLaunchKernelGGL(feat_nn_final_kernel, dim3((nq + 255) / 256), dim3(256), 0, s, d_part_d, d_part_i, nq, chunks,
                      d_nn);
+}
+
+// ---- the batched front-end (features.hip): the same workgroup bodies, one launch for many clouds ----------------
+// A block finds its cloud (or search) through a host-built block -> problem map and the descriptor table, then runs
+// the body above with that problem's own pointers: the chunking of a cloud depends on that cloud alone, so what is
+// computed for it -- and, after the (d2, idx) sort, in which order -- does not depend on its neighbours in the batch.
+namespace {
+
+template <int FILL>
+__global__ __launch_bounds__(64) void feat_radius_batch_kernel(const FeatCloudDesc* __restrict__ desc,
+                                                               const int32_t* __restrict__ blk_cloud, int blk_base,
+                                                               int which, const float* __restrict__ pts,
+                                                               int32_t* __restrict__ counts,
+                                                               const int64_t* __restrict__ offsets,
+                                                               Nbr* __restrict__ list) {
+  const int blk = blk_base + (int)blockIdx.x;
+  const FeatCloudDesc d = desc[blk_cloud[blk]];
+  const int local = blk - d.blk_off;
+  const int chunk = local / d.qblocks, qblock = local - chunk * d.qblocks;
+  feat_radius_block<FILL>(pts + 3 * d.off, d.n, d.r2[which], counts + d.off, FILL ? offsets + d.off : nullptr, list,
+                          qblock, chunk);
+}
+
+// one workgroup per cloud
+__global__ __launch_bounds__(1024) void feat_scan_batch_kernel(const FeatCloudDesc* __restrict__ desc,
+                                                               const int32_t* __restrict__ counts,
+                                                               int64_t* __restrict__ offsets,
+                                                               int64_t* __restrict__ meta) {
+  const FeatCloudDesc d = desc[blockIdx.x];
+  feat_scan_block<false>(counts + d.off, d.n, offsets + d.off, meta + 2 * (size_t)blockIdx.x);
+}
+
+__global__ __launch_bounds__(256) void feat_rebase_kernel(const int32_t* __restrict__ pt_cloud,
+                                                          const int64_t* __restrict__ base, int64_t n_pts,
+                                                          int64_t* __restrict__ offsets) {
+  const int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (g < n_pts) offsets[g] += base[pt_cloud[g]];
+}
+
+__global__ __launch_bounds__(128) void feat_normals_batch_kernel(const FeatCloudDesc* __restrict__ desc,
+                                                                 const int32_t* __restrict__ pt_cloud, int64_t pt0,
+                                                                 int64_t pt1, const float* __restrict__ pts,
+                                                                 const int64_t* __restrict__ offsets,
+                                                                 const int32_t* __restrict__ counts,
+                                                                 const Nbr* __restrict__ list,
+                                                                 float* __restrict__ normals) {
+  const int64_t g = pt0 + (int64_t)blockIdx.x * 128 + threadIdx.x;
+  if (g >= pt1) return;
+  const int64_t off = desc[pt_cloud[g]].off;
+  feat_normal_point(pts + 3 * off, (int)(g - off), offsets + off, counts + off, list, normals + 3 * off);
+}
+
+__global__ __launch_bounds__(256) void feat_spfh_batch_kernel(const FeatCloudDesc* __restrict__ desc,
+                                                              const int32_t* __restrict__ pt_cloud, int64_t pt0,
+                                                              int64_t pt1, const float* __restrict__ pts,
+                                                              const float* __restrict__ normals,
+                                                              const int64_t* __restrict__ offsets,
+                                                              const int32_t* __restrict__ counts,
+                                                              const Nbr* __restrict__ list, float* __restrict__ spfh) {
+  const int64_t g = pt0 + (int64_t)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const bool live = g < pt1;
+  const int64_t off = live ? desc[pt_cloud[g]].off : 0;
+  feat_spfh_point(pts + 3 * off, normals + 3 * off, live, (int)(g - off), offsets + off, counts + off, list,
+                  spfh + 33 * off);
+}
+
+__global__ __launch_bounds__(256) void feat_fpfh_batch_kernel(const FeatCloudDesc* __restrict__ desc,
+                                                              const int32_t* __restrict__ pt_cloud, int64_t pt0,
+                                                              int64_t pt1, const int64_t* __restrict__ offsets,
+                                                              const int32_t* __restrict__ counts,
+                                                              const Nbr* __restrict__ list,
+                                                              const float* __restrict__ spfh, float* __restrict__ out) {
+  const int64_t g = pt0 + (int64_t)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  if (g >= pt1) return;
+  const int64_t off = desc[pt_cloud[g]].off;
+  feat_fpfh_point((int)(g - off), offsets + off, counts + off, list, spfh + 33 * off, out + 33 * off);
+}
+
+template <int DIM>
+__global__ __launch_bounds__(64) void feat_nn_partial_batch_kernel(const FeatSearchDesc* __restrict__ search,
+                                                                   const int32_t* __restrict__ blk_search,
+                                                                   int blk_base, const float* __restrict__ feat,
+                                                                   int dim_rt, float* __restrict__ part_d,
+                                                                   int32_t* __restrict__ part_i) {
+  const int blk = blk_base + (int)blockIdx.x;
+  const FeatSearchDesc d = search[blk_search[blk]];
+  const int local = blk - d.blk_off;
+  const int chunk = local / d.qblocks, qblock = local - chunk * d.qblocks;
+  const int dim = DIM > 0 ? DIM : dim_rt;
+  feat_nn_partial_block<DIM>(feat + d.data_row * dim, d.nd, feat + d.query_row * dim, d.nq, dim_rt,
+                             part_d + d.part_off, part_i + d.part_off, qblock, chunk);
+}
+// grid (query blocks of 256 of the largest search, searches)
+__global__ __launch_bounds__(256) void feat_nn_final_batch_kernel(const FeatSearchDesc* __restrict__ search, int s0,
+                                                                  const float* __restrict__ part_d,
+                                                                  const int32_t* __restrict__ part_i,
+                                                                  int32_t* __restrict__ nn) {
+  const FeatSearchDesc d = search[s0 + (int)blockIdx.y];
+  const int q = blockIdx.x * 256 + threadIdx.x;
+  if (q >= d.nq) return;
+  feat_nn_final_query(part_d + d.part_off, part_i + d.part_off, d.nq, (d.nd + kNnChunk - 1) / kNnChunk,
+                      nn + d.nn_off, q);
+}
+
+}  // namespace
+
+int feat_radius_chunk() { return kFeatChunk; }
+
+void launch_feat_radius_count_batch(hipStream_t s, const FeatCloudDesc* d_desc, const int32_t* d_blk_cloud, int blk_base,
+                                    int n_blk, int which, const float* d_pts, int32_t* d_counts) {
+  if (n_blk <= 0) return;
+  hipLaunchKernelGGL(feat_radius_batch_kernel<0>, dim3(n_blk), dim3(64), 0, s, d_desc, d_blk_cloud, blk_base, which,
+                     d_pts, d_counts, static_cast<const int64_t*>(nullptr), static_cast<Nbr*>(nullptr));
+}
+void launch_feat_scan_batch(hipStream_t s, const FeatCloudDesc* d_desc, int batch, const int32_t* d_counts,
+                            int64_t* d_offsets, int64_t* d_meta) {
+  if (batch <= 0) return;
+  hipLaunchKernelGGL(feat_scan_batch_kernel, dim3(batch), dim3(1024), 0, s, d_desc, d_counts, d_offsets, d_meta);
+}
+void launch_feat_rebase(hipStream_t s, const int32_t* d_pt_cloud, const int64_t* d_base, int64_t n_pts,
+                        int64_t* d_offsets) {
+  if (n_pts <= 0) return;
+  hipLaunchKernelGGL(feat_rebase_kernel, dim3((unsigned)((n_pts + 255) / 256)), dim3(256), 0, s, d_pt_cloud, d_base,
+                     n_pts, d_offsets);
+}
+void launch_feat_lists_batch(hipStream_t s, const FeatCloudDesc* d_desc, const int32_t* d_blk_cloud, int blk_base,
+                             int n_blk, int which, int64_t pt0, int64_t pt1, const float* d_pts,
+                             const int32_t* d_counts, int32_t* d_cursor, const int64_t* d_offsets, void* d_list,
+                             void* d_scratch) {
+  if (n_blk <= 0 || pt1 <= pt0) return;
+  Nbr* list = reinterpret_cast<Nbr*>(d_list);
+  hipLaunchKernelGGL(feat_radius_batch_kernel<1>, dim3(n_blk), dim3(64), 0, s, d_desc, d_blk_cloud, blk_base, which,
+                     d_pts, d_cursor, d_offsets, list);
+  const unsigned n = (unsigned)(pt1 - pt0);  // one workgroup per list: the single-cloud sort kernels, offsets being global
+  hipLaunchKernelGGL(feat_sort_kernel, dim3(n), dim3(256), 0, s, d_offsets + pt0, d_counts + pt0, list);
+  if (d_scratch)
+    hipLaunchKernelGGL(feat_sort_long_kernel, dim3(n), dim3(256), 0, s, d_offsets + pt0, d_counts + pt0, list,
+                       reinterpret_cast<Nbr*>(d_scratch));
+}
+void launch_feat_normals_batch(hipStream_t s, const FeatCloudDesc* d_desc, const int32_t* d_pt_cloud, int64_t pt0,
+                               int64_t pt1, const float* d_pts, const int64_t* d_offsets, const int32_t* d_counts,
+                               const void* d_list, float* d_normals) {
+  if (pt1 <= pt0) return;
+  hipLaunchKernelGGL(feat_normals_batch_kernel, dim3((unsigned)((pt1 - pt0 + 127) / 128)), dim3(128), 0, s, d_desc,
+                     d_pt_cloud, pt0, pt1, d_pts, d_offsets, d_counts, reinterpret_cast<const Nbr*>(d_list), d_normals);
+}
+void launch_feat_fpfh_batch(hipStream_t s, const FeatCloudDesc* d_desc, const int32_t* d_pt_cloud, int64_t pt0,
+                            int64_t pt1, const float* d_pts, const float* d_normals, const int64_t* d_offsets,
+                            const int32_t* d_counts, const void* d_list, float* d_spfh, float* d_out) {
+  if (pt1 <= pt0) return;
+  const unsigned blocks = (unsigned)((pt1 - pt0 + 3) / 4);
+  hipLaunchKernelGGL(feat_spfh_batch_kernel, dim3(blocks), dim3(256), 0, s, d_desc, d_pt_cloud, pt0, pt1, d_pts,
+                     d_normals, d_offsets, d_counts, reinterpret_cast<const Nbr*>(d_list), d_spfh);
+  hipLaunchKernelGGL(feat_fpfh_batch_kernel, dim3(blocks), dim3(256), 0, s, d_desc, d_pt_cloud, pt0, pt1, d_offsets,
+                     d_counts, reinterpret_cast<const Nbr*>(d_list), d_spfh, d_out);
+}
+void launch_feat_nn1_batch(hipStream_t s, const FeatSearchDesc* d_search, const int32_t* d_blk_search, int blk_base,
+                           int n_blk, int s0, int s1, int max_nq, const float* d_feat, int dim, float* d_part_d,
+                           int32_t* d_part_i, int32_t* d_nn) {
+  if (n_blk <= 0 || s1 <= s0 || max_nq <= 0) return;
+  if (dim == 33)  // pcl::FPFHSignature33
+    hipLaunchKernelGGL(feat_nn_partial_batch_kernel<33>, dim3(n_blk), dim3(64), 0, s, d_search, d_blk_search, blk_base,
+                       d_feat, dim, d_part_d, d_part_i);
+  else
+    hipLaunchKernelGGL(feat_nn_partial_batch_kernel<0>, dim3(n_blk), dim3(64), 0, s, d_search, d_blk_search, blk_base,
+                       d_feat, dim, d_part_d, d_part_i);
+  for (int y0 = s0; y0 < s1; y0 += 65535)  // (the grid's y extent)
+    hipLaunchKernelGGL(feat_nn_final_batch_kernel, dim3((max_nq + 255) / 256, std::min(65535, s1 - y0)), dim3(256), 0, s,
+                       d_search, y0, d_part_d, d_part_i, d_nn);
 }
 
 }  // namespace thip

@@ -18,6 +18,7 @@
 #include <thread>
 #include <vector>
 
+#include "features_internal.h"
 #include "internal.h"
 
 namespace thip {
@@ -2818,27 +2819,8 @@ int32_t teaser_hip_match_features(teaser_hip_solver* h, const float* src_feat, i
       h->err = "teaser_hip_match_features: non-finite feature values (no nearest neighbour for a point)";
       return TEASER_HIP_ERR_BAD_ARG;
     }
-  // index bookkeeping of matcher.cc:155-233, 281-296 (O(n) on the host)
-  std::vector<int32_t> i_to_j((size_t)ni, -1);
-  for (int j = 0; j < nj; ++j) {
-    const int i = j_to_i[(size_t)j];
-    if (i_to_j[(size_t)i] == -1) i_to_j[(size_t)i] = i_nn[(size_t)i];
-  }
-  std::vector<std::pair<int32_t, int32_t>> corres;
-  if (use_crosscheck) {
-    for (int i = 0; i < ni; ++i) {
-      const int j = i_to_j[(size_t)i];
-      if (j >= 0 && j_to_i[(size_t)j] == i) corres.emplace_back(i, j);
-    }
-  } else {
-    for (int i = 0; i < ni; ++i)
-      if (i_to_j[(size_t)i] != -1) corres.emplace_back(i, i_to_j[(size_t)i]);
-    for (int j = 0; j < nj; ++j) corres.emplace_back(j_to_i[(size_t)j], j);
-  }
-  if (swapped)
-    for (auto& c : corres) std::swap(c.first, c.second);
-  std::sort(corres.begin(), corres.end());
-  corres.erase(std::unique(corres.begin(), corres.end()), corres.end());
+  // index bookkeeping of matcher.cc:155-233, 281-296 (O(n) on the host; shared with the batched front-end)
+  const auto corres = feat_match_pairs(j_to_i.data(), nj, i_nn.data(), ni, swapped, use_crosscheck != 0);
   *n_pairs = (int64_t)corres.size();
   if ((int64_t)corres.size() > cap) return TEASER_HIP_ERR_BAD_ARG;
   for (size_t k = 0; k < corres.size(); ++k) {

@@ -1,0 +1,228 @@
+"""The batched correspondence front-end on the GPU: FPFH descriptors and mutual-nearest-neighbour matching for many
+clouds / pairs per call -- ``compute_fpfh_batch``, ``match_features_batch`` and ``correspondences_batch`` (clouds in,
+correspondences out, the features staying on the device in between).  The arithmetic is that of
+``FPFHEstimation.computeFPFHFeatures`` / ``Matcher.calculateCorrespondences`` bit for bit; the contract is written out
+in include/teaser_hip.h ("Batched correspondence front-end").
+
+One library handle is kept per device between calls; calls from several threads are safe -- each handle has a lock,
+so calls for one device run one after the other.  device=-1 means the calling thread's current HIP device at the
+time of the call.  Without a GPU the calls raise TeaserHipError (NO_DEVICE): there is no CPU path."""
+import atexit
+import ctypes as C
+import threading
+
+import numpy as np
+
+from .icp import _current_device
+
+_vp, _ip, _fp, _dp, _i64p = (C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_float), C.POINTER(C.c_double),
+                             C.POINTER(C.c_int64))
+
+
+def declare(L):
+    """ctypes signatures of the front-end entry points (called by the package's lib())."""
+    L.teaser_hip_features_create.argtypes = [C.c_int32, C.POINTER(_vp)]
+    L.teaser_hip_features_destroy.argtypes = [_vp]
+    L.teaser_hip_features_last_error.argtypes = [_vp]
+    L.teaser_hip_features_last_error.restype = C.c_char_p
+    L.teaser_hip_features_set_budgets.argtypes = [_vp, C.c_int64, C.c_int64]
+    L.teaser_hip_features_fpfh_batch.argtypes = [_vp, C.c_int32, C.POINTER(_fp), _ip, _dp, _dp, C.POINTER(_fp),
+                                                 C.POINTER(_fp)]
+    L.teaser_hip_features_match_batch.argtypes = [_vp, C.c_int32, C.POINTER(_fp), _ip, C.POINTER(_fp), _ip, C.c_int32,
+                                                  C.c_int32, C.POINTER(_ip), _i64p, _i64p]
+    L.teaser_hip_features_correspondences_batch.argtypes = [
+        _vp, C.c_int32, C.POINTER(_fp), _ip, C.POINTER(_fp), _ip, _dp, _dp, C.c_int32, C.POINTER(_ip), _i64p, _i64p,
+        C.POINTER(_fp), C.POINTER(_fp), C.POINTER(_fp), C.POINTER(_fp)]
+
+
+class _Handle:
+    """One C handle and the lock that serialises its calls."""
+
+    def __init__(self, device):
+        from . import TeaserHipError, lib
+        self._lib = lib()
+        self._h = _vp()
+        rc = self._lib.teaser_hip_features_create(int(device), C.byref(self._h))
+        if rc != 0:
+            self._h = None
+            raise TeaserHipError(rc, "(no MI355X visible: the product has no CPU path)" if rc == 3 else "")
+        self.lock = threading.Lock()
+
+    def _set_budget(self, list_bytes=None, part_bytes=None):
+        """Test hook: the budgets of one wave in bytes (None or <= 0: the default) -- list_bytes for the neighbour lists
+        of a wave of clouds, part_bytes for the partial nearest-neighbour results of a wave of pairs.  Small values
+        split a call into many waves; results do not depend on them."""
+        with self.lock:
+            self._lib.teaser_hip_features_set_budgets(self._h, int(list_bytes or 0), int(part_bytes or 0))
+
+    def call(self, fn, *args):
+        from . import TeaserHipError
+        with self.lock:  # the handle serves one call at a time
+            rc = fn(self._h, *args)
+            err = self._lib.teaser_hip_features_last_error(self._h).decode() if rc != 0 else ""
+        if rc != 0:
+            raise TeaserHipError(rc, err)
+
+    def close(self):
+        if self._h is not None:
+            with self.lock:
+                self._lib.teaser_hip_features_destroy(self._h)
+            self._h = None
+
+
+# One handle per device, shared by every thread of the process (see icp.py).
+_handles = {}
+_handles_lock = threading.Lock()
+
+
+def _handle(device=-1):
+    """The cached handle of `device`; device < 0 is resolved to the calling thread's current device first."""
+    from . import lib
+    lib()
+    device = int(device)
+    if device < 0:
+        device = _current_device()
+    with _handles_lock:
+        h = _handles.get(device)
+        if h is None:
+            h = _handles[device] = _Handle(device)
+        return h
+
+
+@atexit.register
+def _release():
+    with _handles_lock:
+        for h in _handles.values():
+            h.close()
+        _handles.clear()
+
+
+# ---- argument normalisation (no device needed) ----------------------------------------------------------------------
+def _clouds(clouds, what="clouds"):
+    """A list of n_b x 3 float32 C-contiguous arrays (an empty cloud is 0 x 3)."""
+    out = []
+    for k, c in enumerate(clouds):
+        a = np.ascontiguousarray(np.asarray(c, dtype=np.float32))
+        if a.size == 0:
+            a = np.zeros((0, 3), dtype=np.float32)
+        elif a.ndim != 2 or a.shape[1] != 3:
+            raise ValueError("%s[%d] must be an n x 3 array, got shape %s" % (what, k, a.shape))
+        out.append(a)
+    return out
+
+
+def _radii(r, batch, what):
+    """One float64 per problem from a scalar or a sequence of `batch` values."""
+    a = np.asarray(r, dtype=np.float64)
+    if a.ndim == 0:
+        return np.full(max(batch, 1), float(a))
+    if a.shape != (batch,):
+        raise ValueError("%s must be a scalar or one value per problem (%d), got shape %s" % (what, batch, a.shape))
+    return np.ascontiguousarray(a) if batch else np.zeros(1)
+
+
+def _features(feats, what):
+    """A list of n_b x dim float32 C-contiguous arrays and their common dim (None when every array is empty)."""
+    out, dim = [], None
+    for k, f in enumerate(feats):
+        a = np.ascontiguousarray(np.asarray(f, dtype=np.float32))
+        if a.ndim != 2:
+            if a.size:
+                raise ValueError("%s[%d] must be an n x dim array, got shape %s" % (what, k, a.shape))
+            a = a.reshape(0, 0)
+        if a.shape[0] and a.shape[1]:
+            if dim is not None and a.shape[1] != dim:
+                raise ValueError("%s[%d] has dim %d, earlier features have dim %d" % (what, k, a.shape[1], dim))
+            dim = a.shape[1]
+        out.append(a)
+    return out, dim
+
+
+def _same_length(a, b, what_a, what_b):
+    if len(a) != len(b):
+        raise ValueError("%s and %s must have the same length, got %d and %d" % (what_a, what_b, len(a), len(b)))
+
+
+def _ptrs(arrays, ty):
+    """A ctypes array of pointers to the arrays (at least one slot, so that an empty batch still has an address)."""
+    return (ty * max(len(arrays), 1))(*[a.ctypes.data_as(ty) for a in arrays])
+
+
+def _counts(arrays):
+    return np.array([a.shape[0] for a in arrays] or [0], dtype=np.int32)
+
+
+def _pair_buffers(n_src, n_dst, batch):
+    cap = np.array([int(n_src[b]) + int(n_dst[b]) for b in range(batch)] or [0], dtype=np.int64)
+    bufs = [np.zeros((max(int(cap[b]), 1), 2), dtype=np.int32) for b in range(batch)]
+    return cap, bufs, np.zeros(max(batch, 1), dtype=np.int64)
+
+
+# ---- the calls ------------------------------------------------------------------------------------------------------
+def compute_fpfh_batch(clouds, normal_radius, fpfh_radius, device=-1, return_normals=False):
+    """FPFH of many clouds (mixed sizes allowed) in one launch sequence.  clouds: list of n_b x 3 arrays; the radii:
+    one value for all clouds or one per cloud.  Returns the list of n_b x 33 float32 features -- with
+    return_normals=True the tuple (features, normals), normals being the list of n_b x 3 float32 PCL-semantics normals.
+    Each result is bit-identical to FPFHEstimation.computeFPFHFeatures on the same cloud alone."""
+    pts = _clouds(clouds)
+    b = len(pts)
+    nr, fr = _radii(normal_radius, b, "normal_radius"), _radii(fpfh_radius, b, "fpfh_radius")
+    n = _counts(pts)
+    out = [np.zeros((p.shape[0], 33), dtype=np.float32) for p in pts]
+    nrm = [np.zeros((p.shape[0], 3), dtype=np.float32) for p in pts] if return_normals else None
+    h = _handle(device)
+    h.call(h._lib.teaser_hip_features_fpfh_batch, b, _ptrs(pts, _fp), n.ctypes.data_as(_ip), nr.ctypes.data_as(_dp),
+           fr.ctypes.data_as(_dp), _ptrs(out, _fp), None if nrm is None else _ptrs(nrm, _fp))
+    return (out, nrm) if return_normals else out
+
+
+def match_features_batch(src_feats, dst_feats, use_crosscheck=True, device=-1):
+    """Matcher.calculateCorrespondences (use_tuple_test=False) for many feature pairs in one launch sequence: per
+    pair the k_b x 2 int32 array of sorted unique (src, dst) index pairs."""
+    _same_length(src_feats, dst_feats, "src_feats", "dst_feats")
+    a, dim_a = _features(src_feats, "src_feats")
+    d, dim_d = _features(dst_feats, "dst_feats")
+    if dim_a is not None and dim_d is not None and dim_a != dim_d:
+        raise ValueError("src_feats have dim %d, dst_feats have dim %d" % (dim_a, dim_d))
+    dim = dim_a or dim_d or 33
+    b = len(a)
+    n_src, n_dst = _counts(a), _counts(d)
+    cap, bufs, cnt = _pair_buffers(n_src, n_dst, b)
+    h = _handle(device)
+    h.call(h._lib.teaser_hip_features_match_batch, b, _ptrs(a, _fp), n_src.ctypes.data_as(_ip), _ptrs(d, _fp),
+           n_dst.ctypes.data_as(_ip), dim, 1 if use_crosscheck else 0, _ptrs(bufs, _ip), cap.ctypes.data_as(_i64p),
+           cnt.ctypes.data_as(_i64p))
+    return [bufs[k][:int(cnt[k])].copy() for k in range(b)]
+
+
+def correspondences_batch(src_clouds, dst_clouds, normal_radius, fpfh_radius, use_crosscheck=True, tuple_scale=0.0,
+                          tuple_seed=0, return_features=False, return_normals=False, device=-1):
+    """Clouds in, correspondences out, for many pairs in one launch sequence: FPFH of both clouds of every pair, then
+    the mutual nearest-neighbour matching, with the features staying on the device in between.  Returns the list of
+    k_b x 2 int32 arrays of (src, dst) pairs; with return_features / return_normals a tuple
+    (pairs, [src_feats, dst_feats], [src_normals, dst_normals]) holding the parts asked for.  tuple_scale != 0 applies
+    the tuple test per pair (host routine, seeded by tuple_seed)."""
+    _same_length(src_clouds, dst_clouds, "src_clouds", "dst_clouds")
+    sp, dp = _clouds(src_clouds, "src_clouds"), _clouds(dst_clouds, "dst_clouds")
+    b = len(sp)
+    nr, fr = _radii(normal_radius, b, "normal_radius"), _radii(fpfh_radius, b, "fpfh_radius")
+    n_src, n_dst = _counts(sp), _counts(dp)
+    cap, bufs, cnt = _pair_buffers(n_src, n_dst, b)
+    feats = nrms = None
+    if return_features:
+        feats = [[np.zeros((p.shape[0], 33), dtype=np.float32) for p in side] for side in (sp, dp)]
+    if return_normals:
+        nrms = [[np.zeros((p.shape[0], 3), dtype=np.float32) for p in side] for side in (sp, dp)]
+    h = _handle(device)
+    h.call(h._lib.teaser_hip_features_correspondences_batch, b, _ptrs(sp, _fp), n_src.ctypes.data_as(_ip),
+           _ptrs(dp, _fp), n_dst.ctypes.data_as(_ip), nr.ctypes.data_as(_dp), fr.ctypes.data_as(_dp),
+           1 if use_crosscheck else 0, _ptrs(bufs, _ip), cap.ctypes.data_as(_i64p), cnt.ctypes.data_as(_i64p),
+           None if feats is None else _ptrs(feats[0], _fp), None if feats is None else _ptrs(feats[1], _fp),
+           None if nrms is None else _ptrs(nrms[0], _fp), None if nrms is None else _ptrs(nrms[1], _fp))
+    pairs = [bufs[k][:int(cnt[k])].copy() for k in range(b)]
+    if tuple_scale:
+        from . import tuple_test
+        pairs = [np.asarray(tuple_test(sp[k], dp[k], pairs[k], tuple_scale, tuple_seed), dtype=np.int32).reshape(-1, 2)
+                 for k in range(b)]
+    parts = [pairs] + ([feats] if return_features else []) + ([nrms] if return_normals else [])
+    return parts[0] if len(parts) == 1 else tuple(parts)
