@@ -6,7 +6,8 @@ nearest-neighbour correspondences -> TEASER++ registration -> optional DRS certi
 on the MI355X.  Usage:
 
     python examples/teaser_python_fpfh.py [src.ply dst.ply] [--voxel 0.05] [--certify] [--icp [--icp-iterations 100]]
-                                          [--icp-plane [--icp-kernel tukey --icp-kernel-k K]] [--batch K]
+                                          [--icp-plane [--icp-kernel tukey --icp-kernel-k K]]
+                                          [--icp-gicp [--gicp-radius R --gicp-max-nn K]] [--batch K]
 
 --icp-plane refines with point-to-plane ICP instead, on the target normals the FPFH stage already computed
 (rows PCL leaves non-finite, below 3 neighbours, set to zero: they contribute nothing), optionally with a robust kernel.
@@ -102,6 +103,10 @@ def main():
     ap.add_argument("--icp-iterations", type=int, default=100)
     ap.add_argument("--icp-plane", action="store_true",
                     help="refine the TEASER++ pose with point-to-plane ICP on the FPFH stage's target normals")
+    ap.add_argument("--icp-gicp", action="store_true",
+                    help="refine with Generalized ICP instead, on covariances estimated on the GPU from both clouds")
+    ap.add_argument("--gicp-radius", type=float, default=None, help="covariance search radius (default: 2 voxels)")
+    ap.add_argument("--gicp-max-nn", type=int, default=20)
     ap.add_argument("--icp-kernel", choices=["l2", "huber", "cauchy", "gm", "tukey"], default="l2")
     ap.add_argument("--icp-kernel-k", type=float, default=None, help="kernel parameter (default: the voxel size)")
     ap.add_argument("--batch", type=int, default=0, metavar="K",
@@ -186,6 +191,25 @@ def main():
         print("ICP before: fitness %.6f rmse %.6f" % (before.fitness, before.inlier_rmse))
         print("ICP after:  fitness %.6f rmse %.6f iterations %d (%.2f ms)" % (icp.fitness, icp.inlier_rmse,
                                                                               icp.iterations, 1e3 * (t4 - t3)))
+        print("T_icp =\n%s" % icp.transformation)
+    if a.icp_gicp:
+        T = np.eye(4)
+        T[:3, :3], T[:3, 3] = sol.rotation, sol.translation
+        P, Q = np.asarray(A, dtype=np.float64), np.asarray(B, dtype=np.float64)
+        radius = a.gicp_radius if a.gicp_radius is not None else 2 * vox
+        crit = tp.ICPConvergenceCriteria(max_iteration=a.icp_iterations)
+        before = tp.registration_icp(P, Q, vox, T, criteria=tp.ICPConvergenceCriteria(max_iteration=0))
+        t3 = time.perf_counter()
+        Cs, Ct = tp.estimate_covariances_batch([P, Q], radius, a.gicp_max_nn)
+        t4 = time.perf_counter()
+        icp = tp.registration_generalized_icp(P, Q, vox, T, tp.TransformationEstimationForGeneralizedICP(), crit,
+                                              source_covariances=Cs, target_covariances=Ct)
+        t5 = time.perf_counter()
+        print("Generalized ICP, covariances from radius %g, max_nn %d (%.2f ms)" % (radius, a.gicp_max_nn,
+                                                                                    1e3 * (t4 - t3)))
+        print("ICP before: fitness %.6f rmse %.6f" % (before.fitness, before.inlier_rmse))
+        print("ICP after:  fitness %.6f rmse %.6f iterations %d (%.2f ms)" % (icp.fitness, icp.inlier_rmse,
+                                                                              icp.iterations, 1e3 * (t5 - t4)))
         print("T_icp =\n%s" % icp.transformation)
 
 

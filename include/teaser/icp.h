@@ -1,6 +1,8 @@
 // teaser/icp.h -- ICP refinement (Open3D's RegistrationICP with TransformationEstimationPointToPoint(with_scaling =
 // false), or with TransformationEstimationPointToPlane and an optional robust kernel on caller-given target
-// normals) over the MI355X C ABI (include/teaser_hip.h, "ICP refinement", where the contracts are written out).
+// normals, or with TransformationEstimationForGeneralizedICP on per-point covariances of both clouds, which
+// ICP::estimateCovariances computes on the GPU) over the MI355X C ABI (include/teaser_hip.h, "ICP refinement", where
+// the contracts are written out).
 // Header-only.
 //
 // Types follow teaser/registration.h: with Eigen the clouds are Matrix<double,3,Dynamic> and the transform is
@@ -10,6 +12,7 @@
 // visible (there is no CPU path), registrationICP throws teaser::ICPError on a failed call.
 #pragma once
 
+#include <cmath>
 #include <stdexcept>
 #include <string>
 #include <utility>
@@ -57,6 +60,32 @@ struct TransformationEstimationPointToPlane {
   explicit TransformationEstimationPointToPlane(const RobustKernel& k) : kernel(k) {}
 };
 
+// Open3D's TransformationEstimationForGeneralizedICP, L2 only (include/teaser_hip.h says why).  The covariances of both
+// clouds are arguments of registrationICP; epsilon is what estimateCovariances / covariancesFromNormals take.
+struct TransformationEstimationForGeneralizedICP {
+  double epsilon = 1e-3;
+  TransformationEstimationForGeneralizedICP() = default;
+  explicit TransformationEstimationForGeneralizedICP(double eps) : epsilon(eps) {}
+};
+
+// One 3 x 3 covariance per point: 9 doubles each, row-major (only the upper triangle is read).
+using Covariances = std::vector<double>;
+
+// C = I - (1 - epsilon) n n^T / (n^T n) per normal; the identity for a zero or non-finite normal.  Host arithmetic.
+inline Covariances covariancesFromNormals(const Matrix3X& normals, double epsilon = 1e-3) {
+  const size_t n = (size_t)normals.cols();
+  Covariances out(9 * n, 0.0);
+  for (size_t i = 0; i < n; ++i) {
+    const double v[3] = {normals(0, (int64_t)i), normals(1, (int64_t)i), normals(2, (int64_t)i)};
+    const double nn = (v[0] * v[0] + v[1] * v[1]) + v[2] * v[2];
+    const bool ok = std::isfinite(nn) && nn > 0;
+    for (int a = 0; a < 3; ++a)
+      for (int b = 0; b < 3; ++b)
+        out[9 * i + (size_t)(3 * a + b)] = (a == b ? 1.0 : 0.0) - (ok ? ((1.0 - epsilon) * v[a]) * v[b] / nn : 0.0);
+  }
+  return out;
+}
+
 // Open3D's RegistrationResult + the number of iterations run.
 struct ICPResult {
   Matrix4 transformation;
@@ -97,6 +126,62 @@ class ICP {
     return run(src, dst, max_correspondence_distance, init, criteria, nullptr, nullptr);
   }
 
+  // The same with Generalized ICP: src_cov[b] / dst_cov[b] hold one covariance per point of src[b] / dst[b].
+  std::vector<ICPResult> registrationICPBatch(const std::vector<Matrix3X>& src, const std::vector<Matrix3X>& dst,
+                                              const std::vector<Covariances>& src_cov,
+                                              const std::vector<Covariances>& dst_cov,
+                                              const std::vector<double>& max_correspondence_distance,
+                                              const std::vector<Matrix4>& init,
+                                              const std::vector<TransformationEstimationForGeneralizedICP>& estimation,
+                                              const std::vector<ICPConvergenceCriteria>& criteria) {
+    const size_t b = src.size();
+    if (dst.size() != b || src_cov.size() != b || dst_cov.size() != b || estimation.size() != b)
+      throw std::invalid_argument("teaser::ICP: one entry per problem in every argument");
+    std::vector<const double*> ps(b), pd(b);
+    std::vector<teaser_icp_estimation_c> est(b);
+    for (size_t k = 0; k < b; ++k) {
+      if (src_cov[k].size() != 9 * (size_t)src[k].cols() || dst_cov[k].size() != 9 * (size_t)dst[k].cols())
+        throw std::invalid_argument("teaser::ICP: one 3 x 3 covariance (9 doubles) per point");
+      ps[k] = src_cov[k].data();
+      pd[k] = dst_cov[k].data();
+      est[k].method = 2;
+      est[k].kernel = 0;
+      est[k].kernel_k = 1.0;
+    }
+    return run(src, dst, max_correspondence_distance, init, criteria, nullptr, est.data(), ps.data(), pd.data());
+  }
+
+  // Covariances for Generalized ICP, estimated on the GPU (include/teaser_hip.h, "Covariance estimation"): per point
+  // the max_nn nearest neighbours inside radius, C = I - (1 - epsilon) n n^T; the identity below 3 neighbours.
+  std::vector<Covariances> estimateCovariancesBatch(const std::vector<Matrix3X>& clouds,
+                                                    const std::vector<double>& radius,
+                                                    const std::vector<int>& max_nn,
+                                                    const std::vector<double>& epsilon) {
+    const size_t b = clouds.size();
+    if (radius.size() != b || max_nn.size() != b || epsilon.size() != b)
+      throw std::invalid_argument("teaser::ICP: one entry per cloud in every argument");
+    std::vector<const double*> pp(b);
+    std::vector<int32_t> n(b), k(b);
+    std::vector<Covariances> out(b);
+    std::vector<double*> po(b);
+    for (size_t c = 0; c < b; ++c) {
+      pp[c] = clouds[c].data();
+      n[c] = (int32_t)clouds[c].cols();
+      k[c] = max_nn[c];
+      out[c].resize(9 * (size_t)n[c]);
+      po[c] = out[c].data();
+    }
+    const int32_t rc = teaser_hip_icp_covariances_batch(h_, (int32_t)b, pp.data(), n.data(), radius.data(), k.data(),
+                                                        epsilon.data(), po.data());
+    if (rc != TEASER_HIP_OK)
+      throw ICPError(rc, "teaser::ICP: status " + std::to_string(rc) + ": " + teaser_hip_icp_last_error(h_));
+    return out;
+  }
+
+  Covariances estimateCovariances(const Matrix3X& cloud, double radius, int max_nn = 20, double epsilon = 1e-3) {
+    return estimateCovariancesBatch({cloud}, {radius}, {max_nn}, {epsilon})[0];
+  }
+
   // The same with point-to-plane estimation: dst_normals[b] holds one normal per point of dst[b], used as given.
   std::vector<ICPResult> registrationICPBatch(const std::vector<Matrix3X>& src, const std::vector<Matrix3X>& dst,
                                               const std::vector<Matrix3X>& dst_normals,
@@ -134,11 +219,20 @@ class ICP {
                                 {criteria})[0];
   }
 
+  ICPResult registrationICP(const Matrix3X& src, const Matrix3X& dst, const Covariances& src_cov,
+                            const Covariances& dst_cov, double max_correspondence_distance, const Matrix4& init,
+                            const TransformationEstimationForGeneralizedICP& estimation,
+                            const ICPConvergenceCriteria& criteria = ICPConvergenceCriteria()) {
+    return registrationICPBatch({src}, {dst}, {src_cov}, {dst_cov}, {max_correspondence_distance}, {init},
+                                {estimation}, {criteria})[0];
+  }
+
  private:
   std::vector<ICPResult> run(const std::vector<Matrix3X>& src, const std::vector<Matrix3X>& dst,
                              const std::vector<double>& max_correspondence_distance,
                              const std::vector<Matrix4>& init, const std::vector<ICPConvergenceCriteria>& criteria,
-                             const double* const* normals, const teaser_icp_estimation_c* est) {
+                             const double* const* normals, const teaser_icp_estimation_c* est,
+                             const double* const* src_cov = nullptr, const double* const* dst_cov = nullptr) {
     const size_t b = src.size();
     if (dst.size() != b || max_correspondence_distance.size() != b || init.size() != b || criteria.size() != b)
       throw std::invalid_argument("teaser::ICP: one entry per problem in every argument");
@@ -164,7 +258,9 @@ class ICP {
     }
     std::vector<teaser_icp_result_c> out(b);
     const int32_t rc =
-        est ? teaser_hip_icp_batch_ex(h_, (int32_t)b, ps.data(), ns.data(), pd.data(), nd.data(), T.data(),
+        src_cov ? teaser_hip_icp_batch_cov(h_, (int32_t)b, ps.data(), ns.data(), pd.data(), nd.data(), T.data(),
+                                           params.data(), out.data(), pc.data(), normals, est, src_cov, dst_cov)
+        : est ? teaser_hip_icp_batch_ex(h_, (int32_t)b, ps.data(), ns.data(), pd.data(), nd.data(), T.data(),
                                       params.data(), out.data(), pc.data(), normals, est)
             : teaser_hip_icp_batch(h_, (int32_t)b, ps.data(), ns.data(), pd.data(), nd.data(), T.data(),
                                    params.data(), out.data(), pc.data());
@@ -202,6 +298,25 @@ inline ICPResult registrationICP(const Matrix3X& src, const Matrix3X& dst, const
                                  const ICPConvergenceCriteria& criteria = ICPConvergenceCriteria()) {
   ICP icp;
   return icp.registrationICP(src, dst, dst_normals, max_correspondence_distance, init, estimation, criteria);
+}
+
+}  // namespace teaser
+
+namespace teaser {
+
+// Open3D's registration_generalized_icp with given covariances, one problem; creates a handle per call.
+inline ICPResult registrationICP(const Matrix3X& src, const Matrix3X& dst, const Covariances& src_cov,
+                                 const Covariances& dst_cov, double max_correspondence_distance, const Matrix4& init,
+                                 const TransformationEstimationForGeneralizedICP& estimation,
+                                 const ICPConvergenceCriteria& criteria = ICPConvergenceCriteria()) {
+  ICP icp;
+  return icp.registrationICP(src, dst, src_cov, dst_cov, max_correspondence_distance, init, estimation, criteria);
+}
+
+// Covariances of one cloud for Generalized ICP, estimated on the GPU; creates a handle per call.
+inline Covariances estimateCovariances(const Matrix3X& cloud, double radius, int max_nn = 20, double epsilon = 1e-3) {
+  ICP icp;
+  return icp.estimateCovariances(cloud, radius, max_nn, epsilon);
 }
 
 }  // namespace teaser

@@ -499,7 +499,7 @@ TEASER_HIP_API int32_t teaser_hip_icp_solve(teaser_hip_icp* icp, const double* s
  * point-to-plane with n_t > 0 and no dst_normals, non-finite dst_normals.  Point-to-point problems give the same bits
  * through the _ex entry points as through the ones above, alone or mixed with point-to-plane problems. */
 typedef struct teaser_icp_estimation_c {
-  int32_t method;  /* 0 point-to-point (default), 1 point-to-plane */
+  int32_t method;  /* 0 point-to-point (default), 1 point-to-plane, 2 Generalized ICP (_cov entry points only) */
   int32_t kernel;  /* 0 L2 (default), 1 Huber, 2 Cauchy, 3 GM, 4 Tukey */
   double kernel_k; /* 1.0 (Open3D's default); ignored for L2 */
 } teaser_icp_estimation_c;
@@ -518,6 +518,90 @@ TEASER_HIP_API int32_t teaser_hip_icp_solve_ex(teaser_hip_icp* icp, const double
                                                const teaser_icp_params_c* params, teaser_icp_result_c* out,
                                                int32_t* corr, const double* dst_normals,
                                                const teaser_icp_estimation_c* est);
+
+/* ICP refinement: Generalized ICP (plane-to-plane; Segal, Haehnel, Thrun, "Generalized-ICP", RSS 2009; the formulation
+ * of Open3D's registration_generalized_icp / TransformationEstimationForGeneralizedICP), a third estimation method
+ * (method = 2) of the same batched ICP: same handle, search, stop rule and determinism guarantees, selectable per
+ * problem and mixed freely with methods 0 and 1 in one batch.
+ * The loop, apply, corr (the lexicographic minimum of (d2, j), strict d2 < r r), fitness, the EUCLIDEAN inlier_rmse,
+ * T = U T, the iteration count, the stop rule on absolute differences, max_iteration = 0, empty clouds and the corr
+ * output are exactly those written out above.  Only U differs.
+ * Additional input per Generalized-ICP problem: source covariances Cs (n_s x 9 doubles) and target covariances Ct
+ * (n_t x 9), one row-major 3 x 3 per point.  ONLY THE UPPER TRIANGLE (entries 0, 1, 2, 4, 5, 8) IS READ; the matrix is
+ * taken as symmetric.  With c = the problem's target bounding-box centre, Rk = the rotation block of the accumulated T
+ * that the current moved points X correspond to (init for the first step, then U T), and for every correspondence
+ * (i, j) of C in ascending i, x = X[i], q = Q[j]:
+ *   x' = x - c,  q' = q - c,  e = x' - q'
+ *   B  = Rk Cs[i]                B[r][c] = (Rk[r][0] Cs[0][c] + Rk[r][1] Cs[1][c]) + Rk[r][2] Cs[2][c]
+ *   M  = Ct[j] + B Rk^T          M[r][c] = Ct[r][c] + ((B[r][0] Rk[c][0] + B[r][1] Rk[c][1]) + B[r][2] Rk[c][2]), c >= r
+ *                                (symmetric 3 x 3, FP64, no fused operations)
+ *   adj: a00 = M11 M22 - M12 M12,  a01 = M02 M12 - M01 M22,  a02 = M01 M12 - M02 M11,
+ *        a11 = M00 M22 - M02 M02,  a12 = M01 M02 - M00 M12,  a22 = M00 M11 - M01 M01
+ *   det = (M00 a00 + M01 a01) + M02 a02,   W = adj / det (each entry one division)
+ *        The correspondence contributes NOTHING to A and g when det is not finite or not > 0.  It still counts for
+ *        fitness and inlier_rmse.
+ *   J  = [ -[x']x | I3 ]                                3 x 6: e(xi) ~ e + J xi, xi = (alpha, beta, gamma, t'x, t'y, t'z)
+ *   A  = sum J^T W J  (6 x 6, symmetric),  g = sum J^T W e
+ *        with G = [x']x W (column k of G = x' x column k of W):  A = [ rows (x' x row r of G) | G ; . | W ],
+ *        W e = per row (W[r][0] e0 + W[r][1] e1) + W[r][2] e2,  g = [ x' x (W e) ; W e ]
+ *   solve A xi = -g by the LDL^T of point-to-plane;  R = Rz(gamma) Ry(beta) Rx(alpha);  U = [ R | t' + c - R c ]
+ * U is the identity in the cases point-to-plane names: C empty, a pivot that is not finite or not positive (which
+ * includes every correspondence having been left out), xi not finite.  With W = n n^T this is the point-to-plane step
+ * (J^T n = [x' x n ; n]).
+ * Robust kernels: L2 ONLY.  Open3D weights each row of the whitened residual M^(-1/2) e, which needs a 3 x 3 matrix
+ * square root per correspondence and iteration; a different weighting under the same names would mislead, so a
+ * Generalized-ICP problem with kernel != 0 is refused (TEASER_HIP_ERR_BAD_ARG, "kernel" in the message).
+ * Differences from Open3D (this states the FORMULATION; bit parity with Open3D is not claimed and was not measured):
+ *   - the step is linearised in the frame centred on c, as for point-to-plane;
+ *   - Rk Cs Rk^T is formed each iteration from the caller's Cs and the accumulated T, not by transforming stored
+ *     covariances step after step;
+ *   - L2 only.
+ * Methods 0, 1 and 2 go through the _cov entry points below; the older entry points keep refusing method 2 ("method").
+ * Point-to-point and point-to-plane problems give the same bits through the _cov entry points as through their own,
+ * alone or mixed.  TEASER_HIP_ERR_BAD_ARG (argument and problem named) in addition to the lists above: method 2 with
+ * n_src > 0 and no src_cov or n_dst > 0 and no dst_cov, a non-finite entry among the six read of any covariance,
+ * kernel != 0 with method 2.
+ * src_cov / dst_cov: NULL, or per problem NULL (methods 0 and 1) or n x 9 doubles, borrowed for the call. */
+TEASER_HIP_API int32_t teaser_hip_icp_batch_cov(teaser_hip_icp* icp, int32_t batch, const double* const* src,
+                                                const int32_t* n_src, const double* const* dst,
+                                                const int32_t* n_dst, const double* init,
+                                                const teaser_icp_params_c* params, teaser_icp_result_c* out,
+                                                int32_t* const* corr, const double* const* dst_normals,
+                                                const teaser_icp_estimation_c* est, const double* const* src_cov,
+                                                const double* const* dst_cov);
+/* One problem: teaser_hip_icp_batch_cov with batch = 1. */
+TEASER_HIP_API int32_t teaser_hip_icp_solve_cov(teaser_hip_icp* icp, const double* src, int32_t n_src,
+                                                const double* dst, int32_t n_dst, const double* init,
+                                                const teaser_icp_params_c* params, teaser_icp_result_c* out,
+                                                int32_t* corr, const double* dst_normals,
+                                                const teaser_icp_estimation_c* est, const double* src_cov,
+                                                const double* dst_cov);
+/* Covariance estimation for Generalized ICP, on the ICP handle: a batch of clouds (n x 3 doubles each) with a radius, a
+ * max_nn in [3, TEASER_HIP_ICP_COV_MAX_NN] and an epsilon (NULL = 1e-3 for every cloud) per cloud.  Per point i:
+ *   neighbourhood: the points j (i itself included) with d2 = ((dx dx + dy dy) + dz dz) < radius radius,
+ *                  dx = P[i].x - P[j].x (the expression of corr); when there are more than max_nn, the max_nn smallest
+ *                  by (d2, j).  m = their number.
+ *   m < 3:         C = the identity.
+ *   otherwise:     o = P[j] - P[i];  S1 = sum o,  S2 = sum o o^T (upper triangle), both added one neighbour at a time in
+ *                  ascending (d2, j) from 0, so the bits depend on neither bucket order, batch nor run;
+ *                  cov[a][b] = (S2[a][b] - (S1[a] S1[b]) / m) / (m - 1)
+ *                  cyclic Jacobi in FP64 on cov with V = I: at most 16 sweeps over the pairs (0,1), (0,2), (1,2); a pair
+ *                  is skipped when a_pq = 0 or |a_pq| <= 1e-17 (|a_pp| + |a_qq|), a sweep that rotates nothing ends
+ *                  the iteration; theta = (a_qq - a_pp) / (2 a_pq), t = sign(theta) / (|theta| + sqrt(1 + theta^2))
+ *                  (sign(0) = +1), cs = 1 / sqrt(1 + t^2), sn = t cs; a_pp -= t a_pq, a_qq += t a_pq, a_pq = 0,
+ *                  (a_op, a_oq) = (cs a_op - sn a_oq, sn a_op + cs a_oq) for the third index o, and the columns p, q
+ *                  of V likewise
+ *                  n^ = the column of V of the smallest diagonal entry (the first on a tie), divided by its length
+ *                  C = I - ((1 - epsilon) n^) n^^T, that is V diag(epsilon, 1, 1) V^T; the sign of n^ cannot matter.
+ * out[b]: n[b] x 9 doubles, row-major symmetric 3 x 3 per point.  TEASER_HIP_ERR_BAD_ARG (argument and cloud named):
+ * non-finite points, a radius (or its square) or epsilon that is not finite and > 0, max_nn outside its range, NULL
+ * where n > 0.  Deterministic like every call on this handle.  Performance only: a call whose largest max_nn exceeds
+ * 32 runs every cloud of the call through the kernel with the longer neighbour list (lower occupancy). */
+#define TEASER_HIP_ICP_COV_MAX_NN 100
+TEASER_HIP_API int32_t teaser_hip_icp_covariances_batch(teaser_hip_icp* icp, int32_t batch,
+                                                        const double* const* points, const int32_t* n,
+                                                        const double* radius, const int32_t* max_nn,
+                                                        const double* epsilon, double* const* out);
 
 /* Voxel down-sampling (the reference's 3DMatch tutorial, examples/teaser_python_fpfh_icp/example.py:19-20, runs
  * Open3D's pcd.voxel_down_sample(0.05) on the raw clouds): batched, with Open3D's arithmetic and a deterministic output

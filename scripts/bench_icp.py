@@ -9,9 +9,13 @@ point-to-plane side by side in the same run, and prints ONE JSON object.  Point-
 Point-to-plane, under "plane" (target normals of the committed fixture tests/golden/icp_plane_golden.npz): the same
 three workloads for the L2 kernel (single_l2) and Tukey with k = voxel / 2 (single, batch64, dense), each with its
 per-iteration cost relative to point-to-point in this run.
+Generalized ICP, under "gicp" (covariances estimated on the GPU at radius = 2 voxel, max_nn = 20): the same three
+workloads, beside point-to-plane L2 on all three from the same run ("plane_l2") and the per-iteration ratio against it,
+the iterations to convergence of the three methods on config 5, and "covariances": the estimation time per cloud for
+the config-5 pair (each cloud alone, both in one call, 64 pairs in one call) and the dense pair.
 Wall-clock medians over --reps calls after --warmup calls (every call is synchronous); ms_min / ms_max give the spread
-of the repeats.  --method point skips the point-to-plane part (the form that also runs on a build without it).  Usage:
-    python scripts/bench_icp.py [--reps 20] [--warmup 3] [--no-host-ref] [--method both|point|plane]"""
+of the repeats.  --method point skips the other parts (the form that also runs on a build without them); both = point + plane.  Usage:
+    python scripts/bench_icp.py [--reps 20] [--warmup 3] [--no-host-ref] [--method all|both|point|plane|gicp]"""
 import argparse
 import importlib
 import json
@@ -75,7 +79,7 @@ def main():
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--no-host-ref", action="store_true")
-    ap.add_argument("--method", choices=["both", "point", "plane"], default="both")
+    ap.add_argument("--method", choices=["all", "both", "point", "plane", "gicp"], default="all")
     a = ap.parse_args()
     if tp.device_count() < 1:
         sys.exit("bench_icp.py needs an MI355X")
@@ -90,15 +94,26 @@ def main():
     A = np.repeat(P, 48, axis=0) + drng.normal(0, 0.01, size=(48 * len(P), 3))
     B = np.repeat(Q, 50, axis=0) + drng.normal(0, 0.01, size=(50 * len(Q), 3))
 
-    def workloads(est, N):
-        """single / batch64 / dense for one estimation method (None: point-to-point, through the original calls)."""
-        kw = {} if est is None else dict(estimation_method=est, target_normals=N)
+    def workloads(est, N=None, cov=None, dense_cov=None):
+        """single / batch64 / dense for one estimation method (None: point-to-point, through the original calls).
+        N: target normals of a point-to-plane method; cov / dense_cov: (source, target) covariances of a Generalized-ICP
+        method for the config-5 pair and for the dense pair."""
+        kw, bkw, dkw, gathered = {}, {}, {}, 0  # gathered: bytes read once per matched point after the search
+        if cov is not None:
+            kw = dict(estimation_method=est, source_covariances=cov[0], target_covariances=cov[1])
+            bkw = dict(estimation_methods=est, source_covariances=[cov[0]] * 64, target_covariances=[cov[1]] * 64)
+            dkw = dict(estimation_method=est, source_covariances=dense_cov[0], target_covariances=dense_cov[1])
+            gathered = 96
+        elif est is not None:
+            kw = dict(estimation_method=est, target_normals=N)
+            bkw = dict(estimation_methods=est, target_normals=[N] * 64)
+            dkw = dict(estimation_method=est, target_normals=np.repeat(N, 50, axis=0))
+            gathered = 24
         out = {}
         t, o = timed(lambda: tp.registration_icp(P, Q, r, init, criteria=crit, **kw), a.reps, a.warmup)
         out["single"] = dict(ms=1e3 * t, iterations=o.iterations, us_per_iteration=1e6 * t / max(o.iterations, 1),
                              fitness=o.fitness, inlier_rmse=o.inlier_rmse, correspondences=len(o.correspondence_set),
                              **timed.spread)
-        bkw = {} if est is None else dict(estimation_methods=est, target_normals=[N] * 64)
         srcs, dsts = [P] * 64, [Q] * 64
         tb, ob = timed(lambda: tp.registration_icp_batch(srcs, dsts, r, inits, crit, **bkw), a.reps, a.warmup)
         sb = timed.spread
@@ -108,10 +123,9 @@ def main():
         out["batch64"] = dict(batch_ms=1e3 * tb, sequential_ms=1e3 * ts, speedup=ts / tb,
                               iterations_min=min(its), iterations_max=max(its), iterations_mean=float(np.mean(its)),
                               us_per_batch_iteration=1e6 * tb / max(its), **sb)
-        dkw = {} if est is None else dict(estimation_method=est, target_normals=np.repeat(N, 50, axis=0))
         td, od = timed(lambda: tp.registration_icp(A, B, r, init, criteria=crit, **dkw), max(a.reps // 4, 3), 1)
         cand = candidate_visits(R.apply(od.transformation, A), B, r)
-        per_pass = len(A) * (48 + 4 + (24 if est is not None else 0)) + cand * 28  # + one gathered normal per point
+        per_pass = len(A) * (48 + 4 + gathered) + cand * 28
         out["dense"] = dict(points=[len(A), len(B)], ms=1e3 * td, iterations=od.iterations,
                             us_per_iteration=1e6 * td / max(od.iterations, 1), fitness=od.fitness,
                             candidates_per_pass=cand, bytes_per_pass_estimate=per_pass,
@@ -119,10 +133,10 @@ def main():
         return out
 
     t = None
-    if a.method in ("both", "point"):
+    if a.method in ("all", "both", "point"):
         res.update(workloads(None, None))
         t = res["single"]["ms"] / 1e3
-    if a.method in ("both", "plane"):
+    if a.method in ("all", "both", "plane"):
         g = np.load(os.path.join(ROOT, "tests", "golden", "icp_plane_golden.npz"))
         N = g["target_normals"]
         pl = workloads(tp.TransformationEstimationPointToPlane(tp.TukeyLoss(float(g["tukey_k"]))), N)
@@ -138,6 +152,33 @@ def main():
                 dense=pl["dense"]["us_per_iteration"] / res["dense"]["us_per_iteration"],
                 batch64=pl["batch64"]["us_per_batch_iteration"] / res["batch64"]["us_per_batch_iteration"])
         res["plane"] = pl
+
+    if a.method in ("all", "gicp"):
+        radius, max_nn = 2 * r, 20
+        cv = {}
+        tc, cov = timed(lambda: tp.estimate_covariances_batch([P, Q], radius, max_nn), a.reps, a.warmup)
+        cv["config5_pair_one_call"] = dict(ms=1e3 * tc, ms_per_cloud=1e3 * tc / 2, **timed.spread)
+        ts_, _ = timed(lambda: tp.estimate_covariances(P, radius, max_nn), a.reps, a.warmup)
+        cv["config5_source_alone"] = dict(ms=1e3 * ts_, points=len(P), **timed.spread)
+        tt_, _ = timed(lambda: tp.estimate_covariances(Q, radius, max_nn), a.reps, a.warmup)
+        cv["config5_target_alone"] = dict(ms=1e3 * tt_, points=len(Q), **timed.spread)
+        t64, _ = timed(lambda: tp.estimate_covariances_batch([P, Q] * 64, radius, max_nn), max(a.reps // 4, 3), 1)
+        cv["config5_64_pairs_one_call"] = dict(ms=1e3 * t64, ms_per_cloud=1e3 * t64 / 128, **timed.spread)
+        tdc, dense_cov = timed(lambda: tp.estimate_covariances_batch([A, B], radius, max_nn), 3, 1)
+        cv["dense_pair_one_call"] = dict(ms=1e3 * tdc, ms_per_cloud=1e3 * tdc / 2, points=[len(A), len(B)],
+                                         **timed.spread)
+        gi = workloads(tp.TransformationEstimationForGeneralizedICP(), cov=cov, dense_cov=dense_cov)
+        gi["covariances"] = dict(radius=radius, max_nn=max_nn, **cv)
+        N = np.load(os.path.join(ROOT, "tests", "golden", "icp_plane_golden.npz"))["target_normals"]
+        l2 = workloads(tp.TransformationEstimationPointToPlane(), N)
+        gi["plane_l2"] = l2
+        gi["per_iteration_vs_plane_l2"] = dict(
+            single=gi["single"]["us_per_iteration"] / l2["single"]["us_per_iteration"],
+            dense=gi["dense"]["us_per_iteration"] / l2["dense"]["us_per_iteration"],
+            batch64=gi["batch64"]["us_per_batch_iteration"] / l2["batch64"]["us_per_batch_iteration"])
+        gi["iterations_config5"] = dict(gicp=gi["single"]["iterations"], plane_l2=l2["single"]["iterations"],
+                                        point=res["single"]["iterations"] if "single" in res else None)
+        res["gicp"] = gi
 
     if not a.no_host_ref and t is not None:
         t0 = time.perf_counter()

@@ -131,7 +131,8 @@ EXPORTED_SYMBOLS = [
     "teaser_hip_comm_gather_solutions", "teaser_hip_comm_gather_indices", "teaser_hip_comm_last_error",
     "teaser_hip_icp_params_default", "teaser_hip_icp_create", "teaser_hip_icp_destroy", "teaser_hip_icp_last_error",
     "teaser_hip_icp_batch", "teaser_hip_icp_solve", "teaser_hip_icp_estimation_default", "teaser_hip_icp_batch_ex",
-    "teaser_hip_icp_solve_ex",
+    "teaser_hip_icp_solve_ex", "teaser_hip_icp_batch_cov", "teaser_hip_icp_solve_cov",
+    "teaser_hip_icp_covariances_batch",
     "teaser_hip_voxel_create", "teaser_hip_voxel_destroy", "teaser_hip_voxel_last_error",
     "teaser_hip_voxel_down_sample_batch", "teaser_hip_voxel_down_sample",
     "teaser_hip_features_create", "teaser_hip_features_destroy", "teaser_hip_features_last_error",
@@ -1031,7 +1032,9 @@ class MultiDeviceSolver:
 from . import batched  # noqa: E402,F401  (sharding + record gather for the multi-GPU batched mode)
 from .icp import (CauchyLoss, GMLoss, HuberLoss, ICPConvergenceCriteria, L2Loss, RegistrationResult,  # noqa: E402
                   TransformationEstimationPointToPlane, TransformationEstimationPointToPoint, TukeyLoss,
-                  registration_icp, registration_icp_batch)
+                  registration_icp, registration_icp_batch, TransformationEstimationForGeneralizedICP,
+                  covariances_from_normals, estimate_covariances, estimate_covariances_batch,
+                  registration_generalized_icp)
 from .voxel import voxel_down_sample, voxel_down_sample_batch  # noqa: E402
 from .features import compute_fpfh_batch, correspondences_batch, match_features_batch  # noqa: E402
 
@@ -1041,4 +1044,6 @@ __all__ = ["batched", "FPFHEstimation", "Matcher", "MultiDeviceSolver", "RobustR
            "ICPConvergenceCriteria", "TransformationEstimationPointToPoint", "RegistrationResult", "registration_icp",
            "registration_icp_batch", "voxel_down_sample", "voxel_down_sample_batch",
            "compute_fpfh_batch", "match_features_batch", "correspondences_batch",
-           "TransformationEstimationPointToPlane", "L2Loss", "HuberLoss", "CauchyLoss", "GMLoss", "TukeyLoss"]
+           "TransformationEstimationPointToPlane", "L2Loss", "HuberLoss", "CauchyLoss", "GMLoss", "TukeyLoss",
+           "TransformationEstimationForGeneralizedICP", "registration_generalized_icp", "estimate_covariances",
+           "estimate_covariances_batch", "covariances_from_normals"]

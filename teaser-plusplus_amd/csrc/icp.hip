@@ -1,5 +1,6 @@
-// icp.hip -- host side of the batched ICP (include/teaser_hip.h, "ICP refinement": point-to-point and point-to-plane
-// with robust kernels): its own handle, argument validation, the per-call target index and the iteration loop.
+// icp.hip -- host side of the batched ICP (include/teaser_hip.h, "ICP refinement": point-to-point, point-to-plane
+// with robust kernels, Generalized ICP) and of the covariance estimation on the same handle: argument validation,
+// the per-call index and the iteration loop.
 // Kernels: kernels_icp.hip.
 //
 // The host enqueues iterations in groups of kIcpGroup (two launches each); after a group ONE small copy of the
@@ -20,6 +21,7 @@ using namespace thip;
 namespace {
 
 constexpr int kIcpGroup = 8;
+static_assert(kIcpCovMaxNN == TEASER_HIP_ICP_COV_MAX_NN, "the header states K");
 
 struct DevBuf {
   void* p = nullptr;
@@ -44,7 +46,7 @@ struct DevBuf {
 };
 
 enum { B_DESC, B_STATE, B_BLK, B_TBLK, B_X, B_Q, B_TBUCKET, B_BCOUNT, B_BSTART, B_CURSOR, B_QS, B_QJ, B_MATCH,
-       B_PARTIALS, B_LIVE, B_NORMALS, B_COUNT };
+       B_PARTIALS, B_LIVE, B_NORMALS, B_COV_S, B_COV_T, B_COUNT };
 
 }  // namespace
 
@@ -75,12 +77,28 @@ bool finite_points(const double* p, int64_t n) {
   return true;
 }
 
+// the six entries of the contract (upper triangle) of n row-major 3 x 3 matrices
+bool finite_cov(const double* c, int64_t n) {
+  static const int kUpper[6] = {0, 1, 2, 4, 5, 8};
+  for (int64_t k = 0; k < n; ++k)
+    for (int u : kUpper)
+      if (!std::isfinite(c[9 * k + u])) return false;
+  return true;
+}
+
+void pack_cov(const double* c, int64_t n, double* out) {
+  static const int kUpper[6] = {0, 1, 2, 4, 5, 8};
+  for (int64_t k = 0; k < n; ++k)
+    for (int u = 0; u < 6; ++u) out[6 * k + u] = c[9 * k + kUpper[u]];
+}
+
 std::string at(int b) { return " (problem " + std::to_string(b) + ")"; }
 
 int32_t validate(teaser_hip_icp* h, int32_t batch, const double* const* src, const int32_t* n_src,
                  const double* const* dst, const int32_t* n_dst, const double* init,
                  const teaser_icp_params_c* params, teaser_icp_result_c* out, const double* const* dst_normals,
-                 const teaser_icp_estimation_c* est) {
+                 const teaser_icp_estimation_c* est, const double* const* src_cov, const double* const* dst_cov,
+                 int max_method) {
   if (batch < 0) return fail(h, TEASER_HIP_ERR_BAD_ARG, "batch must be >= 0");
   if (batch == 0) return TEASER_HIP_OK;
   if (!n_src || !n_dst) return fail(h, TEASER_HIP_ERR_BAD_ARG, "n_src / n_dst must not be NULL");
@@ -115,8 +133,10 @@ int32_t validate(teaser_hip_icp* h, int32_t batch, const double* const* src, con
     }
     if (est) {
       const teaser_icp_estimation_c& m = est[b];
-      if (m.method != kIcpMethodPoint && m.method != kIcpMethodPlane)
-        return fail(h, TEASER_HIP_ERR_BAD_ARG, "est: unknown method" + at(b));
+      if (m.method < kIcpMethodPoint || m.method > max_method)
+        return fail(h, TEASER_HIP_ERR_BAD_ARG,
+                    (m.method == kIcpMethodGicp ? "est: method 2 (Generalized ICP) needs the _cov entry points"
+                                                : "est: unknown method") + at(b));
       if (m.kernel < kIcpKernelL2 || m.kernel > kIcpKernelTukey)
         return fail(h, TEASER_HIP_ERR_BAD_ARG, "est: unknown kernel" + at(b));
       if (m.method == kIcpMethodPoint && m.kernel != kIcpKernelL2)
@@ -124,6 +144,22 @@ int32_t validate(teaser_hip_icp* h, int32_t batch, const double* const* src, con
                     "est: a kernel other than L2 needs point-to-plane (kernel given with point-to-point)" + at(b));
       if (m.kernel != kIcpKernelL2 && (!std::isfinite(m.kernel_k) || !(m.kernel_k > 0)))
         return fail(h, TEASER_HIP_ERR_BAD_ARG, "est: kernel_k must be finite and > 0" + at(b));
+      if (m.method == kIcpMethodGicp) {
+        if (m.kernel != kIcpKernelL2)
+          return fail(h, TEASER_HIP_ERR_BAD_ARG, "est: Generalized ICP takes the L2 kernel only" + at(b));
+        if (n_src[b] > 0) {
+          if (!src_cov || !src_cov[b])
+            return fail(h, TEASER_HIP_ERR_BAD_ARG, "src_cov is NULL for a Generalized-ICP problem" + at(b));
+          if (!finite_cov(src_cov[b], n_src[b]))
+            return fail(h, TEASER_HIP_ERR_BAD_ARG, "src_cov has a non-finite entry" + at(b));
+        }
+        if (n_dst[b] > 0) {
+          if (!dst_cov || !dst_cov[b])
+            return fail(h, TEASER_HIP_ERR_BAD_ARG, "dst_cov is NULL for a Generalized-ICP problem" + at(b));
+          if (!finite_cov(dst_cov[b], n_dst[b]))
+            return fail(h, TEASER_HIP_ERR_BAD_ARG, "dst_cov has a non-finite entry" + at(b));
+        }
+      }
       if (m.method == kIcpMethodPlane && n_dst[b] > 0) {
         if (!dst_normals || !dst_normals[b])
           return fail(h, TEASER_HIP_ERR_BAD_ARG, "dst_normals is NULL for a point-to-plane problem" + at(b));
@@ -144,6 +180,36 @@ int64_t next_pow2(int64_t v) {
   while (p < v) p <<= 1;
   return p;
 }
+
+// The hash grid of one cloud q (d.n_t > 0 points) for search radius r: origin, cell edge, extent, bucket count, and
+// the centre the sums are taken about.
+void set_grid(IcpDesc& d, const double* q, double r) {
+  double lo[3], hi[3];
+  for (int c = 0; c < 3; ++c) lo[c] = hi[c] = q[c];
+  for (int64_t j = 1; j < d.n_t; ++j)
+    for (int c = 0; c < 3; ++c) {
+      lo[c] = std::min(lo[c], q[3 * j + c]);
+      hi[c] = std::max(hi[c], q[3 * j + c]);
+    }
+  double mag = 0;
+  for (int c = 0; c < 3; ++c) mag = std::max(mag, std::max(fabs(lo[c]), fabs(hi[c])));
+  // cell edge slightly above r: two points closer than r then differ by at most one cell per axis although
+  // their cell coordinates are rounded (relative margin 1e-6; absolute 1e-12 of the coordinates' magnitude)
+  const double cell = r * (1 + 1e-6) + 1e-12 * mag;
+  d.inv_h = 1.0 / cell;
+  for (int c = 0; c < 3; ++c) {
+    d.origin[c] = lo[c];
+    d.centre[c] = 0.5 * (lo[c] + hi[c]);
+    d.cmax[c] = icp_cell(hi[c], lo[c], d.inv_h);
+  }
+  d.tb_mask = next_pow2(2 * (int64_t)d.n_t) - 1;
+}
+
+int32_t run_batch(teaser_hip_icp* h, int32_t batch, const double* const* src, const int32_t* n_src,
+                  const double* const* dst, const int32_t* n_dst, const double* init,
+                  const teaser_icp_params_c* params, teaser_icp_result_c* out, int32_t* const* corr,
+                  const double* const* dst_normals, const teaser_icp_estimation_c* est,
+                  const double* const* src_cov, const double* const* dst_cov, int max_method);
 
 }  // namespace
 
@@ -212,9 +278,33 @@ int32_t teaser_hip_icp_batch_ex(teaser_hip_icp* h, int32_t batch, const double* 
                                 const double* const* dst, const int32_t* n_dst, const double* init,
                                 const teaser_icp_params_c* params, teaser_icp_result_c* out, int32_t* const* corr,
                                 const double* const* dst_normals, const teaser_icp_estimation_c* est) {
+  return run_batch(h, batch, src, n_src, dst, n_dst, init, params, out, corr, dst_normals, est, nullptr, nullptr,
+                   kIcpMethodPlane);
+}
+
+int32_t teaser_hip_icp_batch_cov(teaser_hip_icp* h, int32_t batch, const double* const* src, const int32_t* n_src,
+                                 const double* const* dst, const int32_t* n_dst, const double* init,
+                                 const teaser_icp_params_c* params, teaser_icp_result_c* out, int32_t* const* corr,
+                                 const double* const* dst_normals, const teaser_icp_estimation_c* est,
+                                 const double* const* src_cov, const double* const* dst_cov) {
+  return run_batch(h, batch, src, n_src, dst, n_dst, init, params, out, corr, dst_normals, est, src_cov, dst_cov,
+                   kIcpMethodGicp);
+}
+
+}  // extern "C"
+
+namespace {
+
+// Every batched entry point: max_method is the largest estimation method the entry accepts.
+int32_t run_batch(teaser_hip_icp* h, int32_t batch, const double* const* src, const int32_t* n_src,
+                  const double* const* dst, const int32_t* n_dst, const double* init,
+                  const teaser_icp_params_c* params, teaser_icp_result_c* out, int32_t* const* corr,
+                  const double* const* dst_normals, const teaser_icp_estimation_c* est,
+                  const double* const* src_cov, const double* const* dst_cov, int max_method) {
   if (!h) return TEASER_HIP_ERR_BAD_ARG;
   h->err.clear();
-  int32_t rc = validate(h, batch, src, n_src, dst, n_dst, init, params, out, dst_normals, est);
+  int32_t rc = validate(h, batch, src, n_src, dst, n_dst, init, params, out, dst_normals, est, src_cov, dst_cov,
+                        max_method);
   if (rc != TEASER_HIP_OK || batch == 0) return rc;
   hipError_t e = hipSetDevice(h->device);
   if (e != hipSuccess) return hip_fail(h, e, "hipSetDevice");
@@ -226,6 +316,7 @@ int32_t teaser_hip_icp_batch_ex(teaser_hip_icp* h, int32_t batch, const double* 
   int64_t s_off = 0, t_off = 0, b_off = 0;
   int max_iter = 0;
   bool plane = false;  // any point-to-plane problem: the launches with the wider partials
+  bool gicp = false;   // any Generalized-ICP problem: the third instantiation and the packed covariances
   for (int b = 0; b < batch; ++b) {
     IcpDesc& d = desc[(size_t)b];
     memset(&d, 0, sizeof(d));
@@ -249,27 +340,10 @@ int32_t teaser_hip_icp_batch_ex(teaser_hip_icp* h, int32_t batch, const double* 
       d.kernel = est[b].kernel;
       d.kernel_k = est[b].kernel == kIcpKernelL2 ? 0.0 : est[b].kernel_k;
       plane |= d.method == kIcpMethodPlane;
+      gicp |= d.method == kIcpMethodGicp;
     }
     if (d.n_t > 0) {
-      double lo[3], hi[3];
-      for (int c = 0; c < 3; ++c) lo[c] = hi[c] = dst[b][c];
-      for (int64_t j = 1; j < d.n_t; ++j)
-        for (int c = 0; c < 3; ++c) {
-          lo[c] = std::min(lo[c], dst[b][3 * j + c]);
-          hi[c] = std::max(hi[c], dst[b][3 * j + c]);
-        }
-      double mag = 0;
-      for (int c = 0; c < 3; ++c) mag = std::max(mag, std::max(fabs(lo[c]), fabs(hi[c])));
-      // cell edge slightly above r: two points closer than r then differ by at most one cell per axis although
-      // their cell coordinates are rounded (relative margin 1e-6; absolute 1e-12 of the coordinates' magnitude)
-      const double cell = r * (1 + 1e-6) + 1e-12 * mag;
-      d.inv_h = 1.0 / cell;
-      for (int c = 0; c < 3; ++c) {
-        d.origin[c] = lo[c];
-        d.centre[c] = 0.5 * (lo[c] + hi[c]);
-        d.cmax[c] = icp_cell(hi[c], lo[c], d.inv_h);
-      }
-      d.tb_mask = next_pow2(2 * (int64_t)d.n_t) - 1;
+      set_grid(d, dst[b], r);
       b_off += d.tb_mask + 2;  // tb + 1 starts
     }
     for (int k = 0; k < d.nblk; ++k) blk_prob.push_back(b);
@@ -293,14 +367,16 @@ int32_t teaser_hip_icp_batch_ex(teaser_hip_icp* h, int32_t batch, const double* 
       sizeof(int32_t) * std::max<int64_t>(b_off, 1), sizeof(int32_t) * std::max<int64_t>(b_off, 1),
       sizeof(int32_t) * std::max<int64_t>(b_off, 1), sizeof(double) * 3 * std::max<int64_t>(t_off, 1),
       sizeof(int32_t) * std::max<int64_t>(t_off, 1), sizeof(int32_t) * std::max<int64_t>(s_off, 1),
-      sizeof(double) * (plane ? kIcpPlaneSums : kIcpSums) * std::max(n_blk, 1), sizeof(int32_t),
-      plane ? sizeof(double) * 3 * std::max<int64_t>(t_off, 1) : 0};
+      sizeof(double) * (plane || gicp ? kIcpPlaneSums : kIcpSums) * std::max(n_blk, 1), sizeof(int32_t),
+      plane ? sizeof(double) * 3 * std::max<int64_t>(t_off, 1) : 0,
+      gicp ? sizeof(double) * 6 * std::max<int64_t>(s_off, 1) : 0,
+      gicp ? sizeof(double) * 6 * std::max<int64_t>(t_off, 1) : 0};
   for (int k = 0; k < B_COUNT; ++k)
     if (!h->buf[k].ensure(bytes[k])) return fail(h, TEASER_HIP_ERR_OOM, "hipMalloc failed (ICP buffers)");
   hipStream_t s = h->stream;
   DevBuf* B = h->buf;
 
-  h->stage.resize((size_t)(3 * (s_off + t_off)));
+  h->stage.resize((size_t)((gicp ? 9 : 3) * (s_off + t_off)));  // points, then the packed covariances
   for (int b = 0; b < batch; ++b) {
     if (desc[(size_t)b].n_s) memcpy(&h->stage[(size_t)(3 * desc[(size_t)b].s_off)], src[b], 24 * (size_t)n_src[b]);
     if (desc[(size_t)b].n_t)
@@ -326,6 +402,22 @@ int32_t teaser_hip_icp_batch_ex(teaser_hip_icp* h, int32_t batch, const double* 
                             hipMemcpyHostToDevice, s)) != hipSuccess)
       return hip_fail(h, e, "hipMemcpyAsync (normals)");
   }
+  if (gicp) {  // upper triangles packed 6 doubles per point; rows of other problems are never read
+    double* cs = h->stage.data() + 3 * (s_off + t_off);
+    double* ct = cs + 6 * s_off;
+    for (int b = 0; b < batch; ++b) {
+      const IcpDesc& d = desc[(size_t)b];
+      if (d.method != kIcpMethodGicp) continue;
+      if (d.n_s) pack_cov(src_cov[b], d.n_s, cs + 6 * d.s_off);
+      if (d.n_t) pack_cov(dst_cov[b], d.n_t, ct + 6 * d.t_off);
+    }
+    if (s_off && (e = hipMemcpyAsync(B[B_COV_S].p, cs, sizeof(double) * 6 * s_off, hipMemcpyHostToDevice, s)) !=
+                     hipSuccess)
+      return hip_fail(h, e, "hipMemcpyAsync (source covariances)");
+    if (t_off && (e = hipMemcpyAsync(B[B_COV_T].p, ct, sizeof(double) * 6 * t_off, hipMemcpyHostToDevice, s)) !=
+                     hipSuccess)
+      return hip_fail(h, e, "hipMemcpyAsync (target covariances)");
+  }
   if (b_off && (e = hipMemsetAsync(B[B_BCOUNT].p, 0, sizeof(int32_t) * b_off, s)) != hipSuccess)
     return hip_fail(h, e, "hipMemsetAsync");
 
@@ -338,7 +430,8 @@ int32_t teaser_hip_icp_batch_ex(teaser_hip_icp* h, int32_t batch, const double* 
     for (int g = 0; g < kIcpGroup && passes <= (int64_t)max_iter; ++g, ++passes)
       launch_icp_iteration(s, B[B_DESC].as<IcpDesc>(), B[B_STATE].as<IcpState>(), B[B_BLK].as<int32_t>(), n_blk,
                            batch, B[B_X].as<double>(), B[B_QS].as<double>(), B[B_QJ].as<int32_t>(),
-                           B[B_BSTART].as<int32_t>(), B[B_NORMALS].as<double>(), plane, B[B_MATCH].as<int32_t>(),
+                           B[B_BSTART].as<int32_t>(), B[B_NORMALS].as<double>(), B[B_COV_S].as<double>(),
+                           B[B_COV_T].as<double>(), gicp ? 2 : plane ? 1 : 0, B[B_MATCH].as<int32_t>(),
                            B[B_PARTIALS].as<double>());
     launch_icp_live(s, B[B_STATE].as<IcpState>(), batch, B[B_LIVE].as<int32_t>());
     if ((e = hipGetLastError()) != hipSuccess) return hip_fail(h, e, "ICP kernel launch");
@@ -384,6 +477,10 @@ int32_t teaser_hip_icp_batch_ex(teaser_hip_icp* h, int32_t batch, const double* 
   return TEASER_HIP_OK;
 }
 
+}  // namespace
+
+extern "C" {
+
 int32_t teaser_hip_icp_solve(teaser_hip_icp* h, const double* src, int32_t n_src, const double* dst, int32_t n_dst,
                              const double* init, const teaser_icp_params_c* params, teaser_icp_result_c* out,
                              int32_t* corr) {
@@ -397,6 +494,122 @@ int32_t teaser_hip_icp_solve_ex(teaser_hip_icp* h, const double* src, int32_t n_
   int32_t* const corrs[1] = {corr};
   return teaser_hip_icp_batch_ex(h, 1, &src, &n_src, &dst, &n_dst, init, params, out, corrs,
                                  dst_normals ? &dst_normals : nullptr, est);
+}
+
+int32_t teaser_hip_icp_solve_cov(teaser_hip_icp* h, const double* src, int32_t n_src, const double* dst,
+                                 int32_t n_dst, const double* init, const teaser_icp_params_c* params,
+                                 teaser_icp_result_c* out, int32_t* corr, const double* dst_normals,
+                                 const teaser_icp_estimation_c* est, const double* src_cov, const double* dst_cov) {
+  int32_t* const corrs[1] = {corr};
+  return teaser_hip_icp_batch_cov(h, 1, &src, &n_src, &dst, &n_dst, init, params, out, corrs,
+                                  dst_normals ? &dst_normals : nullptr, est, src_cov ? &src_cov : nullptr,
+                                  dst_cov ? &dst_cov : nullptr);
+}
+
+int32_t teaser_hip_icp_covariances_batch(teaser_hip_icp* h, int32_t batch, const double* const* points,
+                                         const int32_t* n, const double* radius, const int32_t* max_nn,
+                                         const double* epsilon, double* const* out) {
+  if (!h) return TEASER_HIP_ERR_BAD_ARG;
+  h->err.clear();
+  if (batch < 0) return fail(h, TEASER_HIP_ERR_BAD_ARG, "batch must be >= 0");
+  if (batch == 0) return TEASER_HIP_OK;
+  if (!n) return fail(h, TEASER_HIP_ERR_BAD_ARG, "n must not be NULL");
+  if (!radius) return fail(h, TEASER_HIP_ERR_BAD_ARG, "radius must not be NULL");
+  if (!max_nn) return fail(h, TEASER_HIP_ERR_BAD_ARG, "max_nn must not be NULL");
+  int64_t total = 0;
+  for (int b = 0; b < batch; ++b) {
+    const double r = radius[b], eps = epsilon ? epsilon[b] : 1e-3;
+    if (!std::isfinite(r) || !(r > 0) || !std::isfinite(r * r) || !(r * r > 0))
+      return fail(h, TEASER_HIP_ERR_BAD_ARG, "radius (and its square) must be finite and > 0" + at(b));
+    if (!std::isfinite(eps) || !(eps > 0)) return fail(h, TEASER_HIP_ERR_BAD_ARG, "epsilon must be finite and > 0" + at(b));
+    if (max_nn[b] < 3 || max_nn[b] > kIcpCovMaxNN)
+      return fail(h, TEASER_HIP_ERR_BAD_ARG, "max_nn must lie in [3, " + std::to_string(kIcpCovMaxNN) + "]" + at(b));
+    if (n[b] < 0) return fail(h, TEASER_HIP_ERR_BAD_ARG, "n must be >= 0" + at(b));
+    if (n[b] > 0 && (!points || !points[b])) return fail(h, TEASER_HIP_ERR_BAD_ARG, "points is NULL" + at(b));
+    if (n[b] > 0 && (!out || !out[b])) return fail(h, TEASER_HIP_ERR_BAD_ARG, "out is NULL" + at(b));
+    if (n[b] > 0 && !finite_points(points[b], n[b]))
+      return fail(h, TEASER_HIP_ERR_BAD_ARG, "points has a non-finite coordinate" + at(b));
+    total += n[b];
+  }
+  if (total >= INT32_MAX / 9) return fail(h, TEASER_HIP_ERR_BAD_ARG, "too many points in one call");
+  hipError_t e = hipSetDevice(h->device);
+  if (e != hipSuccess) return hip_fail(h, e, "hipSetDevice");
+
+  // the ICP grid over each cloud itself (the cloud is the descriptor's target), cell edge from its radius
+  std::vector<IcpDesc> desc((size_t)batch);
+  std::vector<IcpCovDesc> cov((size_t)batch);
+  std::vector<int32_t> blk_prob, tblk_prob;
+  int64_t t_off = 0, b_off = 0;
+  int top_nn = 0;
+  for (int b = 0; b < batch; ++b) {
+    IcpDesc& d = desc[(size_t)b];
+    memset(&d, 0, sizeof(d));
+    d.n_t = n[b];
+    d.t_off = t_off;
+    d.b_off = b_off;
+    d.blk_off = (int32_t)blk_prob.size();
+    d.nblk = (d.n_t + kIcpCovBlock - 1) / kIcpCovBlock;
+    d.tblk_off = (int32_t)tblk_prob.size();
+    d.r2 = radius[b] * radius[b];
+    cov[(size_t)b].max_nn = max_nn[b];
+    cov[(size_t)b].pad = 0;
+    cov[(size_t)b].eps = epsilon ? epsilon[b] : 1e-3;
+    if (d.n_t > 0) {
+      top_nn = std::max(top_nn, max_nn[b]);
+      set_grid(d, points[b], radius[b]);
+      b_off += d.tb_mask + 2;
+    }
+    for (int k = 0; k < d.nblk; ++k) blk_prob.push_back(b);
+    for (int k = 0; k < (d.n_t + 255) / 256; ++k) tblk_prob.push_back(b);
+    t_off += d.n_t;
+  }
+  if (t_off == 0) return TEASER_HIP_OK;
+  const int n_blk = (int)blk_prob.size(), n_tblk = (int)tblk_prob.size();
+  // B_STATE holds the IcpCovDesc records and B_X the 9 doubles per point of the output during this call
+  size_t bytes[B_COUNT] = {};
+  bytes[B_DESC] = sizeof(IcpDesc) * batch;
+  bytes[B_STATE] = sizeof(IcpCovDesc) * batch;
+  bytes[B_BLK] = sizeof(int32_t) * n_blk;
+  bytes[B_TBLK] = sizeof(int32_t) * n_tblk;
+  bytes[B_X] = sizeof(double) * 9 * t_off;
+  bytes[B_Q] = sizeof(double) * 3 * t_off;
+  bytes[B_TBUCKET] = sizeof(int32_t) * t_off;
+  bytes[B_BCOUNT] = bytes[B_BSTART] = bytes[B_CURSOR] = sizeof(int32_t) * b_off;
+  bytes[B_QS] = sizeof(double) * 3 * t_off;
+  bytes[B_QJ] = sizeof(int32_t) * t_off;
+  for (int k = 0; k < B_COUNT; ++k)
+    if (!h->buf[k].ensure(bytes[k])) return fail(h, TEASER_HIP_ERR_OOM, "hipMalloc failed (covariance buffers)");
+  hipStream_t s = h->stream;
+  DevBuf* B = h->buf;
+  h->stage.resize((size_t)(9 * t_off));
+  for (int b = 0; b < batch; ++b)
+    if (n[b]) memcpy(&h->stage[(size_t)(3 * desc[(size_t)b].t_off)], points[b], 24 * (size_t)n[b]);
+  struct Copy {
+    void* d;
+    const void* hsrc;
+    size_t n;
+  } copies[] = {{B[B_DESC].p, desc.data(), bytes[B_DESC]},
+                {B[B_STATE].p, cov.data(), bytes[B_STATE]},
+                {B[B_BLK].p, blk_prob.data(), bytes[B_BLK]},
+                {B[B_TBLK].p, tblk_prob.data(), bytes[B_TBLK]},
+                {B[B_Q].p, h->stage.data(), bytes[B_Q]}};
+  for (const Copy& c : copies)
+    if (c.n && (e = hipMemcpyAsync(c.d, c.hsrc, c.n, hipMemcpyHostToDevice, s)) != hipSuccess)
+      return hip_fail(h, e, "hipMemcpyAsync (inputs)");
+  if ((e = hipMemsetAsync(B[B_BCOUNT].p, 0, bytes[B_BCOUNT], s)) != hipSuccess) return hip_fail(h, e, "hipMemsetAsync");
+  launch_icp_index(s, B[B_DESC].as<IcpDesc>(), B[B_TBLK].as<int32_t>(), n_tblk, batch, B[B_Q].as<double>(),
+                   B[B_TBUCKET].as<int32_t>(), B[B_BCOUNT].as<int32_t>(), B[B_BSTART].as<int32_t>(),
+                   B[B_CURSOR].as<int32_t>(), B[B_QS].as<double>(), B[B_QJ].as<int32_t>());
+  launch_icp_covariances(s, B[B_DESC].as<IcpDesc>(), B[B_STATE].as<IcpCovDesc>(), B[B_BLK].as<int32_t>(), n_blk,
+                         top_nn, B[B_Q].as<double>(), B[B_QS].as<double>(), B[B_QJ].as<int32_t>(),
+                         B[B_BSTART].as<int32_t>(), B[B_X].as<double>());
+  if ((e = hipGetLastError()) != hipSuccess) return hip_fail(h, e, "covariance kernel launch");
+  if ((e = hipMemcpyAsync(h->stage.data(), B[B_X].p, bytes[B_X], hipMemcpyDeviceToHost, s)) != hipSuccess)
+    return hip_fail(h, e, "hipMemcpyAsync (covariances)");
+  if ((e = hipStreamSynchronize(s)) != hipSuccess) return hip_fail(h, e, "covariance estimation");
+  for (int b = 0; b < batch; ++b)
+    if (n[b]) memcpy(out[b], &h->stage[(size_t)(9 * desc[(size_t)b].t_off)], 72 * (size_t)n[b]);
+  return TEASER_HIP_OK;
 }
 
 }  // extern "C"

@@ -11,9 +11,12 @@ constexpr int kIcpBlock = 256;   // source points per correspondence block (the 
 constexpr int kIcpSums = 17;     // {count, sum d2, sum p' (3), sum q' (3), sum p' q'^T (9)} of one block
 constexpr int kIcpPlaneSums = 29;  // point-to-plane: {count, sum d2, upper triangle of A by rows (21), g (6)}
 constexpr int kIcpScanThreads = 1024;
+constexpr int kIcpCovBlock = 64;   // points per covariance block: one wave, one point per lane
+constexpr int kIcpCovMaxNN = 100;  // K of the contract: the largest max_nn of covariance estimation
+constexpr int kIcpCovSmallNN = 32; // capacity of the small instantiation's per-lane neighbour list
 
 // IcpDesc::method / IcpDesc::kernel: the values of teaser_icp_estimation_c (include/teaser_hip.h)
-enum { kIcpMethodPoint = 0, kIcpMethodPlane = 1 };
+enum { kIcpMethodPoint = 0, kIcpMethodPlane = 1, kIcpMethodGicp = 2 };
 enum { kIcpKernelL2 = 0, kIcpKernelHuber = 1, kIcpKernelCauchy = 2, kIcpKernelGM = 3, kIcpKernelTukey = 4 };
 
 // One problem of a batch (host-built, read-only on the device).  Cell coordinates of a point x are
@@ -34,7 +37,7 @@ struct IcpDesc {
   double rel_fitness, rel_rmse;
   int32_t max_iteration;
   int32_t tblk_off;   // first target block of this problem (index build)
-  int32_t method;     // kIcpMethodPoint / kIcpMethodPlane
+  int32_t method;     // kIcpMethodPoint / kIcpMethodPlane / kIcpMethodGicp
   int32_t kernel;     // robust kernel of a point-to-plane problem (kIcpKernelL2 ...)
   double kernel_k;    // its parameter; unused for L2
 };
@@ -48,6 +51,14 @@ struct IcpState {
   int32_t count;      // |C| of the current result
   int32_t phase;      // 0: the first correspondence pass has not been finalized yet
   int32_t done;       // 1: converged or out of iterations -- every later launch returns at once
+};
+
+// One cloud of a covariance-estimation call, beside its IcpDesc (the cloud is the "target" of that descriptor: n_t,
+// t_off, the grid and r2 = radius^2; blk_off / nblk count its blocks of kIcpCovBlock points).
+struct IcpCovDesc {
+  int32_t max_nn;     // 3 .. kIcpCovMaxNN
+  int32_t pad;
+  double eps;         // the eigenvalue given to the normal direction
 };
 
 // Grid cell of one coordinate; host (descriptor set-up) and device (index build, search) run the same expression.
@@ -71,8 +82,11 @@ void launch_icp_index(hipStream_t s, const IcpDesc* d_desc, const int32_t* d_tbl
                       int32_t* d_cursor, double* d_qs, int32_t* d_qj);
 void launch_icp_iteration(hipStream_t s, const IcpDesc* d_desc, IcpState* d_state, const int32_t* d_blk_prob,
                           int n_blk, int batch, double* d_x, const double* d_qs, const int32_t* d_qj,
-                          const int32_t* d_bstart, const double* d_normals, bool plane, int32_t* d_match,
-                          double* d_partials);
+                          const int32_t* d_bstart, const double* d_normals, const double* d_cov_s,
+                          const double* d_cov_t, int mode, int32_t* d_match, double* d_partials);
+void launch_icp_covariances(hipStream_t s, const IcpDesc* d_desc, const IcpCovDesc* d_cov, const int32_t* d_blk_prob,
+                            int n_blk, int max_nn, const double* d_q, const double* d_qs, const int32_t* d_qj,
+                            const int32_t* d_bstart, double* d_out);
 void launch_icp_live(hipStream_t s, const IcpState* d_state, int batch, int32_t* d_live);
 
 }  // namespace thip

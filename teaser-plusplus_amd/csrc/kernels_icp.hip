@@ -24,6 +24,19 @@
 // point-to-point code exactly as before, launched when a call has no point-to-plane problem; <true> has the wider
 // partial and branches per block on the problem's method (uniform over the block), its point-to-point branch
 // executing the same operations in the same order, so a point-to-point problem keeps its bits in a mixed batch.
+//
+// Generalized ICP (IcpDesc::method = 2; "ICP refinement: Generalized ICP" in include/teaser_hip.h): the template
+// parameter is kMode = 0 (point-to-point only, the former <false>), 1 (point-to-plane present, the former <true>) or
+// 2 (a Generalized-ICP problem present), each launched only for calls that need it; <0> and <1> compile to what they
+// were.  <2> keeps the 29-value partial and the plane finalize; after the search it gathers the 6 + 6 packed
+// upper-triangle covariance entries of the matched pair once, forms M = Ct + R Cs R^T with R the rotation block of
+// the accumulated T (the transform the moved points X correspond to), W = adj(M) / det(M), and adds J^T W J and
+// J^T W e with J = [-[x']x | I].  Its point and plane branches are those of <1>, operation for operation.
+//
+// Covariance estimation (icp_cov_kernel): the same grid built over the cloud itself, one point per lane, the max_nn
+// smallest (d2, j) kept in a per-lane insertion-sorted list in LDS (slot-major, so the lanes of a wave hit distinct
+// banks; a per-lane register array indexed at run time would go to scratch), then the sums in list order, a cyclic
+// Jacobi iteration on the symmetric 3 x 3 and the output, all by that lane.
 #include <math.h>
 
 #include "icp_internal.h"
@@ -138,7 +151,67 @@ __global__ __launch_bounds__(256) void icp_fill_kernel(const IcpDesc* __restrict
 }
 
 // ---- one iteration ----------------------------------------------------------------------------------------------
-template <bool kPlane>
+// What one Generalized-ICP correspondence adds to v[2..28]: nothing when det(M) is not finite or not > 0.
+__device__ __forceinline__ void icp_gicp_terms(const double (&x)[3], const double (&q)[3], const double* T,
+                                               const double* cs, const double* ct, double (&v)[kIcpPlaneSums]) {
+  const double R[9] = {T[0], T[1], T[2], T[4], T[5], T[6], T[8], T[9], T[10]};
+  const double S[9] = {cs[0], cs[1], cs[2], cs[1], cs[3], cs[4], cs[2], cs[4], cs[5]};
+  double B[9];  // R Cs
+#pragma unroll
+  for (int r = 0; r < 3; ++r)
+#pragma unroll
+    for (int c = 0; c < 3; ++c) B[3 * r + c] = (R[3 * r] * S[c] + R[3 * r + 1] * S[3 + c]) + R[3 * r + 2] * S[6 + c];
+#define THIP_RCR(r, c) ((B[3 * r] * R[3 * c] + B[3 * r + 1] * R[3 * c + 1]) + B[3 * r + 2] * R[3 * c + 2])
+  const double m00 = ct[0] + THIP_RCR(0, 0), m01 = ct[1] + THIP_RCR(0, 1), m02 = ct[2] + THIP_RCR(0, 2),
+               m11 = ct[3] + THIP_RCR(1, 1), m12 = ct[4] + THIP_RCR(1, 2), m22 = ct[5] + THIP_RCR(2, 2);
+#undef THIP_RCR
+  const double a00 = m11 * m22 - m12 * m12, a01 = m02 * m12 - m01 * m22, a02 = m01 * m12 - m02 * m11,
+               a11 = m00 * m22 - m02 * m02, a12 = m01 * m02 - m00 * m12, a22 = m00 * m11 - m01 * m01;
+  const double det = (m00 * a00 + m01 * a01) + m02 * a02;
+  if (!isfinite(det) || !(det > 0.0)) return;
+  const double W[9] = {a00 / det, a01 / det, a02 / det, a01 / det, a11 / det, a12 / det,
+                       a02 / det, a12 / det, a22 / det};
+  const double e0 = x[0] - q[0], e1 = x[1] - q[1], e2 = x[2] - q[2];
+  double we[3], G[9];  // W e;  G = [x']x W (column c of G = x' x column c of W)
+#pragma unroll
+  for (int r = 0; r < 3; ++r) we[r] = (W[3 * r] * e0 + W[3 * r + 1] * e1) + W[3 * r + 2] * e2;
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    G[c] = x[1] * W[6 + c] - x[2] * W[3 + c];
+    G[3 + c] = x[2] * W[c] - x[0] * W[6 + c];
+    G[6 + c] = x[0] * W[3 + c] - x[1] * W[c];
+  }
+  // upper triangle of A by rows: [x']x W [x']x^T (row r = x' x row r of G), then G, then W
+  v[2] = x[1] * G[2] - x[2] * G[1];
+  v[3] = x[2] * G[0] - x[0] * G[2];
+  v[4] = x[0] * G[1] - x[1] * G[0];
+  v[5] = G[0];
+  v[6] = G[1];
+  v[7] = G[2];
+  v[8] = x[2] * G[3] - x[0] * G[5];
+  v[9] = x[0] * G[4] - x[1] * G[3];
+  v[10] = G[3];
+  v[11] = G[4];
+  v[12] = G[5];
+  v[13] = x[0] * G[7] - x[1] * G[6];
+  v[14] = G[6];
+  v[15] = G[7];
+  v[16] = G[8];
+  v[17] = W[0];
+  v[18] = W[1];
+  v[19] = W[2];
+  v[20] = W[4];
+  v[21] = W[5];
+  v[22] = W[8];
+  v[23] = x[1] * we[2] - x[2] * we[1];
+  v[24] = x[2] * we[0] - x[0] * we[2];
+  v[25] = x[0] * we[1] - x[1] * we[0];
+  v[26] = we[0];
+  v[27] = we[1];
+  v[28] = we[2];
+}
+
+template <int kMode>
 __global__ __launch_bounds__(kIcpBlock) void icp_corr_kernel(const IcpDesc* __restrict__ descs,
                                                              const IcpState* __restrict__ state,
                                                              const int32_t* __restrict__ blk_prob,
@@ -146,8 +219,11 @@ __global__ __launch_bounds__(kIcpBlock) void icp_corr_kernel(const IcpDesc* __re
                                                              const int32_t* __restrict__ qj,
                                                              const int32_t* __restrict__ bstart,
                                                              const double* __restrict__ normals,
+                                                             const double* __restrict__ cov_s,
+                                                             const double* __restrict__ cov_t,
                                                              int32_t* __restrict__ match,
                                                              double* __restrict__ partials) {
+  constexpr bool kPlane = kMode >= 1;
   constexpr int NS = kPlane ? kIcpPlaneSums : kIcpSums;
   __shared__ double s[4][NS];
   const int p = blk_prob[blockIdx.x];
@@ -233,6 +309,9 @@ __global__ __launch_bounds__(kIcpBlock) void icp_corr_kernel(const IcpDesc* __re
         }
 #pragma unroll
         for (int r = 0; r < 6; ++r) v[23 + r] = wr * J[r];
+      } else if (kMode == 2 && d.method == kIcpMethodGicp) {  // uniform over the block
+        if constexpr (kMode == 2)
+          icp_gicp_terms(pc, qc, state[p].T, cov_s + 6 * (d.s_off + i), cov_t + 6 * (d.t_off + bj), v);
       } else {
 #pragma unroll
         for (int r = 0; r < 3; ++r) {
@@ -296,10 +375,11 @@ __device__ void icp_plane_step(const double* tot, const double* c, double* U) {
   }
 }
 
-template <bool kPlane>
+template <int kMode>
 __global__ __launch_bounds__(256) void icp_finalize_kernel(const IcpDesc* __restrict__ descs,
                                                            IcpState* __restrict__ state,
                                                            const double* __restrict__ partials) {
+  constexpr bool kPlane = kMode >= 1;
   constexpr int NS = kPlane ? kIcpPlaneSums : kIcpSums;
   __shared__ double s[4][NS];
   __shared__ double tot[NS];
@@ -334,8 +414,8 @@ __global__ __launch_bounds__(256) void icp_finalize_kernel(const IcpDesc* __rest
   }
   // Umeyama without scaling on the sums centred on d.centre: H = sum p' q'^T - sum p' (sum q')^T / n
   double U[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
-  if (kPlane && d.method == kIcpMethodPlane) {
-    if (cnt > 0) icp_plane_step(tot, d.centre, U);
+  if (kPlane && (d.method == kIcpMethodPlane || (kMode == 2 && d.method == kIcpMethodGicp))) {
+    if (cnt > 0) icp_plane_step(tot, d.centre, U);  // Generalized ICP: the same 29 sums, the same solve
   } else if (cnt > 0) {
     double mp[3], mq[3], H[9], R[9];
     for (int r = 0; r < 3; ++r) {
@@ -380,6 +460,146 @@ __global__ __launch_bounds__(256) void icp_live_kernel(const IcpState* __restric
   if (threadIdx.x == 0) *live = n;
 }
 
+// ---- covariance estimation ---------------------------------------------------------------------------------------
+// One Jacobi rotation of the symmetric 3 x 3 a = {a00, a01, a02, a11, a12, a22} in the (P, Q) plane, O the third
+// index; V accumulates the rotations (columns = eigenvectors).  Indices are compile-time: everything stays in VGPRs.
+__device__ __forceinline__ constexpr int icp_sym(int i, int j) {
+  return i <= j ? (i == 0 ? j : i + j + 1) : (j == 0 ? i : i + j + 1);
+}
+
+template <int P, int Q, int O>
+__device__ __forceinline__ bool icp_jacobi_rotate(double (&a)[6], double (&V)[9]) {
+  constexpr int PQ = icp_sym(P, Q), PP = icp_sym(P, P), QQ = icp_sym(Q, Q), OP = icp_sym(O, P), OQ = icp_sym(O, Q);
+  const double apq = a[PQ], app = a[PP], aqq = a[QQ];
+  if (apq == 0.0 || fabs(apq) <= 1e-17 * (fabs(app) + fabs(aqq))) return false;
+  const double theta = (aqq - app) / (2.0 * apq);
+  const double t = (theta >= 0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(1.0 + theta * theta));
+  const double c = 1.0 / sqrt(1.0 + t * t), sn = t * c;
+  a[PP] = app - t * apq;
+  a[QQ] = aqq + t * apq;
+  a[PQ] = 0.0;
+  const double aop = a[OP], aoq = a[OQ];
+  a[OP] = c * aop - sn * aoq;
+  a[OQ] = sn * aop + c * aoq;
+  const double v0p = V[P], v0q = V[Q], v1p = V[3 + P], v1q = V[3 + Q], v2p = V[6 + P], v2q = V[6 + Q];
+  V[P] = c * v0p - sn * v0q;
+  V[Q] = sn * v0p + c * v0q;
+  V[3 + P] = c * v1p - sn * v1q;
+  V[3 + Q] = sn * v1p + c * v1q;
+  V[6 + P] = c * v2p - sn * v2q;
+  V[6 + Q] = sn * v2p + c * v2q;
+  return true;
+}
+
+template <int CAP>
+__global__ __launch_bounds__(kIcpCovBlock) void icp_cov_kernel(const IcpDesc* __restrict__ descs,
+                                                              const IcpCovDesc* __restrict__ covs,
+                                                              const int32_t* __restrict__ blk_prob,
+                                                              const double* __restrict__ q,
+                                                              const double* __restrict__ qs,
+                                                              const int32_t* __restrict__ qj,
+                                                              const int32_t* __restrict__ bstart,
+                                                              double* __restrict__ out) {
+  __shared__ double ld[CAP][kIcpCovBlock];   // slot-major: lane l owns ld[.][l]
+  __shared__ int32_t lj[CAP][kIcpCovBlock];
+  const int p = blk_prob[blockIdx.x];
+  const IcpDesc& d = descs[p];
+  const int lane = threadIdx.x;
+  const int64_t i = (int64_t)((int)blockIdx.x - d.blk_off) * kIcpCovBlock + lane;
+  if (i >= d.n_t) return;
+  const int cap = covs[p].max_nn < CAP ? covs[p].max_nn : CAP;  // <= CAP: every list index below stays inside
+  const double* xp = q + 3 * (d.t_off + i);
+  const double x[3] = {xp[0], xp[1], xp[2]};
+  const int64_t c0 = icp_cell(x[0], d.origin[0], d.inv_h), c1 = icp_cell(x[1], d.origin[1], d.inv_h),
+                c2 = icp_cell(x[2], d.origin[2], d.inv_h);
+  const double r2 = d.r2;
+  // A bucket reached through two neighbour cells repeats its candidates; a repeated (d2, j) is recognised at its
+  // place in the list (or is beyond a full list's last entry, like the first time) and is not inserted twice.
+  int m = 0;
+  for (int dz = -1; dz <= 1; ++dz)
+    for (int dy = -1; dy <= 1; ++dy)
+      for (int dx = -1; dx <= 1; ++dx) {
+        const int64_t b = d.b_off + icp_bucket(c0 + dx, c1 + dy, c2 + dz, d.tb_mask);
+        const int32_t k1 = bstart[b + 1];
+        for (int32_t k = bstart[b]; k < k1; ++k) {
+          const double e0 = x[0] - qs[3 * (int64_t)k], e1 = x[1] - qs[3 * (int64_t)k + 1],
+                       e2 = x[2] - qs[3 * (int64_t)k + 2];
+          const double d2 = (e0 * e0 + e1 * e1) + e2 * e2;
+          if (!(d2 < r2)) continue;
+          const int32_t j = qj[k];
+          int pos = m;  // the number of kept entries below (d2, j)
+          while (pos > 0) {
+            const double pd = ld[pos - 1][lane];
+            if (!(d2 < pd || (d2 == pd && j < lj[pos - 1][lane]))) break;
+            --pos;
+          }
+          if (pos > 0 && ld[pos - 1][lane] == d2 && lj[pos - 1][lane] == j) continue;  // seen before
+          if (pos == cap) continue;                                                    // not among the cap best
+          if (m < cap) ++m;
+          for (int t = m - 1; t > pos; --t) {  // t <= cap - 1 < CAP
+            ld[t][lane] = ld[t - 1][lane];
+            lj[t][lane] = lj[t - 1][lane];
+          }
+          ld[pos][lane] = d2;
+          lj[pos][lane] = j;
+        }
+      }
+  double nrm[3] = {0.0, 0.0, 0.0};
+  double scale = 0.0;  // (1 - eps) when a normal exists: C = I - scale n n^T; fewer than 3 neighbours: the identity
+  if (m >= 3) {
+    double s1[3] = {0.0, 0.0, 0.0}, s2[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    for (int k = 0; k < m; ++k) {  // ascending (d2, j)
+      const double* yp = q + 3 * (d.t_off + lj[k][lane]);
+      const double o0 = yp[0] - x[0], o1 = yp[1] - x[1], o2 = yp[2] - x[2];
+      s1[0] += o0;
+      s1[1] += o1;
+      s1[2] += o2;
+      s2[0] += o0 * o0;
+      s2[1] += o0 * o1;
+      s2[2] += o0 * o2;
+      s2[3] += o1 * o1;
+      s2[4] += o1 * o2;
+      s2[5] += o2 * o2;
+    }
+    const double dm = (double)m, dm1 = (double)(m - 1);
+    double a[6] = {(s2[0] - (s1[0] * s1[0]) / dm) / dm1, (s2[1] - (s1[0] * s1[1]) / dm) / dm1,
+                   (s2[2] - (s1[0] * s1[2]) / dm) / dm1, (s2[3] - (s1[1] * s1[1]) / dm) / dm1,
+                   (s2[4] - (s1[1] * s1[2]) / dm) / dm1, (s2[5] - (s1[2] * s1[2]) / dm) / dm1};
+    double V[9] = {1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0};
+    for (int sweep = 0; sweep < 16; ++sweep) {
+      bool rotated = icp_jacobi_rotate<0, 1, 2>(a, V);
+      rotated |= icp_jacobi_rotate<0, 2, 1>(a, V);
+      rotated |= icp_jacobi_rotate<1, 2, 0>(a, V);
+      if (!rotated) break;
+    }
+    // the column of the smallest diagonal entry, the first one on a tie
+    // (selected value by value: a selected column index would turn V into a scratch array)
+    const bool k1 = a[3] < a[0];
+    const double lam = k1 ? a[3] : a[0];
+    const bool k2 = a[5] < lam;
+    nrm[0] = k2 ? V[2] : (k1 ? V[1] : V[0]);
+    nrm[1] = k2 ? V[5] : (k1 ? V[4] : V[3]);
+    nrm[2] = k2 ? V[8] : (k1 ? V[7] : V[6]);
+    const double len = sqrt((nrm[0] * nrm[0] + nrm[1] * nrm[1]) + nrm[2] * nrm[2]);
+    nrm[0] = nrm[0] / len;
+    nrm[1] = nrm[1] / len;
+    nrm[2] = nrm[2] / len;
+    scale = 1.0 - covs[p].eps;
+  }
+  double* o = out + 9 * (d.t_off + i);
+  const double u0 = scale * nrm[0], u1 = scale * nrm[1], u2 = scale * nrm[2];
+  const double c01 = 0.0 - u0 * nrm[1], c02 = 0.0 - u0 * nrm[2], c12 = 0.0 - u1 * nrm[2];
+  o[0] = 1.0 - u0 * nrm[0];
+  o[1] = c01;
+  o[2] = c02;
+  o[3] = c01;
+  o[4] = 1.0 - u1 * nrm[1];
+  o[5] = c12;
+  o[6] = c02;
+  o[7] = c12;
+  o[8] = 1.0 - u2 * nrm[2];
+}
+
 // ---- launchers ------------------------------------------------------------------------------------------------
 void launch_icp_index(hipStream_t s, const IcpDesc* d_desc, const int32_t* d_tblk_prob, int n_tblk, int batch,
                       const double* d_q, int32_t* d_tbucket, int32_t* d_bcount, int32_t* d_bstart,
@@ -394,21 +614,44 @@ void launch_icp_index(hipStream_t s, const IcpDesc* d_desc, const int32_t* d_tbl
                        d_cursor, d_qs, d_qj);
 }
 
+template <int kMode>
+static void icp_iteration(hipStream_t s, const IcpDesc* d_desc, IcpState* d_state, const int32_t* d_blk_prob, int n_blk,
+                          int batch, double* d_x, const double* d_qs, const int32_t* d_qj, const int32_t* d_bstart,
+                          const double* d_normals, const double* d_cov_s, const double* d_cov_t, int32_t* d_match,
+                          double* d_partials) {
+  if (n_blk > 0)
+    hipLaunchKernelGGL(icp_corr_kernel<kMode>, dim3(n_blk), dim3(kIcpBlock), 0, s, d_desc, d_state, d_blk_prob, d_x,
+                       d_qs, d_qj, d_bstart, d_normals, d_cov_s, d_cov_t, d_match, d_partials);
+  hipLaunchKernelGGL(icp_finalize_kernel<kMode>, dim3(batch), dim3(256), 0, s, d_desc, d_state, d_partials);
+}
+
+// mode: 0 no point-to-plane and no Generalized-ICP problem in the call; 1 a point-to-plane problem (the wider
+// partials, the method read per block); 2 a Generalized-ICP problem
 void launch_icp_iteration(hipStream_t s, const IcpDesc* d_desc, IcpState* d_state, const int32_t* d_blk_prob,
                           int n_blk, int batch, double* d_x, const double* d_qs, const int32_t* d_qj,
-                          const int32_t* d_bstart, const double* d_normals, bool plane, int32_t* d_match,
-                          double* d_partials) {
-  if (plane) {  // at least one point-to-plane problem: the wider partials, the method read per block
-    if (n_blk > 0)
-      hipLaunchKernelGGL(icp_corr_kernel<true>, dim3(n_blk), dim3(kIcpBlock), 0, s, d_desc, d_state, d_blk_prob,
-                         d_x, d_qs, d_qj, d_bstart, d_normals, d_match, d_partials);
-    hipLaunchKernelGGL(icp_finalize_kernel<true>, dim3(batch), dim3(256), 0, s, d_desc, d_state, d_partials);
-    return;
-  }
-  if (n_blk > 0)
-    hipLaunchKernelGGL(icp_corr_kernel<false>, dim3(n_blk), dim3(kIcpBlock), 0, s, d_desc, d_state, d_blk_prob, d_x,
-                       d_qs, d_qj, d_bstart, d_normals, d_match, d_partials);
-  hipLaunchKernelGGL(icp_finalize_kernel<false>, dim3(batch), dim3(256), 0, s, d_desc, d_state, d_partials);
+                          const int32_t* d_bstart, const double* d_normals, const double* d_cov_s,
+                          const double* d_cov_t, int mode, int32_t* d_match, double* d_partials) {
+  if (mode == 2)
+    icp_iteration<2>(s, d_desc, d_state, d_blk_prob, n_blk, batch, d_x, d_qs, d_qj, d_bstart, d_normals, d_cov_s,
+                     d_cov_t, d_match, d_partials);
+  else if (mode == 1)
+    icp_iteration<1>(s, d_desc, d_state, d_blk_prob, n_blk, batch, d_x, d_qs, d_qj, d_bstart, d_normals, d_cov_s,
+                     d_cov_t, d_match, d_partials);
+  else
+    icp_iteration<0>(s, d_desc, d_state, d_blk_prob, n_blk, batch, d_x, d_qs, d_qj, d_bstart, d_normals, d_cov_s,
+                     d_cov_t, d_match, d_partials);
+}
+
+void launch_icp_covariances(hipStream_t s, const IcpDesc* d_desc, const IcpCovDesc* d_cov, const int32_t* d_blk_prob,
+                            int n_blk, int max_nn, const double* d_q, const double* d_qs, const int32_t* d_qj,
+                            const int32_t* d_bstart, double* d_out) {
+  if (n_blk <= 0) return;
+  if (max_nn <= kIcpCovSmallNN)  // the capacity only bounds the list: it never changes a result
+    hipLaunchKernelGGL(icp_cov_kernel<kIcpCovSmallNN>, dim3(n_blk), dim3(kIcpCovBlock), 0, s, d_desc, d_cov,
+                       d_blk_prob, d_q, d_qs, d_qj, d_bstart, d_out);
+  else
+    hipLaunchKernelGGL(icp_cov_kernel<kIcpCovMaxNN>, dim3(n_blk), dim3(kIcpCovBlock), 0, s, d_desc, d_cov, d_blk_prob,
+                       d_q, d_qs, d_qj, d_bstart, d_out);
 }
 
 void launch_icp_live(hipStream_t s, const IcpState* d_state, int batch, int32_t* d_live) {

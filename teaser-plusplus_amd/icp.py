@@ -2,8 +2,9 @@
 ``registration_icp(source, target, max_correspondence_distance, init, estimation_method, criteria)`` and the batched
 ``registration_icp_batch``.  The semantics are those of Open3D's RegistrationICP with
 TransformationEstimationPointToPoint(with_scaling=False) or TransformationEstimationPointToPlane(kernel) (target
-normals given by the caller, robust kernels L2 / Huber / Cauchy / GM / Tukey), written out in include/teaser_hip.h
-("ICP refinement").
+normals given by the caller, robust kernels L2 / Huber / Cauchy / GM / Tukey) or the formulation of
+TransformationEstimationForGeneralizedICP (per-point covariances of both clouds, L2 only; ``estimate_covariances``
+computes them on the GPU), written out in include/teaser_hip.h ("ICP refinement").
 
 One library handle is kept per device between calls (no HIP context per call); calls from several threads are safe --
 each handle has a lock, so calls for one device run one after the other.  device=-1 means the calling thread's
@@ -47,6 +48,9 @@ def declare(L):
     L.teaser_hip_icp_estimation_default.argtypes = [C.POINTER(IcpEstimationC)]
     L.teaser_hip_icp_batch_ex.argtypes = L.teaser_hip_icp_batch.argtypes + [C.POINTER(_dp), C.POINTER(IcpEstimationC)]
     L.teaser_hip_icp_solve_ex.argtypes = L.teaser_hip_icp_solve.argtypes + [_dp, C.POINTER(IcpEstimationC)]
+    L.teaser_hip_icp_batch_cov.argtypes = L.teaser_hip_icp_batch_ex.argtypes + [C.POINTER(_dp), C.POINTER(_dp)]
+    L.teaser_hip_icp_solve_cov.argtypes = L.teaser_hip_icp_solve_ex.argtypes + [_dp, _dp]
+    L.teaser_hip_icp_covariances_batch.argtypes = [_vp, C.c_int32, C.POINTER(_dp), _ip, _dp, _ip, _dp, C.POINTER(_dp)]
 
 
 class ICPConvergenceCriteria:
@@ -122,6 +126,25 @@ class TransformationEstimationPointToPlane:
         if not isinstance(kernel, _RobustKernel):
             raise ValueError("kernel must be L2Loss, HuberLoss, CauchyLoss, GMLoss or TukeyLoss")
         self.kernel = kernel
+
+
+class TransformationEstimationForGeneralizedICP:
+    """Open3D's Generalized-ICP estimation (plane-to-plane), L2 only: Open3D's robust kernels weight the whitened
+    residual, which is not offered here, so a kernel other than None / L2Loss is refused.  The covariances of both
+    clouds are given to registration_icp(..., source_covariances=..., target_covariances=...); epsilon is the value
+    estimate_covariances is called with when registration_generalized_icp computes them."""
+
+    def __init__(self, epsilon=1e-3, kernel=None):
+        if kernel is not None and not isinstance(kernel, L2Loss):
+            raise ValueError("TransformationEstimationForGeneralizedICP: only the L2 kernel is supported")
+        epsilon = float(epsilon)
+        if not (np.isfinite(epsilon) and epsilon > 0):
+            raise ValueError("epsilon must be finite and > 0")
+        self.epsilon = epsilon
+        self.kernel = L2Loss()
+
+
+MAX_NN_LIMIT = 100  # TEASER_HIP_ICP_COV_MAX_NN
 
 
 class RegistrationResult:
@@ -219,16 +242,46 @@ def _estimation(m):
         return 0, 0, 1.0
     if isinstance(m, TransformationEstimationPointToPlane):
         return 1, m.kernel.code, m.kernel.k
-    raise ValueError("estimation_method must be TransformationEstimationPointToPoint(with_scaling=False) or "
-                     "TransformationEstimationPointToPlane(kernel)")
+    if isinstance(m, TransformationEstimationForGeneralizedICP):
+        return 2, 0, 1.0
+    raise ValueError("estimation_method must be TransformationEstimationPointToPoint(with_scaling=False), "
+                     "TransformationEstimationPointToPlane(kernel) or TransformationEstimationForGeneralizedICP()")
+
+
+def _covariances(a, n, what, k):
+    a = np.ascontiguousarray(np.asarray(a, dtype=np.float64))
+    if a.size == 0 and n == 0:
+        return np.zeros((0, 3, 3))
+    if a.shape not in ((n, 3, 3), (n, 9)):
+        raise ValueError("%s must be %d x 3 x 3 (or %d x 9), got shape %s (problem %d)" % (what, n, n, a.shape, k))
+    return a.reshape(n, 3, 3)
+
+
+def _per_problem_covariances(given, ests, clouds, what):
+    """One n x 3 x 3 array per Generalized-ICP problem (None elsewhere); ValueError when one is missing."""
+    b = len(ests)
+    out = [None] * b
+    if not any(m[0] == 2 for m in ests):
+        return out
+    if given is None or len(given) != b:
+        raise ValueError("Generalized ICP needs %s: one entry per problem" % what)
+    for k in range(b):
+        if ests[k][0] != 2:
+            continue
+        if given[k] is None:
+            raise ValueError("Generalized ICP needs %s (problem %d)" % (what, k))
+        out[k] = _covariances(given[k], len(clouds[k]), what, k)
+    return out
 
 
 def registration_icp_batch(sources, targets, max_correspondence_distance, inits=None, criteria=None, device=-1,
-                           estimation_methods=None, target_normals=None):
+                           estimation_methods=None, target_normals=None, source_covariances=None,
+                           target_covariances=None):
     """One launch sequence for many independent problems (mixed sizes allowed).  max_correspondence_distance and
     criteria: one value for all or one per problem; inits: None (identity), one 4 x 4 for all, or one per problem;
     estimation_methods: None (point-to-point), one for all or one per problem; target_normals: None, or one entry per
-    problem (None for a point-to-point problem, else one normal per target point).
+    problem (None for a point-to-point problem, else one normal per target point); source_covariances /
+    target_covariances: None, or one entry per problem (None unless the problem is Generalized ICP, else n x 3 x 3).
     Returns a list of RegistrationResult, each identical to the same problem run alone."""
     from . import TeaserHipError, lib
     srcs = [_cloud(s, "source") for s in sources]
@@ -255,6 +308,9 @@ def registration_icp_batch(sources, targets, max_correspondence_distance, inits=
                 raise ValueError("target_normals must have the target's shape %s, got %s (problem %d)"
                                  % (dsts[k].shape, nv.shape, k))
             normals[k] = nv
+    gicp = any(m[0] == 2 for m in ests)
+    cov_s = _per_problem_covariances(source_covariances, ests, srcs, "source_covariances")
+    cov_t = _per_problem_covariances(target_covariances, ests, dsts, "target_covariances")
     rs = np.broadcast_to(np.asarray(max_correspondence_distance, dtype=np.float64), (b,))
     crit = criteria if isinstance(criteria, (list, tuple)) else [criteria] * b
     if len(crit) != b:
@@ -279,7 +335,13 @@ def registration_icp_batch(sources, targets, max_correspondence_distance, inits=
     args = (h, b, sp, n_s.ctypes.data_as(_ip), tp, n_t.ctypes.data_as(_ip),
             None if init is None else init.ctypes.data_as(_dp), params, out, cp)
     with lock:  # the handle serves one call at a time
-        if plane:
+        if gicp:  # the entry that takes covariances; it serves the other two methods of a mixed batch too
+            nptr = (_dp * max(b, 1))(*[None if nv is None else nv.ctypes.data_as(_dp) for nv in normals])
+            est = (IcpEstimationC * max(b, 1))(*[IcpEstimationC(*m) for m in ests])
+            csp = (_dp * max(b, 1))(*[None if c is None else c.ctypes.data_as(_dp) for c in cov_s])
+            ctp = (_dp * max(b, 1))(*[None if c is None else c.ctypes.data_as(_dp) for c in cov_t])
+            rc = L.teaser_hip_icp_batch_cov(*args, nptr, est, csp, ctp)
+        elif plane:
             nptr = (_dp * max(b, 1))(*[None if nv is None else nv.ctypes.data_as(_dp) for nv in normals])
             est = (IcpEstimationC * max(b, 1))(*[IcpEstimationC(*m) for m in ests])
             rc = L.teaser_hip_icp_batch_ex(*args, nptr, est)
@@ -298,17 +360,108 @@ def registration_icp_batch(sources, targets, max_correspondence_distance, inits=
 
 
 def registration_icp(source, target, max_correspondence_distance, init=np.eye(4), estimation_method=None,
-                     criteria=None, device=-1, *, target_normals=None):
+                     criteria=None, device=-1, *, target_normals=None, source_covariances=None,
+                     target_covariances=None):
     """Open3D's registration_icp (same argument order): refines `init` so that it maps source onto target.
     source / target: n x 3 points (np.asarray(pcd.points)).  estimation_method: None or
     TransformationEstimationPointToPoint() (with_scaling=False), or TransformationEstimationPointToPlane(kernel), which
-    needs target_normals (n_t x 3, np.asarray(target_pcd.normals))."""
+    needs target_normals (n_t x 3, np.asarray(target_pcd.normals)), or TransformationEstimationForGeneralizedICP(),
+    which needs source_covariances (n_s x 3 x 3) and target_covariances (n_t x 3 x 3)."""
     if estimation_method is not None and not isinstance(
-            estimation_method, (TransformationEstimationPointToPoint, TransformationEstimationPointToPlane)):
-        raise ValueError("only TransformationEstimationPointToPoint(with_scaling=False) and "
-                         "TransformationEstimationPointToPlane(kernel) are supported")
+            estimation_method, (TransformationEstimationPointToPoint, TransformationEstimationPointToPlane,
+                                TransformationEstimationForGeneralizedICP)):
+        raise ValueError("only TransformationEstimationPointToPoint(with_scaling=False), "
+                         "TransformationEstimationPointToPlane(kernel) and "
+                         "TransformationEstimationForGeneralizedICP() are supported")
     if isinstance(estimation_method, TransformationEstimationPointToPlane) and target_normals is None:
         raise ValueError("TransformationEstimationPointToPlane needs target_normals")
+    if isinstance(estimation_method, TransformationEstimationForGeneralizedICP):
+        if source_covariances is None:
+            raise ValueError("TransformationEstimationForGeneralizedICP needs source_covariances")
+        if target_covariances is None:
+            raise ValueError("TransformationEstimationForGeneralizedICP needs target_covariances")
     return registration_icp_batch([source], [target], max_correspondence_distance, inits=_init(init)[None],
                                   criteria=[criteria], device=device, estimation_methods=[estimation_method],
-                                  target_normals=None if target_normals is None else [target_normals])[0]
+                                  target_normals=None if target_normals is None else [target_normals],
+                                  source_covariances=None if source_covariances is None else [source_covariances],
+                                  target_covariances=None if target_covariances is None else [target_covariances])[0]
+
+
+def covariances_from_normals(normals, epsilon=1e-3):
+    """C = I - (1 - epsilon) n n^T / (n^T n) per normal (n x 3 -> n x 3 x 3): the covariance Generalized ICP gives a
+    point whose surface normal is n (eigenvalue epsilon along n, 1 across).  A zero or non-finite normal gives the
+    identity.  Host arithmetic; lets a caller reuse FPFHEstimation.getNormals()."""
+    epsilon = float(epsilon)
+    if not (np.isfinite(epsilon) and epsilon > 0):
+        raise ValueError("epsilon must be finite and > 0")
+    nv = _cloud(normals, "normals")
+    out = np.tile(np.eye(3), (len(nv), 1, 1))
+    with np.errstate(all="ignore"):
+        nn = (nv[:, 0] * nv[:, 0] + nv[:, 1] * nv[:, 1]) + nv[:, 2] * nv[:, 2]
+    ok = np.isfinite(nv).all(axis=1) & np.isfinite(nn) & (nn > 0)
+    v = nv[ok]
+    out[ok] -= ((1.0 - epsilon) * v)[:, :, None] * v[:, None, :] / nn[ok][:, None, None]
+    return out
+
+
+def estimate_covariances_batch(clouds, radius, max_nn=20, epsilon=1e-3, device=-1):
+    """Generalized-ICP covariances of many clouds in one launch sequence (include/teaser_hip.h, "Covariance
+    estimation"): per point the max_nn nearest neighbours inside `radius` (the point itself included), their sample
+    covariance, and C = I - (1 - epsilon) n n^T with n its smallest eigenvector; the identity below 3 neighbours.
+    radius, max_nn, epsilon: one value for all clouds or one per cloud.  Returns a list of n x 3 x 3 arrays, each
+    identical to the same cloud estimated alone."""
+    from . import TeaserHipError, lib
+    pts = [_cloud(c, "points") for c in clouds]
+    b = len(pts)
+    rs = np.ascontiguousarray(np.broadcast_to(np.asarray(radius, dtype=np.float64), (b,)))
+    es = np.ascontiguousarray(np.broadcast_to(np.asarray(epsilon, dtype=np.float64), (b,)))
+    ks = np.ascontiguousarray(np.broadcast_to(np.asarray(max_nn), (b,)).astype(np.int32))
+    if b and (ks.min() < 3 or ks.max() > MAX_NN_LIMIT):
+        raise ValueError("max_nn must lie in [3, %d]" % MAX_NN_LIMIT)
+    if b and not (np.isfinite(rs).all() and (rs > 0).all()):
+        raise ValueError("radius must be finite and > 0")
+    if b and not (np.isfinite(es).all() and (es > 0).all()):
+        raise ValueError("epsilon must be finite and > 0")
+    out = [np.empty((len(p), 3, 3)) for p in pts]
+    if b == 0:
+        return out
+    h, lock = _handle(device)
+    L = lib()
+    n = np.array([len(p) for p in pts], dtype=np.int32)
+    pp = (_dp * b)(*[p.ctypes.data_as(_dp) for p in pts])
+    op = (_dp * b)(*[o.ctypes.data_as(_dp) for o in out])
+    with lock:
+        rc = L.teaser_hip_icp_covariances_batch(h, b, pp, n.ctypes.data_as(_ip), rs.ctypes.data_as(_dp),
+                                                ks.ctypes.data_as(_ip), es.ctypes.data_as(_dp), op)
+        err = L.teaser_hip_icp_last_error(h).decode() if rc != 0 else ""
+    if rc != 0:
+        raise TeaserHipError(rc, err)
+    return out
+
+
+def estimate_covariances(points, radius, max_nn=20, epsilon=1e-3, device=-1):
+    """estimate_covariances_batch for one cloud: n x 3 points -> n x 3 x 3 covariances."""
+    return estimate_covariances_batch([points], radius, max_nn, epsilon, device)[0]
+
+
+def registration_generalized_icp(source, target, max_correspondence_distance, init=np.eye(4), estimation_method=None,
+                                 criteria=None, source_covariances=None, target_covariances=None,
+                                 search_radius=None, max_nn=20, device=-1):
+    """Open3D's registration_generalized_icp (same leading arguments).  Covariances that are not given are estimated on
+    the GPU from the cloud itself with estimate_covariances(cloud, search_radius, max_nn, estimation.epsilon); without
+    them and without search_radius the call raises ValueError."""
+    est = TransformationEstimationForGeneralizedICP() if estimation_method is None else estimation_method
+    if not isinstance(est, TransformationEstimationForGeneralizedICP):
+        raise ValueError("estimation_method must be TransformationEstimationForGeneralizedICP()")
+    missing = [c for c, given in ((source, source_covariances), (target, target_covariances)) if given is None]
+    if missing:
+        if search_radius is None:
+            raise ValueError("registration_generalized_icp needs source_covariances and target_covariances, or a "
+                             "search_radius to estimate them with")
+        found = iter(estimate_covariances_batch(missing, search_radius, max_nn, est.epsilon, device))
+        if source_covariances is None:
+            source_covariances = next(found)
+        if target_covariances is None:
+            target_covariances = next(found)
+    return registration_icp(source, target, max_correspondence_distance, init, est, criteria, device,
+                            source_covariances=source_covariances, target_covariances=target_covariances)
