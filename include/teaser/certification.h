@@ -19,6 +19,7 @@
 #define TEASER_HIP_CERT_HAVE_EIGEN 0
 #endif
 
+#include "teaser/handle.h"
 #include "teaser_hip.h"
 
 namespace teaser {
@@ -49,9 +50,6 @@ class DRSCertifier {
   }
   DRSCertifier(const DRSCertifier&) = delete;
   DRSCertifier& operator=(const DRSCertifier&) = delete;
-  ~DRSCertifier() {
-    if (h_) teaser_hip_solver_destroy(h_);
-  }
 
   // R row-major 3 x 3; src / dst: n points, xyz interleaved (the memory of the reference's 3 x N column-major
   // matrices); theta: +1 inlier / -1 outlier.
@@ -59,12 +57,7 @@ class DRSCertifier {
     if (!h_) {
       teaser_params_c c;
       teaser_hip_params_default(&c);
-      const int32_t rc = teaser_hip_solver_create(&c, /*device=*/-1, &h_);
-      if (rc != TEASER_HIP_OK) {
-        h_ = nullptr;
-        throw std::runtime_error("teaser::DRSCertifier: teaser_hip_solver_create failed (status " +
-                                 std::to_string(rc) + "; 3 = no HIP device)");
-      }
+      h_.create("teaser::DRSCertifier", &c);
     }
     teaser_certifier_params_c p;
     p.noise_bound = params_.noise_bound;
@@ -109,7 +102,7 @@ class DRSCertifier {
 
  private:
   Params params_;
-  teaser_hip_solver* h_ = nullptr;
+  detail::LazySolver h_;
 };
 
 }  // namespace teaser

@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "teaser/geometry.h"
+#include "teaser/handle.h"
 #include "teaser_hip.h"
 
 namespace teaser {
@@ -34,24 +35,13 @@ class FPFHEstimation {
   FPFHEstimation() = default;
   FPFHEstimation(const FPFHEstimation&) = delete;
   FPFHEstimation& operator=(const FPFHEstimation&) = delete;
-  ~FPFHEstimation() {
-    if (h_) teaser_hip_solver_destroy(h_);
-    if (fh_) teaser_hip_features_destroy(fh_);
-  }
 
   // fpfh.h:40-42, fpfh.cc:15-43: normals with a radius search (viewpoint at the origin), then FPFH.
   // Throws std::runtime_error when no MI355X is visible (no CPU path) or the call fails.
   FPFHCloudPtr computeFPFHFeatures(const PointCloud& input_cloud, double normal_search_radius = 0.03,
                                    double fpfh_search_radius = 0.05) {
     static_assert(sizeof(PointXYZ) == 12 && sizeof(FPFHSignature33) == 132 && sizeof(Normal) == 12, "packed");
-    if (!h_) {
-      const int32_t rc = teaser_hip_solver_create(nullptr, /*device=*/-1, &h_);
-      if (rc != TEASER_HIP_OK) {
-        h_ = nullptr;
-        throw std::runtime_error("teaser::FPFHEstimation: teaser_hip_solver_create failed (status " +
-                                 std::to_string(rc) + "; 3 = no HIP device)");
-      }
-    }
+    h_.create("teaser::FPFHEstimation");
     const int32_t n = (int32_t)input_cloud.size();
     FPFHCloudPtr out = std::make_shared<FPFHCloud>((size_t)n);
     normals_.assign((size_t)n, Normal());
@@ -73,14 +63,7 @@ class FPFHEstimation {
   std::vector<FPFHCloud> computeFPFHFeaturesBatch(const std::vector<PointCloud>& input_clouds,
                                                   double normal_search_radius = 0.03,
                                                   double fpfh_search_radius = 0.05) {
-    if (!fh_) {
-      const int32_t rc = teaser_hip_features_create(/*device=*/-1, &fh_);
-      if (rc != TEASER_HIP_OK) {
-        fh_ = nullptr;
-        throw std::runtime_error("teaser::FPFHEstimation: teaser_hip_features_create failed (status " +
-                                 std::to_string(rc) + "; 3 = no HIP device)");
-      }
-    }
+    fh_.create("teaser::FPFHEstimation");
     const size_t batch = input_clouds.size();
     std::vector<FPFHCloud> out(batch);
     batch_normals_.assign(batch, NormalCloud());
@@ -107,8 +90,8 @@ class FPFHEstimation {
   const std::vector<NormalCloud>& getNormalsBatch() const { return batch_normals_; }
 
  private:
-  teaser_hip_solver* h_ = nullptr;
-  teaser_hip_features* fh_ = nullptr;
+  detail::LazyFeatures fh_;  // (declared first: destroyed after the solver)
+  detail::LazySolver h_;
   NormalCloud normals_;
   std::vector<NormalCloud> batch_normals_;
 };

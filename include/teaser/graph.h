@@ -25,6 +25,7 @@
 #define TEASER_HIP_GRAPH_HAVE_EIGEN 0
 #endif
 
+#include "teaser/handle.h"
 #include "teaser_hip.h"
 
 namespace teaser {
@@ -129,9 +130,6 @@ class MaxCliqueSolver {
   MaxCliqueSolver(Params params) : params_(params) {}
   MaxCliqueSolver(const MaxCliqueSolver&) = delete;
   MaxCliqueSolver& operator=(const MaxCliqueSolver&) = delete;
-  ~MaxCliqueSolver() {
-    if (h_) teaser_hip_solver_destroy(h_);
-  }
 
   // Vertices of a maximum clique, ascending (the reference returns pmc's order and its caller sorts,
   // registration.cc:636).  Throws std::runtime_error when no MI355X is visible (no CPU path).
@@ -144,21 +142,12 @@ class MaxCliqueSolver {
     c.kcore_heuristic_threshold = params_.kcore_heuristic_threshold;
     c.max_clique_time_limit = params_.time_limit;
     c.max_clique_num_threads = params_.num_threads;
-    int32_t rc;
-    if (!h_) {
-      rc = teaser_hip_solver_create(&c, /*device=*/-1, &h_);
-      if (rc != TEASER_HIP_OK) {
-        h_ = nullptr;
-        throw std::runtime_error("teaser::MaxCliqueSolver: teaser_hip_solver_create failed (status " +
-                                 std::to_string(rc) + "; 3 = no HIP device)");
-      }
-    } else if ((rc = teaser_hip_solver_reset(h_, &c)) != TEASER_HIP_OK) {
+    if (!h_.create("teaser::MaxCliqueSolver", &c) && teaser_hip_solver_reset(h_, &c) != TEASER_HIP_OK)
       throw std::runtime_error("teaser::MaxCliqueSolver: reset failed");
-    }
     const std::vector<uint64_t> bm = graph.toBitmap();
     std::vector<int32_t> clique((size_t)n);
     int32_t size = 0, exact = 0;
-    rc = teaser_hip_max_clique(h_, bm.data(), n, clique.data(), &size, &exact);
+    const int32_t rc = teaser_hip_max_clique(h_, bm.data(), n, clique.data(), &size, &exact);
     if (rc != TEASER_HIP_OK && rc != TEASER_HIP_ERR_TIME_LIMIT)  // time limit: the incumbent, as graph.cc:44
       throw std::runtime_error(std::string("teaser_hip_max_clique status ") + std::to_string(rc) + ": " +
                                teaser_hip_last_error(h_));
@@ -170,7 +159,7 @@ class MaxCliqueSolver {
 
  private:
   Params params_;
-  teaser_hip_solver* h_ = nullptr;
+  detail::LazySolver h_;
   bool exact_search_ran_ = false;
 };
 

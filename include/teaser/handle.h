@@ -1,0 +1,53 @@
+// teaser/handle.h -- the library handles that the classes of this directory create on first use and own.
+#pragma once
+
+#include <stdexcept>
+#include <string>
+
+#include "teaser_hip.h"
+
+namespace teaser {
+namespace detail {
+
+// Owns one handle of type H: nullptr until the derived holder's create(), destroyed with the holder.  Converts to
+// H* so that it stands where the C functions take the handle.
+template <class H, int32_t (*Destroy)(H*)>
+class LazyHandle {
+ public:
+  LazyHandle() = default;
+  LazyHandle(const LazyHandle&) = delete;
+  LazyHandle& operator=(const LazyHandle&) = delete;
+  ~LazyHandle() {
+    if (h_) Destroy(h_);
+  }
+  operator H*() const { return h_; }
+
+ protected:
+  // rc: what teaser_hip_<kind>_create returned when it filled h_; `who` is the class the exception names.
+  void created(const char* who, const char* kind, int32_t rc) {
+    if (rc == TEASER_HIP_OK) return;
+    h_ = nullptr;
+    throw std::runtime_error(std::string(who) + ": teaser_hip_" + kind + "_create failed (status " +
+                             std::to_string(rc) + "; 3 = no HIP device)");
+  }
+  H* h_ = nullptr;
+};
+
+struct LazySolver : LazyHandle<teaser_hip_solver, teaser_hip_solver_destroy> {
+  // Creates the solver from `params` (nullptr: the defaults) on the current device unless it exists already;
+  // returns whether this call created it.  Throws std::runtime_error when it cannot (no MI355X: no CPU path).
+  bool create(const char* who, const teaser_params_c* params = nullptr) {
+    if (h_) return false;
+    created(who, "solver", teaser_hip_solver_create(params, /*device=*/-1, &h_));
+    return true;
+  }
+};
+
+struct LazyFeatures : LazyHandle<teaser_hip_features, teaser_hip_features_destroy> {
+  void create(const char* who) {
+    if (!h_) created(who, "features", teaser_hip_features_create(/*device=*/-1, &h_));
+  }
+};
+
+}  // namespace detail
+}  // namespace teaser

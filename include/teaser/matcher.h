@@ -16,6 +16,7 @@
 
 #include "teaser/fpfh.h"
 #include "teaser/geometry.h"
+#include "teaser/handle.h"
 #include "teaser_hip.h"
 
 namespace teaser {
@@ -25,10 +26,6 @@ class Matcher {
   Matcher() = default;
   Matcher(const Matcher&) = delete;
   Matcher& operator=(const Matcher&) = delete;
-  ~Matcher() {
-    if (h_) teaser_hip_solver_destroy(h_);
-    if (fh_) teaser_hip_features_destroy(fh_);
-  }
 
   // matcher.h:40-44: (source index, target index) pairs, sorted, unique
   std::vector<std::pair<int, int>> calculateCorrespondences(const PointCloud& source_points,
@@ -38,14 +35,7 @@ class Matcher {
                                                             bool use_absolute_scale = true, bool use_crosscheck = true,
                                                             bool use_tuple_test = true, float tuple_scale = 0) {
     (void)use_absolute_scale;
-    if (!h_) {
-      const int32_t rc = teaser_hip_solver_create(nullptr, /*device=*/-1, &h_);
-      if (rc != TEASER_HIP_OK) {
-        h_ = nullptr;
-        throw std::runtime_error("teaser::Matcher: teaser_hip_solver_create failed (status " + std::to_string(rc) +
-                                 "; 3 = no HIP device)");
-      }
-    }
+    h_.create("teaser::Matcher");
     static_assert(sizeof(std::pair<int, int>) == 8, "packed pairs expected");
     std::vector<std::pair<int, int>> out(source_features.size() + target_features.size() + 1);
     int64_t cnt = (int64_t)out.size();
@@ -80,14 +70,7 @@ class Matcher {
     const bool tuple = use_tuple_test && tuple_scale != 0;
     if (target_features.size() != batch || (tuple && (source_points.size() != batch || target_points.size() != batch)))
       throw std::invalid_argument("teaser::Matcher::calculateCorrespondencesBatch: lists of different lengths");
-    if (!fh_) {
-      const int32_t rc = teaser_hip_features_create(/*device=*/-1, &fh_);
-      if (rc != TEASER_HIP_OK) {
-        fh_ = nullptr;
-        throw std::runtime_error("teaser::Matcher: teaser_hip_features_create failed (status " + std::to_string(rc) +
-                                 "; 3 = no HIP device)");
-      }
-    }
+    fh_.create("teaser::Matcher");
     std::vector<std::vector<std::pair<int, int>>> out(batch);
     std::vector<const float*> fs(batch), ft(batch);
     std::vector<int32_t*> pairs(batch);
@@ -122,8 +105,8 @@ class Matcher {
   }
 
  private:
-  teaser_hip_solver* h_ = nullptr;
-  teaser_hip_features* fh_ = nullptr;
+  detail::LazyFeatures fh_;  // (declared first: destroyed after the solver)
+  detail::LazySolver h_;
 };
 
 }  // namespace teaser

@@ -43,6 +43,7 @@
 
 #include "teaser/geometry.h"
 #include "teaser/graph.h"
+#include "teaser/handle.h"
 #include "teaser_hip.h"
 
 namespace teaser {
@@ -141,22 +142,9 @@ namespace detail {
 // One process-wide "stage" handle per thread for the stand-alone stage-solver classes below (they carry
 // only their parameters, like the reference's; the device context lives here).  Throws without a GPU.
 inline teaser_hip_solver* stage_handle() {
-  struct Holder {
-    teaser_hip_solver* h = nullptr;
-    ~Holder() {
-      if (h) teaser_hip_solver_destroy(h);
-    }
-  };
-  static thread_local Holder holder;
-  if (!holder.h) {
-    const int32_t rc = teaser_hip_solver_create(nullptr, /*device=*/-1, &holder.h);
-    if (rc != TEASER_HIP_OK) {
-      holder.h = nullptr;
-      throw std::runtime_error("teaser stage solver: teaser_hip_solver_create failed (status " + std::to_string(rc) +
-                               "; 3 = no HIP device)");
-    }
-  }
-  return holder.h;
+  static thread_local LazySolver holder;
+  holder.create("teaser stage solver");
+  return holder;
 }
 inline void stage_params(teaser_hip_solver* h, double noise_bound, double cbar2, bool estimate_scaling, int alg,
                          double gnc_factor, size_t max_iterations, double cost_threshold) {
@@ -380,9 +368,6 @@ class RobustRegistrationSolver {
   }
   RobustRegistrationSolver(const RobustRegistrationSolver&) = delete;
   RobustRegistrationSolver& operator=(const RobustRegistrationSolver&) = delete;
-  ~RobustRegistrationSolver() {
-    if (h_) teaser_hip_solver_destroy(h_);
-  }
 
   // registration.h:891.  Throws std::runtime_error when no MI355X is visible: the product has no
   // CPU path (the reference's constructor cannot fail; a host without a GPU must say so loudly).
@@ -391,16 +376,7 @@ class RobustRegistrationSolver {
   void reset(const Params& params) {
     params_ = params;
     const teaser_params_c c = to_c(params);
-    if (!h_) {
-      const int32_t rc = teaser_hip_solver_create(&c, /*device=*/-1, &h_);
-      if (rc != TEASER_HIP_OK) {
-        h_ = nullptr;
-        throw std::runtime_error("teaser::RobustRegistrationSolver: teaser_hip_solver_create failed (status " +
-                                 std::to_string(rc) + "; 3 = no HIP device)");
-      }
-    } else {
-      check(teaser_hip_solver_reset(h_, &c));
-    }
+    if (!h_.create("teaser::RobustRegistrationSolver", &c)) check(teaser_hip_solver_reset(h_, &c));
     scale_solver_.reset();
     rotation_solver_.reset();
     translation_solver_.reset();
@@ -867,7 +843,7 @@ class RobustRegistrationSolver {
     }
   }
 
-  teaser_hip_solver* h_ = nullptr;
+  detail::LazySolver h_;
   Params params_;
   RegistrationSolution solution_;
   teaser_solution_c raw_{};

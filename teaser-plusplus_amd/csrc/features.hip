@@ -26,6 +26,7 @@
 #include <vector>
 
 #include "features_internal.h"
+#include "host_common.h"
 #include "internal.h"
 #include "teaser_hip.h"
 
@@ -39,51 +40,6 @@ constexpr int64_t kFeatListBudgetBytes = (int64_t)4 << 30;
 // Partial results (8 bytes per query and data chunk) of one wave of pairs.
 constexpr int64_t kFeatPartBudgetBytes = (int64_t)1 << 30;
 
-struct DevBuf {
-  void* p = nullptr;
-  size_t cap = 0;
-  bool ensure(size_t bytes) {
-    if (bytes <= cap) return true;
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    cap = 0;
-    const size_t want = std::max<size_t>(bytes + bytes / 4, 256);
-    if (hipMalloc(&p, want) != hipSuccess) return false;
-    cap = want;
-    return true;
-  }
-  void release() {
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    cap = 0;
-  }
-  template <typename T>
-  T* as() const { return static_cast<T*>(p); }
-};
-
-// page-locked staging (the packed points going in, the small data-dependent results coming back)
-struct HostBuf {
-  void* p = nullptr;
-  size_t cap = 0;
-  bool ensure(size_t bytes) {
-    if (bytes <= cap) return true;
-    if (p) (void)hipHostFree(p);
-    p = nullptr;
-    cap = 0;
-    const size_t want = std::max<size_t>(bytes + bytes / 4, 256);
-    if (hipHostMalloc(&p, want, hipHostMallocDefault) != hipSuccess) return false;
-    cap = want;
-    return true;
-  }
-  void release() {
-    if (p) (void)hipHostFree(p);
-    p = nullptr;
-    cap = 0;
-  }
-  template <typename T>
-  T* as() const { return static_cast<T*>(p); }
-};
-
 enum { B_DESC, B_BLK, B_PT_CLOUD, B_PTS, B_COUNTS, B_OFFSETS, B_CURSOR, B_META, B_BASE, B_LIST, B_LIST2, B_NORMALS,
        B_SPFH, B_FEAT, B_SEARCH, B_SBLK, B_PART_D, B_PART_I, B_NN, B_MFEAT, B_COUNT_OF_BUFS };
 enum { H_PTS, H_META, H_NN, H_COUNT_OF_BUFS };
@@ -94,40 +50,24 @@ struct Wave {
 
 }  // namespace
 
-struct teaser_hip_features {
-  int device = 0;
-  hipStream_t stream = nullptr;
+struct teaser_hip_features : HandleBase {
   DevBuf buf[B_COUNT_OF_BUFS];
-  HostBuf host[H_COUNT_OF_BUFS];
+  HostBuf host[H_COUNT_OF_BUFS];  // the packed points going in, the small data-dependent results coming back
   int64_t list_budget = kFeatListBudgetBytes;
   int64_t part_budget = kFeatPartBudgetBytes;
-  std::string err;
   // host tables of the call in flight (kept here so that they outlive their asynchronous uploads)
   std::vector<FeatCloudDesc> desc;
   std::vector<int32_t> blk_cloud, pt_cloud, blk_search;
   std::vector<int64_t> base;
   std::vector<FeatSearchDesc> search;
+  ~teaser_hip_features() {
+    for (DevBuf& b : buf) b.release();
+    for (HostBuf& b : host) b.release();
+  }
 };
 
 namespace {
 
-int32_t fail(teaser_hip_features* h, int32_t status, const std::string& msg) {
-  h->err = msg;
-  return status;
-}
-
-int32_t hip_fail(teaser_hip_features* h, hipError_t e, const char* what) {
-  h->err = std::string(what) + ": " + hipGetErrorString(e);
-  return TEASER_HIP_ERR_HIP;
-}
-
-std::string at(int b) { return " (problem " + std::to_string(b) + ")"; }
-
-#define FCHK(h, call, what)                                   \
-  do {                                                        \
-    const hipError_t e_ = (call);                             \
-    if (e_ != hipSuccess) return hip_fail((h), e_, (what));   \
-  } while (0)
 #define FENSURE(h, b, bytes) \
   do {                       \
     if (!(b).ensure(bytes)) return fail((h), TEASER_HIP_ERR_OOM, "allocation failed (front-end buffers)"); \
@@ -434,34 +374,9 @@ int32_t run_match(teaser_hip_features* h, int32_t batch, const float* d_feat, co
 
 extern "C" {
 
-int32_t teaser_hip_features_create(int32_t device, teaser_hip_features** out) {
-  if (!out) return TEASER_HIP_ERR_BAD_ARG;
-  *out = nullptr;
-  int count = 0;
-  if (hipGetDeviceCount(&count) != hipSuccess || count <= 0) return TEASER_HIP_ERR_NO_DEVICE;
-  if (device < 0 && hipGetDevice(&device) != hipSuccess) return TEASER_HIP_ERR_NO_DEVICE;
-  if (device >= count) return TEASER_HIP_ERR_BAD_ARG;
-  if (hipSetDevice(device) != hipSuccess) return TEASER_HIP_ERR_HIP;
-  teaser_hip_features* h = new teaser_hip_features();
-  h->device = device;
-  if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess) {
-    delete h;
-    return TEASER_HIP_ERR_HIP;
-  }
-  *out = h;
-  return TEASER_HIP_OK;
-}
+int32_t teaser_hip_features_create(int32_t device, teaser_hip_features** out) { return open_handle(device, out); }
 
-int32_t teaser_hip_features_destroy(teaser_hip_features* h) {
-  if (!h) return TEASER_HIP_OK;
-  (void)hipSetDevice(h->device);
-  if (h->stream) (void)hipStreamSynchronize(h->stream);
-  for (DevBuf& b : h->buf) b.release();
-  for (HostBuf& b : h->host) b.release();
-  if (h->stream) (void)hipStreamDestroy(h->stream);
-  delete h;
-  return TEASER_HIP_OK;
-}
+int32_t teaser_hip_features_destroy(teaser_hip_features* h) { return close_handle(h); }
 
 const char* teaser_hip_features_last_error(const teaser_hip_features* h) { return h ? h->err.c_str() : ""; }
 

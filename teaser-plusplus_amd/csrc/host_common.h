@@ -1,0 +1,109 @@
+// host_common.h -- what the host sides of the auxiliary handles (icp.hip, voxel.hip, features.hip) share: the
+// grow-only buffers, the members and the error reporting every handle has, and the create / destroy sequences.
+// solver.hip keeps its own DevBuf / PinnedBuf: they grow by another rule, return hipError_t and have a view mode.
+#pragma once
+
+#include <hip/hip_runtime.h>
+#include <math.h>
+
+#include <algorithm>
+#include <string>
+
+#include "teaser_hip.h"
+
+namespace thip {
+
+inline hipError_t device_alloc(void** p, size_t bytes) { return hipMalloc(p, bytes); }
+inline hipError_t pinned_alloc(void** p, size_t bytes) { return hipHostMalloc(p, bytes, hipHostMallocDefault); }
+
+// A buffer that only grows: a request above the capacity frees it and allocates a quarter more than asked for.
+template <hipError_t (*Alloc)(void**, size_t), hipError_t (*Free)(void*)>
+struct GrowBuf {
+  void* p = nullptr;
+  size_t cap = 0;
+  bool ensure(size_t bytes) {
+    if (bytes <= cap) return true;
+    release();
+    const size_t want = std::max<size_t>(bytes + bytes / 4, 256);
+    if (Alloc(&p, want) != hipSuccess) return false;
+    cap = want;
+    return true;
+  }
+  void release() {
+    if (p) (void)Free(p);
+    p = nullptr;
+    cap = 0;
+  }
+  template <typename T>
+  T* as() const { return static_cast<T*>(p); }
+};
+struct DevBuf : GrowBuf<device_alloc, hipFree> {};
+struct HostBuf : GrowBuf<pinned_alloc, hipHostFree> {};  // page-locked staging
+
+// What every handle has.  A handle derives from it, adds its buffers and releases them in its destructor; the
+// stream goes after them.
+struct HandleBase {
+  int device = 0;
+  hipStream_t stream = nullptr;
+  std::string err;
+  ~HandleBase() {
+    if (stream) (void)hipStreamDestroy(stream);
+  }
+};
+
+inline int32_t fail(HandleBase* h, int32_t status, const std::string& msg) {
+  h->err = msg;
+  return status;
+}
+
+inline int32_t hip_fail(HandleBase* h, hipError_t e, const char* what) {
+  h->err = std::string(what) + ": " + hipGetErrorString(e);
+  return TEASER_HIP_ERR_HIP;
+}
+
+inline std::string at(int b) { return " (problem " + std::to_string(b) + ")"; }
+
+// Leaves the calling function with hip_fail(h, error, what) when a HIP call fails.
+#define FCHK(h, call, what)                                 \
+  do {                                                      \
+    const hipError_t e_ = (call);                           \
+    if (e_ != hipSuccess) return hip_fail((h), e_, (what)); \
+  } while (0)
+
+inline bool finite_points(const double* p, int64_t n) {
+  for (int64_t k = 0; k < 3 * n; ++k)
+    if (!std::isfinite(p[k])) return false;
+  return true;
+}
+
+// teaser_hip_*_create: a handle of type H on `device` (< 0: the current device) with a non-blocking stream.
+template <class H>
+int32_t open_handle(int32_t device, H** out) {
+  if (!out) return TEASER_HIP_ERR_BAD_ARG;
+  *out = nullptr;
+  int count = 0;
+  if (hipGetDeviceCount(&count) != hipSuccess || count <= 0) return TEASER_HIP_ERR_NO_DEVICE;
+  if (device < 0 && hipGetDevice(&device) != hipSuccess) return TEASER_HIP_ERR_NO_DEVICE;
+  if (device >= count) return TEASER_HIP_ERR_BAD_ARG;
+  if (hipSetDevice(device) != hipSuccess) return TEASER_HIP_ERR_HIP;
+  H* h = new H();
+  h->device = device;
+  if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess) {
+    delete h;
+    return TEASER_HIP_ERR_HIP;
+  }
+  *out = h;
+  return TEASER_HIP_OK;
+}
+
+// teaser_hip_*_destroy: drains the stream, then ~H releases the buffers and ~HandleBase the stream.
+template <class H>
+int32_t close_handle(H* h) {
+  if (!h) return TEASER_HIP_OK;
+  (void)hipSetDevice(h->device);
+  if (h->stream) (void)hipStreamSynchronize(h->stream);
+  delete h;
+  return TEASER_HIP_OK;
+}
+
+}  // namespace thip

@@ -13,6 +13,7 @@
 #include <string>
 #include <vector>
 
+#include "host_common.h"
 #include "icp_internal.h"
 #include "teaser_hip.h"
 
@@ -23,59 +24,22 @@ namespace {
 constexpr int kIcpGroup = 8;
 static_assert(kIcpCovMaxNN == TEASER_HIP_ICP_COV_MAX_NN, "the header states K");
 
-struct DevBuf {
-  void* p = nullptr;
-  size_t cap = 0;
-  bool ensure(size_t bytes) {
-    if (bytes <= cap) return true;
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    cap = 0;
-    const size_t want = std::max<size_t>(bytes + bytes / 4, 256);
-    if (hipMalloc(&p, want) != hipSuccess) return false;
-    cap = want;
-    return true;
-  }
-  void release() {
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    cap = 0;
-  }
-  template <typename T>
-  T* as() const { return static_cast<T*>(p); }
-};
-
 enum { B_DESC, B_STATE, B_BLK, B_TBLK, B_X, B_Q, B_TBUCKET, B_BCOUNT, B_BSTART, B_CURSOR, B_QS, B_QJ, B_MATCH,
        B_PARTIALS, B_LIVE, B_NORMALS, B_COV_S, B_COV_T, B_COUNT };
 
 }  // namespace
 
-struct teaser_hip_icp {
-  int device = 0;
-  hipStream_t stream = nullptr;
+struct teaser_hip_icp : HandleBase {
   int32_t* h_live = nullptr;  // page-locked: the one copy per iteration group
   DevBuf buf[B_COUNT];
-  std::string err;
   std::vector<double> stage;  // host packing of the points
+  ~teaser_hip_icp() {
+    for (DevBuf& b : buf) b.release();
+    if (h_live) (void)hipHostFree(h_live);
+  }
 };
 
 namespace {
-
-int32_t fail(teaser_hip_icp* h, int32_t status, const std::string& msg) {
-  h->err = msg;
-  return status;
-}
-
-int32_t hip_fail(teaser_hip_icp* h, hipError_t e, const char* what) {
-  h->err = std::string(what) + ": " + hipGetErrorString(e);
-  return TEASER_HIP_ERR_HIP;
-}
-
-bool finite_points(const double* p, int64_t n) {
-  for (int64_t k = 0; k < 3 * n; ++k)
-    if (!std::isfinite(p[k])) return false;
-  return true;
-}
 
 // the six entries of the contract (upper triangle) of n row-major 3 x 3 matrices
 bool finite_cov(const double* c, int64_t n) {
@@ -91,8 +55,6 @@ void pack_cov(const double* c, int64_t n, double* out) {
   for (int64_t k = 0; k < n; ++k)
     for (int u = 0; u < 6; ++u) out[6 * k + u] = c[9 * k + kUpper[u]];
 }
-
-std::string at(int b) { return " (problem " + std::to_string(b) + ")"; }
 
 int32_t validate(teaser_hip_icp* h, int32_t batch, const double* const* src, const int32_t* n_src,
                  const double* const* dst, const int32_t* n_dst, const double* init,
@@ -205,6 +167,75 @@ void set_grid(IcpDesc& d, const double* q, double r) {
   d.tb_mask = next_pow2(2 * (int64_t)d.n_t) - 1;
 }
 
+// The target index of one call under construction: per problem the descriptor with its offsets and hash grid, the
+// block -> problem maps of both kernels' grids, and the running totals of source points, target points and buckets.
+struct IcpIndex {
+  std::vector<IcpDesc> desc;
+  std::vector<int32_t> blk_prob, tblk_prob;
+  int64_t s_off = 0, t_off = 0, b_off = 0;
+};
+
+// Appends problem b (n_s source points; the n_t points q[b] indexed for search radius r) with nblk blocks of the
+// kernel that consumes the index; the caller fills in the descriptor's other fields.
+IcpDesc& add_problem(IcpIndex& ix, int b, int32_t n_s, int32_t n_t, const double* const* q, double r, int32_t nblk) {
+  ix.desc.emplace_back();
+  IcpDesc& d = ix.desc.back();
+  memset(&d, 0, sizeof(d));
+  d.n_s = n_s;
+  d.n_t = n_t;
+  d.s_off = ix.s_off;
+  d.t_off = ix.t_off;
+  d.b_off = ix.b_off;
+  d.blk_off = (int32_t)ix.blk_prob.size();
+  d.nblk = nblk;
+  d.tblk_off = (int32_t)ix.tblk_prob.size();
+  d.r2 = r * r;
+  if (n_t > 0) {
+    set_grid(d, q[b], r);
+    ix.b_off += d.tb_mask + 2;  // tb + 1 starts
+  }
+  for (int k = 0; k < nblk; ++k) ix.blk_prob.push_back(b);
+  for (int k = 0; k < (n_t + 255) / 256; ++k) ix.tblk_prob.push_back(b);
+  ix.s_off += n_s;
+  ix.t_off += n_t;
+  return d;
+}
+
+// Packs the points into h->stage (sources, then targets; src may be NULL when no problem has any) and enqueues
+// the uploads: descriptors, the per-problem `records` for B_STATE, both block maps, sources, targets.
+int32_t upload_inputs(teaser_hip_icp* h, const IcpIndex& ix, const double* const* src, const double* const* dst,
+                      const void* records, size_t record_bytes) {
+  for (size_t b = 0; b < ix.desc.size(); ++b) {
+    const IcpDesc& d = ix.desc[b];
+    if (d.n_s) memcpy(&h->stage[(size_t)(3 * d.s_off)], src[b], 24 * (size_t)d.n_s);
+    if (d.n_t) memcpy(&h->stage[(size_t)(3 * (ix.s_off + d.t_off))], dst[b], 24 * (size_t)d.n_t);
+  }
+  DevBuf* B = h->buf;
+  const struct {
+    void* d;
+    const void* hsrc;
+    size_t n;
+  } copies[] = {{B[B_DESC].p, ix.desc.data(), sizeof(IcpDesc) * ix.desc.size()},
+                {B[B_STATE].p, records, record_bytes},
+                {B[B_BLK].p, ix.blk_prob.data(), sizeof(int32_t) * ix.blk_prob.size()},
+                {B[B_TBLK].p, ix.tblk_prob.data(), sizeof(int32_t) * ix.tblk_prob.size()},
+                {B[B_X].p, h->stage.data(), sizeof(double) * 3 * ix.s_off},
+                {B[B_Q].p, h->stage.data() + 3 * ix.s_off, sizeof(double) * 3 * ix.t_off}};
+  for (const auto& c : copies)
+    if (c.n) FCHK(h, hipMemcpyAsync(c.d, c.hsrc, c.n, hipMemcpyHostToDevice, h->stream), "hipMemcpyAsync (inputs)");
+  return TEASER_HIP_OK;
+}
+
+// Clears the bucket counts and enqueues the kernels that build the index over the uploaded targets.
+int32_t launch_index(teaser_hip_icp* h, const IcpIndex& ix) {
+  DevBuf* B = h->buf;
+  if (ix.b_off) FCHK(h, hipMemsetAsync(B[B_BCOUNT].p, 0, sizeof(int32_t) * ix.b_off, h->stream), "hipMemsetAsync");
+  launch_icp_index(h->stream, B[B_DESC].as<IcpDesc>(), B[B_TBLK].as<int32_t>(), (int)ix.tblk_prob.size(),
+                   (int)ix.desc.size(), B[B_Q].as<double>(), B[B_TBUCKET].as<int32_t>(), B[B_BCOUNT].as<int32_t>(),
+                   B[B_BSTART].as<int32_t>(), B[B_CURSOR].as<int32_t>(), B[B_QS].as<double>(), B[B_QJ].as<int32_t>());
+  return TEASER_HIP_OK;
+}
+
 int32_t run_batch(teaser_hip_icp* h, int32_t batch, const double* const* src, const int32_t* n_src,
                   const double* const* dst, const int32_t* n_dst, const double* init,
                   const teaser_icp_params_c* params, teaser_icp_result_c* out, int32_t* const* corr,
@@ -225,38 +256,16 @@ int32_t teaser_hip_icp_params_default(teaser_icp_params_c* p) {
 }
 
 int32_t teaser_hip_icp_create(int32_t device, teaser_hip_icp** out) {
-  if (!out) return TEASER_HIP_ERR_BAD_ARG;
-  *out = nullptr;
-  int count = 0;
-  if (hipGetDeviceCount(&count) != hipSuccess || count <= 0) return TEASER_HIP_ERR_NO_DEVICE;
-  if (device < 0 && hipGetDevice(&device) != hipSuccess) return TEASER_HIP_ERR_NO_DEVICE;
-  if (device >= count) return TEASER_HIP_ERR_BAD_ARG;
-  if (hipSetDevice(device) != hipSuccess) return TEASER_HIP_ERR_HIP;
-  teaser_hip_icp* h = new teaser_hip_icp();
-  h->device = device;
-  if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess) {
-    delete h;
+  const int32_t rc = open_handle(device, out);
+  if (rc == TEASER_HIP_OK && hipHostMalloc((void**)&(*out)->h_live, sizeof(int32_t)) != hipSuccess) {
+    delete *out;
+    *out = nullptr;
     return TEASER_HIP_ERR_HIP;
   }
-  if (hipHostMalloc((void**)&h->h_live, sizeof(int32_t)) != hipSuccess) {
-    (void)hipStreamDestroy(h->stream);
-    delete h;
-    return TEASER_HIP_ERR_HIP;
-  }
-  *out = h;
-  return TEASER_HIP_OK;
+  return rc;
 }
 
-int32_t teaser_hip_icp_destroy(teaser_hip_icp* h) {
-  if (!h) return TEASER_HIP_OK;
-  (void)hipSetDevice(h->device);
-  if (h->stream) (void)hipStreamSynchronize(h->stream);
-  for (DevBuf& b : h->buf) b.release();
-  if (h->h_live) (void)hipHostFree(h->h_live);
-  if (h->stream) (void)hipStreamDestroy(h->stream);
-  delete h;
-  return TEASER_HIP_OK;
-}
+int32_t teaser_hip_icp_destroy(teaser_hip_icp* h) { return close_handle(h); }
 
 const char* teaser_hip_icp_last_error(const teaser_hip_icp* h) { return h ? h->err.c_str() : ""; }
 
@@ -306,31 +315,18 @@ int32_t run_batch(teaser_hip_icp* h, int32_t batch, const double* const* src, co
   int32_t rc = validate(h, batch, src, n_src, dst, n_dst, init, params, out, dst_normals, est, src_cov, dst_cov,
                         max_method);
   if (rc != TEASER_HIP_OK || batch == 0) return rc;
-  hipError_t e = hipSetDevice(h->device);
-  if (e != hipSuccess) return hip_fail(h, e, "hipSetDevice");
+  FCHK(h, hipSetDevice(h->device), "hipSetDevice");
 
   // ---- descriptors, block maps and initial state (host) ----
-  std::vector<IcpDesc> desc((size_t)batch);
+  IcpIndex ix;
   std::vector<IcpState> state((size_t)batch);
-  std::vector<int32_t> blk_prob, tblk_prob;
-  int64_t s_off = 0, t_off = 0, b_off = 0;
   int max_iter = 0;
   bool plane = false;  // any point-to-plane problem: the launches with the wider partials
   bool gicp = false;   // any Generalized-ICP problem: the third instantiation and the packed covariances
   for (int b = 0; b < batch; ++b) {
-    IcpDesc& d = desc[(size_t)b];
-    memset(&d, 0, sizeof(d));
     const teaser_icp_params_c& p = params[b];
-    const double r = p.max_correspondence_distance;
-    d.n_s = n_src[b];
-    d.n_t = n_dst[b];
-    d.s_off = s_off;
-    d.t_off = t_off;
-    d.b_off = b_off;
-    d.blk_off = (int32_t)blk_prob.size();
-    d.nblk = (d.n_s + kIcpBlock - 1) / kIcpBlock;
-    d.tblk_off = (int32_t)tblk_prob.size();
-    d.r2 = r * r;
+    IcpDesc& d = add_problem(ix, b, n_src[b], n_dst[b], dst, p.max_correspondence_distance,
+                             (n_src[b] + kIcpBlock - 1) / kIcpBlock);
     d.rel_fitness = p.relative_fitness;
     d.rel_rmse = p.relative_rmse;
     d.max_iteration = p.max_iteration;
@@ -342,14 +338,6 @@ int32_t run_batch(teaser_hip_icp* h, int32_t batch, const double* const* src, co
       plane |= d.method == kIcpMethodPlane;
       gicp |= d.method == kIcpMethodGicp;
     }
-    if (d.n_t > 0) {
-      set_grid(d, dst[b], r);
-      b_off += d.tb_mask + 2;  // tb + 1 starts
-    }
-    for (int k = 0; k < d.nblk; ++k) blk_prob.push_back(b);
-    for (int k = 0; k < (d.n_t + 255) / 256; ++k) tblk_prob.push_back(b);
-    s_off += d.n_s;
-    t_off += d.n_t;
     IcpState& st = state[(size_t)b];
     memset(&st, 0, sizeof(st));
     static const double kEye[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
@@ -357,7 +345,9 @@ int32_t run_batch(teaser_hip_icp* h, int32_t batch, const double* const* src, co
     for (int k = 0; k < 16; ++k) st.T[k] = T0[k];
     for (int k = 0; k < 12; ++k) st.U[k] = T0[k];  // the first correspondence pass applies init to P
   }
-  const int n_blk = (int)blk_prob.size(), n_tblk = (int)tblk_prob.size();
+  const std::vector<IcpDesc>& desc = ix.desc;
+  const int64_t s_off = ix.s_off, t_off = ix.t_off, b_off = ix.b_off;
+  const int n_blk = (int)ix.blk_prob.size(), n_tblk = (int)ix.tblk_prob.size();
 
   // ---- device buffers ----
   const size_t bytes[B_COUNT] = {
@@ -377,30 +367,13 @@ int32_t run_batch(teaser_hip_icp* h, int32_t batch, const double* const* src, co
   DevBuf* B = h->buf;
 
   h->stage.resize((size_t)((gicp ? 9 : 3) * (s_off + t_off)));  // points, then the packed covariances
-  for (int b = 0; b < batch; ++b) {
-    if (desc[(size_t)b].n_s) memcpy(&h->stage[(size_t)(3 * desc[(size_t)b].s_off)], src[b], 24 * (size_t)n_src[b]);
-    if (desc[(size_t)b].n_t)
-      memcpy(&h->stage[(size_t)(3 * (s_off + desc[(size_t)b].t_off))], dst[b], 24 * (size_t)n_dst[b]);
-  }
-  struct Copy {
-    void* d;
-    const void* hsrc;
-    size_t n;
-  } copies[] = {{B[B_DESC].p, desc.data(), bytes[B_DESC]},
-                {B[B_STATE].p, state.data(), bytes[B_STATE]},
-                {B[B_BLK].p, blk_prob.data(), sizeof(int32_t) * n_blk},
-                {B[B_TBLK].p, tblk_prob.data(), sizeof(int32_t) * n_tblk},
-                {B[B_X].p, h->stage.data(), sizeof(double) * 3 * s_off},
-                {B[B_Q].p, h->stage.data() + 3 * s_off, sizeof(double) * 3 * t_off}};
-  for (const Copy& c : copies)
-    if (c.n && (e = hipMemcpyAsync(c.d, c.hsrc, c.n, hipMemcpyHostToDevice, s)) != hipSuccess)
-      return hip_fail(h, e, "hipMemcpyAsync (inputs)");
+  if ((rc = upload_inputs(h, ix, src, dst, state.data(), bytes[B_STATE])) != TEASER_HIP_OK) return rc;
   for (int b = 0; b < batch; ++b) {  // one copy per point-to-plane problem, straight from the caller's normals
     const IcpDesc& d = desc[(size_t)b];
-    if (d.method == kIcpMethodPlane && d.n_t > 0 &&
-        (e = hipMemcpyAsync(B[B_NORMALS].as<double>() + 3 * d.t_off, dst_normals[b], 24 * (size_t)d.n_t,
-                            hipMemcpyHostToDevice, s)) != hipSuccess)
-      return hip_fail(h, e, "hipMemcpyAsync (normals)");
+    if (d.method == kIcpMethodPlane && d.n_t > 0)
+      FCHK(h, hipMemcpyAsync(B[B_NORMALS].as<double>() + 3 * d.t_off, dst_normals[b], 24 * (size_t)d.n_t,
+                             hipMemcpyHostToDevice, s),
+           "hipMemcpyAsync (normals)");
   }
   if (gicp) {  // upper triangles packed 6 doubles per point; rows of other problems are never read
     double* cs = h->stage.data() + 3 * (s_off + t_off);
@@ -411,20 +384,16 @@ int32_t run_batch(teaser_hip_icp* h, int32_t batch, const double* const* src, co
       if (d.n_s) pack_cov(src_cov[b], d.n_s, cs + 6 * d.s_off);
       if (d.n_t) pack_cov(dst_cov[b], d.n_t, ct + 6 * d.t_off);
     }
-    if (s_off && (e = hipMemcpyAsync(B[B_COV_S].p, cs, sizeof(double) * 6 * s_off, hipMemcpyHostToDevice, s)) !=
-                     hipSuccess)
-      return hip_fail(h, e, "hipMemcpyAsync (source covariances)");
-    if (t_off && (e = hipMemcpyAsync(B[B_COV_T].p, ct, sizeof(double) * 6 * t_off, hipMemcpyHostToDevice, s)) !=
-                     hipSuccess)
-      return hip_fail(h, e, "hipMemcpyAsync (target covariances)");
+    if (s_off)
+      FCHK(h, hipMemcpyAsync(B[B_COV_S].p, cs, sizeof(double) * 6 * s_off, hipMemcpyHostToDevice, s),
+           "hipMemcpyAsync (source covariances)");
+    if (t_off)
+      FCHK(h, hipMemcpyAsync(B[B_COV_T].p, ct, sizeof(double) * 6 * t_off, hipMemcpyHostToDevice, s),
+           "hipMemcpyAsync (target covariances)");
   }
-  if (b_off && (e = hipMemsetAsync(B[B_BCOUNT].p, 0, sizeof(int32_t) * b_off, s)) != hipSuccess)
-    return hip_fail(h, e, "hipMemsetAsync");
 
   // ---- target index, then the iteration groups ----
-  launch_icp_index(s, B[B_DESC].as<IcpDesc>(), B[B_TBLK].as<int32_t>(), n_tblk, batch, B[B_Q].as<double>(),
-                   B[B_TBUCKET].as<int32_t>(), B[B_BCOUNT].as<int32_t>(), B[B_BSTART].as<int32_t>(),
-                   B[B_CURSOR].as<int32_t>(), B[B_QS].as<double>(), B[B_QJ].as<int32_t>());
+  if ((rc = launch_index(h, ix)) != TEASER_HIP_OK) return rc;
   int64_t passes = 0;  // correspondence passes enqueued: the first one + one per iteration
   for (;;) {
     for (int g = 0; g < kIcpGroup && passes <= (int64_t)max_iter; ++g, ++passes)
@@ -434,27 +403,26 @@ int32_t run_batch(teaser_hip_icp* h, int32_t batch, const double* const* src, co
                            B[B_COV_T].as<double>(), gicp ? 2 : plane ? 1 : 0, B[B_MATCH].as<int32_t>(),
                            B[B_PARTIALS].as<double>());
     launch_icp_live(s, B[B_STATE].as<IcpState>(), batch, B[B_LIVE].as<int32_t>());
-    if ((e = hipGetLastError()) != hipSuccess) return hip_fail(h, e, "ICP kernel launch");
-    if ((e = hipMemcpyAsync(h->h_live, B[B_LIVE].p, sizeof(int32_t), hipMemcpyDeviceToHost, s)) != hipSuccess)
-      return hip_fail(h, e, "hipMemcpyAsync (live count)");
-    if ((e = hipStreamSynchronize(s)) != hipSuccess) return hip_fail(h, e, "ICP iterations");
+    FCHK(h, hipGetLastError(), "ICP kernel launch");
+    FCHK(h, hipMemcpyAsync(h->h_live, B[B_LIVE].p, sizeof(int32_t), hipMemcpyDeviceToHost, s),
+         "hipMemcpyAsync (live count)");
+    FCHK(h, hipStreamSynchronize(s), "ICP iterations");
     if (*h->h_live == 0) break;
     if (passes > (int64_t)max_iter) return fail(h, TEASER_HIP_ERR_HIP, "ICP: problems left unfinished");
   }
 
   // ---- results ----
-  if ((e = hipMemcpyAsync(state.data(), B[B_STATE].p, bytes[B_STATE], hipMemcpyDeviceToHost, s)) != hipSuccess)
-    return hip_fail(h, e, "hipMemcpyAsync (state)");
+  FCHK(h, hipMemcpyAsync(state.data(), B[B_STATE].p, bytes[B_STATE], hipMemcpyDeviceToHost, s),
+       "hipMemcpyAsync (state)");
   bool want_corr = false;
   for (int b = 0; corr && b < batch; ++b) want_corr |= corr[b] != nullptr && n_src[b] > 0;
   std::vector<int32_t> match;
   if (want_corr) {
     match.resize((size_t)s_off);
-    if ((e = hipMemcpyAsync(match.data(), B[B_MATCH].p, sizeof(int32_t) * s_off, hipMemcpyDeviceToHost, s)) !=
-        hipSuccess)
-      return hip_fail(h, e, "hipMemcpyAsync (correspondences)");
+    FCHK(h, hipMemcpyAsync(match.data(), B[B_MATCH].p, sizeof(int32_t) * s_off, hipMemcpyDeviceToHost, s),
+         "hipMemcpyAsync (correspondences)");
   }
-  if ((e = hipStreamSynchronize(s)) != hipSuccess) return hip_fail(h, e, "ICP results");
+  FCHK(h, hipStreamSynchronize(s), "ICP results");
   for (int b = 0; b < batch; ++b) {
     const IcpState& st = state[(size_t)b];
     teaser_icp_result_c& o = out[b];
@@ -532,49 +500,33 @@ int32_t teaser_hip_icp_covariances_batch(teaser_hip_icp* h, int32_t batch, const
     total += n[b];
   }
   if (total >= INT32_MAX / 9) return fail(h, TEASER_HIP_ERR_BAD_ARG, "too many points in one call");
-  hipError_t e = hipSetDevice(h->device);
-  if (e != hipSuccess) return hip_fail(h, e, "hipSetDevice");
+  FCHK(h, hipSetDevice(h->device), "hipSetDevice");
 
   // the ICP grid over each cloud itself (the cloud is the descriptor's target), cell edge from its radius
-  std::vector<IcpDesc> desc((size_t)batch);
+  IcpIndex ix;
   std::vector<IcpCovDesc> cov((size_t)batch);
-  std::vector<int32_t> blk_prob, tblk_prob;
-  int64_t t_off = 0, b_off = 0;
   int top_nn = 0;
   for (int b = 0; b < batch; ++b) {
-    IcpDesc& d = desc[(size_t)b];
-    memset(&d, 0, sizeof(d));
-    d.n_t = n[b];
-    d.t_off = t_off;
-    d.b_off = b_off;
-    d.blk_off = (int32_t)blk_prob.size();
-    d.nblk = (d.n_t + kIcpCovBlock - 1) / kIcpCovBlock;
-    d.tblk_off = (int32_t)tblk_prob.size();
-    d.r2 = radius[b] * radius[b];
+    add_problem(ix, b, 0, n[b], points, radius[b], (n[b] + kIcpCovBlock - 1) / kIcpCovBlock);
     cov[(size_t)b].max_nn = max_nn[b];
     cov[(size_t)b].pad = 0;
     cov[(size_t)b].eps = epsilon ? epsilon[b] : 1e-3;
-    if (d.n_t > 0) {
-      top_nn = std::max(top_nn, max_nn[b]);
-      set_grid(d, points[b], radius[b]);
-      b_off += d.tb_mask + 2;
-    }
-    for (int k = 0; k < d.nblk; ++k) blk_prob.push_back(b);
-    for (int k = 0; k < (d.n_t + 255) / 256; ++k) tblk_prob.push_back(b);
-    t_off += d.n_t;
+    if (n[b] > 0) top_nn = std::max(top_nn, max_nn[b]);
   }
+  const std::vector<IcpDesc>& desc = ix.desc;
+  const int64_t t_off = ix.t_off;
   if (t_off == 0) return TEASER_HIP_OK;
-  const int n_blk = (int)blk_prob.size(), n_tblk = (int)tblk_prob.size();
+  const int n_blk = (int)ix.blk_prob.size();
   // B_STATE holds the IcpCovDesc records and B_X the 9 doubles per point of the output during this call
   size_t bytes[B_COUNT] = {};
   bytes[B_DESC] = sizeof(IcpDesc) * batch;
   bytes[B_STATE] = sizeof(IcpCovDesc) * batch;
   bytes[B_BLK] = sizeof(int32_t) * n_blk;
-  bytes[B_TBLK] = sizeof(int32_t) * n_tblk;
+  bytes[B_TBLK] = sizeof(int32_t) * ix.tblk_prob.size();
   bytes[B_X] = sizeof(double) * 9 * t_off;
   bytes[B_Q] = sizeof(double) * 3 * t_off;
   bytes[B_TBUCKET] = sizeof(int32_t) * t_off;
-  bytes[B_BCOUNT] = bytes[B_BSTART] = bytes[B_CURSOR] = sizeof(int32_t) * b_off;
+  bytes[B_BCOUNT] = bytes[B_BSTART] = bytes[B_CURSOR] = sizeof(int32_t) * ix.b_off;
   bytes[B_QS] = sizeof(double) * 3 * t_off;
   bytes[B_QJ] = sizeof(int32_t) * t_off;
   for (int k = 0; k < B_COUNT; ++k)
@@ -582,31 +534,16 @@ int32_t teaser_hip_icp_covariances_batch(teaser_hip_icp* h, int32_t batch, const
   hipStream_t s = h->stream;
   DevBuf* B = h->buf;
   h->stage.resize((size_t)(9 * t_off));
-  for (int b = 0; b < batch; ++b)
-    if (n[b]) memcpy(&h->stage[(size_t)(3 * desc[(size_t)b].t_off)], points[b], 24 * (size_t)n[b]);
-  struct Copy {
-    void* d;
-    const void* hsrc;
-    size_t n;
-  } copies[] = {{B[B_DESC].p, desc.data(), bytes[B_DESC]},
-                {B[B_STATE].p, cov.data(), bytes[B_STATE]},
-                {B[B_BLK].p, blk_prob.data(), bytes[B_BLK]},
-                {B[B_TBLK].p, tblk_prob.data(), bytes[B_TBLK]},
-                {B[B_Q].p, h->stage.data(), bytes[B_Q]}};
-  for (const Copy& c : copies)
-    if (c.n && (e = hipMemcpyAsync(c.d, c.hsrc, c.n, hipMemcpyHostToDevice, s)) != hipSuccess)
-      return hip_fail(h, e, "hipMemcpyAsync (inputs)");
-  if ((e = hipMemsetAsync(B[B_BCOUNT].p, 0, bytes[B_BCOUNT], s)) != hipSuccess) return hip_fail(h, e, "hipMemsetAsync");
-  launch_icp_index(s, B[B_DESC].as<IcpDesc>(), B[B_TBLK].as<int32_t>(), n_tblk, batch, B[B_Q].as<double>(),
-                   B[B_TBUCKET].as<int32_t>(), B[B_BCOUNT].as<int32_t>(), B[B_BSTART].as<int32_t>(),
-                   B[B_CURSOR].as<int32_t>(), B[B_QS].as<double>(), B[B_QJ].as<int32_t>());
+  int32_t rc = upload_inputs(h, ix, nullptr, points, cov.data(), bytes[B_STATE]);
+  if (rc == TEASER_HIP_OK) rc = launch_index(h, ix);
+  if (rc != TEASER_HIP_OK) return rc;
   launch_icp_covariances(s, B[B_DESC].as<IcpDesc>(), B[B_STATE].as<IcpCovDesc>(), B[B_BLK].as<int32_t>(), n_blk,
                          top_nn, B[B_Q].as<double>(), B[B_QS].as<double>(), B[B_QJ].as<int32_t>(),
                          B[B_BSTART].as<int32_t>(), B[B_X].as<double>());
-  if ((e = hipGetLastError()) != hipSuccess) return hip_fail(h, e, "covariance kernel launch");
-  if ((e = hipMemcpyAsync(h->stage.data(), B[B_X].p, bytes[B_X], hipMemcpyDeviceToHost, s)) != hipSuccess)
-    return hip_fail(h, e, "hipMemcpyAsync (covariances)");
-  if ((e = hipStreamSynchronize(s)) != hipSuccess) return hip_fail(h, e, "covariance estimation");
+  FCHK(h, hipGetLastError(), "covariance kernel launch");
+  FCHK(h, hipMemcpyAsync(h->stage.data(), B[B_X].p, bytes[B_X], hipMemcpyDeviceToHost, s),
+       "hipMemcpyAsync (covariances)");
+  FCHK(h, hipStreamSynchronize(s), "covariance estimation");
   for (int b = 0; b < batch; ++b)
     if (n[b]) memcpy(out[b], &h->stage[(size_t)(9 * desc[(size_t)b].t_off)], 72 * (size_t)n[b]);
   return TEASER_HIP_OK;

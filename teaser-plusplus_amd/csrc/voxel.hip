@@ -14,6 +14,7 @@
 #include <string>
 #include <vector>
 
+#include "host_common.h"
 #include "teaser_hip.h"
 #include "voxel_internal.h"
 
@@ -21,53 +22,19 @@ using namespace thip;
 
 namespace {
 
-struct DevBuf {
-  void* p = nullptr;
-  size_t cap = 0;
-  bool ensure(size_t bytes) {
-    if (bytes <= cap) return true;
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    cap = 0;
-    const size_t want = std::max<size_t>(bytes + bytes / 4, 256);
-    if (hipMalloc(&p, want) != hipSuccess) return false;
-    cap = want;
-    return true;
-  }
-  void release() {
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    cap = 0;
-  }
-  template <typename T>
-  T* as() const { return static_cast<T*>(p); }
-};
-
 enum { B_DESC, B_BLK, B_PTS, B_KEY_LO, B_KEY_HI, B_IOTA, B_SORTED, B_GATHERED, B_PERM1, B_PERM, B_SPTS, B_HEAD,
        B_RUN_ID, B_RUN_START, B_SUMMARY, B_MEAN, B_COUNT, B_TRACE, B_TEMP, B_COUNT_OF_BUFS };
 
 }  // namespace
 
-struct teaser_hip_voxel {
-  int device = 0;
-  hipStream_t stream = nullptr;
+struct teaser_hip_voxel : HandleBase {
   DevBuf buf[B_COUNT_OF_BUFS];
-  std::string err;
+  ~teaser_hip_voxel() {
+    for (DevBuf& b : buf) b.release();
+  }
 };
 
 namespace {
-
-int32_t fail(teaser_hip_voxel* h, int32_t status, const std::string& msg) {
-  h->err = msg;
-  return status;
-}
-
-int32_t hip_fail(teaser_hip_voxel* h, hipError_t e, const char* what) {
-  h->err = std::string(what) + ": " + hipGetErrorString(e);
-  return TEASER_HIP_ERR_HIP;
-}
-
-std::string at(int b) { return " (problem " + std::to_string(b) + ")"; }
 
 // Number of bits that hold every value in [0, v].
 int bits_for(uint64_t v) {
@@ -131,33 +98,9 @@ int32_t validate(teaser_hip_voxel* h, int32_t batch, const double* const* pts, c
 
 extern "C" {
 
-int32_t teaser_hip_voxel_create(int32_t device, teaser_hip_voxel** out) {
-  if (!out) return TEASER_HIP_ERR_BAD_ARG;
-  *out = nullptr;
-  int count = 0;
-  if (hipGetDeviceCount(&count) != hipSuccess || count <= 0) return TEASER_HIP_ERR_NO_DEVICE;
-  if (device < 0 && hipGetDevice(&device) != hipSuccess) return TEASER_HIP_ERR_NO_DEVICE;
-  if (device >= count) return TEASER_HIP_ERR_BAD_ARG;
-  if (hipSetDevice(device) != hipSuccess) return TEASER_HIP_ERR_HIP;
-  teaser_hip_voxel* h = new teaser_hip_voxel();
-  h->device = device;
-  if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess) {
-    delete h;
-    return TEASER_HIP_ERR_HIP;
-  }
-  *out = h;
-  return TEASER_HIP_OK;
-}
+int32_t teaser_hip_voxel_create(int32_t device, teaser_hip_voxel** out) { return open_handle(device, out); }
 
-int32_t teaser_hip_voxel_destroy(teaser_hip_voxel* h) {
-  if (!h) return TEASER_HIP_OK;
-  (void)hipSetDevice(h->device);
-  if (h->stream) (void)hipStreamSynchronize(h->stream);
-  for (DevBuf& b : h->buf) b.release();
-  if (h->stream) (void)hipStreamDestroy(h->stream);
-  delete h;
-  return TEASER_HIP_OK;
-}
+int32_t teaser_hip_voxel_destroy(teaser_hip_voxel* h) { return close_handle(h); }
 
 const char* teaser_hip_voxel_last_error(const teaser_hip_voxel* h) { return h ? h->err.c_str() : ""; }
 
@@ -195,8 +138,7 @@ int32_t teaser_hip_voxel_down_sample_batch(teaser_hip_voxel* h, int32_t batch, c
   const bool two_words = bits > 64;
   const int n_blk = (int)blk_prob.size();
 
-  hipError_t e = hipSetDevice(h->device);
-  if (e != hipSuccess) return hip_fail(h, e, "hipSetDevice");
+  FCHK(h, hipSetDevice(h->device), "hipSetDevice");
   const size_t N = (size_t)total;
   const size_t bytes[B_COUNT_OF_BUFS] = {
       sizeof(VoxDesc) * batch, sizeof(int32_t) * n_blk, 24 * N, 8 * N, two_words ? 8 * N : 8,
@@ -207,28 +149,29 @@ int32_t teaser_hip_voxel_down_sample_batch(teaser_hip_voxel* h, int32_t batch, c
   hipStream_t s = h->stream;
   DevBuf* B = h->buf;
 
-  if ((e = hipMemcpyAsync(B[B_DESC].p, desc.data(), bytes[B_DESC], hipMemcpyHostToDevice, s)) != hipSuccess ||
-      (e = hipMemcpyAsync(B[B_BLK].p, blk_prob.data(), bytes[B_BLK], hipMemcpyHostToDevice, s)) != hipSuccess)
-    return hip_fail(h, e, "hipMemcpyAsync (descriptors)");
+  FCHK(h, hipMemcpyAsync(B[B_DESC].p, desc.data(), bytes[B_DESC], hipMemcpyHostToDevice, s),
+       "hipMemcpyAsync (descriptors)");
+  FCHK(h, hipMemcpyAsync(B[B_BLK].p, blk_prob.data(), bytes[B_BLK], hipMemcpyHostToDevice, s),
+       "hipMemcpyAsync (descriptors)");
   for (int b = 0; b < batch; ++b)
-    if (n[b] > 0 && (e = hipMemcpyAsync(B[B_PTS].as<double>() + 3 * desc[(size_t)b].off, pts[b], 24 * (size_t)n[b],
-                                        hipMemcpyHostToDevice, s)) != hipSuccess)
-      return hip_fail(h, e, "hipMemcpyAsync (points)");
+    if (n[b] > 0)
+      FCHK(h, hipMemcpyAsync(B[B_PTS].as<double>() + 3 * desc[(size_t)b].off, pts[b], 24 * (size_t)n[b],
+                             hipMemcpyHostToDevice, s),
+           "hipMemcpyAsync (points)");
 
   // ---- keys, sort, runs, sums ----
   launch_voxel_keys(s, B[B_DESC].as<VoxDesc>(), B[B_BLK].as<int32_t>(), n_blk, B[B_PTS].as<double>(), prob_shift,
                     B[B_KEY_LO].as<uint64_t>(), two_words ? B[B_KEY_HI].as<uint64_t>() : nullptr,
                     B[B_IOTA].as<int32_t>());
-  if ((e = launch_voxel_sort(s, B[B_TEMP].p, bytes[B_TEMP], total, bits, B[B_KEY_LO].as<uint64_t>(),
-                             B[B_KEY_HI].as<uint64_t>(), B[B_IOTA].as<int32_t>(), B[B_SORTED].as<uint64_t>(),
-                             B[B_GATHERED].as<uint64_t>(), B[B_PERM1].as<int32_t>(), B[B_PERM].as<int32_t>())) !=
-      hipSuccess)
-    return hip_fail(h, e, "voxel sort");
-  if ((e = launch_voxel_runs(s, B[B_TEMP].p, bytes[B_TEMP], total, two_words, B[B_PTS].as<double>(),
-                             B[B_KEY_LO].as<uint64_t>(), B[B_KEY_HI].as<uint64_t>(), B[B_PERM].as<int32_t>(),
-                             B[B_SPTS].as<double>(), B[B_HEAD].as<int32_t>(), B[B_RUN_ID].as<int32_t>(),
-                             B[B_RUN_START].as<int32_t>())) != hipSuccess)
-    return hip_fail(h, e, "voxel runs");
+  FCHK(h, launch_voxel_sort(s, B[B_TEMP].p, bytes[B_TEMP], total, bits, B[B_KEY_LO].as<uint64_t>(),
+                            B[B_KEY_HI].as<uint64_t>(), B[B_IOTA].as<int32_t>(), B[B_SORTED].as<uint64_t>(),
+                            B[B_GATHERED].as<uint64_t>(), B[B_PERM1].as<int32_t>(), B[B_PERM].as<int32_t>()),
+       "voxel sort");
+  FCHK(h, launch_voxel_runs(s, B[B_TEMP].p, bytes[B_TEMP], total, two_words, B[B_PTS].as<double>(),
+                            B[B_KEY_LO].as<uint64_t>(), B[B_KEY_HI].as<uint64_t>(), B[B_PERM].as<int32_t>(),
+                            B[B_SPTS].as<double>(), B[B_HEAD].as<int32_t>(), B[B_RUN_ID].as<int32_t>(),
+                            B[B_RUN_START].as<int32_t>()),
+       "voxel runs");
   launch_voxel_reduce(s, B[B_DESC].as<VoxDesc>(), batch, total, B[B_RUN_ID].as<int32_t>(),
                       B[B_RUN_START].as<int32_t>(), B[B_SPTS].as<double>(), B[B_SUMMARY].as<int32_t>(),
                       B[B_MEAN].as<double>(), B[B_COUNT].as<int32_t>());
@@ -240,26 +183,26 @@ int32_t teaser_hip_voxel_down_sample_batch(teaser_hip_voxel* h, int32_t batch, c
   if (want_trace)
     launch_voxel_trace(s, B[B_DESC].as<VoxDesc>(), B[B_BLK].as<int32_t>(), n_blk, B[B_PERM].as<int32_t>(),
                        B[B_RUN_ID].as<int32_t>(), B[B_SUMMARY].as<int32_t>(), B[B_TRACE].as<int32_t>());
-  if ((e = hipGetLastError()) != hipSuccess) return hip_fail(h, e, "voxel kernel launch");
+  FCHK(h, hipGetLastError(), "voxel kernel launch");
 
   // ---- results: run counts first, then exactly the voxels ----
   std::vector<int32_t> summary(2 * (size_t)batch);
-  if ((e = hipMemcpyAsync(summary.data(), B[B_SUMMARY].p, bytes[B_SUMMARY], hipMemcpyDeviceToHost, s)) !=
-          hipSuccess ||
-      (e = hipStreamSynchronize(s)) != hipSuccess)
-    return hip_fail(h, e, "voxel run counts");
+  FCHK(h, hipMemcpyAsync(summary.data(), B[B_SUMMARY].p, bytes[B_SUMMARY], hipMemcpyDeviceToHost, s),
+       "voxel run counts");
+  FCHK(h, hipStreamSynchronize(s), "voxel run counts");
   int64_t runs = 0;
   for (int b = 0; b < batch; ++b) runs += summary[2 * (size_t)b + 1];
   std::vector<double> mean(3 * (size_t)runs);
   std::vector<int32_t> count(want_counts ? (size_t)runs : 0), trace(want_trace ? N : 0);
-  if ((e = hipMemcpyAsync(mean.data(), B[B_MEAN].p, 24 * (size_t)runs, hipMemcpyDeviceToHost, s)) != hipSuccess)
-    return hip_fail(h, e, "hipMemcpyAsync (voxels)");
-  if (want_counts &&
-      (e = hipMemcpyAsync(count.data(), B[B_COUNT].p, 4 * (size_t)runs, hipMemcpyDeviceToHost, s)) != hipSuccess)
-    return hip_fail(h, e, "hipMemcpyAsync (counts)");
-  if (want_trace && (e = hipMemcpyAsync(trace.data(), B[B_TRACE].p, 4 * N, hipMemcpyDeviceToHost, s)) != hipSuccess)
-    return hip_fail(h, e, "hipMemcpyAsync (voxel_of_point)");
-  if ((e = hipStreamSynchronize(s)) != hipSuccess) return hip_fail(h, e, "voxel results");
+  FCHK(h, hipMemcpyAsync(mean.data(), B[B_MEAN].p, 24 * (size_t)runs, hipMemcpyDeviceToHost, s),
+       "hipMemcpyAsync (voxels)");
+  if (want_counts)
+    FCHK(h, hipMemcpyAsync(count.data(), B[B_COUNT].p, 4 * (size_t)runs, hipMemcpyDeviceToHost, s),
+         "hipMemcpyAsync (counts)");
+  if (want_trace)
+    FCHK(h, hipMemcpyAsync(trace.data(), B[B_TRACE].p, 4 * N, hipMemcpyDeviceToHost, s),
+         "hipMemcpyAsync (voxel_of_point)");
+  FCHK(h, hipStreamSynchronize(s), "voxel results");
   for (int b = 0; b < batch; ++b) {
     const int64_t first = summary[2 * (size_t)b], m = summary[2 * (size_t)b + 1];
     n_out[b] = m;

@@ -7,13 +7,11 @@ in include/teaser_hip.h ("Batched correspondence front-end").
 One library handle is kept per device between calls; calls from several threads are safe -- each handle has a lock,
 so calls for one device run one after the other.  device=-1 means the calling thread's current HIP device at the
 time of the call.  Without a GPU the calls raise TeaserHipError (NO_DEVICE): there is no CPU path."""
-import atexit
 import ctypes as C
-import threading
 
 import numpy as np
 
-from .icp import _current_device
+from ._handles import Handle, HandleCache, _cloud
 
 _vp, _ip, _fp, _dp, _i64p = (C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_float), C.POINTER(C.c_double),
                              C.POINTER(C.c_int64))
@@ -35,80 +33,23 @@ def declare(L):
         C.POINTER(_fp), C.POINTER(_fp), C.POINTER(_fp), C.POINTER(_fp)]
 
 
-class _Handle:
-    """One C handle and the lock that serialises its calls."""
-
-    def __init__(self, device):
-        from . import TeaserHipError, lib
-        self._lib = lib()
-        self._h = _vp()
-        rc = self._lib.teaser_hip_features_create(int(device), C.byref(self._h))
-        if rc != 0:
-            self._h = None
-            raise TeaserHipError(rc, "(no MI355X visible: the product has no CPU path)" if rc == 3 else "")
-        self.lock = threading.Lock()
-
+class _Handle(Handle):
     def _set_budget(self, list_bytes=None, part_bytes=None):
         """Test hook: the budgets of one wave in bytes (None or <= 0: the default) -- list_bytes for the neighbour lists
         of a wave of clouds, part_bytes for the partial nearest-neighbour results of a wave of pairs.  Small values
         split a call into many waves; results do not depend on them."""
         with self.lock:
-            self._lib.teaser_hip_features_set_budgets(self._h, int(list_bytes or 0), int(part_bytes or 0))
-
-    def call(self, fn, *args):
-        from . import TeaserHipError
-        with self.lock:  # the handle serves one call at a time
-            rc = fn(self._h, *args)
-            err = self._lib.teaser_hip_features_last_error(self._h).decode() if rc != 0 else ""
-        if rc != 0:
-            raise TeaserHipError(rc, err)
-
-    def close(self):
-        if self._h is not None:
-            with self.lock:
-                self._lib.teaser_hip_features_destroy(self._h)
-            self._h = None
+            self._lib.teaser_hip_features_set_budgets(self.h, int(list_bytes or 0), int(part_bytes or 0))
 
 
-# One handle per device, shared by every thread of the process (see icp.py).
-_handles = {}
-_handles_lock = threading.Lock()
-
-
-def _handle(device=-1):
-    """The cached handle of `device`; device < 0 is resolved to the calling thread's current device first."""
-    from . import lib
-    lib()
-    device = int(device)
-    if device < 0:
-        device = _current_device()
-    with _handles_lock:
-        h = _handles.get(device)
-        if h is None:
-            h = _handles[device] = _Handle(device)
-        return h
-
-
-@atexit.register
-def _release():
-    with _handles_lock:
-        for h in _handles.values():
-            h.close()
-        _handles.clear()
+_cache = HandleCache("teaser_hip_features", _Handle)
+_handle = _cache.get
 
 
 # ---- argument normalisation (no device needed) ----------------------------------------------------------------------
 def _clouds(clouds, what="clouds"):
     """A list of n_b x 3 float32 C-contiguous arrays (an empty cloud is 0 x 3)."""
-    out = []
-    for k, c in enumerate(clouds):
-        a = np.ascontiguousarray(np.asarray(c, dtype=np.float32))
-        if a.size == 0:
-            a = np.zeros((0, 3), dtype=np.float32)
-        elif a.ndim != 2 or a.shape[1] != 3:
-            raise ValueError("%s[%d] must be an n x 3 array, got shape %s" % (what, k, a.shape))
-        out.append(a)
-    return out
+    return [_cloud(c, "%s[%d]" % (what, k), np.float32) for k, c in enumerate(clouds)]
 
 
 def _radii(r, batch, what):

@@ -10,12 +10,11 @@ One library handle is kept per device between calls (no HIP context per call); c
 each handle has a lock, so calls for one device run one after the other.  device=-1 means the calling thread's
 current HIP device at the time of the call.  Without a GPU the calls raise
 TeaserHipError (NO_DEVICE): there is no CPU path."""
-import atexit
 import ctypes as C
-import os
-import threading
 
 import numpy as np
+
+from ._handles import HandleCache, _cloud
 
 _vp, _ip, _dp = C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_double)
 
@@ -162,66 +161,12 @@ class RegistrationResult:
             self.fitness, self.inlier_rmse, len(self.correspondence_set), self.iterations)
 
 
-# One C handle per device, shared by every thread of the process.  A handle is not re-entrant (its stream, device
-# buffers and staging memory serve one call at a time) and ctypes releases the GIL during the call, so each handle
-# has a lock held around every call on it; calls for different devices run concurrently.
-_handles = {}            # device ordinal -> (handle, lock)
-_handles_lock = threading.Lock()
+_cache = HandleCache("teaser_hip_icp")
+_handle = _cache.get
 
 
-def _current_device():
-    """The calling thread's current HIP device, asked of the HIP runtime this package's library is linked against
-    (already loaded: RTLD_NOLOAD never loads a second runtime).  -1 when it cannot be asked."""
-    for name in ("libamdhip64.so.7", "libamdhip64.so.6", "libamdhip64.so"):
-        try:
-            rt = C.CDLL(name, mode=os.RTLD_NOLOAD | os.RTLD_GLOBAL)
-        except OSError:
-            continue
-        d = C.c_int(-1)
-        return d.value if rt.hipGetDevice(C.byref(d)) == 0 else -1
-    return -1
-
-
-def _handle(device):
-    """(handle, lock) for `device`; device < 0 is resolved to the calling thread's current device first."""
-    from . import TeaserHipError, lib
-    device = int(device)
-    L = lib()
-    if device < 0:
-        device = _current_device()
-    with _handles_lock:
-        entry = _handles.get(device)
-        if entry is not None:
-            return entry
-        h = _vp()
-        rc = L.teaser_hip_icp_create(device, C.byref(h))
-        if rc != 0:
-            raise TeaserHipError(rc, "(no MI355X visible: the product has no CPU path)" if rc == 3 else "")
-        entry = (h, threading.Lock())
-        _handles[device] = entry
-        return entry
-
-
-@atexit.register
-def _release():
-    with _handles_lock:
-        if not _handles:
-            return
-        from . import lib
-        L = lib()
-        for h, lock in _handles.values():
-            with lock:
-                L.teaser_hip_icp_destroy(h)
-        _handles.clear()
-
-
-def _cloud(a, what):
-    a = np.ascontiguousarray(np.asarray(a, dtype=np.float64))
-    if a.size == 0:
-        return np.zeros((0, 3))
-    if a.ndim != 2 or a.shape[1] != 3:
-        raise ValueError("%s must be an n x 3 array of points, got shape %s" % (what, a.shape))
-    return a
+def _points(a, what):
+    return _cloud(a, what, kind="array of points")
 
 
 def _init(T):
@@ -283,9 +228,9 @@ def registration_icp_batch(sources, targets, max_correspondence_distance, inits=
     problem (None for a point-to-point problem, else one normal per target point); source_covariances /
     target_covariances: None, or one entry per problem (None unless the problem is Generalized ICP, else n x 3 x 3).
     Returns a list of RegistrationResult, each identical to the same problem run alone."""
-    from . import TeaserHipError, lib
-    srcs = [_cloud(s, "source") for s in sources]
-    dsts = [_cloud(t, "target") for t in targets]
+    from . import lib
+    srcs = [_points(s, "source") for s in sources]
+    dsts = [_points(t, "target") for t in targets]
     b = len(srcs)
     if len(dsts) != b:
         raise ValueError("sources and targets differ in length (%d vs %d)" % (b, len(dsts)))
@@ -303,7 +248,7 @@ def registration_icp_batch(sources, targets, max_correspondence_distance, inits=
                 continue
             if target_normals[k] is None:
                 raise ValueError("point-to-plane needs target_normals (problem %d)" % k)
-            nv = _cloud(target_normals[k], "target_normals")
+            nv = _points(target_normals[k], "target_normals")
             if nv.shape != dsts[k].shape:
                 raise ValueError("target_normals must have the target's shape %s, got %s (problem %d)"
                                  % (dsts[k].shape, nv.shape, k))
@@ -323,7 +268,6 @@ def registration_icp_batch(sources, targets, max_correspondence_distance, inits=
         init = np.ascontiguousarray(np.broadcast_to(a, (b, 4, 4)) if a.shape == (4, 4) else a)
         if init.shape != (b, 4, 4):
             raise ValueError("inits: one 4 x 4 for all problems or b x 4 x 4")
-    h, lock = _handle(device)
     L = lib()
     n_s = np.array([len(s) for s in srcs], dtype=np.int32)
     n_t = np.array([len(t) for t in dsts], dtype=np.int32)
@@ -332,24 +276,18 @@ def registration_icp_batch(sources, targets, max_correspondence_distance, inits=
     corr = [np.zeros((max(int(n), 1), 2), dtype=np.int32) for n in n_s]
     cp = (_ip * max(b, 1))(*[c.ctypes.data_as(_ip) for c in corr])
     out = (IcpResultC * max(b, 1))()
-    args = (h, b, sp, n_s.ctypes.data_as(_ip), tp, n_t.ctypes.data_as(_ip),
+    fn = L.teaser_hip_icp_batch  # point-to-point only: the original entry point
+    args = (b, sp, n_s.ctypes.data_as(_ip), tp, n_t.ctypes.data_as(_ip),
             None if init is None else init.ctypes.data_as(_dp), params, out, cp)
-    with lock:  # the handle serves one call at a time
-        if gicp:  # the entry that takes covariances; it serves the other two methods of a mixed batch too
-            nptr = (_dp * max(b, 1))(*[None if nv is None else nv.ctypes.data_as(_dp) for nv in normals])
-            est = (IcpEstimationC * max(b, 1))(*[IcpEstimationC(*m) for m in ests])
-            csp = (_dp * max(b, 1))(*[None if c is None else c.ctypes.data_as(_dp) for c in cov_s])
-            ctp = (_dp * max(b, 1))(*[None if c is None else c.ctypes.data_as(_dp) for c in cov_t])
-            rc = L.teaser_hip_icp_batch_cov(*args, nptr, est, csp, ctp)
-        elif plane:
-            nptr = (_dp * max(b, 1))(*[None if nv is None else nv.ctypes.data_as(_dp) for nv in normals])
-            est = (IcpEstimationC * max(b, 1))(*[IcpEstimationC(*m) for m in ests])
-            rc = L.teaser_hip_icp_batch_ex(*args, nptr, est)
-        else:  # point-to-point only: the original entry point
-            rc = L.teaser_hip_icp_batch(*args)
-        err = L.teaser_hip_icp_last_error(h).decode() if rc != 0 else ""
-    if rc != 0:
-        raise TeaserHipError(rc, err)
+    if plane or gicp:
+        fn = L.teaser_hip_icp_batch_ex
+        args += ((_dp * max(b, 1))(*[None if nv is None else nv.ctypes.data_as(_dp) for nv in normals]),
+                 (IcpEstimationC * max(b, 1))(*[IcpEstimationC(*m) for m in ests]))
+    if gicp:  # the entry that takes covariances; it serves the other two methods of a mixed batch too
+        fn = L.teaser_hip_icp_batch_cov
+        args += ((_dp * max(b, 1))(*[None if c is None else c.ctypes.data_as(_dp) for c in cov_s]),
+                 (_dp * max(b, 1))(*[None if c is None else c.ctypes.data_as(_dp) for c in cov_t]))
+    _handle(device).call(fn, *args)
     res = []
     for k in range(b):
         o = out[k]
@@ -394,7 +332,7 @@ def covariances_from_normals(normals, epsilon=1e-3):
     epsilon = float(epsilon)
     if not (np.isfinite(epsilon) and epsilon > 0):
         raise ValueError("epsilon must be finite and > 0")
-    nv = _cloud(normals, "normals")
+    nv = _points(normals, "normals")
     out = np.tile(np.eye(3), (len(nv), 1, 1))
     with np.errstate(all="ignore"):
         nn = (nv[:, 0] * nv[:, 0] + nv[:, 1] * nv[:, 1]) + nv[:, 2] * nv[:, 2]
@@ -410,8 +348,8 @@ def estimate_covariances_batch(clouds, radius, max_nn=20, epsilon=1e-3, device=-
     covariance, and C = I - (1 - epsilon) n n^T with n its smallest eigenvector; the identity below 3 neighbours.
     radius, max_nn, epsilon: one value for all clouds or one per cloud.  Returns a list of n x 3 x 3 arrays, each
     identical to the same cloud estimated alone."""
-    from . import TeaserHipError, lib
-    pts = [_cloud(c, "points") for c in clouds]
+    from . import lib
+    pts = [_points(c, "points") for c in clouds]
     b = len(pts)
     rs = np.ascontiguousarray(np.broadcast_to(np.asarray(radius, dtype=np.float64), (b,)))
     es = np.ascontiguousarray(np.broadcast_to(np.asarray(epsilon, dtype=np.float64), (b,)))
@@ -425,17 +363,11 @@ def estimate_covariances_batch(clouds, radius, max_nn=20, epsilon=1e-3, device=-
     out = [np.empty((len(p), 3, 3)) for p in pts]
     if b == 0:
         return out
-    h, lock = _handle(device)
-    L = lib()
     n = np.array([len(p) for p in pts], dtype=np.int32)
     pp = (_dp * b)(*[p.ctypes.data_as(_dp) for p in pts])
     op = (_dp * b)(*[o.ctypes.data_as(_dp) for o in out])
-    with lock:
-        rc = L.teaser_hip_icp_covariances_batch(h, b, pp, n.ctypes.data_as(_ip), rs.ctypes.data_as(_dp),
-                                                ks.ctypes.data_as(_ip), es.ctypes.data_as(_dp), op)
-        err = L.teaser_hip_icp_last_error(h).decode() if rc != 0 else ""
-    if rc != 0:
-        raise TeaserHipError(rc, err)
+    _handle(device).call(lib().teaser_hip_icp_covariances_batch, b, pp, n.ctypes.data_as(_ip),
+                         rs.ctypes.data_as(_dp), ks.ctypes.data_as(_ip), es.ctypes.data_as(_dp), op)
     return out
 
 

@@ -313,8 +313,8 @@ def test_gicp_calls_use_the_cov_entry_and_the_others_their_own(monkeypatch):
             return 0
 
     monkeypatch.setattr(tp, "lib", lambda: FakeLib())
-    monkeypatch.setattr(tp.icp, "_handles", {})
-    monkeypatch.setattr(tp.icp, "_current_device", lambda: 0)
+    monkeypatch.setattr(tp.icp._cache, "handles", {})
+    monkeypatch.setattr(tp._handles, "_current_device", lambda: 0)
     P, Q = np.zeros((4, 3)), np.zeros((6, 3))
     Cp, Cq = np.tile(np.eye(3), (4, 1, 1)), np.tile(np.eye(3), (6, 1, 1))
     gicp = tp.TransformationEstimationForGeneralizedICP(0.01)

@@ -216,8 +216,8 @@ def test_plane_calls_use_the_ex_entry_and_point_calls_the_original(monkeypatch):
             return 0
 
     monkeypatch.setattr(tp, "lib", lambda: FakeLib())
-    monkeypatch.setattr(tp.icp, "_handles", {})
-    monkeypatch.setattr(tp.icp, "_current_device", lambda: 0)
+    monkeypatch.setattr(tp.icp._cache, "handles", {})
+    monkeypatch.setattr(tp._handles, "_current_device", lambda: 0)
     P = np.zeros((4, 3))
     tp.registration_icp(P, P, 0.1)
     tp.registration_icp(P, P, 0.1, estimation_method=tp.TransformationEstimationPointToPoint())

@@ -175,8 +175,8 @@ def test_calls_on_one_handle_are_serialised(monkeypatch):
 
     fake = FakeLib()
     monkeypatch.setattr(tp, "lib", lambda: fake)
-    monkeypatch.setattr(tp.icp, "_handles", {})
-    monkeypatch.setattr(tp.icp, "_current_device", lambda: 0)
+    monkeypatch.setattr(tp.icp._cache, "handles", {})
+    monkeypatch.setattr(tp._handles, "_current_device", lambda: 0)
     P = np.zeros((4, 3))
     errors = []
 
@@ -194,4 +194,4 @@ def test_calls_on_one_handle_are_serialised(monkeypatch):
         t.join()
     assert not errors, errors
     assert rec["calls"] == 24 and rec["peak"] == 1 and rec["creates"] == 1
-    assert list(tp.icp._handles) == [0]
+    assert list(tp.icp._cache.handles) == [0]
