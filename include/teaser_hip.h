@@ -372,6 +372,21 @@ TEASER_HIP_API int32_t teaser_hip_certifier_warmup(int32_t device);
 TEASER_HIP_API int32_t teaser_hip_certify(teaser_hip_solver* h, const teaser_certifier_params_c* p, const double* R,
                            const double* src, const double* dst, const double* theta, int32_t n,
                            teaser_certification_c* out, double* traj, int32_t traj_cap);
+/* The certifier's projection onto the affine dual subspace alone: DRSCertifier::getOptimalDualProjection
+ * (certification.cc:323-452), by the kernel launches the loop of teaser_hip_certify itself makes.  W, W_dual: (4n + 4)^2
+ * doubles, column-major (host); theta: n entries, each +1 or -1; 1 <= n <= 8000.  Uses neither rocSOLVER nor rocBLAS and
+ * does not wait for their warm-up. */
+TEASER_HIP_API int32_t teaser_hip_certify_dual_projection(teaser_hip_solver* h, const double* W, const double* theta,
+                                                          int32_t n, double* W_dual);
+/* teaser_hip_certify, which also copies out the matrices of the 0-based `iteration` of its loop, from the buffers the loop
+ * works on: stages = 6 (4n + 4)^2 doubles (host), column-major, in this order: M entering the iteration, M_psd, W, W_dual,
+ * M_affine, M leaving it (= M entering where the loop stopped at that iteration).  The run is the one teaser_hip_certify
+ * makes: same launches, same trajectory.  TEASER_HIP_ERR_BAD_ARG (the message names `iteration`) when the run ends before
+ * that iteration; out / traj are filled as by teaser_hip_certify then, too. */
+TEASER_HIP_API int32_t teaser_hip_certify_stages(teaser_hip_solver* h, const teaser_certifier_params_c* p, const double* R,
+                                                 const double* src, const double* dst, const double* theta, int32_t n,
+                                                 int32_t iteration, double* stages, double* traj, int32_t traj_cap,
+                                                 teaser_certification_c* out);
 
 /* MaxCliqueSolver::findMaxClique (graph.cc:12-125) on a caller-supplied adjacency bitmap
  * (host pointer, n rows of (n+63)/64 words).  clique: capacity n; sorted on return. */

@@ -127,6 +127,7 @@ EXPORTED_SYMBOLS = [
     "teaser_hip_multi_solve_batch", "teaser_hip_multi_route", "teaser_hip_multi_device_count",
     "teaser_hip_solve_for_scale", "teaser_hip_compute_fpfh", "teaser_hip_match_features", "teaser_hip_tuple_test",
     "teaser_hip_certifier_params_default", "teaser_hip_certify", "teaser_hip_certifier_warmup",
+    "teaser_hip_certify_dual_projection", "teaser_hip_certify_stages",
     "teaser_hip_comm_shard", "teaser_hip_comm_unique_id", "teaser_hip_comm_create", "teaser_hip_comm_destroy",
     "teaser_hip_comm_gather_solutions", "teaser_hip_comm_gather_indices", "teaser_hip_comm_last_error",
     "teaser_hip_icp_params_default", "teaser_hip_icp_create", "teaser_hip_icp_destroy", "teaser_hip_icp_last_error",
@@ -198,6 +199,9 @@ def lib():
     L.teaser_hip_match_features.argtypes = [_vp, _fp, C.c_int32, _fp, C.c_int32, C.c_int32, C.c_int32, _ip, _i64p]
     L.teaser_hip_tuple_test.argtypes = [_vp, _fp, C.c_int32, _fp, C.c_int32, C.c_float, C.c_uint64, _ip, _i64p]
     L.teaser_hip_certify.argtypes = [_vp, C.c_void_p, _dp, _dp, _dp, _dp, C.c_int32, C.c_void_p, _dp, C.c_int32]
+    L.teaser_hip_certify_dual_projection.argtypes = [_vp, _dp, _dp, C.c_int32, _dp]
+    L.teaser_hip_certify_stages.argtypes = [_vp, C.c_void_p, _dp, _dp, _dp, _dp, C.c_int32, C.c_int32, _dp, _dp,
+                                            C.c_int32, C.c_void_p]
     L.teaser_hip_max_clique.argtypes = [_vp, _u64p, C.c_int32, _ip, _ip, _ip]
     L.teaser_hip_submit_batch.argtypes = [_vp, _vp, _vp, _i64p, _ip, C.c_int32, C.c_int32, _ip]
     L.teaser_hip_wait.argtypes = [_vp, C.c_int32, C.POINTER(SolutionC)]
@@ -948,9 +952,7 @@ class DRSCertifier:
         self.params = params if params is not None else DRSCertifier.Params(**kw)
         self._solver = RobustRegistrationSolver(device=device)
 
-    def certify(self, R_solution, src, dst, theta):
-        """src, dst: 3 x N; theta: N entries (+1 inlier, -1 outlier) or a boolean inlier mask
-        (certification.cc:22-37 converts the mask the same way)."""
+    def _inputs(self, R_solution, src, dst, theta):
         R = np.ascontiguousarray(R_solution, dtype=np.float64)
         a, b = _colmajor(src, "src"), _colmajor(dst, "dst")
         th = np.asarray(theta)
@@ -962,13 +964,50 @@ class DRSCertifier:
             raise ValueError("R must be 3 x 3; src, dst 3 x N; theta N")
         p = self.params
         pc = CertifierParamsC(p.noise_bound, p.cbar2, p.sub_optimality, p.max_iterations, p.gamma_tau)
+        return R, a, b, th, n, pc, max(int(p.max_iterations), 1)
+
+    def certify(self, R_solution, src, dst, theta):
+        """src, dst: 3 x N; theta: N entries (+1 inlier, -1 outlier) or a boolean inlier mask
+        (certification.cc:22-37 converts the mask the same way)."""
+        R, a, b, th, n, pc, cap = self._inputs(R_solution, src, dst, theta)
         out = CertificationC()
-        cap = max(int(p.max_iterations), 1)
         traj = np.zeros(cap, dtype=np.float64)
         s = self._solver
         s._check(s._lib.teaser_hip_certify(s._h, C.byref(pc), _ptr(R), _ptr(a), _ptr(b), _ptr(th), n,
                                            C.byref(out), _ptr(traj), cap))
         return CertificationResult(out.is_optimal, out.best_suboptimality, traj[:out.iterations].copy())
+
+    def certify_stages(self, R_solution, src, dst, theta, iteration):
+        """certify() that also returns the matrices of the 0-based `iteration` of its loop (teaser_hip_certify_stages):
+        (CertificationResult, dict of (4N + 4)-square arrays M_in, M_psd, W, W_dual, M_affine, M_out).  An iteration the
+        run does not reach raises TeaserHipError (BAD_ARG)."""
+        R, a, b, th, n, pc, cap = self._inputs(R_solution, src, dst, theta)
+        out = CertificationC()
+        traj = np.zeros(cap, dtype=np.float64)
+        npm = 4 * n + 4
+        buf = np.zeros(6 * npm * npm, dtype=np.float64)
+        s = self._solver
+        s._check(s._lib.teaser_hip_certify_stages(s._h, C.byref(pc), _ptr(R), _ptr(a), _ptr(b), _ptr(th), n, int(iteration),
+                                                  _ptr(buf), _ptr(traj), cap, C.byref(out)))
+        names = ("M_in", "M_psd", "W", "W_dual", "M_affine", "M_out")
+        stages = {nm: buf[k * npm * npm:(k + 1) * npm * npm].reshape(npm, npm).T for k, nm in enumerate(names)}
+        return CertificationResult(out.is_optimal, out.best_suboptimality, traj[:out.iterations].copy()), stages
+
+    def dual_projection(self, W, theta):
+        """getOptimalDualProjection (certification.cc:323-452) by the kernels of certify()'s loop
+        (teaser_hip_certify_dual_projection): W (4N + 4)-square, theta N entries of +-1 (or a boolean mask) -> W_dual."""
+        th = np.asarray(theta)
+        if th.dtype == np.bool_:
+            th = np.where(th, 1.0, -1.0)
+        th = np.ascontiguousarray(th, dtype=np.float64).reshape(-1)
+        n = th.shape[0]
+        Wf = np.asfortranarray(W, dtype=np.float64)
+        if Wf.shape != (4 * n + 4, 4 * n + 4):
+            raise ValueError("W must be (4N + 4) x (4N + 4) for theta of N entries")
+        Wd = np.zeros_like(Wf, order="F")
+        s = self._solver
+        s._check(s._lib.teaser_hip_certify_dual_projection(s._h, _ptr(Wf), _ptr(th), n, _ptr(Wd)))
+        return Wd
 
 
 class MultiDeviceSolver:

@@ -244,9 +244,18 @@ void launch_exact_finish(hipStream_t s, const ProbDesc* d_desc, const ExactProb*
 // DRS certifier (kernels_certify.hip): 0, or -1 rocSOLVER / rocBLAS not loadable, -2 HIP error, -3 library call failed
 // starts (once per process) a background thread that loads rocBLAS / rocSOLVER and their gfx950 code objects
 void certifier_warmup_async(int device);
+// what certify_on_device copies out of one iteration of its loop (teaser_hip_certify_stages)
+struct CertCapture {
+  int iteration;   // 0-based
+  double* out;     // host, 6 (4 + 4N)^2 doubles
+  bool captured;   // set by the run: it reached `iteration`
+};
 int certify_on_device(hipStream_t s, const double* R, const double* src, const double* dst, const double* theta, int N,
                       double noise_bound, double cbar2, double sub_optimality, double max_iterations,
-                      double gamma_tau, int* is_optimal, double* best_suboptimality, std::vector<double>* traj);
+                      double gamma_tau, int* is_optimal, double* best_suboptimality, std::vector<double>* traj,
+                      CertCapture* cap = nullptr);
+// getOptimalDualProjection alone (the launches of the loop): host W -> host W_dual; 0 or -2 (HIP error)
+int dual_projection_on_device(hipStream_t s, const double* W, const double* theta, int N, double* W_dual);
 // global colouring bound on the peel survivors of the selected problems (kernels_clique.hip)
 constexpr int kColourMaxLb = 4096;  // palette limit (64 LDS words per wave)
 constexpr int kColourRounds = 16;  // one per vertex class (8) + the all-in rounds

@@ -10,8 +10,9 @@
 //     dense (`minit()` below);
 //   * the inverse map A_inv of getLinearProjection (certification.cc:538-657: an N(N+1)/2-square sparse
 //     matrix, 2.5e7 entries at N = 100) is never built: its action on b_W is evaluated from its defining
-//     pattern, O(N) per pair (ainv_apply_kernel; checked against the dense matrix by
-//     tests/test_certifier_oracle.py::test_structured_inverse_map);
+//     pattern, O(N) per pair (ainv_apply_kernel; its loops are checked against the dense matrix by
+//     tests/test_certifier_setup.py::test_structured_inverse_map, the kernel itself by
+//     tests/test_gpu_certifier_stages.py);
 //   * the two eigendecompositions per iteration are rocSOLVER's dsyevd and the reconstruction
 //     V max(D, 0) V^T one rocBLAS dgemm (plain library calls, loaded with dlopen on first use so that the
 //     registration path does not depend on them); everything else is hand-written elementwise / block kernels
@@ -253,7 +254,45 @@ __global__ void cert_update_kernel(const double* __restrict__ Maff, const double
   M[k] += gamma * (Maff[k] - Mpsd[k]);
 }
 
+// getOptimalDualProjection (certification.cc:323-452): W -> W_dual, the five launches in stream order.  thp is theta with
+// a leading 1 (N + 1 entries); bW / bWd hold N (N + 1) / 2 rows of 3, w33 N + 1 blocks of 9.
+void launch_dual_projection(hipStream_t s, const double* dW, const double* dThp, int N, double* dbW, double* dbWd,
+                            double* dw33, double* dWd) {
+  const int n = 4 + 4 * N;
+  const dim3 gp((unsigned)((N + 1 + 63) / 64), (unsigned)(N + 1));
+  hipLaunchKernelGGL(cert_bw_kernel, gp, dim3(64), 0, s, dW, dThp, N, n, dbW);
+  hipLaunchKernelGGL(cert_ainv_apply_kernel, gp, dim3(64), 0, s, dbW, dThp, N, dbWd);
+  hipLaunchKernelGGL(cert_wdual_offdiag_kernel, gp, dim3(64), 0, s, dW, dbWd, N, n, dWd);
+  hipLaunchKernelGGL(cert_wdual_diag_kernel, dim3((unsigned)(N + 1)), dim3(64), 0, s, dW, dThp, N, n, dWd, dw33);
+  hipLaunchKernelGGL(cert_wdual_mean_kernel, dim3((unsigned)std::min(64, (N + 64) / 64)), dim3(64), 0, s, dw33, N, n,
+                     dWd);
+}
+
 }  // namespace
+
+// W, W_dual: (4 + 4N)^2 doubles, column-major, on the host; theta: N entries.  No eigensolver, no library warm-up.
+// Returns 0 or -2 (HIP error).
+int dual_projection_on_device(hipStream_t s, const double* W, const double* theta, int N, double* W_dual) {
+  const int n = 4 + 4 * N;
+  const size_t nn = (size_t)n * (size_t)n;
+  const int64_t pairs = (int64_t)(N + 1) * N / 2;
+  std::vector<double> thp((size_t)N + 1, 1.0);
+  std::copy(theta, theta + N, thp.begin() + 1);
+  double *dW = nullptr, *dWd = nullptr, *dThp = nullptr, *dbW = nullptr, *dbWd = nullptr, *dw33 = nullptr;
+  bool ok = hipMalloc(&dW, nn * 8) == hipSuccess && hipMalloc(&dWd, nn * 8) == hipSuccess &&
+            hipMalloc(&dThp, thp.size() * 8) == hipSuccess && hipMalloc(&dbW, (size_t)pairs * 24) == hipSuccess &&
+            hipMalloc(&dbWd, (size_t)pairs * 24) == hipSuccess && hipMalloc(&dw33, (size_t)(N + 1) * 72) == hipSuccess &&
+            hipMemcpyAsync(dW, W, nn * 8, hipMemcpyHostToDevice, s) == hipSuccess &&
+            hipMemcpyAsync(dThp, thp.data(), thp.size() * 8, hipMemcpyHostToDevice, s) == hipSuccess;
+  if (ok) {
+    launch_dual_projection(s, dW, dThp, N, dbW, dbWd, dw33, dWd);
+    ok = hipGetLastError() == hipSuccess && hipMemcpyAsync(W_dual, dWd, nn * 8, hipMemcpyDeviceToHost, s) == hipSuccess;
+  }
+  ok = hipStreamSynchronize(s) == hipSuccess && ok;  // (also when a step failed: thp is read by a copy in flight)
+  for (void* p : {(void*)dW, (void*)dWd, (void*)dThp, (void*)dbW, (void*)dbWd, (void*)dw33})
+    if (p) (void)hipFree(p);
+  return ok ? 0 : -2;
+}
 
 // ---- cold start ---------------------------------------------------------------------------------------------
 // The first rocBLAS handle + the first rocSOLVER call of a process took about 110 s on a fresh box (profiles/r2l).
@@ -382,9 +421,14 @@ void certifier_warmup_async(int device) {
 
 // src / dst: N points, xyz interleaved (= the 3 x N column-major matrices of the reference); R row-major.
 // Returns 0, or -1 (rocSOLVER / rocBLAS not loadable), -2 (HIP error), -3 (library call failed).
+// cap (optional): the matrices of iteration cap->iteration are copied to cap->out (host, 6 (4 + 4N)^2 doubles: M entering,
+// M_psd, W, W_dual, M_affine, M leaving) from the buffers the loop itself works on; cap->captured tells whether the run
+// reached that iteration.  The copies read only: the launches and their order are the same with and without cap.
 int certify_on_device(hipStream_t s, const double* R, const double* src, const double* dst, const double* theta, int N,
                       double noise_bound, double cbar2, double sub_optimality, double max_iterations,
-                      double gamma_tau, int* is_optimal, double* best_suboptimality, std::vector<double>* traj) {
+                      double gamma_tau, int* is_optimal, double* best_suboptimality, std::vector<double>* traj,
+                      CertCapture* cap) {
+  if (cap) cap->captured = false;
   traj->clear();
   *is_optimal = 0;
   *best_suboptimality = INFINITY;
@@ -438,7 +482,6 @@ int certify_on_device(hipStream_t s, const double* R, const double* src, const d
   if (rc == 0) {
     InitBlocks ib{dBlk, dBlk + diag.size(), dBlk + diag.size() + row0.size()};
     const dim3 g1((unsigned)((nn + 255) / 256)), b1(256);
-    const dim3 gp((unsigned)((N + 1 + 63) / 64), (unsigned)(N + 1));
     const double one = 1.0, zero = 0.0;
     double best = INFINITY;
     hipLaunchKernelGGL(cert_init_kernel, g1, b1, 0, s, ib, n, dM);
@@ -459,12 +502,7 @@ int certify_on_device(hipStream_t s, const double* R, const double* src, const d
       }
       hipLaunchKernelGGL(cert_w_kernel, g1, b1, 0, s, dPsd, dM, ib, n, dW);
       // projection onto the affine dual subspace (certification.cc:323-452)
-      hipLaunchKernelGGL(cert_bw_kernel, gp, dim3(64), 0, s, dW, dThp, N, n, dbW);
-      hipLaunchKernelGGL(cert_ainv_apply_kernel, gp, dim3(64), 0, s, dbW, dThp, N, dbWd);
-      hipLaunchKernelGGL(cert_wdual_offdiag_kernel, gp, dim3(64), 0, s, dW, dbWd, N, n, dWd);
-      hipLaunchKernelGGL(cert_wdual_diag_kernel, dim3((unsigned)(N + 1)), dim3(64), 0, s, dW, dThp, N, n, dWd, dw33);
-      hipLaunchKernelGGL(cert_wdual_mean_kernel, dim3((unsigned)std::min(64, (N + 64) / 64)), dim3(64), 0, s, dw33, N, n,
-                         dWd);
+      launch_dual_projection(s, dW, dThp, N, dbW, dbWd, dw33, dWd);
       hipLaunchKernelGGL(cert_affine_kernel, g1, b1, 0, s, dWd, ib, n, dAff);
       // sub-optimality gap (certification.cc:192-231): smallest eigenvalue of sym(M_affine)
       hipLaunchKernelGGL(cert_sym_kernel, g1, b1, 0, s, dAff, n, dA);
@@ -485,8 +523,19 @@ int certify_on_device(hipStream_t s, const double* R, const double* src, const d
       const double gap = info != 0 ? INFINITY : (min_eig > 0) ? 0.0 : (-min_eig * (N + 1)) / mu;
       traj->push_back(gap);
       if (gap < best) best = gap;
-      if (gap < sub_optimality) break;
-      hipLaunchKernelGGL(cert_update_kernel, g1, b1, 0, s, dAff, dPsd, gamma_tau, n, dM);
+      const bool capture = cap && cap->iteration == it;
+      if (capture) {  // (M is still the one that entered: the update comes below)
+        const double* stage[5] = {dM, dPsd, dW, dWd, dAff};
+        for (int k = 0; k < 5; ++k) CERT_HIP(hipMemcpyAsync(cap->out + k * nn, stage[k], nn * 8, hipMemcpyDeviceToHost, s));
+      }
+      const bool stop = gap < sub_optimality;
+      if (!stop) hipLaunchKernelGGL(cert_update_kernel, g1, b1, 0, s, dAff, dPsd, gamma_tau, n, dM);
+      if (capture) {
+        CERT_HIP(hipMemcpyAsync(cap->out + 5 * nn, dM, nn * 8, hipMemcpyDeviceToHost, s));
+        CERT_HIP(hipStreamSynchronize(s));
+        cap->captured = rc == 0;
+      }
+      if (stop) break;
     }
     if (rc == 0 && hipGetLastError() != hipSuccess) fail(-2);
     *best_suboptimality = best;

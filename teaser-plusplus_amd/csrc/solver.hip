@@ -2743,12 +2743,14 @@ int32_t teaser_hip_certifier_warmup(int32_t device) {
   return TEASER_HIP_OK;
 }
 
-int32_t teaser_hip_certify(teaser_hip_solver* h, const teaser_certifier_params_c* p, const double* R,
-                           const double* src, const double* dst, const double* theta, int32_t n,
-                           teaser_certification_c* out, double* traj, int32_t traj_cap) {
+namespace {
+// teaser_hip_certify and teaser_hip_certify_stages: one run; `cap` (optional) names the iteration whose matrices it copies out
+int32_t certify_entry(const char* who, teaser_hip_solver* h, const teaser_certifier_params_c* p, const double* R,
+                      const double* src, const double* dst, const double* theta, int32_t n, teaser_certification_c* out,
+                      double* traj, int32_t traj_cap, thip::CertCapture* cap) {
   if (!h || !p || !R || !out || n < 0 || (n > 0 && (!src || !dst || !theta))) return TEASER_HIP_ERR_BAD_ARG;
   if (n > 8000) {  // (4 + 4n)^2 doubles x 7 matrices beyond ~57 GB; the reference itself is dense O(n^2) memory
-    h->err = "teaser_hip_certify: more than 8000 correspondences";
+    h->err = std::string(who) + ": more than 8000 correspondences";
     return TEASER_HIP_ERR_UNSUPPORTED;
   }
   if (hipSetDevice(h->device) != hipSuccess) return TEASER_HIP_ERR_HIP;
@@ -2756,13 +2758,13 @@ int32_t teaser_hip_certify(teaser_hip_solver* h, const teaser_certifier_params_c
   int opt = 0;
   double best = INFINITY;
   const int rc = thip::certify_on_device(h->stream, R, src, dst, theta, n, p->noise_bound, p->cbar2, p->sub_optimality,
-                                         p->max_iterations, p->gamma_tau, &opt, &best, &t);
+                                         p->max_iterations, p->gamma_tau, &opt, &best, &t, cap);
   if (rc == -1) {
-    h->err = "teaser_hip_certify: librocsolver / librocblas could not be loaded (symmetric eigensolver)";
+    h->err = std::string(who) + ": librocsolver / librocblas could not be loaded (symmetric eigensolver)";
     return TEASER_HIP_ERR_UNSUPPORTED;
   }
   if (rc != 0) {
-    h->err = rc == -2 ? "teaser_hip_certify: HIP error" : "teaser_hip_certify: rocSOLVER / rocBLAS call failed";
+    h->err = std::string(who) + (rc == -2 ? ": HIP error" : ": rocSOLVER / rocBLAS call failed");
     return TEASER_HIP_ERR_HIP;
   }
   out->is_optimal = opt;
@@ -2770,6 +2772,59 @@ int32_t teaser_hip_certify(teaser_hip_solver* h, const teaser_certifier_params_c
   out->best_suboptimality = best;
   if (traj)
     for (size_t k = 0; k < t.size() && (int32_t)k < traj_cap; ++k) traj[k] = t[k];
+  return TEASER_HIP_OK;
+}
+}  // namespace
+
+int32_t teaser_hip_certify(teaser_hip_solver* h, const teaser_certifier_params_c* p, const double* R,
+                           const double* src, const double* dst, const double* theta, int32_t n,
+                           teaser_certification_c* out, double* traj, int32_t traj_cap) {
+  return certify_entry("teaser_hip_certify", h, p, R, src, dst, theta, n, out, traj, traj_cap, nullptr);
+}
+
+int32_t teaser_hip_certify_stages(teaser_hip_solver* h, const teaser_certifier_params_c* p, const double* R,
+                                  const double* src, const double* dst, const double* theta, int32_t n,
+                                  int32_t iteration, double* stages, double* traj, int32_t traj_cap,
+                                  teaser_certification_c* out) {
+  if (!h) return TEASER_HIP_ERR_BAD_ARG;
+  if (!stages) {
+    h->err = "teaser_hip_certify_stages: stages is NULL";
+    return TEASER_HIP_ERR_BAD_ARG;
+  }
+  if (iteration < 0) {
+    h->err = "teaser_hip_certify_stages: iteration must be >= 0";
+    return TEASER_HIP_ERR_BAD_ARG;
+  }
+  thip::CertCapture cap{iteration, stages, false};
+  const int32_t rc = certify_entry("teaser_hip_certify_stages", h, p, R, src, dst, theta, n, out, traj, traj_cap, &cap);
+  if (rc != TEASER_HIP_OK) return rc;
+  if (!cap.captured) {
+    h->err = "teaser_hip_certify_stages: iteration " + std::to_string(iteration) + " was not reached (the run ended after " +
+             std::to_string(out->iterations) + " iterations)";
+    return TEASER_HIP_ERR_BAD_ARG;
+  }
+  return TEASER_HIP_OK;
+}
+
+int32_t teaser_hip_certify_dual_projection(teaser_hip_solver* h, const double* W, const double* theta, int32_t n,
+                                           double* W_dual) {
+  if (!h) return TEASER_HIP_ERR_BAD_ARG;
+  auto refuse = [&](int32_t code, const char* what) {
+    h->err = std::string("teaser_hip_certify_dual_projection: ") + what;
+    return code;
+  };
+  if (!W) return refuse(TEASER_HIP_ERR_BAD_ARG, "W is NULL");
+  if (!theta) return refuse(TEASER_HIP_ERR_BAD_ARG, "theta is NULL");
+  if (!W_dual) return refuse(TEASER_HIP_ERR_BAD_ARG, "W_dual is NULL");
+  if (n < 1) return refuse(TEASER_HIP_ERR_BAD_ARG, "n must be >= 1");
+  if (n > 8000) return refuse(TEASER_HIP_ERR_UNSUPPORTED, "n: more than 8000 correspondences");
+  for (int32_t k = 0; k < n; ++k)
+    if (theta[k] != 1.0 && theta[k] != -1.0) return refuse(TEASER_HIP_ERR_BAD_ARG, "theta has an entry that is neither +1 nor -1");
+  const int64_t nn = (int64_t)(4 + 4 * n) * (4 + 4 * n);
+  for (int64_t k = 0; k < nn; ++k)
+    if (!std::isfinite(W[k])) return refuse(TEASER_HIP_ERR_BAD_ARG, "W has a non-finite entry");
+  if (hipSetDevice(h->device) != hipSuccess) return TEASER_HIP_ERR_HIP;
+  if (thip::dual_projection_on_device(h->stream, W, theta, n, W_dual) != 0) return refuse(TEASER_HIP_ERR_HIP, "HIP error");
   return TEASER_HIP_OK;
 }
 
