@@ -656,9 +656,10 @@ TEASER_HIP_API int32_t teaser_hip_voxel_down_sample(teaser_hip_voxel* voxel, con
                                                     int32_t* voxel_of_point);
 
 /* Batched correspondence front-end: teaser_hip_compute_fpfh and teaser_hip_match_features (see "Correspondence
- * front-end" above for the arithmetic, which is theirs bit for bit) for a BATCH of clouds / pairs per call, on its OWN
- * handle (nothing is shared with teaser_hip_solver).  Problems of mixed sizes share the launches; radii are given per
- * problem.  A call waits for its stream (hipStreamSynchronize) a fixed number of times whatever the batch: twice where
+ * front-end" above for the arithmetic) for a BATCH of clouds / pairs per call, on its OWN handle.  This is the one
+ * implementation of the front-end: those two calls on a teaser_hip_solver are batches of one, run on a features handle
+ * that the solver handle creates at their first use and destroys with itself (they keep their own argument checks:
+ * they accept every radius > 0).  Problems of mixed sizes share the launches; radii are given per problem.  A call waits for its stream (hipStreamSynchronize) a fixed number of times whatever the batch: twice where
  * FPFH is computed, once for matching alone.  The copies of requested features / normals into the caller's arrays, and
  * of the features match_batch reads from them, are one per problem and additional.  Neighbour lists that would exceed
  * an internal budget (4 GiB per wave of clouds) are built in several waves inside the call, with the same results.

@@ -1,6 +1,7 @@
-// features.hip -- host side of the batched correspondence front-end (include/teaser_hip.h, "Batched correspondence
-// front-end"): its own handle, argument validation, the descriptor tables and the launch sequence of the segmented
-// kernels at the end of kernels_features.hip.
+// features.hip -- host side of the correspondence front-end (include/teaser_hip.h, "Batched correspondence
+// front-end"): its own handle, argument validation, the descriptor tables and the launch sequence of the kernels of
+// kernels_features.hip.  The only one: teaser_hip_compute_fpfh and teaser_hip_match_features (solver.hip) come here
+// with a batch of one.
 //
 // FPFH of a batch of clouds.  The points of all clouds are packed one after the other; every radius block and every
 // point finds its cloud through a block -> cloud / point -> cloud map and the descriptor table.
@@ -73,11 +74,19 @@ namespace {
     if (!(b).ensure(bytes)) return fail((h), TEASER_HIP_ERR_OOM, "allocation failed (front-end buffers)"); \
   } while (0)
 
-int32_t check_radius(teaser_hip_features* h, const double* r, const char* name, int b) {
-  const double v = r[b];
-  const float r2 = (float)(v * v);
-  if (!std::isfinite(v) || !(v > 0) || !std::isfinite(r2) || !(r2 > 0))
-    return fail(h, TEASER_HIP_ERR_BAD_ARG, std::string(name) + " must be finite and > 0" + at(b));
+// The batched entry points' rule for the radii of `batch` problems: finite, > 0, and the float square the kernels
+// compare with neither 0 nor inf.  (Not in validate_clouds: teaser_hip_compute_fpfh keeps its older rule, > 0.)
+int32_t check_radii(teaser_hip_features* h, int32_t batch, const double* normal_radius, const double* fpfh_radius) {
+  if (!normal_radius) return fail(h, TEASER_HIP_ERR_BAD_ARG, "normal_radius must not be NULL");
+  if (!fpfh_radius) return fail(h, TEASER_HIP_ERR_BAD_ARG, "fpfh_radius must not be NULL");
+  for (int b = 0; b < batch; ++b)
+    for (int w = 0; w < 2; ++w) {
+      const double v = (w ? fpfh_radius : normal_radius)[b];
+      const float r2 = (float)(v * v);
+      if (!std::isfinite(v) || !(v > 0) || !std::isfinite(r2) || !(r2 > 0))
+        return fail(h, TEASER_HIP_ERR_BAD_ARG,
+                    std::string(w ? "fpfh_radius" : "normal_radius") + " must be finite and > 0" + at(b));
+    }
   return TEASER_HIP_OK;
 }
 
@@ -90,9 +99,6 @@ int32_t validate_clouds(teaser_hip_features* h, int nc, int per_problem, const f
   for (int c = 0; c < nc; ++c) {
     const int b = c / per_problem, side = c % per_problem;
     const int32_t nb = n[side][b];
-    int32_t rc = check_radius(h, normal_radius, "normal_radius", b);
-    if (rc == TEASER_HIP_OK) rc = check_radius(h, fpfh_radius, "fpfh_radius", b);
-    if (rc != TEASER_HIP_OK) return rc;
     if (nb < 0) return fail(h, TEASER_HIP_ERR_BAD_ARG, std::string("n must be >= 0 for ") + names[side] + at(b));
     if (nb > 0 && (!cloud || !cloud[c]))
       return fail(h, TEASER_HIP_ERR_BAD_ARG, std::string(names[side]) + " is NULL" + at(b));
@@ -372,6 +378,26 @@ int32_t run_match(teaser_hip_features* h, int32_t batch, const float* d_feat, co
 
 }  // namespace
 
+int32_t thip::features_fpfh_batch(teaser_hip_features* h, int32_t batch, const float* const* cloud, const int32_t* n,
+                                  const double* normal_radius, const double* fpfh_radius, float* const* fpfh_out,
+                                  float* const* normals_out) {
+  h->err.clear();
+  if (!n) return fail(h, TEASER_HIP_ERR_BAD_ARG, "n must not be NULL");
+  const char* names[1] = {"cloud"};
+  const int32_t* ns[1] = {n};
+  int32_t rc = validate_clouds(h, batch, 1, cloud, names, ns, normal_radius, fpfh_radius);
+  if (rc != TEASER_HIP_OK) return rc;
+  for (int b = 0; b < batch; ++b)
+    if (n[b] > 0 && (!fpfh_out || !fpfh_out[b])) return fail(h, TEASER_HIP_ERR_BAD_ARG, "fpfh_out is NULL" + at(b));
+  FCHK(h, hipSetDevice(h->device), "hipSetDevice");
+  if ((rc = run_fpfh(h, cloud)) != TEASER_HIP_OK) return rc;
+  if (h->desc.back().off + h->desc.back().n == 0) return TEASER_HIP_OK;
+  if ((rc = copy_out(h, h->buf[B_FEAT].as<float>(), 33, fpfh_out, 0, 1)) != TEASER_HIP_OK) return rc;
+  if ((rc = copy_out(h, h->buf[B_NORMALS].as<float>(), 3, normals_out, 0, 1)) != TEASER_HIP_OK) return rc;
+  FCHK(h, hipStreamSynchronize(h->stream), "hipStreamSynchronize (results)");
+  return TEASER_HIP_OK;
+}
+
 extern "C" {
 
 int32_t teaser_hip_features_create(int32_t device, teaser_hip_features** out) { return open_handle(device, out); }
@@ -394,22 +420,9 @@ int32_t teaser_hip_features_fpfh_batch(teaser_hip_features* h, int32_t batch, co
   h->err.clear();
   if (batch < 0) return fail(h, TEASER_HIP_ERR_BAD_ARG, "batch must be >= 0");
   if (batch == 0) return TEASER_HIP_OK;
-  if (!n) return fail(h, TEASER_HIP_ERR_BAD_ARG, "n must not be NULL");
-  if (!normal_radius) return fail(h, TEASER_HIP_ERR_BAD_ARG, "normal_radius must not be NULL");
-  if (!fpfh_radius) return fail(h, TEASER_HIP_ERR_BAD_ARG, "fpfh_radius must not be NULL");
-  const char* names[1] = {"cloud"};
-  const int32_t* ns[1] = {n};
-  int32_t rc = validate_clouds(h, batch, 1, cloud, names, ns, normal_radius, fpfh_radius);
+  const int32_t rc = check_radii(h, batch, normal_radius, fpfh_radius);
   if (rc != TEASER_HIP_OK) return rc;
-  for (int b = 0; b < batch; ++b)
-    if (n[b] > 0 && (!fpfh_out || !fpfh_out[b])) return fail(h, TEASER_HIP_ERR_BAD_ARG, "fpfh_out is NULL" + at(b));
-  FCHK(h, hipSetDevice(h->device), "hipSetDevice");
-  if ((rc = run_fpfh(h, cloud)) != TEASER_HIP_OK) return rc;
-  if (h->desc.back().off + h->desc.back().n == 0) return TEASER_HIP_OK;
-  if ((rc = copy_out(h, h->buf[B_FEAT].as<float>(), 33, fpfh_out, 0, 1)) != TEASER_HIP_OK) return rc;
-  if ((rc = copy_out(h, h->buf[B_NORMALS].as<float>(), 3, normals_out, 0, 1)) != TEASER_HIP_OK) return rc;
-  FCHK(h, hipStreamSynchronize(h->stream), "hipStreamSynchronize (results)");
-  return TEASER_HIP_OK;
+  return features_fpfh_batch(h, batch, cloud, n, normal_radius, fpfh_radius, fpfh_out, normals_out);
 }
 
 int32_t teaser_hip_features_match_batch(teaser_hip_features* h, int32_t batch, const float* const* src_feat,
@@ -466,9 +479,9 @@ int32_t teaser_hip_features_correspondences_batch(teaser_hip_features* h, int32_
   if (batch < 0) return fail(h, TEASER_HIP_ERR_BAD_ARG, "batch must be >= 0");
   if (batch == 0) return TEASER_HIP_OK;
   if (!n_src || !n_dst) return fail(h, TEASER_HIP_ERR_BAD_ARG, "n_src / n_dst must not be NULL");
-  if (!normal_radius) return fail(h, TEASER_HIP_ERR_BAD_ARG, "normal_radius must not be NULL");
-  if (!fpfh_radius) return fail(h, TEASER_HIP_ERR_BAD_ARG, "fpfh_radius must not be NULL");
-  int32_t rc = validate_match_outputs(h, batch, pairs, pair_cap, n_pairs);
+  int32_t rc = check_radii(h, batch, normal_radius, fpfh_radius);
+  if (rc != TEASER_HIP_OK) return rc;
+  rc = validate_match_outputs(h, batch, pairs, pair_cap, n_pairs);
   if (rc != TEASER_HIP_OK) return rc;
   // the clouds of the call, interleaved: cloud 2 b = source of pair b, cloud 2 b + 1 = its target
   std::vector<const float*> cloud(2 * (size_t)batch);

@@ -1,6 +1,5 @@
-// features_internal.h -- structures shared by the batched correspondence front-end's host code (features.hip) and
-// its gfx950 kernels (the segmented kernels at the end of kernels_features.hip), plus the matcher's host-side index
-// bookkeeping, which the single-pair entry point (solver.hip) and the batched one share.
+// features_internal.h -- structures shared by the correspondence front-end's host code (features.hip) and its gfx950
+// kernels (kernels_features.hip), their launchers, and the matcher's host-side index bookkeeping.
 #pragma once
 
 #include <hip/hip_runtime.h>

@@ -331,27 +331,18 @@ hipError_t launch_tls_scale_large(hipStream_t s, const double* d_src, const doub
                                   double beta, double* d_raw, double* d_alpha, char* d_workspace,
                                   double* d_scale, int32_t* d_overflow);
 
-// correspondence front-end (kernels_features.hip): radius neighbour lists (count -> scan -> fill + sort by
-// (distance, index)), PCL-style normals, SPFH + FPFH, exact L2 1-NN
-int64_t feat_nbr_bytes();
-int feat_sort_capacity();
-// lists with more than feat_sort_capacity() entries (skipped by the LDS sort): rank sort through d_scratch (list-sized)
-void launch_feat_sort_long(hipStream_t s, int n, const int32_t* d_counts, const int64_t* d_offsets, void* d_list,
-                           void* d_scratch);
-void launch_feat_radius_count(hipStream_t s, const float* d_pts, int n, float r2, int32_t* d_counts);
-void launch_feat_scan(hipStream_t s, const int32_t* d_counts, int n, int64_t* d_offsets /* n + 1 */,
-                      int64_t* d_total_max /* 2 */);
-void launch_feat_radius_fill_sort(hipStream_t s, const float* d_pts, int n, float r2, const int32_t* d_counts,
-                                  int32_t* d_cursor /* n, scratch */,
-                                  const int64_t* d_offsets, void* d_list);
-void launch_feat_normals(hipStream_t s, const float* d_pts, int n, const int64_t* d_offsets, const int32_t* d_counts,
-                         const void* d_list, float* d_normals);
-void launch_feat_fpfh(hipStream_t s, const float* d_pts, const float* d_normals, int n, const int64_t* d_offsets,
-                      const int32_t* d_counts, const void* d_list, float* d_spfh, float* d_out);
-int feat_nn_chunks(int nd);
+// correspondence front-end: sizes of kernels_features.hip that the host side (features.hip) plans with; its launchers
+// are in features_internal.h
+int64_t feat_nbr_bytes();    // bytes of one (distance, index) neighbour record
+int feat_sort_capacity();    // longest list the LDS sort holds; longer ones take the rank sort
+int feat_nn_chunks(int nd);  // data chunks of a 1-NN search over nd rows
 int feat_nn_max_dim();
-void launch_feat_nn1(hipStream_t s, const float* d_data, int nd, const float* d_query, int nq, int dim,
-                     float* d_part_d, int32_t* d_part_i, int32_t* d_nn);
+// teaser_hip_features_fpfh_batch (features.hip) without its rule for the radii (finite, and the float square neither
+// 0 nor inf): batch > 0, the radii not NULL.  teaser_hip_compute_fpfh (solver.hip) comes in here with its own, older
+// rule (> 0).
+int32_t features_fpfh_batch(teaser_hip_features* h, int32_t batch, const float* const* cloud, const int32_t* n,
+                            const double* normal_radius, const double* fpfh_radius, float* const* fpfh_out,
+                            float* const* normals_out);
 
 // solveForScale on caller-supplied TIMs: TRIM terms (estimate != 0) or the fixed-scale mask
 void launch_tim_scale_terms(hipStream_t s, const double* d_v1, const double* d_v2, int64_t m, double beta,

@@ -1,7 +1,10 @@
 // kernels_features.hip -- the correspondence front-end on gfx950: FPFH descriptors and the mutual
 // nearest-neighbour feature matcher, the stage BEFORE the registration hot path.
 //
-// Replaces, behind the C ABI (teaser_hip_compute_fpfh, teaser_hip_match_features):
+// One set of kernels, segmented over a batch of clouds or feature pairs; features.hip is their host side.  The
+// single-cloud calls of the C ABI (teaser_hip_compute_fpfh, teaser_hip_match_features) are batches of one.
+//
+// Replaces, behind the C ABI (those two and teaser_hip_features_*):
 //   * teaser::FPFHEstimation::computeFPFHFeatures (reference teaser/src/fpfh.cc:15-43), which is a
 //     pass-through to PCL (NOT in the reference tree): pcl::NormalEstimation with a radius search
 //     (features/normal_3d.hpp -> common/centroid.hpp computeMeanAndCovarianceMatrix, float accumulators ->
@@ -90,8 +93,8 @@ constexpr int kFeatChunk = 512;
 
 // FILL == 0: counts[q] += |{ i in chunk : d2(q, i) < r2 }| (counts zeroed by the launcher);
 // FILL == 1: the chunk's neighbours (d2, i) into list[offset[q] + cursor[q] ...] (cursor zeroed by the launcher)
-// (the body of one workgroup: query block `qblock`, data chunk `chunk` of ONE cloud -- shared by the single-cloud
-// kernel and the batched one, which hands it the cloud's own pointers)
+// (the body of one workgroup: query block `qblock`, data chunk `chunk` of ONE cloud, whose own pointers the kernel
+// hands it)
 template <int FILL>
 __device__ __forceinline__ void feat_radius_block(const float* __restrict__ pts, int n, float r2,
                                                   int32_t* __restrict__ counts, const int64_t* __restrict__ offsets,
@@ -122,17 +125,9 @@ __device__ __forceinline__ void feat_radius_block(const float* __restrict__ pts,
     }
   }
 }
-template <int FILL>
-__global__ __launch_bounds__(64) void feat_radius_kernel(const float* __restrict__ pts, int n, float r2,
-                                                         int32_t* __restrict__ counts,
-                                                         const int64_t* __restrict__ offsets,
-                                                         Nbr* __restrict__ list) {
-  feat_radius_block<FILL>(pts, n, r2, counts, offsets, list, blockIdx.x, blockIdx.y);
-}
 
 // exclusive scan of the counts (one workgroup; n <= a few million) + the largest count
-// (one workgroup's scan of one cloud; END: also offsets[n] = total, as the single-cloud launcher promises)
-template <bool END>
+// (one workgroup's scan of one cloud)
 __device__ __forceinline__ void feat_scan_block(const int32_t* __restrict__ counts, int n,
                                                 int64_t* __restrict__ offsets,
                                                 int64_t* __restrict__ total_and_max) {
@@ -168,12 +163,6 @@ __device__ __forceinline__ void feat_scan_block(const int32_t* __restrict__ coun
     offsets[i] = acc;
     acc += counts[i];
   }
-  if (END && t == 1023) offsets[n] = part[1023] + s;
-}
-__global__ __launch_bounds__(1024) void feat_scan_kernel(const int32_t* __restrict__ counts, int n,
-                                                         int64_t* __restrict__ offsets,
-                                                         int64_t* __restrict__ total_and_max) {
-  feat_scan_block<true>(counts, n, offsets, total_and_max);
 }
 
 // per point: bitonic sort of its list by (d2, idx) in LDS (one 256-thread workgroup per point)
@@ -360,15 +349,6 @@ __device__ __forceinline__ void feat_normal_point(const float* __restrict__ pts,
   out[1] = nv[1];
   out[2] = nv[2];
 }
-__global__ __launch_bounds__(128) void feat_normals_kernel(const float* __restrict__ pts, int n,
-                                                           const int64_t* __restrict__ offsets,
-                                                           const int32_t* __restrict__ counts,
-                                                           const Nbr* __restrict__ list,
-                                                           float* __restrict__ normals) {
-  const int q = blockIdx.x * 128 + threadIdx.x;
-  if (q >= n) return;
-  feat_normal_point(pts, q, offsets, counts, list, normals);
-}
 
 // ---- SPFH / FPFH -----------------------------------------------------------------------------------
 // Eigen::Vector4f dot with a zero 4th component, in the order Eigen's SSE reduction adds the lane products
@@ -459,14 +439,6 @@ __device__ __forceinline__ void feat_spfh_point(const float* __restrict__ pts, c
     spfh[(size_t)p * 33 + lane] = h;
   }
 }
-__global__ __launch_bounds__(256) void feat_spfh_kernel(const float* __restrict__ pts,
-                                                        const float* __restrict__ normals, int n,
-                                                        const int64_t* __restrict__ offsets,
-                                                        const int32_t* __restrict__ counts,
-                                                        const Nbr* __restrict__ list, float* __restrict__ spfh) {
-  const int p = blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  feat_spfh_point(pts, normals, p < n, p, offsets, counts, list, spfh);
-}
 
 // weightPointSPFHSignature: one wave per point, lane b = bin b; the neighbours in order of increasing distance
 // (the float sums depend on it).  Per neighbour the bin values val_b = spfh[b] * weight are one coalesced row;
@@ -515,14 +487,6 @@ __device__ __forceinline__ void feat_fpfh_point(int p, const int64_t* __restrict
   }
   if (sum != 0) sum = 100.0f / sum;
   if (lane < 33) out[(size_t)p * 33 + lane] = o * sum;
-}
-__global__ __launch_bounds__(256) void feat_fpfh_kernel(int n, const int64_t* __restrict__ offsets,
-                                                        const int32_t* __restrict__ counts,
-                                                        const Nbr* __restrict__ list,
-                                                        const float* __restrict__ spfh, float* __restrict__ out) {
-  const int p = blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  if (p >= n) return;
-  feat_fpfh_point(p, offsets, counts, list, spfh, out);
 }
 
 // ---- exact L2 1-NN in `dim` dimensions (the matcher's two searches) -------------------------------
@@ -604,13 +568,6 @@ __device__ __forceinline__ void feat_nn_partial_block(const float* __restrict__ 
     part_i[(size_t)chunk * nq + q] = bi;
   }
 }
-template <int DIM>
-__global__ __launch_bounds__(64) void feat_nn_partial_kernel(const float* __restrict__ data, int nd,
-                                                             const float* __restrict__ query, int nq, int dim_rt,
-                                                             float* __restrict__ part_d,
-                                                             int32_t* __restrict__ part_i) {
-  feat_nn_partial_block<DIM>(data, nd, query, nq, dim_rt, part_d, part_i, blockIdx.x, blockIdx.y);
-}
 __device__ __forceinline__ void feat_nn_final_query(const float* __restrict__ part_d,
                                                     const int32_t* __restrict__ part_i, int nq, int chunks,
                                                     int32_t* __restrict__ nn, int q) {
@@ -625,77 +582,14 @@ __device__ __forceinline__ void feat_nn_final_query(const float* __restrict__ pa
   }
   nn[q] = bi;
 }
-__global__ __launch_bounds__(256) void feat_nn_final_kernel(const float* __restrict__ part_d,
-                                                            const int32_t* __restrict__ part_i, int nq,
-                                                            int chunks, int32_t* __restrict__ nn) {
-  const int q = blockIdx.x * 256 + threadIdx.x;
-  if (q >= nq) return;
-  feat_nn_final_query(part_d, part_i, nq, chunks, nn, q);
-}
 
 }  // namespace
 
-// ---- launchers ---------------------------------------------------------------------------------------
-int64_t feat_nbr_bytes() { return (int64_t)sizeof(Nbr); }
-
-void launch_feat_radius_count(hipStream_t s, const float* d_pts, int n, float r2, int32_t* d_counts) {
-  if (n <= 0) return;
-  (void)hipMemsetAsync(d_counts, 0, (size_t)n * 4, s);
-  hipLaunchKernelGGL(feat_radius_kernel<0>, dim3((n + 63) / 64, (n + kFeatChunk - 1) / kFeatChunk), dim3(64), 0, s, d_pts,
-                     n, r2, d_counts, static_cast<const int64_t*>(nullptr), static_cast<Nbr*>(nullptr));
-}
-void launch_feat_scan(hipStream_t s, const int32_t* d_counts, int n, int64_t* d_offsets, int64_t* d_total_max) {
-  hipLaunchKernelGGL(feat_scan_kernel, dim3(1), dim3(1024), 0, s, d_counts, n, d_offsets, d_total_max);
-}
-void launch_feat_radius_fill_sort(hipStream_t s, const float* d_pts, int n, float r2, const int32_t* d_counts,
-                                  int32_t* d_cursor, const int64_t* d_offsets, void* d_list) {
-  if (n <= 0) return;
-  (void)hipMemsetAsync(d_cursor, 0, (size_t)n * 4, s);
-  hipLaunchKernelGGL(feat_radius_kernel<1>, dim3((n + 63) / 64, (n + kFeatChunk - 1) / kFeatChunk), dim3(64), 0, s, d_pts,
-                     n, r2, d_cursor, d_offsets, reinterpret_cast<Nbr*>(d_list));
-  hipLaunchKernelGGL(feat_sort_kernel, dim3(n), dim3(256), 0, s, d_offsets, d_counts, reinterpret_cast<Nbr*>(d_list));
-}
-int feat_sort_capacity() { return kFeatSortCap; }
-void launch_feat_sort_long(hipStream_t s, int n, const int32_t* d_counts, const int64_t* d_offsets, void* d_list,
-                           void* d_scratch) {
-  if (n <= 0) return;
-  hipLaunchKernelGGL(feat_sort_long_kernel, dim3(n), dim3(256), 0, s, d_offsets, d_counts, reinterpret_cast<Nbr*>(d_list),
-                     reinterpret_cast<Nbr*>(d_scratch));
-}
-void launch_feat_normals(hipStream_t s, const float* d_pts, int n, const int64_t* d_offsets, const int32_t* d_counts,
-                         const void* d_list, float* d_normals) {
-  if (n <= 0) return;
-  hipLaunchKernelGGL(feat_normals_kernel, dim3((n + 127) / 128), dim3(128), 0, s, d_pts, n, d_offsets, d_counts,
-                     reinterpret_cast<const Nbr*>(d_list), d_normals);
-}
-void launch_feat_fpfh(hipStream_t s, const float* d_pts, const float* d_normals, int n, const int64_t* d_offsets,
-                      const int32_t* d_counts, const void* d_list, float* d_spfh, float* d_out) {
-  if (n <= 0) return;
-  hipLaunchKernelGGL(feat_spfh_kernel, dim3((n + 3) / 4), dim3(256), 0, s, d_pts, d_normals, n, d_offsets, d_counts,
-                     reinterpret_cast<const Nbr*>(d_list), d_spfh);
-  hipLaunchKernelGGL(feat_fpfh_kernel, dim3((n + 3) / 4), dim3(256), 0, s, n, d_offsets, d_counts,
-                     reinterpret_cast<const Nbr*>(d_list), d_spfh, d_out);
-}
-int feat_nn_chunks(int nd) { return (nd + kNnChunk - 1) / kNnChunk; }
-int feat_nn_max_dim() { return kNnMaxDim; }
-void launch_feat_nn1(hipStream_t s, const float* d_data, int nd, const float* d_query, int nq, int dim,
-                     float* d_part_d, int32_t* d_part_i, int32_t* d_nn) {
-  if (nq <= 0 || nd <= 0) return;
-  const int chunks = feat_nn_chunks(nd);
-  if (dim == 33)  // pcl::FPFHSignature33
-    hipLaunchKernelGGL(feat_nn_partial_kernel<33>, dim3((nq + 63) / 64, chunks), dim3(64), 0, s, d_data, nd, d_query, nq,
-                       dim, d_part_d, d_part_i);
-  else
-    hipLaunchKernelGGL(feat_nn_partial_kernel<0>, dim3((nq + 63) / 64, chunks), dim3(64), 0, s, d_data, nd, d_query, nq,
-                       dim, d_part_d, d_part_i);
-  hipLaunchKernelGGL(feat_nn_final_kernel, dim3((nq + 255) / 256), dim3(256), 0, s, d_part_d, d_part_i, nq, chunks,
-                     d_nn);
-}
-
-// ---- the batched front-end (features.hip): the same workgroup bodies, one launch for many clouds ----------------
+// ---- the kernels: one launch for many clouds (or searches) -------------------------------------------------------
 // A block finds its cloud (or search) through a host-built block -> problem map and the descriptor table, then runs
 // the body above with that problem's own pointers: the chunking of a cloud depends on that cloud alone, so what is
 // computed for it -- and, after the (d2, idx) sort, in which order -- does not depend on its neighbours in the batch.
+// One cloud or one pair is a batch of one.
 namespace {
 
 template <int FILL>
@@ -719,7 +613,7 @@ __global__ __launch_bounds__(1024) void feat_scan_batch_kernel(const FeatCloudDe
                                                                int64_t* __restrict__ offsets,
                                                                int64_t* __restrict__ meta) {
   const FeatCloudDesc d = desc[blockIdx.x];
-  feat_scan_block<false>(counts + d.off, d.n, offsets + d.off, meta + 2 * (size_t)blockIdx.x);
+  feat_scan_block(counts + d.off, d.n, offsets + d.off, meta + 2 * (size_t)blockIdx.x);
 }
 
 __global__ __launch_bounds__(256) void feat_rebase_kernel(const int32_t* __restrict__ pt_cloud,
@@ -796,7 +690,12 @@ __global__ __launch_bounds__(256) void feat_nn_final_batch_kernel(const FeatSear
 
 }  // namespace
 
+// ---- launchers and the sizes the host plans with ------------------------------------------------------------------
 int feat_radius_chunk() { return kFeatChunk; }
+int64_t feat_nbr_bytes() { return (int64_t)sizeof(Nbr); }
+int feat_sort_capacity() { return kFeatSortCap; }
+int feat_nn_chunks(int nd) { return (nd + kNnChunk - 1) / kNnChunk; }
+int feat_nn_max_dim() { return kNnMaxDim; }
 
 void launch_feat_radius_count_batch(hipStream_t s, const FeatCloudDesc* d_desc, const int32_t* d_blk_cloud, int blk_base,
                                     int n_blk, int which, const float* d_pts, int32_t* d_counts) {
@@ -823,7 +722,7 @@ void launch_feat_lists_batch(hipStream_t s, const FeatCloudDesc* d_desc, const i
   Nbr* list = reinterpret_cast<Nbr*>(d_list);
   hipLaunchKernelGGL(feat_radius_batch_kernel<1>, dim3(n_blk), dim3(64), 0, s, d_desc, d_blk_cloud, blk_base, which,
                      d_pts, d_cursor, d_offsets, list);
-  const unsigned n = (unsigned)(pt1 - pt0);  // one workgroup per list: the single-cloud sort kernels, offsets being global
+  const unsigned n = (unsigned)(pt1 - pt0);  // one workgroup per list, offsets being global
   hipLaunchKernelGGL(feat_sort_kernel, dim3(n), dim3(256), 0, s, d_offsets + pt0, d_counts + pt0, list);
   if (d_scratch)
     hipLaunchKernelGGL(feat_sort_long_kernel, dim3(n), dim3(256), 0, s, d_offsets + pt0, d_counts + pt0, list,

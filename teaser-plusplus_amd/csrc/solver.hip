@@ -18,7 +18,6 @@
 #include <thread>
 #include <vector>
 
-#include "features_internal.h"
 #include "internal.h"
 
 namespace thip {
@@ -327,9 +326,9 @@ struct teaser_hip_solver {
   DevBuf x_order, x_src, x_dst, x_bitmap, x_desc, x_state, x_ctrl, x_clique, x_arena, x_probs, x_probs2, x_keys, x_xbits, x_tasks;
   // stand-alone stages
   DevBuf s_a, s_b, s_c, s_d, s_e;
-  // correspondence front-end (FPFH, matcher)
-  DevBuf f_pts, f_counts, f_cursor, f_offsets, f_list, f_list2, f_normals, f_spfh, f_out, f_meta, f_feat_a, f_feat_b, f_part_d,
-      f_part_i, f_nn_a, f_nn_b;
+  // correspondence front-end (FPFH, matcher): the batched front-end's handle, created by the first call that needs
+  // it (front_end); a lane never has one
+  teaser_hip_features* features = nullptr;
 
   PinnedBuf pin_states;  // D2H landing zone of the problem states
   PinnedBuf pin_in;      // H2D staging of the problem descriptors / initial states
@@ -1639,6 +1638,8 @@ void finisher_stop(teaser_hip_solver* lane);
 void release_handle_resources(teaser_hip_solver* h) {
   finisher_stop(h);
   if (h->stream) (void)hipStreamSynchronize(h->stream);
+  if (h->features) (void)teaser_hip_features_destroy(h->features);
+  h->features = nullptr;
   DevBuf* bufs[] = {&h->d_desc, &h->d_state, &h->d_src, &h->d_dst, &h->d_bitmap, &h->d_deg,
                     &h->d_clique, &h->d_start_cliques, &h->d_alive_a, &h->d_alive_b,
                     &h->d_next_count, &h->d_weights, &h->d_rot_inl, &h->d_trans_inl,
@@ -1646,9 +1647,7 @@ void release_handle_resources(teaser_hip_solver* h) {
                     &h->x_src, &h->x_dst, &h->x_bitmap, &h->x_desc, &h->x_state, &h->x_ctrl,
                     &h->x_clique, &h->x_arena, &h->x_probs, &h->x_probs2, &h->x_keys, &h->x_xbits, &h->x_tasks, &h->c_sel, &h->c_colour, &h->c_tent, &h->c_xlist, &h->c_list_a, &h->c_list_b,
                     &h->c_counts, &h->c_bits, &h->c_class, &h->c_mis,
-                    &h->s_a, &h->s_b, &h->s_c, &h->s_d, &h->s_e, &h->f_pts, &h->f_counts, &h->f_cursor, &h->f_offsets, &h->f_list, &h->f_list2,
-                    &h->f_normals, &h->f_spfh, &h->f_out, &h->f_meta, &h->f_feat_a, &h->f_feat_b, &h->f_part_d,
-                    &h->f_part_i, &h->f_nn_a, &h->f_nn_b};
+                    &h->s_a, &h->s_b, &h->s_c, &h->s_d, &h->s_e};
   for (DevBuf* b : bufs) b->release();
   h->pin_states.release();
   h->pin_in.release();
@@ -2670,30 +2669,27 @@ int32_t teaser_hip_multi_route(teaser_hip_multi* mh, int32_t problem, teaser_hip
 }
 
 // ---- correspondence front-end -----------------------------------------------------------------------
+// The two single-cloud entry points are batches of one of the batched front-end (features.hip), on a features handle
+// that the solver handle owns.  They keep their own argument checks and early returns, so that a caller sees the
+// statuses it always saw; what is left goes to the batched implementation.  That work runs on the features handle's
+// stream, not on the solver's: both entry points take host pointers and return after a host synchronisation, so no
+// caller can tell.
 namespace {
-// neighbour lists of every point for one radius: counts, offsets, sorted (d2, idx) lists in h->f_list
-int32_t feat_neighbours(teaser_hip_solver* h, int n, double radius) {
-  hipStream_t s = h->stream;
-  const float r2 = (float)(radius * radius);  // pcl::KdTreeFLANN::radiusSearch: static_cast<float>(radius * radius)
-  HIPCHK(h, h->f_counts.ensure((size_t)n * 4));
-  HIPCHK(h, h->f_cursor.ensure((size_t)n * 4));
-  HIPCHK(h, h->f_offsets.ensure((size_t)(n + 1) * 8));
-  HIPCHK(h, h->f_meta.ensure(16));
-  launch_feat_radius_count(s, h->f_pts.as<float>(), n, r2, h->f_counts.as<int32_t>());
-  launch_feat_scan(s, h->f_counts.as<int32_t>(), n, h->f_offsets.as<int64_t>(), h->f_meta.as<int64_t>());
-  HIPCHK(h, hipGetLastError());
-  int64_t meta[2] = {0, 0};
-  HIPCHK(h, hipMemcpyAsync(meta, h->f_meta.p, 16, hipMemcpyDeviceToHost, s));
-  HIPCHK(h, hipStreamSynchronize(s));
-  HIPCHK(h, h->f_list.ensure((size_t)std::max<int64_t>(meta[0], 1) * (size_t)feat_nbr_bytes()));
-  launch_feat_radius_fill_sort(s, h->f_pts.as<float>(), n, r2, h->f_counts.as<int32_t>(), h->f_cursor.as<int32_t>(),
-                               h->f_offsets.as<int64_t>(), h->f_list.p);
-  if (meta[1] > feat_sort_capacity()) {  // some list is longer than the LDS sort holds: those take the rank sort
-    HIPCHK(h, h->f_list2.ensure((size_t)std::max<int64_t>(meta[0], 1) * (size_t)feat_nbr_bytes()));
-    launch_feat_sort_long(s, n, h->f_counts.as<int32_t>(), h->f_offsets.as<int64_t>(), h->f_list.p, h->f_list2.p);
+int32_t front_end(teaser_hip_solver* h, const char* who, teaser_hip_features** f) {
+  if (!h->features) {
+    const int32_t rc = teaser_hip_features_create(h->device, &h->features);
+    if (rc != TEASER_HIP_OK) {
+      h->err = std::string(who) + ": the front-end's handle could not be created";
+      return rc;
+    }
   }
-  HIPCHK(h, hipGetLastError());
+  *f = h->features;
   return TEASER_HIP_OK;
+}
+// a failed batched call: its message, under the name of the entry point the caller used
+int32_t front_end_failed(teaser_hip_solver* h, const char* who, int32_t rc) {
+  h->err = std::string(who) + ": " + teaser_hip_features_last_error(h->features);
+  return rc;
 }
 }  // namespace
 
@@ -2703,25 +2699,13 @@ int32_t teaser_hip_compute_fpfh(teaser_hip_solver* h, const float* cloud_xyz, in
     return TEASER_HIP_ERR_BAD_ARG;
   if (n == 0) return TEASER_HIP_OK;
   (void)hipSetDevice(h->device);
-  hipStream_t s = h->stream;
-  HIPCHK(h, h->f_pts.ensure((size_t)n * 12));
-  HIPCHK(h, h->f_normals.ensure((size_t)n * 12));
-  HIPCHK(h, h->f_spfh.ensure((size_t)n * 33 * 4));
-  HIPCHK(h, h->f_out.ensure((size_t)n * 33 * 4));
-  HIPCHK(h, hipMemcpyAsync(h->f_pts.p, cloud_xyz, (size_t)n * 12, hipMemcpyHostToDevice, s));
-  int32_t rc = feat_neighbours(h, n, normal_radius);  // fpfh.cc:27-33
+  teaser_hip_features* f = nullptr;
+  int32_t rc = front_end(h, "teaser_hip_compute_fpfh", &f);
   if (rc != TEASER_HIP_OK) return rc;
-  launch_feat_normals(s, h->f_pts.as<float>(), n, h->f_offsets.as<int64_t>(), h->f_counts.as<int32_t>(),
-                      h->f_list.p, h->f_normals.as<float>());
-  rc = feat_neighbours(h, n, fpfh_radius);  // fpfh.cc:36-40
-  if (rc != TEASER_HIP_OK) return rc;
-  launch_feat_fpfh(s, h->f_pts.as<float>(), h->f_normals.as<float>(), n, h->f_offsets.as<int64_t>(),
-                   h->f_counts.as<int32_t>(), h->f_list.p, h->f_spfh.as<float>(), h->f_out.as<float>());
-  HIPCHK(h, hipGetLastError());
-  HIPCHK(h, hipMemcpyAsync(fpfh_out, h->f_out.p, (size_t)n * 33 * 4, hipMemcpyDeviceToHost, s));
-  if (normals_out) HIPCHK(h, hipMemcpyAsync(normals_out, h->f_normals.p, (size_t)n * 12, hipMemcpyDeviceToHost, s));
-  HIPCHK(h, hipStreamSynchronize(s));
-  return TEASER_HIP_OK;
+  // (below the batched entry point's check of the radii: this one accepts every radius > 0, +inf included)
+  rc = thip::features_fpfh_batch(f, 1, &cloud_xyz, &n, &normal_radius, &fpfh_radius, &fpfh_out,
+                                 normals_out ? &normals_out : nullptr);
+  return rc == TEASER_HIP_OK ? rc : front_end_failed(h, "teaser_hip_compute_fpfh", rc);
 }
 
 int32_t teaser_hip_certifier_params_default(teaser_certifier_params_c* p) {
@@ -2832,57 +2816,18 @@ int32_t teaser_hip_match_features(teaser_hip_solver* h, const float* src_feat, i
                                   const float* dst_feat, int32_t n_dst, int32_t dim, int32_t use_crosscheck,
                                   int32_t* pairs, int64_t* n_pairs) {
   if (!h || !n_pairs || n_src < 0 || n_dst < 0 || dim <= 0 || dim > feat_nn_max_dim()) return TEASER_HIP_ERR_BAD_ARG;
-  const int64_t cap = *n_pairs;
+  const int64_t cap = std::max<int64_t>(*n_pairs, 0);  // (a negative capacity holds nothing, like 0)
   *n_pairs = 0;
   if (n_src == 0 || n_dst == 0) return TEASER_HIP_OK;
   if (!src_feat || !dst_feat || !pairs) return TEASER_HIP_ERR_BAD_ARG;
   (void)hipSetDevice(h->device);
-  hipStream_t s = h->stream;
-  // matcher.cc:123-133: i = the larger cloud, j = the smaller one
-  const bool swapped = n_dst > n_src;
-  const float* fi = swapped ? dst_feat : src_feat;
-  const float* fj = swapped ? src_feat : dst_feat;
-  const int ni = swapped ? n_dst : n_src, nj = swapped ? n_src : n_dst;
-  HIPCHK(h, h->f_feat_a.ensure((size_t)ni * dim * 4));
-  HIPCHK(h, h->f_feat_b.ensure((size_t)nj * dim * 4));
-  HIPCHK(h, h->f_nn_a.ensure((size_t)nj * 4));
-  HIPCHK(h, h->f_nn_b.ensure((size_t)ni * 4));
-  const int chunks = std::max(feat_nn_chunks(ni), feat_nn_chunks(nj));
-  HIPCHK(h, h->f_part_d.ensure((size_t)chunks * (size_t)std::max(ni, nj) * 4));
-  HIPCHK(h, h->f_part_i.ensure((size_t)chunks * (size_t)std::max(ni, nj) * 4));
-  HIPCHK(h, hipMemcpyAsync(h->f_feat_a.p, fi, (size_t)ni * dim * 4, hipMemcpyHostToDevice, s));
-  HIPCHK(h, hipMemcpyAsync(h->f_feat_b.p, fj, (size_t)nj * dim * 4, hipMemcpyHostToDevice, s));
-  // :162 for every j its nearest i;  :165 for every i its nearest j (the reference evaluates these lazily)
-  launch_feat_nn1(s, h->f_feat_a.as<float>(), ni, h->f_feat_b.as<float>(), nj, dim, h->f_part_d.as<float>(),
-                  h->f_part_i.as<int32_t>(), h->f_nn_a.as<int32_t>());
-  std::vector<int32_t> j_to_i((size_t)nj), i_nn((size_t)ni);
-  HIPCHK(h, hipMemcpyAsync(j_to_i.data(), h->f_nn_a.p, (size_t)nj * 4, hipMemcpyDeviceToHost, s));
-  launch_feat_nn1(s, h->f_feat_b.as<float>(), nj, h->f_feat_a.as<float>(), ni, dim, h->f_part_d.as<float>(),
-                  h->f_part_i.as<int32_t>(), h->f_nn_b.as<int32_t>());
-  HIPCHK(h, hipGetLastError());
-  HIPCHK(h, hipMemcpyAsync(i_nn.data(), h->f_nn_b.p, (size_t)ni * 4, hipMemcpyDeviceToHost, s));
-  HIPCHK(h, hipStreamSynchronize(s));
-  // A query whose distances are all NaN / +inf (non-finite caller features) has no nearest neighbour: the
-  // kernel reports -1.  FLANN would return garbage there; an error is the honest answer.
-  for (int j = 0; j < nj; ++j)
-    if (j_to_i[(size_t)j] < 0 || j_to_i[(size_t)j] >= ni) {
-      h->err = "teaser_hip_match_features: non-finite feature values (no nearest neighbour for a point)";
-      return TEASER_HIP_ERR_BAD_ARG;
-    }
-  for (int i = 0; i < ni; ++i)
-    if (i_nn[(size_t)i] < 0 || i_nn[(size_t)i] >= nj) {
-      h->err = "teaser_hip_match_features: non-finite feature values (no nearest neighbour for a point)";
-      return TEASER_HIP_ERR_BAD_ARG;
-    }
-  // index bookkeeping of matcher.cc:155-233, 281-296 (O(n) on the host; shared with the batched front-end)
-  const auto corres = feat_match_pairs(j_to_i.data(), nj, i_nn.data(), ni, swapped, use_crosscheck != 0);
-  *n_pairs = (int64_t)corres.size();
-  if ((int64_t)corres.size() > cap) return TEASER_HIP_ERR_BAD_ARG;
-  for (size_t k = 0; k < corres.size(); ++k) {
-    pairs[2 * k] = corres[k].first;
-    pairs[2 * k + 1] = corres[k].second;
-  }
-  return TEASER_HIP_OK;
+  teaser_hip_features* f = nullptr;
+  int32_t rc = front_end(h, "teaser_hip_match_features", &f);
+  if (rc != TEASER_HIP_OK) return rc;
+  // a capacity that is too small: BAD_ARG, *n_pairs = the number needed, nothing written
+  rc = teaser_hip_features_match_batch(f, 1, &src_feat, &n_src, &dst_feat, &n_dst, dim, use_crosscheck, &pairs, &cap,
+                                       n_pairs);
+  return rc == TEASER_HIP_OK ? rc : front_end_failed(h, "teaser_hip_match_features", rc);
 }
 
 int32_t teaser_hip_set_profiling(teaser_hip_solver* h, int32_t level) {
