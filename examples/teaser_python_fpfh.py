@@ -8,6 +8,11 @@ on the MI355X.  Usage:
     python examples/teaser_python_fpfh.py [src.ply dst.ply] [--voxel 0.05] [--certify] [--icp [--icp-iterations 100]]
                                           [--icp-plane [--icp-kernel tukey --icp-kernel-k K]]
                                           [--icp-gicp [--gicp-radius R --gicp-max-nn K]] [--batch K]
+                                          [--knn K [--no-mutual]]
+
+--knn K matches every point with its K nearest descriptors (helpers.py:19-43, find_knn_cpu(feat0, feat1, knn=K)) in
+place of the single mutual nearest neighbour: more putative correspondences for the solver, on the GPU as well.  Only
+pairs that are among each other's K nearest are kept unless --no-mutual is given.
 
 --icp-plane refines with point-to-plane ICP instead, on the target normals the FPFH stage already computed
 (rows PCL leaves non-finite, below 3 neighbours, set to zero: they contribute nothing), optionally with a robust kernel.
@@ -50,7 +55,7 @@ def read_ply_xyz(path):
         return np.stack([data["x"], data["y"], data["z"]], axis=1).astype(np.float32)
 
 
-def run_batch(A, B, vox, K, icp_iterations):
+def run_batch(A, B, vox, K, icp_iterations, knn=0, mutual=True):
     """K perturbed copies of the pair (A, B) through the batched stages, one call per stage."""
     rng = np.random.default_rng(555)
     srcs, dsts = [], []
@@ -72,7 +77,10 @@ def run_batch(A, B, vox, K, icp_iterations):
         down = tp.voxel_down_sample_batch(srcs + dsts, vox)
         t1 = time.perf_counter()
         sp, dp = down[:K], down[K:]
-        corr = tp.correspondences_batch(sp, dp, 2 * vox, 5 * vox)   # helpers.py:9-43 for every pair
+        if knn:
+            corr = tp.correspondences_knn_batch(sp, dp, 2 * vox, 5 * vox, knn, mutual)
+        else:
+            corr = tp.correspondences_batch(sp, dp, 2 * vox, 5 * vox)   # helpers.py:9-43 for every pair
         t2 = time.perf_counter()
         if min(map(len, corr)) < 3:
             sys.exit("pair %d has %d correspondences: nothing to register" % (int(np.argmin([len(c) for c in corr])),
@@ -111,6 +119,9 @@ def main():
     ap.add_argument("--icp-kernel-k", type=float, default=None, help="kernel parameter (default: the voxel size)")
     ap.add_argument("--batch", type=int, default=0, metavar="K",
                     help="register K perturbed copies of the pair through the batched stages")
+    ap.add_argument("--knn", type=int, default=0, metavar="K",
+                    help="match every point with its K nearest descriptors (1 .. 16) instead of the nearest one")
+    ap.add_argument("--no-mutual", action="store_true", help="with --knn: keep one-directional matches too")
     a = ap.parse_args()
     if a.batch > 0:
         if len(a.clouds) == 2:
@@ -118,7 +129,7 @@ def main():
         else:
             c5 = np.load(os.path.join(ROOT, "tests", "golden", "config5_clouds.npz"))
             A, B, a.voxel = c5["cloud_bin_0"].astype(np.float64), c5["cloud_bin_4"].astype(np.float64), float(c5["voxel_size"])
-        return run_batch(A, B, a.voxel, a.batch, a.icp_iterations)
+        return run_batch(A, B, a.voxel, a.batch, a.icp_iterations, a.knn, not a.no_mutual)
     t_ds = None
     if len(a.clouds) == 2:
         raw = [read_ply_xyz(c).astype(np.float64) for c in a.clouds]
@@ -136,7 +147,10 @@ def main():
     fa = est.computeFPFHFeatures(A, 2 * vox, 5 * vox)   # helpers.py:9-18: radii 2 and 5 voxels
     fb = est.computeFPFHFeatures(B, 2 * vox, 5 * vox)
     nb = est.getNormals()   # the target's normals: point-to-plane ICP refines on them
-    corr = tp.Matcher().calculateCorrespondences(A, B, fa, fb, False, True, False, 0)   # helpers.py:27-43
+    if a.knn:
+        corr = [tuple(r) for r in tp.match_features_knn(fa, fb, a.knn, not a.no_mutual).tolist()]   # helpers.py:19-43
+    else:
+        corr = tp.Matcher().calculateCorrespondences(A, B, fa, fb, False, True, False, 0)   # helpers.py:27-43
     t1 = time.perf_counter()
     params = tp.RobustRegistrationSolver.Params(noise_bound=vox, cbar2=1.0, estimate_scaling=False,
                                                 rotation_gnc_factor=1.4, rotation_max_iterations=10000,

@@ -104,6 +104,53 @@ class Matcher {
     return out;
   }
 
+  // The k nearest target descriptors of every source point (no counterpart in the reference library; its tutorial,
+  // examples/teaser_python_fpfh_icp/helpers.py:19-43, does this with a host KD-tree): the sorted (source index,
+  // target index) pairs (i, j) with j among the k nearest of i -- with `mutual` only those where i is also among
+  // the k nearest of j.  k in [1, TEASER_HIP_FEATURES_KNN_MAX]; semantics in teaser_hip.h ("k nearest").
+  // k = 1, mutual = true equals calculateCorrespondences(..., use_crosscheck = true, use_tuple_test = false).
+  std::vector<std::pair<int, int>> calculateKnnCorrespondences(const FPFHCloud& source_features,
+                                                               const FPFHCloud& target_features, int k,
+                                                               bool mutual = true) {
+    return calculateKnnCorrespondencesBatch({source_features}, {target_features}, k, mutual)[0];
+  }
+
+  // calculateKnnCorrespondences for many pairs in one launch sequence (teaser_hip_features_match_knn_batch).
+  std::vector<std::vector<std::pair<int, int>>> calculateKnnCorrespondencesBatch(
+      const std::vector<FPFHCloud>& source_features, const std::vector<FPFHCloud>& target_features, int k,
+      bool mutual = true) {
+    const size_t batch = source_features.size();
+    if (target_features.size() != batch)
+      throw std::invalid_argument("teaser::Matcher::calculateKnnCorrespondencesBatch: lists of different lengths");
+    if (k < 1 || k > TEASER_HIP_FEATURES_KNN_MAX)
+      throw std::invalid_argument("teaser::Matcher::calculateKnnCorrespondencesBatch: k must be in [1, " +
+                                  std::to_string(TEASER_HIP_FEATURES_KNN_MAX) + "]");
+    fh_.create("teaser::Matcher");
+    static_assert(sizeof(std::pair<int, int>) == 8, "packed pairs expected");
+    std::vector<std::vector<std::pair<int, int>>> out(batch);
+    std::vector<const float*> fs(batch), ft(batch);
+    std::vector<int32_t*> pairs(batch);
+    std::vector<int32_t> ns(batch), nt(batch);
+    std::vector<int64_t> cap(batch), cnt(batch, 0);
+    for (size_t b = 0; b < batch; ++b) {
+      ns[b] = (int32_t)source_features[b].size();
+      nt[b] = (int32_t)target_features[b].size();
+      out[b].resize((size_t)ns[b] * (size_t)(nt[b] < k ? nt[b] : k) + 1);
+      cap[b] = (int64_t)out[b].size();
+      fs[b] = reinterpret_cast<const float*>(source_features[b].data());
+      ft[b] = reinterpret_cast<const float*>(target_features[b].data());
+      pairs[b] = reinterpret_cast<int32_t*>(out[b].data());
+    }
+    const int32_t rc = teaser_hip_features_match_knn_batch(fh_, (int32_t)batch, fs.data(), ns.data(), ft.data(),
+                                                           nt.data(), 33, k, mutual ? 1 : 0, pairs.data(), cap.data(),
+                                                           cnt.data());
+    if (rc != TEASER_HIP_OK)
+      throw std::runtime_error(std::string("teaser_hip_features_match_knn_batch status ") + std::to_string(rc) + ": " +
+                               teaser_hip_features_last_error(fh_));
+    for (size_t b = 0; b < batch; ++b) out[b].resize((size_t)cnt[b]);
+    return out;
+  }
+
  private:
   detail::LazyFeatures fh_;  // (declared first: destroyed after the solver)
   detail::LazySolver h_;

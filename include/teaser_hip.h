@@ -702,6 +702,53 @@ TEASER_HIP_API int32_t teaser_hip_features_correspondences_batch(
     float* const* src_feat_out, float* const* dst_feat_out, float* const* src_normals_out,
     float* const* dst_normals_out);
 
+/* k-nearest-neighbour matching on the same handle (no counterpart in the reference library; its tutorial,
+ * examples/teaser_python_fpfh_icp/helpers.py:19-43, feeds the solver the k nearest descriptors per point from a host
+ * KD-tree).  Everything the comment above promises holds here too: mixed sizes, empty sides, batch = 0, one
+ * synchronisation for search or matching alone and two where FPFH is computed, the same refusals, and the same bits
+ * run to run, for a problem alone or inside any batch, and for any value of the part_bytes budget.
+ *   Distance.  The distance of a query row q to a data row x is the 1-NN search's, unchanged: in float,
+ *     d = 0; for c in 0 .. dim-1: t = q_c - x_c; d += t * t     (every operation rounded, nothing fused).
+ *   k nearest.  The k nearest of a query are the k_eff = min(k, nd) smallest candidates under the lexicographic order
+ *     (d, data index): ties go to the lower index, and the slots appear in ascending (d, index) order.
+ *     k lies in [1, TEASER_HIP_FEATURES_KNN_MAX].
+ *   Non-finite values.  A candidate whose d is NaN or +inf never enters a list.  A query that ends with fewer than
+ *     k_eff entries therefore had non-finite features: TEASER_HIP_ERR_BAD_ARG naming the problem index.
+ *   Lists.  For a pair with source features S (n_src rows) and target features T (n_dst rows): F[i] = the k nearest
+ *     rows of T for source row i; B[j] = the k nearest rows of S for target row j.
+ *   Pairs.  mutual = 0: all (i, j) with j in F[i].  mutual = 1: only those where also i is in B[j].  Output: (src, dst)
+ *     int32 pairs in ascending lexicographic order, without duplicates; n_src x min(k, n_dst) pairs of room always
+ *     suffice, and a pair_cap[b] that is too small behaves as in match_batch (every n_pairs[b] reports the count
+ *     needed, the call returns TEASER_HIP_ERR_BAD_ARG).
+ *   Relation to match_batch.  With k = 1 and mutual = 1 the pairs equal those of
+ *     teaser_hip_features_match_batch(..., use_crosscheck = 1) exactly.  With mutual = 0 the result is deliberately the
+ *     tutorial's one-directional set {(i, j): j in F[i]}, NOT the reference matcher's two-directional union
+ *     (use_crosscheck = 0). */
+#define TEASER_HIP_FEATURES_KNN_MAX 16
+/* The raw search of `batch` problems.  data_feat[b]: n_data[b] x dim floats, query_feat[b]: n_query[b] x dim floats;
+ * idx[b]: n_query[b] x k int32 (indices of data rows); dist: NULL, or per problem NULL or n_query[b] x k floats (the
+ * squared distances d).  Slots beyond k_eff hold -1 / +inf. */
+TEASER_HIP_API int32_t teaser_hip_features_knn_batch(teaser_hip_features* features, int32_t batch,
+                                                     const float* const* data_feat, const int32_t* n_data,
+                                                     const float* const* query_feat, const int32_t* n_query,
+                                                     int32_t dim, int32_t k, int32_t* const* idx, float* const* dist);
+/* Features in, pairs out (arguments as teaser_hip_features_match_batch, with k and mutual in place of
+ * use_crosscheck). */
+TEASER_HIP_API int32_t teaser_hip_features_match_knn_batch(teaser_hip_features* features, int32_t batch,
+                                                           const float* const* src_feat, const int32_t* n_src,
+                                                           const float* const* dst_feat, const int32_t* n_dst,
+                                                           int32_t dim, int32_t k, int32_t mutual,
+                                                           int32_t* const* pairs, const int64_t* pair_cap,
+                                                           int64_t* n_pairs);
+/* Clouds in, pairs out: FPFH of both clouds of every pair, then the k-NN matching, the features staying on the device
+ * in between (arguments and optional outputs as teaser_hip_features_correspondences_batch). */
+TEASER_HIP_API int32_t teaser_hip_features_correspondences_knn_batch(
+    teaser_hip_features* features, int32_t batch, const float* const* src_xyz, const int32_t* n_src,
+    const float* const* dst_xyz, const int32_t* n_dst, const double* normal_radius, const double* fpfh_radius,
+    int32_t k, int32_t mutual, int32_t* const* pairs, const int64_t* pair_cap, int64_t* n_pairs,
+    float* const* src_feat_out, float* const* dst_feat_out, float* const* src_normals_out,
+    float* const* dst_normals_out);
+
 /* Page-locked host memory from the HIP runtime THIS library runs on.  teaser_hip_submit_batch(..., INPUT_HOST) moves
  * the points with one DMA copy per cloud, at PCIe speed only when the runtime knows the pages are locked.  A buffer
  * pinned by another HIP runtime instance in the same process (e.g. the one a Python framework bundles) is pageable

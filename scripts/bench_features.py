@@ -11,9 +11,12 @@ features' round trip through host memory per pair.
   stages64      compute_fpfh_batch (128 clouds) and match_features_batch (64 pairs) separately on the same 64
   fixture       the object / scene pair of tests/golden/features_golden.npz (1 000 / 60 865 points, radii 0.02 and
                 0.04 as the reference's matcher test), both ways: one call per pair, twice, vs one call of two pairs
+  knn           (with --knn these workloads only) match_features_knn_batch with k = 1, 4 and 16, mutual, on the FPFH
+                features of the config-5 pair alone and of the 64 perturbed pairs, beside match_features_batch (the 1-NN
+                path) on the same features in the same run: the baseline the k-NN times are divided by
 The object also records the board's name, the ROCm version and the commit (None outside a git checkout).
 Wall-clock medians over --reps synchronous calls after --warmup calls; ms_min / ms_max give the spread.  Usage:
-    python scripts/bench_features.py [--reps 20] [--warmup 3]"""
+    python scripts/bench_features.py [--reps 20] [--warmup 3] [--knn]"""
 import argparse
 import ctypes
 import importlib
@@ -71,10 +74,28 @@ def board_and_rocm():
     return board, rocm
 
 
+def knn_workloads(res, A, B, src, dst, rn, rf, reps, warmup):
+    """res["knn"]: per workload the 1-NN matcher's time and the k-NN matcher's for k = 1, 4, 16 (mutual), the ratio to
+    the 1-NN time, and the number of pairs found."""
+    fa, fb = tp.compute_fpfh_batch([A, B], rn, rf)
+    feats = tp.compute_fpfh_batch(src + dst, rn, rf)
+    res["knn"] = {}
+    for name, fs, fd in (("single_pair", [fa], [fb]), ("batch64", feats[:64], feats[64:])):
+        base = timed(lambda: tp.match_features_batch(fs, fd), reps, warmup)
+        row = dict(match_features_batch=base, pairs_1nn=sum(len(p) for p in tp.match_features_batch(fs, fd)))
+        for k in (1, 4, 16):
+            t = timed(lambda: tp.match_features_knn_batch(fs, fd, k, True), reps, warmup)
+            t["over_match_features_batch"] = t["ms"] / base["ms"]
+            t["pairs"] = sum(len(p) for p in tp.match_features_knn_batch(fs, fd, k, True))
+            row["knn_k%d_mutual" % k] = t
+        res["knn"][name] = row
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--knn", action="store_true", help="the k-NN matching workloads only")
     a = ap.parse_args()
     if tp.device_count() < 1:
         sys.exit("bench_features.py needs an MI355X")
@@ -97,6 +118,11 @@ def main():
                                        text=True).stdout.strip() or None
     except OSError:
         res["commit"] = None
+    if a.knn:
+        res["workload"] = "k-NN matching (k = 1, 4, 16, mutual) of config-5 FPFH features (%d / %d points)" % (len(A), len(B))
+        knn_workloads(res, A, B, src, dst, rn, rf, a.reps, a.warmup)
+        print(json.dumps(res))
+        return
     one = timed(lambda: single(A, B), a.reps, a.warmup)
     b1 = timed(lambda: tp.correspondences_batch([A], [B], rn, rf), a.reps, a.warmup)
     res["single_pair"] = dict(one_call_per_pair=one, batch1=b1, batch1_over_one_call_per_pair=b1["ms"] / one["ms"],
@@ -119,6 +145,7 @@ def main():
                           one_call_per_pair=timed(lambda: (single(obj, scene, frn, frf), single(scene, obj, frn, frf)), reps, 1),
                           batched=timed(lambda: tp.correspondences_batch([obj, scene], [scene, obj], frn, frf), reps, 1))
     res["fixture"]["speedup"] = res["fixture"]["one_call_per_pair"]["ms"] / res["fixture"]["batched"]["ms"]
+    knn_workloads(res, A, B, src, dst, rn, rf, a.reps, a.warmup)
     print(json.dumps(res))
 
 

@@ -138,7 +138,8 @@ EXPORTED_SYMBOLS = [
     "teaser_hip_voxel_down_sample_batch", "teaser_hip_voxel_down_sample",
     "teaser_hip_features_create", "teaser_hip_features_destroy", "teaser_hip_features_last_error",
     "teaser_hip_features_set_budgets", "teaser_hip_features_fpfh_batch", "teaser_hip_features_match_batch",
-    "teaser_hip_features_correspondences_batch",
+    "teaser_hip_features_correspondences_batch", "teaser_hip_features_knn_batch",
+    "teaser_hip_features_match_knn_batch", "teaser_hip_features_correspondences_knn_batch",
 ]
 
 
@@ -1075,7 +1076,9 @@ from .icp import (CauchyLoss, GMLoss, HuberLoss, ICPConvergenceCriteria, L2Loss,
                   covariances_from_normals, estimate_covariances, estimate_covariances_batch,
                   registration_generalized_icp)
 from .voxel import voxel_down_sample, voxel_down_sample_batch  # noqa: E402
-from .features import compute_fpfh_batch, correspondences_batch, match_features_batch  # noqa: E402
+from .features import (compute_fpfh_batch, correspondences_batch, match_features_batch,  # noqa: E402
+                       knn_features, knn_features_batch, match_features_knn, match_features_knn_batch,
+                       correspondences_knn, correspondences_knn_batch)
 
 __all__ = ["batched", "FPFHEstimation", "Matcher", "MultiDeviceSolver", "RobustRegistrationSolver", "RegistrationSolution", "RotationEstimationAlgorithm",
            "InlierSelectionMode", "InlierGraphFormulation", "TeaserHipError", "synth_problem",
@@ -1083,6 +1086,8 @@ __all__ = ["batched", "FPFHEstimation", "Matcher", "MultiDeviceSolver", "RobustR
            "ICPConvergenceCriteria", "TransformationEstimationPointToPoint", "RegistrationResult", "registration_icp",
            "registration_icp_batch", "voxel_down_sample", "voxel_down_sample_batch",
            "compute_fpfh_batch", "match_features_batch", "correspondences_batch",
+           "knn_features", "knn_features_batch", "match_features_knn", "match_features_knn_batch",
+           "correspondences_knn", "correspondences_knn_batch",
            "TransformationEstimationPointToPlane", "L2Loss", "HuberLoss", "CauchyLoss", "GMLoss", "TukeyLoss",
            "TransformationEstimationForGeneralizedICP", "registration_generalized_icp", "estimate_covariances",
            "estimate_covariances_batch", "covariances_from_normals"]

@@ -16,8 +16,11 @@
 // Matching a batch of feature pairs: two searches per pair in one launch, the results of all searches in one copy, one
 // synchronisation, then the O(n) index bookkeeping per pair on the host.  A call therefore waits for the stream
 // (hipStreamSynchronize) 2 times (FPFH, clouds -> correspondences) or once (matching), whatever the batch and the
-// number of waves.  Features and normals the caller asked for, and the features match_batch takes from the host, are
-// copied per problem between the device and the caller's own (pageable) arrays: those copies are additional.
+// number of waves.  The k-NN calls (knn_batch, match_knn_batch, correspondences_knn_batch) keep that contract: the
+// searches of all problems in one launch sequence (run_knn), the device-side mutual filter, one copy of the lists and
+// the keep mask, one synchronisation, then the O(n k) pair writing on the host.  Features and normals the caller asked
+// for, and the features the matching calls take from the host, are copied per problem between the device and the
+// caller's own (pageable) arrays: those copies are additional.
 #include <math.h>
 #include <string.h>
 
@@ -42,11 +45,18 @@ constexpr int64_t kFeatListBudgetBytes = (int64_t)4 << 30;
 constexpr int64_t kFeatPartBudgetBytes = (int64_t)1 << 30;
 
 enum { B_DESC, B_BLK, B_PT_CLOUD, B_PTS, B_COUNTS, B_OFFSETS, B_CURSOR, B_META, B_BASE, B_LIST, B_LIST2, B_NORMALS,
-       B_SPFH, B_FEAT, B_SEARCH, B_SBLK, B_PART_D, B_PART_I, B_NN, B_MFEAT, B_COUNT_OF_BUFS };
-enum { H_PTS, H_META, H_NN, H_COUNT_OF_BUFS };
+       B_SPFH, B_FEAT, B_SEARCH, B_SBLK, B_PART_D, B_PART_I, B_NN, B_MFEAT, B_KNN_I, B_KNN_D, B_KNN_KEEP,
+       B_COUNT_OF_BUFS };
+enum { H_PTS, H_META, H_NN, H_KNN_I, H_KNN_D, H_KNN_KEEP, H_COUNT_OF_BUFS };
 
 struct Wave {
-  int c0, c1;  // clouds (or pairs) [c0, c1)
+  int c0, c1;  // clouds (or pairs, or k-NN searches) [c0, c1)
+};
+
+// One k-NN search of a call: both sides non-empty, rows of the packed feature array.
+struct KnnSearch {
+  int64_t data_row, query_row;
+  int32_t nd, nq;
 };
 
 }  // namespace
@@ -376,6 +386,241 @@ int32_t run_match(teaser_hip_features* h, int32_t batch, const float* d_feat, co
   return TEASER_HIP_OK;
 }
 
+// The k-NN searches `in` over rows of d_feat, enqueued: row q of search number x in B_KNN_I (and B_KNN_D when
+// want_dist) at h->search[x].nn_off = k slots, the k nearest in (d, index) order, then -1 / +inf.  No synchronisation.
+// The partial lists (8 bytes per query, data chunk and list slot of the kernel serving k) of one wave of searches fit
+// the partial-result budget; a wave always holds at least one search.  *total = result slots of all searches.
+int32_t run_knn(teaser_hip_features* h, const std::vector<KnnSearch>& in, const std::vector<int>& problem_of,
+                const float* d_feat, int dim, int k, bool want_dist, int64_t* total) {
+  hipStream_t s = h->stream;
+  DevBuf* B = h->buf;
+  h->search.clear();
+  *total = 0;
+  if (in.empty()) return TEASER_HIP_OK;
+  const int slots = feat_knn_slots(k);
+  const int64_t part_budget = h->part_budget / 8;
+  std::vector<Wave> waves;
+  std::vector<int> wave_blk0;
+  int64_t blocks = 0, part_acc = 0, part_cap = 1;
+  int q0 = 0;
+  for (int q = 0; q < (int)in.size(); ++q) {
+    const KnnSearch& x = in[(size_t)q];
+    const int64_t part = (int64_t)feat_nn_chunks(x.nd) * slots * x.nq;
+    if (q > q0 && part_acc + part > part_budget) {
+      waves.push_back(Wave{q0, q});
+      q0 = q;
+      part_acc = 0;
+    }
+    if (q == q0) wave_blk0.push_back((int)blocks);
+    const FeatSearchDesc d{x.data_row, x.query_row, part_acc, *total, x.nd, x.nq, (int32_t)blocks, (x.nq + 63) / 64};
+    blocks += (int64_t)d.qblocks * feat_nn_chunks(x.nd);
+    if (blocks >= INT32_MAX)
+      return fail(h, TEASER_HIP_ERR_UNSUPPORTED, "too many features in one call" + at(problem_of[(size_t)q]));
+    part_acc += part;
+    part_cap = std::max(part_cap, part_acc);
+    *total += (int64_t)x.nq * k;
+    h->search.push_back(d);
+  }
+  waves.push_back(Wave{q0, (int)in.size()});
+  h->blk_search.resize((size_t)blocks);
+  for (size_t q = 0; q < h->search.size(); ++q) {
+    const int32_t end = q + 1 < h->search.size() ? h->search[q + 1].blk_off : (int32_t)blocks;
+    std::fill(h->blk_search.begin() + h->search[q].blk_off, h->blk_search.begin() + end, (int32_t)q);
+  }
+  FENSURE(h, B[B_SEARCH], sizeof(FeatSearchDesc) * h->search.size());
+  FENSURE(h, B[B_SBLK], 4 * (size_t)blocks);
+  FENSURE(h, B[B_PART_D], 4 * (size_t)part_cap);
+  FENSURE(h, B[B_PART_I], 4 * (size_t)part_cap);
+  FENSURE(h, B[B_KNN_I], 4 * (size_t)*total);
+  if (want_dist) FENSURE(h, B[B_KNN_D], 4 * (size_t)*total);
+  FCHK(h, hipMemcpyAsync(B[B_SEARCH].p, h->search.data(), sizeof(FeatSearchDesc) * h->search.size(),
+                         hipMemcpyHostToDevice, s),
+       "hipMemcpyAsync (search descriptors)");
+  FCHK(h, hipMemcpyAsync(B[B_SBLK].p, h->blk_search.data(), 4 * (size_t)blocks, hipMemcpyHostToDevice, s),
+       "hipMemcpyAsync (search block map)");
+  for (size_t w = 0; w < waves.size(); ++w) {
+    const int s0 = waves[w].c0, s1 = waves[w].c1;
+    const int blk0 = wave_blk0[w], blk1 = s1 < (int)h->search.size() ? h->search[(size_t)s1].blk_off : (int)blocks;
+    int max_nq = 0;
+    for (int q = s0; q < s1; ++q) max_nq = std::max(max_nq, h->search[(size_t)q].nq);
+    launch_feat_knn_batch(s, B[B_SEARCH].as<FeatSearchDesc>(), B[B_SBLK].as<int32_t>(), blk0, blk1 - blk0, s0, s1,
+                          max_nq, d_feat, dim, k, B[B_PART_D].as<float>(), B[B_PART_I].as<int32_t>(),
+                          B[B_KNN_I].as<int32_t>(), want_dist ? B[B_KNN_D].as<float>() : nullptr);
+  }
+  FCHK(h, hipGetLastError(), "front-end kernel launch (k-NN)");
+  return TEASER_HIP_OK;
+}
+
+// Whether every row of an nq x k list holds its k_eff = min(k, nd) entries (sorted: the last of them decides).
+bool knn_rows_full(const int32_t* idx, int nq, int nd, int k) {
+  const int k_eff = std::min(k, nd);
+  bool ok = true;
+  for (int q = 0; q < nq; ++q) ok &= idx[(size_t)q * k + k_eff - 1] >= 0;
+  return ok;
+}
+
+// k-NN matching of `batch` pairs whose features are rows of d_feat: F[i] for every source row, with mutual also B[j]
+// for every target row and the device-side filter; lists and keep mask come back in one copy phase, ONE
+// synchronisation, then the pairs are written row by row, a row's kept targets in ascending order.
+int32_t run_match_knn(teaser_hip_features* h, int32_t batch, const float* d_feat, const int64_t* src_row,
+                      const int64_t* dst_row, const int32_t* n_src, const int32_t* n_dst, int dim, int k, bool mutual,
+                      int32_t* const* pairs, const int64_t* pair_cap, int64_t* n_pairs) {
+  hipStream_t s = h->stream;
+  DevBuf* B = h->buf;
+  for (int b = 0; b < batch; ++b) n_pairs[b] = 0;
+  std::vector<KnnSearch> in;
+  std::vector<int> problem_of, pair_of;
+  int64_t max_entries = 0;
+  for (int b = 0; b < batch; ++b) {
+    if (n_src[b] == 0 || n_dst[b] == 0) continue;
+    in.push_back(KnnSearch{dst_row[b], src_row[b], n_dst[b], n_src[b]});  // F: source rows ask the target
+    problem_of.push_back(b);
+    if (mutual) {
+      in.push_back(KnnSearch{src_row[b], dst_row[b], n_src[b], n_dst[b]});  // B: target rows ask the source
+      problem_of.push_back(b);
+    }
+    pair_of.push_back(b);
+    max_entries = std::max(max_entries, (int64_t)n_src[b] * k);
+  }
+  int64_t total = 0;
+  const int32_t rc = run_knn(h, in, problem_of, d_feat, dim, k, false, &total);
+  if (rc != TEASER_HIP_OK) return rc;
+  const int per_pair = mutual ? 2 : 1;
+  if (total > 0) {
+    FENSURE(h, h->host[H_KNN_I], 4 * (size_t)total);
+    if (mutual) {
+      FENSURE(h, B[B_KNN_KEEP], (size_t)total);
+      FENSURE(h, h->host[H_KNN_KEEP], (size_t)total);
+      launch_feat_knn_mutual_batch(s, B[B_SEARCH].as<FeatSearchDesc>(), (int)pair_of.size(), max_entries, k,
+                                   B[B_KNN_I].as<int32_t>(), B[B_KNN_KEEP].as<uint8_t>());
+      FCHK(h, hipGetLastError(), "front-end kernel launch (mutual filter)");
+      FCHK(h, hipMemcpyAsync(h->host[H_KNN_KEEP].p, B[B_KNN_KEEP].p, (size_t)total, hipMemcpyDeviceToHost, s),
+           "hipMemcpyAsync (keep mask)");
+    }
+    FCHK(h, hipMemcpyAsync(h->host[H_KNN_I].p, B[B_KNN_I].p, 4 * (size_t)total, hipMemcpyDeviceToHost, s),
+         "hipMemcpyAsync (nearest neighbours)");
+  }
+  FCHK(h, hipStreamSynchronize(s), "hipStreamSynchronize (results)");
+
+  int too_small = -1;
+  std::vector<int32_t> row;
+  for (size_t p = 0; p < pair_of.size(); ++p) {
+    const int b = pair_of[p];
+    const FeatSearchDesc& f = h->search[per_pair * p];
+    const int32_t* F = h->host[H_KNN_I].as<int32_t>() + f.nn_off;
+    const uint8_t* keep = mutual ? h->host[H_KNN_KEEP].as<uint8_t>() + f.nn_off : nullptr;
+    bool ok = knn_rows_full(F, f.nq, f.nd, k);
+    if (mutual) {
+      const FeatSearchDesc& r = h->search[per_pair * p + 1];
+      ok = ok && knn_rows_full(h->host[H_KNN_I].as<int32_t>() + r.nn_off, r.nq, r.nd, k);
+    }
+    if (!ok)
+      return fail(h, TEASER_HIP_ERR_BAD_ARG,
+                  "non-finite feature values (fewer than min(k, n) neighbours for a point)" + at(b));
+    const int k_eff = std::min(k, f.nd);
+    int64_t count = 0;
+    for (int i = 0; i < f.nq; ++i)
+      for (int q = 0; q < k_eff; ++q) count += !keep || keep[(size_t)i * k + q];
+    n_pairs[b] = count;
+    if (count > pair_cap[b]) {
+      if (too_small < 0) too_small = b;
+      continue;
+    }
+    int32_t* out = pairs[b];
+    for (int i = 0; i < f.nq; ++i) {
+      row.clear();
+      for (int q = 0; q < k_eff; ++q)
+        if (!keep || keep[(size_t)i * k + q]) row.push_back(F[(size_t)i * k + q]);
+      std::sort(row.begin(), row.end());
+      for (int32_t j : row) {
+        *out++ = i;
+        *out++ = j;
+      }
+    }
+  }
+  if (too_small >= 0)
+    return fail(h, TEASER_HIP_ERR_BAD_ARG, "pair_cap is too small: " + std::to_string(n_pairs[too_small]) +
+                                               " pairs needed" + at(too_small));
+  return TEASER_HIP_OK;
+}
+
+// The two feature sets of every problem (a[b]: n_a[b] x dim, b[b]: n_b[b] x dim), checked and copied one after the
+// other into B_MFEAT; a problem with an empty side is not read.  a_row / b_row = first row of each side.
+int32_t upload_feature_pairs(teaser_hip_features* h, int32_t batch, const float* const* a, const char* a_name,
+                             const int32_t* n_a, const float* const* b, const char* b_name, const int32_t* n_b,
+                             const char* n_names, int dim, std::vector<int64_t>* a_row, std::vector<int64_t>* b_row,
+                             float** d_feat) {
+  a_row->assign((size_t)batch, 0);
+  b_row->assign((size_t)batch, 0);
+  int64_t rows = 0;
+  for (int p = 0; p < batch; ++p) {
+    if (n_a[p] < 0 || n_b[p] < 0) return fail(h, TEASER_HIP_ERR_BAD_ARG, std::string(n_names) + " must be >= 0" + at(p));
+    const bool both = n_a[p] > 0 && n_b[p] > 0;
+    if (both && (!a || !a[p])) return fail(h, TEASER_HIP_ERR_BAD_ARG, std::string(a_name) + " is NULL" + at(p));
+    if (both && (!b || !b[p])) return fail(h, TEASER_HIP_ERR_BAD_ARG, std::string(b_name) + " is NULL" + at(p));
+    (*a_row)[(size_t)p] = rows;
+    rows += both ? n_a[p] : 0;
+    (*b_row)[(size_t)p] = rows;
+    rows += both ? n_b[p] : 0;
+    if (rows >= INT32_MAX) return fail(h, TEASER_HIP_ERR_UNSUPPORTED, "too many features in one call" + at(p));
+  }
+  FCHK(h, hipSetDevice(h->device), "hipSetDevice");
+  FENSURE(h, h->buf[B_MFEAT], 4 * (size_t)std::max<int64_t>(rows, 1) * (size_t)dim);
+  *d_feat = h->buf[B_MFEAT].as<float>();
+  for (int p = 0; p < batch; ++p) {
+    if (n_a[p] == 0 || n_b[p] == 0) continue;
+    FCHK(h, hipMemcpyAsync(*d_feat + (size_t)(*a_row)[(size_t)p] * dim, a[p], 4 * (size_t)n_a[p] * dim,
+                           hipMemcpyHostToDevice, h->stream),
+         "hipMemcpyAsync (features)");
+    FCHK(h, hipMemcpyAsync(*d_feat + (size_t)(*b_row)[(size_t)p] * dim, b[p], 4 * (size_t)n_b[p] * dim,
+                           hipMemcpyHostToDevice, h->stream),
+         "hipMemcpyAsync (features)");
+  }
+  return TEASER_HIP_OK;
+}
+
+// FPFH of both clouds of every pair (cloud 2 b = source of pair b, cloud 2 b + 1 = its target), the copies of the
+// features / normals the caller asked for enqueued; src_row / dst_row = first row of each side in B_FEAT.
+int32_t run_pair_fpfh(teaser_hip_features* h, int32_t batch, const float* const* src_xyz, const int32_t* n_src,
+                      const float* const* dst_xyz, const int32_t* n_dst, const double* normal_radius,
+                      const double* fpfh_radius, float* const* src_feat_out, float* const* dst_feat_out,
+                      float* const* src_normals_out, float* const* dst_normals_out, std::vector<int64_t>* src_row,
+                      std::vector<int64_t>* dst_row) {
+  std::vector<const float*> cloud(2 * (size_t)batch);
+  for (int b = 0; b < batch; ++b) {
+    cloud[2 * (size_t)b] = src_xyz ? src_xyz[b] : nullptr;
+    cloud[2 * (size_t)b + 1] = dst_xyz ? dst_xyz[b] : nullptr;
+  }
+  const char* names[2] = {"src_xyz", "dst_xyz"};
+  const int32_t* ns[2] = {n_src, n_dst};
+  int32_t rc = validate_clouds(h, 2 * batch, 2, cloud.data(), names, ns, normal_radius, fpfh_radius);
+  if (rc != TEASER_HIP_OK) return rc;
+  FCHK(h, hipSetDevice(h->device), "hipSetDevice");
+  if ((rc = run_fpfh(h, cloud.data())) != TEASER_HIP_OK) return rc;
+  if (h->desc.back().off + h->desc.back().n > 0) {  // (features leave the device only where the caller asked)
+    if ((rc = copy_out(h, h->buf[B_FEAT].as<float>(), 33, src_feat_out, 0, 2)) != TEASER_HIP_OK) return rc;
+    if ((rc = copy_out(h, h->buf[B_FEAT].as<float>(), 33, dst_feat_out, 1, 2)) != TEASER_HIP_OK) return rc;
+    if ((rc = copy_out(h, h->buf[B_NORMALS].as<float>(), 3, src_normals_out, 0, 2)) != TEASER_HIP_OK) return rc;
+    if ((rc = copy_out(h, h->buf[B_NORMALS].as<float>(), 3, dst_normals_out, 1, 2)) != TEASER_HIP_OK) return rc;
+  }
+  src_row->resize((size_t)batch);
+  dst_row->resize((size_t)batch);
+  for (int b = 0; b < batch; ++b) {
+    (*src_row)[(size_t)b] = h->desc[2 * (size_t)b].off;
+    (*dst_row)[(size_t)b] = h->desc[2 * (size_t)b + 1].off;
+  }
+  return TEASER_HIP_OK;
+}
+
+int32_t check_knn_args(teaser_hip_features* h, int32_t batch, int32_t dim, int32_t k) {
+  if (batch < 0) return fail(h, TEASER_HIP_ERR_BAD_ARG, "batch must be >= 0");
+  if (dim <= 0 || dim > feat_nn_max_dim())
+    return fail(h, TEASER_HIP_ERR_BAD_ARG, "dim must be in [1, " + std::to_string(feat_nn_max_dim()) + "]");
+  if (k < 1 || k > TEASER_HIP_FEATURES_KNN_MAX)
+    return fail(h, TEASER_HIP_ERR_BAD_ARG, "k must be in [1, " + std::to_string(TEASER_HIP_FEATURES_KNN_MAX) + "]");
+  return TEASER_HIP_OK;
+}
+
 }  // namespace
 
 int32_t thip::features_fpfh_batch(teaser_hip_features* h, int32_t batch, const float* const* cloud, const int32_t* n,
@@ -438,31 +683,11 @@ int32_t teaser_hip_features_match_batch(teaser_hip_features* h, int32_t batch, c
   if (!n_src || !n_dst) return fail(h, TEASER_HIP_ERR_BAD_ARG, "n_src / n_dst must not be NULL");
   int32_t rc = validate_match_outputs(h, batch, pairs, pair_cap, n_pairs);
   if (rc != TEASER_HIP_OK) return rc;
-  std::vector<int64_t> src_row((size_t)batch), dst_row((size_t)batch);
-  int64_t rows = 0;
-  for (int b = 0; b < batch; ++b) {
-    if (n_src[b] < 0 || n_dst[b] < 0) return fail(h, TEASER_HIP_ERR_BAD_ARG, "n_src / n_dst must be >= 0" + at(b));
-    const bool both = n_src[b] > 0 && n_dst[b] > 0;  // (an empty side: zero pairs, the other side is not read)
-    if (both && (!src_feat || !src_feat[b])) return fail(h, TEASER_HIP_ERR_BAD_ARG, "src_feat is NULL" + at(b));
-    if (both && (!dst_feat || !dst_feat[b])) return fail(h, TEASER_HIP_ERR_BAD_ARG, "dst_feat is NULL" + at(b));
-    src_row[(size_t)b] = rows;
-    rows += both ? n_src[b] : 0;
-    dst_row[(size_t)b] = rows;
-    rows += both ? n_dst[b] : 0;
-    if (rows >= INT32_MAX) return fail(h, TEASER_HIP_ERR_UNSUPPORTED, "too many features in one call" + at(b));
-  }
-  FCHK(h, hipSetDevice(h->device), "hipSetDevice");
-  FENSURE(h, h->buf[B_MFEAT], 4 * (size_t)std::max<int64_t>(rows, 1) * (size_t)dim);
-  float* d_feat = h->buf[B_MFEAT].as<float>();
-  for (int b = 0; b < batch; ++b) {
-    if (n_src[b] == 0 || n_dst[b] == 0) continue;
-    FCHK(h, hipMemcpyAsync(d_feat + (size_t)src_row[(size_t)b] * dim, src_feat[b], 4 * (size_t)n_src[b] * dim,
-                           hipMemcpyHostToDevice, h->stream),
-         "hipMemcpyAsync (features)");
-    FCHK(h, hipMemcpyAsync(d_feat + (size_t)dst_row[(size_t)b] * dim, dst_feat[b], 4 * (size_t)n_dst[b] * dim,
-                           hipMemcpyHostToDevice, h->stream),
-         "hipMemcpyAsync (features)");
-  }
+  std::vector<int64_t> src_row, dst_row;
+  float* d_feat = nullptr;
+  rc = upload_feature_pairs(h, batch, src_feat, "src_feat", n_src, dst_feat, "dst_feat", n_dst, "n_src / n_dst", dim,
+                            &src_row, &dst_row, &d_feat);
+  if (rc != TEASER_HIP_OK) return rc;
   return run_match(h, batch, d_feat, src_row.data(), dst_row.data(), n_src, n_dst, dim, use_crosscheck != 0, pairs,
                    pair_cap, n_pairs);
 }
@@ -483,31 +708,113 @@ int32_t teaser_hip_features_correspondences_batch(teaser_hip_features* h, int32_
   if (rc != TEASER_HIP_OK) return rc;
   rc = validate_match_outputs(h, batch, pairs, pair_cap, n_pairs);
   if (rc != TEASER_HIP_OK) return rc;
-  // the clouds of the call, interleaved: cloud 2 b = source of pair b, cloud 2 b + 1 = its target
-  std::vector<const float*> cloud(2 * (size_t)batch);
-  for (int b = 0; b < batch; ++b) {
-    cloud[2 * (size_t)b] = src_xyz ? src_xyz[b] : nullptr;
-    cloud[2 * (size_t)b + 1] = dst_xyz ? dst_xyz[b] : nullptr;
-  }
-  const char* names[2] = {"src_xyz", "dst_xyz"};
-  const int32_t* ns[2] = {n_src, n_dst};
-  rc = validate_clouds(h, 2 * batch, 2, cloud.data(), names, ns, normal_radius, fpfh_radius);
+  std::vector<int64_t> src_row, dst_row;
+  rc = run_pair_fpfh(h, batch, src_xyz, n_src, dst_xyz, n_dst, normal_radius, fpfh_radius, src_feat_out, dst_feat_out,
+                     src_normals_out, dst_normals_out, &src_row, &dst_row);
   if (rc != TEASER_HIP_OK) return rc;
-  FCHK(h, hipSetDevice(h->device), "hipSetDevice");
-  if ((rc = run_fpfh(h, cloud.data())) != TEASER_HIP_OK) return rc;
-  if (h->desc.back().off + h->desc.back().n > 0) {  // (features leave the device only where the caller asked)
-    if ((rc = copy_out(h, h->buf[B_FEAT].as<float>(), 33, src_feat_out, 0, 2)) != TEASER_HIP_OK) return rc;
-    if ((rc = copy_out(h, h->buf[B_FEAT].as<float>(), 33, dst_feat_out, 1, 2)) != TEASER_HIP_OK) return rc;
-    if ((rc = copy_out(h, h->buf[B_NORMALS].as<float>(), 3, src_normals_out, 0, 2)) != TEASER_HIP_OK) return rc;
-    if ((rc = copy_out(h, h->buf[B_NORMALS].as<float>(), 3, dst_normals_out, 1, 2)) != TEASER_HIP_OK) return rc;
-  }
-  std::vector<int64_t> src_row((size_t)batch), dst_row((size_t)batch);
-  for (int b = 0; b < batch; ++b) {
-    src_row[(size_t)b] = h->desc[2 * (size_t)b].off;
-    dst_row[(size_t)b] = h->desc[2 * (size_t)b + 1].off;
-  }
   return run_match(h, batch, h->buf[B_FEAT].as<float>(), src_row.data(), dst_row.data(), n_src, n_dst, 33,
                    use_crosscheck != 0, pairs, pair_cap, n_pairs);
+}
+
+int32_t teaser_hip_features_knn_batch(teaser_hip_features* h, int32_t batch, const float* const* data_feat,
+                                      const int32_t* n_data, const float* const* query_feat, const int32_t* n_query,
+                                      int32_t dim, int32_t k, int32_t* const* idx, float* const* dist) {
+  if (!h) return TEASER_HIP_ERR_BAD_ARG;
+  h->err.clear();
+  int32_t rc = check_knn_args(h, batch, dim, k);
+  if (rc != TEASER_HIP_OK) return rc;
+  if (batch == 0) return TEASER_HIP_OK;
+  if (!n_data || !n_query) return fail(h, TEASER_HIP_ERR_BAD_ARG, "n_data / n_query must not be NULL");
+  for (int b = 0; b < batch; ++b)
+    if (n_query[b] > 0 && (!idx || !idx[b])) return fail(h, TEASER_HIP_ERR_BAD_ARG, "idx is NULL" + at(b));
+  std::vector<int64_t> data_row, query_row;
+  float* d_feat = nullptr;
+  rc = upload_feature_pairs(h, batch, data_feat, "data_feat", n_data, query_feat, "query_feat", n_query,
+                            "n_data / n_query", dim, &data_row, &query_row, &d_feat);
+  if (rc != TEASER_HIP_OK) return rc;
+  std::vector<KnnSearch> in;
+  std::vector<int> problem_of;
+  for (int b = 0; b < batch; ++b) {
+    if (n_data[b] == 0 || n_query[b] == 0) continue;
+    in.push_back(KnnSearch{data_row[(size_t)b], query_row[(size_t)b], n_data[b], n_query[b]});
+    problem_of.push_back(b);
+  }
+  int64_t total = 0;
+  if ((rc = run_knn(h, in, problem_of, d_feat, dim, k, dist != nullptr, &total)) != TEASER_HIP_OK) return rc;
+  if (total > 0) {
+    FENSURE(h, h->host[H_KNN_I], 4 * (size_t)total);
+    FCHK(h, hipMemcpyAsync(h->host[H_KNN_I].p, h->buf[B_KNN_I].p, 4 * (size_t)total, hipMemcpyDeviceToHost, h->stream),
+         "hipMemcpyAsync (nearest neighbours)");
+    if (dist) {
+      FENSURE(h, h->host[H_KNN_D], 4 * (size_t)total);
+      FCHK(h, hipMemcpyAsync(h->host[H_KNN_D].p, h->buf[B_KNN_D].p, 4 * (size_t)total, hipMemcpyDeviceToHost,
+                             h->stream),
+           "hipMemcpyAsync (distances)");
+    }
+  }
+  FCHK(h, hipStreamSynchronize(h->stream), "hipStreamSynchronize (results)");
+  int bad = -1;
+  size_t x = 0;
+  for (int b = 0; b < batch; ++b) {
+    const size_t slots = (size_t)n_query[b] * (size_t)k;
+    if (slots == 0) continue;
+    float* db = dist ? dist[b] : nullptr;
+    if (n_data[b] == 0) {  // nothing to find: k_eff = 0
+      std::fill_n(idx[b], slots, -1);
+      if (db) std::fill_n(db, slots, (float)INFINITY);
+      continue;
+    }
+    const FeatSearchDesc& d = h->search[x++];
+    memcpy(idx[b], h->host[H_KNN_I].as<int32_t>() + d.nn_off, 4 * slots);
+    if (db) memcpy(db, h->host[H_KNN_D].as<float>() + d.nn_off, 4 * slots);
+    if (bad < 0 && !knn_rows_full(idx[b], d.nq, d.nd, k)) bad = b;
+  }
+  if (bad >= 0)
+    return fail(h, TEASER_HIP_ERR_BAD_ARG,
+                "non-finite feature values (fewer than min(k, n) neighbours for a point)" + at(bad));
+  return TEASER_HIP_OK;
+}
+
+int32_t teaser_hip_features_match_knn_batch(teaser_hip_features* h, int32_t batch, const float* const* src_feat,
+                                            const int32_t* n_src, const float* const* dst_feat, const int32_t* n_dst,
+                                            int32_t dim, int32_t k, int32_t mutual, int32_t* const* pairs,
+                                            const int64_t* pair_cap, int64_t* n_pairs) {
+  if (!h) return TEASER_HIP_ERR_BAD_ARG;
+  h->err.clear();
+  int32_t rc = check_knn_args(h, batch, dim, k);
+  if (rc != TEASER_HIP_OK) return rc;
+  if (batch == 0) return TEASER_HIP_OK;
+  if (!n_src || !n_dst) return fail(h, TEASER_HIP_ERR_BAD_ARG, "n_src / n_dst must not be NULL");
+  if ((rc = validate_match_outputs(h, batch, pairs, pair_cap, n_pairs)) != TEASER_HIP_OK) return rc;
+  std::vector<int64_t> src_row, dst_row;
+  float* d_feat = nullptr;
+  rc = upload_feature_pairs(h, batch, src_feat, "src_feat", n_src, dst_feat, "dst_feat", n_dst, "n_src / n_dst", dim,
+                            &src_row, &dst_row, &d_feat);
+  if (rc != TEASER_HIP_OK) return rc;
+  return run_match_knn(h, batch, d_feat, src_row.data(), dst_row.data(), n_src, n_dst, dim, k, mutual != 0, pairs,
+                       pair_cap, n_pairs);
+}
+
+int32_t teaser_hip_features_correspondences_knn_batch(
+    teaser_hip_features* h, int32_t batch, const float* const* src_xyz, const int32_t* n_src,
+    const float* const* dst_xyz, const int32_t* n_dst, const double* normal_radius, const double* fpfh_radius,
+    int32_t k, int32_t mutual, int32_t* const* pairs, const int64_t* pair_cap, int64_t* n_pairs,
+    float* const* src_feat_out, float* const* dst_feat_out, float* const* src_normals_out,
+    float* const* dst_normals_out) {
+  if (!h) return TEASER_HIP_ERR_BAD_ARG;
+  h->err.clear();
+  int32_t rc = check_knn_args(h, batch, 33, k);
+  if (rc != TEASER_HIP_OK) return rc;
+  if (batch == 0) return TEASER_HIP_OK;
+  if (!n_src || !n_dst) return fail(h, TEASER_HIP_ERR_BAD_ARG, "n_src / n_dst must not be NULL");
+  if ((rc = check_radii(h, batch, normal_radius, fpfh_radius)) != TEASER_HIP_OK) return rc;
+  if ((rc = validate_match_outputs(h, batch, pairs, pair_cap, n_pairs)) != TEASER_HIP_OK) return rc;
+  std::vector<int64_t> src_row, dst_row;
+  rc = run_pair_fpfh(h, batch, src_xyz, n_src, dst_xyz, n_dst, normal_radius, fpfh_radius, src_feat_out, dst_feat_out,
+                     src_normals_out, dst_normals_out, &src_row, &dst_row);
+  if (rc != TEASER_HIP_OK) return rc;
+  return run_match_knn(h, batch, h->buf[B_FEAT].as<float>(), src_row.data(), dst_row.data(), n_src, n_dst, 33, k,
+                       mutual != 0, pairs, pair_cap, n_pairs);
 }
 
 }  // extern "C"

@@ -59,6 +59,19 @@ void launch_feat_nn1_batch(hipStream_t s, const FeatSearchDesc* d_search, const 
                            int n_blk, int s0, int s1, int max_nq, const float* d_feat, int dim, float* d_part_d,
                            int32_t* d_part_i, int32_t* d_nn);
 
+// k-NN (include/teaser_hip.h, "k nearest").  The searches use FeatSearchDesc and the block map as the 1-NN launch
+// does, with part_off counting the chunks x feat_knn_slots(k) x nq partial entries and nn_off the nq x k result slots
+// of the searches before.
+int feat_knn_slots(int k);  // list slots of the kernel instantiation that serves k (2, 4, 8 or 16)
+// searches [s0, s1): row q of d_idx / d_dist (d_dist may be nullptr) = the k nearest in (d, index) order, then -1 / +inf
+void launch_feat_knn_batch(hipStream_t s, const FeatSearchDesc* d_search, const int32_t* d_blk_search, int blk_base,
+                           int n_blk, int s0, int s1, int max_nq, const float* d_feat, int dim, int k, float* d_part_d,
+                           int32_t* d_part_i, int32_t* d_idx, float* d_dist);
+// pairs p < n_pairs with searches 2 p (forward) and 2 p + 1 (backward): d_keep[nn_off of 2 p + i k + slot] = whether
+// source row i is among the k nearest of its neighbour F[i][slot]; max_entries = the largest nq x k of a forward search
+void launch_feat_knn_mutual_batch(hipStream_t s, const FeatSearchDesc* d_search, int n_pairs, int64_t max_entries,
+                                  int k, const int32_t* d_idx, uint8_t* d_keep);
+
 // Index bookkeeping of Matcher::advancedMatching (reference matcher.cc:155-233, 281-296) after the two searches:
 // i = the larger cloud, j = the smaller one, j_to_i[j] = nearest i of j, i_nn[i] = nearest j of i (both valid
 // indices).  Returns the sorted unique (src, dst) pairs.

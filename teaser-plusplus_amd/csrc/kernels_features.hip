@@ -583,6 +583,122 @@ __device__ __forceinline__ void feat_nn_final_query(const float* __restrict__ pa
   nn[q] = bi;
 }
 
+// ---- exact L2 k-NN (include/teaser_hip.h, "k nearest"): the k smallest (d, index) per query ----------------------
+// Same grid, staging and distance arithmetic as the 1-NN pair above; a thread keeps the K best of its chunk as a list
+// sorted by (d, index) in registers.  K is a template parameter (2, 4, 8, 16; a call's k is rounded up): the list
+// is only ever indexed by the unrolled loops' constants, so it stays in VGPRs -- a runtime-indexed array would live in
+// scratch memory.  Candidates arrive in ascending index order and the comparisons are strict, so among equal d the
+// lower index stays ahead; NaN and +inf fail every `<` against the +inf the list starts with and never enter.
+template <int K>
+__device__ __forceinline__ void feat_knn_insert(float (&ld)[K], int32_t (&li)[K], float d, int32_t idx) {
+#pragma unroll
+  for (int s = K - 1; s > 0; --s) {  // (downwards: slot s - 1 is still the old one when slot s takes it)
+    const bool shift = d < ld[s - 1], here = d < ld[s];
+    li[s] = shift ? li[s - 1] : (here ? idx : li[s]);
+    ld[s] = shift ? ld[s - 1] : (here ? d : ld[s]);
+  }
+  li[0] = d < ld[0] ? idx : li[0];
+  ld[0] = d < ld[0] ? d : ld[0];
+}
+// partials: [chunk][slot][query], so that the lanes of a wave store neighbouring words
+template <int DIM, int K>
+__device__ __forceinline__ void feat_knn_partial_block(const float* __restrict__ data, int nd,
+                                                       const float* __restrict__ query, int nq, int dim_rt,
+                                                       float* __restrict__ part_d, int32_t* __restrict__ part_i,
+                                                       int qblock, int chunk) {
+  constexpr int kPad = DIM > 0 ? ((DIM + 3) & ~3) : kNnMaxDim;
+  __shared__ __attribute__((aligned(16))) float tile[kNnTile * kPad];
+  __shared__ float qs[DIM > 0 ? 1 : 64 * (kNnMaxDim + 1)];
+  const int dim = DIM > 0 ? DIM : dim_rt;
+  const int q = qblock * 64 + threadIdx.x;
+  const bool live = q < nq;
+  float qr[DIM > 0 ? kPad : 1];
+  if (DIM > 0) {
+#pragma unroll
+    for (int c = 0; c < kPad; ++c) qr[c] = (live && c < DIM) ? query[(size_t)q * DIM + c] : 0.f;
+  } else {
+    for (int c = 0; c < dim; ++c) qs[threadIdx.x * (kNnMaxDim + 1) + c] = live ? query[(size_t)q * dim + c] : 0.f;
+  }
+  const int lo = chunk * kNnChunk, hi = min(nd, lo + kNnChunk);
+  float ld[K];
+  int32_t li[K];
+#pragma unroll
+  for (int s = 0; s < K; ++s) {
+    ld[s] = __builtin_inff();
+    li[s] = -1;
+  }
+  for (int base = lo; base < hi; base += kNnTile) {
+    const int m = min(kNnTile, hi - base);
+    __syncthreads();
+    if (DIM > 0) {
+      for (int k = threadIdx.x; k < m * kPad; k += 64) {
+        const int pt = k / kPad, c = k - pt * kPad;
+        tile[k] = c < DIM ? data[(size_t)(base + pt) * DIM + c] : 0.f;
+      }
+    } else {
+      for (int k = threadIdx.x; k < m * dim; k += 64) tile[(k / dim) * kPad + (k % dim)] = data[(size_t)base * dim + k];
+    }
+    __syncthreads();
+    for (int k = 0; k < m; ++k) {
+      float d = 0;  // (the 1-NN kernel's arithmetic, operation for operation)
+      if (DIM > 0) {
+        const float4* row = reinterpret_cast<const float4*>(tile + k * kPad);
+#pragma unroll
+        for (int c4 = 0; c4 < kPad / 4; ++c4) {
+          const float4 x = row[c4];
+          const float xs[4] = {x.x, x.y, x.z, x.w};
+#pragma unroll
+          for (int e = 0; e < 4; ++e)
+            if (4 * c4 + e < DIM) {
+              const float t = qr[4 * c4 + e] - xs[e];
+              d += t * t;
+            }
+        }
+      } else {
+        for (int c = 0; c < dim; ++c) {
+          const float t = qs[threadIdx.x * (kNnMaxDim + 1) + c] - tile[k * kPad + c];
+          d += t * t;
+        }
+      }
+      if (d < ld[K - 1]) feat_knn_insert<K>(ld, li, d, base + k);  // one compare per distance in the common case
+    }
+  }
+  if (live) {
+#pragma unroll
+    for (int s = 0; s < K; ++s) {
+      part_d[((size_t)chunk * K + s) * nq + q] = ld[s];
+      part_i[((size_t)chunk * K + s) * nq + q] = li[s];
+    }
+  }
+}
+// One thread per query: the chunks' lists, taken in chunk order and slot order, go through the same strict insertion,
+// so an entry of a lower chunk (lower indices) stays ahead of an equal d of a higher one: the global (d, index) order.
+// A chunk's list is sorted, so its first entry that does not enter ends that chunk.  Row q of idx / dist: k slots.
+template <int K>
+__device__ __forceinline__ void feat_knn_final_query(const float* __restrict__ part_d,
+                                                     const int32_t* __restrict__ part_i, int nq, int chunks, int k,
+                                                     int32_t* __restrict__ idx, float* __restrict__ dist, int q) {
+  float ld[K];
+  int32_t li[K];
+#pragma unroll
+  for (int s = 0; s < K; ++s) {
+    ld[s] = __builtin_inff();
+    li[s] = -1;
+  }
+  for (int c = 0; c < chunks; ++c)
+    for (int s = 0; s < K; ++s) {
+      const float d = part_d[((size_t)c * K + s) * nq + q];
+      if (!(d < ld[K - 1])) break;
+      feat_knn_insert<K>(ld, li, d, part_i[((size_t)c * K + s) * nq + q]);
+    }
+#pragma unroll
+  for (int s = 0; s < K; ++s)
+    if (s < k) {
+      idx[(size_t)q * k + s] = li[s];
+      if (dist) dist[(size_t)q * k + s] = ld[s];
+    }
+}
+
 }  // namespace
 
 // ---- the kernels: one launch for many clouds (or searches) -------------------------------------------------------
@@ -688,6 +804,51 @@ __global__ __launch_bounds__(256) void feat_nn_final_batch_kernel(const FeatSear
                       nn + d.nn_off, q);
 }
 
+// k-NN searches: the descriptors and the block map of the 1-NN launch; part_off counts (chunk, slot, query) entries
+// and nn_off the nq x k result slots of the searches before this one.
+template <int DIM, int K>
+__global__ __launch_bounds__(64) void feat_knn_partial_batch_kernel(const FeatSearchDesc* __restrict__ search,
+                                                                    const int32_t* __restrict__ blk_search,
+                                                                    int blk_base, const float* __restrict__ feat,
+                                                                    int dim_rt, float* __restrict__ part_d,
+                                                                    int32_t* __restrict__ part_i) {
+  const int blk = blk_base + (int)blockIdx.x;
+  const FeatSearchDesc d = search[blk_search[blk]];
+  const int local = blk - d.blk_off;
+  const int chunk = local / d.qblocks, qblock = local - chunk * d.qblocks;
+  const int dim = DIM > 0 ? DIM : dim_rt;
+  feat_knn_partial_block<DIM, K>(feat + d.data_row * dim, d.nd, feat + d.query_row * dim, d.nq, dim_rt,
+                                 part_d + d.part_off, part_i + d.part_off, qblock, chunk);
+}
+template <int K>
+__global__ __launch_bounds__(256) void feat_knn_final_batch_kernel(const FeatSearchDesc* __restrict__ search, int s0,
+                                                                   const float* __restrict__ part_d,
+                                                                   const int32_t* __restrict__ part_i, int k,
+                                                                   int32_t* __restrict__ idx,
+                                                                   float* __restrict__ dist) {
+  const FeatSearchDesc d = search[s0 + (int)blockIdx.y];
+  const int q = blockIdx.x * 256 + threadIdx.x;
+  if (q >= d.nq) return;
+  feat_knn_final_query<K>(part_d + d.part_off, part_i + d.part_off, d.nq, (d.nd + kNnChunk - 1) / kNnChunk, k,
+                          idx + d.nn_off, dist ? dist + d.nn_off : nullptr, q);
+}
+// Searches 2 p (forward: rows F[i] of source row i) and 2 p + 1 (backward: rows B[j] of target row j) of pair
+// p0 + blockIdx.y; one thread per forward entry e = i * k + slot: keep[e] = whether i is in B[F[i][slot]].
+__global__ __launch_bounds__(256) void feat_knn_mutual_batch_kernel(const FeatSearchDesc* __restrict__ search, int p0,
+                                                                    int k, const int32_t* __restrict__ idx,
+                                                                    uint8_t* __restrict__ keep) {
+  const int p = p0 + (int)blockIdx.y;
+  const FeatSearchDesc f = search[2 * p], b = search[2 * p + 1];
+  const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (e >= (int64_t)f.nq * k) return;
+  const int i = (int)(e / k);
+  const int j = idx[f.nn_off + e];
+  bool found = false;
+  if (j >= 0 && j < b.nq)
+    for (int s = 0; s < k; ++s) found |= idx[b.nn_off + (int64_t)j * k + s] == i;
+  keep[f.nn_off + e] = found ? 1 : 0;
+}
+
 }  // namespace
 
 // ---- launchers and the sizes the host plans with ------------------------------------------------------------------
@@ -758,6 +919,51 @@ void launch_feat_nn1_batch(hipStream_t s, const FeatSearchDesc* d_search, const 
   for (int y0 = s0; y0 < s1; y0 += 65535)  // (the grid's y extent)
     hipLaunchKernelGGL(feat_nn_final_batch_kernel, dim3((max_nq + 255) / 256, std::min(65535, s1 - y0)), dim3(256), 0, s,
                        d_search, y0, d_part_d, d_part_i, d_nn);
+}
+
+int feat_knn_slots(int k) { return k <= 2 ? 2 : k <= 4 ? 4 : k <= 8 ? 8 : 16; }
+
+namespace {
+template <int K>
+void launch_feat_knn_slots(hipStream_t s, const FeatSearchDesc* d_search, const int32_t* d_blk_search, int blk_base,
+                           int n_blk, int s0, int s1, int max_nq, const float* d_feat, int dim, int k, float* d_part_d,
+                           int32_t* d_part_i, int32_t* d_idx, float* d_dist) {
+  if (dim == 33)
+    hipLaunchKernelGGL((feat_knn_partial_batch_kernel<33, K>), dim3(n_blk), dim3(64), 0, s, d_search, d_blk_search,
+                       blk_base, d_feat, dim, d_part_d, d_part_i);
+  else
+    hipLaunchKernelGGL((feat_knn_partial_batch_kernel<0, K>), dim3(n_blk), dim3(64), 0, s, d_search, d_blk_search,
+                       blk_base, d_feat, dim, d_part_d, d_part_i);
+  for (int y0 = s0; y0 < s1; y0 += 65535)
+    hipLaunchKernelGGL(feat_knn_final_batch_kernel<K>, dim3((max_nq + 255) / 256, std::min(65535, s1 - y0)), dim3(256),
+                       0, s, d_search, y0, d_part_d, d_part_i, k, d_idx, d_dist);
+}
+}  // namespace
+
+void launch_feat_knn_batch(hipStream_t s, const FeatSearchDesc* d_search, const int32_t* d_blk_search, int blk_base,
+                           int n_blk, int s0, int s1, int max_nq, const float* d_feat, int dim, int k, float* d_part_d,
+                           int32_t* d_part_i, int32_t* d_idx, float* d_dist) {
+  if (n_blk <= 0 || s1 <= s0 || max_nq <= 0) return;
+  switch (feat_knn_slots(k)) {
+#define THIP_KNN_CASE(K)                                                                                         \
+  case K:                                                                                                        \
+    launch_feat_knn_slots<K>(s, d_search, d_blk_search, blk_base, n_blk, s0, s1, max_nq, d_feat, dim, k, d_part_d, \
+                             d_part_i, d_idx, d_dist);                                                           \
+    break;
+    THIP_KNN_CASE(2)
+    THIP_KNN_CASE(4)
+    THIP_KNN_CASE(8)
+    THIP_KNN_CASE(16)
+#undef THIP_KNN_CASE
+  }
+}
+void launch_feat_knn_mutual_batch(hipStream_t s, const FeatSearchDesc* d_search, int n_pairs, int64_t max_entries,
+                                  int k, const int32_t* d_idx, uint8_t* d_keep) {
+  if (n_pairs <= 0 || max_entries <= 0) return;
+  for (int p0 = 0; p0 < n_pairs; p0 += 65535)
+    hipLaunchKernelGGL(feat_knn_mutual_batch_kernel, dim3((unsigned)((max_entries + 255) / 256),
+                                                          std::min(65535, n_pairs - p0)),
+                       dim3(256), 0, s, d_search, p0, k, d_idx, d_keep);
 }
 
 }  // namespace thip

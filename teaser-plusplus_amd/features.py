@@ -2,7 +2,9 @@
 clouds / pairs per call -- ``compute_fpfh_batch``, ``match_features_batch`` and ``correspondences_batch`` (clouds in,
 correspondences out, the features staying on the device in between).  The arithmetic is that of
 ``FPFHEstimation.computeFPFHFeatures`` / ``Matcher.calculateCorrespondences`` bit for bit; the contract is written out
-in include/teaser_hip.h ("Batched correspondence front-end").
+in include/teaser_hip.h ("Batched correspondence front-end").  ``knn_features_batch``, ``match_features_knn_batch`` and
+``correspondences_knn_batch`` (and their single-problem forms) match every point with its k nearest descriptors, as
+the reference's tutorial does with a host KD-tree; their semantics are in the same header ("k nearest").
 
 One library handle is kept per device between calls; calls from several threads are safe -- each handle has a lock,
 so calls for one device run one after the other.  device=-1 means the calling thread's current HIP device at the
@@ -31,6 +33,13 @@ def declare(L):
     L.teaser_hip_features_correspondences_batch.argtypes = [
         _vp, C.c_int32, C.POINTER(_fp), _ip, C.POINTER(_fp), _ip, _dp, _dp, C.c_int32, C.POINTER(_ip), _i64p, _i64p,
         C.POINTER(_fp), C.POINTER(_fp), C.POINTER(_fp), C.POINTER(_fp)]
+    L.teaser_hip_features_knn_batch.argtypes = [_vp, C.c_int32, C.POINTER(_fp), _ip, C.POINTER(_fp), _ip, C.c_int32,
+                                                C.c_int32, C.POINTER(_ip), C.POINTER(_fp)]
+    L.teaser_hip_features_match_knn_batch.argtypes = [_vp, C.c_int32, C.POINTER(_fp), _ip, C.POINTER(_fp), _ip,
+                                                      C.c_int32, C.c_int32, C.c_int32, C.POINTER(_ip), _i64p, _i64p]
+    L.teaser_hip_features_correspondences_knn_batch.argtypes = [
+        _vp, C.c_int32, C.POINTER(_fp), _ip, C.POINTER(_fp), _ip, _dp, _dp, C.c_int32, C.c_int32, C.POINTER(_ip), _i64p,
+        _i64p, C.POINTER(_fp), C.POINTER(_fp), C.POINTER(_fp), C.POINTER(_fp)]
 
 
 class _Handle(Handle):
@@ -95,6 +104,32 @@ def _counts(arrays):
 
 def _pair_buffers(n_src, n_dst, batch):
     cap = np.array([int(n_src[b]) + int(n_dst[b]) for b in range(batch)] or [0], dtype=np.int64)
+    bufs = [np.zeros((max(int(cap[b]), 1), 2), dtype=np.int32) for b in range(batch)]
+    return cap, bufs, np.zeros(max(batch, 1), dtype=np.int64)
+
+
+KNN_MAX = 16  # TEASER_HIP_FEATURES_KNN_MAX
+
+
+def _knn_k(k):
+    """k as an int in [1, KNN_MAX]; anything else (a float, a bool, 0, 17) is a ValueError naming k."""
+    if isinstance(k, (bool, np.bool_)) or not isinstance(k, (int, np.integer)) or not 1 <= int(k) <= KNN_MAX:
+        raise ValueError("k must be an integer in [1, %d], got %r" % (KNN_MAX, k))
+    return int(k)
+
+
+def _two_sides(a_feats, b_feats, what_a, what_b):
+    """Two lists of feature arrays of one length and one dim: (arrays a, arrays b, dim)."""
+    _same_length(a_feats, b_feats, what_a, what_b)
+    a, dim_a = _features(a_feats, what_a)
+    d, dim_d = _features(b_feats, what_b)
+    if dim_a is not None and dim_d is not None and dim_a != dim_d:
+        raise ValueError("%s have dim %d, %s have dim %d" % (what_a, dim_a, what_b, dim_d))
+    return a, d, dim_a or dim_d or 33
+
+
+def _knn_pair_buffers(n_src, n_dst, k, batch):
+    cap = np.array([int(n_src[b]) * min(k, int(n_dst[b])) for b in range(batch)] or [0], dtype=np.int64)
     bufs = [np.zeros((max(int(cap[b]), 1), 2), dtype=np.int32) for b in range(batch)]
     return cap, bufs, np.zeros(max(batch, 1), dtype=np.int64)
 
@@ -167,3 +202,82 @@ def correspondences_batch(src_clouds, dst_clouds, normal_radius, fpfh_radius, us
                  for k in range(b)]
     parts = [pairs] + ([feats] if return_features else []) + ([nrms] if return_normals else [])
     return parts[0] if len(parts) == 1 else tuple(parts)
+
+
+# ---- k nearest neighbours (include/teaser_hip.h, "k nearest") -------------------------------------------------------
+def knn_features_batch(data, query, k, return_distance=False, device=-1):
+    """The raw search for many problems in one launch sequence: per problem the n_query x k int32 array of the k
+    nearest rows of data[b] for every row of query[b], in ascending (squared L2 distance in float, index) order --
+    ties go to the lower index; slots beyond min(k, n_data) hold -1.  With return_distance=True the tuple
+    (indices, distances), distances being the list of n_query x k float32 squared distances (+inf in unused slots)."""
+    k = _knn_k(k)
+    dat, qry, dim = _two_sides(data, query, "data", "query")
+    b = len(dat)
+    n_d, n_q = _counts(dat), _counts(qry)
+    idx = [np.zeros((q.shape[0], k), dtype=np.int32) for q in qry]
+    dist = [np.zeros((q.shape[0], k), dtype=np.float32) for q in qry] if return_distance else None
+    h = _handle(device)
+    h.call(h._lib.teaser_hip_features_knn_batch, b, _ptrs(dat, _fp), n_d.ctypes.data_as(_ip), _ptrs(qry, _fp),
+           n_q.ctypes.data_as(_ip), dim, k, _ptrs(idx, _ip), None if dist is None else _ptrs(dist, _fp))
+    return (idx, dist) if return_distance else idx
+
+
+def match_features_knn_batch(src_feats, dst_feats, k, mutual=True, device=-1):
+    """k-nearest-neighbour matching of many feature pairs in one launch sequence: per pair the sorted (src, dst) int32
+    pairs (i, j) with j among the k nearest target rows of source row i -- with mutual=True only those where i is also
+    among the k nearest source rows of j.  k = 1, mutual=True equals match_features_batch(use_crosscheck=True);
+    mutual=False is the tutorial's one-directional set, not the reference matcher's two-directional union."""
+    k = _knn_k(k)
+    a, d, dim = _two_sides(src_feats, dst_feats, "src_feats", "dst_feats")
+    b = len(a)
+    n_src, n_dst = _counts(a), _counts(d)
+    cap, bufs, cnt = _knn_pair_buffers(n_src, n_dst, k, b)
+    h = _handle(device)
+    h.call(h._lib.teaser_hip_features_match_knn_batch, b, _ptrs(a, _fp), n_src.ctypes.data_as(_ip), _ptrs(d, _fp),
+           n_dst.ctypes.data_as(_ip), dim, k, 1 if mutual else 0, _ptrs(bufs, _ip), cap.ctypes.data_as(_i64p),
+           cnt.ctypes.data_as(_i64p))
+    return [bufs[p][:int(cnt[p])].copy() for p in range(b)]
+
+
+def correspondences_knn_batch(src_clouds, dst_clouds, normal_radius, fpfh_radius, k, mutual=True,
+                              return_features=False, return_normals=False, device=-1):
+    """Clouds in, k-nearest-neighbour correspondences out, for many pairs in one launch sequence: compute_fpfh_batch
+    followed by match_features_knn_batch with the features staying on the device.  Returns as correspondences_batch
+    does: the list of pair arrays, or a tuple with [src_feats, dst_feats] / [src_normals, dst_normals] where asked."""
+    k = _knn_k(k)
+    _same_length(src_clouds, dst_clouds, "src_clouds", "dst_clouds")
+    sp, dp = _clouds(src_clouds, "src_clouds"), _clouds(dst_clouds, "dst_clouds")
+    b = len(sp)
+    nr, fr = _radii(normal_radius, b, "normal_radius"), _radii(fpfh_radius, b, "fpfh_radius")
+    n_src, n_dst = _counts(sp), _counts(dp)
+    cap, bufs, cnt = _knn_pair_buffers(n_src, n_dst, k, b)
+    feats = nrms = None
+    if return_features:
+        feats = [[np.zeros((p.shape[0], 33), dtype=np.float32) for p in side] for side in (sp, dp)]
+    if return_normals:
+        nrms = [[np.zeros((p.shape[0], 3), dtype=np.float32) for p in side] for side in (sp, dp)]
+    h = _handle(device)
+    h.call(h._lib.teaser_hip_features_correspondences_knn_batch, b, _ptrs(sp, _fp), n_src.ctypes.data_as(_ip),
+           _ptrs(dp, _fp), n_dst.ctypes.data_as(_ip), nr.ctypes.data_as(_dp), fr.ctypes.data_as(_dp), k,
+           1 if mutual else 0, _ptrs(bufs, _ip), cap.ctypes.data_as(_i64p), cnt.ctypes.data_as(_i64p),
+           None if feats is None else _ptrs(feats[0], _fp), None if feats is None else _ptrs(feats[1], _fp),
+           None if nrms is None else _ptrs(nrms[0], _fp), None if nrms is None else _ptrs(nrms[1], _fp))
+    pairs = [bufs[p][:int(cnt[p])].copy() for p in range(b)]
+    parts = [pairs] + ([feats] if return_features else []) + ([nrms] if return_normals else [])
+    return parts[0] if len(parts) == 1 else tuple(parts)
+
+
+def knn_features(data, query, k, return_distance=False, device=-1):
+    """knn_features_batch for one problem: the n_query x k index array (and the distance array)."""
+    out = knn_features_batch([data], [query], k, return_distance, device)
+    return (out[0][0], out[1][0]) if return_distance else out[0]
+
+
+def match_features_knn(src_feats, dst_feats, k, mutual=True, device=-1):
+    """match_features_knn_batch for one pair: its array of (src, dst) pairs."""
+    return match_features_knn_batch([src_feats], [dst_feats], k, mutual, device)[0]
+
+
+def correspondences_knn(src_cloud, dst_cloud, normal_radius, fpfh_radius, k, mutual=True, device=-1):
+    """correspondences_knn_batch for one pair: its array of (src, dst) pairs."""
+    return correspondences_knn_batch([src_cloud], [dst_cloud], normal_radius, fpfh_radius, k, mutual, device=device)[0]
