@@ -8,11 +8,15 @@ on the MI355X.  Usage:
     python examples/teaser_python_fpfh.py [src.ply dst.ply] [--voxel 0.05] [--certify] [--icp [--icp-iterations 100]]
                                           [--icp-plane [--icp-kernel tukey --icp-kernel-k K]]
                                           [--icp-gicp [--gicp-radius R --gicp-max-nn K]] [--batch K]
-                                          [--knn K [--no-mutual]]
+                                          [--knn K [--no-mutual]] [--tuple-scale S [--tuple-seed N]]
 
 --knn K matches every point with its K nearest descriptors (helpers.py:19-43, find_knn_cpu(feat0, feat1, knn=K)) in
 place of the single mutual nearest neighbour: more putative correspondences for the solver, on the GPU as well.  Only
 pairs that are among each other's K nearest are kept unless --no-mutual is given.
+
+--tuple-scale S applies the matcher's tuple constraint (matcher.cc:223-283) to the correspondences, with or without
+--knn: a correspondence survives when it occurs in a random triple whose side lengths agree within the factor S in
+both clouds.  --tuple-seed N makes the draw reproducible; 0 (the default) seeds from the clock like the reference.
 
 --icp-plane refines with point-to-plane ICP instead, on the target normals the FPFH stage already computed
 (rows PCL leaves non-finite, below 3 neighbours, set to zero: they contribute nothing), optionally with a robust kernel.
@@ -55,7 +59,7 @@ def read_ply_xyz(path):
         return np.stack([data["x"], data["y"], data["z"]], axis=1).astype(np.float32)
 
 
-def run_batch(A, B, vox, K, icp_iterations, knn=0, mutual=True):
+def run_batch(A, B, vox, K, icp_iterations, knn=0, mutual=True, tuple_scale=0.0, tuple_seed=0):
     """K perturbed copies of the pair (A, B) through the batched stages, one call per stage."""
     rng = np.random.default_rng(555)
     srcs, dsts = [], []
@@ -78,9 +82,11 @@ def run_batch(A, B, vox, K, icp_iterations, knn=0, mutual=True):
         t1 = time.perf_counter()
         sp, dp = down[:K], down[K:]
         if knn:
-            corr = tp.correspondences_knn_batch(sp, dp, 2 * vox, 5 * vox, knn, mutual)
+            corr = tp.correspondences_knn_batch(sp, dp, 2 * vox, 5 * vox, knn, mutual, tuple_scale=tuple_scale,
+                                                tuple_seed=tuple_seed)
         else:
-            corr = tp.correspondences_batch(sp, dp, 2 * vox, 5 * vox)   # helpers.py:9-43 for every pair
+            corr = tp.correspondences_batch(sp, dp, 2 * vox, 5 * vox, tuple_scale=tuple_scale,
+                                            tuple_seed=tuple_seed)   # helpers.py:9-43 for every pair
         t2 = time.perf_counter()
         if min(map(len, corr)) < 3:
             sys.exit("pair %d has %d correspondences: nothing to register" % (int(np.argmin([len(c) for c in corr])),
@@ -122,6 +128,9 @@ def main():
     ap.add_argument("--knn", type=int, default=0, metavar="K",
                     help="match every point with its K nearest descriptors (1 .. 16) instead of the nearest one")
     ap.add_argument("--no-mutual", action="store_true", help="with --knn: keep one-directional matches too")
+    ap.add_argument("--tuple-scale", type=float, default=0.0, metavar="S",
+                    help="apply the matcher's tuple constraint with this factor (0: off, the reference uses 0.95)")
+    ap.add_argument("--tuple-seed", type=int, default=0, metavar="N", help="seed of the tuple test (0: the clock)")
     a = ap.parse_args()
     if a.batch > 0:
         if len(a.clouds) == 2:
@@ -129,7 +138,7 @@ def main():
         else:
             c5 = np.load(os.path.join(ROOT, "tests", "golden", "config5_clouds.npz"))
             A, B, a.voxel = c5["cloud_bin_0"].astype(np.float64), c5["cloud_bin_4"].astype(np.float64), float(c5["voxel_size"])
-        return run_batch(A, B, a.voxel, a.batch, a.icp_iterations, a.knn, not a.no_mutual)
+        return run_batch(A, B, a.voxel, a.batch, a.icp_iterations, a.knn, not a.no_mutual, a.tuple_scale, a.tuple_seed)
     t_ds = None
     if len(a.clouds) == 2:
         raw = [read_ply_xyz(c).astype(np.float64) for c in a.clouds]
@@ -148,9 +157,13 @@ def main():
     fb = est.computeFPFHFeatures(B, 2 * vox, 5 * vox)
     nb = est.getNormals()   # the target's normals: point-to-plane ICP refines on them
     if a.knn:
-        corr = [tuple(r) for r in tp.match_features_knn(fa, fb, a.knn, not a.no_mutual).tolist()]   # helpers.py:19-43
+        corr = tp.match_features_knn(fa, fb, a.knn, not a.no_mutual)   # helpers.py:19-43
+        if a.tuple_scale:
+            corr = tp.tuple_test_batch([A], [B], [corr], a.tuple_scale, a.tuple_seed)[0]
+        corr = [tuple(r) for r in corr.tolist()]
     else:
-        corr = tp.Matcher().calculateCorrespondences(A, B, fa, fb, False, True, False, 0)   # helpers.py:27-43
+        corr = tp.Matcher().calculateCorrespondences(A, B, fa, fb, False, True, bool(a.tuple_scale), a.tuple_scale,
+                                                     a.tuple_seed)   # helpers.py:27-43
     t1 = time.perf_counter()
     params = tp.RobustRegistrationSolver.Params(noise_bound=vox, cbar2=1.0, estimate_scaling=False,
                                                 rotation_gnc_factor=1.4, rotation_max_iterations=10000,

@@ -342,6 +342,28 @@ TEASER_HIP_API int32_t teaser_hip_match_features(teaser_hip_solver* h, const flo
 TEASER_HIP_API int32_t teaser_hip_tuple_test(teaser_hip_solver* h, const float* src_xyz, int32_t n_src,
                               const float* dst_xyz, int32_t n_dst, float tuple_scale, uint64_t seed,
                               int32_t* pairs /* in / out */, int64_t* n_pairs /* in / out */);
+/*   tuple_test_batch -> the same constraint for a BATCH of problems on the GPU (teaser_hip_features_tuple_test_batch,
+ *                     declared with the batched front-end below).  teaser_hip_tuple_test stays the host form and the
+ *                     specification: for every problem and every non-zero seed the batched call returns exactly
+ *                     what it returns.  The contract, per problem, with ncorr = n_pairs input pairs (src, dst), the
+ *                     float clouds, float s = tuple_scale and the uint64 seed; all counters are 64-bit:
+ *                       for i = 0 .. 100 ncorr - 1 and k = 0, 1, 2:
+ *                         z = seed + (3 i + k + 1) 0x9E3779B97F4A7C15            (wrapping: splitmix64's state after
+ *                         z = (z ^ z >> 30) 0xBF58476D1CE4E5B9                    3 i + k + 1 draws, so a trial is a
+ *                         z = (z ^ z >> 27) 0x94D049BB133111EB;  z ^= z >> 31     function of (seed, i) alone)
+ *                         r_k = z mod ncorr                                       (the exact 64-bit remainder)
+ *                       with (i_k, j_k) = input pair r_k, in float, every operation rounded and nothing fused:
+ *                         |a - b| = sqrt(dx dx + dy dy + dz dz), summed in that order, sqrt correctly rounded
+ *                         li0 = |p_i0 - p_i1|, li1 = |p_i1 - p_i2|, li2 = |p_i2 - p_i0| in the source cloud,
+ *                         lj0, lj1, lj2 likewise in the target cloud
+ *                       trial i passes when li s < lj and lj < li / s (a correctly rounded division) for all three
+ *                       sides.  Result: the input pairs that occur in at least one passing trial, sorted by
+ *                       (src, dst), unique.
+ *                     Edge cases as the host function: a problem with !(tuple_scale > 0) or ncorr = 0 is returned
+ *                     untouched (neither sorted nor made unique); input pairs may be unsorted and may repeat, and
+ *                     repeats count towards ncorr; an index outside its cloud is TEASER_HIP_ERR_BAD_ARG naming the
+ *                     problem, found on the host before anything is launched or written; seed = 0 means "from the
+ *                     clock": the call reads time(NULL) once and uses that value for every problem whose seed is 0. */
 
 /* DRS rotation certifier: teaser::DRSCertifier::certify(R, src, dst, theta) (teaser/src/certification.cc:39-190,
  * teaser/include/teaser/certification.h:53-239).  Parameters as DRSCertifier::Params (certification.h:71-104;
@@ -748,6 +770,21 @@ TEASER_HIP_API int32_t teaser_hip_features_correspondences_knn_batch(
     int32_t k, int32_t mutual, int32_t* const* pairs, const int64_t* pair_cap, int64_t* n_pairs,
     float* const* src_feat_out, float* const* dst_feat_out, float* const* src_normals_out,
     float* const* dst_normals_out);
+
+/* The tuple constraint for `batch` problems on the GPU: the contract is written out under "tuple_test_batch" in the
+ * "Correspondence front-end" comment above.  src_xyz[b]: n_src[b] x 3 floats, dst_xyz[b] likewise; tuple_scale and
+ * seed: one value per problem; pairs[b]: n_pairs[b] (src, dst) int32 pairs on entry, the survivors on return, and
+ * n_pairs[b] their count.  One upload of the packed points and pairs, one launch sequence for all problems, one copy
+ * of the keep flags back and one synchronisation, whatever the batch; compaction, sort and unique of the survivors run
+ * on the host.  Problems whose pairs exceed the part_bytes budget together are run in several waves inside the call,
+ * with the same results. */
+TEASER_HIP_API int32_t teaser_hip_features_tuple_test_batch(teaser_hip_features* features, int32_t batch,
+                                                            const float* const* src_xyz, const int32_t* n_src,
+                                                            const float* const* dst_xyz, const int32_t* n_dst,
+                                                            const float* tuple_scale /* per problem */,
+                                                            const uint64_t* seed /* per problem */,
+                                                            int32_t* const* pairs /* in / out */,
+                                                            int64_t* n_pairs /* in / out */);
 
 /* Page-locked host memory from the HIP runtime THIS library runs on.  teaser_hip_submit_batch(..., INPUT_HOST) moves
  * the points with one DMA copy per cloud, at PCIe speed only when the runtime knows the pages are locked.  A buffer

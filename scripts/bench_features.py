@@ -14,9 +14,13 @@ features' round trip through host memory per pair.
   knn           (with --knn these workloads only) match_features_knn_batch with k = 1, 4 and 16, mutual, on the FPFH
                 features of the config-5 pair alone and of the 64 perturbed pairs, beside match_features_batch (the 1-NN
                 path) on the same features in the same run: the baseline the k-NN times are divided by
+  tuple         (with --tuple this workload only) the tuple test of the 64 perturbed pairs' correspondences -- after the
+                1-NN matcher, and after k = 8 mutual matching -- by tuple_test_batch in one call against the per-pair
+                host loop it replaces (tp.tuple_test for every pair, same seeds, same machine), after asserting that
+                the two give the same pairs; also written to profiles/features/tuple_test.json
 The object also records the board's name, the ROCm version and the commit (None outside a git checkout).
 Wall-clock medians over --reps synchronous calls after --warmup calls; ms_min / ms_max give the spread.  Usage:
-    python scripts/bench_features.py [--reps 20] [--warmup 3] [--knn]"""
+    python scripts/bench_features.py [--reps 20] [--warmup 3] [--knn | --tuple]"""
 import argparse
 import ctypes
 import importlib
@@ -91,11 +95,33 @@ def knn_workloads(res, A, B, src, dst, rn, rf, reps, warmup):
         res["knn"][name] = row
 
 
+def tuple_workloads(res, src, dst, rn, rf, reps, warmup, scale=0.9):
+    """res["tuple"]: per matcher the batched call's time, the per-pair host loop's, their ratio and the counts."""
+    res["tuple"] = dict(tuple_scale=scale, seeds="1 .. 64")
+    seeds = np.arange(1, len(src) + 1, dtype=np.uint64)
+    for name, corr in (("after_1nn", tp.correspondences_batch(src, dst, rn, rf)),
+                       ("after_knn_k8_mutual", tp.correspondences_knn_batch(src, dst, rn, rf, 8, True))):
+        def host_loop():
+            return [tp.tuple_test(src[k], dst[k], corr[k], scale, int(seeds[k])) for k in range(len(src))]
+
+        def batched():
+            return tp.tuple_test_batch(src, dst, corr, scale, seeds)
+        want, got = host_loop(), batched()
+        assert all([tuple(r) for r in g.tolist()] == w for g, w in zip(got, want)), name
+        row = dict(tuple_test_batch=timed(batched, reps, warmup), host_loop=timed(host_loop, max(reps // 4, 3), 1),
+                   pairs_in=sum(len(c) for c in corr), pairs_in_max=max(len(c) for c in corr),
+                   pairs_out=sum(len(g) for g in got), trials=100 * sum(len(c) for c in corr))
+        row["host_loop_over_tuple_test_batch"] = row["host_loop"]["ms"] / row["tuple_test_batch"]["ms"]
+        row["host_loop_ns_per_trial"] = 1e6 * row["host_loop"]["ms"] / row["trials"]
+        res["tuple"][name] = row
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--knn", action="store_true", help="the k-NN matching workloads only")
+    ap.add_argument("--tuple", action="store_true", help="the tuple-test workload only")
     a = ap.parse_args()
     if tp.device_count() < 1:
         sys.exit("bench_features.py needs an MI355X")
@@ -121,6 +147,16 @@ def main():
     if a.knn:
         res["workload"] = "k-NN matching (k = 1, 4, 16, mutual) of config-5 FPFH features (%d / %d points)" % (len(A), len(B))
         knn_workloads(res, A, B, src, dst, rn, rf, a.reps, a.warmup)
+        print(json.dumps(res))
+        return
+    if a.tuple:
+        res["workload"] = ("tuple test (scale 0.9) of the correspondences of 64 config-5 pairs (%d / %d points): "
+                           "tuple_test_batch vs the per-pair host loop" % (len(A), len(B)))
+        tuple_workloads(res, src, dst, rn, rf, a.reps, a.warmup)
+        out = os.path.join(ROOT, "profiles", "features", "tuple_test.json")
+        with open(out, "w") as f:
+            json.dump(res, f, indent=1)
+            f.write("\n")
         print(json.dumps(res))
         return
     one = timed(lambda: single(A, B), a.reps, a.warmup)

@@ -140,6 +140,7 @@ EXPORTED_SYMBOLS = [
     "teaser_hip_features_set_budgets", "teaser_hip_features_fpfh_batch", "teaser_hip_features_match_batch",
     "teaser_hip_features_correspondences_batch", "teaser_hip_features_knn_batch",
     "teaser_hip_features_match_knn_batch", "teaser_hip_features_correspondences_knn_batch",
+    "teaser_hip_features_tuple_test_batch",
 ]
 
 
@@ -871,15 +872,16 @@ class Matcher:
                                       use_absolute_scale=True, use_crosscheck=True, use_tuple_test=True,
                                       tuple_scale=0.0, tuple_seed=0):
         """calculateCorrespondences for lists of clouds / feature arrays in one launch sequence
-        (features.match_features_batch): per pair the list of (src, dst) tuples one call per pair returns."""
+        (features.match_features_batch, and features.tuple_test_batch where the tuple test is asked for): per pair the
+        list of (src, dst) tuples one call per pair returns."""
         from . import features
         pairs = features.match_features_batch(source_features, target_features, use_crosscheck,
                                               device=self._device)
         if use_tuple_test and tuple_scale != 0:
             features._same_length(source_points, pairs, "source_points", "source_features")
             features._same_length(target_points, pairs, "target_points", "target_features")
-            return [tuple_test(source_points[k], target_points[k], pairs[k], tuple_scale, tuple_seed)
-                    for k in range(len(pairs))]
+            pairs = features.tuple_test_batch(source_points, target_points, pairs, tuple_scale, tuple_seed,
+                                              device=self._device)
         return [[tuple(int(v) for v in row) for row in p] for p in pairs]
 
 
@@ -1078,7 +1080,7 @@ from .icp import (CauchyLoss, GMLoss, HuberLoss, ICPConvergenceCriteria, L2Loss,
 from .voxel import voxel_down_sample, voxel_down_sample_batch  # noqa: E402
 from .features import (compute_fpfh_batch, correspondences_batch, match_features_batch,  # noqa: E402
                        knn_features, knn_features_batch, match_features_knn, match_features_knn_batch,
-                       correspondences_knn, correspondences_knn_batch)
+                       correspondences_knn, correspondences_knn_batch, tuple_test_batch)
 
 __all__ = ["batched", "FPFHEstimation", "Matcher", "MultiDeviceSolver", "RobustRegistrationSolver", "RegistrationSolution", "RotationEstimationAlgorithm",
            "InlierSelectionMode", "InlierGraphFormulation", "TeaserHipError", "synth_problem",
@@ -1087,7 +1089,7 @@ __all__ = ["batched", "FPFHEstimation", "Matcher", "MultiDeviceSolver", "RobustR
            "registration_icp_batch", "voxel_down_sample", "voxel_down_sample_batch",
            "compute_fpfh_batch", "match_features_batch", "correspondences_batch",
            "knn_features", "knn_features_batch", "match_features_knn", "match_features_knn_batch",
-           "correspondences_knn", "correspondences_knn_batch",
+           "correspondences_knn", "correspondences_knn_batch", "tuple_test_batch",
            "TransformationEstimationPointToPlane", "L2Loss", "HuberLoss", "CauchyLoss", "GMLoss", "TukeyLoss",
            "TransformationEstimationForGeneralizedICP", "registration_generalized_icp", "estimate_covariances",
            "estimate_covariances_batch", "covariances_from_normals"]

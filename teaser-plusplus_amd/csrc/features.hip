@@ -23,6 +23,7 @@
 // caller's own (pageable) arrays: those copies are additional.
 #include <math.h>
 #include <string.h>
+#include <time.h>
 
 #include <algorithm>
 #include <climits>
@@ -46,8 +47,8 @@ constexpr int64_t kFeatPartBudgetBytes = (int64_t)1 << 30;
 
 enum { B_DESC, B_BLK, B_PT_CLOUD, B_PTS, B_COUNTS, B_OFFSETS, B_CURSOR, B_META, B_BASE, B_LIST, B_LIST2, B_NORMALS,
        B_SPFH, B_FEAT, B_SEARCH, B_SBLK, B_PART_D, B_PART_I, B_NN, B_MFEAT, B_KNN_I, B_KNN_D, B_KNN_KEEP,
-       B_COUNT_OF_BUFS };
-enum { H_PTS, H_META, H_NN, H_KNN_I, H_KNN_D, H_KNN_KEEP, H_COUNT_OF_BUFS };
+       B_TUPLE_DESC, B_TUPLE_BLK, B_TUPLE_PAIRS, B_TUPLE_KEEP, B_COUNT_OF_BUFS };
+enum { H_PTS, H_META, H_NN, H_KNN_I, H_KNN_D, H_KNN_KEEP, H_TUPLE_PAIRS, H_TUPLE_KEEP, H_COUNT_OF_BUFS };
 
 struct Wave {
   int c0, c1;  // clouds (or pairs, or k-NN searches) [c0, c1)
@@ -71,6 +72,8 @@ struct teaser_hip_features : HandleBase {
   std::vector<int32_t> blk_cloud, pt_cloud, blk_search;
   std::vector<int64_t> base;
   std::vector<FeatSearchDesc> search;
+  std::vector<FeatTupleDesc> tuple;
+  std::vector<int32_t> blk_tuple;
   ~teaser_hip_features() {
     for (DevBuf& b : buf) b.release();
     for (HostBuf& b : host) b.release();
@@ -815,6 +818,146 @@ int32_t teaser_hip_features_correspondences_knn_batch(
   if (rc != TEASER_HIP_OK) return rc;
   return run_match_knn(h, batch, h->buf[B_FEAT].as<float>(), src_row.data(), dst_row.data(), n_src, n_dst, 33, k,
                        mutual != 0, pairs, pair_cap, n_pairs);
+}
+
+int32_t teaser_hip_features_tuple_test_batch(teaser_hip_features* h, int32_t batch, const float* const* src_xyz,
+                                             const int32_t* n_src, const float* const* dst_xyz, const int32_t* n_dst,
+                                             const float* tuple_scale, const uint64_t* seed, int32_t* const* pairs,
+                                             int64_t* n_pairs) {
+  if (!h) return TEASER_HIP_ERR_BAD_ARG;
+  h->err.clear();
+  if (batch < 0) return fail(h, TEASER_HIP_ERR_BAD_ARG, "batch must be >= 0");
+  if (batch == 0) return TEASER_HIP_OK;
+  if (!n_src || !n_dst) return fail(h, TEASER_HIP_ERR_BAD_ARG, "n_src / n_dst must not be NULL");
+  if (!tuple_scale) return fail(h, TEASER_HIP_ERR_BAD_ARG, "tuple_scale must not be NULL");
+  if (!seed) return fail(h, TEASER_HIP_ERR_BAD_ARG, "seed must not be NULL");
+  if (!n_pairs) return fail(h, TEASER_HIP_ERR_BAD_ARG, "n_pairs must not be NULL");
+
+  // ---- everything that can be refused is refused here, before anything is launched or written ----
+  // The problems the test applies to (teaser_hip_tuple_test returns the others untouched), cut into waves whose pairs
+  // (8 bytes each) fit the partial-result budget; a wave always holds at least one problem.
+  const int64_t pair_budget = h->part_budget / 8;
+  h->tuple.clear();
+  std::vector<int> problem_of;
+  std::vector<Wave> waves;            // in units of active problems
+  std::vector<int64_t> wave_pair0;    // first pair of each wave in the host's packed arrays
+  int64_t n_pts = 0, blocks = 0, pair_acc = 0, pair_cap = 0, pair_total = 0;
+  int a0 = 0;
+  bool clock_seed = false;
+  for (int b = 0; b < batch; ++b) {
+    if (n_src[b] < 0 || n_dst[b] < 0) return fail(h, TEASER_HIP_ERR_BAD_ARG, "n_src / n_dst must be >= 0" + at(b));
+    if (n_pairs[b] < 0) return fail(h, TEASER_HIP_ERR_BAD_ARG, "n_pairs must be >= 0" + at(b));
+    if (n_pairs[b] == 0) continue;
+    if (!pairs || !pairs[b]) return fail(h, TEASER_HIP_ERR_BAD_ARG, "pairs is NULL" + at(b));
+    if (!src_xyz || !src_xyz[b]) return fail(h, TEASER_HIP_ERR_BAD_ARG, "src_xyz is NULL" + at(b));
+    if (!dst_xyz || !dst_xyz[b]) return fail(h, TEASER_HIP_ERR_BAD_ARG, "dst_xyz is NULL" + at(b));
+    if (!(tuple_scale[b] > 0.0f)) continue;  // matcher.cc:223: skipped for tuple_scale == 0
+    const int64_t ncorr = n_pairs[b];
+    for (int64_t k = 0; k < ncorr; ++k)
+      if (pairs[b][2 * k] < 0 || pairs[b][2 * k] >= n_src[b] || pairs[b][2 * k + 1] < 0 ||
+          pairs[b][2 * k + 1] >= n_dst[b])
+        return fail(h, TEASER_HIP_ERR_BAD_ARG, "a pair's index lies outside its cloud" + at(b));
+    const int a = (int)problem_of.size();
+    if (a > a0 && pair_acc + ncorr > pair_budget) {
+      waves.push_back(Wave{a0, a});
+      a0 = a;
+      pair_acc = 0;
+    }
+    if (a == a0) wave_pair0.push_back(pair_total);
+    const int64_t nb = feat_tuple_blocks(ncorr);
+    h->tuple.push_back(FeatTupleDesc{pair_acc, ncorr, n_pts, n_pts + n_src[b], seed[b], tuple_scale[b], (int32_t)blocks,
+                                     (int32_t)nb, 0});
+    blocks += nb;
+    if (blocks >= INT32_MAX) return fail(h, TEASER_HIP_ERR_UNSUPPORTED, "too many pairs in one call" + at(b));
+    n_pts += (int64_t)n_src[b] + n_dst[b];
+    pair_acc += ncorr;
+    pair_total += ncorr;
+    pair_cap = std::max(pair_cap, pair_acc);
+    clock_seed |= seed[b] == 0;
+    problem_of.push_back(b);
+  }
+  const int na = (int)problem_of.size();
+  if (na == 0) return TEASER_HIP_OK;
+  waves.push_back(Wave{a0, na});
+  if (clock_seed) {  // "from the clock": one reading for the call
+    const uint64_t now = (uint64_t)time(nullptr);
+    for (FeatTupleDesc& d : h->tuple)
+      if (d.seed == 0) d.seed = now;
+  }
+  h->blk_tuple.resize((size_t)blocks);
+  for (int a = 0; a < na; ++a)
+    std::fill_n(h->blk_tuple.begin() + h->tuple[(size_t)a].blk_off, h->tuple[(size_t)a].n_blk, a);
+
+  // ---- one upload: descriptors, block map, the packed points (source then target of every problem) and pairs ----
+  hipStream_t s = h->stream;
+  DevBuf* B = h->buf;
+  FCHK(h, hipSetDevice(h->device), "hipSetDevice");
+  FENSURE(h, B[B_TUPLE_DESC], sizeof(FeatTupleDesc) * (size_t)na);
+  FENSURE(h, B[B_TUPLE_BLK], 4 * (size_t)blocks);
+  FENSURE(h, B[B_PTS], 12 * (size_t)std::max<int64_t>(n_pts, 1));
+  FENSURE(h, B[B_TUPLE_PAIRS], 8 * (size_t)pair_cap);
+  FENSURE(h, B[B_TUPLE_KEEP], (size_t)pair_cap);
+  FENSURE(h, h->host[H_PTS], 12 * (size_t)std::max<int64_t>(n_pts, 1));
+  FENSURE(h, h->host[H_TUPLE_PAIRS], 8 * (size_t)pair_total);
+  FENSURE(h, h->host[H_TUPLE_KEEP], (size_t)pair_total);
+  {
+    int32_t* hp = h->host[H_TUPLE_PAIRS].as<int32_t>();
+    for (int a = 0; a < na; ++a) {
+      const int b = problem_of[(size_t)a];
+      const FeatTupleDesc& d = h->tuple[(size_t)a];
+      float* pts = h->host[H_PTS].as<float>();
+      if (n_src[b] > 0) memcpy(pts + 3 * d.src_off, src_xyz[b], 12 * (size_t)n_src[b]);
+      if (n_dst[b] > 0) memcpy(pts + 3 * d.dst_off, dst_xyz[b], 12 * (size_t)n_dst[b]);
+      memcpy(hp, pairs[b], 8 * (size_t)d.ncorr);
+      hp += 2 * d.ncorr;
+    }
+  }
+  FCHK(h, hipMemcpyAsync(B[B_TUPLE_DESC].p, h->tuple.data(), sizeof(FeatTupleDesc) * (size_t)na, hipMemcpyHostToDevice,
+                         s),
+       "hipMemcpyAsync (tuple descriptors)");
+  FCHK(h, hipMemcpyAsync(B[B_TUPLE_BLK].p, h->blk_tuple.data(), 4 * (size_t)blocks, hipMemcpyHostToDevice, s),
+       "hipMemcpyAsync (tuple block map)");
+  if (n_pts > 0)
+    FCHK(h, hipMemcpyAsync(B[B_PTS].p, h->host[H_PTS].p, 12 * (size_t)n_pts, hipMemcpyHostToDevice, s),
+         "hipMemcpyAsync (points)");
+  // ---- per wave (one, normally), stream-ordered: its pairs, the launch, its keep flags back ----
+  for (size_t w = 0; w < waves.size(); ++w) {
+    const FeatTupleDesc& first = h->tuple[(size_t)waves[w].c0];
+    const FeatTupleDesc& last = h->tuple[(size_t)waves[w].c1 - 1];
+    const int64_t n_wave = last.pair_off + last.ncorr;
+    FCHK(h, hipMemcpyAsync(B[B_TUPLE_PAIRS].p, h->host[H_TUPLE_PAIRS].as<int32_t>() + 2 * wave_pair0[w],
+                           8 * (size_t)n_wave, hipMemcpyHostToDevice, s),
+         "hipMemcpyAsync (pairs)");
+    FCHK(h, hipMemsetAsync(B[B_TUPLE_KEEP].p, 0, (size_t)n_wave, s), "hipMemsetAsync (keep flags)");
+    launch_feat_tuple_batch(s, B[B_TUPLE_DESC].as<FeatTupleDesc>(), B[B_TUPLE_BLK].as<int32_t>(), first.blk_off,
+                            last.blk_off + last.n_blk - first.blk_off, B[B_PTS].as<float>(),
+                            B[B_TUPLE_PAIRS].as<int32_t>(), B[B_TUPLE_KEEP].as<uint8_t>());
+    FCHK(h, hipGetLastError(), "front-end kernel launch (tuple test)");
+    FCHK(h, hipMemcpyAsync(h->host[H_TUPLE_KEEP].as<uint8_t>() + wave_pair0[w], B[B_TUPLE_KEEP].p, (size_t)n_wave,
+                           hipMemcpyDeviceToHost, s),
+         "hipMemcpyAsync (keep flags)");
+  }
+  FCHK(h, hipStreamSynchronize(s), "hipStreamSynchronize (results)");
+
+  // ---- the survivors of every problem, sorted and unique (matcher.cc:299-300) ----
+  const uint8_t* keep = h->host[H_TUPLE_KEEP].as<uint8_t>();
+  std::vector<std::pair<int32_t, int32_t>> kept;
+  for (int a = 0; a < na; ++a) {
+    const int b = problem_of[(size_t)a];
+    const int64_t ncorr = h->tuple[(size_t)a].ncorr;
+    kept.clear();
+    for (int64_t k = 0; k < ncorr; ++k)
+      if (keep[k]) kept.emplace_back(pairs[b][2 * k], pairs[b][2 * k + 1]);
+    keep += ncorr;
+    std::sort(kept.begin(), kept.end());
+    kept.erase(std::unique(kept.begin(), kept.end()), kept.end());
+    for (size_t k = 0; k < kept.size(); ++k) {
+      pairs[b][2 * k] = kept[k].first;
+      pairs[b][2 * k + 1] = kept[k].second;
+    }
+    n_pairs[b] = (int64_t)kept.size();
+  }
+  return TEASER_HIP_OK;
 }
 
 }  // extern "C"

@@ -31,6 +31,18 @@ struct FeatSearchDesc {
   int32_t qblocks;  // query blocks of 64 rows; blocks are (chunk, qblock) = (l / qblocks, l % qblocks)
 };
 
+// One problem of a batched tuple test (include/teaser_hip.h, "tuple_test_batch"): its ncorr pairs occupy
+// [pair_off, pair_off + ncorr) of the wave's packed pair array (two int32 each) and keep flags, its clouds start at
+// points src_off / dst_off of the packed point array, its trials are spread over blocks [blk_off, blk_off + n_blk) of
+// the block -> problem map.
+struct FeatTupleDesc {
+  int64_t pair_off, ncorr, src_off, dst_off;
+  uint64_t seed;  // never 0 here: the host has replaced "from the clock" by the call's clock value
+  float scale;
+  int32_t blk_off, n_blk;
+  int32_t pad;
+};
+
 int feat_radius_chunk();  // data points per radius block (kFeatChunk)
 
 // counts[which][g] of every point of the clouds whose blocks are [blk_base, blk_base + n_blk) (counts zeroed first)
@@ -71,6 +83,13 @@ void launch_feat_knn_batch(hipStream_t s, const FeatSearchDesc* d_search, const 
 // source row i is among the k nearest of its neighbour F[i][slot]; max_entries = the largest nq x k of a forward search
 void launch_feat_knn_mutual_batch(hipStream_t s, const FeatSearchDesc* d_search, int n_pairs, int64_t max_entries,
                                   int k, const int32_t* d_idx, uint8_t* d_keep);
+
+// The tuple constraint.  feat_tuple_blocks: blocks of 256 lanes a problem of ncorr pairs gets (one trial per lane, the
+// remaining trials by a grid stride inside the problem).  The launch: the problems whose blocks are [blk_base,
+// blk_base + n_blk); d_keep[pair] (zeroed by the caller) becomes 1 for every pair of a passing trial.
+int64_t feat_tuple_blocks(int64_t ncorr);
+void launch_feat_tuple_batch(hipStream_t s, const FeatTupleDesc* d_desc, const int32_t* d_blk_problem, int blk_base,
+                             int n_blk, const float* d_pts, const int32_t* d_pairs, uint8_t* d_keep);
 
 // Index bookkeeping of Matcher::advancedMatching (reference matcher.cc:155-233, 281-296) after the two searches:
 // i = the larger cloud, j = the smaller one, j_to_i[j] = nearest i of j, i_nn[i] = nearest j of i (both valid

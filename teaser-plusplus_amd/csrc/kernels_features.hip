@@ -849,6 +849,59 @@ __global__ __launch_bounds__(256) void feat_knn_mutual_batch_kernel(const FeatSe
   keep[f.nn_off + e] = found ? 1 : 0;
 }
 
+// The matcher's tuple constraint (include/teaser_hip.h, "tuple_test_batch"): trial i of a problem is a function of
+// (seed, i) alone -- splitmix64's state after m draws is seed + m gamma -- so one lane takes one trial and strides over
+// the problem's trials with the problem's own blocks.  The arithmetic is teaser_hip_tuple_test's, operation by
+// operation: the exact 64-bit remainder, float differences, squares summed in x, y, z order (no contraction: the
+// Makefile's -ffp-contract=off), the correctly rounded sqrt and division hipcc emits for the plain operators.  A
+// passing trial raises the keep flag of its three correspondences; every writer writes 1, so plain byte stores do,
+// and a flag that is already up is not written again.  The six points and three pairs of a trial are gathered
+// straight from global memory: a problem's clouds and pairs are a few hundred KiB, which the L2 holds.
+constexpr int kTupleMaxBlocks = 2048;  // blocks of one problem: 8 per CU, the rest of its trials by the grid stride
+__device__ __forceinline__ uint64_t feat_tuple_draw(uint64_t seed, uint64_t m) {
+  uint64_t z = seed + m * 0x9E3779B97F4A7C15ull;
+  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+  return z ^ (z >> 31);
+}
+__device__ __forceinline__ float feat_tuple_dist(const float* __restrict__ p, int a, int b) {
+  const float dx = p[3 * (int64_t)a] - p[3 * (int64_t)b], dy = p[3 * (int64_t)a + 1] - p[3 * (int64_t)b + 1],
+              dz = p[3 * (int64_t)a + 2] - p[3 * (int64_t)b + 2];
+  return sqrtf(dx * dx + dy * dy + dz * dz);
+}
+__global__ __launch_bounds__(256) void feat_tuple_batch_kernel(const FeatTupleDesc* __restrict__ desc,
+                                                               const int32_t* __restrict__ blk_problem, int blk_base,
+                                                               const float* __restrict__ pts,
+                                                               const int2* __restrict__ pairs,
+                                                               uint8_t* __restrict__ keep) {
+  const int blk = blk_base + (int)blockIdx.x;
+  const FeatTupleDesc d = desc[blk_problem[blk]];
+  const uint64_t n = (uint64_t)d.ncorr;
+  const int64_t trials = 100 * d.ncorr;  // matcher.cc:231
+  const int64_t stride = (int64_t)d.n_blk * 256;
+  const float* __restrict__ src = pts + 3 * d.src_off;
+  const float* __restrict__ dst = pts + 3 * d.dst_off;
+  const int2* __restrict__ pr = pairs + d.pair_off;
+  uint8_t* __restrict__ flag = keep + d.pair_off;
+  const float scale = d.scale;
+  for (int64_t i = (int64_t)(blk - d.blk_off) * 256 + threadIdx.x; i < trials; i += stride) {
+    const uint64_t m = 3 * (uint64_t)i;
+    const uint64_t r0 = feat_tuple_draw(d.seed, m + 1) % n, r1 = feat_tuple_draw(d.seed, m + 2) % n,
+                   r2 = feat_tuple_draw(d.seed, m + 3) % n;
+    const int2 c0 = pr[r0], c1 = pr[r1], c2 = pr[r2];  // (.x, .y) = (source index, target index)
+    const float li0 = feat_tuple_dist(src, c0.x, c1.x), li1 = feat_tuple_dist(src, c1.x, c2.x),
+                li2 = feat_tuple_dist(src, c2.x, c0.x);
+    const float lj0 = feat_tuple_dist(dst, c0.y, c1.y), lj1 = feat_tuple_dist(dst, c1.y, c2.y),
+                lj2 = feat_tuple_dist(dst, c2.y, c0.y);
+    if ((li0 * scale < lj0) && (lj0 < li0 / scale) && (li1 * scale < lj1) && (lj1 < li1 / scale) &&
+        (li2 * scale < lj2) && (lj2 < li2 / scale)) {  // matcher.cc:267-268
+      if (!flag[r0]) flag[r0] = 1;
+      if (!flag[r1]) flag[r1] = 1;
+      if (!flag[r2]) flag[r2] = 1;
+    }
+  }
+}
+
 }  // namespace
 
 // ---- launchers and the sizes the host plans with ------------------------------------------------------------------
@@ -964,6 +1017,17 @@ void launch_feat_knn_mutual_batch(hipStream_t s, const FeatSearchDesc* d_search,
     hipLaunchKernelGGL(feat_knn_mutual_batch_kernel, dim3((unsigned)((max_entries + 255) / 256),
                                                           std::min(65535, n_pairs - p0)),
                        dim3(256), 0, s, d_search, p0, k, d_idx, d_keep);
+}
+
+int64_t feat_tuple_blocks(int64_t ncorr) {
+  const int64_t trials = 100 * ncorr;
+  return std::max<int64_t>(1, std::min<int64_t>((trials + 255) / 256, kTupleMaxBlocks));
+}
+void launch_feat_tuple_batch(hipStream_t s, const FeatTupleDesc* d_desc, const int32_t* d_blk_problem, int blk_base,
+                             int n_blk, const float* d_pts, const int32_t* d_pairs, uint8_t* d_keep) {
+  if (n_blk <= 0) return;
+  hipLaunchKernelGGL(feat_tuple_batch_kernel, dim3(n_blk), dim3(256), 0, s, d_desc, d_blk_problem, blk_base, d_pts,
+                     reinterpret_cast<const int2*>(d_pairs), d_keep);
 }
 
 }  // namespace thip

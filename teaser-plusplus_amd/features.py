@@ -5,6 +5,8 @@ correspondences out, the features staying on the device in between).  The arithm
 in include/teaser_hip.h ("Batched correspondence front-end").  ``knn_features_batch``, ``match_features_knn_batch`` and
 ``correspondences_knn_batch`` (and their single-problem forms) match every point with its k nearest descriptors, as
 the reference's tutorial does with a host KD-tree; their semantics are in the same header ("k nearest").
+``tuple_test_batch`` runs the matcher's tuple constraint for many problems in one launch sequence, with the results of
+the host routine ``tuple_test`` (same header, "tuple_test_batch"); the correspondence calls take ``tuple_scale``.
 
 One library handle is kept per device between calls; calls from several threads are safe -- each handle has a lock,
 so calls for one device run one after the other.  device=-1 means the calling thread's current HIP device at the
@@ -17,6 +19,7 @@ from ._handles import Handle, HandleCache, _cloud
 
 _vp, _ip, _fp, _dp, _i64p = (C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_float), C.POINTER(C.c_double),
                              C.POINTER(C.c_int64))
+_u64p = C.POINTER(C.c_uint64)
 
 
 def declare(L):
@@ -40,12 +43,15 @@ def declare(L):
     L.teaser_hip_features_correspondences_knn_batch.argtypes = [
         _vp, C.c_int32, C.POINTER(_fp), _ip, C.POINTER(_fp), _ip, _dp, _dp, C.c_int32, C.c_int32, C.POINTER(_ip), _i64p,
         _i64p, C.POINTER(_fp), C.POINTER(_fp), C.POINTER(_fp), C.POINTER(_fp)]
+    L.teaser_hip_features_tuple_test_batch.argtypes = [_vp, C.c_int32, C.POINTER(_fp), _ip, C.POINTER(_fp), _ip, _fp,
+                                                       _u64p, C.POINTER(_ip), _i64p]
 
 
 class _Handle(Handle):
     def _set_budget(self, list_bytes=None, part_bytes=None):
         """Test hook: the budgets of one wave in bytes (None or <= 0: the default) -- list_bytes for the neighbour lists
-        of a wave of clouds, part_bytes for the partial nearest-neighbour results of a wave of pairs.  Small values
+        of a wave of clouds, part_bytes for the partial nearest-neighbour results of a wave of pairs (and the pairs of
+        a wave of tuple-test problems).  Small values
         split a call into many waves; results do not depend on them."""
         with self.lock:
             self._lib.teaser_hip_features_set_budgets(self.h, int(list_bytes or 0), int(part_bytes or 0))
@@ -61,14 +67,18 @@ def _clouds(clouds, what="clouds"):
     return [_cloud(c, "%s[%d]" % (what, k), np.float32) for k, c in enumerate(clouds)]
 
 
-def _radii(r, batch, what):
-    """One float64 per problem from a scalar or a sequence of `batch` values."""
-    a = np.asarray(r, dtype=np.float64)
+def _per_problem(v, batch, what, dtype):
+    """One `dtype` value per problem from a scalar or a sequence of `batch` values."""
+    a = np.asarray(v, dtype=dtype)
     if a.ndim == 0:
-        return np.full(max(batch, 1), float(a))
+        return np.full(max(batch, 1), a)
     if a.shape != (batch,):
         raise ValueError("%s must be a scalar or one value per problem (%d), got shape %s" % (what, batch, a.shape))
-    return np.ascontiguousarray(a) if batch else np.zeros(1)
+    return np.ascontiguousarray(a) if batch else np.zeros(1, dtype=dtype)
+
+
+def _radii(r, batch, what):
+    return _per_problem(r, batch, what, np.float64)
 
 
 def _features(feats, what):
@@ -177,7 +187,8 @@ def correspondences_batch(src_clouds, dst_clouds, normal_radius, fpfh_radius, us
     the mutual nearest-neighbour matching, with the features staying on the device in between.  Returns the list of
     k_b x 2 int32 arrays of (src, dst) pairs; with return_features / return_normals a tuple
     (pairs, [src_feats, dst_feats], [src_normals, dst_normals]) holding the parts asked for.  tuple_scale != 0 applies
-    the tuple test per pair (host routine, seeded by tuple_seed)."""
+    the tuple test to all pairs in one more launch sequence (tuple_test_batch, seeded by tuple_seed; one value or one
+    per pair each)."""
     _same_length(src_clouds, dst_clouds, "src_clouds", "dst_clouds")
     sp, dp = _clouds(src_clouds, "src_clouds"), _clouds(dst_clouds, "dst_clouds")
     b = len(sp)
@@ -196,10 +207,8 @@ def correspondences_batch(src_clouds, dst_clouds, normal_radius, fpfh_radius, us
            None if feats is None else _ptrs(feats[0], _fp), None if feats is None else _ptrs(feats[1], _fp),
            None if nrms is None else _ptrs(nrms[0], _fp), None if nrms is None else _ptrs(nrms[1], _fp))
     pairs = [bufs[k][:int(cnt[k])].copy() for k in range(b)]
-    if tuple_scale:
-        from . import tuple_test
-        pairs = [np.asarray(tuple_test(sp[k], dp[k], pairs[k], tuple_scale, tuple_seed), dtype=np.int32).reshape(-1, 2)
-                 for k in range(b)]
+    if np.any(tuple_scale):
+        pairs = tuple_test_batch(sp, dp, pairs, tuple_scale, tuple_seed, device)
     parts = [pairs] + ([feats] if return_features else []) + ([nrms] if return_normals else [])
     return parts[0] if len(parts) == 1 else tuple(parts)
 
@@ -240,10 +249,11 @@ def match_features_knn_batch(src_feats, dst_feats, k, mutual=True, device=-1):
 
 
 def correspondences_knn_batch(src_clouds, dst_clouds, normal_radius, fpfh_radius, k, mutual=True,
-                              return_features=False, return_normals=False, device=-1):
+                              return_features=False, return_normals=False, device=-1, tuple_scale=0.0, tuple_seed=0):
     """Clouds in, k-nearest-neighbour correspondences out, for many pairs in one launch sequence: compute_fpfh_batch
     followed by match_features_knn_batch with the features staying on the device.  Returns as correspondences_batch
-    does: the list of pair arrays, or a tuple with [src_feats, dst_feats] / [src_normals, dst_normals] where asked."""
+    does: the list of pair arrays, or a tuple with [src_feats, dst_feats] / [src_normals, dst_normals] where asked.
+    tuple_scale != 0 then applies the tuple test to all pairs (tuple_test_batch, seeded by tuple_seed)."""
     k = _knn_k(k)
     _same_length(src_clouds, dst_clouds, "src_clouds", "dst_clouds")
     sp, dp = _clouds(src_clouds, "src_clouds"), _clouds(dst_clouds, "dst_clouds")
@@ -263,8 +273,38 @@ def correspondences_knn_batch(src_clouds, dst_clouds, normal_radius, fpfh_radius
            None if feats is None else _ptrs(feats[0], _fp), None if feats is None else _ptrs(feats[1], _fp),
            None if nrms is None else _ptrs(nrms[0], _fp), None if nrms is None else _ptrs(nrms[1], _fp))
     pairs = [bufs[p][:int(cnt[p])].copy() for p in range(b)]
+    if np.any(tuple_scale):
+        pairs = tuple_test_batch(sp, dp, pairs, tuple_scale, tuple_seed, device)
     parts = [pairs] + ([feats] if return_features else []) + ([nrms] if return_normals else [])
     return parts[0] if len(parts) == 1 else tuple(parts)
+
+
+def tuple_test_batch(src_clouds, dst_clouds, pairs, tuple_scale, seed=0, device=-1):
+    """The tuple constraint of Matcher::advancedMatching (matcher.cc:223-283) for many problems in one launch sequence:
+    per problem the k_b x 2 int32 array of the surviving (src, dst) pairs, sorted and unique -- for a non-zero seed
+    exactly what the host routine tuple_test returns for that problem.  pairs: per problem an m_b x 2 array of indices
+    into its clouds (unsorted and repeated pairs allowed); tuple_scale and seed: one value for all problems or one per
+    problem.  A problem with tuple_scale <= 0 or without pairs comes back untouched; seed 0 seeds from the clock, read
+    once per call."""
+    _same_length(src_clouds, dst_clouds, "src_clouds", "dst_clouds")
+    _same_length(src_clouds, pairs, "src_clouds", "pairs")
+    sp, dp = _clouds(src_clouds, "src_clouds"), _clouds(dst_clouds, "dst_clouds")
+    b = len(sp)
+    bufs = []
+    for k, p in enumerate(pairs):
+        a = np.array(p, dtype=np.int32)  # (a copy: the call works in place)
+        if a.size and (a.ndim != 2 or a.shape[1] != 2):
+            raise ValueError("pairs[%d] must be an m x 2 array, got shape %s" % (k, a.shape))
+        bufs.append(np.ascontiguousarray(a.reshape(-1, 2)))
+    scale = _per_problem(tuple_scale, b, "tuple_scale", np.float32)
+    seeds = _per_problem(seed, b, "seed", np.uint64)
+    n_src, n_dst = _counts(sp), _counts(dp)
+    cnt = np.array([a.shape[0] for a in bufs] or [0], dtype=np.int64)
+    h = _handle(device)
+    h.call(h._lib.teaser_hip_features_tuple_test_batch, b, _ptrs(sp, _fp), n_src.ctypes.data_as(_ip), _ptrs(dp, _fp),
+           n_dst.ctypes.data_as(_ip), scale.ctypes.data_as(_fp), seeds.ctypes.data_as(_u64p), _ptrs(bufs, _ip),
+           cnt.ctypes.data_as(_i64p))
+    return [bufs[k][:int(cnt[k])].copy() for k in range(b)]
 
 
 def knn_features(data, query, k, return_distance=False, device=-1):
@@ -278,6 +318,8 @@ def match_features_knn(src_feats, dst_feats, k, mutual=True, device=-1):
     return match_features_knn_batch([src_feats], [dst_feats], k, mutual, device)[0]
 
 
-def correspondences_knn(src_cloud, dst_cloud, normal_radius, fpfh_radius, k, mutual=True, device=-1):
+def correspondences_knn(src_cloud, dst_cloud, normal_radius, fpfh_radius, k, mutual=True, device=-1, tuple_scale=0.0,
+                        tuple_seed=0):
     """correspondences_knn_batch for one pair: its array of (src, dst) pairs."""
-    return correspondences_knn_batch([src_cloud], [dst_cloud], normal_radius, fpfh_radius, k, mutual, device=device)[0]
+    return correspondences_knn_batch([src_cloud], [dst_cloud], normal_radius, fpfh_radius, k, mutual, device=device,
+                                     tuple_scale=tuple_scale, tuple_seed=tuple_seed)[0]
