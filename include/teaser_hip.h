@@ -461,6 +461,10 @@ TEASER_HIP_API int32_t teaser_hip_device_count(void);
  *   umeyama: R = V diag(1,1,s) U^T from the SVD U S V^T of H = sum (p - mu_P)(q - mu_Q)^T, s = -1 iff
  *            det(U) det(V) < 0, t = mu_Q - R mu_P (no scaling).  The sums are centred on a fixed point of each
  *            problem (its target's bounding-box centre), so clouds far from the origin keep their precision.
+ *            Where the best fit is not unique -- a cross-covariance H of rank <= 1 (one correspondence, collinear
+ *            matches, every source matched to one target point) -- U is a maximiser of tr(R H) among the proper
+ *            rotations (R^T R = I, det R = +1, R H symmetric, t = mu_Q - R mu_P), not a specified one; H = 0 gives
+ *            R = the identity exactly.  Rank 2 (coplanar matches) and det(H) < 0 with s1 > s2 have a unique answer.
  * Output: T, fitness and inlier_rmse of the final res, iterations = loop bodies executed (max_iteration = 0
  * returns init and corr(apply(init, P))), and the correspondence set sorted by source index.  n_s = 0 or n_t = 0
  * is valid (no correspondences, fitness 0, rmse 0).  TEASER_HIP_ERR_BAD_ARG (teaser_hip_icp_last_error names the
@@ -520,7 +524,12 @@ TEASER_HIP_API int32_t teaser_hip_icp_solve(teaser_hip_icp* icp, const double* s
  *   R  = Rz(gamma) Ry(beta) Rx(alpha)                   Open3D's TransformVector6dToMatrix4d
  *   U  = [ R | t' + c - R c ]                           the step expressed in the problem's own coordinates
  * U is the identity when C is empty, when the factorisation meets a pivot that is not finite or not positive, or when
- * xi is not finite (Open3D returns the identity when its solve fails).  Solving in the frame centred on c is the ONE
+ * xi is not finite (Open3D returns the identity when its solve fails).  An exactly singular system gives the identity:
+ * parallel normals on a planar target, all normals zero, a single correspondence, every pair of a Generalized-ICP
+ * problem left out -- whenever the FP64 factorisation of the FP64 sums meets a pivot that is exactly zero or negative.
+ * When a pivot is zero only up to rounding (A singular in exact arithmetic, its FP64 pivot a few ulps either side of
+ * 0), either outcome -- the identity or the step the tiny pivot gives -- is conforming, and it is always a rigid
+ * transform: finite, R a proper rotation, last row 0 0 0 1.  Solving in the frame centred on c is the ONE
  * deliberate difference from Open3D, which linearises about the origin: the two steps differ at second order in the
  * step's rotation and have the same fixed point, and the centred form makes the result independent of where the pair
  * sits in space (up to the coordinates' own rounding), as the point-to-point sums already are.
