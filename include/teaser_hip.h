@@ -707,7 +707,7 @@ TEASER_HIP_API int32_t teaser_hip_features_destroy(teaser_hip_features* features
 TEASER_HIP_API const char* teaser_hip_features_last_error(const teaser_hip_features* features);
 /* DIAGNOSTIC (exists for the tests of the wave splitting; may be removed): the budgets of one wave in bytes, each
  * <= 0 for its default -- list_bytes: neighbour lists of a wave of clouds (4 GiB); part_bytes: partial nearest-
- * neighbour results of a wave of pairs (1 GiB).  Small values force a call into many waves; no value changes a result. */
+ * neighbour results of a wave of searches (1 GiB).  Small values force a call into many waves; no value changes a result. */
 TEASER_HIP_API int32_t teaser_hip_features_set_budgets(teaser_hip_features* features, int64_t list_bytes,
                                                        int64_t part_bytes);
 /* FPFH of `batch` clouds.  cloud[b]: n[b] x 3 floats; fpfh_out[b]: n[b] x 33 floats; normals_out: NULL, or per cloud

@@ -13,12 +13,13 @@
 //   3. per wave, stream-ordered and without a host round trip: fill + sort of the normal-radius lists, normals; then
 //      per wave fill + sort of the FPFH-radius lists, SPFH, FPFH;
 //   4. the copies of the outputs and the second (last) synchronisation.
-// Matching a batch of feature pairs: two searches per pair in one launch, the results of all searches in one copy, one
-// synchronisation, then the O(n) index bookkeeping per pair on the host.  A call therefore waits for the stream
-// (hipStreamSynchronize) 2 times (FPFH, clouds -> correspondences) or once (matching), whatever the batch and the
-// number of waves.  The k-NN calls (knn_batch, match_knn_batch, correspondences_knn_batch) keep that contract: the
-// searches of all problems in one launch sequence (run_knn), the device-side mutual filter, one copy of the lists and
-// the keep mask, one synchronisation, then the O(n k) pair writing on the host.  Features and normals the caller asked
+// Matching a batch of feature pairs: two 1-nearest searches per pair, the searches of all pairs in one launch sequence
+// (run_knn with k = 1), the results of all searches in one copy, one synchronisation, then the O(n) index bookkeeping
+// per pair on the host.  A call therefore waits for the stream (hipStreamSynchronize) 2 times (FPFH, clouds ->
+// correspondences) or once (matching), whatever the batch and the number of waves.  The k-NN calls (knn_batch,
+// match_knn_batch, correspondences_knn_batch) keep that contract: the searches of all problems through the same
+// run_knn, the device-side mutual filter, one copy of the lists and the keep mask, one synchronisation, then the
+// O(n k) pair writing on the host.  Features and normals the caller asked
 // for, and the features the matching calls take from the host, are copied per problem between the device and the
 // caller's own (pageable) arrays: those copies are additional.
 #include <math.h>
@@ -42,19 +43,19 @@ namespace {
 // Neighbour lists (8 bytes per neighbour) of one wave of clouds; a wave always holds at least one cloud.  The rank
 // sort of lists longer than the LDS sort's capacity needs a scratch copy of the same size when it is used.
 constexpr int64_t kFeatListBudgetBytes = (int64_t)4 << 30;
-// Partial results (8 bytes per query and data chunk) of one wave of pairs.
+// Partial results (8 bytes per query, data chunk and list slot) of one wave of searches.
 constexpr int64_t kFeatPartBudgetBytes = (int64_t)1 << 30;
 
 enum { B_DESC, B_BLK, B_PT_CLOUD, B_PTS, B_COUNTS, B_OFFSETS, B_CURSOR, B_META, B_BASE, B_LIST, B_LIST2, B_NORMALS,
-       B_SPFH, B_FEAT, B_SEARCH, B_SBLK, B_PART_D, B_PART_I, B_NN, B_MFEAT, B_KNN_I, B_KNN_D, B_KNN_KEEP,
+       B_SPFH, B_FEAT, B_SEARCH, B_SBLK, B_PART_D, B_PART_I, B_MFEAT, B_KNN_I, B_KNN_D, B_KNN_KEEP,
        B_TUPLE_DESC, B_TUPLE_BLK, B_TUPLE_PAIRS, B_TUPLE_KEEP, B_COUNT_OF_BUFS };
-enum { H_PTS, H_META, H_NN, H_KNN_I, H_KNN_D, H_KNN_KEEP, H_TUPLE_PAIRS, H_TUPLE_KEEP, H_COUNT_OF_BUFS };
+enum { H_PTS, H_META, H_KNN_I, H_KNN_D, H_KNN_KEEP, H_TUPLE_PAIRS, H_TUPLE_KEEP, H_COUNT_OF_BUFS };
 
 struct Wave {
-  int c0, c1;  // clouds (or pairs, or k-NN searches) [c0, c1)
+  int c0, c1;  // clouds (or searches) [c0, c1)
 };
 
-// One k-NN search of a call: both sides non-empty, rows of the packed feature array.
+// One nearest-neighbour search of a call: both sides non-empty, rows of the packed feature array.
 struct KnnSearch {
   int64_t data_row, query_row;
   int32_t nd, nq;
@@ -282,113 +283,6 @@ int32_t validate_match_outputs(teaser_hip_features* h, int32_t batch, int32_t* c
   return TEASER_HIP_OK;
 }
 
-// Matches `batch` pairs whose features are rows of d_feat (src_row[b], dst_row[b] = first row of each side), copies
-// the nearest-neighbour indices back, synchronises ONCE and writes the pair lists.
-int32_t run_match(teaser_hip_features* h, int32_t batch, const float* d_feat, const int64_t* src_row,
-                  const int64_t* dst_row, const int32_t* n_src, const int32_t* n_dst, int dim, bool use_crosscheck,
-                  int32_t* const* pairs, const int64_t* pair_cap, int64_t* n_pairs) {
-  hipStream_t s = h->stream;
-  DevBuf* B = h->buf;
-  for (int b = 0; b < batch; ++b) n_pairs[b] = 0;
-  // two searches per pair with both sides non-empty (matcher.cc:123-133: i = the larger cloud, j = the smaller one):
-  // search 2k: for every j its nearest i (:162);  search 2k + 1: for every i its nearest j (:165)
-  h->search.clear();
-  std::vector<int> pair_of;       // pair index of searches 2k, 2k + 1
-  std::vector<Wave> waves;        // in units of k
-  std::vector<int> wave_blk0;
-  int64_t nn_total = 0, blocks = 0, part_acc = 0, part_cap = 1;
-  const int64_t part_budget = h->part_budget / 8;
-  int k0 = 0;
-  for (int b = 0; b < batch; ++b) {
-    if (n_src[b] == 0 || n_dst[b] == 0) continue;
-    const bool swapped = n_dst[b] > n_src[b];
-    const int ni = swapped ? n_dst[b] : n_src[b], nj = swapped ? n_src[b] : n_dst[b];
-    const int64_t ri = swapped ? dst_row[b] : src_row[b], rj = swapped ? src_row[b] : dst_row[b];
-    const int64_t pa = (int64_t)feat_nn_chunks(ni) * nj, pb = (int64_t)feat_nn_chunks(nj) * ni;
-    const int k = (int)pair_of.size();
-    if (k > k0 && part_acc + pa + pb > part_budget) {
-      waves.push_back(Wave{k0, k});
-      k0 = k;
-      part_acc = 0;
-    }
-    if (k == k0) wave_blk0.push_back((int)blocks);
-    FeatSearchDesc a{ri, rj, part_acc, nn_total, ni, nj, (int32_t)blocks, (nj + 63) / 64};
-    blocks += (int64_t)a.qblocks * feat_nn_chunks(ni);
-    FeatSearchDesc c{rj, ri, part_acc + pa, nn_total + nj, nj, ni, (int32_t)blocks, (ni + 63) / 64};
-    blocks += (int64_t)c.qblocks * feat_nn_chunks(nj);
-    if (blocks >= INT32_MAX) return fail(h, TEASER_HIP_ERR_UNSUPPORTED, "too many features in one call" + at(b));
-    part_acc += pa + pb;
-    part_cap = std::max(part_cap, part_acc);
-    nn_total += (int64_t)ni + nj;
-    h->search.push_back(a);
-    h->search.push_back(c);
-    pair_of.push_back(b);
-  }
-  const int nk = (int)pair_of.size();
-  if (nk > 0) {
-    waves.push_back(Wave{k0, nk});
-    h->blk_search.resize((size_t)blocks);
-    for (size_t q = 0; q < h->search.size(); ++q) {
-      const int32_t end = q + 1 < h->search.size() ? h->search[q + 1].blk_off : (int32_t)blocks;
-      std::fill(h->blk_search.begin() + h->search[q].blk_off, h->blk_search.begin() + end, (int32_t)q);
-    }
-    FENSURE(h, B[B_SEARCH], sizeof(FeatSearchDesc) * h->search.size());
-    FENSURE(h, B[B_SBLK], 4 * (size_t)blocks);
-    FENSURE(h, B[B_PART_D], 4 * (size_t)part_cap);
-    FENSURE(h, B[B_PART_I], 4 * (size_t)part_cap);
-    FENSURE(h, B[B_NN], 4 * (size_t)nn_total);
-    FENSURE(h, h->host[H_NN], 4 * (size_t)nn_total);
-    FCHK(h, hipMemcpyAsync(B[B_SEARCH].p, h->search.data(), sizeof(FeatSearchDesc) * h->search.size(),
-                           hipMemcpyHostToDevice, s),
-         "hipMemcpyAsync (search descriptors)");
-    FCHK(h, hipMemcpyAsync(B[B_SBLK].p, h->blk_search.data(), 4 * (size_t)blocks, hipMemcpyHostToDevice, s),
-         "hipMemcpyAsync (search block map)");
-    for (size_t w = 0; w < waves.size(); ++w) {
-      const int s0 = 2 * waves[w].c0, s1 = 2 * waves[w].c1;
-      const int blk0 = wave_blk0[w], blk1 = s1 < (int)h->search.size() ? h->search[(size_t)s1].blk_off : (int)blocks;
-      int max_nq = 0;
-      for (int q = s0; q < s1; ++q) max_nq = std::max(max_nq, h->search[(size_t)q].nq);
-      launch_feat_nn1_batch(s, B[B_SEARCH].as<FeatSearchDesc>(), B[B_SBLK].as<int32_t>(), blk0, blk1 - blk0, s0, s1,
-                            max_nq, d_feat, dim, B[B_PART_D].as<float>(), B[B_PART_I].as<int32_t>(),
-                            B[B_NN].as<int32_t>());
-    }
-    FCHK(h, hipGetLastError(), "front-end kernel launch (matching)");
-    FCHK(h, hipMemcpyAsync(h->host[H_NN].p, B[B_NN].p, 4 * (size_t)nn_total, hipMemcpyDeviceToHost, s),
-         "hipMemcpyAsync (nearest neighbours)");
-  }
-  FCHK(h, hipStreamSynchronize(s), "hipStreamSynchronize (results)");
-
-  int too_small = -1;
-  for (int k = 0; k < nk; ++k) {
-    const int b = pair_of[(size_t)k];
-    const FeatSearchDesc& a = h->search[2 * (size_t)k];
-    const int ni = a.nd, nj = a.nq;
-    const int32_t* j_to_i = h->host[H_NN].as<int32_t>() + a.nn_off;
-    const int32_t* i_nn = j_to_i + nj;
-    // A query whose distances are all NaN / +inf (non-finite features) has no nearest neighbour: the kernel reports
-    // -1.  FLANN would return garbage there; an error is the honest answer.
-    bool ok = true;
-    for (int j = 0; j < nj; ++j) ok &= j_to_i[j] >= 0 && j_to_i[j] < ni;
-    for (int i = 0; i < ni; ++i) ok &= i_nn[i] >= 0 && i_nn[i] < nj;
-    if (!ok)
-      return fail(h, TEASER_HIP_ERR_BAD_ARG, "non-finite feature values (no nearest neighbour for a point)" + at(b));
-    const auto corres = feat_match_pairs(j_to_i, nj, i_nn, ni, n_dst[b] > n_src[b], use_crosscheck);
-    n_pairs[b] = (int64_t)corres.size();
-    if ((int64_t)corres.size() > pair_cap[b]) {
-      if (too_small < 0) too_small = b;
-      continue;
-    }
-    for (size_t q = 0; q < corres.size(); ++q) {
-      pairs[b][2 * q] = corres[q].first;
-      pairs[b][2 * q + 1] = corres[q].second;
-    }
-  }
-  if (too_small >= 0)
-    return fail(h, TEASER_HIP_ERR_BAD_ARG, "pair_cap is too small: " + std::to_string(n_pairs[too_small]) +
-                                               " pairs needed" + at(too_small));
-  return TEASER_HIP_OK;
-}
-
 // The k-NN searches `in` over rows of d_feat, enqueued: row q of search number x in B_KNN_I (and B_KNN_D when
 // want_dist) at h->search[x].nn_off = k slots, the k nearest in (d, index) order, then -1 / +inf.  No synchronisation.
 // The partial lists (8 bytes per query, data chunk and list slot of the kernel serving k) of one wave of searches fit
@@ -452,6 +346,71 @@ int32_t run_knn(teaser_hip_features* h, const std::vector<KnnSearch>& in, const 
   }
   FCHK(h, hipGetLastError(), "front-end kernel launch (k-NN)");
   return TEASER_HIP_OK;
+}
+
+// The end of the matching calls: too_small = the first problem whose pairs did not fit its pair_cap, -1 if all did.
+int32_t check_pair_caps(teaser_hip_features* h, int too_small, const int64_t* n_pairs) {
+  if (too_small < 0) return TEASER_HIP_OK;
+  return fail(h, TEASER_HIP_ERR_BAD_ARG,
+              "pair_cap is too small: " + std::to_string(n_pairs[too_small]) + " pairs needed" + at(too_small));
+}
+
+// Matches `batch` pairs whose features are rows of d_feat (src_row[b], dst_row[b] = first row of each side): two
+// 1-nearest searches per pair through run_knn, the indices copied back, ONE synchronisation, then the pair lists.
+int32_t run_match(teaser_hip_features* h, int32_t batch, const float* d_feat, const int64_t* src_row,
+                  const int64_t* dst_row, const int32_t* n_src, const int32_t* n_dst, int dim, bool use_crosscheck,
+                  int32_t* const* pairs, const int64_t* pair_cap, int64_t* n_pairs) {
+  hipStream_t s = h->stream;
+  for (int b = 0; b < batch; ++b) n_pairs[b] = 0;
+  // two searches per pair with both sides non-empty (matcher.cc:123-133: i = the larger cloud, j = the smaller one):
+  // search 2k: for every j its nearest i (:162);  search 2k + 1: for every i its nearest j (:165)
+  std::vector<KnnSearch> in;
+  std::vector<int> problem_of;  // pair index of searches 2k, 2k + 1
+  for (int b = 0; b < batch; ++b) {
+    if (n_src[b] == 0 || n_dst[b] == 0) continue;
+    const bool swapped = n_dst[b] > n_src[b];
+    const int ni = swapped ? n_dst[b] : n_src[b], nj = swapped ? n_src[b] : n_dst[b];
+    const int64_t ri = swapped ? dst_row[b] : src_row[b], rj = swapped ? src_row[b] : dst_row[b];
+    in.push_back(KnnSearch{ri, rj, ni, nj});
+    in.push_back(KnnSearch{rj, ri, nj, ni});
+    problem_of.insert(problem_of.end(), 2, b);
+  }
+  int64_t total = 0;
+  const int32_t rc = run_knn(h, in, problem_of, d_feat, dim, 1, false, &total);
+  if (rc != TEASER_HIP_OK) return rc;
+  if (total > 0) {
+    FENSURE(h, h->host[H_KNN_I], 4 * (size_t)total);
+    FCHK(h, hipMemcpyAsync(h->host[H_KNN_I].p, h->buf[B_KNN_I].p, 4 * (size_t)total, hipMemcpyDeviceToHost, s),
+         "hipMemcpyAsync (nearest neighbours)");
+  }
+  FCHK(h, hipStreamSynchronize(s), "hipStreamSynchronize (results)");
+
+  int too_small = -1;
+  for (size_t x = 0; x < in.size(); x += 2) {
+    const int b = problem_of[x];
+    const FeatSearchDesc& a = h->search[x];
+    const int ni = a.nd, nj = a.nq;
+    const int32_t* j_to_i = h->host[H_KNN_I].as<int32_t>() + a.nn_off;  // (k = 1: a search's results are its nq rows)
+    const int32_t* i_nn = j_to_i + nj;
+    // A query whose distances are all NaN / +inf (non-finite features) has no nearest neighbour: the kernel reports
+    // -1.  FLANN would return garbage there; an error is the honest answer.
+    bool ok = true;
+    for (int j = 0; j < nj; ++j) ok &= j_to_i[j] >= 0 && j_to_i[j] < ni;
+    for (int i = 0; i < ni; ++i) ok &= i_nn[i] >= 0 && i_nn[i] < nj;
+    if (!ok)
+      return fail(h, TEASER_HIP_ERR_BAD_ARG, "non-finite feature values (no nearest neighbour for a point)" + at(b));
+    const auto corres = feat_match_pairs(j_to_i, nj, i_nn, ni, n_dst[b] > n_src[b], use_crosscheck);
+    n_pairs[b] = (int64_t)corres.size();
+    if ((int64_t)corres.size() > pair_cap[b]) {
+      if (too_small < 0) too_small = b;
+      continue;
+    }
+    for (size_t q = 0; q < corres.size(); ++q) {
+      pairs[b][2 * q] = corres[q].first;
+      pairs[b][2 * q + 1] = corres[q].second;
+    }
+  }
+  return check_pair_caps(h, too_small, n_pairs);
 }
 
 // Whether every row of an nq x k list holds its k_eff = min(k, nd) entries (sorted: the last of them decides).
@@ -541,10 +500,7 @@ int32_t run_match_knn(teaser_hip_features* h, int32_t batch, const float* d_feat
       }
     }
   }
-  if (too_small >= 0)
-    return fail(h, TEASER_HIP_ERR_BAD_ARG, "pair_cap is too small: " + std::to_string(n_pairs[too_small]) +
-                                               " pairs needed" + at(too_small));
-  return TEASER_HIP_OK;
+  return check_pair_caps(h, too_small, n_pairs);
 }
 
 // The two feature sets of every problem (a[b]: n_a[b] x dim, b[b]: n_b[b] x dim), checked and copied one after the

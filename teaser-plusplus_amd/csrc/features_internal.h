@@ -23,7 +23,8 @@ struct FeatCloudDesc {
 };
 
 // One nearest-neighbour search of a batch: for each of nq query rows its nearest of nd data rows.  Rows are rows of
-// the packed feature array; partial results occupy part[part_off .. part_off + chunks * nq), results nn[nn_off ..).
+// the packed feature array; partial results occupy part[part_off .. part_off + chunks * slots * nq), results
+// nn[nn_off .. nn_off + nq * k): for each query row its k nearest (feat_knn_slots, launch_feat_knn_batch below).
 struct FeatSearchDesc {
   int64_t data_row, query_row, part_off, nn_off;
   int32_t nd, nq;
@@ -66,16 +67,12 @@ void launch_feat_normals_batch(hipStream_t s, const FeatCloudDesc* d_desc, const
 void launch_feat_fpfh_batch(hipStream_t s, const FeatCloudDesc* d_desc, const int32_t* d_pt_cloud, int64_t pt0,
                             int64_t pt1, const float* d_pts, const float* d_normals, const int64_t* d_offsets,
                             const int32_t* d_counts, const void* d_list, float* d_spfh, float* d_out);
-// searches [s0, s1), whose blocks are [blk_base, blk_base + n_blk); max_nq = the largest nq among them
-void launch_feat_nn1_batch(hipStream_t s, const FeatSearchDesc* d_search, const int32_t* d_blk_search, int blk_base,
-                           int n_blk, int s0, int s1, int max_nq, const float* d_feat, int dim, float* d_part_d,
-                           int32_t* d_part_i, int32_t* d_nn);
-
-// k-NN (include/teaser_hip.h, "k nearest").  The searches use FeatSearchDesc and the block map as the 1-NN launch
-// does, with part_off counting the chunks x feat_knn_slots(k) x nq partial entries and nn_off the nq x k result slots
-// of the searches before.
-int feat_knn_slots(int k);  // list slots of the kernel instantiation that serves k (2, 4, 8 or 16)
-// searches [s0, s1): row q of d_idx / d_dist (d_dist may be nullptr) = the k nearest in (d, index) order, then -1 / +inf
+// k-NN (include/teaser_hip.h, "k nearest"; k = 1 is the matcher's pair of searches).  The searches use FeatSearchDesc
+// and a block -> search map, with part_off counting the chunks x feat_knn_slots(k) x nq partial entries and nn_off the
+// nq x k result slots of the searches before.
+int feat_knn_slots(int k);  // list slots of the kernel instantiation that serves k (1, 2, 4, 8 or 16)
+// searches [s0, s1), whose blocks are [blk_base, blk_base + n_blk); max_nq = the largest nq among them.
+// Row q of d_idx / d_dist (d_dist may be nullptr) = the k nearest in (d, index) order, then -1 / +inf
 void launch_feat_knn_batch(hipStream_t s, const FeatSearchDesc* d_search, const int32_t* d_blk_search, int blk_base,
                            int n_blk, int s0, int s1, int max_nq, const float* d_feat, int dim, int k, float* d_part_d,
                            int32_t* d_part_i, int32_t* d_idx, float* d_dist);

@@ -335,7 +335,7 @@ hipError_t launch_tls_scale_large(hipStream_t s, const double* d_src, const doub
 // are in features_internal.h
 int64_t feat_nbr_bytes();    // bytes of one (distance, index) neighbour record
 int feat_sort_capacity();    // longest list the LDS sort holds; longer ones take the rank sort
-int feat_nn_chunks(int nd);  // data chunks of a 1-NN search over nd rows
+int feat_nn_chunks(int nd);  // data chunks of a nearest-neighbour search over nd rows
 int feat_nn_max_dim();
 // teaser_hip_features_fpfh_batch (features.hip) without its rule for the radii (finite, and the float square neither
 // 0 nor inf): batch > 0, the radii not NULL.  teaser_hip_compute_fpfh (solver.hip) comes in here with its own, older

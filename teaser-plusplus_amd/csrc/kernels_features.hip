@@ -489,106 +489,24 @@ __device__ __forceinline__ void feat_fpfh_point(int p, const int64_t* __restrict
   if (lane < 33) out[(size_t)p * 33 + lane] = o * sum;
 }
 
-// ---- exact L2 1-NN in `dim` dimensions (the matcher's two searches) -------------------------------
-// grid (query blocks of 64, data chunks of kNnChunk): a thread owns one query (its `dim` values staged in
-// LDS, one row per thread), walks the chunk's data points through an LDS tile, accumulating
-// (q_c - d_c)^2 over c in order in float; first strict minimum = lowest index on ties.
-// Exact L2 1-NN, brute force.  The arithmetic of one distance is fixed by the oracle (flann::L2<float> order:
+// ---- exact L2 k-NN in `dim` dimensions (include/teaser_hip.h, "k nearest"): the k smallest (d, index) per query ------
+// K = 1 is the matcher's two searches.
+// grid (query blocks of 64, data chunks of kNnChunk): a thread owns one query, walks the chunk's data points through
+// an LDS tile, accumulating (q_c - d_c)^2 over c in order in float, and keeps the K best of its chunk as a list sorted
+// by (d, index) in registers.
+// Exact L2, brute force.  The arithmetic of one distance is fixed by the oracle (flann::L2<float> order:
 // d += (q_c - x_c)^2 for c = 0 .. dim-1, float), so the speed has to come from the layout: the query vector of a
 // thread lives in REGISTERS (dim is a template parameter for the 33-bin FPFH signature; other dims take the generic
-// instantiation with the query in LDS), a tile of kNnTile data points is staged in LDS and read back as broadcast
-// ds_read_b128, and the data set is cut into chunks of kNnChunk points so that a 5 000 x 5 000 match fills the GPU
-// (1 700 waves instead of the 164 of the first version, which took 6 ms per direction -- 0.3 TFLOP/s).
+// instantiation with the query in LDS, one row per thread), a tile of kNnTile data points is staged in LDS and read
+// back as broadcast ds_read_b128, and the data set is cut into chunks of kNnChunk points so that a 5 000 x 5 000 match
+// fills the GPU (1 700 waves instead of the 164 of the first version, which took 6 ms per direction -- 0.3 TFLOP/s).
+// K is a template parameter (1, 2, 4, 8, 16; a call's k is rounded up): the list is only ever indexed by the unrolled
+// loops' constants, so it stays in VGPRs -- a runtime-indexed array would live in scratch memory.  Candidates arrive
+// in ascending index order and the comparisons are strict, so among equal d the lower index stays ahead (K = 1: the
+// first strict minimum); NaN and +inf fail every `<` against the +inf the list starts with and never enter.
 constexpr int kNnChunk = 256;
 constexpr int kNnTile = 64;
 constexpr int kNnMaxDim = 64;
-// (the body of one workgroup: query block `qblock` against data chunk `chunk` of ONE search)
-template <int DIM>
-__device__ __forceinline__ void feat_nn_partial_block(const float* __restrict__ data, int nd,
-                                                      const float* __restrict__ query, int nq, int dim_rt,
-                                                      float* __restrict__ part_d, int32_t* __restrict__ part_i,
-                                                      int qblock, int chunk) {
-  constexpr int kPad = DIM > 0 ? ((DIM + 3) & ~3) : kNnMaxDim;  // floats per staged point (16-byte rows)
-  __shared__ __attribute__((aligned(16))) float tile[kNnTile * kPad];
-  __shared__ float qs[DIM > 0 ? 1 : 64 * (kNnMaxDim + 1)];
-  const int dim = DIM > 0 ? DIM : dim_rt;
-  const int q = qblock * 64 + threadIdx.x;
-  const bool live = q < nq;
-  float qr[DIM > 0 ? kPad : 1];
-  if (DIM > 0) {
-#pragma unroll
-    for (int c = 0; c < kPad; ++c) qr[c] = (live && c < DIM) ? query[(size_t)q * DIM + c] : 0.f;
-  } else {
-    for (int c = 0; c < dim; ++c) qs[threadIdx.x * (kNnMaxDim + 1) + c] = live ? query[(size_t)q * dim + c] : 0.f;
-  }
-  const int lo = chunk * kNnChunk, hi = min(nd, lo + kNnChunk);
-  float best = __builtin_inff();
-  int bi = -1;
-  for (int base = lo; base < hi; base += kNnTile) {
-    const int m = min(kNnTile, hi - base);
-    __syncthreads();
-    if (DIM > 0) {
-      for (int k = threadIdx.x; k < m * kPad; k += 64) {
-        const int pt = k / kPad, c = k - pt * kPad;
-        tile[k] = c < DIM ? data[(size_t)(base + pt) * DIM + c] : 0.f;
-      }
-    } else {
-      for (int k = threadIdx.x; k < m * dim; k += 64) tile[(k / dim) * kPad + (k % dim)] = data[(size_t)base * dim + k];
-    }
-    __syncthreads();
-    for (int k = 0; k < m; ++k) {
-      float d = 0;
-      if (DIM > 0) {
-        const float4* row = reinterpret_cast<const float4*>(tile + k * kPad);
-#pragma unroll
-        for (int c4 = 0; c4 < kPad / 4; ++c4) {
-          const float4 x = row[c4];  // broadcast: every lane reads the same 16 bytes
-          const float xs[4] = {x.x, x.y, x.z, x.w};
-#pragma unroll
-          for (int e = 0; e < 4; ++e)
-            if (4 * c4 + e < DIM) {  // (the padding is skipped: d + 0 * 0 would still be a float operation)
-              const float t = qr[4 * c4 + e] - xs[e];
-              d += t * t;
-            }
-        }
-      } else {
-        for (int c = 0; c < dim; ++c) {
-          const float t = qs[threadIdx.x * (kNnMaxDim + 1) + c] - tile[k * kPad + c];
-          d += t * t;
-        }
-      }
-      if (d < best) {
-        best = d;
-        bi = base + k;
-      }
-    }
-  }
-  if (live) {
-    part_d[(size_t)chunk * nq + q] = best;
-    part_i[(size_t)chunk * nq + q] = bi;
-  }
-}
-__device__ __forceinline__ void feat_nn_final_query(const float* __restrict__ part_d,
-                                                    const int32_t* __restrict__ part_i, int nq, int chunks,
-                                                    int32_t* __restrict__ nn, int q) {
-  float best = __builtin_inff();
-  int bi = -1;
-  for (int c = 0; c < chunks; ++c) {  // chunks in index order + strict <: the first minimum overall
-    const float d = part_d[(size_t)c * nq + q];
-    if (d < best) {
-      best = d;
-      bi = part_i[(size_t)c * nq + q];
-    }
-  }
-  nn[q] = bi;
-}
-
-// ---- exact L2 k-NN (include/teaser_hip.h, "k nearest"): the k smallest (d, index) per query ----------------------
-// Same grid, staging and distance arithmetic as the 1-NN pair above; a thread keeps the K best of its chunk as a list
-// sorted by (d, index) in registers.  K is a template parameter (2, 4, 8, 16; a call's k is rounded up): the list
-// is only ever indexed by the unrolled loops' constants, so it stays in VGPRs -- a runtime-indexed array would live in
-// scratch memory.  Candidates arrive in ascending index order and the comparisons are strict, so among equal d the
-// lower index stays ahead; NaN and +inf fail every `<` against the +inf the list starts with and never enter.
 template <int K>
 __device__ __forceinline__ void feat_knn_insert(float (&ld)[K], int32_t (&li)[K], float d, int32_t idx) {
 #pragma unroll
@@ -600,13 +518,14 @@ __device__ __forceinline__ void feat_knn_insert(float (&ld)[K], int32_t (&li)[K]
   li[0] = d < ld[0] ? idx : li[0];
   ld[0] = d < ld[0] ? d : ld[0];
 }
+// (the body of one workgroup: query block `qblock` against data chunk `chunk` of ONE search)
 // partials: [chunk][slot][query], so that the lanes of a wave store neighbouring words
 template <int DIM, int K>
 __device__ __forceinline__ void feat_knn_partial_block(const float* __restrict__ data, int nd,
                                                        const float* __restrict__ query, int nq, int dim_rt,
                                                        float* __restrict__ part_d, int32_t* __restrict__ part_i,
                                                        int qblock, int chunk) {
-  constexpr int kPad = DIM > 0 ? ((DIM + 3) & ~3) : kNnMaxDim;
+  constexpr int kPad = DIM > 0 ? ((DIM + 3) & ~3) : kNnMaxDim;  // floats per staged point (16-byte rows)
   __shared__ __attribute__((aligned(16))) float tile[kNnTile * kPad];
   __shared__ float qs[DIM > 0 ? 1 : 64 * (kNnMaxDim + 1)];
   const int dim = DIM > 0 ? DIM : dim_rt;
@@ -640,16 +559,16 @@ __device__ __forceinline__ void feat_knn_partial_block(const float* __restrict__
     }
     __syncthreads();
     for (int k = 0; k < m; ++k) {
-      float d = 0;  // (the 1-NN kernel's arithmetic, operation for operation)
+      float d = 0;
       if (DIM > 0) {
         const float4* row = reinterpret_cast<const float4*>(tile + k * kPad);
 #pragma unroll
         for (int c4 = 0; c4 < kPad / 4; ++c4) {
-          const float4 x = row[c4];
+          const float4 x = row[c4];  // broadcast: every lane reads the same 16 bytes
           const float xs[4] = {x.x, x.y, x.z, x.w};
 #pragma unroll
           for (int e = 0; e < 4; ++e)
-            if (4 * c4 + e < DIM) {
+            if (4 * c4 + e < DIM) {  // (the padding is skipped: d + 0 * 0 would still be a float operation)
               const float t = qr[4 * c4 + e] - xs[e];
               d += t * t;
             }
@@ -778,34 +697,8 @@ __global__ __launch_bounds__(256) void feat_fpfh_batch_kernel(const FeatCloudDes
   feat_fpfh_point((int)(g - off), offsets + off, counts + off, list, spfh + 33 * off, out + 33 * off);
 }
 
-template <int DIM>
-__global__ __launch_bounds__(64) void feat_nn_partial_batch_kernel(const FeatSearchDesc* __restrict__ search,
-                                                                   const int32_t* __restrict__ blk_search,
-                                                                   int blk_base, const float* __restrict__ feat,
-                                                                   int dim_rt, float* __restrict__ part_d,
-                                                                   int32_t* __restrict__ part_i) {
-  const int blk = blk_base + (int)blockIdx.x;
-  const FeatSearchDesc d = search[blk_search[blk]];
-  const int local = blk - d.blk_off;
-  const int chunk = local / d.qblocks, qblock = local - chunk * d.qblocks;
-  const int dim = DIM > 0 ? DIM : dim_rt;
-  feat_nn_partial_block<DIM>(feat + d.data_row * dim, d.nd, feat + d.query_row * dim, d.nq, dim_rt,
-                             part_d + d.part_off, part_i + d.part_off, qblock, chunk);
-}
-// grid (query blocks of 256 of the largest search, searches)
-__global__ __launch_bounds__(256) void feat_nn_final_batch_kernel(const FeatSearchDesc* __restrict__ search, int s0,
-                                                                  const float* __restrict__ part_d,
-                                                                  const int32_t* __restrict__ part_i,
-                                                                  int32_t* __restrict__ nn) {
-  const FeatSearchDesc d = search[s0 + (int)blockIdx.y];
-  const int q = blockIdx.x * 256 + threadIdx.x;
-  if (q >= d.nq) return;
-  feat_nn_final_query(part_d + d.part_off, part_i + d.part_off, d.nq, (d.nd + kNnChunk - 1) / kNnChunk,
-                      nn + d.nn_off, q);
-}
-
-// k-NN searches: the descriptors and the block map of the 1-NN launch; part_off counts (chunk, slot, query) entries
-// and nn_off the nq x k result slots of the searches before this one.
+// k-NN searches: part_off counts the (chunk, slot, query) partial entries and nn_off the nq x k result slots of the
+// searches before this one.
 template <int DIM, int K>
 __global__ __launch_bounds__(64) void feat_knn_partial_batch_kernel(const FeatSearchDesc* __restrict__ search,
                                                                     const int32_t* __restrict__ blk_search,
@@ -820,6 +713,7 @@ __global__ __launch_bounds__(64) void feat_knn_partial_batch_kernel(const FeatSe
   feat_knn_partial_block<DIM, K>(feat + d.data_row * dim, d.nd, feat + d.query_row * dim, d.nq, dim_rt,
                                  part_d + d.part_off, part_i + d.part_off, qblock, chunk);
 }
+// grid (query blocks of 256 of the largest search, searches)
 template <int K>
 __global__ __launch_bounds__(256) void feat_knn_final_batch_kernel(const FeatSearchDesc* __restrict__ search, int s0,
                                                                    const float* __restrict__ part_d,
@@ -959,35 +853,20 @@ void launch_feat_fpfh_batch(hipStream_t s, const FeatCloudDesc* d_desc, const in
   hipLaunchKernelGGL(feat_fpfh_batch_kernel, dim3(blocks), dim3(256), 0, s, d_desc, d_pt_cloud, pt0, pt1, d_offsets,
                      d_counts, reinterpret_cast<const Nbr*>(d_list), d_spfh, d_out);
 }
-void launch_feat_nn1_batch(hipStream_t s, const FeatSearchDesc* d_search, const int32_t* d_blk_search, int blk_base,
-                           int n_blk, int s0, int s1, int max_nq, const float* d_feat, int dim, float* d_part_d,
-                           int32_t* d_part_i, int32_t* d_nn) {
-  if (n_blk <= 0 || s1 <= s0 || max_nq <= 0) return;
-  if (dim == 33)  // pcl::FPFHSignature33
-    hipLaunchKernelGGL(feat_nn_partial_batch_kernel<33>, dim3(n_blk), dim3(64), 0, s, d_search, d_blk_search, blk_base,
-                       d_feat, dim, d_part_d, d_part_i);
-  else
-    hipLaunchKernelGGL(feat_nn_partial_batch_kernel<0>, dim3(n_blk), dim3(64), 0, s, d_search, d_blk_search, blk_base,
-                       d_feat, dim, d_part_d, d_part_i);
-  for (int y0 = s0; y0 < s1; y0 += 65535)  // (the grid's y extent)
-    hipLaunchKernelGGL(feat_nn_final_batch_kernel, dim3((max_nq + 255) / 256, std::min(65535, s1 - y0)), dim3(256), 0, s,
-                       d_search, y0, d_part_d, d_part_i, d_nn);
-}
-
-int feat_knn_slots(int k) { return k <= 2 ? 2 : k <= 4 ? 4 : k <= 8 ? 8 : 16; }
+int feat_knn_slots(int k) { return k <= 1 ? 1 : k <= 2 ? 2 : k <= 4 ? 4 : k <= 8 ? 8 : 16; }
 
 namespace {
 template <int K>
 void launch_feat_knn_slots(hipStream_t s, const FeatSearchDesc* d_search, const int32_t* d_blk_search, int blk_base,
                            int n_blk, int s0, int s1, int max_nq, const float* d_feat, int dim, int k, float* d_part_d,
                            int32_t* d_part_i, int32_t* d_idx, float* d_dist) {
-  if (dim == 33)
+  if (dim == 33)  // pcl::FPFHSignature33
     hipLaunchKernelGGL((feat_knn_partial_batch_kernel<33, K>), dim3(n_blk), dim3(64), 0, s, d_search, d_blk_search,
                        blk_base, d_feat, dim, d_part_d, d_part_i);
   else
     hipLaunchKernelGGL((feat_knn_partial_batch_kernel<0, K>), dim3(n_blk), dim3(64), 0, s, d_search, d_blk_search,
                        blk_base, d_feat, dim, d_part_d, d_part_i);
-  for (int y0 = s0; y0 < s1; y0 += 65535)
+  for (int y0 = s0; y0 < s1; y0 += 65535)  // (the grid's y extent)
     hipLaunchKernelGGL(feat_knn_final_batch_kernel<K>, dim3((max_nq + 255) / 256, std::min(65535, s1 - y0)), dim3(256),
                        0, s, d_search, y0, d_part_d, d_part_i, k, d_idx, d_dist);
 }
@@ -1003,6 +882,7 @@ void launch_feat_knn_batch(hipStream_t s, const FeatSearchDesc* d_search, const 
     launch_feat_knn_slots<K>(s, d_search, d_blk_search, blk_base, n_blk, s0, s1, max_nq, d_feat, dim, k, d_part_d, \
                              d_part_i, d_idx, d_dist);                                                           \
     break;
+    THIP_KNN_CASE(1)
     THIP_KNN_CASE(2)
     THIP_KNN_CASE(4)
     THIP_KNN_CASE(8)

@@ -2,6 +2,8 @@
 for many clouds / pairs against the CPU oracle (oracle/features_oracle.c), the reference's fixtures
 (tests/golden/features_golden.npz) and the single-call path.  The front-end's contract is bit identity, so every
 comparison is exact: no tolerance appears, except the project's pose parity bar of the end-to-end test."""
+import ctypes as C
+import functools
 import importlib
 import os
 
@@ -109,6 +111,57 @@ def test_matcher_fixture_in_a_batch():
                                                       False, 0)[0] == [tuple(r) for r in m[0].tolist()]
 
 
+# the search kernel's three granularities: the 64-query block, the 64-point tile and the 256-point chunk
+EDGE_N = [(a, b) for a in (1, 63, 64, 65, 255, 256, 257, 513) for b in (1, 64, 65, 130)]
+
+
+@functools.lru_cache(maxsize=None)
+def edge_features(dim):
+    """Both orders of every EDGE_N size pair (the second order runs the swapped-roles path), random features; then a
+    pair full of exact ties, both orders: features in {0, 1, 2}, 513 x 130, rows 10, 255, 256 and 300 of the larger
+    side -- both sides of the chunk boundary at 256 -- copies of row 0 of the smaller (the construction of
+    test_gpu_features_knn.test_ties_go_to_the_lower_index).  Returns (src list, dst list)."""
+    rng = np.random.default_rng(1300 + dim)
+    src, dst = [], []
+    for a, b in EDGE_N:
+        x, y = rng.random((a, dim), dtype=np.float32), rng.random((b, dim), dtype=np.float32)
+        src += [x, y]
+        dst += [y, x]
+    big, small = (rng.integers(0, 3, size=(n, dim)).astype(np.float32) for n in (513, 130))
+    big[[10, 255, 256, 300]] = small[0]
+    return src + [big, small], dst + [small, big]
+
+
+@pytest.mark.parametrize("use_crosscheck", [True, False])
+@pytest.mark.parametrize("dim", [33, 7])
+def test_matcher_edge_sizes_equal_the_oracle(dim, use_crosscheck):
+    """The matcher is served by the k-NN kernels with K = 1, so comparing it with k = 1 k-NN matching compares a kernel
+    with itself.  This pins it against the CPU oracle instead (oracle/features_oracle.c feat_match: a plain double
+    loop, strict <, ascending index), exactly, at every block / tile / chunk edge and on exact ties, one call."""
+    src, dst = edge_features(dim)
+    # the oracle's own tie rule, checked where it matters: its 1-NN on the tie pair is numpy's first minimum (the
+    # distances there are small integers, exact in float whatever the summation order)
+    big, small = src[-2], src[-1]
+    for data, query in ((big, small), (small, big)):
+        nn = np.zeros(len(query), dtype=np.int32)
+        ip, fp = C.POINTER(C.c_int32), C.POINTER(C.c_float)
+        F.lib().feat_nn1(data.ctypes.data_as(fp), C.c_int32(len(data)), query.ctypes.data_as(fp),
+                         C.c_int32(len(query)), C.c_int32(dim), nn.ctypes.data_as(ip))
+        d = ((query[:, None, :] - data[None, :, :]) ** 2).sum(axis=2)
+        assert nn.tolist() == d.argmin(axis=1).tolist()
+
+    got = tp.match_features_batch(src, dst, use_crosscheck=use_crosscheck)
+    assert len(got) == 2 * len(EDGE_N) + 2
+    for p, (a, b) in enumerate(zip(src, dst)):
+        want = F.match(a, b, crosscheck=use_crosscheck)
+        assert len(want) >= 1
+        assert same(got[p], want), "n_src %d n_dst %d%s" % (len(a), len(b), " (ties)" if p >= 2 * len(EDGE_N) else "")
+    # small row 0 has four rows at distance 0 in big: it goes to the lowest, 10, whose nearest is row 0 in turn
+    assert [10, 0] in got[-2].tolist() and [0, 10] in got[-1].tolist()
+    if use_crosscheck:
+        assert not any(r in got[-1].tolist() for r in ([0, 255], [0, 256], [0, 300]))
+
+
 def test_long_lists_inside_a_batch():
     """One call that uses the LDS sort and the rank sort at once."""
     ball, can = ball_cloud(), G["canstick"]
@@ -124,7 +177,7 @@ def test_wave_splitting_does_not_change_a_byte(pairs64):
     """A list budget of 256 KB and a partial-result budget of 4 MB.  Every point is its own neighbour (8 bytes), so
     the lists of the 128 clouds hold at least 8 bytes per point: more than three list budgets.  A pair's two searches
     hold 8 bytes per query and 256-row data chunk: summed over the 64 pairs more than three partial-result budgets.
-    So both the clouds and the pairs fall into at least three waves, whatever the radii catch."""
+    So both the clouds and the searches fall into at least three waves, whatever the radii catch."""
     src, dst, vox, out = pairs64
     total = sum(len(c) for c in src + dst)
     list_budget, part_budget = 256 << 10, 4 << 20
@@ -135,7 +188,7 @@ def test_wave_splitting_does_not_change_a_byte(pairs64):
     h._set_budget(list_budget, part_budget)
     try:
         split = tp.correspondences_batch(src, dst, 2 * vox, 5 * vox, return_features=True, return_normals=True)
-        matched = tp.match_features_batch(out[1][0], out[1][1])  # waves of pairs in the matching-only call
+        matched = tp.match_features_batch(out[1][0], out[1][1])  # waves of searches in the matching-only call
     finally:
         h._set_budget(None, None)
     assert same_bytes(split, out)

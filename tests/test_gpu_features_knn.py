@@ -147,6 +147,9 @@ def config5():
 
 
 def test_k1_mutual_equals_the_existing_matcher(config5):
+    """The matcher's searches are k-NN searches with k = 1 (features.hip, run_match), so this compares two routes
+    through one kernel: the host bookkeeping of the cross check against the device-side mutual filter.  It does not pin
+    the matcher's searches independently; test_gpu_features_batch.test_matcher_edge_sizes_equal_the_oracle does."""
     _, _, _, fa, fb = config5
     old = tp.match_features_batch([fa, fb], [fb, fa], use_crosscheck=True)
     new = tp.match_features_knn_batch([fa, fb], [fb, fa], 1, mutual=True)
