@@ -59,7 +59,15 @@ def read_ply_xyz(path):
         return np.stack([data["x"], data["y"], data["z"]], axis=1).astype(np.float32)
 
 
-def run_batch(A, B, vox, K, icp_iterations, knn=0, mutual=True, tuple_scale=0.0, tuple_seed=0):
+def parse_outliers(text):
+    """--remove-outliers NB,RATIO -> (nb_neighbors, std_ratio), or None when the option is absent."""
+    if not text:
+        return None
+    nb, ratio = text.split(",")
+    return int(nb), float(ratio)
+
+
+def run_batch(A, B, vox, K, icp_iterations, knn=0, mutual=True, tuple_scale=0.0, tuple_seed=0, outliers=None):
     """K perturbed copies of the pair (A, B) through the batched stages, one call per stage."""
     rng = np.random.default_rng(555)
     srcs, dsts = [], []
@@ -79,6 +87,11 @@ def run_batch(A, B, vox, K, icp_iterations, knn=0, mutual=True, tuple_scale=0.0,
     for timed in (False, True):  # the first pass creates the handles and grows the arenas
         t0 = time.perf_counter()
         down = tp.voxel_down_sample_batch(srcs + dsts, vox)
+        n_down = sum(map(len, down))
+        t1 = time.perf_counter()
+        if outliers:  # one call cleans all 2 K clouds
+            down = [c for c, _ in tp.remove_statistical_outlier_batch(down, outliers[0], outliers[1])]
+        t_clean = time.perf_counter() - t1
         t1 = time.perf_counter()
         sp, dp = down[:K], down[K:]
         if knn:
@@ -102,8 +115,11 @@ def run_batch(A, B, vox, K, icp_iterations, knn=0, mutual=True, tuple_scale=0.0,
         t4 = time.perf_counter()
     print("%d pairs: %d .. %d points after down-sampling, %d .. %d correspondences"
           % (K, min(map(len, down)), max(map(len, down)), min(map(len, corr)), max(map(len, corr))))
+    if outliers:
+        print("statistical outlier removal (nb_neighbors %d, std_ratio %g): %d points went from %d clouds, %.1f ms"
+              % (outliers[0], outliers[1], n_down - sum(map(len, down)), 2 * K, 1e3 * t_clean))
     print("down-sampling %.1f ms, front-end %.1f ms, registration %.1f ms, ICP %.1f ms (one call each, second pass)"
-          % (1e3 * (t1 - t0), 1e3 * (t2 - t1), 1e3 * (t3 - t2), 1e3 * (t4 - t3)))
+          % (1e3 * (t1 - t_clean - t0), 1e3 * (t2 - t1), 1e3 * (t3 - t2), 1e3 * (t4 - t3)))
     print("ICP fitness %.4f .. %.4f, rmse %.4f .. %.4f" % (min(r.fitness for r in icp), max(r.fitness for r in icp),
                                                          min(r.inlier_rmse for r in icp), max(r.inlier_rmse for r in icp)))
 
@@ -131,6 +147,9 @@ def main():
     ap.add_argument("--tuple-scale", type=float, default=0.0, metavar="S",
                     help="apply the matcher's tuple constraint with this factor (0: off, the reference uses 0.95)")
     ap.add_argument("--tuple-seed", type=int, default=0, metavar="N", help="seed of the tuple test (0: the clock)")
+    ap.add_argument("--remove-outliers", default="", metavar="NB,RATIO",
+                    help="clean both clouds after down-sampling with statistical outlier removal on the GPU "
+                         "(Open3D's remove_statistical_outlier(NB, RATIO), e.g. 20,2.0)")
     a = ap.parse_args()
     if a.batch > 0:
         if len(a.clouds) == 2:
@@ -138,7 +157,8 @@ def main():
         else:
             c5 = np.load(os.path.join(ROOT, "tests", "golden", "config5_clouds.npz"))
             A, B, a.voxel = c5["cloud_bin_0"].astype(np.float64), c5["cloud_bin_4"].astype(np.float64), float(c5["voxel_size"])
-        return run_batch(A, B, a.voxel, a.batch, a.icp_iterations, a.knn, not a.no_mutual, a.tuple_scale, a.tuple_seed)
+        return run_batch(A, B, a.voxel, a.batch, a.icp_iterations, a.knn, not a.no_mutual, a.tuple_scale, a.tuple_seed,
+                         parse_outliers(a.remove_outliers))
     t_ds = None
     if len(a.clouds) == 2:
         raw = [read_ply_xyz(c).astype(np.float64) for c in a.clouds]
@@ -151,6 +171,14 @@ def main():
         c5 = np.load(os.path.join(ROOT, "tests", "golden", "config5_clouds.npz"))
         A, B, a.voxel = c5["cloud_bin_0"], c5["cloud_bin_4"], float(c5["voxel_size"])
     vox = a.voxel
+    outliers = parse_outliers(a.remove_outliers)
+    if outliers:
+        t = time.perf_counter()
+        (A2, ia), (B2, ib) = tp.remove_statistical_outlier_batch([A, B], outliers[0], outliers[1])
+        print("statistical outlier removal (nb_neighbors %d, std_ratio %g): %d / %d points went, %d / %d stay (%.1f ms)"
+              % (outliers[0], outliers[1], len(A) - len(ia), len(B) - len(ib), len(ia), len(ib),
+                 1e3 * (time.perf_counter() - t)))
+        A, B = A2.astype(A.dtype), B2.astype(B.dtype)
     t0 = time.perf_counter()
     est = tp.FPFHEstimation()
     fa = est.computeFPFHFeatures(A, 2 * vox, 5 * vox)   # helpers.py:9-18: radii 2 and 5 voxels

@@ -649,6 +649,59 @@ TEASER_HIP_API int32_t teaser_hip_icp_covariances_batch(teaser_hip_icp* icp, int
                                                         const double* radius, const int32_t* max_nn,
                                                         const double* epsilon, double* const* out);
 
+/* Self k-NN (no radius), on the ICP handle: a batch of clouds (n x 3 doubles each) and a k in
+ * [1, TEASER_HIP_ICP_KNN_MAX] per cloud (TEASER_HIP_ICP_KNN_MAX = 100, the same number as TEASER_HIP_ICP_COV_MAX_NN).
+ * Per point i: the points j of the SAME cloud, i itself included, in ascending (d2, j), d2 = ((dx dx + dy dy) + dz dz),
+ * dx = P[i].x - P[j].x (the expression of the covariance contract, never contracted); the first m = min(k, n) of them
+ * are written.  idx_out[b]: n x k int32, unused slots -1; d2_out (NULL, or per cloud NULL or) n x k doubles, unused
+ * slots +inf.  Copies of a point tie on d2 = 0 and come in index order (slot 0 of point i is i only when no copy of it
+ * has a smaller index).  Deterministic: the same bits for a cloud alone, inside any batch and run after run; the result
+ * does not depend on which search route served a point (a hash grid searched ring by ring, or a scan of the whole cloud
+ * for the queries still open after "knn_ring_cap" rings: DESIGN.md section 17).  Empty clouds are legal.
+ * TEASER_HIP_ERR_BAD_ARG (argument and cloud named): non-finite points, k outside its range, NULL where n > 0. */
+#define TEASER_HIP_ICP_KNN_MAX 100
+TEASER_HIP_API int32_t teaser_hip_icp_self_knn_batch(teaser_hip_icp* icp, int32_t batch, const double* const* points,
+                                                     const int32_t* n, const int32_t* k, int32_t* const* idx_out,
+                                                     double* const* d2_out);
+/* Outlier removal: statistical (Open3D's remove_statistical_outlier), on the ICP handle.  Per cloud, with
+ * nb_neighbors in [1, TEASER_HIP_ICP_KNN_MAX] and std_ratio finite and > 0:
+ *   avg[i]    = (sum of sqrt(d2) over point i's m = min(nb_neighbors, n) nearest of self k-NN, the point itself
+ *               included -- its 0 comes first --, added one term at a time in ascending (d2, j) from 0.0) / m
+ *   valid     = n
+ *   mean      = (SUM of avg[i] over the points with avg[i] > 0) / valid
+ *   std       = sqrt((SUM of (avg[i] - mean)^2 over the same points) / (valid - 1))
+ *   threshold = mean + std_ratio std
+ *   SUM:        inside each block of 256 consecutive indices (0..255, 256..511, ...) the terms are added in ascending i
+ *               from 0.0; then the block sums are added in ascending block order from 0.0
+ *   kept:       point i is kept iff avg[i] > 0 and avg[i] < threshold.
+ * What follows from the rule (nothing is special-cased): n = 1 keeps nothing (avg = 0; std = 0 / 0); nb_neighbors = 1
+ * keeps nothing (every avg is 0); a point whose nb_neighbors nearest are all copies of itself has avg = 0 and is dropped,
+ * and does not enter the sums although it counts in valid.
+ * keep_out[b]: n bytes (0 / 1); n_kept_out[b]: int32; avg_out (NULL, or per cloud NULL or) n doubles; stats_out: NULL or
+ * 3 doubles per cloud (mean, std, threshold; NaN for an empty cloud, which is legal and keeps nothing).  The mask is the
+ * result: the host compacts nothing.  Deterministic like self k-NN.  TEASER_HIP_ERR_BAD_ARG (argument and cloud named):
+ * non-finite points, nb_neighbors outside its range, a std_ratio that is not finite and > 0, NULL where n > 0. */
+TEASER_HIP_API int32_t teaser_hip_icp_remove_statistical_outliers_batch(
+    teaser_hip_icp* icp, int32_t batch, const double* const* points, const int32_t* n, const int32_t* nb_neighbors,
+    const double* std_ratio, uint8_t* const* keep_out, int32_t* n_kept_out, double* const* avg_out, double* stats_out);
+/* Outlier removal: radius (Open3D's remove_radius_outlier), on the ICP handle.  Per cloud, with nb_points >= 1 and a
+ * radius that is, like its square, finite and > 0: count[i] = the number of j, i itself included, with
+ * d2 < radius radius (d2 as above; the comparison of the covariance contract: a point at exactly the radius does not
+ * count); point i is kept iff count[i] > nb_points.  keep_out / n_kept_out as above; count_out (NULL, or per cloud NULL
+ * or) n int32.  TEASER_HIP_ERR_BAD_ARG as above, with radius and nb_points in place of std_ratio and nb_neighbors. */
+TEASER_HIP_API int32_t teaser_hip_icp_remove_radius_outliers_batch(teaser_hip_icp* icp, int32_t batch,
+                                                                   const double* const* points, const int32_t* n,
+                                                                   const int32_t* nb_points, const double* radius,
+                                                                   uint8_t* const* keep_out, int32_t* n_kept_out,
+                                                                   int32_t* const* count_out);
+/* Options of an ICP handle (none changes a result).  "knn_ring_cap" (0 .. 16, default 4): the number of rings self
+ * k-NN and statistical removal search on the grid before a query goes to the whole-cloud scan; 0 sends every query
+ * there.  "knn_fallbacks" (read-only): how many queries of the handle's last self k-NN or statistical-removal call the
+ * whole-cloud scan served.  An unknown name, a value outside the range or a write to a read-only option:
+ * TEASER_HIP_ERR_BAD_ARG, from both calls with teaser_hip_icp_last_error naming the option. */
+TEASER_HIP_API int32_t teaser_hip_icp_set_option(teaser_hip_icp* icp, const char* name, int64_t value);
+TEASER_HIP_API int32_t teaser_hip_icp_get_option(teaser_hip_icp* icp, const char* name, int64_t* value);
+
 /* Voxel down-sampling (the reference's 3DMatch tutorial, examples/teaser_python_fpfh_icp/example.py:19-20, runs
  * Open3D's pcd.voxel_down_sample(0.05) on the raw clouds): batched, with Open3D's arithmetic and a deterministic output
  * order, on its OWN handle (nothing is shared with teaser_hip_solver or teaser_hip_icp).

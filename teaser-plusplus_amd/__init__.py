@@ -134,6 +134,8 @@ EXPORTED_SYMBOLS = [
     "teaser_hip_icp_batch", "teaser_hip_icp_solve", "teaser_hip_icp_estimation_default", "teaser_hip_icp_batch_ex",
     "teaser_hip_icp_solve_ex", "teaser_hip_icp_batch_cov", "teaser_hip_icp_solve_cov",
     "teaser_hip_icp_covariances_batch",
+    "teaser_hip_icp_self_knn_batch", "teaser_hip_icp_remove_statistical_outliers_batch",
+    "teaser_hip_icp_remove_radius_outliers_batch", "teaser_hip_icp_set_option", "teaser_hip_icp_get_option",
     "teaser_hip_voxel_create", "teaser_hip_voxel_destroy", "teaser_hip_voxel_last_error",
     "teaser_hip_voxel_down_sample_batch", "teaser_hip_voxel_down_sample",
     "teaser_hip_features_create", "teaser_hip_features_destroy", "teaser_hip_features_last_error",
@@ -226,6 +228,8 @@ def lib():
                                            _dp, _dp, _u8p]
     from . import icp as _icp
     _icp.declare(L)
+    from . import outlier as _outlier
+    _outlier.declare(L)
     from . import voxel as _voxel
     _voxel.declare(L)
     from . import features as _features
@@ -1078,6 +1082,8 @@ from .icp import (CauchyLoss, GMLoss, HuberLoss, ICPConvergenceCriteria, L2Loss,
                   covariances_from_normals, estimate_covariances, estimate_covariances_batch,
                   registration_generalized_icp)
 from .voxel import voxel_down_sample, voxel_down_sample_batch  # noqa: E402
+from .outlier import (remove_radius_outlier, remove_radius_outlier_batch, remove_statistical_outlier,  # noqa: E402
+                      remove_statistical_outlier_batch, self_knn, self_knn_batch, get_icp_option, set_icp_option)
 from .features import (compute_fpfh_batch, correspondences_batch, match_features_batch,  # noqa: E402
                        knn_features, knn_features_batch, match_features_knn, match_features_knn_batch,
                        correspondences_knn, correspondences_knn_batch, tuple_test_batch)
@@ -1092,4 +1098,6 @@ __all__ = ["batched", "FPFHEstimation", "Matcher", "MultiDeviceSolver", "RobustR
            "correspondences_knn", "correspondences_knn_batch", "tuple_test_batch",
            "TransformationEstimationPointToPlane", "L2Loss", "HuberLoss", "CauchyLoss", "GMLoss", "TukeyLoss",
            "TransformationEstimationForGeneralizedICP", "registration_generalized_icp", "estimate_covariances",
-           "estimate_covariances_batch", "covariances_from_normals"]
+           "estimate_covariances_batch", "covariances_from_normals",
+           "remove_statistical_outlier", "remove_statistical_outlier_batch", "remove_radius_outlier",
+           "remove_radius_outlier_batch", "self_knn", "self_knn_batch", "get_icp_option", "set_icp_option"]

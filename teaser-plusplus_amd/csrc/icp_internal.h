@@ -14,6 +14,11 @@ constexpr int kIcpScanThreads = 1024;
 constexpr int kIcpCovBlock = 64;   // points per covariance block: one wave, one point per lane
 constexpr int kIcpCovMaxNN = 100;  // K of the contract: the largest max_nn of covariance estimation
 constexpr int kIcpCovSmallNN = 32; // capacity of the small instantiation's per-lane neighbour list
+constexpr int kIcpKnnMax = 100;    // the largest k of self k-NN and nb_neighbors of statistical outlier removal
+constexpr int kIcpKnnSmall = 32;   // capacity of the small instantiation's per-lane list
+constexpr int kIcpKnnRingCap = 4;  // default number of rings searched on the grid before the whole-cloud route
+constexpr int kIcpKnnRingCapMax = 16;
+constexpr int kIcpKnnScanBlocks = 2048;  // waves of the whole-cloud route (each loops over the worklist)
 
 // IcpDesc::method / IcpDesc::kernel: the values of teaser_icp_estimation_c (include/teaser_hip.h)
 enum { kIcpMethodPoint = 0, kIcpMethodPlane = 1, kIcpMethodGicp = 2 };
@@ -61,6 +66,16 @@ struct IcpCovDesc {
   double eps;         // the eigenvalue given to the normal direction
 };
 
+// One cloud of a self k-NN / outlier-removal call, beside its IcpDesc (the cloud is the descriptor's "target", as in
+// covariance estimation; blk_off / nblk count its blocks of kIcpCovBlock points, tblk_off its blocks of 256).
+struct IcpKnnDesc {
+  int32_t k;          // neighbours asked for (self k-NN: k; statistical removal: nb_neighbors; radius removal: nb_points)
+  int32_t ring_cap;   // rings 0 .. ring_cap - 1 are searched on the grid; 0: every query takes the whole-cloud route
+  int64_t out_off;    // first slot of this cloud in the packed n x k outputs (self k-NN)
+  double edge;        // h: the grid's cell edge is at least h (1 + 1e-6), the margin of set_grid
+  double ratio;       // std_ratio (statistical removal)
+};
+
 // Grid cell of one coordinate; host (descriptor set-up) and device (index build, search) run the same expression.
 __host__ __device__ inline int64_t icp_cell(double x, double origin, double inv_h) {
   double v = floor((x - origin) * inv_h);
@@ -87,6 +102,21 @@ void launch_icp_iteration(hipStream_t s, const IcpDesc* d_desc, IcpState* d_stat
 void launch_icp_covariances(hipStream_t s, const IcpDesc* d_desc, const IcpCovDesc* d_cov, const int32_t* d_blk_prob,
                             int n_blk, int max_nn, const double* d_q, const double* d_qs, const int32_t* d_qj,
                             const int32_t* d_bstart, double* d_out);
+// Self k-NN on the indexed clouds.  avg == nullptr: idx / d2 (n x k per cloud at IcpKnnDesc::out_off) are written;
+// otherwise avg[t_off + i] (statistical removal's mean distance).  work: 2 int32 per point; work_count: one int32,
+// cleared by the caller, holds the number of queries the whole-cloud route served when the launches have run.
+void launch_icp_self_knn(hipStream_t s, const IcpDesc* d_desc, const IcpKnnDesc* d_knn, const int32_t* d_blk_prob,
+                         int n_blk, int top_k, const double* d_q, const double* d_qs, const int32_t* d_qj,
+                         const int32_t* d_bstart, int32_t* d_idx, double* d_d2, double* d_avg, int32_t* d_work,
+                         int32_t* d_work_count);
+// mean, std, threshold (stats: 3 doubles per cloud) from avg, then the mask and the kept count (cleared by the caller)
+void launch_icp_statistical(hipStream_t s, const IcpDesc* d_desc, const IcpKnnDesc* d_knn,
+                            const int32_t* d_tblk_prob, int n_tblk, int batch, const double* d_avg,
+                            double* d_partials, double* d_stats, uint8_t* d_keep, int32_t* d_kept);
+// count of points with d2 < r2 (27 cells of the grid built for r), the mask and the kept count (cleared by the caller)
+void launch_icp_radius_count(hipStream_t s, const IcpDesc* d_desc, const IcpKnnDesc* d_knn,
+                             const int32_t* d_tblk_prob, int n_tblk, const double* d_q, const double* d_qs,
+                             const int32_t* d_bstart, int32_t* d_count, uint8_t* d_keep, int32_t* d_kept);
 void launch_icp_live(hipStream_t s, const IcpState* d_state, int batch, int32_t* d_live);
 
 }  // namespace thip

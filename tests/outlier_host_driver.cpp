@@ -1,0 +1,292 @@
+// Host-only check of the self k-NN / outlier-removal entry points (tests/test_outlier_host.py): csrc/icp.hip compiled
+// by g++ against the HIP stand-in header (tests/hip_stub) with CPU stand-ins for the kernel launchers, built with
+// -fsanitize=address,undefined.  "Device" buffers are host allocations of exactly the size the host code asked for, so
+// a descriptor, an output layout or a worklist that is sized or addressed wrongly is an AddressSanitizer report; the
+// results are compared bit for bit with the numbers of tests/outlier_reference.py, read from a text file.
+//   outlier_host_driver CASES.txt    exit code 0: every case equal and every refusal refused
+// TEST INFRASTRUCTURE ONLY.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cmath>
+#include <cstdio>
+#include <cstring>
+#include <string>
+#include <utility>
+#include <vector>
+
+inline hipError_t hipHostMalloc(void** p, size_t n) { return hipHostMalloc(p, n, 0u); }
+thread_local stub_dim3_ blockIdx, threadIdx, gridDim, blockDim;
+
+#include "../teaser-plusplus_amd/csrc/icp.hip"
+
+namespace thip {
+
+void launch_icp_index(hipStream_t, const IcpDesc*, const int32_t*, int, int, const double*, int32_t*, int32_t*,
+                      int32_t*, int32_t*, double*, int32_t*) {}  // the stand-ins below search the points themselves
+void launch_icp_iteration(hipStream_t, const IcpDesc*, IcpState*, const int32_t*, int, int, double*, const double*,
+                          const int32_t*, const int32_t*, const double*, const double*, const double*, int, int32_t*,
+                          double*) {}
+void launch_icp_covariances(hipStream_t, const IcpDesc*, const IcpCovDesc*, const int32_t*, int, int, const double*,
+                            const double*, const int32_t*, const int32_t*, double*) {}
+void launch_icp_live(hipStream_t, const IcpState*, int, int32_t* live) { *live = 0; }
+
+static double dist2(const double* a, const double* b) {
+  const double e0 = a[0] - b[0], e1 = a[1] - b[1], e2 = a[2] - b[2];
+  return (e0 * e0 + e1 * e1) + e2 * e2;
+}
+
+static void serve(const IcpDesc& d, const IcpKnnDesc& kd, int64_t i, const double* q, int32_t* idx, double* d2,
+                  double* avg) {
+  std::vector<std::pair<double, int32_t>> c;
+  for (int32_t j = 0; j < d.n_t; ++j) c.emplace_back(dist2(q + 3 * (d.t_off + i), q + 3 * (d.t_off + j)), j);
+  std::sort(c.begin(), c.end());
+  const int m = std::min(kd.k, d.n_t);
+  if (avg) {
+    double acc = 0.0;
+    for (int t = 0; t < m; ++t) acc += sqrt(c[(size_t)t].first);
+    avg[d.t_off + i] = acc / (double)m;
+    return;
+  }
+  for (int t = 0; t < kd.k; ++t) {
+    idx[kd.out_off + i * kd.k + t] = t < m ? c[(size_t)t].second : -1;
+    d2[kd.out_off + i * kd.k + t] = t < m ? c[(size_t)t].first : INFINITY;
+  }
+}
+
+// Every block of the launch is visited through the block map, as the kernel does; every third query (all of them when
+// the ring cap is 0) goes through the worklist and is served from it afterwards.
+void launch_icp_self_knn(hipStream_t, const IcpDesc* desc, const IcpKnnDesc* knn, const int32_t* blk_prob, int n_blk,
+                         int top_k, const double* q, const double*, const int32_t*, const int32_t*, int32_t* idx,
+                         double* d2, double* avg, int32_t* work, int32_t* work_count) {
+  for (int blk = 0; blk < n_blk; ++blk) {
+    const int p = blk_prob[blk];
+    const IcpDesc& d = desc[p];
+    for (int lane = 0; lane < kIcpCovBlock; ++lane) {
+      const int64_t i = (int64_t)(blk - d.blk_off) * kIcpCovBlock + lane;
+      if (i >= d.n_t) continue;
+      if (std::min(knn[p].k, d.n_t) > top_k) std::abort();  // the capacity the launcher would pick is too small
+      if (knn[p].ring_cap == 0 || i % 3 == 0) {
+        const int32_t w = (*work_count)++;
+        work[2 * (int64_t)w] = p;
+        work[2 * (int64_t)w + 1] = (int32_t)i;
+      } else {
+        serve(d, knn[p], i, q, idx, d2, avg);
+      }
+    }
+  }
+  for (int32_t w = 0; w < *work_count; ++w)
+    serve(desc[work[2 * (int64_t)w]], knn[work[2 * (int64_t)w]], work[2 * (int64_t)w + 1], q, idx, d2, avg);
+}
+
+void launch_icp_statistical(hipStream_t, const IcpDesc* desc, const IcpKnnDesc* knn, const int32_t* tblk_prob,
+                            int n_tblk, int batch, const double* avg, double* partials, double* stats, uint8_t* keep,
+                            int32_t* kept) {
+  for (int pass = 0; pass < 2; ++pass) {
+    for (int t = 0; t < n_tblk; ++t) {
+      const IcpDesc& d = desc[tblk_prob[t]];
+      const int64_t lo = (int64_t)(t - d.tblk_off) * 256, hi = std::min<int64_t>(lo + 256, d.n_t);
+      double s = 0.0;
+      for (int64_t i = lo; i < hi; ++i) {
+        const double a = avg[d.t_off + i];
+        if (!(a > 0.0)) continue;
+        const double e = a - stats[3 * tblk_prob[t]];
+        s += pass ? e * e : a;
+      }
+      partials[t] = s;
+    }
+    for (int p = 0; p < batch; ++p) {
+      const IcpDesc& d = desc[p];
+      if (d.n_t == 0) continue;
+      double s = 0.0;
+      for (int b = 0; b < (d.n_t + 255) / 256; ++b) s += partials[d.tblk_off + b];
+      if (pass == 0) {
+        stats[3 * p] = s / (double)d.n_t;
+      } else {
+        stats[3 * p + 1] = sqrt(s / ((double)d.n_t - 1.0));
+        stats[3 * p + 2] = stats[3 * p] + knn[p].ratio * stats[3 * p + 1];
+      }
+    }
+  }
+  for (int p = 0; p < batch; ++p)
+    for (int64_t i = 0; i < desc[p].n_t; ++i) {
+      const double a = avg[desc[p].t_off + i];
+      const bool k = a > 0.0 && a < stats[3 * p + 2];
+      keep[desc[p].t_off + i] = k;
+      kept[p] += k;
+    }
+}
+
+void launch_icp_radius_count(hipStream_t, const IcpDesc* desc, const IcpKnnDesc* knn, const int32_t* tblk_prob,
+                             int n_tblk, const double* q, const double*, const int32_t*, int32_t* count, uint8_t* keep,
+                             int32_t* kept) {
+  for (int t = 0; t < n_tblk; ++t) {
+    const int p = tblk_prob[t];
+    const IcpDesc& d = desc[p];
+    const int64_t lo = (int64_t)(t - d.tblk_off) * 256, hi = std::min<int64_t>(lo + 256, d.n_t);
+    for (int64_t i = lo; i < hi; ++i) {
+      int32_t c = 0;
+      for (int64_t j = 0; j < d.n_t; ++j) c += dist2(q + 3 * (d.t_off + i), q + 3 * (d.t_off + j)) < d.r2;
+      count[d.t_off + i] = c;
+      keep[d.t_off + i] = c > knn[p].k;
+      kept[p] += c > knn[p].k;
+    }
+  }
+}
+
+}  // namespace thip
+
+struct Case {
+  int n = 0, k = 0, nb = 0;
+  double ratio = 0, radius = 0;
+  std::vector<double> pts, d2, avg, stats;
+  std::vector<int32_t> idx, count;
+  std::vector<uint8_t> keep_s, keep_r;
+};
+
+static bool same(const std::vector<double>& a, const std::vector<double>& b) {
+  if (a.size() != b.size()) return false;
+  for (size_t i = 0; i < a.size(); ++i)
+    if (!(std::isnan(a[i]) && std::isnan(b[i])) && memcmp(&a[i], &b[i], 8) != 0) return false;
+  return true;
+}
+
+static int g_bad = 0;
+static void expect(bool ok, const char* what, int c) {
+  if (!ok) {
+    std::fprintf(stderr, "case %d: %s\n", c, what);
+    ++g_bad;
+  }
+}
+
+int main(int argc, char** argv) {
+  if (argc != 2) return 2;
+  FILE* f = std::fopen(argv[1], "r");
+  if (!f) return 2;
+  int n_cases = 0;
+  if (std::fscanf(f, "%d", &n_cases) != 1) return 2;
+  std::vector<Case> cases((size_t)n_cases);
+  auto doubles = [&](std::vector<double>& v, size_t cnt) {
+    v.resize(cnt);
+    for (double& x : v) {
+      char tok[64];
+      if (std::fscanf(f, "%63s", tok) != 1) std::exit(2);
+      x = std::strtod(tok, nullptr);  // hexadecimal floats, "nan", "inf"
+    }
+  };
+  auto ints = [&](auto& v, size_t cnt) {
+    v.resize(cnt);
+    for (auto& x : v) {
+      int t;
+      if (std::fscanf(f, "%d", &t) != 1) std::exit(2);
+      x = (typename std::remove_reference<decltype(x)>::type)t;
+    }
+  };
+  for (Case& c : cases) {
+    char r1[64], r2[64];
+    if (std::fscanf(f, "%d %d %63s %d %63s", &c.n, &c.k, r1, &c.nb, r2) != 5) return 2;
+    c.ratio = std::strtod(r1, nullptr);
+    c.radius = std::strtod(r2, nullptr);
+    const size_t n = (size_t)c.n;
+    doubles(c.pts, 3 * n);
+    ints(c.idx, n * (size_t)c.k);
+    doubles(c.d2, n * (size_t)c.k);
+    doubles(c.avg, n);
+    doubles(c.stats, 3);
+    ints(c.keep_s, n);
+    ints(c.count, n);
+    ints(c.keep_r, n);
+  }
+  std::fclose(f);
+
+  teaser_hip_icp* h = nullptr;
+  if (teaser_hip_icp_create(0, &h) != TEASER_HIP_OK) return 2;
+  const int B = n_cases;
+  for (int ring_cap : {4, 0}) {
+    if (teaser_hip_icp_set_option(h, "knn_ring_cap", ring_cap) != TEASER_HIP_OK) return 2;
+    for (int pass = 0; pass < 2; ++pass) {  // pass 0: every case alone; pass 1: all of them in one batch
+      for (int lo = 0; lo < B; lo += pass ? B : 1) {
+        const int b = pass ? B : 1;
+        std::vector<const double*> pp((size_t)b);
+        std::vector<int32_t> n((size_t)b), k((size_t)b), nb((size_t)b), kept_s((size_t)b), kept_r((size_t)b);
+        std::vector<double> ratio((size_t)b), radius((size_t)b), stats(3 * (size_t)b);
+        std::vector<std::vector<int32_t>> idx((size_t)b), count((size_t)b);
+        std::vector<std::vector<double>> d2((size_t)b), avg((size_t)b);
+        std::vector<std::vector<uint8_t>> ks((size_t)b), kr((size_t)b);
+        std::vector<int32_t*> pi((size_t)b), pc((size_t)b);
+        std::vector<double*> pd((size_t)b), pa((size_t)b);
+        std::vector<uint8_t*> pks((size_t)b), pkr((size_t)b);
+        for (int c = 0; c < b; ++c) {
+          const Case& cs = cases[(size_t)(lo + c)];
+          const size_t m = (size_t)cs.n;
+          pp[c] = m ? cs.pts.data() : nullptr;  // an empty cloud passes NULL everywhere
+          n[c] = cs.n, k[c] = cs.k, nb[c] = cs.nb, ratio[c] = cs.ratio, radius[c] = cs.radius;
+          idx[c].resize(m * (size_t)cs.k), d2[c].resize(m * (size_t)cs.k), avg[c].resize(m), count[c].resize(m);
+          ks[c].resize(m), kr[c].resize(m);
+          pi[c] = m ? idx[c].data() : nullptr, pd[c] = m ? d2[c].data() : nullptr, pa[c] = m ? avg[c].data() : nullptr;
+          pc[c] = m ? count[c].data() : nullptr, pks[c] = m ? ks[c].data() : nullptr, pkr[c] = m ? kr[c].data() : nullptr;
+        }
+        int64_t fell = -1, total = 0;
+        for (int c = 0; c < b; ++c) total += n[c];
+        expect(teaser_hip_icp_self_knn_batch(h, b, pp.data(), n.data(), k.data(), pi.data(), pd.data()) == 0, "knn rc", lo);
+        teaser_hip_icp_get_option(h, "knn_fallbacks", &fell);
+        expect(ring_cap == 0 ? fell == total : fell <= total, "knn_fallbacks", lo);
+        expect(teaser_hip_icp_remove_statistical_outliers_batch(h, b, pp.data(), n.data(), k.data(), ratio.data(),
+                                                                pks.data(), kept_s.data(), pa.data(), stats.data()) == 0,
+               "statistical rc", lo);
+        expect(teaser_hip_icp_remove_radius_outliers_batch(h, b, pp.data(), n.data(), nb.data(), radius.data(),
+                                                           pkr.data(), kept_r.data(), pc.data()) == 0,
+               "radius rc", lo);
+        for (int c = 0; c < b; ++c) {
+          const Case& cs = cases[(size_t)(lo + c)];
+          expect(idx[c] == cs.idx, "idx", lo + c);
+          expect(same(d2[c], cs.d2), "d2", lo + c);
+          expect(same(avg[c], cs.avg), "avg", lo + c);
+          expect(same(std::vector<double>(stats.begin() + 3 * c, stats.begin() + 3 * c + 3), cs.stats), "stats", lo + c);
+          expect(ks[c] == cs.keep_s, "statistical mask", lo + c);
+          expect(kept_s[c] == (int32_t)std::count(cs.keep_s.begin(), cs.keep_s.end(), 1), "statistical count", lo + c);
+          expect(count[c] == cs.count && kr[c] == cs.keep_r, "radius", lo + c);
+          expect(kept_r[c] == (int32_t)std::count(cs.keep_r.begin(), cs.keep_r.end(), 1), "radius count", lo + c);
+        }
+      }
+    }
+  }
+  // refusals: BAD_ARG, the argument and the cloud named, and the handle still works
+  {
+    const Case& cs = cases[0];
+    const double* pp[2] = {cs.pts.data(), cs.pts.data()};
+    std::vector<double> bad = cs.pts;
+    bad[4] = NAN;
+    const double* pbad[2] = {cs.pts.data(), bad.data()};
+    const int32_t n[2] = {cs.n, cs.n};
+    std::vector<uint8_t> k0((size_t)cs.n), k1((size_t)cs.n);
+    uint8_t* pk[2] = {k0.data(), k1.data()};
+    std::vector<int32_t> i0((size_t)cs.n * 100), i1((size_t)cs.n * 100);
+    int32_t* pi[2] = {i0.data(), i1.data()};
+    int32_t kept[2];
+    auto refused = [&](int32_t rc, const char* w1, const char* w2) {
+      const std::string msg = teaser_hip_icp_last_error(h);
+      expect(rc == TEASER_HIP_ERR_BAD_ARG && msg.find(w1) != std::string::npos && msg.find(w2) != std::string::npos,
+             (std::string("refusal: ") + w1 + " / " + msg).c_str(), -1);
+    };
+    const int32_t k_ok[2] = {5, 5}, k_lo[2] = {5, 0}, k_hi[2] = {101, 5};
+    const double r_ok[2] = {2.0, 2.0}, r_zero[2] = {2.0, 0.0}, r_nan[2] = {NAN, 2.0}, r_big[2] = {0.1, 1e200};
+    refused(teaser_hip_icp_remove_statistical_outliers_batch(h, 2, pbad, n, k_ok, r_ok, pk, kept, nullptr, nullptr), "points", "problem 1");
+    refused(teaser_hip_icp_remove_statistical_outliers_batch(h, 2, pp, n, k_lo, r_ok, pk, kept, nullptr, nullptr), "nb_neighbors", "problem 1");
+    refused(teaser_hip_icp_remove_statistical_outliers_batch(h, 2, pp, n, k_hi, r_ok, pk, kept, nullptr, nullptr), "nb_neighbors", "problem 0");
+    refused(teaser_hip_icp_remove_statistical_outliers_batch(h, 2, pp, n, k_ok, r_zero, pk, kept, nullptr, nullptr), "std_ratio", "problem 1");
+    refused(teaser_hip_icp_remove_statistical_outliers_batch(h, 2, pp, n, k_ok, r_nan, pk, kept, nullptr, nullptr), "std_ratio", "problem 0");
+    refused(teaser_hip_icp_remove_statistical_outliers_batch(h, 2, pp, n, k_ok, r_ok, nullptr, kept, nullptr, nullptr), "keep_out", "problem 0");
+    refused(teaser_hip_icp_remove_radius_outliers_batch(h, 2, pp, n, k_ok, r_zero, pk, kept, nullptr), "radius", "problem 1");
+    refused(teaser_hip_icp_remove_radius_outliers_batch(h, 2, pp, n, k_ok, r_big, pk, kept, nullptr), "radius", "problem 1");
+    refused(teaser_hip_icp_remove_radius_outliers_batch(h, 2, pp, n, k_lo, r_ok, pk, kept, nullptr), "nb_points", "problem 1");
+    refused(teaser_hip_icp_self_knn_batch(h, 2, pp, n, k_hi, pi, nullptr), "k must lie", "problem 0");
+    refused(teaser_hip_icp_self_knn_batch(h, 2, pbad, n, k_ok, pi, nullptr), "non-finite", "problem 1");
+    refused(teaser_hip_icp_self_knn_batch(h, 2, pp, n, k_ok, nullptr, nullptr), "idx_out", "problem 0");
+    expect(teaser_hip_icp_set_option(h, "knn_ring_cap", 17) == TEASER_HIP_ERR_BAD_ARG, "ring cap range", -1);
+    expect(teaser_hip_icp_self_knn_batch(h, 2, pp, n, k_ok, pi, nullptr) == TEASER_HIP_OK, "the handle works afterwards", -1);
+  }
+  teaser_hip_icp_destroy(h);
+  std::printf("cases %d  mismatches %d\n", n_cases, g_bad);
+  return g_bad ? 1 : 0;
+}
