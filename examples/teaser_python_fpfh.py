@@ -7,6 +7,7 @@ on the MI355X.  Usage:
 
     python examples/teaser_python_fpfh.py [src.ply dst.ply] [--voxel 0.05] [--certify] [--icp [--icp-iterations 100]]
                                           [--icp-plane [--icp-kernel tukey --icp-kernel-k K]]
+                                          [--icp-plane-normals hybrid:R:K|knn:K]
                                           [--icp-gicp [--gicp-radius R --gicp-max-nn K]] [--batch K]
                                           [--knn K [--no-mutual]] [--tuple-scale S [--tuple-seed N]]
 
@@ -133,6 +134,9 @@ def main():
     ap.add_argument("--icp-iterations", type=int, default=100)
     ap.add_argument("--icp-plane", action="store_true",
                     help="refine the TEASER++ pose with point-to-plane ICP on the FPFH stage's target normals")
+    ap.add_argument("--icp-plane-normals", default=None, metavar="hybrid:R:K|knn:K",
+                    help="refine with point-to-plane ICP on target normals estimated from the target cloud on the "
+                         "GPU: the K nearest neighbours inside radius R, or the K nearest")
     ap.add_argument("--icp-gicp", action="store_true",
                     help="refine with Generalized ICP instead, on covariances estimated on the GPU from both clouds")
     ap.add_argument("--gicp-radius", type=float, default=None, help="covariance search radius (default: 2 voxels)")
@@ -243,6 +247,31 @@ def main():
                                   target_normals=N)
         t4 = time.perf_counter()
         print("point-to-plane, kernel %r" % (kernel,))
+        print("ICP before: fitness %.6f rmse %.6f" % (before.fitness, before.inlier_rmse))
+        print("ICP after:  fitness %.6f rmse %.6f iterations %d (%.2f ms)" % (icp.fitness, icp.inlier_rmse,
+                                                                              icp.iterations, 1e3 * (t4 - t3)))
+        print("T_icp =\n%s" % icp.transformation)
+    if a.icp_plane_normals:
+        T = np.eye(4)
+        T[:3, :3], T[:3, 3] = sol.rotation, sol.translation
+        P, Q = np.asarray(A, dtype=np.float64), np.asarray(B, dtype=np.float64)
+        kind, *rest = a.icp_plane_normals.split(":")
+        if kind == "hybrid" and len(rest) == 2:
+            search = tp.KDTreeSearchParamHybrid(float(rest[0]), int(rest[1]))
+        elif kind == "knn" and len(rest) == 1:
+            search = tp.KDTreeSearchParamKNN(int(rest[0]))
+        else:
+            raise SystemExit("--icp-plane-normals takes hybrid:R:K or knn:K")
+        k = a.icp_kernel_k if a.icp_kernel_k is not None else vox
+        kernel = dict(l2=tp.L2Loss, huber=lambda: tp.HuberLoss(k), cauchy=lambda: tp.CauchyLoss(k),
+                      gm=lambda: tp.GMLoss(k), tukey=lambda: tp.TukeyLoss(k))[a.icp_kernel]()
+        crit = tp.ICPConvergenceCriteria(max_iteration=a.icp_iterations)
+        before = tp.registration_icp(P, Q, vox, T, criteria=tp.ICPConvergenceCriteria(max_iteration=0))
+        t3 = time.perf_counter()
+        icp = tp.registration_icp(P, Q, vox, T, tp.TransformationEstimationPointToPlane(kernel), crit,
+                                  target_normals=search)  # the normals are estimated on the device and stay there
+        t4 = time.perf_counter()
+        print("point-to-plane on self-estimated normals (%r), kernel %r" % (search, kernel))
         print("ICP before: fitness %.6f rmse %.6f" % (before.fitness, before.inlier_rmse))
         print("ICP after:  fitness %.6f rmse %.6f iterations %d (%.2f ms)" % (icp.fitness, icp.inlier_rmse,
                                                                               icp.iterations, 1e3 * (t4 - t3)))

@@ -53,11 +53,51 @@ inline RobustKernel CauchyLoss(double k = 1.0) { return RobustKernel{2, k}; }
 inline RobustKernel GMLoss(double k = 1.0) { return RobustKernel{3, k}; }
 inline RobustKernel TukeyLoss(double k = 1.0) { return RobustKernel{4, k}; }
 
-// Open3D's TransformationEstimationPointToPlane(kernel); the target normals are an argument of registrationICP.
+// The neighbourhood of normal estimation (include/teaser_hip.h, "Normal estimation"): Open3D's
+// KDTreeSearchParamHybrid(radius, max_nn) or KDTreeSearchParamKNN(knn), optionally with an orientation --
+// .towards(point) (orient_normals_towards_camera_location) or .along(direction)
+// (orient_normals_to_align_with_direction).  A default-constructed NormalSearch means "none" (max_nn = 0).
+struct NormalSearch {
+  teaser_icp_normal_search_c rec{};  // max_nn = 0: none
+  static NormalSearch Hybrid(double radius, int max_nn = 30) {
+    NormalSearch s;
+    s.rec.search = 0, s.rec.max_nn = max_nn, s.rec.radius = radius;
+    return s;
+  }
+  static NormalSearch KNN(int k = 30) {
+    NormalSearch s;
+    s.rec.search = 1, s.rec.max_nn = k;
+    return s;
+  }
+  NormalSearch towards(double x, double y, double z) const { return oriented(1, x, y, z); }
+  NormalSearch along(double x, double y, double z) const { return oriented(2, x, y, z); }
+  bool given() const { return rec.max_nn != 0; }
+
+ private:
+  NormalSearch oriented(int32_t orient, double x, double y, double z) const {
+    NormalSearch s = *this;
+    s.rec.orient = orient, s.rec.ref[0] = x, s.rec.ref[1] = y, s.rec.ref[2] = z;
+    return s;
+  }
+};
+
+// What estimateNormals returns: one unit normal per point (column), and what was asked for of the raw sample
+// covariances (9 doubles per point, row-major) and the ascending eigenvalues (3 per point).
+struct Normals {
+  Matrix3X normals;
+  std::vector<double> covariances;
+  std::vector<double> eigenvalues;
+};
+
+// Open3D's TransformationEstimationPointToPlane(kernel).  The target normals are an argument of registrationICP, or,
+// with a normal_search, estimated from the target on the device (the registrationICP overloads without dst_normals).
 struct TransformationEstimationPointToPlane {
   RobustKernel kernel;
+  NormalSearch normal_search;
   TransformationEstimationPointToPlane() = default;
   explicit TransformationEstimationPointToPlane(const RobustKernel& k) : kernel(k) {}
+  explicit TransformationEstimationPointToPlane(const NormalSearch& s) : normal_search(s) {}
+  TransformationEstimationPointToPlane(const RobustKernel& k, const NormalSearch& s) : kernel(k), normal_search(s) {}
 };
 
 // Open3D's TransformationEstimationForGeneralizedICP, L2 only (include/teaser_hip.h says why).  The covariances of both
@@ -205,6 +245,67 @@ class ICP {
     return run(src, dst, max_correspondence_distance, init, criteria, pn.data(), est.data());
   }
 
+  // Point-to-plane with target normals the library estimates itself: every estimation[b] carries a normal_search
+  // (teaser_hip_icp_batch_auto: the normals go from the normals kernel to the correspondence pass on the device).
+  std::vector<ICPResult> registrationICPBatch(const std::vector<Matrix3X>& src, const std::vector<Matrix3X>& dst,
+                                              const std::vector<double>& max_correspondence_distance,
+                                              const std::vector<Matrix4>& init,
+                                              const std::vector<TransformationEstimationPointToPlane>& estimation,
+                                              const std::vector<ICPConvergenceCriteria>& criteria) {
+    const size_t b = src.size();
+    if (dst.size() != b || estimation.size() != b)
+      throw std::invalid_argument("teaser::ICP: one entry per problem in every argument");
+    std::vector<teaser_icp_estimation_c> est(b);
+    std::vector<teaser_icp_normal_search_c> rec(b);
+    for (size_t k = 0; k < b; ++k) {
+      est[k].method = 1;
+      est[k].kernel = estimation[k].kernel.kernel;
+      est[k].kernel_k = estimation[k].kernel.k;
+      rec[k] = estimation[k].normal_search.rec;
+    }
+    return run(src, dst, max_correspondence_distance, init, criteria, nullptr, est.data(), nullptr, nullptr, rec.data());
+  }
+
+  // Normals of many clouds in one launch sequence (include/teaser_hip.h, "Normal estimation"); result c is identical
+  // to cloud c estimated alone.
+  std::vector<Normals> estimateNormalsBatch(const std::vector<Matrix3X>& clouds, const std::vector<NormalSearch>& search,
+                                            bool covariances = false, bool eigenvalues = false) {
+    const size_t b = clouds.size();
+    if (search.size() != b) throw std::invalid_argument("teaser::ICP: one entry per cloud in every argument");
+    std::vector<const double*> pp(b);
+    std::vector<int32_t> n(b);
+    std::vector<teaser_icp_normal_search_c> rec(b);
+    std::vector<Normals> out(b);
+    std::vector<double*> pn(b), pc(b), pe(b);
+    for (size_t c = 0; c < b; ++c) {
+      pp[c] = clouds[c].data();
+      n[c] = (int32_t)clouds[c].cols();
+      rec[c] = search[c].rec;
+      out[c].normals = Matrix3X(3, clouds[c].cols());
+      if (covariances) out[c].covariances.resize(9 * (size_t)n[c]);
+      if (eigenvalues) out[c].eigenvalues.resize(3 * (size_t)n[c]);
+      pn[c] = out[c].normals.data();
+      pc[c] = out[c].covariances.data();
+      pe[c] = out[c].eigenvalues.data();
+    }
+    const int32_t rc = teaser_hip_icp_normals_batch(h_, (int32_t)b, pp.data(), n.data(), rec.data(), pn.data(),
+                                                    covariances ? pc.data() : nullptr, eigenvalues ? pe.data() : nullptr);
+    if (rc != TEASER_HIP_OK)
+      throw ICPError(rc, "teaser::ICP: status " + std::to_string(rc) + ": " + teaser_hip_icp_last_error(h_));
+    return out;
+  }
+
+  Normals estimateNormals(const Matrix3X& cloud, const NormalSearch& search, bool covariances = false,
+                          bool eigenvalues = false) {
+    return std::move(estimateNormalsBatch({cloud}, {search}, covariances, eigenvalues)[0]);
+  }
+
+  ICPResult registrationICP(const Matrix3X& src, const Matrix3X& dst, double max_correspondence_distance,
+                            const Matrix4& init, const TransformationEstimationPointToPlane& estimation,
+                            const ICPConvergenceCriteria& criteria = ICPConvergenceCriteria()) {
+    return registrationICPBatch({src}, {dst}, {max_correspondence_distance}, {init}, {estimation}, {criteria})[0];
+  }
+
   ICPResult registrationICP(const Matrix3X& src, const Matrix3X& dst, double max_correspondence_distance,
                             const Matrix4& init = Matrix4::Identity(),
                             const ICPConvergenceCriteria& criteria = ICPConvergenceCriteria()) {
@@ -232,7 +333,8 @@ class ICP {
                              const std::vector<double>& max_correspondence_distance,
                              const std::vector<Matrix4>& init, const std::vector<ICPConvergenceCriteria>& criteria,
                              const double* const* normals, const teaser_icp_estimation_c* est,
-                             const double* const* src_cov = nullptr, const double* const* dst_cov = nullptr) {
+                             const double* const* src_cov = nullptr, const double* const* dst_cov = nullptr,
+                             const teaser_icp_normal_search_c* normal_search = nullptr) {
     const size_t b = src.size();
     if (dst.size() != b || max_correspondence_distance.size() != b || init.size() != b || criteria.size() != b)
       throw std::invalid_argument("teaser::ICP: one entry per problem in every argument");
@@ -258,7 +360,11 @@ class ICP {
     }
     std::vector<teaser_icp_result_c> out(b);
     const int32_t rc =
-        src_cov ? teaser_hip_icp_batch_cov(h_, (int32_t)b, ps.data(), ns.data(), pd.data(), nd.data(), T.data(),
+        normal_search
+            ? teaser_hip_icp_batch_auto(h_, (int32_t)b, ps.data(), ns.data(), pd.data(), nd.data(), T.data(),
+                                        params.data(), out.data(), pc.data(), normals, est, src_cov, dst_cov,
+                                        normal_search)
+        : src_cov ? teaser_hip_icp_batch_cov(h_, (int32_t)b, ps.data(), ns.data(), pd.data(), nd.data(), T.data(),
                                            params.data(), out.data(), pc.data(), normals, est, src_cov, dst_cov)
         : est ? teaser_hip_icp_batch_ex(h_, (int32_t)b, ps.data(), ns.data(), pd.data(), nd.data(), T.data(),
                                       params.data(), out.data(), pc.data(), normals, est)
@@ -311,6 +417,21 @@ inline ICPResult registrationICP(const Matrix3X& src, const Matrix3X& dst, const
                                  const ICPConvergenceCriteria& criteria = ICPConvergenceCriteria()) {
   ICP icp;
   return icp.registrationICP(src, dst, src_cov, dst_cov, max_correspondence_distance, init, estimation, criteria);
+}
+
+// Open3D's estimate_normals (+ orient_normals_*), one cloud; creates a handle per call.
+inline Normals estimateNormals(const Matrix3X& cloud, const NormalSearch& search, bool covariances = false,
+                               bool eigenvalues = false) {
+  ICP icp;
+  return icp.estimateNormals(cloud, search, covariances, eigenvalues);
+}
+
+// Point-to-plane ICP that estimates the target normals itself (estimation.normal_search); creates a handle per call.
+inline ICPResult registrationICP(const Matrix3X& src, const Matrix3X& dst, double max_correspondence_distance,
+                                 const Matrix4& init, const TransformationEstimationPointToPlane& estimation,
+                                 const ICPConvergenceCriteria& criteria = ICPConvergenceCriteria()) {
+  ICP icp;
+  return icp.registrationICP(src, dst, max_correspondence_distance, init, estimation, criteria);
 }
 
 // Covariances of one cloud for Generalized ICP, estimated on the GPU; creates a handle per call.

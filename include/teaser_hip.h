@@ -649,6 +649,77 @@ TEASER_HIP_API int32_t teaser_hip_icp_covariances_batch(teaser_hip_icp* icp, int
                                                         const double* radius, const int32_t* max_nn,
                                                         const double* epsilon, double* const* out);
 
+/* Normal estimation (Open3D's estimate_normals with KDTreeSearchParamHybrid or KDTreeSearchParamKNN, plus
+ * estimate_covariances and the two orient_normals_* calls), on the ICP handle: a batch of clouds (n x 3 doubles each)
+ * with one search record per cloud.  Per point i:
+ *   neighbourhood, search 0 (hybrid): exactly the covariance contract's above -- d2 < radius radius, i itself
+ *                  included, the max_nn smallest by (d2, j).  m = their number.
+ *   neighbourhood, search 1 (k-NN):   the m = min(max_nn, n) first of self k-NN's order (d2, j) below; no radius.
+ *   m >= 3:        S1, S2, cov and the cyclic Jacobi are those of the covariance contract above, word for word.
+ *                  cov_out = that cov (the RAW sample covariance before the Jacobi), the full symmetric matrix, the
+ *                            lower triangle mirrored;
+ *                  eig_out = the three diagonal entries after the Jacobi, ascending;
+ *                  n^      = the column of V of the smallest diagonal entry (the first on a tie), divided by its length.
+ *   m < 3:         n^ = 0, cov_out = the zero matrix, eig_out = 0 (hybrid search, or k-NN search on a cloud with n < 3);
+ *                  the orientation step then fills the normal in.
+ *   orientation, applied last; it changes only the sign, or fills a zero normal:
+ *     orient 0:    the sign the Jacobi leaves: deterministic, without meaning.  A zero normal becomes (0, 0, 1).
+ *     orient 1:    n^ is negated when (n^x (ref - p)x + n^y (ref - p)y) + n^z (ref - p)z < 0.  A zero normal becomes
+ *                  (ref - p) / |ref - p|, |v| = sqrt((vx vx + vy vy) + vz vz), or (0, 0, 1) when that length is 0.
+ *     orient 2:    n^ is negated when (n^x refx + n^y refy) + n^z refz < 0.  A zero normal becomes ref as given.
+ *                  (The rules of Open3D's orient_normals_towards_camera_location and
+ *                  orient_normals_to_align_with_direction; bit parity with Open3D is not claimed.)
+ * Radius-only search (Open3D's KDTreeSearchParamRadius: no cap on the neighbours) is NOT offered: the sums are ordered
+ * sums over a bounded sorted list, and without a cap there is no such list.
+ * normals_out[b]: n[b] x 3 doubles.  cov_out: NULL, or per cloud NULL or n x 9 doubles.  eig_out: NULL, or per cloud NULL
+ * or n x 3 doubles.  Empty clouds are legal.  Deterministic like every call on this handle: the same bits alone, inside
+ * any batch, run after run; for k-NN search independent of "knn_ring_cap", and "knn_fallbacks" is updated (a call
+ * without a k-NN cloud sets it to 0).  TEASER_HIP_ERR_BAD_ARG (argument and cloud named): non-finite points, search or
+ * orient outside their ranges, reserved != 0, max_nn outside [3, TEASER_HIP_ICP_COV_MAX_NN], a radius (or its square)
+ * that is not finite and > 0 in hybrid search, a non-finite ref when orient != 0, NULL where n > 0. */
+typedef struct teaser_icp_normal_search_c {
+  int32_t search;   /* 0 hybrid: the max_nn nearest inside radius; 1 knn: the max_nn nearest, no radius */
+  int32_t max_nn;   /* [3, TEASER_HIP_ICP_COV_MAX_NN] */
+  double radius;    /* search 0: finite, > 0, square finite; search 1: ignored */
+  int32_t orient;   /* 0 none, 1 towards the point ref, 2 along the direction ref */
+  int32_t reserved; /* 0 */
+  double ref[3];
+} teaser_icp_normal_search_c;
+#ifdef __cplusplus
+static_assert(sizeof(teaser_icp_normal_search_c) == 48, "teaser_icp_normal_search_c is 48 bytes");
+#else
+_Static_assert(sizeof(teaser_icp_normal_search_c) == 48, "teaser_icp_normal_search_c is 48 bytes");
+#endif
+TEASER_HIP_API int32_t teaser_hip_icp_normals_batch(teaser_hip_icp* icp, int32_t batch, const double* const* points,
+                                                    const int32_t* n, const teaser_icp_normal_search_c* search,
+                                                    double* const* normals_out, double* const* cov_out,
+                                                    double* const* eig_out);
+/* teaser_hip_icp_batch_cov with self-estimated target normals.  dst_normal_search: NULL, or one record per problem; a
+ * record with max_nn = 0 means "none given" (its other fields are not read).  A point-to-plane problem whose
+ * dst_normals[b] is NULL (or dst_normals NULL) and whose record has max_nn != 0 gets its target normals from the rule
+ * above applied to dst[b], on the device: the normals kernel writes them into the buffer the correspondence pass
+ * gathers from; they are neither copied to the host nor uploaded.  The result is, bit for bit, that of
+ * teaser_hip_icp_normals_batch followed by teaser_hip_icp_batch_cov with those normals.  Records of problems that give
+ * dst_normals, or are not point-to-plane, are not read.  Every other problem gives the bits it gives through
+ * teaser_hip_icp_batch_cov; a point-to-plane problem with neither normals nor a record is refused as there
+ * ("dst_normals").  A record that is read is checked as above (the argument is named dst_normal_search). */
+TEASER_HIP_API int32_t teaser_hip_icp_batch_auto(teaser_hip_icp* icp, int32_t batch, const double* const* src,
+                                                 const int32_t* n_src, const double* const* dst,
+                                                 const int32_t* n_dst, const double* init,
+                                                 const teaser_icp_params_c* params, teaser_icp_result_c* out,
+                                                 int32_t* const* corr, const double* const* dst_normals,
+                                                 const teaser_icp_estimation_c* est, const double* const* src_cov,
+                                                 const double* const* dst_cov,
+                                                 const teaser_icp_normal_search_c* dst_normal_search);
+/* One problem: teaser_hip_icp_batch_auto with batch = 1. */
+TEASER_HIP_API int32_t teaser_hip_icp_solve_auto(teaser_hip_icp* icp, const double* src, int32_t n_src,
+                                                 const double* dst, int32_t n_dst, const double* init,
+                                                 const teaser_icp_params_c* params, teaser_icp_result_c* out,
+                                                 int32_t* corr, const double* dst_normals,
+                                                 const teaser_icp_estimation_c* est, const double* src_cov,
+                                                 const double* dst_cov,
+                                                 const teaser_icp_normal_search_c* dst_normal_search);
+
 /* Self k-NN (no radius), on the ICP handle: a batch of clouds (n x 3 doubles each) and a k in
  * [1, TEASER_HIP_ICP_KNN_MAX] per cloud (TEASER_HIP_ICP_KNN_MAX = 100, the same number as TEASER_HIP_ICP_COV_MAX_NN).
  * Per point i: the points j of the SAME cloud, i itself included, in ascending (d2, j), d2 = ((dx dx + dy dy) + dz dz),

@@ -133,7 +133,8 @@ EXPORTED_SYMBOLS = [
     "teaser_hip_icp_params_default", "teaser_hip_icp_create", "teaser_hip_icp_destroy", "teaser_hip_icp_last_error",
     "teaser_hip_icp_batch", "teaser_hip_icp_solve", "teaser_hip_icp_estimation_default", "teaser_hip_icp_batch_ex",
     "teaser_hip_icp_solve_ex", "teaser_hip_icp_batch_cov", "teaser_hip_icp_solve_cov",
-    "teaser_hip_icp_covariances_batch",
+    "teaser_hip_icp_covariances_batch", "teaser_hip_icp_normals_batch", "teaser_hip_icp_batch_auto",
+    "teaser_hip_icp_solve_auto",
     "teaser_hip_icp_self_knn_batch", "teaser_hip_icp_remove_statistical_outliers_batch",
     "teaser_hip_icp_remove_radius_outliers_batch", "teaser_hip_icp_set_option", "teaser_hip_icp_get_option",
     "teaser_hip_voxel_create", "teaser_hip_voxel_destroy", "teaser_hip_voxel_last_error",
@@ -1080,7 +1081,8 @@ from .icp import (CauchyLoss, GMLoss, HuberLoss, ICPConvergenceCriteria, L2Loss,
                   TransformationEstimationPointToPlane, TransformationEstimationPointToPoint, TukeyLoss,
                   registration_icp, registration_icp_batch, TransformationEstimationForGeneralizedICP,
                   covariances_from_normals, estimate_covariances, estimate_covariances_batch,
-                  registration_generalized_icp)
+                  registration_generalized_icp, KDTreeSearchParamHybrid, KDTreeSearchParamKNN, estimate_normals,
+                  estimate_normals_batch, surface_variation)
 from .voxel import voxel_down_sample, voxel_down_sample_batch  # noqa: E402
 from .outlier import (remove_radius_outlier, remove_radius_outlier_batch, remove_statistical_outlier,  # noqa: E402
                       remove_statistical_outlier_batch, self_knn, self_knn_batch, get_icp_option, set_icp_option)
@@ -1098,6 +1100,7 @@ __all__ = ["batched", "FPFHEstimation", "Matcher", "MultiDeviceSolver", "RobustR
            "correspondences_knn", "correspondences_knn_batch", "tuple_test_batch",
            "TransformationEstimationPointToPlane", "L2Loss", "HuberLoss", "CauchyLoss", "GMLoss", "TukeyLoss",
            "TransformationEstimationForGeneralizedICP", "registration_generalized_icp", "estimate_covariances",
-           "estimate_covariances_batch", "covariances_from_normals",
+           "estimate_covariances_batch", "covariances_from_normals", "KDTreeSearchParamHybrid", "KDTreeSearchParamKNN",
+           "estimate_normals", "estimate_normals_batch", "surface_variation",
            "remove_statistical_outlier", "remove_statistical_outlier_batch", "remove_radius_outlier",
            "remove_radius_outlier_batch", "self_knn", "self_knn_batch", "get_icp_option", "set_icp_option"]

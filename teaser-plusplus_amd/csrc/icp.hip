@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "host_common.h"
+#include "icp_host.h"
 #include "icp_internal.h"
 #include "teaser_hip.h"
 
@@ -25,26 +26,6 @@ namespace {
 constexpr int kIcpGroup = 8;
 static_assert(kIcpCovMaxNN == TEASER_HIP_ICP_COV_MAX_NN, "the header states K");
 static_assert(kIcpKnnMax == TEASER_HIP_ICP_KNN_MAX, "the header states the largest k");
-
-enum { B_DESC, B_STATE, B_BLK, B_TBLK, B_X, B_Q, B_TBUCKET, B_BCOUNT, B_BSTART, B_CURSOR, B_QS, B_QJ, B_MATCH,
-       B_PARTIALS, B_LIVE, B_NORMALS, B_COV_S, B_COV_T, B_COUNT };
-
-}  // namespace
-
-struct teaser_hip_icp : HandleBase {
-  int32_t* h_live = nullptr;  // page-locked: the one copy per iteration group
-  DevBuf buf[B_COUNT];
-  std::vector<double> stage;  // host packing of the points
-  std::vector<double> back;   // self k-NN / outlier removal: the one copy back of a call
-  int32_t knn_ring_cap = kIcpKnnRingCap;  // option "knn_ring_cap"
-  int64_t knn_fallbacks = 0;              // option "knn_fallbacks": queries of the last call served by the whole-cloud route
-  ~teaser_hip_icp() {
-    for (DevBuf& b : buf) b.release();
-    if (h_live) (void)hipHostFree(h_live);
-  }
-};
-
-namespace {
 
 // the six entries of the contract (upper triangle) of n row-major 3 x 3 matrices
 bool finite_cov(const double* c, int64_t n) {
@@ -65,7 +46,7 @@ int32_t validate(teaser_hip_icp* h, int32_t batch, const double* const* src, con
                  const double* const* dst, const int32_t* n_dst, const double* init,
                  const teaser_icp_params_c* params, teaser_icp_result_c* out, const double* const* dst_normals,
                  const teaser_icp_estimation_c* est, const double* const* src_cov, const double* const* dst_cov,
-                 int max_method) {
+                 int max_method, const teaser_icp_normal_search_c* nsearch) {
   if (batch < 0) return fail(h, TEASER_HIP_ERR_BAD_ARG, "batch must be >= 0");
   if (batch == 0) return TEASER_HIP_OK;
   if (!n_src || !n_dst) return fail(h, TEASER_HIP_ERR_BAD_ARG, "n_src / n_dst must not be NULL");
@@ -127,7 +108,8 @@ int32_t validate(teaser_hip_icp* h, int32_t batch, const double* const* src, con
             return fail(h, TEASER_HIP_ERR_BAD_ARG, "dst_cov has a non-finite entry" + at(b));
         }
       }
-      if (m.method == kIcpMethodPlane && n_dst[b] > 0) {
+      const bool estimated = nsearch && nsearch[b].max_nn != 0 && !(dst_normals && dst_normals[b]);
+      if (m.method == kIcpMethodPlane && n_dst[b] > 0 && !estimated) {
         if (!dst_normals || !dst_normals[b])
           return fail(h, TEASER_HIP_ERR_BAD_ARG, "dst_normals is NULL for a point-to-plane problem" + at(b));
         if (!finite_points(dst_normals[b], n_dst[b]))
@@ -141,111 +123,6 @@ int32_t validate(teaser_hip_icp* h, int32_t batch, const double* const* src, con
     return fail(h, TEASER_HIP_ERR_BAD_ARG, "too many points in one call");
   return TEASER_HIP_OK;
 }
-
-int64_t next_pow2(int64_t v) {
-  int64_t p = 1;
-  while (p < v) p <<= 1;
-  return p;
-}
-
-// The hash grid of one cloud q (d.n_t > 0 points) for search radius r: origin, cell edge, extent, bucket count, and
-// the centre the sums are taken about.
-void set_grid(IcpDesc& d, const double* q, double r) {
-  double lo[3], hi[3];
-  for (int c = 0; c < 3; ++c) lo[c] = hi[c] = q[c];
-  for (int64_t j = 1; j < d.n_t; ++j)
-    for (int c = 0; c < 3; ++c) {
-      lo[c] = std::min(lo[c], q[3 * j + c]);
-      hi[c] = std::max(hi[c], q[3 * j + c]);
-    }
-  double mag = 0;
-  for (int c = 0; c < 3; ++c) mag = std::max(mag, std::max(fabs(lo[c]), fabs(hi[c])));
-  // cell edge slightly above r: two points closer than r then differ by at most one cell per axis although
-  // their cell coordinates are rounded (relative margin 1e-6; absolute 1e-12 of the coordinates' magnitude)
-  const double cell = r * (1 + 1e-6) + 1e-12 * mag;
-  d.inv_h = 1.0 / cell;
-  for (int c = 0; c < 3; ++c) {
-    d.origin[c] = lo[c];
-    d.centre[c] = 0.5 * (lo[c] + hi[c]);
-    d.cmax[c] = icp_cell(hi[c], lo[c], d.inv_h);
-  }
-  d.tb_mask = next_pow2(2 * (int64_t)d.n_t) - 1;
-}
-
-// The target index of one call under construction: per problem the descriptor with its offsets and hash grid, the
-// block -> problem maps of both kernels' grids, and the running totals of source points, target points and buckets.
-struct IcpIndex {
-  std::vector<IcpDesc> desc;
-  std::vector<int32_t> blk_prob, tblk_prob;
-  int64_t s_off = 0, t_off = 0, b_off = 0;
-};
-
-// Appends problem b (n_s source points; the n_t points q[b] indexed for search radius r) with nblk blocks of the
-// kernel that consumes the index; the caller fills in the descriptor's other fields.
-IcpDesc& add_problem(IcpIndex& ix, int b, int32_t n_s, int32_t n_t, const double* const* q, double r, int32_t nblk) {
-  ix.desc.emplace_back();
-  IcpDesc& d = ix.desc.back();
-  memset(&d, 0, sizeof(d));
-  d.n_s = n_s;
-  d.n_t = n_t;
-  d.s_off = ix.s_off;
-  d.t_off = ix.t_off;
-  d.b_off = ix.b_off;
-  d.blk_off = (int32_t)ix.blk_prob.size();
-  d.nblk = nblk;
-  d.tblk_off = (int32_t)ix.tblk_prob.size();
-  d.r2 = r * r;
-  if (n_t > 0) {
-    set_grid(d, q[b], r);
-    ix.b_off += d.tb_mask + 2;  // tb + 1 starts
-  }
-  for (int k = 0; k < nblk; ++k) ix.blk_prob.push_back(b);
-  for (int k = 0; k < (n_t + 255) / 256; ++k) ix.tblk_prob.push_back(b);
-  ix.s_off += n_s;
-  ix.t_off += n_t;
-  return d;
-}
-
-// Packs the points into h->stage (sources, then targets; src may be NULL when no problem has any) and enqueues
-// the uploads: descriptors, the per-problem `records` for B_STATE, both block maps, sources, targets.
-int32_t upload_inputs(teaser_hip_icp* h, const IcpIndex& ix, const double* const* src, const double* const* dst,
-                      const void* records, size_t record_bytes) {
-  for (size_t b = 0; b < ix.desc.size(); ++b) {
-    const IcpDesc& d = ix.desc[b];
-    if (d.n_s) memcpy(&h->stage[(size_t)(3 * d.s_off)], src[b], 24 * (size_t)d.n_s);
-    if (d.n_t) memcpy(&h->stage[(size_t)(3 * (ix.s_off + d.t_off))], dst[b], 24 * (size_t)d.n_t);
-  }
-  DevBuf* B = h->buf;
-  const struct {
-    void* d;
-    const void* hsrc;
-    size_t n;
-  } copies[] = {{B[B_DESC].p, ix.desc.data(), sizeof(IcpDesc) * ix.desc.size()},
-                {B[B_STATE].p, records, record_bytes},
-                {B[B_BLK].p, ix.blk_prob.data(), sizeof(int32_t) * ix.blk_prob.size()},
-                {B[B_TBLK].p, ix.tblk_prob.data(), sizeof(int32_t) * ix.tblk_prob.size()},
-                {B[B_X].p, h->stage.data(), sizeof(double) * 3 * ix.s_off},
-                {B[B_Q].p, h->stage.data() + 3 * ix.s_off, sizeof(double) * 3 * ix.t_off}};
-  for (const auto& c : copies)
-    if (c.n) FCHK(h, hipMemcpyAsync(c.d, c.hsrc, c.n, hipMemcpyHostToDevice, h->stream), "hipMemcpyAsync (inputs)");
-  return TEASER_HIP_OK;
-}
-
-// Clears the bucket counts and enqueues the kernels that build the index over the uploaded targets.
-int32_t launch_index(teaser_hip_icp* h, const IcpIndex& ix) {
-  DevBuf* B = h->buf;
-  if (ix.b_off) FCHK(h, hipMemsetAsync(B[B_BCOUNT].p, 0, sizeof(int32_t) * ix.b_off, h->stream), "hipMemsetAsync");
-  launch_icp_index(h->stream, B[B_DESC].as<IcpDesc>(), B[B_TBLK].as<int32_t>(), (int)ix.tblk_prob.size(),
-                   (int)ix.desc.size(), B[B_Q].as<double>(), B[B_TBUCKET].as<int32_t>(), B[B_BCOUNT].as<int32_t>(),
-                   B[B_BSTART].as<int32_t>(), B[B_CURSOR].as<int32_t>(), B[B_QS].as<double>(), B[B_QJ].as<int32_t>());
-  return TEASER_HIP_OK;
-}
-
-int32_t run_batch(teaser_hip_icp* h, int32_t batch, const double* const* src, const int32_t* n_src,
-                  const double* const* dst, const int32_t* n_dst, const double* init,
-                  const teaser_icp_params_c* params, teaser_icp_result_c* out, int32_t* const* corr,
-                  const double* const* dst_normals, const teaser_icp_estimation_c* est,
-                  const double* const* src_cov, const double* const* dst_cov, int max_method);
 
 }  // namespace
 
@@ -292,8 +169,8 @@ int32_t teaser_hip_icp_batch_ex(teaser_hip_icp* h, int32_t batch, const double* 
                                 const double* const* dst, const int32_t* n_dst, const double* init,
                                 const teaser_icp_params_c* params, teaser_icp_result_c* out, int32_t* const* corr,
                                 const double* const* dst_normals, const teaser_icp_estimation_c* est) {
-  return run_batch(h, batch, src, n_src, dst, n_dst, init, params, out, corr, dst_normals, est, nullptr, nullptr,
-                   kIcpMethodPlane);
+  return icp_run_batch(h, batch, src, n_src, dst, n_dst, init, params, out, corr, dst_normals, est, nullptr, nullptr,
+                       kIcpMethodPlane, nullptr, nullptr, nullptr);
 }
 
 int32_t teaser_hip_icp_batch_cov(teaser_hip_icp* h, int32_t batch, const double* const* src, const int32_t* n_src,
@@ -301,24 +178,25 @@ int32_t teaser_hip_icp_batch_cov(teaser_hip_icp* h, int32_t batch, const double*
                                  const teaser_icp_params_c* params, teaser_icp_result_c* out, int32_t* const* corr,
                                  const double* const* dst_normals, const teaser_icp_estimation_c* est,
                                  const double* const* src_cov, const double* const* dst_cov) {
-  return run_batch(h, batch, src, n_src, dst, n_dst, init, params, out, corr, dst_normals, est, src_cov, dst_cov,
-                   kIcpMethodGicp);
+  return icp_run_batch(h, batch, src, n_src, dst, n_dst, init, params, out, corr, dst_normals, est, src_cov, dst_cov,
+                       kIcpMethodGicp, nullptr, nullptr, nullptr);
 }
 
 }  // extern "C"
 
-namespace {
+namespace thip {
 
-// Every batched entry point: max_method is the largest estimation method the entry accepts.
-int32_t run_batch(teaser_hip_icp* h, int32_t batch, const double* const* src, const int32_t* n_src,
-                  const double* const* dst, const int32_t* n_dst, const double* init,
-                  const teaser_icp_params_c* params, teaser_icp_result_c* out, int32_t* const* corr,
-                  const double* const* dst_normals, const teaser_icp_estimation_c* est,
-                  const double* const* src_cov, const double* const* dst_cov, int max_method) {
+// Every batched entry point (icp_host.h).
+int32_t icp_run_batch(teaser_hip_icp* h, int32_t batch, const double* const* src, const int32_t* n_src,
+                      const double* const* dst, const int32_t* n_dst, const double* init,
+                      const teaser_icp_params_c* params, teaser_icp_result_c* out, int32_t* const* corr,
+                      const double* const* dst_normals, const teaser_icp_estimation_c* est,
+                      const double* const* src_cov, const double* const* dst_cov, int max_method,
+                      const teaser_icp_normal_search_c* nsearch, IcpPreIndexHook hook, void* ctx) {
   if (!h) return TEASER_HIP_ERR_BAD_ARG;
   h->err.clear();
   int32_t rc = validate(h, batch, src, n_src, dst, n_dst, init, params, out, dst_normals, est, src_cov, dst_cov,
-                        max_method);
+                        max_method, nsearch);
   if (rc != TEASER_HIP_OK || batch == 0) return rc;
   FCHK(h, hipSetDevice(h->device), "hipSetDevice");
 
@@ -361,7 +239,8 @@ int32_t run_batch(teaser_hip_icp* h, int32_t batch, const double* const* src, co
       sizeof(double) * 3 * std::max<int64_t>(t_off, 1), sizeof(int32_t) * std::max<int64_t>(t_off, 1),
       sizeof(int32_t) * std::max<int64_t>(b_off, 1), sizeof(int32_t) * std::max<int64_t>(b_off, 1),
       sizeof(int32_t) * std::max<int64_t>(b_off, 1), sizeof(double) * 3 * std::max<int64_t>(t_off, 1),
-      sizeof(int32_t) * std::max<int64_t>(t_off, 1), sizeof(int32_t) * std::max<int64_t>(s_off, 1),
+      sizeof(int32_t) * std::max<int64_t>(t_off, 1),
+      sizeof(int32_t) * std::max<int64_t>(hook ? std::max(s_off, 2 * t_off) : s_off, 1),  // (the hook's worklist)
       sizeof(double) * (plane || gicp ? kIcpPlaneSums : kIcpSums) * std::max(n_blk, 1), sizeof(int32_t),
       plane ? sizeof(double) * 3 * std::max<int64_t>(t_off, 1) : 0,
       gicp ? sizeof(double) * 6 * std::max<int64_t>(s_off, 1) : 0,
@@ -375,7 +254,7 @@ int32_t run_batch(teaser_hip_icp* h, int32_t batch, const double* const* src, co
   if ((rc = upload_inputs(h, ix, src, dst, state.data(), bytes[B_STATE])) != TEASER_HIP_OK) return rc;
   for (int b = 0; b < batch; ++b) {  // one copy per point-to-plane problem, straight from the caller's normals
     const IcpDesc& d = desc[(size_t)b];
-    if (d.method == kIcpMethodPlane && d.n_t > 0)
+    if (d.method == kIcpMethodPlane && d.n_t > 0 && dst_normals && dst_normals[b])  // else: the hook estimates them
       FCHK(h, hipMemcpyAsync(B[B_NORMALS].as<double>() + 3 * d.t_off, dst_normals[b], 24 * (size_t)d.n_t,
                              hipMemcpyHostToDevice, s),
            "hipMemcpyAsync (normals)");
@@ -397,7 +276,8 @@ int32_t run_batch(teaser_hip_icp* h, int32_t batch, const double* const* src, co
            "hipMemcpyAsync (target covariances)");
   }
 
-  // ---- target index, then the iteration groups ----
+  // ---- (self-estimated normals,) target index, then the iteration groups ----
+  if (hook && (rc = hook(h, ctx, ix)) != TEASER_HIP_OK) return rc;
   if ((rc = launch_index(h, ix)) != TEASER_HIP_OK) return rc;
   int64_t passes = 0;  // correspondence passes enqueued: the first one + one per iteration
   for (;;) {
@@ -450,7 +330,7 @@ int32_t run_batch(teaser_hip_icp* h, int32_t batch, const double* const* src, co
   return TEASER_HIP_OK;
 }
 
-}  // namespace
+}  // namespace thip
 
 extern "C" {
 
@@ -558,54 +438,6 @@ int32_t teaser_hip_icp_covariances_batch(teaser_hip_icp* h, int32_t batch, const
 
 // ---- self k-NN, statistical and radius outlier removal ---------------------------------------------------------------
 namespace {
-
-// What the three calls check alike: n, the clouds and their coordinates.  *total = the number of points.
-int32_t check_clouds(teaser_hip_icp* h, int32_t batch, const double* const* points, const int32_t* n, int64_t* total) {
-  *total = 0;
-  if (!n) return fail(h, TEASER_HIP_ERR_BAD_ARG, "n must not be NULL");
-  for (int b = 0; b < batch; ++b) {
-    if (n[b] < 0) return fail(h, TEASER_HIP_ERR_BAD_ARG, "n must be >= 0" + at(b));
-    if (n[b] > 0 && (!points || !points[b])) return fail(h, TEASER_HIP_ERR_BAD_ARG, "points is NULL" + at(b));
-    if (n[b] > 0 && !finite_points(points[b], n[b]))
-      return fail(h, TEASER_HIP_ERR_BAD_ARG, "points has a non-finite coordinate" + at(b));
-    *total += n[b];
-  }
-  if (*total >= INT32_MAX / 9) return fail(h, TEASER_HIP_ERR_BAD_ARG, "too many points in one call");
-  return TEASER_HIP_OK;
-}
-
-// The cell edge h of the self k-NN grid of one cloud (n > 0 points, `want` = min(k, n) neighbours per query): the
-// bounding box is cut into about n / c cells, c = max(2, want / 2) points per cell, counting only the axes along
-// which the box is wider than a cell (a planar cloud gets a 2-D grid of square cells, a collinear one a 1-D grid),
-// and never into more than 2^20 cells per axis.  A cloud of identical points gets h = 1 (one cell).  *rings_ok is
-// cleared for an extent whose squares leave the normal range: such a cloud is served by the whole-cloud route.
-double knn_edge(const double* q, int32_t n, int32_t want, bool* rings_ok) {
-  double lo[3], hi[3], e[3];
-  for (int c = 0; c < 3; ++c) lo[c] = hi[c] = q[c];
-  for (int64_t j = 1; j < n; ++j)
-    for (int c = 0; c < 3; ++c) {
-      lo[c] = std::min(lo[c], q[3 * j + c]);
-      hi[c] = std::max(hi[c], q[3 * j + c]);
-    }
-  for (int c = 0; c < 3; ++c) e[c] = hi[c] - lo[c];
-  std::sort(e, e + 3);  // e[2] the largest
-  const double E = e[2];
-  *rings_ok = true;
-  if (E == 0) return 1.0;
-  if (!(E > 1e-140 && E < 1e140)) {
-    *rings_ok = false;
-    return 1.0;
-  }
-  const double cells = std::max(1.0, floor((double)n / (double)std::max(2, want / 2)));
-  // the thin axes are found by comparing the extents themselves with the edge of the lower-dimensional grid, from
-  // one dimension up, so that no product of two tiny ratios decides anything
-  double hh = E / cells;                                   // a 1-D grid along the longest axis
-  if (e[1] > hh) {
-    hh = E * sqrt((e[1] / E) / cells);                     // a 2-D grid of square cells
-    if (e[0] > hh) hh = E * cbrt((e[1] / E) * (e[0] / E) / cells);
-  }
-  return std::max(hh, E / 1048576.0);
-}
 
 // Index and self k-NN launches of one call.  k[b] neighbours per cloud; ratio NULL: self k-NN (idx / d2 outputs at
 // out_idx / out_d2 of B_X), else statistical removal (avg at out_avg).  Leaves the descriptors in *ix.

@@ -1,0 +1,202 @@
+// icp_host.h -- what the host files of the ICP handle (icp.hip: the iteration loop, covariance estimation, self k-NN and
+// outlier removal; icp_normals.hip: normal estimation and the self-estimating point-to-plane entry) share: the handle,
+// its buffers, the per-call index under construction and the uploads.
+#pragma once
+
+#include <math.h>
+#include <string.h>
+
+#include <algorithm>
+#include <string>
+#include <vector>
+
+#include "host_common.h"
+#include "icp_internal.h"
+#include "teaser_hip.h"
+
+namespace thip {
+
+// B_N*: the descriptors, records and block maps of the normal estimation that precedes the iterations of
+// teaser_hip_icp_batch_auto (its other buffers are the ICP's own)
+enum { B_DESC, B_STATE, B_BLK, B_TBLK, B_X, B_Q, B_TBUCKET, B_BCOUNT, B_BSTART, B_CURSOR, B_QS, B_QJ, B_MATCH,
+       B_PARTIALS, B_LIVE, B_NORMALS, B_COV_S, B_COV_T, B_NDESC, B_NKNN, B_NREC, B_NBLK, B_NTBLK, B_COUNT };
+
+}  // namespace thip
+
+struct teaser_hip_icp : thip::HandleBase {
+  int32_t* h_live = nullptr;  // page-locked: the one copy per iteration group
+  thip::DevBuf buf[thip::B_COUNT];
+  std::vector<double> stage;  // host packing of the points
+  std::vector<double> back;   // self k-NN / outlier removal: the one copy back of a call
+  int32_t knn_ring_cap = thip::kIcpKnnRingCap;  // option "knn_ring_cap"
+  int64_t knn_fallbacks = 0;              // option "knn_fallbacks": queries of the last call served by the whole-cloud route
+  ~teaser_hip_icp() {
+    for (thip::DevBuf& b : buf) b.release();
+    if (h_live) (void)hipHostFree(h_live);
+  }
+};
+
+namespace thip {
+
+inline int64_t next_pow2(int64_t v) {
+  int64_t p = 1;
+  while (p < v) p <<= 1;
+  return p;
+}
+
+// The hash grid of one cloud q (d.n_t > 0 points) for search radius r: origin, cell edge, extent, bucket count, and
+// the centre the sums are taken about.
+inline void set_grid(IcpDesc& d, const double* q, double r) {
+  double lo[3], hi[3];
+  for (int c = 0; c < 3; ++c) lo[c] = hi[c] = q[c];
+  for (int64_t j = 1; j < d.n_t; ++j)
+    for (int c = 0; c < 3; ++c) {
+      lo[c] = std::min(lo[c], q[3 * j + c]);
+      hi[c] = std::max(hi[c], q[3 * j + c]);
+    }
+  double mag = 0;
+  for (int c = 0; c < 3; ++c) mag = std::max(mag, std::max(fabs(lo[c]), fabs(hi[c])));
+  // cell edge slightly above r: two points closer than r then differ by at most one cell per axis although
+  // their cell coordinates are rounded (relative margin 1e-6; absolute 1e-12 of the coordinates' magnitude)
+  const double cell = r * (1 + 1e-6) + 1e-12 * mag;
+  d.inv_h = 1.0 / cell;
+  for (int c = 0; c < 3; ++c) {
+    d.origin[c] = lo[c];
+    d.centre[c] = 0.5 * (lo[c] + hi[c]);
+    d.cmax[c] = icp_cell(hi[c], lo[c], d.inv_h);
+  }
+  d.tb_mask = next_pow2(2 * (int64_t)d.n_t) - 1;
+}
+
+// The target index of one call under construction: per problem the descriptor with its offsets and hash grid, the
+// block -> problem maps of both kernels' grids, and the running totals of source points, target points and buckets.
+struct IcpIndex {
+  std::vector<IcpDesc> desc;
+  std::vector<int32_t> blk_prob, tblk_prob;
+  int64_t s_off = 0, t_off = 0, b_off = 0;
+};
+
+// Appends problem b (n_s source points; the n_t points q[b] indexed for search radius r) with nblk blocks of the
+// kernel that consumes the index; the caller fills in the descriptor's other fields.
+inline IcpDesc& add_problem(IcpIndex& ix, int b, int32_t n_s, int32_t n_t, const double* const* q, double r, int32_t nblk) {
+  ix.desc.emplace_back();
+  IcpDesc& d = ix.desc.back();
+  memset(&d, 0, sizeof(d));
+  d.n_s = n_s;
+  d.n_t = n_t;
+  d.s_off = ix.s_off;
+  d.t_off = ix.t_off;
+  d.b_off = ix.b_off;
+  d.blk_off = (int32_t)ix.blk_prob.size();
+  d.nblk = nblk;
+  d.tblk_off = (int32_t)ix.tblk_prob.size();
+  d.r2 = r * r;
+  if (n_t > 0) {
+    set_grid(d, q[b], r);
+    ix.b_off += d.tb_mask + 2;  // tb + 1 starts
+  }
+  for (int k = 0; k < nblk; ++k) ix.blk_prob.push_back(b);
+  for (int k = 0; k < (n_t + 255) / 256; ++k) ix.tblk_prob.push_back(b);
+  ix.s_off += n_s;
+  ix.t_off += n_t;
+  return d;
+}
+
+// Packs the points into h->stage (sources, then targets; src may be NULL when no problem has any) and enqueues
+// the uploads: descriptors, the per-problem `records` for B_STATE, both block maps, sources, targets.
+inline int32_t upload_inputs(teaser_hip_icp* h, const IcpIndex& ix, const double* const* src, const double* const* dst,
+                      const void* records, size_t record_bytes) {
+  for (size_t b = 0; b < ix.desc.size(); ++b) {
+    const IcpDesc& d = ix.desc[b];
+    if (d.n_s) memcpy(&h->stage[(size_t)(3 * d.s_off)], src[b], 24 * (size_t)d.n_s);
+    if (d.n_t) memcpy(&h->stage[(size_t)(3 * (ix.s_off + d.t_off))], dst[b], 24 * (size_t)d.n_t);
+  }
+  DevBuf* B = h->buf;
+  const struct {
+    void* d;
+    const void* hsrc;
+    size_t n;
+  } copies[] = {{B[B_DESC].p, ix.desc.data(), sizeof(IcpDesc) * ix.desc.size()},
+                {B[B_STATE].p, records, record_bytes},
+                {B[B_BLK].p, ix.blk_prob.data(), sizeof(int32_t) * ix.blk_prob.size()},
+                {B[B_TBLK].p, ix.tblk_prob.data(), sizeof(int32_t) * ix.tblk_prob.size()},
+                {B[B_X].p, h->stage.data(), sizeof(double) * 3 * ix.s_off},
+                {B[B_Q].p, h->stage.data() + 3 * ix.s_off, sizeof(double) * 3 * ix.t_off}};
+  for (const auto& c : copies)
+    if (c.n) FCHK(h, hipMemcpyAsync(c.d, c.hsrc, c.n, hipMemcpyHostToDevice, h->stream), "hipMemcpyAsync (inputs)");
+  return TEASER_HIP_OK;
+}
+
+// Clears the bucket counts and enqueues the kernels that build the index over the uploaded targets.
+inline int32_t launch_index(teaser_hip_icp* h, const IcpIndex& ix) {
+  DevBuf* B = h->buf;
+  if (ix.b_off) FCHK(h, hipMemsetAsync(B[B_BCOUNT].p, 0, sizeof(int32_t) * ix.b_off, h->stream), "hipMemsetAsync");
+  launch_icp_index(h->stream, B[B_DESC].as<IcpDesc>(), B[B_TBLK].as<int32_t>(), (int)ix.tblk_prob.size(),
+                   (int)ix.desc.size(), B[B_Q].as<double>(), B[B_TBUCKET].as<int32_t>(), B[B_BCOUNT].as<int32_t>(),
+                   B[B_BSTART].as<int32_t>(), B[B_CURSOR].as<int32_t>(), B[B_QS].as<double>(), B[B_QJ].as<int32_t>());
+  return TEASER_HIP_OK;
+}
+
+// What the three calls check alike: n, the clouds and their coordinates.  *total = the number of points.
+inline int32_t check_clouds(teaser_hip_icp* h, int32_t batch, const double* const* points, const int32_t* n, int64_t* total) {
+  *total = 0;
+  if (!n) return fail(h, TEASER_HIP_ERR_BAD_ARG, "n must not be NULL");
+  for (int b = 0; b < batch; ++b) {
+    if (n[b] < 0) return fail(h, TEASER_HIP_ERR_BAD_ARG, "n must be >= 0" + at(b));
+    if (n[b] > 0 && (!points || !points[b])) return fail(h, TEASER_HIP_ERR_BAD_ARG, "points is NULL" + at(b));
+    if (n[b] > 0 && !finite_points(points[b], n[b]))
+      return fail(h, TEASER_HIP_ERR_BAD_ARG, "points has a non-finite coordinate" + at(b));
+    *total += n[b];
+  }
+  if (*total >= INT32_MAX / 9) return fail(h, TEASER_HIP_ERR_BAD_ARG, "too many points in one call");
+  return TEASER_HIP_OK;
+}
+
+// The cell edge h of the self k-NN grid of one cloud (n > 0 points, `want` = min(k, n) neighbours per query): the
+// bounding box is cut into about n / c cells, c = max(2, want / 2) points per cell, counting only the axes along
+// which the box is wider than a cell (a planar cloud gets a 2-D grid of square cells, a collinear one a 1-D grid),
+// and never into more than 2^20 cells per axis.  A cloud of identical points gets h = 1 (one cell).  *rings_ok is
+// cleared for an extent whose squares leave the normal range: such a cloud is served by the whole-cloud route.
+inline double knn_edge(const double* q, int32_t n, int32_t want, bool* rings_ok) {
+  double lo[3], hi[3], e[3];
+  for (int c = 0; c < 3; ++c) lo[c] = hi[c] = q[c];
+  for (int64_t j = 1; j < n; ++j)
+    for (int c = 0; c < 3; ++c) {
+      lo[c] = std::min(lo[c], q[3 * j + c]);
+      hi[c] = std::max(hi[c], q[3 * j + c]);
+    }
+  for (int c = 0; c < 3; ++c) e[c] = hi[c] - lo[c];
+  std::sort(e, e + 3);  // e[2] the largest
+  const double E = e[2];
+  *rings_ok = true;
+  if (E == 0) return 1.0;
+  if (!(E > 1e-140 && E < 1e140)) {
+    *rings_ok = false;
+    return 1.0;
+  }
+  const double cells = std::max(1.0, floor((double)n / (double)std::max(2, want / 2)));
+  // the thin axes are found by comparing the extents themselves with the edge of the lower-dimensional grid, from
+  // one dimension up, so that no product of two tiny ratios decides anything
+  double hh = E / cells;                                   // a 1-D grid along the longest axis
+  if (e[1] > hh) {
+    hh = E * sqrt((e[1] / E) / cells);                     // a 2-D grid of square cells
+    if (e[0] > hh) hh = E * cbrt((e[1] / E) * (e[0] / E) / cells);
+  }
+  return std::max(hh, E / 1048576.0);
+}
+
+// Called by icp_run_batch between the uploads and the index build of the iterations: ix is the call's index, the
+// targets lie in B_Q at its offsets.  Returns a status.
+typedef int32_t (*IcpPreIndexHook)(teaser_hip_icp* h, void* ctx, const IcpIndex& ix);
+
+// Every batched ICP entry point (icp.hip).  max_method: the largest estimation method the entry accepts.  nsearch: NULL,
+// or per problem a record whose max_nn != 0 stands in for the dst_normals of a point-to-plane problem that gives none;
+// `hook` then has to fill those rows of B_NORMALS.
+int32_t icp_run_batch(teaser_hip_icp* h, int32_t batch, const double* const* src, const int32_t* n_src,
+                      const double* const* dst, const int32_t* n_dst, const double* init,
+                      const teaser_icp_params_c* params, teaser_icp_result_c* out, int32_t* const* corr,
+                      const double* const* dst_normals, const teaser_icp_estimation_c* est,
+                      const double* const* src_cov, const double* const* dst_cov, int max_method,
+                      const teaser_icp_normal_search_c* nsearch, IcpPreIndexHook hook, void* ctx);
+
+}  // namespace thip

@@ -76,6 +76,18 @@ struct IcpKnnDesc {
   double ratio;       // std_ratio (statistical removal)
 };
 
+// One cloud of a normal-estimation call, beside its IcpDesc (the cloud is the descriptor's "target"; hybrid search: the
+// grid and r2 of the radius, as in covariance estimation; k-NN search: an IcpKnnDesc with k = max_nn beside it).  Offsets
+// count rows (points) of the packed outputs.
+struct IcpNormalDesc {
+  int32_t max_nn;     // 3 .. kIcpCovMaxNN
+  int32_t orient;     // 0 none, 1 towards the point ref, 2 along the direction ref
+  int64_t nrm_off;    // first row of this cloud's normals
+  int64_t cov_off;    // first row of its raw covariances, -1: not asked for
+  int64_t eig_off;    // first row of its eigenvalues, -1: not asked for
+  double ref[3];
+};
+
 // Grid cell of one coordinate; host (descriptor set-up) and device (index build, search) run the same expression.
 __host__ __device__ inline int64_t icp_cell(double x, double origin, double inv_h) {
   double v = floor((x - origin) * inv_h);
@@ -109,6 +121,18 @@ void launch_icp_self_knn(hipStream_t s, const IcpDesc* d_desc, const IcpKnnDesc*
                          int n_blk, int top_k, const double* d_q, const double* d_qs, const int32_t* d_qj,
                          const int32_t* d_bstart, int32_t* d_idx, double* d_d2, double* d_avg, int32_t* d_work,
                          int32_t* d_work_count);
+// Normal estimation on the indexed clouds (the normals contract of include/teaser_hip.h): the normals at
+// IcpNormalDesc::nrm_off of d_nrm, the raw covariances / ascending eigenvalues of the clouds that ask for them at
+// cov_off / eig_off of d_cov / d_eig.  Hybrid search: one launch over n_blk blocks of kIcpCovBlock points.  k-NN search:
+// the ring and scan launches of self k-NN with the covariance consumer (work / work_count as there).
+void launch_icp_normals_hybrid(hipStream_t s, const IcpDesc* d_desc, const IcpNormalDesc* d_nd,
+                               const int32_t* d_blk_prob, int n_blk, int max_nn, const double* d_q, const double* d_qs,
+                               const int32_t* d_qj, const int32_t* d_bstart, double* d_nrm, double* d_cov,
+                               double* d_eig);
+void launch_icp_normals_knn(hipStream_t s, const IcpDesc* d_desc, const IcpKnnDesc* d_knn, const IcpNormalDesc* d_nd,
+                            const int32_t* d_blk_prob, int n_blk, int top_k, const double* d_q, const double* d_qs,
+                            const int32_t* d_qj, const int32_t* d_bstart, double* d_nrm, double* d_cov, double* d_eig,
+                            int32_t* d_work, int32_t* d_work_count);
 // mean, std, threshold (stats: 3 doubles per cloud) from avg, then the mask and the kept count (cleared by the caller)
 void launch_icp_statistical(hipStream_t s, const IcpDesc* d_desc, const IcpKnnDesc* d_knn,
                             const int32_t* d_tblk_prob, int n_tblk, int batch, const double* d_avg,

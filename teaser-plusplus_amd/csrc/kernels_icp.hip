@@ -39,6 +39,7 @@
 // Jacobi iteration on the symmetric 3 x 3 and the output, all by that lane.
 #include <math.h>
 
+#include "icp_cov_device.h"
 #include "icp_internal.h"
 #include "svd3.h"  // svd_rot3 (shared with kernels_estimate.hip)
 
@@ -461,36 +462,10 @@ __global__ __launch_bounds__(256) void icp_live_kernel(const IcpState* __restric
 }
 
 // ---- covariance estimation ---------------------------------------------------------------------------------------
-// One Jacobi rotation of the symmetric 3 x 3 a = {a00, a01, a02, a11, a12, a22} in the (P, Q) plane, O the third
-// index; V accumulates the rotations (columns = eigenvectors).  Indices are compile-time: everything stays in VGPRs.
-__device__ __forceinline__ constexpr int icp_sym(int i, int j) {
-  return i <= j ? (i == 0 ? j : i + j + 1) : (j == 0 ? i : i + j + 1);
-}
-
-template <int P, int Q, int O>
-__device__ __forceinline__ bool icp_jacobi_rotate(double (&a)[6], double (&V)[9]) {
-  constexpr int PQ = icp_sym(P, Q), PP = icp_sym(P, P), QQ = icp_sym(Q, Q), OP = icp_sym(O, P), OQ = icp_sym(O, Q);
-  const double apq = a[PQ], app = a[PP], aqq = a[QQ];
-  if (apq == 0.0 || fabs(apq) <= 1e-17 * (fabs(app) + fabs(aqq))) return false;
-  const double theta = (aqq - app) / (2.0 * apq);
-  const double t = (theta >= 0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(1.0 + theta * theta));
-  const double c = 1.0 / sqrt(1.0 + t * t), sn = t * c;
-  a[PP] = app - t * apq;
-  a[QQ] = aqq + t * apq;
-  a[PQ] = 0.0;
-  const double aop = a[OP], aoq = a[OQ];
-  a[OP] = c * aop - sn * aoq;
-  a[OQ] = sn * aop + c * aoq;
-  const double v0p = V[P], v0q = V[Q], v1p = V[3 + P], v1q = V[3 + Q], v2p = V[6 + P], v2q = V[6 + Q];
-  V[P] = c * v0p - sn * v0q;
-  V[Q] = sn * v0p + c * v0q;
-  V[3 + P] = c * v1p - sn * v1q;
-  V[3 + Q] = sn * v1p + c * v1q;
-  V[6 + P] = c * v2p - sn * v2q;
-  V[6 + Q] = sn * v2p + c * v2q;
-  return true;
-}
-
+// The Jacobi rotation: icp_cov_device.h.  The list, the sums and the choice of the normal are also there as functions,
+// for normal estimation; this kernel keeps them written out, because the factored form changes its register
+// allocation (61 instead of 101 VGPRs, another schedule) and that form has no measurement behind it (DESIGN.md
+// section 18).  The two forms are the same operations in the same order.
 template <int CAP>
 __global__ __launch_bounds__(kIcpCovBlock) void icp_cov_kernel(const IcpDesc* __restrict__ descs,
                                                               const IcpCovDesc* __restrict__ covs,
@@ -600,6 +575,34 @@ __global__ __launch_bounds__(kIcpCovBlock) void icp_cov_kernel(const IcpDesc* __
   o[8] = 1.0 - u2 * nrm[2];
 }
 
+// ---- normal estimation, hybrid search ------------------------------------------------------------------------------
+// The search and the sums of icp_cov_kernel; the normal, the raw covariance and the eigenvalues are written instead
+// of C (icp_normal_store).  A kernel of its own, so that icp_cov_kernel keeps its registers.
+template <int CAP>
+__global__ __launch_bounds__(kIcpCovBlock) void icp_normals_kernel(const IcpDesc* __restrict__ descs,
+                                                                  const int32_t* __restrict__ blk_prob,
+                                                                  const double* __restrict__ q,
+                                                                  const double* __restrict__ qs,
+                                                                  const int32_t* __restrict__ qj,
+                                                                  const int32_t* __restrict__ bstart,
+                                                                  const IcpNormalOut out) {
+  __shared__ double ld[CAP][kIcpCovBlock];   // slot-major: lane l owns ld[.][l]
+  __shared__ int32_t lj[CAP][kIcpCovBlock];
+  const int p = blk_prob[blockIdx.x];
+  const IcpDesc& d = descs[p];
+  const IcpNormalDesc& nd = out.nd[p];
+  const int lane = threadIdx.x;
+  const int64_t i = (int64_t)((int)blockIdx.x - d.blk_off) * kIcpCovBlock + lane;
+  if (i >= d.n_t) return;
+  const int cap = nd.max_nn < CAP ? nd.max_nn : CAP;  // <= CAP: every list index stays inside
+  const double* xp = q + 3 * (d.t_off + i);
+  const double x[3] = {xp[0], xp[1], xp[2]};
+  const int m = icp_hybrid_list<CAP>(ld, lj, lane, cap, d, x, qs, qj, bstart);
+  double a[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+  if (m >= 3) icp_list_cov(lj, lane, m, q + 3 * d.t_off, x, a);
+  icp_normal_store(out, nd, i, x, m, a);
+}
+
 // ---- launchers ------------------------------------------------------------------------------------------------
 void launch_icp_index(hipStream_t s, const IcpDesc* d_desc, const int32_t* d_tblk_prob, int n_tblk, int batch,
                       const double* d_q, int32_t* d_tbucket, int32_t* d_bcount, int32_t* d_bstart,
@@ -652,6 +655,20 @@ void launch_icp_covariances(hipStream_t s, const IcpDesc* d_desc, const IcpCovDe
   else
     hipLaunchKernelGGL(icp_cov_kernel<kIcpCovMaxNN>, dim3(n_blk), dim3(kIcpCovBlock), 0, s, d_desc, d_cov, d_blk_prob,
                        d_q, d_qs, d_qj, d_bstart, d_out);
+}
+
+void launch_icp_normals_hybrid(hipStream_t s, const IcpDesc* d_desc, const IcpNormalDesc* d_nd,
+                               const int32_t* d_blk_prob, int n_blk, int max_nn, const double* d_q, const double* d_qs,
+                               const int32_t* d_qj, const int32_t* d_bstart, double* d_nrm, double* d_cov,
+                               double* d_eig) {
+  if (n_blk <= 0) return;
+  const IcpNormalOut out = {d_nd, d_nrm, d_cov, d_eig};
+  if (max_nn <= kIcpCovSmallNN)  // the capacity only bounds the list: it never changes a result
+    hipLaunchKernelGGL(icp_normals_kernel<kIcpCovSmallNN>, dim3(n_blk), dim3(kIcpCovBlock), 0, s, d_desc, d_blk_prob,
+                       d_q, d_qs, d_qj, d_bstart, out);
+  else
+    hipLaunchKernelGGL(icp_normals_kernel<kIcpCovMaxNN>, dim3(n_blk), dim3(kIcpCovBlock), 0, s, d_desc, d_blk_prob,
+                       d_q, d_qs, d_qj, d_bstart, out);
 }
 
 void launch_icp_live(hipStream_t s, const IcpState* d_state, int batch, int32_t* d_live) {

@@ -18,39 +18,33 @@
 // list (or lies beyond a full list's end, like the first time).
 #include <math.h>
 
+#include "icp_cov_device.h"
 #include "icp_internal.h"
 
 namespace thip {
 
-// Inserts (d2, j) into the lane's list (ascending (d2, j), at most cap <= CAP entries, m of them in use).
-template <int CAP>
-__device__ __forceinline__ void icp_knn_insert(double (*ld)[kIcpCovBlock], int32_t (*lj)[kIcpCovBlock], int lane,
-                                               int cap, int& m, double d2, int32_t j) {
-  int pos = m;  // the number of kept entries below (d2, j)
-  while (pos > 0) {
-    const double pd = ld[pos - 1][lane];
-    if (!(d2 < pd || (d2 == pd && j < lj[pos - 1][lane]))) break;
-    --pos;
-  }
-  if (pos > 0 && ld[pos - 1][lane] == d2 && lj[pos - 1][lane] == j) return;  // seen before
-  if (pos == cap) return;                                                    // not among the cap best
-  if (m < cap) ++m;
-  for (int t = m - 1; t > pos; --t) {  // t <= cap - 1 < CAP
-    ld[t][lane] = ld[t - 1][lane];
-    lj[t][lane] = lj[t - 1][lane];
-  }
-  ld[pos][lane] = d2;
-  lj[pos][lane] = j;
-}
+// icp_knn_insert, the per-lane list: icp_cov_device.h.
+//
+// What the two kernels do with a query's finished neighbours, in ascending (d2, j), is the template argument Out:
+// IcpKnnListOut writes them (avg == nullptr) or the mean of their distances (statistical removal); IcpNormalOut
+// (icp_cov_device.h) feeds them to the covariance sums of normal estimation.
+struct IcpKnnListOut {
+  static constexpr bool kNormals = false;
+  int32_t* idx;
+  double* d2;
+  double* avg;
+};
+struct IcpKnnNormalOut : IcpNormalOut {
+  static constexpr bool kNormals = true;
+};
 
-template <int CAP>
-__global__ __launch_bounds__(kIcpCovBlock) void icp_knn_ring_kernel(
-    const IcpDesc* __restrict__ descs, const IcpKnnDesc* __restrict__ knns, const int32_t* __restrict__ blk_prob,
-    const double* __restrict__ q, const double* __restrict__ qs, const int32_t* __restrict__ qj,
-    const int32_t* __restrict__ bstart, int32_t* __restrict__ idx_out, double* __restrict__ d2_out,
-    double* __restrict__ avg_out, int32_t* __restrict__ work, int32_t* __restrict__ work_count) {
-  __shared__ double ld[CAP][kIcpCovBlock];  // slot-major: lane l owns ld[.][l]
-  __shared__ int32_t lj[CAP][kIcpCovBlock];
+template <int CAP, class Out>
+__device__ __forceinline__ void icp_knn_ring(double (*ld)[kIcpCovBlock], int32_t (*lj)[kIcpCovBlock],
+                                             const IcpDesc* __restrict__ descs, const IcpKnnDesc* __restrict__ knns,
+                                             const int32_t* __restrict__ blk_prob, const double* __restrict__ q,
+                                             const double* __restrict__ qs, const int32_t* __restrict__ qj,
+                                             const int32_t* __restrict__ bstart, const Out& out,
+                                             int32_t* __restrict__ work, int32_t* __restrict__ work_count) {
   const int p = blk_prob[blockIdx.x];
   const IcpDesc& d = descs[p];
   const IcpKnnDesc& kd = knns[p];
@@ -100,27 +94,58 @@ __global__ __launch_bounds__(kIcpCovBlock) void icp_knn_ring_kernel(
     work[2 * (int64_t)w + 1] = (int32_t)i;
     return;
   }
-  if (avg_out) {  // statistical removal: the distances one at a time in ascending (d2, j), from 0.0
-    double acc = 0.0;
-    for (int t = 0; t < m; ++t) acc += sqrt(ld[t][lane]);
-    avg_out[d.t_off + i] = acc / (double)m;
+  if constexpr (Out::kNormals) {  // the list in ascending (d2, j) into the sums of the covariance contract
+    double a[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    if (m >= 3) icp_list_cov(lj, lane, m, q + 3 * d.t_off, x, a);
+    icp_normal_store(out, out.nd[p], i, x, m, a);
   } else {
-    const int64_t base = kd.out_off + i * kd.k;
-    for (int t = 0; t < kd.k; ++t) {
-      idx_out[base + t] = t < m ? lj[t][lane] : -1;
-      d2_out[base + t] = t < m ? ld[t][lane] : INFINITY;
+    int32_t* __restrict__ idx_out = out.idx;
+    double* __restrict__ d2_out = out.d2;
+    double* __restrict__ avg_out = out.avg;
+    if (avg_out) {  // statistical removal: the distances one at a time in ascending (d2, j), from 0.0
+      double acc = 0.0;
+      for (int t = 0; t < m; ++t) acc += sqrt(ld[t][lane]);
+      avg_out[d.t_off + i] = acc / (double)m;
+    } else {
+      const int64_t base = kd.out_off + i * kd.k;
+      for (int t = 0; t < kd.k; ++t) {
+        idx_out[base + t] = t < m ? lj[t][lane] : -1;
+        d2_out[base + t] = t < m ? ld[t][lane] : INFINITY;
+      }
     }
   }
 }
 
-// The whole-cloud route: block (one wave) w, w + gridDim.x, ... of the worklist.
 template <int CAP>
-__global__ __launch_bounds__(kIcpCovBlock) void icp_knn_scan_kernel(
-    const IcpDesc* __restrict__ descs, const IcpKnnDesc* __restrict__ knns, const double* __restrict__ q,
-    int32_t* __restrict__ idx_out, double* __restrict__ d2_out, double* __restrict__ avg_out,
-    const int32_t* __restrict__ work, const int32_t* __restrict__ work_count) {
+__global__ __launch_bounds__(kIcpCovBlock) void icp_knn_ring_kernel(
+    const IcpDesc* __restrict__ descs, const IcpKnnDesc* __restrict__ knns, const int32_t* __restrict__ blk_prob,
+    const double* __restrict__ q, const double* __restrict__ qs, const int32_t* __restrict__ qj,
+    const int32_t* __restrict__ bstart, int32_t* __restrict__ idx_out, double* __restrict__ d2_out,
+    double* __restrict__ avg_out, int32_t* __restrict__ work, int32_t* __restrict__ work_count) {
+  __shared__ double ld[CAP][kIcpCovBlock];  // slot-major: lane l owns ld[.][l]
+  __shared__ int32_t lj[CAP][kIcpCovBlock];
+  const IcpKnnListOut out = {idx_out, d2_out, avg_out};
+  icp_knn_ring<CAP>(ld, lj, descs, knns, blk_prob, q, qs, qj, bstart, out, work, work_count);
+}
+
+template <int CAP>
+__global__ __launch_bounds__(kIcpCovBlock) void icp_knn_ring_normals_kernel(
+    const IcpDesc* __restrict__ descs, const IcpKnnDesc* __restrict__ knns, const int32_t* __restrict__ blk_prob,
+    const double* __restrict__ q, const double* __restrict__ qs, const int32_t* __restrict__ qj,
+    const int32_t* __restrict__ bstart, const IcpKnnNormalOut out, int32_t* __restrict__ work,
+    int32_t* __restrict__ work_count) {
   __shared__ double ld[CAP][kIcpCovBlock];
   __shared__ int32_t lj[CAP][kIcpCovBlock];
+  icp_knn_ring<CAP>(ld, lj, descs, knns, blk_prob, q, qs, qj, bstart, out, work, work_count);
+}
+
+// The whole-cloud route: block (one wave) w, w + gridDim.x, ... of the worklist.
+template <int CAP, class Out>
+__device__ __forceinline__ void icp_knn_scan(double (*ld)[kIcpCovBlock], int32_t (*lj)[kIcpCovBlock],
+                                             const IcpDesc* __restrict__ descs, const IcpKnnDesc* __restrict__ knns,
+                                             const double* __restrict__ q, const Out& out,
+                                             const int32_t* __restrict__ work,
+                                             const int32_t* __restrict__ work_count) {
   const int lane = threadIdx.x;
   const int32_t total = *work_count;
   for (int32_t w = blockIdx.x; w < total; w += gridDim.x) {  // uniform over the wave
@@ -143,6 +168,8 @@ __global__ __launch_bounds__(kIcpCovBlock) void icp_knn_scan_kernel(
     int head = 0;
     double acc = 0.0;
     const int64_t base = kd.out_off + i * kd.k;
+    // normal estimation: every lane sees each merged element after the butterfly; lane 0 keeps the sums and stores
+    double s1[3] = {0.0, 0.0, 0.0}, s2[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
     for (int t = 0; t < want; ++t) {
       const double hd = head < m ? ld[head][lane] : INFINITY;
       const int32_t hj = head < m ? lj[head][lane] : INT32_MAX;
@@ -158,24 +185,50 @@ __global__ __launch_bounds__(kIcpCovBlock) void icp_knn_scan_kernel(
         }
       }
       if (head < m && mj == hj) ++head;
-      if (avg_out) {
+      if constexpr (Out::kNormals) {
+        if (lane == 0) icp_cov_add(s1, s2, q + 3 * (d.t_off + mj), x);  // mj < n_t: want <= n_t real entries exist
+      } else if (out.avg) {
         acc += sqrt(md);
       } else if (lane == 0) {
-        idx_out[base + t] = mj;
-        d2_out[base + t] = md;
+        out.idx[base + t] = mj;
+        out.d2[base + t] = md;
       }
     }
     if (lane == 0) {
-      if (avg_out) {
-        avg_out[d.t_off + i] = acc / (double)want;
+      if constexpr (Out::kNormals) {
+        double a[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+        if (want >= 3) icp_cov_finish(s1, s2, want, a);
+        icp_normal_store(out, out.nd[p], i, x, want, a);
+      } else if (out.avg) {
+        out.avg[d.t_off + i] = acc / (double)want;
       } else {
         for (int t = want; t < kd.k; ++t) {
-          idx_out[base + t] = -1;
-          d2_out[base + t] = INFINITY;
+          out.idx[base + t] = -1;
+          out.d2[base + t] = INFINITY;
         }
       }
     }
   }
+}
+
+template <int CAP>
+__global__ __launch_bounds__(kIcpCovBlock) void icp_knn_scan_kernel(
+    const IcpDesc* __restrict__ descs, const IcpKnnDesc* __restrict__ knns, const double* __restrict__ q,
+    int32_t* __restrict__ idx_out, double* __restrict__ d2_out, double* __restrict__ avg_out,
+    const int32_t* __restrict__ work, const int32_t* __restrict__ work_count) {
+  __shared__ double ld[CAP][kIcpCovBlock];
+  __shared__ int32_t lj[CAP][kIcpCovBlock];
+  const IcpKnnListOut out = {idx_out, d2_out, avg_out};
+  icp_knn_scan<CAP>(ld, lj, descs, knns, q, out, work, work_count);
+}
+
+template <int CAP>
+__global__ __launch_bounds__(kIcpCovBlock) void icp_knn_scan_normals_kernel(
+    const IcpDesc* __restrict__ descs, const IcpKnnDesc* __restrict__ knns, const double* __restrict__ q,
+    const IcpKnnNormalOut out, const int32_t* __restrict__ work, const int32_t* __restrict__ work_count) {
+  __shared__ double ld[CAP][kIcpCovBlock];
+  __shared__ int32_t lj[CAP][kIcpCovBlock];
+  icp_knn_scan<CAP>(ld, lj, descs, knns, q, out, work, work_count);
 }
 
 // ---- statistical removal: mean, std, threshold, mask -----------------------------------------------------------
@@ -312,6 +365,18 @@ static void icp_self_knn(hipStream_t s, const IcpDesc* d_desc, const IcpKnnDesc*
                      d_avg, d_work, d_work_count);
 }
 
+template <int CAP>
+static void icp_normals_knn(hipStream_t s, const IcpDesc* d_desc, const IcpKnnDesc* d_knn, const int32_t* d_blk_prob,
+                            int n_blk, const double* d_q, const double* d_qs, const int32_t* d_qj,
+                            const int32_t* d_bstart, const IcpKnnNormalOut& out, int32_t* d_work,
+                            int32_t* d_work_count) {
+  hipLaunchKernelGGL(icp_knn_ring_normals_kernel<CAP>, dim3(n_blk), dim3(kIcpCovBlock), 0, s, d_desc, d_knn,
+                     d_blk_prob, d_q, d_qs, d_qj, d_bstart, out, d_work, d_work_count);
+  const int scan = n_blk < kIcpKnnScanBlocks ? n_blk : kIcpKnnScanBlocks;
+  hipLaunchKernelGGL(icp_knn_scan_normals_kernel<CAP>, dim3(scan), dim3(kIcpCovBlock), 0, s, d_desc, d_knn, d_q, out,
+                     d_work, d_work_count);
+}
+
 void launch_icp_self_knn(hipStream_t s, const IcpDesc* d_desc, const IcpKnnDesc* d_knn, const int32_t* d_blk_prob,
                          int n_blk, int top_k, const double* d_q, const double* d_qs, const int32_t* d_qj,
                          const int32_t* d_bstart, int32_t* d_idx, double* d_d2, double* d_avg, int32_t* d_work,
@@ -323,6 +388,21 @@ void launch_icp_self_knn(hipStream_t s, const IcpDesc* d_desc, const IcpKnnDesc*
   else
     icp_self_knn<kIcpKnnMax>(s, d_desc, d_knn, d_blk_prob, n_blk, d_q, d_qs, d_qj, d_bstart, d_idx, d_d2, d_avg,
                              d_work, d_work_count);
+}
+
+void launch_icp_normals_knn(hipStream_t s, const IcpDesc* d_desc, const IcpKnnDesc* d_knn, const IcpNormalDesc* d_nd,
+                            const int32_t* d_blk_prob, int n_blk, int top_k, const double* d_q, const double* d_qs,
+                            const int32_t* d_qj, const int32_t* d_bstart, double* d_nrm, double* d_cov, double* d_eig,
+                            int32_t* d_work, int32_t* d_work_count) {
+  if (n_blk <= 0) return;
+  IcpKnnNormalOut out;
+  out.nd = d_nd, out.nrm = d_nrm, out.cov = d_cov, out.eig = d_eig;
+  if (top_k <= kIcpKnnSmall)
+    icp_normals_knn<kIcpKnnSmall>(s, d_desc, d_knn, d_blk_prob, n_blk, d_q, d_qs, d_qj, d_bstart, out, d_work,
+                                  d_work_count);
+  else
+    icp_normals_knn<kIcpKnnMax>(s, d_desc, d_knn, d_blk_prob, n_blk, d_q, d_qs, d_qj, d_bstart, out, d_work,
+                                d_work_count);
 }
 
 void launch_icp_statistical(hipStream_t s, const IcpDesc* d_desc, const IcpKnnDesc* d_knn,

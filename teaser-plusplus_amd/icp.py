@@ -33,6 +33,14 @@ class IcpEstimationC(C.Structure):
     _fields_ = [("method", C.c_int32), ("kernel", C.c_int32), ("kernel_k", C.c_double)]
 
 
+class IcpNormalSearchC(C.Structure):
+    _fields_ = [("search", C.c_int32), ("max_nn", C.c_int32), ("radius", C.c_double), ("orient", C.c_int32),
+                ("reserved", C.c_int32), ("ref", C.c_double * 3)]
+
+
+assert C.sizeof(IcpNormalSearchC) == 48  # teaser_icp_normal_search_c: the header asserts the same
+
+
 def declare(L):
     """ctypes signatures of the ICP entry points (called by the package's lib())."""
     L.teaser_hip_icp_params_default.argtypes = [C.POINTER(IcpParamsC)]
@@ -50,6 +58,10 @@ def declare(L):
     L.teaser_hip_icp_batch_cov.argtypes = L.teaser_hip_icp_batch_ex.argtypes + [C.POINTER(_dp), C.POINTER(_dp)]
     L.teaser_hip_icp_solve_cov.argtypes = L.teaser_hip_icp_solve_ex.argtypes + [_dp, _dp]
     L.teaser_hip_icp_covariances_batch.argtypes = [_vp, C.c_int32, C.POINTER(_dp), _ip, _dp, _ip, _dp, C.POINTER(_dp)]
+    L.teaser_hip_icp_normals_batch.argtypes = [_vp, C.c_int32, C.POINTER(_dp), _ip, C.POINTER(IcpNormalSearchC),
+                                               C.POINTER(_dp), C.POINTER(_dp), C.POINTER(_dp)]
+    L.teaser_hip_icp_batch_auto.argtypes = L.teaser_hip_icp_batch_cov.argtypes + [C.POINTER(IcpNormalSearchC)]
+    L.teaser_hip_icp_solve_auto.argtypes = L.teaser_hip_icp_solve_cov.argtypes + [C.POINTER(IcpNormalSearchC)]
 
 
 class ICPConvergenceCriteria:
@@ -165,6 +177,63 @@ _cache = HandleCache("teaser_hip_icp")
 _handle = _cache.get
 
 
+class _NormalSearch:
+    """A neighbourhood for normal estimation, optionally with an orientation: ``.towards(point)`` (Open3D's
+    orient_normals_towards_camera_location) or ``.along(direction)`` (orient_normals_to_align_with_direction) return
+    a copy with that orientation."""
+    search = 0
+
+    def __init__(self, radius, max_nn):
+        self.radius, self.max_nn = float(radius), int(max_nn)
+        self.orient, self.ref = 0, (0.0, 0.0, 0.0)
+        if not 3 <= self.max_nn <= MAX_NN_LIMIT:
+            raise ValueError("max_nn / knn must lie in [3, %d]" % MAX_NN_LIMIT)
+
+    def _oriented(self, orient, ref, what):
+        v = np.asarray(ref, dtype=np.float64).ravel()
+        if v.shape != (3,) or not np.isfinite(v).all():
+            raise ValueError("%s must be 3 finite numbers" % what)
+        out = type(self).__new__(type(self))
+        out.__dict__.update(self.__dict__)
+        out.orient, out.ref = orient, tuple(float(x) for x in v)
+        return out
+
+    def towards(self, point):
+        return self._oriented(1, point, "towards")
+
+    def along(self, direction):
+        return self._oriented(2, direction, "along")
+
+    def record(self):
+        return IcpNormalSearchC(self.search, self.max_nn, self.radius, self.orient, 0, (C.c_double * 3)(*self.ref))
+
+
+class KDTreeSearchParamHybrid(_NormalSearch):
+    """Open3D's KDTreeSearchParamHybrid(radius, max_nn): the max_nn nearest neighbours inside radius."""
+    search = 0
+
+    def __init__(self, radius, max_nn):
+        super().__init__(radius, max_nn)
+        if not (np.isfinite(self.radius) and self.radius > 0):
+            raise ValueError("radius must be finite and > 0")
+
+    def __repr__(self):
+        return "KDTreeSearchParamHybrid(radius=%g, max_nn=%d)" % (self.radius, self.max_nn)
+
+
+class KDTreeSearchParamKNN(_NormalSearch):
+    """Open3D's KDTreeSearchParamKNN(knn): the knn nearest neighbours, no radius.  (KDTreeSearchParamRadius, a radius
+    without a cap, is not offered: include/teaser_hip.h, "Normal estimation".)"""
+    search = 1
+
+    def __init__(self, knn=30):
+        super().__init__(0.0, knn)
+        self.knn = self.max_nn
+
+    def __repr__(self):
+        return "KDTreeSearchParamKNN(knn=%d)" % self.max_nn
+
+
 def _points(a, what):
     return _cloud(a, what, kind="array of points")
 
@@ -225,7 +294,8 @@ def registration_icp_batch(sources, targets, max_correspondence_distance, inits=
     """One launch sequence for many independent problems (mixed sizes allowed).  max_correspondence_distance and
     criteria: one value for all or one per problem; inits: None (identity), one 4 x 4 for all, or one per problem;
     estimation_methods: None (point-to-point), one for all or one per problem; target_normals: None, or one entry per
-    problem (None for a point-to-point problem, else one normal per target point); source_covariances /
+    problem (None for a point-to-point problem, else one normal per target point, or a KDTreeSearchParamHybrid /
+    KDTreeSearchParamKNN object: the normals are then estimated from the target on the device); source_covariances /
     target_covariances: None, or one entry per problem (None unless the problem is Generalized ICP, else n x 3 x 3).
     Returns a list of RegistrationResult, each identical to the same problem run alone."""
     from . import lib
@@ -240,6 +310,7 @@ def registration_icp_batch(sources, targets, max_correspondence_distance, inits=
     ests = [_estimation(m) for m in ests]
     plane = any(m[0] == 1 for m in ests)
     normals = [None] * b
+    searches = [None] * b  # a search-parameter object in place of normals: they are estimated on the device
     if plane:
         if target_normals is None or len(target_normals) != b:
             raise ValueError("point-to-plane needs target_normals: one entry per problem")
@@ -248,6 +319,9 @@ def registration_icp_batch(sources, targets, max_correspondence_distance, inits=
                 continue
             if target_normals[k] is None:
                 raise ValueError("point-to-plane needs target_normals (problem %d)" % k)
+            if isinstance(target_normals[k], _NormalSearch):
+                searches[k] = target_normals[k]
+                continue
             nv = _points(target_normals[k], "target_normals")
             if nv.shape != dsts[k].shape:
                 raise ValueError("target_normals must have the target's shape %s, got %s (problem %d)"
@@ -287,6 +361,12 @@ def registration_icp_batch(sources, targets, max_correspondence_distance, inits=
         fn = L.teaser_hip_icp_batch_cov
         args += ((_dp * max(b, 1))(*[None if c is None else c.ctypes.data_as(_dp) for c in cov_s]),
                  (_dp * max(b, 1))(*[None if c is None else c.ctypes.data_as(_dp) for c in cov_t]))
+    if any(sp_ is not None for sp_ in searches):  # the entry that estimates missing target normals itself
+        if not gicp:
+            args += (None, None)
+        fn = L.teaser_hip_icp_batch_auto
+        args += ((IcpNormalSearchC * max(b, 1))(*[IcpNormalSearchC() if sp_ is None else sp_.record()
+                                                   for sp_ in searches]),)
     _handle(device).call(fn, *args)
     res = []
     for k in range(b):
@@ -303,7 +383,8 @@ def registration_icp(source, target, max_correspondence_distance, init=np.eye(4)
     """Open3D's registration_icp (same argument order): refines `init` so that it maps source onto target.
     source / target: n x 3 points (np.asarray(pcd.points)).  estimation_method: None or
     TransformationEstimationPointToPoint() (with_scaling=False), or TransformationEstimationPointToPlane(kernel), which
-    needs target_normals (n_t x 3, np.asarray(target_pcd.normals)), or TransformationEstimationForGeneralizedICP(),
+    needs target_normals (n_t x 3, np.asarray(target_pcd.normals), or a KDTreeSearchParamHybrid / KDTreeSearchParamKNN
+    object to estimate them from the target on the device), or TransformationEstimationForGeneralizedICP(),
     which needs source_covariances (n_s x 3 x 3) and target_covariances (n_t x 3 x 3)."""
     if estimation_method is not None and not isinstance(
             estimation_method, (TransformationEstimationPointToPoint, TransformationEstimationPointToPlane,
@@ -368,6 +449,54 @@ def estimate_covariances_batch(clouds, radius, max_nn=20, epsilon=1e-3, device=-
     op = (_dp * b)(*[o.ctypes.data_as(_dp) for o in out])
     _handle(device).call(lib().teaser_hip_icp_covariances_batch, b, pp, n.ctypes.data_as(_ip),
                          rs.ctypes.data_as(_dp), ks.ctypes.data_as(_ip), es.ctypes.data_as(_dp), op)
+    return out
+
+
+def estimate_normals_batch(clouds, search_param, towards=None, along=None, covariances=False, eigenvalues=False,
+                           device=-1):
+    """Normals of many clouds in one launch sequence (include/teaser_hip.h, "Normal estimation"; Open3D's
+    estimate_normals).  search_param: a KDTreeSearchParamHybrid or KDTreeSearchParamKNN for all clouds or one per
+    cloud; towards / along: None, or a point / direction (for all clouds) the normals are oriented by, overriding the
+    search parameter's own orientation.  Returns a list with one entry per cloud: the n x 3 normals, or a tuple
+    (normals[, covariances n x 3 x 3 (the raw sample covariances)][, eigenvalues n x 3 ascending]) when asked for.
+    Each cloud's result is identical to the same cloud estimated alone."""
+    from . import lib
+    pts = [_points(c, "points") for c in clouds]
+    b = len(pts)
+    sps = list(search_param) if isinstance(search_param, (list, tuple)) else [search_param] * b
+    if len(sps) != b or not all(isinstance(p, _NormalSearch) for p in sps):
+        raise ValueError("search_param: a KDTreeSearchParamHybrid / KDTreeSearchParamKNN, one for all or one per cloud")
+    if towards is not None and along is not None:
+        raise ValueError("towards and along exclude each other")
+    if towards is not None:
+        sps = [p.towards(towards) for p in sps]
+    if along is not None:
+        sps = [p.along(along) for p in sps]
+    nrm = [np.empty((len(p), 3)) for p in pts]
+    cov = [np.empty((len(p), 3, 3)) for p in pts] if covariances else None
+    eig = [np.empty((len(p), 3)) for p in pts] if eigenvalues else None
+    if b:
+        n = np.array([len(p) for p in pts], dtype=np.int32)
+        ptrs = lambda arrs: None if arrs is None else (_dp * b)(*[a.ctypes.data_as(_dp) for a in arrs])  # noqa: E731
+        _handle(device).call(lib().teaser_hip_icp_normals_batch, b, ptrs(pts), n.ctypes.data_as(_ip),
+                             (IcpNormalSearchC * b)(*[p.record() for p in sps]), ptrs(nrm), ptrs(cov), ptrs(eig))
+    if not covariances and not eigenvalues:
+        return nrm
+    return [tuple(x[k] for x in (nrm, cov, eig) if x is not None) for k in range(b)]
+
+
+def estimate_normals(points, search_param, towards=None, along=None, covariances=False, eigenvalues=False, device=-1):
+    """estimate_normals_batch for one cloud: n x 3 points -> n x 3 unit normals (or the tuple described there)."""
+    return estimate_normals_batch([points], search_param, towards, along, covariances, eigenvalues, device)[0]
+
+
+def surface_variation(eigenvalues):
+    """lambda0 / (lambda0 + lambda1 + lambda2) per row of ascending eigenvalues (estimate_normals(...,
+    eigenvalues=True)); 0 where the sum is 0."""
+    e = np.asarray(eigenvalues, dtype=np.float64)
+    s = (e[..., 0] + e[..., 1]) + e[..., 2]
+    out = np.zeros(s.shape)
+    np.divide(e[..., 0], s, out=out, where=s != 0)
     return out
 
 
