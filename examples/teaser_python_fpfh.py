@@ -10,6 +10,12 @@ on the MI355X.  Usage:
                                           [--icp-plane-normals hybrid:R:K|knn:K]
                                           [--icp-gicp [--gicp-radius R --gicp-max-nn K]] [--batch K]
                                           [--knn K [--no-mutual]] [--tuple-scale S [--tuple-seed N]]
+                                          [--iss [--iss-radii RS,RN]]
+
+--iss detects ISS keypoints (Open3D's compute_iss_keypoints) in both down-sampled clouds on the GPU and matches only
+them: FPFH is still computed on the whole clouds (its neighbourhoods need every point), the descriptor rows at the
+keypoints go to the matcher, and the returned pairs are mapped back to cloud indices.  --iss-radii RS,RN gives the
+salient and the suppression radius; the default takes 6 and 4 times each cloud's resolution, like Open3D.
 
 --knn K matches every point with its K nearest descriptors (helpers.py:19-43, find_knn_cpu(feat0, feat1, knn=K)) in
 place of the single mutual nearest neighbour: more putative correspondences for the solver, on the GPU as well.  Only
@@ -154,7 +160,13 @@ def main():
     ap.add_argument("--remove-outliers", default="", metavar="NB,RATIO",
                     help="clean both clouds after down-sampling with statistical outlier removal on the GPU "
                          "(Open3D's remove_statistical_outlier(NB, RATIO), e.g. 20,2.0)")
+    ap.add_argument("--iss", action="store_true",
+                    help="match only the ISS keypoints of both clouds (detected on the GPU); single pair only")
+    ap.add_argument("--iss-radii", default="", metavar="RS,RN",
+                    help="with --iss: salient and non-maximum-suppression radius (default: 6 and 4 resolutions)")
     a = ap.parse_args()
+    if a.iss and a.batch > 0:
+        ap.error("--iss registers a single pair: it cannot be combined with --batch")
     if a.batch > 0:
         if len(a.clouds) == 2:
             A, B = (read_ply_xyz(c).astype(np.float64) for c in a.clouds)
@@ -188,6 +200,16 @@ def main():
     fa = est.computeFPFHFeatures(A, 2 * vox, 5 * vox)   # helpers.py:9-18: radii 2 and 5 voxels
     fb = est.computeFPFHFeatures(B, 2 * vox, 5 * vox)
     nb = est.getNormals()   # the target's normals: point-to-plane ICP refines on them
+    full = (A, B)
+    if a.iss:  # the matcher sees the keypoints only; `keys` maps its pairs back to cloud indices
+        rs, rn = (float(v) for v in a.iss_radii.split(",")) if a.iss_radii else (0.0, 0.0)
+        t = time.perf_counter()
+        keys = tp.compute_iss_keypoints_batch([A, B], rs, rn)
+        print("ISS keypoints: %d of %d / %d of %d points (%.1f ms)" % (len(keys[0]), len(A), len(keys[1]), len(B),
+                                                                       1e3 * (time.perf_counter() - t)))
+        if min(map(len, keys)) < 3:
+            sys.exit("fewer than 3 keypoints in a cloud: nothing to match")
+        A, B, fa, fb = A[keys[0]], B[keys[1]], fa[keys[0]], fb[keys[1]]
     if a.knn:
         corr = tp.match_features_knn(fa, fb, a.knn, not a.no_mutual)   # helpers.py:19-43
         if a.tuple_scale:
@@ -196,6 +218,9 @@ def main():
     else:
         corr = tp.Matcher().calculateCorrespondences(A, B, fa, fb, False, True, bool(a.tuple_scale), a.tuple_scale,
                                                      a.tuple_seed)   # helpers.py:27-43
+    if a.iss:
+        corr = [(int(keys[0][i]), int(keys[1][j])) for i, j in corr]
+        A, B = full
     t1 = time.perf_counter()
     params = tp.RobustRegistrationSolver.Params(noise_bound=vox, cbar2=1.0, estimate_scaling=False,
                                                 rotation_gnc_factor=1.4, rotation_max_iterations=10000,

@@ -670,7 +670,8 @@ TEASER_HIP_API int32_t teaser_hip_icp_covariances_batch(teaser_hip_icp* icp, int
  *                  (The rules of Open3D's orient_normals_towards_camera_location and
  *                  orient_normals_to_align_with_direction; bit parity with Open3D is not claimed.)
  * Radius-only search (Open3D's KDTreeSearchParamRadius: no cap on the neighbours) is NOT offered: the sums are ordered
- * sums over a bounded sorted list, and without a cap there is no such list.
+ * sums over a bounded sorted list, and without a cap there is no such list.  (ISS keypoints below sum an uncapped
+ * radius neighbourhood in another, stated order.)
  * normals_out[b]: n[b] x 3 doubles.  cov_out: NULL, or per cloud NULL or n x 9 doubles.  eig_out: NULL, or per cloud NULL
  * or n x 3 doubles.  Empty clouds are legal.  Deterministic like every call on this handle: the same bits alone, inside
  * any batch, run after run; for k-NN search independent of "knn_ring_cap", and "knn_fallbacks" is updated (a call
@@ -765,6 +766,63 @@ TEASER_HIP_API int32_t teaser_hip_icp_remove_radius_outliers_batch(teaser_hip_ic
                                                                    const int32_t* nb_points, const double* radius,
                                                                    uint8_t* const* keep_out, int32_t* n_kept_out,
                                                                    int32_t* const* count_out);
+/* ISS keypoints (Open3D's compute_iss_keypoints, PCL's ISSKeypoint3D), on the ICP handle: a batch of clouds (n x 3
+ * doubles each) with one parameter record per cloud.  Nothing is fused; d2 = ((dx dx + dy dy) + dz dz),
+ * dx = P[i].x - P[j].x, as everywhere on this handle.  Per cloud:
+ *   resolution   (Open3D's ComputeModelResolution) only when salient_radius == 0 || non_max_radius == 0:
+ *                res = SUM_i sqrt(d2 of slot 1 of point i's self k-NN with k = 2) / n, SUM the 256-index block rule of
+ *                statistical outlier removal above; res = 0 when n < 2.  Then BOTH radii are replaced, as Open3D does:
+ *                r_s = 6 res, r_n = 4 res.  Otherwise r_s, r_n are as given.
+ *   no radius    a cloud whose r_s r_s or r_n r_n is not > 0 after this step (an empty cloud, n = 1 or identical points
+ *                under automatic radii, a radius whose square underflows): no j has d2 < 0, so there are no neighbours
+ *                and no keypoints; m = cnt = 0, saliency 0.  No grid is built and nothing divides by it.
+ *   salient      neighbourhood of i: every j, i included, with d2 < r_s r_s.  NO cap.  m = their number.
+ *   sum order    c(j) = the cell coordinates the handle's grid gives point j for radius r_s over this cloud: per axis a
+ *                floor((P[j].a - lo_a) * (1 / h)) clamped to [-2, 2^40], lo = the bounding box's minimum,
+ *                h = r_s (1 + 1e-6) + 1e-12 max |bounding-box coordinate|.  The neighbours are added one at a time from
+ *                0 in ascending (c_x, c_y, c_z, j):  o = P[j] - P[i];  S1 = sum o;  S2 = sum o o^T (upper triangle);
+ *                cov[a][b] = (S2[a][b] - (S1[a] S1[b]) / m) / m   (the POPULATION covariance of Open3D's
+ *                ComputeCovariance).  This is the one place a contract names the grid: an order by (d2, j) needs a sort
+ *                of an unbounded list per point, an order by j alone a 27-way merge; the cell order is the order a
+ *                sorted grid stores the points in, so the sum is taken while streaming (voxel down-sampling fixes its
+ *                output order the same way).
+ *   saliency     sal[i] = 0 when m < min_neighbors.  Otherwise the cyclic Jacobi of the covariance contract above, word
+ *                for word, and its three diagonal entries in ascending order e3 <= e2 <= e1 (three exchanges);
+ *                sal[i] = e3 when e2 / e1 < gamma_21 and e3 / e2 < gamma_32, else 0.  IEEE divisions: 0 / 0 is NaN and
+ *                a comparison with NaN is false, so a neighbourhood of copies gives 0 with nothing special-cased.
+ *   suppression  cnt[i] = the number of j, i included, with d2 < r_n r_n.  Point i is a keypoint iff sal[i] > 0 and
+ *                cnt[i] >= min_neighbors and no such j has sal[j] > sal[i] (ties survive together: Open3D's
+ *                IsLocalMaxima with its strict <).  Any ratio r_n / r_s is served.
+ * keep_out[b]: n bytes (0 / 1); n_keypoints_out[b]: int32; saliency_out (NULL, or per cloud NULL or) n doubles; count_out
+ * (NULL, or per cloud NULL or) n x 2 int32 (m, cnt); radii_out: NULL or 3 doubles per cloud (res, NaN when it was not
+ * computed; r_s; r_n).  The mask is the result: the host compacts nothing.  Empty clouds are legal.  Deterministic like
+ * every call on this handle: the same bits alone, inside any batch, run after run; clouds of mixed sizes share the
+ * launches.  "knn_fallbacks" is updated by the resolution's self k-NN (0 when no cloud asks for automatic radii).
+ * TEASER_HIP_ERR_BAD_ARG (argument and cloud named): non-finite points; a radius that is negative or whose value or
+ * square is not finite (also an automatic one); non-finite gammas; a negative min_neighbors; reserved != 0; NULL where
+ * n > 0; and a radius so small against the cloud's extent that the cell keys of the call (grid id, c_x, c_y, c_z, each
+ * with the bits its largest value needs) exceed 63 bits.  The handle stays usable after a refusal. */
+typedef struct teaser_icp_iss_params_c {
+  double salient_radius; /* >= 0; 0 (in either radius): both radii from the resolution */
+  double non_max_radius; /* >= 0 */
+  double gamma_21;       /* default 0.975 */
+  double gamma_32;       /* default 0.975 */
+  int32_t min_neighbors; /* >= 0, default 5 */
+  int32_t reserved;      /* 0 */
+} teaser_icp_iss_params_c;
+#ifdef __cplusplus
+static_assert(sizeof(teaser_icp_iss_params_c) == 40, "teaser_icp_iss_params_c is 40 bytes");
+#else
+_Static_assert(sizeof(teaser_icp_iss_params_c) == 40, "teaser_icp_iss_params_c is 40 bytes");
+#endif
+/* Open3D's defaults: radii 0 (automatic), gammas 0.975, min_neighbors 5. */
+TEASER_HIP_API int32_t teaser_hip_icp_iss_params_default(teaser_icp_iss_params_c* params);
+TEASER_HIP_API int32_t teaser_hip_icp_iss_keypoints_batch(teaser_hip_icp* icp, int32_t batch,
+                                                          const double* const* points, const int32_t* n,
+                                                          const teaser_icp_iss_params_c* params,
+                                                          uint8_t* const* keep_out, int32_t* n_keypoints_out,
+                                                          double* const* saliency_out, int32_t* const* count_out,
+                                                          double* radii_out);
 /* Options of an ICP handle (none changes a result).  "knn_ring_cap" (0 .. 16, default 4): the number of rings self
  * k-NN and statistical removal search on the grid before a query goes to the whole-cloud scan; 0 sends every query
  * there.  "knn_fallbacks" (read-only): how many queries of the handle's last self k-NN or statistical-removal call the

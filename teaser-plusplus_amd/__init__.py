@@ -137,6 +137,7 @@ EXPORTED_SYMBOLS = [
     "teaser_hip_icp_solve_auto",
     "teaser_hip_icp_self_knn_batch", "teaser_hip_icp_remove_statistical_outliers_batch",
     "teaser_hip_icp_remove_radius_outliers_batch", "teaser_hip_icp_set_option", "teaser_hip_icp_get_option",
+    "teaser_hip_icp_iss_params_default", "teaser_hip_icp_iss_keypoints_batch",
     "teaser_hip_voxel_create", "teaser_hip_voxel_destroy", "teaser_hip_voxel_last_error",
     "teaser_hip_voxel_down_sample_batch", "teaser_hip_voxel_down_sample",
     "teaser_hip_features_create", "teaser_hip_features_destroy", "teaser_hip_features_last_error",
@@ -231,6 +232,8 @@ def lib():
     _icp.declare(L)
     from . import outlier as _outlier
     _outlier.declare(L)
+    from . import keypoints as _keypoints
+    _keypoints.declare(L)
     from . import voxel as _voxel
     _voxel.declare(L)
     from . import features as _features
@@ -1086,6 +1089,7 @@ from .icp import (CauchyLoss, GMLoss, HuberLoss, ICPConvergenceCriteria, L2Loss,
 from .voxel import voxel_down_sample, voxel_down_sample_batch  # noqa: E402
 from .outlier import (remove_radius_outlier, remove_radius_outlier_batch, remove_statistical_outlier,  # noqa: E402
                       remove_statistical_outlier_batch, self_knn, self_knn_batch, get_icp_option, set_icp_option)
+from .keypoints import compute_iss_keypoints, compute_iss_keypoints_batch  # noqa: E402
 from .features import (compute_fpfh_batch, correspondences_batch, match_features_batch,  # noqa: E402
                        knn_features, knn_features_batch, match_features_knn, match_features_knn_batch,
                        correspondences_knn, correspondences_knn_batch, tuple_test_batch)
@@ -1103,4 +1107,5 @@ __all__ = ["batched", "FPFHEstimation", "Matcher", "MultiDeviceSolver", "RobustR
            "estimate_covariances_batch", "covariances_from_normals", "KDTreeSearchParamHybrid", "KDTreeSearchParamKNN",
            "estimate_normals", "estimate_normals_batch", "surface_variation",
            "remove_statistical_outlier", "remove_statistical_outlier_batch", "remove_radius_outlier",
-           "remove_radius_outlier_batch", "self_knn", "self_knn_batch", "get_icp_option", "set_icp_option"]
+           "remove_radius_outlier_batch", "self_knn", "self_knn_batch", "get_icp_option", "set_icp_option",
+           "compute_iss_keypoints", "compute_iss_keypoints_batch"]

@@ -1,5 +1,6 @@
 // icp_host.h -- what the host files of the ICP handle (icp.hip: the iteration loop, covariance estimation, self k-NN and
-// outlier removal; icp_normals.hip: normal estimation and the self-estimating point-to-plane entry) share: the handle,
+// outlier removal; icp_normals.hip: normal estimation and the self-estimating point-to-plane entry; icp_keypoints.hip:
+// ISS keypoints) share: the handle,
 // its buffers, the per-call index under construction and the uploads.
 #pragma once
 
@@ -17,9 +18,12 @@
 namespace thip {
 
 // B_N*: the descriptors, records and block maps of the normal estimation that precedes the iterations of
-// teaser_hip_icp_batch_auto (its other buffers are the ICP's own)
+// teaser_hip_icp_batch_auto (its other buffers are the ICP's own).  B_K*: the sorted cell index of ISS keypoint
+// detection (icp_keypoints.hip): descriptors, block map, keys and entries before and after the sort, the sorted points
+// and the sort's scratch
 enum { B_DESC, B_STATE, B_BLK, B_TBLK, B_X, B_Q, B_TBUCKET, B_BCOUNT, B_BSTART, B_CURSOR, B_QS, B_QJ, B_MATCH,
-       B_PARTIALS, B_LIVE, B_NORMALS, B_COV_S, B_COV_T, B_NDESC, B_NKNN, B_NREC, B_NBLK, B_NTBLK, B_COUNT };
+       B_PARTIALS, B_LIVE, B_NORMALS, B_COV_S, B_COV_T, B_NDESC, B_NKNN, B_NREC, B_NBLK, B_NTBLK, B_KDESC, B_KBLK,
+       B_KKEY, B_KIOTA, B_KSKEY, B_KSIDX, B_KSPTS, B_KTEMP, B_COUNT };
 
 }  // namespace thip
 
