@@ -40,6 +40,47 @@ def cells(P, r):
     return np.clip(v, -2.0, 1099511627776.0).astype(np.int64)
 
 
+def bits_for(v):
+    """Number of bits that hold every value in [0, v]."""
+    return int(v).bit_length()
+
+
+def key_bits(clouds, r_s, r_n, details=False):
+    """The width of the call's cell keys (icp_keypoints.hip, "descriptors, grids and the key layout"): per cloud with
+    neighbours to find (n > 0, both radii squared > 0) each grid needs the sum over the axes of bits_for(its largest
+    cell coordinate); the cell field is as wide as the wider grid of the widest cloud, and the grid id above it
+    (cloud b: b for r_s, batch + b for r_n) is bits_for(2 batch - 1) wide.  r_s, r_n: one value for all clouds or one
+    per cloud, 0 meaning automatic as in iss_keypoints.  details=True: (bits, cell bits, id bits, [(w_s, w_n) per
+    cloud]).  A call is served up to 63 bits."""
+    b = len(clouds)
+    r_s = np.broadcast_to(np.asarray(r_s, dtype=np.float64), (b,))
+    r_n = np.broadcast_to(np.asarray(r_n, dtype=np.float64), (b,))
+    widths = []
+    for c, rs, rn in zip(clouds, r_s, r_n):
+        P = np.asarray(c, dtype=np.float64).reshape(-1, 3)
+        _, rs, rn = radii(P, rs, rn)
+        if len(P) == 0 or not rs * rs > 0 or not rn * rn > 0:
+            widths.append((0, 0))
+            continue
+        widths.append(tuple(sum(bits_for(m) for m in cells(P, r).max(axis=0)) for r in (rs, rn)))
+    cell_bits = max([max(w) for w in widths], default=0)
+    id_bits = bits_for(2 * b - 1) if b else 0
+    if details:
+        return cell_bits + id_bits, cell_bits, id_bits, widths
+    return cell_bits + id_bits
+
+
+def refused_for_width(clouds, r_s, r_n):
+    """None when the call's keys fit in 63 bits, else (cloud, "salient_radius" or "non_max_radius"): the first cloud
+    whose wider grid is the call's widest, and r_s when its r_s grid is that wide -- what the refusal names."""
+    bits, cell_bits, _, widths = key_bits(clouds, r_s, r_n, details=True)
+    if bits <= 63:
+        return None
+    for c, (ws, wn) in enumerate(widths):
+        if max(ws, wn) == cell_bits:
+            return c, "salient_radius" if ws == cell_bits else "non_max_radius"
+
+
 def population_covariance(P, i, js):
     """The six upper entries (00 01 02 11 12 22) of (S2 - S1 S1^T / m) / m, the sums added one neighbour at a time in
     the order of js from 0."""
@@ -98,3 +139,24 @@ def dyadic_cloud(n=150, seed=11):
     """Coordinates k / 16, k in [0, 64): every offset, product and sum of a neighbourhood is exact in FP64, so a
     covariance does not depend on the order of its sums."""
     return np.random.default_rng(seed).integers(0, 64, size=(n, 3)).astype(np.float64) / 16.0
+
+
+def corner_clusters(sx, sy, sz):
+    """Eight tight clusters of 40 points (half-unit cubes) at the corners of a box: keypoints exist inside the
+    clusters, while the cell coordinates span side / cell edge per axis."""
+    return np.concatenate([RN.cube(40, 60 + k) * 0.5 + np.array([sx * (k & 1), sy * (k >> 1 & 1), sz * (k >> 2 & 1)])
+                           for k in range(8)])
+
+
+def wide_batch_params(b):
+    """Per cloud of normals_reference.wide_batch() the ISS parameters that differ from the defaults: odd clouds keep
+    the automatic radii, min_neighbors cycles, every third cloud passes both ratio tests."""
+    params = []
+    for i in range(b):
+        p = dict(min_neighbors=(0, 3, 5)[i % 3])
+        if i % 2 == 0:
+            p.update(salient_radius=0.4, non_max_radius=0.3)
+        if i % 3 == 0:
+            p.update(gamma_21=2.0, gamma_32=2.0)
+        params.append(p)
+    return params

@@ -125,3 +125,20 @@ def tied_lattice():
     """5 x 5 x 5 lattice with spacing 1/4: every coordinate and every d2 exact, so neighbours tie exactly."""
     g = 0.25 * np.arange(5.0)
     return np.stack([a.ravel() for a in np.meshgrid(g, g, g, indexing="ij")], 1)
+
+
+WIDE_BATCH = 320
+WIDE_CYCLE = (0, 1, 2, 5, 33, 64, 65, 40)
+WIDE_ROTATE = 4  # cloud i has WIDE_CYCLE[(i + 4) % 8] points: 255, 256, 257 -> 5, 33, 64; 260 -> 0; 319 -> 5
+
+
+def wide_batch():
+    """320 small clouds for the calls that need more than 256 clouds and more than 256 point blocks
+    (tests/test_gpu_batch_width.py), with what those tests rest on asserted from the sizes alone."""
+    b = WIDE_BATCH
+    n = [WIDE_CYCLE[(i + WIDE_ROTATE) % len(WIDE_CYCLE)] for i in range(b)]
+    assert b > 256
+    assert sum((k + 255) // 256 for k in n) >= 257  # point blocks: thread 256 of the per-block kernels has work
+    assert all(n[i] > 0 for i in (255, 256, 257)) and len({n[255], n[256], n[257]}) == 3
+    assert any(n[i] == 0 for i in range(257, b)) and n[b - 1] > 0 and n[0] > 0
+    return [cube(n[i], 1000 + i) for i in range(b)]

@@ -114,6 +114,78 @@ def test_down_sampled_config5_cloud():
     assert ref["keep"].sum() > 0
 
 
+WIDE = dict(salient_radius=0.4, non_max_radius=0.3, gamma_21=2.0, gamma_32=2.0, min_neighbors=3)
+ORDINARY = dict(salient_radius=0.4, non_max_radius=0.3)
+
+
+def width(clouds, params):
+    return RK.key_bits(clouds, [p["salient_radius"] for p in params], [p["non_max_radius"] for p in params])
+
+
+def in_a_batch(X):
+    return [RN.cube(65, 65), X, np.zeros((0, 3)), RN.cube(129, 129)], [ORDINARY, WIDE, ORDINARY, ORDINARY]
+
+
+def test_keys_wider_than_a_word_half_and_the_63_bit_boundary():
+    """One cloud's key is 3 k + 1 bits when its box is a cube (k cell bits per axis and one bit of grid id), which 63
+    is not: the single cloud of 63 bits has its z side halved (21 + 21 + 20 cell bits).  In the batch of four the id
+    takes 3 bits, and a cube of 20 cell bits per axis gives 63."""
+    a, b, b4 = RK.corner_clusters(512.0, 512.0, 512.0), RK.corner_clusters(393216.0, 393216.0, 196608.0), \
+        RK.corner_clusters(196608.0, 196608.0, 196608.0)
+    assert width([a], [WIDE]) == 34 and width(*in_a_batch(a)) == 36      # (a): above 32, the shifts leave the low half
+    assert width([b], [WIDE]) == 63 and width(*in_a_batch(b4)) == 63     # (b): the widest key the call serves
+    for X in (a, b, b4):
+        ref = check(run([X], [WIDE])[0], X, WIDE, "clusters alone")
+        assert ref["keep"].sum() > 0 and (ref["count"][:, 0] > 0).any()
+    for X in (a, b4):
+        clouds, params = in_a_batch(X)
+        got = run(clouds, params)
+        for c, (Y, p, g) in enumerate(zip(clouds, params, got)):
+            check(g, Y, p, "clusters in a batch, cloud %d" % c)
+        alone = run([X], [WIDE])[0]
+        assert alone[0].tobytes() == got[1][0].tobytes() and alone[1]["saliency"].tobytes() == got[1][1]["saliency"].tobytes()
+        assert alone[1]["count"].tobytes() == got[1][1]["count"].tobytes()
+
+
+def test_a_64_bit_key_is_refused_naming_the_finer_grid():
+    """One bit above the boundary, alone and at index 1 of a batch; the radius named is the one the predictor finds."""
+    X = RK.corner_clusters(393216.0, 393216.0, 393216.0)  # 3 * 2^17: 21 cell bits per axis at r = 0.3, 20 at 0.4 and 0.45
+    mirrored = dict(WIDE, salient_radius=0.3, non_max_radius=0.45)
+    ok = RN.cube(65, 5)
+    for p, named in ((WIDE, "non_max_radius"), (mirrored, "salient_radius")):
+        assert width([X], [p]) == 64
+        assert RK.refused_for_width([X], p["salient_radius"], p["non_max_radius"]) == (0, named)
+        with pytest.raises(tp.TeaserHipError) as e:
+            run([X], [p])
+        assert named + " is too small" in str(e.value) and "problem 0" in str(e.value), str(e.value)
+        assert width([ok, X], [ORDINARY, p]) == 65
+        assert RK.refused_for_width([ok, X], [0.4, p["salient_radius"]], [0.3, p["non_max_radius"]]) == (1, named)
+        with pytest.raises(tp.TeaserHipError) as e:
+            run([ok, X], [ORDINARY, p])
+        assert named + " is too small" in str(e.value) and "problem 1" in str(e.value), str(e.value)
+        check(run([ok], [ORDINARY])[0], ok, ORDINARY, "after the refusal of " + named)
+
+
+def test_keypoint_counts_equal_the_masks():
+    """n_keypoints_out comes from a ballot and an atomicAdd per wave; the mask is written per point.  Straight through
+    the C ABI for the mixed batch, next to the Python wrapper's own check of the same equality."""
+    from importlib import import_module
+    kp = import_module("teaser-plusplus_amd.keypoints")
+    icp = import_module("teaser-plusplus_amd.icp")
+    clouds, params = mixed_batch()
+    clouds = [np.ascontiguousarray(X, dtype=np.float64) for X in clouds]
+    b = len(clouds)
+    rec = (kp.ISSParamsC * b)(*[kp.ISSParamsC(*[dict(DEFAULTS, **p)[k] for k in DEFAULTS], 0) for p in params])
+    dp, ip, bp = C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(C.c_uint8)
+    n = np.array([len(X) for X in clouds], dtype=np.int32)
+    keep = [np.full(len(X), 7, dtype=np.uint8) for X in clouds]
+    kept = np.full(b, -1, dtype=np.int32)
+    icp._handle(-1).call(tp.lib().teaser_hip_icp_iss_keypoints_batch, b, (dp * b)(*[X.ctypes.data_as(dp) for X in clouds]),
+                         n.ctypes.data_as(ip), rec, (bp * b)(*[k.ctypes.data_as(bp) for k in keep]),
+                         kept.ctypes.data_as(ip), None, None, None)
+    assert kept.tolist() == [int(k.sum()) for k in keep] and kept.sum() > 50 and all(k.max(initial=0) <= 1 for k in keep)
+
+
 def test_refusals_name_the_argument_and_the_cloud_and_leave_the_handle_usable():
     X = RN.cube(65, 5)
     bad = X.copy()

@@ -117,6 +117,61 @@ def test_wide_grid_takes_the_second_sort_pass():
         assert_bits(r, R.voxel_down_sample(q, v))
 
 
+def test_key_width_edges():
+    """The key at the word boundary: 64 bits in one pass, 65 with one bit for the second pass, a voxel index and the
+    problem index straddling bit 64, the problem index alone in the high word and at the top of the low word."""
+    tiny, empty = np.array([[0.0, 0.0, 0.0], [1.0, 2.0, 3.0], [1.2, 2.1, 3.1]]), np.zeros((0, 3))
+
+    def run(clouds, bits, x_shift, prob_shift):
+        got_bits, shifts, got_prob_shift = R.key_bits(clouds, 1.0)
+        assert (got_bits, shifts[0][0], got_prob_shift) == (bits, x_shift, prob_shift)
+        refs = [R.voxel_down_sample(c, 1.0) for c in clouds]
+        assert refs[0][1].max() >= 2 and (refs[0][1] == 1).any()
+        res = tp.voxel_down_sample_batch(clouds, 1.0, return_counts=True, return_trace=True)
+        for r, ref in zip(res, refs):
+            assert_bits(r, ref)
+
+    w64 = R.corner_cloud(22, 21, 21, 31)
+    run([w64], 64, 42, 64)                              # one pass, end_bit 64, no high word
+    run([w64, w64[::-1]], 65, 42, 64)                   # the problem bit alone in the high word: a 1-bit second pass
+    w65 = R.corner_cloud(22, 22, 21, 32)
+    run([w65], 65, 43, 65)                              # i_x (22 bits at 43) straddles bit 64
+    w62 = R.corner_cloud(21, 21, 20, 33)
+    run([w62, tiny, empty, w62[::-1]], 64, 41, 62)      # the problem field is bits 62 and 63, nothing above
+    w63 = R.corner_cloud(21, 21, 21, 34)
+    run([w63, tiny, empty, w63[::-1]], 65, 42, 63)      # the problem field straddles bit 64
+
+
+RUN_LENGTHS = (1, 2, 63, 64, 65, 66, 127, 128, 129, 191, 192, 193, 256, 257)
+
+
+def test_run_lengths_at_the_lane_and_chunk_edges():
+    """Runs of 64 points stay with the lane kernel, 65 go to the wave kernel; its 64-point chunks end at 128, 192, 256."""
+    lengths = RUN_LENGTHS * 3
+    p = R.line_of_runs(lengths, 41)
+    ref = R.voxel_down_sample(p, 1.0)
+    assert ref[1].tolist() == list(lengths)
+    assert_bits(gpu(p, 1.0), ref)
+    # between two clouds: long runs on both sides of both problem boundaries
+    first, third = R.line_of_runs((3, 70, 130), 42), R.line_of_runs((200, 5, 64), 43)
+    refs = [R.voxel_down_sample(c, 1.0) for c in (first, p, third)]
+    assert refs[0][1][-1] > 64 and refs[1][1][-1] > 64 and refs[2][1][0] > 64
+    for r, ref in zip(tp.voxel_down_sample_batch([first, p, third], 1.0, return_counts=True, return_trace=True), refs):
+        assert_bits(r, ref)
+
+
+def test_more_long_runs_than_waves():
+    """16 400 voxels of 65 points: more runs for the wave kernel than the 16 384 waves of its grid, so the last ones are
+    reached by the grid stride; a tail of 100 one-point voxels for the lane kernel in the same call.  The restatement
+    of this 1.07 M-point cloud takes 0.7 s on the CPU."""
+    long_runs, tail = 16400, 100
+    assert long_runs > 4096 * 4  # kVoxLongBlocks blocks of 4 waves
+    p = R.many_runs(long_runs, 65, tail, 51)
+    ref = R.voxel_down_sample(p, 1.0)
+    assert (ref[1] == 65).sum() == long_runs and (ref[1] == 1).sum() == tail and len(ref[1]) == long_runs + tail
+    assert_bits(gpu(p, 1.0), ref)
+
+
 def test_int_max_guard():
     ok = np.array([[0.0, 0.0, 0.0], [2147483646.0, 0.0, 0.0]])
     check(ok, 1.0)

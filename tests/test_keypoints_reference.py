@@ -117,3 +117,48 @@ def test_tied_maxima_survive_together():
     tied = [(a, b) for a in range(len(kept)) for b in range(a + 1, len(kept)) if D[a, b] < rn * rn and s[a] == s[b]]
     assert len(kept) > 1 and len(tied) > 10  # keypoints inside each other's suppression ball with equal saliency bits
     assert (s > 0).all()
+
+
+def test_key_bits_on_hand_computed_cases():
+    one = np.array([[3.0, -2.0, 7.5]])
+    two_cells = np.array([[0.0, 0.0, 0.0], [0.5, 0.0, 0.0]])  # r = 0.3: c_x in {0, 1}, one bit; r = 0.2: {0, 2}, two
+    assert RK.key_bits([one], 0.4, 0.3, details=True) == (1, 0, 1, [(0, 0)])  # ids 0 and 1: one bit
+    assert RK.key_bits([two_cells], 0.6, 0.3, details=True) == (2, 1, 1, [(0, 1)])
+    assert RK.key_bits([two_cells], 0.3, 0.2, details=True) == (3, 2, 1, [(1, 2)])
+    assert RK.key_bits([two_cells, one], 0.3, 0.2) == 2 + 2          # ids 0 .. 3
+    assert RK.key_bits([two_cells] + [one] * 256, 0.3, 0.2) == 2 + 10  # batch 257: ids 0 .. 513
+    assert RK.key_bits([two_cells] + [one] * 255, 0.3, 0.2) == 2 + 9   # batch 256: ids 0 .. 511
+    # a cloud without neighbours to find has no grid: empty, or a resolution of 0
+    assert RK.key_bits([np.zeros((0, 3)), RN.identical()], [0.3, 0.0], [0.2, 0.0], details=True)[1] == 0
+    box = np.array([[0.0, 0.0, 0.0], [1.0, 0.5, 0.25]])
+    assert [int(v) for v in RK.cells(box, 0.1).max(axis=0)] == [9, 4, 2]
+    assert RK.key_bits([box], 0.1, 0.1, details=True) == (4 + 3 + 2 + 1, 9, 1, [(9, 9)])
+    assert RK.refused_for_width([box], 0.1, 0.1) is None
+
+
+def test_key_bits_of_the_clouds_at_the_63_bit_boundary():
+    """The clouds and radii of tests/test_gpu_keypoints.py's key-width tests and of tests/test_gpu_batch_width.py."""
+    others = [RN.cube(65, 65), None, np.zeros((0, 3)), RN.cube(129, 129)]
+
+    def batched(X):
+        return RK.key_bits([X if c is None else c for c in others], 0.4, 0.3, details=True)
+
+    a = RK.corner_clusters(512.0, 512.0, 512.0)
+    assert RK.key_bits([a], 0.4, 0.3, details=True) == (34, 33, 1, [(33, 33)]) and batched(a)[:3] == (36, 33, 3)
+    b = RK.corner_clusters(393216.0, 393216.0, 196608.0)
+    assert RK.key_bits([b], 0.4, 0.3, details=True) == (63, 62, 1, [(59, 62)])
+    b4 = RK.corner_clusters(196608.0, 196608.0, 196608.0)
+    assert batched(b4)[:3] == (63, 60, 3) and RK.refused_for_width([b4], 0.4, 0.3) is None
+    c = RK.corner_clusters(393216.0, 393216.0, 393216.0)
+    assert RK.key_bits([c], 0.4, 0.3, details=True) == (64, 63, 1, [(60, 63)])
+    assert RK.refused_for_width([c], 0.4, 0.3) == (0, "non_max_radius")
+    assert RK.key_bits([c], 0.3, 0.45, details=True) == (64, 63, 1, [(63, 60)])
+    assert RK.refused_for_width([c], 0.3, 0.45) == (0, "salient_radius")
+    assert RK.refused_for_width([RN.cube(65, 5), c], [0.4, 0.4], [0.3, 0.3]) == (1, "non_max_radius")
+    assert RK.refused_for_width([RN.cube(65, 5), c], [0.4, 0.3], [0.3, 0.45]) == (1, "salient_radius")
+    wide = RN.wide_batch()
+    p = RK.wide_batch_params(len(wide))
+    bits, cell_bits, id_bits, widths = RK.key_bits(wide, [q.get("salient_radius", 0.0) for q in p],
+                                                   [q.get("non_max_radius", 0.0) for q in p], details=True)
+    assert len(wide) == 320 and id_bits == 10 and bits == cell_bits + 10 <= 63
+    assert widths[260] == (0, 0) and max(widths[256]) > 0

@@ -131,6 +131,44 @@ def test_crop_fixture_is_consistent():
     assert all(tuple(first[k]) < tuple(first[k + 1]) for k in range(len(first) - 1))  # ascending (i_x, i_y, i_z)
 
 
+def test_key_bits_on_hand_computed_cases():
+    one = np.array([[3.0, -2.0, 7.5]])
+    two_cells = np.array([[0.0, 0.0, 0.0], [1.0, 0.0, 0.0]])  # v = 1: i_x in {0, 1}, one bit
+    assert R.key_bits([one], 1.0) == (1, [(0, 0, 0)], 0)      # no cell bits, no problem bits: the sort still gets 1
+    assert R.key_bits([two_cells], 1.0) == (1, [(0, 0, 0)], 1)
+    assert R.key_bits([two_cells, one], 1.0) == (2, [(0, 0, 0), (0, 0, 0)], 1)
+    assert R.key_bits([two_cells], 0.5) == (2, [(0, 0, 0)], 2)  # i_x in {0, 2}
+    box = np.array([[0.0, 0.0, 0.0], [5.0, 2.0, 1.0]])          # largest indices 5, 2, 1: 3 + 2 + 1 bits, i_z lowest
+    assert R.key_bits([box], 1.0) == (6, [(3, 1, 0)], 6)
+    assert R.key_bits([np.zeros((0, 3)), box], [0.3, 1.0]) == (7, [None, (3, 1, 0)], 6)
+    assert R.key_bits([box] + [one] * 256, 1.0)[::2] == (6 + 9, 6)  # batch 257: problem indices up to 256, nine bits
+    assert R.key_bits([box] + [one] * 255, 1.0)[0] == 6 + 8
+
+
+def test_key_bits_of_the_clouds_at_the_word_boundary():
+    """The clouds of tests/test_gpu_voxel.py::test_key_width_edges and the widths it names."""
+    tiny, empty = np.array([[0.0, 0.0, 0.0], [1.0, 2.0, 3.0], [1.2, 2.1, 3.1]]), np.zeros((0, 3))
+    w64, w65 = R.corner_cloud(22, 21, 21, 31), R.corner_cloud(22, 22, 21, 32)
+    w62, w63 = R.corner_cloud(21, 21, 20, 33), R.corner_cloud(21, 21, 21, 34)
+    assert R.voxel_indices(w64, 1.0).max(0).tolist() == [2 ** 22 - 1, 2 ** 21 - 1, 2 ** 21 - 1]
+    assert R.key_bits([w64], 1.0) == (64, [(42, 21, 0)], 64)
+    assert R.key_bits([w64, w64[::-1]], 1.0) == (65, [(42, 21, 0)] * 2, 64)
+    assert R.key_bits([w65], 1.0) == (65, [(43, 21, 0)], 65)  # i_x: bits 43 .. 64
+    assert R.key_bits([w62, tiny, empty, w62[::-1]], 1.0) == (64, [(41, 20, 0), (4, 2, 0), None, (41, 20, 0)], 62)
+    assert R.key_bits([w63, tiny, empty, w63[::-1]], 1.0) == (65, [(42, 21, 0), (4, 2, 0), None, (42, 21, 0)], 63)
+    for w in (w64, w65, w62, w63):  # runs of two points, exact faces, and the restatement accepts the extent
+        idx = R.voxel_indices(w, 1.0)
+        assert ((w - np.floor(w)) == 0.5).any() and len(np.unique(idx, axis=0)) < len(w)
+        assert R.voxel_down_sample(w, 1.0)[1].max() >= 2
+
+
+def test_run_length_clouds_hold_the_lengths_they_name():
+    lengths = (1, 2, 63, 64, 65, 66, 127, 128, 129, 191, 192, 193, 256, 257) * 3
+    assert R.voxel_down_sample(R.line_of_runs(lengths, 41), 1.0)[1].tolist() == list(lengths)
+    counts = R.voxel_down_sample(R.many_runs(300, 65, 20, 5), 1.0)[1]
+    assert (counts == 65).sum() == 300 and (counts == 1).sum() == 20 and len(counts) == 320
+
+
 def test_public_names():
     assert "voxel_down_sample" in tp.__all__ and "voxel_down_sample_batch" in tp.__all__
     for sym in ("teaser_hip_voxel_create", "teaser_hip_voxel_destroy", "teaser_hip_voxel_last_error",

@@ -65,6 +65,64 @@ def voxel_down_sample(points, voxel_size):
     return means, count.astype(np.int32), trace
 
 
+def bits_for(v):
+    """Number of bits that hold every value in [0, v]."""
+    return int(v).bit_length()
+
+
+def key_bits(clouds, sizes):
+    """The sort key the library lays out for this call (voxel.hip, "key layout"): (bits, shifts, prob_shift).  Per
+    non-empty cloud the fields i_z, i_y, i_x from bit 0 up, each bits_for(the axis' largest voxel index) wide: shifts[b]
+    = (shift of i_x, of i_y, of i_z), None for an empty cloud.  The problem index sits above the widest cloud, at
+    prob_shift, and is bits_for(batch - 1) wide; bits is the whole width, at least 1.  Up to 64 bits the sort is one
+    pass over the low word; above, a second pass sorts the bits - 64 bits of the high word."""
+    sizes = np.broadcast_to(np.asarray(sizes, dtype=np.float64), (len(clouds),))
+    shifts, widest = [], 0
+    for c, v in zip(clouds, sizes):
+        p = np.asarray(c, dtype=np.float64).reshape(-1, 3)
+        if len(p) == 0:
+            shifts.append(None)
+            continue
+        bx, by, bz = (bits_for(m) for m in voxel_indices(p, v).max(0))
+        shifts.append((by + bz, bz, 0))
+        widest = max(widest, bx + by + bz)
+    return max(1, widest + bits_for(max(len(clouds) - 1, 0))), shifts, widest
+
+
+def corner_cloud(a, b, c, seed, n=300):
+    """v = 1: the origin and the corner (2^a - 1, 2^b - 1, 2^c - 1) fix the largest voxel indices, hence a, b and c key
+    bits; between them n random points, a third of them on exact faces (x = k + 1/2), and a copy of the first 100
+    moved by 1/4, most of which share their voxel with the original."""
+    rng = np.random.default_rng(seed)
+    corner = np.array([2.0 ** a - 1, 2.0 ** b - 1, 2.0 ** c - 1])
+    p = rng.uniform(0, corner - 2, size=(n, 3))
+    p[: n // 3] = np.floor(p[: n // 3]) + 0.5
+    p = np.concatenate([[[0.0, 0.0, 0.0]], p, p[:100] + 0.25, [corner]])
+    return p[rng.permutation(len(p))]
+
+
+def line_of_runs(lengths, seed):
+    """Voxel j of a line along x (v = 1) holds exactly lengths[j] points, uniform inside it, the cloud shuffled."""
+    rng = np.random.default_rng(seed)
+    j = np.repeat(np.arange(len(lengths)), lengths)
+    p = rng.uniform(0, 0.5, size=(len(j), 3))  # min_bound 0 (set below) -> lo = -1/2: voxel j is [j - 1/2, j + 1/2)
+    p[0] = 0.0
+    p[:, 0] += j
+    return p[rng.permutation(len(p))]
+
+
+def many_runs(runs, length, tail, seed):
+    """`runs` voxels of exactly `length` points each and `tail` voxels of one point, on a 128-wide sheet of voxels
+    (v = 1), the points uniform inside their voxel, the cloud shuffled."""
+    rng = np.random.default_rng(seed)
+    cell = np.arange(runs + tail)
+    cell = np.stack([cell // 128, cell % 128, np.zeros_like(cell)], 1).astype(np.float64)
+    p = np.concatenate([np.repeat(cell[:runs], length, axis=0), cell[runs:]])
+    p += rng.uniform(0, 0.5, size=p.shape)
+    p[0] = 0.0  # min_bound 0 -> lo = -1/2
+    return p[rng.permutation(len(p))]
+
+
 def scan_like(seed=5, n=313395, offset=0.0):
     """A room-sized scan: noisy planes (floor, walls, a table) and a few blobs, float32 like a PLY."""
     rng = np.random.default_rng(seed)
