@@ -1,6 +1,7 @@
 // icp.hip -- host side of the batched ICP (include/teaser_hip.h, "ICP refinement": point-to-point, point-to-plane
 // with robust kernels, Generalized ICP) and of the covariance estimation on the same handle: argument validation,
-// the per-call index and the iteration loop.
+// the per-call index and the iteration loop.  The handle's other calls: icp_outlier.hip, icp_normals.hip,
+// icp_keypoints.hip; what they share: icp_host.h.
 // Kernels: kernels_icp.hip.
 //
 // The host enqueues iterations in groups of kIcpGroup (two launches each); after a group ONE small copy of the
@@ -10,7 +11,6 @@
 #include <string.h>
 
 #include <algorithm>
-#include <limits>
 #include <string>
 #include <vector>
 
@@ -229,29 +229,27 @@ int32_t icp_run_batch(teaser_hip_icp* h, int32_t batch, const double* const* src
     for (int k = 0; k < 12; ++k) st.U[k] = T0[k];  // the first correspondence pass applies init to P
   }
   const std::vector<IcpDesc>& desc = ix.desc;
-  const int64_t s_off = ix.s_off, t_off = ix.t_off, b_off = ix.b_off;
-  const int n_blk = (int)ix.blk_prob.size(), n_tblk = (int)ix.tblk_prob.size();
+  const int64_t s_off = ix.s_off, t_off = ix.t_off;
+  const int n_blk = (int)ix.blk_prob.size();
 
   // ---- device buffers ----
-  const size_t bytes[B_COUNT] = {
-      sizeof(IcpDesc) * batch, sizeof(IcpState) * batch, sizeof(int32_t) * std::max(n_blk, 1),
-      sizeof(int32_t) * std::max(n_tblk, 1), sizeof(double) * 3 * std::max<int64_t>(s_off, 1),
-      sizeof(double) * 3 * std::max<int64_t>(t_off, 1), sizeof(int32_t) * std::max<int64_t>(t_off, 1),
-      sizeof(int32_t) * std::max<int64_t>(b_off, 1), sizeof(int32_t) * std::max<int64_t>(b_off, 1),
-      sizeof(int32_t) * std::max<int64_t>(b_off, 1), sizeof(double) * 3 * std::max<int64_t>(t_off, 1),
-      sizeof(int32_t) * std::max<int64_t>(t_off, 1),
-      sizeof(int32_t) * std::max<int64_t>(hook ? std::max(s_off, 2 * t_off) : s_off, 1),  // (the hook's worklist)
-      sizeof(double) * (plane || gicp ? kIcpPlaneSums : kIcpSums) * std::max(n_blk, 1), sizeof(int32_t),
-      plane ? sizeof(double) * 3 * std::max<int64_t>(t_off, 1) : 0,
-      gicp ? sizeof(double) * 6 * std::max<int64_t>(s_off, 1) : 0,
-      gicp ? sizeof(double) * 6 * std::max<int64_t>(t_off, 1) : 0};
-  for (int k = 0; k < B_COUNT; ++k)
-    if (!h->buf[k].ensure(bytes[k])) return fail(h, TEASER_HIP_ERR_OOM, "hipMalloc failed (ICP buffers)");
+  const size_t pts_s = (size_t)std::max<int64_t>(s_off, 1), pts_t = (size_t)std::max<int64_t>(t_off, 1);
+  size_t bytes[B_COUNT] = {};
+  index_bytes(ix, 1, hook != nullptr, bytes);  // (the hook's worklist)
+  bytes[B_STATE] = sizeof(IcpState) * batch;
+  bytes[B_X] = sizeof(double) * 3 * pts_s;
+  bytes[B_MATCH] = std::max(bytes[B_MATCH], sizeof(int32_t) * pts_s);
+  bytes[B_PARTIALS] = sizeof(double) * (plane || gicp ? kIcpPlaneSums : kIcpSums) * std::max(n_blk, 1);
+  bytes[B_LIVE] = sizeof(int32_t);
+  bytes[B_NORMALS] = plane ? sizeof(double) * 3 * pts_t : 0;
+  bytes[B_COV_S] = gicp ? sizeof(double) * 6 * pts_s : 0;
+  bytes[B_COV_T] = gicp ? sizeof(double) * 6 * pts_t : 0;
+  if ((rc = ensure_buffers(h, bytes, "hipMalloc failed (ICP buffers)")) != TEASER_HIP_OK) return rc;
   hipStream_t s = h->stream;
   DevBuf* B = h->buf;
 
   h->stage.resize((size_t)((gicp ? 9 : 3) * (s_off + t_off)));  // points, then the packed covariances
-  if ((rc = upload_inputs(h, ix, src, dst, state.data(), bytes[B_STATE])) != TEASER_HIP_OK) return rc;
+  if ((rc = upload_inputs(h, ix, src, dst, n_dst, state.data(), bytes[B_STATE])) != TEASER_HIP_OK) return rc;
   for (int b = 0; b < batch; ++b) {  // one copy per point-to-plane problem, straight from the caller's normals
     const IcpDesc& d = desc[(size_t)b];
     if (d.method == kIcpMethodPlane && d.n_t > 0 && dst_normals && dst_normals[b])  // else: the hook estimates them
@@ -404,22 +402,15 @@ int32_t teaser_hip_icp_covariances_batch(teaser_hip_icp* h, int32_t batch, const
   const int n_blk = (int)ix.blk_prob.size();
   // B_STATE holds the IcpCovDesc records and B_X the 9 doubles per point of the output during this call
   size_t bytes[B_COUNT] = {};
-  bytes[B_DESC] = sizeof(IcpDesc) * batch;
+  index_bytes(ix, 0, false, bytes);
   bytes[B_STATE] = sizeof(IcpCovDesc) * batch;
-  bytes[B_BLK] = sizeof(int32_t) * n_blk;
-  bytes[B_TBLK] = sizeof(int32_t) * ix.tblk_prob.size();
   bytes[B_X] = sizeof(double) * 9 * t_off;
-  bytes[B_Q] = sizeof(double) * 3 * t_off;
-  bytes[B_TBUCKET] = sizeof(int32_t) * t_off;
-  bytes[B_BCOUNT] = bytes[B_BSTART] = bytes[B_CURSOR] = sizeof(int32_t) * ix.b_off;
-  bytes[B_QS] = sizeof(double) * 3 * t_off;
-  bytes[B_QJ] = sizeof(int32_t) * t_off;
-  for (int k = 0; k < B_COUNT; ++k)
-    if (!h->buf[k].ensure(bytes[k])) return fail(h, TEASER_HIP_ERR_OOM, "hipMalloc failed (covariance buffers)");
+  int32_t rc = ensure_buffers(h, bytes, "hipMalloc failed (covariance buffers)");
+  if (rc != TEASER_HIP_OK) return rc;
   hipStream_t s = h->stream;
   DevBuf* B = h->buf;
   h->stage.resize((size_t)(9 * t_off));
-  int32_t rc = upload_inputs(h, ix, nullptr, points, cov.data(), bytes[B_STATE]);
+  rc = upload_inputs(h, ix, nullptr, points, n, cov.data(), bytes[B_STATE]);
   if (rc == TEASER_HIP_OK) rc = launch_index(h, ix);
   if (rc != TEASER_HIP_OK) return rc;
   launch_icp_covariances(s, B[B_DESC].as<IcpDesc>(), B[B_STATE].as<IcpCovDesc>(), B[B_BLK].as<int32_t>(), n_blk,
@@ -431,292 +422,6 @@ int32_t teaser_hip_icp_covariances_batch(teaser_hip_icp* h, int32_t batch, const
   FCHK(h, hipStreamSynchronize(s), "covariance estimation");
   for (int b = 0; b < batch; ++b)
     if (n[b]) memcpy(out[b], &h->stage[(size_t)(9 * desc[(size_t)b].t_off)], 72 * (size_t)n[b]);
-  return TEASER_HIP_OK;
-}
-
-}  // extern "C"
-
-// ---- self k-NN, statistical and radius outlier removal ---------------------------------------------------------------
-namespace {
-
-// Index and self k-NN launches of one call.  k[b] neighbours per cloud; ratio NULL: self k-NN (idx / d2 outputs at
-// out_idx / out_d2 of B_X), else statistical removal (avg at out_avg).  Leaves the descriptors in *ix.
-struct KnnLayout {
-  size_t d2 = 0, idx = 0, avg = 0, stats = 0, ints = 0, keep = 0, bytes = 0;  // byte offsets inside B_X
-  int64_t slots = 0;                                                          // sum of n k (self k-NN)
-};
-
-int32_t run_self_knn(teaser_hip_icp* h, int32_t batch, const double* const* points, const int32_t* n, const int32_t* k,
-                     const double* ratio, IcpIndex& ix, KnnLayout& L) {
-  std::vector<IcpKnnDesc> knn((size_t)batch);
-  int top = 0;
-  for (int b = 0; b < batch; ++b) {
-    IcpKnnDesc& kd = knn[(size_t)b];
-    memset(&kd, 0, sizeof(kd));
-    kd.k = k[b];
-    kd.ring_cap = h->knn_ring_cap;
-    kd.out_off = L.slots;
-    kd.edge = 1.0;
-    kd.ratio = ratio ? ratio[b] : 0.0;
-    if (n[b] > 0) {
-      const int want = std::min(k[b], n[b]);
-      bool rings_ok = true;
-      kd.edge = knn_edge(points[b], n[b], want, &rings_ok);
-      if (!rings_ok) kd.ring_cap = 0;
-      top = std::max(top, want);
-    }
-    add_problem(ix, b, 0, n[b], points, kd.edge, (n[b] + kIcpCovBlock - 1) / kIcpCovBlock);
-    L.slots += (int64_t)n[b] * k[b];
-  }
-  const int64_t t_off = ix.t_off;
-  const int n_blk = (int)ix.blk_prob.size(), n_tblk = (int)ix.tblk_prob.size();
-  // B_X: doubles first, then int32 (the last one is the worklist counter), then the mask bytes
-  if (ratio) {
-    L.avg = 0;
-    L.stats = sizeof(double) * t_off;
-    L.ints = L.stats + sizeof(double) * 3 * batch;
-    L.keep = L.ints + sizeof(int32_t) * ((size_t)batch + 1);
-    L.bytes = L.keep + (size_t)t_off;
-  } else {
-    L.d2 = 0;
-    L.idx = sizeof(double) * L.slots;
-    L.ints = L.idx + sizeof(int32_t) * L.slots;
-    L.bytes = L.ints + sizeof(int32_t);
-  }
-  size_t bytes[B_COUNT] = {};
-  bytes[B_DESC] = sizeof(IcpDesc) * batch;
-  bytes[B_STATE] = sizeof(IcpKnnDesc) * batch;
-  bytes[B_BLK] = sizeof(int32_t) * n_blk;
-  bytes[B_TBLK] = sizeof(int32_t) * n_tblk;
-  bytes[B_X] = L.bytes;
-  bytes[B_Q] = sizeof(double) * 3 * t_off;
-  bytes[B_TBUCKET] = sizeof(int32_t) * t_off;
-  bytes[B_BCOUNT] = bytes[B_BSTART] = bytes[B_CURSOR] = sizeof(int32_t) * ix.b_off;
-  bytes[B_QS] = sizeof(double) * 3 * t_off;
-  bytes[B_QJ] = sizeof(int32_t) * t_off;
-  bytes[B_MATCH] = sizeof(int32_t) * 2 * t_off;  // the worklist
-  bytes[B_PARTIALS] = ratio ? sizeof(double) * n_tblk : 0;
-  for (int b = 0; b < B_COUNT; ++b)
-    if (!h->buf[b].ensure(bytes[b])) return fail(h, TEASER_HIP_ERR_OOM, "hipMalloc failed (k-NN buffers)");
-  hipStream_t s = h->stream;
-  DevBuf* B = h->buf;
-  char* out = B[B_X].as<char>();
-  h->stage.resize((size_t)(3 * t_off));
-  int32_t rc = upload_inputs(h, ix, nullptr, points, knn.data(), bytes[B_STATE]);
-  if (rc != TEASER_HIP_OK) return rc;
-  // the counters: the worklist's and, for statistical removal, the kept counts in front of it
-  FCHK(h, hipMemsetAsync(out + L.ints, 0, sizeof(int32_t) * (ratio ? (size_t)batch + 1 : 1), s), "hipMemsetAsync");
-  if ((rc = launch_index(h, ix)) != TEASER_HIP_OK) return rc;
-  int32_t* counter = (int32_t*)(out + L.ints) + (ratio ? batch : 0);
-  launch_icp_self_knn(s, B[B_DESC].as<IcpDesc>(), B[B_STATE].as<IcpKnnDesc>(), B[B_BLK].as<int32_t>(), n_blk, top,
-                      B[B_Q].as<double>(), B[B_QS].as<double>(), B[B_QJ].as<int32_t>(), B[B_BSTART].as<int32_t>(),
-                      (int32_t*)(out + L.idx), (double*)(out + L.d2), ratio ? (double*)(out + L.avg) : nullptr,
-                      B[B_MATCH].as<int32_t>(), counter);
-  return TEASER_HIP_OK;
-}
-
-// The one copy back of a call (B_X -> h->back) and its synchronisation.
-int32_t copy_back(teaser_hip_icp* h, size_t bytes, const char* what) {
-  h->back.resize((bytes + 7) / 8);
-  FCHK(h, hipGetLastError(), "kernel launch (k-NN / outlier removal)");
-  FCHK(h, hipMemcpyAsync(h->back.data(), h->buf[B_X].p, bytes, hipMemcpyDeviceToHost, h->stream),
-       "hipMemcpyAsync (results)");
-  FCHK(h, hipStreamSynchronize(h->stream), what);
-  return TEASER_HIP_OK;
-}
-
-}  // namespace
-
-extern "C" {
-
-int32_t teaser_hip_icp_set_option(teaser_hip_icp* h, const char* name, int64_t value) {
-  if (!h || !name) return TEASER_HIP_ERR_BAD_ARG;
-  h->err.clear();
-  if (strcmp(name, "knn_ring_cap") == 0) {
-    if (value < 0 || value > kIcpKnnRingCapMax)
-      return fail(h, TEASER_HIP_ERR_BAD_ARG, "knn_ring_cap must lie in [0, " + std::to_string(kIcpKnnRingCapMax) + "]");
-    h->knn_ring_cap = (int32_t)value;
-    return TEASER_HIP_OK;
-  }
-  if (strcmp(name, "knn_fallbacks") == 0) return fail(h, TEASER_HIP_ERR_BAD_ARG, "knn_fallbacks is read-only");
-  return fail(h, TEASER_HIP_ERR_BAD_ARG, std::string("unknown ICP option ") + name);
-}
-
-int32_t teaser_hip_icp_get_option(teaser_hip_icp* h, const char* name, int64_t* value) {
-  if (!h) return TEASER_HIP_ERR_BAD_ARG;
-  h->err.clear();
-  if (!name || !value) return fail(h, TEASER_HIP_ERR_BAD_ARG, "name / value must not be NULL");
-  if (strcmp(name, "knn_ring_cap") == 0) {
-    *value = h->knn_ring_cap;
-    return TEASER_HIP_OK;
-  }
-  if (strcmp(name, "knn_fallbacks") == 0) {
-    *value = h->knn_fallbacks;
-    return TEASER_HIP_OK;
-  }
-  return fail(h, TEASER_HIP_ERR_BAD_ARG, std::string("unknown ICP option ") + name);
-}
-
-int32_t teaser_hip_icp_self_knn_batch(teaser_hip_icp* h, int32_t batch, const double* const* points, const int32_t* n,
-                                      const int32_t* k, int32_t* const* idx_out, double* const* d2_out) {
-  if (!h) return TEASER_HIP_ERR_BAD_ARG;
-  h->err.clear();
-  h->knn_fallbacks = 0;
-  if (batch < 0) return fail(h, TEASER_HIP_ERR_BAD_ARG, "batch must be >= 0");
-  if (batch == 0) return TEASER_HIP_OK;
-  int64_t total = 0, slots = 0;
-  int32_t rc = check_clouds(h, batch, points, n, &total);
-  if (rc != TEASER_HIP_OK) return rc;
-  if (!k) return fail(h, TEASER_HIP_ERR_BAD_ARG, "k must not be NULL");
-  for (int b = 0; b < batch; ++b) {
-    if (k[b] < 1 || k[b] > kIcpKnnMax)
-      return fail(h, TEASER_HIP_ERR_BAD_ARG, "k must lie in [1, " + std::to_string(kIcpKnnMax) + "]" + at(b));
-    if (n[b] > 0 && (!idx_out || !idx_out[b])) return fail(h, TEASER_HIP_ERR_BAD_ARG, "idx_out is NULL" + at(b));
-    slots += (int64_t)n[b] * k[b];
-  }
-  if (slots >= INT32_MAX) return fail(h, TEASER_HIP_ERR_BAD_ARG, "too many output slots (sum of n k) in one call");
-  if (total == 0) return TEASER_HIP_OK;
-  FCHK(h, hipSetDevice(h->device), "hipSetDevice");
-  IcpIndex ix;
-  KnnLayout L;
-  if ((rc = run_self_knn(h, batch, points, n, k, nullptr, ix, L)) != TEASER_HIP_OK) return rc;
-  if ((rc = copy_back(h, L.bytes, "self k-NN")) != TEASER_HIP_OK) return rc;
-  const char* back = (const char*)h->back.data();
-  int32_t fallbacks = 0;
-  memcpy(&fallbacks, back + L.ints, sizeof(int32_t));
-  h->knn_fallbacks = fallbacks;
-  int64_t off = 0;
-  for (int b = 0; b < batch; ++b) {
-    const size_t cnt = (size_t)n[b] * (size_t)k[b];
-    if (cnt) memcpy(idx_out[b], back + L.idx + sizeof(int32_t) * off, sizeof(int32_t) * cnt);
-    if (cnt && d2_out && d2_out[b]) memcpy(d2_out[b], back + L.d2 + sizeof(double) * off, sizeof(double) * cnt);
-    off += (int64_t)cnt;
-  }
-  return TEASER_HIP_OK;
-}
-
-int32_t teaser_hip_icp_remove_statistical_outliers_batch(teaser_hip_icp* h, int32_t batch,
-                                                         const double* const* points, const int32_t* n,
-                                                         const int32_t* nb_neighbors, const double* std_ratio,
-                                                         uint8_t* const* keep_out, int32_t* n_kept_out,
-                                                         double* const* avg_out, double* stats_out) {
-  if (!h) return TEASER_HIP_ERR_BAD_ARG;
-  h->err.clear();
-  h->knn_fallbacks = 0;
-  if (batch < 0) return fail(h, TEASER_HIP_ERR_BAD_ARG, "batch must be >= 0");
-  if (batch == 0) return TEASER_HIP_OK;
-  int64_t total = 0;
-  int32_t rc = check_clouds(h, batch, points, n, &total);
-  if (rc != TEASER_HIP_OK) return rc;
-  if (!nb_neighbors) return fail(h, TEASER_HIP_ERR_BAD_ARG, "nb_neighbors must not be NULL");
-  if (!std_ratio) return fail(h, TEASER_HIP_ERR_BAD_ARG, "std_ratio must not be NULL");
-  if (!n_kept_out) return fail(h, TEASER_HIP_ERR_BAD_ARG, "n_kept_out must not be NULL");
-  for (int b = 0; b < batch; ++b) {
-    if (nb_neighbors[b] < 1 || nb_neighbors[b] > kIcpKnnMax)
-      return fail(h, TEASER_HIP_ERR_BAD_ARG,
-                  "nb_neighbors must lie in [1, " + std::to_string(kIcpKnnMax) + "]" + at(b));
-    if (!std::isfinite(std_ratio[b]) || !(std_ratio[b] > 0))
-      return fail(h, TEASER_HIP_ERR_BAD_ARG, "std_ratio must be finite and > 0" + at(b));
-    if (n[b] > 0 && (!keep_out || !keep_out[b])) return fail(h, TEASER_HIP_ERR_BAD_ARG, "keep_out is NULL" + at(b));
-  }
-  const double kNaN = std::numeric_limits<double>::quiet_NaN();
-  for (int b = 0; b < batch; ++b) {  // an empty cloud: nothing kept, no statistics
-    n_kept_out[b] = 0;
-    if (stats_out) stats_out[3 * b] = stats_out[3 * b + 1] = stats_out[3 * b + 2] = kNaN;
-  }
-  if (total == 0) return TEASER_HIP_OK;
-  FCHK(h, hipSetDevice(h->device), "hipSetDevice");
-  IcpIndex ix;
-  KnnLayout L;
-  if ((rc = run_self_knn(h, batch, points, n, nb_neighbors, std_ratio, ix, L)) != TEASER_HIP_OK) return rc;
-  DevBuf* B = h->buf;
-  char* out = B[B_X].as<char>();
-  launch_icp_statistical(h->stream, B[B_DESC].as<IcpDesc>(), B[B_STATE].as<IcpKnnDesc>(), B[B_TBLK].as<int32_t>(),
-                         (int)ix.tblk_prob.size(), batch, (const double*)(out + L.avg), B[B_PARTIALS].as<double>(),
-                         (double*)(out + L.stats), (uint8_t*)(out + L.keep), (int32_t*)(out + L.ints));
-  if ((rc = copy_back(h, L.bytes, "statistical outlier removal")) != TEASER_HIP_OK) return rc;
-  const char* back = (const char*)h->back.data();
-  int32_t fallbacks = 0;
-  memcpy(&fallbacks, back + L.ints + sizeof(int32_t) * batch, sizeof(int32_t));
-  h->knn_fallbacks = fallbacks;
-  for (int b = 0; b < batch; ++b) {
-    if (n[b] == 0) continue;
-    const int64_t o = ix.desc[(size_t)b].t_off;
-    memcpy(keep_out[b], back + L.keep + o, (size_t)n[b]);
-    memcpy(&n_kept_out[b], back + L.ints + sizeof(int32_t) * b, sizeof(int32_t));
-    if (avg_out && avg_out[b]) memcpy(avg_out[b], back + L.avg + sizeof(double) * o, sizeof(double) * n[b]);
-    if (stats_out) memcpy(stats_out + 3 * b, back + L.stats + sizeof(double) * 3 * b, sizeof(double) * 3);
-  }
-  return TEASER_HIP_OK;
-}
-
-int32_t teaser_hip_icp_remove_radius_outliers_batch(teaser_hip_icp* h, int32_t batch, const double* const* points,
-                                                    const int32_t* n, const int32_t* nb_points, const double* radius,
-                                                    uint8_t* const* keep_out, int32_t* n_kept_out,
-                                                    int32_t* const* count_out) {
-  if (!h) return TEASER_HIP_ERR_BAD_ARG;
-  h->err.clear();
-  if (batch < 0) return fail(h, TEASER_HIP_ERR_BAD_ARG, "batch must be >= 0");
-  if (batch == 0) return TEASER_HIP_OK;
-  int64_t total = 0;
-  int32_t rc = check_clouds(h, batch, points, n, &total);
-  if (rc != TEASER_HIP_OK) return rc;
-  if (!nb_points) return fail(h, TEASER_HIP_ERR_BAD_ARG, "nb_points must not be NULL");
-  if (!radius) return fail(h, TEASER_HIP_ERR_BAD_ARG, "radius must not be NULL");
-  if (!n_kept_out) return fail(h, TEASER_HIP_ERR_BAD_ARG, "n_kept_out must not be NULL");
-  for (int b = 0; b < batch; ++b) {
-    const double r = radius[b];
-    if (!std::isfinite(r) || !(r > 0) || !std::isfinite(r * r) || !(r * r > 0))
-      return fail(h, TEASER_HIP_ERR_BAD_ARG, "radius (and its square) must be finite and > 0" + at(b));
-    if (nb_points[b] < 1) return fail(h, TEASER_HIP_ERR_BAD_ARG, "nb_points must be >= 1" + at(b));
-    if (n[b] > 0 && (!keep_out || !keep_out[b])) return fail(h, TEASER_HIP_ERR_BAD_ARG, "keep_out is NULL" + at(b));
-  }
-  for (int b = 0; b < batch; ++b) n_kept_out[b] = 0;
-  if (total == 0) return TEASER_HIP_OK;
-  FCHK(h, hipSetDevice(h->device), "hipSetDevice");
-  IcpIndex ix;
-  std::vector<IcpKnnDesc> knn((size_t)batch);
-  for (int b = 0; b < batch; ++b) {
-    memset(&knn[(size_t)b], 0, sizeof(IcpKnnDesc));
-    knn[(size_t)b].k = nb_points[b];
-    add_problem(ix, b, 0, n[b], points, radius[b], (n[b] + kIcpCovBlock - 1) / kIcpCovBlock);
-  }
-  const int64_t t_off = ix.t_off;
-  const int n_tblk = (int)ix.tblk_prob.size();
-  // B_X: the counts, the kept counts, the mask bytes
-  const size_t o_kept = sizeof(int32_t) * t_off, o_keep = o_kept + sizeof(int32_t) * batch;
-  const size_t out_bytes = o_keep + (size_t)t_off;
-  size_t bytes[B_COUNT] = {};
-  bytes[B_DESC] = sizeof(IcpDesc) * batch;
-  bytes[B_STATE] = sizeof(IcpKnnDesc) * batch;
-  bytes[B_BLK] = sizeof(int32_t) * ix.blk_prob.size();
-  bytes[B_TBLK] = sizeof(int32_t) * n_tblk;
-  bytes[B_X] = out_bytes;
-  bytes[B_Q] = sizeof(double) * 3 * t_off;
-  bytes[B_TBUCKET] = sizeof(int32_t) * t_off;
-  bytes[B_BCOUNT] = bytes[B_BSTART] = bytes[B_CURSOR] = sizeof(int32_t) * ix.b_off;
-  bytes[B_QS] = sizeof(double) * 3 * t_off;
-  bytes[B_QJ] = sizeof(int32_t) * t_off;
-  for (int b = 0; b < B_COUNT; ++b)
-    if (!h->buf[b].ensure(bytes[b])) return fail(h, TEASER_HIP_ERR_OOM, "hipMalloc failed (radius removal buffers)");
-  DevBuf* B = h->buf;
-  char* out = B[B_X].as<char>();
-  h->stage.resize((size_t)(3 * t_off));
-  if ((rc = upload_inputs(h, ix, nullptr, points, knn.data(), bytes[B_STATE])) != TEASER_HIP_OK) return rc;
-  FCHK(h, hipMemsetAsync(out + o_kept, 0, sizeof(int32_t) * batch, h->stream), "hipMemsetAsync");
-  if ((rc = launch_index(h, ix)) != TEASER_HIP_OK) return rc;
-  launch_icp_radius_count(h->stream, B[B_DESC].as<IcpDesc>(), B[B_STATE].as<IcpKnnDesc>(), B[B_TBLK].as<int32_t>(),
-                          n_tblk, B[B_Q].as<double>(), B[B_QS].as<double>(), B[B_BSTART].as<int32_t>(),
-                          (int32_t*)out, (uint8_t*)(out + o_keep), (int32_t*)(out + o_kept));
-  if ((rc = copy_back(h, out_bytes, "radius outlier removal")) != TEASER_HIP_OK) return rc;
-  const char* back = (const char*)h->back.data();
-  for (int b = 0; b < batch; ++b) {
-    if (n[b] == 0) continue;
-    const int64_t o = ix.desc[(size_t)b].t_off;
-    memcpy(keep_out[b], back + o_keep + o, (size_t)n[b]);
-    memcpy(&n_kept_out[b], back + o_kept + sizeof(int32_t) * b, sizeof(int32_t));
-    if (count_out && count_out[b]) memcpy(count_out[b], back + sizeof(int32_t) * o, sizeof(int32_t) * n[b]);
-  }
   return TEASER_HIP_OK;
 }
 

@@ -1,7 +1,12 @@
-// icp_host.h -- what the host files of the ICP handle (icp.hip: the iteration loop, covariance estimation, self k-NN and
-// outlier removal; icp_normals.hip: normal estimation and the self-estimating point-to-plane entry; icp_keypoints.hip:
-// ISS keypoints) share: the handle,
-// its buffers, the per-call index under construction and the uploads.
+// icp_host.h -- what the host files of the ICP handle share (icp.hip: the iteration loop and covariance estimation;
+// icp_outlier.hip: self k-NN, outlier removal and the options; icp_normals.hip: normal estimation and the
+// self-estimating point-to-plane entry; icp_keypoints.hip: ISS keypoints): the handle and its buffers, and the scaffold
+// of a cloud call -- the entry checks (begin_cloud_call), the per-call index under construction (IcpIndex,
+// add_problem), the sizes of the index buffers by name (index_bytes, ensure_buffers), the packing and the uploads
+// (upload_points, upload_inputs), the index build (launch_index), the one copy back (copy_back, read_fallbacks) and
+// the self k-NN stage that outlier removal and the keypoints' resolution run (run_self_knn).  An entry point writes
+// itself what is its own: its argument checks, its records, the layout of B_X, its launches and the scatter of the
+// results.
 #pragma once
 
 #include <math.h>
@@ -106,14 +111,51 @@ inline IcpDesc& add_problem(IcpIndex& ix, int b, int32_t n_s, int32_t n_t, const
   return d;
 }
 
+// The sizes of the buffers that hold a call's index: descriptors, both block maps, the points (B_Q), and per point and
+// per bucket what launch_index fills; with `worklist` also B_MATCH as the self k-NN worklist (2 int32 per point).
+// Counts below `least` (0 or 1) are sized as `least`.  The caller sets what is its own: B_STATE, B_X, B_PARTIALS, ...
+inline void index_bytes(const IcpIndex& ix, int64_t least, bool worklist, size_t (&bytes)[B_COUNT]) {
+  const size_t t = (size_t)std::max(ix.t_off, least), b = (size_t)std::max(ix.b_off, least);
+  bytes[B_DESC] = sizeof(IcpDesc) * ix.desc.size();
+  bytes[B_BLK] = sizeof(int32_t) * std::max<size_t>(ix.blk_prob.size(), (size_t)least);
+  bytes[B_TBLK] = sizeof(int32_t) * std::max<size_t>(ix.tblk_prob.size(), (size_t)least);
+  bytes[B_Q] = bytes[B_QS] = sizeof(double) * 3 * t;
+  bytes[B_TBUCKET] = bytes[B_QJ] = sizeof(int32_t) * t;
+  bytes[B_BCOUNT] = bytes[B_BSTART] = bytes[B_CURSOR] = sizeof(int32_t) * b;
+  if (worklist) bytes[B_MATCH] = sizeof(int32_t) * 2 * (size_t)ix.t_off;
+}
+
+// Grows every buffer of the handle to its entry of `bytes`; `what`: the message of a failed allocation.
+inline int32_t ensure_buffers(teaser_hip_icp* h, const size_t (&bytes)[B_COUNT], const char* what) {
+  for (int k = 0; k < B_COUNT; ++k)
+    if (!h->buf[k].ensure(bytes[k])) return fail(h, TEASER_HIP_ERR_OOM, what);
+  return TEASER_HIP_OK;
+}
+
+// Packs the clouds q[b] (n[b] points each) one after the other -- the order of their descriptors' offsets -- into
+// h->stage from its double `first` on, and enqueues their upload to B_Q; `what`: the message of a failed copy.
+inline int32_t upload_points(teaser_hip_icp* h, int32_t batch, const double* const* q, const int32_t* n, size_t first,
+                             const char* what) {
+  size_t at = first;
+  for (int b = 0; b < batch; ++b) {
+    if (n[b]) memcpy(&h->stage[at], q[b], 24 * (size_t)n[b]);
+    at += 3 * (size_t)n[b];
+  }
+  if (at > first)
+    FCHK(h, hipMemcpyAsync(h->buf[B_Q].p, &h->stage[first], sizeof(double) * (at - first), hipMemcpyHostToDevice,
+                           h->stream),
+         what);
+  return TEASER_HIP_OK;
+}
+
 // Packs the points into h->stage (sources, then targets; src may be NULL when no problem has any) and enqueues
-// the uploads: descriptors, the per-problem `records` for B_STATE, both block maps, sources, targets.
+// the uploads: descriptors, the per-problem `records` for B_STATE, both block maps, sources, targets (n_dst points
+// per problem).
 inline int32_t upload_inputs(teaser_hip_icp* h, const IcpIndex& ix, const double* const* src, const double* const* dst,
-                      const void* records, size_t record_bytes) {
+                             const int32_t* n_dst, const void* records, size_t record_bytes) {
   for (size_t b = 0; b < ix.desc.size(); ++b) {
     const IcpDesc& d = ix.desc[b];
     if (d.n_s) memcpy(&h->stage[(size_t)(3 * d.s_off)], src[b], 24 * (size_t)d.n_s);
-    if (d.n_t) memcpy(&h->stage[(size_t)(3 * (ix.s_off + d.t_off))], dst[b], 24 * (size_t)d.n_t);
   }
   DevBuf* B = h->buf;
   const struct {
@@ -124,11 +166,11 @@ inline int32_t upload_inputs(teaser_hip_icp* h, const IcpIndex& ix, const double
                 {B[B_STATE].p, records, record_bytes},
                 {B[B_BLK].p, ix.blk_prob.data(), sizeof(int32_t) * ix.blk_prob.size()},
                 {B[B_TBLK].p, ix.tblk_prob.data(), sizeof(int32_t) * ix.tblk_prob.size()},
-                {B[B_X].p, h->stage.data(), sizeof(double) * 3 * ix.s_off},
-                {B[B_Q].p, h->stage.data() + 3 * ix.s_off, sizeof(double) * 3 * ix.t_off}};
+                {B[B_X].p, h->stage.data(), sizeof(double) * 3 * ix.s_off}};
   for (const auto& c : copies)
     if (c.n) FCHK(h, hipMemcpyAsync(c.d, c.hsrc, c.n, hipMemcpyHostToDevice, h->stream), "hipMemcpyAsync (inputs)");
-  return TEASER_HIP_OK;
+  return upload_points(h, (int32_t)ix.desc.size(), dst, n_dst, (size_t)(3 * ix.s_off),
+                       "hipMemcpyAsync (inputs)");
 }
 
 // Clears the bucket counts and enqueues the kernels that build the index over the uploaded targets.
@@ -154,6 +196,45 @@ inline int32_t check_clouds(teaser_hip_icp* h, int32_t batch, const double* cons
   }
   if (*total >= INT32_MAX / 9) return fail(h, TEASER_HIP_ERR_BAD_ARG, "too many points in one call");
   return TEASER_HIP_OK;
+}
+
+// How a cloud call begins: the handle, its cleared error (and, for the calls that report it, fallback count), batch
+// and check_clouds.  done: the entry point returns rc at once; else total = the number of points.
+struct CallStart {
+  int32_t rc;
+  bool done;
+  int64_t total;
+};
+inline CallStart begin_cloud_call(teaser_hip_icp* h, int32_t batch, const double* const* points, const int32_t* n,
+                                  bool reset_fallbacks) {
+  if (!h) return {TEASER_HIP_ERR_BAD_ARG, true, 0};
+  h->err.clear();
+  if (reset_fallbacks) h->knn_fallbacks = 0;
+  if (batch < 0) return {fail(h, TEASER_HIP_ERR_BAD_ARG, "batch must be >= 0"), true, 0};
+  if (batch == 0) return {TEASER_HIP_OK, true, 0};
+  CallStart c = {TEASER_HIP_OK, false, 0};
+  c.rc = check_clouds(h, batch, points, n, &c.total);
+  c.done = c.rc != TEASER_HIP_OK;
+  return c;
+}
+
+// The one copy back of a call (`bytes` of B_X from byte `off` -> h->back) and its synchronisation.  launch NULL: the
+// caller has checked its launches already.
+inline int32_t copy_back(teaser_hip_icp* h, size_t off, size_t bytes, const char* sync,
+                         const char* launch = "kernel launch (k-NN / outlier removal)",
+                         const char* copy = "hipMemcpyAsync (results)") {
+  h->back.resize((bytes + 7) / 8);
+  if (launch) FCHK(h, hipGetLastError(), launch);
+  FCHK(h, hipMemcpyAsync(h->back.data(), h->buf[B_X].as<char>() + off, bytes, hipMemcpyDeviceToHost, h->stream), copy);
+  FCHK(h, hipStreamSynchronize(h->stream), sync);
+  return TEASER_HIP_OK;
+}
+
+// knn_fallbacks of the call: the worklist counter, at byte `off` of what copy_back brought.
+inline void read_fallbacks(teaser_hip_icp* h, size_t off) {
+  int32_t fallbacks = 0;
+  memcpy(&fallbacks, (const char*)h->back.data() + off, sizeof(int32_t));
+  h->knn_fallbacks = fallbacks;
 }
 
 // The cell edge h of the self k-NN grid of one cloud (n > 0 points, `want` = min(k, n) neighbours per query): the
@@ -188,6 +269,22 @@ inline double knn_edge(const double* q, int32_t n, int32_t want, bool* rings_ok)
   }
   return std::max(hh, E / 1048576.0);
 }
+
+// Where one self k-NN stage puts its outputs in B_X (byte offsets).  res_per_cloud is set by the caller: doubles per
+// cloud, cleared with the worklist counter and lying right in front of it, so that one memset and one copy serve both
+// (self k-NN only; the keypoints' resolutions).
+struct KnnLayout {
+  int res_per_cloud = 0;
+  size_t d2 = 0, idx = 0, avg = 0, stats = 0, res = 0, ints = 0, counter = 0, keep = 0, bytes = 0;
+  int64_t slots = 0;  // sum of n k (self k-NN)
+};
+
+// Index and self k-NN launches of one call (icp_outlier.hip).  k[b] neighbours per cloud; ratio NULL: self k-NN (idx /
+// d2 outputs at L.idx / L.d2 of B_X), else statistical removal (avg at L.avg, the kept counts at L.ints); the worklist
+// counter at L.counter.  B_PARTIALS holds a double per target block unless the call is
+// plain self k-NN.  Leaves the descriptors in ix.
+int32_t run_self_knn(teaser_hip_icp* h, int32_t batch, const double* const* points, const int32_t* n, const int32_t* k,
+                     const double* ratio, IcpIndex& ix, KnnLayout& L);
 
 // Called by icp_run_batch between the uploads and the index build of the iterations: ix is the call's index, the
 // targets lie in B_Q at its offsets.  Returns a status.

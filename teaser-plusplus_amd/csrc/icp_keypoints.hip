@@ -37,69 +37,25 @@ bool auto_radii(const teaser_icp_iss_params_c& p) { return p.salient_radius == 0
 // A radius as given: not negative, finite like its square.
 bool radius_ok(double r) { return std::isfinite(r) && r >= 0 && std::isfinite(r * r); }
 
-// Stage A: res[b] of the clouds with want[b] (n[b] >= 2), through self k-NN with k = 2.
+// Stage A: res[b] of the clouds with want[b] (n[b] >= 2), through self k-NN with k = 2 over those clouds alone.
 int32_t resolutions(teaser_hip_icp* h, int32_t batch, const double* const* points, const int32_t* n,
                     const std::vector<char>& want, std::vector<double>& res) {
+  std::vector<int32_t> nb((size_t)batch), k((size_t)batch, 2);
+  for (int b = 0; b < batch; ++b) nb[(size_t)b] = want[(size_t)b] ? n[b] : 0;
   IcpIndex ix;
-  std::vector<IcpKnnDesc> knn((size_t)batch);
-  int64_t slots = 0;
-  for (int b = 0; b < batch; ++b) {
-    IcpKnnDesc& kd = knn[(size_t)b];
-    memset(&kd, 0, sizeof(kd));
-    kd.k = 2;
-    kd.ring_cap = h->knn_ring_cap;
-    kd.out_off = slots;
-    kd.edge = 1.0;
-    const int32_t nb = want[(size_t)b] ? n[b] : 0;
-    if (nb > 0) {
-      bool rings_ok = true;
-      kd.edge = knn_edge(points[b], nb, 2, &rings_ok);
-      if (!rings_ok) kd.ring_cap = 0;
-    }
-    add_problem(ix, b, 0, nb, points, kd.edge, (nb + kIcpCovBlock - 1) / kIcpCovBlock);
-    slots += 2 * (int64_t)nb;
-  }
-  const int64_t t_off = ix.t_off;
-  const int n_blk = (int)ix.blk_prob.size(), n_tblk = (int)ix.tblk_prob.size();
-  // B_X: the squared distances, the per-cloud resolutions, the worklist counter, then the neighbour indices
-  const size_t o_res = sizeof(double) * slots, o_cnt = o_res + sizeof(double) * batch, o_idx = o_cnt + 8,
-               out_bytes = o_idx + sizeof(int32_t) * slots;
-  size_t bytes[B_COUNT] = {};
-  bytes[B_DESC] = sizeof(IcpDesc) * batch;
-  bytes[B_STATE] = sizeof(IcpKnnDesc) * batch;
-  bytes[B_BLK] = sizeof(int32_t) * n_blk;
-  bytes[B_TBLK] = sizeof(int32_t) * n_tblk;
-  bytes[B_X] = out_bytes;
-  bytes[B_Q] = sizeof(double) * 3 * t_off;
-  bytes[B_TBUCKET] = sizeof(int32_t) * t_off;
-  bytes[B_BCOUNT] = bytes[B_BSTART] = bytes[B_CURSOR] = sizeof(int32_t) * ix.b_off;
-  bytes[B_QS] = sizeof(double) * 3 * t_off;
-  bytes[B_QJ] = sizeof(int32_t) * t_off;
-  bytes[B_MATCH] = sizeof(int32_t) * 2 * t_off;  // the worklist
-  bytes[B_PARTIALS] = sizeof(double) * n_tblk;
-  for (int k = 0; k < B_COUNT; ++k)
-    if (bytes[k] && !h->buf[k].ensure(bytes[k])) return fail(h, TEASER_HIP_ERR_OOM, "hipMalloc failed (resolution buffers)");
-  hipStream_t s = h->stream;
+  KnnLayout L;
+  L.res_per_cloud = 1;  // cleared and copied back together with the worklist counter behind them
+  int32_t rc = run_self_knn(h, batch, points, nb.data(), k.data(), nullptr, ix, L);
+  if (rc != TEASER_HIP_OK) return rc;
   DevBuf* B = h->buf;
   char* out = B[B_X].as<char>();
-  h->stage.resize((size_t)(3 * t_off));
-  int32_t rc = upload_inputs(h, ix, nullptr, points, knn.data(), bytes[B_STATE]);
-  if (rc != TEASER_HIP_OK) return rc;
-  FCHK(h, hipMemsetAsync(out + o_res, 0, sizeof(double) * batch + 8, s), "hipMemsetAsync");
-  if ((rc = launch_index(h, ix)) != TEASER_HIP_OK) return rc;
-  launch_icp_self_knn(s, B[B_DESC].as<IcpDesc>(), B[B_STATE].as<IcpKnnDesc>(), B[B_BLK].as<int32_t>(), n_blk, 2,
-                      B[B_Q].as<double>(), B[B_QS].as<double>(), B[B_QJ].as<int32_t>(), B[B_BSTART].as<int32_t>(),
-                      (int32_t*)(out + o_idx), (double*)out, nullptr, B[B_MATCH].as<int32_t>(), (int32_t*)(out + o_cnt));
-  launch_iss_resolution(s, B[B_DESC].as<IcpDesc>(), B[B_STATE].as<IcpKnnDesc>(), B[B_TBLK].as<int32_t>(), n_tblk, batch,
-                        (const double*)out, B[B_PARTIALS].as<double>(), (double*)(out + o_res));
-  FCHK(h, hipGetLastError(), "kernel launch (resolution)");
-  h->back.resize((size_t)batch + 1);
-  FCHK(h, hipMemcpyAsync(h->back.data(), out + o_res, sizeof(double) * batch + 8, hipMemcpyDeviceToHost, s),
-       "hipMemcpyAsync (resolution)");
-  FCHK(h, hipStreamSynchronize(s), "resolution");
-  int32_t fallbacks = 0;
-  memcpy(&fallbacks, h->back.data() + batch, sizeof(int32_t));
-  h->knn_fallbacks = fallbacks;
+  launch_iss_resolution(h->stream, B[B_DESC].as<IcpDesc>(), B[B_STATE].as<IcpKnnDesc>(), B[B_TBLK].as<int32_t>(),
+                        (int)ix.tblk_prob.size(), batch, (const double*)(out + L.d2), B[B_PARTIALS].as<double>(),
+                        (double*)(out + L.res));
+  if ((rc = copy_back(h, L.res, L.idx - L.res, "resolution", "kernel launch (resolution)",
+                      "hipMemcpyAsync (resolution)")) != TEASER_HIP_OK)
+    return rc;
+  read_fallbacks(h, L.counter - L.res);
   for (int b = 0; b < batch; ++b)
     if (want[(size_t)b]) res[(size_t)b] = h->back[(size_t)b];
   return TEASER_HIP_OK;
@@ -136,14 +92,10 @@ int32_t teaser_hip_icp_iss_keypoints_batch(teaser_hip_icp* h, int32_t batch, con
                                            const int32_t* n, const teaser_icp_iss_params_c* params,
                                            uint8_t* const* keep_out, int32_t* n_keypoints_out,
                                            double* const* saliency_out, int32_t* const* count_out, double* radii_out) {
-  if (!h) return TEASER_HIP_ERR_BAD_ARG;
-  h->err.clear();
-  h->knn_fallbacks = 0;
-  if (batch < 0) return fail(h, TEASER_HIP_ERR_BAD_ARG, "batch must be >= 0");
-  if (batch == 0) return TEASER_HIP_OK;
-  int64_t total = 0;
-  int32_t rc = check_clouds(h, batch, points, n, &total);
-  if (rc != TEASER_HIP_OK) return rc;
+  const CallStart c = begin_cloud_call(h, batch, points, n, true);
+  if (c.done) return c.rc;
+  const int64_t total = c.total;
+  int32_t rc = TEASER_HIP_OK;
   if (!params) return fail(h, TEASER_HIP_ERR_BAD_ARG, "params must not be NULL");
   if (!n_keypoints_out) return fail(h, TEASER_HIP_ERR_BAD_ARG, "n_keypoints_out must not be NULL");
   if (2 * total >= INT32_MAX) return fail(h, TEASER_HIP_ERR_BAD_ARG, "too many points in one call");
@@ -263,15 +215,12 @@ int32_t teaser_hip_icp_iss_keypoints_batch(teaser_hip_icp* h, int32_t batch, con
   bytes[B_KIOTA] = bytes[B_KSIDX] = 4 * 2 * T;
   bytes[B_KSPTS] = 24 * 2 * T;
   bytes[B_KTEMP] = iss_sort_temp_bytes(2 * total);
-  for (int k = 0; k < B_COUNT; ++k)
-    if (bytes[k] && !h->buf[k].ensure(bytes[k])) return fail(h, TEASER_HIP_ERR_OOM, "hipMalloc failed (keypoint buffers)");
+  if ((rc = ensure_buffers(h, bytes, "hipMalloc failed (keypoint buffers)")) != TEASER_HIP_OK) return rc;
   hipStream_t s = h->stream;
   DevBuf* B = h->buf;
   char* out = B[B_X].as<char>();
   h->stage.resize(3 * T);
-  for (int b = 0; b < batch; ++b)
-    if (n[b]) memcpy(&h->stage[3 * (size_t)desc[(size_t)b].off], points[b], 24 * (size_t)n[b]);
-  FCHK(h, hipMemcpyAsync(B[B_Q].p, h->stage.data(), bytes[B_Q], hipMemcpyHostToDevice, s), "hipMemcpyAsync (points)");
+  if ((rc = upload_points(h, batch, points, n, 0, "hipMemcpyAsync (points)")) != TEASER_HIP_OK) return rc;
   FCHK(h, hipMemcpyAsync(B[B_KDESC].p, desc.data(), bytes[B_KDESC], hipMemcpyHostToDevice, s),
        "hipMemcpyAsync (descriptors)");
   FCHK(h, hipMemcpyAsync(B[B_KBLK].p, blk.data(), bytes[B_KBLK], hipMemcpyHostToDevice, s),
@@ -289,10 +238,7 @@ int32_t teaser_hip_icp_iss_keypoints_batch(teaser_hip_icp* h, int32_t batch, con
   launch_iss_suppress(s, dd, dblk, n_blk, total, B[B_KSKEY].as<uint64_t>(), B[B_KSIDX].as<int32_t>(),
                       B[B_KSPTS].as<double>(), (const double*)out, (int32_t*)(out + o_cnt), (uint8_t*)(out + o_keep),
                       (int32_t*)(out + o_kept));
-  FCHK(h, hipGetLastError(), "kernel launch (keypoints)");
-  h->back.resize((out_bytes + 7) / 8);
-  FCHK(h, hipMemcpyAsync(h->back.data(), out, out_bytes, hipMemcpyDeviceToHost, s), "hipMemcpyAsync (results)");
-  FCHK(h, hipStreamSynchronize(s), "keypoint detection");
+  if ((rc = copy_back(h, 0, out_bytes, "keypoint detection", "kernel launch (keypoints)")) != TEASER_HIP_OK) return rc;
   const char* back = (const char*)h->back.data();
   for (int b = 0; b < batch; ++b) {
     if (n[b] == 0) continue;

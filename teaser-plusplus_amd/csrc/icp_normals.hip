@@ -168,21 +168,16 @@ extern "C" {
 int32_t teaser_hip_icp_normals_batch(teaser_hip_icp* h, int32_t batch, const double* const* points, const int32_t* n,
                                      const teaser_icp_normal_search_c* search, double* const* normals_out,
                                      double* const* cov_out, double* const* eig_out) {
-  if (!h) return TEASER_HIP_ERR_BAD_ARG;
-  h->err.clear();
-  h->knn_fallbacks = 0;
-  if (batch < 0) return fail(h, TEASER_HIP_ERR_BAD_ARG, "batch must be >= 0");
-  if (batch == 0) return TEASER_HIP_OK;
-  int64_t total = 0;
-  int32_t rc = check_clouds(h, batch, points, n, &total);
-  if (rc != TEASER_HIP_OK) return rc;
+  const CallStart c = begin_cloud_call(h, batch, points, n, true);
+  if (c.done) return c.rc;
+  int32_t rc = TEASER_HIP_OK;
   if (!search) return fail(h, TEASER_HIP_ERR_BAD_ARG, "search must not be NULL");
   for (int b = 0; b < batch; ++b) {
     if ((rc = check_search(h, search[b], b, "search")) != TEASER_HIP_OK) return rc;
     if (n[b] > 0 && (!normals_out || !normals_out[b]))
       return fail(h, TEASER_HIP_ERR_BAD_ARG, "normals_out is NULL" + at(b));
   }
-  if (total == 0) return TEASER_HIP_OK;
+  if (c.total == 0) return TEASER_HIP_OK;
   FCHK(h, hipSetDevice(h->device), "hipSetDevice");
 
   NormalsPlan P;
@@ -207,33 +202,20 @@ int32_t teaser_hip_icp_normals_batch(teaser_hip_icp* h, int32_t batch, const dou
   const size_t o_cov = sizeof(double) * 3 * t_off, o_eig = o_cov + sizeof(double) * 9 * cov_rows,
                o_cnt = o_eig + sizeof(double) * 3 * eig_rows, out_bytes = o_cnt + sizeof(int32_t);
   size_t bytes[B_COUNT] = {};
+  index_bytes(P.ix, 0, true, bytes);
+  bytes[B_DESC] = bytes[B_TBLK] = 0;  // launch_normals keeps the descriptors and the block maps in B_N*
   bytes[B_X] = out_bytes;
-  bytes[B_Q] = sizeof(double) * 3 * t_off;
-  bytes[B_TBUCKET] = sizeof(int32_t) * t_off;
-  bytes[B_BCOUNT] = bytes[B_BSTART] = bytes[B_CURSOR] = sizeof(int32_t) * P.ix.b_off;
-  bytes[B_QS] = sizeof(double) * 3 * t_off;
-  bytes[B_QJ] = sizeof(int32_t) * t_off;
-  bytes[B_MATCH] = sizeof(int32_t) * 2 * t_off;  // the worklist
-  for (int k = 0; k < B_COUNT; ++k)
-    if (!h->buf[k].ensure(bytes[k])) return fail(h, TEASER_HIP_ERR_OOM, "hipMalloc failed (normals buffers)");
+  if ((rc = ensure_buffers(h, bytes, "hipMalloc failed (normals buffers)")) != TEASER_HIP_OK) return rc;
   DevBuf* B = h->buf;
   h->stage.resize((size_t)(3 * t_off));
-  for (int b = 0; b < batch; ++b)
-    if (n[b]) memcpy(&h->stage[(size_t)(3 * P.ix.desc[(size_t)b].t_off)], points[b], 24 * (size_t)n[b]);
-  FCHK(h, hipMemcpyAsync(B[B_Q].p, h->stage.data(), bytes[B_Q], hipMemcpyHostToDevice, h->stream),
-       "hipMemcpyAsync (points)");
+  if ((rc = upload_points(h, batch, points, n, 0, "hipMemcpyAsync (points)")) != TEASER_HIP_OK) return rc;
   char* out = B[B_X].as<char>();
   if ((rc = launch_normals(h, P, B[B_Q].as<double>(), (double*)out, (double*)(out + o_cov), (double*)(out + o_eig),
                            (int32_t*)(out + o_cnt))) != TEASER_HIP_OK)
     return rc;
-  h->back.resize((out_bytes + 7) / 8);
-  FCHK(h, hipMemcpyAsync(h->back.data(), B[B_X].p, out_bytes, hipMemcpyDeviceToHost, h->stream),
-       "hipMemcpyAsync (results)");
-  FCHK(h, hipStreamSynchronize(h->stream), "normal estimation");
+  if ((rc = copy_back(h, 0, out_bytes, "normal estimation", nullptr)) != TEASER_HIP_OK) return rc;
+  read_fallbacks(h, o_cnt);
   const char* back = (const char*)h->back.data();
-  int32_t fallbacks = 0;
-  memcpy(&fallbacks, back + o_cnt, sizeof(int32_t));
-  h->knn_fallbacks = fallbacks;
   for (int b = 0; b < batch; ++b) {
     if (n[b] == 0) continue;
     const IcpNormalDesc& nd = P.nd[(size_t)b];

@@ -1,5 +1,5 @@
-// Host-only check of ISS keypoint detection (tests/test_keypoints_host.py): csrc/icp.hip and csrc/icp_keypoints.hip
-// compiled by g++ against the HIP stand-in header, with the SOURCE of the lane-independent device code --
+// Host-only check of ISS keypoint detection (tests/test_keypoints_host.py): csrc/icp.hip, csrc/icp_outlier.hip and
+// csrc/icp_keypoints.hip compiled by g++ against the HIP stand-in header, with the SOURCE of the lane-independent device code --
 // csrc/icp_iss_device.h (keys, gather, the ordered neighbourhood walk, saliency, suppression, resolution) and the ring
 // kernel of csrc/kernels_outlier.hip for the resolution's self k-NN -- run one lane at a time (tests/hip_stub runs a
 // launch sequentially), built with -fsanitize=address,undefined as a stand-alone program.  "Device" buffers are host
@@ -11,59 +11,15 @@
 // reaches the worklist (asserted).
 //   keypoints_host_driver CASES.txt    exit code 0: every case equal and every refusal refused
 // TEST INFRASTRUCTURE ONLY.
-#include <hip/hip_runtime.h>
-
-#include <algorithm>
-#include <cmath>
-#include <cstdio>
-#include <cstring>
 #include <numeric>
-#include <string>
-#include <vector>
 
-inline hipError_t hipHostMalloc(void** p, size_t n) { return hipHostMalloc(p, n, 0u); }
-thread_local stub_dim3_ blockIdx, threadIdx, gridDim, blockDim;
-template <class T> T atomicAdd(T* p, T v) { T o = *p; *p += v; return o; }
-#define __ballot(k) ((k) ? 1ull : 0ull)
-#define __popcll(b) __builtin_popcountll(b)
-template <class T> T __shfl_xor(T v, int, int) { return v; }
-#define __forceinline__ inline
+#include "icp_host_prelude.h"
 #include "../teaser-plusplus_amd/csrc/kernels_outlier.hip"
 #include "../teaser-plusplus_amd/csrc/icp.hip"
+#include "../teaser-plusplus_amd/csrc/icp_outlier.hip"
 #include "../teaser-plusplus_amd/csrc/icp_keypoints.hip"
 
 namespace thip {
-
-// the index of kernels_icp.hip (count, scan, fill), in plain loops: bucket starts, points and indices in bucket order
-void launch_icp_index(hipStream_t, const IcpDesc* desc, const int32_t*, int, int batch, const double* q, int32_t*,
-                      int32_t*, int32_t* bstart, int32_t*, double* qs, int32_t* qj) {
-  for (int p = 0; p < batch; ++p) {
-    const IcpDesc& d = desc[p];
-    if (d.n_t == 0) continue;
-    const int64_t tb = d.tb_mask + 1;
-    std::vector<int32_t> start((size_t)tb + 1, 0), cur((size_t)tb, 0);
-    std::vector<int64_t> bk((size_t)d.n_t);
-    for (int j = 0; j < d.n_t; ++j) {
-      const double* y = q + 3 * (d.t_off + j);
-      bk[(size_t)j] = icp_bucket(icp_cell(y[0], d.origin[0], d.inv_h), icp_cell(y[1], d.origin[1], d.inv_h),
-                                 icp_cell(y[2], d.origin[2], d.inv_h), d.tb_mask);
-      start[(size_t)bk[(size_t)j] + 1]++;
-    }
-    for (int64_t b = 0; b < tb; ++b) start[(size_t)b + 1] += start[(size_t)b];
-    for (int64_t b = 0; b <= tb; ++b) bstart[d.b_off + b] = (int32_t)d.t_off + start[(size_t)b];
-    for (int j = d.n_t - 1; j >= 0; --j) {  // any order inside a bucket: the list is sorted by (d2, j)
-      const int64_t pos = d.t_off + start[(size_t)bk[(size_t)j]] + cur[(size_t)bk[(size_t)j]]++;
-      qj[pos] = j;
-      for (int c = 0; c < 3; ++c) qs[3 * pos + c] = q[3 * (d.t_off + j) + c];
-    }
-  }
-}
-void launch_icp_iteration(hipStream_t, const IcpDesc*, IcpState*, const int32_t*, int, int, double*, const double*,
-                          const int32_t*, const int32_t*, const double*, const double*, const double*, int, int32_t*,
-                          double*) {}
-void launch_icp_covariances(hipStream_t, const IcpDesc*, const IcpCovDesc*, const int32_t*, int, int, const double*,
-                            const double*, const int32_t*, const int32_t*, double*) {}
-void launch_icp_live(hipStream_t, const IcpState*, int, int32_t* live) { *live = 0; }
 
 // ---- kernels_keypoints.hip: the sort behind one function, the shells restated on the same bodies ----
 size_t iss_sort_temp_bytes(int64_t) { return 16; }
@@ -135,23 +91,6 @@ struct Case {
   std::vector<int32_t> count;
 };
 
-static int g_bad = 0;
-static void expect(bool ok, const char* what, int c) {
-  if (!ok) {
-    std::fprintf(stderr, "case %d: %s\n", c, what);
-    ++g_bad;
-  }
-}
-// equal bits; NaN equals NaN (the contract only says NaN)
-static bool same(const std::vector<double>& a, const std::vector<double>& b) {
-  if (a.size() != b.size()) return false;
-  for (size_t k = 0; k < a.size(); ++k) {
-    if (std::isnan(a[k]) && std::isnan(b[k])) continue;
-    if (memcmp(&a[k], &b[k], 8) != 0) return false;
-  }
-  return true;
-}
-
 int main(int argc, char** argv) {
   if (argc != 2) return 2;
   FILE* f = std::fopen(argv[1], "r");
@@ -159,28 +98,19 @@ int main(int argc, char** argv) {
   int n_cases = 0;
   if (std::fscanf(f, "%d", &n_cases) != 1) return 2;
   std::vector<Case> cases((size_t)n_cases);
-  auto number = [&]() {
-    char tok[64];
-    if (std::fscanf(f, "%63s", tok) != 1) std::exit(2);
-    return std::strtod(tok, nullptr);
-  };
-  auto doubles = [&](std::vector<double>& v, size_t cnt) {
-    v.resize(cnt);
-    for (double& x : v) x = number();
-  };
   for (Case& c : cases) {
-    c.n = (int)number();
+    c.n = (int)read_number(f);
     memset(&c.prm, 0, sizeof(c.prm));
-    c.prm.salient_radius = number(), c.prm.non_max_radius = number();
-    c.prm.gamma_21 = number(), c.prm.gamma_32 = number();
-    c.prm.min_neighbors = (int32_t)number();
-    doubles(c.pts, 3 * (size_t)c.n);
+    c.prm.salient_radius = read_number(f), c.prm.non_max_radius = read_number(f);
+    c.prm.gamma_21 = read_number(f), c.prm.gamma_32 = read_number(f);
+    c.prm.min_neighbors = (int32_t)read_number(f);
+    read_numbers(f, c.pts, 3 * (size_t)c.n);
     c.keep.resize((size_t)c.n);
-    for (uint8_t& k : c.keep) k = (uint8_t)number();
-    doubles(c.sal, (size_t)c.n);
+    for (uint8_t& k : c.keep) k = (uint8_t)read_number(f);
+    read_numbers(f, c.sal, (size_t)c.n);
     c.count.resize(2 * (size_t)c.n);
-    for (int32_t& k : c.count) k = (int32_t)number();
-    doubles(c.radii, 3);
+    for (int32_t& k : c.count) k = (int32_t)read_number(f);
+    read_numbers(f, c.radii, 3);
   }
   std::fclose(f);
 
@@ -225,9 +155,9 @@ int main(int argc, char** argv) {
           const Case& cs = cases[(size_t)(lo + c)];
           expect(keep[c] == cs.keep, "mask", lo + c);
           expect(kept[c] == (int32_t)std::count(cs.keep.begin(), cs.keep.end(), 1), "keypoint count", lo + c);
-          if (ps[c]) expect(same(sal[c], cs.sal), "saliencies", lo + c);
+          if (ps[c]) expect(same(sal[c], cs.sal, true), "saliencies", lo + c);
           if (pc[c]) expect(cnt[c] == cs.count, "counts", lo + c);
-          expect(same(std::vector<double>(radii.begin() + 3 * c, radii.begin() + 3 * c + 3), cs.radii), "radii", lo + c);
+          expect(same(std::vector<double>(radii.begin() + 3 * c, radii.begin() + 3 * c + 3), cs.radii, true), "radii", lo + c);
         }
       }
     }

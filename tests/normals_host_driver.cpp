@@ -1,4 +1,4 @@
-// Host-only check of normal estimation (tests/test_normals_host.py): csrc/icp.hip and csrc/icp_normals.hip compiled by
+// Host-only check of normal estimation (tests/test_normals_host.py): csrc/icp.hip, csrc/icp_outlier.hip and csrc/icp_normals.hip compiled by
 // g++ against the HIP stand-in header, with the SOURCE of the lane-independent device code -- icp_cov_device.h and the
 // ring kernel of csrc/kernels_outlier.hip with its covariance consumer -- run one lane at a time (tests/hip_stub runs a
 // launch sequentially), built with -fsanitize=address,undefined.  "Device" buffers are host allocations of exactly the
@@ -9,58 +9,13 @@
 // time: no query of these cases reaches the worklist (asserted), and the scan launch finds it empty.
 //   normals_host_driver CASES.txt    exit code 0: every case equal and every refusal refused
 // TEST INFRASTRUCTURE ONLY.
-#include <hip/hip_runtime.h>
-
-#include <algorithm>
-#include <cmath>
-#include <cstdio>
-#include <cstring>
-#include <string>
-#include <vector>
-
-inline hipError_t hipHostMalloc(void** p, size_t n) { return hipHostMalloc(p, n, 0u); }
-thread_local stub_dim3_ blockIdx, threadIdx, gridDim, blockDim;
-template <class T> T atomicAdd(T* p, T v) { T o = *p; *p += v; return o; }
-#define __ballot(k) ((k) ? 1ull : 0ull)
-#define __popcll(b) __builtin_popcountll(b)
-template <class T> T __shfl_xor(T v, int, int) { return v; }
-#define __forceinline__ inline
+#include "icp_host_prelude.h"
 #include "../teaser-plusplus_amd/csrc/kernels_outlier.hip"
 #include "../teaser-plusplus_amd/csrc/icp.hip"
+#include "../teaser-plusplus_amd/csrc/icp_outlier.hip"
 #include "../teaser-plusplus_amd/csrc/icp_normals.hip"
 
 namespace thip {
-
-// the index of kernels_icp.hip (count, scan, fill), in plain loops: bucket starts, points and indices in bucket order
-void launch_icp_index(hipStream_t, const IcpDesc* desc, const int32_t*, int, int batch, const double* q, int32_t*,
-                      int32_t*, int32_t* bstart, int32_t*, double* qs, int32_t* qj) {
-  for (int p = 0; p < batch; ++p) {
-    const IcpDesc& d = desc[p];
-    if (d.n_t == 0) continue;
-    const int64_t tb = d.tb_mask + 1;
-    std::vector<int32_t> start((size_t)tb + 1, 0), cur((size_t)tb, 0);
-    std::vector<int64_t> bk((size_t)d.n_t);
-    for (int j = 0; j < d.n_t; ++j) {
-      const double* y = q + 3 * (d.t_off + j);
-      bk[(size_t)j] = icp_bucket(icp_cell(y[0], d.origin[0], d.inv_h), icp_cell(y[1], d.origin[1], d.inv_h),
-                                 icp_cell(y[2], d.origin[2], d.inv_h), d.tb_mask);
-      start[(size_t)bk[(size_t)j] + 1]++;
-    }
-    for (int64_t b = 0; b < tb; ++b) start[(size_t)b + 1] += start[(size_t)b];
-    for (int64_t b = 0; b <= tb; ++b) bstart[d.b_off + b] = (int32_t)d.t_off + start[(size_t)b];
-    for (int j = d.n_t - 1; j >= 0; --j) {  // any order inside a bucket: the list is sorted by (d2, j)
-      const int64_t pos = d.t_off + start[(size_t)bk[(size_t)j]] + cur[(size_t)bk[(size_t)j]]++;
-      qj[pos] = j;
-      for (int c = 0; c < 3; ++c) qs[3 * pos + c] = q[3 * (d.t_off + j) + c];
-    }
-  }
-}
-void launch_icp_iteration(hipStream_t, const IcpDesc*, IcpState*, const int32_t*, int, int, double*, const double*,
-                          const int32_t*, const int32_t*, const double*, const double*, const double*, int, int32_t*,
-                          double*) {}
-void launch_icp_covariances(hipStream_t, const IcpDesc*, const IcpCovDesc*, const int32_t*, int, int, const double*,
-                            const double*, const int32_t*, const int32_t*, double*) {}
-void launch_icp_live(hipStream_t, const IcpState*, int, int32_t* live) { *live = 0; }
 
 // icp_normals_kernel of kernels_icp.hip, restated on the same device functions
 template <int CAP>
@@ -105,16 +60,6 @@ struct Case {
   std::vector<double> pts, nrm, cov, eig;
 };
 
-static int g_bad = 0;
-static void expect(bool ok, const char* what, int c) {
-  if (!ok) {
-    std::fprintf(stderr, "case %d: %s\n", c, what);
-    ++g_bad;
-  }
-}
-static bool same(const std::vector<double>& a, const std::vector<double>& b) {
-  return a.size() == b.size() && (a.empty() || memcmp(a.data(), b.data(), 8 * a.size()) == 0);
-}
 static teaser_icp_normal_search_c record(const Case& c) {
   teaser_icp_normal_search_c r;
   memset(&r, 0, sizeof(r));
@@ -150,30 +95,19 @@ int main(int argc, char** argv) {
   int n_cases = 0;
   if (std::fscanf(f, "%d", &n_cases) != 1) return 2;
   std::vector<Case> cases((size_t)n_cases);
-  auto doubles = [&](std::vector<double>& v, size_t cnt) {
-    v.resize(cnt);
-    for (double& x : v) {
-      char tok[64];
-      if (std::fscanf(f, "%63s", tok) != 1) std::exit(2);
-      x = std::strtod(tok, nullptr);
-    }
-  };
   for (Case& c : cases) {
-    char t[4][64];
-    if (std::fscanf(f, "%d %d %d %d %63s %63s %63s %63s", &c.n, &c.search, &c.max_nn, &c.orient, t[0], t[1], t[2],
-                    t[3]) != 8)
-      return 2;
-    c.radius = std::strtod(t[0], nullptr);
-    for (int k = 0; k < 3; ++k) c.ref[k] = std::strtod(t[k + 1], nullptr);
-    doubles(c.pts, 3 * (size_t)c.n);
-    doubles(c.nrm, 3 * (size_t)c.n);
-    doubles(c.cov, 9 * (size_t)c.n);
-    doubles(c.eig, 3 * (size_t)c.n);
+    c.n = (int)read_number(f), c.search = (int)read_number(f), c.max_nn = (int)read_number(f);
+    c.orient = (int)read_number(f), c.radius = read_number(f);
+    for (int k = 0; k < 3; ++k) c.ref[k] = read_number(f);
+    read_numbers(f, c.pts, 3 * (size_t)c.n);
+    read_numbers(f, c.nrm, 3 * (size_t)c.n);
+    read_numbers(f, c.cov, 9 * (size_t)c.n);
+    read_numbers(f, c.eig, 3 * (size_t)c.n);
   }
   std::vector<double> planted;  // outlier_reference.planted_cloud(), after the cases
   int n_planted = 0;
   if (std::fscanf(f, "%d", &n_planted) != 1) return 2;
-  doubles(planted, 3 * (size_t)n_planted);
+  read_numbers(f, planted, 3 * (size_t)n_planted);
   std::fclose(f);
   // what tests/test_gpu_normals.py expects of the planted cloud at ring cap 4: k = 10 reaches the worklist, k = 30 not
   const int fell10 = worklist_entries(planted, 10), fell30 = worklist_entries(planted, 30);

@@ -1,36 +1,19 @@
-// Host-only check of the self k-NN / outlier-removal entry points (tests/test_outlier_host.py): csrc/icp.hip compiled
+// Host-only check of the self k-NN / outlier-removal entry points (tests/test_outlier_host.py): csrc/icp_outlier.hip compiled
 // by g++ against the HIP stand-in header (tests/hip_stub) with CPU stand-ins for the kernel launchers, built with
 // -fsanitize=address,undefined.  "Device" buffers are host allocations of exactly the size the host code asked for, so
 // a descriptor, an output layout or a worklist that is sized or addressed wrongly is an AddressSanitizer report; the
 // results are compared bit for bit with the numbers of tests/outlier_reference.py, read from a text file.
 //   outlier_host_driver CASES.txt    exit code 0: every case equal and every refusal refused
 // TEST INFRASTRUCTURE ONLY.
-#include <hip/hip_runtime.h>
-
-#include <algorithm>
-#include <cmath>
-#include <cstdio>
-#include <cstring>
-#include <string>
 #include <utility>
-#include <vector>
 
-inline hipError_t hipHostMalloc(void** p, size_t n) { return hipHostMalloc(p, n, 0u); }
-thread_local stub_dim3_ blockIdx, threadIdx, gridDim, blockDim;
-
+#include "icp_host_prelude.h"
 #include "../teaser-plusplus_amd/csrc/icp.hip"
+#include "../teaser-plusplus_amd/csrc/icp_outlier.hip"
 
 namespace thip {
 
-void launch_icp_index(hipStream_t, const IcpDesc*, const int32_t*, int, int, const double*, int32_t*, int32_t*,
-                      int32_t*, int32_t*, double*, int32_t*) {}  // the stand-ins below search the points themselves
-void launch_icp_iteration(hipStream_t, const IcpDesc*, IcpState*, const int32_t*, int, int, double*, const double*,
-                          const int32_t*, const int32_t*, const double*, const double*, const double*, int, int32_t*,
-                          double*) {}
-void launch_icp_covariances(hipStream_t, const IcpDesc*, const IcpCovDesc*, const int32_t*, int, int, const double*,
-                            const double*, const int32_t*, const int32_t*, double*) {}
-void launch_icp_live(hipStream_t, const IcpState*, int, int32_t* live) { *live = 0; }
-
+// (the search stand-ins below look through the points themselves, not the index)
 static double dist2(const double* a, const double* b) {
   const double e0 = a[0] - b[0], e1 = a[1] - b[1], e2 = a[2] - b[2];
   return (e0 * e0 + e1 * e1) + e2 * e2;
@@ -144,21 +127,6 @@ struct Case {
   std::vector<uint8_t> keep_s, keep_r;
 };
 
-static bool same(const std::vector<double>& a, const std::vector<double>& b) {
-  if (a.size() != b.size()) return false;
-  for (size_t i = 0; i < a.size(); ++i)
-    if (!(std::isnan(a[i]) && std::isnan(b[i])) && memcmp(&a[i], &b[i], 8) != 0) return false;
-  return true;
-}
-
-static int g_bad = 0;
-static void expect(bool ok, const char* what, int c) {
-  if (!ok) {
-    std::fprintf(stderr, "case %d: %s\n", c, what);
-    ++g_bad;
-  }
-}
-
 int main(int argc, char** argv) {
   if (argc != 2) return 2;
   FILE* f = std::fopen(argv[1], "r");
@@ -166,36 +134,18 @@ int main(int argc, char** argv) {
   int n_cases = 0;
   if (std::fscanf(f, "%d", &n_cases) != 1) return 2;
   std::vector<Case> cases((size_t)n_cases);
-  auto doubles = [&](std::vector<double>& v, size_t cnt) {
-    v.resize(cnt);
-    for (double& x : v) {
-      char tok[64];
-      if (std::fscanf(f, "%63s", tok) != 1) std::exit(2);
-      x = std::strtod(tok, nullptr);  // hexadecimal floats, "nan", "inf"
-    }
-  };
-  auto ints = [&](auto& v, size_t cnt) {
-    v.resize(cnt);
-    for (auto& x : v) {
-      int t;
-      if (std::fscanf(f, "%d", &t) != 1) std::exit(2);
-      x = (typename std::remove_reference<decltype(x)>::type)t;
-    }
-  };
   for (Case& c : cases) {
-    char r1[64], r2[64];
-    if (std::fscanf(f, "%d %d %63s %d %63s", &c.n, &c.k, r1, &c.nb, r2) != 5) return 2;
-    c.ratio = std::strtod(r1, nullptr);
-    c.radius = std::strtod(r2, nullptr);
+    c.n = (int)read_number(f), c.k = (int)read_number(f), c.ratio = read_number(f);
+    c.nb = (int)read_number(f), c.radius = read_number(f);
     const size_t n = (size_t)c.n;
-    doubles(c.pts, 3 * n);
-    ints(c.idx, n * (size_t)c.k);
-    doubles(c.d2, n * (size_t)c.k);
-    doubles(c.avg, n);
-    doubles(c.stats, 3);
-    ints(c.keep_s, n);
-    ints(c.count, n);
-    ints(c.keep_r, n);
+    read_numbers(f, c.pts, 3 * n);
+    read_numbers(f, c.idx, n * (size_t)c.k);
+    read_numbers(f, c.d2, n * (size_t)c.k);
+    read_numbers(f, c.avg, n);
+    read_numbers(f, c.stats, 3);
+    read_numbers(f, c.keep_s, n);
+    read_numbers(f, c.count, n);
+    read_numbers(f, c.keep_r, n);
   }
   std::fclose(f);
 
@@ -240,9 +190,9 @@ int main(int argc, char** argv) {
         for (int c = 0; c < b; ++c) {
           const Case& cs = cases[(size_t)(lo + c)];
           expect(idx[c] == cs.idx, "idx", lo + c);
-          expect(same(d2[c], cs.d2), "d2", lo + c);
-          expect(same(avg[c], cs.avg), "avg", lo + c);
-          expect(same(std::vector<double>(stats.begin() + 3 * c, stats.begin() + 3 * c + 3), cs.stats), "stats", lo + c);
+          expect(same(d2[c], cs.d2, true), "d2", lo + c);
+          expect(same(avg[c], cs.avg, true), "avg", lo + c);
+          expect(same(std::vector<double>(stats.begin() + 3 * c, stats.begin() + 3 * c + 3), cs.stats, true), "stats", lo + c);
           expect(ks[c] == cs.keep_s, "statistical mask", lo + c);
           expect(kept_s[c] == (int32_t)std::count(cs.keep_s.begin(), cs.keep_s.end(), 1), "statistical count", lo + c);
           expect(count[c] == cs.count && kr[c] == cs.keep_r, "radius", lo + c);

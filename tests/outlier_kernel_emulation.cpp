@@ -1,37 +1,17 @@
 // The SOURCE of the ring-search and radius-count kernels (csrc/kernels_outlier.hip) compiled for the host and run one
-// thread at a time (tests/hip_stub runs a launch sequentially) against brute force, with the grids that csrc/icp.hip's
-// own set_grid / knn_edge build (icp.hip is part of this translation unit) -- tests/test_outlier_host.py builds it
+// thread at a time (tests/hip_stub runs a launch sequentially) against brute force, with the grids that csrc/icp_host.h's
+// own set_grid / knn_edge build (the handle's host files are part of this translation unit) -- tests/test_outlier_host.py builds it
 // with -fsanitize=address,undefined.  One lane at a time is exact for these two kernels: a lane reads and writes only
 // its own column of the LDS lists and its own outputs.  The wave-wide operations are NOT emulated: the kept counts (a
 // ballot) are not compared, and a query the ring kernel puts on the worklist is only counted -- the scan kernel, whose
 // merge is a wave shuffle, does not run here.
 // TEST INFRASTRUCTURE ONLY.
-#include <hip/hip_runtime.h>
-#include <algorithm>
-#include <cmath>
-#include <cstdio>
 #include <random>
-#include <vector>
-inline hipError_t hipHostMalloc(void** p, size_t n) { return hipHostMalloc(p, n, 0u); }
-thread_local stub_dim3_ blockIdx, threadIdx, gridDim, blockDim;
-template <class T> T atomicAdd(T* p, T v) { T o = *p; *p += v; return o; }
-#define __ballot(k) ((k) ? 1ull : 0ull)
-#define __popcll(b) __builtin_popcountll(b)
-template <class T> T __shfl_xor(T v, int, int) { return v; }
-#define __forceinline__ inline
+
+#include "icp_host_prelude.h"
 #include "../teaser-plusplus_amd/csrc/kernels_outlier.hip"
 #include "../teaser-plusplus_amd/csrc/icp.hip"
-
-namespace thip {  // the launchers of kernels_icp.hip that icp.hip refers to; nothing here calls them
-void launch_icp_index(hipStream_t, const IcpDesc*, const int32_t*, int, int, const double*, int32_t*, int32_t*,
-                      int32_t*, int32_t*, double*, int32_t*) {}
-void launch_icp_iteration(hipStream_t, const IcpDesc*, IcpState*, const int32_t*, int, int, double*, const double*,
-                          const int32_t*, const int32_t*, const double*, const double*, const double*, int, int32_t*,
-                          double*) {}
-void launch_icp_covariances(hipStream_t, const IcpDesc*, const IcpCovDesc*, const int32_t*, int, int, const double*,
-                            const double*, const int32_t*, const int32_t*, double*) {}
-void launch_icp_live(hipStream_t, const IcpState*, int, int32_t*) {}
-}  // namespace thip
+#include "../teaser-plusplus_amd/csrc/icp_outlier.hip"
 
 static int g_fell = 0;  // worklist entries of the last run
 static int expect_fell(bool ok, const char* what) {

@@ -7,7 +7,11 @@ icp_live_kernel, icp_finalize_kernel) launch (batch + 255) / 256 blocks of 256: 
 from cloud 256 on.  The kernels that give one thread to a 256-point block of the packed clouds
 (icp_stat_block_kernel<0/1>, iss_res_block_kernel) need more than 256 such blocks for the same reason, and the block
 maps (blk_prob, tblk_prob, blk_off, tblk_off) then hold hundreds of clouds.  One shared batch of 320 small clouds serves
-all of it; clouds 0, 255, 256, 257 and 319 are also compared with the same cloud called alone (tobytes equality)."""
+all of it; clouds 0, 255, 256, 257 and 319 are also compared with the same cloud called alone (tobytes equality).
+
+The last test is about the handle, not the width: the calls of every kind on the ICP handle share its buffers and the
+host scaffold of csrc/icp_host.h, so they are run one after the other on ONE handle, in both orders, and compared bit
+for bit with the same calls on fresh handles."""
 import importlib
 
 import numpy as np
@@ -250,3 +254,61 @@ def test_registration_icp_batch_with_300_problems(method):
                                     source_covariances=cs[i], target_covariances=ct[i])
         assert same_bits(got[i], alone), i
         assert not np.array_equal(alone.transformation, np.eye(4)), i
+
+
+def blob(x):
+    """Every number of a result as bytes, in a fixed order."""
+    if isinstance(x, dict):
+        return [(k, blob(x[k])) for k in sorted(x)]
+    if isinstance(x, (list, tuple)):
+        return [blob(v) for v in x]
+    if hasattr(x, "__dict__"):
+        return blob(vars(x))
+    return np.asarray(x).tobytes()
+
+
+def test_calls_of_every_kind_on_one_handle_equal_the_same_calls_on_fresh_handles():
+    """Keypoints with automatic radii, radius removal, normals with k-NN search, self k-NN, statistical removal,
+    covariances and the ICP entry that estimates its normals, then the same list backwards, all on one handle; every
+    call over clouds of 300, 0, 65, 1 and 257 points (the largest first: the later clouds meet grown buffers).  A call
+    that left something behind in a shared buffer, or sized one for itself alone, shows as a bit that differs from the
+    same call on a handle of its own -- and so does "knn_fallbacks", which the far point of the first cloud makes
+    non-zero.  Radius removal and covariance estimation run no k-NN search and by the contract leave the option alone
+    (include/teaser_hip.h, "Options of an ICP handle"): after them it must still hold what the last call that reports
+    it left, which is 0 on a fresh handle.  No restatement: 14 + 7 small calls, well under a second."""
+    clouds = [RN.cube(n, 300 + n) for n in (300, 0, 65, 1, 257)]
+    clouds[0][7] = 1000.0  # rings 0 .. 3 of its grid hold none of its neighbours: the whole-cloud route serves it
+    rng = np.random.default_rng(12)
+    srcs = [X + rng.normal(0, 0.01, X.shape) for X in clouds]
+    plane = tp.TransformationEstimationPointToPlane()
+    ests = [plane if len(X) else None for X in clouds]
+    searches = [KNN(10) if len(X) else None for X in clouds]
+    crit = tp.ICPConvergenceCriteria(max_iteration=5)
+    calls = [
+        ("keypoints", True, lambda: tp.compute_iss_keypoints_batch(clouds, return_saliency=True)),
+        ("radius", False, lambda: tp.remove_radius_outlier_batch(clouds, 3, 0.2, return_counts=True)),
+        ("normals", True, lambda: tp.estimate_normals_batch(clouds, KNN(10), covariances=True, eigenvalues=True)),
+        ("self_knn", True, lambda: tp.self_knn_batch(clouds, 7, return_distance=True)),
+        ("statistical", True, lambda: tp.remove_statistical_outlier_batch(clouds, 8, 1.5, return_stats=True)),
+        ("covariances", False, lambda: tp.estimate_covariances_batch(clouds, 0.3, 20)),
+        ("icp_auto", True, lambda: tp.registration_icp_batch(srcs, clouds, 0.3, criteria=crit, estimation_methods=ests,
+                                                             target_normals=searches)),
+    ]  # (name, whether the call reports "knn_fallbacks", the call)
+
+    def run(fn):
+        return blob(fn()), tp.get_icp_option("knn_fallbacks")
+
+    fresh = {}
+    for name, reports, fn in calls:
+        tp.icp._cache.release()  # the next call opens a new handle
+        fresh[name] = run(fn)
+        assert reports or fresh[name][1] == 0, name
+    assert fresh["self_knn"][1] >= 1 and fresh["statistical"][1] >= 1
+    tp.icp._cache.release()
+    last = 0  # "knn_fallbacks" of the last call on this handle that reports it
+    for name, reports, fn in calls + calls[::-1]:
+        got = run(fn)
+        want = fresh[name][1] if reports else last
+        assert got[1] == want, "%s: knn_fallbacks %d, expected %d" % (name, got[1], want)
+        assert got[0] == fresh[name][0], name
+        last = got[1]
