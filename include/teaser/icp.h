@@ -34,6 +34,18 @@ struct Matrix4 {  // column-major 4 x 4, like Eigen::Matrix4d
 };
 #endif
 
+// The 6 x 6 information matrix of a registered pair (rotation block first, like Open3D's 6-vectors).
+#if TEASER_HIP_HAVE_EIGEN
+using Matrix6 = Eigen::Matrix<double, 6, 6>;
+#else
+struct Matrix6 {  // column-major 6 x 6, like Eigen::Matrix<double, 6, 6>; zero-initialised
+  std::array<double, 36> v{};
+  static Matrix6 Zero() { return Matrix6(); }
+  double& operator()(int r, int c) { return v[(size_t)(6 * c + r)]; }
+  double operator()(int r, int c) const { return v[(size_t)(6 * c + r)]; }
+};
+#endif
+
 // Open3D's ICPConvergenceCriteria (the stop rule compares ABSOLUTE changes of fitness and inlier RMSE).
 struct ICPConvergenceCriteria {
   double relative_fitness = 1e-6;
@@ -300,6 +312,67 @@ class ICP {
     return std::move(estimateNormalsBatch({cloud}, {search}, covariances, eigenvalues)[0]);
   }
 
+  // Open3D's evaluate_registration for many pairs in one launch sequence: the correspondences, fitness and inlier RMSE
+  // of the given poses (registrationICPBatch with max_iteration = 0).
+  std::vector<ICPResult> evaluateRegistrationBatch(const std::vector<Matrix3X>& src, const std::vector<Matrix3X>& dst,
+                                                   const std::vector<double>& max_correspondence_distance,
+                                                   const std::vector<Matrix4>& transformation) {
+    ICPConvergenceCriteria none;
+    none.max_iteration = 0;
+    return run(src, dst, max_correspondence_distance, transformation,
+               std::vector<ICPConvergenceCriteria>(src.size(), none), nullptr, nullptr);
+  }
+
+  ICPResult evaluateRegistration(const Matrix3X& src, const Matrix3X& dst, double max_correspondence_distance,
+                                 const Matrix4& transformation = Matrix4::Identity()) {
+    return evaluateRegistrationBatch({src}, {dst}, {max_correspondence_distance}, {transformation})[0];
+  }
+
+  // The information matrices of many registered pairs in one launch sequence (include/teaser_hip.h, "Information
+  // matrices"; Open3D's GetInformationMatrixFromPointClouds); matrix b is identical to pair b evaluated alone.
+  // evaluation: NULL, or receives what evaluateRegistrationBatch returns for the same arguments.
+  std::vector<Matrix6> getInformationMatrixFromPointCloudsBatch(const std::vector<Matrix3X>& src,
+                                                                const std::vector<Matrix3X>& dst,
+                                                                const std::vector<double>& max_correspondence_distance,
+                                                                const std::vector<Matrix4>& transformation,
+                                                                std::vector<ICPResult>* evaluation = nullptr) {
+    const size_t b = src.size();
+    if (dst.size() != b || max_correspondence_distance.size() != b || transformation.size() != b)
+      throw std::invalid_argument("teaser::ICP: one entry per problem in every argument");
+    std::vector<const double*> ps(b), pd(b);
+    std::vector<int32_t> ns(b), nd(b);
+    std::vector<double> T(16 * b), info(36 * b);
+    std::vector<std::vector<int32_t>> corr(b);
+    std::vector<int32_t*> pc(b);
+    for (size_t k = 0; k < b; ++k) {
+      ps[k] = src[k].data();
+      pd[k] = dst[k].data();
+      ns[k] = (int32_t)src[k].cols();
+      nd[k] = (int32_t)dst[k].cols();
+      for (int r = 0; r < 4; ++r)
+        for (int c = 0; c < 4; ++c) T[16 * k + (size_t)(4 * r + c)] = transformation[k](r, c);
+      if (evaluation) corr[k].resize(2 * (size_t)(ns[k] > 0 ? ns[k] : 1));
+      pc[k] = evaluation ? corr[k].data() : nullptr;
+    }
+    std::vector<teaser_icp_result_c> out(b);
+    const int32_t rc = teaser_hip_icp_information_batch(h_, (int32_t)b, ps.data(), ns.data(), pd.data(), nd.data(),
+                                                        T.data(), max_correspondence_distance.data(), info.data(),
+                                                        evaluation ? out.data() : nullptr, evaluation ? pc.data() : nullptr);
+    if (rc != TEASER_HIP_OK)
+      throw ICPError(rc, "teaser::ICP: status " + std::to_string(rc) + ": " + teaser_hip_icp_last_error(h_));
+    std::vector<Matrix6> res(b);
+    for (size_t k = 0; k < b; ++k)
+      for (int r = 0; r < 6; ++r)
+        for (int c = 0; c < 6; ++c) res[k](r, c) = info[36 * k + (size_t)(6 * r + c)];
+    if (evaluation) *evaluation = unpack(out, corr);
+    return res;
+  }
+
+  Matrix6 getInformationMatrixFromPointClouds(const Matrix3X& src, const Matrix3X& dst,
+                                              double max_correspondence_distance, const Matrix4& transformation) {
+    return getInformationMatrixFromPointCloudsBatch({src}, {dst}, {max_correspondence_distance}, {transformation})[0];
+  }
+
   ICPResult registrationICP(const Matrix3X& src, const Matrix3X& dst, double max_correspondence_distance,
                             const Matrix4& init, const TransformationEstimationPointToPlane& estimation,
                             const ICPConvergenceCriteria& criteria = ICPConvergenceCriteria()) {
@@ -372,6 +445,13 @@ class ICP {
                                    params.data(), out.data(), pc.data());
     if (rc != TEASER_HIP_OK)
       throw ICPError(rc, "teaser::ICP: status " + std::to_string(rc) + ": " + teaser_hip_icp_last_error(h_));
+    return unpack(out, corr);
+  }
+
+  // The records and correspondence buffers of a call as results.
+  static std::vector<ICPResult> unpack(const std::vector<teaser_icp_result_c>& out,
+                                       const std::vector<std::vector<int32_t>>& corr) {
+    const size_t b = out.size();
     std::vector<ICPResult> res(b);
     for (size_t k = 0; k < b; ++k) {
       for (int r = 0; r < 4; ++r)
@@ -432,6 +512,20 @@ inline ICPResult registrationICP(const Matrix3X& src, const Matrix3X& dst, doubl
                                  const ICPConvergenceCriteria& criteria = ICPConvergenceCriteria()) {
   ICP icp;
   return icp.registrationICP(src, dst, max_correspondence_distance, init, estimation, criteria);
+}
+
+// Open3D's evaluate_registration, one pair; creates a handle per call.
+inline ICPResult evaluateRegistration(const Matrix3X& src, const Matrix3X& dst, double max_correspondence_distance,
+                                      const Matrix4& transformation = Matrix4::Identity()) {
+  ICP icp;
+  return icp.evaluateRegistration(src, dst, max_correspondence_distance, transformation);
+}
+
+// Open3D's GetInformationMatrixFromPointClouds, one pair; creates a handle per call.
+inline Matrix6 getInformationMatrixFromPointClouds(const Matrix3X& src, const Matrix3X& dst,
+                                                   double max_correspondence_distance, const Matrix4& transformation) {
+  ICP icp;
+  return icp.getInformationMatrixFromPointClouds(src, dst, max_correspondence_distance, transformation);
 }
 
 // Covariances of one cloud for Generalized ICP, estimated on the GPU; creates a handle per call.

@@ -831,6 +831,45 @@ TEASER_HIP_API int32_t teaser_hip_icp_iss_keypoints_batch(teaser_hip_icp* icp, i
 TEASER_HIP_API int32_t teaser_hip_icp_set_option(teaser_hip_icp* icp, const char* name, int64_t value);
 TEASER_HIP_API int32_t teaser_hip_icp_get_option(teaser_hip_icp* icp, const char* name, int64_t* value);
 
+/* Information matrices (Open3D's GetInformationMatrixFromPointClouds, the 6 x 6 weight a registered pair enters a
+ * pose graph with, and evaluate_registration, whose result the same call returns): batched, on the ICP handle, from the
+ * correspondences of a GIVEN pose.  Open3D's formulation was restated (tests/information_reference.py), not run.
+ * Per problem: source P (n_s points), target Q (n_t points), T = transformation (4 x 4 row-major, last row 0 0 0 1),
+ * r = max_correspondence_distance.  With apply and corr exactly as "ICP refinement" above defines them:
+ *   X = apply(T, P);  C = corr(X)          -- the bits of teaser_hip_icp_batch with max_iteration = 0 and init = T:
+ *                                             the same correspondence set, fitness, inlier_rmse and n_correspondences
+ *   for every (i, j) of C, q = Q[j] in the caller's own coordinates (NOT centred: a pose graph takes its residual
+ *   about the origin too):
+ *     G_j = [ -[q]x | I3 ]   rows (0, q_z, -q_y, 1, 0, 0), (-q_z, 0, q_x, 0, 1, 0), (q_y, -q_x, 0, 0, 0, 1)
+ *     information = SUM_j G_j^T G_j         (rotation block first: the order of Open3D's 6-vectors)
+ *   so information[3:,3:] = |C| I3 and information(5,5) = |C| exactly, and an empty C (n_s = 0, n_t = 0, or no point
+ *   within r) gives the zero matrix.  Per term nothing is fused: (0,0) = q_z q_z + q_y q_y, (0,1) = 0 - q_y q_x,
+ *   (0,2) = 0 - q_z q_x, (1,1) = q_z q_z + q_x q_x, (1,2) = 0 - q_z q_y, (2,2) = q_y q_y + q_x q_x; the off-diagonal
+ *   block holds the coordinates themselves.
+ *   SUM: 21 FP64 sums (the upper triangle; the lower one is its mirror image, bit for bit).  The source points are cut
+ *   into blocks of 256 consecutive indices (a point without a match adds 0); inside a block lane l of each 64-lane
+ *   wave adds across lanes by xor 32, 16, 8, 4, 2, 1, then (w0 + w1) + (w2 + w3) over its four waves; the block
+ *   results b = t, t + 256, ... are added in ascending order by thread t of a 256-thread block, which is then summed by
+ *   the same rule.  No atomics: the same bits run to run, and for a problem alone or inside any batch.  With inputs
+ *   for which every product and sum is exact (integer coordinates of moderate size) the result is THE sum, whatever
+ *   the order.  In general |information - exact| <= (|C| + 3) 2^-52 SUM_j |term_j| elementwise.
+ * transformation: batch x 16; max_correspondence_distance: [batch]; information: batch x 36 row-major; out: NULL, or
+ * [batch] records (transformation echoed, iterations 0); corr: NULL, or as in teaser_hip_icp_batch.  Problems of mixed
+ * sizes share the launches; one synchronisation per call.  TEASER_HIP_ERR_BAD_ARG (argument and problem named): a
+ * non-finite transformation or one whose last row is not 0 0 0 1, a non-finite or non-positive r (or r r), non-finite
+ * points, NULL where n > 0, a NULL transformation / max_correspondence_distance / information.  n = 0 is valid. */
+TEASER_HIP_API int32_t teaser_hip_icp_information_batch(teaser_hip_icp* icp, int32_t batch, const double* const* src,
+                                                        const int32_t* n_src, const double* const* dst,
+                                                        const int32_t* n_dst, const double* transformation,
+                                                        const double* max_correspondence_distance,
+                                                        double* information, teaser_icp_result_c* out,
+                                                        int32_t* const* corr);
+/* One problem: teaser_hip_icp_information_batch with batch = 1.  out may be NULL; corr NULL or room for n_src x 2. */
+TEASER_HIP_API int32_t teaser_hip_icp_information(teaser_hip_icp* icp, const double* src, int32_t n_src,
+                                                  const double* dst, int32_t n_dst, const double* transformation,
+                                                  double max_correspondence_distance, double* information,
+                                                  teaser_icp_result_c* out, int32_t* corr);
+
 /* Voxel down-sampling (the reference's 3DMatch tutorial, examples/teaser_python_fpfh_icp/example.py:19-20, runs
  * Open3D's pcd.voxel_down_sample(0.05) on the raw clouds): batched, with Open3D's arithmetic and a deterministic output
  * order, on its OWN handle (nothing is shared with teaser_hip_solver or teaser_hip_icp).

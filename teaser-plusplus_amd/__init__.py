@@ -138,6 +138,7 @@ EXPORTED_SYMBOLS = [
     "teaser_hip_icp_self_knn_batch", "teaser_hip_icp_remove_statistical_outliers_batch",
     "teaser_hip_icp_remove_radius_outliers_batch", "teaser_hip_icp_set_option", "teaser_hip_icp_get_option",
     "teaser_hip_icp_iss_params_default", "teaser_hip_icp_iss_keypoints_batch",
+    "teaser_hip_icp_information_batch", "teaser_hip_icp_information",
     "teaser_hip_voxel_create", "teaser_hip_voxel_destroy", "teaser_hip_voxel_last_error",
     "teaser_hip_voxel_down_sample_batch", "teaser_hip_voxel_down_sample",
     "teaser_hip_features_create", "teaser_hip_features_destroy", "teaser_hip_features_last_error",
@@ -1085,7 +1086,8 @@ from .icp import (CauchyLoss, GMLoss, HuberLoss, ICPConvergenceCriteria, L2Loss,
                   registration_icp, registration_icp_batch, TransformationEstimationForGeneralizedICP,
                   covariances_from_normals, estimate_covariances, estimate_covariances_batch,
                   registration_generalized_icp, KDTreeSearchParamHybrid, KDTreeSearchParamKNN, estimate_normals,
-                  estimate_normals_batch, surface_variation)
+                  estimate_normals_batch, surface_variation, evaluate_registration, evaluate_registration_batch,
+                  get_information_matrix_from_point_clouds, get_information_matrix_from_point_clouds_batch)
 from .voxel import voxel_down_sample, voxel_down_sample_batch  # noqa: E402
 from .outlier import (remove_radius_outlier, remove_radius_outlier_batch, remove_statistical_outlier,  # noqa: E402
                       remove_statistical_outlier_batch, self_knn, self_knn_batch, get_icp_option, set_icp_option)
@@ -1106,6 +1108,8 @@ __all__ = ["batched", "FPFHEstimation", "Matcher", "MultiDeviceSolver", "RobustR
            "TransformationEstimationForGeneralizedICP", "registration_generalized_icp", "estimate_covariances",
            "estimate_covariances_batch", "covariances_from_normals", "KDTreeSearchParamHybrid", "KDTreeSearchParamKNN",
            "estimate_normals", "estimate_normals_batch", "surface_variation",
+           "evaluate_registration", "evaluate_registration_batch", "get_information_matrix_from_point_clouds",
+           "get_information_matrix_from_point_clouds_batch",
            "remove_statistical_outlier", "remove_statistical_outlier_batch", "remove_radius_outlier",
            "remove_radius_outlier_batch", "self_knn", "self_knn_batch", "get_icp_option", "set_icp_option",
            "compute_iss_keypoints", "compute_iss_keypoints_batch"]

@@ -10,6 +10,7 @@ namespace thip {
 constexpr int kIcpBlock = 256;   // source points per correspondence block (the chunking depends on n_s alone)
 constexpr int kIcpSums = 17;     // {count, sum d2, sum p' (3), sum q' (3), sum p' q'^T (9)} of one block
 constexpr int kIcpPlaneSums = 29;  // point-to-plane: {count, sum d2, upper triangle of A by rows (21), g (6)}
+constexpr int kIcpInfoSums = 21;   // information matrix: the upper triangle of the 6 x 6 by rows
 constexpr int kIcpScanThreads = 1024;
 constexpr int kIcpCovBlock = 64;   // points per covariance block: one wave, one point per lane
 constexpr int kIcpCovMaxNN = 100;  // K of the contract: the largest max_nn of covariance estimation
@@ -141,6 +142,11 @@ void launch_icp_statistical(hipStream_t s, const IcpDesc* d_desc, const IcpKnnDe
 void launch_icp_radius_count(hipStream_t s, const IcpDesc* d_desc, const IcpKnnDesc* d_knn,
                              const int32_t* d_tblk_prob, int n_tblk, const double* d_q, const double* d_qs,
                              const int32_t* d_bstart, int32_t* d_count, uint8_t* d_keep, int32_t* d_kept);
+// The information matrices of the problems whose matches (d_match, written by the mode-0 correspondence pass over the
+// same block map) and targets as given (d_q) are on the device: d_partials takes kIcpInfoSums doubles per block,
+// d_info 36 per problem (row-major 6 x 6).  kernels_icp_information.hip.
+void launch_icp_information(hipStream_t s, const IcpDesc* d_desc, const int32_t* d_blk_prob, int n_blk, int batch,
+                            const double* d_q, const int32_t* d_match, double* d_partials, double* d_info);
 void launch_icp_live(hipStream_t s, const IcpState* d_state, int batch, int32_t* d_live);
 
 }  // namespace thip

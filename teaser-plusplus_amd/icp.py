@@ -62,6 +62,10 @@ def declare(L):
                                                C.POINTER(_dp), C.POINTER(_dp), C.POINTER(_dp)]
     L.teaser_hip_icp_batch_auto.argtypes = L.teaser_hip_icp_batch_cov.argtypes + [C.POINTER(IcpNormalSearchC)]
     L.teaser_hip_icp_solve_auto.argtypes = L.teaser_hip_icp_solve_cov.argtypes + [C.POINTER(IcpNormalSearchC)]
+    L.teaser_hip_icp_information_batch.argtypes = [_vp, C.c_int32, C.POINTER(_dp), _ip, C.POINTER(_dp), _ip, _dp, _dp,
+                                                   _dp, C.POINTER(IcpResultC), C.POINTER(_ip)]
+    L.teaser_hip_icp_information.argtypes = [_vp, _dp, C.c_int32, _dp, C.c_int32, _dp, C.c_double, _dp,
+                                             C.POINTER(IcpResultC), _ip]
 
 
 class ICPConvergenceCriteria:
@@ -404,6 +408,67 @@ def registration_icp(source, target, max_correspondence_distance, init=np.eye(4)
                                   target_normals=None if target_normals is None else [target_normals],
                                   source_covariances=None if source_covariances is None else [source_covariances],
                                   target_covariances=None if target_covariances is None else [target_covariances])[0]
+
+
+def evaluate_registration_batch(sources, targets, max_correspondence_distance, transformations=None, device=-1):
+    """Open3D's evaluate_registration for many pairs in one launch sequence: the correspondences, fitness and inlier
+    RMSE of the given poses, nothing refined (registration_icp_batch with max_iteration = 0).  transformations: None
+    (identity), one 4 x 4 for all or one per pair.  Returns a list of RegistrationResult."""
+    return registration_icp_batch(sources, targets, max_correspondence_distance, inits=transformations,
+                                  criteria=ICPConvergenceCriteria(max_iteration=0), device=device)
+
+
+def evaluate_registration(source, target, max_correspondence_distance, transformation=np.eye(4), device=-1):
+    """Open3D's evaluate_registration (same argument order): how well `transformation` maps source onto target."""
+    return evaluate_registration_batch([source], [target], max_correspondence_distance, _init(transformation)[None],
+                                       device)[0]
+
+
+def get_information_matrix_from_point_clouds_batch(sources, targets, max_correspondence_distance, transformations,
+                                                   device=-1, return_results=False):
+    """The 6 x 6 information matrices of many registered pairs in one launch sequence (include/teaser_hip.h,
+    "Information matrices"; Open3D's get_information_matrix_from_point_clouds): per pair SUM G^T G over the
+    correspondences of `transformation` within max_correspondence_distance, G = [-[q]x | I] at the matched target
+    point q, so entry (5, 5) is the number of correspondences.  max_correspondence_distance: one value for all or one
+    per pair; transformations: one 4 x 4 for all or one per pair.  Returns a b x 6 x 6 array, each matrix identical to
+    the same pair evaluated alone; with return_results=True also the list of RegistrationResult that
+    evaluate_registration_batch gives for the same arguments."""
+    from . import lib
+    srcs = [_points(s, "source") for s in sources]
+    dsts = [_points(t, "target") for t in targets]
+    b = len(srcs)
+    if len(dsts) != b:
+        raise ValueError("sources and targets differ in length (%d vs %d)" % (b, len(dsts)))
+    rs = np.ascontiguousarray(np.broadcast_to(np.asarray(max_correspondence_distance, dtype=np.float64), (b,)))
+    a = np.asarray(transformations, dtype=np.float64)
+    T = np.ascontiguousarray(np.broadcast_to(a, (b, 4, 4)) if a.shape == (4, 4) else a.reshape(-1, 4, 4) if b == 0 else a)
+    if T.shape != (b, 4, 4):
+        raise ValueError("transformations: one 4 x 4 for all pairs or b x 4 x 4")
+    info = np.zeros((b, 6, 6))
+    out = (IcpResultC * max(b, 1))()
+    corr = [np.zeros((max(len(s), 1), 2), dtype=np.int32) for s in srcs] if return_results else None
+    if b:
+        n_s = np.array([len(s) for s in srcs], dtype=np.int32)
+        n_t = np.array([len(t) for t in dsts], dtype=np.int32)
+        sp = (_dp * b)(*[s.ctypes.data_as(_dp) for s in srcs])
+        tp = (_dp * b)(*[t.ctypes.data_as(_dp) for t in dsts])
+        cp = None if corr is None else (_ip * b)(*[c.ctypes.data_as(_ip) for c in corr])
+        _handle(device).call(lib().teaser_hip_icp_information_batch, b, sp, n_s.ctypes.data_as(_ip), tp,
+                             n_t.ctypes.data_as(_ip), T.ctypes.data_as(_dp), rs.ctypes.data_as(_dp),
+                             info.ctypes.data_as(_dp), out, cp)
+    if not return_results:
+        return info
+    res = [RegistrationResult(np.array(out[k].transformation[:], dtype=np.float64).reshape(4, 4),
+                              float(out[k].fitness), float(out[k].inlier_rmse),
+                              corr[k][:out[k].n_correspondences].copy(), int(out[k].iterations)) for k in range(b)]
+    return info, res
+
+
+def get_information_matrix_from_point_clouds(source, target, max_correspondence_distance, transformation, device=-1):
+    """Open3D's get_information_matrix_from_point_clouds (same argument order): the 6 x 6 information matrix of one
+    registered pair."""
+    return get_information_matrix_from_point_clouds_batch([source], [target], max_correspondence_distance,
+                                                          _init(transformation)[None], device)[0]
 
 
 def covariances_from_normals(normals, epsilon=1e-3):
