@@ -1,6 +1,8 @@
-// host_common.h -- what the host sides of the auxiliary handles (icp.hip, voxel.hip, features.hip) share: the
-// grow-only buffers, the members and the error reporting every handle has, and the create / destroy sequences.
-// solver.hip keeps its own DevBuf / PinnedBuf: they grow by another rule, return hipError_t and have a view mode.
+// host_common.h -- what the host sides of the handles share: the members and the error reporting every handle has
+// (HandleBase), the create sequence (open_handle) and, for the auxiliary handles (icp.hip, voxel.hip, features.hip), the
+// grow-only buffers and the destroy sequence.  solver.hip derives its handle from HandleBase and opens it with
+// open_handle, but keeps buffer types of its own under other names (SolverBuf, PinnedBuf: another growth rule, a
+// hipError_t answer with a retry at the exact size, and a view mode) and its own teardown (lanes, finisher threads).
 #pragma once
 
 #include <hip/hip_runtime.h>

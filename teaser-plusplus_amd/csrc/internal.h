@@ -17,6 +17,7 @@ namespace thip {
 constexpr int kWave = 64;          // CDNA4 wavefront
 constexpr int kMaxStarts = 16;     // greedy start vertices per problem
 constexpr int kPeelRounds = 3;     // k-core style peel launches before the host decision
+constexpr int kSmallCap = 768;     // largest graph the all-starts greedy serves (launch_greedy_small: the adjacency in LDS)
 
 // One registration problem inside a (possibly ragged) batch.  Packed layouts in HBM:
 //   points   : src/dst  [sum n][3] doubles        (offset pt_off points)
@@ -177,7 +178,7 @@ void launch_heuristic(hipStream_t s, const ProbDesc* d_desc, int batch, int max_
                       int32_t* d_trace /* diagnostics or null */, int32_t* d_clique /* [sum n] */,
                       int nblk = 0 /* workgroups per problem = ProbState.next_start of the batch; 0: the built-in count */,
                       int rows = 0 /* grid rows: 0 = one per problem; fewer = shared by the problems the degree closure left open */);
-// all-starts greedy for small graphs (n <= 1024), between the 16-start greedy and the selection: returns the slots per
+// all-starts greedy for small graphs (n <= kSmallCap), between the 16-start greedy and the selection: returns the slots per
 // problem to hand to launch_select_best (0: nothing launched).  d_best_seen: batch ints, zero on entry
 int64_t greedy_small_scratch_bytes(int batch);
 int launch_greedy_small(hipStream_t s, const ProbDesc* d_desc, int batch, int max_small_n, const uint64_t* d_bitmap,
@@ -301,7 +302,16 @@ void launch_estimate_fused(hipStream_t s, const ProbDesc* d_desc, int batch, con
                            const int32_t* d_clique, ProbState* d_state, EstParams ep, double* d_weights,
                            int32_t* d_rot_inliers, const int64_t* d_tim_off, char* d_tls_scratch, int64_t tls_stride,
                            int32_t* d_trans_inliers, void* host_states /* page-locked mirror, or null */);
-// generic scalar TLS on device arrays (one workgroup)
+// generic scalar TLS on device arrays (one workgroup): a bitonic sort of the 2 n interval endpoints, padded to a power
+// of two, as (double key, int32 tag) records
+constexpr int64_t kScalarTlsSingleMax = (int64_t)1 << 18;  // measurements one workgroup sorts; above: launch_scalar_tls_large
+inline int64_t tls_endpoint_slots(int64_t n) {
+  int64_t P2 = 2;
+  while (P2 < 2 * n) P2 <<= 1;
+  return P2;
+}
+inline int64_t tls_endpoint_bytes(int64_t n) { return tls_endpoint_slots(n) * 12; }
+int64_t scalar_tls_small_workspace_bytes(int64_t n);  // d_scratch (kernels_scale.hip)
 void launch_scalar_tls(hipStream_t s, const double* d_x, const double* d_r, int32_t n,
                        char* d_scratch, double* d_est, uint8_t* d_mask);
 

@@ -1378,7 +1378,6 @@ __global__ __launch_bounds__(kGreedyThreads) void greedy_clique_kernel(
 // not depend on the order in which the waves finish.  Every workgroup leaves its best (size, start, members) in its own
 // slot; select_best_kernel takes the best slot when it beats the 16 starts (and only then: equal size keeps them).
 // ------------------------------------------------------------------------------------------
-constexpr int kSmallCap = 768;
 constexpr int kSmallMaxW = kSmallCap / 64;
 constexpr int kSmallSlotWords = 2 + kSmallMaxW;  // 64-bit words: key (size << 32 | ~start), spare, the clique as a bit set
 

@@ -1177,6 +1177,9 @@ static size_t sort_temp_bytes(int64_t m) {
 // 64-bit sort for everything (setting scale_sort64: the A/B test of the two sort routes)
 static bool force_sort64() { return setting(S_SCALE_SORT64) != 0; }
 
+// the single-workgroup route (launch_scalar_tls): its endpoint records and 64 bytes of slack
+int64_t scalar_tls_small_workspace_bytes(int64_t n) { return tls_endpoint_bytes(n) + 64; }
+
 int64_t scalar_tls_large_workspace_bytes(int64_t n) {
   const int64_t m = 2 * n;
   const int64_t nblk = (m + kSwChunk - 1) / kSwChunk;

@@ -12,12 +12,14 @@
 #include <atomic>
 #include <chrono>
 #include <condition_variable>
+#include <deque>
 #include <memory>
 #include <mutex>
 #include <string>
 #include <thread>
 #include <vector>
 
+#include "host_common.h"
 #include "internal.h"
 
 namespace thip {
@@ -207,26 +209,26 @@ void warn_hw_queues_once(int lanes) {
                     "queue (export GPU_MAX_HW_QUEUES=8 before the first HIP call)\n", q, lanes);
 }
 
-struct DevBuf {
+// The solver's device buffer.  Unlike host_common.h's DevBuf it can be a VIEW into another buffer (the per-solve
+// header block), answers with the hipError_t (HIPCHK tells out-of-memory from the rest), and an allocation with
+// headroom that fails is tried again at the exact size.  It frees what it owns when it dies; a view never frees.
+struct SolverBuf {
   void* p = nullptr;
   size_t cap = 0;
-  bool view = false;  // p points into another DevBuf (the per-solve header block): never freed here
+  bool view = false;  // p points into another SolverBuf: never freed here
+  SolverBuf() = default;
+  SolverBuf(const SolverBuf&) = delete;
+  SolverBuf& operator=(const SolverBuf&) = delete;
+  ~SolverBuf() { release(); }
   void set_view(void* q, size_t bytes) {
-    if (p && !view) (void)hipFree(p);
+    release();
     p = q;
     cap = bytes;
     view = true;
   }
   hipError_t ensure(size_t bytes) {
     if (bytes <= cap && !view) return hipSuccess;
-    if (view) {
-      p = nullptr;
-      cap = 0;
-      view = false;
-    }
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    cap = 0;
+    release();
     size_t want = bytes + bytes / 4 + 256;
     hipError_t e = hipMalloc(&p, want);
     if (e != hipSuccess) {
@@ -253,11 +255,13 @@ struct DevBuf {
 struct PinnedBuf {
   void* p = nullptr;
   size_t cap = 0;
+  PinnedBuf() = default;
+  PinnedBuf(const PinnedBuf&) = delete;
+  PinnedBuf& operator=(const PinnedBuf&) = delete;
+  ~PinnedBuf() { release(); }
   hipError_t ensure(size_t bytes) {
     if (bytes <= cap) return hipSuccess;
-    if (p) (void)hipHostFree(p);
-    p = nullptr;
-    cap = 0;
+    release();
     const size_t want = bytes + bytes / 2 + 256;
     hipError_t e = hipHostMalloc(&p, want, hipHostMallocDefault);
     if (e == hipSuccess) cap = want;
@@ -289,12 +293,9 @@ struct LaneFinisher {
   int32_t rc = TEASER_HIP_OK;
 };
 
-struct teaser_hip_solver {
+struct teaser_hip_solver : HandleBase {
   teaser_params_c params;        // what the solve paths read (reference_snapshot_semantics applied)
   teaser_params_c params_given;  // what the caller passed (teaser_hip_solver_get_params)
-  int device = 0;
-  hipStream_t stream = nullptr;
-  std::string err;
   int profiling = 0;  // 0 off, 1 every stage, 2 K1 only (the kernel, and its pre-pass / fix-up)
   teaser_profile_c prof;
   std::vector<hipEvent_t> ev_pool;
@@ -316,16 +317,16 @@ struct teaser_hip_solver {
   const double* cur_dst = nullptr;
   bool have_graph = false;
 
-  DevBuf d_desc, d_state, d_src, d_dst, d_bitmap, d_deg, d_clique, d_start_cliques, d_alive_a,
+  SolverBuf d_desc, d_state, d_src, d_dst, d_bitmap, d_deg, d_clique, d_start_cliques, d_alive_a,
       d_alive_b, d_next_count, d_weights, d_rot_inl, d_trans_inl, d_tls_scratch, d_tim_off,
       d_pk, d_prep, d_work, d_core, d_small;
   // colouring bound
-  DevBuf c_sel, c_colour, c_tent, c_xlist, c_list_a, c_list_b, c_counts, c_bits, c_class, c_mis;
+  SolverBuf c_sel, c_colour, c_tent, c_xlist, c_list_a, c_list_b, c_counts, c_bits, c_class, c_mis;
   std::vector<int32_t> colour_x;  // |X| per problem of the last solve (-1: stage not run)
   // exact stage
-  DevBuf x_order, x_src, x_dst, x_bitmap, x_desc, x_state, x_ctrl, x_clique, x_arena, x_probs, x_probs2, x_keys, x_xbits, x_tasks;
+  SolverBuf x_order, x_src, x_dst, x_bitmap, x_ctrl, x_clique, x_arena, x_probs, x_probs2, x_keys, x_xbits, x_tasks;
   // stand-alone stages
-  DevBuf s_a, s_b, s_c, s_d, s_e;
+  SolverBuf s_a, s_b, s_c, s_d, s_e;
   // correspondence front-end (FPFH, matcher): the batched front-end's handle, created by the first call that needs
   // it (front_end); a lane never has one
   teaser_hip_features* features = nullptr;
@@ -402,7 +403,7 @@ struct teaser_hip_solver {
     int in_set = -1;                       // parent's input set holding the (host-submitted) points, or -1
     int32_t ticket = -1;
   } job;
-  DevBuf hdr;                              // descs | states | tim offsets | peel counters | K1 prep
+  SolverBuf hdr;                           // descs | states | tim offsets | peel counters | K1 prep
   // ---- host inputs of asynchronous batches (parent only) ------------------------------------------
   // TEASER_HIP_INPUT_HOST batches are copied on a dedicated copy stream (SDMA: 56 GB/s on MI355X,
   // unaffected by the kernels in flight -- profiles/r3a) into one of depth + 1 input sets owned by the
@@ -411,11 +412,14 @@ struct teaser_hip_solver {
   // submit / wait call.  With the copy inside a lane's own stream the lane's serial chain
   // tail(k) -> H2D(k+2) -> pre-pass -> K1(k+2) was longer than two K1 periods (2.04 vs 1.55 ms per step).
   struct InSet {
-    DevBuf src, dst;
+    SolverBuf src, dst;
     hipEvent_t ready = nullptr;
     bool in_use = false;
+    ~InSet() {
+      if (ready) (void)hipEventDestroy(ready);
+    }
   };
-  std::vector<InSet> in_sets;
+  std::deque<InSet> in_sets;  // (a deque: an InSet neither copies nor moves)
   hipStream_t copy_stream = nullptr;
   struct Staged {
     bool active = false;
@@ -547,22 +551,21 @@ EstParams est_params(const teaser_params_c& p) {
 
 int64_t tls_scratch_bytes(int n) {
   const int64_t Kp = (n + 1) & ~1;
-  int64_t P2 = 2;
-  while (P2 < 2 * (int64_t)n) P2 <<= 1;
-  return 3 * Kp * 8 + 3 * Kp + 16 + 3 * (P2 * 12 + 16) + 64;
+  return 3 * Kp * 8 + 3 * Kp + 16 + 3 * (tls_endpoint_bytes(n) + 16) + 64;
 }
 
 // --------------------------------------------------------------------------------------------
 // estimate_scaling = true: TRIMs + scalar TLS over all M pairs (registration.cc:410-425)
 // --------------------------------------------------------------------------------------------
-// Up to kSmallScaledN points the M <= 2^18 TRIMs are sorted by ONE workgroup (lowest latency; every
+// Up to kSmallScaledN points the M <= kScalarTlsSingleMax TRIMs are sorted by ONE workgroup (lowest latency; every
 // reference fixture is in this range); above, kernels_scale.hip: fused TRIM/endpoint kernel ->
 // device radix sort -> three-pass sweep.  The reference's `int nr_centers = 2*N`
 // (registration.cc:47) overflows for M > 2^30, i.e. n > 46341: refused here rather than undefined.
-constexpr int kSmallScaledN = 724;  // capability of the single-workgroup sort (2^19 endpoints)
+constexpr int kSmallScaledN = 724;  // capability of the single-workgroup sort: M <= kScalarTlsSingleMax
 // ... but one workgroup sorting M log^2 M takes 8.6 ms at n = 200 and 137 ms at n = 724 (profiles/r2j), against
 // ~0.22 ms of launch-bound kernels on the radix-sort path: a problem on its own takes the single-workgroup path
 // only while that is the faster one; batches weigh the two (scale_stage_batch).
+static_assert((int64_t)kSmallScaledN * (kSmallScaledN - 1) / 2 <= kScalarTlsSingleMax, "one workgroup sorts the TRIMs");
 constexpr int kSingleSmallN = 64;
 constexpr double kLargePathMs = 0.22;  // measured: 64 x n = 724 in 13.7 ms (profiles/r2j)
 constexpr int kMaxScaledN = 46341;
@@ -571,13 +574,8 @@ constexpr int64_t kMidChunkTrims = (int64_t)1 << 27;    // TRIMs per shared sort
 
 // measured model of the single-workgroup path: bitonic sort of P2 >= 2 M endpoints, L (L + 1) / 2 passes
 static double small_path_ms(int n) {
-  const int64_t M = (int64_t)n * (n - 1) / 2;
-  int64_t P2 = 2;
-  int L = 1;
-  while (P2 < 2 * M) {
-    P2 <<= 1;
-    ++L;
-  }
+  const int64_t P2 = tls_endpoint_slots((int64_t)n * (n - 1) / 2);
+  const int L = __builtin_ctzll((unsigned long long)P2);
   return 8.6 * ((double)P2 * L * (L + 1) / 2) / (65536.0 * 136.0) + 0.05;
 }
 
@@ -602,9 +600,7 @@ int32_t scale_stage(teaser_hip_solver* h, int p, bool sort64) {
                                      d_scale, sort64 ? nullptr : &(h->d_state.as<ProbState>()[p].scale_overflow)));
     return TEASER_HIP_OK;
   }
-  int64_t P2 = 2;
-  while (P2 < 2 * M) P2 <<= 1;
-  HIPCHK(h, h->s_c.ensure((size_t)P2 * 12 + 64));
+  HIPCHK(h, h->s_c.ensure((size_t)scalar_tls_small_workspace_bytes(M)));
   launch_trims(s, h->cur_src + 3 * d.pt_off, h->cur_dst + 3 * d.pt_off, n, beta,
                h->s_a.as<double>(), h->s_b.as<double>());
   launch_scalar_tls(s, h->s_a.as<double>(), h->s_b.as<double>(), (int32_t)M, h->s_c.as<char>(),
@@ -646,9 +642,7 @@ int32_t scale_stage_batch(teaser_hip_solver* h, int batch, bool sort64) {
     while (at < small.size()) {
       const int n = h->descs[(size_t)small[at]].n;
       const int64_t M = (int64_t)n * (n - 1) / 2;
-      int64_t P2 = 2;
-      while (P2 < 2 * M) P2 <<= 1;
-      const int64_t sb = (P2 * 12 + 64 + 255) & ~(int64_t)255;
+      const int64_t sb = (scalar_tls_small_workspace_bytes(M) + 255) & ~(int64_t)255;
       if (!sel.empty() && 16 * (trims + M) + scratch + sb > kChunkBytes) break;
       sel.push_back(small[at]);
       off.push_back(trims);
@@ -733,6 +727,34 @@ int32_t scale_stage_batch(teaser_hip_solver* h, int batch, bool sort64) {
   return TEASER_HIP_OK;
 }
 
+// The peel's rounds alternate between the two alive masks: where the last round left the survivors, and the other one
+// (the bound stage's candidate sets go there).
+struct AliveMasks {
+  const uint64_t* final_alive;
+  uint64_t* spare_alive;
+};
+AliveMasks alive_masks(teaser_hip_solver* h) {
+  uint64_t* a = h->d_alive_a.as<uint64_t>();
+  uint64_t* b = h->d_alive_b.as<uint64_t>();
+  return (kPeelRounds % 2 == 0) ? AliveMasks{a, b} : AliveMasks{b, a};
+}
+
+// Scratch of the colouring bound and the root filter for launches over `nprob` problems of a batch of total_n vertices.
+int32_t ensure_bound_scratch(teaser_hip_solver* h, int nprob, int64_t total_n) {
+  const size_t tw = (size_t)std::max<int64_t>(h->total_w, 1);
+  HIPCHK(h, h->c_colour.ensure(4 * (size_t)total_n));
+  HIPCHK(h, h->c_tent.ensure(4 * (size_t)total_n));
+  HIPCHK(h, h->c_xlist.ensure(4 * (size_t)total_n));
+  HIPCHK(h, h->c_list_a.ensure(4 * (size_t)total_n));
+  HIPCHK(h, h->c_list_b.ensure(4 * (size_t)total_n));
+  HIPCHK(h, h->c_counts.ensure((size_t)colour_counts_bytes(nprob)));
+  HIPCHK(h, h->c_bits.ensure(8 * 10 * tw));
+  HIPCHK(h, h->c_class.ensure(4 * 8 * (size_t)total_n));
+  HIPCHK(h, h->x_probs.ensure(sizeof(ExactProb) * (size_t)nprob));
+  HIPCHK(h, h->x_xbits.ensure(8 * tw));
+  return TEASER_HIP_OK;
+}
+
 // --------------------------------------------------------------------------------------------
 // After the greedy + peel stages (host copies of the states are fresh): for every problem whose
 // bound is still open run the global colouring bound, then the exact search from the roots it
@@ -747,9 +769,7 @@ int32_t close_clique_bounds(teaser_hip_solver* h, int batch, int64_t total_n, bo
   hipStream_t s = h->stream;
   const ProbDesc* dd = h->d_desc.as<ProbDesc>();
   ProbState* ds = h->d_state.as<ProbState>();
-  const uint64_t* final_alive =
-      (kPeelRounds % 2 == 0) ? h->d_alive_a.as<uint64_t>() : h->d_alive_b.as<uint64_t>();
-  uint64_t* spare_alive = (kPeelRounds % 2 == 0) ? h->d_alive_b.as<uint64_t>() : h->d_alive_a.as<uint64_t>();
+  const auto [final_alive, spare_alive] = alive_masks(h);
   // problems whose greedy bound the peel did not close: first the global colouring bound
   std::vector<int32_t> unproven, csel;
   for (int b = 0; b < batch; ++b) {
@@ -772,17 +792,11 @@ int32_t close_clique_bounds(teaser_hip_solver* h, int batch, int64_t total_n, bo
     const ExactProb* got = reinterpret_cast<const ExactProb*>(h->pin_ep.p);
     for (size_t k = 0; k < unproven.size(); ++k) ep[k] = got[unproven[k]];
   } else {
-    HIPCHK(h, h->c_colour.ensure(4 * (size_t)total_n));
-    HIPCHK(h, h->c_tent.ensure(4 * (size_t)total_n));
-    HIPCHK(h, h->c_xlist.ensure(4 * (size_t)total_n));
+    const int32_t rc = ensure_bound_scratch(h, (int)unproven.size(), total_n);
+    if (rc != TEASER_HIP_OK) return rc;
     if (!csel.empty()) {
       StageScope sc(h, ST_COLOUR);
       HIPCHK(h, h->c_sel.ensure(4 * csel.size()));
-      HIPCHK(h, h->c_list_a.ensure(4 * (size_t)total_n));
-      HIPCHK(h, h->c_list_b.ensure(4 * (size_t)total_n));
-      HIPCHK(h, h->c_counts.ensure((size_t)colour_counts_bytes((int)csel.size())));
-      HIPCHK(h, h->c_bits.ensure(8 * 10 * (size_t)std::max<int64_t>(h->total_w, 1)));
-      HIPCHK(h, h->c_class.ensure(4 * 8 * (size_t)total_n));
       HIPCHK(h, hipMemcpyAsync(h->c_sel.p, csel.data(), 4 * csel.size(), hipMemcpyHostToDevice, s));
       int cmax_n = 0;
       for (int32_t b : csel) cmax_n = std::max(cmax_n, h->descs[(size_t)b].n);
@@ -815,8 +829,6 @@ int32_t close_clique_bounds(teaser_hip_solver* h, int batch, int64_t total_n, bo
       ep[k].prob = unproven[k];
       ep[k].use_x = std::find(csel.begin(), csel.end(), unproven[k]) != csel.end() ? 1 : 0;
     }
-    HIPCHK(h, h->x_probs.ensure(sizeof(ExactProb) * ep.size()));
-    HIPCHK(h, h->x_xbits.ensure(8 * (size_t)std::max<int64_t>(h->total_w, 1)));
     HIPCHK(h, hipMemcpyAsync(h->x_probs.p, ep.data(), sizeof(ExactProb) * ep.size(), hipMemcpyHostToDevice, s));
     launch_exact_count(s, dd, h->x_probs.as<ExactProb>(), (int)ep.size(), max_W, h->d_bitmap.as<uint64_t>(), final_alive,
                        h->d_deg.as<int32_t>(), ds, h->c_xlist.as<int32_t>(), h->c_tent.as<int32_t>(), spare_alive,
@@ -919,9 +931,9 @@ int32_t close_clique_bounds(teaser_hip_solver* h, int batch, int64_t total_n, bo
       }
     }
     HIPCHK(h, h->x_arena.ensure((size_t)arena_waves * (size_t)arena_bytes));
-    // task queues of the expansion phases + the donation queue of the sequential phase (32768 slots of header |
+    // task queues of the expansion phases + the donation queue of the sequential phase (2^15 slots of header |
     // candidate set | clique prefix of up to min(64 W2, 512) vertices, + flags: launch_exact_clique)
-    const int64_t donate_bytes = (int64_t)32768 * (48 + 8 * max_W2 + 4 * std::min(64 * max_W2, 512) + 32 + 4);
+    const int64_t donate_bytes = ((int64_t)1 << 15) * (48 + 8 * max_W2 + 4 * std::min(64 * max_W2, 512) + 32 + 4);
     const int64_t task_bytes = std::min<int64_t>((int64_t)1 << 30, std::max<int64_t>((int64_t)64 << 20, (int64_t)(64 + 8 * max_W2) * 65536)) + donate_bytes;
     HIPCHK(h, h->x_tasks.ensure((size_t)task_bytes));
     HIPCHK(h, h->x_ctrl.ensure(kExactCounterInts * sizeof(int32_t)));
@@ -1002,20 +1014,10 @@ int32_t enqueue_bounds_speculative(teaser_hip_solver* h, int batch, int64_t tota
   hipStream_t s = h->stream;
   const ProbDesc* dd = h->d_desc.as<ProbDesc>();
   ProbState* ds = h->d_state.as<ProbState>();
-  const uint64_t* final_alive =
-      (kPeelRounds % 2 == 0) ? h->d_alive_a.as<uint64_t>() : h->d_alive_b.as<uint64_t>();
-  uint64_t* spare_alive = (kPeelRounds % 2 == 0) ? h->d_alive_b.as<uint64_t>() : h->d_alive_a.as<uint64_t>();
-  const size_t tw = (size_t)std::max<int64_t>(h->total_w, 1);
-  HIPCHK(h, h->c_colour.ensure(4 * (size_t)total_n));
-  HIPCHK(h, h->c_tent.ensure(4 * (size_t)total_n));
-  HIPCHK(h, h->c_xlist.ensure(4 * (size_t)total_n));
-  HIPCHK(h, h->c_list_a.ensure(4 * (size_t)total_n));
-  HIPCHK(h, h->c_list_b.ensure(4 * (size_t)total_n));
-  HIPCHK(h, h->c_counts.ensure((size_t)colour_counts_bytes(batch)));
-  HIPCHK(h, h->c_bits.ensure(8 * 10 * tw));
-  HIPCHK(h, h->c_class.ensure(4 * 8 * (size_t)total_n));
-  HIPCHK(h, h->x_probs.ensure(sizeof(ExactProb) * (size_t)batch));
-  HIPCHK(h, h->x_xbits.ensure(8 * tw));
+  const auto [final_alive, spare_alive] = alive_masks(h);
+  const int64_t tw = std::max<int64_t>(h->total_w, 1);
+  const int32_t rc = ensure_bound_scratch(h, batch, total_n);
+  if (rc != TEASER_HIP_OK) return rc;
   HIPCHK(h, h->pin_ep.ensure(sizeof(ExactProb) * (size_t)batch));
   bool mis = setting(S_COLOUR_MIS) > 0 && h->max_n >= setting(S_COLOUR_MIS) && h->max_n <= 65536;
   // (the host does not know this batch's cliques yet: the open problems of the PREVIOUS batch -- the reason the stage is
@@ -1027,7 +1029,7 @@ int32_t enqueue_bounds_speculative(teaser_hip_solver* h, int batch, int64_t tota
     launch_colour_bound(s, dd, nullptr, batch, h->max_n, h->d_bitmap.as<uint64_t>(), final_alive,
                         h->d_clique.as<int32_t>(), ds, h->c_colour.as<int32_t>(), h->c_tent.as<int32_t>(),
                         h->c_xlist.as<int32_t>(), h->c_class.as<int32_t>(), h->c_list_a.as<int32_t>(),
-                        h->c_list_b.as<int32_t>(), h->c_counts.as<int32_t>(), h->c_bits.as<uint64_t>(), (int64_t)tw, total_n,
+                        h->c_list_b.as<int32_t>(), h->c_counts.as<int32_t>(), h->c_bits.as<uint64_t>(), tw, total_n,
                         kColourRounds, mis ? h->c_mis.p : nullptr, h->d_deg.as<int32_t>());
   }
   {
@@ -1107,7 +1109,7 @@ int32_t enqueue_heuristic_stage(teaser_hip_solver* h, int batch, int mode, bool 
     if (setting(S_GREEDY_SMALL) != 0) {
       int max_small = 0;
       for (int b = 0; b < batch; ++b)
-        if (h->descs[(size_t)b].n <= 768) max_small = std::max(max_small, h->descs[(size_t)b].n);
+        if (h->descs[(size_t)b].n <= kSmallCap) max_small = std::max(max_small, h->descs[(size_t)b].n);
       if (max_small >= 2) {
         HIPCHK(h, h->d_small.ensure((size_t)greedy_small_scratch_bytes(batch)));
         small_G = launch_greedy_small(s, dd, batch, max_small, h->d_bitmap.as<uint64_t>(), h->d_deg.as<int32_t>(), ds,
@@ -1128,6 +1130,66 @@ int32_t enqueue_heuristic_stage(teaser_hip_solver* h, int batch, int mode, bool 
   return TEASER_HIP_OK;
 }
 
+// One problem of n points / vertices at the given offsets of the packed arrays.
+ProbDesc problem_desc(int n, int64_t pt_off, int64_t bm_off, int64_t w_off) {
+  ProbDesc d;
+  d.n = n;
+  d.W = (n + 63) / 64;
+  d.pt_off = pt_off;
+  d.bm_off = bm_off;
+  d.w_off = w_off;
+  return d;
+}
+
+// What a problem's state holds before any kernel has run: the identity transform, no clique, no start taken.
+ProbState initial_state(int heu_blocks) {
+  ProbState st;
+  memset(&st, 0, sizeof(st));
+  st.scale = 1.0;
+  st.R[0] = st.R[4] = st.R[8] = 1.0;
+  st.gnc_cost = INFINITY;
+  st.next_start = heu_blocks;  // (the heuristic's start queue begins behind its workgroups)
+  for (int k = 0; k < kMaxStarts; ++k) st.start_vertex[k] = -1;
+  return st;
+}
+
+// The problem table of a batch: descriptors at packed offsets, initial states, TIM offsets, the totals the stages size
+// their buffers with, and the geometry of the greedy launch.  closure: the degree closure may run in front of the
+// heuristic stage (it does when no problem is too large for it).
+int32_t layout_batch(teaser_hip_solver* h, const int64_t* pt_off, const int32_t* n, int batch, bool closure) {
+  h->batch = batch;
+  h->descs.assign((size_t)batch, ProbDesc());
+  h->tim_off.assign((size_t)batch, 0);
+  h->exact_run.assign((size_t)batch, 0);
+  h->heu_size.assign((size_t)batch, 0);
+  h->prob_status.assign((size_t)batch, TEASER_HIP_OK);
+  h->colour_x.assign((size_t)batch, -1);
+  int max_n = 0;
+  for (int b = 0; b < batch; ++b) max_n = std::max(max_n, n[b]);
+  const bool closure_ahead = closure && max_n <= 65536;
+  h->heu_blocks = heuristic_blocks_per_problem(batch, (max_n + 63) / 64, closure_ahead ? h->closure_open_prev : -1);
+  h->heu_rows = closure_ahead && h->closure_open_prev * 4 <= batch ? std::min(batch, std::max(4, 2 * h->closure_open_prev)) : 0;
+  h->states.assign((size_t)batch, initial_state(h->heu_blocks));
+  int64_t bm = 0, wo = 0, tims = 0, maxpt = 0;
+  for (int b = 0; b < batch; ++b) {
+    if (n[b] < 0) return TEASER_HIP_ERR_BAD_ARG;
+    const ProbDesc d = h->descs[(size_t)b] = problem_desc(n[b], pt_off[b], bm, wo);
+    bm += (int64_t)d.n * d.W;
+    wo += d.W;
+    h->tim_off[(size_t)b] = tims;
+    const int64_t kt = h->params.rotation_tim_graph == TEASER_TIM_CHAIN ? (int64_t)d.n : (int64_t)d.n * (d.n - 1) / 2;
+    tims += kt + 2;
+    maxpt = std::max<int64_t>(maxpt, d.pt_off + d.n);
+  }
+  h->max_n = max_n;
+  h->max_W = (max_n + 63) / 64;
+  h->total_n = maxpt;
+  h->total_bm = bm;
+  h->total_w = wo;
+  h->total_tims = tims;
+  return TEASER_HIP_OK;
+}
+
 // First half of a solve: everything that can be enqueued without a host sync.
 int32_t solve_packed_enqueue(teaser_hip_solver* h, const double* d_src, const double* d_dst,
                              const int64_t* pt_off, const int32_t* n, int batch, bool fp64_k1) {
@@ -1139,54 +1201,15 @@ int32_t solve_packed_enqueue(teaser_hip_solver* h, const double* d_src, const do
     return TEASER_HIP_ERR_UNSUPPORTED;
   }
   const int mode = effective_mode(P);
-  h->batch = batch;
-  h->descs.assign((size_t)batch, ProbDesc());
-  h->states.assign((size_t)batch, ProbState());
-  h->tim_off.assign((size_t)batch, 0);
-  h->exact_run.assign((size_t)batch, 0);
-  h->heu_size.assign((size_t)batch, 0);
-  h->prob_status.assign((size_t)batch, TEASER_HIP_OK);
   h->cur_src = d_src;
   h->cur_dst = d_dst;
   h->have_graph = false;
   h->pend.closure = false;
   h->pend.heuristic_enqueued = true;
-  h->colour_x.assign((size_t)batch, -1);
-  int64_t bm = 0, wo = 0, tims = 0, maxpt = 0;
-  int max_n = 0;
-  int heu_blocks = 1;
-  {
-    int mx = 0;
-    for (int b = 0; b < batch; ++b) mx = std::max(mx, n[b]);
-    const bool closure_ahead = effective_mode(P) == TEASER_INLIER_PMC_EXACT && mx <= 65536 && setting(S_DEG_CLOSURE) != 0;
-    heu_blocks = heuristic_blocks_per_problem(batch, (mx + 63) / 64, closure_ahead ? h->closure_open_prev : -1);
-    h->heu_blocks = heu_blocks;
-    h->heu_rows = closure_ahead && h->closure_open_prev * 4 <= batch ? std::min(batch, std::max(4, 2 * h->closure_open_prev)) : 0;
-  }
-  for (int b = 0; b < batch; ++b) {
-    if (n[b] < 0) return TEASER_HIP_ERR_BAD_ARG;
-    ProbDesc& d = h->descs[(size_t)b];
-    d.n = n[b];
-    d.W = (n[b] + 63) / 64;
-    d.pt_off = pt_off[b];
-    d.bm_off = bm;
-    d.w_off = wo;
-    bm += (int64_t)d.n * d.W;
-    wo += d.W;
-    h->tim_off[(size_t)b] = tims;
-    const int64_t kt = P.rotation_tim_graph == TEASER_TIM_CHAIN ? (int64_t)d.n
-                                                                : (int64_t)d.n * (d.n - 1) / 2;
-    tims += kt + 2;
-    max_n = std::max(max_n, d.n);
-    maxpt = std::max<int64_t>(maxpt, d.pt_off + d.n);
-    ProbState& st = h->states[(size_t)b];
-    memset(&st, 0, sizeof(st));
-    st.scale = 1.0;
-    st.R[0] = st.R[4] = st.R[8] = 1.0;
-    st.gnc_cost = INFINITY;
-    st.next_start = heu_blocks;  // (the heuristic's start queue begins behind its workgroups)
-    for (int k = 0; k < kMaxStarts; ++k) st.start_vertex[k] = -1;
-  }
+  const int32_t lrc = layout_batch(h, pt_off, n, batch, mode == TEASER_INLIER_PMC_EXACT && setting(S_DEG_CLOSURE) != 0);
+  if (lrc != TEASER_HIP_OK) return lrc;
+  const int max_n = h->max_n;
+  const int64_t bm = h->total_bm, wo = h->total_w, tims = h->total_tims;
   if (tims > ((int64_t)1 << 31)) {
     h->err = "rotation_tim_graph = COMPLETE needs too many TIMs for this batch";
     return TEASER_HIP_ERR_UNSUPPORTED;
@@ -1195,13 +1218,7 @@ int32_t solve_packed_enqueue(teaser_hip_solver* h, const double* d_src, const do
     h->err = "inlier_selection_mode = KCORE_HEU supports at most 65536 correspondences per problem";
     return TEASER_HIP_ERR_UNSUPPORTED;
   }
-  h->max_n = max_n;
-  h->max_W = (max_n + 63) / 64;
-  h->total_n = maxpt;
-  h->total_bm = bm;
-  h->total_w = wo;
-  h->total_tims = tims;
-  const int64_t total_n = std::max<int64_t>(maxpt, 1);
+  const int64_t total_n = std::max<int64_t>(h->total_n, 1);
 
   // descs | initial states | tim offsets | peel counters (zero) | K1 prep + worklist counter (zero):
   // ONE device block, filled by ONE H2D copy per solve (no memsets, no per-array copies)
@@ -1478,6 +1495,7 @@ int32_t solve_packed_impl(teaser_hip_solver* h, const double* d_src, const doubl
 }
 
 int32_t make_lane(teaser_hip_solver* h, teaser_hip_solver** out);
+void destroy_handle(teaser_hip_solver* h);
 
 // K1 runs as the matrix-core filter; if its FP64 fix-up list overflowed (adversarial geometry) the
 // whole batch is solved again with the all-FP64 K1 -- same results, slower.
@@ -1615,11 +1633,7 @@ int32_t make_lane(teaser_hip_solver* h, teaser_hip_solver** out) {
   if (es != hipSuccess || hipEventCreateWithFlags(&lane->k1_done, hipEventDisableTiming) != hipSuccess ||
       hipEventCreateWithFlags(&lane->k1_phase_done, hipEventDisableTiming) != hipSuccess ||
       hipEventCreateWithFlags(&lane->inputs_ready, hipEventDisableTiming) != hipSuccess) {
-    if (lane->stream) (void)hipStreamDestroy(lane->stream);
-    if (lane->k1_done) (void)hipEventDestroy(lane->k1_done);
-    if (lane->k1_phase_done) (void)hipEventDestroy(lane->k1_phase_done);
-    if (lane->inputs_ready) (void)hipEventDestroy(lane->inputs_ready);
-    delete lane;
+    destroy_handle(lane);  // (k1_stream is still unset: the parent's is not touched)
     h->err = "could not create a lane (stream / events)";
     return TEASER_HIP_ERR_HIP;
   }
@@ -1635,48 +1649,34 @@ int32_t make_lane(teaser_hip_solver* h, teaser_hip_solver** out) {
 
 void finisher_stop(teaser_hip_solver* lane);
 
+// What has an order when a handle (or a lane) goes: its finisher stops, its streams drain, the front-end's handle
+// goes, then the events and the streams it owns.  The buffers free themselves, and ~HandleBase destroys h->stream.
 void release_handle_resources(teaser_hip_solver* h) {
   finisher_stop(h);
   if (h->stream) (void)hipStreamSynchronize(h->stream);
   if (h->features) (void)teaser_hip_features_destroy(h->features);
   h->features = nullptr;
-  DevBuf* bufs[] = {&h->d_desc, &h->d_state, &h->d_src, &h->d_dst, &h->d_bitmap, &h->d_deg,
-                    &h->d_clique, &h->d_start_cliques, &h->d_alive_a, &h->d_alive_b,
-                    &h->d_next_count, &h->d_weights, &h->d_rot_inl, &h->d_trans_inl,
-                    &h->d_tls_scratch, &h->d_tim_off, &h->d_pk, &h->d_prep, &h->d_work, &h->d_core, &h->d_small, &h->hdr, &h->x_order,
-                    &h->x_src, &h->x_dst, &h->x_bitmap, &h->x_desc, &h->x_state, &h->x_ctrl,
-                    &h->x_clique, &h->x_arena, &h->x_probs, &h->x_probs2, &h->x_keys, &h->x_xbits, &h->x_tasks, &h->c_sel, &h->c_colour, &h->c_tent, &h->c_xlist, &h->c_list_a, &h->c_list_b,
-                    &h->c_counts, &h->c_bits, &h->c_class, &h->c_mis,
-                    &h->s_a, &h->s_b, &h->s_c, &h->s_d, &h->s_e};
-  for (DevBuf* b : bufs) b->release();
-  h->pin_states.release();
-  h->pin_in.release();
-  h->pin_pts.release();
-  h->pin_ep.release();
   for (hipEvent_t e : h->ev_pool) (void)hipEventDestroy(e);
   h->ev_pool.clear();
   if (h->k1_done) (void)hipEventDestroy(h->k1_done);
   if (h->k1_phase_done) (void)hipEventDestroy(h->k1_phase_done);
   if (h->inputs_ready) (void)hipEventDestroy(h->inputs_ready);
+  h->k1_done = h->k1_phase_done = h->inputs_ready = nullptr;
   if (h->k1_stream && !h->is_lane) {  // the parent owns the shared K1 stream (lanes borrow it)
     (void)hipStreamSynchronize(h->k1_stream);
     (void)hipStreamDestroy(h->k1_stream);
   }
+  h->k1_stream = nullptr;
   if (h->copy_stream) {
     (void)hipStreamSynchronize(h->copy_stream);
     if (h->copy_stream != h->stream) (void)hipStreamDestroy(h->copy_stream);
     h->copy_stream = nullptr;
   }
-  for (auto& is : h->in_sets) {
-    is.src.release();
-    is.dst.release();
-    if (is.ready) (void)hipEventDestroy(is.ready);
-  }
-  h->in_sets.clear();
-  if (h->stream) (void)hipStreamDestroy(h->stream);
-  h->k1_done = h->k1_phase_done = h->inputs_ready = nullptr;
-  h->k1_stream = nullptr;
-  h->stream = nullptr;
+}
+
+void destroy_handle(teaser_hip_solver* h) {
+  release_handle_resources(h);
+  delete h;
 }
 
 // ---- asynchronous batches ------------------------------------------------------------------
@@ -2082,27 +2082,15 @@ int32_t teaser_hip_params_default(teaser_params_c* p) {
 
 int32_t teaser_hip_solver_create(const teaser_params_c* params, int32_t device,
                                  teaser_hip_solver** out) {
-  if (!out) return TEASER_HIP_ERR_BAD_ARG;
-  *out = nullptr;
-  int count = 0;
-  if (hipGetDeviceCount(&count) != hipSuccess || count <= 0) return TEASER_HIP_ERR_NO_DEVICE;
-  if (device < 0) {
-    if (hipGetDevice(&device) != hipSuccess) return TEASER_HIP_ERR_NO_DEVICE;
-  }
-  if (device >= count) return TEASER_HIP_ERR_BAD_ARG;
-  if (hipSetDevice(device) != hipSuccess) return TEASER_HIP_ERR_HIP;
-  teaser_hip_solver* h = new teaser_hip_solver();
-  h->device = device;
+  const int32_t rc = open_handle(device, out);
+  if (rc != TEASER_HIP_OK) return rc;
+  teaser_hip_solver* h = *out;
   if (params)
     h->params_given = *params;
   else
     teaser_hip_params_default(&h->params_given);
   h->params = snapshot_params(h->params_given);
   memset(&h->prof, 0, sizeof(h->prof));
-  if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess) {
-    delete h;
-    return TEASER_HIP_ERR_HIP;
-  }
   {  // schedule of the asynchronous batches: the settings' values at creation (internal.h)
     const int dv = (int)setting(S_DEPTH), sg = (int)setting(S_STAGGER), ks = (int)setting(S_K1_STREAM);
     if (dv >= 1 && dv <= 16) h->depth = dv;
@@ -2113,20 +2101,15 @@ int32_t teaser_hip_solver_create(const teaser_params_c* params, int32_t device,
     h->tail_cus = std::max(0, (int)setting(S_TAIL_CUS));
     h->tail_cu_block = setting(S_TAIL_CU_BLOCK) != 0;
   }
-  *out = h;
   return TEASER_HIP_OK;
 }
 
 int32_t teaser_hip_solver_destroy(teaser_hip_solver* h) {
   if (!h) return TEASER_HIP_OK;
   (void)hipSetDevice(h->device);
-  for (teaser_hip_solver* lane : h->lanes) {
-    release_handle_resources(lane);
-    delete lane;
-  }
+  for (teaser_hip_solver* lane : h->lanes) destroy_handle(lane);
   h->lanes.clear();
-  release_handle_resources(h);
-  delete h;
+  destroy_handle(h);
   g_trace.dump();
   return TEASER_HIP_OK;
 }
@@ -2315,16 +2298,8 @@ int32_t teaser_hip_solve_for_translation(teaser_hip_solver* h, const double* src
   // one-problem batch whose clique is the identity and whose rotation/scale are the identity:
   // raw translation = dst - src (registration.cc:455)
   hipStream_t s = h->stream;
-  ProbDesc d;
-  d.n = k;
-  d.W = (k + 63) / 64;
-  d.pt_off = 0;
-  d.bm_off = 0;
-  d.w_off = 0;
-  ProbState st;
-  memset(&st, 0, sizeof(st));
-  st.scale = 1;
-  st.R[0] = st.R[4] = st.R[8] = 1;
+  const ProbDesc d = problem_desc(k, 0, 0, 0);
+  ProbState st = initial_state(0);
   st.clique_size = k;
   std::vector<int32_t> ident((size_t)k);
   for (int32_t i = 0; i < k; ++i) ident[(size_t)i] = i;
@@ -2359,32 +2334,25 @@ int32_t teaser_hip_solve_for_translation(teaser_hip_solver* h, const double* src
   return TEASER_HIP_OK;
 }
 
-int32_t teaser_hip_scalar_tls(teaser_hip_solver* h, const double* x, const double* ranges,
-                              int32_t n, double* estimate, uint8_t* inlier_mask) {
-  if (!h || !x || !ranges || n <= 0 || !estimate) return TEASER_HIP_ERR_BAD_ARG;
-  (void)hipSetDevice(h->device);
+namespace {
+// Scalar TLS over n measurements on the device (x, ranges): up to kScalarTlsSingleMax of them one sorting workgroup;
+// above, the radix sort + blocked sweep, first on float keys, and when a run of equal float keys was too long to put
+// right (the flag behind the estimate) once more with the 64-bit sort.  Writes the estimate and, if asked, the mask.
+int32_t run_scalar_tls(teaser_hip_solver* h, const double* d_x, const double* d_r, int64_t n, double* estimate,
+                       uint8_t* inlier_mask) {
   hipStream_t s = h->stream;
-  const bool large = n > (1 << 18);  // beyond the single-workgroup sort: radix sort + blocked sweep
-  int64_t P2 = 2;
-  while (P2 < 2 * (int64_t)n) P2 <<= 1;
-  HIPCHK(h, h->s_a.ensure((size_t)n * 8));
-  HIPCHK(h, h->s_b.ensure((size_t)n * 8));
-  HIPCHK(h, h->s_c.ensure(large ? (size_t)scalar_tls_large_workspace_bytes(n) : (size_t)P2 * 12 + 64));
+  const bool large = n > kScalarTlsSingleMax;
+  HIPCHK(h, h->s_c.ensure((size_t)(large ? scalar_tls_large_workspace_bytes(n) : scalar_tls_small_workspace_bytes(n))));
   HIPCHK(h, h->s_d.ensure(64));
   HIPCHK(h, h->s_e.ensure((size_t)n + 16));
-  HIPCHK(h, hipMemcpyAsync(h->s_a.p, x, (size_t)n * 8, hipMemcpyHostToDevice, s));
-  HIPCHK(h, hipMemcpyAsync(h->s_b.p, ranges, (size_t)n * 8, hipMemcpyHostToDevice, s));
-  // large: float-key sort first; a run of equal float keys too long to fix (flag at s_d + 8) repeats the call
-  // with the 64-bit sort
+  int32_t* d_flag = reinterpret_cast<int32_t*>(h->s_d.as<char>() + 8);
   for (int attempt = 0; attempt < 2; ++attempt) {
-    int32_t* d_flag = reinterpret_cast<int32_t*>(h->s_d.as<char>() + 8);
     if (large) {
       HIPCHK(h, hipMemsetAsync(d_flag, 0, 4, s));
-      HIPCHK(h, launch_scalar_tls_large(s, h->s_a.as<double>(), h->s_b.as<double>(), n, h->s_c.as<char>(),
-                                        h->s_d.as<double>(), h->s_e.as<uint8_t>(), attempt == 0 ? d_flag : nullptr));
+      HIPCHK(h, launch_scalar_tls_large(s, d_x, d_r, n, h->s_c.as<char>(), h->s_d.as<double>(), h->s_e.as<uint8_t>(),
+                                        attempt == 0 ? d_flag : nullptr));
     } else {
-      launch_scalar_tls(s, h->s_a.as<double>(), h->s_b.as<double>(), n, h->s_c.as<char>(),
-                        h->s_d.as<double>(), h->s_e.as<uint8_t>());
+      launch_scalar_tls(s, d_x, d_r, (int32_t)n, h->s_c.as<char>(), h->s_d.as<double>(), h->s_e.as<uint8_t>());
     }
     HIPCHK(h, hipGetLastError());
     int32_t flag = 0;
@@ -2396,6 +2364,18 @@ int32_t teaser_hip_scalar_tls(teaser_hip_solver* h, const double* x, const doubl
   }
   return TEASER_HIP_OK;
 }
+}  // namespace
+
+int32_t teaser_hip_scalar_tls(teaser_hip_solver* h, const double* x, const double* ranges,
+                              int32_t n, double* estimate, uint8_t* inlier_mask) {
+  if (!h || !x || !ranges || n <= 0 || !estimate) return TEASER_HIP_ERR_BAD_ARG;
+  (void)hipSetDevice(h->device);
+  HIPCHK(h, h->s_a.ensure((size_t)n * 8));
+  HIPCHK(h, h->s_b.ensure((size_t)n * 8));
+  HIPCHK(h, hipMemcpyAsync(h->s_a.p, x, (size_t)n * 8, hipMemcpyHostToDevice, h->stream));
+  HIPCHK(h, hipMemcpyAsync(h->s_b.p, ranges, (size_t)n * 8, hipMemcpyHostToDevice, h->stream));
+  return run_scalar_tls(h, h->s_a.as<double>(), h->s_b.as<double>(), n, estimate, inlier_mask);
+}
 
 int32_t teaser_hip_solve_for_scale(teaser_hip_solver* h, const double* v1, const double* v2, int64_t m,
                                    double* scale, uint8_t* inlier_mask) {
@@ -2406,47 +2386,24 @@ int32_t teaser_hip_solve_for_scale(teaser_hip_solver* h, const double* v1, const
   }
   (void)hipSetDevice(h->device);
   hipStream_t s = h->stream;
-  const int estimate = h->params.estimate_scaling ? 1 : 0;
   const double beta = 2 * h->params.noise_bound * std::sqrt(h->params.cbar2);  // registration.cc:421 / :438
   HIPCHK(h, h->s_a.ensure((size_t)m * 24));
   HIPCHK(h, h->s_b.ensure((size_t)m * 24));
-  HIPCHK(h, h->s_e.ensure((size_t)m + 16));
-  HIPCHK(h, h->s_d.ensure(64));
   HIPCHK(h, hipMemcpyAsync(h->s_a.p, v1, (size_t)m * 24, hipMemcpyHostToDevice, s));
   HIPCHK(h, hipMemcpyAsync(h->s_b.p, v2, (size_t)m * 24, hipMemcpyHostToDevice, s));
   *scale = 1.0;  // ScaleInliersSelector, registration.cc:432
-  if (estimate) {
-    // raw / alpha reuse the TIM buffers' tails?  No: separate arrays (the sweep gathers from them)
-    const bool large = m > (1 << 18);
-    int64_t P2 = 2;
-    while (P2 < 2 * m) P2 <<= 1;
+  if (h->params.estimate_scaling) {
+    // raw / alpha in arrays of their own (the sweep gathers from them), then scalar TLS over them
     HIPCHK(h, h->x_src.ensure((size_t)m * 8));
     HIPCHK(h, h->x_dst.ensure((size_t)m * 8));
-    HIPCHK(h, h->s_c.ensure(large ? (size_t)scalar_tls_large_workspace_bytes(m) : (size_t)P2 * 12 + 64));
     launch_tim_scale_terms(s, h->s_a.as<double>(), h->s_b.as<double>(), m, beta, 1, h->x_src.as<double>(),
                            h->x_dst.as<double>(), nullptr);
-    for (int attempt = 0; attempt < 2; ++attempt) {  // (as teaser_hip_scalar_tls)
-      int32_t* d_flag = reinterpret_cast<int32_t*>(h->s_d.as<char>() + 8);
-      int32_t flag = 0;
-      if (large) {
-        HIPCHK(h, hipMemsetAsync(d_flag, 0, 4, s));
-        HIPCHK(h, launch_scalar_tls_large(s, h->x_src.as<double>(), h->x_dst.as<double>(), m, h->s_c.as<char>(),
-                                          h->s_d.as<double>(), h->s_e.as<uint8_t>(), attempt == 0 ? d_flag : nullptr));
-        HIPCHK(h, hipMemcpyAsync(&flag, d_flag, 4, hipMemcpyDeviceToHost, s));
-        HIPCHK(h, hipStreamSynchronize(s));
-      } else {
-        launch_scalar_tls(s, h->x_src.as<double>(), h->x_dst.as<double>(), (int32_t)m, h->s_c.as<char>(),
-                          h->s_d.as<double>(), h->s_e.as<uint8_t>());
-      }
-      if (!flag) break;
-    }
-    HIPCHK(h, hipGetLastError());
-    HIPCHK(h, hipMemcpyAsync(scale, h->s_d.p, 8, hipMemcpyDeviceToHost, s));
-  } else {
-    launch_tim_scale_terms(s, h->s_a.as<double>(), h->s_b.as<double>(), m, beta, 0, nullptr, nullptr,
-                           h->s_e.as<uint8_t>());
-    HIPCHK(h, hipGetLastError());
+    return run_scalar_tls(h, h->x_src.as<double>(), h->x_dst.as<double>(), m, scale, inlier_mask);
   }
+  HIPCHK(h, h->s_e.ensure((size_t)m + 16));
+  launch_tim_scale_terms(s, h->s_a.as<double>(), h->s_b.as<double>(), m, beta, 0, nullptr, nullptr,
+                         h->s_e.as<uint8_t>());
+  HIPCHK(h, hipGetLastError());
   if (inlier_mask) HIPCHK(h, hipMemcpyAsync(inlier_mask, h->s_e.p, (size_t)m, hipMemcpyDeviceToHost, s));
   HIPCHK(h, hipStreamSynchronize(s));
   return TEASER_HIP_OK;
@@ -2463,28 +2420,13 @@ int32_t teaser_hip_max_clique(teaser_hip_solver* h, const uint64_t* bitmap, int3
     h->err = "KCORE_HEU supports at most 65536 vertices";
     return TEASER_HIP_ERR_UNSUPPORTED;
   }
-  // a one-problem "batch" whose graph is the caller's bitmap
+  // a one-problem "batch" whose graph is the caller's bitmap: no points, no degree closure
+  const int64_t off = 0;
+  int32_t rc = layout_batch(h, &off, &n, 1, false);
+  if (rc != TEASER_HIP_OK) return rc;
   h->batch = 0;  // getters of a previous solve are invalidated
   h->pend.spec_bounds = false;  // (a previous solve's speculative bound results are not this graph's)
-  h->descs.assign(1, ProbDesc());
-  h->states.assign(1, ProbState());
-  h->exact_run.assign(1, 0);
-  h->heu_size.assign(1, 0);
-  h->prob_status.assign(1, TEASER_HIP_OK);
-  h->colour_x.assign(1, -1);
-  ProbDesc& d = h->descs[0];
-  d.n = n;
-  d.W = W;
-  d.pt_off = 0;
-  d.bm_off = 0;
-  d.w_off = 0;
-  h->total_n = n;
-  h->total_w = W;
-  h->total_bm = (int64_t)n * W;
   ProbState& st = h->states[0];
-  memset(&st, 0, sizeof(st));
-  st.next_start = heuristic_blocks_per_problem(1, W);
-  for (int k = 0; k < kMaxStarts; ++k) st.start_vertex[k] = -1;
   HIPCHK(h, h->d_desc.ensure(sizeof(ProbDesc)));
   HIPCHK(h, h->d_state.ensure(sizeof(ProbState)));
   HIPCHK(h, h->d_bitmap.ensure((size_t)n * W * 8));
@@ -2494,40 +2436,28 @@ int32_t teaser_hip_max_clique(teaser_hip_solver* h, const uint64_t* bitmap, int3
   HIPCHK(h, h->d_alive_a.ensure((size_t)W * 8));
   HIPCHK(h, h->d_alive_b.ensure((size_t)W * 8));
   HIPCHK(h, h->d_next_count.ensure(32));
-  HIPCHK(h, hipMemcpyAsync(h->d_desc.p, &d, sizeof(d), hipMemcpyHostToDevice, s));
+  HIPCHK(h, hipMemcpyAsync(h->d_desc.p, h->descs.data(), sizeof(ProbDesc), hipMemcpyHostToDevice, s));
   HIPCHK(h, hipMemcpyAsync(h->d_state.p, &st, sizeof(st), hipMemcpyHostToDevice, s));
   HIPCHK(h, hipMemcpyAsync(h->d_bitmap.p, bitmap, (size_t)n * W * 8, hipMemcpyHostToDevice, s));
   HIPCHK(h, hipMemsetAsync(h->d_next_count.p, 0, 32, s));
-  const ProbDesc* dd = h->d_desc.as<ProbDesc>();
-  ProbState* ds = h->d_state.as<ProbState>();
   const bool exact = (mode == TEASER_INLIER_PMC_EXACT);
-  launch_degrees(s, dd, 1, n, h->d_bitmap.as<uint64_t>(), h->d_deg.as<int32_t>(), ds);
-  launch_heuristic(s, dd, 1, W, h->d_bitmap.as<uint64_t>(), h->d_deg.as<int32_t>(), ds,
-                   h->d_start_cliques.as<int32_t>(), n, nullptr, h->d_clique.as<int32_t>());
-  int small_G = 0;
-  if (setting(S_GREEDY_SMALL) != 0 && n <= 768) {
-    HIPCHK(h, h->d_small.ensure((size_t)greedy_small_scratch_bytes(1)));
-    small_G = launch_greedy_small(s, dd, 1, n, h->d_bitmap.as<uint64_t>(), h->d_deg.as<int32_t>(), ds, h->d_small.p,
-                                  h->d_next_count.as<int32_t>() + 4);
-  }
-  launch_select_best(s, dd, 1, W, h->d_deg.as<int32_t>(), ds, h->d_start_cliques.as<int32_t>(), n,
-                     h->d_clique.as<int32_t>(), h->d_alive_a.as<uint64_t>(), exact ? 1 : 0, h->d_small.p, small_G);
+  launch_degrees(s, h->d_desc.as<ProbDesc>(), 1, n, h->d_bitmap.as<uint64_t>(), h->d_deg.as<int32_t>(),
+                 h->d_state.as<ProbState>());
+  rc = enqueue_heuristic_stage(h, 1, mode, false);
+  if (rc != TEASER_HIP_OK) return rc;
   if (mode == TEASER_INLIER_KCORE_HEU) {  // graph.cc:58-81 (n <= 65536: checked above)
     HIPCHK(h, h->c_colour.ensure(4 * (size_t)n));
     HIPCHK(h, h->c_tent.ensure(4 * (size_t)n));
-    launch_kcore_heuristic(s, dd, 1, h->d_bitmap.as<uint64_t>(), h->d_deg.as<int32_t>(), ds,
-                           h->c_colour.as<int32_t>(), h->c_tent.as<int32_t>(), h->d_clique.as<int32_t>(),
-                           h->params.kcore_heuristic_threshold);
+    launch_kcore_heuristic(s, h->d_desc.as<ProbDesc>(), 1, h->d_bitmap.as<uint64_t>(), h->d_deg.as<int32_t>(),
+                           h->d_state.as<ProbState>(), h->c_colour.as<int32_t>(), h->c_tent.as<int32_t>(),
+                           h->d_clique.as<int32_t>(), h->params.kcore_heuristic_threshold);
   }
-  if (exact)
-    launch_peel_rounds(s, dd, 1, W, h->d_bitmap.as<uint64_t>(), ds, h->d_alive_a.as<uint64_t>(),
-                       h->d_alive_b.as<uint64_t>(), h->d_next_count.as<int32_t>(), kPeelRounds);
   HIPCHK(h, hipGetLastError());
   HIPCHK(h, hipMemcpyAsync(&st, h->d_state.p, sizeof(st), hipMemcpyDeviceToHost, s));
   HIPCHK(h, hipStreamSynchronize(s));
   if (exact && n >= 2) {
     bool changed = false;
-    int32_t rc = close_clique_bounds(h, 1, n, &changed);
+    rc = close_clique_bounds(h, 1, n, &changed);
     if (rc != TEASER_HIP_OK) return rc;
   }
   if (exact_run) *exact_run = h->exact_run[0];
@@ -2569,10 +2499,7 @@ int32_t teaser_hip_set_pipeline_depth(teaser_hip_solver* h, int32_t depth) {
   h->ticket_lane.assign((size_t)depth + 1, -2);
   if (depth < (int32_t)h->lanes.size()) {
     (void)hipSetDevice(h->device);
-    for (size_t k = (size_t)depth; k < h->lanes.size(); ++k) {
-      release_handle_resources(h->lanes[k]);
-      delete h->lanes[k];
-    }
+    for (size_t k = (size_t)depth; k < h->lanes.size(); ++k) destroy_handle(h->lanes[k]);
     h->lanes.resize((size_t)depth);
     h->route.clear();
     h->batch = 0;

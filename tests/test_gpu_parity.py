@@ -560,6 +560,85 @@ def test_solve_for_scale_stage_vs_oracle():
         assert (s.scale_inliers_mask_of_last_stage == ref_mask).all()
 
 
+def _large_route_tims(case):
+    """2^18 + 1 TIM pairs, the smallest count the single-workgroup sort does not take."""
+    m = (1 << 18) + 1
+    rng = np.random.default_rng(31)
+    if case == "random":
+        v1 = rng.uniform(-1, 1, size=(3, m))
+        v2 = 1.7 * v1 + rng.uniform(-0.004, 0.004, size=(3, m))
+        out = rng.permutation(m)[:m // 2]
+        v2[:, out] = rng.uniform(-3, 3, size=(3, out.size))
+        return v1, v2, None
+    # heavy ties: 64 distinct lengths, eight distinct ratios, 1.5 for two thirds of the pairs -- the endpoint keys fall
+    # into runs of thousands of equal keys, far beyond what the order-fix kernel repairs in place (kFxHalo = 64): the
+    # float-key attempt must hand over to the 64-bit sort
+    v1 = np.zeros((3, m))
+    v2 = np.zeros((3, m))
+    v1[0] = rng.integers(32, 96, size=m) / 64.0
+    k = np.where(rng.uniform(size=m) < 0.6, 1.5, rng.integers(1, 8, size=m) / 2.0)
+    v2[0] = v1[0] * k
+    return v1, v2, 1.5
+
+
+@pytest.mark.parametrize("case", ["random", "ties"])
+def test_solve_for_scale_large_route_vs_oracle(case):
+    """solveForScale with estimate_scaling on more TIMs than one workgroup sorts (radix sort + blocked sweep, float keys
+    first): the oracle's scale to 1e-9 and its mask, and the same bytes whichever sort the `scale_sort64` option picks."""
+    v1, v2, exact = _large_route_tims(case)
+    ref_scale, ref_mask = oracle.scale_inliers_mask(v1, v2, 0.01, 1.0, True)
+    print(case, "oracle scale %.17g, %d of %d in the mask" % (ref_scale, int(np.sum(ref_mask)), v1.shape[1]))
+    if exact is not None:
+        assert ref_scale == exact
+    s = make_solver(noise_bound=0.01, estimate_scaling=True)
+    got = {}
+    try:
+        for sort64 in (0, 1):
+            tp.set_option("scale_sort64", sort64)
+            scale = s.solveForScale(v1, v2)
+            got[sort64] = (np.float64(scale).tobytes(), s.scale_inliers_mask_of_last_stage.copy())
+            print(case, "scale_sort64 =", sort64, "scale %.17g" % scale)
+            assert abs(scale - ref_scale) <= 1e-9 * max(1.0, scale)
+            assert (got[sort64][1] == np.asarray(ref_mask).ravel()).all()
+    finally:
+        tp.set_option("scale_sort64", 0)
+    assert got[0][0] == got[1][0] and (got[0][1] == got[1][1]).all()
+
+
+def test_stage_calls_between_two_solves_on_one_handle():
+    """One handle, in order: a solve, maxClique, the getters (refused: the stage call holds no batch), scalarTLS,
+    solveForTranslation, the same solve again.  The stage calls replace the solve's views into the header block
+    (descriptors, states, peel counters) by buffers of their own and the next solve takes them back: both solves must
+    equal a fresh handle's bit for bit."""
+    pr = tp.synth_problem(20250523 + 1, 64, 0.5, 0.01)
+
+    def solve(s):
+        sol = s.solve(pr["src"], pr["dst"])
+        return (sol.valid, np.float64(sol.scale).tobytes(), sol.rotation.tobytes(), sol.translation.tobytes(),
+                s.getInlierMaxClique(), s.getRotationInliers(), s.getTranslationInliers(),
+                s.getInlierGraphBitmap().tobytes(), s.getDegrees().tobytes())
+
+    fresh = solve(make_solver(**bench_params()))
+    s = make_solver(**bench_params())
+    first = solve(s)
+    c, _ = s.maxClique(oracle.bitmap_from_edges(5, G["graph_k5_edges"]), 5)
+    assert c == [0, 1, 2, 3, 4]
+    for getter in (s.getInlierMaxClique, s.getRotationInliers, s.getTranslationInliers, s.getInlierGraphBitmap, s.getDegrees):
+        with pytest.raises(tp.TeaserHipError):
+            getter(0)
+    rng = np.random.default_rng(12)
+    x = np.concatenate([rng.normal(0.7, 0.01, size=8), rng.uniform(-5, 5, size=9)])
+    r = rng.uniform(0.01, 0.05, size=17)
+    est, mask = s.scalarTLS(x, r)
+    oe, om = oracle.scalar_tls(x, r)
+    assert abs(est - oe) < 1e-10 and (mask == om).all()
+    t = s.solveForTranslation(G["trans_v1"], G["trans_v2"])
+    ot, om = oracle.tls_translation(G["trans_v1"], G["trans_v2"], 0.01)
+    assert np.linalg.norm(t - ot) < 1e-12 and (s._last_translation["inliers"] == om).all()
+    again = solve(s)
+    assert first == fresh and again == fresh
+
+
 def test_translation_known_answer():
     s = make_solver(noise_bound=float(G["trans_noise_bound"]))
     t = s.solveForTranslation(G["trans_v1"], G["trans_v2"])
@@ -643,7 +722,8 @@ def test_mid_size_graph_cliques_vs_oracle():
     rng = np.random.default_rng(16)
     s = make_solver()
     n_exact = 0
-    for n, p in ((600, 0.12), (760, 0.10), (900, 0.08), (1020, 0.08), (1080, 0.07)):
+    # (768 and 769: the last size the all-starts greedy serves, kSmallCap, and the first it does not)
+    for n, p in ((600, 0.12), (760, 0.10), (900, 0.08), (1020, 0.08), (1080, 0.07), (768, 0.10), (769, 0.10)):
         A = np.triu(rng.uniform(size=(n, n)) < p, 1)
         members = np.sort(rng.choice(n, size=9, replace=False))  # a planted 9-clique above the random graph's 5 - 6
         A[np.ix_(members, members)] |= np.triu(np.ones((9, 9), dtype=bool), 1)
