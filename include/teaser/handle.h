@@ -49,5 +49,11 @@ struct LazyFeatures : LazyHandle<teaser_hip_features, teaser_hip_features_destro
   }
 };
 
+struct LazyPoseGraph : LazyHandle<teaser_hip_posegraph, teaser_hip_posegraph_destroy> {
+  void create(const char* who) {
+    if (!h_) created(who, "posegraph", teaser_hip_posegraph_create(/*device=*/-1, &h_));
+  }
+};
+
 }  // namespace detail
 }  // namespace teaser

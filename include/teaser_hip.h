@@ -1016,6 +1016,133 @@ TEASER_HIP_API int32_t teaser_hip_features_tuple_test_batch(teaser_hip_features*
                                                             int32_t* const* pairs /* in / out */,
                                                             int64_t* n_pairs /* in / out */);
 
+/* Pose-graph optimisation: Open3D's global_optimization with GlobalOptimizationLevenbergMarquardt (Levenberg-Marquardt
+ * with a line process on the uncertain edges, then edge pruning and a second pass) for a BATCH of graphs per call, on
+ * its OWN handle.  It consumes the 6 x 6 matrices of "Information matrices" above as edge weights.  Everything is FP64.
+ *   Data.  n node poses T_i (4 x 4 row-major, node i's frame -> the common frame); m edges (s, t, X, L, uncertain): X
+ *     aligns s to t, so a consistent graph has T_t^-1 T_s = X; L is the 6 x 6 information matrix (the upper triangle is
+ *     read and taken symmetric), rotation block first.
+ *   V(xi)    xi = (a, b, c, tx, ty, tz): R = Rz(c) Ry(b) Rx(a), translation (tx, ty, tz)
+ *   v6(M)    its inverse: sy = sqrt(M00^2 + M10^2); sy > 1e-6: a = atan2(M21, M22), b = atan2(-M20, sy),
+ *            c = atan2(M10, M00); otherwise a = atan2(-M12, M11), b = atan2(-M20, sy), c = 0; then the translation
+ *   inverse  of a pose or an edge transformation: the transpose of the rotation block and -(R^T t)
+ *   edge k   e_k = v6(X^-1 T_t^-1 T_s), r_k = e_k^T L e_k; l_k = 1 (certain) or (mu / (mu + r_k))^2 (uncertain)
+ *   F        SUM l_k r_k + SUM_uncertain mu (sqrt(l_k) - 1)^2
+ *   mu       preference_loop_closure * max_correspondence_distance^2 * mean over the pass's uncertain edges of L(5,5);
+ *            0 without uncertain edges; fixed per pass from the edges the pass starts with
+ *   Jacobian left perturbation T_i <- V(d_i) T_i: J_s[:, c] = lin6(X^-1 T_t^-1 D_c T_s), D_c the six generators of V
+ *            at 0, lin6(M) = ((M21 - M12)/2, (M02 - M20)/2, (M10 - M01)/2, M03, M13, M23); J_t = -J_s
+ *   system   A_k = l_k J^T L J (computed on its upper triangle and mirrored) goes into the blocks (s,s), (t,t) with
+ *            + and (s,t), (t,s) with -; b_k = l_k J^T L e_k into g(s) with + and g(t) with -; every entry is summed
+ *            over its edges in ascending edge index.  The reference node is held: its six unknowns are left out, so
+ *            the system has N = 6 (n - 1) unknowns.
+ *   LM loop of one pass (tau = 1e-5), in trials; T, F, H, g belong to the current poses:
+ *     start  lam = tau * max diag H, nu = 2, it = 0, lm = 0; |g|inf <= min_right_term -> stop RIGHT_TERM
+ *     trial  solve (H + lam I) d = -g by Cholesky; a pivot that is not finite or not positive -> rejected step
+ *            |d|2 <= min_relative_increment (|x|2 + min_relative_increment), x the stacked v6 of the free poses
+ *                -> stop INCREMENT
+ *            T' = V(d_i) T_i, F' = F(T'), rho = (F - F') / d^T (lam d - g)
+ *            rho > 0:  F - F' < min_relative_residual_increment F -> stop REL_RESIDUAL (the step is not taken)
+ *                      accept: lam *= max(lower_scale_factor, min(upper_scale_factor, 1 - (2 rho - 1)^3)), nu = 2,
+ *                      T = T', relinearise; |g|inf <= min_right_term -> stop RIGHT_TERM; it += 1, lm = 0;
+ *                      F < min_residual -> stop RESIDUAL; it >= max_iteration -> stop MAX_ITERATION
+ *            else      (a NaN rho and a failed factorisation too) lam *= nu, nu *= 2, lm += 1;
+ *                      lm >= max_iteration_lm -> stop MAX_ITERATION_LM
+ *   Passes.  After pass one every uncertain edge with l_k < edge_prune_threshold (l_k at the final poses) is pruned;
+ *     if any was, pass two runs from pass one's poses without them.  edge_prune_threshold = 0: one pass.
+ *   Trivial graphs.  n = 0, n = 1 or m = 0 return the input, confidence 1 and status TRIVIAL.  batch = 0 is valid.
+ * One workgroup owns a graph and runs both passes in one launch: a call waits for its stream once, whatever the batch
+ * and the number of trials.  The system is dense, which is why n is limited; more nodes need another method.
+ * TEASER_HIP_ERR_BAD_ARG (teaser_hip_posegraph_last_error names the argument and the problem index) when anything
+ * read is not finite, the last row of a pose or an edge transformation is not 0 0 0 1, an edge endpoint is out of
+ * range or source == target, reference_node >= n, a limit below is exceeded, an iteration cap is negative, or an
+ * array that is needed is NULL.  A refusal leaves every output untouched and the handle usable.  The information
+ * matrices are NOT checked for positive definiteness: an indefinite system ends as rejected trials.
+ * Results are deterministic: the same bits run to run, and for a graph alone or at any position of any batch.  A
+ * handle is not re-entrant (one call at a time; distinct handles are independent). */
+#define TEASER_HIP_POSEGRAPH_MAX_NODES 128
+#define TEASER_HIP_POSEGRAPH_MAX_EDGES 16384
+#define TEASER_HIP_POSEGRAPH_MAX_ITERATION 1000   /* max_iteration and max_iteration_lm bound one kernel's */
+#define TEASER_HIP_POSEGRAPH_MAX_ITERATION_LM 100 /* running time */
+/* Why a pass stopped (the status of the last pass run is reported). */
+#define TEASER_HIP_PG_RIGHT_TERM 0
+#define TEASER_HIP_PG_INCREMENT 1
+#define TEASER_HIP_PG_REL_RESIDUAL 2
+#define TEASER_HIP_PG_RESIDUAL 3
+#define TEASER_HIP_PG_MAX_ITERATION 4
+#define TEASER_HIP_PG_MAX_ITERATION_LM 5
+#define TEASER_HIP_PG_TRIVIAL 6
+typedef struct teaser_posegraph_option_c {
+  int32_t max_iteration;    /* 100 */
+  int32_t max_iteration_lm; /* 20 */
+  double min_relative_increment;          /* 1e-6 */
+  double min_relative_residual_increment; /* 1e-6 */
+  double min_right_term;                  /* 1e-6 */
+  double min_residual;                    /* 1e-6 */
+  double upper_scale_factor;              /* 2/3 */
+  double lower_scale_factor;              /* 1/3 */
+  double max_correspondence_distance;     /* 0.03 */
+  double edge_prune_threshold;            /* 0.25 */
+  double preference_loop_closure;         /* 1.0 */
+  int32_t reference_node;                 /* -1: node 0 */
+  int32_t reserved;
+} teaser_posegraph_option_c;
+typedef struct teaser_posegraph_result_c {
+  double F0, F;          /* the objective at the input poses (pass one's weights) and at the end of the last pass */
+  double mu[2];          /* per pass; 0 for a pass that did not run */
+  int32_t iterations[2]; /* accepted steps per pass */
+  int32_t trials[2];     /* trace rows per pass: trials that reached the gain ratio or failed to factorise */
+  int32_t status;        /* TEASER_HIP_PG_* of the last pass run */
+  int32_t n_trace;       /* rows the call produced, whether or not they fitted */
+} teaser_posegraph_result_c;
+/* One trial: lam it was solved with, the gain ratio and F' (0 when the factorisation failed), and whether the step
+ * was accepted (rho > 0).  A trial that stops with INCREMENT leaves no row. */
+typedef struct teaser_posegraph_trace_c {
+  double lam, rho, F_new;
+  int32_t pass, accepted, factorised, reserved;
+} teaser_posegraph_trace_c;
+typedef struct teaser_hip_posegraph teaser_hip_posegraph;
+/* device < 0: the current HIP device.  TEASER_HIP_ERR_NO_DEVICE without a GPU. */
+TEASER_HIP_API int32_t teaser_hip_posegraph_create(int32_t device, teaser_hip_posegraph** out);
+TEASER_HIP_API int32_t teaser_hip_posegraph_destroy(teaser_hip_posegraph* posegraph);
+TEASER_HIP_API const char* teaser_hip_posegraph_last_error(const teaser_hip_posegraph* posegraph);
+/* The defaults noted beside the fields above. */
+TEASER_HIP_API int32_t teaser_hip_posegraph_option_default(teaser_posegraph_option_c* out);
+/* `batch` graphs as concatenated arrays: n_nodes[b] and poses (16 doubles per node); n_edges[b], edge_source,
+ * edge_target (node indices within the graph), edge_transformation (16 doubles per edge), edge_information (36 per
+ * edge), edge_uncertain (one byte per edge); options: NULL for the defaults, or one record per graph.  Outputs, each
+ * laid out like its input: poses_out (16 per node; the reference node's pose is the input's, bit for bit), confidence
+ * (the final l_k; of a pruned edge its value when it was pruned), pruned (one byte per edge), results (one record per
+ * graph); confidence, pruned and results may be NULL.  trace: NULL, or room for SUM trace_cap[b] rows, graph b's rows
+ * starting at SUM_{c<b} trace_cap[c]; rows beyond a graph's capacity are dropped, results[b].n_trace counts them all. */
+TEASER_HIP_API int32_t teaser_hip_posegraph_optimize_batch(
+    teaser_hip_posegraph* posegraph, int32_t batch, const int32_t* n_nodes, const double* poses,
+    const int32_t* n_edges, const int32_t* edge_source, const int32_t* edge_target, const double* edge_transformation,
+    const double* edge_information, const uint8_t* edge_uncertain, const teaser_posegraph_option_c* options,
+    double* poses_out, double* confidence, uint8_t* pruned, teaser_posegraph_result_c* results,
+    teaser_posegraph_trace_c* trace, const int32_t* trace_cap);
+/* One graph: teaser_hip_posegraph_optimize_batch with batch = 1; trace_cap is the room of `trace` in rows. */
+TEASER_HIP_API int32_t teaser_hip_posegraph_optimize(
+    teaser_hip_posegraph* posegraph, int32_t n_nodes, const double* poses, int32_t n_edges,
+    const int32_t* edge_source, const int32_t* edge_target, const double* edge_transformation,
+    const double* edge_information, const uint8_t* edge_uncertain, const teaser_posegraph_option_c* option,
+    double* poses_out, double* confidence, uint8_t* pruned, teaser_posegraph_result_c* result,
+    teaser_posegraph_trace_c* trace, int32_t trace_cap);
+/* Stage call: the linearisation at the given poses, with pass one's mu.  Per graph, concatenated: e (6 per edge), r,
+ * l (one per edge), mu, F (one per graph), H ((6 n)^2 per graph, row-major; the reference node's rows and columns are
+ * zero and the lower triangle mirrors the upper bit for bit) and g (6 n per graph).  Any output may be NULL. */
+TEASER_HIP_API int32_t teaser_hip_posegraph_linearize_batch(
+    teaser_hip_posegraph* posegraph, int32_t batch, const int32_t* n_nodes, const double* poses,
+    const int32_t* n_edges, const int32_t* edge_source, const int32_t* edge_target, const double* edge_transformation,
+    const double* edge_information, const uint8_t* edge_uncertain, const teaser_posegraph_option_c* options,
+    double* e, double* r, double* l, double* mu, double* F, double* H, double* g);
+/* One graph: teaser_hip_posegraph_linearize_batch with batch = 1. */
+TEASER_HIP_API int32_t teaser_hip_posegraph_linearize(
+    teaser_hip_posegraph* posegraph, int32_t n_nodes, const double* poses, int32_t n_edges,
+    const int32_t* edge_source, const int32_t* edge_target, const double* edge_transformation,
+    const double* edge_information, const uint8_t* edge_uncertain, const teaser_posegraph_option_c* option,
+    double* e, double* r, double* l, double* mu, double* F, double* H, double* g);
+
 /* Page-locked host memory from the HIP runtime THIS library runs on.  teaser_hip_submit_batch(..., INPUT_HOST) moves
  * the points with one DMA copy per cloud, at PCIe speed only when the runtime knows the pages are locked.  A buffer
  * pinned by another HIP runtime instance in the same process (e.g. the one a Python framework bundles) is pageable

@@ -146,6 +146,9 @@ EXPORTED_SYMBOLS = [
     "teaser_hip_features_correspondences_batch", "teaser_hip_features_knn_batch",
     "teaser_hip_features_match_knn_batch", "teaser_hip_features_correspondences_knn_batch",
     "teaser_hip_features_tuple_test_batch",
+    "teaser_hip_posegraph_create", "teaser_hip_posegraph_destroy", "teaser_hip_posegraph_last_error",
+    "teaser_hip_posegraph_option_default", "teaser_hip_posegraph_optimize_batch", "teaser_hip_posegraph_optimize",
+    "teaser_hip_posegraph_linearize_batch", "teaser_hip_posegraph_linearize",
 ]
 
 
@@ -239,6 +242,8 @@ def lib():
     _voxel.declare(L)
     from . import features as _features
     _features.declare(L)
+    from . import posegraph as _posegraph
+    _posegraph.declare(L)
     _lib = L
     return L
 
@@ -1095,6 +1100,10 @@ from .keypoints import compute_iss_keypoints, compute_iss_keypoints_batch  # noq
 from .features import (compute_fpfh_batch, correspondences_batch, match_features_batch,  # noqa: E402
                        knn_features, knn_features_batch, match_features_knn, match_features_knn_batch,
                        correspondences_knn, correspondences_knn_batch, tuple_test_batch)
+from .posegraph import (PoseGraph, PoseGraphNode, PoseGraphEdge, GlobalOptimizationOption,  # noqa: E402
+                        GlobalOptimizationConvergenceCriteria, GlobalOptimizationLevenbergMarquardt,
+                        GlobalOptimizationGaussNewton, PoseGraphOptimizationResult, global_optimization,
+                        global_optimization_batch, linearize_pose_graph)
 
 __all__ = ["batched", "FPFHEstimation", "Matcher", "MultiDeviceSolver", "RobustRegistrationSolver", "RegistrationSolution", "RotationEstimationAlgorithm",
            "InlierSelectionMode", "InlierGraphFormulation", "TeaserHipError", "synth_problem",
@@ -1112,4 +1121,8 @@ __all__ = ["batched", "FPFHEstimation", "Matcher", "MultiDeviceSolver", "RobustR
            "get_information_matrix_from_point_clouds_batch",
            "remove_statistical_outlier", "remove_statistical_outlier_batch", "remove_radius_outlier",
            "remove_radius_outlier_batch", "self_knn", "self_knn_batch", "get_icp_option", "set_icp_option",
-           "compute_iss_keypoints", "compute_iss_keypoints_batch"]
+           "compute_iss_keypoints", "compute_iss_keypoints_batch",
+           "PoseGraph", "PoseGraphNode", "PoseGraphEdge", "GlobalOptimizationOption",
+           "GlobalOptimizationConvergenceCriteria", "GlobalOptimizationLevenbergMarquardt",
+           "GlobalOptimizationGaussNewton", "PoseGraphOptimizationResult", "global_optimization",
+           "global_optimization_batch", "linearize_pose_graph"]

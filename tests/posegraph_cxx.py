@@ -1,0 +1,18 @@
+"""Builds tests/cxx/posegraph_example.cpp against libteaser_hip.so (as tests/information_cxx.py builds its example)."""
+import os
+import subprocess
+
+from util import ROOT
+
+SRC = os.path.join(ROOT, "tests", "cxx", "posegraph_example.cpp")
+EXE = os.path.join(ROOT, "tests", "cxx", "posegraph_example")
+LIBDIR = os.path.join(ROOT, "teaser-plusplus_amd")
+
+
+def build_posegraph_example():
+    if not os.path.exists(os.path.join(LIBDIR, "libteaser_hip.so")):
+        raise RuntimeError("libteaser_hip.so is not built: run __graft_entry__.build() first")
+    subprocess.check_call(["g++", "-std=c++17", "-O1", "-Wall", "-Werror", "-I" + os.path.join(ROOT, "include"), SRC,
+                           "-o", EXE, "-L" + LIBDIR, "-lteaser_hip", "-Wl,-rpath," + LIBDIR,
+                           "-Wl,-rpath,/opt/rocm/lib"])
+    return EXE
