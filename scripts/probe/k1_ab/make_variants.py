@@ -11,10 +11,11 @@ behind an opaque use (empty graph, no worklist overflow, no fallback: the events
   load32    buffer_load_dword instead of dwordx4 (same instruction count, a quarter of the bytes)
   ldsload   the loop's operands come from LDS (ds_read_b128 of a constant buffer) instead of global memory
   touch     (correct results) one extra dword load per 64-byte line of the half tile after the next, as a prefetch
-  seq3/seq4 (correct results) ONE accumulator set live at a time (row half 0: 4 MFMAs + epilogue, then row half 1 with the
+  seq3/seq4 (correct results) ONE accumulator set live at a time (row half 0: 3 MFMAs + epilogue, then row half 1 with the
             next half tile's loads behind its MFMAs) at 3 / 4 waves per SIMD: 151 VGPRs / 128 with no scratch access in
             the steady-state loop.  Round 6: 0.606 - 0.612 ms alone against 0.596 - 0.611 for the product (two sets,
-            168 VGPRs, 3 waves): the fourth wave buys nothing (profiles/r6b/k1_sequential_accumulators.txt)
+            168 VGPRs, 3 waves): the fourth wave buys nothing (profiles/r6b/k1_sequential_accumulators.txt; the
+            figures of that round are the bf16 formulation's: four MFMAs per quarter tile)
 usage: make_variants.py [name ...]   then  bash scripts/probe/k1_ab/build.sh <name> ...   (see README.md)"""
 import os
 import sys
@@ -22,7 +23,7 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 SRC = open(os.path.join(ROOT, "teaser-plusplus_amd", "csrc", "kernels_graph.hip")).read()
 OUT = os.path.join(ROOT, "gpurun_ab")
-LOADS = ["      bX[%d] = load_op(Jn, 1, gn, %d);" % (m, m) for m in range(3)]  # the three column operands of the next half tile
+LOADS = ["      bX[%d] = load_op(Jn, 1, gn, %d);" % (m, m) for m in range(2)]  # the two column operands of the next half tile
 EPI = "      for (int rt = 0; rt < 2; ++rt) tr[ct][rt] = epi(acc[rt], DIAG && ct == rt);"
 
 
@@ -32,7 +33,7 @@ def once(s, old, new):
 
 
 def each_load(bd, f):
-    """replace the three operand-load lines of the flat body: f(m) -> replacement line"""
+    """replace the two operand-load lines of the flat body: f(m) -> replacement line"""
     for m, l in enumerate(LOADS):
         bd = once(bd, l, f(m))
     return bd
@@ -60,7 +61,7 @@ def in_body(s, f):
 
 
 def no_mfma(bd, keep=lambda l: False):
-    out = [l for l in bd.split("\n") if not ("__builtin_amdgcn_mfma_f32_32x32x16_bf16" in l and "acc[" in l) or keep(l)]
+    out = [l for l in bd.split("\n") if not ("__builtin_amdgcn_mfma_f32_32x32x16_f16" in l and "acc[" in l) or keep(l)]
     return "\n".join(out)
 
 
@@ -70,21 +71,18 @@ SEQ_BODY = '''  auto body_flat = [&](const int J, auto diag_tag) {
     unsigned int tr[2][2];  // [ct][rt]: this lane's 16 column bits
 #pragma unroll
     for (int ct = 0; ct < 2; ++ct) {
-      const bf16x8 b0 = __builtin_bit_cast(bf16x8, bX[0]), b1 = __builtin_bit_cast(bf16x8, bX[1]);
-      const bf16x8 b2 = __builtin_bit_cast(bf16x8, bX[2]);
+      const f16x8 b0 = __builtin_bit_cast(f16x8, bX[0]), b1 = __builtin_bit_cast(f16x8, bX[1]);
       const int Jn = (ct == 0 || J + 1 >= Jend) ? J : J + 1, gn = ct ^ 1;
       f32x16 z;
       for (int k = 0; k < 16; ++k) z[k] = 0.f;
       {
         Acc acc;
         __builtin_amdgcn_s_setprio(2);
-        acc.U = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ar[0][0], b0, z, 0, 0, 0);
+        acc.U = __builtin_amdgcn_mfma_f32_32x32x16_f16(ar[0][0], b0, z, 0, 0, 0);
         __builtin_amdgcn_sched_barrier(0);
-        acc.W = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ar[0][3], b0, z, 0, 0, 0);
+        acc.W = __builtin_amdgcn_mfma_f32_32x32x16_f16(ar[0][2], b0, z, 0, 0, 0);
         __builtin_amdgcn_sched_barrier(0);
-        acc.U = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ar[0][1], b1, acc.U, 0, 0, 0);
-        __builtin_amdgcn_sched_barrier(0);
-        acc.U = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ar[0][2], b2, acc.U, 0, 0, 0);
+        acc.U = __builtin_amdgcn_mfma_f32_32x32x16_f16(ar[0][1], b1, acc.U, 0, 0, 0);
         __builtin_amdgcn_s_setprio(0);
         __builtin_amdgcn_sched_barrier(0);
         tr[ct][0] = epi(acc, DIAG && ct == 0);
@@ -93,19 +91,15 @@ SEQ_BODY = '''  auto body_flat = [&](const int J, auto diag_tag) {
       {
         Acc acc;
         __builtin_amdgcn_s_setprio(2);
-        acc.U = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ar[1][0], b0, z, 0, 0, 0);
+        acc.U = __builtin_amdgcn_mfma_f32_32x32x16_f16(ar[1][0], b0, z, 0, 0, 0);
         __builtin_amdgcn_sched_barrier(0);
-        acc.W = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ar[1][3], b0, z, 0, 0, 0);
+        acc.W = __builtin_amdgcn_mfma_f32_32x32x16_f16(ar[1][2], b0, z, 0, 0, 0);
         __builtin_amdgcn_sched_barrier(0);
         bX[0] = load_op(Jn, 1, gn, 0);
         __builtin_amdgcn_sched_barrier(0);
-        acc.U = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ar[1][1], b1, acc.U, 0, 0, 0);
+        acc.U = __builtin_amdgcn_mfma_f32_32x32x16_f16(ar[1][1], b1, acc.U, 0, 0, 0);
         __builtin_amdgcn_sched_barrier(0);
         bX[1] = load_op(Jn, 1, gn, 1);
-        __builtin_amdgcn_sched_barrier(0);
-        acc.U = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ar[1][2], b2, acc.U, 0, 0, 0);
-        __builtin_amdgcn_sched_barrier(0);
-        bX[2] = load_op(Jn, 1, gn, 2);
         __builtin_amdgcn_s_setprio(0);
         __builtin_amdgcn_sched_barrier(0);
         tr[ct][1] = epi(acc, DIAG && ct == 1);
@@ -127,8 +121,8 @@ VARIANTS = {
     "seq4": lambda: sequential(4),
     "zero": lambda: zeroed(SRC),
     "nomfma": lambda: in_body(zeroed(SRC), lambda bd: once(no_mfma(bd), LOADS[0],
-        '      asm volatile("" : "=v"(acc[0].U), "=v"(acc[0].W), "=v"(acc[1].U), "=v"(acc[1].W) : "v"(b0), "v"(b1), "v"(b2));\n' + LOADS[0])),
-    "halfmfma": lambda: in_body(zeroed(SRC), lambda bd: no_mfma(bd, keep=lambda l: not ("b1, acc" in l or "b2, acc" in l))),
+        '      asm volatile("" : "=v"(acc[0].U), "=v"(acc[0].W), "=v"(acc[1].U), "=v"(acc[1].W) : "v"(b0), "v"(b1));\n' + LOADS[0])),
+    "halfmfma": lambda: in_body(zeroed(SRC), lambda bd: no_mfma(bd, keep=lambda l: "b1, acc" not in l)),
     "noepi": lambda: in_body(zeroed(SRC), lambda bd: once(bd, EPI,
         '      for (int rt = 0; rt < 2; ++rt) { asm volatile("" :: "v"(acc[rt].U), "v"(acc[rt].W)); tr[ct][rt] = (unsigned int)lane * 2654435761u + J; }')),
     "nofinish": lambda: in_body(zeroed(SRC), lambda bd: once(bd, "    finish_tile(J, DIAG, tr);",
@@ -142,7 +136,7 @@ VARIANTS = {
         "      (void)Jn; bX[%d] = lds_b[(2 * J + gn) & 1][%d][lane];" % (m, m))),
         "  uint4 bX[kTimColOperands], bY[kTimColOperands];",
         "  __shared__ uint4 lds_b[2][4][64];\n  lds_b[0][wave][lane] = make_uint4(lane, wave, 1, 2); lds_b[1][wave][lane] = make_uint4(wave, lane, 3, 4);\n  __syncthreads();\n  uint4 bX[kTimColOperands], bY[kTimColOperands];"),
-    "touch": lambda: once(once(in_body(SRC, lambda bd: once(bd, LOADS[2], LOADS[2] + """
+    "touch": lambda: once(once(in_body(SRC, lambda bd: once(bd, LOADS[1], LOADS[1] + """
       {
         const int half2 = 2 * J + ct + 2, J2 = min(half2 >> 1, Jend - 1), g2 = half2 & 1;
         asm volatile("" :: "v"(touch[ct]));

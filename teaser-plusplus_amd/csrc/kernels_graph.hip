@@ -17,6 +17,7 @@
 #include <cstdlib>
 
 #include "internal.h"
+#include "k1_consts.h"
 #include "wave_utils.h"
 
 namespace thip {
@@ -273,11 +274,11 @@ __global__ __launch_bounds__(256) void tim_graph_kernel(const ProbDesc* __restri
 // matrix pipe for a 32 x 32 tile of pairs at a time; the f32 result is a FILTER whose sign is trusted only outside
 // a rigorous error band, everything inside the band is re-evaluated with the reference expression in FP64
 // (tim_fixup_group_kernel), so the bitmap stays bit-identical to the oracle.  Points are centred (and scaled) per
-// problem and rounded to f32 by the pre-pass; every f32 operand is split EXACTLY into three bf16 pieces
-// (x = x_h + x_m + x_l, 8 + 8 + 8 significant bits) and the products that matter are laid out along K; every
-// bf16 x bf16 product is exact in f32, only the accumulation rounds (hardware model: every internal addition errs
-// by at most one f32 ulp of the sum of |terms|; scripts/probe/mfma_bf16_error.hip measures <= 4.9 u per
-// instruction).  Geometry the filter cannot resolve (beta tiny or huge against the cloud, non-finite input)
+// problem and rounded to f32 by the pre-pass; every f32 coordinate is split into two fp16 pieces (x = x_h + x_m
+// to 2^-22 relative, 11 + 11 significant bits) and the products that matter are laid out along K; every
+// fp16 x fp16 product is exact in f32, only the accumulation rounds (hardware model: every internal addition errs
+// by at most one f32 ulp of the sum of |terms|; scripts/probe/mfma_f16_error.hip measures the instruction's own
+// figure).  Geometry the filter cannot resolve (beta tiny or huge against the cloud, non-finite input)
 // => that problem runs the FP64 body (tim_wave_fp64) instead, chosen per problem on the device; n > 65536 (16-bit
 // worklist indices) => the host launches tim_graph_kernel<0>.
 // Two earlier formulations (A, B from the matrix pipe; u / w with a per-value band) are archived, not compiled:
@@ -285,7 +286,7 @@ __global__ __launch_bounds__(256) void tim_graph_kernel(const ProbDesc* __restri
 // ==========================================================================================
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
 
 struct TimPrep {         // per problem, zeroed then filled by the pre-pass
@@ -347,19 +348,6 @@ __global__ __launch_bounds__(256) void tim_prep_bbox_kernel(const ProbDesc* __re
   }
 }
 
-// exact three-way bf16 split of an f32: v = h + m + l + r, |r| <= 2^-27 |v| (each step rounds to
-// nearest even on the upper 16 bits; the differences are exact in f32)
-__device__ __forceinline__ unsigned int bf16_rne(float v) {
-  const unsigned int b = __float_as_uint(v);
-  return (b + 0x7fffu + ((b >> 16) & 1u)) >> 16;
-}
-__device__ __forceinline__ void bf16_split3(float v, unsigned int* h, unsigned int* m, unsigned int* l) {
-  *h = bf16_rne(v);
-  const float r1 = v - __uint_as_float(*h << 16);
-  *m = bf16_rne(r1);
-  const float r2 = r1 - __uint_as_float(*m << 16);
-  *l = bf16_rne(r2);
-}
 // (a & m) | (b & ~m) as ONE v_bfi / v_bitop3
 __device__ __forceinline__ unsigned int bit_select(unsigned int m, unsigned int a, unsigned int b) {
   return __builtin_amdgcn_bitop3_b32(m, a, b, 0xCA);  // (written with & | ^ the compiler re-associates three selects into nine instructions)
@@ -394,71 +382,60 @@ constexpr int kRegionItems = kRegionWords - 1;
 // With A = |s_j - s_i|^2 (src), B = |d_j - d_i|^2 (dst):   | sqrt A - sqrt B | <= beta
 //   <=>  sqrt A + sqrt B <= beta   or   d := u^2 + w <= 0,   u = B - A - beta^2,  w = -4 beta^2 A
 // (d = (x^2 - beta^2)(S^2 - beta^2) with x = sqrt B - sqrt A, S = sqrt A + sqrt B).  Both u and w are LINEAR in
-// the Gram terms, so they come straight out of the matrix pipe: u over 42 K slots (18 + 18 coordinate products of
-// the exact three-way bf16 split, 6 for the per-point constants m_i - n_i - beta^2 and m_j - n_j) = three chained
-// v_mfma_f32_32x32x16_bf16, w over 13 slots (two-piece operands: w is multiplied by nothing and only needs
-// ~1e-4 relative accuracy) = one more -- four MFMAs per 32 x 32 tile.  The points are centred AND scaled per
-// problem by g in (1, sqrt 2] such that 4 (g beta)^2 is a power of two: the factor of w is then an exponent shift
-// of the column operands, exact.  mfma2_consts below is the per-VALUE band K2 |w| + K0 of an earlier epilogue (two
-// band edges per value); the product's kernel uses the constant band of mfma3_consts, which builds on it (the
-// admission test, G, and K0 >= 4 beta^4: every short pair -- S <= beta: A, B <= beta^2, |d| <= 4 beta^4 -- lies
-// inside the band by construction, so the `S <= beta` branch needs no test of its own).
-//
-// Error budget in the scaled system (u = 2^-24, R = max |scaled centred point|, beta = g beta_0):
-//   eps_u = kEpsU2 u R^2 bounds |u~ - u*|: f32 rounding of the scaled centred coordinates 16 u R^2 (8 per cloud),
-//     rounding of the per-point constants 2, split residuals / dropped products 2, accumulation: 3 x 16 products
-//     + 3 accumulator adds = 51 additions, each erring by at most one f32 ulp (2u) of a magnitude <= the sum of
-//     |terms| <= 6 R^2 + beta^2 <= 6.17 R^2 (beta <= R/ 2.4 is required) => 629; total 649 -> kEpsU2 = 680;
-//   eps_A = kEpsA2 u R^2 bounds |A~ - A*| inside w: coordinates 8, dropped low pieces of the norms 256, dropped
-//     products (m m', h l', l h', ...) 820, accumulation 17 x 2u x 4 R^2 = 136; total 1220 -> kEpsA2 = 1300;
-//   with lam = 2 beta R, eta = eps_u / lam:  |d~ - d*| <= [ (eta + u) |d~| + eta |w~| + K0' ] / (1 - eta),
-//     K0' = eps_u lam + eps_u^2 + kappa eps_A (1 + eta) (kappa = 4 beta^2), so sign(d~) is trusted iff
-//     |d~| > K2 |w~| + K0,  K2 = eta / (1 - 2 eta - 2u),  K0 = (K0' + G) / (1 - 2 eta - 2u) + 2 K2 kappa eps_A
-//     (G: the gap between the reference's rounded double predicate and the exact one), both x 1.001 and
-//     rounded outwards;
+// the Gram terms, so they come straight out of the matrix pipe.  The operands are fp16: 11 significant bits, so TWO
+// round-to-nearest pieces h + m carry an f32 coordinate to 2^-22 relative and only the products h h', h m', m h' are
+// needed -- u over 30 K slots (9 + 9 coordinate products, 6 for the per-point constants m_i - n_i - beta^2 and
+// m_j - n_j in three exact pieces each) = two chained v_mfma_f32_32x32x16_f16, w over 15 slots of the chain's FIRST
+// column operand = one more -- three MFMAs per 32 x 32 tile and two 1-KB column-operand loads per half tile.  (The
+// bf16 formulation this replaces -- three pieces, six products per coordinate, four MFMAs, three loads -- is
+// archived: scripts/probe/experiments/k1_bf16_three_piece.patch.)
+// The points are centred and scaled per problem by g 2^s: g in (1, sqrt 2] such that kappa = 4 (g beta)^2 is a power
+// of two -- the factor of w is then an exponent shift of the row operands, exact -- and 2^s (k1c::norm_shift, from
+// the bounding boxes) such that the largest half extent lies in [16, 32): fp16 has 5 exponent bits, and in this
+// window every piece stays below 65504 (squared norms <= 8192) while the low pieces keep the precision the budget
+// assumes (a piece below 2^-14 is subnormal and rounds to a multiple of 2^-24: an ABSOLUTE error with its own term).
+// What the window cannot hold -- kappa R > 60000, kappa outside [2^-24, 2^15], R^2 > 8192 -- fails the admission
+// test and runs the FP64 body.  The error budget (eps_u = 500 u R^2 + u (12.1 R + 1), eps_w = kappa 200 u R^2 + ...),
+// the band constants and the admission test are in k1_consts.h, term by term; host programs evaluate the same code.
+//   per-value band (admission only): with lam = 2 beta R, eta = eps_u / lam:
+//     |d~ - d*| <= [ (eta + u) |d~| + eta |w~| + K0' ] / (1 - eta), K0' = eps_u lam + eps_u^2 + eps_w (1 + eta);
 //   short pairs: S <= beta implies A, B <= beta^2, hence u* in [-2 beta^2, 0], w* in [-4 beta^4, 0] and |d*| <= 4 beta^4;
-//     K0 >= short_d (mfma2_consts: that bound plus the error terms) keeps |d~| <= band for all of them: they go to
-//     the fix-up individually, where the reference expression decides.
-// eta > 1/8, beta > R / 2.4, non-finite input, R^2 or beta^2 out of range => the problem runs the FP64 body.
+//     the band is at least that bound plus the error terms: they go to the fix-up, where the reference expression decides.
 // ==========================================================================================
-constexpr float kEpsU2 = 680.0f;
-constexpr float kEpsA2 = 1300.0f;
 
 // Packed operands of one 64-point tile (tile t of a problem = points 64 t .. 64 t + 63, padded with copies of the
-// problem's last point; tiles are indexed like the bitmap's row words, ProbDesc.w_off + t): 224 B per
-// correspondence.  Laid out so that the 64 lanes of a wave -- lane = (h, c), c = point within a 32-point group,
-// lane half h holding K slots 8h..8h+7 -- load 1 KB of CONSECUTIVE memory per MFMA operand:
+// problem's last point; tiles are indexed like the bitmap's row words, ProbDesc.w_off + t): 160 B per
+// correspondence, 10 KB per tile.  Laid out so that the 64 lanes of a wave -- lane = (h, c), c = point within a
+// 32-point group, lane half h holding K slots 8h..8h+7 -- load 1 KB of CONSECUTIVE memory per MFMA operand:
 // [32-point group][MFMA][h][c].  (A first layout with 128 B per point made every such load touch 32 separate
 // 128-B lines: the vector L1 was the kernel's hidden bottleneck.)
 struct TimOperandTile2 {
-  uint4 a[2][4][2][32];  // row side: the u chain's three operands, then the w MFMA's
-  uint4 b[2][3][2][32];  // column side: three operands -- the w MFMA multiplies the u chain's FIRST one again (below)
+  uint4 a[2][3][2][32];  // row side: the u chain's two operands, then the w MFMA's
+  uint4 b[2][2][2][32];  // column side: two operands -- the w MFMA multiplies the u chain's FIRST one again (below)
 };
-constexpr int kTimColOperands = 3;
+constexpr int kTimColOperands = 2;
+constexpr int kTimRowOperands = 3;
 
-// scale g and kappa = 4 (g beta)^2 = 2^kexp (the smallest power of two above 4 beta^2)
-__device__ __forceinline__ double pow2_d(int e) {  // 2^e for -1022 <= e <= 1023
-  return __longlong_as_double((long long)(e + 1023) << 52);
+// fp16 bits of v, round to nearest even, subnormals kept (v_cvt_f16_f32 under the kernel's default denormal mode)
+__device__ __forceinline__ unsigned short f16_bits(float v) { return __builtin_bit_cast(unsigned short, (_Float16)v); }
+__device__ __forceinline__ float f16_value(unsigned short b) { return (float)__builtin_bit_cast(_Float16, b); }
+// two / three fp16 pieces of an f32: v = h + m (+ l) + r.  Two pieces: |r| <= max(2^-22 |v|, 2^-25); three: r = 0
+// for |v| >= 1/2 and |r| <= 2^-25 below (the differences are exact in f32)
+__device__ __forceinline__ void f16_split3(float v, float* h, float* m, float* l) {
+  *h = f16_value(f16_bits(v));
+  const float r1 = v - *h;
+  *m = f16_value(f16_bits(r1));
+  *l = f16_value(f16_bits(r1 - *m));
 }
-__device__ __forceinline__ void tim2_scale(double beta_d, double* g, int* kexp) {
-  const double x = 4.0 * beta_d * beta_d;
-  int e = 0;
-  const bool ok = x > 1e-300 && x < 1e300;
-  if (ok) e = (int)((__double_as_longlong(x) >> 52) & 0x7ff) - 1023 + 1;  // floor(log2 x) + 1
-  *kexp = e;
-  *g = ok ? __builtin_sqrt(pow2_d(e) / x) : 1.0;
-}
-
-// bf16 bits of +-(value * 2^j) (exact; underflow flushes to zero, which the error band absorbs: such pieces are
-// below 2^-126)
-__device__ __forceinline__ unsigned int bf16_mul_pow2(unsigned int b, int j, bool negate) {
-  const unsigned int mag = b & 0x7fffu;
-  int e = (int)(mag >> 7);
-  if (e == 0) return 0u;
-  e += j;
-  if (e <= 0) return 0u;
-  if (e > 254) e = 254;  // (excluded by the range checks of mfma2_consts)
-  return (mag & 0x7fu) | ((unsigned int)e << 7) | ((b & 0x8000u) ^ (negate ? 0x8000u : 0u));
+// largest half extent of the two clouds' f32 bounding boxes
+__device__ __forceinline__ double prep_half_extent(const TimPrep* pr) {
+  double H = 0.0;
+  for (int k = 0; k < 6; ++k) {
+    const float hi = f32_unkey(pr->hi[k]), lo = f32_unkey(~pr->lo[k]);
+    const double e = 0.5 * ((double)hi - (double)lo);
+    H = e > H ? e : H;  // (NaN never enters)
+  }
+  return H;
 }
 
 __global__ __launch_bounds__(256) void tim_prep_pack2_kernel(const ProbDesc* __restrict__ descs,
@@ -473,9 +450,12 @@ __global__ __launch_bounds__(256) void tim_prep_pack2_kernel(const ProbDesc* __r
   if (ip < d.W * 64 && d.n > 0) {
     double g;
     int kexp;
-    tim2_scale(beta, &g, &kexp);
+    k1c::scale(beta, &g, &kexp);
     const int i = min(ip, d.n - 1);
     const TimPrep* pr = prep + blockIdx.y;
+    const int sh = k1c::norm_shift(prep_half_extent(pr));
+    kexp += 2 * sh;  // kappa of the normalised system
+    g *= k1c::pow2_d(sh);
     const double* a = src + 3 * (d.pt_off + i);
     const double* b = dst + 3 * (d.pt_off + i);
     const float sx = (float)((a[0] - prep_centre(pr, 0, 0)) * g), sy = (float)((a[1] - prep_centre(pr, 0, 1)) * g),
@@ -486,64 +466,59 @@ __global__ __launch_bounds__(256) void tim_prep_pack2_kernel(const ProbDesc* __r
     const double na_d = ((double)sx * sx + (double)sy * sy) + (double)sz * sz;
     const double nb_d = ((double)dx * dx + (double)dy * dy) + (double)dz * dz;
     const float na = (float)na_d, nb = (float)nb_d;
-    const double beta2s = pow2_d(kexp - 2);  // (g beta)^2 = kappa / 4, exact
+    const double beta2s = k1c::pow2_d(kexp - 2);  // (normalised beta)^2 = kappa / 4, exact
+    const float kappa = (float)k1c::pow2_d(kexp);
     const float delta_row = (float)(nb_d - na_d - beta2s);  // m_i - n_i - beta^2 (this point as a ROW)
     const float delta_col = (float)(nb_d - na_d);           // m_j - n_j          (this point as a COLUMN)
-    // K slots.  Column side B[0..47] = the three operands of the u chain; row side A[0..47] the u chain's, A[48..63]
+    // K slots.  Column side B[0..31] = the two operands of the u chain; row side A[0..31] the u chain's, A[32..47]
     // the w MFMA's, which runs over the FIRST column operand B[0..15] again: that operand holds exactly what w needs
-    // from a column point -- the (h, m, h) pieces of the src coordinates, its squared-norm pieces and `one` -- and every
-    // factor that is w's alone (kappa, the row's own norm) sits on the row side, which stays in registers.  One
-    // operand load in four is gone from the column-tile loop, whose load instructions are what bounds the kernel.
-    //   slot  B (column j)                         A, u chain (row i)        A, w (row i)
-    //   3c+0  2 h(s_c)                             h(s_c)                    kappa h(s_c)
-    //   3c+1  2 m(s_c)                             h(s_c)                    kappa h(s_c)
-    //   3c+2  2 h(s_c)                             m(s_c)                    kappa m(s_c)          c = 0, 1, 2
-    //   9,10  -h(n_j), -m(n_j)                     0                         kappa
-    //   11-13 1                                    h, m, l (m_i - n_i - b^2)  -kappa h(n_i), -kappa m(n_i), 0
-    //   16+3c 2 l(s_c), 2 h(s_c), 2 m(s_c)         h, l, m (s_c)                                    (second operand)
-    //   25-27 h, m, l (m_j - n_j)                  1
-    //   28..  the dst coordinates' six products each, negated: (h,h,m,h,l,m) x -2 (h,m,h,l,h,m), 18 slots up to 45
-    unsigned short A[64], B[48];
-    for (int k = 0; k < 64; ++k) A[k] = 0;
-    for (int k = 0; k < 48; ++k) B[k] = 0;
+    // from a column point -- the (h, m, h) pieces of the src coordinates, its squared-norm pieces and kappa -- and
+    // every other factor that is w's alone sits on the row side, which stays in registers.
+    //   slot   B (column j)                        A, u chain (row i)         A, w (row i)
+    //   3c+0   2 h(s_c)                            h(s_c)                     kappa h(s_c)
+    //   3c+1   2 m(s_c)                            h(s_c)                     kappa h(s_c)
+    //   3c+2   2 h(s_c)                            m(s_c)                     kappa m(s_c)          c = 0, 1, 2
+    //   9,10   -h(n_j), -m(n_j)                    0                          kappa
+    //   11-13  1                                   h, m, l (m_i - n_i - b^2)  0
+    //   14,15  kappa                               0                          -h(n_i), -m(n_i)
+    //   16+3c  -2 h(d_c), -2 m(d_c), -2 h(d_c)     h, h, m (d_c)                                     (second operand)
+    //   25-27  h, m, l (m_j - n_j)                 1
+    // (kappa h etc. are rounded to fp16 once more only where they are subnormal: below 2^-14; kappa as a column
+    // slot is exact for 2^-24 <= kappa <= 2^15, which the admission test requires)
+    unsigned short A[48], B[32];
+    for (int k = 0; k < 48; ++k) A[k] = 0;
+    for (int k = 0; k < 32; ++k) B[k] = 0;
     const float cs[3] = {sx, sy, sz}, cd[3] = {dx, dy, dz};
-    const unsigned short one = 0x3f80;
-    unsigned int h, m, l;
+    const unsigned short one = 0x3c00;
+    float h, m, l;
     for (int c = 0; c < 3; ++c) {
-      bf16_split3(cs[c], &h, &m, &l);  // -A contributes +2 s.s'
-      const unsigned short h2 = (unsigned short)bf16_mul_pow2(h, 1, false), m2 = (unsigned short)bf16_mul_pow2(m, 1, false),
-                           l2 = (unsigned short)bf16_mul_pow2(l, 1, false);
-      B[3 * c] = h2; B[3 * c + 1] = m2; B[3 * c + 2] = h2;
-      A[3 * c] = h; A[3 * c + 1] = h; A[3 * c + 2] = m;
-      // w = -kappa n_i - kappa n_j + 2 kappa s.s': products (h,h') (h,m') (m,h'), kappa = 2^kexp on the row side
-      A[48 + 3 * c] = (unsigned short)bf16_mul_pow2(h, kexp, false); A[48 + 3 * c + 1] = A[48 + 3 * c];
-      A[48 + 3 * c + 2] = (unsigned short)bf16_mul_pow2(m, kexp, false);
-      B[16 + 3 * c] = l2; B[16 + 3 * c + 1] = h2; B[16 + 3 * c + 2] = m2;
-      A[16 + 3 * c] = h; A[16 + 3 * c + 1] = l; A[16 + 3 * c + 2] = m;
-      bf16_split3(cd[c], &h, &m, &l);  // +B contributes -2 d.d'
-      unsigned short* ua = A + 28 + 6 * c;
-      unsigned short* ub = B + 28 + 6 * c;
-      ua[0] = h; ua[1] = h; ua[2] = m; ua[3] = h; ua[4] = l; ua[5] = m;
-      ub[0] = bf16_mul_pow2(h, 1, true); ub[1] = bf16_mul_pow2(m, 1, true); ub[2] = ub[0];
-      ub[3] = bf16_mul_pow2(l, 1, true); ub[4] = ub[0]; ub[5] = ub[1];
+      f16_split3(cs[c], &h, &m, &l);  // -A contributes +2 s.s'
+      B[3 * c] = f16_bits(2.0f * h); B[3 * c + 1] = f16_bits(2.0f * m); B[3 * c + 2] = B[3 * c];
+      A[3 * c] = f16_bits(h); A[3 * c + 1] = A[3 * c]; A[3 * c + 2] = f16_bits(m);
+      // w = -kappa n_i - kappa n_j + 2 kappa s.s': products (h,h') (h,m') (m,h'), kappa on the row side
+      A[32 + 3 * c] = f16_bits(kappa * h); A[32 + 3 * c + 1] = A[32 + 3 * c]; A[32 + 3 * c + 2] = f16_bits(kappa * m);
+      f16_split3(cd[c], &h, &m, &l);  // +B contributes -2 d.d'
+      B[16 + 3 * c] = f16_bits(-2.0f * h); B[16 + 3 * c + 1] = f16_bits(-2.0f * m); B[16 + 3 * c + 2] = B[16 + 3 * c];
+      A[16 + 3 * c] = f16_bits(h); A[16 + 3 * c + 1] = A[16 + 3 * c]; A[16 + 3 * c + 2] = f16_bits(m);
     }
-    bf16_split3(na, &h, &m, &l);
-    B[9] = (unsigned short)bf16_mul_pow2(h, 0, true); B[10] = (unsigned short)bf16_mul_pow2(m, 0, true);  // -n_j
-    A[48 + 9] = (unsigned short)bf16_mul_pow2(one, kexp, false); A[48 + 10] = A[48 + 9];                    // kappa
+    f16_split3(na, &h, &m, &l);
+    B[9] = f16_bits(-h); B[10] = f16_bits(-m);      // -n_j
+    A[32 + 9] = f16_bits(kappa); A[32 + 10] = A[32 + 9];
     B[11] = one; B[12] = one; B[13] = one;
-    A[48 + 11] = (unsigned short)bf16_mul_pow2(h, kexp, true); A[48 + 12] = (unsigned short)bf16_mul_pow2(m, kexp, true);  // -kappa n_i
-    bf16_split3(delta_row, &h, &m, &l);
-    A[11] = h; A[12] = m; A[13] = l;
-    bf16_split3(delta_col, &h, &m, &l);
-    A[25] = one; A[26] = one; A[27] = one; B[25] = h; B[26] = m; B[27] = l;
+    B[14] = f16_bits(kappa); B[15] = B[14];
+    A[32 + 14] = f16_bits(-h); A[32 + 15] = f16_bits(-m);  // -n_i (times the column's kappa)
+    f16_split3(delta_row, &h, &m, &l);
+    A[11] = f16_bits(h); A[12] = f16_bits(m); A[13] = f16_bits(l);
+    f16_split3(delta_col, &h, &m, &l);
+    A[25] = one; A[26] = one; A[27] = one; B[25] = f16_bits(h); B[26] = f16_bits(m); B[27] = f16_bits(l);
     TimOperandTile2* tile = ops + d.w_off + (ip >> 6);
     const int gq = (ip >> 5) & 1, cc = ip & 31;
-    for (int mf = 0; mf < 4; ++mf)
+    for (int mf = 0; mf < kTimRowOperands; ++mf)
       for (int hh = 0; hh < 2; ++hh) {
         const unsigned short* pa = A + 16 * mf + 8 * hh;
         tile->a[gq][mf][hh][cc] = make_uint4(pa[0] | ((unsigned int)pa[1] << 16), pa[2] | ((unsigned int)pa[3] << 16),
                                              pa[4] | ((unsigned int)pa[5] << 16), pa[6] | ((unsigned int)pa[7] << 16));
-        if (mf == kTimColOperands) continue;
+        if (mf >= kTimColOperands) continue;
         const unsigned short* pb = B + 16 * mf + 8 * hh;
         tile->b[gq][mf][hh][cc] = make_uint4(pb[0] | ((unsigned int)pb[1] << 16), pb[2] | ((unsigned int)pb[3] << 16),
                                              pb[4] | ((unsigned int)pb[5] << 16), pb[6] | ((unsigned int)pb[7] << 16));
@@ -557,53 +532,6 @@ __global__ __launch_bounds__(256) void tim_prep_pack2_kernel(const ProbDesc* __r
     mx = t > mx ? t : mx;
   }
   if ((threadIdx.x & 63) == 0 && mx > 0.f) atomicMax(&prep[blockIdx.y].r2_bits, __float_as_uint(mx));
-}
-
-struct Mfma2Const {
-  float K2, K0, K0k, wtau, utau;  // K0k: K0 as used by the cold path's fused form (a hair wider)
-  int use_mfma;
-};
-
-// Band constants in f32, every step rounded towards "wider" by a relative 2^-20 inflation.  r2_bits = max
-// squared norm of the SCALED centred f32 points.
-__device__ __forceinline__ Mfma2Const mfma2_consts(double beta_d, unsigned int r2_bits) {
-  Mfma2Const c;
-  double g;
-  int kexp;
-  tim2_scale(beta_d, &g, &kexp);
-  const float u = 5.9604644775390625e-8f;  // 2^-24
-  const float up = 1.000001f;
-  const float beta = (float)(beta_d * g) * up;                 // scaled beta
-  const float kappa = (float)pow2_d(kexp);      // 4 beta^2, exact
-  const float R2 = __uint_as_float(r2_bits) * up;
-  const float R = __builtin_sqrtf(R2) * up;
-  const float b2 = 0.25f * kappa;                              // beta^2, exact
-  const float eps_u = kEpsU2 * u * R2 * up;
-  const float eps_a = kEpsA2 * u * R2 * up;
-  const float lam_lo = 2.0f * (float)(beta_d * g) * __builtin_sqrtf(__uint_as_float(r2_bits)) * 0.999999f;  // divisor
-  const float lam_hi = 2.0f * beta * R * up;
-  const float eta = eps_u / lam_lo * up;
-  const bool ok = (R2 > 1e-30f) && (R2 < 1e12f) && (beta_d > 0) && (eta <= 0.125f) && (eta == eta) && (kexp > -60) &&
-                  (kexp < 40) && (b2 * 5.76f <= R2);
-  const float den = 1.0f - 2.0f * (ok ? eta : 0.0f) - 2.0f * u;
-  const float K2 = eta / den * up;
-  const float G = (1.3e-13f * beta * R2 * R + 8e-15f * b2 * R2) * up;
-  const float K0p = (eps_u * lam_hi + eps_u * eps_u + kappa * eps_a * (1.0f + eta) + G) * up;
-  const float K0 = (K0p / den + 2.0f * K2 * kappa * eps_a) * up;
-  c.K2 = K2 * 1.001f * up;
-  // Short pairs (S <= beta: the one region where the sign of d misleads) have A <= beta^2 and B <= beta^2, hence
-  // u in [-2 beta^2, 0], w in [-4 beta^4, 0] and |d| = |u^2 + w| <= 4 beta^4: with K0 at least that (plus what
-  // the computed u~, w~ can add: 4 beta^2 eps_u + eps_u^2 + kappa eps_A) they all count as "inside the band" and
-  // reach the FP64 fix-up -- no separate test.  (At the bench geometry 4 beta^4 is 1.09 x the error term.)
-  const float short_d = (4.0f * b2 * b2 * (1.0f + 16.0f * u) + 4.0f * b2 * eps_u + eps_u * eps_u + kappa * eps_a) * 1.001f * up;
-  const float K0e = K0 * 1.001f * up;
-  c.K0 = (K0e > short_d ? K0e : short_d) * 1.00001f;  // (+ the f32 roundings of x = fma(w, K2, |d| - K0))
-  c.K0k = c.K0;
-  c.wtau = 0.f;
-  c.utau = 0.f;
-  // a band dominated by the short-pair term (beta close to the size of the cloud) would send most pairs to FP64
-  c.use_mfma = (ok && c.K0 == c.K0 && c.K0 < 1e30f && short_d <= 16.0f * K0e) ? 1 : 0;
-  return c;
 }
 
 // ==========================================================================================
@@ -630,42 +558,10 @@ __device__ __forceinline__ Mfma2Const mfma2_consts(double beta_d, unsigned int r
 // Self pairs (u = -beta^2, w = 0, d = beta^4 <= C) would flag every lane of a diagonal tile: the diagonal column tile
 // of a wave runs a second copy of the loop body that leaves them out of the minimum.
 // ==========================================================================================
-struct Mfma3Const {
-  float K2, K0, C;
-  int use_mfma;
-};
-__device__ __forceinline__ Mfma3Const mfma3_consts(double beta_d, unsigned int r2_bits) {
-  const Mfma2Const c2 = mfma2_consts(beta_d, r2_bits);
-  Mfma3Const c;
-  c.K2 = c2.K2;
-  c.K0 = c2.K0;
-  double g;
-  int kexp;
-  tim2_scale(beta_d, &g, &kexp);
-  const float u = 5.9604644775390625e-8f;  // 2^-24
-  const float up = 1.000001f;
-  const float beta = (float)(beta_d * g) * up;
-  const float kappa = (float)pow2_d(kexp);
-  const float R2 = __uint_as_float(r2_bits) * up;
-  const float R = __builtin_sqrtf(R2) * up;
-  const float b2 = 0.25f * kappa;
-  const float eps_u = kEpsU2 * u * R2 * up;
-  const float eps_w = kappa * (kEpsA2 * u * R2 * up) * up;
-  const float U0 = (4.0f * beta * R * 1.001f + 2.0f * eps_u) * up;
-  const float G = (1.3e-13f * beta * R2 * R + 8e-15f * b2 * R2) * up;
-  const float E = (2.0f * U0 * eps_u + eps_u * eps_u + eps_w + G) * up;
-  const float C0 = E / (1.0f - 4.0f * u) * 1.001f * up;
-  const float short_d = (4.0f * b2 * b2 * (1.0f + 16.0f * u) + 4.0f * b2 * eps_u + eps_u * eps_u + eps_w) * 1.001f * up;
-  c.C = (C0 > short_d ? C0 : short_d) * 1.00001f;
-  // (same admission as mfma2_consts; a band dominated by the short-pair term would flag most lane-tiles)
-  c.use_mfma = (c2.use_mfma && c.C == c.C && c.C < 1e30f && short_d <= 16.0f * C0) ? 1 : 0;
-  return c;
-}
-
 __global__ void tim_prep_consts_kernel(TimPrep* __restrict__ prep, int batch, double beta) {
   const int p = blockIdx.x * blockDim.x + threadIdx.x;
   if (p >= batch) return;
-  const Mfma3Const c = mfma3_consts(beta, prep[p].r2_bits);
+  const k1c::Consts c = k1c::consts(beta, k1c::norm_shift(prep_half_extent(prep + p)), prep[p].r2_bits);
   prep[p].band_c = c.C;
   prep[p].use_mfma = c.use_mfma;
 }
@@ -677,9 +573,9 @@ constexpr bool kK1Pipe = false, kK1Plain = true;
 constexpr int kK1Chunks = 1, kK1Occ = 3;
 
 // PIPE: software-pipelined schedule.  The wave works on QUARTER tiles (32 x 32) with two accumulator sets: while the
-// matrix pipe runs the four MFMAs of quarter k + 1, the vector ALU runs the epilogue of quarter k -- interleaved
+// matrix pipe runs the three MFMAs of quarter k + 1, the vector ALU runs the epilogue of quarter k -- interleaved
 // inside the one wave (sched_group_barrier: one MFMA, then a share of the epilogue), across the column tiles of the
-// loop as well.  The flat schedule (PIPE = false: 8 MFMAs, then both epilogues) relies on the other two waves of the
+// loop as well.  The flat schedule (PIPE = false: 6 MFMAs, then both epilogues) relies on the other two waves of the
 // SIMD to fill the matrix pipe's shadow.
 // PLAIN: d = fma(u, u, w) as one v_fma_f32 per value instead of one v_pk_fma_f32 per two (MI355X_MICROARCH.md prices
 // a packed f32 instruction beside MFMAs above two plain ones).  Measured (profiles/r5a/k1_lab.jsonl, 64 x 10 k, kernel
@@ -750,17 +646,17 @@ __global__ __launch_bounds__(256, OCC) void tim_graph_mfma3_kernel(
   typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
   const __amdgpu_buffer_rsrc_t q_rsrc = __builtin_amdgcn_make_buffer_rsrc(
       (void*)qt, 0, (int)((unsigned int)T * (unsigned int)sizeof(TimOperandTile2)), 0x00020000);
-  auto load_op = [&](int tile, int side, int g, int m) -> uint4 {  // side 0 = a (rows: m = 0..3), 1 = b (columns: m = 0..2)
+  auto load_op = [&](int tile, int side, int g, int m) -> uint4 {  // side 0 = a (rows: m = 0..2), 1 = b (columns: m = 0..1)
     const int soff = tile * (int)sizeof(TimOperandTile2) +
-                     (side ? (int)offsetof(TimOperandTile2, b) + (g * kTimColOperands + m) * 1024 : (g * 4 + m) * 1024);
+                     (side ? (int)offsetof(TimOperandTile2, b) + (g * kTimColOperands + m) * 1024 : (g * kTimRowOperands + m) * 1024);
     const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(q_rsrc, lane * 16, soff, 0);
     return make_uint4(v.x, v.y, v.z, v.w);
   };
-  bf16x8 ar[2][4];
+  f16x8 ar[2][kTimRowOperands];
   {
     const int It = min(I, T - 1);
     for (int rt = 0; rt < 2; ++rt)
-      for (int m = 0; m < 4; ++m) ar[rt][m] = __builtin_bit_cast(bf16x8, load_op(It, 0, rt, m));
+      for (int m = 0; m < kTimRowOperands; ++m) ar[rt][m] = __builtin_bit_cast(f16x8, load_op(It, 0, rt, m));
   }
   const bool rowvalid = I < T;
   const uint64_t rowmask = !rowvalid ? 0ull : (n - I * 64 >= 64) ? ~0ull : ((1ull << (n - I * 64)) - 1ull);
@@ -801,15 +697,14 @@ __global__ __launch_bounds__(256, OCC) void tim_graph_mfma3_kernel(
   struct Acc {
     f32x16 U, W;
   };
-  // the four MFMAs of one 32 x 32 quarter tile: u = B - A - beta^2 over 48 K slots (three chained), w = -4 beta^2 A
-  // over 16 (one, over the chain's first column operand again); w sits between the first two links of the chain
-  auto mf = [&](Acc& a, const bf16x8(&arow)[4], const uint4(&b)[kTimColOperands]) {
+  // the three MFMAs of one 32 x 32 quarter tile: u = B - A - beta^2 over 32 K slots (two chained), w = -4 beta^2 A
+  // over 16 (one, over the chain's first column operand again); w sits between the two links of the chain
+  auto mf = [&](Acc& a, const f16x8(&arow)[kTimRowOperands], const uint4(&b)[kTimColOperands]) {
     f32x16 z;
     for (int k = 0; k < 16; ++k) z[k] = 0.f;
-    a.U = __builtin_amdgcn_mfma_f32_32x32x16_bf16(arow[0], __builtin_bit_cast(bf16x8, b[0]), z, 0, 0, 0);
-    a.W = __builtin_amdgcn_mfma_f32_32x32x16_bf16(arow[3], __builtin_bit_cast(bf16x8, b[0]), z, 0, 0, 0);
-    a.U = __builtin_amdgcn_mfma_f32_32x32x16_bf16(arow[1], __builtin_bit_cast(bf16x8, b[1]), a.U, 0, 0, 0);
-    a.U = __builtin_amdgcn_mfma_f32_32x32x16_bf16(arow[2], __builtin_bit_cast(bf16x8, b[2]), a.U, 0, 0, 0);
+    a.U = __builtin_amdgcn_mfma_f32_32x32x16_f16(arow[0], __builtin_bit_cast(f16x8, b[0]), z, 0, 0, 0);
+    a.W = __builtin_amdgcn_mfma_f32_32x32x16_f16(arow[2], __builtin_bit_cast(f16x8, b[0]), z, 0, 0, 0);
+    a.U = __builtin_amdgcn_mfma_f32_32x32x16_f16(arow[1], __builtin_bit_cast(f16x8, b[1]), a.U, 0, 0, 0);
   };
   // epilogue of one quarter tile: the lane's 16 provisional column bits (sign of d = u^2 + w) and the group flag
   auto epi = [&](const Acc& a, bool self_tile) -> unsigned int {
@@ -902,14 +797,13 @@ __global__ __launch_bounds__(256, OCC) void tim_graph_mfma3_kernel(
     lds_tr[(J - Jbase) & (kMfmaColTiles - 1)][lane][wave] = trw_out;
   };
 
-  // flat schedule: per 32-column half the 8 MFMAs of both row halves (chains interleaved by hand), then the epilogues
+  // flat schedule: per 32-column half the 6 MFMAs of both row halves (chains interleaved by hand), then the epilogues
   auto body_flat = [&](const int J, auto diag_tag) {
     constexpr bool DIAG = decltype(diag_tag)::value;
     unsigned int tr[2][2];  // [ct][rt]: this lane's 16 column bits
 #pragma unroll
     for (int ct = 0; ct < 2; ++ct) {
-      const bf16x8 b0 = __builtin_bit_cast(bf16x8, bX[0]), b1 = __builtin_bit_cast(bf16x8, bX[1]);
-      const bf16x8 b2 = __builtin_bit_cast(bf16x8, bX[2]);
+      const f16x8 b0 = __builtin_bit_cast(f16x8, bX[0]), b1 = __builtin_bit_cast(f16x8, bX[1]);
       const int Jn = (ct == 0 || J + 1 >= Jend) ? J : J + 1, gn = ct ^ 1;
       f32x16 z;
       for (int k = 0; k < 16; ++k) z[k] = 0.f;
@@ -918,30 +812,24 @@ __global__ __launch_bounds__(256, OCC) void tim_graph_mfma3_kernel(
       // wave's loads win the arbitration against the other waves' vector work (-2 % on the bench step, profiles/r5t;
       // lowering the priority BEFORE the loads, or one level for the whole loop, gains nothing)
       __builtin_amdgcn_s_setprio(2);
-      acc[0].U = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ar[0][0], b0, z, 0, 0, 0);
+      acc[0].U = __builtin_amdgcn_mfma_f32_32x32x16_f16(ar[0][0], b0, z, 0, 0, 0);
       __builtin_amdgcn_sched_barrier(0);
-      acc[1].U = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ar[1][0], b0, z, 0, 0, 0);
+      acc[1].U = __builtin_amdgcn_mfma_f32_32x32x16_f16(ar[1][0], b0, z, 0, 0, 0);
       __builtin_amdgcn_sched_barrier(0);
-      acc[0].W = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ar[0][3], b0, z, 0, 0, 0);
+      acc[0].W = __builtin_amdgcn_mfma_f32_32x32x16_f16(ar[0][2], b0, z, 0, 0, 0);
       __builtin_amdgcn_sched_barrier(0);
-      acc[1].W = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ar[1][3], b0, z, 0, 0, 0);
+      acc[1].W = __builtin_amdgcn_mfma_f32_32x32x16_f16(ar[1][2], b0, z, 0, 0, 0);
       __builtin_amdgcn_sched_barrier(0);
       // each operand of the next half tile is requested right behind the last MFMA that reads its registers: the
       // load's way into the address unit runs beside the matrix pipe (0.592 -> 0.576 ms alone, -0.6 % on the bench
       // step: profiles/r5t/r5t21)
       bX[0] = load_op(Jn, 1, gn, 0);
       __builtin_amdgcn_sched_barrier(0);
-      acc[0].U = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ar[0][1], b1, acc[0].U, 0, 0, 0);
+      acc[0].U = __builtin_amdgcn_mfma_f32_32x32x16_f16(ar[0][1], b1, acc[0].U, 0, 0, 0);
       __builtin_amdgcn_sched_barrier(0);
-      acc[1].U = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ar[1][1], b1, acc[1].U, 0, 0, 0);
+      acc[1].U = __builtin_amdgcn_mfma_f32_32x32x16_f16(ar[1][1], b1, acc[1].U, 0, 0, 0);
       __builtin_amdgcn_sched_barrier(0);
       bX[1] = load_op(Jn, 1, gn, 1);
-      __builtin_amdgcn_sched_barrier(0);
-      acc[0].U = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ar[0][2], b2, acc[0].U, 0, 0, 0);
-      __builtin_amdgcn_sched_barrier(0);
-      acc[1].U = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ar[1][2], b2, acc[1].U, 0, 0, 0);
-      __builtin_amdgcn_sched_barrier(0);
-      bX[2] = load_op(Jn, 1, gn, 2);
       __builtin_amdgcn_s_setprio(0);
       __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
@@ -1397,7 +1285,7 @@ static K1Variant k1_lab_variant() {
 }
 #endif
 
-// phase 0 pre-pass (bbox, centred bf16 operands, R^2, degrees zeroed), 1 the matrix-core kernel (bitmap
+// phase 0 pre-pass (bbox, centred fp16 operands, R^2, degrees zeroed), 1 the matrix-core kernel (bitmap
 // + degrees), 2 FP64 fix-up of the worklist (+ overflow clear).  Three calls so that the profiling span
 // of phase 1 is that kernel alone.  d_pk: total_tiles TimOperandTile2, total_tiles = sum of the problems' W;
 // d_prep: tim_prep_bytes(batch), zero except the segment fields (tim_prep_fill_segments), part of the header upload;
