@@ -120,6 +120,20 @@ struct TransformationEstimationForGeneralizedICP {
   explicit TransformationEstimationForGeneralizedICP(double eps) : epsilon(eps) {}
 };
 
+// Open3D's TransformationEstimationForColoredICP(lambda_geometric, kernel) (include/teaser_hip.h, "ICP refinement:
+// Colored ICP"): the kernel weights both residuals.  The colours of both clouds and the target normals are arguments
+// of registrationColoredICP; gradient_radius (<= 0: twice max_correspondence_distance, Open3D's choice) and
+// gradient_max_nn choose the neighbourhood the target's colour gradients are estimated from on the device.
+struct TransformationEstimationForColoredICP {
+  double lambda_geometric = 0.968;
+  RobustKernel kernel;
+  double gradient_radius = 0.0;
+  int gradient_max_nn = 30;
+  TransformationEstimationForColoredICP() = default;
+  explicit TransformationEstimationForColoredICP(double lambda, const RobustKernel& k = L2Loss())
+      : lambda_geometric(lambda), kernel(k) {}
+};
+
 // One 3 x 3 covariance per point: 9 doubles each, row-major (only the upper triangle is read).
 using Covariances = std::vector<double>;
 
@@ -232,6 +246,88 @@ class ICP {
 
   Covariances estimateCovariances(const Matrix3X& cloud, double radius, int max_nn = 20, double epsilon = 1e-3) {
     return estimateCovariancesBatch({cloud}, {radius}, {max_nn}, {epsilon})[0];
+  }
+
+  // Colored ICP: src_colors[b] / dst_colors[b] hold one colour (r, g, b) per point, dst_normals[b] one normal per
+  // target point; dst_gradients: empty (every problem's colour gradients are estimated on the device), or per problem
+  // an empty matrix or one gradient per target point.
+  std::vector<ICPResult> registrationColoredICPBatch(
+      const std::vector<Matrix3X>& src, const std::vector<Matrix3X>& dst, const std::vector<Matrix3X>& src_colors,
+      const std::vector<Matrix3X>& dst_colors, const std::vector<Matrix3X>& dst_normals,
+      const std::vector<double>& max_correspondence_distance, const std::vector<Matrix4>& init,
+      const std::vector<TransformationEstimationForColoredICP>& estimation,
+      const std::vector<ICPConvergenceCriteria>& criteria, const std::vector<Matrix3X>& dst_gradients = {}) {
+    const size_t b = src.size();
+    if (dst.size() != b || src_colors.size() != b || dst_colors.size() != b || dst_normals.size() != b ||
+        estimation.size() != b || (!dst_gradients.empty() && dst_gradients.size() != b))
+      throw std::invalid_argument("teaser::ICP: one entry per problem in every argument");
+    ColorArgs col;
+    col.src_colors.resize(b), col.dst_colors.resize(b), col.dst_gradients.assign(b, nullptr), col.rec.resize(b);
+    std::vector<const double*> pn(b);
+    std::vector<teaser_icp_estimation_c> est(b);
+    for (size_t k = 0; k < b; ++k) {
+      const bool given = !dst_gradients.empty() && dst_gradients[k].cols() > 0;
+      if (src_colors[k].cols() != src[k].cols() || dst_colors[k].cols() != dst[k].cols() ||
+          dst_normals[k].cols() != dst[k].cols() || (given && dst_gradients[k].cols() != dst[k].cols()))
+        throw std::invalid_argument("teaser::ICP: one colour per point, one normal and one gradient per target point");
+      pn[k] = dst_normals[k].data();
+      col.src_colors[k] = src_colors[k].data();
+      col.dst_colors[k] = dst_colors[k].data();
+      if (given) col.dst_gradients[k] = dst_gradients[k].data();
+      est[k].method = 3;
+      est[k].kernel = estimation[k].kernel.kernel;
+      est[k].kernel_k = estimation[k].kernel.k;
+      col.rec[k].lambda_geometric = estimation[k].lambda_geometric;
+      col.rec[k].gradient_radius = estimation[k].gradient_radius;
+      col.rec[k].gradient_max_nn = estimation[k].gradient_max_nn;
+      col.rec[k].reserved = 0;
+    }
+    return run(src, dst, max_correspondence_distance, init, criteria, pn.data(), est.data(), nullptr, nullptr, nullptr,
+               &col);
+  }
+
+  ICPResult registrationColoredICP(const Matrix3X& src, const Matrix3X& dst, const Matrix3X& src_colors,
+                                   const Matrix3X& dst_colors, const Matrix3X& dst_normals,
+                                   double max_correspondence_distance, const Matrix4& init = Matrix4::Identity(),
+                                   const TransformationEstimationForColoredICP& estimation =
+                                       TransformationEstimationForColoredICP(),
+                                   const ICPConvergenceCriteria& criteria = ICPConvergenceCriteria()) {
+    return registrationColoredICPBatch({src}, {dst}, {src_colors}, {dst_colors}, {dst_normals},
+                                       {max_correspondence_distance}, {init}, {estimation}, {criteria})[0];
+  }
+
+  // The colour gradients Colored ICP uses, for many clouds in one launch sequence; result c is identical to cloud c
+  // estimated alone.
+  std::vector<Matrix3X> estimateColorGradientsBatch(const std::vector<Matrix3X>& clouds,
+                                                    const std::vector<Matrix3X>& normals,
+                                                    const std::vector<Matrix3X>& colors,
+                                                    const std::vector<double>& radius, const std::vector<int>& max_nn) {
+    const size_t b = clouds.size();
+    if (normals.size() != b || colors.size() != b || radius.size() != b || max_nn.size() != b)
+      throw std::invalid_argument("teaser::ICP: one entry per cloud in every argument");
+    std::vector<const double*> pp(b), pn(b), pc(b);
+    std::vector<int32_t> n(b), k(b);
+    std::vector<Matrix3X> out(b);
+    std::vector<double*> po(b);
+    for (size_t c = 0; c < b; ++c) {
+      if (normals[c].cols() != clouds[c].cols() || colors[c].cols() != clouds[c].cols())
+        throw std::invalid_argument("teaser::ICP: one normal and one colour per point");
+      pp[c] = clouds[c].data(), pn[c] = normals[c].data(), pc[c] = colors[c].data();
+      n[c] = (int32_t)clouds[c].cols();
+      k[c] = max_nn[c];
+      out[c] = Matrix3X(3, clouds[c].cols());
+      po[c] = out[c].data();
+    }
+    const int32_t rc = teaser_hip_icp_color_gradients_batch(h_, (int32_t)b, pp.data(), n.data(), pn.data(), pc.data(),
+                                                            radius.data(), k.data(), po.data());
+    if (rc != TEASER_HIP_OK)
+      throw ICPError(rc, "teaser::ICP: status " + std::to_string(rc) + ": " + teaser_hip_icp_last_error(h_));
+    return out;
+  }
+
+  Matrix3X estimateColorGradients(const Matrix3X& cloud, const Matrix3X& normals, const Matrix3X& colors, double radius,
+                                  int max_nn = 30) {
+    return std::move(estimateColorGradientsBatch({cloud}, {normals}, {colors}, {radius}, {max_nn})[0]);
   }
 
   // The same with point-to-plane estimation: dst_normals[b] holds one normal per point of dst[b], used as given.
@@ -402,12 +498,19 @@ class ICP {
   }
 
  private:
+  // What a coloured call hands to teaser_hip_icp_batch_color besides run's own arguments.
+  struct ColorArgs {
+    std::vector<const double*> src_colors, dst_colors, dst_gradients;
+    std::vector<teaser_icp_color_c> rec;
+  };
+
   std::vector<ICPResult> run(const std::vector<Matrix3X>& src, const std::vector<Matrix3X>& dst,
                              const std::vector<double>& max_correspondence_distance,
                              const std::vector<Matrix4>& init, const std::vector<ICPConvergenceCriteria>& criteria,
                              const double* const* normals, const teaser_icp_estimation_c* est,
                              const double* const* src_cov = nullptr, const double* const* dst_cov = nullptr,
-                             const teaser_icp_normal_search_c* normal_search = nullptr) {
+                             const teaser_icp_normal_search_c* normal_search = nullptr,
+                             const ColorArgs* color = nullptr) {
     const size_t b = src.size();
     if (dst.size() != b || max_correspondence_distance.size() != b || init.size() != b || criteria.size() != b)
       throw std::invalid_argument("teaser::ICP: one entry per problem in every argument");
@@ -433,7 +536,11 @@ class ICP {
     }
     std::vector<teaser_icp_result_c> out(b);
     const int32_t rc =
-        normal_search
+        color ? teaser_hip_icp_batch_color(h_, (int32_t)b, ps.data(), ns.data(), pd.data(), nd.data(), T.data(),
+                                           params.data(), out.data(), pc.data(), normals, est, src_cov, dst_cov,
+                                           color->src_colors.data(), color->dst_colors.data(),
+                                           color->dst_gradients.data(), color->rec.data())
+        : normal_search
             ? teaser_hip_icp_batch_auto(h_, (int32_t)b, ps.data(), ns.data(), pd.data(), nd.data(), T.data(),
                                         params.data(), out.data(), pc.data(), normals, est, src_cov, dst_cov,
                                         normal_search)
@@ -532,6 +639,18 @@ inline Matrix6 getInformationMatrixFromPointClouds(const Matrix3X& src, const Ma
 inline Covariances estimateCovariances(const Matrix3X& cloud, double radius, int max_nn = 20, double epsilon = 1e-3) {
   ICP icp;
   return icp.estimateCovariances(cloud, radius, max_nn, epsilon);
+}
+
+// Open3D's registration_colored_icp, one problem; creates a handle per call.
+inline ICPResult registrationColoredICP(const Matrix3X& src, const Matrix3X& dst, const Matrix3X& src_colors,
+                                        const Matrix3X& dst_colors, const Matrix3X& dst_normals,
+                                        double max_correspondence_distance, const Matrix4& init = Matrix4::Identity(),
+                                        const TransformationEstimationForColoredICP& estimation =
+                                            TransformationEstimationForColoredICP(),
+                                        const ICPConvergenceCriteria& criteria = ICPConvergenceCriteria()) {
+  ICP icp;
+  return icp.registrationColoredICP(src, dst, src_colors, dst_colors, dst_normals, max_correspondence_distance, init,
+                                    estimation, criteria);
 }
 
 }  // namespace teaser

@@ -545,7 +545,8 @@ TEASER_HIP_API int32_t teaser_hip_icp_solve(teaser_hip_icp* icp, const double* s
  * point-to-plane with n_t > 0 and no dst_normals, non-finite dst_normals.  Point-to-point problems give the same bits
  * through the _ex entry points as through the ones above, alone or mixed with point-to-plane problems. */
 typedef struct teaser_icp_estimation_c {
-  int32_t method;  /* 0 point-to-point (default), 1 point-to-plane, 2 Generalized ICP (_cov entry points only) */
+  int32_t method;  /* 0 point-to-point (default), 1 point-to-plane, 2 Generalized ICP (_cov entry points and later),
+                      3 Colored ICP (_color entry points only) */
   int32_t kernel;  /* 0 L2 (default), 1 Huber, 2 Cauchy, 3 GM, 4 Tukey */
   double kernel_k; /* 1.0 (Open3D's default); ignored for L2 */
 } teaser_icp_estimation_c;
@@ -720,6 +721,103 @@ TEASER_HIP_API int32_t teaser_hip_icp_solve_auto(teaser_hip_icp* icp, const doub
                                                  const teaser_icp_estimation_c* est, const double* src_cov,
                                                  const double* dst_cov,
                                                  const teaser_icp_normal_search_c* dst_normal_search);
+
+/* ICP refinement: Colored ICP (Park, Zhou, Koltun, "Colored Point Cloud Registration Revisited", ICCV 2017; the
+ * formulation of Open3D's registration_colored_icp / TransformationEstimationForColoredICP), a fourth estimation method
+ * (method = 3) of the same batched ICP: same handle, search, stop rule and determinism guarantees, selectable per
+ * problem and mixed freely with methods 0, 1 and 2 in one batch.
+ * The loop, apply, corr (the lexicographic minimum of (d2, j), strict d2 < r r), fitness, the EUCLIDEAN inlier_rmse,
+ * T = U T, the iteration count, the stop rule on absolute differences, max_iteration = 0, empty clouds and the corr
+ * output are exactly those written out above.  Only U differs.
+ * Additional input per Colored-ICP problem: source colours (n_s x 3 doubles), target colours (n_t x 3), target normals N
+ * (n_t x 3, used as given), optionally target colour gradients (n_t x 3), and one teaser_icp_color_c record.
+ * Intensity of a point with colour (r, g, b):  I = ((r + g) + b) / 3.0.
+ * Colour gradient of target point i, x = Q[i], n = N[i], R = gradient_radius (<= 0: 2 max_correspondence_distance,
+ * Open3D's choice):
+ *   neighbourhood: exactly the covariance contract's above -- the points j (i itself included) with d2 < R R, in
+ *                  ascending (d2, j), when there are more than gradient_max_nn the gradient_max_nn smallest.  m = their
+ *                  number.  m < 4: the gradient is 0.
+ *   slot 0 of that list is skipped, whichever point it is (Open3D skips point_idx[0]).  For slots k = 1 .. m - 1 in
+ *   list order, y = the neighbour, j its index:
+ *     o = y - x,  s = (o0 n0 + o1 n1) + o2 n2,  a = o - s n   (per component a_c = o_c - s n_c)
+ *     b = I[j] - I[i]
+ *     G += a a^T (upper triangle, six sums),  h += a b          one neighbour at a time from 0
+ *   then the orthogonality row:  w = (double)(m - 1),  G[r][c] += (w n_r)(w n_c)
+ *   solve G d = h by 3 x 3 LDL^T without pivoting (the recurrences of the 6 x 6 solve of point-to-plane);  d = 0 when a
+ *   pivot is not finite or not > 0, or when d is not finite.  No fused operations anywhere.
+ * Step U.  With c = the problem's target bounding-box centre, sg = sqrt(lambda_geometric), sp = sqrt(1 -
+ * lambda_geometric), and for every correspondence (i, j) of C in ascending i, x = the current moved source point,
+ * q = Q[j], n = N[j], d = gradient[j], Is = the source intensity, It = the target intensity:
+ *   x' = x - c,  q' = q - c,  e = x' - q',  s = (e0 n0 + e1 n1) + e2 n2
+ *   Jg = sg [ x' x n ; n ]  (each entry multiplied by sg),  rg = sg s,  wg = kernel(rg)
+ *   u  = e - s n,  isp = ((d0 u0 + d1 u1) + d2 u2) + It
+ *   t  = (d0 n0 + d1 n1) + d2 n2,  dm = t n - d                     (= -(I - n n^T) d)
+ *   Ji = sp [ x' x dm ; dm ],  ri = sp (Is - isp),  wi = kernel(ri)
+ *   A += (wg Jg[r]) Jg[c] + (wi Ji[r]) Ji[c]  (c >= r),   g += (wg rg) Jg[r] + (wi ri) Ji[r]
+ *   -- the geometric term first, then the photometric one; each entry is ONE sum over the correspondences.
+ *   solve A xi = -g by the LDL^T of point-to-plane;  R = Rz(gamma) Ry(beta) Rx(alpha);  U = [ R | t' + c - R c ];  the
+ *   identity fall-backs are those of point-to-plane.
+ * Robust kernels: the five of point-to-plane, applied to each of the two residuals (Open3D does the same).  With
+ * lambda_geometric = 1 the step is point-to-plane's operation for operation, up to the sign of zeros.
+ * Differences from Open3D (this states the FORMULATION; bit parity with Open3D is not claimed and was not measured):
+ *   - the step is linearised in the frame centred on c, as for point-to-plane;
+ *   - a is formed from the centred o = y - x rather than as vt_proj - vt;
+ *   - the 3 x 3 LDL^T is unpivoted where Eigen's is pivoted.
+ * Methods 0 - 3 go through the _color entry points below; the older entry points keep refusing method 3 ("method").
+ * Problems of methods 0, 1 and 2 give the same bits through the _color entry points as through _cov, alone or mixed
+ * with coloured problems.  Gradients that are not given are estimated inside the call, written on the device into the
+ * buffer the correspondence pass gathers from and never copied to the host; the result is, bit for bit, that of
+ * teaser_hip_icp_color_gradients_batch followed by the call with those gradients given.  Target normals are not estimated
+ * inside the call (teaser_hip_icp_normals_batch first).
+ * TEASER_HIP_ERR_BAD_ARG (argument and problem named) in addition to the lists above, for a method-3 problem:
+ * lambda_geometric outside [0, 1] or not finite, gradient_max_nn outside [4, TEASER_HIP_ICP_COV_MAX_NN], reserved != 0,
+ * a gradient radius whose square is not finite and > 0, n_src > 0 and no src_colors, n_dst > 0 and no dst_colors or no
+ * dst_normals, a non-finite colour, normal or given gradient. */
+typedef struct teaser_icp_color_c {
+  double lambda_geometric; /* 0.968 (Open3D's default); [0, 1] */
+  double gradient_radius;  /* <= 0: 2 max_correspondence_distance */
+  int32_t gradient_max_nn; /* 30; [4, TEASER_HIP_ICP_COV_MAX_NN] */
+  int32_t reserved;        /* 0 */
+} teaser_icp_color_c;
+#ifdef __cplusplus
+static_assert(sizeof(teaser_icp_color_c) == 24, "teaser_icp_color_c is 24 bytes");
+#else
+_Static_assert(sizeof(teaser_icp_color_c) == 24, "teaser_icp_color_c is 24 bytes");
+#endif
+TEASER_HIP_API int32_t teaser_hip_icp_color_default(teaser_icp_color_c* color);
+/* teaser_hip_icp_batch_cov plus src_colors / dst_colors (NULL, or per problem NULL unless the problem is Colored ICP,
+ * else n x 3 doubles), dst_gradients (NULL, or per problem NULL = "estimate on the device", else n_dst x 3 doubles) and
+ * color (NULL = the defaults for every problem, else one record per problem; read for method 3 only).  All borrowed
+ * for the call. */
+TEASER_HIP_API int32_t teaser_hip_icp_batch_color(teaser_hip_icp* icp, int32_t batch, const double* const* src,
+                                                  const int32_t* n_src, const double* const* dst,
+                                                  const int32_t* n_dst, const double* init,
+                                                  const teaser_icp_params_c* params, teaser_icp_result_c* out,
+                                                  int32_t* const* corr, const double* const* dst_normals,
+                                                  const teaser_icp_estimation_c* est, const double* const* src_cov,
+                                                  const double* const* dst_cov, const double* const* src_colors,
+                                                  const double* const* dst_colors,
+                                                  const double* const* dst_gradients,
+                                                  const teaser_icp_color_c* color);
+/* One problem: teaser_hip_icp_batch_color with batch = 1. */
+TEASER_HIP_API int32_t teaser_hip_icp_solve_color(teaser_hip_icp* icp, const double* src, int32_t n_src,
+                                                  const double* dst, int32_t n_dst, const double* init,
+                                                  const teaser_icp_params_c* params, teaser_icp_result_c* out,
+                                                  int32_t* corr, const double* dst_normals,
+                                                  const teaser_icp_estimation_c* est, const double* src_cov,
+                                                  const double* dst_cov, const double* src_colors,
+                                                  const double* dst_colors, const double* dst_gradients,
+                                                  const teaser_icp_color_c* color);
+/* The colour gradients of the rule above for a batch of clouds: points, normals and colours (n x 3 doubles each), a
+ * radius and a max_nn in [4, TEASER_HIP_ICP_COV_MAX_NN] per cloud; out[b]: n[b] x 3 doubles.  Empty clouds are legal.
+ * Deterministic like every call on this handle.  TEASER_HIP_ERR_BAD_ARG (argument and cloud named): non-finite points,
+ * normals or colours, a radius (or its square) that is not finite and > 0, max_nn outside its range, NULL where n > 0.
+ * Performance only: a call whose largest max_nn exceeds 32 runs every cloud through the kernel with the longer list. */
+TEASER_HIP_API int32_t teaser_hip_icp_color_gradients_batch(teaser_hip_icp* icp, int32_t batch,
+                                                            const double* const* points, const int32_t* n,
+                                                            const double* const* normals,
+                                                            const double* const* colors, const double* radius,
+                                                            const int32_t* max_nn, double* const* out);
 
 /* Self k-NN (no radius), on the ICP handle: a batch of clouds (n x 3 doubles each) and a k in
  * [1, TEASER_HIP_ICP_KNN_MAX] per cloud (TEASER_HIP_ICP_KNN_MAX = 100, the same number as TEASER_HIP_ICP_COV_MAX_NN).

@@ -13,9 +13,16 @@ Generalized ICP, under "gicp" (covariances estimated on the GPU at radius = 2 vo
 workloads, beside point-to-plane L2 on all three from the same run ("plane_l2") and the per-iteration ratio against it,
 the iterations to convergence of the three methods on config 5, and "covariances": the estimation time per cloud for
 the config-5 pair (each cloud alone, both in one call, 64 pairs in one call) and the dense pair.
+Colored ICP, with --colored alone (nothing else runs): under "colored" the textured scene of
+tests/icp_colored_reference.py scaled up (144 x 144 targets, 15 000 sources, r = 0.04) and config 5 with a synthetic
+texture (intensity 0.5 + 0.2 sin 4x + 0.2 cos 3y of the world position, the fixture's target normals), each alone and
+x 64 in one call: ms per call and per iteration beside point-to-plane L2 on the same pairs in the same run, the pose
+errors on the scene, and the gradient estimation alone.  The object is also written to
+profiles/icp_colored/bench_icp_colored.json.
 Wall-clock medians over --reps calls after --warmup calls (every call is synchronous); ms_min / ms_max give the spread
 of the repeats.  --method point skips the other parts (the form that also runs on a build without them); both = point + plane.  Usage:
-    python scripts/bench_icp.py [--reps 20] [--warmup 3] [--no-host-ref] [--method all|both|point|plane|gicp]"""
+    python scripts/bench_icp.py [--reps 20] [--warmup 3] [--no-host-ref] [--method all|both|point|plane|gicp]
+    python scripts/bench_icp.py --colored [--reps 20] [--warmup 3]"""
 import argparse
 import importlib
 import json
@@ -74,15 +81,67 @@ def candidate_visits(X, Q, r):
     return total
 
 
+def colored_part(a):
+    """The "colored" object: Colored ICP beside point-to-plane L2 on the same pairs."""
+    import icp_colored_reference as RC
+    crit = tp.ICPConvergenceCriteria(max_iteration=100)
+
+    def texture(X):
+        i = 0.5 + 0.2 * np.sin(4 * X[:, 0]) + 0.2 * np.cos(3 * X[:, 1])
+        return np.stack([i, i, i], 1)
+
+    def pair(name, P, Q, N, Cs, Ct, r, init, T_true=None):
+        est, pl = tp.TransformationEstimationForColoredICP(), tp.TransformationEstimationPointToPlane()
+        out = {"points": [len(P), len(Q)], "r": r}
+        for label, b in (("single", 1), ("batch64", 64)):
+            kw = dict(estimation_methods=est, target_normals=[N] * b, source_colors=[Cs] * b, target_colors=[Ct] * b)
+            reps = a.reps if b == 1 else max(a.reps // 4, 3)
+            tc, oc = timed(lambda: tp.registration_icp_batch([P] * b, [Q] * b, r, init, crit, **kw), reps, a.warmup)
+            sc = timed.spread
+            tpl, op = timed(lambda: tp.registration_icp_batch([P] * b, [Q] * b, r, init, crit, estimation_methods=pl,
+                                                              target_normals=[N] * b), reps, a.warmup)
+            row = dict(colored_ms=1e3 * tc, colored_iterations=oc[0].iterations,
+                       colored_us_per_iteration=1e6 * tc / max(oc[0].iterations, 1), colored_fitness=oc[0].fitness,
+                       plane_ms=1e3 * tpl, plane_iterations=op[0].iterations,
+                       plane_us_per_iteration=1e6 * tpl / max(op[0].iterations, 1), plane_spread=timed.spread, **sc)
+            if T_true is not None:
+                row["colored_pose_error"] = float(np.linalg.norm(oc[0].transformation - T_true))
+                row["plane_pose_error"] = float(np.linalg.norm(op[0].transformation - T_true))
+            out[label] = row
+        tg, _ = timed(lambda: tp.estimate_color_gradients(Q, N, Ct, 2 * r), a.reps, a.warmup)
+        out["gradients_alone"] = dict(ms=1e3 * tg, radius=2 * r, max_nn=30, **timed.spread)
+        return name, out
+
+    res = {}
+    s = RC.scene(seed=0, n_src=15000, grid=144)
+    k, v = pair("scene", s["source"], s["target"], s["target_normals"], s["source_colors"], s["target_colors"], 0.04,
+                np.eye(4), s["T_true"])
+    res[k] = v
+    P, Q, r, init = R.config5_problem()
+    N = np.load(os.path.join(ROOT, "tests", "golden", "icp_plane_golden.npz"))["target_normals"]
+    k, v = pair("config5", P, Q, N, texture(R.apply(init, P)), texture(Q), r, init)
+    res[k] = v
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--no-host-ref", action="store_true")
     ap.add_argument("--method", choices=["all", "both", "point", "plane", "gicp"], default="all")
+    ap.add_argument("--colored", action="store_true", help="Colored ICP beside point-to-plane, nothing else")
     a = ap.parse_args()
     if tp.device_count() < 1:
         sys.exit("bench_icp.py needs an MI355X")
+    if a.colored:
+        res = {"workload": "Colored ICP beside point-to-plane L2, max_iteration 100", "colored": colored_part(a)}
+        out_dir = os.path.join(ROOT, "profiles", "icp_colored")
+        os.makedirs(out_dir, exist_ok=True)
+        with open(os.path.join(out_dir, "bench_icp_colored.json"), "w") as f:
+            json.dump(res, f, indent=1)
+        print(json.dumps(res))
+        return
     P, Q, r, init = R.config5_problem()
     crit = tp.ICPConvergenceCriteria(max_iteration=100)
     res = {"workload": "ICP, config-5 pair (%d / %d points), r = voxel = %.4f, max_iteration 100"

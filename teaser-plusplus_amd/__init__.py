@@ -139,6 +139,8 @@ EXPORTED_SYMBOLS = [
     "teaser_hip_icp_remove_radius_outliers_batch", "teaser_hip_icp_set_option", "teaser_hip_icp_get_option",
     "teaser_hip_icp_iss_params_default", "teaser_hip_icp_iss_keypoints_batch",
     "teaser_hip_icp_information_batch", "teaser_hip_icp_information",
+    "teaser_hip_icp_color_default", "teaser_hip_icp_batch_color", "teaser_hip_icp_solve_color",
+    "teaser_hip_icp_color_gradients_batch",
     "teaser_hip_voxel_create", "teaser_hip_voxel_destroy", "teaser_hip_voxel_last_error",
     "teaser_hip_voxel_down_sample_batch", "teaser_hip_voxel_down_sample",
     "teaser_hip_features_create", "teaser_hip_features_destroy", "teaser_hip_features_last_error",
@@ -1092,7 +1094,9 @@ from .icp import (CauchyLoss, GMLoss, HuberLoss, ICPConvergenceCriteria, L2Loss,
                   covariances_from_normals, estimate_covariances, estimate_covariances_batch,
                   registration_generalized_icp, KDTreeSearchParamHybrid, KDTreeSearchParamKNN, estimate_normals,
                   estimate_normals_batch, surface_variation, evaluate_registration, evaluate_registration_batch,
-                  get_information_matrix_from_point_clouds, get_information_matrix_from_point_clouds_batch)
+                  get_information_matrix_from_point_clouds, get_information_matrix_from_point_clouds_batch,
+                  TransformationEstimationForColoredICP, registration_colored_icp, estimate_color_gradients,
+                  estimate_color_gradients_batch)
 from .voxel import voxel_down_sample, voxel_down_sample_batch  # noqa: E402
 from .outlier import (remove_radius_outlier, remove_radius_outlier_batch, remove_statistical_outlier,  # noqa: E402
                       remove_statistical_outlier_batch, self_knn, self_knn_batch, get_icp_option, set_icp_option)
@@ -1119,6 +1123,8 @@ __all__ = ["batched", "FPFHEstimation", "Matcher", "MultiDeviceSolver", "RobustR
            "estimate_normals", "estimate_normals_batch", "surface_variation",
            "evaluate_registration", "evaluate_registration_batch", "get_information_matrix_from_point_clouds",
            "get_information_matrix_from_point_clouds_batch",
+           "TransformationEstimationForColoredICP", "registration_colored_icp", "estimate_color_gradients",
+           "estimate_color_gradients_batch",
            "remove_statistical_outlier", "remove_statistical_outlier_batch", "remove_radius_outlier",
            "remove_radius_outlier_batch", "self_knn", "self_knn_batch", "get_icp_option", "set_icp_option",
            "compute_iss_keypoints", "compute_iss_keypoints_batch",

@@ -1,7 +1,7 @@
 // icp.hip -- host side of the batched ICP (include/teaser_hip.h, "ICP refinement": point-to-point, point-to-plane
-// with robust kernels, Generalized ICP) and of the covariance estimation on the same handle: argument validation,
+// with robust kernels, Generalized ICP, Colored ICP) and of the covariance estimation on the same handle: argument validation,
 // the per-call index and the iteration loop.  The handle's other calls: icp_outlier.hip, icp_normals.hip,
-// icp_keypoints.hip; what they share: icp_host.h.
+// icp_keypoints.hip, icp_color.hip (the Colored-ICP entry points and their checks); what they share: icp_host.h.
 // Kernels: kernels_icp.hip.
 //
 // The host enqueues iterations in groups of kIcpGroup (two launches each); after a group ONE small copy of the
@@ -83,8 +83,9 @@ int32_t validate(teaser_hip_icp* h, int32_t batch, const double* const* src, con
       const teaser_icp_estimation_c& m = est[b];
       if (m.method < kIcpMethodPoint || m.method > max_method)
         return fail(h, TEASER_HIP_ERR_BAD_ARG,
-                    (m.method == kIcpMethodGicp ? "est: method 2 (Generalized ICP) needs the _cov entry points"
-                                                : "est: unknown method") + at(b));
+                    (m.method == kIcpMethodGicp    ? "est: method 2 (Generalized ICP) needs the _cov entry points"
+                     : m.method == kIcpMethodColor ? "est: method 3 (Colored ICP) needs the _color entry points"
+                                                   : "est: unknown method") + at(b));
       if (m.kernel < kIcpKernelL2 || m.kernel > kIcpKernelTukey)
         return fail(h, TEASER_HIP_ERR_BAD_ARG, "est: unknown kernel" + at(b));
       if (m.method == kIcpMethodPoint && m.kernel != kIcpKernelL2)
@@ -109,6 +110,12 @@ int32_t validate(teaser_hip_icp* h, int32_t batch, const double* const* src, con
         }
       }
       const bool estimated = nsearch && nsearch[b].max_nn != 0 && !(dst_normals && dst_normals[b]);
+      if (m.method == kIcpMethodColor && n_dst[b] > 0) {
+        if (!dst_normals || !dst_normals[b])
+          return fail(h, TEASER_HIP_ERR_BAD_ARG, "dst_normals is NULL for a Colored-ICP problem" + at(b));
+        if (!finite_points(dst_normals[b], n_dst[b]))
+          return fail(h, TEASER_HIP_ERR_BAD_ARG, "dst_normals has a non-finite component" + at(b));
+      }
       if (m.method == kIcpMethodPlane && n_dst[b] > 0 && !estimated) {
         if (!dst_normals || !dst_normals[b])
           return fail(h, TEASER_HIP_ERR_BAD_ARG, "dst_normals is NULL for a point-to-plane problem" + at(b));
@@ -192,7 +199,8 @@ int32_t icp_run_batch(teaser_hip_icp* h, int32_t batch, const double* const* src
                       const teaser_icp_params_c* params, teaser_icp_result_c* out, int32_t* const* corr,
                       const double* const* dst_normals, const teaser_icp_estimation_c* est,
                       const double* const* src_cov, const double* const* dst_cov, int max_method,
-                      const teaser_icp_normal_search_c* nsearch, IcpPreIndexHook hook, void* ctx) {
+                      const teaser_icp_normal_search_c* nsearch, IcpPreIndexHook hook, void* ctx,
+                      IcpIterateFn iterate) {
   if (!h) return TEASER_HIP_ERR_BAD_ARG;
   h->err.clear();
   int32_t rc = validate(h, batch, src, n_src, dst, n_dst, init, params, out, dst_normals, est, src_cov, dst_cov,
@@ -206,6 +214,7 @@ int32_t icp_run_batch(teaser_hip_icp* h, int32_t batch, const double* const* src
   int max_iter = 0;
   bool plane = false;  // any point-to-plane problem: the launches with the wider partials
   bool gicp = false;   // any Generalized-ICP problem: the third instantiation and the packed covariances
+  bool color = false;  // any Colored-ICP problem: the fourth instantiation, reached through `iterate`
   for (int b = 0; b < batch; ++b) {
     const teaser_icp_params_c& p = params[b];
     IcpDesc& d = add_problem(ix, b, n_src[b], n_dst[b], dst, p.max_correspondence_distance,
@@ -220,6 +229,7 @@ int32_t icp_run_batch(teaser_hip_icp* h, int32_t batch, const double* const* src
       d.kernel_k = est[b].kernel == kIcpKernelL2 ? 0.0 : est[b].kernel_k;
       plane |= d.method == kIcpMethodPlane;
       gicp |= d.method == kIcpMethodGicp;
+      color |= d.method == kIcpMethodColor;
     }
     IcpState& st = state[(size_t)b];
     memset(&st, 0, sizeof(st));
@@ -228,6 +238,8 @@ int32_t icp_run_batch(teaser_hip_icp* h, int32_t batch, const double* const* src
     for (int k = 0; k < 16; ++k) st.T[k] = T0[k];
     for (int k = 0; k < 12; ++k) st.U[k] = T0[k];  // the first correspondence pass applies init to P
   }
+  if (color && !iterate) return fail(h, TEASER_HIP_ERR_BAD_ARG, "est: method 3 (Colored ICP) needs the _color entry points");
+  plane |= color;  // the normals and the wider partials
   const std::vector<IcpDesc>& desc = ix.desc;
   const int64_t s_off = ix.s_off, t_off = ix.t_off;
   const int n_blk = (int)ix.blk_prob.size();
@@ -252,7 +264,8 @@ int32_t icp_run_batch(teaser_hip_icp* h, int32_t batch, const double* const* src
   if ((rc = upload_inputs(h, ix, src, dst, n_dst, state.data(), bytes[B_STATE])) != TEASER_HIP_OK) return rc;
   for (int b = 0; b < batch; ++b) {  // one copy per point-to-plane problem, straight from the caller's normals
     const IcpDesc& d = desc[(size_t)b];
-    if (d.method == kIcpMethodPlane && d.n_t > 0 && dst_normals && dst_normals[b])  // else: the hook estimates them
+    if ((d.method == kIcpMethodPlane || d.method == kIcpMethodColor) && d.n_t > 0 && dst_normals &&
+        dst_normals[b])  // else: the hook estimates them
       FCHK(h, hipMemcpyAsync(B[B_NORMALS].as<double>() + 3 * d.t_off, dst_normals[b], 24 * (size_t)d.n_t,
                              hipMemcpyHostToDevice, s),
            "hipMemcpyAsync (normals)");
@@ -280,11 +293,14 @@ int32_t icp_run_batch(teaser_hip_icp* h, int32_t batch, const double* const* src
   int64_t passes = 0;  // correspondence passes enqueued: the first one + one per iteration
   for (;;) {
     for (int g = 0; g < kIcpGroup && passes <= (int64_t)max_iter; ++g, ++passes)
-      launch_icp_iteration(s, B[B_DESC].as<IcpDesc>(), B[B_STATE].as<IcpState>(), B[B_BLK].as<int32_t>(), n_blk,
-                           batch, B[B_X].as<double>(), B[B_QS].as<double>(), B[B_QJ].as<int32_t>(),
-                           B[B_BSTART].as<int32_t>(), B[B_NORMALS].as<double>(), B[B_COV_S].as<double>(),
-                           B[B_COV_T].as<double>(), gicp ? 2 : plane ? 1 : 0, B[B_MATCH].as<int32_t>(),
-                           B[B_PARTIALS].as<double>());
+      if (color)
+        iterate(h, ctx, n_blk, batch);
+      else
+        launch_icp_iteration(s, B[B_DESC].as<IcpDesc>(), B[B_STATE].as<IcpState>(), B[B_BLK].as<int32_t>(), n_blk,
+                             batch, B[B_X].as<double>(), B[B_QS].as<double>(), B[B_QJ].as<int32_t>(),
+                             B[B_BSTART].as<int32_t>(), B[B_NORMALS].as<double>(), B[B_COV_S].as<double>(),
+                             B[B_COV_T].as<double>(), gicp ? 2 : plane ? 1 : 0, B[B_MATCH].as<int32_t>(),
+                             B[B_PARTIALS].as<double>());
     launch_icp_live(s, B[B_STATE].as<IcpState>(), batch, B[B_LIVE].as<int32_t>());
     FCHK(h, hipGetLastError(), "ICP kernel launch");
     FCHK(h, hipMemcpyAsync(h->h_live, B[B_LIVE].p, sizeof(int32_t), hipMemcpyDeviceToHost, s),

@@ -1,6 +1,6 @@
 // icp_host.h -- what the host files of the ICP handle share (icp.hip: the iteration loop and covariance estimation;
 // icp_outlier.hip: self k-NN, outlier removal and the options; icp_normals.hip: normal estimation and the
-// self-estimating point-to-plane entry; icp_keypoints.hip: ISS keypoints): the handle and its buffers, and the scaffold
+// self-estimating point-to-plane entry; icp_keypoints.hip: ISS keypoints; icp_color.hip: Colored ICP): the handle and its buffers, and the scaffold
 // of a cloud call -- the entry checks (begin_cloud_call), the per-call index under construction (IcpIndex,
 // add_problem), the sizes of the index buffers by name (index_bytes, ensure_buffers), the packing and the uploads
 // (upload_points, upload_inputs), the index build (launch_index), the one copy back (copy_back, read_fallbacks) and
@@ -25,10 +25,12 @@ namespace thip {
 // B_N*: the descriptors, records and block maps of the normal estimation that precedes the iterations of
 // teaser_hip_icp_batch_auto (its other buffers are the ICP's own).  B_K*: the sorted cell index of ISS keypoint
 // detection (icp_keypoints.hip): descriptors, block map, keys and entries before and after the sort, the sorted points
-// and the sort's scratch
+// and the sort's scratch.  B_COLOR_*: Colored ICP (icp_color.hip): the per-problem IcpColorDesc records, one intensity per
+// source point, and per target point the {gradient, intensity} record; its gradient pass keeps its descriptors, records
+// and block maps in B_N* (a coloured call estimates no normals)
 enum { B_DESC, B_STATE, B_BLK, B_TBLK, B_X, B_Q, B_TBUCKET, B_BCOUNT, B_BSTART, B_CURSOR, B_QS, B_QJ, B_MATCH,
        B_PARTIALS, B_LIVE, B_NORMALS, B_COV_S, B_COV_T, B_NDESC, B_NKNN, B_NREC, B_NBLK, B_NTBLK, B_KDESC, B_KBLK,
-       B_KKEY, B_KIOTA, B_KSKEY, B_KSIDX, B_KSPTS, B_KTEMP, B_COUNT };
+       B_KKEY, B_KIOTA, B_KSKEY, B_KSIDX, B_KSPTS, B_KTEMP, B_COLOR_DESC, B_COLOR_S, B_COLOR_T, B_COUNT };
 
 }  // namespace thip
 
@@ -37,6 +39,7 @@ struct teaser_hip_icp : thip::HandleBase {
   thip::DevBuf buf[thip::B_COUNT];
   std::vector<double> stage;  // host packing of the points
   std::vector<double> back;   // self k-NN / outlier removal: the one copy back of a call
+  std::vector<double> cstage; // Colored ICP: host packing of the intensities and the {gradient, intensity} records
   int32_t knn_ring_cap = thip::kIcpKnnRingCap;  // option "knn_ring_cap"
   int64_t knn_fallbacks = 0;              // option "knn_fallbacks": queries of the last call served by the whole-cloud route
   ~teaser_hip_icp() {
@@ -290,14 +293,20 @@ int32_t run_self_knn(teaser_hip_icp* h, int32_t batch, const double* const* poin
 // targets lie in B_Q at its offsets.  Returns a status.
 typedef int32_t (*IcpPreIndexHook)(teaser_hip_icp* h, void* ctx, const IcpIndex& ix);
 
+// One iteration (a correspondence pass and its finalize) of a call that holds a Colored-ICP problem, enqueued on the
+// handle's buffers; ctx is the hook's.  icp.hip reaches the mode-3 launcher through it and names no launcher of its own.
+typedef void (*IcpIterateFn)(teaser_hip_icp* h, void* ctx, int n_blk, int batch);
+
 // Every batched ICP entry point (icp.hip).  max_method: the largest estimation method the entry accepts.  nsearch: NULL,
 // or per problem a record whose max_nn != 0 stands in for the dst_normals of a point-to-plane problem that gives none;
-// `hook` then has to fill those rows of B_NORMALS.
+// `hook` then has to fill those rows of B_NORMALS.  iterate: what enqueues an iteration when the call holds a
+// Colored-ICP problem (max_method = 3 needs it); the hook then has to fill B_COLOR_*.
 int32_t icp_run_batch(teaser_hip_icp* h, int32_t batch, const double* const* src, const int32_t* n_src,
                       const double* const* dst, const int32_t* n_dst, const double* init,
                       const teaser_icp_params_c* params, teaser_icp_result_c* out, int32_t* const* corr,
                       const double* const* dst_normals, const teaser_icp_estimation_c* est,
                       const double* const* src_cov, const double* const* dst_cov, int max_method,
-                      const teaser_icp_normal_search_c* nsearch, IcpPreIndexHook hook, void* ctx);
+                      const teaser_icp_normal_search_c* nsearch, IcpPreIndexHook hook, void* ctx,
+                      IcpIterateFn iterate = nullptr);
 
 }  // namespace thip

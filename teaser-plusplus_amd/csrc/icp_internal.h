@@ -22,7 +22,7 @@ constexpr int kIcpKnnRingCapMax = 16;
 constexpr int kIcpKnnScanBlocks = 2048;  // waves of the whole-cloud route (each loops over the worklist)
 
 // IcpDesc::method / IcpDesc::kernel: the values of teaser_icp_estimation_c (include/teaser_hip.h)
-enum { kIcpMethodPoint = 0, kIcpMethodPlane = 1, kIcpMethodGicp = 2 };
+enum { kIcpMethodPoint = 0, kIcpMethodPlane = 1, kIcpMethodGicp = 2, kIcpMethodColor = 3 };
 enum { kIcpKernelL2 = 0, kIcpKernelHuber = 1, kIcpKernelCauchy = 2, kIcpKernelGM = 3, kIcpKernelTukey = 4 };
 
 // One problem of a batch (host-built, read-only on the device).  Cell coordinates of a point x are
@@ -89,6 +89,25 @@ struct IcpNormalDesc {
   double ref[3];
 };
 
+// One cloud of a colour-gradient pass, beside its IcpDesc (the cloud is the descriptor's "target": the grid and r2 of the
+// gradient radius; blk_off / nblk count its blocks of kIcpCovBlock points).
+struct IcpGradDesc {
+  int32_t max_nn;     // 4 .. kIcpCovMaxNN
+  int32_t pad;
+};
+
+// One problem of a call that holds a Colored-ICP problem, beside its IcpDesc; read for method 3 only.
+struct IcpColorDesc {
+  double sg, sp;      // sqrt(lambda_geometric), sqrt(1 - lambda_geometric)
+};
+
+// What the mode-3 correspondence kernel gathers from besides the arrays of the other modes (kernel argument, by value).
+struct IcpColorArgs {
+  const IcpColorDesc* cd;  // one per problem
+  const double* rec_t;     // 4 doubles per target point at t_off: the colour gradient, then the intensity
+  const double* int_s;     // one intensity per source point at s_off
+};
+
 // Grid cell of one coordinate; host (descriptor set-up) and device (index build, search) run the same expression.
 __host__ __device__ inline int64_t icp_cell(double x, double origin, double inv_h) {
   double v = floor((x - origin) * inv_h);
@@ -112,6 +131,17 @@ void launch_icp_iteration(hipStream_t s, const IcpDesc* d_desc, IcpState* d_stat
                           int n_blk, int batch, double* d_x, const double* d_qs, const int32_t* d_qj,
                           const int32_t* d_bstart, const double* d_normals, const double* d_cov_s,
                           const double* d_cov_t, int mode, int32_t* d_match, double* d_partials);
+// One iteration of a call that holds a Colored-ICP problem (mode 3; kernels_icp.hip): launch_icp_iteration's arguments
+// and what the coloured branch gathers from.
+void launch_icp_iteration_color(hipStream_t s, const IcpDesc* d_desc, IcpState* d_state, const int32_t* d_blk_prob,
+                                int n_blk, int batch, double* d_x, const double* d_qs, const int32_t* d_qj,
+                                const int32_t* d_bstart, const double* d_normals, const double* d_cov_s,
+                                const double* d_cov_t, int32_t* d_match, double* d_partials, const IcpColorArgs& col);
+// Colour gradients of the indexed clouds (the Colored-ICP contract of include/teaser_hip.h): point i of a cloud reads its
+// normal at d_normals[3 (t_off + i)] and the intensities at d_rec[4 (t_off + .) + 3], and writes d_rec[4 (t_off + i) + 0..2].
+void launch_icp_color_gradients(hipStream_t s, const IcpDesc* d_desc, const IcpGradDesc* d_gd, const int32_t* d_blk_prob,
+                                int n_blk, int max_nn, const double* d_q, const double* d_qs, const int32_t* d_qj,
+                                const int32_t* d_bstart, const double* d_normals, double* d_rec);
 void launch_icp_covariances(hipStream_t s, const IcpDesc* d_desc, const IcpCovDesc* d_cov, const int32_t* d_blk_prob,
                             int n_blk, int max_nn, const double* d_q, const double* d_qs, const int32_t* d_qj,
                             const int32_t* d_bstart, double* d_out);

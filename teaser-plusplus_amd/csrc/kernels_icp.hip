@@ -33,6 +33,12 @@
 // the accumulated T (the transform the moved points X correspond to), W = adj(M) / det(M), and adds J^T W J and
 // J^T W e with J = [-[x']x | I].  Its point and plane branches are those of <1>, operation for operation.
 //
+// Colored ICP (IcpDesc::method = 3; "ICP refinement: Colored ICP" in include/teaser_hip.h): kMode = 3, launched only
+// for calls that hold a coloured problem.  It keeps the 29-value partial and the plane finalize and carries the branches
+// of <2> operation for operation; the coloured branch gathers once per matched source point the target's normal, its
+// {gradient, intensity} record and the source intensity (icp_color_device.h).  What it gathers from arrives in a trailing
+// parameter pack that is empty for <0>, <1> and <2>, whose signatures and code are therefore what they were.
+//
 // Covariance estimation (icp_cov_kernel): the same grid built over the cloud itself, one point per lane, the max_nn
 // smallest (d2, j) kept in a per-lane insertion-sorted list in LDS (slot-major, so the lanes of a wave hit distinct
 // banks; a per-lane register array indexed at run time would go to scratch), then the sums in list order, a cyclic
@@ -86,6 +92,10 @@ __device__ __forceinline__ double icp_kernel_weight(int kernel, double k, double
     default: return 1.0;
   }
 }
+
+}  // namespace thip
+#include "icp_color_device.h"  // icp_color_terms, behind icp_kernel_weight
+namespace thip {
 
 // ---- target index ---------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void icp_count_kernel(const IcpDesc* __restrict__ descs,
@@ -212,7 +222,9 @@ __device__ __forceinline__ void icp_gicp_terms(const double (&x)[3], const doubl
   v[28] = we[2];
 }
 
-template <int kMode>
+__device__ __forceinline__ const IcpColorArgs& icp_color_args(const IcpColorArgs& a) { return a; }
+
+template <int kMode, class... Color /* IcpColorArgs for kMode = 3, else nothing */>
 __global__ __launch_bounds__(kIcpBlock) void icp_corr_kernel(const IcpDesc* __restrict__ descs,
                                                              const IcpState* __restrict__ state,
                                                              const int32_t* __restrict__ blk_prob,
@@ -223,7 +235,8 @@ __global__ __launch_bounds__(kIcpBlock) void icp_corr_kernel(const IcpDesc* __re
                                                              const double* __restrict__ cov_s,
                                                              const double* __restrict__ cov_t,
                                                              int32_t* __restrict__ match,
-                                                             double* __restrict__ partials) {
+                                                             double* __restrict__ partials, const Color... color) {
+  static_assert(sizeof...(Color) == (kMode == 3 ? 1 : 0), "the colour arguments go with mode 3 alone");
   constexpr bool kPlane = kMode >= 1;
   constexpr int NS = kPlane ? kIcpPlaneSums : kIcpSums;
   __shared__ double s[4][NS];
@@ -310,9 +323,17 @@ __global__ __launch_bounds__(kIcpBlock) void icp_corr_kernel(const IcpDesc* __re
         }
 #pragma unroll
         for (int r = 0; r < 6; ++r) v[23 + r] = wr * J[r];
-      } else if (kMode == 2 && d.method == kIcpMethodGicp) {  // uniform over the block
-        if constexpr (kMode == 2)
+      } else if (kMode >= 2 && d.method == kIcpMethodGicp) {  // uniform over the block
+        if constexpr (kMode >= 2)
           icp_gicp_terms(pc, qc, state[p].T, cov_s + 6 * (d.s_off + i), cov_t + 6 * (d.t_off + bj), v);
+      } else if (kMode == 3 && d.method == kIcpMethodColor) {  // uniform over the block
+        if constexpr (kMode == 3) {
+          const IcpColorArgs& ca = icp_color_args(color...);
+          const double* np = normals + 3 * (d.t_off + bj);
+          const double n[3] = {np[0], np[1], np[2]};
+          icp_color_terms(pc, qc, n, ca.rec_t + 4 * (d.t_off + bj), ca.int_s[d.s_off + i], ca.cd[p], d.kernel,
+                          d.kernel_k, v);
+        }
       } else {
 #pragma unroll
         for (int r = 0; r < 3; ++r) {
@@ -415,8 +436,9 @@ __global__ __launch_bounds__(256) void icp_finalize_kernel(const IcpDesc* __rest
   }
   // Umeyama without scaling on the sums centred on d.centre: H = sum p' q'^T - sum p' (sum q')^T / n
   double U[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
-  if (kPlane && (d.method == kIcpMethodPlane || (kMode == 2 && d.method == kIcpMethodGicp))) {
-    if (cnt > 0) icp_plane_step(tot, d.centre, U);  // Generalized ICP: the same 29 sums, the same solve
+  if (kPlane && (d.method == kIcpMethodPlane || (kMode >= 2 && d.method == kIcpMethodGicp) ||
+                 (kMode == 3 && d.method == kIcpMethodColor))) {
+    if (cnt > 0) icp_plane_step(tot, d.centre, U);  // Generalized and Colored ICP: the same 29 sums, the same solve
   } else if (cnt > 0) {
     double mp[3], mq[3], H[9], R[9];
     for (int r = 0; r < 3; ++r) {
@@ -643,6 +665,16 @@ void launch_icp_iteration(hipStream_t s, const IcpDesc* d_desc, IcpState* d_stat
   else
     icp_iteration<0>(s, d_desc, d_state, d_blk_prob, n_blk, batch, d_x, d_qs, d_qj, d_bstart, d_normals, d_cov_s,
                      d_cov_t, d_match, d_partials);
+}
+
+void launch_icp_iteration_color(hipStream_t s, const IcpDesc* d_desc, IcpState* d_state, const int32_t* d_blk_prob,
+                                int n_blk, int batch, double* d_x, const double* d_qs, const int32_t* d_qj,
+                                const int32_t* d_bstart, const double* d_normals, const double* d_cov_s,
+                                const double* d_cov_t, int32_t* d_match, double* d_partials, const IcpColorArgs& col) {
+  if (n_blk > 0)
+    hipLaunchKernelGGL((icp_corr_kernel<3, IcpColorArgs>), dim3(n_blk), dim3(kIcpBlock), 0, s, d_desc, d_state,
+                       d_blk_prob, d_x, d_qs, d_qj, d_bstart, d_normals, d_cov_s, d_cov_t, d_match, d_partials, col);
+  hipLaunchKernelGGL(icp_finalize_kernel<3>, dim3(batch), dim3(256), 0, s, d_desc, d_state, d_partials);
 }
 
 void launch_icp_covariances(hipStream_t s, const IcpDesc* d_desc, const IcpCovDesc* d_cov, const int32_t* d_blk_prob,

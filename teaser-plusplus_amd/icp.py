@@ -4,7 +4,8 @@
 TransformationEstimationPointToPoint(with_scaling=False) or TransformationEstimationPointToPlane(kernel) (target
 normals given by the caller, robust kernels L2 / Huber / Cauchy / GM / Tukey) or the formulation of
 TransformationEstimationForGeneralizedICP (per-point covariances of both clouds, L2 only; ``estimate_covariances``
-computes them on the GPU), written out in include/teaser_hip.h ("ICP refinement").
+computes them on the GPU) or of TransformationEstimationForColoredICP (colours of both clouds and target normals;
+``registration_colored_icp``), written out in include/teaser_hip.h ("ICP refinement").
 
 One library handle is kept per device between calls (no HIP context per call); calls from several threads are safe --
 each handle has a lock, so calls for one device run one after the other.  device=-1 means the calling thread's
@@ -41,6 +42,14 @@ class IcpNormalSearchC(C.Structure):
 assert C.sizeof(IcpNormalSearchC) == 48  # teaser_icp_normal_search_c: the header asserts the same
 
 
+class IcpColorC(C.Structure):
+    _fields_ = [("lambda_geometric", C.c_double), ("gradient_radius", C.c_double), ("gradient_max_nn", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
+assert C.sizeof(IcpColorC) == 24  # teaser_icp_color_c: the header asserts the same
+
+
 def declare(L):
     """ctypes signatures of the ICP entry points (called by the package's lib())."""
     L.teaser_hip_icp_params_default.argtypes = [C.POINTER(IcpParamsC)]
@@ -62,6 +71,12 @@ def declare(L):
                                                C.POINTER(_dp), C.POINTER(_dp), C.POINTER(_dp)]
     L.teaser_hip_icp_batch_auto.argtypes = L.teaser_hip_icp_batch_cov.argtypes + [C.POINTER(IcpNormalSearchC)]
     L.teaser_hip_icp_solve_auto.argtypes = L.teaser_hip_icp_solve_cov.argtypes + [C.POINTER(IcpNormalSearchC)]
+    L.teaser_hip_icp_color_default.argtypes = [C.POINTER(IcpColorC)]
+    L.teaser_hip_icp_batch_color.argtypes = L.teaser_hip_icp_batch_cov.argtypes + [C.POINTER(_dp), C.POINTER(_dp),
+                                                                                   C.POINTER(_dp), C.POINTER(IcpColorC)]
+    L.teaser_hip_icp_solve_color.argtypes = L.teaser_hip_icp_solve_cov.argtypes + [_dp, _dp, _dp, C.POINTER(IcpColorC)]
+    L.teaser_hip_icp_color_gradients_batch.argtypes = [_vp, C.c_int32, C.POINTER(_dp), _ip, C.POINTER(_dp),
+                                                       C.POINTER(_dp), _dp, _ip, C.POINTER(_dp)]
     L.teaser_hip_icp_information_batch.argtypes = [_vp, C.c_int32, C.POINTER(_dp), _ip, C.POINTER(_dp), _ip, _dp, _dp,
                                                    _dp, C.POINTER(IcpResultC), C.POINTER(_ip)]
     L.teaser_hip_icp_information.argtypes = [_vp, _dp, C.c_int32, _dp, C.c_int32, _dp, C.c_double, _dp,
@@ -160,6 +175,34 @@ class TransformationEstimationForGeneralizedICP:
 
 
 MAX_NN_LIMIT = 100  # TEASER_HIP_ICP_COV_MAX_NN
+
+
+class TransformationEstimationForColoredICP:
+    """Open3D's Colored-ICP estimation (Park, Zhou, Koltun, ICCV 2017): the joint geometric + photometric objective,
+    lambda_geometric the weight of the geometric term, with an optional robust kernel applied to both residuals
+    (default L2Loss).  The colours and the target normals are given to registration_colored_icp / registration_icp;
+    gradient_radius (None: twice max_correspondence_distance) and gradient_max_nn choose the neighbourhood the target's
+    colour gradients are estimated from."""
+
+    def __init__(self, lambda_geometric=0.968, kernel=None, gradient_radius=None, gradient_max_nn=30):
+        kernel = L2Loss() if kernel is None else kernel
+        if not isinstance(kernel, _RobustKernel):
+            raise ValueError("kernel must be L2Loss, HuberLoss, CauchyLoss, GMLoss or TukeyLoss")
+        lambda_geometric = float(lambda_geometric)
+        if not (np.isfinite(lambda_geometric) and 0.0 <= lambda_geometric <= 1.0):
+            raise ValueError("lambda_geometric must lie in [0, 1]")
+        if gradient_radius is not None and not (np.isfinite(gradient_radius) and gradient_radius > 0):
+            raise ValueError("gradient_radius must be finite and > 0")
+        if not 4 <= int(gradient_max_nn) <= MAX_NN_LIMIT:
+            raise ValueError("gradient_max_nn must lie in [4, %d]" % MAX_NN_LIMIT)
+        self.lambda_geometric = lambda_geometric
+        self.kernel = kernel
+        self.gradient_radius = None if gradient_radius is None else float(gradient_radius)
+        self.gradient_max_nn = int(gradient_max_nn)
+
+    def record(self):
+        return IcpColorC(self.lambda_geometric, 0.0 if self.gradient_radius is None else self.gradient_radius,
+                         self.gradient_max_nn, 0)
 
 
 class RegistrationResult:
@@ -262,8 +305,11 @@ def _estimation(m):
         return 1, m.kernel.code, m.kernel.k
     if isinstance(m, TransformationEstimationForGeneralizedICP):
         return 2, 0, 1.0
+    if isinstance(m, TransformationEstimationForColoredICP):
+        return 3, m.kernel.code, m.kernel.k
     raise ValueError("estimation_method must be TransformationEstimationPointToPoint(with_scaling=False), "
-                     "TransformationEstimationPointToPlane(kernel) or TransformationEstimationForGeneralizedICP()")
+                     "TransformationEstimationPointToPlane(kernel), TransformationEstimationForGeneralizedICP() or "
+                     "TransformationEstimationForColoredICP()")
 
 
 def _covariances(a, n, what, k):
@@ -292,15 +338,44 @@ def _per_problem_covariances(given, ests, clouds, what):
     return out
 
 
+def _per_problem_rows(given, ests, clouds, what, required=True):
+    """One n x 3 array per Colored-ICP problem (None elsewhere, or where an optional one is not given)."""
+    b = len(ests)
+    out = [None] * b
+    if not any(m[0] == 3 for m in ests):
+        return out
+    if given is None or len(given) != b:
+        if not required and given is None:
+            return out
+        raise ValueError("Colored ICP needs %s: one entry per problem" % what)
+    for k in range(b):
+        if ests[k][0] != 3:
+            continue
+        if given[k] is None:
+            if required:
+                raise ValueError("Colored ICP needs %s (problem %d)" % (what, k))
+            continue
+        a = _points(given[k], what)
+        if a.shape != clouds[k].shape:
+            raise ValueError("%s must have the cloud's shape %s, got %s (problem %d)"
+                             % (what, clouds[k].shape, a.shape, k))
+        out[k] = a
+    return out
+
+
 def registration_icp_batch(sources, targets, max_correspondence_distance, inits=None, criteria=None, device=-1,
                            estimation_methods=None, target_normals=None, source_covariances=None,
-                           target_covariances=None):
+                           target_covariances=None, *, source_colors=None, target_colors=None,
+                           target_color_gradients=None):
     """One launch sequence for many independent problems (mixed sizes allowed).  max_correspondence_distance and
     criteria: one value for all or one per problem; inits: None (identity), one 4 x 4 for all, or one per problem;
     estimation_methods: None (point-to-point), one for all or one per problem; target_normals: None, or one entry per
     problem (None for a point-to-point problem, else one normal per target point, or a KDTreeSearchParamHybrid /
     KDTreeSearchParamKNN object: the normals are then estimated from the target on the device); source_covariances /
-    target_covariances: None, or one entry per problem (None unless the problem is Generalized ICP, else n x 3 x 3).
+    target_covariances: None, or one entry per problem (None unless the problem is Generalized ICP, else n x 3 x 3);
+    source_colors / target_colors: None, or one entry per problem (None unless the problem is Colored ICP, else n x 3
+    colours; such a problem also needs its target normals as an array); target_color_gradients: None, or per problem
+    None (estimated on the device) or n_t x 3.
     Returns a list of RegistrationResult, each identical to the same problem run alone."""
     from . import lib
     srcs = [_points(s, "source") for s in sources]
@@ -311,8 +386,10 @@ def registration_icp_batch(sources, targets, max_correspondence_distance, inits=
     ests = estimation_methods if isinstance(estimation_methods, (list, tuple)) else [estimation_methods] * b
     if len(ests) != b:
         raise ValueError("estimation_methods: one per problem or one for all")
+    methods = ests
     ests = [_estimation(m) for m in ests]
     plane = any(m[0] == 1 for m in ests)
+    colored = any(m[0] == 3 for m in ests)
     normals = [None] * b
     searches = [None] * b  # a search-parameter object in place of normals: they are estimated on the device
     if plane:
@@ -331,6 +408,25 @@ def registration_icp_batch(sources, targets, max_correspondence_distance, inits=
                 raise ValueError("target_normals must have the target's shape %s, got %s (problem %d)"
                                  % (dsts[k].shape, nv.shape, k))
             normals[k] = nv
+    if colored:
+        if target_normals is None or len(target_normals) != b:
+            raise ValueError("Colored ICP needs target_normals: one entry per problem")
+        for k in range(b):
+            if ests[k][0] != 3:
+                continue
+            if target_normals[k] is None or isinstance(target_normals[k], _NormalSearch):
+                raise ValueError("Colored ICP needs target_normals as an array: estimate_normals first "
+                                 "(problem %d)" % k)
+            nv = _points(target_normals[k], "target_normals")
+            if nv.shape != dsts[k].shape:
+                raise ValueError("target_normals must have the target's shape %s, got %s (problem %d)"
+                                 % (dsts[k].shape, nv.shape, k))
+            normals[k] = nv
+        if any(sp_ is not None for sp_ in searches):
+            raise ValueError("a batch with a Colored-ICP problem takes every target_normals as an array")
+    col_s = _per_problem_rows(source_colors, ests, srcs, "source_colors")
+    col_t = _per_problem_rows(target_colors, ests, dsts, "target_colors")
+    grad_t = _per_problem_rows(target_color_gradients, ests, dsts, "target_color_gradients", required=False)
     gicp = any(m[0] == 2 for m in ests)
     cov_s = _per_problem_covariances(source_covariances, ests, srcs, "source_covariances")
     cov_t = _per_problem_covariances(target_covariances, ests, dsts, "target_covariances")
@@ -357,14 +453,22 @@ def registration_icp_batch(sources, targets, max_correspondence_distance, inits=
     fn = L.teaser_hip_icp_batch  # point-to-point only: the original entry point
     args = (b, sp, n_s.ctypes.data_as(_ip), tp, n_t.ctypes.data_as(_ip),
             None if init is None else init.ctypes.data_as(_dp), params, out, cp)
-    if plane or gicp:
+    if plane or gicp or colored:
         fn = L.teaser_hip_icp_batch_ex
         args += ((_dp * max(b, 1))(*[None if nv is None else nv.ctypes.data_as(_dp) for nv in normals]),
                  (IcpEstimationC * max(b, 1))(*[IcpEstimationC(*m) for m in ests]))
-    if gicp:  # the entry that takes covariances; it serves the other two methods of a mixed batch too
+    if gicp or colored:  # the entry that takes covariances; it serves the other two methods of a mixed batch too
         fn = L.teaser_hip_icp_batch_cov
         args += ((_dp * max(b, 1))(*[None if c is None else c.ctypes.data_as(_dp) for c in cov_s]),
                  (_dp * max(b, 1))(*[None if c is None else c.ctypes.data_as(_dp) for c in cov_t]))
+    if colored:  # the entry that takes colours; it serves the other three methods of a mixed batch too
+        def ptrs(arrs):
+            return (_dp * max(b, 1))(*[None if a is None else a.ctypes.data_as(_dp) for a in arrs])
+
+        fn = L.teaser_hip_icp_batch_color
+        args += (ptrs(col_s), ptrs(col_t), ptrs(grad_t),
+                 (IcpColorC * max(b, 1))(*[m.record() if isinstance(m, TransformationEstimationForColoredICP)
+                                           else IcpColorC(0.968, 0.0, 30, 0) for m in methods]))
     if any(sp_ is not None for sp_ in searches):  # the entry that estimates missing target normals itself
         if not gicp:
             args += (None, None)
@@ -383,19 +487,27 @@ def registration_icp_batch(sources, targets, max_correspondence_distance, inits=
 
 def registration_icp(source, target, max_correspondence_distance, init=np.eye(4), estimation_method=None,
                      criteria=None, device=-1, *, target_normals=None, source_covariances=None,
-                     target_covariances=None):
+                     target_covariances=None, source_colors=None, target_colors=None, target_color_gradients=None):
     """Open3D's registration_icp (same argument order): refines `init` so that it maps source onto target.
     source / target: n x 3 points (np.asarray(pcd.points)).  estimation_method: None or
     TransformationEstimationPointToPoint() (with_scaling=False), or TransformationEstimationPointToPlane(kernel), which
     needs target_normals (n_t x 3, np.asarray(target_pcd.normals), or a KDTreeSearchParamHybrid / KDTreeSearchParamKNN
     object to estimate them from the target on the device), or TransformationEstimationForGeneralizedICP(),
-    which needs source_covariances (n_s x 3 x 3) and target_covariances (n_t x 3 x 3)."""
+    which needs source_covariances (n_s x 3 x 3) and target_covariances (n_t x 3 x 3), or
+    TransformationEstimationForColoredICP(), which needs source_colors (n_s x 3), target_colors (n_t x 3) and
+    target_normals (n_t x 3) and takes target_color_gradients (n_t x 3; None: estimated on the device)."""
     if estimation_method is not None and not isinstance(
             estimation_method, (TransformationEstimationPointToPoint, TransformationEstimationPointToPlane,
-                                TransformationEstimationForGeneralizedICP)):
+                                TransformationEstimationForGeneralizedICP, TransformationEstimationForColoredICP)):
         raise ValueError("only TransformationEstimationPointToPoint(with_scaling=False), "
-                         "TransformationEstimationPointToPlane(kernel) and "
-                         "TransformationEstimationForGeneralizedICP() are supported")
+                         "TransformationEstimationPointToPlane(kernel), "
+                         "TransformationEstimationForGeneralizedICP() and "
+                         "TransformationEstimationForColoredICP() are supported")
+    if isinstance(estimation_method, TransformationEstimationForColoredICP):
+        for given, what in ((source_colors, "source_colors"), (target_colors, "target_colors"),
+                            (target_normals, "target_normals")):
+            if given is None:
+                raise ValueError("TransformationEstimationForColoredICP needs %s" % what)
     if isinstance(estimation_method, TransformationEstimationPointToPlane) and target_normals is None:
         raise ValueError("TransformationEstimationPointToPlane needs target_normals")
     if isinstance(estimation_method, TransformationEstimationForGeneralizedICP):
@@ -407,7 +519,11 @@ def registration_icp(source, target, max_correspondence_distance, init=np.eye(4)
                                   criteria=[criteria], device=device, estimation_methods=[estimation_method],
                                   target_normals=None if target_normals is None else [target_normals],
                                   source_covariances=None if source_covariances is None else [source_covariances],
-                                  target_covariances=None if target_covariances is None else [target_covariances])[0]
+                                  target_covariances=None if target_covariances is None else [target_covariances],
+                                  source_colors=None if source_colors is None else [source_colors],
+                                  target_colors=None if target_colors is None else [target_colors],
+                                  target_color_gradients=(None if target_color_gradients is None
+                                                          else [target_color_gradients]))[0]
 
 
 def evaluate_registration_batch(sources, targets, max_correspondence_distance, transformations=None, device=-1):
@@ -591,3 +707,63 @@ def registration_generalized_icp(source, target, max_correspondence_distance, in
             target_covariances = next(found)
     return registration_icp(source, target, max_correspondence_distance, init, est, criteria, device,
                             source_covariances=source_covariances, target_covariances=target_covariances)
+
+
+def estimate_color_gradients_batch(clouds, normals, colors, radius, max_nn=30, device=-1):
+    """The colour gradients Colored ICP uses, for many clouds in one launch sequence (include/teaser_hip.h, "ICP
+    refinement: Colored ICP"): per point the max_nn nearest neighbours inside `radius`, projected onto the tangent plane
+    of its normal, and the least-squares gradient of the intensity ((r + g) + b) / 3 over them; 0 below 4 neighbours.
+    clouds, normals, colors: one n x 3 array per cloud each; radius, max_nn: one value for all clouds or one per cloud.
+    Returns a list of n x 3 arrays, each identical to the same cloud estimated alone."""
+    from . import lib
+    pts = [_points(c, "points") for c in clouds]
+    b = len(pts)
+    if len(normals) != b or len(colors) != b:
+        raise ValueError("clouds, normals and colors differ in length")
+    nrm = [_points(a, "normals") for a in normals]
+    col = [_points(a, "colors") for a in colors]
+    for k in range(b):
+        if nrm[k].shape != pts[k].shape or col[k].shape != pts[k].shape:
+            raise ValueError("normals and colors must have the cloud's shape %s (cloud %d)" % (pts[k].shape, k))
+    rs = np.ascontiguousarray(np.broadcast_to(np.asarray(radius, dtype=np.float64), (b,)))
+    ks = np.ascontiguousarray(np.broadcast_to(np.asarray(max_nn), (b,)).astype(np.int32))
+    if b and (ks.min() < 4 or ks.max() > MAX_NN_LIMIT):
+        raise ValueError("max_nn must lie in [4, %d]" % MAX_NN_LIMIT)
+    if b and not (np.isfinite(rs).all() and (rs > 0).all()):
+        raise ValueError("radius must be finite and > 0")
+    out = [np.empty((len(p), 3)) for p in pts]
+    if b == 0:
+        return out
+    n = np.array([len(p) for p in pts], dtype=np.int32)
+    ptrs = lambda arrs: (_dp * b)(*[a.ctypes.data_as(_dp) for a in arrs])  # noqa: E731
+    _handle(device).call(lib().teaser_hip_icp_color_gradients_batch, b, ptrs(pts), n.ctypes.data_as(_ip), ptrs(nrm),
+                         ptrs(col), rs.ctypes.data_as(_dp), ks.ctypes.data_as(_ip), ptrs(out))
+    return out
+
+
+def estimate_color_gradients(points, normals, colors, radius, max_nn=30, device=-1):
+    """estimate_color_gradients_batch for one cloud: n x 3 points, normals and colours -> n x 3 gradients."""
+    return estimate_color_gradients_batch([points], [normals], [colors], radius, max_nn, device)[0]
+
+
+def registration_colored_icp(source, target, max_correspondence_distance, init=np.eye(4), estimation_method=None,
+                             criteria=None, *, source_colors=None, target_colors=None, target_normals=None,
+                             gradient_radius=None, gradient_max_nn=30, target_color_gradients=None, device=-1):
+    """Open3D's registration_colored_icp (same leading arguments; the colours and normals Open3D reads from its point
+    clouds are keyword arguments here).  estimation_method: None or TransformationEstimationForColoredICP(...);
+    gradient_radius / gradient_max_nn: the neighbourhood of the target's colour gradients (None: twice
+    max_correspondence_distance, Open3D's choice), unless target_color_gradients gives them.  The target normals are not
+    estimated here: estimate_normals first."""
+    est = TransformationEstimationForColoredICP() if estimation_method is None else estimation_method
+    if not isinstance(est, TransformationEstimationForColoredICP):
+        raise ValueError("estimation_method must be TransformationEstimationForColoredICP()")
+    for given, what in ((source_colors, "source_colors"), (target_colors, "target_colors"),
+                        (target_normals, "target_normals")):
+        if given is None:
+            raise ValueError("registration_colored_icp needs %s" % what)
+    est = TransformationEstimationForColoredICP(
+        est.lambda_geometric, est.kernel, est.gradient_radius if gradient_radius is None else gradient_radius,
+        est.gradient_max_nn if gradient_max_nn == 30 else gradient_max_nn)
+    return registration_icp(source, target, max_correspondence_distance, init, est, criteria, device,
+                            target_normals=target_normals, source_colors=source_colors, target_colors=target_colors,
+                            target_color_gradients=target_color_gradients)
