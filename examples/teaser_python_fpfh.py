@@ -11,6 +11,12 @@ on the MI355X.  Usage:
                                           [--icp-gicp [--gicp-radius R --gicp-max-nn K]] [--batch K]
                                           [--knn K [--no-mutual]] [--tuple-scale S [--tuple-seed N]]
                                           [--iss [--iss-radii RS,RN]]
+                                          [--ransac [--ransac-iterations N --ransac-seed N]]
+
+--ransac runs Open3D's registration_ransac_based_on_correspondence on the GPU on the SAME correspondences the TEASER++
+solver got (max_correspondence_distance = 1.5 voxels, the edge-length checker at 0.9 and the distance checker at 1.5
+voxels, as Open3D's global-registration tutorial sets them) and prints its pose, fitness, RMSE and trial counts beside
+TEASER++'s, with the rotation and translation difference between the two.  --ransac-iterations is RANSAC-1K / 10K's N.
 
 --iss detects ISS keypoints (Open3D's compute_iss_keypoints) in both down-sampled clouds on the GPU and matches only
 them: FPFH is still computed on the whole clouds (its neighbourhoods need every point), the descriptor rows at the
@@ -164,6 +170,10 @@ def main():
                     help="match only the ISS keypoints of both clouds (detected on the GPU); single pair only")
     ap.add_argument("--iss-radii", default="", metavar="RS,RN",
                     help="with --iss: salient and non-maximum-suppression radius (default: 6 and 4 resolutions)")
+    ap.add_argument("--ransac", action="store_true",
+                    help="also run RANSAC on the same correspondences (on the GPU) and print it beside TEASER++")
+    ap.add_argument("--ransac-iterations", type=int, default=100000, metavar="N")
+    ap.add_argument("--ransac-seed", type=int, default=1, metavar="N", help="seed of the trials (0: the clock)")
     a = ap.parse_args()
     if a.iss and a.batch > 0:
         ap.error("--iss registers a single pair: it cannot be combined with --batch")
@@ -233,6 +243,25 @@ def main():
     print("%sfront-end %.1f ms, registration %.1f ms" % ("" if t_ds is None else "down-sampling %.1f ms, " % (1e3 * t_ds),
                                                        1e3 * (t1 - t0), 1e3 * (t2 - t1)))
     print("R =\n%s\nt = %s" % (sol.rotation, sol.translation))
+    if a.ransac:
+        P, Q = np.asarray(A, dtype=np.float64), np.asarray(B, dtype=np.float64)
+        pairs = np.array(corr, dtype=np.int32).reshape(-1, 2)
+        checkers = [tp.CorrespondenceCheckerBasedOnEdgeLength(0.9), tp.CorrespondenceCheckerBasedOnDistance(1.5 * vox)]
+        crit = tp.RANSACConvergenceCriteria(a.ransac_iterations, 0.999)
+        tp.registration_ransac_based_on_correspondence(P[:3], Q[:3], [[0, 0]] * 3, vox, seed=1,
+                                                       criteria=tp.RANSACConvergenceCriteria(1, 0.999))  # the handle
+        t3 = time.perf_counter()
+        rs = tp.registration_ransac_based_on_correspondence(P, Q, pairs, 1.5 * vox, None, 3, checkers, crit,
+                                                            seed=a.ransac_seed)
+        t4 = time.perf_counter()
+        Rr, tr = rs.transformation[:3, :3], rs.transformation[:3, 3]
+        cos = min(1.0, max(-1.0, (np.trace(Rr.T @ sol.rotation) - 1.0) / 2.0))
+        print("RANSAC on the same %d correspondences: %d of %d trials valid, best trial %d, %.1f ms"
+              % (len(pairs), rs.valid_trials, rs.trials, rs.best_trial, 1e3 * (t4 - t3)))
+        print("RANSAC fitness %.6f rmse %.6f inliers %d" % (rs.fitness, rs.inlier_rmse, len(rs.correspondence_set)))
+        print("R_ransac =\n%s\nt_ransac = %s" % (Rr, tr))
+        print("RANSAC against TEASER++: rotation %.4g rad, translation %.4g" % (np.arccos(cos),
+                                                                               np.linalg.norm(tr - sol.translation)))
     if a.certify:
         c = np.array(corr)
         inl = np.zeros(len(c), dtype=bool)

@@ -55,5 +55,11 @@ struct LazyPoseGraph : LazyHandle<teaser_hip_posegraph, teaser_hip_posegraph_des
   }
 };
 
+struct LazyRansac : LazyHandle<teaser_hip_ransac, teaser_hip_ransac_destroy> {
+  void create(const char* who) {
+    if (!h_) created(who, "ransac", teaser_hip_ransac_create(/*device=*/-1, &h_));
+  }
+};
+
 }  // namespace detail
 }  // namespace teaser

@@ -1241,6 +1241,113 @@ TEASER_HIP_API int32_t teaser_hip_posegraph_linearize(
     const double* edge_information, const uint8_t* edge_uncertain, const teaser_posegraph_option_c* option,
     double* e, double* r, double* l, double* mu, double* F, double* H, double* g);
 
+/* RANSAC registration on correspondences: Open3D's registration_ransac_based_on_correspondence with
+ * TransformationEstimationPointToPoint(with_scaling = false), CorrespondenceCheckerBasedOnEdgeLength and
+ * CorrespondenceCheckerBasedOnDistance, batched, on its OWN handle.  Open3D is RESTATED here, not run: what follows is
+ * the contract, and where it departs from Open3D it says so.
+ * Per problem: source P (n_s x 3 doubles) and target Q (n_t x 3 doubles), xyz interleaved; ncorr pairs (i, j) int32,
+ * used in the caller's order, repeats allowed; r = max_correspondence_distance; ransac_n in 3 .. 8; max_iteration
+ * (int32 >= 0); confidence in [0, 1]; a uint64 seed; optionally the edge-length checker with its threshold s in (0, 1]
+ * and the distance checker with its threshold d > 0.  apply(T, p) is the ICP contract's (above), nothing fused.
+ *   trial i (int64, from 0): its samples are c_k = z(seed, ransac_n i + k + 1) mod ncorr for k = 0 .. ransac_n - 1,
+ *            z(seed, m) the splitmix64 finaliser of seed + m 0x9E3779B97F4A7C15 exactly as the tuple-test contract
+ *            writes it (wrapping 64-bit arithmetic, the exact 64-bit remainder).  A trial is a function of (seed, i)
+ *            alone and samples WITH replacement, as Open3D does (Open3D draws from its own generator, so its trials are
+ *            other trials).  seed = 0 means "from the clock": the call reads time(NULL) once and uses that value for
+ *            every problem whose seed is 0.
+ *   edge-length checker: for all a < b among the samples, ls = |P[i_a] - P[i_b]|, lt = |Q[j_a] - Q[j_b]|, each
+ *            sqrt((dx dx + dy dy) + dz dz) in FP64 with a correctly rounded sqrt; the trial fails when ls < lt s or
+ *            lt < ls s for any pair.
+ *   estimate: Umeyama without scaling on the ransac_n sampled pairs: mu_P, mu_Q = the sums in sample order divided by
+ *            ransac_n; H = sum (p - mu_P)(q - mu_Q)^T in sample order; R = V diag(1, 1, det) U^T from the SVD of H as
+ *            the ICP contract's umeyama, t = mu_Q - R mu_P, T = [R | t].  Where rank(H) <= 1 (repeated samples,
+ *            collinear triples) R is a maximiser of tr(R H) among the proper rotations, not a specified one, exactly
+ *            as the ICP contract words it; H = 0 gives the identity rotation.
+ *   distance checker: the trial fails when sqrt(d2(apply(T, P[i_k]), Q[j_k])) > d for any sample k.
+ *   score    of a trial that passed its checkers, over ALL ncorr pairs in input order: x = apply(T, P[i]),
+ *            d2 = (dx dx + dy dy) + dz dz, dx = x.x - Q[j].x; the pair is an inlier iff d2 < r r -- the rule of corr()
+ *            above.  Open3D compares sqrt(d2) < r: the two differ only for a pair at the boundary.  count = the number
+ *            of inliers; S = the sum of d2 over the inliers in this order: the pairs are cut into blocks of 256
+ *            consecutive input positions, a block's inliers are added in ascending position starting from 0, and the
+ *            block sums are added in ascending block order starting from 0.  fitness = count / ncorr,
+ *            inlier_rmse = sqrt(S / count), 0 when count = 0.
+ *   loop     Open3D's, as ONE thread runs it (Open3D runs it in parallel and its result depends on the schedule):
+ *            best = {identity, count 0, rmse 0}, est_k = max_iteration; for i = 0, 1, ... while i < max_iteration and
+ *            i < est_k: a trial that fails a checker is skipped; it replaces best iff count > best.count, or
+ *            count == best.count and rmse < best.rmse (strict: ties stay with the earlier trial); on a replacement
+ *            k = log(1 - confidence) / log(1 - pow(count / ncorr, ransac_n)) in host double with the C library's log
+ *            and pow, and if k < est_k then est_k = ceil(k).  The IEEE special cases fall as they fall: confidence = 1
+ *            gives k = +inf or NaN and never stops early; count = ncorr gives k = 0 and stops at once; a ratio so
+ *            small that 1 - pow(..) rounds to 1 gives k = -inf and stops at once, too.
+ * Output per problem: the winning trial's T bit for bit, fitness, inlier_rmse, n_correspondences = its inlier count,
+ * best_trial (-1: no trial replaced the start), trials = the loop indices visited, valid_trials = those of them that
+ * passed their checkers, and optionally the inlier pairs of T in input order.  The result is a function of the inputs
+ * alone: not of how the trials are cut into launches ("chunk_trials" below), not of the batch around the problem, and
+ * the same bits run to run.  Work past the stopping trial is discarded, never reported.
+ * ncorr < ransac_n or max_iteration = 0 is not an error: the result is the start (identity, zeros, best_trial = -1,
+ * trials = 0).  TEASER_HIP_ERR_BAD_ARG (teaser_hip_ransac_last_error names the argument and the problem), found on the
+ * host before anything is launched or written: a non-finite or non-positive r, ransac_n outside 3 .. 8, a confidence
+ * outside [0, 1] or NaN, a negative max_iteration, a checker threshold out of range, an index outside its cloud,
+ * non-finite points, NULL where a count is positive.  NOT OFFERED, and refused by name with the same status rather
+ * than stubbed: with_scaling, point-to-plane estimation inside RANSAC, the normal-angle checker. */
+typedef struct teaser_ransac_params_c {
+  double max_correspondence_distance; /* r; no default (Open3D's argument is required) */
+  int32_t ransac_n;                   /* 3 */
+  int32_t max_iteration;              /* 100000 */
+  double confidence;                  /* 0.999 */
+  uint64_t seed;                      /* 0: from the clock */
+  double edge_length_threshold;       /* 0: checker off; else s in (0, 1] (Open3D's similarity_threshold) */
+  double distance_threshold;          /* 0: checker off; else d > 0 */
+  int32_t with_scaling;               /* must be 0 */
+  int32_t estimation;                 /* must be 0 (point to point) */
+  int32_t normal_checker;             /* must be 0 */
+  int32_t reserved;
+} teaser_ransac_params_c;
+typedef struct teaser_ransac_result_c {
+  double transformation[16]; /* row-major 4 x 4 */
+  double fitness;
+  double inlier_rmse;
+  int64_t best_trial;
+  int64_t trials;
+  int64_t valid_trials;
+  int32_t n_correspondences;
+  int32_t reserved;
+} teaser_ransac_result_c;
+typedef struct teaser_hip_ransac teaser_hip_ransac;
+/* device < 0: the current HIP device.  TEASER_HIP_ERR_NO_DEVICE without a GPU: there is no CPU path. */
+TEASER_HIP_API int32_t teaser_hip_ransac_create(int32_t device, teaser_hip_ransac** out);
+TEASER_HIP_API int32_t teaser_hip_ransac_destroy(teaser_hip_ransac* ransac);
+TEASER_HIP_API const char* teaser_hip_ransac_last_error(const teaser_hip_ransac* ransac);
+/* The defaults noted beside the fields above (Open3D's RANSACConvergenceCriteria; both checkers off). */
+TEASER_HIP_API int32_t teaser_hip_ransac_params_default(teaser_ransac_params_c* params);
+/* `batch` independent problems, HOST pointers per problem, borrowed for the call: src[b] n_src[b] x 3, dst[b]
+ * n_dst[b] x 3, corr[b] n_corr[b] x 2 int32 (source index, target index); params and out: one per problem; inliers:
+ * NULL, or per problem NULL or room for n_corr[b] x 2 int32, out[b].n_correspondences pairs written. */
+TEASER_HIP_API int32_t teaser_hip_ransac_correspondence_batch(
+    teaser_hip_ransac* ransac, int32_t batch, const double* const* src, const int32_t* n_src,
+    const double* const* dst, const int32_t* n_dst, const int32_t* const* corr, const int32_t* n_corr,
+    const teaser_ransac_params_c* params, teaser_ransac_result_c* out, int32_t* const* inliers);
+/* One problem: teaser_hip_ransac_correspondence_batch with batch = 1; inliers NULL or room for n_corr x 2. */
+TEASER_HIP_API int32_t teaser_hip_ransac_correspondence(teaser_hip_ransac* ransac, const double* src, int32_t n_src,
+                                                        const double* dst, int32_t n_dst, const int32_t* corr,
+                                                        int32_t n_corr, const teaser_ransac_params_c* params,
+                                                        teaser_ransac_result_c* out, int32_t* inliers);
+/* One knob per handle, "chunk_trials" in [64, 65536] (default 4096): the trials of a problem one launch sequence
+ * covers.  A tuning switch: no value changes a bit of any result.  BAD_ARG for another name or a value out of range. */
+TEASER_HIP_API int32_t teaser_hip_ransac_set_option(teaser_hip_ransac* ransac, const char* name, int64_t value);
+TEASER_HIP_API int32_t teaser_hip_ransac_get_option(const teaser_hip_ransac* ransac, const char* name, int64_t* value);
+/* Stage call (in the spirit of teaser_hip_certify_stages): trials first .. first + n - 1 (first >= 0, 0 <= n <= 65536)
+ * of every problem through the SAME kernels, with no stopping rule and no use of max_iteration or confidence.  Per
+ * problem b and trial q, at [b n + q]: samples (8 int32, the first ransac_n used, the rest -1), flags (one byte: bit 0
+ * the edge-length test passed or is off, bit 1 the distance test passed or is off, bit 2 scored = both; a trial that
+ * fails the edge-length test is not estimated: T = identity, bits 1 and 2 clear), T (16 doubles), count and sum_d2 (0
+ * where not scored).  A problem with ncorr < ransac_n draws nothing: samples -1, flags 0.  Any output may be NULL. */
+TEASER_HIP_API int32_t teaser_hip_ransac_trials_batch(
+    teaser_hip_ransac* ransac, int32_t batch, const double* const* src, const int32_t* n_src,
+    const double* const* dst, const int32_t* n_dst, const int32_t* const* corr, const int32_t* n_corr,
+    const teaser_ransac_params_c* params, int64_t first, int32_t n, int32_t* samples, uint8_t* flags,
+    double* transformations, int32_t* count, double* sum_d2);
+
 /* Page-locked host memory from the HIP runtime THIS library runs on.  teaser_hip_submit_batch(..., INPUT_HOST) moves
  * the points with one DMA copy per cloud, at PCIe speed only when the runtime knows the pages are locked.  A buffer
  * pinned by another HIP runtime instance in the same process (e.g. the one a Python framework bundles) is pageable

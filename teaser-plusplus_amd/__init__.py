@@ -151,6 +151,9 @@ EXPORTED_SYMBOLS = [
     "teaser_hip_posegraph_create", "teaser_hip_posegraph_destroy", "teaser_hip_posegraph_last_error",
     "teaser_hip_posegraph_option_default", "teaser_hip_posegraph_optimize_batch", "teaser_hip_posegraph_optimize",
     "teaser_hip_posegraph_linearize_batch", "teaser_hip_posegraph_linearize",
+    "teaser_hip_ransac_create", "teaser_hip_ransac_destroy", "teaser_hip_ransac_last_error",
+    "teaser_hip_ransac_params_default", "teaser_hip_ransac_correspondence_batch", "teaser_hip_ransac_correspondence",
+    "teaser_hip_ransac_set_option", "teaser_hip_ransac_get_option", "teaser_hip_ransac_trials_batch",
 ]
 
 
@@ -246,6 +249,8 @@ def lib():
     _features.declare(L)
     from . import posegraph as _posegraph
     _posegraph.declare(L)
+    from . import ransac as _ransac
+    _ransac.declare(L)
     _lib = L
     return L
 
@@ -1108,6 +1113,11 @@ from .posegraph import (PoseGraph, PoseGraphNode, PoseGraphEdge, GlobalOptimizat
                         GlobalOptimizationConvergenceCriteria, GlobalOptimizationLevenbergMarquardt,
                         GlobalOptimizationGaussNewton, PoseGraphOptimizationResult, global_optimization,
                         global_optimization_batch, linearize_pose_graph)
+from .ransac import (RANSACConvergenceCriteria, CorrespondenceCheckerBasedOnEdgeLength,  # noqa: E402
+                     CorrespondenceCheckerBasedOnDistance, CorrespondenceCheckerBasedOnNormal,
+                     registration_ransac_based_on_correspondence, registration_ransac_based_on_correspondence_batch,
+                     registration_ransac_based_on_feature_matching, feature_matching_correspondences,
+                     ransac_trials_batch, set_ransac_option, get_ransac_option)
 
 __all__ = ["batched", "FPFHEstimation", "Matcher", "MultiDeviceSolver", "RobustRegistrationSolver", "RegistrationSolution", "RotationEstimationAlgorithm",
            "InlierSelectionMode", "InlierGraphFormulation", "TeaserHipError", "synth_problem",
@@ -1131,4 +1141,8 @@ __all__ = ["batched", "FPFHEstimation", "Matcher", "MultiDeviceSolver", "RobustR
            "PoseGraph", "PoseGraphNode", "PoseGraphEdge", "GlobalOptimizationOption",
            "GlobalOptimizationConvergenceCriteria", "GlobalOptimizationLevenbergMarquardt",
            "GlobalOptimizationGaussNewton", "PoseGraphOptimizationResult", "global_optimization",
-           "global_optimization_batch", "linearize_pose_graph"]
+           "global_optimization_batch", "linearize_pose_graph",
+           "RANSACConvergenceCriteria", "CorrespondenceCheckerBasedOnEdgeLength", "CorrespondenceCheckerBasedOnDistance",
+           "CorrespondenceCheckerBasedOnNormal", "registration_ransac_based_on_correspondence",
+           "registration_ransac_based_on_correspondence_batch", "registration_ransac_based_on_feature_matching",
+           "feature_matching_correspondences", "ransac_trials_batch", "set_ransac_option", "get_ransac_option"]

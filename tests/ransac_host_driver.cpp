@@ -1,0 +1,484 @@
+// Host-only check of csrc/ransac.hip (tests/test_ransac_host.py): compiled by g++ against the HIP stand-in header
+// (tests/hip_stub) with -fsanitize=address,undefined as a stand-alone program.  The launchers are stand-ins that run the
+// one-lane functions of csrc/ransac_device.h on the CPU, one lane at a time, into the very buffers the host side sized
+// and packed (a wrong size or offset is an AddressSanitizer report or a wrong value): the pack, the hypotheses with the
+// survivors compacted in REVERSE order (the order must not matter), the score in its stated order, and the prefix as a
+// plain sequential walk.  Checked: the packing; the chunk plan at chunk_trials 64, 4096 and 65536; the full call
+// against the contract's loop written out here; speculative chunks enqueued and dropped; a list of strict improvements
+// longer than one launch hands over (fabricated records); the stage call; every refusal with its argument and problem.
+//   ransac_host_driver    exit code 0 and "mismatches 0": every expectation met
+// TEST INFRASTRUCTURE ONLY.
+#include <hip/hip_runtime.h>
+
+#include <cstdio>
+#include <limits>
+
+#include "../teaser-plusplus_amd/csrc/ransac.hip"
+
+static int g_bad = 0;
+#define EXPECT(c)                                                \
+  do {                                                           \
+    if (!(c)) {                                                  \
+      ++g_bad;                                                   \
+      printf("line %d: expectation failed: %s\n", __LINE__, #c); \
+    }                                                            \
+  } while (0)
+
+static int g_packs = 0, g_chunks = 0, g_prefixes = 0, g_refetches = 0;
+static int64_t g_trials_launched = 0;
+static bool g_fabricate = false;  // records with count = trial + 1: every trial a strict improvement
+static std::vector<int> g_chunk_sizes;
+
+namespace thip {
+
+void launch_ransac_pack(hipStream_t, int batch, int max_corr, const RsDesc* desc, const double* src, const double* dst,
+                        const int32_t* corr, double* pairs) {
+  ++g_packs;
+  for (int b = 0; b < batch; ++b) {
+    const RsDesc& D = desc[b];
+    EXPECT(D.ncorr <= max_corr);
+    for (int c = 0; c < D.ncorr; ++c) {
+      const int64_t i = corr[2 * (D.corr_off + c)], j = corr[2 * (D.corr_off + c) + 1];
+      for (int k = 0; k < 3; ++k) {
+        pairs[6 * (D.pair_off + c) + k] = src[3 * (D.src_off + i) + k];
+        pairs[6 * (D.pair_off + c) + 3 + k] = dst[3 * (D.dst_off + j) + k];
+      }
+    }
+  }
+}
+
+static void score_lane(const RsDesc& D, const double* P, const double* T, int32_t* count, double* sum) {
+  *count = 0;
+  *sum = 0.0;
+  for (int c0 = 0; c0 < D.ncorr; c0 += RS_BLOCK) {
+    double bs = 0.0;
+    for (int c = c0; c < std::min(D.ncorr, c0 + RS_BLOCK); ++c) {
+      const double d2 = rs_pair_d2(T, P + 6 * c);
+      if (d2 < D.r2) {
+        ++*count;
+        bs += d2;
+      }
+    }
+    *sum += bs;
+  }
+}
+
+void launch_ransac_chunk(hipStream_t, int batch, int chunk, int max_n, const RsDesc* desc, const double* pairs,
+                         const RsSlot& slot, int64_t first) {
+  ++g_chunks;
+  g_chunk_sizes.push_back(chunk);
+  int seen_max = 0;
+  for (int b = 0; b < batch; ++b) {
+    const RsDesc& D = desc[b];
+    const int n = slot.n[b];
+    EXPECT(n >= 0 && n <= chunk);
+    EXPECT(slot.nsurv[b] == 0);  // zeroed before every chunk
+    seen_max = std::max(seen_max, n);
+    g_trials_launched += n;
+    const int64_t base = (int64_t)b * chunk;
+    for (int t = n - 1; t >= 0; --t) {  // lanes in reverse: the survivors' order must not matter
+      int32_t smp[RS_MAX_N];
+      double T[12];
+      int flags = 0;
+      if (D.run) {
+        flags = rs_hypothesis(D, pairs + 6 * D.pair_off, first + t, smp, T);
+      } else {
+        for (int k = 0; k < 12; ++k) T[k] = (k % 5 == 0) ? 1.0 : 0.0;
+      }
+      if (g_fabricate) flags = RS_FLAG_EDGE | RS_FLAG_DIST | RS_FLAG_SCORED;
+      for (int k = 0; k < 12; ++k) slot.T[12 * (base + t) + k] = T[k];
+      slot.flags[base + t] = (uint8_t)flags;
+      slot.count[base + t] = 0;
+      slot.sum[base + t] = 0.0;
+      if (slot.samples)
+        for (int k = 0; k < RS_MAX_N; ++k) slot.samples[RS_MAX_N * (base + t) + k] = (D.run && k < D.ransac_n) ? smp[k] : -1;
+      if (flags & RS_FLAG_SCORED) slot.surv[base + slot.nsurv[b]++] = t;
+    }
+    for (int q = 0; q < slot.nsurv[b]; ++q) {
+      const int64_t at = base + slot.surv[base + q];
+      if (g_fabricate) {
+        slot.count[at] = (int32_t)(first + slot.surv[base + q]) + 1;
+        slot.sum[at] = 1.0;
+      } else {
+        score_lane(D, pairs + 6 * D.pair_off, slot.T + 12 * at, slot.count + at, slot.sum + at);
+      }
+    }
+  }
+  EXPECT(seen_max == max_n);
+}
+
+void launch_ransac_prefix(hipStream_t, int batch, int chunk, const RsSlot& slot, int64_t first, int32_t skip) {
+  ++g_prefixes;
+  if (skip > 0) ++g_refetches;
+  for (int b = 0; b < batch; ++b) {
+    RsBest run = slot.best_in[b];
+    int found = 0;
+    const int64_t base = (int64_t)b * chunk;
+    for (int t = 0; t < slot.n[b]; ++t) {
+      if (!(slot.flags[base + t] & RS_FLAG_SCORED)) continue;
+      const int32_t c = slot.count[base + t];
+      const double rm = rs_rmse(c, slot.sum[base + t]);
+      if (!rs_better(c, rm, run)) continue;
+      run.count = c;
+      run.rmse = rm;
+      const int pos = found++ - skip;
+      if (pos < 0 || pos >= RS_LIST_CAP) continue;
+      RsEntry& e = slot.entries[(int64_t)b * RS_LIST_CAP + pos];
+      e.trial = first + t;
+      e.sum = slot.sum[base + t];
+      e.count = c;
+      e.pad = 0;
+      for (int k = 0; k < 12; ++k) e.T[k] = slot.T[12 * (base + t) + k];
+    }
+    slot.n_imp[b] = found;
+    slot.best_out[b] = run;
+  }
+}
+
+}  // namespace thip
+
+// ---- problems ----
+struct Problem {
+  std::vector<double> P, Q;
+  std::vector<int32_t> corr;
+  teaser_ransac_params_c prm;
+};
+
+static uint64_t g_rng = 12345;
+static double uni() {
+  g_rng = g_rng * 6364136223846793005ull + 1442695040888963407ull;
+  return (double)(g_rng >> 11) / 9007199254740992.0 * 2.0 - 1.0;
+}
+
+static Problem make_problem(int ncorr, double inlier_ratio, int max_iteration, double confidence, double s, double d,
+                            int ransac_n, uint64_t seed) {
+  Problem p;
+  const int ns = ncorr + 3, nt = ncorr + 7;
+  for (int k = 0; k < 3 * ns; ++k) p.P.push_back(uni());
+  for (int k = 0; k < 3 * nt; ++k) p.Q.push_back(uni());
+  const double c = cos(0.7), sn = sin(0.7);
+  for (int k = 0; k < ncorr; ++k) {
+    const int i = (7 * k + 1) % ns, j = (13 * k + 2) % nt;
+    p.corr.push_back(i);
+    p.corr.push_back(j);
+    if (k < inlier_ratio * ncorr) {
+      const double* a = &p.P[3 * i];
+      p.Q[3 * j] = c * a[0] - sn * a[1] + 0.3 + 1e-3 * uni();
+      p.Q[3 * j + 1] = sn * a[0] + c * a[1] - 0.2 + 1e-3 * uni();
+      p.Q[3 * j + 2] = a[2] + 0.1 + 1e-3 * uni();
+    }
+  }
+  teaser_hip_ransac_params_default(&p.prm);
+  p.prm.max_correspondence_distance = 0.02;
+  p.prm.max_iteration = max_iteration;
+  p.prm.confidence = confidence;
+  p.prm.edge_length_threshold = s;
+  p.prm.distance_threshold = d;
+  p.prm.ransac_n = ransac_n;
+  p.prm.seed = seed;
+  return p;
+}
+
+// The contract's loop, written out: what the full call must return.
+static teaser_ransac_result_c expected(const Problem& p, std::vector<int32_t>* inliers) {
+  teaser_ransac_result_c r;
+  memset(&r, 0, sizeof(r));
+  r.transformation[0] = r.transformation[5] = r.transformation[10] = r.transformation[15] = 1.0;
+  r.best_trial = -1;
+  const int ncorr = (int)p.corr.size() / 2;
+  if (ncorr < p.prm.ransac_n || p.prm.max_iteration == 0) return r;
+  std::vector<double> pairs;
+  for (int k = 0; k < ncorr; ++k) {
+    for (int a = 0; a < 3; ++a) pairs.push_back(p.P[3 * p.corr[2 * k] + a]);
+    for (int a = 0; a < 3; ++a) pairs.push_back(p.Q[3 * p.corr[2 * k + 1] + a]);
+  }
+  RsDesc D;
+  memset(&D, 0, sizeof(D));
+  D.seed = p.prm.seed;
+  D.r2 = p.prm.max_correspondence_distance * p.prm.max_correspondence_distance;
+  D.s = p.prm.edge_length_threshold;
+  D.d = p.prm.distance_threshold;
+  D.ncorr = ncorr;
+  D.ransac_n = p.prm.ransac_n;
+  D.run = 1;
+  double est_k = p.prm.max_iteration, best_rmse = 0.0, bestT[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
+  int best_count = 0;
+  for (int64_t i = 0; i < p.prm.max_iteration && (double)i < est_k; ++i) {
+    ++r.trials;
+    int32_t smp[RS_MAX_N], count;
+    double T[12], sum;
+    if (!(rs_hypothesis(D, pairs.data(), i, smp, T) & RS_FLAG_SCORED)) continue;
+    ++r.valid_trials;
+    score_lane(D, pairs.data(), T, &count, &sum);
+    const double rmse = count > 0 ? sqrt(sum / count) : 0.0;
+    if (count > best_count || (count == best_count && rmse < best_rmse)) {
+      best_count = count;
+      best_rmse = rmse;
+      memcpy(bestT, T, sizeof(T));
+      r.best_trial = i;
+      const double k = log(1.0 - p.prm.confidence) / log(1.0 - pow((double)count / ncorr, (double)p.prm.ransac_n));
+      if (k < est_k) est_k = ceil(k);
+    }
+  }
+  if (r.best_trial >= 0) {
+    memcpy(r.transformation, bestT, sizeof(bestT));
+    r.n_correspondences = best_count;
+    r.fitness = (double)best_count / ncorr;
+    r.inlier_rmse = best_rmse;
+    for (int k = 0; inliers && k < ncorr; ++k)
+      if (rs_pair_d2(bestT, pairs.data() + 6 * k) < D.r2) {
+        inliers->push_back(p.corr[2 * k]);
+        inliers->push_back(p.corr[2 * k + 1]);
+      }
+  }
+  return r;
+}
+
+struct Batch {
+  std::vector<Problem> ps;  // its own copy: the pointers below point into it
+  std::vector<const double*> src, dst;
+  std::vector<const int32_t*> corr;
+  std::vector<int32_t> ns, nt, nc;
+  std::vector<teaser_ransac_params_c> prm;
+  explicit Batch(const std::vector<Problem>& problems) : ps(problems) {
+    for (const Problem& p : ps) {
+      src.push_back(p.P.empty() ? nullptr : p.P.data());
+      dst.push_back(p.Q.empty() ? nullptr : p.Q.data());
+      corr.push_back(p.corr.empty() ? nullptr : p.corr.data());
+      ns.push_back((int32_t)p.P.size() / 3);
+      nt.push_back((int32_t)p.Q.size() / 3);
+      nc.push_back((int32_t)p.corr.size() / 2);
+      prm.push_back(p.prm);
+    }
+  }
+  int32_t run(teaser_hip_ransac* h, teaser_ransac_result_c* out, int32_t* const* inl) {
+    return teaser_hip_ransac_correspondence_batch(h, (int32_t)src.size(), src.data(), ns.data(), dst.data(), nt.data(),
+                                                  corr.data(), nc.data(), prm.data(), out, inl);
+  }
+};
+
+static bool same(const teaser_ransac_result_c& a, const teaser_ransac_result_c& b) { return memcmp(&a, &b, sizeof(a)) == 0; }
+
+static void refusal(teaser_hip_ransac* h, std::vector<Problem> ps, const char* needle, bool null_src = false) {
+  Batch bt(ps);
+  if (null_src) bt.src[1] = nullptr;
+  std::vector<teaser_ransac_result_c> out(ps.size());
+  memset(out.data(), 0x5a, sizeof(teaser_ransac_result_c) * out.size());
+  const std::vector<teaser_ransac_result_c> before = out;
+  const int packs = g_packs, chunks = g_chunks;
+  const int32_t rc = bt.run(h, out.data(), nullptr);
+  const std::string msg = teaser_hip_ransac_last_error(h);
+  if (rc != TEASER_HIP_ERR_BAD_ARG || msg.find(needle) == std::string::npos || msg.find("(problem 1)") == std::string::npos) {
+    ++g_bad;
+    printf("refusal '%s': status %d, message '%s'\n", needle, rc, msg.c_str());
+  }
+  EXPECT(g_packs == packs && g_chunks == chunks);  // found before any launch
+  EXPECT(memcmp(out.data(), before.data(), sizeof(teaser_ransac_result_c) * out.size()) == 0);
+}
+
+int main() {
+  teaser_hip_ransac* h = nullptr;
+  EXPECT(teaser_hip_ransac_create(-1, &h) == TEASER_HIP_OK && h);
+  int64_t v = 0;
+  EXPECT(teaser_hip_ransac_get_option(h, "chunk_trials", &v) == TEASER_HIP_OK && v == 4096);
+  EXPECT(teaser_hip_ransac_set_option(h, "chunk_trials", 63) == TEASER_HIP_ERR_BAD_ARG);
+  EXPECT(teaser_hip_ransac_set_option(h, "chunk_trials", 65537) == TEASER_HIP_ERR_BAD_ARG);
+  EXPECT(teaser_hip_ransac_set_option(h, "no_such", 64) == TEASER_HIP_ERR_BAD_ARG);
+  EXPECT(teaser_hip_ransac_get_option(h, "no_such", &v) == TEASER_HIP_ERR_BAD_ARG && v == 4096);
+  teaser_ransac_params_c dflt;
+  EXPECT(teaser_hip_ransac_params_default(&dflt) == TEASER_HIP_OK && dflt.ransac_n == 3 && dflt.max_iteration == 100000 &&
+         dflt.confidence == 0.999 && dflt.edge_length_threshold == 0 && dflt.distance_threshold == 0 && dflt.seed == 0);
+  EXPECT(rs_group_chunks(64, 6) == 4 && rs_group_chunks(65536, 64) == 1 && rs_group_chunks(65536, 8) == 4);
+
+  std::vector<Problem> ps;
+  ps.push_back(make_problem(300, 0.6, 5000, 0.999, 0.0, 0.0, 3, 11));   // stops inside the first chunk of 64
+  ps.push_back(make_problem(257, 0.25, 5000, 0.999, 0.9, 0.05, 3, 12)); // stops in a later group, both checkers on
+  ps.push_back(make_problem(48, 0.5, 1000, 1.0, 0.0, 0.0, 4, 13));      // never stops early: a partial last chunk
+  ps.push_back(make_problem(2, 1.0, 100, 0.999, 0.0, 0.0, 3, 14));      // ncorr < ransac_n
+  ps.push_back(make_problem(40, 0.5, 0, 0.999, 0.0, 0.0, 3, 15));       // max_iteration = 0
+  ps.push_back(Problem());                                              // empty
+  teaser_hip_ransac_params_default(&ps.back().prm);
+  ps.back().prm.max_correspondence_distance = 0.02;
+  ps.back().prm.seed = 16;
+  const size_t B = ps.size();
+  std::vector<teaser_ransac_result_c> want(B);
+  std::vector<std::vector<int32_t>> want_inl(B);
+  for (size_t b = 0; b < B; ++b) want[b] = expected(ps[b], &want_inl[b]);
+  for (size_t b = 0; b < B; ++b)
+    printf("problem %zu: trials %lld valid %lld best %lld count %d\n", b, (long long)want[b].trials,
+           (long long)want[b].valid_trials, (long long)want[b].best_trial, want[b].n_correspondences);
+  EXPECT(want[0].trials > 3 && want[0].trials < 64 && want[0].best_trial >= 0);
+  EXPECT(want[1].trials > 256 && want[1].trials < 5000 && want[1].trials % 64 != 0 && want[1].valid_trials < want[1].trials);
+  EXPECT(want[2].trials == 1000 && want[3].best_trial == -1 && want[3].trials == 0 && want[4].trials == 0);
+
+  const int64_t chunks_of[3] = {64, 4096, 65536};
+  for (int64_t chunk : chunks_of) {
+    EXPECT(teaser_hip_ransac_set_option(h, "chunk_trials", chunk) == TEASER_HIP_OK);
+    // the whole batch
+    Batch bt(ps);
+    std::vector<teaser_ransac_result_c> out(B);
+    std::vector<std::vector<int32_t>> inl(B);
+    std::vector<int32_t*> ip;
+    for (size_t b = 0; b < B; ++b) {
+      inl[b].assign(2 * std::max<size_t>(ps[b].corr.size() / 2, 1), -7);
+      ip.push_back(inl[b].data());
+    }
+    g_chunk_sizes.clear();
+    g_trials_launched = 0;
+    const int packs = g_packs;
+    EXPECT(bt.run(h, out.data(), ip.data()) == TEASER_HIP_OK);
+    EXPECT(g_packs == packs + 1);
+    for (int c : g_chunk_sizes) EXPECT(c == chunk);
+    int64_t visited = 0;
+    for (size_t b = 0; b < B; ++b) {
+      visited += want[b].trials;
+      if (!same(out[b], want[b])) {
+        ++g_bad;
+        printf("chunk %lld problem %zu: trials %lld (want %lld) best %lld (want %lld) valid %lld (want %lld) count %d (want %d)\n",
+               (long long)chunk, b, (long long)out[b].trials, (long long)want[b].trials, (long long)out[b].best_trial,
+               (long long)want[b].best_trial, (long long)out[b].valid_trials, (long long)want[b].valid_trials,
+               out[b].n_correspondences, want[b].n_correspondences);
+      }
+      const size_t k = want_inl[b].size();
+      EXPECT((int)k == 2 * out[b].n_correspondences && std::equal(want_inl[b].begin(), want_inl[b].end(), inl[b].begin()));
+      EXPECT(inl[b].size() <= k || inl[b][k] == -7);  // nothing written past the inliers
+    }
+    EXPECT(g_trials_launched >= visited);
+    if (chunk == 64) EXPECT(g_trials_launched > visited);  // speculative chunks were enqueued -- and dropped
+    // every problem alone: the same record
+    for (size_t b = 0; b < B; ++b) {
+      Batch one(std::vector<Problem>(1, ps[b]));
+      teaser_ransac_result_c r;
+      EXPECT(one.run(h, &r, nullptr) == TEASER_HIP_OK && same(r, want[b]));
+    }
+  }
+  // the one-problem entry
+  {
+    teaser_ransac_result_c r;
+    std::vector<int32_t> inl(ps[0].corr.size(), -7);
+    EXPECT(teaser_hip_ransac_correspondence(h, ps[0].P.data(), (int32_t)ps[0].P.size() / 3, ps[0].Q.data(),
+                                            (int32_t)ps[0].Q.size() / 3, ps[0].corr.data(), (int32_t)ps[0].corr.size() / 2,
+                                            &ps[0].prm, &r, inl.data()) == TEASER_HIP_OK);
+    EXPECT(same(r, want[0]) && std::equal(want_inl[0].begin(), want_inl[0].end(), inl.begin()));
+  }
+  // a list of strict improvements longer than one launch hands over: fabricated records, count = trial + 1
+  {
+    Problem f = make_problem(5000, 0.0, 300, 1.0, 0.0, 0.0, 3, 17);
+    EXPECT(teaser_hip_ransac_set_option(h, "chunk_trials", 256) == TEASER_HIP_OK);
+    g_fabricate = true;
+    g_refetches = 0;
+    Batch one(std::vector<Problem>(1, f));
+    teaser_ransac_result_c r;
+    EXPECT(one.run(h, &r, nullptr) == TEASER_HIP_OK);
+    g_fabricate = false;
+    EXPECT(g_refetches == 3);  // 256 improvements in the first chunk: 64 + three more windows
+    EXPECT(r.best_trial == 299 && r.trials == 300 && r.valid_trials == 300 && r.n_correspondences == 300);
+    EXPECT(r.fitness == 300.0 / 5000.0 && r.inlier_rmse == sqrt(1.0 / 300.0));
+    // ... and the stop rule on them: confidence 0.5 stops as soon as ceil(k) <= trial + 1
+    f.prm.confidence = 0.5;
+    f.prm.max_iteration = 3000;
+    g_fabricate = true;
+    Batch two(std::vector<Problem>(1, f));
+    EXPECT(two.run(h, &r, nullptr) == TEASER_HIP_OK);
+    g_fabricate = false;
+    int64_t stop = -1;
+    double est_k = 3000;
+    for (int64_t i = 0; i < 3000 && (double)i < est_k; ++i) {
+      const double k = log(1.0 - 0.5) / log(1.0 - pow((double)(i + 1) / 5000.0, 3.0));
+      if (k < est_k) est_k = ceil(k);
+      stop = i + 1;
+    }
+    EXPECT(stop > 256 && stop < 3000 && r.trials == stop && r.best_trial == stop - 1 && r.valid_trials == stop);
+  }
+  // the stage call: the records of the trials first .. first + n - 1, T with its last row, nothing for ncorr < ransac_n
+  {
+    std::vector<Problem> st = {ps[1], ps[3]};
+    Batch bt(st);
+    const int n = 70;
+    const int64_t first = (1ll << 33) + 5;
+    std::vector<int32_t> smp(2 * n * 8, 99), cnt(2 * n, 99);
+    std::vector<uint8_t> fl(2 * n, 99);
+    std::vector<double> T(2 * n * 16, 99.0), sm(2 * n, 99.0);
+    EXPECT(teaser_hip_ransac_trials_batch(h, 2, bt.src.data(), bt.ns.data(), bt.dst.data(), bt.nt.data(), bt.corr.data(),
+                                          bt.nc.data(), bt.prm.data(), first, n, smp.data(), fl.data(), T.data(),
+                                          cnt.data(), sm.data()) == TEASER_HIP_OK);
+    const int ncorr = (int)ps[1].corr.size() / 2;
+    int scored = 0;
+    for (int q = 0; q < n; ++q) {
+      for (int k = 0; k < 8; ++k) {
+        const int32_t w = k < 3 ? (int32_t)(rs_draw(12, 3ull * (uint64_t)(first + q) + k + 1) % (uint64_t)ncorr) : -1;
+        EXPECT(smp[8 * q + k] == w);
+        EXPECT(smp[8 * (n + q) + k] == -1);
+      }
+      EXPECT(T[16 * q + 12] == 0 && T[16 * q + 13] == 0 && T[16 * q + 14] == 0 && T[16 * q + 15] == 1);
+      EXPECT(fl[n + q] == 0 && cnt[n + q] == 0 && sm[n + q] == 0 && T[16 * (n + q)] == 1 && T[16 * (n + q) + 15] == 1);
+      scored += (fl[q] & RS_FLAG_SCORED) ? 1 : 0;
+      if (!(fl[q] & RS_FLAG_SCORED)) EXPECT(cnt[q] == 0 && sm[q] == 0);
+      if (!(fl[q] & RS_FLAG_EDGE)) EXPECT(fl[q] == 0 && T[16 * q] == 1 && T[16 * q + 3] == 0);
+    }
+    EXPECT(scored > 0 && scored < n);
+    EXPECT(teaser_hip_ransac_trials_batch(h, 2, bt.src.data(), bt.ns.data(), bt.dst.data(), bt.nt.data(), bt.corr.data(),
+                                          bt.nc.data(), bt.prm.data(), -1, n, nullptr, nullptr, nullptr, nullptr,
+                                          nullptr) == TEASER_HIP_ERR_BAD_ARG);
+    EXPECT(teaser_hip_ransac_trials_batch(h, 2, bt.src.data(), bt.ns.data(), bt.dst.data(), bt.nt.data(), bt.corr.data(),
+                                          bt.nc.data(), bt.prm.data(), 0, 65537, nullptr, nullptr, nullptr, nullptr,
+                                          nullptr) == TEASER_HIP_ERR_BAD_ARG);
+  }
+  // every refusal names its argument and the problem, is found before any launch and leaves the outputs alone
+  {
+    const std::vector<Problem> ok = {ps[0], ps[2]};
+    const double nan = std::numeric_limits<double>::quiet_NaN(), inf = std::numeric_limits<double>::infinity();
+    auto with = [&](auto edit) {
+      std::vector<Problem> q = ok;
+      edit(q[1]);
+      return q;
+    };
+    refusal(h, with([&](Problem& p) { p.prm.max_correspondence_distance = 0; }), "max_correspondence_distance");
+    refusal(h, with([&](Problem& p) { p.prm.max_correspondence_distance = inf; }), "max_correspondence_distance");
+    refusal(h, with([&](Problem& p) { p.prm.max_correspondence_distance = nan; }), "max_correspondence_distance");
+    refusal(h, with([&](Problem& p) { p.prm.ransac_n = 2; }), "ransac_n");
+    refusal(h, with([&](Problem& p) { p.prm.ransac_n = 9; }), "ransac_n");
+    refusal(h, with([&](Problem& p) { p.prm.confidence = -0.1; }), "confidence");
+    refusal(h, with([&](Problem& p) { p.prm.confidence = 1.5; }), "confidence");
+    refusal(h, with([&](Problem& p) { p.prm.confidence = nan; }), "confidence");
+    refusal(h, with([&](Problem& p) { p.prm.max_iteration = -1; }), "max_iteration");
+    refusal(h, with([&](Problem& p) { p.prm.edge_length_threshold = 1.5; }), "edge_length_threshold");
+    refusal(h, with([&](Problem& p) { p.prm.edge_length_threshold = -0.5; }), "edge_length_threshold");
+    refusal(h, with([&](Problem& p) { p.prm.edge_length_threshold = nan; }), "edge_length_threshold");
+    refusal(h, with([&](Problem& p) { p.prm.distance_threshold = -1; }), "distance_threshold");
+    refusal(h, with([&](Problem& p) { p.prm.distance_threshold = inf; }), "distance_threshold");
+    refusal(h, with([&](Problem& p) { p.prm.with_scaling = 1; }), "with_scaling");
+    refusal(h, with([&](Problem& p) { p.prm.estimation = 1; }), "point-to-plane");
+    refusal(h, with([&](Problem& p) { p.prm.normal_checker = 1; }), "normal-angle checker");
+    refusal(h, with([&](Problem& p) { p.corr[4] = -1; }), "corr: source index of pair 2");
+    refusal(h, with([&](Problem& p) { p.corr[4] = (int32_t)p.P.size() / 3; }), "corr: source index of pair 2");
+    refusal(h, with([&](Problem& p) { p.corr[7] = (int32_t)p.Q.size() / 3; }), "corr: target index of pair 3");
+    refusal(h, with([&](Problem& p) { p.P[5] = nan; }), "src has non-finite points");
+    refusal(h, with([&](Problem& p) { p.Q[5] = inf; }), "dst has non-finite points");
+    refusal(h, ok, "src is NULL", true);
+    teaser_ransac_result_c r;
+    Batch bt(ok);
+    EXPECT(teaser_hip_ransac_correspondence_batch(h, -1, bt.src.data(), bt.ns.data(), bt.dst.data(), bt.nt.data(),
+                                                  bt.corr.data(), bt.nc.data(), bt.prm.data(), &r, nullptr) == TEASER_HIP_ERR_BAD_ARG);
+    EXPECT(teaser_hip_ransac_correspondence_batch(h, 2, bt.src.data(), bt.ns.data(), bt.dst.data(), bt.nt.data(),
+                                                  bt.corr.data(), bt.nc.data(), bt.prm.data(), nullptr, nullptr) == TEASER_HIP_ERR_BAD_ARG);
+    EXPECT(teaser_hip_ransac_correspondence_batch(h, 2, bt.src.data(), bt.ns.data(), bt.dst.data(), bt.nt.data(),
+                                                  bt.corr.data(), bt.nc.data(), nullptr, &r, nullptr) == TEASER_HIP_ERR_BAD_ARG);
+    EXPECT(teaser_hip_ransac_correspondence_batch(h, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
+                                                  nullptr, nullptr) == TEASER_HIP_OK);
+    EXPECT(teaser_hip_ransac_correspondence_batch(nullptr, 1, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
+                                                  nullptr, nullptr, nullptr) == TEASER_HIP_ERR_BAD_ARG);
+    // seed 0: from the clock, one value for the call -- two such problems with the same input draw the same trials
+    std::vector<Problem> clk = {ps[0], ps[0]};
+    clk[0].prm.seed = clk[1].prm.seed = 0;
+    Batch cb(clk);
+    teaser_ransac_result_c two[2];
+    EXPECT(cb.run(h, two, nullptr) == TEASER_HIP_OK && same(two[0], two[1]));
+    // the handle is sound after the refusals
+    Batch one(std::vector<Problem>(1, ps[0]));
+    EXPECT(one.run(h, &r, nullptr) == TEASER_HIP_OK && same(r, want[0]));
+  }
+  EXPECT(teaser_hip_ransac_destroy(h) == TEASER_HIP_OK);
+  printf("packs %d chunks %d prefixes %d\nmismatches %d\n", g_packs, g_chunks, g_prefixes, g_bad);
+  return g_bad ? 1 : 0;
+}
