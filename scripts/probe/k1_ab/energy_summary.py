@@ -27,7 +27,7 @@ for lib in sys.argv[2:]:
             mine = [r["pci"].lower() for r in runs if r.get("probe") == "device"]
             if mine and mine[0] in pci:
                 rows = nodes[pci[mine[0]]]
-            runs = [r for r in runs if r.get("probe") != "device"]
+            runs = [r for r in runs if r.get("probe") not in ("device", "work")]  # (the worklist line of mode "one" has no times)
         except OSError:
             continue
         if not runs or not rows:

@@ -8,7 +8,7 @@ timeout 300 $D/k1_lab_probe 64 10000 10 k1 0.95 $VS > $OUT/k1_lab.jsonl 2> $OUT/
 cat $OUT/k1_lab.jsonl | cut -c1-220
 python - <<PY
 import json
-rows=[json.loads(l) for l in open("$OUT/k1_lab.jsonl") if l.startswith("{")]
+rows=[r for r in (json.loads(l) for l in open("$OUT/k1_lab.jsonl") if l.startswith("{")) if "bitmap_hash" in r]
 h={r["bitmap_hash"] for r in rows}
 print("bitmap hashes:", h, "OK" if len(h)==1 else "MISMATCH")
 PY

@@ -9,7 +9,11 @@
 //                   K1 staggering on and off
 //     (K1_PROBE_TAIL_SKIP=<mask> in the environment: the library's tail_skip setting -- stages not enqueued -- switched
 //      on behind the warm-up of modes k1 / one / pipe: timing only, the results are wrong)
-//     mode "one"  : only the variant in the environment, `iters` synchronous steps (for rocprofv3)
+//     mode "one"  : only the variant in the environment, `iters` synchronous steps (for rocprofv3), then the worklist line of
+//                   mode "work"
+//     mode "work" : the fix-up's worklist as K1 left it after one synchronous step (the library's diagnostic hook
+//                   teaser_hip_probe_k1_worklist): total group items, items per region (histogram), items per row
+//                   tile (min / median / max), share of empty regions, items in the counted overflow segments
 //     mode "storm": K1 (synchronous steps, HIP events around K1) while a second host thread keeps a SIDE stream busy with
 //                   (a) nothing, (b) empty one-wave kernels back to back (kernel boundaries only), (c) the same, each
 //                   dirtying one cache line, (d) ONE long sleeping kernel of 64 workgroups per 2 ms (occupancy, no
@@ -22,6 +26,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <deque>
+#include <algorithm>
 #include <atomic>
 #include <string>
 #include <thread>
@@ -38,6 +43,10 @@
     }                                                                                  \
   } while (0)
 
+// the library's diagnostic hook (not declared in teaser_hip.h)
+extern "C" int32_t teaser_hip_probe_k1_worklist(teaser_hip_solver* h, uint64_t* regions, int64_t* stride_words,
+                                                int64_t* used_regions, int32_t* problems, uint32_t* seg_counts);
+
 static double now_ms() {
   return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
 }
@@ -49,6 +58,46 @@ static uint64_t fnv(const uint64_t* p, size_t n) {
     h *= 1099511628211ull;
   }
   return h;
+}
+
+// the fix-up's worklist as the handle's last K1 left it: one JSON line
+static void report_worklist(teaser_hip_solver* h, int n) {
+  int64_t stride = 0, used = 0;
+  int32_t probs = 0;
+  CK(teaser_hip_probe_k1_worklist(h, nullptr, &stride, &used, &probs, nullptr));
+  std::vector<uint64_t> reg((size_t)stride * probs);
+  std::vector<uint32_t> segc((size_t)probs);
+  CK(teaser_hip_probe_k1_worklist(h, reg.data(), &stride, &used, &probs, segc.data()));
+  const int T = (n + 63) / 64;
+  std::vector<long long> hist(64, 0), tile_items((size_t)probs * T, 0);
+  long long in_regions = 0, in_segments = 0, empty = 0, full = 0;
+  for (int p = 0; p < probs; ++p) {
+    in_segments += segc[(size_t)p];
+    for (int64_t r = 0; r < used; ++r) {
+      const uint64_t* g = reg.data() + (size_t)p * stride + (size_t)r * 64;
+      const int cnt = (int)std::min<uint64_t>(g[0], 63);
+      ++hist[(size_t)cnt];
+      in_regions += cnt;
+      empty += cnt == 0;
+      full += cnt == 63;
+      if (cnt > 0) {
+        const int tile = (int)((g[1] >> 16) & 0xffff) >> 6;
+        if (tile < T) tile_items[(size_t)p * T + tile] += cnt;
+      }
+    }
+  }
+  std::vector<long long> sorted = tile_items;
+  std::sort(sorted.begin(), sorted.end());
+  printf("{\"probe\":\"work\",\"batch\":%d,\"n\":%d,\"regions_per_problem\":%lld,\"arena_words_per_problem\":%lld,"
+         "\"items_total\":%lld,\"items_in_regions\":%lld,\"items_in_segments\":%lld,\"items_per_problem\":%.1f,"
+         "\"mean_items_per_region\":%.3f,\"empty_region_share\":%.4f,\"full_region_share\":%.5f,"
+         "\"items_per_row_tile\":{\"min\":%lld,\"median\":%lld,\"max\":%lld},\"hist_items_per_region\":[",
+         probs, n, (long long)used, (long long)stride, in_regions + in_segments, in_regions, in_segments,
+         (double)(in_regions + in_segments) / probs, (double)in_regions / ((double)used * probs),
+         (double)empty / ((double)used * probs), (double)full / ((double)used * probs), sorted.front(),
+         sorted[sorted.size() / 2], sorted.back());
+  for (int k = 0; k < 64; ++k) printf("%s%lld", k ? "," : "", hist[(size_t)k]);
+  printf("]}\n");
 }
 
 __global__ void side_empty_kernel() {}
@@ -180,8 +229,17 @@ int main(int argc, char** argv) {
              ("\"" + v + "\"").c_str(), B, n, launches ? k1 / launches : (mode == "one" ? 0.0 : k1 / iters), aux / iters, launches,
              (t1 - t0) / iters, out[0].clique_size, out[0].valid, (unsigned long long)hsh);
       fflush(stdout);
+      if (mode == "one" && v != "fp64") report_worklist(h, n);
       teaser_hip_solver_destroy(h);
     }
+  }
+  if (mode == "work") {
+    teaser_hip_solver* h = nullptr;
+    CK(teaser_hip_solver_create(&prm, 0, &h));
+    for (int w = 0; w < iters; ++w)
+      CK(teaser_hip_solve_batch_device(h, P.d_src[w % 4], P.d_dst[w % 4], P.off.data(), P.n.data(), B, out.data()));
+    report_worklist(h, n);
+    teaser_hip_solver_destroy(h);
   }
   if (mode == "storm") {
     teaser_hip_solver* h = nullptr;

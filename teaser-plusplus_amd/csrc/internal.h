@@ -158,6 +158,9 @@ void launch_tim_graph(hipStream_t s, const ProbDesc* d_desc, int batch, int max_
 int64_t tim_prep_bytes(int batch);
 int64_t tim_operand_bytes(int64_t total_tiles);  // total_tiles = sum of the problems' W
 int64_t tim_work_items(const int32_t* n, int batch);
+int tim_probe_worklist(const void* d_prep, const void* d_work, int64_t work_cap, int batch, int max_n,
+                       unsigned long long* regions_out, int64_t* stride_words, int64_t* used_regions,
+                       unsigned int* seg_counts);  // diagnostic: scripts/probe/k1_probe
 // writes the per-problem worklist segments into the host-staged (otherwise zero) prep block of the header upload
 int64_t tim_prep_fill_segments(void* host_prep, const int32_t* n, int batch);
 // phase 1 also leaves the vertex degrees in d_deg (row popcounts accumulated by the kernel)

@@ -17,6 +17,7 @@
 #include <cstdlib>
 
 #include "internal.h"
+#include "fixup_regions.h"
 #include "k1_consts.h"
 #include "wave_utils.h"
 
@@ -371,10 +372,11 @@ constexpr int kMfmaRowTiles = 4;
 constexpr int kMfmaColTiles = 8;
 
 constexpr int kWorkBuf = 64 * 6;  // per-wave LDS staging (the FP64 path's column buffer): 384 items
-// u / w kernels: every wave owns a region of the worklist: a count word + 63 items (the constant band of the third
-// formulation flags ~23 lane-tiles per wave at the bench geometry; 31 slots sent 4 % of the waves through the atomic)
-constexpr int kRegionWords = 64;
-constexpr int kRegionItems = kRegionWords - 1;
+// u / w kernels: every wave owns a region of the worklist per column chunk: a count word + 63 items (fixup_regions.h;
+// the constant band flags ~5 lane-tiles per region at the bench geometry, none above 18: profiles/r8a)
+using fxr::kRegionItems;
+using fxr::kRegionWords;
+static_assert(fxr::kChunkTiles == kMfmaColTiles && fxr::kRowTiles == kMfmaRowTiles, "fixup_regions.h mirrors the block shape");
 
 // ------------------------------------------------------------------------------------------
 // Operands and band constants of the u / w algebra
@@ -591,7 +593,7 @@ __global__ __launch_bounds__(256, OCC) void tim_graph_mfma3_kernel(
     const double* __restrict__ dst, const TimOperandTile2* __restrict__ ops, const TimPrep* __restrict__ prep,
     uint64_t* __restrict__ bitmap, double beta, int gyr,
     unsigned long long* __restrict__ work, unsigned int* __restrict__ work_count,
-    ProbState* __restrict__ states, int32_t* __restrict__ deg, unsigned long long* __restrict__ regions) {
+    ProbState* __restrict__ states, int32_t* __restrict__ deg, unsigned long long* __restrict__ regions, int Tmax) {
   const ProbDesc d = descs[blockIdx.y];
   const int n = d.n, W = d.W;
   const int T = W;
@@ -600,26 +602,31 @@ __global__ __launch_bounds__(256, OCC) void tim_graph_mfma3_kernel(
   // 8 XCDs round robin in dispatch order, so the blocks of one XCD take CONSECUTIVE logical indices -- the four
   // neighbouring row groups whose transposed words fill one 128-byte line of a bitmap row run on the same XCD at
   // about the same time and merge in that L2, and a column group's operands are fetched into one L2 instead of eight
-  int Ig, X = 0;
-  {
-    const int nb = gridDim.x, c = blockIdx.x & 7, q = nb >> 3, rem = nb & 7;
-    Ig = c * q + min(c, rem) + (blockIdx.x >> 3);
-  }
+  // (fxr::decode_block, fixup_regions.h: the host test of the region arena runs the same decode)
+  int Ig, X;
+  fxr::decode_block((int)blockIdx.x, (int)gridDim.x, gyr, CHUNKS, &Ig, &X);
   // a block = 4 row tiles x CHUNKS chunks of kMfmaColTiles column tiles, walked chunk after chunk by the same four
   // waves: a wave's set-up (descriptors, band constants, row operands: three dependent memory round trips) and its
   // wind-down (the last stores' acknowledgement) took 40 % of its lifetime when it lived for 8 column tiles only
   // (s_memtime trace, profiles/r4f); column group X has min(gyr, 2 CHUNKS (X + 1)) row groups
   constexpr int kBlockColTiles = kMfmaColTiles * CHUNKS;
-  while (Ig >= min(gyr, 2 * CHUNKS * (X + 1))) {
-    Ig -= min(gyr, 2 * CHUNKS * (X + 1));
-    ++X;
-  }
   const int I0 = Ig * kMfmaRowTiles, Jbase = X * kBlockColTiles;
-  // the wave's region of chunk c: regions_of_wave + c * kRegionWords
-  unsigned long long* const regions_of_wave =
-      regions + ((size_t)(blockIdx.y * gridDim.x + blockIdx.x) * kMfmaRowTiles + (threadIdx.x >> 6)) * CHUNKS * kRegionWords;
+  // The wave's region of chunk c is the CELL (row tile I0 + wave, column chunk X CHUNKS + c) of the problem's arena
+  // (fixup_regions.h), addressed by what it covers and not by where the launch grid put the wave: the fix-up finds all
+  // regions of a row tile as one run.  Cells exist in the upper triangle of the batch's largest problem (Tmax tiles)
+  // only; every cell a wave owns gets a count word on every path, also on the early exits (the arena is not cleared).
+  auto region_of = [&](int wv, int chunk) -> unsigned long long* {
+    const int Iw = I0 + wv, Xc = X * CHUNKS + chunk;
+    return fxr::is_cell(Iw, Xc, Tmax) ? regions + fxr::region_offset((int)blockIdx.y, Tmax, Iw, Xc) : nullptr;
+  };
+  auto zero_regions = [&]() {
+    if ((threadIdx.x & 63) < CHUNKS) {
+      unsigned long long* r = region_of((int)(threadIdx.x >> 6), (int)(threadIdx.x & 63));
+      if (r) r[0] = 0ull;
+    }
+  };
   if (I0 >= T || Jbase >= T || Jbase + kBlockColTiles - 1 < I0) {  // outside / below the diagonal
-    if ((threadIdx.x & 63) < CHUNKS) regions_of_wave[(threadIdx.x & 63) * kRegionWords] = 0ull;
+    zero_regions();
     return;
   }
   const int lane = threadIdx.x & 63;
@@ -680,7 +687,7 @@ __global__ __launch_bounds__(256, OCC) void tim_graph_mfma3_kernel(
       for (int jb = Jbase; jb < Jbase + kBlockColTiles; jb += kColTilesPerWave)
         if (!(jb + kColTilesPerWave - 1 < I || jb >= T))
           tim_wave_fp64<0>(ps, pd, bm, n, W, I, jb, kc, reinterpret_cast<double*>(&lds_own[wave][0][0]));
-    if (lane < CHUNKS) regions_of_wave[lane * kRegionWords] = 0ull;
+    zero_regions();
     return;
   }
   const __amdgpu_buffer_rsrc_t deg_rsrc = __builtin_amdgcn_make_buffer_rsrc(
@@ -886,8 +893,9 @@ __global__ __launch_bounds__(256, OCC) void tim_graph_mfma3_kernel(
 #pragma nounroll
   for (int chunk = 0; chunk < CHUNKS; ++chunk) {
     const int Jc0 = Jbase + chunk * kMfmaColTiles, Jc1 = min(Jc0 + kMfmaColTiles, Jend);
+    unsigned long long* const region = region_of(wave, chunk);  // (wave-uniform; null: no such cell)
     if (Jc0 >= Jend) {  // (block-uniform) beyond the problem: no region to resolve
-      if (lane == 0) regions_of_wave[chunk * kRegionWords] = 0ull;
+      if (lane == 0 && region) region[0] = 0ull;
       continue;
     }
     const int Ja = rowvalid ? max(Jc0, Jfirst) : Jc1;  // this wave's first column tile of the chunk
@@ -1013,12 +1021,12 @@ __global__ __launch_bounds__(256, OCC) void tim_graph_mfma3_kernel(
     }
     flags = 0;
     {
-      unsigned long long* region = regions_of_wave + chunk * kRegionWords;
-      const int nreg = wcount < kRegionItems ? wcount : kRegionItems;
-      if (lane == 0) region[0] = (unsigned long long)nreg;
+      // (a wave has items only where its row tile reaches the chunk's columns, i.e. in a cell: region != null then)
+      const int nreg = !region ? 0 : (wcount < kRegionItems ? wcount : kRegionItems);
+      if (lane == 0 && region) region[0] = (unsigned long long)nreg;
       if (lane < nreg) region[1 + lane] = wbuf[lane];
-      if (wcount > kRegionItems) {
-        const int extra = wcount - kRegionItems;
+      if (wcount > nreg) {
+        const int extra = wcount - nreg;
         unsigned int base = 0;
         if (lane == 0) base = atomicAdd(work_count + blockIdx.y, (unsigned int)extra);
         base = __builtin_amdgcn_readfirstlane(base);
@@ -1027,7 +1035,7 @@ __global__ __launch_bounds__(256, OCC) void tim_graph_mfma3_kernel(
         } else {
           unsigned long long* seg = work + (((size_t)pr.seg_off_hi << 32) | (size_t)pr.seg_off_lo);
 #pragma nounroll
-          for (int k2i = lane; k2i < extra; k2i += 64) seg[base + k2i] = wbuf[kRegionItems + k2i];
+          for (int k2i = lane; k2i < extra; k2i += 64) seg[base + k2i] = wbuf[nreg + k2i];
         }
       }
     }
@@ -1040,9 +1048,12 @@ __global__ __launch_bounds__(256, OCC) void tim_graph_mfma3_kernel(
 // (row0 + (q & 3) + 8 (q >> 2), col).  The bitmap holds the filter's provisional bit sign(d~); a pair whose reference
 // predicate disagrees flips its bit(s) with one atomicXor each (row-major copy; transposed copy outside diagonal
 // blocks) and the two degrees follow.  Every bit is owned by exactly one lane of one item, so the plain read of the
-// provisional bit races with nothing.  A WAVE takes a whole region with one load (lane 0: the count word, lane k:
-// item k) and resolves four items per step, every load of a step issued before the first use (two memory round
-// trips per region, not three per item: this kernel sits on its batch's serial chain, beside the next batch's K1).
+// provisional bit races with nothing.  A WAVE takes a whole ROW TILE: it stages the tile's 64 points once, walks the
+// tile's regions (fixup_regions.h: one run of cells, one 64-lane load each -- lane 0: the count word, lane k: item k),
+// queues their items in LDS and resolves the queue in dense rounds of 64 items, four items per step, every load of
+// a round issued before the first use.  (A wave per REGION -- the layout up to round 7 -- paid the staging, the
+// column-side loads, two fences and two half-empty resolve steps for the ~5 items of a region, and staged a row
+// tile's points once per column chunk it meets: profiles/r8a.)
 // 15 of a group's 16 pairs are far from the boundary: the FP64 fast path (FMA, no sqrt, its own 2e-12 guard band:
 // tim_edge_fast) decides them, the reference expression itself only inside that band.
 // Overflow (the problem's counted segment was too small): its bitmap is cleared instead (the stages enqueued behind
@@ -1057,7 +1068,7 @@ __global__ __launch_bounds__(256) void tim_fixup_group_kernel(const ProbDesc* __
                                                               ProbState* __restrict__ states,
                                                               int32_t* __restrict__ deg,
                                                               const unsigned long long* __restrict__ regions,
-                                                              unsigned int regions_per_problem,
+                                                              int Tmax,
                                                               const TimPrep* __restrict__ prep) {
   TAIL_WAVE_PRIO();
   const int prob = blockIdx.y;
@@ -1099,14 +1110,14 @@ __global__ __launch_bounds__(256) void tim_fixup_group_kernel(const ProbDesc* __
   kc.s_hat = 1.0;
   const int lane = threadIdx.x & 63, q = lane & 15, sub = lane >> 4, wave = threadIdx.x >> 6;
   const int rq = (q & 3) + 8 * (q >> 2);
-  // STAGED = true (items of a region): all items of a region come from ONE K1 wave, i.e. one 64-row tile.  Its 64 points
-  // are staged once per region in the wave's LDS slice, and outside the diagonal tile the 16 provisional bits of an item
+  // STAGED = true (items of the regions): all items of a wave's queue come from ONE 64-row tile.  Its 64 points
+  // are staged once per tile in the wave's LDS slice, and outside the diagonal tile the 16 provisional bits of an item
   // are read from the TRANSPOSED copy, where they sit in one word (bitmap row `col`, word of the row tile).  Per item:
   // one broadcast fetch of the column point and one word, instead of 17 points and 16 words on 16 different bitmap
   // rows (1.8 KB of sectors per item: that traffic, not the arithmetic, was the kernel's 0.175 ms per 64 x 10 k launch).
   __shared__ double row_pts[4][64][6];
-  // ... and so are the COLUMN sides of a region's items (round 6): lane k fetches the column point of item k and the
-  // transposed word that holds its 16 provisional bits -- seven load instructions per region, whatever its item count --
+  // ... and so are the COLUMN sides of a round's items (round 6): lane k fetches the column point of item k and the
+  // transposed word that holds its 16 provisional bits -- seven load instructions per round of up to 64 items --
   // and the 16 lanes of an item read them back from the wave's LDS slice.  (Fetched inside the item loop they were
   // seven instructions per FOUR items, each for four distinct addresses: ~5 M vector-memory instructions per
   // 64 x 10 k batch, two thirds of what K1 itself issues, and on a step bound by the board's power limit the fix-up's
@@ -1155,23 +1166,14 @@ __global__ __launch_bounds__(256) void tim_fixup_group_kernel(const ProbDesc* __
       atomicAdd(dg + col, e ? 1 : -1);
     }
   };
-  const unsigned long long* reg = regions + (size_t)prob * regions_per_problem * kRegionWords;
-  const unsigned int wv = blockIdx.x * 4 + (threadIdx.x >> 6), nwv = gridDim.x * 4;
+  // The per-wave item queue: a region adds at most 63 items to fewer than 64 pending ones.
+  __shared__ unsigned long long queue[4][2 * kRegionWords];
   static_assert(kRegionWords == 64, "one region = one 64-lane load");
-  for (unsigned int rg = wv; rg < regions_per_problem; rg += nwv) {
-    const unsigned long long mine = reg[(size_t)rg * kRegionWords + lane];
-    const int cnt = (int)__builtin_amdgcn_readfirstlane((unsigned int)mine);
-    if (cnt <= 0) continue;
-    // the region's row tile (from its first item), staged: lane l holds point 64 tile + l
-    const int tile = (int)((((unsigned int)__builtin_amdgcn_readlane((int)(unsigned int)mine, 1)) >> 16) & 0xffffu) >> 6;
-    {
-      const int pr = min(tile * 64 + lane, n - 1);
-      double* rp = row_pts[wave][lane];
-      rp[0] = ps[3 * pr]; rp[1] = ps[3 * pr + 1]; rp[2] = ps[3 * pr + 2];
-      rp[3] = pd[3 * pr]; rp[4] = pd[3 * pr + 1]; rp[5] = pd[3 * pr + 2];
-    }
-    if (lane >= 1 && lane <= cnt) {  // item `lane`: its column point and (off the diagonal tile) its transposed word
-      const int col = min((int)(mine & 0xffffull), n - 1);
+  const int T = W, nch = fxr::n_chunks(T);
+  // one round: the first `cnt` (<= 64) items of the queue, all of row tile `tile`
+  auto round = [&](int cnt, int tile) {
+    if (lane < cnt) {  // item `lane`: its column point and (off the diagonal tile) its transposed word
+      const int col = min((int)(queue[wave][lane] & 0xffffull), n - 1);
       double* cp = col_pts[wave][lane];
       const double c0 = ps[3 * col], c1 = ps[3 * col + 1], c2 = ps[3 * col + 2];
       const double e0 = pd[3 * col], e1 = pd[3 * col + 1], e2 = pd[3 * col + 2];
@@ -1179,15 +1181,54 @@ __global__ __launch_bounds__(256) void tim_fixup_group_kernel(const ProbDesc* __
       cp[0] = c0; cp[1] = c1; cp[2] = c2; cp[3] = e0; cp[4] = e1; cp[5] = e2;
       cp[6] = __longlong_as_double((long long)tw);
     }
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");  // wave-private LDS slice: same-wave ordering suffices
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");  // wave-private LDS slices: same-wave ordering suffices
 #pragma nounroll
-    for (int base = 1; base <= cnt; base += 4) {
+    for (int base = 0; base < cnt; base += 4) {
       const int k = base + sub;
-      const unsigned int lo = (unsigned int)__shfl((int)(unsigned int)mine, k & 63, 64);
-      const unsigned int hi = (unsigned int)__shfl((int)(unsigned int)(mine >> 32), k & 63, 64);
-      resolve(((unsigned long long)hi << 32) | lo, k <= cnt, std::true_type(), tile, k & 63);
+      resolve(queue[wave][k], k < cnt, std::true_type(), tile, k);
     }
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");  // (the next region overwrites the slice)
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");  // (the next round overwrites the slices)
+  };
+  // Row tiles are taken in pairs (p, T - 1 - p): tile I has n_chunks - first_chunk(I) regions, so every pair walks
+  // about n_chunks + 1 of them and the four waves of a workgroup finish together.  Waves stride over the pairs: the
+  // grid (launch_tim_graph_mfma: a wave per pair of the largest problem, or S_FIXUP_WGS workgroups) may be any size.
+  const int wv = blockIdx.x * 4 + wave, nwv = gridDim.x * 4, npairs = (T + 1) >> 1;
+  for (int pi = wv; pi < npairs; pi += nwv) {
+    for (int side = 0; side < 2; ++side) {
+      const int tile = side ? T - 1 - pi : pi;
+      if (side && tile == pi) break;  // (the middle tile of an odd T)
+      {  // the tile's 64 row points, staged once: lane l holds point 64 tile + l
+        const int pr = min(tile * 64 + lane, n - 1);
+        double* rp = row_pts[wave][lane];
+        rp[0] = ps[3 * pr]; rp[1] = ps[3 * pr + 1]; rp[2] = ps[3 * pr + 2];
+        rp[3] = pd[3 * pr]; rp[4] = pd[3 * pr + 1]; rp[5] = pd[3 * pr + 2];
+      }
+      const int Xc0 = fxr::first_chunk(tile);
+      const unsigned long long* reg = regions + fxr::region_offset(prob, Tmax, tile, Xc0);
+      int qn = 0;  // queued items (wave-uniform), < 64 between regions
+      unsigned long long mine = reg[lane];
+      for (int Xc = Xc0; Xc < nch; ++Xc) {
+        const unsigned long long cur = mine;
+        if (Xc + 1 < nch) mine = reg[(size_t)(Xc + 1 - Xc0) * kRegionWords + lane];  // (in flight beside this region's work)
+        const int cnt = min((int)__builtin_amdgcn_readfirstlane((unsigned int)cur), kRegionItems);
+        if (cnt <= 0) continue;
+        // append: the valid lanes are 1 .. cnt, so the exclusive prefix of the valid flags is lane - 1
+        if (lane >= 1 && lane <= cnt) queue[wave][qn + lane - 1] = cur;
+        qn += cnt;
+        if (qn >= kRegionWords) {
+          __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+          round(kRegionWords, tile);
+          qn -= kRegionWords;
+          const unsigned long long moved = queue[wave][kRegionWords + lane];  // (every lane reads before any writes)
+          __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+          if (lane < qn) queue[wave][lane] = moved;
+        }
+      }
+      if (qn > 0) {
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+        round(qn, tile);
+      }
+    }
   }
   const unsigned long long* seg = work + (((size_t)tpr.seg_off_hi << 32) | (size_t)tpr.seg_off_lo);
   const unsigned int ngrp = gridDim.x * 16;
@@ -1217,27 +1258,16 @@ int64_t tim_operand_bytes(int64_t total_tiles) { return total_tiles * (int64_t)s
 
 // blocks of the matrix-core kernel for a problem of T 64-point tiles: those touching the upper triangle; a block
 // covers 4 row tiles x `chunks` chunks of kMfmaColTiles column tiles
-static int tim_mfma_blocks(int T, int chunks) {
-  const int ct = kMfmaColTiles * chunks;
-  const int gxc = (T + ct - 1) / ct, gyr = (T + kMfmaRowTiles - 1) / kMfmaRowTiles;
-  int nblk = 0;
-  for (int X = 0; X < gxc; ++X) nblk += std::min(gyr, 2 * chunks * (X + 1));
-  return nblk;
-}
-// per-wave regions of one problem for a launch geometry (one region per wave and chunk)
-static int64_t tim_regions_per_problem(int T, int chunks) { return (int64_t)tim_mfma_blocks(T, chunks) * kMfmaRowTiles * chunks; }
-static int64_t tim_region_words(int max_n) {  // (the largest of the launch geometries: the arena's stride)
-  const int T = (max_n + 63) / 64;
-  int64_t r = 0;
-  for (int ch : {1, 2, 4}) r = std::max(r, tim_regions_per_problem(T, ch));
-  return r * kRegionWords;
-}
+static int tim_mfma_blocks(int T, int chunks) { return fxr::blocks(T, chunks); }
+// the region arena's stride per problem: one region per cell (row tile, column chunk) of the largest problem's upper
+// triangle (fixup_regions.h) -- the same for every launch geometry, so also the largest of them
+static int64_t tim_region_words(int max_n) { return fxr::arena_words((max_n + 63) / 64); }
 
 // Worklist layout in 8-byte words: one counted segment per problem (the overflow of the waves' own regions) sized
 // from THAT problem's pair count -- pairs / 256 items, at least 2^16 (typical use: ~1e-3 of the pairs as group items,
 // most of them in the regions) -- at prefix offsets, so that one large problem in a batch of small ones gets the
-// room it needs (a uniform stride from the batch average sent it to the all-FP64 rerun); then the per-wave regions
-// (kRegionWords per wave of every block of the launch grid, i.e. shaped by the largest problem).  A segment that
+// room it needs (a uniform stride from the batch average sent it to the all-FP64 rerun); then the regions
+// (kRegionWords per (row tile, column chunk) cell of the upper triangle, shaped by the largest problem).  A segment that
 // overflows flags its problem and the host reruns the batch on the FP64 kernel.
 static int64_t tim_segment_items(int n) {
   const int64_t seg = std::max<int64_t>((int64_t)n * (n - 1) / 2 / 256, 1 << 16);
@@ -1265,6 +1295,24 @@ int64_t tim_prep_fill_segments(void* host_prep, const int32_t* n, int batch) {
     off += seg;
   }
   return off;
+}
+
+// Diagnostic (scripts/probe/k1_probe, mode "work"): the region arena and the segment counters K1 left behind.  With
+// regions_out == nullptr only the sizes are returned: the arena's stride per problem in 8-byte words and the regions
+// per problem in use (the cells of the largest problem's upper triangle).
+int tim_probe_worklist(const void* d_prep, const void* d_work, int64_t work_cap, int batch, int max_n,
+                       unsigned long long* regions_out, int64_t* stride_words, int64_t* used_regions,
+                       unsigned int* seg_counts) {
+  const int64_t reg_words = tim_region_words(max_n);
+  *stride_words = reg_words;
+  *used_regions = fxr::cells((max_n + 63) / 64);
+  if (!regions_out) return 0;
+  const unsigned long long* regions = reinterpret_cast<const unsigned long long*>(d_work) + (work_cap - reg_words * (int64_t)batch);
+  hipError_t e = hipMemcpy(regions_out, regions, (size_t)reg_words * (size_t)batch * 8, hipMemcpyDeviceToHost);
+  if (e == hipSuccess && seg_counts)
+    e = hipMemcpy(seg_counts, reinterpret_cast<const char*>(d_prep) + sizeof(TimPrep) * (size_t)batch, 4 * (size_t)batch,
+                  hipMemcpyDeviceToHost);
+  return (int)e;
 }
 
 #ifdef TEASER_K1_LAB
@@ -1305,12 +1353,9 @@ void launch_tim_graph_mfma(hipStream_t s, int phase, const ProbDesc* d_desc, int
                                                             sizeof(TimPrep) * (size_t)batch);  // [batch]
   const int64_t reg_words = tim_region_words(max_n);  // per problem
   unsigned long long* regions = work + (work_cap - reg_words * (int64_t)batch);  // behind the counted segments
-  int chunks = kK1Chunks;
 #ifdef TEASER_K1_LAB
   const K1Variant lab = k1_lab_variant();
-  chunks = lab.chunks;
 #endif
-  const int64_t regs_per_problem = tim_regions_per_problem(T, chunks);
   if (phase == 0) {
     // prep (and the worklist counter behind it) arrive zeroed: part of the solve's header upload
     hipLaunchKernelGGL(tim_prep_bbox_kernel, dim3((max_n + 1023) / 1024, batch), dim3(256), 0, s, d_desc,
@@ -1324,7 +1369,7 @@ void launch_tim_graph_mfma(hipStream_t s, int phase, const ProbDesc* d_desc, int
 #define TIM_K1_LAUNCH_OCC(PIPE, PLAIN, OCC, CHUNKS)                                                               \
   hipLaunchKernelGGL((tim_graph_mfma3_kernel<PIPE, PLAIN, OCC, CHUNKS>), dim3(tim_mfma_blocks(T, CHUNKS), batch), \
                      dim3(256), 0, s, d_desc, d_src, d_dst, reinterpret_cast<const TimOperandTile2*>(d_pk), prep, \
-                     d_bitmap, beta, gyr, work, work_count, d_state, d_deg, regions)
+                     d_bitmap, beta, gyr, work, work_count, d_state, d_deg, regions, T)
 #ifdef TEASER_K1_LAB
 #define TIM_K1_LAB_CASE(PIPE, PLAIN)                             \
   if (lab.pipe == (PIPE ? 1 : 0) && lab.plain == (PLAIN ? 1 : 0)) { \
@@ -1347,13 +1392,14 @@ void launch_tim_graph_mfma(hipStream_t s, int phase, const ProbDesc* d_desc, int
 #undef TIM_K1_LAUNCH
 #undef TIM_K1_LAUNCH_OCC
   } else {
-    // a wave per region of the largest problem (up to 2048 workgroups per problem); the kernel also counts the
-    // degrees of the problems that ran the FP64 body inside K1 (no degree atomics there)
+    // a wave per PAIR of row tiles (p, T - 1 - p) of the largest problem, four pairs per workgroup; S_FIXUP_WGS forces
+    // the workgroups per problem (the waves stride over the pairs).  The kernel also counts the degrees of the
+    // problems that ran the FP64 body inside K1 (no degree atomics there)
     const int64_t forced_wgs = setting(S_FIXUP_WGS);
-    const int64_t fix_wgs = forced_wgs > 0 ? forced_wgs : std::min<int64_t>(2048, (regs_per_problem + 3) / 4);
+    const int64_t fix_wgs = forced_wgs > 0 ? forced_wgs : ((T + 1) / 2 + 3) / 4;
     hipLaunchKernelGGL(tim_fixup_group_kernel, dim3((unsigned)std::max<int64_t>(4, fix_wgs), batch),
                        dim3(256), 0, s, d_desc, batch, d_src, d_dst, d_bitmap, beta, work, work_count, d_state, d_deg,
-                       regions, (unsigned int)regs_per_problem, prep);
+                       regions, T, prep);
   }
 }
 

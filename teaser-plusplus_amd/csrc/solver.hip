@@ -2262,6 +2262,25 @@ int32_t teaser_hip_get_degrees(teaser_hip_solver* h, int32_t problem, int32_t* b
   return copy_out(h, h->d_deg.as<int32_t>() + d.pt_off, (int64_t)d.n, buf, len);
 }
 
+// DIAGNOSTIC, not part of the ABI (no declaration in teaser_hip.h; scripts/probe/k1_probe declares it itself): the
+// fix-up's region arena and per-problem segment counters as the last matrix-core K1 of this handle left them.
+// regions == nullptr: sizes only (stride per problem in 8-byte words, regions per problem in use, problems).
+TEASER_HIP_API int32_t teaser_hip_probe_k1_worklist(teaser_hip_solver* h, uint64_t* regions, int64_t* stride_words,
+                                                    int64_t* used_regions, int32_t* problems, uint32_t* seg_counts) {
+  int32_t problem = 0;
+  CHECK_PROBLEM(h, problem);
+  if (!stride_words || !used_regions || !problems || !h->d_work.p || !h->d_prep.p) return TEASER_HIP_ERR_BAD_ARG;
+  std::vector<int32_t> n((size_t)h->batch);
+  int max_n = 0;
+  for (int b = 0; b < h->batch; ++b) max_n = std::max(max_n, n[(size_t)b] = h->descs[(size_t)b].n);
+  *problems = h->batch;
+  HIPCHK(h, hipDeviceSynchronize());
+  HIPCHK(h, (hipError_t)tim_probe_worklist(h->d_prep.p, h->d_work.p, tim_work_items(n.data(), h->batch), h->batch, max_n,
+                                           reinterpret_cast<unsigned long long*>(regions), stride_words, used_regions,
+                                           seg_counts));
+  return TEASER_HIP_OK;
+}
+
 int32_t teaser_hip_solve_for_rotation(teaser_hip_solver* h, const double* src, const double* dst,
                                       int32_t k, double noise_bound, double* rotation,
                                       uint8_t* inlier_mask, double* cost, int32_t* iterations) {
