@@ -12,11 +12,17 @@ on the MI355X.  Usage:
                                           [--knn K [--no-mutual]] [--tuple-scale S [--tuple-seed N]]
                                           [--iss [--iss-radii RS,RN]]
                                           [--ransac [--ransac-iterations N --ransac-seed N]]
+                                          [--fgr [--fgr-tuple-test --fgr-seed N]]
 
 --ransac runs Open3D's registration_ransac_based_on_correspondence on the GPU on the SAME correspondences the TEASER++
 solver got (max_correspondence_distance = 1.5 voxels, the edge-length checker at 0.9 and the distance checker at 1.5
 voxels, as Open3D's global-registration tutorial sets them) and prints its pose, fitness, RMSE and trial counts beside
 TEASER++'s, with the rotation and translation difference between the two.  --ransac-iterations is RANSAC-1K / 10K's N.
+
+--fgr runs Open3D's registration_fgr_based_on_correspondence (Fast Global Registration) on the GPU on the SAME
+correspondences (maximum_correspondence_distance = 0.5 voxels, as Open3D's global-registration tutorial sets it, the
+other options at their defaults) and prints its pose, fitness and RMSE beside TEASER++'s in the same way.
+--fgr-tuple-test first passes the pairs through the tuple test (tuple_scale 0.95, seeded by --fgr-seed).
 
 --iss detects ISS keypoints (Open3D's compute_iss_keypoints) in both down-sampled clouds on the GPU and matches only
 them: FPFH is still computed on the whole clouds (its neighbourhoods need every point), the descriptor rows at the
@@ -174,6 +180,10 @@ def main():
                     help="also run RANSAC on the same correspondences (on the GPU) and print it beside TEASER++")
     ap.add_argument("--ransac-iterations", type=int, default=100000, metavar="N")
     ap.add_argument("--ransac-seed", type=int, default=1, metavar="N", help="seed of the trials (0: the clock)")
+    ap.add_argument("--fgr", action="store_true",
+                    help="also run Fast Global Registration on the same correspondences (on the GPU)")
+    ap.add_argument("--fgr-tuple-test", action="store_true", help="with --fgr: Open3D's tuple test on the pairs first")
+    ap.add_argument("--fgr-seed", type=int, default=1, metavar="N", help="seed of the tuple test (0: the clock)")
     a = ap.parse_args()
     if a.iss and a.batch > 0:
         ap.error("--iss registers a single pair: it cannot be combined with --batch")
@@ -262,6 +272,24 @@ def main():
         print("R_ransac =\n%s\nt_ransac = %s" % (Rr, tr))
         print("RANSAC against TEASER++: rotation %.4g rad, translation %.4g" % (np.arccos(cos),
                                                                                np.linalg.norm(tr - sol.translation)))
+    if a.fgr:
+        P, Q = np.asarray(A, dtype=np.float64), np.asarray(B, dtype=np.float64)
+        pairs = np.array(corr, dtype=np.int32).reshape(-1, 2)
+        opt = tp.FastGlobalRegistrationOption(maximum_correspondence_distance=0.5 * vox, tuple_test=a.fgr_tuple_test,
+                                              seed=a.fgr_seed)
+        tp.registration_fgr_based_on_correspondence(P[:3], Q[:3], [[0, 0]] * 3, opt)  # the handles
+        t3 = time.perf_counter()
+        fg = tp.registration_fgr_based_on_correspondence(P, Q, pairs, opt)
+        t4 = time.perf_counter()
+        Rf, tf = fg.transformation[:3, :3], fg.transformation[:3, 3]
+        cos = min(1.0, max(-1.0, (np.trace(Rf.T @ sol.rotation) - 1.0) / 2.0))
+        print("FGR on %d of the same %d correspondences: %d iterations, %d failed solves, final mu %.4g, %.1f ms"
+              % (fg.fgr["n_corr"], len(pairs), fg.fgr["iterations"], fg.fgr["failed_solves"], fg.fgr["final_mu"],
+                 1e3 * (t4 - t3)))
+        print("FGR fitness %.6f rmse %.6f inliers %d" % (fg.fitness, fg.inlier_rmse, len(fg.correspondence_set)))
+        print("R_fgr =\n%s\nt_fgr = %s" % (Rf, tf))
+        print("FGR against TEASER++: rotation %.4g rad, translation %.4g" % (np.arccos(cos),
+                                                                            np.linalg.norm(tf - sol.translation)))
     if a.certify:
         c = np.array(corr)
         inl = np.zeros(len(c), dtype=bool)

@@ -61,5 +61,11 @@ struct LazyRansac : LazyHandle<teaser_hip_ransac, teaser_hip_ransac_destroy> {
   }
 };
 
+struct LazyFgr : LazyHandle<teaser_hip_fgr, teaser_hip_fgr_destroy> {
+  void create(const char* who) {
+    if (!h_) created(who, "fgr", teaser_hip_fgr_create(/*device=*/-1, &h_));
+  }
+};
+
 }  // namespace detail
 }  // namespace teaser

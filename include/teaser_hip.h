@@ -1348,6 +1348,122 @@ TEASER_HIP_API int32_t teaser_hip_ransac_trials_batch(
     const teaser_ransac_params_c* params, int64_t first, int32_t n, int32_t* samples, uint8_t* flags,
     double* transformations, int32_t* count, double* sum_d2);
 
+/* Fast Global Registration on correspondences: Open3D's registration_fgr_based_on_correspondence (Zhou, Park, Koltun,
+ * ECCV 2016; Open3D's FastGlobalRegistration.cpp from NormalizePointCloud on), batched, on its OWN handle.  Open3D is
+ * RESTATED here, not run: what follows is the contract, and where it departs from Open3D it says so.  Everything is
+ * FP64, nothing is fused, there are no floating-point atomics, and every summation order depends on the problem's own
+ * sizes alone.
+ * Per problem: source P (n_s x 3 doubles) and target Q (n_t x 3), xyz interleaved, both non-empty; ncorr >= 0 pairs
+ * (i, j) int32, used in the caller's order, repeats allowed; the options of teaser_fgr_params_c.
+ *   block order of a sum over n items (points of a cloud, or pairs): the items are cut into blocks of 256 consecutive
+ *            items, the last one padded with +0.0 terms.  Inside a block item k sits in lane k mod 64 of wave k div 64;
+ *            the 64 lanes of a wave are combined by v <- v + v[lane xor o] for o = 32, 16, 8, 4, 2, 1 (every lane ends
+ *            with the same value), and the four waves as (w0 + w1) + (w2 + w3): the block's partial.  The partials of
+ *            the ceil(n / 256) blocks are combined by 256 accumulators, accumulator t = ((0.0 + partial[t]) +
+ *            partial[t + 256]) + ... in ascending block index, and the 256 accumulators by the same rule as the 256
+ *            items of a block.
+ *   normalise (Open3D's NormalizePointCloud): mu_P, mu_Q = the coordinate sums over ALL points of each cloud in the
+ *            block order, divided by n; scale = the largest sqrt((dx dx + dy dy) + dz dz) of any centred point
+ *            (dx = x - mu.x ...) of either cloud.  use_absolute_scale: scale_global = 1, scale_start = scale; otherwise
+ *            scale_global = scale, scale_start = 1.  Records per pair c: p~_c = (P[i_c] - mu_P) / scale_global,
+ *            q_c = (Q[j_c] - mu_Q) / scale_global, one subtraction and one correctly rounded division per coordinate.
+ *            scale = 0 (both clouds a single repeated point whose mean is that point): the records are 0, the
+ *            optimisation is skipped and flag bit 1 is set.
+ *   optimise (Open3D's OptimizePairwiseRegistration; the TARGET side moves, as in Open3D): trans = I, mu = scale_start.
+ *            ncorr < 10: Open3D's rule, no iterations, flag bit 0.  Otherwise for itr = 0 .. iteration_number - 1, per
+ *            pair with p = p~_c, q = q_c:
+ *              e = p - q;  t = mu / (((e0 e0 + e1 e1) + e2 e2) + mu);  s = t t
+ *              rows J0 = (0, -q2, q1, -1, 0, 0), J1 = (q2, 0, -q0, 0, -1, 0), J2 = (-q1, q0, 0, 0, 0, -1), residuals e0 e1 e2
+ *              the pair's term of A = s (J0 J0^T + J1 J1^T + J2 J2^T), upper triangle by rows:
+ *                A00 = s (q2 q2 + q1 q1)  A01 = s (0 - q1 q0)  A02 = s (0 - q2 q0)  A03 = 0  A04 = s (0 - q2)  A05 = s q1
+ *                A11 = s (q2 q2 + q0 q0)  A12 = s (0 - q2 q1)  A13 = s q2  A14 = 0  A15 = s (0 - q0)
+ *                A22 = s (q1 q1 + q0 q0)  A23 = s (0 - q1)  A24 = s q0  A25 = 0
+ *                A33 = s  A34 = 0  A35 = 0  A44 = s  A45 = 0  A55 = s
+ *              and of g = s (e0 J0 + e1 J1 + e2 J2):
+ *                g0 = s (e1 q2 - e2 q1)  g1 = s (e2 q0 - e0 q2)  g2 = s (e0 q1 - e1 q0)
+ *                g3 = s (0 - e0)  g4 = s (0 - e1)  g5 = s (0 - e2)
+ *            A and g = the 27 sums over the pairs in the block order.  Solve A xi = -g by the unpivoted LDL^T of
+ *            point-to-plane ICP (above: the same recurrences); delta = [Rz(xi2) Ry(xi1) Rx(xi0) | xi3 xi4 xi5] with
+ *            the entries of R written as the ICP contract's.  If a pivot is not finite or not positive, or xi is not
+ *            finite, delta = I and failed_solves counts the step; the ICP contract's wording on pivots that are zero
+ *            only up to rounding applies.  trans = delta trans (row r, column c: ((d_r0 t_0c + d_r1 t_1c) + d_r2 t_2c)
+ *            + d_r3 t_3c); every record moves in place, q <- apply(delta, q) of the ICP contract (Open3D also moves
+ *            its copy step by step).  Then, if decrease_mu and itr % 4 == 0 and mu > maximum_correspondence_distance:
+ *            mu = mu / division_factor.  Open3D's quirk is kept: with use_absolute_scale = 0 this compares a distance
+ *            given in the caller's units with mu in NORMALISED units.
+ *   back to the caller's frame (Open3D's GetTransformationOriginalScale, then the inverse): with trans = [R | t],
+ *            t_M = ((t scale_global) - ((R_r0 muQ_0 + R_r1 muQ_1) + R_r2 muQ_2)) + muP_r per row r, M = [R | t_M] maps
+ *            target to source, and the result T = [R^T | 0 - ((R_0r tM_0 + R_1r tM_1) + R_2r tM_2)] maps source to
+ *            target.  DEPARTURE: Open3D calls a general 4 x 4 inverse; this takes the rigid inverse.  ncorr < 10,
+ *            iteration_number = 0 and scale = 0 therefore give the centroid alignment [I | mu_Q - mu_P], not the
+ *            identity.
+ * Output per problem: transformation (T), optimised (trans), scale_global, scale_start, final_mu, iterations,
+ * n_corr, failed_solves, flags (bit 0: ncorr < 10, bit 1: scale = 0).  The result is a function of the inputs alone:
+ * not of the batch around the problem, not of the route ("resident_max_corr" below), and the same bits run to run.
+ * maximum_tuple_count, tuple_scale and the tuple test itself belong to the front-ends (teaser_hip_features_tuple_test_batch).
+ * TEASER_HIP_ERR_BAD_ARG (teaser_hip_fgr_last_error names the argument and the problem), found on the host before
+ * anything is launched or written: an empty cloud, non-finite points, an index outside its cloud, division_factor not
+ * finite or <= 1, maximum_correspondence_distance not finite or <= 0, iteration_number outside 0 .. 1024, a switch
+ * that is not 0 or 1, NULL where a count is positive. */
+typedef struct teaser_fgr_params_c {
+  double division_factor;                 /* 1.4 */
+  double maximum_correspondence_distance; /* 0.025 */
+  int32_t use_absolute_scale;             /* 0 */
+  int32_t decrease_mu;                    /* 1 */
+  int32_t iteration_number;               /* 64 */
+  int32_t reserved;
+} teaser_fgr_params_c;
+typedef struct teaser_fgr_result_c {
+  double transformation[16]; /* row-major 4 x 4, source -> target */
+  double optimised[16];      /* trans: moves the normalised target records */
+  double scale_global;
+  double scale_start;
+  double final_mu;
+  int32_t iterations;
+  int32_t n_corr;
+  int32_t failed_solves;
+  int32_t flags;
+} teaser_fgr_result_c;
+typedef struct teaser_hip_fgr teaser_hip_fgr;
+/* device < 0: the current HIP device.  TEASER_HIP_ERR_NO_DEVICE without a GPU: there is no CPU path. */
+TEASER_HIP_API int32_t teaser_hip_fgr_create(int32_t device, teaser_hip_fgr** out);
+TEASER_HIP_API int32_t teaser_hip_fgr_destroy(teaser_hip_fgr* fgr);
+TEASER_HIP_API const char* teaser_hip_fgr_last_error(const teaser_hip_fgr* fgr);
+/* The defaults noted beside the fields above (Open3D's FastGlobalRegistrationOption). */
+TEASER_HIP_API int32_t teaser_hip_fgr_params_default(teaser_fgr_params_c* params);
+/* `batch` independent problems, HOST pointers per problem, borrowed for the call: src[b] n_src[b] x 3, dst[b]
+ * n_dst[b] x 3, corr[b] n_corr[b] x 2 int32 (source index, target index); params and out: one per problem.  One
+ * upload, one download and one synchronisation per call, whatever the batch. */
+TEASER_HIP_API int32_t teaser_hip_fgr_correspondence_batch(
+    teaser_hip_fgr* fgr, int32_t batch, const double* const* src, const int32_t* n_src, const double* const* dst,
+    const int32_t* n_dst, const int32_t* const* corr, const int32_t* n_corr, const teaser_fgr_params_c* params,
+    teaser_fgr_result_c* out);
+/* One problem: teaser_hip_fgr_correspondence_batch with batch = 1. */
+TEASER_HIP_API int32_t teaser_hip_fgr_correspondence(teaser_hip_fgr* fgr, const double* src, int32_t n_src,
+                                                     const double* dst, int32_t n_dst, const int32_t* corr,
+                                                     int32_t n_corr, const teaser_fgr_params_c* params,
+                                                     teaser_fgr_result_c* out);
+/* One knob per handle, "resident_max_corr" in [0, 3072] (default 256): a problem with at most that many pairs is
+ * solved by ONE launch that keeps its records (48 bytes a pair, whole blocks of 256) in LDS; a larger one streams its
+ * records from device memory, two launches an iteration.  0 forces the streamed route.  The bound is 12 blocks =
+ * 147 456 bytes, what fits the 160 KB of LDS a workgroup may own beside the sums; the default is 1 block = 12 KB: a
+ * resident problem's one workgroup walks its blocks in turn, and from a few blocks up the streamed route, which spreads
+ * them over the device, was measured faster.  A tuning switch: no value changes a bit of any result.  BAD_ARG for
+ * another name or a value out of range. */
+TEASER_HIP_API int32_t teaser_hip_fgr_set_option(teaser_hip_fgr* fgr, const char* name, int64_t value);
+TEASER_HIP_API int32_t teaser_hip_fgr_get_option(const teaser_hip_fgr* fgr, const char* name, int64_t* value);
+/* Stage call: the first n iterations (0 <= n <= iteration_number of every problem) through the SAME kernels and
+ * routes.  Per problem b and iteration k, at [b n + k]: mu (the value the step used), A (36, row-major, mirrored),
+ * g (6), xi (6; zeros when a pivot failed), solve_flag (1: the solve failed and delta = I) and trans (16) after the
+ * step; a problem that is not optimised (ncorr < 10, scale = 0) leaves zeros.  p_records / q_records: p~ and the moved
+ * records q AFTER the n-th step, 3 doubles a pair, the problems' pairs one after the other in batch order.  out as in
+ * the full call, with transformation taken from trans after n steps.  Any output may be NULL. */
+TEASER_HIP_API int32_t teaser_hip_fgr_iterations_batch(
+    teaser_hip_fgr* fgr, int32_t batch, const double* const* src, const int32_t* n_src, const double* const* dst,
+    const int32_t* n_dst, const int32_t* const* corr, const int32_t* n_corr, const teaser_fgr_params_c* params,
+    int32_t n, teaser_fgr_result_c* out, double* mu, double* A, double* g, double* xi, int32_t* solve_flag,
+    double* trans, double* p_records, double* q_records);
+
 /* Page-locked host memory from the HIP runtime THIS library runs on.  teaser_hip_submit_batch(..., INPUT_HOST) moves
  * the points with one DMA copy per cloud, at PCIe speed only when the runtime knows the pages are locked.  A buffer
  * pinned by another HIP runtime instance in the same process (e.g. the one a Python framework bundles) is pageable

@@ -154,6 +154,9 @@ EXPORTED_SYMBOLS = [
     "teaser_hip_ransac_create", "teaser_hip_ransac_destroy", "teaser_hip_ransac_last_error",
     "teaser_hip_ransac_params_default", "teaser_hip_ransac_correspondence_batch", "teaser_hip_ransac_correspondence",
     "teaser_hip_ransac_set_option", "teaser_hip_ransac_get_option", "teaser_hip_ransac_trials_batch",
+    "teaser_hip_fgr_create", "teaser_hip_fgr_destroy", "teaser_hip_fgr_last_error", "teaser_hip_fgr_params_default",
+    "teaser_hip_fgr_correspondence_batch", "teaser_hip_fgr_correspondence", "teaser_hip_fgr_set_option",
+    "teaser_hip_fgr_get_option", "teaser_hip_fgr_iterations_batch",
 ]
 
 
@@ -251,6 +254,8 @@ def lib():
     _posegraph.declare(L)
     from . import ransac as _ransac
     _ransac.declare(L)
+    from . import fgr as _fgr
+    _fgr.declare(L)
     _lib = L
     return L
 
@@ -1118,6 +1123,9 @@ from .ransac import (RANSACConvergenceCriteria, CorrespondenceCheckerBasedOnEdge
                      registration_ransac_based_on_correspondence, registration_ransac_based_on_correspondence_batch,
                      registration_ransac_based_on_feature_matching, feature_matching_correspondences,
                      ransac_trials_batch, set_ransac_option, get_ransac_option)
+from .fgr import (FastGlobalRegistrationOption, registration_fgr_based_on_correspondence,  # noqa: E402
+                  registration_fgr_based_on_correspondence_batch, registration_fgr_based_on_feature_matching,
+                  fgr_iterations_batch, set_fgr_option, get_fgr_option)
 
 __all__ = ["batched", "FPFHEstimation", "Matcher", "MultiDeviceSolver", "RobustRegistrationSolver", "RegistrationSolution", "RotationEstimationAlgorithm",
            "InlierSelectionMode", "InlierGraphFormulation", "TeaserHipError", "synth_problem",
@@ -1145,4 +1153,7 @@ __all__ = ["batched", "FPFHEstimation", "Matcher", "MultiDeviceSolver", "RobustR
            "RANSACConvergenceCriteria", "CorrespondenceCheckerBasedOnEdgeLength", "CorrespondenceCheckerBasedOnDistance",
            "CorrespondenceCheckerBasedOnNormal", "registration_ransac_based_on_correspondence",
            "registration_ransac_based_on_correspondence_batch", "registration_ransac_based_on_feature_matching",
-           "feature_matching_correspondences", "ransac_trials_batch", "set_ransac_option", "get_ransac_option"]
+           "feature_matching_correspondences", "ransac_trials_batch", "set_ransac_option", "get_ransac_option",
+           "FastGlobalRegistrationOption", "registration_fgr_based_on_correspondence",
+           "registration_fgr_based_on_correspondence_batch", "registration_fgr_based_on_feature_matching",
+           "fgr_iterations_batch", "set_fgr_option", "get_fgr_option"]
