@@ -6,6 +6,7 @@ nearest-neighbour correspondences -> TEASER++ registration -> optional DRS certi
 on the MI355X.  Usage:
 
     python examples/teaser_python_fpfh.py [src.ply dst.ply] [--voxel 0.05] [--certify] [--icp [--icp-iterations 100]]
+                                          [--remove-plane D [--plane-seed N]]
                                           [--icp-plane [--icp-kernel tukey --icp-kernel-k K]]
                                           [--icp-plane-normals hybrid:R:K|knn:K]
                                           [--icp-gicp [--gicp-radius R --gicp-max-nn K]] [--batch K]
@@ -13,6 +14,11 @@ on the MI355X.  Usage:
                                           [--iss [--iss-radii RS,RN]]
                                           [--ransac [--ransac-iterations N --ransac-seed N]]
                                           [--fgr [--fgr-tuple-test --fgr-seed N]]
+
+--remove-plane D drops the dominant plane (Open3D's segment_plane on the GPU: distance_threshold D, ransac_n 3, 1 000
+iterations, seeded by --plane-seed) from BOTH clouds after down-sampling and before FPFH, in one batched call, and
+prints each plane and the share of points removed.  A floor or a road holds a large part of a scan, its descriptors are
+all alike, and it lets ICP slide along it.  Off by default.
 
 --ransac runs Open3D's registration_ransac_based_on_correspondence on the GPU on the SAME correspondences the TEASER++
 solver got (max_correspondence_distance = 1.5 voxels, the edge-length checker at 0.9 and the distance checker at 1.5
@@ -184,7 +190,12 @@ def main():
                     help="also run Fast Global Registration on the same correspondences (on the GPU)")
     ap.add_argument("--fgr-tuple-test", action="store_true", help="with --fgr: Open3D's tuple test on the pairs first")
     ap.add_argument("--fgr-seed", type=int, default=1, metavar="N", help="seed of the tuple test (0: the clock)")
+    ap.add_argument("--remove-plane", type=float, default=0.0, metavar="D",
+                    help="drop the dominant plane (segment_plane, distance threshold D) from both clouds before FPFH")
+    ap.add_argument("--plane-seed", type=int, default=1, metavar="N", help="seed of the plane trials (0: the clock)")
     a = ap.parse_args()
+    if a.remove_plane > 0 and a.batch > 0:
+        ap.error("--remove-plane serves a single pair: it cannot be combined with --batch")
     if a.iss and a.batch > 0:
         ap.error("--iss registers a single pair: it cannot be combined with --batch")
     if a.batch > 0:
@@ -207,6 +218,18 @@ def main():
         c5 = np.load(os.path.join(ROOT, "tests", "golden", "config5_clouds.npz"))
         A, B, a.voxel = c5["cloud_bin_0"], c5["cloud_bin_4"], float(c5["voxel_size"])
     vox = a.voxel
+    if a.remove_plane > 0:  # the floor or the road floods the matcher with look-alike descriptors: take it out first
+        t = time.perf_counter()
+        found = tp.segment_plane_batch([A, B], a.remove_plane, 3, 1000, 0.99999999, a.plane_seed)
+        t_plane = time.perf_counter() - t
+        kept = []
+        for name, cloud, r in (("source", A, found[0]), ("target", B, found[1])):
+            print("dominant plane of the %s: %s, %d of %d points (%.1f %%) removed after %d trials"
+                  % (name, np.array2string(r.plane_model, precision=5), len(r.inliers), len(cloud),
+                     100.0 * len(r.inliers) / max(len(cloud), 1), r.trials))
+            kept.append(cloud[r.mask == 0])
+        print("plane segmentation of both clouds: %.1f ms (one call)" % (1e3 * t_plane))
+        A, B = kept
     outliers = parse_outliers(a.remove_outliers)
     if outliers:
         t = time.perf_counter()

@@ -67,5 +67,11 @@ struct LazyFgr : LazyHandle<teaser_hip_fgr, teaser_hip_fgr_destroy> {
   }
 };
 
+struct LazyPlane : LazyHandle<teaser_hip_plane, teaser_hip_plane_destroy> {
+  void create(const char* who) {
+    if (!h_) created(who, "plane", teaser_hip_plane_create(/*device=*/-1, &h_));
+  }
+};
+
 }  // namespace detail
 }  // namespace teaser

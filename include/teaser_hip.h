@@ -1464,6 +1464,120 @@ TEASER_HIP_API int32_t teaser_hip_fgr_iterations_batch(
     int32_t n, teaser_fgr_result_c* out, double* mu, double* A, double* g, double* xi, int32_t* solve_flag,
     double* trans, double* p_records, double* q_records);
 
+/* Plane segmentation: Open3D's PointCloud.segment_plane (RANSAC for the dominant plane), batched, on its OWN handle.
+ * Open3D is RESTATED here, not run: what follows is the contract, and where it departs from Open3D it says so.
+ * Everything is FP64, nothing is fused, there are no floating-point atomics, square roots and divisions are correctly
+ * rounded, and every summation order is a function of the problem's own n alone.
+ * Per problem: the cloud P (n x 3 doubles, xyz interleaved); distance_threshold d, finite and > 0; ransac_n in 3 .. 8;
+ * num_iterations (int32 >= 0); probability in (0, 1]; a uint64 seed (0: from the clock, time(NULL) read once per call
+ * and used for every problem whose seed is 0, as in the RANSAC contract).
+ *   trial i (int64, from 0): its samples are c_k = z(seed, ransac_n i + k + 1) mod n for k = 0 .. ransac_n - 1, z the
+ *            splitmix64 finaliser of the tuple-test and RANSAC contracts (wrapping 64-bit arithmetic, the exact 64-bit
+ *            remainder).  Sampling is WITH replacement.  DEPARTURE: Open3D samples without replacement from its own
+ *            generator; here a repeated index simply gives a degenerate (ransac_n = 3) or a less spread trial.
+ *   normalise(abc, anchor): len = sqrt((a a + b b) + c c).  If len is zero or not finite (inf, NaN) the result is the
+ *            ZERO plane (0, 0, 0, 0).  Otherwise a, b, c are each divided by len (three divisions),
+ *            s = (a anchor.x + b anchor.y) + c anchor.z and the plane is (a, b, c, -s).
+ *   model, ransac_n = 3: p0, p1, p2 = the samples; e0 = p1 - p0, e1 = p2 - p0; abc = e0 x e1, each component
+ *            u v - w x as two products and one subtraction: (e0.y e1.z - e0.z e1.y, e0.z e1.x - e0.x e1.z,
+ *            e0.x e1.y - e0.y e1.x); the plane is normalise(abc, p0).
+ *   model, ransac_n > 3: plane_from_points over the samples in sample order, every sum sequential from 0.0.
+ *   A trial whose model is the zero plane is DEGENERATE.
+ *   plane_from_points(S): Open3D's GetPlaneFromPoints, the determinant-based fast fit -- NOT a total-least-squares
+ *            plane.  m = |S|; centroid = the three coordinate sums, each divided by (double) m; with r = p - centroid
+ *            the six sums xx, xy, xz, yy, yz, zz of the products of r's components; det_x = yy zz - yz yz,
+ *            det_y = xx zz - xz xz, det_z = xx yy - xy xy.  The axis is x, unless det_y > det_x: then y; and z if det_z
+ *            exceeds the larger of the two (on a tie the first of x, y, z wins).
+ *              x: abc = (det_x, xz yz - xy zz, xy yz - xz yy)
+ *              y: abc = (xz yz - xy zz, det_y, xy xz - yz xx)
+ *              z: abc = (xy yz - xz yy, xy xz - yz xx, det_z)
+ *            The result is normalise(abc, centroid).
+ *   position order of a sum over the n positions of the cloud: the positions are cut into blocks of 256 consecutive
+ *            indices; a block's terms are added in ascending index starting from 0.0; the blocks are cut into groups of
+ *            64 consecutive blocks and a group's block sums are added in ascending order from 0.0; the group sums are
+ *            added in ascending order from 0.0.  A position that contributes nothing adds nothing (it is skipped, not
+ *            added as 0.0).  DEPARTURE: Open3D adds in plain index order.
+ *   score    of a trial that is not degenerate, over ALL n points: dist = |((a x + b y) + c z) + d4|; a point is an
+ *            inlier iff dist < d; count = the number of inliers; E = the sum of dist over the inliers in position
+ *            order; fitness = count / n; inlier_rmse = E / sqrt(count), 0 when count = 0 (Open3D's expression, kept
+ *            although it sums distances and not squares: it only breaks ties).
+ *   loop     Open3D's, as ONE thread runs it: best = {zero plane, count 0, rmse 0}, k = +inf (a double), counted = 0;
+ *            for i = 0 .. num_iterations - 1: stop when counted > k; a degenerate trial is skipped and not counted; a
+ *            trial replaces best iff count > best.count, or count == best.count and rmse < best.rmse (strict: earlier
+ *            trials keep ties); on a replacement k = 0 when count == n, otherwise
+ *            k = min(log(1 - probability) / log(1 - pow(fitness, ransac_n)), num_iterations) in host double with the C
+ *            library's log and pow, min(a, b) = a < b ? a : b with the quotient first; then counted += 1 for every
+ *            trial that is not degenerate.  DEPARTURE: k stays a double; this equals Open3D's truncated size_t
+ *            wherever that conversion is defined; a negative or -inf k stops at once (a fitness so small that
+ *            1 - pow(..) rounds to 1 gives log(..) = 0 and k = -inf, whatever the probability), a NaN k (min gives
+ *            num_iterations) never stops early, and neither does probability = 1 otherwise (k = +inf, capped).
+ *   finish   No trial replaced the start: the zero plane, no inliers.  Otherwise the inliers are the indices with
+ *            dist < d under the WINNING TRIAL's plane, ascending, and the returned plane is plane_from_points over
+ *            those inliers with all nine sums in position order (m > 0 always holds here).  As in Open3D the inliers
+ *            are those of the trial's plane, not of the refit; a refit that gives the zero plane is returned as such
+ *            with the inliers kept.
+ * Output per problem: plane[4], n_inliers, fitness and inlier_rmse of the winning trial, best_trial (-1: none),
+ * trials = the loop indices visited, valid_trials = those of them that were not degenerate, and optionally the inlier
+ * indices (int32, ascending, room for n) and / or a byte mask of n entries.  The result is a function of the inputs
+ * alone: not of "chunk_trials" or "partial_bytes" below, not of the batch around the problem, and the same bits run to
+ * run.  Work past the stopping trial is discarded, never reported.  n < ransac_n or num_iterations = 0 is not an
+ * error: the result is the start (zero plane, zeros, best_trial = -1, trials = 0).
+ * TEASER_HIP_ERR_BAD_ARG (teaser_hip_plane_last_error names the argument and the problem), found on the host before
+ * anything is launched or written: non-finite points, d not finite and > 0, ransac_n outside 3 .. 8, probability
+ * outside (0, 1] or NaN, a negative num_iterations, a negative n, NULL where a count is positive.  The handle stays
+ * usable after a refusal. */
+typedef struct teaser_plane_params_c {
+  double distance_threshold; /* d; no default (Open3D's argument is required) */
+  int32_t ransac_n;          /* 3 */
+  int32_t num_iterations;    /* 100 */
+  double probability;        /* 0.99999999 */
+  uint64_t seed;             /* 0: from the clock */
+} teaser_plane_params_c;
+typedef struct teaser_plane_result_c {
+  double plane[4]; /* a, b, c, d4: a x + b y + c z + d4 = 0 */
+  double fitness;
+  double inlier_rmse;
+  int64_t best_trial;
+  int64_t trials;
+  int64_t valid_trials;
+  int32_t n_inliers;
+  int32_t reserved;
+} teaser_plane_result_c;
+typedef struct teaser_hip_plane teaser_hip_plane;
+/* device < 0: the current HIP device.  TEASER_HIP_ERR_NO_DEVICE without a GPU: there is no CPU path. */
+TEASER_HIP_API int32_t teaser_hip_plane_create(int32_t device, teaser_hip_plane** out);
+TEASER_HIP_API int32_t teaser_hip_plane_destroy(teaser_hip_plane* plane);
+TEASER_HIP_API const char* teaser_hip_plane_last_error(const teaser_hip_plane* plane);
+/* The defaults noted beside the fields above (Open3D's segment_plane). */
+TEASER_HIP_API int32_t teaser_hip_plane_params_default(teaser_plane_params_c* params);
+/* `batch` independent problems, HOST pointers per problem, borrowed for the call: points[b] n[b] x 3; params and out:
+ * one per problem; inliers: NULL, or per problem NULL or room for n[b] int32, out[b].n_inliers written; mask: NULL, or
+ * per problem NULL or n[b] bytes (1: inlier).  Mixed sizes share the launches; batch = 0 and n[b] = 0 are valid. */
+TEASER_HIP_API int32_t teaser_hip_plane_segment_batch(teaser_hip_plane* plane, int32_t batch,
+                                                      const double* const* points, const int32_t* n,
+                                                      const teaser_plane_params_c* params, teaser_plane_result_c* out,
+                                                      int32_t* const* inliers, uint8_t* const* mask);
+/* One problem: teaser_hip_plane_segment_batch with batch = 1. */
+TEASER_HIP_API int32_t teaser_hip_plane_segment(teaser_hip_plane* plane, const double* points, int32_t n,
+                                                const teaser_plane_params_c* params, teaser_plane_result_c* out,
+                                                int32_t* inliers, uint8_t* mask);
+/* Two knobs per handle, both tuning switches: no value changes a bit of any result.  "chunk_trials" in [64, 4096]
+ * (default 256): the trials of a problem one launch sequence covers.  "partial_bytes" in [65536, 17179869184] (default
+ * 67108864): the budget of the (block, trial) partial array; a cloud whose partials exceed it is scored in waves of
+ * groups of blocks (one group per problem is the floor).  BAD_ARG for another name or a value out of range. */
+TEASER_HIP_API int32_t teaser_hip_plane_set_option(teaser_hip_plane* plane, const char* name, int64_t value);
+TEASER_HIP_API int32_t teaser_hip_plane_get_option(const teaser_hip_plane* plane, const char* name, int64_t* value);
+/* Stage call: trials first .. first + cnt - 1 (first >= 0, 0 <= cnt <= 65536) of every problem through the SAME
+ * kernels, with no stopping rule and no use of num_iterations or probability.  Per problem b and trial q, at
+ * [b cnt + q]: samples (8 int32, the first ransac_n used, the rest -1), flags (one byte: bit 0 = not degenerate),
+ * planes (4 doubles, zero when degenerate), count and E (0 when degenerate).  A problem with n < ransac_n draws
+ * nothing: samples -1, flags 0.  Any output may be NULL. */
+TEASER_HIP_API int32_t teaser_hip_plane_trials_batch(teaser_hip_plane* plane, int32_t batch,
+                                                     const double* const* points, const int32_t* n,
+                                                     const teaser_plane_params_c* params, int64_t first, int32_t cnt,
+                                                     int32_t* samples, uint8_t* flags, double* planes, int32_t* count,
+                                                     double* E);
+
 /* Page-locked host memory from the HIP runtime THIS library runs on.  teaser_hip_submit_batch(..., INPUT_HOST) moves
  * the points with one DMA copy per cloud, at PCIe speed only when the runtime knows the pages are locked.  A buffer
  * pinned by another HIP runtime instance in the same process (e.g. the one a Python framework bundles) is pageable

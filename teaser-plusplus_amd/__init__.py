@@ -157,6 +157,9 @@ EXPORTED_SYMBOLS = [
     "teaser_hip_fgr_create", "teaser_hip_fgr_destroy", "teaser_hip_fgr_last_error", "teaser_hip_fgr_params_default",
     "teaser_hip_fgr_correspondence_batch", "teaser_hip_fgr_correspondence", "teaser_hip_fgr_set_option",
     "teaser_hip_fgr_get_option", "teaser_hip_fgr_iterations_batch",
+    "teaser_hip_plane_create", "teaser_hip_plane_destroy", "teaser_hip_plane_last_error",
+    "teaser_hip_plane_params_default", "teaser_hip_plane_segment_batch", "teaser_hip_plane_segment",
+    "teaser_hip_plane_set_option", "teaser_hip_plane_get_option", "teaser_hip_plane_trials_batch",
 ]
 
 
@@ -256,6 +259,8 @@ def lib():
     _ransac.declare(L)
     from . import fgr as _fgr
     _fgr.declare(L)
+    from . import plane as _plane
+    _plane.declare(L)
     _lib = L
     return L
 
@@ -1126,6 +1131,8 @@ from .ransac import (RANSACConvergenceCriteria, CorrespondenceCheckerBasedOnEdge
 from .fgr import (FastGlobalRegistrationOption, registration_fgr_based_on_correspondence,  # noqa: E402
                   registration_fgr_based_on_correspondence_batch, registration_fgr_based_on_feature_matching,
                   fgr_iterations_batch, set_fgr_option, get_fgr_option)
+from .plane import (segment_plane, segment_plane_batch, plane_trials_batch, set_plane_option,  # noqa: E402
+                    get_plane_option)
 
 __all__ = ["batched", "FPFHEstimation", "Matcher", "MultiDeviceSolver", "RobustRegistrationSolver", "RegistrationSolution", "RotationEstimationAlgorithm",
            "InlierSelectionMode", "InlierGraphFormulation", "TeaserHipError", "synth_problem",
@@ -1156,4 +1163,5 @@ __all__ = ["batched", "FPFHEstimation", "Matcher", "MultiDeviceSolver", "RobustR
            "feature_matching_correspondences", "ransac_trials_batch", "set_ransac_option", "get_ransac_option",
            "FastGlobalRegistrationOption", "registration_fgr_based_on_correspondence",
            "registration_fgr_based_on_correspondence_batch", "registration_fgr_based_on_feature_matching",
-           "fgr_iterations_batch", "set_fgr_option", "get_fgr_option"]
+           "fgr_iterations_batch", "set_fgr_option", "get_fgr_option",
+           "segment_plane", "segment_plane_batch", "plane_trials_batch", "set_plane_option", "get_plane_option"]

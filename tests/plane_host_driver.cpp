@@ -1,0 +1,475 @@
+// Host-only check of csrc/plane.hip (tests/test_plane_host.py): compiled by g++ against the HIP stand-in header
+// (tests/hip_stub) with -fsanitize=address,undefined as a stand-alone program.  The launchers are stand-ins that run the
+// one-lane functions of csrc/plane_device.h on the CPU, one lane at a time, into the very buffers the host side sized
+// and packed (a wrong size or offset is an AddressSanitizer report or a wrong value).  Checked: the packing; the chunk
+// plan at chunk_trials 64, 256 and 4096; the full call against the contract's loop written out here, with a stop inside
+// a chunk and speculative chunks enqueued and dropped; point waves forced by a tiny partial budget; the stage call;
+// every refusal with its argument and problem.
+//   plane_host_driver    exit code 0 and "mismatches 0": every expectation met
+// TEST INFRASTRUCTURE ONLY.
+#include <hip/hip_runtime.h>
+
+#include <cstdio>
+#include <limits>
+
+#include "../teaser-plusplus_amd/csrc/plane.hip"
+
+static int g_bad = 0;
+#define EXPECT(c)                                                \
+  do {                                                           \
+    if (!(c)) {                                                  \
+      ++g_bad;                                                   \
+      printf("line %d: expectation failed: %s\n", __LINE__, #c); \
+    }                                                            \
+  } while (0)
+
+static int g_models = 0, g_scores = 0, g_finishes = 0, g_max_W = 0;
+static int64_t g_trials_launched = 0;
+static std::vector<int> g_chunk_sizes;
+static std::vector<const double*> g_clouds;  // the caller's clouds of the running call: the packing is checked against them
+
+namespace thip {
+
+void launch_plane_models(hipStream_t, int batch, int chunk, int max_n, const PlDesc* desc, const double* pts,
+                         const PlSlot& slot, int64_t first) {
+  ++g_models;
+  g_chunk_sizes.push_back(chunk);
+  int seen_max = 0;
+  for (int b = 0; b < batch; ++b) {
+    const PlDesc& D = desc[b];
+    if ((size_t)b < g_clouds.size() && D.n > 0)
+      EXPECT(memcmp(pts + 3 * D.pt_off, g_clouds[(size_t)b], sizeof(double) * 3 * D.n) == 0);
+    const int n = slot.n[b];
+    EXPECT(n >= 0 && n <= chunk);
+    seen_max = std::max(seen_max, n);
+    g_trials_launched += n;
+    for (int t = 0; t < n; ++t) {
+      const int64_t at = (int64_t)b * chunk + t;
+      int32_t smp[PL_MAX_N];
+      double w[4] = {0, 0, 0, 0};
+      int flags = 0;
+      if (D.run) flags = pl_model(D, pts + 3 * D.pt_off, first + t, smp, w);
+      for (int k = 0; k < 4; ++k) slot.model[4 * at + k] = w[k];
+      slot.flags[at] = (uint8_t)flags;
+      slot.count[at] = 0;
+      slot.E[at] = 0.0;
+      if (slot.samples)
+        for (int k = 0; k < PL_MAX_N; ++k) slot.samples[PL_MAX_N * at + k] = D.run ? smp[k] : -1;
+    }
+  }
+  EXPECT(seen_max == max_n);
+}
+
+void launch_plane_score(hipStream_t, int batch, int chunk, int max_n, const PlDesc* desc, const double* pts,
+                        const PlSlot& slot, const PlPart& part, int g0, int W) {
+  ++g_scores;
+  g_max_W = std::max(g_max_W, W);
+  for (int b = 0; b < batch; ++b) {
+    const PlDesc& D = desc[b];
+    const int64_t nblk = pl_blocks(D.n), ng = pl_groups(D.n);
+    EXPECT(slot.n[b] <= max_n);
+    for (int t = 0; t < slot.n[b]; ++t) {
+      const int64_t at = (int64_t)b * chunk + t;
+      const bool live = (slot.flags[at] & PL_FLAG_VALID) != 0;
+      for (int gl = 0; gl < W && g0 + gl < ng; ++gl) {
+        const int64_t gs = D.part_grp + gl;
+        int32_t gc = 0;
+        double gsum = 0.0;
+        for (int k = 0; k < PL_GROUP && (g0 + gl) * (int64_t)PL_GROUP + k < nblk; ++k) {
+          const int64_t blk = (g0 + gl) * (int64_t)PL_GROUP + k;
+          const int m = (int)std::min<int64_t>(PL_BLOCK, D.n - blk * PL_BLOCK);
+          int32_t c;
+          double s;
+          pl_score_block(slot.model + 4 * at, D.d, pts + 3 * (D.pt_off + blk * PL_BLOCK), m, &c, &s);
+          part.bcnt[(gs * PL_GROUP + k) * chunk + t] = live ? c : 0;
+          part.bsum[(gs * PL_GROUP + k) * chunk + t] = live ? s : 0.0;
+          gc += part.bcnt[(gs * PL_GROUP + k) * chunk + t];
+          gsum += part.bsum[(gs * PL_GROUP + k) * chunk + t];
+        }
+        part.gcnt[gs * chunk + t] = gc;
+        part.gsum[gs * chunk + t] = gsum;
+      }
+      for (int gl = 0; gl < W && g0 + gl < ng; ++gl) {
+        slot.count[at] += part.gcnt[(D.part_grp + gl) * chunk + t];
+        slot.E[at] += part.gsum[(D.part_grp + gl) * chunk + t];
+      }
+    }
+  }
+}
+
+static void fin_reduce(const PlDesc& D, const PlFin& fin, int32_t* count, double* S) {
+  const int64_t nblk = pl_blocks(D.n), ng = pl_groups(D.n);
+  for (int64_t g = 0; g < ng; ++g) {
+    double gs[6] = {0, 0, 0, 0, 0, 0};
+    int32_t c = 0;
+    for (int64_t k = g * PL_GROUP; k < std::min<int64_t>(nblk, (g + 1) * PL_GROUP); ++k) {
+      c += fin.bcnt[D.blk_off + k];
+      for (int q = 0; q < 6; ++q) gs[q] += fin.bsum[6 * (D.blk_off + k) + q];
+    }
+    fin.gcnt[D.grp_off + g] = c;
+    for (int q = 0; q < 6; ++q) fin.gsum[6 * (D.grp_off + g) + q] = gs[q];
+  }
+  *count = 0;
+  for (int q = 0; q < 6; ++q) S[q] = 0.0;
+  for (int64_t g = 0; g < ng; ++g) {
+    *count += fin.gcnt[D.grp_off + g];
+    for (int q = 0; q < 6; ++q) S[q] += fin.gsum[6 * (D.grp_off + g) + q];
+  }
+}
+
+void launch_plane_finish(hipStream_t, int batch, int max_points, const PlDesc* desc, const double* pts,
+                         const PlFin& fin) {
+  ++g_finishes;
+  for (int b = 0; b < batch; ++b) {
+    const PlDesc& D = desc[b];
+    EXPECT(D.n <= max_points);
+    double* w = fin.win + 4 * b;
+    int32_t smp[PL_MAX_N];
+    w[0] = w[1] = w[2] = w[3] = 0.0;
+    if (D.run && fin.best[b] >= 0) pl_model(D, pts + 3 * D.pt_off, fin.best[b], smp, w);
+    const int64_t nblk = pl_blocks(D.n);
+    double S[6];
+    int32_t c;
+    for (int64_t blk = 0; blk < nblk; ++blk) {
+      const int m = (int)std::min<int64_t>(PL_BLOCK, D.n - blk * PL_BLOCK);
+      const int64_t p0 = D.pt_off + blk * PL_BLOCK;
+      pl_fin_block_mask(fin.best[b] >= 0, w, D.d, pts + 3 * p0, m, fin.mask + p0, fin.bcnt + D.blk_off + blk,
+                        fin.bsum + 6 * (D.blk_off + blk));
+    }
+    fin_reduce(D, fin, &c, S);
+    fin.m[b] = c;
+    for (int q = 0; q < 3; ++q) fin.centroid[3 * b + q] = c > 0 ? S[q] / (double)c : 0.0;
+    for (int64_t blk = 0; blk < nblk; ++blk) {
+      const int m = (int)std::min<int64_t>(PL_BLOCK, D.n - blk * PL_BLOCK);
+      const int64_t p0 = D.pt_off + blk * PL_BLOCK;
+      pl_fin_block_cov(fin.centroid + 3 * b, pts + 3 * p0, m, fin.mask + p0, fin.bsum + 6 * (D.blk_off + blk));
+    }
+    fin_reduce(D, fin, &c, S);
+    double out[4] = {0, 0, 0, 0};
+    if (fin.m[b] > 0) pl_from_sums(fin.centroid + 3 * b, S, out);
+    for (int q = 0; q < 4; ++q) fin.plane[4 * b + q] = out[q];
+  }
+}
+
+}  // namespace thip
+
+// ---- problems ----
+struct Problem {
+  std::vector<double> P;
+  teaser_plane_params_c prm;
+};
+
+static uint64_t g_rng = 12345;
+static double uni() {
+  g_rng = g_rng * 6364136223846793005ull + 1442695040888963407ull;
+  return (double)(g_rng >> 11) / 9007199254740992.0 * 2.0 - 1.0;
+}
+
+// a noisy plane z = 0.1 x - 0.2 y + 0.3 holding `ratio` of the points, the rest clutter
+static Problem make_problem(int n, double ratio, int num_iterations, double probability, int ransac_n, uint64_t seed) {
+  Problem p;
+  for (int i = 0; i < n; ++i) {
+    const double x = uni(), y = uni();
+    const bool on = i % 100 < ratio * 100;
+    p.P.push_back(x);
+    p.P.push_back(y);
+    p.P.push_back(on ? 0.1 * x - 0.2 * y + 0.3 + 0.004 * uni() : uni());
+  }
+  teaser_hip_plane_params_default(&p.prm);
+  p.prm.distance_threshold = 0.01;
+  p.prm.num_iterations = num_iterations;
+  p.prm.probability = probability;
+  p.prm.ransac_n = ransac_n;
+  p.prm.seed = seed;
+  return p;
+}
+
+// One trial as the contract words it, with plain loops over blocks and groups.
+static int trial_of(const Problem& p, int64_t i, int32_t* smp, double* w, int32_t* count, double* E) {
+  const int n = (int)p.P.size() / 3;
+  PlDesc D;
+  memset(&D, 0, sizeof(D));
+  D.seed = p.prm.seed;
+  D.n = n;
+  D.ransac_n = p.prm.ransac_n;
+  const int flags = pl_model(D, p.P.data(), i, smp, w);
+  *count = 0;
+  *E = 0.0;
+  if (!flags) return 0;
+  for (int g0 = 0; g0 < n; g0 += PL_BLOCK * PL_GROUP) {
+    double gs = 0.0;
+    for (int b0 = g0; b0 < std::min(n, g0 + PL_BLOCK * PL_GROUP); b0 += PL_BLOCK) {
+      double bs = 0.0;
+      for (int q = b0; q < std::min(n, b0 + PL_BLOCK); ++q) {
+        const double dist = pl_dist(w, &p.P[3 * q]);
+        if (dist < p.prm.distance_threshold) {
+          ++*count;
+          bs += dist;
+        }
+      }
+      gs += bs;
+    }
+    *E += gs;
+  }
+  return flags;
+}
+
+// The contract's loop, written out: what the full call must return.
+static teaser_plane_result_c expected(const Problem& p, std::vector<int32_t>* inliers) {
+  teaser_plane_result_c r;
+  memset(&r, 0, sizeof(r));
+  r.best_trial = -1;
+  const int n = (int)p.P.size() / 3;
+  if (n < p.prm.ransac_n) return r;
+  double k = std::numeric_limits<double>::infinity(), best_rmse = 0.0, best_w[4] = {0, 0, 0, 0};
+  int32_t best_count = 0;
+  for (int64_t i = 0; i < p.prm.num_iterations; ++i) {
+    if ((double)r.valid_trials > k) break;
+    ++r.trials;
+    int32_t smp[PL_MAX_N], count;
+    double w[4], E;
+    if (!trial_of(p, i, smp, w, &count, &E)) continue;
+    const double rmse = count > 0 ? E / sqrt((double)count) : 0.0;
+    if (count > best_count || (count == best_count && rmse < best_rmse)) {
+      best_count = count;
+      best_rmse = rmse;
+      memcpy(best_w, w, sizeof(w));
+      r.best_trial = i;
+      if (count == n) {
+        k = 0.0;
+      } else {
+        const double q = log(1.0 - p.prm.probability) / log(1.0 - pow((double)count / n, (double)p.prm.ransac_n));
+        k = q < (double)p.prm.num_iterations ? q : (double)p.prm.num_iterations;
+      }
+    }
+    ++r.valid_trials;
+  }
+  if (r.best_trial < 0) return r;
+  r.n_inliers = best_count;
+  r.fitness = (double)best_count / n;
+  r.inlier_rmse = best_rmse;
+  for (int q = 0; q < n; ++q)
+    if (pl_dist(best_w, &p.P[3 * q]) < p.prm.distance_threshold) inliers->push_back(q);
+  return r;  // the refit is compared between runs, not restated here (the numpy restatement does that on the GPU)
+}
+
+struct Batch {
+  std::vector<Problem> ps;  // its own copy: the pointers below point into it
+  std::vector<const double*> pts;
+  std::vector<int32_t> n;
+  std::vector<teaser_plane_params_c> prm;
+  explicit Batch(const std::vector<Problem>& problems) : ps(problems) {
+    for (const Problem& p : ps) {
+      pts.push_back(p.P.empty() ? nullptr : p.P.data());
+      n.push_back((int32_t)p.P.size() / 3);
+      prm.push_back(p.prm);
+    }
+  }
+  int32_t run(teaser_hip_plane* h, teaser_plane_result_c* out, int32_t* const* inl, uint8_t* const* mask) {
+    g_clouds = pts;
+    const int32_t rc = teaser_hip_plane_segment_batch(h, (int32_t)pts.size(), pts.data(), n.data(), prm.data(), out, inl, mask);
+    g_clouds.clear();
+    return rc;
+  }
+};
+
+static void refusal(teaser_hip_plane* h, std::vector<Problem> ps, const char* needle, bool null_points = false,
+                    int32_t n1 = -2) {
+  Batch bt(ps);
+  if (null_points) bt.pts[1] = nullptr;
+  if (n1 != -2) bt.n[1] = n1;
+  std::vector<teaser_plane_result_c> out(ps.size());
+  memset(out.data(), 0x5a, sizeof(teaser_plane_result_c) * out.size());
+  const std::vector<teaser_plane_result_c> before = out;
+  const int models = g_models, finishes = g_finishes;
+  const int32_t rc = bt.run(h, out.data(), nullptr, nullptr);
+  const std::string msg = teaser_hip_plane_last_error(h);
+  if (rc != TEASER_HIP_ERR_BAD_ARG || msg.find(needle) == std::string::npos || msg.find("(problem 1)") == std::string::npos) {
+    ++g_bad;
+    printf("refusal '%s': status %d, message '%s'\n", needle, rc, msg.c_str());
+  }
+  EXPECT(g_models == models && g_finishes == finishes);  // found before any launch
+  EXPECT(memcmp(out.data(), before.data(), sizeof(teaser_plane_result_c) * out.size()) == 0);
+}
+
+int main() {
+  teaser_hip_plane* h = nullptr;
+  EXPECT(teaser_hip_plane_create(-1, &h) == TEASER_HIP_OK && h);
+  int64_t v = 0;
+  EXPECT(teaser_hip_plane_get_option(h, "chunk_trials", &v) == TEASER_HIP_OK && v == 256);
+  EXPECT(teaser_hip_plane_get_option(h, "partial_bytes", &v) == TEASER_HIP_OK && v == (64ll << 20));
+  EXPECT(teaser_hip_plane_set_option(h, "chunk_trials", 63) == TEASER_HIP_ERR_BAD_ARG);
+  EXPECT(teaser_hip_plane_set_option(h, "chunk_trials", 4097) == TEASER_HIP_ERR_BAD_ARG);
+  EXPECT(teaser_hip_plane_set_option(h, "partial_bytes", 65535) == TEASER_HIP_ERR_BAD_ARG);
+  EXPECT(teaser_hip_plane_set_option(h, "no_such", 64) == TEASER_HIP_ERR_BAD_ARG);
+  EXPECT(teaser_hip_plane_get_option(h, "no_such", &v) == TEASER_HIP_ERR_BAD_ARG && v == (64ll << 20));
+  teaser_plane_params_c dflt;
+  EXPECT(teaser_hip_plane_params_default(&dflt) == TEASER_HIP_OK && dflt.ransac_n == 3 && dflt.num_iterations == 100 &&
+         dflt.probability == 0.99999999 && dflt.distance_threshold == 0 && dflt.seed == 0);
+  {  // the wave plan: everything fits; a budget of one group; the floor of one group per problem
+    std::vector<PlDesc> d(2);
+    memset(d.data(), 0, sizeof(PlDesc) * 2);
+    d[0].n = 100000;  // 391 blocks, 7 groups
+    d[1].n = 300;     // 2 blocks, 1 group
+    EXPECT(pl_blocks(100000) == 391 && pl_groups(100000) == 7 && pl_blocks(0) == 0 && pl_groups(256 * 64 + 1) == 2);
+    EXPECT(pl_wave_groups(d, 256, 64ll << 20) == 7);
+    EXPECT(pl_wave_groups(d, 256, 5 * 256 * PL_GROUP_BYTES) == 4);
+    EXPECT(pl_wave_groups(d, 256, 65536) == 1);
+  }
+
+  std::vector<Problem> ps;
+  ps.push_back(make_problem(3000, 0.6, 5000, 0.99999999, 3, 11));  // stops inside the first chunk of 256, not of 64
+  ps.push_back(make_problem(257, 0.3, 5000, 0.999999, 3, 12));     // stops in a later round
+  ps.push_back(make_problem(700, 0.5, 300, 1.0, 5, 13));           // never stops early: a partial last chunk
+  ps.push_back(make_problem(2, 1.0, 100, 0.99, 3, 14));            // n < ransac_n
+  ps.push_back(make_problem(40, 0.5, 0, 0.99, 3, 15));             // num_iterations = 0
+  ps.push_back(make_problem(0, 0.5, 100, 0.99, 3, 16));            // empty
+  ps.push_back(make_problem(2 * 16384 + 1, 0.5, 100, 0.99999999, 4, 17));  // three groups
+  const size_t B = ps.size();
+  std::vector<teaser_plane_result_c> want(B);
+  std::vector<std::vector<int32_t>> want_inl(B);
+  for (size_t b = 0; b < B; ++b) want[b] = expected(ps[b], &want_inl[b]);
+  for (size_t b = 0; b < B; ++b)
+    printf("problem %zu: trials %lld valid %lld best %lld count %d\n", b, (long long)want[b].trials,
+           (long long)want[b].valid_trials, (long long)want[b].best_trial, want[b].n_inliers);
+  EXPECT(want[0].trials > 64 && want[0].trials < 256 && want[0].best_trial >= 0);
+  EXPECT(want[1].trials > 256 && want[1].trials < 5000 && want[1].trials % 64 != 0);
+  EXPECT(want[2].trials == 300 && want[3].best_trial == -1 && want[3].trials == 0 && want[4].trials == 0 && want[5].trials == 0);
+
+  std::vector<teaser_plane_result_c> first_out;
+  std::vector<std::vector<uint8_t>> first_mask;
+  const int64_t configs[4][2] = {{64, 64ll << 20}, {256, 64ll << 20}, {4096, 64ll << 20}, {64, 65536}};
+  for (const auto& cfg : configs) {
+    EXPECT(teaser_hip_plane_set_option(h, "chunk_trials", cfg[0]) == TEASER_HIP_OK);
+    EXPECT(teaser_hip_plane_set_option(h, "partial_bytes", cfg[1]) == TEASER_HIP_OK);
+    Batch bt(ps);
+    std::vector<teaser_plane_result_c> out(B);
+    std::vector<std::vector<int32_t>> inl(B);
+    std::vector<std::vector<uint8_t>> msk(B);
+    std::vector<int32_t*> ip;
+    std::vector<uint8_t*> mp;
+    for (size_t b = 0; b < B; ++b) {
+      inl[b].assign(std::max<size_t>(ps[b].P.size() / 3, 1), -7);
+      msk[b].assign(std::max<size_t>(ps[b].P.size() / 3, 1), 9);
+      ip.push_back(inl[b].data());
+      mp.push_back(msk[b].data());
+    }
+    g_chunk_sizes.clear();
+    g_trials_launched = 0;
+    g_max_W = 0;
+    const int scores = g_scores, models = g_models, finishes = g_finishes;
+    EXPECT(bt.run(h, out.data(), ip.data(), mp.data()) == TEASER_HIP_OK);
+    EXPECT(g_finishes == finishes + 1);
+    for (int c : g_chunk_sizes) EXPECT(c == cfg[0]);
+    int64_t reported = 0;
+    for (size_t b = 0; b < B; ++b) reported += out[b].trials;
+    EXPECT(g_trials_launched >= reported);
+    if (cfg[0] == 4096) EXPECT(g_trials_launched > reported);  // work past the stopping trials, dropped
+    if (cfg[1] == 65536) {  // one group per problem and wave: three waves per chunk for the longest cloud
+      EXPECT(g_max_W == 1 && g_scores - scores == 3 * (g_models - models));
+    } else {
+      EXPECT(g_max_W == 3 && g_scores - scores == g_models - models);
+    }
+    for (size_t b = 0; b < B; ++b) {
+      const teaser_plane_result_c& r = out[b];
+      const teaser_plane_result_c& w = want[b];
+      EXPECT(r.trials == w.trials && r.valid_trials == w.valid_trials && r.best_trial == w.best_trial);
+      EXPECT(r.n_inliers == w.n_inliers && r.fitness == w.fitness && r.inlier_rmse == w.inlier_rmse);
+      EXPECT((size_t)r.n_inliers == want_inl[b].size());
+      for (size_t q = 0; q < want_inl[b].size(); ++q) EXPECT(inl[b][q] == want_inl[b][q]);
+      size_t on = 0;
+      for (size_t q = 0; q < ps[b].P.size() / 3; ++q) on += msk[b][q] == 1;
+      EXPECT(on == want_inl[b].size());
+      if (w.best_trial >= 0) {  // the refit: a unit normal that keeps the inliers within the threshold's scale
+        const double len = sqrt(r.plane[0] * r.plane[0] + r.plane[1] * r.plane[1] + r.plane[2] * r.plane[2]);
+        EXPECT(fabs(len - 1.0) < 1e-12);
+        for (int32_t q : want_inl[b]) EXPECT(pl_dist(r.plane, &ps[b].P[3 * q]) < 3 * ps[b].prm.distance_threshold);
+      } else {
+        EXPECT(r.plane[0] == 0 && r.plane[1] == 0 && r.plane[2] == 0 && r.plane[3] == 0);
+      }
+    }
+    if (first_out.empty()) {
+      first_out = out;
+      first_mask = msk;
+    } else {  // no bit depends on the chunk or the budget
+      EXPECT(memcmp(first_out.data(), out.data(), sizeof(teaser_plane_result_c) * B) == 0);
+      EXPECT(first_mask == msk);
+    }
+    // each problem alone: the bits of the batch
+    for (size_t b = 0; b < B; ++b) {
+      teaser_plane_result_c one;
+      g_clouds.assign(1, bt.pts[b]);
+      EXPECT(teaser_hip_plane_segment(h, bt.pts[b], bt.n[b], &bt.prm[b], &one, nullptr, nullptr) == TEASER_HIP_OK);
+      g_clouds.clear();
+      EXPECT(memcmp(&one, &out[b], sizeof(one)) == 0);
+    }
+  }
+
+  // ---- the stage call: chunked by chunk_trials = 64, 150 trials from a first trial above 2^32 ----
+  {
+    Batch bt(ps);
+    const int cnt = 150;
+    const int64_t first = (1ll << 32) + 5;
+    std::vector<int32_t> smp(B * cnt * 8, 7), count(B * cnt, -1);
+    std::vector<uint8_t> fl(B * cnt, 9);
+    std::vector<double> pl(B * cnt * 4, 7.0), E(B * cnt, -1.0);
+    EXPECT(teaser_hip_plane_trials_batch(h, (int32_t)B, bt.pts.data(), bt.n.data(), bt.prm.data(), first, cnt, smp.data(),
+                                         fl.data(), pl.data(), count.data(), E.data()) == TEASER_HIP_OK);
+    for (size_t b = 0; b < B; ++b)
+      for (int q = 0; q < cnt; ++q) {
+        const size_t at = b * cnt + q;
+        int32_t s[PL_MAX_N], c = 0;
+        double w[4] = {0, 0, 0, 0}, e = 0.0;
+        int flags = 0;
+        const bool run = (int)ps[b].P.size() / 3 >= ps[b].prm.ransac_n;
+        if (run) flags = trial_of(ps[b], first + q, s, w, &c, &e);
+        EXPECT(fl[at] == flags && count[at] == c && E[at] == e);
+        EXPECT(memcmp(&pl[4 * at], w, sizeof(w)) == 0);
+        for (int k = 0; k < 8; ++k) EXPECT(smp[8 * at + k] == (run && k < ps[b].prm.ransac_n ? s[k] : -1));
+      }
+    EXPECT(teaser_hip_plane_trials_batch(h, (int32_t)B, bt.pts.data(), bt.n.data(), bt.prm.data(), -1, cnt, nullptr, nullptr,
+                                         nullptr, nullptr, nullptr) == TEASER_HIP_ERR_BAD_ARG);
+    EXPECT(teaser_hip_plane_trials_batch(h, (int32_t)B, bt.pts.data(), bt.n.data(), bt.prm.data(), 0, 65537, nullptr, nullptr,
+                                         nullptr, nullptr, nullptr) == TEASER_HIP_ERR_BAD_ARG);
+    EXPECT(teaser_hip_plane_trials_batch(h, (int32_t)B, bt.pts.data(), bt.n.data(), bt.prm.data(), 0, 0, nullptr, nullptr,
+                                         nullptr, nullptr, nullptr) == TEASER_HIP_OK);
+  }
+
+  // ---- refusals: each names its argument and problem 1; nothing is launched or written ----
+  {
+    std::vector<Problem> two = {make_problem(50, 0.5, 10, 0.99, 3, 1), make_problem(50, 0.5, 10, 0.99, 3, 2)};
+    auto with = [&](auto edit) {
+      std::vector<Problem> q = two;
+      edit(q[1]);
+      return q;
+    };
+    const double inf = std::numeric_limits<double>::infinity(), nan = std::numeric_limits<double>::quiet_NaN();
+    refusal(h, with([&](Problem& p) { p.P[7] = nan; }), "points has non-finite");
+    refusal(h, with([&](Problem& p) { p.P[8] = inf; }), "points has non-finite");
+    refusal(h, with([&](Problem& p) { p.prm.distance_threshold = 0; }), "distance_threshold");
+    refusal(h, with([&](Problem& p) { p.prm.distance_threshold = inf; }), "distance_threshold");
+    refusal(h, with([&](Problem& p) { p.prm.distance_threshold = nan; }), "distance_threshold");
+    refusal(h, with([&](Problem& p) { p.prm.ransac_n = 2; }), "ransac_n");
+    refusal(h, with([&](Problem& p) { p.prm.ransac_n = 9; }), "ransac_n");
+    refusal(h, with([&](Problem& p) { p.prm.probability = 0; }), "probability");
+    refusal(h, with([&](Problem& p) { p.prm.probability = 1.5; }), "probability");
+    refusal(h, with([&](Problem& p) { p.prm.probability = nan; }), "probability");
+    refusal(h, with([&](Problem& p) { p.prm.num_iterations = -1; }), "num_iterations");
+    refusal(h, two, "n must be >= 0", false, -1);
+    refusal(h, two, "points is NULL", true);
+    teaser_plane_result_c r;
+    EXPECT(teaser_hip_plane_segment_batch(h, -1, nullptr, nullptr, nullptr, &r, nullptr, nullptr) == TEASER_HIP_ERR_BAD_ARG);
+    EXPECT(teaser_hip_plane_segment_batch(h, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr) == TEASER_HIP_OK);
+    Batch bt(two);
+    EXPECT(teaser_hip_plane_segment_batch(h, 2, bt.pts.data(), bt.n.data(), bt.prm.data(), nullptr, nullptr, nullptr) ==
+           TEASER_HIP_ERR_BAD_ARG);
+    EXPECT(teaser_hip_plane_segment_batch(h, 2, bt.pts.data(), nullptr, bt.prm.data(), &r, nullptr, nullptr) == TEASER_HIP_ERR_BAD_ARG);
+    EXPECT(teaser_hip_plane_segment_batch(h, 2, bt.pts.data(), bt.n.data(), nullptr, &r, nullptr, nullptr) == TEASER_HIP_ERR_BAD_ARG);
+    std::vector<teaser_plane_result_c> out(2);
+    EXPECT(bt.run(h, out.data(), nullptr, nullptr) == TEASER_HIP_OK);  // the handle is usable after the refusals
+    EXPECT(std::string(teaser_hip_plane_last_error(h)).empty() && out[0].best_trial >= 0);
+  }
+  EXPECT(teaser_hip_plane_destroy(h) == TEASER_HIP_OK);
+  printf("mismatches %d\n", g_bad);
+  return g_bad ? 1 : 0;
+}
