@@ -6,7 +6,7 @@ nearest-neighbour correspondences -> TEASER++ registration -> optional DRS certi
 on the MI355X.  Usage:
 
     python examples/teaser_python_fpfh.py [src.ply dst.ply] [--voxel 0.05] [--certify] [--icp [--icp-iterations 100]]
-                                          [--remove-plane D [--plane-seed N]]
+                                          [--remove-plane D [--plane-seed N]] [--cluster EPS,MIN_POINTS]
                                           [--icp-plane [--icp-kernel tukey --icp-kernel-k K]]
                                           [--icp-plane-normals hybrid:R:K|knn:K]
                                           [--icp-gicp [--gicp-radius R --gicp-max-nn K]] [--batch K]
@@ -19,6 +19,11 @@ on the MI355X.  Usage:
 iterations, seeded by --plane-seed) from BOTH clouds after down-sampling and before FPFH, in one batched call, and
 prints each plane and the share of points removed.  A floor or a road holds a large part of a scan, its descriptors are
 all alike, and it lets ICP slide along it.  Off by default.
+
+--cluster EPS,MIN_POINTS splits each cloud into objects (Open3D's cluster_dbscan on the GPU, both clouds in one call)
+after --remove-plane and --remove-outliers and before FPFH, prints the number of clusters and of noise points per cloud,
+and keeps the most populous cluster of each (ties go to the smaller label): what is left of a scene once its floor is
+gone is a handful of objects, and the largest one is what gets registered.  Off by default.
 
 --ransac runs Open3D's registration_ransac_based_on_correspondence on the GPU on the SAME correspondences the TEASER++
 solver got (max_correspondence_distance = 1.5 voxels, the edge-length checker at 0.9 and the distance checker at 1.5
@@ -193,9 +198,13 @@ def main():
     ap.add_argument("--remove-plane", type=float, default=0.0, metavar="D",
                     help="drop the dominant plane (segment_plane, distance threshold D) from both clouds before FPFH")
     ap.add_argument("--plane-seed", type=int, default=1, metavar="N", help="seed of the plane trials (0: the clock)")
+    ap.add_argument("--cluster", default="", metavar="EPS,MIN_POINTS",
+                    help="keep the most populous DBSCAN cluster of each cloud (cluster_dbscan on the GPU, e.g. 0.1,10)")
     a = ap.parse_args()
     if a.remove_plane > 0 and a.batch > 0:
         ap.error("--remove-plane serves a single pair: it cannot be combined with --batch")
+    if a.cluster and a.batch > 0:
+        ap.error("--cluster serves a single pair: it cannot be combined with --batch")
     if a.iss and a.batch > 0:
         ap.error("--iss registers a single pair: it cannot be combined with --batch")
     if a.batch > 0:
@@ -238,6 +247,21 @@ def main():
               % (outliers[0], outliers[1], len(A) - len(ia), len(B) - len(ib), len(ia), len(ib),
                  1e3 * (time.perf_counter() - t)))
         A, B = A2.astype(A.dtype), B2.astype(B.dtype)
+    if a.cluster:  # what is left of the scene falls into objects: register the largest one
+        eps, min_points = a.cluster.split(",")
+        t = time.perf_counter()
+        labels, n_clusters = tp.cluster_dbscan_batch([A, B], float(eps), int(min_points))
+        t_cluster = time.perf_counter() - t
+        kept = []
+        for name, cloud, lab, c in (("source", A, labels[0], int(n_clusters[0])), ("target", B, labels[1], int(n_clusters[1]))):
+            print("DBSCAN clusters of the %s: %d clusters, %d of %d points are noise" % (name, c, int((lab < 0).sum()), len(cloud)))
+            if c == 0:
+                sys.exit("no cluster in the %s: nothing to register" % name)
+            largest = int(np.argmax(np.bincount(lab[lab >= 0], minlength=c)))  # argmax: the first of equal sizes
+            kept.append(cloud[lab == largest])
+            print("  kept cluster %d: %d points" % (largest, len(kept[-1])))
+        print("clustering of both clouds: %.1f ms (one call)" % (1e3 * t_cluster))
+        A, B = kept
     t0 = time.perf_counter()
     est = tp.FPFHEstimation()
     fa = est.computeFPFHFeatures(A, 2 * vox, 5 * vox)   # helpers.py:9-18: radii 2 and 5 voxels

@@ -921,6 +921,48 @@ TEASER_HIP_API int32_t teaser_hip_icp_iss_keypoints_batch(teaser_hip_icp* icp, i
                                                           uint8_t* const* keep_out, int32_t* n_keypoints_out,
                                                           double* const* saliency_out, int32_t* const* count_out,
                                                           double* radii_out);
+/* DBSCAN clustering (Open3D's PointCloud.cluster_dbscan), on the ICP handle: a batch of clouds (n x 3 doubles each)
+ * with one parameter record per cloud.  Open3D's loop was restated in closed form (tests/dbscan_reference.py), not run:
+ * its result is a function of the cloud alone, whatever order its unordered_set is popped in.  Per cloud of n points:
+ *   neighbours   j is a neighbour of i iff d2(i, j) < eps eps, d2 = ((dx dx + dy dy) + dz dz), dx = P[i].x - P[j].x, in
+ *                FP64 without contraction, as everywhere on this handle (nanoflann's strict radius rule).  d2 is
+ *                symmetric bit for bit, and a point is its own neighbour when eps eps > 0.
+ *                count[i] = the number of neighbours of i, itself included.  NO cap.
+ *   core         i is a core point iff count[i] >= min_points.
+ *   components   core points that are neighbours belong to one cluster; clusters are the connected components of that
+ *                relation.  root[i] = the smallest point index among the core points of i's component; -1 for a point
+ *                that is not core.
+ *   numbering    clusters are numbered 0 .. c - 1 in ascending order of their root: the order in which Open3D's outer
+ *                loop opens them (a cluster is opened at a core point and labelled whole before the loop moves on).
+ *   border/noise a point that is not core gets the smallest label among the clusters of its core neighbours (the first
+ *                cluster whose flood reaches it in Open3D, where -1 is overwritten once and never again), -1 without one.
+ *   no radius    a cloud whose eps eps is not > 0: no neighbours; every count 0, every label and root -1, c = 0.  No
+ *                grid is built for it and nothing divides by it.
+ * Departures from Open3D: min_points >= 1 (its size_t accepts 0, which makes every point core).
+ * labels_out[b]: n int32; n_clusters_out[b]: int32 (c); count_out (NULL, or per cloud NULL or) n int32; root_out (NULL,
+ * or per cloud NULL or) n int32, the stage output of "components".  Empty clouds are legal.  Every output is an integer
+ * and a function of the cloud and its record only: the same bits alone, inside any batch, in any batch position, run
+ * after run, although the components are found by concurrent lock-free hooks (the smallest index of a component is its
+ * root whatever the interleaving).  One upload, one copy back; the launches do not depend on the data.
+ * TEASER_HIP_ERR_BAD_ARG (argument and cloud named): non-finite points; an eps that is negative or whose value or square
+ * is not finite; min_points < 1; reserved != 0; NULL where it is required; total >= INT32_MAX points; and an eps so small
+ * against the cloud's extent that the cell keys of the call (grid id, c_x, c_y, c_z, each with the bits its largest value
+ * needs; the grid is that of ISS keypoints with h from eps) exceed 63 bits.  The handle stays usable after a refusal. */
+typedef struct teaser_icp_dbscan_params_c {
+  double eps;         /* >= 0, finite like its square */
+  int32_t min_points; /* >= 1 */
+  int32_t reserved;   /* 0 */
+} teaser_icp_dbscan_params_c;
+#ifdef __cplusplus
+static_assert(sizeof(teaser_icp_dbscan_params_c) == 16, "teaser_icp_dbscan_params_c is 16 bytes");
+#else
+_Static_assert(sizeof(teaser_icp_dbscan_params_c) == 16, "teaser_icp_dbscan_params_c is 16 bytes");
+#endif
+TEASER_HIP_API int32_t teaser_hip_icp_cluster_dbscan_batch(teaser_hip_icp* icp, int32_t batch,
+                                                           const double* const* points, const int32_t* n,
+                                                           const teaser_icp_dbscan_params_c* params,
+                                                           int32_t* const* labels_out, int32_t* n_clusters_out,
+                                                           int32_t* const* count_out, int32_t* const* root_out);
 /* Options of an ICP handle (none changes a result).  "knn_ring_cap" (0 .. 16, default 4): the number of rings self
  * k-NN and statistical removal search on the grid before a query goes to the whole-cloud scan; 0 sends every query
  * there.  "knn_fallbacks" (read-only): how many queries of the handle's last self k-NN or statistical-removal call the

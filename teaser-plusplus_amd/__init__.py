@@ -138,6 +138,7 @@ EXPORTED_SYMBOLS = [
     "teaser_hip_icp_self_knn_batch", "teaser_hip_icp_remove_statistical_outliers_batch",
     "teaser_hip_icp_remove_radius_outliers_batch", "teaser_hip_icp_set_option", "teaser_hip_icp_get_option",
     "teaser_hip_icp_iss_params_default", "teaser_hip_icp_iss_keypoints_batch",
+    "teaser_hip_icp_cluster_dbscan_batch",
     "teaser_hip_icp_information_batch", "teaser_hip_icp_information",
     "teaser_hip_icp_color_default", "teaser_hip_icp_batch_color", "teaser_hip_icp_solve_color",
     "teaser_hip_icp_color_gradients_batch",
@@ -249,6 +250,8 @@ def lib():
     _outlier.declare(L)
     from . import keypoints as _keypoints
     _keypoints.declare(L)
+    from . import cluster as _cluster
+    _cluster.declare(L)
     from . import voxel as _voxel
     _voxel.declare(L)
     from . import features as _features
@@ -1116,6 +1119,7 @@ from .voxel import voxel_down_sample, voxel_down_sample_batch  # noqa: E402
 from .outlier import (remove_radius_outlier, remove_radius_outlier_batch, remove_statistical_outlier,  # noqa: E402
                       remove_statistical_outlier_batch, self_knn, self_knn_batch, get_icp_option, set_icp_option)
 from .keypoints import compute_iss_keypoints, compute_iss_keypoints_batch  # noqa: E402
+from .cluster import cluster_dbscan, cluster_dbscan_batch  # noqa: E402
 from .features import (compute_fpfh_batch, correspondences_batch, match_features_batch,  # noqa: E402
                        knn_features, knn_features_batch, match_features_knn, match_features_knn_batch,
                        correspondences_knn, correspondences_knn_batch, tuple_test_batch)
@@ -1152,7 +1156,7 @@ __all__ = ["batched", "FPFHEstimation", "Matcher", "MultiDeviceSolver", "RobustR
            "estimate_color_gradients_batch",
            "remove_statistical_outlier", "remove_statistical_outlier_batch", "remove_radius_outlier",
            "remove_radius_outlier_batch", "self_knn", "self_knn_batch", "get_icp_option", "set_icp_option",
-           "compute_iss_keypoints", "compute_iss_keypoints_batch",
+           "compute_iss_keypoints", "compute_iss_keypoints_batch", "cluster_dbscan", "cluster_dbscan_batch",
            "PoseGraph", "PoseGraphNode", "PoseGraphEdge", "GlobalOptimizationOption",
            "GlobalOptimizationConvergenceCriteria", "GlobalOptimizationLevenbergMarquardt",
            "GlobalOptimizationGaussNewton", "PoseGraphOptimizationResult", "global_optimization",

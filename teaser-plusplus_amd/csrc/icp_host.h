@@ -1,6 +1,6 @@
 // icp_host.h -- what the host files of the ICP handle share (icp.hip: the iteration loop and covariance estimation;
 // icp_outlier.hip: self k-NN, outlier removal and the options; icp_normals.hip: normal estimation and the
-// self-estimating point-to-plane entry; icp_keypoints.hip: ISS keypoints; icp_color.hip: Colored ICP): the handle and its buffers, and the scaffold
+// self-estimating point-to-plane entry; icp_keypoints.hip: ISS keypoints; icp_cluster.hip: DBSCAN clustering; icp_color.hip: Colored ICP): the handle and its buffers, and the scaffold
 // of a cloud call -- the entry checks (begin_cloud_call), the per-call index under construction (IcpIndex,
 // add_problem), the sizes of the index buffers by name (index_bytes, ensure_buffers), the packing and the uploads
 // (upload_points, upload_inputs), the index build (launch_index), the one copy back (copy_back, read_fallbacks) and
@@ -25,12 +25,14 @@ namespace thip {
 // B_N*: the descriptors, records and block maps of the normal estimation that precedes the iterations of
 // teaser_hip_icp_batch_auto (its other buffers are the ICP's own).  B_K*: the sorted cell index of ISS keypoint
 // detection (icp_keypoints.hip): descriptors, block map, keys and entries before and after the sort, the sorted points
-// and the sort's scratch.  B_COLOR_*: Colored ICP (icp_color.hip): the per-problem IcpColorDesc records, one intensity per
+// and the sort's scratch; DBSCAN clustering (icp_cluster.hip) builds the same index with one grid per cloud, shares
+// B_KTEMP between the sort and the scan, and adds B_DPARENT (the union-find), B_DFLAG ("is a root", total + 1 entries)
+// and B_DSCAN (its exclusive scan).  B_COLOR_*: Colored ICP (icp_color.hip): the per-problem IcpColorDesc records, one intensity per
 // source point, and per target point the {gradient, intensity} record; its gradient pass keeps its descriptors, records
 // and block maps in B_N* (a coloured call estimates no normals)
 enum { B_DESC, B_STATE, B_BLK, B_TBLK, B_X, B_Q, B_TBUCKET, B_BCOUNT, B_BSTART, B_CURSOR, B_QS, B_QJ, B_MATCH,
        B_PARTIALS, B_LIVE, B_NORMALS, B_COV_S, B_COV_T, B_NDESC, B_NKNN, B_NREC, B_NBLK, B_NTBLK, B_KDESC, B_KBLK,
-       B_KKEY, B_KIOTA, B_KSKEY, B_KSIDX, B_KSPTS, B_KTEMP, B_COLOR_DESC, B_COLOR_S, B_COLOR_T, B_COUNT };
+       B_KKEY, B_KIOTA, B_KSKEY, B_KSIDX, B_KSPTS, B_KTEMP, B_DPARENT, B_DFLAG, B_DSCAN, B_COLOR_DESC, B_COLOR_S, B_COLOR_T, B_COUNT };
 
 }  // namespace thip
 
@@ -78,6 +80,33 @@ inline void set_grid(IcpDesc& d, const double* q, double r) {
     d.cmax[c] = icp_cell(hi[c], lo[c], d.inv_h);
   }
   d.tb_mask = next_pow2(2 * (int64_t)d.n_t) - 1;
+}
+
+// What the calls on the sorted cell index share (icp_keypoints.hip, icp_cluster.hip; the grid type is IssGrid of
+// icp_iss_device.h).  The bits a value needs:
+inline int key_bits_for(uint64_t v) {
+  int b = 0;
+  while (b < 64 && (v >> b) != 0) ++b;
+  return b;
+}
+
+// A radius as given: not negative, finite like its square.
+inline bool radius_ok(double r) { return std::isfinite(r) && r >= 0 && std::isfinite(r * r); }
+
+// The grid of radius r over the cloud q (n > 0 points), and the bits its three cell coordinates need.
+template <class Grid>
+void make_sorted_grid(Grid& g, const double* q, int32_t n, double r, int (&bits)[3]) {
+  IcpDesc d;
+  memset(&d, 0, sizeof(d));
+  d.n_t = n;
+  set_grid(d, q, r);
+  g.inv_h = d.inv_h;
+  g.r2 = r * r;
+  for (int c = 0; c < 3; ++c) {
+    g.origin[c] = d.origin[c];
+    g.cmax[c] = d.cmax[c];
+    bits[c] = key_bits_for((uint64_t)d.cmax[c]);
+  }
 }
 
 // The target index of one call under construction: per problem the descriptor with its offsets and hash grid, the

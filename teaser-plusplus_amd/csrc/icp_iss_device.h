@@ -94,30 +94,44 @@ __device__ __forceinline__ bool iss_locate(const IssDesc* __restrict__ descs, co
   return k < descs[p].n;
 }
 
-// keys: both entries of point k of its cloud, and the identity permutation
-__device__ __forceinline__ void iss_keys_body(const IssDesc* __restrict__ descs, const int32_t* __restrict__ blk_prob,
-                                              const double* __restrict__ pts, int64_t total,
-                                              uint64_t* __restrict__ key, int32_t* __restrict__ iota) {
+// keys: the entries of point k of its cloud in its first `grids` grids (2: the grid of r_s and the grid of r_n; 1: the
+// grid gs alone, as DBSCAN clustering keeps one grid per cloud -- icp_dbscan_device.h), and the identity permutation
+__device__ __forceinline__ void iss_keys_grids_body(const IssDesc* __restrict__ descs,
+                                                    const int32_t* __restrict__ blk_prob,
+                                                    const double* __restrict__ pts, int64_t total, int grids,
+                                                    uint64_t* __restrict__ key, int32_t* __restrict__ iota) {
   int p;
   int64_t k;
   if (!iss_locate(descs, blk_prob, p, k)) return;
   const IssDesc& d = descs[p];
   const int64_t i = d.off + k;
   key[i] = iss_point_key(d.gs, pts + 3 * i);
-  key[total + i] = iss_point_key(d.gn, pts + 3 * i);
   iota[i] = (int32_t)i;
+  if (grids < 2) return;
+  key[total + i] = iss_point_key(d.gn, pts + 3 * i);
   iota[total + i] = (int32_t)(total + i);
 }
 
-// the points in sorted order: entry e of 2 total
-__device__ __forceinline__ void iss_gather_body(int64_t total, const double* __restrict__ pts,
-                                                const int32_t* __restrict__ sidx, double* __restrict__ spts) {
+__device__ __forceinline__ void iss_keys_body(const IssDesc* __restrict__ descs, const int32_t* __restrict__ blk_prob,
+                                              const double* __restrict__ pts, int64_t total,
+                                              uint64_t* __restrict__ key, int32_t* __restrict__ iota) {
+  iss_keys_grids_body(descs, blk_prob, pts, total, 2, key, iota);
+}
+
+// the points in sorted order: entry e of `entries` (2 total for ISS, total for one grid per cloud)
+__device__ __forceinline__ void iss_gather_entries_body(int64_t total, int64_t entries, const double* __restrict__ pts,
+                                                        const int32_t* __restrict__ sidx, double* __restrict__ spts) {
   const int64_t e = (int64_t)blockIdx.x * kIssBlock + threadIdx.x;
-  if (e >= 2 * total) return;
+  if (e >= entries) return;
   const int64_t s = sidx[e], i = s >= total ? s - total : s;
   spts[3 * e] = pts[3 * i];
   spts[3 * e + 1] = pts[3 * i + 1];
   spts[3 * e + 2] = pts[3 * i + 2];
+}
+
+__device__ __forceinline__ void iss_gather_body(int64_t total, const double* __restrict__ pts,
+                                                const int32_t* __restrict__ sidx, double* __restrict__ spts) {
+  iss_gather_entries_body(total, 2 * total, pts, sidx, spts);
 }
 
 // saliency: the query at sorted position k of the grid of r_s.  m, S1 and S2 live in registers; every array below is
@@ -229,6 +243,11 @@ hipError_t launch_iss_sort(hipStream_t s, void* d_temp, size_t temp_bytes, int64
 void launch_iss_keys(hipStream_t s, const IssDesc* d_desc, const int32_t* d_blk_prob, int n_blk, const double* d_pts,
                      int64_t total, uint64_t* d_key, int32_t* d_iota);
 void launch_iss_gather(hipStream_t s, int64_t total, const double* d_pts, const int32_t* d_sidx, double* d_spts);
+// The same two kernels for a call with `grids` (1 or 2) grids per cloud, grids * total entries
+void launch_iss_keys_grids(hipStream_t s, const IssDesc* d_desc, const int32_t* d_blk_prob, int n_blk,
+                           const double* d_pts, int64_t total, int grids, uint64_t* d_key, int32_t* d_iota);
+void launch_iss_gather_entries(hipStream_t s, int64_t total, int64_t entries, const double* d_pts,
+                               const int32_t* d_sidx, double* d_spts);
 // sal[i] and count[2 i] = m of every point of the active clouds (the rest is left as the caller cleared it)
 void launch_iss_saliency(hipStream_t s, const IssDesc* d_desc, const int32_t* d_blk_prob, int n_blk,
                          const uint64_t* d_skey, const int32_t* d_sidx, const double* d_spts, double* d_sal,

@@ -26,16 +26,7 @@ static_assert(sizeof(teaser_icp_iss_params_c) == 40, "the header states the reco
 
 namespace {
 
-int bits_for(uint64_t v) {
-  int b = 0;
-  while (b < 64 && (v >> b) != 0) ++b;
-  return b;
-}
-
 bool auto_radii(const teaser_icp_iss_params_c& p) { return p.salient_radius == 0 || p.non_max_radius == 0; }
-
-// A radius as given: not negative, finite like its square.
-bool radius_ok(double r) { return std::isfinite(r) && r >= 0 && std::isfinite(r * r); }
 
 // Stage A: res[b] of the clouds with want[b] (n[b] >= 2), through self k-NN with k = 2 over those clouds alone.
 int32_t resolutions(teaser_hip_icp* h, int32_t batch, const double* const* points, const int32_t* n,
@@ -59,21 +50,6 @@ int32_t resolutions(teaser_hip_icp* h, int32_t batch, const double* const* point
   for (int b = 0; b < batch; ++b)
     if (want[(size_t)b]) res[(size_t)b] = h->back[(size_t)b];
   return TEASER_HIP_OK;
-}
-
-// The grid of radius r over the cloud q (n > 0 points), and the bits its three cell coordinates need.
-void make_grid(IssGrid& g, const double* q, int32_t n, double r, int (&bits)[3]) {
-  IcpDesc d;
-  memset(&d, 0, sizeof(d));
-  d.n_t = n;
-  set_grid(d, q, r);
-  g.inv_h = d.inv_h;
-  g.r2 = r * r;
-  for (int c = 0; c < 3; ++c) {
-    g.origin[c] = d.origin[c];
-    g.cmax[c] = d.cmax[c];
-    bits[c] = bits_for((uint64_t)d.cmax[c]);
-  }
 }
 
 }  // namespace
@@ -156,8 +132,8 @@ int32_t teaser_hip_icp_iss_keypoints_batch(teaser_hip_icp* h, int32_t batch, con
     d.active = n[b] > 0 && r_s * r_s > 0 && r_n * r_n > 0;
     if (d.active) {
       int bs[3], bn[3];
-      make_grid(d.gs, points[b], n[b], r_s, bs);
-      make_grid(d.gn, points[b], n[b], r_n, bn);
+      make_sorted_grid(d.gs, points[b], n[b], r_s, bs);
+      make_sorted_grid(d.gn, points[b], n[b], r_n, bn);
       for (int c = 0; c < 3; ++c) sbits[3 * (size_t)b + c] = bs[c], nbits[3 * (size_t)b + c] = bn[c];
       key_bits = std::max(key_bits, std::max(bs[0] + bs[1] + bs[2], bn[0] + bn[1] + bn[2]));
       any_active = true;
@@ -165,7 +141,7 @@ int32_t teaser_hip_icp_iss_keypoints_batch(teaser_hip_icp* h, int32_t batch, con
     for (int k = 0; k < (n[b] + kIssBlock - 1) / kIssBlock; ++k) blk.push_back(b);
     off += n[b];
   }
-  const int id_bits = bits_for((uint64_t)(2 * (int64_t)batch - 1));
+  const int id_bits = key_bits_for((uint64_t)(2 * (int64_t)batch - 1));
   const int bits = key_bits + id_bits;
   if (bits > 63)
     for (int b = 0; b < batch; ++b) {  // the cloud and the radius whose grid is the widest

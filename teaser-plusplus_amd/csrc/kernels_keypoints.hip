@@ -22,14 +22,16 @@ namespace {
 __global__ __launch_bounds__(kIssBlock) void iss_keys_kernel(const IssDesc* __restrict__ descs,
                                                              const int32_t* __restrict__ blk_prob,
                                                              const double* __restrict__ pts, int64_t total,
-                                                             uint64_t* __restrict__ key, int32_t* __restrict__ iota) {
-  iss_keys_body(descs, blk_prob, pts, total, key, iota);
+                                                             int grids, uint64_t* __restrict__ key,
+                                                             int32_t* __restrict__ iota) {
+  iss_keys_grids_body(descs, blk_prob, pts, total, grids, key, iota);
 }
 
-__global__ __launch_bounds__(kIssBlock) void iss_gather_kernel(int64_t total, const double* __restrict__ pts,
+__global__ __launch_bounds__(kIssBlock) void iss_gather_kernel(int64_t total, int64_t entries,
+                                                               const double* __restrict__ pts,
                                                                const int32_t* __restrict__ sidx,
                                                                double* __restrict__ spts) {
-  iss_gather_body(total, pts, sidx, spts);
+  iss_gather_entries_body(total, entries, pts, sidx, spts);
 }
 
 __global__ __launch_bounds__(kIssBlock) void iss_saliency_kernel(const IssDesc* __restrict__ descs,
@@ -84,17 +86,27 @@ hipError_t launch_iss_sort(hipStream_t s, void* d_temp, size_t temp_bytes, int64
   return rocprim::radix_sort_pairs(d_temp, tb, d_key, d_skey, d_iota, d_sidx, (size_t)entries, 0, (unsigned)bits, s);
 }
 
+void launch_iss_keys_grids(hipStream_t s, const IssDesc* d_desc, const int32_t* d_blk_prob, int n_blk,
+                           const double* d_pts, int64_t total, int grids, uint64_t* d_key, int32_t* d_iota) {
+  if (n_blk <= 0) return;
+  hipLaunchKernelGGL(iss_keys_kernel, dim3(n_blk), dim3(kIssBlock), 0, s, d_desc, d_blk_prob, d_pts, total, grids,
+                     d_key, d_iota);
+}
+
 void launch_iss_keys(hipStream_t s, const IssDesc* d_desc, const int32_t* d_blk_prob, int n_blk, const double* d_pts,
                      int64_t total, uint64_t* d_key, int32_t* d_iota) {
-  if (n_blk <= 0) return;
-  hipLaunchKernelGGL(iss_keys_kernel, dim3(n_blk), dim3(kIssBlock), 0, s, d_desc, d_blk_prob, d_pts, total, d_key,
-                     d_iota);
+  launch_iss_keys_grids(s, d_desc, d_blk_prob, n_blk, d_pts, total, 2, d_key, d_iota);
+}
+
+void launch_iss_gather_entries(hipStream_t s, int64_t total, int64_t entries, const double* d_pts,
+                               const int32_t* d_sidx, double* d_spts) {
+  if (entries <= 0) return;
+  hipLaunchKernelGGL(iss_gather_kernel, dim3((unsigned)((entries + kIssBlock - 1) / kIssBlock)), dim3(kIssBlock), 0, s,
+                     total, entries, d_pts, d_sidx, d_spts);
 }
 
 void launch_iss_gather(hipStream_t s, int64_t total, const double* d_pts, const int32_t* d_sidx, double* d_spts) {
-  if (total <= 0) return;
-  hipLaunchKernelGGL(iss_gather_kernel, dim3((unsigned)((2 * total + kIssBlock - 1) / kIssBlock)), dim3(kIssBlock), 0,
-                     s, total, d_pts, d_sidx, d_spts);
+  launch_iss_gather_entries(s, total, 2 * total, d_pts, d_sidx, d_spts);
 }
 
 void launch_iss_saliency(hipStream_t s, const IssDesc* d_desc, const int32_t* d_blk_prob, int n_blk,
