@@ -11,7 +11,7 @@ on the MI355X.  Usage:
                                           [--icp-plane-normals hybrid:R:K|knn:K]
                                           [--icp-gicp [--gicp-radius R --gicp-max-nn K]] [--batch K]
                                           [--knn K [--no-mutual]] [--tuple-scale S [--tuple-seed N]]
-                                          [--iss [--iss-radii RS,RN]]
+                                          [--iss [--iss-radii RS,RN]] [--fps K]
                                           [--ransac [--ransac-iterations N --ransac-seed N]]
                                           [--fgr [--fgr-tuple-test --fgr-seed N]]
 
@@ -39,6 +39,13 @@ other options at their defaults) and prints its pose, fitness and RMSE beside TE
 them: FPFH is still computed on the whole clouds (its neighbourhoods need every point), the descriptor rows at the
 keypoints go to the matcher, and the returned pairs are mapped back to cloud indices.  --iss-radii RS,RN gives the
 salient and the suppression radius; the default takes 6 and 4 times each cloud's resolution, like Open3D.
+
+--fps K matches only K well-spread points of each down-sampled cloud (Open3D's farthest_point_down_sample on the GPU,
+both clouds in one call), applied where --iss is applied: the descriptors are computed on the whole cloud and kept at the
+K samples, and the returned pairs are mapped back to cloud indices.  A cloud of fewer than K points keeps all of them.
+Unlike a voxel size or the ISS radii, K fixes the number of keypoints, and with it the solver's cost, in advance; with
+--batch every pair gets exactly min(K, n) keypoints per cloud, all clouds sampled in one call.  --fps and --iss together
+are an error.
 
 --knn K matches every point with its K nearest descriptors (helpers.py:19-43, find_knn_cpu(feat0, feat1, knn=K)) in
 place of the single mutual nearest neighbour: more putative correspondences for the solver, on the GPU as well.  Only
@@ -97,7 +104,7 @@ def parse_outliers(text):
     return int(nb), float(ratio)
 
 
-def run_batch(A, B, vox, K, icp_iterations, knn=0, mutual=True, tuple_scale=0.0, tuple_seed=0, outliers=None):
+def run_batch(A, B, vox, K, icp_iterations, knn=0, mutual=True, tuple_scale=0.0, tuple_seed=0, outliers=None, fps=0):
     """K perturbed copies of the pair (A, B) through the batched stages, one call per stage."""
     rng = np.random.default_rng(555)
     srcs, dsts = [], []
@@ -124,7 +131,19 @@ def run_batch(A, B, vox, K, icp_iterations, knn=0, mutual=True, tuple_scale=0.0,
         t_clean = time.perf_counter() - t1
         t1 = time.perf_counter()
         sp, dp = down[:K], down[K:]
-        if knn:
+        if fps:  # descriptors on the whole clouds, matching at min(fps, n) well-spread samples of each
+            feats = tp.compute_fpfh_batch(down, 2 * vox, 5 * vox)
+            keys = tp.farthest_point_down_sample_batch(down, [min(fps, len(c)) for c in down])
+            fk = [f[k] for f, k in zip(feats, keys)]
+            if knn:
+                corr = tp.match_features_knn_batch(fk[:K], fk[K:], knn, mutual)
+            else:
+                corr = tp.match_features_batch(fk[:K], fk[K:])
+            if tuple_scale:
+                corr = tp.tuple_test_batch([c[k] for c, k in zip(sp, keys[:K])], [c[k] for c, k in zip(dp, keys[K:])],
+                                           corr, tuple_scale, tuple_seed)
+            corr = [np.stack([keys[k][c[:, 0]], keys[K + k][c[:, 1]]], axis=1) for k, c in enumerate(corr)]
+        elif knn:
             corr = tp.correspondences_knn_batch(sp, dp, 2 * vox, 5 * vox, knn, mutual, tuple_scale=tuple_scale,
                                                 tuple_seed=tuple_seed)
         else:
@@ -145,6 +164,9 @@ def run_batch(A, B, vox, K, icp_iterations, knn=0, mutual=True, tuple_scale=0.0,
         t4 = time.perf_counter()
     print("%d pairs: %d .. %d points after down-sampling, %d .. %d correspondences"
           % (K, min(map(len, down)), max(map(len, down)), min(map(len, corr)), max(map(len, corr))))
+    if fps:
+        print("farthest-point samples: %d .. %d per cloud (--fps %d, one call for all %d clouds)"
+              % (min(map(len, keys)), max(map(len, keys)), fps, 2 * K))
     if outliers:
         print("statistical outlier removal (nb_neighbors %d, std_ratio %g): %d points went from %d clouds, %.1f ms"
               % (outliers[0], outliers[1], n_down - sum(map(len, down)), 2 * K, 1e3 * t_clean))
@@ -187,6 +209,8 @@ def main():
                     help="match only the ISS keypoints of both clouds (detected on the GPU); single pair only")
     ap.add_argument("--iss-radii", default="", metavar="RS,RN",
                     help="with --iss: salient and non-maximum-suppression radius (default: 6 and 4 resolutions)")
+    ap.add_argument("--fps", type=int, default=0, metavar="K",
+                    help="match only K farthest-point samples of each cloud (selected on the GPU)")
     ap.add_argument("--ransac", action="store_true",
                     help="also run RANSAC on the same correspondences (on the GPU) and print it beside TEASER++")
     ap.add_argument("--ransac-iterations", type=int, default=100000, metavar="N")
@@ -205,6 +229,10 @@ def main():
         ap.error("--remove-plane serves a single pair: it cannot be combined with --batch")
     if a.cluster and a.batch > 0:
         ap.error("--cluster serves a single pair: it cannot be combined with --batch")
+    if a.fps < 0:
+        ap.error("--fps takes a number of samples")
+    if a.fps and a.iss:
+        ap.error("--fps and --iss both choose the keypoints: give one of them")
     if a.iss and a.batch > 0:
         ap.error("--iss registers a single pair: it cannot be combined with --batch")
     if a.batch > 0:
@@ -214,7 +242,7 @@ def main():
             c5 = np.load(os.path.join(ROOT, "tests", "golden", "config5_clouds.npz"))
             A, B, a.voxel = c5["cloud_bin_0"].astype(np.float64), c5["cloud_bin_4"].astype(np.float64), float(c5["voxel_size"])
         return run_batch(A, B, a.voxel, a.batch, a.icp_iterations, a.knn, not a.no_mutual, a.tuple_scale, a.tuple_seed,
-                         parse_outliers(a.remove_outliers))
+                         parse_outliers(a.remove_outliers), a.fps)
     t_ds = None
     if len(a.clouds) == 2:
         raw = [read_ply_xyz(c).astype(np.float64) for c in a.clouds]
@@ -277,6 +305,14 @@ def main():
         if min(map(len, keys)) < 3:
             sys.exit("fewer than 3 keypoints in a cloud: nothing to match")
         A, B, fa, fb = A[keys[0]], B[keys[1]], fa[keys[0]], fb[keys[1]]
+    if a.fps:  # the same, at a number of well-spread points fixed in advance
+        t = time.perf_counter()
+        keys = tp.farthest_point_down_sample_batch([A, B], [min(a.fps, len(A)), min(a.fps, len(B))])
+        print("farthest-point samples: %d of %d / %d of %d points (%.1f ms)"
+              % (len(keys[0]), len(A), len(keys[1]), len(B), 1e3 * (time.perf_counter() - t)))
+        if min(map(len, keys)) < 3:
+            sys.exit("fewer than 3 samples in a cloud: nothing to match")
+        A, B, fa, fb = A[keys[0]], B[keys[1]], fa[keys[0]], fb[keys[1]]
     if a.knn:
         corr = tp.match_features_knn(fa, fb, a.knn, not a.no_mutual)   # helpers.py:19-43
         if a.tuple_scale:
@@ -285,7 +321,7 @@ def main():
     else:
         corr = tp.Matcher().calculateCorrespondences(A, B, fa, fb, False, True, bool(a.tuple_scale), a.tuple_scale,
                                                      a.tuple_seed)   # helpers.py:27-43
-    if a.iss:
+    if a.iss or a.fps:
         corr = [(int(keys[0][i]), int(keys[1][j])) for i, j in corr]
         A, B = full
     t1 = time.perf_counter()

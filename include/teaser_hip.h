@@ -963,10 +963,53 @@ TEASER_HIP_API int32_t teaser_hip_icp_cluster_dbscan_batch(teaser_hip_icp* icp, 
                                                            const teaser_icp_dbscan_params_c* params,
                                                            int32_t* const* labels_out, int32_t* n_clusters_out,
                                                            int32_t* const* count_out, int32_t* const* root_out);
+/* Farthest-point down-sampling (Open3D's PointCloud.farthest_point_down_sample(num_samples, start_index)), on the ICP
+ * handle: a batch of clouds (n x 3 doubles each) with one parameter record per cloud.  Open3D's loop was restated
+ * (tests/fps_reference.py), not run.  Per cloud of n points P, K = num_samples, s = start_index:
+ *   d[j] = +inf for all j;  cur = s
+ *   for k = 0 .. K - 1:
+ *     index[k]    = cur
+ *     sel_dist[k] = d[cur]           before the update: +inf for k = 0, else the squared distance of sample k to the
+ *                                    nearest earlier sample
+ *     d[j] = min(d[j], d2(j, cur))   for all j; d2 = ((dx dx + dy dy) + dz dz), dx = P[j].x - P[cur].x, in FP64 without
+ *                                    contraction, as everywhere on this handle
+ *     m = the SMALLEST j among those with the largest d[j]
+ *     if d[m] > 0: cur = m           else cur stays (Open3D's max_dist = 0 and its strict >): a cloud with fewer than K
+ *                                    distinct positions repeats its last sample
+ * index_out[b]: K int32 (required when K > 0); sel_dist_out (NULL, or per cloud NULL or) K doubles; final_dist_out (NULL,
+ * or per cloud NULL or) n doubles: d after the last round, the squared distance of every point to its nearest sample.
+ * K = 0 is legal, also for n = 0: nothing is written for the cloud and start_index is not looked at.  K = n is legal and
+ * runs the loop as stated (Open3D's shortcut for it is the Python wrapper's business).  A d2 that overflows to +inf is
+ * no error, and ties at +inf go to the smallest index like every tie.
+ * min, and max under the total order on (distance, index), are exact, so the outputs are a function of (P, K, s) alone:
+ * the same bits alone, inside any batch, in any batch position, run after run, and on both routes.  A cloud of at most
+ * "fps_resident_max" points (an option of the handle, below) is served by one workgroup that keeps it in registers for
+ * the whole loop, all such clouds of a call in ONE launch; the others by one launch per round, max K launches for all of
+ * them.  One upload, one copy back, one synchronisation; the launch count depends on (n, K, the option) only.
+ * TEASER_HIP_ERR_BAD_ARG (argument and cloud named): non-finite points; num_samples < 0 or > n; with num_samples > 0 a
+ * start_index < 0 or >= n; NULL where it is required; total >= INT32_MAX points.  The handle stays usable after a
+ * refusal. */
+typedef struct teaser_icp_fps_params_c {
+  int32_t num_samples; /* 0 .. n */
+  int32_t start_index; /* 0 .. n - 1 when num_samples > 0 */
+} teaser_icp_fps_params_c;
+#ifdef __cplusplus
+static_assert(sizeof(teaser_icp_fps_params_c) == 8, "teaser_icp_fps_params_c is 8 bytes");
+#else
+_Static_assert(sizeof(teaser_icp_fps_params_c) == 8, "teaser_icp_fps_params_c is 8 bytes");
+#endif
+TEASER_HIP_API int32_t teaser_hip_icp_farthest_point_down_sample_batch(teaser_hip_icp* icp, int32_t batch,
+                                                                       const double* const* points, const int32_t* n,
+                                                                       const teaser_icp_fps_params_c* params,
+                                                                       int32_t* const* index_out,
+                                                                       double* const* sel_dist_out,
+                                                                       double* const* final_dist_out);
 /* Options of an ICP handle (none changes a result).  "knn_ring_cap" (0 .. 16, default 4): the number of rings self
  * k-NN and statistical removal search on the grid before a query goes to the whole-cloud scan; 0 sends every query
  * there.  "knn_fallbacks" (read-only): how many queries of the handle's last self k-NN or statistical-removal call the
- * whole-cloud scan served.  An unknown name, a value outside the range or a write to a read-only option:
+ * whole-cloud scan served.  "fps_resident_max" (0 .. 10240, the compiled capacity, which is also the default): the
+ * largest cloud farthest-point down-sampling serves by its one-launch resident route; 0 sends every cloud to the
+ * launch-per-round route.  An unknown name, a value outside the range or a write to a read-only option:
  * TEASER_HIP_ERR_BAD_ARG, from both calls with teaser_hip_icp_last_error naming the option. */
 TEASER_HIP_API int32_t teaser_hip_icp_set_option(teaser_hip_icp* icp, const char* name, int64_t value);
 TEASER_HIP_API int32_t teaser_hip_icp_get_option(teaser_hip_icp* icp, const char* name, int64_t* value);

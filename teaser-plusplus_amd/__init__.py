@@ -138,7 +138,7 @@ EXPORTED_SYMBOLS = [
     "teaser_hip_icp_self_knn_batch", "teaser_hip_icp_remove_statistical_outliers_batch",
     "teaser_hip_icp_remove_radius_outliers_batch", "teaser_hip_icp_set_option", "teaser_hip_icp_get_option",
     "teaser_hip_icp_iss_params_default", "teaser_hip_icp_iss_keypoints_batch",
-    "teaser_hip_icp_cluster_dbscan_batch",
+    "teaser_hip_icp_cluster_dbscan_batch", "teaser_hip_icp_farthest_point_down_sample_batch",
     "teaser_hip_icp_information_batch", "teaser_hip_icp_information",
     "teaser_hip_icp_color_default", "teaser_hip_icp_batch_color", "teaser_hip_icp_solve_color",
     "teaser_hip_icp_color_gradients_batch",
@@ -252,6 +252,8 @@ def lib():
     _keypoints.declare(L)
     from . import cluster as _cluster
     _cluster.declare(L)
+    from . import fps as _fps
+    _fps.declare(L)
     from . import voxel as _voxel
     _voxel.declare(L)
     from . import features as _features
@@ -1120,6 +1122,8 @@ from .outlier import (remove_radius_outlier, remove_radius_outlier_batch, remove
                       remove_statistical_outlier_batch, self_knn, self_knn_batch, get_icp_option, set_icp_option)
 from .keypoints import compute_iss_keypoints, compute_iss_keypoints_batch  # noqa: E402
 from .cluster import cluster_dbscan, cluster_dbscan_batch  # noqa: E402
+from .fps import (farthest_point_down_sample, farthest_point_down_sample_batch,  # noqa: E402
+                  farthest_point_indices)
 from .features import (compute_fpfh_batch, correspondences_batch, match_features_batch,  # noqa: E402
                        knn_features, knn_features_batch, match_features_knn, match_features_knn_batch,
                        correspondences_knn, correspondences_knn_batch, tuple_test_batch)
@@ -1157,6 +1161,7 @@ __all__ = ["batched", "FPFHEstimation", "Matcher", "MultiDeviceSolver", "RobustR
            "remove_statistical_outlier", "remove_statistical_outlier_batch", "remove_radius_outlier",
            "remove_radius_outlier_batch", "self_knn", "self_knn_batch", "get_icp_option", "set_icp_option",
            "compute_iss_keypoints", "compute_iss_keypoints_batch", "cluster_dbscan", "cluster_dbscan_batch",
+           "farthest_point_down_sample", "farthest_point_down_sample_batch", "farthest_point_indices",
            "PoseGraph", "PoseGraphNode", "PoseGraphEdge", "GlobalOptimizationOption",
            "GlobalOptimizationConvergenceCriteria", "GlobalOptimizationLevenbergMarquardt",
            "GlobalOptimizationGaussNewton", "PoseGraphOptimizationResult", "global_optimization",

@@ -1,6 +1,6 @@
 // icp_host.h -- what the host files of the ICP handle share (icp.hip: the iteration loop and covariance estimation;
 // icp_outlier.hip: self k-NN, outlier removal and the options; icp_normals.hip: normal estimation and the
-// self-estimating point-to-plane entry; icp_keypoints.hip: ISS keypoints; icp_cluster.hip: DBSCAN clustering; icp_color.hip: Colored ICP): the handle and its buffers, and the scaffold
+// self-estimating point-to-plane entry; icp_keypoints.hip: ISS keypoints; icp_cluster.hip: DBSCAN clustering; icp_fps.hip: farthest-point down-sampling; icp_color.hip: Colored ICP): the handle and its buffers, and the scaffold
 // of a cloud call -- the entry checks (begin_cloud_call), the per-call index under construction (IcpIndex,
 // add_problem), the sizes of the index buffers by name (index_bytes, ensure_buffers), the packing and the uploads
 // (upload_points, upload_inputs), the index build (launch_index), the one copy back (copy_back, read_fallbacks) and
@@ -44,6 +44,7 @@ struct teaser_hip_icp : thip::HandleBase {
   std::vector<double> cstage; // Colored ICP: host packing of the intensities and the {gradient, intensity} records
   int32_t knn_ring_cap = thip::kIcpKnnRingCap;  // option "knn_ring_cap"
   int64_t knn_fallbacks = 0;              // option "knn_fallbacks": queries of the last call served by the whole-cloud route
+  int32_t fps_resident_max = thip::kFpsResidentCap;  // option "fps_resident_max" (icp_fps.hip)
   ~teaser_hip_icp() {
     for (thip::DevBuf& b : buf) b.release();
     if (h_live) (void)hipHostFree(h_live);

@@ -20,6 +20,7 @@ constexpr int kIcpKnnSmall = 32;   // capacity of the small instantiation's per-
 constexpr int kIcpKnnRingCap = 4;  // default number of rings searched on the grid before the whole-cloud route
 constexpr int kIcpKnnRingCapMax = 16;
 constexpr int kIcpKnnScanBlocks = 2048;  // waves of the whole-cloud route (each loops over the worklist)
+constexpr int kFpsResidentCap = 10240;   // farthest-point down-sampling: the resident route's compiled capacity
 
 // IcpDesc::method / IcpDesc::kernel: the values of teaser_icp_estimation_c (include/teaser_hip.h)
 enum { kIcpMethodPoint = 0, kIcpMethodPlane = 1, kIcpMethodGicp = 2, kIcpMethodColor = 3 };

@@ -97,6 +97,12 @@ int32_t teaser_hip_icp_set_option(teaser_hip_icp* h, const char* name, int64_t v
     h->knn_ring_cap = (int32_t)value;
     return TEASER_HIP_OK;
   }
+  if (strcmp(name, "fps_resident_max") == 0) {
+    if (value < 0 || value > kFpsResidentCap)
+      return fail(h, TEASER_HIP_ERR_BAD_ARG, "fps_resident_max must lie in [0, " + std::to_string(kFpsResidentCap) + "]");
+    h->fps_resident_max = (int32_t)value;
+    return TEASER_HIP_OK;
+  }
   if (strcmp(name, "knn_fallbacks") == 0) return fail(h, TEASER_HIP_ERR_BAD_ARG, "knn_fallbacks is read-only");
   return fail(h, TEASER_HIP_ERR_BAD_ARG, std::string("unknown ICP option ") + name);
 }
@@ -111,6 +117,10 @@ int32_t teaser_hip_icp_get_option(teaser_hip_icp* h, const char* name, int64_t* 
   }
   if (strcmp(name, "knn_fallbacks") == 0) {
     *value = h->knn_fallbacks;
+    return TEASER_HIP_OK;
+  }
+  if (strcmp(name, "fps_resident_max") == 0) {
+    *value = h->fps_resident_max;
     return TEASER_HIP_OK;
   }
   return fail(h, TEASER_HIP_ERR_BAD_ARG, std::string("unknown ICP option ") + name);
