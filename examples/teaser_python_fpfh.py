@@ -40,6 +40,10 @@ them: FPFH is still computed on the whole clouds (its neighbourhoods need every 
 keypoints go to the matcher, and the returned pairs are mapped back to cloud indices.  --iss-radii RS,RN gives the
 salient and the suppression radius; the default takes 6 and 4 times each cloud's resolution, like Open3D.
 
+--cloud-distance prints, after the registration, the mean and the largest distance from the registered source's
+points to their nearest target points (Open3D's compute_point_cloud_distance: a k = 1 search between the two clouds on
+the GPU) and how many of them lie closer than the voxel size -- the overlap of the pair.
+
 --fps K matches only K well-spread points of each down-sampled cloud (Open3D's farthest_point_down_sample on the GPU,
 both clouds in one call), applied where --iss is applied: the descriptors are computed on the whole cloud and kept at the
 K samples, and the returned pairs are mapped back to cloud indices.  A cloud of fewer than K points keeps all of them.
@@ -222,6 +226,9 @@ def main():
     ap.add_argument("--remove-plane", type=float, default=0.0, metavar="D",
                     help="drop the dominant plane (segment_plane, distance threshold D) from both clouds before FPFH")
     ap.add_argument("--plane-seed", type=int, default=1, metavar="N", help="seed of the plane trials (0: the clock)")
+    ap.add_argument("--cloud-distance", action="store_true",
+                    help="print the mean and the largest source-to-target distance after registration (nearest-"
+                         "neighbour search between the two clouds on the GPU); single pair only")
     ap.add_argument("--cluster", default="", metavar="EPS,MIN_POINTS",
                     help="keep the most populous DBSCAN cluster of each cloud (cluster_dbscan on the GPU, e.g. 0.1,10)")
     a = ap.parse_args()
@@ -235,6 +242,8 @@ def main():
         ap.error("--fps and --iss both choose the keypoints: give one of them")
     if a.iss and a.batch > 0:
         ap.error("--iss registers a single pair: it cannot be combined with --batch")
+    if a.cloud_distance and a.batch > 0:
+        ap.error("--cloud-distance measures a single pair: it cannot be combined with --batch")
     if a.batch > 0:
         if len(a.clouds) == 2:
             A, B = (read_ply_xyz(c).astype(np.float64) for c in a.clouds)
@@ -336,6 +345,15 @@ def main():
     print("%sfront-end %.1f ms, registration %.1f ms" % ("" if t_ds is None else "down-sampling %.1f ms, " % (1e3 * t_ds),
                                                        1e3 * (t1 - t0), 1e3 * (t2 - t1)))
     print("R =\n%s\nt = %s" % (sol.rotation, sol.translation))
+    if a.cloud_distance:  # Open3D's source.compute_point_cloud_distance(target) on the registered source
+        moved = np.asarray(A, dtype=np.float64) @ np.asarray(sol.rotation).T + np.asarray(sol.translation)
+        t3 = time.perf_counter()
+        dist = tp.compute_point_cloud_distance(moved, np.asarray(B, dtype=np.float64))
+        t4 = time.perf_counter()
+        print("source-to-target distance after registration: mean %.6f max %.6f, %d of %d source points closer than "
+              "the voxel size (%.1f ms, %d queries served by the scan of the whole target)"
+              % (dist.mean(), dist.max(), int((dist < vox).sum()), len(dist), 1e3 * (t4 - t3),
+                 tp.get_icp_option("knn_fallbacks")))
     if a.ransac:
         P, Q = np.asarray(A, dtype=np.float64), np.asarray(B, dtype=np.float64)
         pairs = np.array(corr, dtype=np.int32).reshape(-1, 2)

@@ -833,6 +833,51 @@ TEASER_HIP_API int32_t teaser_hip_icp_color_gradients_batch(teaser_hip_icp* icp,
 TEASER_HIP_API int32_t teaser_hip_icp_self_knn_batch(teaser_hip_icp* icp, int32_t batch, const double* const* points,
                                                      const int32_t* n, const int32_t* k, int32_t* const* idx_out,
                                                      double* const* d2_out);
+/* Neighbour search between two clouds (Open3D's KDTreeFlann / core.nns.NearestNeighborSearch), on the ICP handle:
+ * k-NN, hybrid and uncapped radius search, batched.  Problem b has a data cloud data[b] (n_data[b] x 3 doubles) and a
+ * query set query[b] (n_query[b] x 3 doubles); the neighbours of query i are points j of the data cloud.
+ *   d2(i, j) = ((dx dx + dy dy) + dz dz), dx = Q[i].x - P[j].x, never contracted (the expression used everywhere on this
+ *   handle); every order is ascending (d2, j).  n_data = 0 and n_query = 0 are legal; queries may lie anywhere, far
+ *   outside the data's bounding box included.  Deterministic: the same bits for a problem alone, inside any batch, in any
+ *   batch position, run after run, and whichever route served a query.
+ *   TEASER_HIP_ERR_BAD_ARG (argument and problem named): non-finite coordinates on either side, a parameter out of
+ *   range, NULL where the matching n > 0.
+ * knn_search:    k[b] in [1, TEASER_HIP_ICP_KNN_MAX].  Row i holds the min(k, n_data) smallest (d2, j) over the whole data
+ *                cloud, then -1 / +inf.  idx_out[b]: n_query x k int32; d2_out: NULL, or per problem NULL or n_query x k
+ *                doubles.  The options "knn_ring_cap" / "knn_fallbacks" are those of self k-NN: the rings are counted from
+ *                the first ring that can touch the data's grid, "knn_fallbacks" is the number of queries of the call that
+ *                the scan of the whole data cloud served.  Two clouds that overlap in part send every query far from the
+ *                data there.
+ * hybrid_search: radius, like its square, finite and > 0; max_nn[b] in [1, TEASER_HIP_ICP_KNN_MAX].  The neighbours are the
+ *                j with d2 < radius radius (strict, as in the radius-outlier and covariance contracts); row i holds the
+ *                first min(max_nn, number inside) of them, then -1 / +inf.  idx_out[b] / d2_out[b]: n_query x max_nn;
+ *                count_out: NULL, or per problem NULL or n_query int32, the number written per row.
+ * radius_search: uncapped.  count_out[b][i] (int32; required where n_query > 0) = the number of j with
+ *                d2 < radius radius; total_out[b] (int64; required) = their sum over the problem's queries.  Row i
+ *                occupies the slots [prefix(i), prefix(i) + count[i]) of idx_out[b] (int32) and d2_out[b] (doubles; NULL,
+ *                or per problem NULL), prefix = the exclusive sum of count_out[b], in ascending (d2, j).  capacity[b]
+ *                (int64, >= 0; may be NULL when idx_out is) = the entries the caller's arrays hold.  Where idx_out or
+ *                idx_out[b] is NULL or capacity[b] < total, the problem gets its counts and its total only and its arrays
+ *                are not touched: not an error, but the first half of count-then-fill (like the buf, len getters of the
+ *                solver).  Device and host memory of a call: 12 bytes x the sum over the problems with arrays of
+ *                min(capacity, n_query n_data), twice; a call that cannot get it fails with TEASER_HIP_ERR_OOM and leaves
+ *                the handle usable.  Rows are ordered by ranking every entry inside its row, O(row length) per entry.
+ * The last two have one route each and leave "knn_fallbacks" at 0. */
+TEASER_HIP_API int32_t teaser_hip_icp_knn_search_batch(teaser_hip_icp* icp, int32_t batch, const double* const* data,
+                                                       const int32_t* n_data, const double* const* query,
+                                                       const int32_t* n_query, const int32_t* k,
+                                                       int32_t* const* idx_out, double* const* d2_out);
+TEASER_HIP_API int32_t teaser_hip_icp_hybrid_search_batch(teaser_hip_icp* icp, int32_t batch, const double* const* data,
+                                                          const int32_t* n_data, const double* const* query,
+                                                          const int32_t* n_query, const double* radius,
+                                                          const int32_t* max_nn, int32_t* const* idx_out,
+                                                          double* const* d2_out, int32_t* const* count_out);
+TEASER_HIP_API int32_t teaser_hip_icp_radius_search_batch(teaser_hip_icp* icp, int32_t batch, const double* const* data,
+                                                          const int32_t* n_data, const double* const* query,
+                                                          const int32_t* n_query, const double* radius,
+                                                          const int64_t* capacity, int32_t* const* count_out,
+                                                          int32_t* const* idx_out, double* const* d2_out,
+                                                          int64_t* total_out);
 /* Outlier removal: statistical (Open3D's remove_statistical_outlier), on the ICP handle.  Per cloud, with
  * nb_neighbors in [1, TEASER_HIP_ICP_KNN_MAX] and std_ratio finite and > 0:
  *   avg[i]    = (sum of sqrt(d2) over point i's m = min(nb_neighbors, n) nearest of self k-NN, the point itself

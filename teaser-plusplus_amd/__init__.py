@@ -137,6 +137,7 @@ EXPORTED_SYMBOLS = [
     "teaser_hip_icp_solve_auto",
     "teaser_hip_icp_self_knn_batch", "teaser_hip_icp_remove_statistical_outliers_batch",
     "teaser_hip_icp_remove_radius_outliers_batch", "teaser_hip_icp_set_option", "teaser_hip_icp_get_option",
+    "teaser_hip_icp_knn_search_batch", "teaser_hip_icp_hybrid_search_batch", "teaser_hip_icp_radius_search_batch",
     "teaser_hip_icp_iss_params_default", "teaser_hip_icp_iss_keypoints_batch",
     "teaser_hip_icp_cluster_dbscan_batch", "teaser_hip_icp_farthest_point_down_sample_batch",
     "teaser_hip_icp_information_batch", "teaser_hip_icp_information",
@@ -248,6 +249,8 @@ def lib():
     _icp.declare(L)
     from . import outlier as _outlier
     _outlier.declare(L)
+    from . import search as _search
+    _search.declare(L)
     from . import keypoints as _keypoints
     _keypoints.declare(L)
     from . import cluster as _cluster
@@ -1120,6 +1123,9 @@ from .icp import (CauchyLoss, GMLoss, HuberLoss, ICPConvergenceCriteria, L2Loss,
 from .voxel import voxel_down_sample, voxel_down_sample_batch  # noqa: E402
 from .outlier import (remove_radius_outlier, remove_radius_outlier_batch, remove_statistical_outlier,  # noqa: E402
                       remove_statistical_outlier_batch, self_knn, self_knn_batch, get_icp_option, set_icp_option)
+from .search import (KDTreeFlann, NearestNeighborSearch, compute_nearest_neighbor_distance,  # noqa: E402
+                     compute_point_cloud_distance, hybrid_search, hybrid_search_batch, knn_search, knn_search_batch,
+                     radius_search, radius_search_batch)
 from .keypoints import compute_iss_keypoints, compute_iss_keypoints_batch  # noqa: E402
 from .cluster import cluster_dbscan, cluster_dbscan_batch  # noqa: E402
 from .fps import (farthest_point_down_sample, farthest_point_down_sample_batch,  # noqa: E402
@@ -1160,6 +1166,9 @@ __all__ = ["batched", "FPFHEstimation", "Matcher", "MultiDeviceSolver", "RobustR
            "estimate_color_gradients_batch",
            "remove_statistical_outlier", "remove_statistical_outlier_batch", "remove_radius_outlier",
            "remove_radius_outlier_batch", "self_knn", "self_knn_batch", "get_icp_option", "set_icp_option",
+           "knn_search", "knn_search_batch", "hybrid_search", "hybrid_search_batch", "radius_search",
+           "radius_search_batch", "NearestNeighborSearch", "KDTreeFlann", "compute_point_cloud_distance",
+           "compute_nearest_neighbor_distance",
            "compute_iss_keypoints", "compute_iss_keypoints_batch", "cluster_dbscan", "cluster_dbscan_batch",
            "farthest_point_down_sample", "farthest_point_down_sample_batch", "farthest_point_indices",
            "PoseGraph", "PoseGraphNode", "PoseGraphEdge", "GlobalOptimizationOption",

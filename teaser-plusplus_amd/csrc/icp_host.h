@@ -1,6 +1,7 @@
 // icp_host.h -- what the host files of the ICP handle share (icp.hip: the iteration loop and covariance estimation;
 // icp_outlier.hip: self k-NN, outlier removal and the options; icp_normals.hip: normal estimation and the
-// self-estimating point-to-plane entry; icp_keypoints.hip: ISS keypoints; icp_cluster.hip: DBSCAN clustering; icp_fps.hip: farthest-point down-sampling; icp_color.hip: Colored ICP): the handle and its buffers, and the scaffold
+// self-estimating point-to-plane entry; icp_keypoints.hip: ISS keypoints; icp_cluster.hip: DBSCAN clustering; icp_fps.hip: farthest-point down-sampling; icp_color.hip: Colored ICP;
+// icp_search.hip: neighbour search between two clouds): the handle and its buffers, and the scaffold
 // of a cloud call -- the entry checks (begin_cloud_call), the per-call index under construction (IcpIndex,
 // add_problem), the sizes of the index buffers by name (index_bytes, ensure_buffers), the packing and the uploads
 // (upload_points, upload_inputs), the index build (launch_index), the one copy back (copy_back, read_fallbacks) and
@@ -29,10 +30,11 @@ namespace thip {
 // B_KTEMP between the sort and the scan, and adds B_DPARENT (the union-find), B_DFLAG ("is a root", total + 1 entries)
 // and B_DSCAN (its exclusive scan).  B_COLOR_*: Colored ICP (icp_color.hip): the per-problem IcpColorDesc records, one intensity per
 // source point, and per target point the {gradient, intensity} record; its gradient pass keeps its descriptors, records
-// and block maps in B_N* (a coloured call estimates no normals)
+// and block maps in B_N* (a coloured call estimates no normals).  B_SEARCH_TMP: the radius search's rows before they are
+// ordered (icp_search.hip)
 enum { B_DESC, B_STATE, B_BLK, B_TBLK, B_X, B_Q, B_TBUCKET, B_BCOUNT, B_BSTART, B_CURSOR, B_QS, B_QJ, B_MATCH,
        B_PARTIALS, B_LIVE, B_NORMALS, B_COV_S, B_COV_T, B_NDESC, B_NKNN, B_NREC, B_NBLK, B_NTBLK, B_KDESC, B_KBLK,
-       B_KKEY, B_KIOTA, B_KSKEY, B_KSIDX, B_KSPTS, B_KTEMP, B_DPARENT, B_DFLAG, B_DSCAN, B_COLOR_DESC, B_COLOR_S, B_COLOR_T, B_COUNT };
+       B_KKEY, B_KIOTA, B_KSKEY, B_KSIDX, B_KSPTS, B_KTEMP, B_DPARENT, B_DFLAG, B_DSCAN, B_COLOR_DESC, B_COLOR_S, B_COLOR_T, B_SEARCH_TMP, B_COUNT };
 
 }  // namespace thip
 

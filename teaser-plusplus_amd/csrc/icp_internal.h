@@ -20,6 +20,7 @@ constexpr int kIcpKnnSmall = 32;   // capacity of the small instantiation's per-
 constexpr int kIcpKnnRingCap = 4;  // default number of rings searched on the grid before the whole-cloud route
 constexpr int kIcpKnnRingCapMax = 16;
 constexpr int kIcpKnnScanBlocks = 2048;  // waves of the whole-cloud route (each loops over the worklist)
+constexpr int kIcpSearchR0Max = 16;      // two-cloud k-NN: a query more cells than this outside the grid skips the rings
 constexpr int kFpsResidentCap = 10240;   // farthest-point down-sampling: the resident route's compiled capacity
 
 // IcpDesc::method / IcpDesc::kernel: the values of teaser_icp_estimation_c (include/teaser_hip.h)
@@ -76,6 +77,19 @@ struct IcpKnnDesc {
   int64_t out_off;    // first slot of this cloud in the packed n x k outputs (self k-NN)
   double edge;        // h: the grid's cell edge is at least h (1 + 1e-6), the margin of set_grid
   double ratio;       // std_ratio (statistical removal)
+};
+
+// One problem of a two-cloud neighbour search (kernels_search.hip), beside its IcpDesc: the data cloud is the
+// descriptor's "target" (n_t, t_off, the grid), the query set its "source" (n_s, s_off in the packed queries); blk_off /
+// nblk count the blocks of queries (kIcpCovBlock per block for k-NN and hybrid, 256 for the radius search).
+struct IcpSearchDesc {
+  int32_t k;          // k (k-NN) or max_nn (hybrid)
+  int32_t ring_cap;   // k-NN: rings r0 .. r0 + ring_cap - 1 are searched on the grid; 0: every query is scanned
+  int32_t fill;       // radius: 1 when the caller gave arrays for this problem
+  int32_t pad;
+  int64_t out_off;    // k-NN, hybrid: first slot of the packed n_query x k outputs; radius: first entry of the problem
+  int64_t capacity;   // radius: entries the caller's arrays hold; the problem is filled iff fill && capacity >= total
+  double edge;        // k-NN: h of IcpKnnDesc::edge
 };
 
 // One cloud of a normal-estimation call, beside its IcpDesc (the cloud is the descriptor's "target"; hybrid search: the
@@ -173,6 +187,26 @@ void launch_icp_statistical(hipStream_t s, const IcpDesc* d_desc, const IcpKnnDe
 void launch_icp_radius_count(hipStream_t s, const IcpDesc* d_desc, const IcpKnnDesc* d_knn,
                              const int32_t* d_tblk_prob, int n_tblk, const double* d_q, const double* d_qs,
                              const int32_t* d_bstart, int32_t* d_count, uint8_t* d_keep, int32_t* d_kept);
+// Neighbour search between two clouds (kernels_search.hip; the contract "Neighbour search" of include/teaser_hip.h).
+// d_x: the packed queries (IcpDesc::s_off), the data clouds are indexed.  k-NN: n_query x k slots per problem at
+// IcpSearchDesc::out_off of d_idx / d_d2; work: 2 int32 per query, work_count as for self k-NN.
+void launch_icp_search_knn(hipStream_t s, const IcpDesc* d_desc, const IcpSearchDesc* d_sd, const int32_t* d_blk_prob,
+                           int n_blk, int top_k, const double* d_x, const double* d_q, const double* d_qs,
+                           const int32_t* d_qj, const int32_t* d_bstart, int32_t* d_idx, double* d_d2, int32_t* d_work,
+                           int32_t* d_work_count);
+// Hybrid: the rows as above and d_cnt[s_off + i] = the number written.
+void launch_icp_search_hybrid(hipStream_t s, const IcpDesc* d_desc, const IcpSearchDesc* d_sd,
+                              const int32_t* d_blk_prob, int n_blk, int top_nn, const double* d_x, const double* d_qs,
+                              const int32_t* d_qj, const int32_t* d_bstart, int32_t* d_idx, double* d_d2,
+                              int32_t* d_cnt);
+// Radius: d_count / d_prefix per query at s_off (the count and its exclusive sum over the problem), d_total per problem;
+// the problems that are filled get their rows in ascending (d2, j) at out_off + prefix of d_idx / d_d2, through the
+// unordered d_tmp_d2 / d_tmp_j.  entries: the sum of the entries reserved (0: the count half only, no array is touched).
+void launch_icp_search_radius(hipStream_t s, const IcpDesc* d_desc, const IcpSearchDesc* d_sd,
+                              const int32_t* d_blk_prob, int n_blk, int batch, int64_t entries, const double* d_x,
+                              const double* d_qs, const int32_t* d_qj, const int32_t* d_bstart, int32_t* d_count,
+                              int64_t* d_prefix, int64_t* d_total, double* d_tmp_d2, int32_t* d_tmp_j, int32_t* d_idx,
+                              double* d_d2);
 // The information matrices of the problems whose matches (d_match, written by the mode-0 correspondence pass over the
 // same block map) and targets as given (d_q) are on the device: d_partials takes kIcpInfoSums doubles per block,
 // d_info 36 per problem (row-major 6 x 6).  kernels_icp_information.hip.
