@@ -13,7 +13,13 @@ on the MI355X.  Usage:
                                           [--knn K [--no-mutual]] [--tuple-scale S [--tuple-seed N]]
                                           [--iss [--iss-radii RS,RN]] [--fps K]
                                           [--ransac [--ransac-iterations N --ransac-seed N]]
-                                          [--fgr [--fgr-tuple-test --fgr-seed N]]
+                                          [--fgr [--fgr-tuple-test --fgr-seed N]] [--open3d-fpfh]
+
+--open3d-fpfh computes the descriptors the way Open3D's global-registration scripts do, in place of the PCL form: the
+extract_fpfh helper's estimate_normals(KDTreeSearchParamHybrid(2 voxels, 30)) and compute_fpfh_feature(
+KDTreeSearchParamHybrid(5 voxels, 100)) in FP64, both clouds (with --batch all 2 K clouds) in ONE call on the GPU, the
+normals never leaving the device in between.  Everything downstream -- the matcher, --knn, --ransac, --fgr, --batch --
+takes these rows as it takes the PCL form's; --icp-plane then refines on these normals.
 
 --remove-plane D drops the dominant plane (Open3D's segment_plane on the GPU: distance_threshold D, ransac_n 3, 1 000
 iterations, seeded by --plane-seed) from BOTH clouds after down-sampling and before FPFH, in one batched call, and
@@ -108,7 +114,16 @@ def parse_outliers(text):
     return int(nb), float(ratio)
 
 
-def run_batch(A, B, vox, K, icp_iterations, knn=0, mutual=True, tuple_scale=0.0, tuple_seed=0, outliers=None, fps=0):
+def open3d_fpfh(clouds, vox, return_normals=False):
+    """Open3D's extract_fpfh for every cloud, one call: normals Hybrid(2 v, 30), features Hybrid(5 v, 100)."""
+    return tp.compute_fpfh_feature_batch([np.asarray(c, dtype=np.float64) for c in clouds], None,
+                                         tp.KDTreeSearchParamHybrid(5 * vox, 100),
+                                         normal_search=tp.KDTreeSearchParamHybrid(2 * vox, 30),
+                                         return_normals=return_normals)
+
+
+def run_batch(A, B, vox, K, icp_iterations, knn=0, mutual=True, tuple_scale=0.0, tuple_seed=0, outliers=None, fps=0,
+              o3d=False):
     """K perturbed copies of the pair (A, B) through the batched stages, one call per stage."""
     rng = np.random.default_rng(555)
     srcs, dsts = [], []
@@ -135,9 +150,12 @@ def run_batch(A, B, vox, K, icp_iterations, knn=0, mutual=True, tuple_scale=0.0,
         t_clean = time.perf_counter() - t1
         t1 = time.perf_counter()
         sp, dp = down[:K], down[K:]
-        if fps:  # descriptors on the whole clouds, matching at min(fps, n) well-spread samples of each
-            feats = tp.compute_fpfh_batch(down, 2 * vox, 5 * vox)
-            keys = tp.farthest_point_down_sample_batch(down, [min(fps, len(c)) for c in down])
+        if fps or o3d:  # descriptors on the whole clouds, matching at min(fps, n) well-spread samples of each
+            feats = open3d_fpfh(down, vox) if o3d else tp.compute_fpfh_batch(down, 2 * vox, 5 * vox)
+            if fps:
+                keys = tp.farthest_point_down_sample_batch(down, [min(fps, len(c)) for c in down])
+            else:
+                keys = [np.arange(len(c)) for c in down]
             fk = [f[k] for f, k in zip(feats, keys)]
             if knn:
                 corr = tp.match_features_knn_batch(fk[:K], fk[K:], knn, mutual)
@@ -229,6 +247,9 @@ def main():
     ap.add_argument("--cloud-distance", action="store_true",
                     help="print the mean and the largest source-to-target distance after registration (nearest-"
                          "neighbour search between the two clouds on the GPU); single pair only")
+    ap.add_argument("--open3d-fpfh", action="store_true",
+                    help="Open3D's descriptors (estimate_normals Hybrid(2 v, 30) + compute_fpfh_feature Hybrid(5 v, "
+                         "100), FP64, one call on the GPU) in place of the PCL form")
     ap.add_argument("--cluster", default="", metavar="EPS,MIN_POINTS",
                     help="keep the most populous DBSCAN cluster of each cloud (cluster_dbscan on the GPU, e.g. 0.1,10)")
     a = ap.parse_args()
@@ -251,7 +272,7 @@ def main():
             c5 = np.load(os.path.join(ROOT, "tests", "golden", "config5_clouds.npz"))
             A, B, a.voxel = c5["cloud_bin_0"].astype(np.float64), c5["cloud_bin_4"].astype(np.float64), float(c5["voxel_size"])
         return run_batch(A, B, a.voxel, a.batch, a.icp_iterations, a.knn, not a.no_mutual, a.tuple_scale, a.tuple_seed,
-                         parse_outliers(a.remove_outliers), a.fps)
+                         parse_outliers(a.remove_outliers), a.fps, a.open3d_fpfh)
     t_ds = None
     if len(a.clouds) == 2:
         raw = [read_ply_xyz(c).astype(np.float64) for c in a.clouds]
@@ -300,10 +321,14 @@ def main():
         print("clustering of both clouds: %.1f ms (one call)" % (1e3 * t_cluster))
         A, B = kept
     t0 = time.perf_counter()
-    est = tp.FPFHEstimation()
-    fa = est.computeFPFHFeatures(A, 2 * vox, 5 * vox)   # helpers.py:9-18: radii 2 and 5 voxels
-    fb = est.computeFPFHFeatures(B, 2 * vox, 5 * vox)
-    nb = est.getNormals()   # the target's normals: point-to-plane ICP refines on them
+    if a.open3d_fpfh:  # Open3D's extract_fpfh for both clouds in one call
+        (fa, _), (fb, nb) = open3d_fpfh([A, B], vox, return_normals=True)
+        print("Open3D-form FPFH: %d + %d rows of %d float64, normals and features in one call" % (len(fa), len(fb), fa.shape[1]))
+    else:
+        est = tp.FPFHEstimation()
+        fa = est.computeFPFHFeatures(A, 2 * vox, 5 * vox)   # helpers.py:9-18: radii 2 and 5 voxels
+        fb = est.computeFPFHFeatures(B, 2 * vox, 5 * vox)
+        nb = est.getNormals()   # the target's normals: point-to-plane ICP refines on them
     full = (A, B)
     if a.iss:  # the matcher sees the keypoints only; `keys` maps its pairs back to cloud indices
         rs, rn = (float(v) for v in a.iss_radii.split(",")) if a.iss_radii else (0.0, 0.0)

@@ -878,6 +878,63 @@ TEASER_HIP_API int32_t teaser_hip_icp_radius_search_batch(teaser_hip_icp* icp, i
                                                           const int64_t* capacity, int32_t* const* count_out,
                                                           int32_t* const* idx_out, double* const* d2_out,
                                                           int64_t* total_out);
+/* FPFH (Open3D form) (Open3D's compute_fpfh_feature with KDTreeSearchParamHybrid or KDTreeSearchParamKNN on normals that
+ * are GIVEN), batched, FP64, on the ICP handle.  The PCL-form calls (teaser_hip_compute_fpfh and its batch) are another
+ * descriptor with other bits and are untouched.  Per cloud: points P (n x 3 doubles), unit normals N (n x 3 doubles, used
+ * as given), one search record (teaser_icp_normal_search_c: orient must be 0, ref is not read, max_nn in [2, 100]).
+ *   list of i:    (j_0, d2_0), ..., (j_{m-1}, d2_{m-1}) in ascending (d2, j), i itself included, with
+ *                 d2 = (e0 e0 + e1 e1) + e2 e2, e = P[i] - P[j] -- the rows of teaser_hip_icp_hybrid_search_batch /
+ *                 _knn_search_batch with the cloud as its own query set.  search 0 (hybrid): the max_nn smallest with
+ *                 d2 < radius radius.  search 1 (k-NN): the first min(max_nn, n).  Position 0 is skipped WHATEVER it
+ *                 holds (Open3D skips by position, not by identity: among coincident points position 0 is the smallest
+ *                 index of them).  Radius-only search (search 2, KDTreeSearchParamRadius) is refused by name for the
+ *                 reason the normals contract gives: it is uncapped, so there is no bounded sorted list to sum over.
+ *   pair (i, j_k), k >= 1, with (p1, n1) = (P[i], N[i]) and (p2, n2) = (P[j_k], N[j_k]).  dot(a, b) = (ax bx + ay by) +
+ *                 az bz, cross(a, b) = (ay bz - az by, az bx - ax bz, ax by - ay bx) with every product rounded; no
+ *                 product-add is fused anywhere:
+ *                   dp = p2 - p1;  f3 = sqrt(dot(dp, dp));  f3 == 0: the pair is degenerate
+ *                   a1 = dot(n1, dp) / f3;  a2 = dot(n2, dp) / f3
+ *                   |a1| < |a2|: n1 <-> n2, dp = -dp, f2 = -a2; otherwise f2 = a1.  (Open3D tests acos(|a1|) >
+ *                                acos(|a2|); stated on the cosines it is the same decision except where two different
+ *                                cosines round to one arc cosine.)
+ *                   v = cross(dp, n1);  |v| = sqrt(dot(v, v));  |v| == 0: the pair is degenerate;  v = v / |v| per
+ *                   component;  w = cross(n1, v);  f1 = dot(v, n2)
+ *                   f0 = atan2(dot(w, n2), dot(n1, n2)) by the deterministic FP64 formula of csrc/fdet_math.h (IEEE basic
+ *                   operations in a fixed order: two argument halvings, a 25-term series)
+ *                 A degenerate pair has f0 = f1 = f2 = 0 and is still binned (bins 5, 16 and 27), as in Open3D.
+ *   SPFH row i:   33 doubles, zero when m <= 1.  Otherwise c = 100.0 / (double)(m - 1) and for k = 1 .. m-1, with
+ *                 pi = 3.14159265358979323846, h0 = floor((11 (f0 + pi)) / (2.0 pi)), h1 = floor((11 (f1 + 1.0)) 0.5),
+ *                 h2 = floor((11 (f2 + 1.0)) 0.5), each clamped to [0, 10] (a NaN, which only normals with overflowing
+ *                 products can give, goes to 0): c is added to the bins h0, 11 + h1 and 22 + h2.  A bin's value is c added
+ *                 one at a time from 0.0, as often as it was hit.
+ *   FPFH row i:   zero when m <= 1.  Otherwise
+ *                   F[0..32] = 0;  S[0..2] = 0
+ *                   for k = 1 .. m-1 in list order:  if d2_k == 0: skip k
+ *                       for j = 0 .. 32 in order:  val = SPFH[j_k][j] / d2_k  (the SQUARED distance, as in Open3D);
+ *                                                  S[j / 11] += val;  F[j] += val
+ *                   for g = 0 .. 2:  if S[g] != 0: S[g] = 100.0 / S[g]
+ *                   for j = 0 .. 32: F[j] = F[j] S[j / 11];  F[j] = F[j] + SPFH[i][j]   (two roundings)
+ *                 S[g] is one sequential chain over (k, then j inside the group).
+ * fpfh_out[b]: n[b] x 33 doubles, one row per point: the transpose of Open3D's 33 x n Feature.data, the same memory as
+ * Eigen's column-major matrix.  spfh_out: NULL, or per cloud NULL or n x 33 doubles.  Empty clouds are legal.
+ * Normals inside the call: where normals[b] is NULL (or normals is NULL) and normal_search (NULL, or one record per
+ * cloud; max_nn = 0 means "none given") has a record for the cloud, the cloud's normals are first estimated on the
+ * device by the rule of teaser_hip_icp_normals_batch (any orient) and stay there; the result is bit-equal to that call
+ * followed by this one on its normals.  normals_out: NULL, or per cloud NULL or n x 3 doubles: the normals the cloud
+ * was computed with.  A cloud with neither normals nor a record: TEASER_HIP_ERR_BAD_ARG.
+ * Deterministic like every call on this handle: a cloud gives the same bits alone, at any position in any batch, run
+ * after run, for any value of "fpfh_list_bytes" (below) and, for k-NN search, of "knn_ring_cap"; "knn_fallbacks" is left
+ * at 0.  Bit parity with an Open3D binary is NOT claimed: Open3D's libm (atan2, acos) and Eigen's summation order are
+ * not ours; tests/fpfh_o3d_reference.py restates this text, and tests/test_fpfh_o3d_reference.py bounds its distance from
+ * the libm form.  TEASER_HIP_ERR_BAD_ARG (argument and cloud named): non-finite points or normals; search, max_nn or
+ * orient outside their ranges; reserved != 0; a radius (or its square) that is not finite and > 0 in hybrid search; NULL
+ * where n > 0.  One stream synchronisation per call whatever the batch. */
+TEASER_HIP_API int32_t teaser_hip_icp_fpfh_batch(teaser_hip_icp* icp, int32_t batch, const double* const* points,
+                                                 const double* const* normals, const int32_t* n,
+                                                 const teaser_icp_normal_search_c* search,
+                                                 const teaser_icp_normal_search_c* normal_search,
+                                                 double* const* fpfh_out, double* const* spfh_out,
+                                                 double* const* normals_out);
 /* Outlier removal: statistical (Open3D's remove_statistical_outlier), on the ICP handle.  Per cloud, with
  * nb_neighbors in [1, TEASER_HIP_ICP_KNN_MAX] and std_ratio finite and > 0:
  *   avg[i]    = (sum of sqrt(d2) over point i's m = min(nb_neighbors, n) nearest of self k-NN, the point itself
@@ -1054,7 +1111,9 @@ TEASER_HIP_API int32_t teaser_hip_icp_farthest_point_down_sample_batch(teaser_hi
  * there.  "knn_fallbacks" (read-only): how many queries of the handle's last self k-NN or statistical-removal call the
  * whole-cloud scan served.  "fps_resident_max" (0 .. 10240, the compiled capacity, which is also the default): the
  * largest cloud farthest-point down-sampling serves by its one-launch resident route; 0 sends every cloud to the
- * launch-per-round route.  An unknown name, a value outside the range or a write to a read-only option:
+ * launch-per-round route.  "fpfh_list_bytes" (1 .. 2^40, default 512 MiB): the bound of the neighbour-list scratch of
+ * teaser_hip_icp_fpfh_batch (12 bytes per point and max_nn slot); a call whose lists exceed it runs in several passes
+ * and computes its lists twice; a piece of a cloud is never smaller than 64 points.  An unknown name, a value outside the range or a write to a read-only option:
  * TEASER_HIP_ERR_BAD_ARG, from both calls with teaser_hip_icp_last_error naming the option. */
 TEASER_HIP_API int32_t teaser_hip_icp_set_option(teaser_hip_icp* icp, const char* name, int64_t value);
 TEASER_HIP_API int32_t teaser_hip_icp_get_option(teaser_hip_icp* icp, const char* name, int64_t* value);

@@ -138,6 +138,7 @@ EXPORTED_SYMBOLS = [
     "teaser_hip_icp_self_knn_batch", "teaser_hip_icp_remove_statistical_outliers_batch",
     "teaser_hip_icp_remove_radius_outliers_batch", "teaser_hip_icp_set_option", "teaser_hip_icp_get_option",
     "teaser_hip_icp_knn_search_batch", "teaser_hip_icp_hybrid_search_batch", "teaser_hip_icp_radius_search_batch",
+    "teaser_hip_icp_fpfh_batch",
     "teaser_hip_icp_iss_params_default", "teaser_hip_icp_iss_keypoints_batch",
     "teaser_hip_icp_cluster_dbscan_batch", "teaser_hip_icp_farthest_point_down_sample_batch",
     "teaser_hip_icp_information_batch", "teaser_hip_icp_information",
@@ -251,6 +252,8 @@ def lib():
     _outlier.declare(L)
     from . import search as _search
     _search.declare(L)
+    from . import fpfh_open3d as _fpfh_open3d
+    _fpfh_open3d.declare(L)
     from . import keypoints as _keypoints
     _keypoints.declare(L)
     from . import cluster as _cluster
@@ -1126,6 +1129,8 @@ from .outlier import (remove_radius_outlier, remove_radius_outlier_batch, remove
 from .search import (KDTreeFlann, NearestNeighborSearch, compute_nearest_neighbor_distance,  # noqa: E402
                      compute_point_cloud_distance, hybrid_search, hybrid_search_batch, knn_search, knn_search_batch,
                      radius_search, radius_search_batch)
+from .fpfh_open3d import (KDTreeSearchParamRadius, compute_fpfh_feature, compute_fpfh_feature_batch,  # noqa: E402
+                          extract_fpfh)
 from .keypoints import compute_iss_keypoints, compute_iss_keypoints_batch  # noqa: E402
 from .cluster import cluster_dbscan, cluster_dbscan_batch  # noqa: E402
 from .fps import (farthest_point_down_sample, farthest_point_down_sample_batch,  # noqa: E402
@@ -1169,6 +1174,7 @@ __all__ = ["batched", "FPFHEstimation", "Matcher", "MultiDeviceSolver", "RobustR
            "knn_search", "knn_search_batch", "hybrid_search", "hybrid_search_batch", "radius_search",
            "radius_search_batch", "NearestNeighborSearch", "KDTreeFlann", "compute_point_cloud_distance",
            "compute_nearest_neighbor_distance",
+           "compute_fpfh_feature", "compute_fpfh_feature_batch", "extract_fpfh", "KDTreeSearchParamRadius",
            "compute_iss_keypoints", "compute_iss_keypoints_batch", "cluster_dbscan", "cluster_dbscan_batch",
            "farthest_point_down_sample", "farthest_point_down_sample_batch", "farthest_point_indices",
            "PoseGraph", "PoseGraphNode", "PoseGraphEdge", "GlobalOptimizationOption",

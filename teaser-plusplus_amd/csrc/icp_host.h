@@ -1,7 +1,7 @@
 // icp_host.h -- what the host files of the ICP handle share (icp.hip: the iteration loop and covariance estimation;
 // icp_outlier.hip: self k-NN, outlier removal and the options; icp_normals.hip: normal estimation and the
 // self-estimating point-to-plane entry; icp_keypoints.hip: ISS keypoints; icp_cluster.hip: DBSCAN clustering; icp_fps.hip: farthest-point down-sampling; icp_color.hip: Colored ICP;
-// icp_search.hip: neighbour search between two clouds): the handle and its buffers, and the scaffold
+// icp_search.hip: neighbour search between two clouds; icp_fpfh.hip: the Open3D-form FPFH): the handle and its buffers, and the scaffold
 // of a cloud call -- the entry checks (begin_cloud_call), the per-call index under construction (IcpIndex,
 // add_problem), the sizes of the index buffers by name (index_bytes, ensure_buffers), the packing and the uploads
 // (upload_points, upload_inputs), the index build (launch_index), the one copy back (copy_back, read_fallbacks) and
@@ -31,10 +31,12 @@ namespace thip {
 // and B_DSCAN (its exclusive scan).  B_COLOR_*: Colored ICP (icp_color.hip): the per-problem IcpColorDesc records, one intensity per
 // source point, and per target point the {gradient, intensity} record; its gradient pass keeps its descriptors, records
 // and block maps in B_N* (a coloured call estimates no normals).  B_SEARCH_TMP: the radius search's rows before they are
-// ordered (icp_search.hip)
+// ordered (icp_search.hip).  B_FPFH_*: the Open3D-form FPFH (icp_fpfh.hip): the pieces' descriptors, search records and
+// block map and the list scratch (d2, then indices)
 enum { B_DESC, B_STATE, B_BLK, B_TBLK, B_X, B_Q, B_TBUCKET, B_BCOUNT, B_BSTART, B_CURSOR, B_QS, B_QJ, B_MATCH,
        B_PARTIALS, B_LIVE, B_NORMALS, B_COV_S, B_COV_T, B_NDESC, B_NKNN, B_NREC, B_NBLK, B_NTBLK, B_KDESC, B_KBLK,
-       B_KKEY, B_KIOTA, B_KSKEY, B_KSIDX, B_KSPTS, B_KTEMP, B_DPARENT, B_DFLAG, B_DSCAN, B_COLOR_DESC, B_COLOR_S, B_COLOR_T, B_SEARCH_TMP, B_COUNT };
+       B_KKEY, B_KIOTA, B_KSKEY, B_KSIDX, B_KSPTS, B_KTEMP, B_DPARENT, B_DFLAG, B_DSCAN, B_COLOR_DESC, B_COLOR_S, B_COLOR_T, B_SEARCH_TMP,
+       B_FPFH_DESC, B_FPFH_SD, B_FPFH_BLK, B_FPFH_LIST, B_COUNT };
 
 }  // namespace thip
 
@@ -47,6 +49,7 @@ struct teaser_hip_icp : thip::HandleBase {
   int32_t knn_ring_cap = thip::kIcpKnnRingCap;  // option "knn_ring_cap"
   int64_t knn_fallbacks = 0;              // option "knn_fallbacks": queries of the last call served by the whole-cloud route
   int32_t fps_resident_max = thip::kFpsResidentCap;  // option "fps_resident_max" (icp_fps.hip)
+  int64_t fpfh_list_bytes = thip::kFpfhListBytes;    // option "fpfh_list_bytes" (icp_fpfh.hip)
   ~teaser_hip_icp() {
     for (thip::DevBuf& b : buf) b.release();
     if (h_live) (void)hipHostFree(h_live);
@@ -320,6 +323,28 @@ struct KnnLayout {
 // plain self k-NN.  Leaves the descriptors in ix.
 int32_t run_self_knn(teaser_hip_icp* h, int32_t batch, const double* const* points, const int32_t* n, const int32_t* k,
                      const double* ratio, IcpIndex& ix, KnnLayout& L);
+
+// The descriptors of one normal-estimation pass over `batch` clouds; a cloud with n[b] = 0 has no blocks.
+struct NormalsPlan {
+  IcpIndex ix;
+  std::vector<IcpKnnDesc> knn;
+  std::vector<IcpNormalDesc> nd;
+  std::vector<int32_t> blk;  // hybrid blocks, then k-NN blocks
+  int n_hyb = 0, n_knn = 0;  // blocks of either kind
+  int top_hyb = 0, top_knn = 0;
+};
+
+// What a call that estimates normals on the way (icp_fpfh.hip) needs of icp_normals.hip.  check_normal_search: one
+// search record of the normals contract; `arg` names the argument in the message.  plan_normals_in_place: the plan of
+// the clouds b with estimated[b] != 0 (record rec[b]) where ALL clouds of the call lie packed one after the other in the
+// point array, the normals going to the same rows of d_nrm.  launch_normals_plan: uploads the plan (B_N*), builds the
+// index over d_q and enqueues the search launches; the caller has sized the index buffers for P.ix (index_bytes with
+// the worklist) and gives the worklist counter, one int32 on the device.
+int32_t check_normal_search(teaser_hip_icp* h, const teaser_icp_normal_search_c& r, int b, const char* arg);
+void plan_normals_in_place(teaser_hip_icp* h, NormalsPlan& P, int32_t batch, const double* const* points,
+                           const int32_t* n, const teaser_icp_normal_search_c* rec, const char* estimated);
+int32_t launch_normals_plan(teaser_hip_icp* h, const NormalsPlan& P, const double* d_q, double* d_nrm,
+                            int32_t* d_counter);
 
 // Called by icp_run_batch between the uploads and the index build of the iterations: ix is the call's index, the
 // targets lie in B_Q at its offsets.  Returns a status.

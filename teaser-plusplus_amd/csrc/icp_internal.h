@@ -22,6 +22,8 @@ constexpr int kIcpKnnRingCapMax = 16;
 constexpr int kIcpKnnScanBlocks = 2048;  // waves of the whole-cloud route (each loops over the worklist)
 constexpr int kIcpSearchR0Max = 16;      // two-cloud k-NN: a query more cells than this outside the grid skips the rings
 constexpr int kFpsResidentCap = 10240;   // farthest-point down-sampling: the resident route's compiled capacity
+constexpr int64_t kFpfhListBytes = (int64_t)512 << 20;  // Open3D-form FPFH: default bound of the neighbour-list scratch
+constexpr int64_t kFpfhListBytesMax = (int64_t)1 << 40;
 
 // IcpDesc::method / IcpDesc::kernel: the values of teaser_icp_estimation_c (include/teaser_hip.h)
 enum { kIcpMethodPoint = 0, kIcpMethodPlane = 1, kIcpMethodGicp = 2, kIcpMethodColor = 3 };
@@ -207,6 +209,18 @@ void launch_icp_search_radius(hipStream_t s, const IcpDesc* d_desc, const IcpSea
                               const double* d_qs, const int32_t* d_qj, const int32_t* d_bstart, int32_t* d_count,
                               int64_t* d_prefix, int64_t* d_total, double* d_tmp_d2, int32_t* d_tmp_j, int32_t* d_idx,
                               double* d_d2);
+// The Open3D-form FPFH (kernels_fpfh.hip; the contract "FPFH (Open3D form)" of include/teaser_hip.h).  The descriptors
+// are those of the PIECES of the clouds (n_s points from s_off of d_q; the cloud itself at t_off), the block map holds
+// n_hyb blocks of hybrid pieces, then n_knn blocks of k-NN pieces, each kind counting blk_off from its own start; the
+// lists (k slots per point at IcpSearchDesc::out_off, index -1 behind the valid entries) are the search launchers'.
+// SPFH: row s_off + i of d_spfh from the points and normals of the cloud.  FPFH: row s_off + i of d_fpfh from the SPFH
+// rows of the whole cloud, which must be complete.
+void launch_icp_fpfh_spfh(hipStream_t s, const IcpDesc* d_desc, const IcpSearchDesc* d_sd, const int32_t* d_blk_prob,
+                          int n_hyb, int n_knn, const double* d_q, const double* d_normals, const int32_t* d_list_idx,
+                          double* d_spfh);
+void launch_icp_fpfh(hipStream_t s, const IcpDesc* d_desc, const IcpSearchDesc* d_sd, const int32_t* d_blk_prob,
+                     int n_hyb, int n_knn, const int32_t* d_list_idx, const double* d_list_d2, const double* d_spfh,
+                     double* d_fpfh);
 // The information matrices of the problems whose matches (d_match, written by the mode-0 correspondence pass over the
 // same block map) and targets as given (d_q) are on the device: d_partials takes kIcpInfoSums doubles per block,
 // d_info 36 per problem (row-major 6 x 6).  kernels_icp_information.hip.

@@ -42,16 +42,6 @@ int32_t check_search(teaser_hip_icp* h, const teaser_icp_normal_search_c& r, int
   return TEASER_HIP_OK;
 }
 
-// The descriptors of one normal-estimation pass over `batch` clouds; a cloud with n[b] = 0 has no blocks.
-struct NormalsPlan {
-  IcpIndex ix;
-  std::vector<IcpKnnDesc> knn;
-  std::vector<IcpNormalDesc> nd;
-  std::vector<int32_t> blk;  // hybrid blocks, then k-NN blocks
-  int n_hyb = 0, n_knn = 0;  // blocks of either kind
-  int top_hyb = 0, top_knn = 0;
-};
-
 // Appends cloud b (n points at points[b]; n = 0: skipped) with search record r.  t_off < 0: the clouds are packed one
 // after the other; else the cloud's first point in the caller's own packing of B_Q.
 void plan_cloud(teaser_hip_icp* h, NormalsPlan& P, int b, int32_t n, const double* const* points,
@@ -162,6 +152,31 @@ int32_t auto_hook(teaser_hip_icp* h, void* ctx, const IcpIndex&) {
 }
 
 }  // namespace
+
+namespace thip {
+
+int32_t check_normal_search(teaser_hip_icp* h, const teaser_icp_normal_search_c& r, int b, const char* arg) {
+  return check_search(h, r, b, arg);
+}
+
+void plan_normals_in_place(teaser_hip_icp* h, NormalsPlan& P, int32_t batch, const double* const* points,
+                           const int32_t* n, const teaser_icp_normal_search_c* rec, const char* estimated) {
+  std::vector<int32_t> hyb, knn_blk;
+  int64_t t_off = 0;
+  for (int b = 0; b < batch; ++b) {
+    plan_cloud(h, P, b, estimated[b] ? n[b] : 0, points, rec[b], t_off, hyb, knn_blk);
+    P.nd.back().nrm_off = t_off;
+    t_off += n[b];
+  }
+  finish_plan(P, hyb, knn_blk);
+}
+
+int32_t launch_normals_plan(teaser_hip_icp* h, const NormalsPlan& P, const double* d_q, double* d_nrm,
+                            int32_t* d_counter) {
+  return launch_normals(h, P, d_q, d_nrm, nullptr, nullptr, d_counter);
+}
+
+}  // namespace thip
 
 extern "C" {
 

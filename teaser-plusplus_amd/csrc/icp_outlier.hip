@@ -103,6 +103,12 @@ int32_t teaser_hip_icp_set_option(teaser_hip_icp* h, const char* name, int64_t v
     h->fps_resident_max = (int32_t)value;
     return TEASER_HIP_OK;
   }
+  if (strcmp(name, "fpfh_list_bytes") == 0) {
+    if (value < 1 || value > kFpfhListBytesMax)
+      return fail(h, TEASER_HIP_ERR_BAD_ARG, "fpfh_list_bytes must lie in [1, " + std::to_string(kFpfhListBytesMax) + "]");
+    h->fpfh_list_bytes = value;
+    return TEASER_HIP_OK;
+  }
   if (strcmp(name, "knn_fallbacks") == 0) return fail(h, TEASER_HIP_ERR_BAD_ARG, "knn_fallbacks is read-only");
   return fail(h, TEASER_HIP_ERR_BAD_ARG, std::string("unknown ICP option ") + name);
 }
@@ -121,6 +127,10 @@ int32_t teaser_hip_icp_get_option(teaser_hip_icp* h, const char* name, int64_t* 
   }
   if (strcmp(name, "fps_resident_max") == 0) {
     *value = h->fps_resident_max;
+    return TEASER_HIP_OK;
+  }
+  if (strcmp(name, "fpfh_list_bytes") == 0) {
+    *value = h->fpfh_list_bytes;
     return TEASER_HIP_OK;
   }
   return fail(h, TEASER_HIP_ERR_BAD_ARG, std::string("unknown ICP option ") + name);

@@ -27,6 +27,7 @@
 // with -ffp-contract=off like the rest of the library: no product-add is fused by the compiler; the ONE place where the
 // reference's fixtures need fused multiply-adds -- the covariance accumulators of the normals -- says so explicitly.
 #include "internal.h"
+#include "fdet_math.h"
 #include "features_internal.h"
 
 namespace thip {
@@ -39,23 +40,7 @@ struct Nbr {
 };
 
 // ---- deterministic elementary functions (IEEE double basic operations only, fixed order) ---------
-__device__ double fdet_atan_d(double x) {  // |x| <= 1: two argument halvings, then the Taylor series
-  double t = x / (1.0 + __builtin_sqrt(1.0 + x * x));
-  t = t / (1.0 + __builtin_sqrt(1.0 + t * t));
-  const double t2 = t * t;
-  double s = 0.0;
-#pragma unroll  // (the quotients 1 / (2k + 1) fold to constants: correctly rounded at compile time as at run time)
-  for (int k = 24; k >= 0; --k) s = 1.0 / (double)(2 * k + 1) - t2 * s;
-  return 4.0 * (t * s);
-}
-__device__ double fdet_atan2_d(double y, double x) {
-  const double pi = 3.14159265358979323846;
-  if (x == 0.0 && y == 0.0) return 0.0;
-  const double ax = __builtin_fabs(x), ay = __builtin_fabs(y);
-  double a = (ax >= ay) ? fdet_atan_d(ay / ax) : pi / 2 - fdet_atan_d(ax / ay);
-  if (x < 0.0) a = pi - a;
-  return (y < 0.0) ? -a : a;
-}
+// fdet_atan_d / fdet_atan2_d: fdet_math.h, shared with the Open3D-form FPFH
 __device__ float fdet_atan2f(float y, float x) { return (float)fdet_atan2_d((double)y, (double)x); }
 __device__ float fdet_acosf(float x) {  // x in [0, 1]
   const double xd = (double)x;

@@ -172,7 +172,7 @@ def registration_fgr_based_on_feature_matching(source, target, source_feature, t
     """Open3D's registration_fgr_based_on_feature_matching (same argument order) composed on the device front-end: the
     mutual nearest-neighbour matches of the features (feature_matching_correspondences with the mutual filter, as the
     RANSAC form), the tuple test, then registration_fgr_based_on_correspondence.  The features are n x dim rows (what
-    compute_fpfh_batch returns), not Open3D's dim x n Feature.data."""
+    compute_fpfh_batch or compute_fpfh_feature returns), not Open3D's dim x n Feature.data."""
     from .ransac import feature_matching_correspondences
     pairs = feature_matching_correspondences(source_feature, target_feature, True, 3, device)
     return registration_fgr_based_on_correspondence(source, target, pairs, option, device)

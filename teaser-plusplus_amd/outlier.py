@@ -48,7 +48,7 @@ def _per_cloud(v, b, dtype, what):
 
 def set_icp_option(name, value, device=-1):
     """teaser_hip_icp_set_option on the device's ICP handle ("knn_ring_cap": 0 .. 16, default 4; "fps_resident_max":
-    0 .. 10240, the default; see fps.py).  The handle is the
+    0 .. 10240, the default; see fps.py; "fpfh_list_bytes": 1 .. 2^40, default 512 MiB; see fpfh_open3d.py).  The handle is the
     one every call of this module and of icp.py shares for that device, so the setting is global to the device and
     stays until it is set again; it changes the cost of a search, never a result."""
     from . import lib
@@ -56,7 +56,8 @@ def set_icp_option(name, value, device=-1):
 
 
 def get_icp_option(name, device=-1):
-    """teaser_hip_icp_get_option on the device's ICP handle ("knn_ring_cap", "knn_fallbacks", "fps_resident_max")."""
+    """teaser_hip_icp_get_option on the device's ICP handle ("knn_ring_cap", "knn_fallbacks", "fps_resident_max",
+    "fpfh_list_bytes")."""
     from . import lib
     v = C.c_int64(0)
     _handle(device).call(lib().teaser_hip_icp_get_option, name.encode(), C.byref(v))

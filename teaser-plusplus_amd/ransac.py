@@ -228,7 +228,7 @@ def registration_ransac_based_on_feature_matching(source, target, source_feature
                                                   checkers=(), criteria=None, seed=0, device=-1):
     """Open3D's registration_ransac_based_on_feature_matching (same argument order) composed on the device front-end:
     feature_matching_correspondences, then registration_ransac_based_on_correspondence.  The features are n x dim rows
-    (what compute_fpfh_batch returns), not Open3D's dim x n Feature.data."""
+    (what compute_fpfh_batch or compute_fpfh_feature returns), not Open3D's dim x n Feature.data."""
     pairs = feature_matching_correspondences(source_feature, target_feature, mutual_filter, ransac_n, device)
     return registration_ransac_based_on_correspondence(source, target, pairs, max_correspondence_distance,
                                                        estimation_method, ransac_n, checkers, criteria, seed, device)
