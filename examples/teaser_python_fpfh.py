@@ -14,12 +14,19 @@ on the MI355X.  Usage:
                                           [--iss [--iss-radii RS,RN]] [--fps K]
                                           [--ransac [--ransac-iterations N --ransac-seed N]]
                                           [--fgr [--fgr-tuple-test --fgr-seed N]] [--open3d-fpfh]
+                                          [--drop-boundary ANGLE]
 
 --open3d-fpfh computes the descriptors the way Open3D's global-registration scripts do, in place of the PCL form: the
 extract_fpfh helper's estimate_normals(KDTreeSearchParamHybrid(2 voxels, 30)) and compute_fpfh_feature(
 KDTreeSearchParamHybrid(5 voxels, 100)) in FP64, both clouds (with --batch all 2 K clouds) in ONE call on the GPU, the
 normals never leaving the device in between.  Everything downstream -- the matcher, --knn, --ransac, --fgr, --batch --
 takes these rows as it takes the PCL form's; --icp-plane then refines on these normals.
+
+--drop-boundary ANGLE removes the boundary points of BOTH clouds (Open3D's compute_boundary_points on the GPU: the
+normals' own neighbourhood KDTreeSearchParamHybrid(2 voxels, 30), the normals estimated inside the same call, angle
+threshold ANGLE degrees) after every other filter and before the descriptors, and prints how many points and
+correspondences remain beside the count of the same run without it.  The clouds are partial scans: along their rim the
+neighbourhood is half empty, and normals and descriptors are least reliable there.  Off by default.
 
 --remove-plane D drops the dominant plane (Open3D's segment_plane on the GPU: distance_threshold D, ransac_n 3, 1 000
 iterations, seeded by --plane-seed) from BOTH clouds after down-sampling and before FPFH, in one batched call, and
@@ -250,6 +257,9 @@ def main():
     ap.add_argument("--open3d-fpfh", action="store_true",
                     help="Open3D's descriptors (estimate_normals Hybrid(2 v, 30) + compute_fpfh_feature Hybrid(5 v, "
                          "100), FP64, one call on the GPU) in place of the PCL form")
+    ap.add_argument("--drop-boundary", type=float, default=None, metavar="ANGLE",
+                    help="drop the boundary points of both clouds (compute_boundary_points on the GPU, normals estimated "
+                         "in the call, Hybrid(2 v, 30), angle threshold in degrees, e.g. 90) before the descriptors")
     ap.add_argument("--cluster", default="", metavar="EPS,MIN_POINTS",
                     help="keep the most populous DBSCAN cluster of each cloud (cluster_dbscan on the GPU, e.g. 0.1,10)")
     a = ap.parse_args()
@@ -257,6 +267,8 @@ def main():
         ap.error("--remove-plane serves a single pair: it cannot be combined with --batch")
     if a.cluster and a.batch > 0:
         ap.error("--cluster serves a single pair: it cannot be combined with --batch")
+    if a.drop_boundary is not None and a.batch > 0:
+        ap.error("--drop-boundary serves a single pair: it cannot be combined with --batch")
     if a.fps < 0:
         ap.error("--fps takes a number of samples")
     if a.fps and a.iss:
@@ -320,15 +332,42 @@ def main():
             print("  kept cluster %d: %d points" % (largest, len(kept[-1])))
         print("clustering of both clouds: %.1f ms (one call)" % (1e3 * t_cluster))
         A, B = kept
-    t0 = time.perf_counter()
-    if a.open3d_fpfh:  # Open3D's extract_fpfh for both clouds in one call
-        (fa, _), (fb, nb) = open3d_fpfh([A, B], vox, return_normals=True)
-        print("Open3D-form FPFH: %d + %d rows of %d float64, normals and features in one call" % (len(fa), len(fb), fa.shape[1]))
-    else:
+
+    def descriptors(A, B, quiet=False):
+        if a.open3d_fpfh:  # Open3D's extract_fpfh for both clouds in one call
+            (fa, _), (fb, nb) = open3d_fpfh([A, B], vox, return_normals=True)
+            if not quiet:
+                print("Open3D-form FPFH: %d + %d rows of %d float64, normals and features in one call" % (len(fa), len(fb), fa.shape[1]))
+            return fa, fb, nb
         est = tp.FPFHEstimation()
         fa = est.computeFPFHFeatures(A, 2 * vox, 5 * vox)   # helpers.py:9-18: radii 2 and 5 voxels
         fb = est.computeFPFHFeatures(B, 2 * vox, 5 * vox)
-        nb = est.getNormals()   # the target's normals: point-to-plane ICP refines on them
+        return fa, fb, est.getNormals()   # the target's normals: point-to-plane ICP refines on them
+
+    def match(A, B, fa, fb):
+        if a.knn:
+            corr = tp.match_features_knn(fa, fb, a.knn, not a.no_mutual)   # helpers.py:19-43
+            if a.tuple_scale:
+                corr = tp.tuple_test_batch([A], [B], [corr], a.tuple_scale, a.tuple_seed)[0]
+            return [tuple(r) for r in corr.tolist()]
+        return tp.Matcher().calculateCorrespondences(A, B, fa, fb, False, True, bool(a.tuple_scale), a.tuple_scale,
+                                                     a.tuple_seed)   # helpers.py:27-43
+
+    if a.drop_boundary is not None:  # the rim of a partial scan: half-empty neighbourhoods, unreliable descriptors
+        fa, fb, _ = descriptors(A, B, quiet=True)
+        without = len(match(A, B, fa, fb))
+        t = time.perf_counter()
+        search = tp.KDTreeSearchParamHybrid(2 * vox, 30)   # the normals' own neighbourhood
+        rim = tp.compute_boundary_points_batch([np.asarray(A, dtype=np.float64), np.asarray(B, dtype=np.float64)], None,
+                                               search, a.drop_boundary, normal_search=search)
+        t_rim = time.perf_counter() - t
+        print("boundary points (Hybrid(%g, 30), angle threshold %g degrees): %d of %d / %d of %d points dropped, "
+              "%d / %d remain (%.1f ms, one call)" % (2 * vox, a.drop_boundary, rim[0].n_boundary, len(A),
+                                                      rim[1].n_boundary, len(B), len(A) - rim[0].n_boundary,
+                                                      len(B) - rim[1].n_boundary, 1e3 * t_rim))
+        A, B = A[~rim[0].mask], B[~rim[1].mask]
+    t0 = time.perf_counter()
+    fa, fb, nb = descriptors(A, B)
     full = (A, B)
     if a.iss:  # the matcher sees the keypoints only; `keys` maps its pairs back to cloud indices
         rs, rn = (float(v) for v in a.iss_radii.split(",")) if a.iss_radii else (0.0, 0.0)
@@ -347,14 +386,7 @@ def main():
         if min(map(len, keys)) < 3:
             sys.exit("fewer than 3 samples in a cloud: nothing to match")
         A, B, fa, fb = A[keys[0]], B[keys[1]], fa[keys[0]], fb[keys[1]]
-    if a.knn:
-        corr = tp.match_features_knn(fa, fb, a.knn, not a.no_mutual)   # helpers.py:19-43
-        if a.tuple_scale:
-            corr = tp.tuple_test_batch([A], [B], [corr], a.tuple_scale, a.tuple_seed)[0]
-        corr = [tuple(r) for r in corr.tolist()]
-    else:
-        corr = tp.Matcher().calculateCorrespondences(A, B, fa, fb, False, True, bool(a.tuple_scale), a.tuple_scale,
-                                                     a.tuple_seed)   # helpers.py:27-43
+    corr = match(A, B, fa, fb)
     if a.iss or a.fps:
         corr = [(int(keys[0][i]), int(keys[1][j])) for i, j in corr]
         A, B = full
@@ -367,6 +399,9 @@ def main():
     t2 = time.perf_counter()
     print("%d / %d points, %d correspondences, max clique %d" % (len(A), len(B), len(corr),
                                                                  len(solver.getInlierMaxClique())))
+    if a.drop_boundary is not None:
+        print("without --drop-boundary: %d correspondences; with it: %d; solution valid: %s"
+              % (without, len(corr), bool(sol.valid)))
     print("%sfront-end %.1f ms, registration %.1f ms" % ("" if t_ds is None else "down-sampling %.1f ms, " % (1e3 * t_ds),
                                                        1e3 * (t1 - t0), 1e3 * (t2 - t1)))
     print("R =\n%s\nt = %s" % (sol.rotation, sol.translation))

@@ -935,6 +935,54 @@ TEASER_HIP_API int32_t teaser_hip_icp_fpfh_batch(teaser_hip_icp* icp, int32_t ba
                                                  const teaser_icp_normal_search_c* normal_search,
                                                  double* const* fpfh_out, double* const* spfh_out,
                                                  double* const* normals_out);
+/* Boundary points (Open3D's PointCloud.compute_boundary_points(radius, max_nn, angle_threshold): the angle criterion of
+ * PCL's BoundaryEstimation, which PCL's ISS detector applies through setBorderRadius), batched, FP64, on the ICP handle.
+ * Per cloud: points P (n x 3 doubles), normals N (n x 3 doubles, used as given and never normalised), one search record
+ * (teaser_icp_normal_search_c: search 0 hybrid or 1 k-NN, max_nn in [2, 100], orient must be 0, ref is not read) and
+ * angle_threshold[b], a double in degrees.  Radius-only search (search 2) is refused by name for the reason the FPFH
+ * contract gives.  No product-add is fused anywhere; dot and cross are those of the FPFH contract.
+ *   list of i:    exactly the list of the FPFH contract: ascending (d2, j), i itself included, length m.  Position 0 is
+ *                 skipped WHATEVER it holds.
+ *   frame of i:   Eigen's unitOrthogonal (PCL's getCoordinateSystemOnPlane).  With n = N[i]:
+ *                   !(|n.x| <= 1e-12 |n.z|) || !(|n.y| <= 1e-12 |n.z|):
+ *                              s = 1.0 / sqrt(n.x n.x + n.y n.y);  v = (-n.y s, n.x s, 0)
+ *                   otherwise: s = 1.0 / sqrt(n.y n.y + n.z n.z);  v = (0, -n.z s, n.y s)
+ *                   u = cross(n, v)
+ *                 A component of u or v that is not finite (a zero or overflowing normal): the point is NOT a boundary
+ *                 point and its max_gap is NaN, whatever m is.
+ *   angles:       for k = 1 .. m-1:  delta = P[j_k] - P[i].  All three components zero: the angle is 0.0 (QUIRK, as in
+ *                 Open3D: a coincident neighbour counts as a direction along u).  Otherwise
+ *                 a_k = atan2(dot(v, delta), dot(u, delta)) by the deterministic formula of csrc/fdet_math.h.
+ *                 An angle that is a NaN (delta or a dot product overflowed): NOT a boundary point, max_gap is NaN.
+ *   gap:          m <= 1: NOT a boundary point, max_gap = 0.0.  Otherwise the m-1 angles are sorted in ascending order,
+ *                 max_gap = 0.0; for consecutive sorted angles d = a[t+1] - a[t], and if d > max_gap then max_gap = d;
+ *                 then, with pi = 3.14159265358979323846, d = (2.0 pi - a[last]) + a[first] under the same rule.
+ *                 The set of differences does not depend on how equal angles (+0.0 and -0.0 included) are ordered, so
+ *                 max_gap is a function of the inputs alone, whatever sort is used.
+ *   boundary:     max_gap > (angle_threshold pi) / 180.0.
+ * Nothing else is special-cased.  mask_out[b]: n[b] bytes, 0 or 1; the mask is the result and nothing is compacted.
+ * n_boundary_out[b]: the number of ones.  max_gap_out: NULL, or per cloud NULL or n doubles.  count_out: NULL, or per
+ * cloud NULL or n int32 holding m.  Empty clouds are legal.
+ * Normals inside the call: where normals[b] is NULL (or normals is NULL) and normal_search (NULL, or one record per
+ * cloud; max_nn = 0 means "none given") has a record for the cloud, the cloud's normals are first estimated on the
+ * device by the rule of teaser_hip_icp_normals_batch (any orient) and stay there; the result is bit-equal to that call
+ * followed by this one on its normals.  normals_out: NULL, or per cloud NULL or n x 3 doubles: the normals the cloud
+ * was computed with.  A cloud with neither normals nor a record: TEASER_HIP_ERR_BAD_ARG.
+ * Deterministic like every call on this handle: a cloud gives the same bits alone, at any position in any batch, run
+ * after run, for any value of "fpfh_list_bytes" (which bounds the list scratch of this call as of the FPFH call) and of
+ * "knn_ring_cap"; "knn_fallbacks" is left at 0.  Bit parity with an Open3D binary is NOT claimed: Open3D's libm and its
+ * float32 path are not ours; tests/boundary_reference.py restates this text.  The tangent basis influences the mask only
+ * through rounding at the threshold.  TEASER_HIP_ERR_BAD_ARG (argument and cloud named; the handle stays usable):
+ * non-finite points or normals; search, max_nn or orient outside their ranges; reserved != 0; a radius (or its square)
+ * that is not finite and > 0 in hybrid search; an angle_threshold that is not finite or lies outside [0, 360]; NULL
+ * where n > 0.  One stream synchronisation per call whatever the batch. */
+TEASER_HIP_API int32_t teaser_hip_icp_boundary_points_batch(teaser_hip_icp* icp, int32_t batch,
+                                                            const double* const* points, const double* const* normals,
+                                                            const int32_t* n, const teaser_icp_normal_search_c* search,
+                                                            const teaser_icp_normal_search_c* normal_search,
+                                                            const double* angle_threshold, uint8_t* const* mask_out,
+                                                            int32_t* n_boundary_out, double* const* max_gap_out,
+                                                            int32_t* const* count_out, double* const* normals_out);
 /* Outlier removal: statistical (Open3D's remove_statistical_outlier), on the ICP handle.  Per cloud, with
  * nb_neighbors in [1, TEASER_HIP_ICP_KNN_MAX] and std_ratio finite and > 0:
  *   avg[i]    = (sum of sqrt(d2) over point i's m = min(nb_neighbors, n) nearest of self k-NN, the point itself
@@ -1112,8 +1160,9 @@ TEASER_HIP_API int32_t teaser_hip_icp_farthest_point_down_sample_batch(teaser_hi
  * whole-cloud scan served.  "fps_resident_max" (0 .. 10240, the compiled capacity, which is also the default): the
  * largest cloud farthest-point down-sampling serves by its one-launch resident route; 0 sends every cloud to the
  * launch-per-round route.  "fpfh_list_bytes" (1 .. 2^40, default 512 MiB): the bound of the neighbour-list scratch of
- * teaser_hip_icp_fpfh_batch (12 bytes per point and max_nn slot); a call whose lists exceed it runs in several passes
- * and computes its lists twice; a piece of a cloud is never smaller than 64 points.  An unknown name, a value outside the range or a write to a read-only option:
+ * teaser_hip_icp_fpfh_batch and teaser_hip_icp_boundary_points_batch (12 bytes per point and max_nn slot); a call
+ * whose lists exceed it runs in several passes (the FPFH call then computes its lists twice); a piece of a cloud is
+ * never smaller than 64 points.  An unknown name, a value outside the range or a write to a read-only option:
  * TEASER_HIP_ERR_BAD_ARG, from both calls with teaser_hip_icp_last_error naming the option. */
 TEASER_HIP_API int32_t teaser_hip_icp_set_option(teaser_hip_icp* icp, const char* name, int64_t value);
 TEASER_HIP_API int32_t teaser_hip_icp_get_option(teaser_hip_icp* icp, const char* name, int64_t* value);

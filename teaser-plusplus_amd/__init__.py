@@ -138,7 +138,7 @@ EXPORTED_SYMBOLS = [
     "teaser_hip_icp_self_knn_batch", "teaser_hip_icp_remove_statistical_outliers_batch",
     "teaser_hip_icp_remove_radius_outliers_batch", "teaser_hip_icp_set_option", "teaser_hip_icp_get_option",
     "teaser_hip_icp_knn_search_batch", "teaser_hip_icp_hybrid_search_batch", "teaser_hip_icp_radius_search_batch",
-    "teaser_hip_icp_fpfh_batch",
+    "teaser_hip_icp_fpfh_batch", "teaser_hip_icp_boundary_points_batch",
     "teaser_hip_icp_iss_params_default", "teaser_hip_icp_iss_keypoints_batch",
     "teaser_hip_icp_cluster_dbscan_batch", "teaser_hip_icp_farthest_point_down_sample_batch",
     "teaser_hip_icp_information_batch", "teaser_hip_icp_information",
@@ -254,6 +254,8 @@ def lib():
     _search.declare(L)
     from . import fpfh_open3d as _fpfh_open3d
     _fpfh_open3d.declare(L)
+    from . import boundary as _boundary
+    _boundary.declare(L)
     from . import keypoints as _keypoints
     _keypoints.declare(L)
     from . import cluster as _cluster
@@ -1131,6 +1133,8 @@ from .search import (KDTreeFlann, NearestNeighborSearch, compute_nearest_neighbo
                      radius_search, radius_search_batch)
 from .fpfh_open3d import (KDTreeSearchParamRadius, compute_fpfh_feature, compute_fpfh_feature_batch,  # noqa: E402
                           extract_fpfh)
+from .boundary import (BoundaryResult, boundary_mask, compute_boundary_points,  # noqa: E402
+                       compute_boundary_points_batch)
 from .keypoints import compute_iss_keypoints, compute_iss_keypoints_batch  # noqa: E402
 from .cluster import cluster_dbscan, cluster_dbscan_batch  # noqa: E402
 from .fps import (farthest_point_down_sample, farthest_point_down_sample_batch,  # noqa: E402
@@ -1175,6 +1179,7 @@ __all__ = ["batched", "FPFHEstimation", "Matcher", "MultiDeviceSolver", "RobustR
            "radius_search_batch", "NearestNeighborSearch", "KDTreeFlann", "compute_point_cloud_distance",
            "compute_nearest_neighbor_distance",
            "compute_fpfh_feature", "compute_fpfh_feature_batch", "extract_fpfh", "KDTreeSearchParamRadius",
+           "compute_boundary_points", "compute_boundary_points_batch", "boundary_mask", "BoundaryResult",
            "compute_iss_keypoints", "compute_iss_keypoints_batch", "cluster_dbscan", "cluster_dbscan_batch",
            "farthest_point_down_sample", "farthest_point_down_sample_batch", "farthest_point_indices",
            "PoseGraph", "PoseGraphNode", "PoseGraphEdge", "GlobalOptimizationOption",

@@ -9,6 +9,8 @@
 // the lists (hybrid pieces, then k-NN pieces), then the SPFH rows.  When every SPFH row of the call is written, the
 // passes run again for the FPFH rows; a call of one pass keeps its lists, a call of several recomputes them.  A point's
 // list, SPFH row and FPFH row do not depend on the piece or the pass it falls into, so the option changes no bit.
+// The pieces, the passes and the list launches (plan_lists .. launch_lists, declared in icp_host.h) also serve
+// icp_boundary.hip.
 #include <math.h>
 #include <string.h>
 
@@ -24,16 +26,9 @@
 
 using namespace thip;
 
-namespace {
+namespace thip {
 
-// One pass: its pieces' blocks in B_FPFH_BLK from blk0 (n_hyb hybrid blocks, then n_knn k-NN blocks).
-struct FpfhPass {
-  int64_t blk0 = 0, slots = 0;
-  int n_hyb = 0, n_knn = 0;
-  std::vector<int32_t> hyb, knn;  // the pieces of either kind
-};
-
-int32_t check_fpfh_search(teaser_hip_icp* h, const teaser_icp_normal_search_c& r, int b) {
+int32_t check_list_search(teaser_hip_icp* h, const teaser_icp_normal_search_c& r, int b) {
   if (r.search == 2)
     return fail(h, TEASER_HIP_ERR_BAD_ARG, "search: radius-only search (KDTreeSearchParamRadius) is not supported, it is "
                                            "uncapped: there is no bounded sorted list to sum over" + at(b));
@@ -50,7 +45,112 @@ int32_t check_fpfh_search(teaser_hip_icp* h, const teaser_icp_normal_search_c& r
   return TEASER_HIP_OK;
 }
 
-}  // namespace
+void plan_lists(teaser_hip_icp* h, ListPlan& L, int32_t batch, const double* const* points, const int32_t* n,
+                const teaser_icp_normal_search_c* search) {
+  IcpIndex& ix = L.ix;
+  std::vector<IcpDesc>& piece = L.piece;
+  std::vector<IcpSearchDesc>& psd = L.psd;
+  std::vector<ListPass>& passes = L.passes;
+  int& top_hyb = L.top_hyb;
+  int& top_knn = L.top_knn;
+  const int64_t bound = h->fpfh_list_bytes;
+  int64_t pass_bytes = 0;
+  for (int b = 0; b < batch; ++b) {
+    const teaser_icp_normal_search_c& r = search[b];
+    double edge = r.search == 0 ? r.radius : 1.0;
+    bool rings_ok = true;
+    if (r.search == 1 && n[b] > 0) edge = knn_edge(points[b], n[b], std::min(r.max_nn, n[b]), &rings_ok);
+    const IcpDesc cloud = add_problem(ix, b, 0, n[b], points, edge, 0);
+    if (n[b] == 0) continue;
+    if (r.search == 0) top_hyb = std::max(top_hyb, r.max_nn);
+    else top_knn = std::max(top_knn, std::min(r.max_nn, n[b]));
+    // points per piece: what the bound holds, in whole blocks, and never less than one block
+    const int64_t per = std::max<int64_t>(bound / (12 * (int64_t)r.max_nn) / kIcpCovBlock, 1) * kIcpCovBlock;
+    for (int64_t start = 0; start < n[b]; start += per) {
+      const int32_t cnt = (int32_t)std::min<int64_t>(per, n[b] - start);
+      const int64_t bytes = 12 * (int64_t)cnt * r.max_nn;
+      if (passes.empty() || pass_bytes + bytes > bound) {
+        passes.emplace_back();
+        pass_bytes = 0;
+      }
+      ListPass& P = passes.back();
+      IcpDesc d = cloud;
+      d.n_s = cnt;
+      d.s_off = cloud.t_off + start;
+      d.nblk = (cnt + kIcpCovBlock - 1) / kIcpCovBlock;
+      d.blk_off = r.search == 0 ? P.n_hyb : P.n_knn;  // inside its own kind's range of the pass
+      IcpSearchDesc s;
+      memset(&s, 0, sizeof(s));
+      s.k = r.max_nn;
+      s.ring_cap = rings_ok ? h->knn_ring_cap : 0;
+      s.out_off = P.slots;
+      s.edge = r.search == 1 ? edge : 1.0;
+      (r.search == 0 ? P.hyb : P.knn).push_back((int32_t)piece.size());
+      (r.search == 0 ? P.n_hyb : P.n_knn) += d.nblk;
+      P.slots += (int64_t)cnt * r.max_nn;
+      pass_bytes += bytes;
+      piece.push_back(d);
+      psd.push_back(s);
+      L.cloud.push_back(b);
+    }
+  }
+  std::vector<int32_t>& blk = L.blk;
+  int64_t& max_slots = L.max_slots;
+  for (ListPass& P : passes) {
+    P.blk0 = (int64_t)blk.size();
+    for (const std::vector<int32_t>* kind : {&P.hyb, &P.knn})
+      for (int32_t p : *kind) blk.insert(blk.end(), (size_t)piece[(size_t)p].nblk, p);
+    max_slots = std::max(max_slots, P.slots);
+  }
+}
+
+void list_bytes(const ListPlan& L, size_t (&bytes)[B_COUNT]) {
+  bytes[B_FPFH_DESC] = sizeof(IcpDesc) * L.piece.size();
+  bytes[B_FPFH_SD] = sizeof(IcpSearchDesc) * L.psd.size();
+  bytes[B_FPFH_BLK] = sizeof(int32_t) * L.blk.size();
+  bytes[B_FPFH_LIST] = 12 * (size_t)L.max_slots;
+}
+
+int32_t upload_lists(teaser_hip_icp* h, const ListPlan& L) {
+  DevBuf* B = h->buf;
+  const struct {
+    int buf;
+    const void* src;
+    size_t n;
+  } copies[] = {{B_DESC, L.ix.desc.data(), sizeof(IcpDesc) * L.ix.desc.size()},
+                {B_TBLK, L.ix.tblk_prob.data(), sizeof(int32_t) * L.ix.tblk_prob.size()},
+                {B_FPFH_DESC, L.piece.data(), sizeof(IcpDesc) * L.piece.size()},
+                {B_FPFH_SD, L.psd.data(), sizeof(IcpSearchDesc) * L.psd.size()},
+                {B_FPFH_BLK, L.blk.data(), sizeof(int32_t) * L.blk.size()}};
+  for (const auto& cp : copies)
+    if (cp.n)
+      FCHK(h, hipMemcpyAsync(B[cp.buf].p, cp.src, cp.n, hipMemcpyHostToDevice, h->stream), "hipMemcpyAsync (inputs)");
+  return TEASER_HIP_OK;
+}
+
+int32_t launch_lists(teaser_hip_icp* h, const ListPlan& L, const ListPass& P, int32_t* counter) {
+  DevBuf* B = h->buf;
+  hipStream_t s = h->stream;
+  const IcpDesc* d_piece = B[B_FPFH_DESC].as<IcpDesc>();
+  const IcpSearchDesc* d_sd = B[B_FPFH_SD].as<IcpSearchDesc>();
+  double* list_d2 = B[B_FPFH_LIST].as<double>();
+  int32_t* list_idx = (int32_t*)(list_d2 + L.max_slots);
+  const double* d_q = B[B_Q].as<double>();
+  const int32_t* map = B[B_FPFH_BLK].as<int32_t>() + P.blk0;
+  // (the hybrid search's per-query counts are not needed: a row's valid entries end at its first index -1; they go
+  // to B_TBUCKET, which is free once the index is built)
+  launch_icp_search_hybrid(s, d_piece, d_sd, map, P.n_hyb, L.top_hyb, d_q, B[B_QS].as<double>(), B[B_QJ].as<int32_t>(),
+                           B[B_BSTART].as<int32_t>(), list_idx, list_d2, B[B_TBUCKET].as<int32_t>());
+  if (P.n_knn) {
+    FCHK(h, hipMemsetAsync(counter, 0, sizeof(int32_t), s), "hipMemsetAsync");
+    launch_icp_search_knn(s, d_piece, d_sd, map + P.n_hyb, P.n_knn, L.top_knn, d_q, d_q, B[B_QS].as<double>(),
+                          B[B_QJ].as<int32_t>(), B[B_BSTART].as<int32_t>(), list_idx, list_d2,
+                          B[B_MATCH].as<int32_t>(), counter);
+  }
+  return TEASER_HIP_OK;
+}
+
+}  // namespace thip
 
 extern "C" {
 
@@ -66,7 +166,7 @@ int32_t teaser_hip_icp_fpfh_batch(teaser_hip_icp* h, int32_t batch, const double
   std::vector<char> estimated((size_t)batch, 0);
   bool any_estimated = false, any_given = false, want_spfh = false, want_normals = false;
   for (int b = 0; b < batch; ++b) {
-    if ((rc = check_fpfh_search(h, search[b], b)) != TEASER_HIP_OK) return rc;
+    if ((rc = check_list_search(h, search[b], b)) != TEASER_HIP_OK) return rc;
     if (n[b] == 0) continue;
     if (normals && normals[b]) {
       if (!finite_points(normals[b], n[b]))
@@ -87,59 +187,11 @@ int32_t teaser_hip_icp_fpfh_batch(teaser_hip_icp* h, int32_t batch, const double
   FCHK(h, hipSetDevice(h->device), "hipSetDevice");
 
   // the clouds with the grids of the descriptor's search, and their pieces
-  IcpIndex ix;
-  std::vector<IcpDesc> piece;
-  std::vector<IcpSearchDesc> psd;
-  std::vector<FpfhPass> passes;
-  const int64_t bound = h->fpfh_list_bytes;
-  int top_hyb = 0, top_knn = 0;
-  int64_t pass_bytes = 0;
-  for (int b = 0; b < batch; ++b) {
-    const teaser_icp_normal_search_c& r = search[b];
-    double edge = r.search == 0 ? r.radius : 1.0;
-    bool rings_ok = true;
-    if (r.search == 1 && n[b] > 0) edge = knn_edge(points[b], n[b], std::min(r.max_nn, n[b]), &rings_ok);
-    const IcpDesc cloud = add_problem(ix, b, 0, n[b], points, edge, 0);
-    if (n[b] == 0) continue;
-    if (r.search == 0) top_hyb = std::max(top_hyb, r.max_nn);
-    else top_knn = std::max(top_knn, std::min(r.max_nn, n[b]));
-    // points per piece: what the bound holds, in whole blocks, and never less than one block
-    const int64_t per = std::max<int64_t>(bound / (12 * (int64_t)r.max_nn) / kIcpCovBlock, 1) * kIcpCovBlock;
-    for (int64_t start = 0; start < n[b]; start += per) {
-      const int32_t cnt = (int32_t)std::min<int64_t>(per, n[b] - start);
-      const int64_t bytes = 12 * (int64_t)cnt * r.max_nn;
-      if (passes.empty() || pass_bytes + bytes > bound) {
-        passes.emplace_back();
-        pass_bytes = 0;
-      }
-      FpfhPass& P = passes.back();
-      IcpDesc d = cloud;
-      d.n_s = cnt;
-      d.s_off = cloud.t_off + start;
-      d.nblk = (cnt + kIcpCovBlock - 1) / kIcpCovBlock;
-      d.blk_off = r.search == 0 ? P.n_hyb : P.n_knn;  // inside its own kind's range of the pass
-      IcpSearchDesc s;
-      memset(&s, 0, sizeof(s));
-      s.k = r.max_nn;
-      s.ring_cap = rings_ok ? h->knn_ring_cap : 0;
-      s.out_off = P.slots;
-      s.edge = r.search == 1 ? edge : 1.0;
-      (r.search == 0 ? P.hyb : P.knn).push_back((int32_t)piece.size());
-      (r.search == 0 ? P.n_hyb : P.n_knn) += d.nblk;
-      P.slots += (int64_t)cnt * r.max_nn;
-      pass_bytes += bytes;
-      piece.push_back(d);
-      psd.push_back(s);
-    }
-  }
-  std::vector<int32_t> blk;
-  int64_t max_slots = 1;
-  for (FpfhPass& P : passes) {
-    P.blk0 = (int64_t)blk.size();
-    for (const std::vector<int32_t>* kind : {&P.hyb, &P.knn})
-      for (int32_t p : *kind) blk.insert(blk.end(), (size_t)piece[(size_t)p].nblk, p);
-    max_slots = std::max(max_slots, P.slots);
-  }
+  ListPlan L;
+  plan_lists(h, L, batch, points, n, search);
+  const IcpIndex& ix = L.ix;
+  const std::vector<ListPass>& passes = L.passes;
+  const int64_t max_slots = L.max_slots;
 
   NormalsPlan NP;
   if (any_estimated) plan_normals_in_place(h, NP, batch, points, n, normal_search, estimated.data());
@@ -154,10 +206,7 @@ int32_t teaser_hip_icp_fpfh_batch(teaser_hip_icp* h, int32_t batch, const double
   const size_t nb = (size_t)std::max(ix.b_off, NP.ix.b_off);
   bytes[B_BCOUNT] = bytes[B_BSTART] = bytes[B_CURSOR] = sizeof(int32_t) * std::max<size_t>(nb, 1);
   bytes[B_X] = o_cnt + 8;
-  bytes[B_FPFH_DESC] = sizeof(IcpDesc) * piece.size();
-  bytes[B_FPFH_SD] = sizeof(IcpSearchDesc) * psd.size();
-  bytes[B_FPFH_BLK] = sizeof(int32_t) * blk.size();
-  bytes[B_FPFH_LIST] = 12 * (size_t)max_slots;
+  list_bytes(L, bytes);
   if ((rc = ensure_buffers(h, bytes, "hipMalloc failed (FPFH buffers)")) != TEASER_HIP_OK) return rc;
   DevBuf* B = h->buf;
   hipStream_t s = h->stream;
@@ -171,17 +220,7 @@ int32_t teaser_hip_icp_fpfh_batch(teaser_hip_icp* h, int32_t batch, const double
         memcpy(&h->cstage[(size_t)(3 * ix.desc[(size_t)b].t_off)], normals[b], 24 * (size_t)n[b]);
     FCHK(h, hipMemcpyAsync(out, h->cstage.data(), o_fpfh, hipMemcpyHostToDevice, s), "hipMemcpyAsync (normals)");
   }
-  const struct {
-    int buf;
-    const void* src;
-    size_t n;
-  } copies[] = {{B_DESC, ix.desc.data(), sizeof(IcpDesc) * ix.desc.size()},
-                {B_TBLK, ix.tblk_prob.data(), sizeof(int32_t) * ix.tblk_prob.size()},
-                {B_FPFH_DESC, piece.data(), bytes[B_FPFH_DESC]},
-                {B_FPFH_SD, psd.data(), bytes[B_FPFH_SD]},
-                {B_FPFH_BLK, blk.data(), bytes[B_FPFH_BLK]}};
-  for (const auto& cp : copies)
-    if (cp.n) FCHK(h, hipMemcpyAsync(B[cp.buf].p, cp.src, cp.n, hipMemcpyHostToDevice, s), "hipMemcpyAsync (inputs)");
+  if ((rc = upload_lists(h, L)) != TEASER_HIP_OK) return rc;
   int32_t* counter = (int32_t*)(out + o_cnt);
   if (any_estimated &&
       (rc = launch_normals_plan(h, NP, B[B_Q].as<double>(), (double*)out, counter)) != TEASER_HIP_OK)
@@ -194,27 +233,13 @@ int32_t teaser_hip_icp_fpfh_batch(teaser_hip_icp* h, int32_t batch, const double
   int32_t* list_idx = (int32_t*)(list_d2 + max_slots);
   const double* d_q = B[B_Q].as<double>();
   double* d_spfh = (double*)(out + o_spfh);
-  auto lists = [&](const FpfhPass& P) -> int32_t {
-    const int32_t* map = B[B_FPFH_BLK].as<int32_t>() + P.blk0;
-    // (the hybrid search's per-query counts are not needed: a row's valid entries end at its first index -1; they go
-    // to B_TBUCKET, which is free once the index is built)
-    launch_icp_search_hybrid(s, d_piece, d_sd, map, P.n_hyb, top_hyb, d_q, B[B_QS].as<double>(), B[B_QJ].as<int32_t>(),
-                             B[B_BSTART].as<int32_t>(), list_idx, list_d2, B[B_TBUCKET].as<int32_t>());
-    if (P.n_knn) {
-      FCHK(h, hipMemsetAsync(counter, 0, sizeof(int32_t), s), "hipMemsetAsync");
-      launch_icp_search_knn(s, d_piece, d_sd, map + P.n_hyb, P.n_knn, top_knn, d_q, d_q, B[B_QS].as<double>(),
-                            B[B_QJ].as<int32_t>(), B[B_BSTART].as<int32_t>(), list_idx, list_d2,
-                            B[B_MATCH].as<int32_t>(), counter);
-    }
-    return TEASER_HIP_OK;
-  };
-  for (const FpfhPass& P : passes) {
-    if ((rc = lists(P)) != TEASER_HIP_OK) return rc;
+  for (const ListPass& P : passes) {
+    if ((rc = launch_lists(h, L, P, counter)) != TEASER_HIP_OK) return rc;
     launch_icp_fpfh_spfh(s, d_piece, d_sd, B[B_FPFH_BLK].as<int32_t>() + P.blk0, P.n_hyb, P.n_knn, d_q,
                          (const double*)out, list_idx, d_spfh);
   }
-  for (const FpfhPass& P : passes) {
-    if (passes.size() > 1 && (rc = lists(P)) != TEASER_HIP_OK) return rc;
+  for (const ListPass& P : passes) {
+    if (passes.size() > 1 && (rc = launch_lists(h, L, P, counter)) != TEASER_HIP_OK) return rc;
     launch_icp_fpfh(s, d_piece, d_sd, B[B_FPFH_BLK].as<int32_t>() + P.blk0, P.n_hyb, P.n_knn, list_idx, list_d2, d_spfh,
                     (double*)(out + o_fpfh));
   }

@@ -1,7 +1,8 @@
 // icp_host.h -- what the host files of the ICP handle share (icp.hip: the iteration loop and covariance estimation;
 // icp_outlier.hip: self k-NN, outlier removal and the options; icp_normals.hip: normal estimation and the
 // self-estimating point-to-plane entry; icp_keypoints.hip: ISS keypoints; icp_cluster.hip: DBSCAN clustering; icp_fps.hip: farthest-point down-sampling; icp_color.hip: Colored ICP;
-// icp_search.hip: neighbour search between two clouds; icp_fpfh.hip: the Open3D-form FPFH): the handle and its buffers, and the scaffold
+// icp_search.hip: neighbour search between two clouds; icp_fpfh.hip: the Open3D-form FPFH and the neighbour lists in
+// pieces; icp_boundary.hip: boundary points): the handle and its buffers, and the scaffold
 // of a cloud call -- the entry checks (begin_cloud_call), the per-call index under construction (IcpIndex,
 // add_problem), the sizes of the index buffers by name (index_bytes, ensure_buffers), the packing and the uploads
 // (upload_points, upload_inputs), the index build (launch_index), the one copy back (copy_back, read_fallbacks) and
@@ -32,11 +33,12 @@ namespace thip {
 // source point, and per target point the {gradient, intensity} record; its gradient pass keeps its descriptors, records
 // and block maps in B_N* (a coloured call estimates no normals).  B_SEARCH_TMP: the radius search's rows before they are
 // ordered (icp_search.hip).  B_FPFH_*: the Open3D-form FPFH (icp_fpfh.hip): the pieces' descriptors, search records and
-// block map and the list scratch (d2, then indices)
+// block map and the list scratch (d2, then indices); boundary points (icp_boundary.hip) run on the same four and add
+// B_BND_DESC, the pieces' IcpBoundaryDesc records
 enum { B_DESC, B_STATE, B_BLK, B_TBLK, B_X, B_Q, B_TBUCKET, B_BCOUNT, B_BSTART, B_CURSOR, B_QS, B_QJ, B_MATCH,
        B_PARTIALS, B_LIVE, B_NORMALS, B_COV_S, B_COV_T, B_NDESC, B_NKNN, B_NREC, B_NBLK, B_NTBLK, B_KDESC, B_KBLK,
        B_KKEY, B_KIOTA, B_KSKEY, B_KSIDX, B_KSPTS, B_KTEMP, B_DPARENT, B_DFLAG, B_DSCAN, B_COLOR_DESC, B_COLOR_S, B_COLOR_T, B_SEARCH_TMP,
-       B_FPFH_DESC, B_FPFH_SD, B_FPFH_BLK, B_FPFH_LIST, B_COUNT };
+       B_FPFH_DESC, B_FPFH_SD, B_FPFH_BLK, B_FPFH_LIST, B_BND_DESC, B_COUNT };
 
 }  // namespace thip
 
@@ -345,6 +347,39 @@ void plan_normals_in_place(teaser_hip_icp* h, NormalsPlan& P, int32_t batch, con
                            const int32_t* n, const teaser_icp_normal_search_c* rec, const char* estimated);
 int32_t launch_normals_plan(teaser_hip_icp* h, const NormalsPlan& P, const double* d_q, double* d_nrm,
                             int32_t* d_counter);
+
+// The neighbour lists of a call that walks every point's sorted list (icp_fpfh.hip, icp_boundary.hip), in pieces under
+// the option "fpfh_list_bytes".  One pass: its pieces' blocks in B_FPFH_BLK from blk0 (n_hyb hybrid blocks, then n_knn
+// k-NN blocks).
+struct ListPass {
+  int64_t blk0 = 0, slots = 0;
+  int n_hyb = 0, n_knn = 0;
+  std::vector<int32_t> hyb, knn;  // the pieces of either kind
+};
+// The plan of a call: the clouds with the grids of the search (ix), their pieces (an IcpDesc of n_s points from s_off,
+// the cloud itself at t_off, and an IcpSearchDesc of max_nn slots per row from out_off of the list scratch), the passes
+// and the block map of all passes.
+struct ListPlan {
+  IcpIndex ix;
+  std::vector<IcpDesc> piece;
+  std::vector<IcpSearchDesc> psd;
+  std::vector<int32_t> cloud;  // the cloud of every piece
+  std::vector<ListPass> passes;
+  std::vector<int32_t> blk;
+  int64_t max_slots = 1;  // the list scratch holds this many (d2, index) slots
+  int top_hyb = 0, top_knn = 0;
+};
+// icp_fpfh.hip.  check_list_search: one search record of such a call (hybrid or k-NN, max_nn in [2, 100], not oriented;
+// the argument is named "search").  plan_lists: the plan of the checked clouds.  list_bytes: the sizes of B_FPFH_*.
+// upload_lists: enqueues the uploads of the plan (B_DESC, B_TBLK, B_FPFH_DESC / _SD / _BLK).  launch_lists: enqueues the
+// search launches that fill the lists of one pass (d2 at B_FPFH_LIST, the indices max_slots doubles behind); counter:
+// the worklist counter of the k-NN search, one int32 on the device.
+int32_t check_list_search(teaser_hip_icp* h, const teaser_icp_normal_search_c& r, int b);
+void plan_lists(teaser_hip_icp* h, ListPlan& L, int32_t batch, const double* const* points, const int32_t* n,
+                const teaser_icp_normal_search_c* search);
+void list_bytes(const ListPlan& L, size_t (&bytes)[B_COUNT]);
+int32_t upload_lists(teaser_hip_icp* h, const ListPlan& L);
+int32_t launch_lists(teaser_hip_icp* h, const ListPlan& L, const ListPass& P, int32_t* counter);
 
 // Called by icp_run_batch between the uploads and the index build of the iterations: ix is the call's index, the
 // targets lie in B_Q at its offsets.  Returns a status.

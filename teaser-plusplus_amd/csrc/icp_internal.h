@@ -106,6 +106,13 @@ struct IcpNormalDesc {
   double ref[3];
 };
 
+// One piece of a boundary-point call (kernels_boundary.hip), beside its IcpDesc and IcpSearchDesc.
+struct IcpBoundaryDesc {
+  double threshold;   // (angle_threshold pi) / 180.0
+  int32_t cloud;      // the cloud of the piece: its entry of the n_boundary counters
+  int32_t pad;
+};
+
 // One cloud of a colour-gradient pass, beside its IcpDesc (the cloud is the descriptor's "target": the grid and r2 of the
 // gradient radius; blk_off / nblk count its blocks of kIcpCovBlock points).
 struct IcpGradDesc {
@@ -140,6 +147,20 @@ __host__ __device__ inline int64_t icp_bucket(int64_t cx, int64_t cy, int64_t cz
   k ^= k >> 32;
   return (int64_t)(k & (uint64_t)mask);
 }
+
+#if defined(__HIPCC__)
+// The point of this thread's map block in a launch over list pieces (kernels_fpfh.hip, kernels_boundary.hip: n_hyb blocks
+// of hybrid pieces, then the blocks of the k-NN pieces, each kind counting blk_off from its own start): the piece p and
+// the first point i0 of the block inside it.
+__device__ __forceinline__ int list_block_piece(const IcpDesc* __restrict__ descs, const int32_t* __restrict__ blk_prob,
+                                                int n_hyb, int64_t* i0) {
+  const int blk = (int)blockIdx.x;
+  const int p = blk_prob[blk];
+  const int rel = blk < n_hyb ? blk : blk - n_hyb;
+  *i0 = (int64_t)(rel - descs[p].blk_off) * kIcpCovBlock;
+  return p;
+}
+#endif
 
 void launch_icp_index(hipStream_t s, const IcpDesc* d_desc, const int32_t* d_tblk_prob, int n_tblk, int batch,
                       const double* d_q, int32_t* d_tbucket, int32_t* d_bcount, int32_t* d_bstart,
@@ -221,6 +242,13 @@ void launch_icp_fpfh_spfh(hipStream_t s, const IcpDesc* d_desc, const IcpSearchD
 void launch_icp_fpfh(hipStream_t s, const IcpDesc* d_desc, const IcpSearchDesc* d_sd, const int32_t* d_blk_prob,
                      int n_hyb, int n_knn, const int32_t* d_list_idx, const double* d_list_d2, const double* d_spfh,
                      double* d_fpfh);
+// Boundary points (kernels_boundary.hip; the contract "Boundary points" of include/teaser_hip.h) over the pieces and
+// lists of the FPFH launches above, with an IcpBoundaryDesc per piece: for point s_off + i the byte d_mask, and where the
+// arrays are not NULL its max_gap and its list length m; the boundary points of cloud c are ADDED to d_n_boundary[c].
+void launch_icp_boundary(hipStream_t s, const IcpDesc* d_desc, const IcpSearchDesc* d_sd, const IcpBoundaryDesc* d_bd,
+                         const int32_t* d_blk_prob, int n_hyb, int n_knn, const double* d_q, const double* d_normals,
+                         const int32_t* d_list_idx, uint8_t* d_mask, double* d_max_gap, int32_t* d_count,
+                         int32_t* d_n_boundary);
 // The information matrices of the problems whose matches (d_match, written by the mode-0 correspondence pass over the
 // same block map) and targets as given (d_q) are on the device: d_partials takes kIcpInfoSums doubles per block,
 // d_info 36 per problem (row-major 6 x 6).  kernels_icp_information.hip.

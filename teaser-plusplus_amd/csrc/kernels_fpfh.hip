@@ -18,23 +18,13 @@
 
 namespace thip {
 
-// The point of this thread's map block: the piece p and the first point i0 of the block inside it.
-__device__ __forceinline__ int fpfh_block_piece(const IcpDesc* __restrict__ descs, const int32_t* __restrict__ blk_prob,
-                                                int n_hyb, int64_t* i0) {
-  const int blk = (int)blockIdx.x;
-  const int p = blk_prob[blk];
-  const int rel = blk < n_hyb ? blk : blk - n_hyb;
-  *i0 = (int64_t)(rel - descs[p].blk_off) * kIcpCovBlock;
-  return p;
-}
-
 __global__ __launch_bounds__(kIcpCovBlock) void icp_fpfh_spfh_kernel(
     const IcpDesc* __restrict__ descs, const IcpSearchDesc* __restrict__ sds, const int32_t* __restrict__ blk_prob,
     int n_hyb, const double* __restrict__ q, const double* __restrict__ normals, const int32_t* __restrict__ list_idx,
     double* __restrict__ spfh) {
   __shared__ double hist[kFpfhDim][kIcpCovBlock];  // bin-major: lane l owns hist[.][l]
   int64_t i0;
-  const int p = fpfh_block_piece(descs, blk_prob, n_hyb, &i0);
+  const int p = list_block_piece(descs, blk_prob, n_hyb, &i0);
   const IcpDesc& d = descs[p];
   const IcpSearchDesc& sd = sds[p];
   const int lane = threadIdx.x;
@@ -58,7 +48,7 @@ __global__ __launch_bounds__(kIcpCovBlock* kFpfhWaves) void icp_fpfh_kernel(
     int n_hyb, const int32_t* __restrict__ list_idx, const double* __restrict__ list_d2,
     const double* __restrict__ spfh, double* __restrict__ fpfh) {
   int64_t i0;
-  const int p = fpfh_block_piece(descs, blk_prob, n_hyb, &i0);
+  const int p = list_block_piece(descs, blk_prob, n_hyb, &i0);
   const IcpDesc& d = descs[p];
   const IcpSearchDesc& sd = sds[p];
   const int lane = threadIdx.x % kIcpCovBlock, wave = threadIdx.x / kIcpCovBlock;
