@@ -983,6 +983,103 @@ TEASER_HIP_API int32_t teaser_hip_icp_boundary_points_batch(teaser_hip_icp* icp,
                                                             const double* angle_threshold, uint8_t* const* mask_out,
                                                             int32_t* n_boundary_out, double* const* max_gap_out,
                                                             int32_t* const* count_out, double* const* normals_out);
+/* Depth frames (Open3D's PointCloud.create_from_depth_image / create_from_rgbd_image and, the other way,
+ * t.geometry.PointCloud.project_to_depth_image / project_to_rgbd_image), batched, FP64, on the ICP handle.  The text below
+ * IS the contract; it restates Open3D and fixes what Open3D leaves to a race.  No product-add is fused and every sum is
+ * taken left to right as written.  tests/rgbd_reference.py restates this text; bit parity with an Open3D binary is NOT
+ * claimed.
+ *
+ * teaser_hip_icp_unproject_depth_batch: frames to clouds.  Per problem one record teaser_icp_frame_c, a depth image
+ * depth[b] (height rows of depth_row_bytes bytes; uint16 or float32 samples) and, with color_format != 0, a colour image
+ * color[b] (height rows of color_row_bytes bytes).  Rows may be padded; only the first width samples of a row are read.
+ *   visited pixels: i = 0, stride, 2 stride, ... < height and inside that j = 0, stride, ... < width, in that row-major
+ *                   order: ceil(height / stride) ceil(width / stride) of them.
+ *   depth:          a uint16 sample d gives zf = (float)d / (float)depth_scale in float32, then zf = 0 if
+ *                   (double)zf >= depth_trunc.  A float32 sample is zf as it is: neither scale nor truncation applies
+ *                   (as in Open3D).  The pixel is valid iff zf > 0: NaN and negative samples are invalid, +inf is valid.
+ *   point:          z = (double)zf;  x = (((double)j - cx) z) / fx;  y = (((double)i - cy) z) / fy;
+ *                   p_r = ((M[r][0] x + M[r][1] y) + M[r][2] z) + M[r][3] for r = 0, 1, 2 with M = camera_pose, the
+ *                   row-major 4 x 4 camera-to-world matrix (Open3D's extrinsic.inverse(); row 3 is not read).
+ *   colour:         three doubles.  Format 1 (uint8 x 3, RGB): (R, G, B) / 255.0.  Format 1 with intensity = 1:
+ *                   I = ((0.2990f R + 0.5870f G) + 0.1140f B) / 255.0f in float32 (R, G, B converted to float32 first), then
+ *                   (I, I, I).  Format 2 (float32 x 1): (I, I, I).  Format 3 (float32 x 3): as it is.
+ *   NaN:            a component of a point or a colour that is a NaN is stored as the quiet NaN 0x7ff8000000000000.
+ *   rows:           valid_only = 1: one row per VALID visited pixel, packed in visiting order; count_out[b] is their number.
+ *                   valid_only = 0: one row per visited pixel; an invalid pixel's point is (NaN, NaN, NaN), its colour is
+ *                   computed all the same; count_out[b] is the number of visited pixels.
+ * points_out[b]: room for the visited-pixel count x 3 doubles (required where that count is > 0).  colors_out: NULL, or
+ * per problem NULL or as many rows (only with color_format != 0).  pixel_out: NULL, or per problem NULL or as many
+ * int32: i width + j of every row.  Rows behind count_out[b] are not written.  A frame with width or height 0 is legal
+ * and gives count 0; an empty batch and a batch of empty frames return OK without touching the device.
+ * TEASER_HIP_ERR_BAD_ARG (argument and problem named; the handle stays usable): a depth_format outside {0, 1} or a
+ * color_format outside {0 .. 3}; intensity outside {0, 1} or set without color_format 1; valid_only outside {0, 1};
+ * reserved != 0; stride < 1; fx or fy zero or not finite; a pose, cx, cy, depth_scale or depth_trunc that is not finite;
+ * depth_scale <= 0; row bytes below a row's size; width or height negative or above 16384; more than 2^31 - 1 visited
+ * pixels in one call; NULL where something is required; colors_out[b] given for a frame without colour.
+ *
+ * teaser_hip_icp_project_depth_batch: clouds to frames.  Per problem points (n x 3 doubles), optionally colours (n x 3
+ * doubles) and one record teaser_icp_projection_c; E = extrinsic, the row-major 4 x 4 world-to-camera matrix, used as
+ * given (row 3 is not read).  For point k = (X, Y, Z):
+ *   c_r = ((E[r][0] X + E[r][1] Y) + E[r][2] Z) + E[r][3] for r = 0, 1, 2;  (xc, yc, zc) = (c_0, c_1, c_2)
+ *   skipped unless zc > 0 and zc <= depth_max (a NaN is skipped)
+ *   u = (fx xc) / zc + cx;  v = (fy yc) / zc + cy;  skipped unless both are finite and below 2^31 in magnitude
+ *   ui = round(u), vi = round(v), halves away from zero;  skipped unless 0 <= ui < width and 0 <= vi < height
+ *   d = (float)(zc depth_scale);  skipped if d is not finite
+ *   winner:  pixel (vi, ui) keeps the point with the smallest d and, among equal d, the smallest k (Open3D leaves this to
+ *            a race).
+ * depth_out[b]: height x width float32, the winner's d, 0 where no point landed (required where the image has pixels).
+ * color_out: NULL, or per problem NULL or height x width x 3 float32: the winner's colour rounded to float32, 0 where
+ * empty (only for a problem with colours).  index_out: NULL, or per problem NULL or height x width int32: the winner's
+ * k, -1 where empty.  n_hit_out[b] (required): the number of non-empty pixels.  Images are dense, without row padding.
+ * TEASER_HIP_ERR_BAD_ARG: as above for width, height, fx, fy, cx, cy, the matrix, depth_scale and (in place of
+ * depth_trunc) depth_max, for more than 2^31 - 1 pixels in one call and for NULL; n < 0; non-finite points or colours;
+ * color_out[b] given for a problem without colours.
+ *
+ * Both calls are deterministic like every call on this handle: a problem gives the same bits alone, at any position in
+ * any batch, run after run.  The number of launches depends neither on the data nor on the batch; one stream
+ * synchronisation per call. */
+typedef struct teaser_icp_frame_c {
+  int32_t width, height;
+  int32_t depth_format;     /* 0 uint16, 1 float32 */
+  int32_t color_format;     /* 0 none, 1 uint8 x 3 (RGB), 2 float32 x 1, 3 float32 x 3 */
+  int64_t depth_row_bytes;  /* bytes from one row of the depth image to the next */
+  int64_t color_row_bytes;  /* likewise for the colour image; not read with color_format 0 */
+  int32_t intensity;        /* 1: a format-1 colour becomes its float32 intensity */
+  int32_t stride;           /* every stride-th row and column is visited (default 1) */
+  int32_t valid_only;       /* 1 (default): only valid pixels give rows */
+  int32_t reserved;         /* must be 0 */
+  double fx, fy, cx, cy;
+  double camera_pose[16];   /* row-major, camera to world (default: identity) */
+  double depth_scale;       /* default 1000.0 */
+  double depth_trunc;       /* default 1000.0 */
+} teaser_icp_frame_c;
+typedef struct teaser_icp_projection_c {
+  int32_t width, height;
+  double fx, fy, cx, cy;
+  double extrinsic[16];     /* row-major, world to camera */
+  double depth_scale;
+  double depth_max;
+} teaser_icp_projection_c;
+#ifdef __cplusplus
+static_assert(sizeof(teaser_icp_frame_c) == 224, "teaser_icp_frame_c is 224 bytes");
+static_assert(sizeof(teaser_icp_projection_c) == 184, "teaser_icp_projection_c is 184 bytes");
+#else
+_Static_assert(sizeof(teaser_icp_frame_c) == 224, "teaser_icp_frame_c is 224 bytes");
+_Static_assert(sizeof(teaser_icp_projection_c) == 184, "teaser_icp_projection_c is 184 bytes");
+#endif
+/* Zeroes the record and sets the defaults noted beside the fields (the sizes, formats, row bytes and intrinsics are the
+ * caller's to fill). */
+TEASER_HIP_API int32_t teaser_hip_icp_frame_default(teaser_icp_frame_c* frame);
+TEASER_HIP_API int32_t teaser_hip_icp_unproject_depth_batch(teaser_hip_icp* icp, int32_t batch,
+                                                            const teaser_icp_frame_c* frames, const void* const* depth,
+                                                            const void* const* color, int32_t* count_out,
+                                                            double* const* points_out, double* const* colors_out,
+                                                            int32_t* const* pixel_out);
+TEASER_HIP_API int32_t teaser_hip_icp_project_depth_batch(teaser_hip_icp* icp, int32_t batch,
+                                                          const double* const* points, const double* const* colors,
+                                                          const int32_t* n, const teaser_icp_projection_c* cameras,
+                                                          float* const* depth_out, float* const* color_out,
+                                                          int32_t* const* index_out, int32_t* n_hit_out);
 /* Outlier removal: statistical (Open3D's remove_statistical_outlier), on the ICP handle.  Per cloud, with
  * nb_neighbors in [1, TEASER_HIP_ICP_KNN_MAX] and std_ratio finite and > 0:
  *   avg[i]    = (sum of sqrt(d2) over point i's m = min(nb_neighbors, n) nearest of self k-NN, the point itself

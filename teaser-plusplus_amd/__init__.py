@@ -139,6 +139,7 @@ EXPORTED_SYMBOLS = [
     "teaser_hip_icp_remove_radius_outliers_batch", "teaser_hip_icp_set_option", "teaser_hip_icp_get_option",
     "teaser_hip_icp_knn_search_batch", "teaser_hip_icp_hybrid_search_batch", "teaser_hip_icp_radius_search_batch",
     "teaser_hip_icp_fpfh_batch", "teaser_hip_icp_boundary_points_batch",
+    "teaser_hip_icp_frame_default", "teaser_hip_icp_unproject_depth_batch", "teaser_hip_icp_project_depth_batch",
     "teaser_hip_icp_iss_params_default", "teaser_hip_icp_iss_keypoints_batch",
     "teaser_hip_icp_cluster_dbscan_batch", "teaser_hip_icp_farthest_point_down_sample_batch",
     "teaser_hip_icp_information_batch", "teaser_hip_icp_information",
@@ -256,6 +257,8 @@ def lib():
     _fpfh_open3d.declare(L)
     from . import boundary as _boundary
     _boundary.declare(L)
+    from . import rgbd as _rgbd
+    _rgbd.declare(L)
     from . import keypoints as _keypoints
     _keypoints.declare(L)
     from . import cluster as _cluster
@@ -1135,6 +1138,11 @@ from .fpfh_open3d import (KDTreeSearchParamRadius, compute_fpfh_feature, compute
                           extract_fpfh)
 from .boundary import (BoundaryResult, boundary_mask, compute_boundary_points,  # noqa: E402
                        compute_boundary_points_batch)
+from .rgbd import (PinholeCameraIntrinsic, DepthCloud, DepthProjection, unproject_depth_batch,  # noqa: E402
+                   project_depth_batch, create_point_cloud_from_depth_image,
+                   create_point_cloud_from_depth_image_batch, create_point_cloud_from_rgbd_image,
+                   create_point_cloud_from_rgbd_image_batch, project_to_depth_image, project_to_depth_image_batch,
+                   project_to_rgbd_image, project_to_rgbd_image_batch)
 from .keypoints import compute_iss_keypoints, compute_iss_keypoints_batch  # noqa: E402
 from .cluster import cluster_dbscan, cluster_dbscan_batch  # noqa: E402
 from .fps import (farthest_point_down_sample, farthest_point_down_sample_batch,  # noqa: E402
@@ -1180,6 +1188,10 @@ __all__ = ["batched", "FPFHEstimation", "Matcher", "MultiDeviceSolver", "RobustR
            "compute_nearest_neighbor_distance",
            "compute_fpfh_feature", "compute_fpfh_feature_batch", "extract_fpfh", "KDTreeSearchParamRadius",
            "compute_boundary_points", "compute_boundary_points_batch", "boundary_mask", "BoundaryResult",
+           "PinholeCameraIntrinsic", "DepthCloud", "DepthProjection", "unproject_depth_batch", "project_depth_batch",
+           "create_point_cloud_from_depth_image", "create_point_cloud_from_depth_image_batch",
+           "create_point_cloud_from_rgbd_image", "create_point_cloud_from_rgbd_image_batch", "project_to_depth_image",
+           "project_to_depth_image_batch", "project_to_rgbd_image", "project_to_rgbd_image_batch",
            "compute_iss_keypoints", "compute_iss_keypoints_batch", "cluster_dbscan", "cluster_dbscan_batch",
            "farthest_point_down_sample", "farthest_point_down_sample_batch", "farthest_point_indices",
            "PoseGraph", "PoseGraphNode", "PoseGraphEdge", "GlobalOptimizationOption",

@@ -249,6 +249,22 @@ void launch_icp_boundary(hipStream_t s, const IcpDesc* d_desc, const IcpSearchDe
                          const int32_t* d_blk_prob, int n_hyb, int n_knn, const double* d_q, const double* d_normals,
                          const int32_t* d_list_idx, uint8_t* d_mask, double* d_max_gap, int32_t* d_count,
                          int32_t* d_n_boundary);
+// Depth frames (kernels_rgbd.hip; the contract "Depth frames" of include/teaser_hip.h; the records are those of
+// icp_rgbd_device.h).  Unprojection: three launches over the n_tiles tiles of all frames (d_tile_frame: the frame of
+// every tile) -- the rows of every tile into d_tile_count, their exclusive sums per frame into d_tile_start and the
+// frames' counts into d_count, then the rows themselves at the frames' offsets of d_points / d_colors / d_pixels.
+struct IcpFrameDesc;
+struct IcpProjDesc;
+void launch_icp_rgbd_unproject(hipStream_t s, const IcpFrameDesc* d_frames, const int32_t* d_tile_frame, int n_tiles,
+                               int batch, const unsigned char* d_in, int32_t* d_tile_count, int32_t* d_tile_start,
+                               int32_t* d_count, double* d_points, double* d_colors, int32_t* d_pixels);
+// Projection: the scatter over n_blk blocks of points into the key image (filled with ones by the caller), then the
+// resolve over n_tiles blocks of pixels: depth, and where a problem asks for them colour and index; the non-empty pixels
+// of problem b are ADDED to d_n_hit[b].
+void launch_icp_rgbd_project(hipStream_t s, const IcpProjDesc* d_desc, const int32_t* d_blk_prob, int n_blk,
+                             const int32_t* d_tile_prob, int n_tiles, const double* d_points, const double* d_colors,
+                             uint64_t* d_keys, float* d_depth, float* d_color_img, int32_t* d_index_img,
+                             int32_t* d_n_hit);
 // The information matrices of the problems whose matches (d_match, written by the mode-0 correspondence pass over the
 // same block map) and targets as given (d_q) are on the device: d_partials takes kIcpInfoSums doubles per block,
 // d_info 36 per problem (row-major 6 x 6).  kernels_icp_information.hip.
