@@ -163,7 +163,12 @@ int tim_probe_worklist(const void* d_prep, const void* d_work, int64_t work_cap,
                        unsigned int* seg_counts);  // diagnostic: scripts/probe/k1_probe
 // writes the per-problem worklist segments into the host-staged (otherwise zero) prep block of the header upload
 int64_t tim_prep_fill_segments(void* host_prep, const int32_t* n, int batch);
-// phase 1 also leaves the vertex degrees in d_deg (row popcounts accumulated by the kernel)
+// phase 1 also leaves the vertex degrees in d_deg (row popcounts accumulated by the kernel).
+// phase: 0 pre-pass, 1 K1, 2 fix-up; 1 and 2 take kTimUpperOnly on top when nobody behind them but the degree closure
+// reads the bitmap: K1 then leaves the lower triangle (row r, words in front of r / 64) as an earlier batch left it,
+// and kTimMirror (all problems) / kTimMirrorOpen (those the closure left open) rebuild it from the upper one for every
+// other reader.
+constexpr int kTimUpperOnly = 8, kTimMirror = 3, kTimMirrorOpen = 4;
 void launch_tim_graph_mfma(hipStream_t s, int phase, const ProbDesc* d_desc, int batch, int max_n,
                            int64_t total_tiles, const double* d_src, const double* d_dst,
                            void* d_pk, void* d_prep, void* d_work, int64_t work_cap,

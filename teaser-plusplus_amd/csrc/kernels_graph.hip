@@ -17,6 +17,7 @@
 #include <cstdlib>
 
 #include "internal.h"
+#include "fixup_item.h"
 #include "fixup_regions.h"
 #include "k1_consts.h"
 #include "wave_utils.h"
@@ -568,7 +569,7 @@ __global__ void tim_prep_consts_kernel(TimPrep* __restrict__ prep, int batch, do
   prep[p].use_mfma = c.use_mfma;
 }
 
-constexpr unsigned long long kGroupItem = 1ull << 63;  // worklist item: 16 rows of one column (tim_fixup_group_kernel)
+// worklist item: 16 rows of one column and their provisional bits (fixup_item.h; tim_fixup_group_kernel)
 
 // The product's instantiation (launch_tim_graph_mfma); the lab build (scripts/probe/k1_lab) times the others.
 constexpr bool kK1Pipe = false, kK1Plain = true;
@@ -587,7 +588,11 @@ constexpr int kK1Chunks = 1, kK1Occ = 3;
 // accesses per column tile: 1.01 ms packed, 1.26 ms plain (profiles/r5p) -- the fourth wave needs a kernel with a
 // smaller live set (one accumulator set, row operands in LDS), not a register cap.
 // CHUNKS: column chunks (of kMfmaColTiles tiles) a block walks with the same four waves.
-template <bool PIPE, bool PLAIN, int OCC, int CHUNKS>
+// LOWER: the transposed words (the bitmap's lower triangle) are stored.  Without it the flush behind the loop still
+// counts them for the degrees and issues neither of their stores: a bitmap row r is then valid from word r / 64 on, and
+// what lies in front of it is whatever an earlier batch left there.  The route whose only reader of the bitmap is the
+// degree closure runs so (solver.hip); tim_mirror_lower_kernel rebuilds the lower triangle for whoever else reads it.
+template <bool PIPE, bool PLAIN, int OCC, int CHUNKS, bool LOWER>
 __global__ __launch_bounds__(256, OCC) void tim_graph_mfma3_kernel(
     const ProbDesc* __restrict__ descs, const double* __restrict__ src,
     const double* __restrict__ dst, const TimOperandTile2* __restrict__ ops, const TimPrep* __restrict__ prep,
@@ -938,8 +943,10 @@ __global__ __launch_bounds__(256, OCC) void tim_graph_mfma3_kernel(
         if (Jc0 > I0 + 3 && I0 + 3 < T) {  // (block-uniform) the chunk lies strictly right of all four row tiles
           const int cnt = (__builtin_popcount(lo.x) + __builtin_popcount(lo.y)) + (__builtin_popcount(lo.z) + __builtin_popcount(lo.w)) +
                           (__builtin_popcount(hi.x) + __builtin_popcount(hi.y)) + (__builtin_popcount(hi.z) + __builtin_popcount(hi.w));
-          __builtin_amdgcn_raw_buffer_store_b128(u32x4{lo.x, lo.y, lo.z, lo.w}, bm_rsrc, rowok ? base : kOobOffset, 0, 0);
-          __builtin_amdgcn_raw_buffer_store_b128(u32x4{hi.x, hi.y, hi.z, hi.w}, bm_rsrc, rowok ? base + 16u : kOobOffset, 0, 0);
+          if (LOWER) {
+            __builtin_amdgcn_raw_buffer_store_b128(u32x4{lo.x, lo.y, lo.z, lo.w}, bm_rsrc, rowok ? base : kOobOffset, 0, 0);
+            __builtin_amdgcn_raw_buffer_store_b128(u32x4{hi.x, hi.y, hi.z, hi.w}, bm_rsrc, rowok ? base + 16u : kOobOffset, 0, 0);
+          }
           __builtin_amdgcn_raw_ptr_buffer_atomic_add_i32(cnt, deg_rsrc, (rowok && cnt) ? (unsigned int)j * 4u : kOobOffset, 0, 0);
           continue;
         }
@@ -948,7 +955,8 @@ __global__ __launch_bounds__(256, OCC) void tim_graph_mfma3_kernel(
         const unsigned int w32[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
         int cnt = 0;
         for (int k = 0; k < 4; ++k) cnt += ok[k] ? __builtin_popcount(w32[2 * k]) + __builtin_popcount(w32[2 * k + 1]) : 0;
-        if (ok[3]) {  // (ok[3] implies the other three)
+        if (!LOWER) {  // (counted for the degrees, not stored)
+        } else if (ok[3]) {  // (ok[3] implies the other three)
           __builtin_amdgcn_raw_buffer_store_b128(u32x4{lo.x, lo.y, lo.z, lo.w}, bm_rsrc, base, 0, 0);
           __builtin_amdgcn_raw_buffer_store_b128(u32x4{hi.x, hi.y, hi.z, hi.w}, bm_rsrc, base + 16u, 0, 0);
         } else {
@@ -1004,7 +1012,6 @@ __global__ __launch_bounds__(256, OCC) void tim_graph_mfma3_kernel(
           if (lane == 0) states[blockIdx.y].k1_overflow = 1;
         } else {
           int kk = base;
-          const unsigned long long hi = kGroupItem | ((unsigned long long)blockIdx.y << 32);
 #pragma nounroll
           while (vf) {
             const int pos = 31 - __builtin_clz(vf);
@@ -1013,7 +1020,11 @@ __global__ __launch_bounds__(256, OCC) void tim_graph_mfma3_kernel(
             const int ct = ((pos >> 1) & 1) ^ 1, rt = (pos & 1) ^ 1;
             const unsigned int rowp = (unsigned int)(I * 64 + 32 * rt + 4 * h);
             const unsigned int colp = (unsigned int)(J * 64 + 32 * ct + c);
-            wbuf[kk++] = hi | ((unsigned long long)rowp << 16) | (unsigned long long)colp;
+            // the item's 16 provisional bits: the column's transposed word is still parked in lds_tr (its flush only
+            // read it; a diagonal tile parks zero: the fix-up reads those bits from the own words, which hold both
+            // directions)
+            const uint64_t tword = lds_tr[(J - Jbase) & (kMfmaColTiles - 1)][32 * ct + c][wave];
+            wbuf[kk++] = fxi::pack(rowp, colp, fxi::gather_bits(tword, rt, h));
           }
           wcount = total;
         }
@@ -1045,10 +1056,10 @@ __global__ __launch_bounds__(256, OCC) void tim_graph_mfma3_kernel(
 }
 
 // FP64 resolution of the filter's GROUP items: 16 lanes per item, lane q owns the pair
-// (row0 + (q & 3) + 8 (q >> 2), col).  The bitmap holds the filter's provisional bit sign(d~); a pair whose reference
-// predicate disagrees flips its bit(s) with one atomicXor each (row-major copy; transposed copy outside diagonal
-// blocks) and the two degrees follow.  Every bit is owned by exactly one lane of one item, so the plain read of the
-// provisional bit races with nothing.  A WAVE takes a whole ROW TILE: it stages the tile's 64 points once, walks the
+// (row0 + (q & 3) + 8 (q >> 2), col).  The bitmap holds the filter's provisional bit sign(d~), and so does the item
+// (fixup_item.h); a pair whose reference predicate disagrees flips its bit(s) with one atomicXor each (row-major copy;
+// transposed copy outside diagonal blocks, unless K1 left the lower triangle out: `upper`) and the two degrees follow.
+// Every bit is owned by exactly one lane of one item, so the plain read of the provisional bit races with nothing.  A WAVE takes a whole ROW TILE: it stages the tile's 64 points once, walks the
 // tile's regions (fixup_regions.h: one run of cells, one 64-lane load each -- lane 0: the count word, lane k: item k),
 // queues their items in LDS and resolves the queue in dense rounds of 64 items, four items per step, every load of
 // a round issued before the first use.  (A wave per REGION -- the layout up to round 7 -- paid the staging, the
@@ -1069,7 +1080,7 @@ __global__ __launch_bounds__(256) void tim_fixup_group_kernel(const ProbDesc* __
                                                               int32_t* __restrict__ deg,
                                                               const unsigned long long* __restrict__ regions,
                                                               int Tmax,
-                                                              const TimPrep* __restrict__ prep) {
+                                                              const TimPrep* __restrict__ prep, int upper) {
   TAIL_WAVE_PRIO();
   const int prob = blockIdx.y;
   const unsigned int total = work_count[prob];
@@ -1112,33 +1123,29 @@ __global__ __launch_bounds__(256) void tim_fixup_group_kernel(const ProbDesc* __
   const int rq = (q & 3) + 8 * (q >> 2);
   // STAGED = true (items of the regions): all items of a wave's queue come from ONE 64-row tile.  Its 64 points
   // are staged once per tile in the wave's LDS slice, and outside the diagonal tile the 16 provisional bits of an item
-  // are read from the TRANSPOSED copy, where they sit in one word (bitmap row `col`, word of the row tile).  Per item:
-  // one broadcast fetch of the column point and one word, instead of 17 points and 16 words on 16 different bitmap
-  // rows (1.8 KB of sectors per item: that traffic, not the arithmetic, was the kernel's 0.175 ms per 64 x 10 k launch).
+  // come with the item itself.  Per item: one broadcast fetch of the column point, instead of 17 points and 16 words on
+  // 16 different bitmap rows (1.8 KB of sectors per item: that traffic, not the arithmetic, was the kernel's 0.175 ms
+  // per 64 x 10 k launch).
   __shared__ double row_pts[4][64][6];
-  // ... and so are the COLUMN sides of a round's items (round 6): lane k fetches the column point of item k and the
-  // transposed word that holds its 16 provisional bits -- seven load instructions per round of up to 64 items --
-  // and the 16 lanes of an item read them back from the wave's LDS slice.  (Fetched inside the item loop they were
+  // ... and so are the COLUMN sides of a round's items (round 6): lane k fetches the column point of item k -- six
+  // load instructions per round of up to 64 items -- and the 16 lanes of an item read it back from the wave's LDS slice.  (Fetched inside the item loop they were
   // seven instructions per FOUR items, each for four distinct addresses: ~5 M vector-memory instructions per
   // 64 x 10 k batch, two thirds of what K1 itself issues, and on a step bound by the board's power limit the fix-up's
   // energy -- 0.1 J of 1.1 -- is paid for in K1's clock: profiles/r6v, r6w.)
-  __shared__ __attribute__((aligned(16))) double col_pts[4][64][8];  // [6]: the word's bits, [7]: unused
-  const uint64_t* bm64 = bitmap + d.bm_off;
+  __shared__ __attribute__((aligned(16))) double col_pts[4][64][6];
   auto resolve = [&](unsigned long long it, bool valid, auto staged, int tile, int slot) {
     constexpr bool STAGED = decltype(staged)::value;
-    int r = (int)((it >> 16) & 0xffff) + rq, col = (int)(it & 0xffff);
+    int r = fxi::row0(it) + rq, col = fxi::col(it);
     valid = valid && r < n && col < n && r != col;
     r = valid ? r : (STAGED ? tile * 64 : 0);
     col = valid ? col : 0;
-    // every load up front: the two points and the word that holds the provisional bit
+    // every load up front: the two points (and, below, the word that holds the provisional bit where the item does not)
     double sx, sy, sz, dx, dy, dz, cx, cy, cz, ex, ey, ez;
-    unsigned long long tword = 0ull;
     if (STAGED) {
       const double* rp = row_pts[wave][r & 63];
       sx = rp[0]; sy = rp[1]; sz = rp[2]; dx = rp[3]; dy = rp[4]; dz = rp[5];
       const double* cp = col_pts[wave][slot];
       cx = cp[0]; cy = cp[1]; cz = cp[2]; ex = cp[3]; ey = cp[4]; ez = cp[5];
-      tword = (unsigned long long)__double_as_longlong(cp[6]);
     } else {
       sx = ps[3 * r]; sy = ps[3 * r + 1]; sz = ps[3 * r + 2];
       dx = pd[3 * r]; dy = pd[3 * r + 1]; dz = pd[3 * r + 2];
@@ -1149,7 +1156,7 @@ __global__ __launch_bounds__(256) void tim_fixup_group_kernel(const ProbDesc* __
     const unsigned int bit = 1u << (col & 31);
     bool prov;
     if (STAGED && (r >> 6) != (col >> 6)) {  // (uniform over the 16 lanes of an item)
-      prov = ((tword >> (r & 63)) & 1ull) != 0ull;
+      prov = fxi::bit(it, q);
     } else {
       prov = (*wp & bit) != 0u;
     }
@@ -1161,8 +1168,8 @@ __global__ __launch_bounds__(256) void tim_fixup_group_kernel(const ProbDesc* __
     if (!valid || prov == e) return;
     atomicXor(wp, bit);
     atomicAdd(dg + r, e ? 1 : -1);
-    if ((r >> 6) != (col >> 6)) {  // the transposed copy
-      atomicXor(bm32 + 2 * ((int64_t)col * W + (r >> 6)) + ((r >> 5) & 1), 1u << (r & 31));
+    if ((r >> 6) != (col >> 6)) {  // the transposed copy, where there is one, and the column's degree
+      if (!upper) atomicXor(bm32 + 2 * ((int64_t)col * W + (r >> 6)) + ((r >> 5) & 1), 1u << (r & 31));
       atomicAdd(dg + col, e ? 1 : -1);
     }
   };
@@ -1172,14 +1179,12 @@ __global__ __launch_bounds__(256) void tim_fixup_group_kernel(const ProbDesc* __
   const int T = W, nch = fxr::n_chunks(T);
   // one round: the first `cnt` (<= 64) items of the queue, all of row tile `tile`
   auto round = [&](int cnt, int tile) {
-    if (lane < cnt) {  // item `lane`: its column point and (off the diagonal tile) its transposed word
-      const int col = min((int)(queue[wave][lane] & 0xffffull), n - 1);
+    if (lane < cnt) {  // item `lane`: its column point
+      const int col = min(fxi::col(queue[wave][lane]), n - 1);
       double* cp = col_pts[wave][lane];
       const double c0 = ps[3 * col], c1 = ps[3 * col + 1], c2 = ps[3 * col + 2];
       const double e0 = pd[3 * col], e1 = pd[3 * col + 1], e2 = pd[3 * col + 2];
-      const unsigned long long tw = (col >> 6) != tile ? bm64[(int64_t)col * W + tile] : 0ull;
       cp[0] = c0; cp[1] = c1; cp[2] = c2; cp[3] = e0; cp[4] = e1; cp[5] = e2;
-      cp[6] = __longlong_as_double((long long)tw);
     }
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");  // wave-private LDS slices: same-wave ordering suffices
 #pragma nounroll
@@ -1234,6 +1239,48 @@ __global__ __launch_bounds__(256) void tim_fixup_group_kernel(const ProbDesc* __
   const unsigned int ngrp = gridDim.x * 16;
   for (unsigned int w = (blockIdx.x * 256 + threadIdx.x) >> 4; w < total; w += ngrp) resolve(seg[w], true, std::false_type(), 0, 0);
 }
+
+// The lower triangle of a bitmap whose K1 stored the upper one only (LOWER = false), rebuilt on demand: per problem and
+// pair of tiles I < J the 64 own words U[64 I + l][J] are read, their 64 x 64 bits transposed and written as
+// L[64 J + l][I].  A wave takes a run of kMirrorRun consecutive I of one J -- lane l keeps the words of row 64 J + l
+// and stores them as one contiguous run.  The upper triangle is only read: the kernel is idempotent, and harmless on a
+// bitmap that holds both halves.  skip_closed: problems the degree closure has decided are left as they are (nobody
+// behind the closure reads their rows).
+constexpr int kMirrorRun = 8;
+__global__ __launch_bounds__(256) void tim_mirror_lower_kernel(const ProbDesc* __restrict__ descs,
+                                                               uint64_t* __restrict__ bitmap,
+                                                               const ProbState* __restrict__ states, int skip_closed) {
+  const ProbDesc d = descs[blockIdx.y];
+  const int n = d.n, W = d.W, T = W;
+  if (T < 2 || (skip_closed && states[blockIdx.y].deg_closed)) return;
+  const int lane = threadIdx.x & 63;
+  const int runs = (T + kMirrorRun - 1) / kMirrorRun;  // runs of row tiles per column tile (those at or beyond J: idle)
+  uint64_t* bm = bitmap + d.bm_off;
+  for (int wv = blockIdx.x * 4 + (int)(threadIdx.x >> 6); wv < T * runs; wv += gridDim.x * 4) {
+    const int J = wv / runs, Ia = (wv % runs) * kMirrorRun, Ib = min(Ia + kMirrorRun, J);
+    if (Ia >= Ib) continue;
+    uint64_t out[kMirrorRun];
+#pragma unroll
+    for (int k = 0; k < kMirrorRun; ++k) {
+      out[k] = 0ull;
+      if (Ia + k >= Ib) continue;  // (wave-uniform)
+      // row 64 (Ia + k) + lane < 64 J <= n: every lane has a row
+      const uint64_t x = bm[(int64_t)(64 * (Ia + k) + lane) * W + J];
+#pragma unroll
+      for (int c = 0; c < 64; ++c) {  // bit r of the ballot = bit c of row r's word = bit r of column c's word
+        const uint64_t m = __builtin_amdgcn_ballot_w64(((x >> c) & 1ull) != 0ull);
+        out[k] = lane == c ? m : out[k];
+      }
+    }
+    const int row = 64 * J + lane;
+    if (row < n) {
+#pragma unroll
+      for (int k = 0; k < kMirrorRun; ++k)
+        if (Ia + k < Ib) bm[(int64_t)row * W + Ia + k] = out[k];
+    }
+  }
+}
+
 void launch_tim_graph(hipStream_t s, const ProbDesc* d_desc, int batch, int max_n,
                       const double* d_src, const double* d_dst, uint64_t* d_bitmap,
                       double noise_bound, double cbar2, int mode, const ProbState* d_state) {
@@ -1335,7 +1382,9 @@ static K1Variant k1_lab_variant() {
 
 // phase 0 pre-pass (bbox, centred fp16 operands, R^2, degrees zeroed), 1 the matrix-core kernel (bitmap
 // + degrees), 2 FP64 fix-up of the worklist (+ overflow clear).  Three calls so that the profiling span
-// of phase 1 is that kernel alone.  d_pk: total_tiles TimOperandTile2, total_tiles = sum of the problems' W;
+// of phase 1 is that kernel alone.  Phases 1 and 2 with kTimUpperOnly added: K1 stores the upper triangle only and the
+// fix-up flips no transposed bit.  kTimMirror / kTimMirrorOpen: the lower triangle rebuilt from the upper one, for
+// every problem / for the problems the degree closure left open (only d_desc, batch, max_n, d_bitmap, d_state are read).  d_pk: total_tiles TimOperandTile2, total_tiles = sum of the problems' W;
 // d_prep: tim_prep_bytes(batch), zero except the segment fields (tim_prep_fill_segments), part of the header upload;
 // work_cap = tim_work_items(n, batch).
 void launch_tim_graph_mfma(hipStream_t s, int phase, const ProbDesc* d_desc, int batch, int max_n,
@@ -1346,6 +1395,21 @@ void launch_tim_graph_mfma(hipStream_t s, int phase, const ProbDesc* d_desc, int
   if (batch <= 0 || max_n <= 0) return;
   (void)total_tiles;
   const int T = (max_n + 63) / 64;
+  if (phase == kTimMirror || phase == kTimMirrorOpen) {
+    if (T < 2) return;
+    const int waves = T * ((T + kMirrorRun - 1) / kMirrorRun);
+    // (the waves stride over the runs: a grid sized for the work of ONE open problem would be ~800 workgroups per
+    // problem that leave at once behind a batch the closure decided -- 30 us of dispatch at 64 x 10 k)
+    hipLaunchKernelGGL(tim_mirror_lower_kernel, dim3((unsigned)std::min(64, (waves + 3) / 4), batch), dim3(256), 0, s, d_desc,
+                       d_bitmap, d_state, phase == kTimMirrorOpen ? 1 : 0);
+    return;
+  }
+#ifdef TEASER_K1_LAB
+  const bool upper = false;  // the lab instantiations keep the full store, and the fix-up its transposed flips with them
+#else
+  const bool upper = (phase & kTimUpperOnly) != 0;
+#endif
+  phase &= ~kTimUpperOnly;
   const double beta = 2 * noise_bound * sqrt(cbar2);  // registration.cc:438
   TimPrep* prep = reinterpret_cast<TimPrep*>(d_prep);
   unsigned long long* work = reinterpret_cast<unsigned long long*>(d_work);
@@ -1365,10 +1429,10 @@ void launch_tim_graph_mfma(hipStream_t s, int phase, const ProbDesc* d_desc, int
     hipLaunchKernelGGL(tim_prep_consts_kernel, dim3((batch + 63) / 64), dim3(64), 0, s, prep, batch, beta);
   } else if (phase == 1) {
     const int gyr = (T + kMfmaRowTiles - 1) / kMfmaRowTiles;
-#define TIM_K1_LAUNCH(PIPE, PLAIN, CHUNKS) TIM_K1_LAUNCH_OCC(PIPE, PLAIN, kK1Occ, CHUNKS)
-#define TIM_K1_LAUNCH_OCC(PIPE, PLAIN, OCC, CHUNKS)                                                               \
-  hipLaunchKernelGGL((tim_graph_mfma3_kernel<PIPE, PLAIN, OCC, CHUNKS>), dim3(tim_mfma_blocks(T, CHUNKS), batch), \
-                     dim3(256), 0, s, d_desc, d_src, d_dst, reinterpret_cast<const TimOperandTile2*>(d_pk), prep, \
+#define TIM_K1_LAUNCH(PIPE, PLAIN, CHUNKS) TIM_K1_LAUNCH_OCC(PIPE, PLAIN, kK1Occ, CHUNKS, true)
+#define TIM_K1_LAUNCH_OCC(PIPE, PLAIN, OCC, CHUNKS, LOWER)                                                               \
+  hipLaunchKernelGGL((tim_graph_mfma3_kernel<PIPE, PLAIN, OCC, CHUNKS, LOWER>), dim3(tim_mfma_blocks(T, CHUNKS), batch), \
+                     dim3(256), 0, s, d_desc, d_src, d_dst, reinterpret_cast<const TimOperandTile2*>(d_pk), prep,        \
                      d_bitmap, beta, gyr, work, work_count, d_state, d_deg, regions, T)
 #ifdef TEASER_K1_LAB
 #define TIM_K1_LAB_CASE(PIPE, PLAIN)                             \
@@ -1378,7 +1442,7 @@ void launch_tim_graph_mfma(hipStream_t s, int phase, const ProbDesc* d_desc, int
     else { TIM_K1_LAUNCH(PIPE, PLAIN, 4); }                      \
   }
     if (lab.occ4) {
-      if (lab.plain) { TIM_K1_LAUNCH_OCC(false, true, 4, 1); } else { TIM_K1_LAUNCH_OCC(false, false, 4, 1); }
+      if (lab.plain) { TIM_K1_LAUNCH_OCC(false, true, 4, 1, true); } else { TIM_K1_LAUNCH_OCC(false, false, 4, 1, true); }
     } else {
       TIM_K1_LAB_CASE(false, false)
       TIM_K1_LAB_CASE(false, true)
@@ -1387,7 +1451,11 @@ void launch_tim_graph_mfma(hipStream_t s, int phase, const ProbDesc* d_desc, int
     }
 #undef TIM_K1_LAB_CASE
 #else
-    TIM_K1_LAUNCH(kK1Pipe, kK1Plain, kK1Chunks);
+    if (upper) {
+      TIM_K1_LAUNCH_OCC(kK1Pipe, kK1Plain, kK1Occ, kK1Chunks, false);
+    } else {
+      TIM_K1_LAUNCH(kK1Pipe, kK1Plain, kK1Chunks);
+    }
 #endif
 #undef TIM_K1_LAUNCH
 #undef TIM_K1_LAUNCH_OCC
@@ -1399,7 +1467,7 @@ void launch_tim_graph_mfma(hipStream_t s, int phase, const ProbDesc* d_desc, int
     const int64_t fix_wgs = forced_wgs > 0 ? forced_wgs : ((T + 1) / 2 + 3) / 4;
     hipLaunchKernelGGL(tim_fixup_group_kernel, dim3((unsigned)std::max<int64_t>(4, fix_wgs), batch),
                        dim3(256), 0, s, d_desc, batch, d_src, d_dst, d_bitmap, beta, work, work_count, d_state, d_deg,
-                       regions, T, prep);
+                       regions, T, prep, upper ? 1 : 0);
   }
 }
 

@@ -636,11 +636,14 @@ __device__ __attribute__((noinline)) void closure_round(const uint64_t* __restri
 // degree-only bound is 530 - 537 for a clique of 500; with H it is 500 exactly.
 // Work: R = the <= kCoreCap vertices of largest degree, R = { deg >= t }; everything below holds for k - 1 >= t
 // (a smaller clique could use vertices outside R: decline).  R is sorted by (degree desc, index asc); for every row of R
-// the bits of its R-columns are gathered in that order (lane = column, one ballot per 64 columns): the prefix popcounts
-// give H(v) = max_i min(P_i, d_i), and the ballots ARE the row of the compact |R| x |R| adjacency, which is stored.
-// Grid (G, batch): the G workgroups of a problem each work out R and its order (redundantly: cheaper than a launch),
-// gather a slice of the rows, and the LAST workgroup to arrive gives the verdict from the H values and the compact
-// matrix (<= 128 KB, L2-resident): h1, the core peel, the clique in ascending order, the problem state.
+// the bits of its R-columns are gathered in that order (lane = column, one ballot per 64 columns): the ballots ARE the
+// row of the compact |R| x |R| adjacency, and its prefix popcounts give H(v) = max_i min(P_i, d_i).
+// Only the UPPER triangle of the bitmap is read (column c out of row r where c / 64 >= r / 64: the matrix-core K1 of
+// this route does not store the lower one), so the gathered rows are partial and a launch of its own ORs them with the
+// transpose of the compact matrix (|R| x |R| bits, <= 512 KB) and works out H from the full rows.
+// Four launches: the order of R (one workgroup per problem), the partial rows (G workgroups per problem), the
+// symmetrise + H launch, and the verdict from the H values and the compact matrix (one workgroup per problem): h1, the
+// core peel, the clique in ascending order, the problem state.
 // ------------------------------------------------------------------------------------------
 constexpr int kCoreCap = 2048;     // |R|
 constexpr int kCoreWords = kCoreCap / 64;
@@ -874,16 +877,19 @@ __global__ __launch_bounds__(kDegThreads) void degree_closure_order_kernel(
   }
 }
 
-// Launch 2 of the closure, grid (G, batch): H and the compact rows of this workgroup's slice of R.  A wave takes four
-// rows at a time: the bitmap rows are read ONCE, whole, with coalesced loads into the wave's LDS slice, and the bits of
+// Launch 2 of the closure, grid (G, batch): the compact rows of this workgroup's slice of R, from the bitmap's UPPER
+// triangle only: column c is picked out of row r when c / 64 >= r / 64 (a diagonal tile's words hold both directions).
+// The bitmap is symmetric, so nothing is lost -- the symmetrise launch ORs every partial row with the transpose of the
+// compact matrix -- and the words in front of r / 64 are never read: behind the K1 that stores the upper triangle only
+// they hold an earlier batch's bits.  A wave takes four rows at a time: the bitmap rows are read ONCE, whole, with coalesced loads into the wave's LDS slice, and the bits of
 // the |R| candidate columns are picked out of LDS (round 6; it was one global gather instruction per row and 64 columns
 // -- ~9 per row at N = 10 k, each touching most of the row's 20 cache lines: seven times the row's lines through the
 // address units, 0.13 J of the headline step's 1.13 J).  Rows longer than kRowStageWords words keep the gather.
 constexpr int kRowStageWords = 256;  // n <= 16384
 __global__ __launch_bounds__(kDegThreads) void degree_closure_rows_kernel(
     const ProbDesc* __restrict__ descs, const uint64_t* __restrict__ bitmap,
-    uint64_t* __restrict__ comp_pool /* [batch][kCoreCap][kCoreWords] */,
-    int32_t* __restrict__ h_pool /* [batch][kCoreCap] */, const uint32_t* __restrict__ key_pool /* [batch][kCoreCap] */,
+    uint64_t* __restrict__ comp_pool /* [batch][kCoreCap][kCoreWords]: the PARTIAL rows */,
+    const uint32_t* __restrict__ key_pool /* [batch][kCoreCap] */,
     const int32_t* __restrict__ counters, int batch) {
   TAIL_WAVE_PRIO();
   constexpr int kRows = 4, kGrp = 8;
@@ -901,24 +907,22 @@ __global__ __launch_bounds__(kDegThreads) void degree_closure_rows_kernel(
   __syncthreads();
   const int ng = (m + 63) >> 6;
   uint64_t* comp = comp_pool + (size_t)blockIdx.y * kCoreCap * kCoreWords;
-  int32_t* hout = h_pool + (size_t)blockIdx.y * kCoreCap;
   const bool staged = W <= kRowStageWords;
   {
     const int G = gridDim.x;
     const int per = (((m + G - 1) / G) + 15) & ~15;
     const int k0 = min(m, (int)blockIdx.x * per), k1 = min(m, k0 + per);
     const unsigned int* bm32 = reinterpret_cast<const unsigned int*>(bm);
-    const uint64_t le_mask = lane == 63 ? ~0ull : ((2ull << lane) - 1ull);
     for (int rb = k0 + wave * kRows; rb < k1; rb += 4 * kRows) {
       const unsigned int* rp[kRows];
-      int hmax[kRows], base[kRows];
+      int rtile[kRows];  // the row's tile: its first valid word
       uint64_t myword[kRows];
 #pragma unroll
       for (int r = 0; r < kRows; ++r) {
         const int rr = min(rb + r, k1 - 1);
-        rp[r] = bm32 + 2 * ((int64_t)(keys[rr] & 0xffffu) * W);
-        hmax[r] = 0;
-        base[r] = 0;
+        const int v = (int)(keys[rr] & 0xffffu);
+        rp[r] = bm32 + 2 * ((int64_t)v * W);
+        rtile[r] = v >> 6;
         myword[r] = 0;
       }
       if (staged) {  // (uniform per problem) every load of the four rows first, then the LDS stores
@@ -927,7 +931,7 @@ __global__ __launch_bounds__(kDegThreads) void degree_closure_rows_kernel(
         for (int r = 0; r < kRows; ++r)
 #pragma unroll
           for (int u = 0; u < kRowStageWords / 64; ++u)
-            wv[r][u] = 64 * u + lane < W ? reinterpret_cast<const uint64_t*>(rp[r])[64 * u + lane] : 0ull;
+            wv[r][u] = (64 * u + lane < W && 64 * u + lane >= rtile[r]) ? reinterpret_cast<const uint64_t*>(rp[r])[64 * u + lane] : 0ull;
 #pragma unroll
         for (int r = 0; r < kRows; ++r)
 #pragma unroll
@@ -950,18 +954,14 @@ __global__ __launch_bounds__(kDegThreads) void degree_closure_rows_kernel(
             cbit[q] = c & 31;
 #pragma unroll
             for (int r = 0; r < kRows; ++r)
-              x[r][q] = (cdeg[q] >= 0) ? (STAGED ? rowlds[r * 2 * kRowStageWords + (c >> 5)] : rp[r][c >> 5]) : 0u;
+              x[r][q] = (cdeg[q] >= 0 && (c >> 6) >= rtile[r]) ? (STAGED ? rowlds[r * 2 * kRowStageWords + (c >> 5)] : rp[r][c >> 5]) : 0u;
           }
 #pragma unroll
           for (int q = 0; q < kGrp; ++q) {
             if (g0 + q >= ng) break;
 #pragma unroll
             for (int r = 0; r < kRows; ++r) {
-              const bool bit = cdeg[q] >= 0 && ((x[r][q] >> cbit[q]) & 1u);
-              const uint64_t mask = __ballot(bit);
-              const int P = base[r] + __popcll(mask & le_mask);
-              if (bit) hmax[r] = max(hmax[r], min(P, cdeg[q]));
-              base[r] += __popcll(mask);
+              const uint64_t mask = __ballot(((x[r][q] >> cbit[q]) & 1u) != 0u);  // (x = 0 where nothing is picked)
               if (lane == g0 + q) myword[r] = mask;
             }
           }
@@ -972,24 +972,107 @@ __global__ __launch_bounds__(kDegThreads) void degree_closure_rows_kernel(
       else
         groups(std::false_type());
 #pragma unroll
-      for (int r = 0; r < kRows; ++r) {
-        int hv = hmax[r];
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) hv = max(hv, __shfl_xor(hv, o, 64));
-        if (rb + r < k1) {
-          if (lane < kCoreWords) comp[(size_t)(rb + r) * kCoreWords + lane] = myword[r];
-          if (lane == 0) hout[rb + r] = hv;
-        }
-      }
+      for (int r = 0; r < kRows; ++r)
+        if (rb + r < k1 && lane < kCoreWords) comp[(size_t)(rb + r) * kCoreWords + lane] = myword[r];
       __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");  // (the next pass overwrites the slice)
     }
   }
 }
 
+// Launch 3 of the closure, grid (G, batch): full compact rows and H.  A wave takes 64 rows of R at a time (rank block
+// A, lane l = rank 64 A + l) and walks the column blocks B in rank order: the full word is the partial row's own word
+// (A, B) ORed with the 64 x 64 transpose of block (B, A) -- lane c's word of that block is column c of it: one ballot
+// per bit -- written to a SECOND pool (the partial pool is the other waves' transpose source; staged in LDS so that a
+// row's words leave in 64-byte runs), and H(v) = max over the row's set bits i of min(P_i, d_i), P_i = the set bits up
+// to and including i, d_i the degree of rank i: the prefix rule of the ballots this replaces, on words, with the
+// running count per lane.  d is not increasing in the rank and P not decreasing, so a block whose P all lie at or
+// below its smallest d contributes its last P, one whose P all lie at or above its largest d the d of its first set
+// bit; only the block in which a row's P crosses d walks its bits.  No bitmap read.
+__global__ __launch_bounds__(kDegThreads) void degree_closure_symmetrise_kernel(
+    const uint64_t* __restrict__ part_pool /* [batch][kCoreCap][kCoreWords] */,
+    uint64_t* __restrict__ comp_pool /* [batch][kCoreCap][kCoreWords]: the full rows */,
+    int32_t* __restrict__ h_pool /* [batch][kCoreCap] */, const uint32_t* __restrict__ key_pool /* [batch][kCoreCap] */,
+    const int32_t* __restrict__ counters, int batch) {
+  TAIL_WAVE_PRIO();
+  // degree by rank, clamped to kCoreCap: P <= |R| <= kCoreCap, so min(P, d) is the same, and the clamped sequence does
+  // not increase (the keys' order inside the run of degrees >= kDegBins is by vertex)
+  __shared__ unsigned short cdeg[kCoreCap];
+  constexpr int kOutWords = 8;  // column blocks per flush of the staged rows
+  __shared__ uint64_t outbuf[kDegThreads / 64][64][kOutWords + 1];  // +1: conflict-free
+  static_assert(kCoreCap <= 65535 && kDegBins >= kCoreCap, "clamped degrees fit and stay ordered");
+  const int m = counters[blockIdx.y];
+  if (m < 2) return;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  {
+    const uint32_t* kin = key_pool + (size_t)blockIdx.y * kCoreCap;
+    for (int r = tid; r < m; r += kDegThreads) cdeg[r] = (unsigned short)min(kin[r] >> 16, (uint32_t)kCoreCap);
+  }
+  __syncthreads();
+  const int ng = (m + 63) >> 6;
+  const uint64_t* part = part_pool + (size_t)blockIdx.y * kCoreCap * kCoreWords;
+  uint64_t* comp = comp_pool + (size_t)blockIdx.y * kCoreCap * kCoreWords;
+  int32_t* hout = h_pool + (size_t)blockIdx.y * kCoreCap;
+  for (int A = blockIdx.x * 4 + wave; A < ng; A += gridDim.x * 4) {
+    const int row = 64 * A + lane;
+    const bool rowok = row < m;
+    int base = 0, hmax = 0;
+    // block B's two words are requested while block B - 1 is worked on
+    uint64_t own_n = rowok ? part[(size_t)row * kCoreWords] : 0ull;
+    uint64_t src_n = lane < m ? part[(size_t)lane * kCoreWords + A] : 0ull;
+    for (int B = 0; B < ng; ++B) {
+      const uint64_t own = own_n, src = src_n;  // src: lane's row of the transposed source block (B, A)
+      if (B + 1 < ng) {
+        const int trow = 64 * (B + 1) + lane;
+        own_n = rowok ? part[(size_t)row * kCoreWords + B + 1] : 0ull;
+        src_n = trow < m ? part[(size_t)trow * kCoreWords + A] : 0ull;
+      }
+      uint64_t tr = 0ull;
+      if (__builtin_amdgcn_ballot_w64(src != 0ull) != 0ull) {
+#pragma unroll
+        for (int c = 0; c < 64; ++c) {
+          const uint64_t mk = __builtin_amdgcn_ballot_w64(((src >> c) & 1ull) != 0ull);
+          tr = lane == c ? mk : tr;
+        }
+      }
+      // (ranks beyond m: no row is stored for them and no source row sets their column bit)
+      const uint64_t full = rowok ? (own | tr) : 0ull;
+      outbuf[wave][lane][B & (kOutWords - 1)] = full;
+      const int cnt = __popcll(full);
+      const int cols = min(64, m - 64 * B);
+      const int d_hi = cdeg[64 * B], d_lo = cdeg[64 * B + cols - 1];
+      const bool below = base + cnt <= d_lo;  // every P of the block <= every d of it: min = P, largest at the last bit
+      const bool above = base + 1 >= d_hi;    // every P >= every d: min = d, largest at the first set bit
+      if (__builtin_amdgcn_ballot_w64(cnt > 0 && !below && !above) != 0ull) {
+        for (int k = 0; k < cols; ++k) {
+          const uint64_t upto = k == 63 ? ~0ull : ((2ull << k) - 1ull);
+          const int P = base + __popcll(full & upto);
+          const int cand = min(P, (int)cdeg[64 * B + k]);
+          hmax = ((full >> k) & 1ull) ? max(hmax, cand) : hmax;
+        }
+      } else if (cnt > 0) {
+        hmax = max(hmax, below ? base + cnt : (int)cdeg[64 * B + __builtin_ctzll(full)]);
+      }
+      base += cnt;
+      if ((B & (kOutWords - 1)) == kOutWords - 1 || B == ng - 1) {
+        // flush: lanes 8 r .. 8 r + 7 store the (up to) 8 consecutive words of one row
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");  // wave-private slice: same-wave ordering suffices
+        const int w = lane & (kOutWords - 1), Bw = (B & ~(kOutWords - 1)) + w;
+#pragma unroll
+        for (int it = 0; it < 8; ++it) {
+          const int r = it * 8 + (lane >> 3);
+          if (64 * A + r < m && Bw <= B) comp[(size_t)(64 * A + r) * kCoreWords + Bw] = outbuf[wave][r][w];
+        }
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");  // (the next blocks overwrite the slice)
+      }
+    }
+    if (rowok) hout[row] = hmax;
+  }
+}
+
 constexpr int kCoverMax = 4;   // a core of up to k + kCoverMax vertices is still decided (vertex cover of its missing edges)
 constexpr int kMissCap = 64;   // ... when it misses at most this many edges
-// Launch 2 of the closure, one workgroup per problem: h1 from the H values, the core peel inside the compact graph
-// (its rows come from launch 1: plain loads behind a kernel boundary), the clique in ascending order, the state.
+// Launch 4 of the closure, one workgroup per problem: h1 from the H values, the core peel inside the compact graph
+// (its rows come from launch 3: plain loads behind a kernel boundary), the clique in ascending order, the state.
 __global__ __launch_bounds__(kDegThreads) void degree_closure_verdict_kernel(
     const ProbDesc* __restrict__ descs, ProbState* __restrict__ states, int32_t* __restrict__ clique,
     const uint64_t* __restrict__ comp_pool, const int32_t* __restrict__ h_pool, const uint32_t* __restrict__ key_pool,
@@ -1217,7 +1300,7 @@ __global__ __launch_bounds__(kDegThreads) void degree_closure_verdict_kernel(
 }
 
 int64_t degree_closure_scratch_bytes(int batch) {
-  return (int64_t)std::max(batch, 1) * ((int64_t)kCoreCap * kCoreWords * 8 + (int64_t)kCoreCap * 8);
+  return (int64_t)std::max(batch, 1) * (2 * (int64_t)kCoreCap * kCoreWords * 8 /* partial + full rows */ + (int64_t)kCoreCap * 8);
 }
 
 void launch_degree_closure(hipStream_t s, const ProbDesc* d_desc, int batch, const uint64_t* d_bitmap,
@@ -1227,11 +1310,14 @@ void launch_degree_closure(hipStream_t s, const ProbDesc* d_desc, int batch, con
   const int forced = (int)setting(S_DEG_CLOSURE_WGS);
   const int G = forced > 0 ? std::min(forced, 64) : std::max(1, std::min(16, 1024 / batch));
   uint64_t* comp = reinterpret_cast<uint64_t*>(d_scratch);
-  int32_t* hp = reinterpret_cast<int32_t*>(comp + (size_t)batch * kCoreCap * kCoreWords);
+  uint64_t* part = comp + (size_t)batch * kCoreCap * kCoreWords;
+  int32_t* hp = reinterpret_cast<int32_t*>(part + (size_t)batch * kCoreCap * kCoreWords);
   uint32_t* kp = reinterpret_cast<uint32_t*>(hp + (size_t)batch * kCoreCap);
   hipLaunchKernelGGL(degree_closure_order_kernel, dim3(1, batch), dim3(kDegThreads), 0, s, d_desc, d_deg, d_state, kp,
                      d_counters, batch);
-  hipLaunchKernelGGL(degree_closure_rows_kernel, dim3(G, batch), dim3(kDegThreads), 0, s, d_desc, d_bitmap, comp, hp, kp,
+  hipLaunchKernelGGL(degree_closure_rows_kernel, dim3(G, batch), dim3(kDegThreads), 0, s, d_desc, d_bitmap, part, kp,
+                     d_counters, batch);
+  hipLaunchKernelGGL(degree_closure_symmetrise_kernel, dim3(std::min(G, 8), batch), dim3(kDegThreads), 0, s, part, comp, hp, kp,
                      d_counters, batch);
   hipLaunchKernelGGL(degree_closure_verdict_kernel, dim3(batch), dim3(kDegThreads), 0, s, d_desc, d_state, d_clique, comp, hp,
                      kp, d_counters, batch);

@@ -316,6 +316,10 @@ struct teaser_hip_solver : HandleBase {
   const double* cur_src = nullptr;  // device pointers of the current inputs
   const double* cur_dst = nullptr;
   bool have_graph = false;
+  // d_bitmap of the last solve holds the UPPER triangle only (row r is valid from word r / 64 on): K1 ran on the route
+  // whose one reader is the degree closure.  Whoever else reads the arena runs the mirror kernel first
+  // (launch_tim_graph_mfma, kTimMirror / kTimMirrorOpen).  The flag lives with the arena: every lane has its own.
+  bool bm_lower_missing = false;
 
   SolverBuf d_desc, d_state, d_src, d_dst, d_bitmap, d_deg, d_clique, d_start_cliques, d_alive_a,
       d_alive_b, d_next_count, d_weights, d_rot_inl, d_trans_inl, d_tls_scratch, d_tim_off,
@@ -1092,6 +1096,13 @@ int32_t enqueue_heuristic_stage(teaser_hip_solver* h, int batch, int mode, bool 
   const int64_t total_n = std::max<int64_t>(h->total_n, 1);
   {
     StageScope sc(h, ST_HEU);
+    // K1 stored the upper triangle only: the problems the degree closure left open get their lower one now, so that
+    // everything from here to the end of the solve (greedy, selection, peel, the bound stages, the exact search -- all
+    // of them skip the closed problems) reads full rows.  The closed problems' rows stay as they are (the getter's
+    // business), so the arena's flag stays up.
+    if (h->bm_lower_missing)
+      launch_tim_graph_mfma(s, kTimMirrorOpen, dd, batch, h->max_n, 0, nullptr, nullptr, nullptr, nullptr, nullptr, 0,
+                            h->d_bitmap.as<uint64_t>(), ds, nullptr, 0.0, 0.0);
     int32_t* heu_trace = nullptr;
     if (setting(S_K4_DEBUG) && batch <= 4) {  // diagnostics only: per-start phase clocks of the greedy kernel
       HIPCHK(h, h->s_e.ensure(sizeof(long long) * 8 * kMaxStarts * (size_t)batch));
@@ -1261,6 +1272,13 @@ int32_t solve_packed_enqueue(teaser_hip_solver* h, const double* d_src, const do
       HIPCHK(h, h->d_work.ensure(8 * (size_t)tim_work_items(n, batch) + 64));
     }
   }
+  // Degree closure (PMC_EXACT: the answer must be THE maximum clique, which is what the closure proves), below.  Behind
+  // the matrix-core K1 it is the one reader of the bitmap on the common path, and it reads the upper triangle only: K1
+  // then does not store the lower one (every other route keeps the full store).
+  const bool closure = need_graph && mode == TEASER_INLIER_PMC_EXACT && max_n <= 65536 && setting(S_DEG_CLOSURE) != 0 &&
+                       !(setting(S_TAIL_SKIP) & 2);
+  const bool upper_k1 = mfma_k1 && closure;
+  if (need_graph) h->bm_lower_missing = upper_k1;
   const bool k1_only = mfma_k1 && h->is_lane && h->k1_stream && h->k1_kernel_only;
   if (mfma_k1 && h->is_lane && h->k1_stream && !k1_only) {
     s1 = h->k1_stream;
@@ -1318,7 +1336,7 @@ int32_t solve_packed_enqueue(teaser_hip_solver* h, const double* d_src, const do
         }
         {
           StageScope sc(h, phase == 1 ? ST_TIM : ST_TIMAUX, sp);
-          launch_tim_graph_mfma(sp, phase, dd, batch, max_n, wo, d_src, d_dst, h->d_pk.p, h->d_prep.p,
+          launch_tim_graph_mfma(sp, (upper_k1 && phase > 0) ? (phase | kTimUpperOnly) : phase, dd, batch, max_n, wo, d_src, d_dst, h->d_pk.p, h->d_prep.p,
                                 h->d_work.p, cap, h->d_bitmap.as<uint64_t>(), ds, h->d_deg.as<int32_t>(),
                                 P.noise_bound, P.cbar2);
         }
@@ -1345,12 +1363,10 @@ int32_t solve_packed_enqueue(teaser_hip_solver* h, const double* d_src, const do
       StageScope sc(h, ST_DEG);
       launch_degrees(s, dd, batch, max_n, h->d_bitmap.as<uint64_t>(), h->d_deg.as<int32_t>(), ds);
     }
-    // Degree closure (PMC_EXACT: the answer must be THE maximum clique, which is what the closure proves): problems
-    // whose clique follows from the degrees are closed before any heuristic runs.  (heu_skip_closed = 1: when the
-    // previous batch of this handle was closed entirely, the greedy / select / peel launches are not even enqueued:
-    // the finish half runs them for the problems the closure left open, should there be any.)
-    const bool closure = mode == TEASER_INLIER_PMC_EXACT && max_n <= 65536 && setting(S_DEG_CLOSURE) != 0 &&
-                         !(setting(S_TAIL_SKIP) & 2);
+    // Degree closure: problems whose clique follows from the degrees are closed before any heuristic runs.
+    // (heu_skip_closed = 1: when the previous batch of this handle was closed entirely, the greedy / select / peel
+    // launches are not even enqueued: the finish half runs them for the problems the closure left open, should there
+    // be any.)
     if (closure) {
       StageScope sc(h, ST_HEU);
       HIPCHK(h, h->d_core.ensure((size_t)degree_closure_scratch_bytes(batch)));
@@ -2249,6 +2265,14 @@ int32_t teaser_hip_get_inlier_graph_bitmap(teaser_hip_solver* h, int32_t problem
     return len ? TEASER_HIP_OK : TEASER_HIP_ERR_BAD_ARG;
   }
   const ProbDesc& d = h->descs[(size_t)problem];
+  if (buf && h->bm_lower_missing) {
+    // the solve's K1 stored the upper triangle only: rebuild the lower one for every problem of the batch, once
+    launch_tim_graph_mfma(h->stream, kTimMirror, h->d_desc.as<ProbDesc>(), h->batch, h->max_n, 0, nullptr, nullptr, nullptr,
+                          nullptr, nullptr, 0, h->d_bitmap.as<uint64_t>(), h->d_state.as<ProbState>(), nullptr, 0.0, 0.0);
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    h->bm_lower_missing = false;
+  }
   return copy_out(h, h->d_bitmap.as<uint64_t>() + d.bm_off, (int64_t)d.n * d.W, buf, len);
 }
 
@@ -2445,6 +2469,7 @@ int32_t teaser_hip_max_clique(teaser_hip_solver* h, const uint64_t* bitmap, int3
   if (rc != TEASER_HIP_OK) return rc;
   h->batch = 0;  // getters of a previous solve are invalidated
   h->pend.spec_bounds = false;  // (a previous solve's speculative bound results are not this graph's)
+  h->bm_lower_missing = false;  // (the arena takes the caller's bitmap, both halves)
   ProbState& st = h->states[0];
   HIPCHK(h, h->d_desc.ensure(sizeof(ProbDesc)));
   HIPCHK(h, h->d_state.ensure(sizeof(ProbState)));
