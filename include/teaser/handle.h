@@ -73,5 +73,16 @@ struct LazyPlane : LazyHandle<teaser_hip_plane, teaser_hip_plane_destroy> {
   }
 };
 
+// A TSDF handle IS its volume, so it is created from the volume's record; the status is returned (the class that owns
+// the holder throws its own error with it) and h_ stays nullptr unless it is TEASER_HIP_OK.
+struct LazyTsdf : LazyHandle<teaser_hip_tsdf, teaser_hip_tsdf_destroy> {
+  int32_t create(const teaser_tsdf_volume_c& volume, int32_t device = -1) {
+    if (h_) return TEASER_HIP_OK;
+    const int32_t rc = teaser_hip_tsdf_create(&volume, device, &h_);
+    if (rc != TEASER_HIP_OK) h_ = nullptr;
+    return rc;
+  }
+};
+
 }  // namespace detail
 }  // namespace teaser

@@ -1,0 +1,149 @@
+// teaser/tsdf.h -- TSDF volume integration on the MI355X with the surface of open3d::pipelines::integration::
+// UniformTSDFVolume: depth frames and their camera poses in, one fused cloud out, over the C ABI (include/teaser_hip.h,
+// "TSDF volume", where the contract is written out).  Header-only.
+//
+// The volume lives on the device as long as the object: frames go up, only the extracted surface comes back.  Images
+// come in as teaser::DepthFrame (teaser/rgbd.h), a view that owns nothing; `extrinsic` is world-to-camera as in Open3D.
+// Clouds are teaser::Matrix3X (one point per column).  An object is reusable but not re-entrant.  A failed call throws
+// teaser::TSDFError, the constructor too when no MI355X is visible (there is no CPU path).
+#pragma once
+
+#include <cstdint>
+#include <stdexcept>
+#include <string>
+#include <vector>
+
+#include "teaser/handle.h"
+#include "teaser/rgbd.h"
+#include "teaser_hip.h"
+
+namespace teaser {
+
+enum class TSDFVolumeColorType { NoColor = 0, RGB8 = 1, Gray32 = 2 };
+
+class TSDFError : public std::runtime_error {
+ public:
+  TSDFError(int32_t status, const std::string& what) : std::runtime_error(what), status_(status) {}
+  int32_t status() const { return status_; }
+
+ private:
+  int32_t status_;
+};
+
+// What the extractions return; normals and colors have no columns where they do not exist.
+struct TSDFPointCloud {
+  Matrix3X points, normals, colors;
+};
+
+class UniformTSDFVolume {
+ public:
+  UniformTSDFVolume(double length, int resolution, double sdf_trunc, TSDFVolumeColorType color_type,
+                    double origin_x = 0.0, double origin_y = 0.0, double origin_z = 0.0, int device = -1)
+      : length_(length), resolution_(resolution), color_type_(color_type) {
+    teaser_tsdf_volume_c v;
+    teaser_hip_tsdf_volume_default(&v);
+    v.length = length, v.resolution = resolution, v.sdf_trunc = sdf_trunc, v.color_type = (int32_t)color_type;
+    v.origin[0] = origin_x, v.origin[1] = origin_y, v.origin[2] = origin_z;
+    const int32_t rc = h_.create(v, device);
+    if (rc != TEASER_HIP_OK)
+      throw TSDFError(rc, "teaser::UniformTSDFVolume: teaser_hip_tsdf_create failed (status " + std::to_string(rc) +
+                              (rc == TEASER_HIP_ERR_NO_DEVICE ? ": no MI355X visible, there is no CPU path)"
+                                                              : std::string("): ") + teaser_hip_tsdf_last_error(nullptr)));
+  }
+
+  double voxelLength() const { return length_ / resolution_; }
+  int resolution() const { return resolution_; }
+
+  // Open3D's Integrate(image, intrinsic, extrinsic), the RGBD image given as the frame's parts.
+  void integrate(const DepthFrame& frame, const PinholeCameraIntrinsic& intrinsic, const Matrix4& extrinsic,
+                 double depth_scale = 1000.0, double depth_trunc = 3.0) {
+    integrateBatch({frame}, {intrinsic}, {extrinsic}, depth_scale, depth_trunc);
+  }
+
+  // The frames, in the order given, in one call: a voxel ends with the bits one integrate() per frame leaves.
+  // intrinsics: one for all or one per frame.
+  void integrateBatch(const std::vector<DepthFrame>& frames, const std::vector<PinholeCameraIntrinsic>& intrinsics,
+                      const std::vector<Matrix4>& extrinsics, double depth_scale = 1000.0, double depth_trunc = 3.0) {
+    const size_t b = frames.size();
+    if ((intrinsics.size() != 1 && intrinsics.size() != b) || extrinsics.size() != b)
+      throw std::invalid_argument("teaser::UniformTSDFVolume: one intrinsic (or one per frame) and one extrinsic per frame");
+    std::vector<teaser_tsdf_frame_c> rec(b);
+    std::vector<const void*> pd(b), pc(b);
+    for (size_t k = 0; k < b; ++k) {
+      const DepthFrame& f = frames[k];
+      const PinholeCameraIntrinsic& K = intrinsics[intrinsics.size() == 1 ? 0 : k];
+      teaser_tsdf_frame_c& r = rec[k];
+      r = teaser_tsdf_frame_c{};
+      r.width = f.width, r.height = f.height, r.depth_format = f.depth_format, r.color_format = f.color_format;
+      r.depth_row_bytes = f.depth_row_bytes, r.color_row_bytes = f.color_row_bytes;
+      r.fx = K.fx, r.fy = K.fy, r.cx = K.cx, r.cy = K.cy;
+      detail::row_major(extrinsics[k], r.extrinsic);
+      r.depth_scale = depth_scale, r.depth_trunc = depth_trunc;
+      pd[k] = f.depth, pc[k] = f.color;
+    }
+    check(teaser_hip_tsdf_integrate_batch(h_, (int32_t)b, rec.data(), pd.data(), pc.data()));
+  }
+
+  // Open3D's ExtractPointCloud: points, normals (unless with_normals is false) and, for a volume with a colour type,
+  // colours, in Open3D's order.
+  TSDFPointCloud extractPointCloud(bool with_normals = true) {
+    const bool colored = color_type_ != TSDFVolumeColorType::NoColor;
+    int64_t count = 0;
+    check(teaser_hip_tsdf_extract_point_cloud(h_, 0, nullptr, nullptr, nullptr, &count));
+    TSDFPointCloud out;
+    out.points = Matrix3X(3, count);
+    if (with_normals) out.normals = Matrix3X(3, count);
+    if (colored) out.colors = Matrix3X(3, count);
+    if (count > 0)
+      check(teaser_hip_tsdf_extract_point_cloud(h_, count, out.points.data(), with_normals ? out.normals.data() : nullptr,
+                                                colored ? out.colors.data() : nullptr, &count));
+    return out;
+  }
+
+  // Open3D's ExtractVoxelPointCloud: every observed voxel's centre, (tsdf + 1) / 2 as its colour.
+  TSDFPointCloud extractVoxelPointCloud() {
+    int64_t count = 0;
+    check(teaser_hip_tsdf_extract_voxel_point_cloud(h_, 0, nullptr, nullptr, &count));
+    TSDFPointCloud out;
+    out.points = Matrix3X(3, count);
+    out.colors = Matrix3X(3, count);
+    if (count > 0)
+      check(teaser_hip_tsdf_extract_voxel_point_cloud(h_, count, out.points.data(), out.colors.data(), &count));
+    return out;
+  }
+
+  // resolution^3 x 2 floats (tsdf, weight) in Open3D's voxel order (x R + y) R + z.
+  std::vector<float> extractVolumeTSDF() {
+    std::vector<float> out(2 * voxels());
+    check(teaser_hip_tsdf_download(h_, out.data(), nullptr));
+    return out;
+  }
+  // resolution^3 x 3 doubles in Open3D's voxel order (a volume with a colour type only).
+  std::vector<double> extractVolumeColor() {
+    std::vector<double> out(3 * voxels());
+    check(teaser_hip_tsdf_download(h_, nullptr, out.data()));
+    return out;
+  }
+  void injectVolumeTSDF(const std::vector<float>& tsdf_weight) {
+    if (tsdf_weight.size() != 2 * voxels()) throw std::invalid_argument("teaser::UniformTSDFVolume: tsdf_weight has another size");
+    check(teaser_hip_tsdf_upload(h_, tsdf_weight.data(), nullptr));
+  }
+  void injectVolumeColor(const std::vector<double>& color) {
+    if (color.size() != 3 * voxels()) throw std::invalid_argument("teaser::UniformTSDFVolume: color has another size");
+    check(teaser_hip_tsdf_upload(h_, nullptr, color.data()));
+  }
+  void reset() { check(teaser_hip_tsdf_reset(h_)); }
+
+ private:
+  size_t voxels() const { return (size_t)resolution_ * (size_t)resolution_ * (size_t)resolution_; }
+  void check(int32_t rc) {
+    if (rc != TEASER_HIP_OK)
+      throw TSDFError(rc, "teaser::UniformTSDFVolume: status " + std::to_string(rc) + ": " + teaser_hip_tsdf_last_error(h_));
+  }
+  double length_;
+  int resolution_;
+  TSDFVolumeColorType color_type_;
+  detail::LazyTsdf h_;
+};
+
+}  // namespace teaser

@@ -1913,6 +1913,129 @@ TEASER_HIP_API int32_t teaser_hip_plane_trials_batch(teaser_hip_plane* plane, in
                                                      int32_t* samples, uint8_t* flags, double* planes, int32_t* count,
                                                      double* E);
 
+/* TSDF volume: Open3D's pipelines.integration.UniformTSDFVolume (integrate, extract_point_cloud,
+ * extract_voxel_point_cloud), on its OWN handle.  A handle owns ONE volume, which lives on the device from create to
+ * destroy: frames go up, the extracted surface comes back, the voxels move only through download and upload.  The text
+ * below IS the contract.  It restates Open3D's UniformTSDFVolume.cpp from memory; Open3D is not run and bit parity with
+ * an Open3D binary is NOT claimed.  tests/tsdf_reference.py restates this text in numpy and is the parity target of the
+ * host and GPU tests.  No product-add is fused and every sum is taken left to right as written; float32 divisions and
+ * square roots are correctly rounded.
+ *
+ * State.  R = resolution.  Per voxel (x, y, z), 0 <= x, y, z < R: tsdf and weight, float32, both 0 after create and
+ * reset; with a colour type, color: three doubles, 0.  vl = length / R in double.  The float32 constants:
+ *   vl_f = (float)vl;  half_f = vl_f 0.5f;  trunc_f = (float)sdf_trunc;  inv_f = 1.0f / trunc_f;  o_f = (float)origin,
+ *   and per frame E_f = (float)E element by element (E = extrinsic, the row-major 4 x 4 world-to-camera matrix, used as
+ *   given; row 3 is not read);  s_r = E_f[r][2] vl_f;  fx_f, fy_f, cx_f, cy_f = (float) of the intrinsics;
+ *   safe_w = (float)width - 0.0001f;  safe_h = (float)height - 0.0001f.
+ *
+ * Depth sample: the rule of "Depth frames".  A uint16 sample d gives (float)d / (float)depth_scale, set to 0 when
+ * (double) of it is >= depth_trunc; a float32 sample is taken as it is.
+ *
+ * teaser_hip_tsdf_integrate_batch: the frames apply in the order given, and a voxel's result equals applying them one
+ * call at a time.  All arithmetic is float32 unless stated.  For each column (x, y):
+ *   p   = ((half_f + vl_f (float)x) + o_f[0], (half_f + vl_f (float)y) + o_f[1], half_f + o_f[2])
+ *   c_r = ((E_f[r][0] p_x + E_f[r][1] p_y) + E_f[r][2] p_z) + E_f[r][3]   for r = 0, 1, 2
+ *   voxel z uses c after z successive additions c_r = c_r + s_r.  This is Open3D's running sum; it is part of the bits
+ *   and is never replaced by a product.
+ * Then for each voxel:
+ *   skip unless c_2 > 0
+ *   u_f = ((c_0 fx_f) / c_2 + cx_f) + 0.5f;  v_f = ((c_1 fy_f) / c_2 + cy_f) + 0.5f
+ *   skip unless u_f >= 0.0001f && u_f < safe_w && v_f >= 0.0001f && v_f < safe_h   (a NaN skips)
+ *   u = (int)u_f, v = (int)v_f;  d = the depth sample of row v, column u;  skip unless d > 0   (a NaN skips; +inf does not)
+ *   xx = ((float)u - cx_f) (1.0f / fx_f);  yy = ((float)v - cy_f) (1.0f / fy_f);  m = sqrtf((xx xx + yy yy) + 1.0f)
+ *   sdf = (d - c_2) m;  skip unless sdf > -trunc_f
+ *   q = sdf inv_f;  t = q < 1.0f ? q : 1.0f
+ *   tsdf = (tsdf weight + t) / (weight + 1.0f)
+ *   with colour, per component in double: color = (color (double)weight + (double)s) / (double)(weight + 1.0f), s the
+ *   uint8 channel of pixel (v, u) for RGB8, or its float32 sample for all three components for Gray32 (a NaN colour of
+ *   a Gray32 volume is stored as the quiet NaN 0x7ff8000000000000)
+ *   last: weight = weight + 1.0f
+ * Per frame one record teaser_tsdf_frame_c, a depth image depth[b] (height rows of depth_row_bytes bytes) and, for a
+ * volume with a colour type, a colour image color[b] (height rows of color_row_bytes bytes): RGB8 needs color_format 1
+ * (uint8 x 3), Gray32 color_format 2 (float32 x 1).  A volume without colour reads no colour image: color may be NULL and
+ * color_format only has to lie in [0, 3].  Rows may be padded.  A frame with width or height 0 is legal and touches
+ * nothing; n_frames = 0 returns OK without touching the device.
+ *
+ * teaser_hip_tsdf_extract_point_cloud.  A voxel is USABLE when weight != 0 && tsdf < 0.98f && tsdf >= -0.98f.  The rows
+ * come in the order of Open3D's serial loop: x, y, z ascending and inside a voxel the axes i = 0, 1, 2.  For a usable
+ * voxel 0 = (x, y, z) with value f0 and its +1 neighbour 1 along axis i with value f1, a row is emitted when the
+ * neighbour's index along i is < R - 1, the neighbour is usable and f0 f1 < 0 (float32).  Then
+ *   r0 = |f0|, r1 = |f1| in float32;  half = vl 0.5 and p0 = (half + vl x, half + vl y, half + vl z) in double
+ *   p = p0 except p_i = (p0_i (double)r1 + (p0_i + vl) (double)r0) / (double)(r0 + r1);  the point is p + origin
+ *   colour: (c0 (double)r1 + c1 (double)r0) / (double)(r0 + r1) per component, then / 255.0 for RGB8 only
+ *   normal, in double: g = 0.99 vl;  n_k = T(p + g e_k) - T(p - g e_k) with p in volume coordinates (without the
+ *   origin);  T(q): a = q / vl - 0.5 per component, idx = floor(a), r = a - idx;  the value is the eight-corner sum in
+ *   the order 000, 001, 010, 011, 100, 101, 110, 111 of the offsets (x y z), each term
+ *   ((wx wy) wz) (double)tsdf(idx + offset) with w = r for offset 1 and 1.0 - r for offset 0, the first term starting
+ *   the sum.  A corner outside the volume has tsdf 0 (DEPARTURE: Open3D reads out of bounds there).  Then
+ *   s = (n_0 n_0 + n_1 n_1) + n_2 n_2 and n = n / sqrt(s) (three divisions) if s > 0.
+ * teaser_hip_tsdf_extract_voxel_point_cloud: every usable voxel in x, y, z order: the point
+ * ((half + vl x) + origin_x, ...), the colour ((double)tsdf + 1.0) 0.5 three times.
+ * Both: count_out (required) receives the number of rows.  capacity = 0 with points NULL returns the count alone.
+ * Otherwise points has room for capacity x 3 doubles and normals, colors are NULL or as large (colors of the surface
+ * only for a volume with a colour type).  A capacity below the count is TEASER_HIP_ERR_BAD_ARG: the message names the
+ * count, count_out holds it, and no row is written.  Rows behind the count are not written.
+ *
+ * teaser_hip_tsdf_download / _upload: tsdf_weight is R^3 x 2 float32 (tsdf, weight), color R^3 x 3 doubles (only for a
+ * volume with a colour type), both in Open3D's voxel order (x R + y) R + z whatever the device layout is; either may be
+ * NULL, not both.  upload refuses values that are not finite, except a NaN colour of a Gray32 volume, which is stored
+ * as the quiet NaN.
+ *
+ * TEASER_HIP_ERR_BAD_ARG (the argument and the frame are named; the handle stays usable; create has no handle yet, so
+ * teaser_hip_tsdf_last_error(NULL) returns the calling thread's last create message): resolution outside [1, 1024];
+ * length or sdf_trunc not finite or <= 0; origin not finite; color_type outside {0, 1, 2}; reserved != 0; per frame
+ * width or height negative or above 16384, fx or fy zero or not finite, cx, cy, the extrinsic, depth_scale or
+ * depth_trunc not finite, depth_scale <= 0, depth_format outside {0, 1}, color_format outside [0, 3] or not the one the
+ * volume's colour type needs, row bytes below a row's size; NULL where something is required; a capacity below the
+ * count.  An allocation failure is TEASER_HIP_ERR_OOM.  Every call is deterministic: the same bits run after run, for
+ * any split of the frames into calls.  One stream synchronisation per call; the number of launches does not depend on
+ * the data. */
+typedef struct teaser_tsdf_volume_c {
+  double length;      /* the cube's side; default 4.0 */
+  double sdf_trunc;   /* default 0.04 */
+  double origin[3];   /* the corner of voxel (0, 0, 0); default 0 */
+  int32_t resolution; /* R; default 512 */
+  int32_t color_type; /* 0 none (default), 1 RGB8, 2 Gray32 */
+  int64_t reserved;   /* must be 0 */
+} teaser_tsdf_volume_c;
+typedef struct teaser_tsdf_frame_c {
+  int32_t width, height;
+  int32_t depth_format;    /* 0 uint16, 1 float32 */
+  int32_t color_format;    /* 0 none, 1 uint8 x 3 (RGB), 2 float32 x 1, 3 float32 x 3 */
+  int64_t depth_row_bytes; /* bytes from one row of the depth image to the next */
+  int64_t color_row_bytes; /* likewise for the colour image; not read by a volume without colour */
+  double fx, fy, cx, cy;
+  double extrinsic[16];    /* row-major, world to camera */
+  double depth_scale;
+  double depth_trunc;
+} teaser_tsdf_frame_c;
+#ifdef __cplusplus
+static_assert(sizeof(teaser_tsdf_volume_c) == 56, "teaser_tsdf_volume_c is 56 bytes");
+static_assert(sizeof(teaser_tsdf_frame_c) == 208, "teaser_tsdf_frame_c is 208 bytes");
+#else
+_Static_assert(sizeof(teaser_tsdf_volume_c) == 56, "teaser_tsdf_volume_c is 56 bytes");
+_Static_assert(sizeof(teaser_tsdf_frame_c) == 208, "teaser_tsdf_frame_c is 208 bytes");
+#endif
+typedef struct teaser_hip_tsdf teaser_hip_tsdf;
+/* The defaults noted beside the fields above. */
+TEASER_HIP_API int32_t teaser_hip_tsdf_volume_default(teaser_tsdf_volume_c* volume);
+/* device < 0: the current HIP device.  The record is checked first; then TEASER_HIP_ERR_NO_DEVICE without a GPU: there
+ * is no CPU path.  The volume is allocated (8 bytes per voxel, 32 with a colour type) and zeroed here. */
+TEASER_HIP_API int32_t teaser_hip_tsdf_create(const teaser_tsdf_volume_c* volume, int32_t device, teaser_hip_tsdf** out);
+TEASER_HIP_API int32_t teaser_hip_tsdf_destroy(teaser_hip_tsdf* tsdf);
+TEASER_HIP_API const char* teaser_hip_tsdf_last_error(const teaser_hip_tsdf* tsdf);
+/* Every voxel back to the state after create. */
+TEASER_HIP_API int32_t teaser_hip_tsdf_reset(teaser_hip_tsdf* tsdf);
+TEASER_HIP_API int32_t teaser_hip_tsdf_integrate_batch(teaser_hip_tsdf* tsdf, int32_t n_frames,
+                                                       const teaser_tsdf_frame_c* frames, const void* const* depth,
+                                                       const void* const* color);
+TEASER_HIP_API int32_t teaser_hip_tsdf_extract_point_cloud(teaser_hip_tsdf* tsdf, int64_t capacity, double* points,
+                                                           double* normals, double* colors, int64_t* count_out);
+TEASER_HIP_API int32_t teaser_hip_tsdf_extract_voxel_point_cloud(teaser_hip_tsdf* tsdf, int64_t capacity, double* points,
+                                                                 double* colors, int64_t* count_out);
+TEASER_HIP_API int32_t teaser_hip_tsdf_download(teaser_hip_tsdf* tsdf, float* tsdf_weight, double* color);
+TEASER_HIP_API int32_t teaser_hip_tsdf_upload(teaser_hip_tsdf* tsdf, const float* tsdf_weight, const double* color);
+
 /* Page-locked host memory from the HIP runtime THIS library runs on.  teaser_hip_submit_batch(..., INPUT_HOST) moves
  * the points with one DMA copy per cloud, at PCIe speed only when the runtime knows the pages are locked.  A buffer
  * pinned by another HIP runtime instance in the same process (e.g. the one a Python framework bundles) is pageable

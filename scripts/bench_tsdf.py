@@ -1,0 +1,176 @@
+#!/usr/bin/env python3
+"""TSDF volume integration (UniformTSDFVolume on its own handle) on the MI355X: what a call costs, how much of it is the
+kernel, and what applying several frames per pass over the volume buys.
+
+  (1) 64 frames of 640 x 480 uint16 (the analytic scene of examples/teaser_python_tsdf.py, 16 poses four times over)
+      into R = 256 and R = 512, without colour and with RGB8, in ONE call (passes of 8 frames) and as 64 calls (passes
+      of one frame); the two volumes must hold the same bits;
+  (2) extract_point_cloud (with normals) and extract_voxel_point_cloud from each of those volumes;
+  (3) the numpy restatement (tests/tsdf_reference.py) at R = 32 on 8 frames of 160 x 120, for context only.
+
+Call times are a host clock around a Python call that ends in a device synchronise, after `--warmup` untimed calls:
+median, minimum and maximum of `--reps` (at least nine).  An integration call includes the host's checks, the packing of
+the rows into page-locked memory, the upload, the launches and the synchronisation.  The volume keeps accumulating over
+the timed calls: the voxels a frame touches do not depend on what the volume holds, so every call does the same work.
+
+Kernel time comes from a run of its own: `--profile-workload` runs the calls of (1) and (2) at one setting and writes
+nothing; `rocprofv3 --kernel-trace --stats` is pointed at it, and its kernel_stats.csv is kept beside the JSON.  The
+bytes the integration kernel moves per pass -- every touched voxel read and written once, plus the images read once --
+follow from `touched_voxels_per_pass` in the JSON (counted at R <= 256 by integrating each chunk into an emptied volume
+and downloading the weights); over the kernel's time they give the share of the 8 TB/s HBM peak that
+profiles/tsdf/README.md works out.  Needs an MI355X: there is no CPU path.
+
+    python scripts/bench_tsdf.py --reps 9 --warmup 1 --out profiles/tsdf/bench_tsdf.json"""
+import argparse
+import importlib
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+sys.path.insert(0, os.path.join(ROOT, "examples"))
+tp = importlib.import_module("teaser-plusplus_amd")
+ex = importlib.import_module("teaser_python_tsdf")
+
+W, H, FRAMES, POSES, CHUNK = 640, 480, 64, 16, 8
+HBM_PEAK = 8.0e12
+
+
+def timed(fn, reps, warmup):
+    for _ in range(warmup):
+        fn()
+    ts = []
+    for _ in range(reps):
+        t = time.perf_counter()
+        fn()
+        ts.append(1e3 * (time.perf_counter() - t))
+    return dict(median_ms=float(np.median(ts)), min_ms=float(min(ts)), max_ms=float(max(ts)), reps=reps)
+
+
+def workload():
+    """(K, 64 depth frames, 64 extrinsics, 64 RGB images)."""
+    K, depths, ext = ex.scene_frames(W, H, POSES)
+    rng = np.random.default_rng(5)
+    rgb = [rng.integers(0, 256, size=(H, W, 3)).astype(np.uint8) for _ in range(POSES)]
+    rep = FRAMES // POSES
+    return K, depths * rep, ext * rep, rgb * rep
+
+
+def make(R, colour):
+    length, R, trunc, origin = ex.volume_settings(R)
+    return tp.UniformTSDFVolume(length, R, trunc, tp.TSDFVolumeColorType.RGB8 if colour else tp.TSDFVolumeColorType.NoColor, origin)
+
+
+def one_call(vol, K, d, e, c):
+    vol.integrate_batch(d, K, e, c, 1000.0, 6.0)
+
+
+def many_calls(vol, K, d, e, c):
+    for k in range(len(d)):
+        vol.integrate(d[k], K, e[k], None if c is None else c[k], 1000.0, 6.0)
+
+
+def touched_per_pass(R, colour, K, d, e, c):
+    """Per pass of CHUNK frames the voxels it touches: each chunk goes into an emptied volume, the weights come back."""
+    out = []
+    with make(R, colour) as vol:
+        for k in range(0, FRAMES, CHUNK):
+            vol.reset()
+            one_call(vol, K, d[k:k + CHUNK], e[k:k + CHUNK], None if c is None else c[k:k + CHUNK])
+            out.append(int(np.count_nonzero(vol.extract_volume_tsdf()[:, 1])))
+    return out
+
+
+def run_setting(R, colour, K, d, e, c, reps, warmup, compare_colour):
+    cc = c if colour else None
+    res = dict(R=R, colour=bool(colour), voxel_bytes=32 if colour else 8)
+    with make(R, colour) as a, make(R, colour) as b:
+        one_call(a, K, d, e, cc)
+        many_calls(b, K, d, e, cc)
+        ta, tb = a.extract_volume_tsdf(), b.extract_volume_tsdf()
+        res["same_bits_tsdf_weight"] = bool(np.array_equal(ta.view(np.uint32), tb.view(np.uint32)))
+        res["observed_voxels"] = int(np.count_nonzero(ta[:, 1]))
+        del ta, tb
+        if colour and compare_colour:
+            res["same_bits_colour"] = bool(a.extract_volume_color().tobytes() == b.extract_volume_color().tobytes())
+        pc = a.extract_point_cloud()
+        res["surface_points"] = len(pc.points)
+        res["max_distance_to_surface"] = float(ex.distance_to_surface(pc.points).max())
+        res["extract_point_cloud"] = timed(lambda: a.extract_point_cloud(), reps, warmup)
+        res["extract_point_cloud_no_normals"] = timed(lambda: a.extract_point_cloud(normals=False), reps, warmup)
+        res["voxel_points"] = len(a.extract_voxel_point_cloud().points)
+        res["extract_voxel_point_cloud"] = timed(lambda: a.extract_voxel_point_cloud(), reps, warmup)
+        res["integrate_one_call_64_frames"] = timed(lambda: one_call(a, K, d, e, cc), reps, warmup)
+        res["integrate_64_calls"] = timed(lambda: many_calls(b, K, d, e, cc), reps, warmup)
+    for key in ("integrate_one_call_64_frames", "integrate_64_calls"):
+        res[key]["ms_per_frame"] = res[key]["median_ms"] / FRAMES
+    return res
+
+
+def restatement():
+    import tsdf_reference as T
+    K, d, e = ex.scene_frames(160, 120, 8)
+    length, R, trunc, origin = ex.volume_settings(32)
+    t = time.perf_counter()
+    vol = T.Volume(length, R, trunc, T.NONE, origin)
+    for k in range(8):
+        vol.integrate(d[k], (K.fx, K.fy, K.cx, K.cy), e[k], None, 1000.0, 6.0)
+    t1 = time.perf_counter()
+    P, _, _ = vol.extract_point_cloud()
+    t2 = time.perf_counter()
+    with tp.UniformTSDFVolume(length, R, trunc, 0, origin) as g:
+        g.integrate_batch(d, K, e, None, 1000.0, 6.0)
+        same = g.extract_volume_tsdf().tobytes() == vol.tsdf_weight().tobytes() and g.extract_point_cloud().points.tobytes() == P.tobytes()
+    return dict(R=32, frames=8, width=160, height=120, integrate_ms=1e3 * (t1 - t), extract_ms=1e3 * (t2 - t1), points=len(P),
+                device_equals_restatement=bool(same))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reps", type=int, default=9)
+    ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--sizes", type=int, nargs="+", default=[256, 512])
+    ap.add_argument("--profile-workload", choices=["one_call", "calls", "extract"], default=None)
+    ap.add_argument("--profile-R", type=int, default=512)
+    ap.add_argument("--profile-colour", type=int, default=1)
+    a = ap.parse_args()
+    if tp.device_count() < 1:
+        sys.exit("bench_tsdf.py needs an MI355X: no HIP device visible")
+    K, d, e, c = workload()
+    if a.profile_workload:
+        cc = c if a.profile_colour else None
+        with make(a.profile_R, a.profile_colour) as vol:
+            for _ in range(3):
+                if a.profile_workload == "one_call":
+                    one_call(vol, K, d, e, cc)
+                elif a.profile_workload == "calls":
+                    many_calls(vol, K, d, e, cc)
+                else:
+                    one_call(vol, K, d[:CHUNK], e[:CHUNK], None if cc is None else cc[:CHUNK])
+                    vol.extract_point_cloud()
+                    vol.extract_voxel_point_cloud()
+        return
+    out = dict(workload=dict(width=W, height=H, frames=FRAMES, poses=POSES, chunk=CHUNK, hbm_peak=HBM_PEAK), settings=[])
+    for R in a.sizes:
+        for colour in (0, 1):
+            r = run_setting(R, colour, K, d, e, c, a.reps, a.warmup, compare_colour=R <= 256)
+            if R <= 256:
+                r["touched_voxels_per_pass"] = touched_per_pass(R, colour, K, d, e, c)
+            print(json.dumps(r), flush=True)
+            out["settings"].append(r)
+    out["restatement"] = restatement()
+    print(json.dumps(out["restatement"]), flush=True)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            json.dump(out, f, indent=1)
+
+
+if __name__ == "__main__":
+    main()

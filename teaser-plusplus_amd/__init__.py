@@ -164,6 +164,9 @@ EXPORTED_SYMBOLS = [
     "teaser_hip_plane_create", "teaser_hip_plane_destroy", "teaser_hip_plane_last_error",
     "teaser_hip_plane_params_default", "teaser_hip_plane_segment_batch", "teaser_hip_plane_segment",
     "teaser_hip_plane_set_option", "teaser_hip_plane_get_option", "teaser_hip_plane_trials_batch",
+    "teaser_hip_tsdf_volume_default", "teaser_hip_tsdf_create", "teaser_hip_tsdf_destroy", "teaser_hip_tsdf_last_error",
+    "teaser_hip_tsdf_reset", "teaser_hip_tsdf_integrate_batch", "teaser_hip_tsdf_extract_point_cloud",
+    "teaser_hip_tsdf_extract_voxel_point_cloud", "teaser_hip_tsdf_download", "teaser_hip_tsdf_upload",
 ]
 
 
@@ -277,6 +280,8 @@ def lib():
     _fgr.declare(L)
     from . import plane as _plane
     _plane.declare(L)
+    from . import tsdf as _tsdf
+    _tsdf.declare(L)
     _lib = L
     return L
 
@@ -1164,6 +1169,7 @@ from .fgr import (FastGlobalRegistrationOption, registration_fgr_based_on_corres
                   fgr_iterations_batch, set_fgr_option, get_fgr_option)
 from .plane import (segment_plane, segment_plane_batch, plane_trials_batch, set_plane_option,  # noqa: E402
                     get_plane_option)
+from .tsdf import UniformTSDFVolume, TSDFVolumeColorType, TSDFPointCloud  # noqa: E402
 
 __all__ = ["batched", "FPFHEstimation", "Matcher", "MultiDeviceSolver", "RobustRegistrationSolver", "RegistrationSolution", "RotationEstimationAlgorithm",
            "InlierSelectionMode", "InlierGraphFormulation", "TeaserHipError", "synth_problem",
@@ -1205,4 +1211,5 @@ __all__ = ["batched", "FPFHEstimation", "Matcher", "MultiDeviceSolver", "RobustR
            "FastGlobalRegistrationOption", "registration_fgr_based_on_correspondence",
            "registration_fgr_based_on_correspondence_batch", "registration_fgr_based_on_feature_matching",
            "fgr_iterations_batch", "set_fgr_option", "get_fgr_option",
-           "segment_plane", "segment_plane_batch", "plane_trials_batch", "set_plane_option", "get_plane_option"]
+           "segment_plane", "segment_plane_batch", "plane_trials_batch", "set_plane_option", "get_plane_option",
+           "UniformTSDFVolume", "TSDFVolumeColorType", "TSDFPointCloud"]

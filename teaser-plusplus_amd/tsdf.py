@@ -1,0 +1,268 @@
+"""TSDF volume integration on the GPU with the surface of open3d.pipelines.integration.UniformTSDFVolume: depth frames
+and their camera poses in, one fused cloud out.
+
+    vol = UniformTSDFVolume(length=4.0, resolution=512, sdf_trunc=0.04, color_type=TSDFVolumeColorType.RGB8)
+    vol.integrate_batch(depths, intrinsic, extrinsics, colors)     # any number of frames in one call
+    cloud = vol.extract_point_cloud()                              # .points, .normals, .colors
+
+The volume lives on the device from construction to ``close()`` (or garbage collection): frames go up at two bytes per
+pixel, only the extracted surface comes back.  The arithmetic is written out in include/teaser_hip.h ("TSDF volume"):
+float32 as Open3D forms it, frames applied in the order given, a voxel's bits the same for any split of the frames into
+calls; bit parity with an Open3D binary is not claimed.  ``extrinsic`` is world-to-camera as in Open3D.
+
+Images are numpy arrays: depth ``height x width`` uint16 or float32; colour ``height x width x 3`` uint8 for an RGB8
+volume, ``height x width`` float32 for a Gray32 volume.  Rows may lie any distance apart.  Every volume has a handle of
+its own (a lock serialises its calls).  Without a GPU the constructor raises TeaserHipError (NO_DEVICE): there is no CPU
+path."""
+import ctypes as C
+import math
+import threading
+
+import numpy as np
+
+from .rgbd import _each, _fxfycxcy, _image, _is_intrinsic, _is_matrix, _is_scalar
+
+_vp, _dp, _fp, _i64p = C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_float), C.POINTER(C.c_int64)
+
+
+class TsdfVolumeC(C.Structure):
+    """teaser_tsdf_volume_c (include/teaser_hip.h)."""
+    _fields_ = [("length", C.c_double), ("sdf_trunc", C.c_double), ("origin", C.c_double * 3),
+                ("resolution", C.c_int32), ("color_type", C.c_int32), ("reserved", C.c_int64)]
+
+
+class TsdfFrameC(C.Structure):
+    """teaser_tsdf_frame_c (include/teaser_hip.h)."""
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("depth_format", C.c_int32), ("color_format", C.c_int32),
+                ("depth_row_bytes", C.c_int64), ("color_row_bytes", C.c_int64), ("fx", C.c_double), ("fy", C.c_double),
+                ("cx", C.c_double), ("cy", C.c_double), ("extrinsic", C.c_double * 16), ("depth_scale", C.c_double),
+                ("depth_trunc", C.c_double)]
+
+
+assert C.sizeof(TsdfVolumeC) == 56 and C.sizeof(TsdfFrameC) == 208  # the header asserts the same
+
+
+def declare(L):
+    """ctypes signatures of the entry points (called by the package's lib())."""
+    L.teaser_hip_tsdf_volume_default.argtypes = [C.POINTER(TsdfVolumeC)]
+    L.teaser_hip_tsdf_create.argtypes = [C.POINTER(TsdfVolumeC), C.c_int32, C.POINTER(_vp)]
+    L.teaser_hip_tsdf_destroy.argtypes = [_vp]
+    L.teaser_hip_tsdf_last_error.argtypes = [_vp]
+    L.teaser_hip_tsdf_last_error.restype = C.c_char_p
+    L.teaser_hip_tsdf_reset.argtypes = [_vp]
+    L.teaser_hip_tsdf_integrate_batch.argtypes = [_vp, C.c_int32, C.POINTER(TsdfFrameC), C.POINTER(_vp), C.POINTER(_vp)]
+    L.teaser_hip_tsdf_extract_point_cloud.argtypes = [_vp, C.c_int64, _dp, _dp, _dp, _i64p]
+    L.teaser_hip_tsdf_extract_voxel_point_cloud.argtypes = [_vp, C.c_int64, _dp, _dp, _i64p]
+    L.teaser_hip_tsdf_download.argtypes = [_vp, _fp, _dp]
+    L.teaser_hip_tsdf_upload.argtypes = [_vp, _fp, _dp]
+
+
+class TSDFVolumeColorType:
+    """Open3D's pipelines.integration.TSDFVolumeColorType."""
+    NoColor, RGB8, Gray32 = 0, 1, 2
+
+
+class TSDFPointCloud:
+    """What the extractions return: ``points`` (count x 3 float64) and, where they exist, ``normals`` and ``colors``
+    (count x 3 float64, else None)."""
+
+    def __init__(self, points, normals=None, colors=None):
+        self.points, self.normals, self.colors = points, normals, colors
+
+    def __len__(self):
+        return len(self.points)
+
+
+class UniformTSDFVolume:
+    """Open3D's UniformTSDFVolume(length, resolution, sdf_trunc, color_type, origin): a cube of resolution^3 voxels with
+    its corner at ``origin``, kept on ``device`` (-1: the current one)."""
+
+    def __init__(self, length, resolution, sdf_trunc, color_type=TSDFVolumeColorType.NoColor, origin=(0.0, 0.0, 0.0),
+                 device=-1):
+        from . import TeaserHipError, lib
+        if int(resolution) != resolution or not 1 <= int(resolution) <= 1024:
+            raise ValueError("resolution must be an integer in [1, 1024]")
+        if not (math.isfinite(float(length)) and float(length) > 0):
+            raise ValueError("length must be finite and > 0")
+        if not (math.isfinite(float(sdf_trunc)) and float(sdf_trunc) > 0):
+            raise ValueError("sdf_trunc must be finite and > 0")
+        if color_type not in (0, 1, 2):
+            raise ValueError("color_type must be one of TSDFVolumeColorType.NoColor, RGB8, Gray32")
+        o = np.asarray(origin, dtype=np.float64)
+        if o.shape != (3,) or not np.isfinite(o).all():
+            raise ValueError("origin must be three finite numbers")
+        self.length, self.sdf_trunc, self.color_type = float(length), float(sdf_trunc), int(color_type)
+        self._resolution, self.origin = int(resolution), o.copy()
+        self._lib = lib()
+        rec = TsdfVolumeC()
+        self._lib.teaser_hip_tsdf_volume_default(C.byref(rec))
+        rec.length, rec.sdf_trunc, rec.resolution, rec.color_type = self.length, self.sdf_trunc, self._resolution, self.color_type
+        rec.origin[:] = list(o)
+        self._h = _vp()
+        self._lock = threading.Lock()
+        rc = self._lib.teaser_hip_tsdf_create(C.byref(rec), int(device), C.byref(self._h))
+        if rc != 0:
+            self._h = None
+            msg = self._lib.teaser_hip_tsdf_last_error(None).decode()
+            raise TeaserHipError(rc, "(no MI355X visible: the product has no CPU path)" if rc == 3 else msg)
+
+    # ---- the handle ---------------------------------------------------------------------------------------------
+    def _call(self, fn, *args):
+        from . import TeaserHipError
+        if self._h is None:
+            raise ValueError("the volume is closed")
+        with self._lock:  # the handle serves one call at a time
+            rc = fn(self._h, *args)
+            err = self._lib.teaser_hip_tsdf_last_error(self._h).decode() if rc != 0 else ""
+        if rc != 0:
+            raise TeaserHipError(rc, err)
+
+    def close(self):
+        """Frees the volume; the object is unusable afterwards."""
+        h, self._h = getattr(self, "_h", None), None
+        if h is not None:
+            self._lib.teaser_hip_tsdf_destroy(h)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # interpreter shutdown
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    @property
+    def voxel_length(self):
+        return self.length / self._resolution
+
+    @property
+    def resolution(self):
+        return self._resolution
+
+    # ---- integration --------------------------------------------------------------------------------------------
+    def _frames(self, depths, intrinsic, extrinsics, colors, depth_scale, depth_trunc):
+        b = len(depths)
+        cols = list(colors) if colors is not None else [None] * b
+        if len(cols) != b:
+            raise ValueError("colors: one image per frame")
+        K = [_fxfycxcy(k) for k in _each(intrinsic, b, "intrinsic", _is_intrinsic)]
+        ext = _each(extrinsics, b, "extrinsics", _is_matrix)
+        scale, trunc = _each(depth_scale, b, "depth_scale", _is_scalar), _each(depth_trunc, b, "depth_trunc", _is_scalar)
+        frames = (TsdfFrameC * max(b, 1))()
+        dimg, cimg = [], []
+        for k in range(b):
+            d, dpx = _image(depths[k], "depth", (np.uint16, np.float32), (1,))
+            if d.ndim != 2:
+                raise ValueError("depth has shape %s" % (d.shape,))
+            E = np.array(np.eye(4) if ext[k] is None else ext[k], dtype=np.float64)
+            if E.shape != (4, 4):
+                raise ValueError("extrinsic must be a 4 x 4 matrix")
+            f = frames[k]
+            f.height, f.width = d.shape
+            f.depth_format = 0 if d.dtype == np.uint16 else 1
+            f.depth_row_bytes = d.strides[0] if d.size else d.shape[1] * dpx
+            c = cols[k]
+            if self.color_type == TSDFVolumeColorType.NoColor:
+                c = None  # Open3D ignores the colour image of a frame here, too
+            elif c is None:
+                raise ValueError("color: a volume with a colour type needs a colour image per frame")
+            else:
+                want = (np.uint8,) if self.color_type == TSDFVolumeColorType.RGB8 else (np.float32,)
+                c, cpx = _image(c, "color", want, (3,) if self.color_type == TSDFVolumeColorType.RGB8 else (1,))
+                if c.shape[:2] != d.shape:
+                    raise ValueError("color has shape %s beside a depth image of shape %s" % (c.shape, d.shape))
+                f.color_format = 1 if self.color_type == TSDFVolumeColorType.RGB8 else 2
+                f.color_row_bytes = c.strides[0] if c.size else c.shape[1] * cpx
+            f.fx, f.fy, f.cx, f.cy = K[k]
+            f.extrinsic[:] = list(E.ravel())
+            f.depth_scale, f.depth_trunc = float(scale[k]), float(trunc[k])
+            dimg.append(d)
+            cimg.append(c)
+        return b, frames, dimg, cimg
+
+    def integrate_batch(self, depths, intrinsic, extrinsics, colors=None, depth_scale=1000.0, depth_trunc=3.0):
+        """The frames, in the order given, in one call: a voxel ends with the bits that one integrate() per frame leaves.
+        depths: a list of depth images; colors: a list of colour images (ignored by a volume without colour);
+        intrinsic, extrinsics, depth_scale, depth_trunc: one for all frames or a list with one per frame."""
+        if len(depths) == 0:
+            return
+        b, frames, dimg, cimg = self._frames(depths, intrinsic, extrinsics, colors, depth_scale, depth_trunc)
+
+        def ptrs(arrs):
+            return (_vp * b)(*[None if a is None or a.size == 0 else a.ctypes.data_as(_vp) for a in arrs])
+        self._call(self._lib.teaser_hip_tsdf_integrate_batch, b, frames, ptrs(dimg), ptrs(cimg))
+
+    def integrate(self, depth, intrinsic, extrinsic, color=None, depth_scale=1000.0, depth_trunc=3.0):
+        """Open3D's integrate(rgbd, intrinsic, extrinsic) with the RGBD image given as its parts: the depth image, and
+        for a volume with a colour type the colour image."""
+        self.integrate_batch([depth], intrinsic, extrinsic, None if color is None else [color], depth_scale, depth_trunc)
+
+    # ---- extraction ---------------------------------------------------------------------------------------------
+    def _extract(self, fn, outputs):
+        """The count first, then the rows into arrays of exactly that size; outputs: which optional arrays to ask for."""
+        cnt = C.c_int64(0)
+        none = [None] * (1 + len(outputs))
+        self._call(fn, 0, *none, C.byref(cnt))
+        n = int(cnt.value)
+        pts = np.empty((n, 3))
+        extra = [np.empty((n, 3)) if want else None for want in outputs]
+        if n:
+            self._call(fn, n, pts.ctypes.data_as(_dp), *[None if a is None else a.ctypes.data_as(_dp) for a in extra],
+                       C.byref(cnt))
+        return pts, extra
+
+    def extract_point_cloud(self, normals=True):
+        """Open3D's extract_point_cloud: the zero crossings between neighbouring voxels in Open3D's order, with their
+        normals (unless normals=False) and, for a volume with a colour type, their colours."""
+        pts, (nrm, col) = self._extract(self._lib.teaser_hip_tsdf_extract_point_cloud,
+                                        [bool(normals), self.color_type != TSDFVolumeColorType.NoColor])
+        return TSDFPointCloud(pts, nrm, col)
+
+    def extract_voxel_point_cloud(self):
+        """Open3D's extract_voxel_point_cloud: the centre of every observed voxel with (tsdf + 1) / 2 as its colour."""
+        pts, (col,) = self._extract(self._lib.teaser_hip_tsdf_extract_voxel_point_cloud, [True])
+        return TSDFPointCloud(pts, None, col)
+
+    # ---- the voxels ---------------------------------------------------------------------------------------------
+    def extract_volume_tsdf(self):
+        """R^3 x 2 float32 (tsdf, weight) in Open3D's voxel order (x R + y) R + z."""
+        out = np.empty((self._resolution ** 3, 2), dtype=np.float32)
+        self._call(self._lib.teaser_hip_tsdf_download, out.ctypes.data_as(_fp), None)
+        return out
+
+    def extract_volume_color(self):
+        """R^3 x 3 float64 in Open3D's voxel order (a volume with a colour type only)."""
+        if self.color_type == TSDFVolumeColorType.NoColor:
+            raise ValueError("the volume has no colour")
+        out = np.empty((self._resolution ** 3, 3))
+        self._call(self._lib.teaser_hip_tsdf_download, None, out.ctypes.data_as(_dp))
+        return out
+
+    def inject_volume_tsdf(self, tsdf_weight):
+        a = np.ascontiguousarray(tsdf_weight, dtype=np.float32)
+        if a.shape != (self._resolution ** 3, 2):
+            raise ValueError("tsdf_weight must have shape %d x 2, got %s" % (self._resolution ** 3, a.shape))
+        if not np.isfinite(a).all():
+            raise ValueError("tsdf_weight has a non-finite value")
+        self._call(self._lib.teaser_hip_tsdf_upload, a.ctypes.data_as(_fp), None)
+
+    def inject_volume_color(self, color):
+        if self.color_type == TSDFVolumeColorType.NoColor:
+            raise ValueError("the volume has no colour")
+        a = np.ascontiguousarray(color, dtype=np.float64)
+        if a.shape != (self._resolution ** 3, 3):
+            raise ValueError("color must have shape %d x 3, got %s" % (self._resolution ** 3, a.shape))
+        if not (np.isfinite(a) | (np.isnan(a) if self.color_type == TSDFVolumeColorType.Gray32 else False)).all():
+            raise ValueError("color has a non-finite value")
+        self._call(self._lib.teaser_hip_tsdf_upload, None, a.ctypes.data_as(_dp))
+
+    def reset(self):
+        """Every voxel back to the empty state."""
+        self._call(self._lib.teaser_hip_tsdf_reset)
+
+
+__all__ = ["UniformTSDFVolume", "TSDFVolumeColorType", "TSDFPointCloud"]
