@@ -1080,6 +1080,178 @@ TEASER_HIP_API int32_t teaser_hip_icp_project_depth_batch(teaser_hip_icp* icp, i
                                                           const int32_t* n, const teaser_icp_projection_c* cameras,
                                                           float* const* depth_out, float* const* color_out,
                                                           int32_t* const* index_out, int32_t* n_hit_out);
+/* RGB-D odometry (Open3D's pipelines.odometry.compute_rgbd_odometry with RGBDOdometryJacobianFromColorTerm /
+ * FromHybridTerm), batched, on the ICP handle: the motion between two RGB-D frames, source to target, with its 6 x 6
+ * information matrix.  The text below IS the contract; it restates Open3D's Odometry.cpp, RGBDOdometryJacobian.cpp and
+ * Image filters from knowledge and fixes what Open3D leaves to a race.  No product-add is fused; every sum is taken left
+ * to right as written; "float32" operations round to float32 after every operation, everything else is FP64.
+ * tests/odometry_reference.py restates this text; bit parity with an Open3D binary is NOT claimed.  Every float32 value
+ * that is stored in an image is stored as the quiet NaN 0x7fc00000 when it is a NaN, every double that is handed out as
+ * 0x7ff8000000000000.
+ *
+ * Per pair one record teaser_icp_odometry_pair_c and four images: source and target depth (uint16 or float32), source
+ * and target colour (color_format 1: uint8 x 3, RGB; 2: float32 x 1, an intensity).  Rows may be padded; only the first
+ * width samples of a row are read.  One record teaser_icp_odometry_option_c serves the call: n_levels L in 1 .. 8 and
+ * iterations[0 .. L - 1], iterations[0] belonging to the COARSEST level (Open3D's iteration_number_per_pyramid_level).
+ *
+ * Images.  Level l of a pair has w_l = width >> l columns, h_l = height >> l rows, n_l = w_l h_l pixels and eleven
+ * float32 planes, row-major: 0 I_s, 1 I_t (intensity of source, target), 2 D_s, 3 D_t (depth), 4 X, 5 Y, 6 Z (the source
+ * XYZ image), 7 I_t dx, 8 I_t dy, 9 D_t dx, 10 D_t dy.  Level intrinsics: fx_l = fx 2^-l, and so fy_l, cx_l, cy_l.
+ *   filter      F(p; kh, kv)(y, x) = (kv[0] H(y - 1, x) + kv[1] H(y, x)) + kv[2] H(y + 1, x) with
+ *               H(y, x) = (kh[0] p(y, x - 1) + kh[1] p(y, x)) + kh[2] p(y, x + 1), float32, row and column indices clamped
+ *               into the image.  Gaussian: kh = kv = (0.25, 0.5, 0.25).  Sobel dx: kh = (-1, 0, 1), kv = (1, 2, 1).  Sobel
+ *               dy: kh = (1, 2, 1), kv = (-1, 0, 1).  A NaN propagates.
+ *   1 convert   depth: zf by the rule of "Depth frames" (uint16: (float)d / (float)depth_scale, 0 when (double)zf >=
+ *               depth_trunc; float32: the sample); then NaN when zf is not finite, (double)zf <= depth_min or (double)zf >
+ *               depth_max.  Intensity: format 1 by the float32 formula of "Depth frames", format 2 the sample.
+ *   2 smooth    planes 0 .. 3 of level 0 = the Gaussian of the converted images.
+ *   3 match     the correspondences at level 0 and pose odo_init (below), n of them.
+ *   4 normalise if n > 0: sum_s = SUM (double)I_s(source pixel), sum_t = SUM (double)I_t(target pixel) over the
+ *               correspondences in the summation order (below); every I_s becomes (float)((0.5 / (sum_s / n)) (double)I_s),
+ *               every I_t likewise with sum_t.  n = 0: the images stay.
+ *   5 XYZ       level 0: z = D_s(y, x);  X = (float)((((double)x - cx) (double)z) (1.0 / fx)),
+ *               Y = (float)((((double)y - cy) (double)z) (1.0 / fy)),  Z = z.
+ *   6 pyramid   level l + 1 from level l:  q(y, x) = (((p(2y, 2x) + p(2y, 2x + 1)) + p(2y + 1, 2x)) + p(2y + 1, 2x + 1)) / 4.0f
+ *               in float32, where p is the Gaussian of plane 0 or 1, and plane 2 .. 6 itself.
+ *   7 gradients planes 7, 8 of every level = Sobel dx, dy of plane 1; planes 9, 10 = Sobel dx, dy of plane 3.
+ *
+ * Correspondences at level l and pose T = [R | t] (row-major 4 x 4, source to target).  With f = fx_l, g = fy_l, a = cx_l,
+ * b = cy_l:  A[0][c] = f R[0][c] + a R[2][c];  A[1][c] = g R[1][c] + b R[2][c];  A[2][c] = R[2][c];
+ *   M[r][0] = A[r][0] / f;  M[r][1] = A[r][1] / g;  M[r][2] = (A[r][2] - (A[r][0] a) / f) - (A[r][1] b) / g;
+ *   Kt = (f t_0 + a t_2, g t_1 + b t_2, t_2)                                   (M = K R K^-1, Kt = K t)
+ * For source pixel (v, u), index s = v w_l + u, with d = D_s(v, u) not a NaN:
+ *   q_r = (double)d ((M[r][0] u + M[r][1] v) + M[r][2]) + Kt_r for r = 0, 1, 2;  skipped unless q_2 > 0
+ *   x = q_0 / q_2 + 0.5, y = q_1 / q_2 + 0.5;  skipped unless both are finite and below 2^31 in magnitude
+ *   ut = (int)x, vt = (int)y (truncated towards zero);  skipped unless 0 <= ut < w_l and 0 <= vt < h_l
+ *   skipped if D_t(vt, ut) is a NaN, unless |q_2 - (double)D_t(vt, ut)| <= depth_diff_max, or if zf = (float)q_2 is not finite
+ *   winner: target pixel (vt, ut) keeps the source pixel with the smallest zf and, among equal zf, the smallest s (the rule
+ *   of "Depth frames"; Open3D leaves ties to a race).  The correspondences are listed in ascending target pixel vt w_l + ut.
+ *
+ * Summation order.  Every sum below runs over the n_l target pixels p = vt w_l + ut of the level; a pixel without a
+ * correspondence contributes +0.0, as do the positions behind n_l.  Blocks of TEASER_HIP_ODOMETRY_BLOCK = 256 consecutive
+ * pixels; within a block four runs of 64, each summed by the tree  for o = 32, 16, 8, 4, 2, 1: v[i] = v[i] + v[i + o] for
+ * i < o;  block = (run_0 + run_1) + (run_2 + run_3).  Groups of TEASER_HIP_ODOMETRY_GROUP = 64 consecutive blocks: a group
+ * sum starts at 0.0 and adds its block sums in ascending order; the total starts at 0.0 and adds the group sums in
+ * ascending order.
+ *
+ * One iteration at level l (pose T).  The correspondences; then per correspondence (target (vt, ut), source (vs, us)):
+ *   P = (X, Y, Z)(vs, us) as doubles;  p_r = ((R[r][0] P_0 + R[r][1] P_1) + R[r][2] P_2) + t_r
+ *   dp = (double)(I_t(vt, ut) - I_s(vs, us)) (the difference in float32);  dg = (double)D_t(vt, ut) - p_2;  iz = 1.0 / p_2
+ *   gIx = 0.125 (double)(I_t dx)(vt, ut), gIy, gDx, gDy likewise from planes 8, 9, 10;  a NaN gDx or gDy counts as 0
+ *   c0 = (gIx f) iz;  c1 = (gIy g) iz;  c2 = (-(c0 p_0 + c1 p_1)) iz;  d0, d1, d2 likewise from gDx, gDy
+ *   colour term (jacobian 0), one row:  J = ((-p_2) c1 + p_1 c2,  p_2 c0 - p_0 c2,  (-p_1) c0 + p_0 c1,  c0, c1, c2),  r = dp
+ *   hybrid term (jacobian 1), two rows with sI = sqrt(1.0 - 0.968), sD = sqrt(0.968):  row 0 = sI times every component of
+ *     the colour row, r_0 = sI dp;  row 1 = sD times (((-p_2) d1 + p_1 d2) - p_1,  (p_2 d0 - p_0 d2) + p_0,
+ *     (-p_1) d0 + p_0 d1,  d0, d1, d2 - 1.0),  r_1 = sD dg
+ *   the pixel's 29 values: J_i J_j for i <= j by rows (21), J_i r (6), r r, and 1.0 -- for two rows the value of row 0
+ *   plus the value of row 1.
+ * Their sums give A (symmetric 6 x 6), g, e and the count n.  A x = -g by LDL^T without pivoting:
+ *   for j = 0 .. 5:  d_j = A[j][j] - SUM_{m < j} (L[j][m] L[j][m]) d_m (subtracted one at a time, m ascending);  the pair
+ *   FAILS if d_j is zero or not finite;  L[i][j] = (A[i][j] - SUM_{m < j} (L[i][m] L[j][m]) d_m) / d_j for i > j.
+ *   the pair FAILS if |((((d_0 d_1) d_2) d_3) d_4) d_5| < 1e-6
+ *   y_i = -g_i - SUM_{m < i} L[i][m] y_m;  y_i = y_i / d_i;  x_i = y_i - SUM_{m > i} L[m][i] x_m for i = 5 .. 0 (m ascending)
+ *   the pair FAILS if an x_i is not finite.
+ * Update: (sa, ca), (sb, cb), (sc, cc) = the deterministic sine and cosine of x_0, x_1, x_2 (csrc/fdet_math.h,
+ * fdet_sincos_d: the reduction and the series are written out there and are part of this contract);
+ *   U = [[cc cb, (cc sb) sa - sc ca, (cc sb) ca + sc sa, x_3], [sc cb, (sc sb) sa + cc ca, (sc sb) ca - cc sa, x_4],
+ *        [-sb, cb sa, cb ca, x_5]];  T'[r][c] = (U[r][0] T[0][c] + U[r][1] T[1][c]) + U[r][2] T[2][c], plus U[r][3] for
+ *   c = 3;  row 3 stays (0, 0, 0, 1).
+ * Levels run from L - 1 down to 0, level l for iterations[L - 1 - l] iterations (an entry may be 0), starting from
+ * odo_init.  A pair that FAILS stops there: success = 0, transformation = the identity, information = zero, count = the
+ * count of the failing iteration; the other pairs of the call are not touched by it.
+ *
+ * Information matrix of a pair that has not failed: the correspondences at level 0 and the final pose; count = their
+ * number.  Per correspondence with z = D_t(vt, ut):  x = (double)(float)((((double)ut - cx) (double)z) (1.0 / fx)),
+ * y likewise with vt, cy, fy, z = (double)z;  rows G_0 = (0, z, -y, 1, 0, 0), G_1 = (-z, 0, x, 0, 1, 0), G_2 = (y, -x, 0, 0,
+ * 0, 1);  the pixel's values (G_0i G_0j + G_1i G_1j) + G_2i G_2j for i <= j, summed in the summation order; information is
+ * the symmetric matrix.
+ *
+ * teaser_hip_icp_rgbd_odometry_batch: results[b] per pair.  trace_out: NULL, or per pair NULL or room for N = SUM
+ * iterations[] records teaser_icp_odometry_trace_c, one per iteration in execution order: level, executed (0 for the
+ * iterations behind a failure: the rest of such a record is zero), count, failed, e, A (21), g (6) and the pose after the
+ * update (the identity when the iteration failed).
+ * teaser_hip_icp_rgbd_odometry_pyramid_batch: steps 1 .. 7 alone, run by the same kernels.  images_out[b] takes
+ * 11 SUM_l n_l float32: level l begins at 11 SUM_{k < l} n_k, plane p of it n_l p further on.
+ * Both calls: batch = 0 does nothing.  The launch sequence depends on the options and the image sizes alone, never on
+ * the data; one stream synchronisation per call.  Every output of a pair is a function of that pair alone: the same bits
+ * alone, at any position of any batch, run after run.
+ * TEASER_HIP_ERR_BAD_ARG (argument and pair named, before the device is asked for; the handle stays usable): NULL where
+ * something is required; depth_format outside {0, 1}, color_format outside {1, 2}, jacobian outside {0, 1}; reserved != 0;
+ * n_levels outside 1 .. 8; a negative iteration count; fx or fy not finite or not > 0; cx, cy, odo_init, depth_scale,
+ * depth_trunc, depth_diff_max, depth_min or depth_max not finite; depth_scale <= 0; depth_diff_max < 0; depth_min < 0;
+ * target_width / target_height different from width / height; width or height below 2^(n_levels - 1) (a level without a
+ * pixel) or above 16384; row bytes below a row's size; more than 2^31 - 1 pixels in one call. */
+#define TEASER_HIP_ODOMETRY_BLOCK 256
+#define TEASER_HIP_ODOMETRY_GROUP 64
+#define TEASER_HIP_ODOMETRY_MAX_LEVELS 8
+typedef struct teaser_icp_odometry_option_c {
+  int32_t n_levels;        /* default 3 */
+  int32_t iterations[8];   /* default {20, 10, 5}: the first entry is the coarsest level's */
+  int32_t reserved[3];     /* must be 0 */
+  double depth_diff_max;   /* default 0.03 */
+  double depth_min;        /* default 0.0 */
+  double depth_max;        /* default 4.0 */
+  double reserved2;        /* must be 0 */
+} teaser_icp_odometry_option_c;
+typedef struct teaser_icp_odometry_pair_c {
+  int32_t width, height;                /* of the source images */
+  int32_t target_width, target_height;  /* must equal them */
+  int32_t depth_format;                 /* 0 uint16, 1 float32 (both depth images) */
+  int32_t color_format;                 /* 1 uint8 x 3 (RGB), 2 float32 x 1 (both colour images) */
+  int32_t jacobian;                     /* 0 colour term, 1 hybrid term */
+  int32_t reserved;                     /* must be 0 */
+  int64_t source_depth_row_bytes, source_color_row_bytes;
+  int64_t target_depth_row_bytes, target_color_row_bytes;
+  double fx, fy, cx, cy;
+  double odo_init[16];                  /* row-major, source to target; row 3 must be finite and counts as (0, 0, 0, 1) */
+  double depth_scale;                   /* uint16 depth only */
+  double depth_trunc;
+} teaser_icp_odometry_pair_c;
+typedef struct teaser_icp_odometry_result_c {
+  int32_t success;
+  int32_t count;            /* correspondences at the final pose (of the failing iteration for a failed pair) */
+  int32_t iterations;       /* iterations executed */
+  int32_t reserved;
+  double transformation[16];
+  double information[36];
+} teaser_icp_odometry_result_c;
+typedef struct teaser_icp_odometry_trace_c {
+  int32_t level, executed, count, failed;
+  double e;
+  double A[21];
+  double g[6];
+  double pose[16];
+  double reserved[2];
+} teaser_icp_odometry_trace_c;
+#ifdef __cplusplus
+static_assert(sizeof(teaser_icp_odometry_option_c) == 80, "teaser_icp_odometry_option_c is 80 bytes");
+static_assert(sizeof(teaser_icp_odometry_pair_c) == 240, "teaser_icp_odometry_pair_c is 240 bytes");
+static_assert(sizeof(teaser_icp_odometry_result_c) == 432, "teaser_icp_odometry_result_c is 432 bytes");
+static_assert(sizeof(teaser_icp_odometry_trace_c) == 384, "teaser_icp_odometry_trace_c is 384 bytes");
+#else
+_Static_assert(sizeof(teaser_icp_odometry_option_c) == 80, "teaser_icp_odometry_option_c is 80 bytes");
+_Static_assert(sizeof(teaser_icp_odometry_pair_c) == 240, "teaser_icp_odometry_pair_c is 240 bytes");
+_Static_assert(sizeof(teaser_icp_odometry_result_c) == 432, "teaser_icp_odometry_result_c is 432 bytes");
+_Static_assert(sizeof(teaser_icp_odometry_trace_c) == 384, "teaser_icp_odometry_trace_c is 384 bytes");
+#endif
+TEASER_HIP_API int32_t teaser_hip_icp_odometry_option_default(teaser_icp_odometry_option_c* option);
+TEASER_HIP_API int32_t teaser_hip_icp_rgbd_odometry_batch(teaser_hip_icp* icp, int32_t batch,
+                                                          const teaser_icp_odometry_pair_c* pairs,
+                                                          const teaser_icp_odometry_option_c* option,
+                                                          const void* const* source_depth,
+                                                          const void* const* source_color,
+                                                          const void* const* target_depth,
+                                                          const void* const* target_color,
+                                                          teaser_icp_odometry_result_c* results,
+                                                          teaser_icp_odometry_trace_c* const* trace_out);
+TEASER_HIP_API int32_t teaser_hip_icp_rgbd_odometry_pyramid_batch(teaser_hip_icp* icp, int32_t batch,
+                                                                  const teaser_icp_odometry_pair_c* pairs,
+                                                                  const teaser_icp_odometry_option_c* option,
+                                                                  const void* const* source_depth,
+                                                                  const void* const* source_color,
+                                                                  const void* const* target_depth,
+                                                                  const void* const* target_color,
+                                                                  float* const* images_out);
 /* Outlier removal: statistical (Open3D's remove_statistical_outlier), on the ICP handle.  Per cloud, with
  * nb_neighbors in [1, TEASER_HIP_ICP_KNN_MAX] and std_ratio finite and > 0:
  *   avg[i]    = (sum of sqrt(d2) over point i's m = min(nb_neighbors, n) nearest of self k-NN, the point itself

@@ -167,6 +167,8 @@ EXPORTED_SYMBOLS = [
     "teaser_hip_tsdf_volume_default", "teaser_hip_tsdf_create", "teaser_hip_tsdf_destroy", "teaser_hip_tsdf_last_error",
     "teaser_hip_tsdf_reset", "teaser_hip_tsdf_integrate_batch", "teaser_hip_tsdf_extract_point_cloud",
     "teaser_hip_tsdf_extract_voxel_point_cloud", "teaser_hip_tsdf_download", "teaser_hip_tsdf_upload",
+    "teaser_hip_icp_odometry_option_default", "teaser_hip_icp_rgbd_odometry_batch",
+    "teaser_hip_icp_rgbd_odometry_pyramid_batch",
 ]
 
 
@@ -282,6 +284,8 @@ def lib():
     _plane.declare(L)
     from . import tsdf as _tsdf
     _tsdf.declare(L)
+    from . import odometry as _odometry
+    _odometry.declare(L)
     _lib = L
     return L
 
@@ -1170,6 +1174,9 @@ from .fgr import (FastGlobalRegistrationOption, registration_fgr_based_on_corres
 from .plane import (segment_plane, segment_plane_batch, plane_trials_batch, set_plane_option,  # noqa: E402
                     get_plane_option)
 from .tsdf import UniformTSDFVolume, TSDFVolumeColorType, TSDFPointCloud  # noqa: E402
+from .odometry import (OdometryOption, RGBDOdometryJacobianFromColorTerm,  # noqa: E402
+                       RGBDOdometryJacobianFromHybridTerm, RGBDImage, compute_rgbd_odometry,
+                       compute_rgbd_odometry_batch, rgbd_odometry_pyramid_batch)
 
 __all__ = ["batched", "FPFHEstimation", "Matcher", "MultiDeviceSolver", "RobustRegistrationSolver", "RegistrationSolution", "RotationEstimationAlgorithm",
            "InlierSelectionMode", "InlierGraphFormulation", "TeaserHipError", "synth_problem",
@@ -1212,4 +1219,6 @@ __all__ = ["batched", "FPFHEstimation", "Matcher", "MultiDeviceSolver", "RobustR
            "registration_fgr_based_on_correspondence_batch", "registration_fgr_based_on_feature_matching",
            "fgr_iterations_batch", "set_fgr_option", "get_fgr_option",
            "segment_plane", "segment_plane_batch", "plane_trials_batch", "set_plane_option", "get_plane_option",
-           "UniformTSDFVolume", "TSDFVolumeColorType", "TSDFPointCloud"]
+           "UniformTSDFVolume", "TSDFVolumeColorType", "TSDFPointCloud",
+           "OdometryOption", "RGBDOdometryJacobianFromColorTerm", "RGBDOdometryJacobianFromHybridTerm", "RGBDImage",
+           "compute_rgbd_odometry", "compute_rgbd_odometry_batch", "rgbd_odometry_pyramid_batch"]

@@ -2,7 +2,7 @@
 // icp_outlier.hip: self k-NN, outlier removal and the options; icp_normals.hip: normal estimation and the
 // self-estimating point-to-plane entry; icp_keypoints.hip: ISS keypoints; icp_cluster.hip: DBSCAN clustering; icp_fps.hip: farthest-point down-sampling; icp_color.hip: Colored ICP;
 // icp_search.hip: neighbour search between two clouds; icp_fpfh.hip: the Open3D-form FPFH and the neighbour lists in
-// pieces; icp_boundary.hip: boundary points; icp_rgbd.hip: depth frames): the handle and its buffers, and the scaffold
+// pieces; icp_boundary.hip: boundary points; icp_rgbd.hip: depth frames; icp_odometry.hip: RGB-D odometry): the handle and its buffers, and the scaffold
 // of a cloud call -- the entry checks (begin_cloud_call), the per-call index under construction (IcpIndex,
 // add_problem), the sizes of the index buffers by name (index_bytes, ensure_buffers), the packing and the uploads
 // (upload_points, upload_inputs), the index build (launch_index), the one copy back (copy_back, read_fallbacks) and
@@ -36,11 +36,12 @@ namespace thip {
 // block map and the list scratch (d2, then indices); boundary points (icp_boundary.hip) run on the same four and add
 // B_BND_DESC, the pieces' IcpBoundaryDesc records.  B_RGBD_*: the depth-frame calls (icp_rgbd.hip): the records of the
 // frames or projections, the packed images (unprojection) or colours (projection), and the tiles' counts and starts
-// (unprojection) or the key image (projection)
+// (unprojection) or the key image (projection).  B_ODO_*: RGB-D odometry (icp_odometry.hip): the image pyramids of all
+// pairs and the level-0 scratch planes; its records, inputs, keys and partials live in B_RGBD_*, B_STATE, B_BLK, B_PARTIALS
 enum { B_DESC, B_STATE, B_BLK, B_TBLK, B_X, B_Q, B_TBUCKET, B_BCOUNT, B_BSTART, B_CURSOR, B_QS, B_QJ, B_MATCH,
        B_PARTIALS, B_LIVE, B_NORMALS, B_COV_S, B_COV_T, B_NDESC, B_NKNN, B_NREC, B_NBLK, B_NTBLK, B_KDESC, B_KBLK,
        B_KKEY, B_KIOTA, B_KSKEY, B_KSIDX, B_KSPTS, B_KTEMP, B_DPARENT, B_DFLAG, B_DSCAN, B_COLOR_DESC, B_COLOR_S, B_COLOR_T, B_SEARCH_TMP,
-       B_FPFH_DESC, B_FPFH_SD, B_FPFH_BLK, B_FPFH_LIST, B_BND_DESC, B_RGBD_DESC, B_RGBD_IN, B_RGBD_WORK, B_COUNT };
+       B_FPFH_DESC, B_FPFH_SD, B_FPFH_BLK, B_FPFH_LIST, B_BND_DESC, B_RGBD_DESC, B_RGBD_IN, B_RGBD_WORK, B_ODO_IMG, B_ODO_TMP, B_COUNT };
 
 }  // namespace thip
 
