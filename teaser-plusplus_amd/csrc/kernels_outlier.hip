@@ -18,26 +18,15 @@
 // list (or lies beyond a full list's end, like the first time).
 #include <math.h>
 
-#include "icp_cov_device.h"
 #include "icp_internal.h"
+#include "icp_knn_device.h"
 
 namespace thip {
 
-// icp_knn_insert, the per-lane list: icp_cov_device.h.
-//
-// What the two kernels do with a query's finished neighbours, in ascending (d2, j), is the template argument Out:
-// IcpKnnListOut writes them (avg == nullptr) or the mean of their distances (statistical removal); IcpNormalOut
-// (icp_cov_device.h) feeds them to the covariance sums of normal estimation.
-struct IcpKnnListOut {
-  static constexpr bool kNormals = false;
-  int32_t* idx;
-  double* d2;
-  double* avg;
-};
-struct IcpKnnNormalOut : IcpNormalOut {
-  static constexpr bool kNormals = true;
-};
-
+// icp_knn_insert, the per-lane list: icp_cov_device.h.  What the kernels do with a query's finished neighbours, in
+// ascending (d2, j), is the template argument Out (icp_knn_device.h): IcpKnnListOut writes them (avg == nullptr) or
+// the mean of their distances (statistical removal); IcpKnnNormalOut feeds them to the covariance sums of normal
+// estimation.  The ring walk is written out here; the scan is icp_knn_scan of that header.
 template <int CAP, class Out>
 __device__ __forceinline__ void icp_knn_ring(double (*ld)[kIcpCovBlock], int32_t (*lj)[kIcpCovBlock],
                                              const IcpDesc* __restrict__ descs, const IcpKnnDesc* __restrict__ knns,
@@ -139,78 +128,7 @@ __global__ __launch_bounds__(kIcpCovBlock) void icp_knn_ring_normals_kernel(
   icp_knn_ring<CAP>(ld, lj, descs, knns, blk_prob, q, qs, qj, bstart, out, work, work_count);
 }
 
-// The whole-cloud route: block (one wave) w, w + gridDim.x, ... of the worklist.
-template <int CAP, class Out>
-__device__ __forceinline__ void icp_knn_scan(double (*ld)[kIcpCovBlock], int32_t (*lj)[kIcpCovBlock],
-                                             const IcpDesc* __restrict__ descs, const IcpKnnDesc* __restrict__ knns,
-                                             const double* __restrict__ q, const Out& out,
-                                             const int32_t* __restrict__ work,
-                                             const int32_t* __restrict__ work_count) {
-  const int lane = threadIdx.x;
-  const int32_t total = *work_count;
-  for (int32_t w = blockIdx.x; w < total; w += gridDim.x) {  // uniform over the wave
-    const int p = work[2 * (int64_t)w];
-    const int64_t i = work[2 * (int64_t)w + 1];
-    const IcpDesc& d = descs[p];
-    const IcpKnnDesc& kd = knns[p];
-    int want = kd.k < d.n_t ? kd.k : d.n_t;
-    want = want < CAP ? want : CAP;
-    const double* xp = q + 3 * (d.t_off + i);
-    const double x[3] = {xp[0], xp[1], xp[2]};
-    int m = 0;
-    for (int64_t j = lane; j < d.n_t; j += kIcpCovBlock) {
-      const double* yp = q + 3 * (d.t_off + j);
-      const double e0 = x[0] - yp[0], e1 = x[1] - yp[1], e2 = x[2] - yp[2];
-      const double d2 = (e0 * e0 + e1 * e1) + e2 * e2;
-      icp_knn_insert<CAP>(ld, lj, lane, want, m, d2, (int32_t)j);
-    }
-    // merge: the smallest head of the 64 lists, want times (want <= n_t entries exist; an index has one owner)
-    int head = 0;
-    double acc = 0.0;
-    const int64_t base = kd.out_off + i * kd.k;
-    // normal estimation: every lane sees each merged element after the butterfly; lane 0 keeps the sums and stores
-    double s1[3] = {0.0, 0.0, 0.0}, s2[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-    for (int t = 0; t < want; ++t) {
-      const double hd = head < m ? ld[head][lane] : INFINITY;
-      const int32_t hj = head < m ? lj[head][lane] : INT32_MAX;
-      double md = hd;
-      int32_t mj = hj;
-#pragma unroll
-      for (int o = 32; o > 0; o >>= 1) {
-        const double od = __shfl_xor(md, o, 64);
-        const int32_t oj = __shfl_xor(mj, o, 64);
-        if (od < md || (od == md && oj < mj)) {
-          md = od;
-          mj = oj;
-        }
-      }
-      if (head < m && mj == hj) ++head;
-      if constexpr (Out::kNormals) {
-        if (lane == 0) icp_cov_add(s1, s2, q + 3 * (d.t_off + mj), x);  // mj < n_t: want <= n_t real entries exist
-      } else if (out.avg) {
-        acc += sqrt(md);
-      } else if (lane == 0) {
-        out.idx[base + t] = mj;
-        out.d2[base + t] = md;
-      }
-    }
-    if (lane == 0) {
-      if constexpr (Out::kNormals) {
-        double a[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-        if (want >= 3) icp_cov_finish(s1, s2, want, a);
-        icp_normal_store(out, out.nd[p], i, x, want, a);
-      } else if (out.avg) {
-        out.avg[d.t_off + i] = acc / (double)want;
-      } else {
-        for (int t = want; t < kd.k; ++t) {
-          out.idx[base + t] = -1;
-          out.d2[base + t] = INFINITY;
-        }
-      }
-    }
-  }
-}
-
+// The whole-cloud route: icp_knn_scan (icp_knn_device.h) with the query a point of the cloud.
 template <int CAP>
 __global__ __launch_bounds__(kIcpCovBlock) void icp_knn_scan_kernel(
     const IcpDesc* __restrict__ descs, const IcpKnnDesc* __restrict__ knns, const double* __restrict__ q,
@@ -219,7 +137,7 @@ __global__ __launch_bounds__(kIcpCovBlock) void icp_knn_scan_kernel(
   __shared__ double ld[CAP][kIcpCovBlock];
   __shared__ int32_t lj[CAP][kIcpCovBlock];
   const IcpKnnListOut out = {idx_out, d2_out, avg_out};
-  icp_knn_scan<CAP>(ld, lj, descs, knns, q, out, work, work_count);
+  icp_knn_scan<CAP>(ld, lj, descs, knns, IcpKnnSelfQuery{q}, q, out, work, work_count);
 }
 
 template <int CAP>
@@ -228,7 +146,7 @@ __global__ __launch_bounds__(kIcpCovBlock) void icp_knn_scan_normals_kernel(
     const IcpKnnNormalOut out, const int32_t* __restrict__ work, const int32_t* __restrict__ work_count) {
   __shared__ double ld[CAP][kIcpCovBlock];
   __shared__ int32_t lj[CAP][kIcpCovBlock];
-  icp_knn_scan<CAP>(ld, lj, descs, knns, q, out, work, work_count);
+  icp_knn_scan<CAP>(ld, lj, descs, knns, IcpKnnSelfQuery{q}, q, out, work, work_count);
 }
 
 // ---- statistical removal: mean, std, threshold, mask -----------------------------------------------------------
@@ -353,56 +271,30 @@ __global__ __launch_bounds__(256) void icp_radius_count_kernel(
 }
 
 // ---- launchers ------------------------------------------------------------------------------------------------
-template <int CAP>
-static void icp_self_knn(hipStream_t s, const IcpDesc* d_desc, const IcpKnnDesc* d_knn, const int32_t* d_blk_prob,
-                         int n_blk, const double* d_q, const double* d_qs, const int32_t* d_qj,
-                         const int32_t* d_bstart, int32_t* d_idx, double* d_d2, double* d_avg, int32_t* d_work,
-                         int32_t* d_work_count) {
-  hipLaunchKernelGGL(icp_knn_ring_kernel<CAP>, dim3(n_blk), dim3(kIcpCovBlock), 0, s, d_desc, d_knn, d_blk_prob, d_q,
-                     d_qs, d_qj, d_bstart, d_idx, d_d2, d_avg, d_work, d_work_count);
-  const int scan = n_blk < kIcpKnnScanBlocks ? n_blk : kIcpKnnScanBlocks;
-  hipLaunchKernelGGL(icp_knn_scan_kernel<CAP>, dim3(scan), dim3(kIcpCovBlock), 0, s, d_desc, d_knn, d_q, d_idx, d_d2,
-                     d_avg, d_work, d_work_count);
-}
-
-template <int CAP>
-static void icp_normals_knn(hipStream_t s, const IcpDesc* d_desc, const IcpKnnDesc* d_knn, const int32_t* d_blk_prob,
-                            int n_blk, const double* d_q, const double* d_qs, const int32_t* d_qj,
-                            const int32_t* d_bstart, const IcpKnnNormalOut& out, int32_t* d_work,
-                            int32_t* d_work_count) {
-  hipLaunchKernelGGL(icp_knn_ring_normals_kernel<CAP>, dim3(n_blk), dim3(kIcpCovBlock), 0, s, d_desc, d_knn,
-                     d_blk_prob, d_q, d_qs, d_qj, d_bstart, out, d_work, d_work_count);
-  const int scan = n_blk < kIcpKnnScanBlocks ? n_blk : kIcpKnnScanBlocks;
-  hipLaunchKernelGGL(icp_knn_scan_normals_kernel<CAP>, dim3(scan), dim3(kIcpCovBlock), 0, s, d_desc, d_knn, d_q, out,
-                     d_work, d_work_count);
-}
-
 void launch_icp_self_knn(hipStream_t s, const IcpDesc* d_desc, const IcpKnnDesc* d_knn, const int32_t* d_blk_prob,
                          int n_blk, int top_k, const double* d_q, const double* d_qs, const int32_t* d_qj,
                          const int32_t* d_bstart, int32_t* d_idx, double* d_d2, double* d_avg, int32_t* d_work,
                          int32_t* d_work_count) {
-  if (n_blk <= 0) return;
-  if (top_k <= kIcpKnnSmall)  // the capacity only bounds the list: it never changes a result
-    icp_self_knn<kIcpKnnSmall>(s, d_desc, d_knn, d_blk_prob, n_blk, d_q, d_qs, d_qj, d_bstart, d_idx, d_d2, d_avg,
-                               d_work, d_work_count);
-  else
-    icp_self_knn<kIcpKnnMax>(s, d_desc, d_knn, d_blk_prob, n_blk, d_q, d_qs, d_qj, d_bstart, d_idx, d_d2, d_avg,
-                             d_work, d_work_count);
+  icp_knn_launch(n_blk, top_k, [&](auto cap, dim3 ring, dim3 scan) {
+    hipLaunchKernelGGL(icp_knn_ring_kernel<cap()>, ring, dim3(kIcpCovBlock), 0, s, d_desc, d_knn, d_blk_prob, d_q,
+                       d_qs, d_qj, d_bstart, d_idx, d_d2, d_avg, d_work, d_work_count);
+    hipLaunchKernelGGL(icp_knn_scan_kernel<cap()>, scan, dim3(kIcpCovBlock), 0, s, d_desc, d_knn, d_q, d_idx, d_d2,
+                       d_avg, d_work, d_work_count);
+  });
 }
 
 void launch_icp_normals_knn(hipStream_t s, const IcpDesc* d_desc, const IcpKnnDesc* d_knn, const IcpNormalDesc* d_nd,
                             const int32_t* d_blk_prob, int n_blk, int top_k, const double* d_q, const double* d_qs,
                             const int32_t* d_qj, const int32_t* d_bstart, double* d_nrm, double* d_cov, double* d_eig,
                             int32_t* d_work, int32_t* d_work_count) {
-  if (n_blk <= 0) return;
   IcpKnnNormalOut out;
   out.nd = d_nd, out.nrm = d_nrm, out.cov = d_cov, out.eig = d_eig;
-  if (top_k <= kIcpKnnSmall)
-    icp_normals_knn<kIcpKnnSmall>(s, d_desc, d_knn, d_blk_prob, n_blk, d_q, d_qs, d_qj, d_bstart, out, d_work,
-                                  d_work_count);
-  else
-    icp_normals_knn<kIcpKnnMax>(s, d_desc, d_knn, d_blk_prob, n_blk, d_q, d_qs, d_qj, d_bstart, out, d_work,
-                                d_work_count);
+  icp_knn_launch(n_blk, top_k, [&](auto cap, dim3 ring, dim3 scan) {
+    hipLaunchKernelGGL(icp_knn_ring_normals_kernel<cap()>, ring, dim3(kIcpCovBlock), 0, s, d_desc, d_knn, d_blk_prob,
+                       d_q, d_qs, d_qj, d_bstart, out, d_work, d_work_count);
+    hipLaunchKernelGGL(icp_knn_scan_normals_kernel<cap()>, scan, dim3(kIcpCovBlock), 0, s, d_desc, d_knn, d_q, out,
+                       d_work, d_work_count);
+  });
 }
 
 void launch_icp_statistical(hipStream_t s, const IcpDesc* d_desc, const IcpKnnDesc* d_knn,

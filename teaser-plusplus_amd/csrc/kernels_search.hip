@@ -11,10 +11,10 @@
 // box [0, cmax] before it is enumerated, so a loop never runs over cells that hold nothing.  (2) The rings start at
 // r0, the Chebyshev distance from the query's cell to that box (smaller rings hold no cell of the grid), and ring_cap
 // rings are searched from there.  (3) A query with r0 > kIcpSearchR0Max goes straight to the worklist: ring r0 of such a
-// query is a whole face of the grid.  The bound is the one of the self search: after ring r every data point not yet
-// seen lies in a cell that differs from the query's by more than r on some axis, so it is more than r h away; the
-// clamp of icp_cell moves the query's cell towards the box, never away from it, so a clamped query is at least as far
-// from every data cell as the bound assumes.  icp_search_scan_kernel is the whole-cloud route with the query taken
+// query is a whole face of the grid.  The bound and the clamp argument: DESIGN.md section 17.  The two ring kernels
+// stay written out, each in its file: as instantiations of one walk both measured slower (DESIGN.md section 17,
+// profiles/knn_shared/); tests/search_kernel_emulation.cpp and tests/test_gpu_knn_shared.py hold them to the same
+// bits on a cloud searched in itself.  icp_search_scan_kernel is icp_knn_scan of icp_knn_device.h with the query taken
 // from x.  Both routes produce the min(k, n_data) smallest (d2, j) exactly, so the route never shows.
 //
 // Hybrid and radius search run on the grid built for the radius, over the 27 cells around the query's cell: a cell
@@ -25,8 +25,8 @@
 // are a permutation of the row, whatever order the buckets were traversed in.
 #include <math.h>
 
-#include "icp_cov_device.h"
 #include "icp_internal.h"
+#include "icp_knn_device.h"
 
 namespace thip {
 
@@ -145,9 +145,7 @@ __global__ __launch_bounds__(kIcpCovBlock) void icp_search_ring_kernel(
   icp_search_ring<CAP>(ld, lj, descs, sds, blk_prob, xq, qs, qj, bstart, idx_out, d2_out, work, work_count);
 }
 
-// The whole-cloud route (icp_knn_scan of kernels_outlier.hip with the query taken from xq): block (one wave) w,
-// w + gridDim.x, ... of the worklist; every lane keeps the list of its stride of the data cloud, the 64 lists are
-// merged by repeated wave-wide minima of (d2, j).  Only worklist entries exist for problems with n_t > 0.
+// The whole-cloud route: icp_knn_scan (icp_knn_device.h) with the query taken from xq and the rows as the sink.
 template <int CAP>
 __global__ __launch_bounds__(kIcpCovBlock) void icp_search_scan_kernel(
     const IcpDesc* __restrict__ descs, const IcpSearchDesc* __restrict__ sds, const double* __restrict__ xq,
@@ -155,49 +153,8 @@ __global__ __launch_bounds__(kIcpCovBlock) void icp_search_scan_kernel(
     const int32_t* __restrict__ work, const int32_t* __restrict__ work_count) {
   __shared__ double ld[CAP][kIcpCovBlock];
   __shared__ int32_t lj[CAP][kIcpCovBlock];
-  const int lane = threadIdx.x;
-  const int32_t total = *work_count;
-  for (int32_t w = blockIdx.x; w < total; w += gridDim.x) {  // uniform over the wave
-    const int p = work[2 * (int64_t)w];
-    const int64_t i = work[2 * (int64_t)w + 1];
-    const IcpDesc& d = descs[p];
-    const IcpSearchDesc& sd = sds[p];
-    int want = sd.k < d.n_t ? sd.k : d.n_t;
-    want = want < CAP ? want : CAP;
-    const double* xp = xq + 3 * (d.s_off + i);
-    const double x[3] = {xp[0], xp[1], xp[2]};
-    int m = 0;
-    for (int64_t j = lane; j < d.n_t; j += kIcpCovBlock)
-      icp_knn_insert<CAP>(ld, lj, lane, want, m, icp_search_d2(x, q + 3 * (d.t_off + j)), (int32_t)j);
-    // merge: the smallest head of the 64 lists, want times (want <= n_t entries exist; an index has one owner)
-    int head = 0;
-    const int64_t base = sd.out_off + i * sd.k;
-    for (int t = 0; t < want; ++t) {
-      const double hd = head < m ? ld[head][lane] : INFINITY;
-      const int32_t hj = head < m ? lj[head][lane] : INT32_MAX;
-      double md = hd;
-      int32_t mj = hj;
-#pragma unroll
-      for (int o = 32; o > 0; o >>= 1) {
-        const double od = __shfl_xor(md, o, 64);
-        const int32_t oj = __shfl_xor(mj, o, 64);
-        if (od < md || (od == md && oj < mj)) {
-          md = od;
-          mj = oj;
-        }
-      }
-      if (head < m && mj == hj) ++head;
-      if (lane == 0) {
-        idx_out[base + t] = mj;
-        d2_out[base + t] = md;
-      }
-    }
-    if (lane == 0)
-      for (int t = want; t < sd.k; ++t) {
-        idx_out[base + t] = -1;
-        d2_out[base + t] = INFINITY;
-      }
-  }
+  const IcpKnnListOut out = {idx_out, d2_out, nullptr};
+  icp_knn_scan<CAP>(ld, lj, descs, sds, IcpKnnCloudQuery{xq}, q, out, work, work_count);
 }
 
 // ---- hybrid -------------------------------------------------------------------------------------------------------
@@ -372,29 +329,16 @@ __global__ __launch_bounds__(256) void icp_search_rank_kernel(
 }
 
 // ---- launchers ------------------------------------------------------------------------------------------------
-template <int CAP>
-static void icp_search_knn(hipStream_t s, const IcpDesc* d_desc, const IcpSearchDesc* d_sd, const int32_t* d_blk_prob,
-                           int n_blk, const double* d_x, const double* d_q, const double* d_qs, const int32_t* d_qj,
-                           const int32_t* d_bstart, int32_t* d_idx, double* d_d2, int32_t* d_work,
-                           int32_t* d_work_count) {
-  hipLaunchKernelGGL(icp_search_ring_kernel<CAP>, dim3(n_blk), dim3(kIcpCovBlock), 0, s, d_desc, d_sd, d_blk_prob, d_x,
-                     d_qs, d_qj, d_bstart, d_idx, d_d2, d_work, d_work_count);
-  const int scan = n_blk < kIcpKnnScanBlocks ? n_blk : kIcpKnnScanBlocks;
-  hipLaunchKernelGGL(icp_search_scan_kernel<CAP>, dim3(scan), dim3(kIcpCovBlock), 0, s, d_desc, d_sd, d_x, d_q, d_idx,
-                     d_d2, d_work, d_work_count);
-}
-
 void launch_icp_search_knn(hipStream_t s, const IcpDesc* d_desc, const IcpSearchDesc* d_sd, const int32_t* d_blk_prob,
                            int n_blk, int top_k, const double* d_x, const double* d_q, const double* d_qs,
                            const int32_t* d_qj, const int32_t* d_bstart, int32_t* d_idx, double* d_d2, int32_t* d_work,
                            int32_t* d_work_count) {
-  if (n_blk <= 0) return;
-  if (top_k <= kIcpKnnSmall)  // the capacity only bounds the list: it never changes a result
-    icp_search_knn<kIcpKnnSmall>(s, d_desc, d_sd, d_blk_prob, n_blk, d_x, d_q, d_qs, d_qj, d_bstart, d_idx, d_d2,
-                                 d_work, d_work_count);
-  else
-    icp_search_knn<kIcpKnnMax>(s, d_desc, d_sd, d_blk_prob, n_blk, d_x, d_q, d_qs, d_qj, d_bstart, d_idx, d_d2, d_work,
-                               d_work_count);
+  icp_knn_launch(n_blk, top_k, [&](auto cap, dim3 ring, dim3 scan) {
+    hipLaunchKernelGGL(icp_search_ring_kernel<cap()>, ring, dim3(kIcpCovBlock), 0, s, d_desc, d_sd, d_blk_prob, d_x,
+                       d_qs, d_qj, d_bstart, d_idx, d_d2, d_work, d_work_count);
+    hipLaunchKernelGGL(icp_search_scan_kernel<cap()>, scan, dim3(kIcpCovBlock), 0, s, d_desc, d_sd, d_x, d_q, d_idx,
+                       d_d2, d_work, d_work_count);
+  });
 }
 
 void launch_icp_search_hybrid(hipStream_t s, const IcpDesc* d_desc, const IcpSearchDesc* d_sd,

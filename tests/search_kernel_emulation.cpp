@@ -5,11 +5,15 @@
 // column of the LDS lists, its own outputs and (fill, rank) its own row or entry.  What is NOT emulated: the scan
 // kernel of the whole-cloud route, whose merge is a wave shuffle -- a query the ring kernel puts on the worklist is only
 // counted -- and the prefix kernel, whose threads talk through LDS; the exclusive sums are taken on the host here.
+// With the data cloud as its own query set, the self ring kernel (csrc/kernels_outlier.hip, written out on its own) and
+// the two-cloud one must give the same rows and the same worklist, query by query.
 // TEST INFRASTRUCTURE ONLY.
+#include <cstring>
 #include <random>
 #include <utility>
 
 #include "icp_host_prelude.h"
+#include "../teaser-plusplus_amd/csrc/kernels_outlier.hip"
 #include "../teaser-plusplus_amd/csrc/kernels_search.hip"
 
 using namespace thip;
@@ -174,6 +178,64 @@ static void run(const Cloud& P, const Cloud& Q, int k, int ring_cap, double radi
               ring_cap, radius, fell, bad);
 }
 
+// The data cloud as its own query set through the self ring kernel (icp_knn_ring_kernel: n_t queries, the
+// descriptor built with n_s = 0 as the self calls build it) and through the two-cloud ring kernel
+// (icp_search_ring_kernel: n_s queries): the same rows and the same worklist membership, query by query.
+template <int CAP>
+static int run_self_ring(const Grid& g, const IcpSearchDesc& sd, const Cloud& P, const char* name, int* fell) {
+  const int n = g.d.n_t, k = sd.k, n_blk = (n + 63) / 64;
+  IcpDesc self = g.d;
+  self.n_s = 0;
+  IcpKnnDesc kd{};
+  kd.k = sd.k, kd.ring_cap = sd.ring_cap, kd.edge = sd.edge;
+  std::vector<int32_t> blk(n_blk, 0);
+  std::vector<int32_t> idx[2], work[2], cnt[2];
+  std::vector<double> d2[2];
+  for (int s = 0; s < 2; ++s) idx[s].assign((size_t)n * k, -7), d2[s].assign((size_t)n * k, -7.0), work[s].assign(2 * n + 2, 0), cnt[s].assign(1, 0);
+  hipLaunchKernelGGL(icp_knn_ring_kernel<CAP>, dim3(n_blk), dim3(64), 0, nullptr, &self, &kd, blk.data(), P.data(),
+                     g.qs.data(), g.qj.data(), g.bstart.data(), idx[0].data(), d2[0].data(), (double*)nullptr,
+                     work[0].data(), cnt[0].data());
+  hipLaunchKernelGGL(icp_search_ring_kernel<CAP>, dim3(n_blk), dim3(64), 0, nullptr, &g.d, &sd, blk.data(), P.data(),
+                     g.qs.data(), g.qj.data(), g.bstart.data(), idx[1].data(), d2[1].data(), work[1].data(),
+                     cnt[1].data());
+  std::vector<char> inwork[2] = {std::vector<char>(n, 0), std::vector<char>(n, 0)};
+  for (int s = 0; s < 2; ++s)
+    for (int w = 0; w < cnt[s][0]; ++w) inwork[s][work[s][2 * w + 1]] = 1;
+  *fell = cnt[0][0];
+  int bad = cnt[0][0] != cnt[1][0];
+  for (int i = 0; i < n; ++i) {
+    bool ok = inwork[0][i] == inwork[1][i];
+    for (int t = 0; t < k; ++t)  // a worklist query's row keeps its fill in both
+      ok = ok && idx[0][(size_t)i * k + t] == idx[1][(size_t)i * k + t] &&
+           std::memcmp(&d2[0][(size_t)i * k + t], &d2[1][(size_t)i * k + t], sizeof(double)) == 0;
+    if (!ok) {
+      if (bad < 5) std::printf("%s self/two-cloud ring<%d>: query %d differs (worklist %d / %d)\n", name, CAP, i, inwork[0][i], inwork[1][i]);
+      ++bad;
+    }
+  }
+  return bad;
+}
+
+static void run_self(const Cloud& P, int k, int ring_cap, const char* name) {
+  const int n = (int)P.size() / 3;
+  IcpSearchDesc sd{};
+  sd.k = k, sd.ring_cap = ring_cap;
+  bool rings_ok = true;
+  sd.edge = knn_edge(P.data(), n, std::min(k, n), &rings_ok);
+  if (!rings_ok) sd.ring_cap = 0;
+  Grid g;
+  build(g, P, n, sd.edge);
+  int bad = 0, fell = 0, fell_small = 0;
+  bad += run_self_ring<kIcpKnnMax>(g, sd, P, name, &fell);
+  if (k <= kIcpKnnSmall) {
+    bad += run_self_ring<kIcpKnnSmall>(g, sd, P, name, &fell_small);
+    if (fell_small != fell) ++bad, std::printf("%s: the two capacities disagree on the worklist\n", name);
+  }
+  g_bad_total += bad;
+  std::printf("%-24s n %5d k %3d cap %2d: self == two-cloud, fallbacks %5d  mismatches %d\n", name, n, k, sd.ring_cap,
+              fell, bad);
+}
+
 int main() {
   std::mt19937_64 gen(11);
   std::uniform_real_distribution<double> u(0, 1);
@@ -263,6 +325,18 @@ int main() {
   {
     const Cloud P = cube(300, 1, 0), none;
     run(P, none, 3, 4, 0.1, "no queries");
+  }
+  {  // the query set is the data cloud: the self and the two-cloud ring kernel, bit for bit
+    std::vector<std::pair<Cloud, const char*>> clouds;
+    clouds.emplace_back(cube(1000, 1, 0), "self: cube");
+    clouds.emplace_back(lattice(7, 0.125, 0), "self: lattice");
+    Cloud far = cube(300, 1, 0);  // two far outliers: they are the ones that may reach the worklist
+    far[3 * 17] = 1e3, far[3 * 211 + 1] = 1e6;
+    clouds.emplace_back(far, "self: two far outliers");
+    for (int n : {1, 2, 63, 64, 65, 257}) clouds.emplace_back(cube(n, 1, 0), "self: sizes");
+    for (const auto& c : clouds)
+      for (int k : {1, 32, 33, 100})
+        for (int cap : {4, 1}) run_self(c.first, k, cap, c.second);
   }
   std::printf("TOTAL mismatches %d\n", g_bad_total);
   return g_bad_total != 0;

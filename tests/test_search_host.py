@@ -62,7 +62,9 @@ def test_search_kernel_source_equals_brute_force_on_the_host(tmp_path):
     outside each side (r0 = 1, 3, 5 with 4 rings), a corner, 1e6 extents away (which must reach the worklist), at a
     lattice's points and cell centres (which must not); planar, collinear, identical and tiny shifted data, n_data =
     1 .. 513, k = 1 .. 100, both list capacities, ring caps 4, 1 and 0, five points with colliding buckets.  The scan
-    kernel's shuffle merge and the prefix kernel are not emulated."""
+    kernel's shuffle merge and the prefix kernel are not emulated.  With the data cloud as the query set (a cube, the
+    7^3 lattice, a cloud with two far outliers, n = 1 .. 257, k = 1, 32, 33, 100, ring caps 4 and 1) the self ring
+    kernel and the two-cloud ring kernel give identical rows and worklists."""
     exe = compile_driver("search_kernel_emulation", tmp_path)
     out = subprocess.run([exe], capture_output=True, text=True, timeout=600)
     assert out.returncode == 0 and "TOTAL mismatches 0" in out.stdout, out.stdout[-4000:] + out.stderr[-4000:]
