@@ -1829,7 +1829,10 @@ TEASER_HIP_API const char* teaser_hip_ransac_last_error(const teaser_hip_ransac*
 TEASER_HIP_API int32_t teaser_hip_ransac_params_default(teaser_ransac_params_c* params);
 /* `batch` independent problems, HOST pointers per problem, borrowed for the call: src[b] n_src[b] x 3, dst[b]
  * n_dst[b] x 3, corr[b] n_corr[b] x 2 int32 (source index, target index); params and out: one per problem; inliers:
- * NULL, or per problem NULL or room for n_corr[b] x 2 int32, out[b].n_correspondences pairs written. */
+ * NULL, or per problem NULL or room for n_corr[b] x 2 int32, out[b].n_correspondences pairs written.
+ * A batch holds at most 65535 problems (the grids carry the problem in blockIdx.y or blockIdx.z): more, in this call
+ * or the stage call below, is refused with
+ * TEASER_HIP_ERR_UNSUPPORTED before anything is allocated or copied, and the handle stays usable. */
 TEASER_HIP_API int32_t teaser_hip_ransac_correspondence_batch(
     teaser_hip_ransac* ransac, int32_t batch, const double* const* src, const int32_t* n_src,
     const double* const* dst, const int32_t* n_dst, const int32_t* const* corr, const int32_t* n_corr,
@@ -1940,7 +1943,10 @@ TEASER_HIP_API const char* teaser_hip_fgr_last_error(const teaser_hip_fgr* fgr);
 TEASER_HIP_API int32_t teaser_hip_fgr_params_default(teaser_fgr_params_c* params);
 /* `batch` independent problems, HOST pointers per problem, borrowed for the call: src[b] n_src[b] x 3, dst[b]
  * n_dst[b] x 3, corr[b] n_corr[b] x 2 int32 (source index, target index); params and out: one per problem.  One
- * upload, one download and one synchronisation per call, whatever the batch. */
+ * upload, one download and one synchronisation per call, whatever the batch.
+ * A batch holds at most 65535 problems (the grids carry the problem in blockIdx.y or blockIdx.z): more, in this call
+ * or the stage call below, is refused with
+ * TEASER_HIP_ERR_UNSUPPORTED before anything is allocated or copied, and the handle stays usable. */
 TEASER_HIP_API int32_t teaser_hip_fgr_correspondence_batch(
     teaser_hip_fgr* fgr, int32_t batch, const double* const* src, const int32_t* n_src, const double* const* dst,
     const int32_t* n_dst, const int32_t* const* corr, const int32_t* n_corr, const teaser_fgr_params_c* params,
@@ -2059,7 +2065,10 @@ TEASER_HIP_API const char* teaser_hip_plane_last_error(const teaser_hip_plane* p
 TEASER_HIP_API int32_t teaser_hip_plane_params_default(teaser_plane_params_c* params);
 /* `batch` independent problems, HOST pointers per problem, borrowed for the call: points[b] n[b] x 3; params and out:
  * one per problem; inliers: NULL, or per problem NULL or room for n[b] int32, out[b].n_inliers written; mask: NULL, or
- * per problem NULL or n[b] bytes (1: inlier).  Mixed sizes share the launches; batch = 0 and n[b] = 0 are valid. */
+ * per problem NULL or n[b] bytes (1: inlier).  Mixed sizes share the launches; batch = 0 and n[b] = 0 are valid.
+ * A batch holds at most 65535 problems (the grids carry the problem in blockIdx.y or blockIdx.z): more, in this call
+ * or the stage call below, is refused with
+ * TEASER_HIP_ERR_UNSUPPORTED before anything is allocated or copied, and the handle stays usable. */
 TEASER_HIP_API int32_t teaser_hip_plane_segment_batch(teaser_hip_plane* plane, int32_t batch,
                                                       const double* const* points, const int32_t* n,
                                                       const teaser_plane_params_c* params, teaser_plane_result_c* out,

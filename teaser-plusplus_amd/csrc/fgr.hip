@@ -74,6 +74,8 @@ int32_t run(teaser_hip_fgr* h, int32_t batch, const double* const* src, const in
   h->err.clear();
   const bool staged = sg.n >= 0;
   if (batch < 0) return fail(h, TEASER_HIP_ERR_BAD_ARG, "batch must be >= 0");
+  if (batch > 65535)  // problems are indexed by blockIdx.y or blockIdx.z
+    return fail(h, TEASER_HIP_ERR_UNSUPPORTED, "a batch holds at most 65535 problems; split larger batches across calls");
   if (batch == 0) return TEASER_HIP_OK;
   if (!staged && !out) return fail(h, TEASER_HIP_ERR_BAD_ARG, "out must not be NULL");
   if (!n_src) return fail(h, TEASER_HIP_ERR_BAD_ARG, "n_src must not be NULL");

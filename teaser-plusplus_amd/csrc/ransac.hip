@@ -261,6 +261,8 @@ int32_t run_full(teaser_hip_ransac* h, int32_t batch, const double* const* src, 
   if (!h) return TEASER_HIP_ERR_BAD_ARG;
   h->err.clear();
   if (batch < 0) return fail(h, TEASER_HIP_ERR_BAD_ARG, "batch must be >= 0");
+  if (batch > 65535)  // problems are indexed by blockIdx.y or blockIdx.z
+    return fail(h, TEASER_HIP_ERR_UNSUPPORTED, "a batch holds at most 65535 problems; split larger batches across calls");
   if (batch == 0) return TEASER_HIP_OK;
   if (!out) return fail(h, TEASER_HIP_ERR_BAD_ARG, "out must not be NULL");
   Prep p;
@@ -395,6 +397,8 @@ int32_t run_trials(teaser_hip_ransac* h, int32_t batch, const double* const* src
   if (!h) return TEASER_HIP_ERR_BAD_ARG;
   h->err.clear();
   if (batch < 0) return fail(h, TEASER_HIP_ERR_BAD_ARG, "batch must be >= 0");
+  if (batch > 65535)  // problems are indexed by blockIdx.y or blockIdx.z
+    return fail(h, TEASER_HIP_ERR_UNSUPPORTED, "a batch holds at most 65535 problems; split larger batches across calls");
   if (first < 0) return fail(h, TEASER_HIP_ERR_BAD_ARG, "first must be >= 0");
   if (n < 0 || n > 65536) return fail(h, TEASER_HIP_ERR_BAD_ARG, "n must be in 0 .. 65536");
   if (batch == 0) return TEASER_HIP_OK;

@@ -219,3 +219,16 @@ def expected(name, min_points=None):
     for a in out[:3]:
         a.setflags(write=False)
     return out
+
+
+def wide_batch():
+    """normals_reference.wide_batch()'s 320 clouds of 0 .. 65 points with eps and min_points in turn: (clouds, eps,
+    min_points).  What the wide test rests on (more than 256 clouds and more than 256 point blocks) is asserted there
+    from the sizes alone."""
+    import normals_reference as RN
+    clouds = RN.wide_batch()
+    b = len(clouds)
+    eps = [(0.15, 0.3, 0.6)[i % 3] for i in range(b)]
+    min_points = [(1, 3, 6)[(i // 3) % 3] for i in range(b)]
+    assert len({(eps[i], min_points[i]) for i in range(b)}) == 9  # every pairing of the two cycles
+    return clouds, eps, min_points

@@ -481,12 +481,51 @@ int main() {
       EXPECT(teaser_hip_fgr_correspondence_batch(h, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
                                                  nullptr) == TEASER_HIP_OK);
     }
+    // the batch limit of the grids' y extent: 65 536 problems are refused by name before anything is read, allocated or
+    // launched, by the full call and by the stage call
+    {
+      const int32_t big = 65536;
+      const double pt[3] = {0.25, -1.0, 2.0};
+      std::vector<const double*> one((size_t)big, pt);
+      std::vector<const int32_t*> nc((size_t)big, nullptr);
+      std::vector<int32_t> n1((size_t)big, 1), zero((size_t)big, 0);
+      std::vector<teaser_fgr_params_c> prm((size_t)big, ps[0].prm);
+      std::vector<teaser_fgr_result_c> wide((size_t)big);
+      memset(wide.data(), 0x5a, sizeof(teaser_fgr_result_c) * wide.size());
+      const std::vector<teaser_fgr_result_c> before = wide;
+      const char* limit = "a batch holds at most 65535 problems; split larger batches across calls";
+      EXPECT(teaser_hip_fgr_correspondence_batch(h, big, one.data(), n1.data(), one.data(), n1.data(), nc.data(), zero.data(),
+                                                 prm.data(), wide.data()) == TEASER_HIP_ERR_UNSUPPORTED);
+      EXPECT(std::string(teaser_hip_fgr_last_error(h)) == limit);
+      EXPECT(memcmp(wide.data(), before.data(), sizeof(teaser_fgr_result_c) * wide.size()) == 0);
+      EXPECT(teaser_hip_fgr_iterations_batch(h, big, one.data(), n1.data(), one.data(), n1.data(), nc.data(), zero.data(),
+                                             prm.data(), 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
+                                             nullptr, nullptr) == TEASER_HIP_ERR_UNSUPPORTED);
+      EXPECT(std::string(teaser_hip_fgr_last_error(h)) == limit);
+    }
+    EXPECT(g_normalise == norm0);  // nothing was launched by a refused call
+    // ... and 65 535 one-point problems without correspondences pass it: every one comes back not optimised; the handle
+    // is usable after the refusals
+    {
+      const int32_t most = 65535;
+      const double pt[3] = {0.25, -1.0, 2.0};
+      std::vector<const double*> one((size_t)most, pt);
+      std::vector<const int32_t*> nc((size_t)most, nullptr);
+      std::vector<int32_t> n1((size_t)most, 1), zero((size_t)most, 0);
+      std::vector<teaser_fgr_params_c> prm((size_t)most, ps[0].prm);
+      std::vector<teaser_fgr_result_c> wide((size_t)most);
+      EXPECT(teaser_hip_fgr_correspondence_batch(h, most, one.data(), n1.data(), one.data(), n1.data(), nc.data(), zero.data(),
+                                                 prm.data(), wide.data()) == TEASER_HIP_OK);
+      EXPECT(std::string(teaser_hip_fgr_last_error(h)).empty());
+      EXPECT(same(wide[0], wide[(size_t)most - 1]) && wide[0].iterations == 0 && wide[0].n_corr == 0);
+    }
+    const int norm1 = g_normalise;
     expect_refusal(h, teaser_hip_fgr_set_option(h, "resident_max_corr", 3073), "resident_max_corr must be in 0 .. 3072", -1);
     expect_refusal(h, teaser_hip_fgr_set_option(h, "resident_max_corr", -1), "resident_max_corr must be in 0 .. 3072", -1);
     expect_refusal(h, teaser_hip_fgr_set_option(h, "chunk_trials", 64), "unknown option chunk_trials", -1);
     EXPECT(teaser_hip_fgr_get_option(h, "nothing", &v) == TEASER_HIP_ERR_BAD_ARG);
     EXPECT(teaser_hip_fgr_params_default(nullptr) == TEASER_HIP_ERR_BAD_ARG);
-    EXPECT(g_normalise == norm0);  // nothing was launched by a refused call
+    EXPECT(g_normalise == norm1);  // nothing was launched by a refused call
     EXPECT(std::string(teaser_hip_fgr_last_error(nullptr)).empty());
   }
   EXPECT(teaser_hip_fgr_destroy(h) == TEASER_HIP_OK);

@@ -261,3 +261,32 @@ def case(name):
     seed, n_s, n_t, ncorr, opt = CASES[name]
     P, Q, corr, T = make_case(seed, n_s, n_t, ncorr)
     return P, Q, corr, T, dict(opt)
+
+
+# ---- the batch tests/test_gpu_wide_batches.py and tests/test_wide_batch_cases.py share ----
+WIDE_BATCH = 320
+WIDE_STAGE = 3  # iterations of the wide test's stage call
+WIDE_SPLIT = 40  # resident_max_corr that sends about half of the batch down each route
+
+
+def wide_batch():
+    """320 problems of 20 .. 60 pairs whose iteration_number cycles over 0 .. 16, so that the list of open problems
+    empties unevenly; problem 150 has 5 pairs (fewer than FGR optimises).  Returns (problems, options): (P, Q, corr)
+    and the keyword arguments of fgr() per problem.  What the wide test rests on is asserted from the sizes alone."""
+    b = WIDE_BATCH
+    its = (0, 1, 2, 3, 5, 8, 13, 16, 4)
+    problems, options = [], []
+    for i in range(b):
+        ncorr = 5 if i == 150 else (20, 33, 47, 60)[i % 4]
+        P, Q, corr, _ = make_case(4000 + i, ncorr + 7, ncorr + 12, ncorr)
+        problems.append((P, Q, corr))
+        options.append(dict(iteration_number=its[i % len(its)], use_absolute_scale=bool(i % 5 == 0),
+                            decrease_mu=bool(i % 7 != 0), maximum_correspondence_distance=(0.025, 0.3)[i % 2]))
+    n = [len(p[2]) for p in problems]
+    assert b > 256  # fgr_finish_kernel's second block of 256 threads, blockIdx.y past 255 in fgr_cloud_*
+    assert sum(k < MIN_CORR for k in n) == 1 and n[150] < MIN_CORR
+    res = [k for k in n if MIN_CORR <= k <= WIDE_SPLIT]
+    assert len(res) > 128 and len(n) - len(res) > 128  # both routes' index lists at resident_max_corr = WIDE_SPLIT
+    for lo in (0, 256):  # the open list thins out below and above problem 256
+        assert len({o["iteration_number"] for o in options[lo:lo + 64]}) == len(its)
+    return problems, options

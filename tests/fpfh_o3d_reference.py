@@ -295,3 +295,25 @@ def case_list():
     out.append(("knn_n_below_max_nn", P, N, KNN, 0.0, 50))
     out.append(("knn_100", rng.random((130, 3)), unit(rng.normal(size=(130, 3))), KNN, 0.0, 100))
     return out
+
+
+def wide_batch():
+    """320 clouds of 0 .. 65 points (normals_reference.wide_batch()) with random unit normals, the searches hybrid and
+    k-NN in turn: a list of (points, normals, search, radius, max_nn).  It serves FPFH and boundary detection.  What
+    the wide tests rest on is asserted from the sizes alone."""
+    import normals_reference as RN
+    clouds = RN.wide_batch()
+    b = len(clouds)
+    out = []
+    for i, P in enumerate(clouds):
+        rng = np.random.default_rng(8000 + i)
+        N = unit(rng.normal(size=P.shape)) if len(P) else np.zeros((0, 3))
+        if (i // 8 + i) % 2:
+            out.append((P, N, HYBRID, (0.3, 0.5)[i % 2], (10, 40)[(i // 2) % 2]))
+        else:
+            out.append((P, N, KNN, 0.0, (5, 33, 12)[i % 3]))
+    assert b > 256
+    for search in (HYBRID, KNN):  # each of the two concatenated block lists: a block or more per non-empty cloud
+        assert sum(1 for c in out if c[2] == search and len(c[0])) > 128
+    assert {out[i][2] for i in (255, 256, 257)} == {HYBRID, KNN}
+    return out

@@ -104,3 +104,31 @@ def three_positions(n=600):
     """n points on 3 distinct positions, interleaved."""
     pos = np.array([[0.0, 0.0, 0.0], [3.0, 0.0, 0.0], [0.0, 5.0, 1.0]])
     return pos[np.arange(n) % 3]
+
+
+WIDE_CAPACITY = 10240  # the default of "fps_resident_max" (kFpsResidentCap): the largest cloud the resident route serves
+WIDE_LARGE = (0, 256, 257, 319)  # where the clouds above it stand in the wide batch
+
+
+def wide_batch():
+    """normals_reference.wide_batch()'s 320 clouds of 0 .. 65 points, four of them replaced by clouds of
+    WIDE_CAPACITY + 1 points, with the sample counts 0, 1, n and min(n, 7) and the start indices 0, n - 1 and n / 2 in
+    turn: (clouds, K, start).  What the wide test rests on is asserted from the sizes alone."""
+    import normals_reference as RN
+    clouds = RN.wide_batch()
+    b = len(clouds)
+    rng = np.random.default_rng(41)
+    for i in WIDE_LARGE:
+        clouds[i] = gaussian(rng, WIDE_CAPACITY + 1)
+    n = [len(P) for P in clouds]
+    K = [(0, 1, n[i], min(n[i], 7))[i % 4] for i in range(b)]
+    for i, k in zip(WIDE_LARGE, (5, 17, 1, 33)):
+        K[i] = k
+    start = [0 if n[i] == 0 else (0, n[i] - 1, n[i] // 2)[i % 3] for i in range(b)]
+    assert b > 256 and WIDE_LARGE[-1] == b - 1
+    streamed = [i for i in range(b) if n[i] > WIDE_CAPACITY]
+    resident = [i for i in range(b) if 0 < n[i] <= WIDE_CAPACITY and K[i] > 0]
+    # the resident map: a workgroup per resident cloud, past 128 of them; the block map of the others: past 128 blocks
+    assert tuple(streamed) == WIDE_LARGE and len(resident) > 128 and sum((n[i] + 255) // 256 for i in streamed) > 128
+    assert all(K[i] > 0 for i in WIDE_LARGE) and any(K[i] == n[i] > 1 for i in range(b)) and any(k == 0 for k in K)
+    return clouds, K, start

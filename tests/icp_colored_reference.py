@@ -245,3 +245,32 @@ def scene(seed=0, n_src=1500, grid=48):
     return dict(source=np.ascontiguousarray(source), target=np.ascontiguousarray(target),
                 source_colors=_texture(sx, sy), target_colors=_texture(target[:, 0], target[:, 1]),
                 target_normals=np.ascontiguousarray(gn), T_true=T, r=SCENE_R)
+
+
+# ---- the batch tests/test_gpu_wide_batches.py and tests/test_wide_batch_cases.py share ----
+WIDE_BATCH = 320
+WIDE_R = 0.45  # above the coarsest lattice's spacing (2 / 5), so every gradient has its four neighbours inside 2 r
+WIDE_KERNELS = (("huber", 0.002), ("cauchy", 0.002), ("tukey", 0.01))  # the robust kernels, in turn
+WIDE_ITERATIONS = 3
+
+
+def wide_batch():
+    """320 textured scenes cut down to 36, 49 or 64 target points and 40 to 120 source points (one without source
+    points, one without target points): a list of scene() dicts with r = WIDE_R and the robust kernel of the problem
+    as "kernel".  What the wide test rests on is asserted from the sizes alone."""
+    b = WIDE_BATCH
+    grids = [(6, 7, 8)[i % 3] for i in range(b)]
+    n_src = [(40, 97, 120, 60)[i % 4] for i in range(b)]
+    assert b > 256 and max(g * g for g in grids) <= 200 and max(n_src) <= 200
+    assert len({(grids[i], n_src[i]) for i in (255, 256, 257)}) == 3
+    out = []
+    for i in range(b):
+        s = dict(scene(seed=100 + i, n_src=n_src[i], grid=grids[i]), r=WIDE_R, kernel=WIDE_KERNELS[i % len(WIDE_KERNELS)])
+        if i == 130:
+            s.update(source=np.zeros((0, 3)), source_colors=np.zeros((0, 3)))
+        if i == 190:
+            s.update(target=np.zeros((0, 3)), target_colors=np.zeros((0, 3)), target_normals=np.zeros((0, 3)))
+        out.append(s)
+    # one block of 256 points per non-empty cloud: the gradient kernel's block map holds more than 256 entries
+    assert sum((len(s["target"]) + 255) // 256 for s in out) > 256
+    return out

@@ -489,6 +489,9 @@ def cases():
     blank = make_pair(16, 12, SMALL, jacobian=COLOR)
     blank.source_color[:], blank.target_color[:] = 128, 128
     add("singular", blank, option((2, 2)))
+    blank3 = make_pair(16, 12, SMALL, jacobian=COLOR)  # the same under the options most cases share: for mixed batches
+    blank3.source_color[:], blank3.target_color[:] = 128, 128
+    add("singular_3_levels", blank3, option((3, 2, 2)), host=False)
     add("skip_level", make_pair(37, 29, SMALL), option((0, 3)))
     add("no_iteration", make_pair(16, 12, SMALL, odo_init=pose(0.0, 0.01, 0.0, (0.01, 0.0, 0.0))), option((0,)))
     _cases = c
@@ -509,3 +512,28 @@ def pyramid(name):
     if name not in _pyramids:
         _pyramids[name] = pyramid_floats(result(name).levels)
     return _pyramids[name]
+
+
+
+WIDE_BATCH = 320
+WIDE_CYCLE = ("4x4", "8x8", "37x29", "no_correspondence", "f32_specials", "big_init")
+WIDE_SINGULAR = (255, 257)  # where the pair that fails (a singular system) stands in the wide batch
+
+
+def wide_batch():
+    """The names of 320 cases that share the options (3, 2, 2): WIDE_CYCLE in turn, with the textureless pair, whose
+    system is singular, at 255 and 257.  What the wide test rests on is asserted from the sizes alone."""
+    names = [WIDE_CYCLE[i % len(WIDE_CYCLE)] for i in range(WIDE_BATCH)]
+    for i in WIDE_SINGULAR:
+        names[i] = "singular_3_levels"
+    c = cases()
+    assert len(names) > 256 and len({c[n].opt.iterations for n in names}) == 1 and c[names[0]].opt.iterations == (3, 2, 2)
+    def blocks(n, l):
+        h, w = c[n].pair.source_depth.shape
+        return -(-((h >> l) * (w >> l)) // BLOCK)
+
+    for l in range(3):  # blk_pair: the blocks of level 0 of all pairs, then level 1, ...: past 256 of them at every level
+        assert sum(blocks(n, l) for n in names) > 256
+    assert sum(blocks(n, 0) for n in names) > 1024
+    assert names[256] not in (names[255], names[0]) and names[254] != names[258]
+    return names

@@ -465,6 +465,35 @@ int main() {
            TEASER_HIP_ERR_BAD_ARG);
     EXPECT(teaser_hip_plane_segment_batch(h, 2, bt.pts.data(), nullptr, bt.prm.data(), &r, nullptr, nullptr) == TEASER_HIP_ERR_BAD_ARG);
     EXPECT(teaser_hip_plane_segment_batch(h, 2, bt.pts.data(), bt.n.data(), nullptr, &r, nullptr, nullptr) == TEASER_HIP_ERR_BAD_ARG);
+    // the batch limit of the grids' y and z extents: 65 536 problems are refused by name before anything is read,
+    // allocated or launched, by the full call and by the stage call; 65 535 empty problems pass that check
+    {
+      const int32_t big = 65536;
+      std::vector<const double*> np((size_t)big, nullptr);
+      std::vector<int32_t> zero((size_t)big, 0);
+      std::vector<teaser_plane_params_c> prm((size_t)big, two[0].prm);
+      std::vector<teaser_plane_result_c> wide((size_t)big);
+      memset(wide.data(), 0x5a, sizeof(teaser_plane_result_c) * wide.size());
+      const std::vector<teaser_plane_result_c> before = wide;
+      const char* limit = "a batch holds at most 65535 problems; split larger batches across calls";
+      const int models = g_models, finishes = g_finishes;
+      EXPECT(teaser_hip_plane_segment_batch(h, big, np.data(), zero.data(), prm.data(), wide.data(), nullptr, nullptr) ==
+             TEASER_HIP_ERR_UNSUPPORTED);
+      EXPECT(std::string(teaser_hip_plane_last_error(h)) == limit);
+      EXPECT(memcmp(wide.data(), before.data(), sizeof(teaser_plane_result_c) * wide.size()) == 0);
+      EXPECT(teaser_hip_plane_trials_batch(h, big, np.data(), zero.data(), prm.data(), 0, 0, nullptr, nullptr, nullptr, nullptr,
+                                           nullptr) == TEASER_HIP_ERR_UNSUPPORTED);
+      EXPECT(std::string(teaser_hip_plane_last_error(h)) == limit);
+      // 65 535: the stage call with no trial goes through the checks and the upload; the full call is past the limit
+      // check when it names the next argument it misses
+      EXPECT(teaser_hip_plane_trials_batch(h, big - 1, np.data(), zero.data(), prm.data(), 0, 0, nullptr, nullptr, nullptr,
+                                           nullptr, nullptr) == TEASER_HIP_OK);
+      EXPECT(std::string(teaser_hip_plane_last_error(h)).empty());
+      EXPECT(teaser_hip_plane_segment_batch(h, big - 1, np.data(), zero.data(), nullptr, wide.data(), nullptr, nullptr) ==
+             TEASER_HIP_ERR_BAD_ARG);
+      EXPECT(std::string(teaser_hip_plane_last_error(h)) == "params must not be NULL");
+      EXPECT(g_models == models && g_finishes == finishes);
+    }
     std::vector<teaser_plane_result_c> out(2);
     EXPECT(bt.run(h, out.data(), nullptr, nullptr) == TEASER_HIP_OK);  // the handle is usable after the refusals
     EXPECT(std::string(teaser_hip_plane_last_error(h)).empty() && out[0].best_trial >= 0);

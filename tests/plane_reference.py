@@ -205,3 +205,28 @@ def segment(P, d, ransac_n=3, num_iterations=100, probability=0.99999999, seed=1
                mask=mask.astype(np.uint8), fitness=float(best_count) / float(n), inlier_rmse=best_rmse,
                winning_plane=best_plane)
     return out
+
+
+# ---- the batch tests/test_gpu_wide_batches.py and tests/test_wide_batch_cases.py share ----
+WIDE_CHUNK = 64  # chunk_trials of the wide test: one 64-hypothesis tile per chunk
+
+
+def wide_batch():
+    """320 clouds of 0 .. 65 points (normals_reference's sizes, half of each cloud planted on a plane), 70 trials each:
+    dict(clouds, d, ransac_n, num_iterations, probability, seed), one entry per problem, with what the wide test rests
+    on asserted from the sizes alone."""
+    import normals_reference as RN
+    import plane_scenes as SC
+    b = RN.WIDE_BATCH
+    n = [RN.WIDE_CYCLE[(i + RN.WIDE_ROTATE) % len(RN.WIDE_CYCLE)] for i in range(b)]
+    ransac_n = [(3, 5, 4)[i % 3] for i in range(b)]
+    num_iterations = [70] * b
+    probability = [(1.0, 0.99)[(i // 3) % 2] for i in range(b)]  # 1.0: the loop never stops early
+    assert b > 256  # plane_winner_kernel, plane_fin_total_kernel: a fifth 64-lane tile; blockIdx.y / .z past 255
+    assert min(num_iterations) > WIDE_CHUNK  # a second chunk of trials, a partial one
+    runs = [k >= r for k, r in zip(n, ransac_n)]
+    assert any(runs) and not all(runs)  # "no plane" (n < ransac_n) and trials that run
+    assert all(runs[i] for i in (0, 63, 64, 65, 255, 256, 257, b - 1)) and not runs[260]
+    return dict(clouds=[SC.planted(n[i], 0.5, 2000 + i) for i in range(b)], d=[(0.01, 0.05)[i % 2] for i in range(b)],
+                ransac_n=ransac_n, num_iterations=num_iterations, probability=probability,
+                seed=[3000 + i for i in range(b)])

@@ -257,3 +257,24 @@ def check_against_reference(name, got, report=print, graph=None, refs=None):
     for key, v in ratios.items():
         assert v <= 16.0, (name, key, v)
     return ratios
+
+
+WIDE_BATCH = 320
+WIDE_LARGE = 256  # where the 128-node graph stands in the wide batch
+
+
+def wide_batch():
+    """The names of 320 scenarios for one call: the sized cases of 3, 4, 6, 7 and 9 nodes in turn (the 3-node ring has
+    no uncertain edge, so Levenberg-Marquardt runs without a line process there and with one elsewhere) and the 128-node
+    graph, the tile-edge case, at WIDE_LARGE.  What the wide test rests on is asserted from the sizes alone."""
+    small = [n for n in SIZE_CASES if n != "size_128"]
+    names = [small[i % len(small)] for i in range(WIDE_BATCH)]
+    names[WIDE_LARGE] = "size_128"
+    assert len(names) > 256 and len(small) == 5  # one workgroup per graph: blockIdx.x past 255
+    nodes = [len(build(n)[0]) for n in names]
+    edges = [len(build(n)[1]) for n in names]
+    assert len({nodes[255], nodes[256], nodes[257]}) == 3 and nodes[256] == 128
+    assert len(set(nodes[:5])) == 5 and len(set(edges[:5])) == 5  # no stride by a constant graph size can be right
+    uncertain = [any(E[4] for E in build(n)[1]) for n in small]
+    assert any(uncertain) and not all(uncertain)
+    return names

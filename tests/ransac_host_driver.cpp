@@ -474,6 +474,36 @@ int main() {
     Batch cb(clk);
     teaser_ransac_result_c two[2];
     EXPECT(cb.run(h, two, nullptr) == TEASER_HIP_OK && same(two[0], two[1]));
+    // the batch limit of the grids' y extent: 65 536 problems are refused by name before anything is read, allocated or
+    // launched, by the full call and by the stage call; 65 535 empty problems pass that check
+    {
+      const int32_t big = 65536;
+      std::vector<const double*> np((size_t)big, nullptr);
+      std::vector<const int32_t*> nc((size_t)big, nullptr);
+      std::vector<int32_t> zero((size_t)big, 0);
+      std::vector<teaser_ransac_params_c> prm((size_t)big, ps.back().prm);
+      std::vector<teaser_ransac_result_c> out((size_t)big);
+      memset(out.data(), 0x5a, sizeof(teaser_ransac_result_c) * out.size());
+      const std::vector<teaser_ransac_result_c> before = out;
+      const char* limit = "a batch holds at most 65535 problems; split larger batches across calls";
+      const int packs = g_packs, chunks = g_chunks;
+      EXPECT(teaser_hip_ransac_correspondence_batch(h, big, np.data(), zero.data(), np.data(), zero.data(), nc.data(),
+                                                    zero.data(), prm.data(), out.data(), nullptr) == TEASER_HIP_ERR_UNSUPPORTED);
+      EXPECT(std::string(teaser_hip_ransac_last_error(h)) == limit);
+      EXPECT(memcmp(out.data(), before.data(), sizeof(teaser_ransac_result_c) * out.size()) == 0);
+      EXPECT(teaser_hip_ransac_trials_batch(h, big, np.data(), zero.data(), np.data(), zero.data(), nc.data(), zero.data(),
+                                            prm.data(), 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr) == TEASER_HIP_ERR_UNSUPPORTED);
+      EXPECT(std::string(teaser_hip_ransac_last_error(h)) == limit);
+      EXPECT(g_packs == packs && g_chunks == chunks);
+      // 65 535: the stage call with no trial goes through the checks, the upload and the pack launch; the full call is
+      // past the limit check when it names the next argument it misses
+      EXPECT(teaser_hip_ransac_trials_batch(h, big - 1, np.data(), zero.data(), np.data(), zero.data(), nc.data(),
+                                            zero.data(), prm.data(), 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr) == TEASER_HIP_OK);
+      EXPECT(g_packs == packs + 1 && std::string(teaser_hip_ransac_last_error(h)).empty());
+      EXPECT(teaser_hip_ransac_correspondence_batch(h, big - 1, np.data(), zero.data(), np.data(), zero.data(), nc.data(),
+                                                    zero.data(), nullptr, out.data(), nullptr) == TEASER_HIP_ERR_BAD_ARG);
+      EXPECT(std::string(teaser_hip_ransac_last_error(h)) == "params must not be NULL");
+    }
     // the handle is sound after the refusals
     Batch one(std::vector<Problem>(1, ps[0]));
     EXPECT(one.run(h, &r, nullptr) == TEASER_HIP_OK && same(r, want[0]));

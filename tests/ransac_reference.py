@@ -205,3 +205,58 @@ def ransac(P, Q, corr, r, ransac_n=3, max_iteration=100000, confidence=0.999, se
     else:
         out["inliers"] = np.zeros((0, 2), dtype=np.int32)
     return out
+
+
+# ---- the batch tests/test_gpu_wide_batches.py and tests/test_wide_batch_cases.py share ----
+WIDE_BATCH = 320
+WIDE_CHUNKS = (4096, 3072, 2048, 1024)  # chunk_trials values of the wide test: 1, 2, 3 and 4 chunks in a group
+WIDE_STAGE = 130  # trials of the wide test's stage call: past two tiles of 64
+
+
+def group_chunks(chunk, batch):
+    """The chunks the full call enqueues between two synchronisations: min(4, 2^21 / (chunk batch)), at least 1."""
+    return max(1, min(4, (1 << 21) // (chunk * max(batch, 1))))
+
+
+def wide_batch():
+    """320 problems of 20 .. 40 pairs: dict(P, Q, corr, r, ransac_n, s, max_iteration, confidence, seed), one entry per
+    problem.  Every 80th runs to its max_iteration (confidence 1) of 5 000, 7 000 or 13 000, every 16th after it has a
+    quarter to a third of its pairs planted and stops after some hundreds of trials, the others stop after some tens; one problem
+    has fewer pairs than ransac_n and one is empty.  What the wide test rests on is asserted from the sizes alone."""
+    b = WIDE_BATCH
+    out = dict(P=[], Q=[], corr=[], r=[], ransac_n=[], s=[], max_iteration=[], confidence=[], seed=[])
+    long_runs = (5000, 7000, 13000)
+    for i in range(b):
+        rng = np.random.default_rng(7000 + i)
+        ncorr = (20, 40, 33, 27)[i % 4]
+        if i == 100:
+            ncorr = 2
+        if i == 200:
+            ncorr = 0
+        if i % 80 == 0:
+            ratio, max_iteration, confidence = 0.5, long_runs[(i // 80) % 3], 1.0
+        elif i % 16 == 1:
+            ratio, max_iteration, confidence = (0.25, 0.3, 0.35)[(i // 16) % 3], 13000, 0.999
+        else:
+            ratio, max_iteration, confidence = (0.6, 0.7, 0.8)[(i // 4) % 3], 3000, 0.999
+        n_s, n_t = (ncorr + 5, ncorr + 9) if ncorr else (0, 0)
+        P = rng.uniform(-1.0, 1.0, (n_s, 3))
+        Q = rng.uniform(-1.0, 1.0, (n_t, 3))
+        a = rng.uniform(0.2, 1.0)
+        R = np.array([[np.cos(a), -np.sin(a), 0.0], [np.sin(a), np.cos(a), 0.0], [0.0, 0.0, 1.0]])
+        src, dst = rng.permutation(n_s)[:ncorr], rng.permutation(n_t)[:ncorr]
+        n_in = int(round(ratio * ncorr))
+        Q[dst[:n_in]] = P[src[:n_in]] @ R.T + np.array([0.1, -0.2, 0.3]) + rng.normal(0.0, 0.002, (n_in, 3))
+        corr = np.stack([src, dst], axis=1)[rng.permutation(ncorr)] if ncorr else np.zeros((0, 2))
+        for k, v in zip(out, (P, Q, np.ascontiguousarray(corr, dtype=np.int32), 0.02, (3, 4)[i % 2],
+                              (0.0, 0.9)[i % 3 == 0], max_iteration, confidence, 9000 + i)):
+            out[k].append(v)
+    assert b > 256
+    assert [group_chunks(c, b) for c in WIDE_CHUNKS] == [1, 2, 3, 4]
+    full = [m for m, c in zip(out["max_iteration"], out["confidence"]) if c == 1.0]
+    # at every chunk size some problem that never stops early is done within two groups of chunks, another needs a third
+    assert all(min(full) <= 2 * group_chunks(c, b) * c < max(full) for c in WIDE_CHUNKS)
+    assert all(sorted(full)[-2] > group_chunks(c, b) * c for c in WIDE_CHUNKS)
+    assert out["confidence"][0] == 1.0 and out["confidence"][257] == 0.999 and out["max_iteration"][257] == 13000
+    assert sum(len(c) < n for c, n in zip(out["corr"], out["ransac_n"])) == 2
+    return out

@@ -311,3 +311,26 @@ def round_trip_frame():
     f = Frame(32.0, 64.0, 18.0, 10.0, depth_scale=1024.0, depth_trunc=3.0)
     cam = Camera(w, h, 32.0, 64.0, 18.0, 10.0, None, 1024.0, 3.0)
     return d, f, cam
+
+
+WIDE_BATCH = 320
+TILE = 256  # pixels per tile of the unprojection's tile maps
+
+
+def wide_batch():
+    """(frames, clouds): for each of 320 problems the index of its case in unproject_cases() and in project_cases(), the
+    lists in turn -- every shape (1 x 1, 7 x 5 at three strides, 64 x 4, 257 x 1, 65 x 9, the empty ones), both depth
+    types and every colour variant recur about eleven times.  What the wide test rests on is asserted from the sizes
+    alone."""
+    ucases, pcases = unproject_cases(), project_cases()
+    frames = [i % len(ucases) for i in range(WIDE_BATCH)]
+    clouds = [i % len(pcases) for i in range(WIDE_BATCH)]
+    assert WIDE_BATCH > 256
+    tiles = sum((ucases[k][1].size + TILE - 1) // TILE for k in frames)
+    assert tiles > 256  # d_tile_frame and d_tile_prob past 256 entries (a strided frame may need fewer tiles: 16 cases)
+    assert sum((ucases[k][1].shape[1] * ucases[k][1].shape[0] + TILE - 1) // TILE
+               for k in frames if ucases[k][3].stride == 1) > 256
+    assert {ucases[k][1].dtype for k in frames} == {np.dtype(np.uint16), np.dtype(F32)}
+    assert {ucases[k][3].stride for k in frames} == {1, 2, 3}
+    assert any(len(pcases[k][1]) >= 1000 and pcases[k][3].width == 1 for k in clouds[256:])  # the race for one pixel
+    return frames, clouds

@@ -82,3 +82,33 @@ def lattice(m=7, spacing=0.25):
 def lattice_centres(m=7, spacing=0.25):
     """The (m - 1)^3 cell centres of lattice(m, spacing): eight data points tie at the nearest distance."""
     return lattice(m - 1, spacing) + 0.5 * spacing
+
+
+# ---- the batch tests/test_gpu_wide_batches.py and tests/test_wide_batch_cases.py share ----
+WIDE_KS = (1, 5, 32, 33, 100)
+WIDE_TINY = 1e-9  # a radius no query reaches a data point with (the queries are drawn apart from the data)
+
+
+def wide_batch():
+    """320 two-cloud problems: the data are normals_reference.wide_batch()'s clouds (0 .. 65 points), the queries 0 .. 40
+    points of the unit cube; dict(data, query, k, radius, hybrid_radius).  The radii are WIDE_TINY in runs of five consecutive problems
+    out of every twelve and around problems 255 .. 257, which have entries between neighbours without.  What the wide
+    test rests on is asserted from the sizes alone."""
+    import normals_reference as RN
+    data = RN.wide_batch()
+    b = len(data)
+    nq = [(7, 40, 0, 1, 33, 12, 20)[i % 7] for i in range(b)]
+    for i in (255, 256, 257):
+        nq[i] = (9, 33, 2)[i - 255]
+    query = [RN.cube(nq[i], 5000 + i) * 1.2 - 0.1 for i in range(b)]
+    tiny = [(i % 12 in (2, 3, 4, 5, 6) or 250 <= i <= 262) and i not in (255, 256, 257) for i in range(b)]
+    radius = [WIDE_TINY if tiny[i] else (0.3, 0.5, 2.0)[i % 3] for i in range(b)]
+    radius[257] = 2.0  # covers the cube: every data point of every query
+    k = [WIDE_KS[i % len(WIDE_KS)] for i in range(b)]
+    empty = [tiny[i] or len(data[i]) == 0 or nq[i] == 0 for i in range(b)]  # no entry, whatever the points
+    assert b > 256 and sum(empty) >= 50
+    assert all(empty[i] for i in (250, 251, 252, 253, 254, 258, 259, 260, 261, 262))
+    assert not any(tiny[i] for i in (255, 256, 257)) and all(len(data[i]) and nq[i] for i in (255, 256, 257))
+    assert any(len(data[i]) == 0 and nq[i] > 0 for i in range(b)) and any(len(data[i]) > 0 and nq[i] == 0 for i in range(b))
+    assert sum((n + 255) // 256 for n in nq) > 256  # query blocks
+    return dict(data=data, query=query, k=k, radius=radius, hybrid_radius=[(0.3, 0.5, 2.0)[i % 3] for i in range(b)])

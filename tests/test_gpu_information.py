@@ -13,6 +13,7 @@ import pytest
 
 import icp_reference as R
 import information_reference as I
+from information_reference import grid_pair
 from util import golden
 
 pytestmark = pytest.mark.gpu
@@ -27,25 +28,6 @@ WIDE = np.longdouble if np.finfo(np.longdouble).eps < np.finfo(np.float64).eps e
 def _device():
     if tp.device_count() < 1:
         pytest.fail("the GPU suite needs an MI355X")
-
-
-def grid_pair(seed, n_s, n_t):
-    """Integer clouds in [-64, 64] and a pose (signed axis permutation + integer shift) under which the first
-    ceil(2 n_s / 3) source points land exactly on target points (duplicates among the targets included, so ties
-    occur) and the others a whole unit or more away from every target."""
-    rng = np.random.default_rng(seed)
-    T = np.zeros((4, 4))
-    T[0, 2], T[1, 0], T[2, 1], T[3, 3] = -1.0, 1.0, -1.0, 1.0
-    T[:3, 3] = [3.0, -7.0, 11.0]
-    Q = rng.integers(-12, 13, size=(n_t, 3)).astype(np.float64) * np.array([5.0, 4.0, 2.0])  # |coordinates| <= 60
-    X = np.zeros((n_s, 3))
-    hit = (2 * n_s + 2) // 3
-    if n_t:
-        X[:hit] = Q[rng.integers(0, n_t, size=hit)]
-        X[hit:] = Q[rng.integers(0, n_t, size=n_s - hit)] + np.array([1.0, 1.0, 1.0])  # off the 5 x 4 x 2 lattice
-    P = (X - T[:3, 3]) @ T[:3, :3]  # T^-1 X, exact
-    assert np.array_equal(R.apply(T, P), X)
-    return P, Q, T
 
 
 def bunny():
