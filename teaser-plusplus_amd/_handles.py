@@ -1,5 +1,6 @@
-"""What icp.py, voxel.py and features.py share: the per-device cache of library handles and the normalisation of a
-point-cloud argument.
+"""What the modules of the handles share: the per-device cache of library handles, the normalisation of a point-cloud
+or correspondence argument and of a per-problem argument, the pointer-and-count arrays of a batched call and the
+option accessors of the handles that have tuning knobs (ransac.py, fgr.py, plane.py).
 
 One C handle is kept per device, shared by every thread of the process.  A handle is not re-entrant (its stream,
 device buffers and staging memory serve one call at a time) and ctypes releases the GIL during the call, so each handle
@@ -92,3 +93,45 @@ def _cloud(a, what, dtype=np.float64, kind="array"):
     if a.ndim != 2 or a.shape[1] != 3:
         raise ValueError("%s must be an n x 3 %s, got shape %s" % (what, kind, a.shape))
     return a
+
+
+def _pairs(corres, what):
+    """`corres` as a C-contiguous n x 2 int32 array (an empty one is 0 x 2); ValueError names it `what`."""
+    a = np.ascontiguousarray(np.asarray(corres, dtype=np.int32))
+    if a.size == 0:
+        return np.zeros((0, 2), dtype=np.int32)
+    if a.ndim != 2 or a.shape[1] != 2:
+        raise ValueError("%s must be an n x 2 integer array, got shape %s" % (what, a.shape))
+    return a
+
+
+def _per_problem(value, b, what):
+    """A per-problem argument as a list of b values: a list, tuple or array holds one per problem, anything else is
+    the value of every problem."""
+    if isinstance(value, (list, tuple, np.ndarray)):
+        if len(value) != b:
+            raise ValueError("%s: %d values for %d problems" % (what, len(value), b))
+        return list(value)
+    return [value] * b
+
+
+def _rows(arrays, ptr_type):
+    """What a batched C call takes for a list of 2-D arrays: the array of their row pointers (`ptr_type` each) and the
+    int32 array of their row counts.  The caller keeps `arrays` and the counts alive across the call."""
+    b = len(arrays)
+    ptrs = (ptr_type * max(b, 1))(*[a.ctypes.data_as(ptr_type) for a in arrays])
+    return ptrs, np.array([len(a) for a in arrays], dtype=np.int32)
+
+
+def _set_option(cache, name, value, device):
+    """prefix_set_option(name, value) on the cached handle of `device`."""
+    h = cache.get(device)
+    h.call(getattr(h._lib, cache.prefix + "_set_option"), name.encode(), int(value))
+
+
+def _get_option(cache, name, device):
+    """prefix_get_option(name) on the cached handle of `device`."""
+    h = cache.get(device)
+    v = C.c_int64()
+    h.call(getattr(h._lib, cache.prefix + "_get_option"), name.encode(), C.byref(v))
+    return v.value

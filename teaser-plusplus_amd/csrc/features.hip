@@ -75,10 +75,6 @@ struct teaser_hip_features : HandleBase {
   std::vector<FeatSearchDesc> search;
   std::vector<FeatTupleDesc> tuple;
   std::vector<int32_t> blk_tuple;
-  ~teaser_hip_features() {
-    for (DevBuf& b : buf) b.release();
-    for (HostBuf& b : host) b.release();
-  }
 };
 
 namespace {

@@ -11,7 +11,7 @@
 #include <vector>
 
 #include "fgr_device.h"
-#include "host_common.h"
+#include "packed_call.h"
 #include "teaser_hip.h"
 
 using namespace thip;
@@ -20,27 +20,9 @@ struct teaser_hip_fgr : HandleBase {
   DevBuf in, pairs, work, state, log;
   HostBuf stage, back;  // page-locked: the upload and the download stay asynchronous until the one synchronisation
   int64_t resident_max_corr = FGR_RES_DEFAULT;
-  ~teaser_hip_fgr() {
-    in.release();
-    pairs.release();
-    work.release();
-    state.release();
-    log.release();
-    stage.release();
-    back.release();
-  }
 };
 
 namespace thip {
-
-struct FgrPack {  // offsets of the sections of one buffer, each aligned to 256 bytes
-  size_t bytes = 0;
-  size_t add(size_t n) {
-    const size_t at = bytes;
-    bytes += (n + 255) / 256 * 256;
-    return at;
-  }
-};
 
 // The route of a problem: 0 none (not optimised), 1 resident, 2 streamed.
 inline int fgr_route(int32_t ncorr, int64_t resident_max_corr) {
@@ -51,6 +33,8 @@ inline int fgr_route(int32_t ncorr, int64_t resident_max_corr) {
 }  // namespace thip
 
 namespace {
+
+const Knob<teaser_hip_fgr> kKnobs[] = {{"resident_max_corr", 0, FGR_RES_BOUND, &teaser_hip_fgr::resident_max_corr}};
 
 void params_default(teaser_fgr_params_c* p) {
   memset(p, 0, sizeof(*p));
@@ -70,12 +54,9 @@ struct Stage {  // the stage call's outputs; all NULL in the full call
 int32_t run(teaser_hip_fgr* h, int32_t batch, const double* const* src, const int32_t* n_src, const double* const* dst,
             const int32_t* n_dst, const int32_t* const* corr, const int32_t* n_corr, const teaser_fgr_params_c* params,
             teaser_fgr_result_c* out, const Stage& sg) {
-  if (!h) return TEASER_HIP_ERR_BAD_ARG;
-  h->err.clear();
+  const int32_t r0 = begin_call(h, batch);
+  if (r0 != TEASER_HIP_OK) return r0;
   const bool staged = sg.n >= 0;
-  if (batch < 0) return fail(h, TEASER_HIP_ERR_BAD_ARG, "batch must be >= 0");
-  if (batch > 65535)  // problems are indexed by blockIdx.y or blockIdx.z
-    return fail(h, TEASER_HIP_ERR_UNSUPPORTED, "a batch holds at most 65535 problems; split larger batches across calls");
   if (batch == 0) return TEASER_HIP_OK;
   if (!staged && !out) return fail(h, TEASER_HIP_ERR_BAD_ARG, "out must not be NULL");
   if (!n_src) return fail(h, TEASER_HIP_ERR_BAD_ARG, "n_src must not be NULL");
@@ -108,14 +89,8 @@ int32_t run(teaser_hip_fgr* h, int32_t batch, const double* const* src, const in
     if (n_corr[b] > 0 && (!corr || !corr[b])) return fail(h, TEASER_HIP_ERR_BAD_ARG, "corr is NULL" + at(b));
     if (!finite_points(src[b], n_src[b])) return fail(h, TEASER_HIP_ERR_BAD_ARG, "src has non-finite points" + at(b));
     if (!finite_points(dst[b], n_dst[b])) return fail(h, TEASER_HIP_ERR_BAD_ARG, "dst has non-finite points" + at(b));
-    for (int c = 0; c < n_corr[b]; ++c) {
-      if (corr[b][2 * c] < 0 || corr[b][2 * c] >= n_src[b])
-        return fail(h, TEASER_HIP_ERR_BAD_ARG,
-                    "corr: source index of pair " + std::to_string(c) + " is outside the cloud" + at(b));
-      if (corr[b][2 * c + 1] < 0 || corr[b][2 * c + 1] >= n_dst[b])
-        return fail(h, TEASER_HIP_ERR_BAD_ARG,
-                    "corr: target index of pair " + std::to_string(c) + " is outside the cloud" + at(b));
-    }
+    if (n_corr[b] > 0 && check_pairs(h, b, corr[b], n_corr[b], n_src[b], n_dst[b]) != TEASER_HIP_OK)
+      return TEASER_HIP_ERR_BAD_ARG;  // the message is check_pairs's
     FgrDesc& d = desc[(size_t)b];
     memset(&d, 0, sizeof(d));
     d.src_off = ns;
@@ -155,12 +130,12 @@ int32_t run(teaser_hip_fgr* h, int32_t batch, const double* const* src, const in
   FCHK(h, hipSetDevice(h->device), "hipSetDevice");
   hipStream_t s = h->stream;
   // ---- one upload: descriptors, the route lists, both clouds, the pairs ----
-  FgrPack pin;
+  Pack pin;
   const size_t i_desc = pin.add(sizeof(FgrDesc) * batch), i_res = pin.add(sizeof(int32_t) * batch),
                i_str = pin.add(sizeof(int32_t) * batch), i_src = pin.add(sizeof(double) * 3 * (size_t)ns),
                i_dst = pin.add(sizeof(double) * 3 * (size_t)nt),
                i_corr = pin.add(sizeof(int32_t) * 2 * (size_t)std::max<int64_t>(nc, 1));
-  FgrPack pw;
+  Pack pw;
   const size_t w_sum = pw.add(sizeof(double) * 3 * (size_t)cblk), w_max = pw.add(sizeof(double) * (size_t)cblk),
                w_part = pw.add(sizeof(double) * FGR_SUMS * (size_t)std::max<int64_t>(pblk, 1));
   const size_t log_bytes = staged ? sizeof(FgrLog) * (size_t)batch * (size_t)std::max(sg.n, 1) : 0;
@@ -174,29 +149,26 @@ int32_t run(teaser_hip_fgr* h, int32_t batch, const double* const* src, const in
   memcpy(stage + i_desc, desc.data(), sizeof(FgrDesc) * batch);
   if (!res_idx.empty()) memcpy(stage + i_res, res_idx.data(), sizeof(int32_t) * res_idx.size());
   if (!str_idx.empty()) memcpy(stage + i_str, str_idx.data(), sizeof(int32_t) * str_idx.size());
-  for (int b = 0; b < batch; ++b) {
-    const FgrDesc& d = desc[(size_t)b];
-    memcpy(stage + i_src + sizeof(double) * 3 * d.src_off, src[b], sizeof(double) * 3 * n_src[b]);
-    memcpy(stage + i_dst + sizeof(double) * 3 * d.dst_off, dst[b], sizeof(double) * 3 * n_dst[b]);
-    if (n_corr[b] > 0) memcpy(stage + i_corr + sizeof(int32_t) * 2 * d.corr_off, corr[b], sizeof(int32_t) * 2 * n_corr[b]);
-  }
+  pack_rows(stage + i_src, batch, src, n_src, sizeof(double) * 3);
+  pack_rows(stage + i_dst, batch, dst, n_dst, sizeof(double) * 3);
+  pack_rows(stage + i_corr, batch, corr, n_corr, sizeof(int32_t) * 2);
   FCHK(h, hipMemcpyAsync(h->in.p, stage, pin.bytes, hipMemcpyHostToDevice, s), "hipMemcpyAsync (FGR inputs)");
-  char* din = h->in.as<char>();
-  char* dw = h->work.as<char>();
+  void* din = h->in.p;
+  void* dw = h->work.p;
   FgrBufs B;
-  B.desc = reinterpret_cast<const FgrDesc*>(din + i_desc);
+  B.desc = Pack::at<const FgrDesc>(din, i_desc);
   B.state = h->state.as<FgrState>();
-  B.src = reinterpret_cast<const double*>(din + i_src);
-  B.dst = reinterpret_cast<const double*>(din + i_dst);
-  B.corr = reinterpret_cast<const int32_t*>(din + i_corr);
+  B.src = Pack::at<const double>(din, i_src);
+  B.dst = Pack::at<const double>(din, i_dst);
+  B.corr = Pack::at<const int32_t>(din, i_corr);
   B.pairs = h->pairs.as<double>();
-  B.cloud_sum = reinterpret_cast<double*>(dw + w_sum);
-  B.cloud_max = reinterpret_cast<double*>(dw + w_max);
-  B.partials = reinterpret_cast<double*>(dw + w_part);
+  B.cloud_sum = Pack::at<double>(dw, w_sum);
+  B.cloud_max = Pack::at<double>(dw, w_max);
+  B.partials = Pack::at<double>(dw, w_part);
   B.log = staged && sg.n > 0 ? h->log.as<FgrLog>() : nullptr;
   B.log_stride = staged ? sg.n : 0;
-  const int32_t* d_res = reinterpret_cast<const int32_t*>(din + i_res);
-  const int32_t* d_str = reinterpret_cast<const int32_t*>(din + i_str);
+  const int32_t* d_res = Pack::at<const int32_t>(din, i_res);
+  const int32_t* d_str = Pack::at<const int32_t>(din, i_str);
   if (B.log) FCHK(h, hipMemsetAsync(B.log, 0, log_bytes, s), "hipMemsetAsync (FGR log)");
   launch_fgr_normalise(s, batch, max_cloud_blk, max_pair_blk, B);
   FCHK(h, launch_fgr_resident(s, (int)res_idx.size(), d_res, max_res_blk, B, staged ? 1 : 0), "FGR resident launch");
@@ -278,18 +250,10 @@ int32_t teaser_hip_fgr_correspondence(teaser_hip_fgr* h, const double* src, int3
 }
 
 int32_t teaser_hip_fgr_set_option(teaser_hip_fgr* h, const char* name, int64_t value) {
-  if (!h) return TEASER_HIP_ERR_BAD_ARG;
-  if (!name || strcmp(name, "resident_max_corr") != 0)
-    return fail(h, TEASER_HIP_ERR_BAD_ARG, std::string("unknown option ") + (name ? name : "(NULL)"));
-  if (value < 0 || value > FGR_RES_BOUND) return fail(h, TEASER_HIP_ERR_BAD_ARG, "resident_max_corr must be in 0 .. 3072");
-  h->resident_max_corr = value;
-  return TEASER_HIP_OK;
+  return set_knob(h, kKnobs, name, value);
 }
-
 int32_t teaser_hip_fgr_get_option(const teaser_hip_fgr* h, const char* name, int64_t* value) {
-  if (!h || !value || !name || strcmp(name, "resident_max_corr") != 0) return TEASER_HIP_ERR_BAD_ARG;
-  *value = h->resident_max_corr;
-  return TEASER_HIP_OK;
+  return get_knob(h, kKnobs, name, value);
 }
 
 int32_t teaser_hip_fgr_iterations_batch(teaser_hip_fgr* h, int32_t batch, const double* const* src,

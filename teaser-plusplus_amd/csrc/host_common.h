@@ -1,8 +1,11 @@
 // host_common.h -- what the host sides of the handles share: the members and the error reporting every handle has
-// (HandleBase), the create sequence (open_handle) and, for the auxiliary handles (icp.hip, voxel.hip, features.hip), the
-// grow-only buffers and the destroy sequence.  solver.hip derives its handle from HandleBase and opens it with
-// open_handle, but keeps buffer types of its own under other names (SolverBuf, PinnedBuf: another growth rule, a
-// hipError_t answer with a retry at the exact size, and a view mode) and its own teardown (lanes, finisher threads).
+// (HandleBase), the create and destroy sequences (open_handle, close_handle), the one refusal every batched call words
+// the same way (over_batch_limit), the finiteness checks and, for every handle but the solver's, the grow-only buffers
+// (DevBuf, HostBuf), which free themselves when their handle goes.  The cloud calls of the ICP handle build on it in
+// icp_host.h, the packed calls of the RANSAC, plane, FGR and pose-graph handles in packed_call.h.  solver.hip derives its
+// handle from HandleBase and opens it with open_handle, but keeps buffer types of its own under other names (SolverBuf,
+// PinnedBuf: another growth rule, a hipError_t answer with a retry at the exact size, and a view mode) and its own
+// teardown (lanes, finisher threads).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -18,11 +21,16 @@ namespace thip {
 inline hipError_t device_alloc(void** p, size_t bytes) { return hipMalloc(p, bytes); }
 inline hipError_t pinned_alloc(void** p, size_t bytes) { return hipHostMalloc(p, bytes, hipHostMallocDefault); }
 
-// A buffer that only grows: a request above the capacity frees it and allocates a quarter more than asked for.
+// A buffer that only grows: a request above the capacity frees it and allocates a quarter more than asked for.  It
+// frees itself with the handle it is a member of, before ~HandleBase destroys the stream; it is never copied.
 template <hipError_t (*Alloc)(void**, size_t), hipError_t (*Free)(void*)>
 struct GrowBuf {
   void* p = nullptr;
   size_t cap = 0;
+  GrowBuf() = default;
+  GrowBuf(const GrowBuf&) = delete;
+  GrowBuf& operator=(const GrowBuf&) = delete;
+  ~GrowBuf() { release(); }
   bool ensure(size_t bytes) {
     if (bytes <= cap) return true;
     release();
@@ -42,8 +50,8 @@ struct GrowBuf {
 struct DevBuf : GrowBuf<device_alloc, hipFree> {};
 struct HostBuf : GrowBuf<pinned_alloc, hipHostFree> {};  // page-locked staging
 
-// What every handle has.  A handle derives from it, adds its buffers and releases them in its destructor; the
-// stream goes after them.
+// What every handle has.  A handle derives from it and adds its buffers; they go with the derived handle's members,
+// the stream after them.
 struct HandleBase {
   int device = 0;
   hipStream_t stream = nullptr;
@@ -72,11 +80,18 @@ inline std::string at(int b) { return " (problem " + std::to_string(b) + ")"; }
     if (e_ != hipSuccess) return hip_fail((h), e_, (what)); \
   } while (0)
 
-inline bool finite_points(const double* p, int64_t n) {
-  for (int64_t k = 0; k < 3 * n; ++k)
+// The refusal of a batch above what a grid's y or z extent indexes (problems are indexed by blockIdx.y or blockIdx.z).
+constexpr int32_t kMaxBatch = 65535;
+inline int32_t over_batch_limit(HandleBase* h) {
+  return fail(h, TEASER_HIP_ERR_UNSUPPORTED, "a batch holds at most 65535 problems; split larger batches across calls");
+}
+
+inline bool finite_all(const double* p, int64_t n) {
+  for (int64_t k = 0; k < n; ++k)
     if (!std::isfinite(p[k])) return false;
   return true;
 }
+inline bool finite_points(const double* p, int64_t n) { return finite_all(p, 3 * n); }
 
 // teaser_hip_*_create: a handle of type H on `device` (< 0: the current device) with a non-blocking stream.
 template <class H>

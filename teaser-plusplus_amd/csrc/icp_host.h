@@ -56,7 +56,6 @@ struct teaser_hip_icp : thip::HandleBase {
   int32_t fps_resident_max = thip::kFpsResidentCap;  // option "fps_resident_max" (icp_fps.hip)
   int64_t fpfh_list_bytes = thip::kFpfhListBytes;    // option "fpfh_list_bytes" (icp_fpfh.hip)
   ~teaser_hip_icp() {
-    for (thip::DevBuf& b : buf) b.release();
     if (h_live) (void)hipHostFree(h_live);
   }
 };

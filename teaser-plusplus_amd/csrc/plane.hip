@@ -6,14 +6,13 @@
 // lies past a problem's stopping trial is dropped unread.  The finish recomputes the winner's plane from (seed, trial).
 #include <math.h>
 #include <string.h>
-#include <time.h>
 
 #include <algorithm>
 #include <limits>
 #include <string>
 #include <vector>
 
-#include "host_common.h"
+#include "packed_call.h"
 #include "plane_device.h"
 #include "teaser_hip.h"
 
@@ -24,13 +23,6 @@ struct teaser_hip_plane : HandleBase {
   HostBuf stage;  // page-locked: the upload is one DMA copy at bus speed
   int64_t chunk_trials = 256;
   int64_t partial_bytes = 64ll << 20;
-  ~teaser_hip_plane() {
-    in.release();
-    work.release();
-    part.release();
-    fin.release();
-    stage.release();
-  }
 };
 
 namespace thip {
@@ -39,15 +31,6 @@ constexpr int PL_MAX_ROUND = 4;  // chunks enqueued before the host looks, at th
 constexpr int64_t PL_MIN_CHUNK = 64, PL_MAX_CHUNK = 4096;
 constexpr int64_t PL_MIN_PARTIAL = 1 << 16, PL_MAX_PARTIAL = 1ll << 34;
 constexpr int64_t PL_GROUP_BYTES = (PL_GROUP + 1) * 12;  // per trial of the chunk: 64 block records and the group's
-
-struct PlPack {  // offsets of the sections of one buffer, each aligned to 256 bytes
-  size_t bytes = 0;
-  size_t add(size_t n) {
-    const size_t at = bytes;
-    bytes += (n + 255) / 256 * 256;
-    return at;
-  }
-};
 
 // The groups of points one wave covers: the largest halving of the longest problem's groups whose partials, over the
 // whole batch, stay within the budget; one group per problem at the least.
@@ -108,6 +91,9 @@ struct PlWalk {
 
 namespace {
 
+const Knob<teaser_hip_plane> kKnobs[] = {{"chunk_trials", PL_MIN_CHUNK, PL_MAX_CHUNK, &teaser_hip_plane::chunk_trials},
+                                         {"partial_bytes", PL_MIN_PARTIAL, PL_MAX_PARTIAL, &teaser_hip_plane::partial_bytes}};
+
 void params_default(teaser_plane_params_c* p) {
   memset(p, 0, sizeof(*p));
   p->ransac_n = 3;
@@ -147,11 +133,7 @@ int32_t prepare(teaser_hip_plane* h, int32_t batch, const double* const* points,
     d.pt_off = p.total_points;
     d.blk_off = p.total_blocks;
     d.grp_off = p.total_groups;
-    d.seed = q.seed;
-    if (d.seed == 0) {
-      if (clock_seed == 0) clock_seed = (uint64_t)time(nullptr);  // read once per call
-      d.seed = clock_seed;
-    }
+    d.seed = call_seed(q.seed, clock_seed);
     d.d = q.distance_threshold;
     d.n = n[b];
     d.ransac_n = q.ransac_n;
@@ -168,20 +150,18 @@ int32_t prepare(teaser_hip_plane* h, int32_t batch, const double* const* points,
   }
   FCHK(h, hipSetDevice(h->device), "hipSetDevice");
   // ---- one upload: descriptors and clouds ----
-  PlPack pin;
+  Pack pin;
   const size_t i_desc = pin.add(sizeof(PlDesc) * batch),
                i_pts = pin.add(sizeof(double) * 3 * (size_t)std::max<int64_t>(p.total_points, 1));
   if (!h->in.ensure(pin.bytes) || !h->stage.ensure(pin.bytes))
     return fail(h, TEASER_HIP_ERR_HIP, "hipMalloc failed (plane inputs)");
   char* stage = h->stage.as<char>();
   memcpy(stage + i_desc, p.desc.data(), sizeof(PlDesc) * batch);
-  for (int b = 0; b < batch; ++b)
-    if (n[b] > 0) memcpy(stage + i_pts + sizeof(double) * 3 * p.desc[(size_t)b].pt_off, points[b], sizeof(double) * 3 * n[b]);
+  pack_rows(stage + i_pts, batch, points, n, sizeof(double) * 3);
   FCHK(h, hipMemcpyAsync(h->in.p, stage, pin.bytes, hipMemcpyHostToDevice, h->stream), "hipMemcpyAsync (plane inputs)");
   FCHK(h, hipStreamSynchronize(h->stream), "plane upload");  // the staging buffer is free for the next call
-  char* din = h->in.as<char>();
-  p.d_desc = reinterpret_cast<const PlDesc*>(din + i_desc);
-  p.d_pts = reinterpret_cast<const double*>(din + i_pts);
+  p.d_desc = Pack::at<const PlDesc>(h->in.p, i_desc);
+  p.d_pts = Pack::at<const double>(h->in.p, i_pts);
   return TEASER_HIP_OK;
 }
 
@@ -199,7 +179,7 @@ struct Layout {
     chunk = chunk_;
     samples = samples_;
     const size_t per = (size_t)batch * (size_t)chunk;
-    PlPack w;
+    Pack w;
     w_n = w.add(sizeof(int32_t) * batch);
     w_E = w.add(sizeof(double) * per);
     w_count = w.add(sizeof(int32_t) * per);
@@ -209,7 +189,7 @@ struct Layout {
     w_samples = w.add(samples ? sizeof(int32_t) * PL_MAX_N * per : 0);
     w_slot = w.bytes;
     const size_t groups = (size_t)std::max<int64_t>(p.part_groups, 1);
-    PlPack q;
+    Pack q;
     p_bcnt = q.add(sizeof(int32_t) * groups * PL_GROUP * (size_t)chunk);
     p_bsum = q.add(sizeof(double) * groups * PL_GROUP * (size_t)chunk);
     p_gcnt = q.add(sizeof(int32_t) * groups * (size_t)chunk);
@@ -220,23 +200,23 @@ struct Layout {
   }
   char* base(teaser_hip_plane* h, int g) const { return h->work.as<char>() + w_slot * g; }
   PlSlot slot(teaser_hip_plane* h, int g) const {
-    char* w = base(h, g);
+    void* w = base(h, g);
     PlSlot s;
-    s.n = reinterpret_cast<const int32_t*>(w + w_n);
-    s.E = reinterpret_cast<double*>(w + w_E);
-    s.count = reinterpret_cast<int32_t*>(w + w_count);
-    s.flags = reinterpret_cast<uint8_t*>(w + w_flags);
-    s.model = reinterpret_cast<double*>(w + w_model);
-    s.samples = samples ? reinterpret_cast<int32_t*>(w + w_samples) : nullptr;
+    s.n = Pack::at<const int32_t>(w, w_n);
+    s.E = Pack::at<double>(w, w_E);
+    s.count = Pack::at<int32_t>(w, w_count);
+    s.flags = Pack::at<uint8_t>(w, w_flags);
+    s.model = Pack::at<double>(w, w_model);
+    s.samples = samples ? Pack::at<int32_t>(w, w_samples) : nullptr;
     return s;
   }
   PlPart partials(teaser_hip_plane* h) const {
-    char* q = h->part.as<char>();
+    void* q = h->part.p;
     PlPart s;
-    s.bcnt = reinterpret_cast<int32_t*>(q + p_bcnt);
-    s.bsum = reinterpret_cast<double*>(q + p_bsum);
-    s.gcnt = reinterpret_cast<int32_t*>(q + p_gcnt);
-    s.gsum = reinterpret_cast<double*>(q + p_gsum);
+    s.bcnt = Pack::at<int32_t>(q, p_bcnt);
+    s.bsum = Pack::at<double>(q, p_bsum);
+    s.gcnt = Pack::at<int32_t>(q, p_gcnt);
+    s.gsum = Pack::at<double>(q, p_gsum);
     return s;
   }
 };
@@ -258,11 +238,8 @@ void default_result(teaser_plane_result_c* r) {
 int32_t run_full(teaser_hip_plane* h, int32_t batch, const double* const* points, const int32_t* n,
                  const teaser_plane_params_c* params, teaser_plane_result_c* out, int32_t* const* inliers,
                  uint8_t* const* mask) {
-  if (!h) return TEASER_HIP_ERR_BAD_ARG;
-  h->err.clear();
-  if (batch < 0) return fail(h, TEASER_HIP_ERR_BAD_ARG, "batch must be >= 0");
-  if (batch > 65535)  // problems are indexed by blockIdx.y or blockIdx.z
-    return fail(h, TEASER_HIP_ERR_UNSUPPORTED, "a batch holds at most 65535 problems; split larger batches across calls");
+  const int32_t r0 = begin_call(h, batch);
+  if (r0 != TEASER_HIP_OK) return r0;
   if (batch == 0) return TEASER_HIP_OK;
   if (!out) return fail(h, TEASER_HIP_ERR_BAD_ARG, "out must not be NULL");
   Prep p;
@@ -311,9 +288,9 @@ int32_t run_full(teaser_hip_plane* h, int32_t batch, const double* const* points
       PlWalk& w = walk[(size_t)b];
       for (int g = 0; g < used && !w.done; ++g) {
         const char* rec = down.data() + L.w_read * g;
-        const double* E = reinterpret_cast<const double*>(rec + L.w_E) + (size_t)b * chunk;
-        const int32_t* count = reinterpret_cast<const int32_t*>(rec + L.w_count) + (size_t)b * chunk;
-        const uint8_t* flags = reinterpret_cast<const uint8_t*>(rec + L.w_flags) + (size_t)b * chunk;
+        const double* E = Pack::at<const double>(rec, L.w_E) + (size_t)b * chunk;
+        const int32_t* count = Pack::at<const int32_t>(rec, L.w_count) + (size_t)b * chunk;
+        const uint8_t* flags = Pack::at<const uint8_t>(rec, L.w_flags) + (size_t)b * chunk;
         const int64_t first = first0 + g * chunk;
         const int m = plan[(size_t)g * batch + b];
         for (int t = 0; t < m && !w.done; ++t)
@@ -323,7 +300,7 @@ int32_t run_full(teaser_hip_plane* h, int32_t batch, const double* const* points
     }
   }
   // ---- finish: the mask under the winner, the refit ----
-  PlPack f;
+  Pack f;
   const size_t f_best = f.add(sizeof(int64_t) * batch), f_win = f.add(sizeof(double) * 4 * batch),
                f_cen = f.add(sizeof(double) * 3 * batch), f_out = f.add(sizeof(double) * 4 * batch),
                f_m = f.add(sizeof(int32_t) * batch), f_mask = f.add((size_t)std::max<int64_t>(p.total_points, 1)),
@@ -334,16 +311,16 @@ int32_t run_full(teaser_hip_plane* h, int32_t batch, const double* const* points
   if (!h->fin.ensure(f.bytes)) return fail(h, TEASER_HIP_ERR_HIP, "hipMalloc failed (plane finish buffers)");
   char* df = h->fin.as<char>();
   PlFin fin;
-  fin.best = reinterpret_cast<const int64_t*>(df + f_best);
-  fin.win = reinterpret_cast<double*>(df + f_win);
-  fin.centroid = reinterpret_cast<double*>(df + f_cen);
-  fin.plane = reinterpret_cast<double*>(df + f_out);
-  fin.m = reinterpret_cast<int32_t*>(df + f_m);
-  fin.mask = reinterpret_cast<uint8_t*>(df + f_mask);
-  fin.bsum = reinterpret_cast<double*>(df + f_bsum);
-  fin.bcnt = reinterpret_cast<int32_t*>(df + f_bcnt);
-  fin.gsum = reinterpret_cast<double*>(df + f_gsum);
-  fin.gcnt = reinterpret_cast<int32_t*>(df + f_gcnt);
+  fin.best = Pack::at<const int64_t>(df, f_best);
+  fin.win = Pack::at<double>(df, f_win);
+  fin.centroid = Pack::at<double>(df, f_cen);
+  fin.plane = Pack::at<double>(df, f_out);
+  fin.m = Pack::at<int32_t>(df, f_m);
+  fin.mask = Pack::at<uint8_t>(df, f_mask);
+  fin.bsum = Pack::at<double>(df, f_bsum);
+  fin.bcnt = Pack::at<int32_t>(df, f_bcnt);
+  fin.gsum = Pack::at<double>(df, f_gsum);
+  fin.gcnt = Pack::at<int32_t>(df, f_gcnt);
   std::vector<int64_t> best((size_t)batch);
   for (int b = 0; b < batch; ++b) best[(size_t)b] = walk[(size_t)b].best_trial;
   FCHK(h, hipMemcpyAsync(df + f_best, best.data(), sizeof(int64_t) * batch, hipMemcpyHostToDevice, s),
@@ -388,11 +365,8 @@ int32_t run_full(teaser_hip_plane* h, int32_t batch, const double* const* points
 int32_t run_trials(teaser_hip_plane* h, int32_t batch, const double* const* points, const int32_t* n,
                    const teaser_plane_params_c* params, int64_t first, int32_t cnt, int32_t* samples, uint8_t* flags,
                    double* planes, int32_t* count, double* E) {
-  if (!h) return TEASER_HIP_ERR_BAD_ARG;
-  h->err.clear();
-  if (batch < 0) return fail(h, TEASER_HIP_ERR_BAD_ARG, "batch must be >= 0");
-  if (batch > 65535)  // problems are indexed by blockIdx.y or blockIdx.z
-    return fail(h, TEASER_HIP_ERR_UNSUPPORTED, "a batch holds at most 65535 problems; split larger batches across calls");
+  const int32_t r0 = begin_call(h, batch);
+  if (r0 != TEASER_HIP_OK) return r0;
   if (first < 0) return fail(h, TEASER_HIP_ERR_BAD_ARG, "first must be >= 0");
   if (cnt < 0 || cnt > 65536) return fail(h, TEASER_HIP_ERR_BAD_ARG, "cnt must be in 0 .. 65536");
   if (batch == 0) return TEASER_HIP_OK;
@@ -458,31 +432,10 @@ int32_t teaser_hip_plane_segment(teaser_hip_plane* h, const double* points, int3
 }
 
 int32_t teaser_hip_plane_set_option(teaser_hip_plane* h, const char* name, int64_t value) {
-  if (!h) return TEASER_HIP_ERR_BAD_ARG;
-  if (name && strcmp(name, "chunk_trials") == 0) {
-    if (value < PL_MIN_CHUNK || value > PL_MAX_CHUNK) return fail(h, TEASER_HIP_ERR_BAD_ARG, "chunk_trials must be in 64 .. 4096");
-    h->chunk_trials = value;
-    return TEASER_HIP_OK;
-  }
-  if (name && strcmp(name, "partial_bytes") == 0) {
-    if (value < PL_MIN_PARTIAL || value > PL_MAX_PARTIAL)
-      return fail(h, TEASER_HIP_ERR_BAD_ARG, "partial_bytes must be in 65536 .. 17179869184");
-    h->partial_bytes = value;
-    return TEASER_HIP_OK;
-  }
-  return fail(h, TEASER_HIP_ERR_BAD_ARG, std::string("unknown option ") + (name ? name : "(NULL)"));
+  return set_knob(h, kKnobs, name, value);
 }
-
 int32_t teaser_hip_plane_get_option(const teaser_hip_plane* h, const char* name, int64_t* value) {
-  if (!h || !value || !name) return TEASER_HIP_ERR_BAD_ARG;
-  if (strcmp(name, "chunk_trials") == 0) {
-    *value = h->chunk_trials;
-  } else if (strcmp(name, "partial_bytes") == 0) {
-    *value = h->partial_bytes;
-  } else {
-    return TEASER_HIP_ERR_BAD_ARG;
-  }
-  return TEASER_HIP_OK;
+  return get_knob(h, kKnobs, name, value);
 }
 
 int32_t teaser_hip_plane_trials_batch(teaser_hip_plane* h, int32_t batch, const double* const* points, const int32_t* n,

@@ -10,7 +10,7 @@
 #include <string>
 #include <vector>
 
-#include "host_common.h"
+#include "packed_call.h"
 #include "posegraph_device.h"
 #include "teaser_hip.h"
 
@@ -18,25 +18,9 @@ using namespace thip;
 
 struct teaser_hip_posegraph : HandleBase {
   DevBuf in, work, dense, out;
-  ~teaser_hip_posegraph() {
-    in.release();
-    work.release();
-    dense.release();
-    out.release();
-  }
 };
 
 namespace thip {
-
-// Offsets of the sections of one packed buffer, each aligned to 256 bytes.
-struct PgPack {
-  size_t bytes = 0;
-  size_t add(size_t n) {
-    const size_t at = bytes;
-    bytes += (n + 255) / 256 * 256;
-    return at;
-  }
-};
 
 // The index of a call: descriptors, CSR and pair lists.  Built by pg_build_index; tests/posegraph_host_driver.cpp
 // checks it against brute force.
@@ -120,12 +104,6 @@ inline void pg_build_index(PgIndex& ix, int batch, const int32_t* n_nodes, const
 
 namespace {
 
-bool finite_all(const double* p, int64_t n) {
-  for (int64_t k = 0; k < n; ++k)
-    if (!std::isfinite(p[k])) return false;
-  return true;
-}
-
 void option_default(teaser_posegraph_option_c* o) {
   memset(o, 0, sizeof(*o));
   o->max_iteration = 100;
@@ -154,9 +132,8 @@ int32_t run(teaser_hip_posegraph* h, int mode, int32_t batch, const int32_t* n_n
             const int32_t* n_edges, const int32_t* src, const int32_t* tgt, const double* X, const double* L,
             const uint8_t* unc, const teaser_posegraph_option_c* options, const int32_t* trace_cap,
             const PgOutputs& o) {
-  if (!h) return TEASER_HIP_ERR_BAD_ARG;
-  h->err.clear();
-  if (batch < 0) return fail(h, TEASER_HIP_ERR_BAD_ARG, "batch must be >= 0");
+  const int32_t r0 = begin_call(h, batch, false);  // a workgroup per graph along x: no grid limit
+  if (r0 != TEASER_HIP_OK) return r0;
   if (batch == 0) return TEASER_HIP_OK;
   if (!n_nodes) return fail(h, TEASER_HIP_ERR_BAD_ARG, "n_nodes must not be NULL");
   if (!n_edges) return fail(h, TEASER_HIP_ERR_BAD_ARG, "n_edges must not be NULL");
@@ -239,7 +216,7 @@ int32_t run(teaser_hip_posegraph* h, int mode, int32_t batch, const int32_t* n_n
   // ---- index and packing ----
   PgIndex ix;
   pg_build_index(ix, batch, n_nodes, n_edges, src, tgt, opts.data(), o.trace ? trace_cap : nullptr, mode);
-  PgPack pin, pwork, pout;
+  Pack pin, pwork, pout;
   const size_t N1 = (size_t)std::max<int64_t>(nodes, 1), M1 = (size_t)std::max<int64_t>(edges, 1);
   const size_t i_desc = pin.add(sizeof(PgDesc) * batch), i_poses = pin.add(sizeof(double) * 16 * N1),
                i_src = pin.add(4 * M1), i_tgt = pin.add(4 * M1), i_X = pin.add(sizeof(double) * 16 * M1),
@@ -279,39 +256,39 @@ int32_t run(teaser_hip_posegraph* h, int mode, int32_t batch, const int32_t* n_n
   hipStream_t s = h->stream;
   FCHK(h, hipMemcpyAsync(h->in.p, stage.data(), pin.bytes, hipMemcpyHostToDevice, s), "hipMemcpyAsync (pose graphs)");
 
-  char* din = h->in.as<char>();
-  char* dw = h->work.as<char>();
-  char* dout = h->out.as<char>();
+  void* din = h->in.p;
+  void* dw = h->work.p;
+  void* dout = h->out.p;
   PgArgs a;
   memset(&a, 0, sizeof(a));
-  a.desc = reinterpret_cast<const PgDesc*>(din + i_desc);
-  a.poses_in = reinterpret_cast<const double*>(din + i_poses);
-  a.src = reinterpret_cast<const int32_t*>(din + i_src);
-  a.tgt = reinterpret_cast<const int32_t*>(din + i_tgt);
-  a.X = reinterpret_cast<const double*>(din + i_X);
-  a.L = reinterpret_cast<const double*>(din + i_L);
-  a.unc = reinterpret_cast<const uint8_t*>(din + i_unc);
-  a.node_ptr = reinterpret_cast<const int32_t*>(din + i_nptr);
-  a.inc_edge = reinterpret_cast<const int32_t*>(din + i_inc);
-  a.pair_u = reinterpret_cast<const int32_t*>(din + i_pu);
-  a.pair_v = reinterpret_cast<const int32_t*>(din + i_pv);
-  a.pair_ptr = reinterpret_cast<const int32_t*>(din + i_pptr);
-  a.pair_edge = reinterpret_cast<const int32_t*>(din + i_pe);
-  a.pose_cur = reinterpret_cast<double*>(dw + w_cur);
-  a.pose_cand = reinterpret_cast<double*>(dw + w_cand);
-  a.A = reinterpret_cast<double*>(dw + w_A);
-  a.bv = reinterpret_cast<double*>(dw + w_b);
+  a.desc = Pack::at<const PgDesc>(din, i_desc);
+  a.poses_in = Pack::at<const double>(din, i_poses);
+  a.src = Pack::at<const int32_t>(din, i_src);
+  a.tgt = Pack::at<const int32_t>(din, i_tgt);
+  a.X = Pack::at<const double>(din, i_X);
+  a.L = Pack::at<const double>(din, i_L);
+  a.unc = Pack::at<const uint8_t>(din, i_unc);
+  a.node_ptr = Pack::at<const int32_t>(din, i_nptr);
+  a.inc_edge = Pack::at<const int32_t>(din, i_inc);
+  a.pair_u = Pack::at<const int32_t>(din, i_pu);
+  a.pair_v = Pack::at<const int32_t>(din, i_pv);
+  a.pair_ptr = Pack::at<const int32_t>(din, i_pptr);
+  a.pair_edge = Pack::at<const int32_t>(din, i_pe);
+  a.pose_cur = Pack::at<double>(dw, w_cur);
+  a.pose_cand = Pack::at<double>(dw, w_cand);
+  a.A = Pack::at<double>(dw, w_A);
+  a.bv = Pack::at<double>(dw, w_b);
   a.H = h->dense.as<double>();
   a.M = h->dense.as<double>() + dense1;
-  a.poses_out = reinterpret_cast<double*>(dout + o_poses);
-  a.conf = reinterpret_cast<double*>(dout + o_conf);
-  a.pruned = reinterpret_cast<uint8_t*>(dout + o_pruned);
-  a.res = reinterpret_cast<teaser_posegraph_result_c*>(dout + o_res);
-  a.trace = o.trace ? reinterpret_cast<teaser_posegraph_trace_c*>(dout + o_trace) : nullptr;
-  a.e = reinterpret_cast<double*>(dout + o_e);
-  a.r = reinterpret_cast<double*>(dout + o_r);
-  a.l = reinterpret_cast<double*>(dout + o_l);
-  a.g = reinterpret_cast<double*>(dout + o_g);
+  a.poses_out = Pack::at<double>(dout, o_poses);
+  a.conf = Pack::at<double>(dout, o_conf);
+  a.pruned = Pack::at<uint8_t>(dout, o_pruned);
+  a.res = Pack::at<teaser_posegraph_result_c>(dout, o_res);
+  a.trace = o.trace ? Pack::at<teaser_posegraph_trace_c>(dout, o_trace) : nullptr;
+  a.e = Pack::at<double>(dout, o_e);
+  a.r = Pack::at<double>(dout, o_r);
+  a.l = Pack::at<double>(dout, o_l);
+  a.g = Pack::at<double>(dout, o_g);
   a.mode = mode;
   launch_posegraph(s, batch, a);
   FCHK(h, hipGetLastError(), "pose-graph kernel launch");
@@ -326,7 +303,7 @@ int32_t run(teaser_hip_posegraph* h, int mode, int32_t batch, const int32_t* n_n
          "hipMemcpyAsync (H)");
   }
   FCHK(h, hipStreamSynchronize(s), "pose-graph optimisation");
-  const teaser_posegraph_result_c* res = reinterpret_cast<const teaser_posegraph_result_c*>(back.data() + o_res);
+  const teaser_posegraph_result_c* res = Pack::at<const teaser_posegraph_result_c>(back.data(), o_res);
   auto get = [&](void* dst, size_t at_, size_t n) {
     if (dst && n) memcpy(dst, back.data() + at_, n);
   };
@@ -347,7 +324,7 @@ int32_t run(teaser_hip_posegraph* h, int mode, int32_t batch, const int32_t* n_n
   get(o.e, o_e, sizeof(double) * 6 * (size_t)edges);
   get(o.r, o_r, sizeof(double) * (size_t)edges);
   get(o.l, o_l, sizeof(double) * (size_t)edges);
-  const double* gfree = reinterpret_cast<const double*>(back.data() + o_g);
+  const double* gfree = Pack::at<const double>(back.data(), o_g);
   int64_t h_at = 0;
   for (int b = 0; b < batch; ++b) {
     const PgDesc& d = ix.desc[(size_t)b];

@@ -6,13 +6,12 @@
 // host walks those lists with log, pow and ceil; what lies past a problem's stopping trial is dropped unread.
 #include <math.h>
 #include <string.h>
-#include <time.h>
 
 #include <algorithm>
 #include <string>
 #include <vector>
 
-#include "host_common.h"
+#include "packed_call.h"
 #include "ransac_device.h"
 #include "teaser_hip.h"
 
@@ -21,27 +20,12 @@ using namespace thip;
 struct teaser_hip_ransac : HandleBase {
   DevBuf in, pairs, work, ctl;
   int64_t chunk_trials = 4096;
-  ~teaser_hip_ransac() {
-    in.release();
-    pairs.release();
-    work.release();
-    ctl.release();
-  }
 };
 
 namespace thip {
 
 constexpr int RS_MAX_GROUP = 4;               // chunks enqueued before the host looks
 constexpr int64_t RS_GROUP_RECORDS = 1 << 21;  // ... as long as their per-trial records stay below this many
-
-struct RsPack {  // offsets of the sections of one buffer, each aligned to 256 bytes
-  size_t bytes = 0;
-  size_t add(size_t n) {
-    const size_t at = bytes;
-    bytes += (n + 255) / 256 * 256;
-    return at;
-  }
-};
 
 // The chunks of a group: how many, given the chunk size and the batch.
 inline int rs_group_chunks(int64_t chunk, int batch) {
@@ -85,6 +69,8 @@ struct RsWalk {
 }  // namespace thip
 
 namespace {
+
+const Knob<teaser_hip_ransac> kKnobs[] = {{"chunk_trials", 64, 65536, &teaser_hip_ransac::chunk_trials}};
 
 void params_default(teaser_ransac_params_c* p) {
   memset(p, 0, sizeof(*p));
@@ -139,24 +125,14 @@ int32_t prepare(teaser_hip_ransac* h, int32_t batch, const double* const* src, c
       return fail(h, TEASER_HIP_ERR_BAD_ARG, "src has non-finite points" + at(b));
     if (n_dst[b] > 0 && !finite_points(dst[b], n_dst[b]))
       return fail(h, TEASER_HIP_ERR_BAD_ARG, "dst has non-finite points" + at(b));
-    for (int c = 0; c < n_corr[b]; ++c) {
-      if (corr[b][2 * c] < 0 || corr[b][2 * c] >= n_src[b])
-        return fail(h, TEASER_HIP_ERR_BAD_ARG,
-                    "corr: source index of pair " + std::to_string(c) + " is outside the cloud" + at(b));
-      if (corr[b][2 * c + 1] < 0 || corr[b][2 * c + 1] >= n_dst[b])
-        return fail(h, TEASER_HIP_ERR_BAD_ARG,
-                    "corr: target index of pair " + std::to_string(c) + " is outside the cloud" + at(b));
-    }
+    if (n_corr[b] > 0 && check_pairs(h, b, corr[b], n_corr[b], n_src[b], n_dst[b]) != TEASER_HIP_OK)
+      return TEASER_HIP_ERR_BAD_ARG;  // the message is check_pairs's
     RsDesc& d = p.desc[(size_t)b];
     memset(&d, 0, sizeof(d));
     d.pair_off = d.corr_off = p.total_corr;
     d.src_off = ns;
     d.dst_off = nt;
-    d.seed = q.seed;
-    if (d.seed == 0) {
-      if (clock_seed == 0) clock_seed = (uint64_t)time(nullptr);  // read once per call
-      d.seed = clock_seed;
-    }
+    d.seed = call_seed(q.seed, clock_seed);
     d.r2 = q.max_correspondence_distance * q.max_correspondence_distance;
     d.s = q.edge_length_threshold;
     d.d = q.distance_threshold;
@@ -170,7 +146,7 @@ int32_t prepare(teaser_hip_ransac* h, int32_t batch, const double* const* src, c
   }
   FCHK(h, hipSetDevice(h->device), "hipSetDevice");
   // ---- one upload: descriptors, both clouds, the pairs; then the pack launch ----
-  RsPack pin;
+  Pack pin;
   const size_t i_desc = pin.add(sizeof(RsDesc) * batch), i_src = pin.add(sizeof(double) * 3 * (size_t)std::max<int64_t>(ns, 1)),
                i_dst = pin.add(sizeof(double) * 3 * (size_t)std::max<int64_t>(nt, 1)),
                i_corr = pin.add(sizeof(int32_t) * 2 * (size_t)std::max<int64_t>(p.total_corr, 1));
@@ -178,21 +154,16 @@ int32_t prepare(teaser_hip_ransac* h, int32_t batch, const double* const* src, c
     return fail(h, TEASER_HIP_ERR_HIP, "hipMalloc failed (RANSAC inputs)");
   std::vector<char> stage(pin.bytes, 0);
   memcpy(stage.data() + i_desc, p.desc.data(), sizeof(RsDesc) * batch);
-  for (int b = 0; b < batch; ++b) {
-    const RsDesc& d = p.desc[(size_t)b];
-    if (n_src[b] > 0) memcpy(stage.data() + i_src + sizeof(double) * 3 * d.src_off, src[b], sizeof(double) * 3 * n_src[b]);
-    if (n_dst[b] > 0) memcpy(stage.data() + i_dst + sizeof(double) * 3 * d.dst_off, dst[b], sizeof(double) * 3 * n_dst[b]);
-    if (n_corr[b] > 0)
-      memcpy(stage.data() + i_corr + sizeof(int32_t) * 2 * d.corr_off, corr[b], sizeof(int32_t) * 2 * n_corr[b]);
-  }
+  pack_rows(stage.data() + i_src, batch, src, n_src, sizeof(double) * 3);
+  pack_rows(stage.data() + i_dst, batch, dst, n_dst, sizeof(double) * 3);
+  pack_rows(stage.data() + i_corr, batch, corr, n_corr, sizeof(int32_t) * 2);
   FCHK(h, hipMemcpyAsync(h->in.p, stage.data(), pin.bytes, hipMemcpyHostToDevice, h->stream), "hipMemcpyAsync (RANSAC inputs)");
   FCHK(h, hipStreamSynchronize(h->stream), "RANSAC upload");  // `stage` goes out of scope with this function
-  char* din = h->in.as<char>();
-  p.d_desc = reinterpret_cast<const RsDesc*>(din + i_desc);
+  void* din = h->in.p;
+  p.d_desc = Pack::at<const RsDesc>(din, i_desc);
   p.d_pairs = h->pairs.as<double>();
-  launch_ransac_pack(h->stream, batch, p.max_corr, p.d_desc, reinterpret_cast<const double*>(din + i_src),
-                     reinterpret_cast<const double*>(din + i_dst), reinterpret_cast<const int32_t*>(din + i_corr),
-                     h->pairs.as<double>());
+  launch_ransac_pack(h->stream, batch, p.max_corr, p.d_desc, Pack::at<const double>(din, i_src),
+                     Pack::at<const double>(din, i_dst), Pack::at<const int32_t>(din, i_corr), h->pairs.as<double>());
   FCHK(h, hipGetLastError(), "RANSAC pack launch");
   return TEASER_HIP_OK;
 }
@@ -210,7 +181,7 @@ struct Layout {
     chunk = chunk_;
     samples = samples_;
     const size_t per = (size_t)batch * (size_t)chunk;
-    RsPack w;
+    Pack w;
     w_T = w.add(sizeof(double) * 12 * per);
     w_flags = w.add(per);
     w_count = w.add(sizeof(int32_t) * per);
@@ -218,7 +189,7 @@ struct Layout {
     w_surv = w.add(sizeof(int32_t) * per);
     w_samples = w.add(samples ? sizeof(int32_t) * RS_MAX_N * per : 0);
     w_slot = w.bytes;
-    RsPack c;
+    Pack c;
     c_n = c.add(sizeof(int32_t) * batch * slots);
     c_best = c.add(sizeof(RsBest) * batch * (slots + 1));
     c_nsurv = c.add(sizeof(int32_t) * batch * slots);
@@ -230,21 +201,21 @@ struct Layout {
     return TEASER_HIP_OK;
   }
   RsSlot slot(teaser_hip_ransac* h, int g) const {
-    char* w = h->work.as<char>() + w_slot * g;
-    char* c = h->ctl.as<char>();
+    void* w = h->work.as<char>() + w_slot * g;
+    void* c = h->ctl.p;
     RsSlot s;
-    s.T = reinterpret_cast<double*>(w + w_T);
-    s.flags = reinterpret_cast<uint8_t*>(w + w_flags);
-    s.count = reinterpret_cast<int32_t*>(w + w_count);
-    s.sum = reinterpret_cast<double*>(w + w_sum);
-    s.surv = reinterpret_cast<int32_t*>(w + w_surv);
-    s.samples = samples ? reinterpret_cast<int32_t*>(w + w_samples) : nullptr;
-    s.n = reinterpret_cast<const int32_t*>(c + c_n) + (size_t)batch * g;
-    s.best_in = reinterpret_cast<const RsBest*>(c + c_best) + (size_t)batch * g;
-    s.best_out = reinterpret_cast<RsBest*>(c + c_best) + (size_t)batch * (g + 1);
-    s.nsurv = reinterpret_cast<int32_t*>(c + c_nsurv) + (size_t)batch * g;
-    s.n_imp = reinterpret_cast<int32_t*>(c + c_nimp) + (size_t)batch * g;
-    s.entries = reinterpret_cast<RsEntry*>(c + c_entries) + (size_t)batch * g * RS_LIST_CAP;
+    s.T = Pack::at<double>(w, w_T);
+    s.flags = Pack::at<uint8_t>(w, w_flags);
+    s.count = Pack::at<int32_t>(w, w_count);
+    s.sum = Pack::at<double>(w, w_sum);
+    s.surv = Pack::at<int32_t>(w, w_surv);
+    s.samples = samples ? Pack::at<int32_t>(w, w_samples) : nullptr;
+    s.n = Pack::at<const int32_t>(c, c_n) + (size_t)batch * g;
+    s.best_in = Pack::at<const RsBest>(c, c_best) + (size_t)batch * g;
+    s.best_out = Pack::at<RsBest>(c, c_best) + (size_t)batch * (g + 1);
+    s.nsurv = Pack::at<int32_t>(c, c_nsurv) + (size_t)batch * g;
+    s.n_imp = Pack::at<int32_t>(c, c_nimp) + (size_t)batch * g;
+    s.entries = Pack::at<RsEntry>(c, c_entries) + (size_t)batch * g * RS_LIST_CAP;
     return s;
   }
 };
@@ -258,11 +229,8 @@ void default_result(teaser_ransac_result_c* r) {
 int32_t run_full(teaser_hip_ransac* h, int32_t batch, const double* const* src, const int32_t* n_src,
                  const double* const* dst, const int32_t* n_dst, const int32_t* const* corr, const int32_t* n_corr,
                  const teaser_ransac_params_c* params, teaser_ransac_result_c* out, int32_t* const* inliers) {
-  if (!h) return TEASER_HIP_ERR_BAD_ARG;
-  h->err.clear();
-  if (batch < 0) return fail(h, TEASER_HIP_ERR_BAD_ARG, "batch must be >= 0");
-  if (batch > 65535)  // problems are indexed by blockIdx.y or blockIdx.z
-    return fail(h, TEASER_HIP_ERR_UNSUPPORTED, "a batch holds at most 65535 problems; split larger batches across calls");
+  const int32_t r0 = begin_call(h, batch);
+  if (r0 != TEASER_HIP_OK) return r0;
   if (batch == 0) return TEASER_HIP_OK;
   if (!out) return fail(h, TEASER_HIP_ERR_BAD_ARG, "out must not be NULL");
   Prep p;
@@ -287,8 +255,8 @@ int32_t run_full(teaser_hip_ransac* h, int32_t batch, const double* const* src, 
   for (int64_t first0 = 0; any; first0 += (int64_t)G * chunk) {
     // ---- plan the group ----
     memset(up.data(), 0, up_bytes);
-    int32_t* plan = reinterpret_cast<int32_t*>(up.data() + L.c_n);
-    RsBest* carry = reinterpret_cast<RsBest*>(up.data() + L.c_best);
+    int32_t* plan = Pack::at<int32_t>(up.data(), L.c_n);
+    RsBest* carry = Pack::at<RsBest>(up.data(), L.c_best);
     int used = 0;
     std::vector<int> max_n((size_t)G, 0);
     for (int g = 0; g < G; ++g) {
@@ -313,9 +281,9 @@ int32_t run_full(teaser_hip_ransac* h, int32_t batch, const double* const* src, 
     FCHK(h, hipMemcpyAsync(down.data(), ctl + L.c_nsurv, down.size(), hipMemcpyDeviceToHost, s),
          "hipMemcpyAsync (RANSAC lists)");
     FCHK(h, hipStreamSynchronize(s), "RANSAC trials");
-    const int32_t* nsurv = reinterpret_cast<const int32_t*>(down.data());
-    const int32_t* nimp = reinterpret_cast<const int32_t*>(down.data() + (L.c_nimp - L.c_nsurv));
-    const RsEntry* entries = reinterpret_cast<const RsEntry*>(down.data() + (L.c_entries - L.c_nsurv));
+    const int32_t* nsurv = Pack::at<const int32_t>(down.data(), 0);
+    const int32_t* nimp = Pack::at<const int32_t>(down.data(), L.c_nimp - L.c_nsurv);
+    const RsEntry* entries = Pack::at<const RsEntry>(down.data(), L.c_entries - L.c_nsurv);
     // ---- walk the lists ----
     any = false;
     for (int b = 0; b < batch; ++b) {
@@ -394,11 +362,8 @@ int32_t run_trials(teaser_hip_ransac* h, int32_t batch, const double* const* src
                    const double* const* dst, const int32_t* n_dst, const int32_t* const* corr, const int32_t* n_corr,
                    const teaser_ransac_params_c* params, int64_t first, int32_t n, int32_t* samples, uint8_t* flags,
                    double* T, int32_t* count, double* sum) {
-  if (!h) return TEASER_HIP_ERR_BAD_ARG;
-  h->err.clear();
-  if (batch < 0) return fail(h, TEASER_HIP_ERR_BAD_ARG, "batch must be >= 0");
-  if (batch > 65535)  // problems are indexed by blockIdx.y or blockIdx.z
-    return fail(h, TEASER_HIP_ERR_UNSUPPORTED, "a batch holds at most 65535 problems; split larger batches across calls");
+  const int32_t r0 = begin_call(h, batch);
+  if (r0 != TEASER_HIP_OK) return r0;
   if (first < 0) return fail(h, TEASER_HIP_ERR_BAD_ARG, "first must be >= 0");
   if (n < 0 || n > 65536) return fail(h, TEASER_HIP_ERR_BAD_ARG, "n must be in 0 .. 65536");
   if (batch == 0) return TEASER_HIP_OK;
@@ -466,18 +431,10 @@ int32_t teaser_hip_ransac_correspondence(teaser_hip_ransac* h, const double* src
 }
 
 int32_t teaser_hip_ransac_set_option(teaser_hip_ransac* h, const char* name, int64_t value) {
-  if (!h) return TEASER_HIP_ERR_BAD_ARG;
-  if (!name || strcmp(name, "chunk_trials") != 0)
-    return fail(h, TEASER_HIP_ERR_BAD_ARG, std::string("unknown option ") + (name ? name : "(NULL)"));
-  if (value < 64 || value > 65536) return fail(h, TEASER_HIP_ERR_BAD_ARG, "chunk_trials must be in 64 .. 65536");
-  h->chunk_trials = value;
-  return TEASER_HIP_OK;
+  return set_knob(h, kKnobs, name, value);
 }
-
 int32_t teaser_hip_ransac_get_option(const teaser_hip_ransac* h, const char* name, int64_t* value) {
-  if (!h || !value || !name || strcmp(name, "chunk_trials") != 0) return TEASER_HIP_ERR_BAD_ARG;
-  *value = h->chunk_trials;
-  return TEASER_HIP_OK;
+  return get_knob(h, kKnobs, name, value);
 }
 
 int32_t teaser_hip_ransac_trials_batch(teaser_hip_ransac* h, int32_t batch, const double* const* src,

@@ -1518,10 +1518,7 @@ void destroy_handle(teaser_hip_solver* h);
 int32_t solve_packed(teaser_hip_solver* h, const double* d_src, const double* d_dst,
                      const int64_t* pt_off, const int32_t* n, int batch, teaser_solution_c* out) {
   h->route.clear();
-  if (batch > 65535) {  // problems are indexed by blockIdx.y
-    h->err = "a batch holds at most 65535 problems; split larger batches across calls";
-    return TEASER_HIP_ERR_UNSUPPORTED;
-  }
+  if (batch > kMaxBatch) return over_batch_limit(h);  // problems are indexed by blockIdx.y
   bool overflow = false;
   int32_t rc = solve_packed_impl(h, d_src, d_dst, pt_off, n, batch, out, false, &overflow);
   if (rc == TEASER_HIP_OK && overflow)
@@ -2515,10 +2512,7 @@ int32_t teaser_hip_submit_batch(teaser_hip_solver* h, const double* src, const d
                                 const int64_t* point_offset, const int32_t* n, int32_t batch,
                                 int32_t flags, int32_t* ticket) {
   if (!h || !ticket || batch <= 0 || !src || !dst || !point_offset || !n) return TEASER_HIP_ERR_BAD_ARG;
-  if (batch > 65535) {
-    h->err = "a batch holds at most 65535 problems; split larger batches across calls";
-    return TEASER_HIP_ERR_UNSUPPORTED;
-  }
+  if (batch > kMaxBatch) return over_batch_limit(h);
   (void)hipSetDevice(h->device);
   g_trace.mark(h, "submit: begin");
   const int32_t rc = submit_impl(h, src, dst, point_offset, n, batch, flags, ticket);

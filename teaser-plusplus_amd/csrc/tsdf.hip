@@ -29,11 +29,6 @@ struct teaser_hip_tsdf : HandleBase {
   HostBuf stage, back;
   ~teaser_hip_tsdf() {
     if (volume) (void)hipFree(volume);
-    in.release();
-    work.release();
-    out.release();
-    stage.release();
-    back.release();
   }
 };
 

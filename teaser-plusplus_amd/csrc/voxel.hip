@@ -29,9 +29,6 @@ enum { B_DESC, B_BLK, B_PTS, B_KEY_LO, B_KEY_HI, B_IOTA, B_SORTED, B_GATHERED, B
 
 struct teaser_hip_voxel : HandleBase {
   DevBuf buf[B_COUNT_OF_BUFS];
-  ~teaser_hip_voxel() {
-    for (DevBuf& b : buf) b.release();
-  }
 };
 
 namespace {

@@ -7,9 +7,8 @@ import ctypes as C
 
 import numpy as np
 
-from ._handles import HandleCache, _cloud
+from ._handles import HandleCache, _cloud, _get_option, _pairs, _per_problem, _rows, _set_option
 from .icp import evaluate_registration_batch
-from .ransac import _pairs, _per_problem
 
 _vp, _ip, _dp = C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_double)
 _i64p = C.POINTER(C.c_int64)
@@ -105,13 +104,7 @@ def _gather(sources, targets, corres, option):
 
 
 def _args(src, dst, cor, params):
-    b = len(src)
-    sp = (_dp * max(b, 1))(*[a.ctypes.data_as(_dp) for a in src])
-    dp = (_dp * max(b, 1))(*[a.ctypes.data_as(_dp) for a in dst])
-    cp = (_ip * max(b, 1))(*[a.ctypes.data_as(_ip) for a in cor])
-    n_s = np.array([len(a) for a in src], dtype=np.int32)
-    n_d = np.array([len(a) for a in dst], dtype=np.int32)
-    n_c = np.array([len(a) for a in cor], dtype=np.int32)
+    (sp, n_s), (dp, n_d), (cp, n_c) = _rows(src, _dp), _rows(dst, _dp), _rows(cor, _ip)
     return (sp, n_s.ctypes.data_as(_ip), dp, n_d.ctypes.data_as(_ip), cp, n_c.ctypes.data_as(_ip), params), (n_s, n_d, n_c)
 
 
@@ -211,12 +204,8 @@ def fgr_iterations_batch(sources, targets, corres, n, option=None, device=-1):
 def set_fgr_option(name, value, device=-1):
     """teaser_hip_fgr_set_option on the cached handle of `device` ("resident_max_corr" in 0 .. 3072: a tuning knob, no
     result bit depends on it)."""
-    h = _cache.get(device)
-    h.call(h._lib.teaser_hip_fgr_set_option, name.encode(), int(value))
+    _set_option(_cache, name, value, device)
 
 
 def get_fgr_option(name, device=-1):
-    h = _cache.get(device)
-    v = C.c_int64()
-    h.call(h._lib.teaser_hip_fgr_get_option, name.encode(), C.byref(v))
-    return v.value
+    return _get_option(_cache, name, device)

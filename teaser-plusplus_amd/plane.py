@@ -7,7 +7,7 @@ import math
 
 import numpy as np
 
-from ._handles import HandleCache, _cloud
+from ._handles import HandleCache, _cloud, _get_option, _per_problem, _rows, _set_option
 
 _vp, _ip, _dp, _u8p = C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_double), C.POINTER(C.c_uint8)
 _i64p = C.POINTER(C.c_int64)
@@ -84,14 +84,6 @@ def _params(distance_threshold, ransac_n, num_iterations, probability, seed, k=N
     return q
 
 
-def _per_problem(value, b, what):
-    if isinstance(value, (list, tuple, np.ndarray)):
-        if len(value) != b:
-            raise ValueError("%s: %d values for %d problems" % (what, len(value), b))
-        return list(value)
-    return [value] * b
-
-
 def _gather(clouds, distance_threshold, ransac_n, num_iterations, probability, seed):
     b = len(clouds)
     pts = [_cloud(a, "points %d" % k) for k, a in enumerate(clouds)]
@@ -104,8 +96,7 @@ def _gather(clouds, distance_threshold, ransac_n, num_iterations, probability, s
     params = (PlaneParamsC * max(b, 1))()
     for k in range(b):
         params[k] = _params(ds[k], ns[k], its[k], prs[k], seeds[k], k)
-    pp = (_dp * max(b, 1))(*[a.ctypes.data_as(_dp) for a in pts])
-    n = np.array([len(a) for a in pts], dtype=np.int32)
+    pp, n = _rows(pts, _dp)
     return b, (pp, n.ctypes.data_as(_ip), params), (pts, n)
 
 
@@ -161,12 +152,8 @@ def plane_trials_batch(clouds, distance_threshold, first, n, ransac_n=3, seed=0,
 def set_plane_option(name, value, device=-1):
     """teaser_hip_plane_set_option on the cached handle of `device` ("chunk_trials", "partial_bytes": tuning knobs, no
     result bit depends on them)."""
-    h = _cache.get(device)
-    h.call(h._lib.teaser_hip_plane_set_option, name.encode(), int(value))
+    _set_option(_cache, name, value, device)
 
 
 def get_plane_option(name, device=-1):
-    h = _cache.get(device)
-    v = C.c_int64()
-    h.call(h._lib.teaser_hip_plane_get_option, name.encode(), C.byref(v))
-    return v.value
+    return _get_option(_cache, name, device)

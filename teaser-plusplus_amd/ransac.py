@@ -8,7 +8,7 @@ import ctypes as C
 
 import numpy as np
 
-from ._handles import HandleCache, _cloud
+from ._handles import HandleCache, _cloud, _get_option, _pairs, _per_problem, _rows, _set_option
 from .icp import RegistrationResult, TransformationEstimationPointToPoint
 
 _vp, _ip, _dp, _u8p = C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_double), C.POINTER(C.c_uint8)
@@ -121,23 +121,6 @@ def _params(max_correspondence_distance, estimation_method, ransac_n, checkers, 
     return p
 
 
-def _pairs(corres, what):
-    a = np.ascontiguousarray(np.asarray(corres, dtype=np.int32))
-    if a.size == 0:
-        return np.zeros((0, 2), dtype=np.int32)
-    if a.ndim != 2 or a.shape[1] != 2:
-        raise ValueError("%s must be an n x 2 integer array, got shape %s" % (what, a.shape))
-    return a
-
-
-def _per_problem(value, b, what):
-    if isinstance(value, (list, tuple)):
-        if len(value) != b:
-            raise ValueError("%s: %d values for %d problems" % (what, len(value), b))
-        return list(value)
-    return [value] * b
-
-
 def _gather(sources, targets, corres, max_correspondence_distance, estimation_method, ransac_n, checkers, criteria,
             seed):
     b = len(sources)
@@ -158,12 +141,7 @@ def _gather(sources, targets, corres, max_correspondence_distance, estimation_me
     params = (RansacParamsC * max(b, 1))()
     for k in range(b):
         params[k] = _params(rs[k], estimation_method, ns[k], chk[k], crit[k], seeds[k])
-    sp = (_dp * max(b, 1))(*[a.ctypes.data_as(_dp) for a in src])
-    dp = (_dp * max(b, 1))(*[a.ctypes.data_as(_dp) for a in dst])
-    cp = (_ip * max(b, 1))(*[a.ctypes.data_as(_ip) for a in cor])
-    n_s = np.array([len(a) for a in src], dtype=np.int32)
-    n_d = np.array([len(a) for a in dst], dtype=np.int32)
-    n_c = np.array([len(a) for a in cor], dtype=np.int32)
+    (sp, n_s), (dp, n_d), (cp, n_c) = _rows(src, _dp), _rows(dst, _dp), _rows(cor, _ip)
     keep = (src, dst, cor, n_s, n_d, n_c)
     return b, (sp, n_s.ctypes.data_as(_ip), dp, n_d.ctypes.data_as(_ip), cp, n_c.ctypes.data_as(_ip), params), keep
 
@@ -261,12 +239,8 @@ def ransac_trials_batch(sources, targets, corres, max_correspondence_distance, f
 def set_ransac_option(name, value, device=-1):
     """teaser_hip_ransac_set_option on the cached handle of `device` ("chunk_trials": a tuning knob, no result bit
     depends on it)."""
-    h = _cache.get(device)
-    h.call(h._lib.teaser_hip_ransac_set_option, name.encode(), int(value))
+    _set_option(_cache, name, value, device)
 
 
 def get_ransac_option(name, device=-1):
-    h = _cache.get(device)
-    v = C.c_int64()
-    h.call(h._lib.teaser_hip_ransac_get_option, name.encode(), C.byref(v))
-    return v.value
+    return _get_option(_cache, name, device)

@@ -468,6 +468,10 @@ int main() {
     { std::vector<Problem> q = ps; q[4].Q[0] = inf; Batch b(q); expect_refusal(h, call(b), "dst has non-finite", 4); }
     { std::vector<Problem> q = ps; q[2].corr[8] = 700; Batch b(q); expect_refusal(h, call(b), "source index of pair 4", 2); }
     { std::vector<Problem> q = ps; q[3].corr[7] = -1; Batch b(q); expect_refusal(h, call(b), "target index of pair 3", 3); }
+    { std::vector<Problem> q = ps; q[1].corr[8] = 300; Batch b(q); expect_refusal(h, call(b), "source index of pair 4", 1); }
+    EXPECT(std::string(teaser_hip_fgr_last_error(h)) == "corr: source index of pair 4 is outside the cloud (problem 1)");
+    { std::vector<Problem> q = ps; q[1].corr[7] = -1; Batch b(q); expect_refusal(h, call(b), "target index of pair 3", 1); }
+    EXPECT(std::string(teaser_hip_fgr_last_error(h)) == "corr: target index of pair 3 is outside the cloud (problem 1)");
     {
       Batch b(ps);
       expect_refusal(h, teaser_hip_fgr_correspondence_batch(h, B, b.src.data(), nullptr, b.dst.data(), b.nt.data(), b.corr.data(),
@@ -502,6 +506,16 @@ int main() {
                                              prm.data(), 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
                                              nullptr, nullptr) == TEASER_HIP_ERR_UNSUPPORTED);
       EXPECT(std::string(teaser_hip_fgr_last_error(h)) == limit);
+      // the stage call's n < 0 is refused before the batch is looked at: above the limit, empty or negative
+      for (int32_t batch : {big, (int32_t)0, (int32_t)-1}) {
+        EXPECT(teaser_hip_fgr_iterations_batch(h, batch, one.data(), n1.data(), one.data(), n1.data(), nc.data(), zero.data(),
+                                               prm.data(), -1, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
+                                               nullptr, nullptr) == TEASER_HIP_ERR_BAD_ARG);
+        EXPECT(std::string(teaser_hip_fgr_last_error(h)) == "n must be in 0 .. iteration_number");
+      }
+      EXPECT(teaser_hip_fgr_iterations_batch(h, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr,
+                                             nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr) == TEASER_HIP_OK);
+      EXPECT(std::string(teaser_hip_fgr_last_error(h)).empty());
     }
     EXPECT(g_normalise == norm0);  // nothing was launched by a refused call
     // ... and 65 535 one-point problems without correspondences pass it: every one comes back not optimised; the handle
@@ -523,7 +537,20 @@ int main() {
     expect_refusal(h, teaser_hip_fgr_set_option(h, "resident_max_corr", 3073), "resident_max_corr must be in 0 .. 3072", -1);
     expect_refusal(h, teaser_hip_fgr_set_option(h, "resident_max_corr", -1), "resident_max_corr must be in 0 .. 3072", -1);
     expect_refusal(h, teaser_hip_fgr_set_option(h, "chunk_trials", 64), "unknown option chunk_trials", -1);
-    EXPECT(teaser_hip_fgr_get_option(h, "nothing", &v) == TEASER_HIP_ERR_BAD_ARG);
+    auto said = [&](const char* text) { return std::string(teaser_hip_fgr_last_error(h)) == text; };
+    EXPECT(teaser_hip_fgr_set_option(h, "resident_max_corr", 3073) == TEASER_HIP_ERR_BAD_ARG);
+    EXPECT(said("resident_max_corr must be in 0 .. 3072"));
+    EXPECT(teaser_hip_fgr_set_option(h, "no_such", 64) == TEASER_HIP_ERR_BAD_ARG && said("unknown option no_such"));
+    EXPECT(teaser_hip_fgr_set_option(h, nullptr, 64) == TEASER_HIP_ERR_BAD_ARG && said("unknown option (NULL)"));
+    EXPECT(teaser_hip_fgr_set_option(nullptr, "resident_max_corr", 64) == TEASER_HIP_ERR_BAD_ARG);
+    // a failing get_option answers BAD_ARG, writes no value and leaves the handle's message as it was
+    v = -5;
+    EXPECT(teaser_hip_fgr_get_option(h, "nothing", &v) == TEASER_HIP_ERR_BAD_ARG && v == -5);
+    EXPECT(teaser_hip_fgr_get_option(h, nullptr, &v) == TEASER_HIP_ERR_BAD_ARG && v == -5);
+    EXPECT(teaser_hip_fgr_get_option(h, "resident_max_corr", nullptr) == TEASER_HIP_ERR_BAD_ARG);
+    EXPECT(teaser_hip_fgr_get_option(nullptr, "resident_max_corr", &v) == TEASER_HIP_ERR_BAD_ARG && v == -5);
+    EXPECT(said("unknown option (NULL)"));
+    EXPECT(teaser_hip_fgr_get_option(h, "resident_max_corr", &v) == TEASER_HIP_OK && v == 3072);
     EXPECT(teaser_hip_fgr_params_default(nullptr) == TEASER_HIP_ERR_BAD_ARG);
     EXPECT(g_normalise == norm1);  // nothing was launched by a refused call
     EXPECT(std::string(teaser_hip_fgr_last_error(nullptr)).empty());

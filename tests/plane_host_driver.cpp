@@ -298,11 +298,24 @@ int main() {
   int64_t v = 0;
   EXPECT(teaser_hip_plane_get_option(h, "chunk_trials", &v) == TEASER_HIP_OK && v == 256);
   EXPECT(teaser_hip_plane_get_option(h, "partial_bytes", &v) == TEASER_HIP_OK && v == (64ll << 20));
+  auto said = [&](const char* text) { return std::string(teaser_hip_plane_last_error(h)) == text; };
   EXPECT(teaser_hip_plane_set_option(h, "chunk_trials", 63) == TEASER_HIP_ERR_BAD_ARG);
-  EXPECT(teaser_hip_plane_set_option(h, "chunk_trials", 4097) == TEASER_HIP_ERR_BAD_ARG);
+  EXPECT(said("chunk_trials must be in 64 .. 4096"));
   EXPECT(teaser_hip_plane_set_option(h, "partial_bytes", 65535) == TEASER_HIP_ERR_BAD_ARG);
-  EXPECT(teaser_hip_plane_set_option(h, "no_such", 64) == TEASER_HIP_ERR_BAD_ARG);
+  EXPECT(said("partial_bytes must be in 65536 .. 17179869184"));
+  EXPECT(teaser_hip_plane_set_option(h, "chunk_trials", 4097) == TEASER_HIP_ERR_BAD_ARG);
+  EXPECT(said("chunk_trials must be in 64 .. 4096"));
+  EXPECT(teaser_hip_plane_set_option(h, "partial_bytes", (1ll << 34) + 1) == TEASER_HIP_ERR_BAD_ARG);
+  EXPECT(said("partial_bytes must be in 65536 .. 17179869184"));
+  EXPECT(teaser_hip_plane_set_option(h, "no_such", 64) == TEASER_HIP_ERR_BAD_ARG && said("unknown option no_such"));
+  EXPECT(teaser_hip_plane_set_option(nullptr, "chunk_trials", 64) == TEASER_HIP_ERR_BAD_ARG);
+  EXPECT(teaser_hip_plane_set_option(h, nullptr, 64) == TEASER_HIP_ERR_BAD_ARG && said("unknown option (NULL)"));
+  // a failing get_option answers BAD_ARG, writes no value and leaves the handle's message as it was
   EXPECT(teaser_hip_plane_get_option(h, "no_such", &v) == TEASER_HIP_ERR_BAD_ARG && v == (64ll << 20));
+  EXPECT(teaser_hip_plane_get_option(h, nullptr, &v) == TEASER_HIP_ERR_BAD_ARG && v == (64ll << 20));
+  EXPECT(teaser_hip_plane_get_option(h, "partial_bytes", nullptr) == TEASER_HIP_ERR_BAD_ARG);
+  EXPECT(teaser_hip_plane_get_option(nullptr, "partial_bytes", &v) == TEASER_HIP_ERR_BAD_ARG && v == (64ll << 20));
+  EXPECT(said("unknown option (NULL)"));
   teaser_plane_params_c dflt;
   EXPECT(teaser_hip_plane_params_default(&dflt) == TEASER_HIP_OK && dflt.ransac_n == 3 && dflt.num_iterations == 100 &&
          dflt.probability == 0.99999999 && dflt.distance_threshold == 0 && dflt.seed == 0);
@@ -484,6 +497,22 @@ int main() {
       EXPECT(teaser_hip_plane_trials_batch(h, big, np.data(), zero.data(), prm.data(), 0, 0, nullptr, nullptr, nullptr, nullptr,
                                            nullptr) == TEASER_HIP_ERR_UNSUPPORTED);
       EXPECT(std::string(teaser_hip_plane_last_error(h)) == limit);
+      // the order of the stage call's refusals: the batch limit, then its own arguments, then the empty batch
+      EXPECT(teaser_hip_plane_trials_batch(h, big, np.data(), zero.data(), prm.data(), -1, 0, nullptr, nullptr, nullptr, nullptr,
+                                           nullptr) == TEASER_HIP_ERR_UNSUPPORTED);
+      EXPECT(std::string(teaser_hip_plane_last_error(h)) == limit);
+      EXPECT(teaser_hip_plane_trials_batch(h, 0, nullptr, nullptr, nullptr, 0, 65537, nullptr, nullptr, nullptr, nullptr,
+                                           nullptr) == TEASER_HIP_ERR_BAD_ARG);
+      EXPECT(std::string(teaser_hip_plane_last_error(h)) == "cnt must be in 0 .. 65536");
+      EXPECT(teaser_hip_plane_trials_batch(h, 0, nullptr, nullptr, nullptr, -1, 0, nullptr, nullptr, nullptr, nullptr,
+                                           nullptr) == TEASER_HIP_ERR_BAD_ARG);
+      EXPECT(std::string(teaser_hip_plane_last_error(h)) == "first must be >= 0");
+      EXPECT(teaser_hip_plane_trials_batch(h, -1, nullptr, nullptr, nullptr, -1, 0, nullptr, nullptr, nullptr, nullptr,
+                                           nullptr) == TEASER_HIP_ERR_BAD_ARG);
+      EXPECT(std::string(teaser_hip_plane_last_error(h)) == "batch must be >= 0");
+      EXPECT(teaser_hip_plane_trials_batch(h, 0, nullptr, nullptr, nullptr, 0, 0, nullptr, nullptr, nullptr, nullptr,
+                                           nullptr) == TEASER_HIP_OK);
+      EXPECT(std::string(teaser_hip_plane_last_error(h)).empty());
       // 65 535: the stage call with no trial goes through the checks and the upload; the full call is past the limit
       // check when it names the next argument it misses
       EXPECT(teaser_hip_plane_trials_batch(h, big - 1, np.data(), zero.data(), prm.data(), 0, 0, nullptr, nullptr, nullptr,

@@ -281,10 +281,20 @@ int main() {
   EXPECT(teaser_hip_ransac_create(-1, &h) == TEASER_HIP_OK && h);
   int64_t v = 0;
   EXPECT(teaser_hip_ransac_get_option(h, "chunk_trials", &v) == TEASER_HIP_OK && v == 4096);
+  auto said = [&](const char* text) { return std::string(teaser_hip_ransac_last_error(h)) == text; };
   EXPECT(teaser_hip_ransac_set_option(h, "chunk_trials", 63) == TEASER_HIP_ERR_BAD_ARG);
+  EXPECT(said("chunk_trials must be in 64 .. 65536"));
+  EXPECT(teaser_hip_ransac_set_option(h, "no_such", 64) == TEASER_HIP_ERR_BAD_ARG && said("unknown option no_such"));
+  EXPECT(teaser_hip_ransac_set_option(h, nullptr, 64) == TEASER_HIP_ERR_BAD_ARG && said("unknown option (NULL)"));
   EXPECT(teaser_hip_ransac_set_option(h, "chunk_trials", 65537) == TEASER_HIP_ERR_BAD_ARG);
-  EXPECT(teaser_hip_ransac_set_option(h, "no_such", 64) == TEASER_HIP_ERR_BAD_ARG);
+  EXPECT(said("chunk_trials must be in 64 .. 65536"));
+  EXPECT(teaser_hip_ransac_set_option(nullptr, "chunk_trials", 64) == TEASER_HIP_ERR_BAD_ARG);
+  // a failing get_option answers BAD_ARG, writes no value and leaves the handle's message as it was
   EXPECT(teaser_hip_ransac_get_option(h, "no_such", &v) == TEASER_HIP_ERR_BAD_ARG && v == 4096);
+  EXPECT(teaser_hip_ransac_get_option(h, nullptr, &v) == TEASER_HIP_ERR_BAD_ARG && v == 4096);
+  EXPECT(teaser_hip_ransac_get_option(h, "chunk_trials", nullptr) == TEASER_HIP_ERR_BAD_ARG);
+  EXPECT(teaser_hip_ransac_get_option(nullptr, "chunk_trials", &v) == TEASER_HIP_ERR_BAD_ARG && v == 4096);
+  EXPECT(said("chunk_trials must be in 64 .. 65536"));
   teaser_ransac_params_c dflt;
   EXPECT(teaser_hip_ransac_params_default(&dflt) == TEASER_HIP_OK && dflt.ransac_n == 3 && dflt.max_iteration == 100000 &&
          dflt.confidence == 0.999 && dflt.edge_length_threshold == 0 && dflt.distance_threshold == 0 && dflt.seed == 0);
@@ -452,7 +462,9 @@ int main() {
     refusal(h, with([&](Problem& p) { p.prm.normal_checker = 1; }), "normal-angle checker");
     refusal(h, with([&](Problem& p) { p.corr[4] = -1; }), "corr: source index of pair 2");
     refusal(h, with([&](Problem& p) { p.corr[4] = (int32_t)p.P.size() / 3; }), "corr: source index of pair 2");
+    EXPECT(std::string(teaser_hip_ransac_last_error(h)) == "corr: source index of pair 2 is outside the cloud (problem 1)");
     refusal(h, with([&](Problem& p) { p.corr[7] = (int32_t)p.Q.size() / 3; }), "corr: target index of pair 3");
+    EXPECT(std::string(teaser_hip_ransac_last_error(h)) == "corr: target index of pair 3 is outside the cloud (problem 1)");
     refusal(h, with([&](Problem& p) { p.P[5] = nan; }), "src has non-finite points");
     refusal(h, with([&](Problem& p) { p.Q[5] = inf; }), "dst has non-finite points");
     refusal(h, ok, "src is NULL", true);
@@ -494,6 +506,22 @@ int main() {
       EXPECT(teaser_hip_ransac_trials_batch(h, big, np.data(), zero.data(), np.data(), zero.data(), nc.data(), zero.data(),
                                             prm.data(), 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr) == TEASER_HIP_ERR_UNSUPPORTED);
       EXPECT(std::string(teaser_hip_ransac_last_error(h)) == limit);
+      // the order of the stage call's refusals: the batch limit, then its own arguments, then the empty batch
+      EXPECT(teaser_hip_ransac_trials_batch(h, big, np.data(), zero.data(), np.data(), zero.data(), nc.data(), zero.data(),
+                                            prm.data(), -1, 0, nullptr, nullptr, nullptr, nullptr, nullptr) == TEASER_HIP_ERR_UNSUPPORTED);
+      EXPECT(std::string(teaser_hip_ransac_last_error(h)) == limit);
+      EXPECT(teaser_hip_ransac_trials_batch(h, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, -1, 0,
+                                            nullptr, nullptr, nullptr, nullptr, nullptr) == TEASER_HIP_ERR_BAD_ARG);
+      EXPECT(std::string(teaser_hip_ransac_last_error(h)) == "first must be >= 0");
+      EXPECT(teaser_hip_ransac_trials_batch(h, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, 65537,
+                                            nullptr, nullptr, nullptr, nullptr, nullptr) == TEASER_HIP_ERR_BAD_ARG);
+      EXPECT(std::string(teaser_hip_ransac_last_error(h)) == "n must be in 0 .. 65536");
+      EXPECT(teaser_hip_ransac_trials_batch(h, -1, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, -1, 0,
+                                            nullptr, nullptr, nullptr, nullptr, nullptr) == TEASER_HIP_ERR_BAD_ARG);
+      EXPECT(std::string(teaser_hip_ransac_last_error(h)) == "batch must be >= 0");
+      EXPECT(teaser_hip_ransac_trials_batch(h, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0,
+                                            nullptr, nullptr, nullptr, nullptr, nullptr) == TEASER_HIP_OK);
+      EXPECT(std::string(teaser_hip_ransac_last_error(h)).empty());
       EXPECT(g_packs == packs && g_chunks == chunks);
       // 65 535: the stage call with no trial goes through the checks, the upload and the pack launch; the full call is
       // past the limit check when it names the next argument it misses

@@ -59,7 +59,14 @@ def test_python_argument_errors_need_no_device():
         call(np.zeros((4, 2)), P, corr)
     with pytest.raises(ValueError, match="2 values for 1 problems"):
         tp.registration_fgr_based_on_correspondence_batch([P], [P], [corr], [tp.FastGlobalRegistrationOption()] * 2)
+    with pytest.raises(ValueError, match="option: 2 values for 1 problems"):  # an array holds one per problem too
+        tp.registration_fgr_based_on_correspondence_batch([P], [P], [corr],
+                                                          np.array([tp.FastGlobalRegistrationOption()] * 2, dtype=object))
     with pytest.raises(ValueError, match="differ in length"):
         tp.registration_fgr_based_on_correspondence_batch([P], [P, P], [corr])
+    H = importlib.import_module("teaser-plusplus_amd._handles")  # one copy of the argument helpers
+    assert tp.fgr._pairs is H._pairs and tp.ransac._pairs is H._pairs
+    assert tp.fgr._per_problem is H._per_problem and tp.ransac._per_problem is H._per_problem
+    assert tp.plane._per_problem is H._per_problem
     assert tp.registration_fgr_based_on_correspondence_batch([], [], []) == []  # no problems: no device needed
     assert tp.fgr_iterations_batch([], [], [], 3) == []

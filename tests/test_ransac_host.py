@@ -71,4 +71,6 @@ def test_python_argument_errors_name_what_is_not_offered():
         call(P, P, np.zeros((4, 3), dtype=np.int32), 0.1)
     with pytest.raises(ValueError, match="2 values for 1 problems"):
         tp.registration_ransac_based_on_correspondence_batch([P], [P], [corr], [0.1, 0.2])
+    with pytest.raises(ValueError, match="seed: 2 values for 1 problems"):  # an array holds one value per problem too
+        tp.registration_ransac_based_on_correspondence_batch([P], [P], [corr], 0.1, seed=np.array([1, 2]))
     assert tp.registration_ransac_based_on_correspondence_batch([], [], [], 0.1) == []  # no problems: no device needed
