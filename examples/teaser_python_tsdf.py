@@ -9,9 +9,10 @@ poses (the poses a multiway registration such as examples/teaser_python_multiway
  -> the surface extracted               (extract_point_cloud: points and normals come back)
 
 It prints the number of extracted points and the largest distance from an extracted point to the analytic surface (the
-nearer of the wall and the balls' spheres).  Usage:
+nearer of the wall and the balls' spheres).  With --mesh PATH the triangle mesh is extracted too (extract_triangle_mesh:
+marching cubes on the device) and written to PATH as a PLY file.  Usage:
 
-    python examples/teaser_python_tsdf.py [--width 320 --height 240] [--resolution 128] [--frames 8]
+    python examples/teaser_python_tsdf.py [--width 320 --height 240] [--resolution 128] [--frames 8] [--mesh PATH]
 """
 import argparse
 import importlib
@@ -68,6 +69,7 @@ def main():
     ap.add_argument("--height", type=int, default=240)
     ap.add_argument("--resolution", type=int, default=128)
     ap.add_argument("--frames", type=int, default=8)
+    ap.add_argument("--mesh", default=None, help="also extract the triangle mesh and write it to this PLY file")
     a = ap.parse_args()
     K, depths, extrinsics = scene_frames(a.width, a.height, a.frames)
     length, R, trunc, origin = volume_settings(a.resolution)
@@ -83,6 +85,14 @@ def main():
     print("extraction: %d points with normals, %.1f ms" % (len(cloud.points), 1e3 * (t3 - t2)))
     d = distance_to_surface(cloud.points)
     print("distance to the analytic surface: max %.17g, mean %.6f (voxel %.6f)" % (d.max(), d.mean(), vol.voxel_length))
+    if a.mesh:
+        t4 = time.perf_counter()
+        mesh = vol.extract_triangle_mesh()
+        t5 = time.perf_counter()
+        tp.write_triangle_mesh(a.mesh, mesh)
+        dm = distance_to_surface(mesh.vertices)
+        print("mesh: %d vertices, %d triangles, %.1f ms; distance to the analytic surface: max %.6f; written to %s"
+              % (len(mesh.vertices), len(mesh.triangles), 1e3 * (t5 - t4), dm.max() if len(dm) else 0.0, a.mesh))
     vol.close()
 
 

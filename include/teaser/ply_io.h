@@ -240,6 +240,56 @@ class PLYWriter {
     }
     return out ? 0 : -1;
   }
+
+  // A triangle mesh (teaser::TSDFTriangleMesh of teaser/tsdf.h): `vertex` with double x, y, z and, when `colors` has a
+  // column per vertex, uchar red, green, blue (round(clamp(c, 0, 1) 255), a NaN as 0); `face` with
+  // `list uchar int vertex_indices`, three indices of `triangles` per face.  Mat is a column-major 3 x N matrix of
+  // doubles with cols() and data() (teaser::Matrix3X); a `colors` without columns writes none.  0 on success, -1 on
+  // failure (the file, a colour count that is not the vertex count, a triangle count that is no multiple of three).
+  template <class Mat>
+  int writeMesh(const std::string& file_name, const Mat& vertices, const Mat& colors, const std::vector<int32_t>& triangles,
+                bool binary_mode = true) {
+    const size_t n = (size_t)vertices.cols(), m = triangles.size() / 3;
+    const bool colored = colors.cols() > 0;
+    if ((colored && (size_t)colors.cols() != n) || triangles.size() % 3 != 0) return -1;
+    std::ofstream out(file_name, binary_mode ? std::ios::out | std::ios::binary : std::ios::out);
+    if (!out) return -1;
+    const bool le = ply_detail::host_is_little_endian();
+    out << "ply\nformat " << (binary_mode ? (le ? "binary_little_endian" : "binary_big_endian") : "ascii")
+        << " 1.0\nelement vertex " << n << "\nproperty double x\nproperty double y\nproperty double z\n";
+    if (colored) out << "property uchar red\nproperty uchar green\nproperty uchar blue\n";
+    out << "element face " << m << "\nproperty list uchar int vertex_indices\nend_header\n";
+    const double* v = vertices.data();
+    const double* c = colors.data();
+    out.precision(17);  // round-trips every double
+    for (size_t k = 0; k < n; ++k) {
+      unsigned char rgb[3] = {0, 0, 0};
+      if (colored)
+        for (int q = 0; q < 3; ++q) {
+          const double x = c[3 * k + q];
+          rgb[q] = (unsigned char)(x > 0.0 ? (x < 1.0 ? x * 255.0 + 0.5 : 255.0) : 0.0);  // a NaN compares false: 0
+        }
+      if (binary_mode) {
+        out.write(reinterpret_cast<const char*>(v + 3 * k), 3 * sizeof(double));
+        if (colored) out.write(reinterpret_cast<const char*>(rgb), 3);
+      } else {
+        out << v[3 * k] << ' ' << v[3 * k + 1] << ' ' << v[3 * k + 2];
+        if (colored) out << ' ' << (int)rgb[0] << ' ' << (int)rgb[1] << ' ' << (int)rgb[2];
+        out << '\n';
+      }
+    }
+    for (size_t k = 0; k < m; ++k) {
+      const int32_t* t = triangles.data() + 3 * k;
+      if (binary_mode) {
+        const unsigned char three = 3;
+        out.write(reinterpret_cast<const char*>(&three), 1);
+        out.write(reinterpret_cast<const char*>(t), 3 * sizeof(int32_t));
+      } else {
+        out << "3 " << t[0] << ' ' << t[1] << ' ' << t[2] << '\n';
+      }
+    }
+    return out ? 0 : -1;
+  }
 };
 
 }  // namespace teaser

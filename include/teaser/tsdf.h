@@ -35,6 +35,13 @@ struct TSDFPointCloud {
   Matrix3X points, normals, colors;
 };
 
+// What extractTriangleMesh returns: one vertex per column; vertex_colors and vertex_normals have no columns where they
+// do not exist; triangles holds three vertex indices per triangle.
+struct TSDFTriangleMesh {
+  Matrix3X vertices, vertex_colors, vertex_normals;
+  std::vector<int32_t> triangles;
+};
+
 class UniformTSDFVolume {
  public:
   UniformTSDFVolume(double length, int resolution, double sdf_trunc, TSDFVolumeColorType color_type,
@@ -109,6 +116,25 @@ class UniformTSDFVolume {
     out.colors = Matrix3X(3, count);
     if (count > 0)
       check(teaser_hip_tsdf_extract_voxel_point_cloud(h_, count, out.points.data(), out.colors.data(), &count));
+    return out;
+  }
+
+  // Open3D's ExtractTriangleMesh (marching cubes): vertices and triangles in the order of Open3D's loop, vertex colours
+  // for a volume with a colour type.  with_vertex_normals adds the TSDF gradient at every vertex (the normal rule of the
+  // point cloud), which Open3D's call does not give.
+  TSDFTriangleMesh extractTriangleMesh(bool with_vertex_normals = false) {
+    const bool colored = color_type_ != TSDFVolumeColorType::NoColor;
+    int64_t nv = 0, nt = 0;
+    check(teaser_hip_tsdf_extract_triangle_mesh(h_, 0, nullptr, nullptr, nullptr, 0, nullptr, &nv, &nt));
+    TSDFTriangleMesh out;
+    out.vertices = Matrix3X(3, nv);
+    if (colored) out.vertex_colors = Matrix3X(3, nv);
+    if (with_vertex_normals) out.vertex_normals = Matrix3X(3, nv);
+    out.triangles.resize(3 * (size_t)nt);
+    if (nv > 0 || nt > 0)
+      check(teaser_hip_tsdf_extract_triangle_mesh(h_, nv, out.vertices.data(), colored ? out.vertex_colors.data() : nullptr,
+                                                  with_vertex_normals ? out.vertex_normals.data() : nullptr, nt,
+                                                  out.triangles.data(), &nv, &nt));
     return out;
   }
 

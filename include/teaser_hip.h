@@ -2157,6 +2157,47 @@ TEASER_HIP_API int32_t teaser_hip_plane_trials_batch(teaser_hip_plane* plane, in
  * only for a volume with a colour type).  A capacity below the count is TEASER_HIP_ERR_BAD_ARG: the message names the
  * count, count_out holds it, and no row is written.  Rows behind the count are not written.
  *
+ * teaser_hip_tsdf_extract_triangle_mesh: Open3D's UniformTSDFVolume::ExtractTriangleMesh (marching cubes), vertices and
+ * triangles in the order of Open3D's serial loop with its hash map.  tests/tsdf_mesh_reference.py restates it as that
+ * loop and is the parity target.
+ *   Cubes.  Cube (x, y, z) exists for 0 <= x, y, z < R - 1 (R = 1 has none).  Corner i lies at (x, y, z) + shift[i]:
+ *   shift = (0,0,0) (1,0,0) (1,1,0) (0,1,0) (0,0,1) (1,0,1) (1,1,1) (0,1,1).  Edge i is the lattice edge with base voxel
+ *   (x, y, z) + the first three of edge_shift[i] along the axis that is its fourth: edge_shift = (0,0,0,0) (1,0,0,1)
+ *   (0,1,0,0) (0,0,0,1) (0,0,1,0) (1,0,1,1) (0,1,1,0) (0,0,1,1) (0,0,0,2) (1,0,0,2) (1,1,0,2) (0,1,0,2).  Its corners are
+ *   edge_to_vert[i] = {0,1} {1,2} {3,2} {0,3} {4,5} {5,6} {7,6} {4,7} {0,4} {1,5} {2,6} {3,7}, the base voxel first.
+ *   ACTIVE.  cube_index has bit i set when tsdf(corner i) < 0.0f.  A cube is ACTIVE when all eight corner weights are
+ *   != 0 and cube_index is neither 0 nor 255 (no 0.98 test here, unlike the point cloud).
+ *   Tables.  edge_table[256] (bit i: the corners of edge i differ in sign) and tri_table[256][16] (edge numbers, -1
+ *   terminated, at most five triangles) are Paul Bourke's public-domain "polygonise" tables, written out from memory
+ *   and checked by property (tests/test_tsdf_mesh_reference.py).  The table as written is part of the contract: the
+ *   SHA-256 of tri_table as 4096 int8, row-major, is
+ *   19bf7699e214903d72c94c296546f2e31337d637a1e4b118c3108a0f428e809b.  teaser_hip_tsdf_mesh_tables hands both out
+ *   (host only, no device needed).
+ *   Vertices.  A lattice edge carries a vertex when its end voxels differ in sign (tsdf < 0.0f) and at least one of the
+ *   up to four cubes that contain it is ACTIVE.  Its CREATOR is the smallest such ACTIVE cube, compared as (x, y, z),
+ *   its slot the edge's number i inside the creator.  Vertices are numbered in ascending (creator's (x R + y) R + z,
+ *   slot): the order in which Open3D's loop first meets them.  With a, b = edge_to_vert[slot] in the creator, all in
+ *   double: f0 = |(double)tsdf(a)|, f1 = |(double)tsdf(b)|;  p = (half + vl bx, half + vl by, half + vl bz) for the
+ *   base voxel (bx, by, bz);  p_axis = p_axis + (f0 vl) / (f0 + f1);  the vertex is p + origin.  Colour (a volume with a
+ *   colour type): c0, c1 the end voxels' colours, each / 255.0 first for RGB8; (f1 c0 + f0 c1) / (f0 + f1) per
+ *   component; a NaN colour of a Gray32 volume is the quiet NaN.  (This order of operations is not the point cloud's.)
+ *   Triangles.  For every ACTIVE cube in ascending (x, y, z) and t = 0, 3, 6, ... until tri_table[cube_index][t] = -1
+ *   one row (v[T[t]], v[T[t + 2]], v[T[t + 1]]) -- Open3D swaps the last two -- with v[e] the index of the vertex on the
+ *   cube's edge e, int32.  Coincident vertices (a corner value of exactly 0) keep distinct indices; degenerate triangles
+ *   are kept.
+ *   Vertex normals (an EXTENSION: Open3D's mesh has none until compute_vertex_normals(), and this is not what that
+ *   computes): when vertex_normals is given, the normal rule of the point cloud above evaluated at p (volume
+ *   coordinates, before the origin is added): the same T, g = 0.99 vl, zero outside the volume, the same normalisation.
+ *   The call.  vertex_count_out and triangle_count_out (both required) receive the counts.  Both capacities 0 with
+ *   vertices and triangles NULL returns the counts alone.  Otherwise vertices has room for vertex_capacity x 3 doubles,
+ *   vertex_colors (only for a volume with a colour type) and vertex_normals are NULL or as large, triangles has room for
+ *   triangle_capacity x 3 int32.  A capacity below its count is TEASER_HIP_ERR_BAD_ARG: the message names both counts,
+ *   both outputs hold them, and no row of either array is written.  Rows behind the counts are not written.  A vertex
+ *   count above 2^31 - 1 is TEASER_HIP_ERR_BAD_ARG with the count in the message.  Scratch: 5 bytes per voxel (a byte
+ *   and a 32-bit record per cube) plus 24 bytes per column, allocated by the first call and kept on the handle; a
+ *   failed allocation is TEASER_HIP_ERR_OOM and leaves the volume intact.  Three launches for the counts and one
+ *   more for each array with a capacity above 0; no floating-point atomic, the same bits run after run.
+ *
  * teaser_hip_tsdf_download / _upload: tsdf_weight is R^3 x 2 float32 (tsdf, weight), color R^3 x 3 doubles (only for a
  * volume with a colour type), both in Open3D's voxel order (x R + y) R + z whatever the device layout is; either may be
  * NULL, not both.  upload refuses values that are not finite, except a NaN colour of a Gray32 volume, which is stored
@@ -2216,6 +2257,13 @@ TEASER_HIP_API int32_t teaser_hip_tsdf_extract_voxel_point_cloud(teaser_hip_tsdf
                                                                  double* colors, int64_t* count_out);
 TEASER_HIP_API int32_t teaser_hip_tsdf_download(teaser_hip_tsdf* tsdf, float* tsdf_weight, double* color);
 TEASER_HIP_API int32_t teaser_hip_tsdf_upload(teaser_hip_tsdf* tsdf, const float* tsdf_weight, const double* color);
+TEASER_HIP_API int32_t teaser_hip_tsdf_extract_triangle_mesh(teaser_hip_tsdf* tsdf, int64_t vertex_capacity,
+                                                             double* vertices, double* vertex_colors,
+                                                             double* vertex_normals, int64_t triangle_capacity,
+                                                             int32_t* triangles, int64_t* vertex_count_out,
+                                                             int64_t* triangle_count_out);
+/* Host only: the marching-cubes tables of the call above, edge_table[256] and tri_table[256][16] row-major. */
+TEASER_HIP_API int32_t teaser_hip_tsdf_mesh_tables(int32_t* edge_table, int8_t* tri_table);
 
 /* Page-locked host memory from the HIP runtime THIS library runs on.  teaser_hip_submit_batch(..., INPUT_HOST) moves
  * the points with one DMA copy per cloud, at PCIe speed only when the runtime knows the pages are locked.  A buffer

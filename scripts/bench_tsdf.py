@@ -20,8 +20,17 @@ follow from `touched_voxels_per_pass` in the JSON (counted at R <= 256 by integr
 and downloading the weights); over the kernel's time they give the share of the 8 TB/s HBM peak that
 profiles/tsdf/README.md works out.  Needs an MI355X: there is no CPU path.
 
-    python scripts/bench_tsdf.py --reps 9 --warmup 1 --out profiles/tsdf/bench_tsdf.json"""
+    python scripts/bench_tsdf.py --reps 9 --warmup 1 --out profiles/tsdf/bench_tsdf.json
+
+`--mesh` measures the triangle mesh instead (profiles/tsdf_mesh/): on the same 64-frame scene at every size of `--sizes`,
+with RGB8 colour, extract_triangle_mesh (a count call and a fill call, as the Python method makes them) with and without
+vertex normals beside the handle's own extract_point_cloud, and the Python restatement of the mesh
+(tests/tsdf_mesh_reference.py) on the volume downloaded at R = 64, which must equal the device's mesh.
+`--profile-workload mesh` runs three mesh extractions for rocprofv3.
+
+    python scripts/bench_tsdf.py --mesh --reps 9 --warmup 1 --out profiles/tsdf_mesh/bench_tsdf_mesh.json"""
 import argparse
+import ctypes as C
 import importlib
 import json
 import os
@@ -130,15 +139,60 @@ def restatement():
                 device_equals_restatement=bool(same))
 
 
+def run_mesh(R, K, d, e, c, reps, warmup):
+    res = dict(R=R, colour=True)
+    with make(R, 1) as vol:
+        one_call(vol, K, d, e, c)
+        mesh = vol.extract_triangle_mesh(vertex_normals=True)
+        res["vertices"], res["triangles"] = len(mesh.vertices), len(mesh.triangles)
+        res["output_bytes"] = int(mesh.vertices.nbytes * 3 + mesh.triangles.nbytes)
+        res["max_distance_to_surface"] = float(ex.distance_to_surface(mesh.vertices).max())
+        again = vol.extract_triangle_mesh(vertex_normals=True)
+        res["same_bits_twice"] = bool(again.vertices.tobytes() == mesh.vertices.tobytes() and again.triangles.tobytes() == mesh.triangles.tobytes()
+                                      and again.vertex_normals.tobytes() == mesh.vertex_normals.tobytes())
+        del mesh, again
+        res["extract_triangle_mesh"] = timed(lambda: vol.extract_triangle_mesh(), reps, warmup)
+        res["extract_triangle_mesh_with_normals"] = timed(lambda: vol.extract_triangle_mesh(vertex_normals=True), reps, warmup)
+        nv, nt = C.c_int64(0), C.c_int64(0)
+        res["counts_only_call"] = timed(lambda: vol._call(tp.lib().teaser_hip_tsdf_extract_triangle_mesh, 0, None, None, None, 0, None,
+                                                          C.byref(nv), C.byref(nt)), reps, warmup)
+        res["surface_points"] = len(vol.extract_point_cloud().points)
+        res["extract_point_cloud"] = timed(lambda: vol.extract_point_cloud(), reps, warmup)
+        res["extract_point_cloud_no_normals"] = timed(lambda: vol.extract_point_cloud(normals=False), reps, warmup)
+    return res
+
+
+def mesh_restatement(K, d, e, c):
+    """The Python loop on the host at R = 64 (8 frames), on the volume the device integrated."""
+    import tsdf_mesh_reference as M
+    import tsdf_reference as T
+    length, R, trunc, origin = ex.volume_settings(64)
+    with make(64, 1) as g:
+        one_call(g, K, d[:CHUNK], e[:CHUNK], c[:CHUNK])
+        vol = T.Volume(length, R, trunc, T.RGB8, origin)
+        tw = g.extract_volume_tsdf().reshape(R, R, R, 2)
+        vol.tsdf[:], vol.weight[:], vol.color[:] = tw[..., 0], tw[..., 1], g.extract_volume_color().reshape(R, R, R, 3)
+        t = time.perf_counter()
+        ref = M.extract_triangle_mesh(vol, normals=True)
+        t1 = time.perf_counter()
+        mesh = g.extract_triangle_mesh(vertex_normals=True)
+        t2 = time.perf_counter()
+    same = (mesh.vertices.tobytes() == ref.vertices.tobytes() and mesh.triangles.tobytes() == ref.triangles.tobytes()
+            and mesh.vertex_colors.tobytes() == ref.colors.tobytes() and mesh.vertex_normals.tobytes() == ref.normals.tobytes())
+    return dict(R=64, frames=CHUNK, restatement_ms=1e3 * (t1 - t), device_ms_one_untimed_call=1e3 * (t2 - t1), vertices=len(ref.vertices),
+                triangles=len(ref.triangles), device_equals_restatement=bool(same))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=9)
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--out", default=None)
     ap.add_argument("--sizes", type=int, nargs="+", default=[256, 512])
-    ap.add_argument("--profile-workload", choices=["one_call", "calls", "extract"], default=None)
+    ap.add_argument("--profile-workload", choices=["one_call", "calls", "extract", "mesh"], default=None)
     ap.add_argument("--profile-R", type=int, default=512)
     ap.add_argument("--profile-colour", type=int, default=1)
+    ap.add_argument("--mesh", action="store_true", help="measure the triangle mesh instead (profiles/tsdf_mesh/)")
     a = ap.parse_args()
     if tp.device_count() < 1:
         sys.exit("bench_tsdf.py needs an MI355X: no HIP device visible")
@@ -151,12 +205,27 @@ def main():
                     one_call(vol, K, d, e, cc)
                 elif a.profile_workload == "calls":
                     many_calls(vol, K, d, e, cc)
+                elif a.profile_workload == "mesh":
+                    one_call(vol, K, d[:CHUNK], e[:CHUNK], None if cc is None else cc[:CHUNK])
+                    vol.extract_triangle_mesh(vertex_normals=True)
                 else:
                     one_call(vol, K, d[:CHUNK], e[:CHUNK], None if cc is None else cc[:CHUNK])
                     vol.extract_point_cloud()
                     vol.extract_voxel_point_cloud()
         return
     out = dict(workload=dict(width=W, height=H, frames=FRAMES, poses=POSES, chunk=CHUNK, hbm_peak=HBM_PEAK), settings=[])
+    if a.mesh:
+        for R in a.sizes:
+            r = run_mesh(R, K, d, e, c, a.reps, a.warmup)
+            print(json.dumps(r), flush=True)
+            out["settings"].append(r)
+        out["restatement"] = mesh_restatement(K, d, e, c)
+        print(json.dumps(out["restatement"]), flush=True)
+        if a.out:
+            os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+            with open(a.out, "w") as f:
+                json.dump(out, f, indent=1)
+        return
     for R in a.sizes:
         for colour in (0, 1):
             r = run_setting(R, colour, K, d, e, c, a.reps, a.warmup, compare_colour=R <= 256)

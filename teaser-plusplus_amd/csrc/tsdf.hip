@@ -14,47 +14,19 @@
 #include <string>
 #include <vector>
 
-#include "host_common.h"
-#include "teaser_hip.h"
-#include "tsdf_device.h"
+#include "tsdf_internal.h"
 
 using namespace thip;
-
-struct teaser_hip_tsdf : HandleBase {
-  teaser_tsdf_volume_c vol;
-  TsdfGrid g;
-  void* volume = nullptr;  // tsdf (n floats), weight (n floats), colour (3 n doubles), exactly sized
-  size_t volume_bytes = 0;
-  DevBuf in, work, out;
-  HostBuf stage, back;
-  ~teaser_hip_tsdf() {
-    if (volume) (void)hipFree(volume);
-  }
-};
 
 namespace {
 
 thread_local std::string g_create_error;  // what teaser_hip_tsdf_last_error(NULL) returns: create has no handle yet
 
-inline size_t round_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 inline std::string frame_at(int b) { return " (frame " + std::to_string(b) + ")"; }
 
 int32_t refuse_create(const std::string& msg) {
   g_create_error = msg;
   return TEASER_HIP_ERR_BAD_ARG;
-}
-
-int64_t voxels(const teaser_hip_tsdf* h) { return (int64_t)h->g.R * h->g.R * h->g.R; }
-
-TsdfFields fields(const teaser_hip_tsdf* h) {
-  const int64_t n = voxels(h);
-  char* p = static_cast<char*>(h->volume);
-  TsdfFields v;
-  v.tsdf = reinterpret_cast<float*>(p);
-  v.weight = reinterpret_cast<float*>(p + 4 * (size_t)n);
-  v.color = h->g.color_type != 0 ? reinterpret_cast<double*>(p + 8 * (size_t)n) : nullptr;
-  v.n = n;
-  return v;
 }
 
 int32_t check_frame(teaser_hip_tsdf* h, int b, const teaser_tsdf_frame_c& f) {

@@ -177,6 +177,25 @@ __host__ __device__ __forceinline__ double tsdf_trilinear(const TsdfGrid& g, con
   return sum;
 }
 
+// The normal at p (volume coordinates): the central differences of T over g = 0.99 vl, normalised unless zero.
+__host__ __device__ __forceinline__ void tsdf_normal_at(const TsdfGrid& g, const TsdfFields& v, const double* p,
+                                                        double* normal) {
+  const double gstep = 0.99 * g.vl;
+  double n[3];
+  for (int k = 0; k < 3; ++k) {
+    double hi[3] = {p[0], p[1], p[2]}, lo[3] = {p[0], p[1], p[2]};
+    hi[k] = p[k] + gstep;
+    lo[k] = p[k] - gstep;
+    n[k] = tsdf_trilinear(g, v, hi) - tsdf_trilinear(g, v, lo);
+  }
+  const double s = (n[0] * n[0] + n[1] * n[1]) + n[2] * n[2];
+  if (s > 0.0) {
+    const double len = __builtin_sqrt(s);
+    for (int k = 0; k < 3; ++k) n[k] = n[k] / len;
+  }
+  for (int k = 0; k < 3; ++k) normal[k] = n[k];
+}
+
 // The surface point between voxel (x, y, z) (value f0) and its neighbour along i (at1, value f1): point, and where the
 // pointers are given the normal and the colour.
 __host__ __device__ __forceinline__ void tsdf_surface_point(const TsdfGrid& g, const TsdfFields& v, int x, int y, int z,
@@ -196,22 +215,7 @@ __host__ __device__ __forceinline__ void tsdf_surface_point(const TsdfGrid& g, c
       color[k] = g.color_type == 2 ? rgbd_canonical(c) : c;
     }
   }
-  if (normal) {
-    const double gstep = 0.99 * g.vl;
-    double n[3];
-    for (int k = 0; k < 3; ++k) {
-      double hi[3] = {p[0], p[1], p[2]}, lo[3] = {p[0], p[1], p[2]};
-      hi[k] = p[k] + gstep;
-      lo[k] = p[k] - gstep;
-      n[k] = tsdf_trilinear(g, v, hi) - tsdf_trilinear(g, v, lo);
-    }
-    const double s = (n[0] * n[0] + n[1] * n[1]) + n[2] * n[2];
-    if (s > 0.0) {
-      const double len = __builtin_sqrt(s);
-      for (int k = 0; k < 3; ++k) n[k] = n[k] / len;
-    }
-    for (int k = 0; k < 3; ++k) normal[k] = n[k];
-  }
+  if (normal) tsdf_normal_at(g, v, p, normal);
 }
 
 // The row of the voxel cloud for the usable voxel (x, y, z) with value f0.

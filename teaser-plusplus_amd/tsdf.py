@@ -23,6 +23,7 @@ import numpy as np
 from .rgbd import _each, _fxfycxcy, _image, _is_intrinsic, _is_matrix, _is_scalar
 
 _vp, _dp, _fp, _i64p = C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_float), C.POINTER(C.c_int64)
+_i32p, _i8p = C.POINTER(C.c_int32), C.POINTER(C.c_int8)
 
 
 class TsdfVolumeC(C.Structure):
@@ -55,6 +56,8 @@ def declare(L):
     L.teaser_hip_tsdf_extract_voxel_point_cloud.argtypes = [_vp, C.c_int64, _dp, _dp, _i64p]
     L.teaser_hip_tsdf_download.argtypes = [_vp, _fp, _dp]
     L.teaser_hip_tsdf_upload.argtypes = [_vp, _fp, _dp]
+    L.teaser_hip_tsdf_extract_triangle_mesh.argtypes = [_vp, C.c_int64, _dp, _dp, _dp, C.c_int64, _i32p, _i64p, _i64p]
+    L.teaser_hip_tsdf_mesh_tables.argtypes = [_i32p, _i8p]
 
 
 class TSDFVolumeColorType:
@@ -71,6 +74,55 @@ class TSDFPointCloud:
 
     def __len__(self):
         return len(self.points)
+
+
+class TSDFTriangleMesh:
+    """What extract_triangle_mesh returns: ``vertices`` (n x 3 float64), ``triangles`` (m x 3 int32) and, where they
+    exist, ``vertex_colors`` and ``vertex_normals`` (n x 3 float64, else None)."""
+
+    def __init__(self, vertices, triangles, vertex_colors=None, vertex_normals=None):
+        self.vertices, self.triangles = vertices, triangles
+        self.vertex_colors, self.vertex_normals = vertex_colors, vertex_normals
+
+
+def write_triangle_mesh(path, mesh, binary=True):
+    """The mesh as a PLY file, as teaser::PLYWriter::writeMesh (include/teaser/ply_io.h) writes it: vertex with double
+    x, y, z and, with vertex colours, uchar red, green, blue (round(clamp(c, 0, 1) 255), a NaN as 0); face with
+    ``list uchar int vertex_indices``.  binary: the host's byte order."""
+    import sys
+    vert = np.ascontiguousarray(mesh.vertices, dtype=np.float64).reshape(-1, 3)
+    tri = np.ascontiguousarray(mesh.triangles, dtype=np.int32).reshape(-1, 3)
+    rgb = None
+    if mesh.vertex_colors is not None:
+        c = np.nan_to_num(np.asarray(mesh.vertex_colors, dtype=np.float64).reshape(-1, 3), nan=0.0)
+        rgb = np.floor(np.clip(c, 0.0, 1.0) * 255.0 + 0.5).astype(np.uint8)
+        if len(rgb) != len(vert):
+            raise ValueError("vertex_colors: one row per vertex")
+    fmt = "ascii" if not binary else "binary_%s_endian" % sys.byteorder
+    head = "ply\nformat %s 1.0\nelement vertex %d\nproperty double x\nproperty double y\nproperty double z\n" % (fmt, len(vert))
+    if rgb is not None:
+        head += "property uchar red\nproperty uchar green\nproperty uchar blue\n"
+    head += "element face %d\nproperty list uchar int vertex_indices\nend_header\n" % len(tri)
+    with open(path, "wb") as f:
+        f.write(head.encode())
+        if binary:
+            fields = [("xyz", np.float64, 3)] + ([("rgb", np.uint8, 3)] if rgb is not None else [])
+            v = np.zeros(len(vert), dtype=np.dtype(fields, align=False))
+            v["xyz"] = vert
+            if rgb is not None:
+                v["rgb"] = rgb
+            f.write(v.tobytes())
+            t = np.zeros(len(tri), dtype=np.dtype([("n", np.uint8), ("idx", np.int32, 3)], align=False))
+            t["n"], t["idx"] = 3, tri
+            f.write(t.tobytes())
+        else:
+            for k in range(len(vert)):
+                row = " ".join("%.17g" % x for x in vert[k])
+                if rgb is not None:
+                    row += " %d %d %d" % tuple(rgb[k])
+                f.write((row + "\n").encode())
+            for a, b, c in tri:
+                f.write(("3 %d %d %d\n" % (a, b, c)).encode())
 
 
 class UniformTSDFVolume:
@@ -227,6 +279,24 @@ class UniformTSDFVolume:
         pts, (col,) = self._extract(self._lib.teaser_hip_tsdf_extract_voxel_point_cloud, [True])
         return TSDFPointCloud(pts, None, col)
 
+    def extract_triangle_mesh(self, vertex_normals=False):
+        """Open3D's extract_triangle_mesh: marching cubes over the observed cubes, vertices and triangles in the order
+        of Open3D's loop, with vertex colours for a volume with a colour type.  vertex_normals=True adds the TSDF
+        gradient at every vertex (the normal rule of the point cloud), which Open3D's call does not give."""
+        nv, nt = C.c_int64(0), C.c_int64(0)
+        fn = self._lib.teaser_hip_tsdf_extract_triangle_mesh
+        self._call(fn, 0, None, None, None, 0, None, C.byref(nv), C.byref(nt))
+        n, m = int(nv.value), int(nt.value)
+        colored = self.color_type != TSDFVolumeColorType.NoColor
+        vert, tri = np.empty((n, 3)), np.empty((m, 3), dtype=np.int32)
+        col = np.empty((n, 3)) if colored else None
+        nrm = np.empty((n, 3)) if vertex_normals else None
+        if n or m:
+            self._call(fn, n, vert.ctypes.data_as(_dp), None if col is None else col.ctypes.data_as(_dp),
+                       None if nrm is None else nrm.ctypes.data_as(_dp), m, tri.ctypes.data_as(_i32p), C.byref(nv),
+                       C.byref(nt))
+        return TSDFTriangleMesh(vert, tri, col, nrm)
+
     # ---- the voxels ---------------------------------------------------------------------------------------------
     def extract_volume_tsdf(self):
         """R^3 x 2 float32 (tsdf, weight) in Open3D's voxel order (x R + y) R + z."""
@@ -265,4 +335,4 @@ class UniformTSDFVolume:
         self._call(self._lib.teaser_hip_tsdf_reset)
 
 
-__all__ = ["UniformTSDFVolume", "TSDFVolumeColorType", "TSDFPointCloud"]
+__all__ = ["UniformTSDFVolume", "TSDFVolumeColorType", "TSDFPointCloud", "TSDFTriangleMesh", "write_triangle_mesh"]
