@@ -42,6 +42,21 @@ struct TSDFTriangleMesh {
   std::vector<int32_t> triangles;
 };
 
+// The options of a ray cast: the z-depth range of a ray, the weight a voxel needs to count as surface (Open3D's 3.0)
+// and the maps wanted beside the depth.
+struct TSDFRayCastOptions {
+  double depth_min = 0.1, depth_max = 3.0, weight_threshold = 3.0;
+  bool vertex_map = true, normal_map = true, color = true;
+};
+
+// What rayCast returns: row-major float32 maps, depth height x width (the z-depth, 0 where no surface was met), the
+// others height x width x 3; a map that was not asked for, and the colour of a volume without a colour type, is empty.
+struct TSDFRayCastResult {
+  int width = 0, height = 0;
+  std::vector<float> depth, vertex_map, normal_map, color;
+  int64_t hits = 0;  // the pixels that met a surface
+};
+
 class UniformTSDFVolume {
  public:
   UniformTSDFVolume(double length, int resolution, double sdf_trunc, TSDFVolumeColorType color_type,
@@ -135,6 +150,53 @@ class UniformTSDFVolume {
       check(teaser_hip_tsdf_extract_triangle_mesh(h_, nv, out.vertices.data(), colored ? out.vertex_colors.data() : nullptr,
                                                   with_vertex_normals ? out.vertex_normals.data() : nullptr, nt,
                                                   out.triangles.data(), &nv, &nt));
+    return out;
+  }
+
+  // The fused model seen from a camera (Open3D's VoxelBlockGrid::RayCast for the dense volume): per pixel the z-depth
+  // of the first surface its ray meets, the world point, the normal and the colour.  The rules: include/teaser_hip.h,
+  // "TSDF ray casting".
+  TSDFRayCastResult rayCast(const PinholeCameraIntrinsic& intrinsic, const Matrix4& extrinsic, int width, int height,
+                            const TSDFRayCastOptions& options = TSDFRayCastOptions()) {
+    return rayCastBatch({intrinsic}, {extrinsic}, {width}, {height}, options)[0];
+  }
+
+  // All views in one call: one launch, one synchronisation.  intrinsics, widths, heights: one for all or one per view.
+  std::vector<TSDFRayCastResult> rayCastBatch(const std::vector<PinholeCameraIntrinsic>& intrinsics,
+                                              const std::vector<Matrix4>& extrinsics, const std::vector<int>& widths,
+                                              const std::vector<int>& heights,
+                                              const TSDFRayCastOptions& options = TSDFRayCastOptions()) {
+    const size_t b = extrinsics.size();
+    if ((intrinsics.size() != 1 && intrinsics.size() != b) || (widths.size() != 1 && widths.size() != b) ||
+        (heights.size() != 1 && heights.size() != b))
+      throw std::invalid_argument("teaser::UniformTSDFVolume: one intrinsic, width and height (or one per view)");
+    const bool colored = options.color && color_type_ != TSDFVolumeColorType::NoColor;
+    std::vector<teaser_tsdf_view_c> rec(b);
+    std::vector<TSDFRayCastResult> out(b);
+    std::vector<float*> pd(b), pv(b), pn(b), pc(b);
+    std::vector<int64_t> hits(b, 0);
+    for (size_t k = 0; k < b; ++k) {
+      const PinholeCameraIntrinsic& K = intrinsics[intrinsics.size() == 1 ? 0 : k];
+      teaser_tsdf_view_c& r = rec[k];
+      teaser_hip_tsdf_view_default(&r);
+      r.width = widths[widths.size() == 1 ? 0 : k], r.height = heights[heights.size() == 1 ? 0 : k];
+      r.fx = K.fx, r.fy = K.fy, r.cx = K.cx, r.cy = K.cy;
+      detail::row_major(extrinsics[k], r.extrinsic);
+      r.depth_min = options.depth_min, r.depth_max = options.depth_max, r.weight_threshold = options.weight_threshold;
+      TSDFRayCastResult& o = out[k];
+      o.width = r.width, o.height = r.height;
+      const size_t px = r.width > 0 && r.height > 0 ? (size_t)r.width * (size_t)r.height : 0;
+      o.depth.assign(px, 0.0f);
+      if (options.vertex_map) o.vertex_map.assign(3 * px, 0.0f);
+      if (options.normal_map) o.normal_map.assign(3 * px, 0.0f);
+      if (colored) o.color.assign(3 * px, 0.0f);
+      pd[k] = px ? o.depth.data() : nullptr;
+      pv[k] = px && options.vertex_map ? o.vertex_map.data() : nullptr;
+      pn[k] = px && options.normal_map ? o.normal_map.data() : nullptr;
+      pc[k] = px && colored ? o.color.data() : nullptr;
+    }
+    check(teaser_hip_tsdf_ray_cast_views(h_, (int32_t)b, rec.data(), pd.data(), pv.data(), pn.data(), pc.data(), hits.data()));
+    for (size_t k = 0; k < b; ++k) out[k].hits = hits[k];
     return out;
   }
 

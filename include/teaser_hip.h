@@ -2265,6 +2265,95 @@ TEASER_HIP_API int32_t teaser_hip_tsdf_extract_triangle_mesh(teaser_hip_tsdf* ts
 /* Host only: the marching-cubes tables of the call above, edge_table[256] and tri_table[256][16] row-major. */
 TEASER_HIP_API int32_t teaser_hip_tsdf_mesh_tables(int32_t* edge_table, int8_t* tri_table);
 
+/* TSDF ray casting: the volume of a TSDF handle rendered into cameras -- per pixel the z-depth, the world point, the
+ * normal and the colour of the first surface a ray meets.  The semantics follow Open3D's
+ * t.geometry.VoxelBlockGrid.ray_cast, restated for the dense volume; Open3D is not run and bit parity with an Open3D
+ * binary is NOT claimed.  The text below IS the contract; tests/tsdf_raycast_reference.py restates it in numpy and is
+ * the parity target of the host and GPU tests.  No product-add is fused, every sum is taken left to right as written,
+ * every min and max is written as a comparison (so a NaN's path is stated), float32 divisions are correctly rounded.
+ *
+ * The view.  One record teaser_tsdf_view_c per view; E = extrinsic, the row-major 4 x 4 world-to-camera matrix as in
+ * integration.  On the host, in double: the camera-to-world rotation is the transpose of E's upper 3 x 3 and the centre
+ *   c_k = -((E[0][k] E[0][3] + E[1][k] E[1][3]) + E[2][k] E[2][3]).
+ * That is the inverse of a rigid E; a non-rigid extrinsic is NOT inverted (its rays are whatever these formulas give).
+ * Per-view float32 constants:  o_f[k] = (float)(c_k - origin_k) (the centre in volume coordinates);
+ *   Rt_f[k][j] = (float)E[j][k];  fx_f, fy_f, cx_f, cy_f, dmin_f, dmax_f, wthr_f = (float) of the view's fields;
+ *   L_f = (float)length;  vl_f and trunc_f are those of "TSDF volume".
+ *
+ * The ray of pixel (v, u) (row v, column u), all float32:
+ *   a = ((float)u - cx_f) / fx_f;  b = ((float)v - cy_f) / fy_f;  d_k = (Rt_f[k][0] a + Rt_f[k][1] b) + Rt_f[k][2].
+ * The point at parameter t is o_f + t d, so t is the z-depth in the camera.
+ *
+ * The box clip.  t0 = dmin_f, t1 = dmax_f.  For each axis k = 0, 1, 2 in turn: with d_k != 0,
+ *   lo = (0.0f - o_k) / d_k;  hi = (L_f - o_k) / d_k;  if (hi < lo) the two are exchanged;
+ *   t0 = t0 < lo ? lo : t0;  t1 = hi < t1 ? hi : t1;
+ * with d_k == 0 the pixel is a MISS unless o_k >= 0.0f && o_k < L_f.  The clip only saves steps: safety comes from the
+ * sample rule below, which reads no voxel outside the volume whatever t is.
+ *
+ * The march.  t = t0, t_prev = t0, f_prev = -1.0f.  At most 2 R + 2 steps; a ray that has taken them all is a MISS.  (A
+ * ray inside the box takes fewer than sqrt(3) R + 1, every step being at least vl_f long; the cap exists so that a
+ * rounding t + step == t can never hang a device.)  Each step, in order:
+ *   1. MISS unless t <= t1  (a NaN misses).
+ *   2. p_k = o_k + t d_k;  q_k = floorf(p_k / vl_f).
+ *   3. The sample is voxel ((int)q_0, (int)q_1, (int)q_2) when every q_k >= 0.0f && q_k < (float)R -- the float is tested
+ *      before it is converted, so no conversion overflows; f = its tsdf, w = its weight.  Otherwise f = 0 and w = 0, as
+ *      for an unobserved voxel.
+ *   4. HIT when f_prev > 0.0f && w >= wthr_f && f <= 0.0f.
+ *   5. Otherwise t_prev = t, f_prev = f;  delta = f trunc_f;  t = t + (delta < vl_f ? vl_f : delta).
+ * Consequences: a camera that starts behind a surface sees nothing until its ray has passed an observed positive
+ * voxel (f_prev starts negative), and a surface met from unobserved space (f_prev = 0) is not a hit.  With
+ * weight_threshold <= 0 the space outside the volume (f = 0, w = 0) ends a ray that comes from a positive voxel.
+ *
+ * A hit.  t* = (t f_prev - t_prev f) / (f_prev - f) in float32;  depth = t*.  In double
+ *   q_k = (double)o_k + (double)t* (double)d_k   (volume coordinates);  vertex_k = q_k + origin_k, rounded to float32.
+ * NEAR: every q_k >= -(2.0 vl) && q_k <= vl (double)R + 2.0 vl (double; a NaN is not near).  A hit that is not near has
+ * the normal and the colour 0: every corner the two rules below would read lies outside the volume, so this is their value, and
+ * the test keeps an enormous q from being converted to an integer.  (It needs a camera so far from the volume that
+ * float32 no longer resolves a voxel.)  Otherwise:
+ *   normal: the normal rule of teaser_hip_tsdf_extract_point_cloud at q (the same T, g = 0.99 vl, zero outside the
+ *   volume, the same normalisation), rounded to float32 -- so the point cloud, the mesh and the ray cast agree.
+ *   colour (a volume with a colour type): with a = q / vl - 0.5, idx = floor(a), r = a - idx as in T, over the eight
+ *   corners in T's order 000, 001, ..., 111 with T's weights omega = (wx wy) wz: a corner COUNTS when it lies inside the
+ *   volume and its voxel weight is != 0.  Starting from num_c = 0.0 and den = 0.0, each counting corner adds
+ *   num_c = num_c + omega color_c and den = den + omega.  The value is num_c / den when den > 0, else 0 (no corner
+ *   counts, or only corners of omega 0); then / 255.0 for RGB8 only.  Rounded to float32; a NaN (a Gray32 volume) is
+ *   stored as the quiet NaN 0x7fc00000.
+ * A missed pixel is 0 in every output.
+ *
+ * teaser_hip_tsdf_ray_cast_views.  depth, vertex, normal and color are arrays of n_views host pointers; a whole array
+ * or any single entry may be NULL when that map is not wanted.  depth[b] is height x width float32, the others
+ * height x width x 3 float32, row-major and packed.  color is allowed only for a volume with a colour type.  hit_counts
+ * (optional) receives per view the int64 number of hit pixels (summed in integers).  Views of any mix of sizes go into
+ * one call: one launch covers all pixels of all views (blocks of 16 x 16 pixels and a block map), one stream
+ * synchronisation per call, the maps come back through the handle's page-locked buffer and only the requested ones are
+ * computed and copied.  A view with width or height 0 is legal; n_views = 0 returns OK without touching the device.
+ * The call does not modify the volume, is stream-ordered after earlier integrations on the handle, uses no
+ * floating-point atomic and gives the same bits run after run and for any grouping of the views into calls.
+ * TEASER_HIP_ERR_BAD_ARG (the message names the view and the field; the handle stays usable): n_views negative; width
+ * or height negative or above 16384; fx or fy zero or not finite; cx, cy or the extrinsic not finite; depth_min
+ * negative; depth_min, depth_max or weight_threshold not finite; depth_max < depth_min; reserved != 0; color asked of a
+ * volume without colour; a NULL handle or, with n_views > 0, NULL views; more than 2^31 - 1 blocks in one call. */
+typedef struct teaser_tsdf_view_c {
+  int32_t width, height;
+  double fx, fy, cx, cy;
+  double extrinsic[16];    /* row-major, world to camera */
+  double depth_min;        /* default 0.1 */
+  double depth_max;        /* default 3.0 */
+  double weight_threshold; /* default 3.0 (Open3D's) */
+  int64_t reserved;        /* must be 0 */
+} teaser_tsdf_view_c;
+#ifdef __cplusplus
+static_assert(sizeof(teaser_tsdf_view_c) == 200, "teaser_tsdf_view_c is 200 bytes");
+#else
+_Static_assert(sizeof(teaser_tsdf_view_c) == 200, "teaser_tsdf_view_c is 200 bytes");
+#endif
+/* Zeroes the record, sets the defaults noted beside the fields and the identity extrinsic. */
+TEASER_HIP_API int32_t teaser_hip_tsdf_view_default(teaser_tsdf_view_c* view);
+TEASER_HIP_API int32_t teaser_hip_tsdf_ray_cast_views(teaser_hip_tsdf* tsdf, int32_t n_views,
+                                                      const teaser_tsdf_view_c* views, float* const* depth,
+                                                      float* const* vertex, float* const* normal, float* const* color,
+                                                      int64_t* hit_counts);
+
 /* Page-locked host memory from the HIP runtime THIS library runs on.  teaser_hip_submit_batch(..., INPUT_HOST) moves
  * the points with one DMA copy per cloud, at PCIe speed only when the runtime knows the pages are locked.  A buffer
  * pinned by another HIP runtime instance in the same process (e.g. the one a Python framework bundles) is pageable

@@ -28,7 +28,17 @@ vertex normals beside the handle's own extract_point_cloud, and the Python resta
 (tests/tsdf_mesh_reference.py) on the volume downloaded at R = 64, which must equal the device's mesh.
 `--profile-workload mesh` runs three mesh extractions for rocprofv3.
 
-    python scripts/bench_tsdf.py --mesh --reps 9 --warmup 1 --out profiles/tsdf_mesh/bench_tsdf_mesh.json"""
+    python scripts/bench_tsdf.py --mesh --reps 9 --warmup 1 --out profiles/tsdf_mesh/bench_tsdf_mesh.json
+
+`--ray-cast` measures the ray cast instead (profiles/tsdf_raycast/): on the same 64-frame scene at every size of
+`--sizes`, with RGB8 colour, one 640 x 480 view at the first pose with all maps and with the depth alone, 16 views (the
+16 poses) in one call against 16 calls, and -- the only route to a model depth image without the ray cast --
+extract_point_cloud followed by project_to_depth_image on the same volume and pose, with the share of the image each
+route fills.  The steps every ray takes are counted by the numpy restatement (tests/tsdf_raycast_reference.py) on the
+volume downloaded at R = 64, which must equal the device's maps.  `--profile-workload ray_cast` runs three single-view
+and three 16-view calls for rocprofv3.
+
+    python scripts/bench_tsdf.py --ray-cast --reps 9 --warmup 1 --out profiles/tsdf_raycast/bench_tsdf_raycast.json"""
 import argparse
 import ctypes as C
 import importlib
@@ -183,16 +193,74 @@ def mesh_restatement(K, d, e, c):
                 triangles=len(ref.triangles), device_equals_restatement=bool(same))
 
 
+def run_ray_cast(R, K, d, e, c, reps, warmup):
+    res = dict(R=R, colour=True, width=W, height=H)
+    views = e[:POSES]
+    with make(R, 1) as vol:
+        one_call(vol, K, d, e, c)
+        kw = dict(depth_max=6.0, weight_threshold=3.0)
+        full = vol.ray_cast(K, views[0], **kw)
+        again = vol.ray_cast(K, views[0], **kw)
+        res["hits"], res["filled_share"] = full.hits, full.hits / float(W * H)
+        res["same_bits_twice"] = bool(all(getattr(full, n).tobytes() == getattr(again, n).tobytes() for n in ("depth", "vertex_map", "normal_map", "color")))
+        pts = full.vertex_map[full.depth > 0].astype(np.float64)
+        res["max_distance_to_surface"] = float(ex.distance_to_surface(pts).max())
+        res["output_bytes_all_maps"] = int(full.depth.nbytes + full.vertex_map.nbytes + full.normal_map.nbytes + full.color.nbytes)
+        batch = vol.ray_cast_batch(K, views, **kw)
+        res["batch_equals_single"] = bool(batch[0].depth.tobytes() == full.depth.tobytes() and batch[0].color.tobytes() == full.color.tobytes())
+        res["ray_cast_all_maps"] = timed(lambda: vol.ray_cast(K, views[0], **kw), reps, warmup)
+        res["ray_cast_depth_only"] = timed(lambda: vol.ray_cast(K, views[0], vertex_map=False, normal_map=False, color=False, **kw), reps, warmup)
+        res["ray_cast_16_views_one_call"] = timed(lambda: vol.ray_cast_batch(K, views, **kw), reps, warmup)
+        res["ray_cast_16_calls"] = timed(lambda: [vol.ray_cast(K, v, **kw) for v in views], reps, warmup)
+        res["ray_cast_16_views_one_call_depth_only"] = timed(
+            lambda: vol.ray_cast_batch(K, views, vertex_map=False, normal_map=False, color=False, **kw), reps, warmup)
+        # the route without the ray cast: the surface rows down, then up again into a depth image
+        cloud = vol.extract_point_cloud(normals=False)
+        res["surface_points"] = len(cloud.points)
+        img = tp.project_to_depth_image(cloud.points, W, H, K, views[0], depth_scale=1.0, depth_max=6.0)
+        res["projected_filled_share"] = float(np.count_nonzero(img)) / float(W * H)
+        res["extract_point_cloud_no_normals"] = timed(lambda: vol.extract_point_cloud(normals=False), reps, warmup)
+        res["project_to_depth_image"] = timed(lambda: tp.project_to_depth_image(cloud.points, W, H, K, views[0], depth_scale=1.0, depth_max=6.0), reps, warmup)
+        res["extract_then_project"] = timed(lambda: tp.project_to_depth_image(vol.extract_point_cloud(normals=False).points, W, H, K, views[0],
+                                                                              depth_scale=1.0, depth_max=6.0), reps, warmup)
+    return res
+
+
+def ray_cast_restatement(K, d, e, c):
+    """The numpy restatement at R = 64 (8 frames, a 160 x 120 view) on the volume the device integrated: equality and
+    the steps per ray."""
+    import tsdf_raycast_reference as RC
+    import tsdf_reference as T
+    length, R, trunc, origin = ex.volume_settings(64)
+    Ks = tp.PinholeCameraIntrinsic(160, 120, K.fx / 4, K.fy / 4, (K.cx - 1.5) / 4, (K.cy - 1.5) / 4)
+    with make(64, 1) as g:
+        one_call(g, K, d[:CHUNK], e[:CHUNK], c[:CHUNK])
+        vol = T.Volume(length, R, trunc, T.RGB8, origin)
+        tw = g.extract_volume_tsdf().reshape(R, R, R, 2)
+        vol.tsdf[:], vol.weight[:], vol.color[:] = tw[..., 0], tw[..., 1], g.extract_volume_color().reshape(R, R, R, 3)
+        t = time.perf_counter()
+        ref = RC.ray_cast(vol, (Ks.fx, Ks.fy, Ks.cx, Ks.cy), e[0], 160, 120, 0.1, 6.0, 3.0)
+        t1 = time.perf_counter()
+        got = g.ray_cast(Ks, e[0], depth_max=6.0, weight_threshold=3.0)
+    same = (got.hits == ref.hits and got.depth.tobytes() == ref.depth.tobytes() and got.vertex_map.tobytes() == ref.vertex.tobytes()
+            and got.normal_map.tobytes() == ref.normal.tobytes() and got.color.tobytes() == ref.color.tobytes())
+    steps = ref.steps.ravel()
+    return dict(R=64, frames=CHUNK, width=160, height=120, restatement_ms=1e3 * (t1 - t), hits=ref.hits, device_equals_restatement=bool(same),
+                steps_max=int(steps.max()), steps_mean=float(steps.mean()), steps_median=float(np.median(steps)),
+                steps_histogram_by_8=np.bincount(steps // 8).tolist())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=9)
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--out", default=None)
     ap.add_argument("--sizes", type=int, nargs="+", default=[256, 512])
-    ap.add_argument("--profile-workload", choices=["one_call", "calls", "extract", "mesh"], default=None)
+    ap.add_argument("--profile-workload", choices=["one_call", "calls", "extract", "mesh", "ray_cast"], default=None)
     ap.add_argument("--profile-R", type=int, default=512)
     ap.add_argument("--profile-colour", type=int, default=1)
     ap.add_argument("--mesh", action="store_true", help="measure the triangle mesh instead (profiles/tsdf_mesh/)")
+    ap.add_argument("--ray-cast", action="store_true", help="measure the ray cast instead (profiles/tsdf_raycast/)")
     a = ap.parse_args()
     if tp.device_count() < 1:
         sys.exit("bench_tsdf.py needs an MI355X: no HIP device visible")
@@ -200,7 +268,7 @@ def main():
     if a.profile_workload:
         cc = c if a.profile_colour else None
         with make(a.profile_R, a.profile_colour) as vol:
-            for _ in range(3):
+            for rep in range(3):
                 if a.profile_workload == "one_call":
                     one_call(vol, K, d, e, cc)
                 elif a.profile_workload == "calls":
@@ -208,12 +276,29 @@ def main():
                 elif a.profile_workload == "mesh":
                     one_call(vol, K, d[:CHUNK], e[:CHUNK], None if cc is None else cc[:CHUNK])
                     vol.extract_triangle_mesh(vertex_normals=True)
+                elif a.profile_workload == "ray_cast":
+                    if rep == 0:
+                        one_call(vol, K, d, e, cc)
+                    vol.ray_cast(K, e[0], depth_max=6.0, weight_threshold=3.0)
+                    vol.ray_cast_batch(K, e[:POSES], depth_max=6.0, weight_threshold=3.0)
                 else:
                     one_call(vol, K, d[:CHUNK], e[:CHUNK], None if cc is None else cc[:CHUNK])
                     vol.extract_point_cloud()
                     vol.extract_voxel_point_cloud()
         return
     out = dict(workload=dict(width=W, height=H, frames=FRAMES, poses=POSES, chunk=CHUNK, hbm_peak=HBM_PEAK), settings=[])
+    if a.ray_cast:
+        for R in a.sizes:
+            r = run_ray_cast(R, K, d, e, c, a.reps, a.warmup)
+            print(json.dumps(r), flush=True)
+            out["settings"].append(r)
+        out["restatement"] = ray_cast_restatement(K, d, e, c)
+        print(json.dumps(out["restatement"]), flush=True)
+        if a.out:
+            os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+            with open(a.out, "w") as f:
+                json.dump(out, f, indent=1)
+        return
     if a.mesh:
         for R in a.sizes:
             r = run_mesh(R, K, d, e, c, a.reps, a.warmup)

@@ -167,7 +167,8 @@ EXPORTED_SYMBOLS = [
     "teaser_hip_tsdf_volume_default", "teaser_hip_tsdf_create", "teaser_hip_tsdf_destroy", "teaser_hip_tsdf_last_error",
     "teaser_hip_tsdf_reset", "teaser_hip_tsdf_integrate_batch", "teaser_hip_tsdf_extract_point_cloud",
     "teaser_hip_tsdf_extract_voxel_point_cloud", "teaser_hip_tsdf_download", "teaser_hip_tsdf_upload",
-    "teaser_hip_tsdf_extract_triangle_mesh", "teaser_hip_tsdf_mesh_tables",
+    "teaser_hip_tsdf_extract_triangle_mesh", "teaser_hip_tsdf_mesh_tables", "teaser_hip_tsdf_view_default",
+    "teaser_hip_tsdf_ray_cast_views",
     "teaser_hip_icp_odometry_option_default", "teaser_hip_icp_rgbd_odometry_batch",
     "teaser_hip_icp_rgbd_odometry_pyramid_batch",
 ]
@@ -1175,7 +1176,7 @@ from .fgr import (FastGlobalRegistrationOption, registration_fgr_based_on_corres
 from .plane import (segment_plane, segment_plane_batch, plane_trials_batch, set_plane_option,  # noqa: E402
                     get_plane_option)
 from .tsdf import (UniformTSDFVolume, TSDFVolumeColorType, TSDFPointCloud, TSDFTriangleMesh,  # noqa: E402
-                   write_triangle_mesh)
+                   TSDFRayCastResult, write_triangle_mesh)
 from .odometry import (OdometryOption, RGBDOdometryJacobianFromColorTerm,  # noqa: E402
                        RGBDOdometryJacobianFromHybridTerm, RGBDImage, compute_rgbd_odometry,
                        compute_rgbd_odometry_batch, rgbd_odometry_pyramid_batch)
@@ -1221,6 +1222,7 @@ __all__ = ["batched", "FPFHEstimation", "Matcher", "MultiDeviceSolver", "RobustR
            "registration_fgr_based_on_correspondence_batch", "registration_fgr_based_on_feature_matching",
            "fgr_iterations_batch", "set_fgr_option", "get_fgr_option",
            "segment_plane", "segment_plane_batch", "plane_trials_batch", "set_plane_option", "get_plane_option",
-           "UniformTSDFVolume", "TSDFVolumeColorType", "TSDFPointCloud", "TSDFTriangleMesh", "write_triangle_mesh",
+           "UniformTSDFVolume", "TSDFVolumeColorType", "TSDFPointCloud", "TSDFTriangleMesh", "TSDFRayCastResult",
+           "write_triangle_mesh",
            "OdometryOption", "RGBDOdometryJacobianFromColorTerm", "RGBDOdometryJacobianFromHybridTerm", "RGBDImage",
            "compute_rgbd_odometry", "compute_rgbd_odometry_batch", "rgbd_odometry_pyramid_batch"]

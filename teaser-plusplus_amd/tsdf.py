@@ -40,7 +40,14 @@ class TsdfFrameC(C.Structure):
                 ("depth_trunc", C.c_double)]
 
 
-assert C.sizeof(TsdfVolumeC) == 56 and C.sizeof(TsdfFrameC) == 208  # the header asserts the same
+class TsdfViewC(C.Structure):
+    """teaser_tsdf_view_c (include/teaser_hip.h)."""
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("fx", C.c_double), ("fy", C.c_double), ("cx", C.c_double),
+                ("cy", C.c_double), ("extrinsic", C.c_double * 16), ("depth_min", C.c_double), ("depth_max", C.c_double),
+                ("weight_threshold", C.c_double), ("reserved", C.c_int64)]
+
+
+assert C.sizeof(TsdfVolumeC) == 56 and C.sizeof(TsdfFrameC) == 208 and C.sizeof(TsdfViewC) == 200  # as the header asserts
 
 
 def declare(L):
@@ -58,6 +65,9 @@ def declare(L):
     L.teaser_hip_tsdf_upload.argtypes = [_vp, _fp, _dp]
     L.teaser_hip_tsdf_extract_triangle_mesh.argtypes = [_vp, C.c_int64, _dp, _dp, _dp, C.c_int64, _i32p, _i64p, _i64p]
     L.teaser_hip_tsdf_mesh_tables.argtypes = [_i32p, _i8p]
+    L.teaser_hip_tsdf_view_default.argtypes = [C.POINTER(TsdfViewC)]
+    L.teaser_hip_tsdf_ray_cast_views.argtypes = [_vp, C.c_int32, C.POINTER(TsdfViewC), C.POINTER(_fp), C.POINTER(_fp),
+                                                 C.POINTER(_fp), C.POINTER(_fp), _i64p]
 
 
 class TSDFVolumeColorType:
@@ -83,6 +93,31 @@ class TSDFTriangleMesh:
     def __init__(self, vertices, triangles, vertex_colors=None, vertex_normals=None):
         self.vertices, self.triangles = vertices, triangles
         self.vertex_colors, self.vertex_normals = vertex_colors, vertex_normals
+
+
+class TSDFRayCastResult:
+    """What ray_cast returns: ``depth`` (height x width float32, the z-depth in metres, 0 where no surface was met),
+    ``vertex_map`` (world points), ``normal_map`` and ``color`` (height x width x 3 float32; None when not asked for, or
+    for the colour of a volume without a colour type) and ``hits``, the number of pixels that met a surface."""
+
+    def __init__(self, depth, vertex_map, normal_map, color, hits, color_type):
+        self.depth, self.vertex_map, self.normal_map, self.color, self.hits = depth, vertex_map, normal_map, color, hits
+        self._color_type = color_type
+
+    def as_rgbd_image(self):
+        """The frame as compute_rgbd_odometry takes it: the depth as it is (float32 metres) and a float32 intensity,
+        (0.2990 R + 0.5870 G) + 0.1140 B of the colours in float32 -- the weights of "Depth frames" -- or, for a Gray32
+        volume, the value itself."""
+        from .odometry import RGBDImage
+        if self.color is None:
+            raise ValueError("the frame has no colour: the volume has no colour type, or color=False was given")
+        c = self.color
+        if self._color_type == TSDFVolumeColorType.Gray32:
+            gray = np.ascontiguousarray(c[..., 0])
+        else:
+            f = np.float32
+            gray = (f(0.2990) * c[..., 0] + f(0.5870) * c[..., 1]) + f(0.1140) * c[..., 2]
+        return RGBDImage(gray, self.depth, depth_scale=1.0)  # float32 depth is taken as it is: neither parameter is applied
 
 
 def write_triangle_mesh(path, mesh, binary=True):
@@ -297,6 +332,58 @@ class UniformTSDFVolume:
                        C.byref(nt))
         return TSDFTriangleMesh(vert, tri, col, nrm)
 
+    # ---- ray casting --------------------------------------------------------------------------------------------
+    def ray_cast_batch(self, intrinsic, extrinsics, width=None, height=None, depth_min=0.1, depth_max=3.0,
+                       weight_threshold=3.0, vertex_map=True, normal_map=True, color=True):
+        """One TSDFRayCastResult per extrinsic, all views in one call (one launch, one synchronisation).  intrinsic,
+        width, height, depth_min, depth_max, weight_threshold: one for all views or a list with one per view; width
+        and height default to the intrinsic's.  The rules: include/teaser_hip.h, "TSDF ray casting"."""
+        ext = list(extrinsics)
+        b = len(ext)
+        if b == 0:
+            return []
+        intr = _each(intrinsic, b, "intrinsic", _is_intrinsic)
+        K = [_fxfycxcy(k) for k in intr]
+        W, H = _each(width, b, "width", _is_scalar), _each(height, b, "height", _is_scalar)
+        lo, hi = _each(depth_min, b, "depth_min", _is_scalar), _each(depth_max, b, "depth_max", _is_scalar)
+        thr = _each(weight_threshold, b, "weight_threshold", _is_scalar)
+        colored = bool(color) and self.color_type != TSDFVolumeColorType.NoColor
+        views = (TsdfViewC * b)()
+        maps = [[], [], [], []]
+        for k in range(b):
+            v = views[k]
+            self._lib.teaser_hip_tsdf_view_default(C.byref(v))
+            E = np.array(np.eye(4) if ext[k] is None else ext[k], dtype=np.float64)
+            if E.shape != (4, 4):
+                raise ValueError("extrinsic must be a 4 x 4 matrix")
+            w = W[k] if W[k] is not None else getattr(intr[k], "width", None)
+            h = H[k] if H[k] is not None else getattr(intr[k], "height", None)
+            if w is None or h is None:
+                raise ValueError("width and height: the intrinsic carries none, so they must be given")
+            v.width, v.height = int(w), int(h)
+            v.fx, v.fy, v.cx, v.cy = K[k]
+            v.extrinsic[:] = list(E.ravel())
+            v.depth_min, v.depth_max, v.weight_threshold = float(lo[k]), float(hi[k]), float(thr[k])
+            shape = (max(v.height, 0), max(v.width, 0))
+            for m, want in enumerate((True, bool(vertex_map), bool(normal_map), colored)):
+                maps[m].append(np.zeros(shape + ((3,) if m else ()), dtype=np.float32) if want else None)
+
+        def ptrs(arrs):
+            return (_fp * b)(*[None if a is None or a.size == 0 else a.ctypes.data_as(_fp) for a in arrs])
+        hits = (C.c_int64 * b)()
+        self._call(self._lib.teaser_hip_tsdf_ray_cast_views, b, views, ptrs(maps[0]), ptrs(maps[1]), ptrs(maps[2]),
+                   ptrs(maps[3]), hits)
+        return [TSDFRayCastResult(maps[0][k], maps[1][k], maps[2][k], maps[3][k], int(hits[k]), self.color_type)
+                for k in range(b)]
+
+    def ray_cast(self, intrinsic, extrinsic, width=None, height=None, depth_min=0.1, depth_max=3.0, weight_threshold=3.0,
+                 vertex_map=True, normal_map=True, color=True):
+        """The fused model seen from a camera: per pixel the z-depth of the first surface its ray meets (Open3D's
+        VoxelBlockGrid.ray_cast for the dense volume), with the world points, the normals and the colours.
+        ``extrinsic`` is world-to-camera.  A voxel counts as surface only with a weight >= weight_threshold."""
+        return self.ray_cast_batch(intrinsic, [extrinsic], width, height, depth_min, depth_max, weight_threshold, vertex_map,
+                                   normal_map, color)[0]
+
     # ---- the voxels ---------------------------------------------------------------------------------------------
     def extract_volume_tsdf(self):
         """R^3 x 2 float32 (tsdf, weight) in Open3D's voxel order (x R + y) R + z."""
@@ -335,4 +422,5 @@ class UniformTSDFVolume:
         self._call(self._lib.teaser_hip_tsdf_reset)
 
 
-__all__ = ["UniformTSDFVolume", "TSDFVolumeColorType", "TSDFPointCloud", "TSDFTriangleMesh", "write_triangle_mesh"]
+__all__ = ["UniformTSDFVolume", "TSDFVolumeColorType", "TSDFPointCloud", "TSDFTriangleMesh", "TSDFRayCastResult",
+           "write_triangle_mesh"]
