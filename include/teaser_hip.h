@@ -492,6 +492,17 @@ TEASER_HIP_API int32_t teaser_hip_icp_params_default(teaser_icp_params_c* params
 TEASER_HIP_API int32_t teaser_hip_icp_create(int32_t device, teaser_hip_icp** out);
 TEASER_HIP_API int32_t teaser_hip_icp_destroy(teaser_hip_icp* icp);
 TEASER_HIP_API const char* teaser_hip_icp_last_error(const teaser_hip_icp* icp);
+/* DIAGNOSTIC, on no hot path; it never changes a result.  Every handle but the solver's keeps grow-only scratch
+ * buffers between its calls, and a call may assume nothing about what they hold.  teaser_hip_<kind>_fill_scratch
+ * (icp, voxel, features, posegraph, ransac, fgr, plane, tsdf) sets every byte of every device scratch buffer and of
+ * every page-locked staging buffer of the handle, up to the buffer's CAPACITY (not the last call's size), to `byte`
+ * (0 .. 255, anything else is TEASER_HIP_ERR_BAD_ARG), on the handle's stream, and synchronises; the ICP handle's
+ * pageable staging is filled up to its current size.  *bytes_out = the device bytes filled: 0 for a handle that has
+ * served no call, and unchanged by a call that grew no buffer.  It allocates nothing, frees nothing and leaves what is
+ * state alone: options, the fallback count of the last call, the TSDF volume, the stream.  A test that calls it
+ * between two calls and still finds the second equal to its restatement has shown that the second read nothing the
+ * first one left (tests/test_gpu_scratch_independence.py). */
+TEASER_HIP_API int32_t teaser_hip_icp_fill_scratch(teaser_hip_icp* icp, int32_t byte, int64_t* bytes_out);
 /* `batch` independent problems, HOST pointers per problem, borrowed for the call.  init: batch x 16 row-major
  * or NULL (identity for every problem); params: one per problem; out: [batch]; corr: NULL, or per problem NULL or
  * room for n_src[b] x 2 int32 (source index, target index), ascending source index, out[b].n_correspondences
@@ -1499,6 +1510,8 @@ typedef struct teaser_hip_voxel teaser_hip_voxel;
 TEASER_HIP_API int32_t teaser_hip_voxel_create(int32_t device, teaser_hip_voxel** out);
 TEASER_HIP_API int32_t teaser_hip_voxel_destroy(teaser_hip_voxel* voxel);
 TEASER_HIP_API const char* teaser_hip_voxel_last_error(const teaser_hip_voxel* voxel);
+/* DIAGNOSTIC: fills the handle's scratch and staging buffers with `byte`; see teaser_hip_icp_fill_scratch. */
+TEASER_HIP_API int32_t teaser_hip_voxel_fill_scratch(teaser_hip_voxel* voxel, int32_t byte, int64_t* bytes_out);
 /* `batch` independent problems, HOST pointers per problem, borrowed for the call.  pts[b]: n[b] x 3 doubles;
  * voxel_size[b]; out[b]: room for n[b] x 3 doubles; n_out[b] receives the number of voxels.  counts and
  * voxel_of_point: NULL, or per problem NULL or room for n[b] int32.  Problems of mixed sizes share the launches. */
@@ -1531,6 +1544,8 @@ typedef struct teaser_hip_features teaser_hip_features;
 TEASER_HIP_API int32_t teaser_hip_features_create(int32_t device, teaser_hip_features** out);
 TEASER_HIP_API int32_t teaser_hip_features_destroy(teaser_hip_features* features);
 TEASER_HIP_API const char* teaser_hip_features_last_error(const teaser_hip_features* features);
+/* DIAGNOSTIC: fills the handle's scratch and staging buffers with `byte`; see teaser_hip_icp_fill_scratch. */
+TEASER_HIP_API int32_t teaser_hip_features_fill_scratch(teaser_hip_features* features, int32_t byte, int64_t* bytes_out);
 /* DIAGNOSTIC (exists for the tests of the wave splitting; may be removed): the budgets of one wave in bytes, each
  * <= 0 for its default -- list_bytes: neighbour lists of a wave of clouds (4 GiB); part_bytes: partial nearest-
  * neighbour results of a wave of searches (1 GiB).  Small values force a call into many waves; no value changes a result. */
@@ -1711,6 +1726,8 @@ typedef struct teaser_hip_posegraph teaser_hip_posegraph;
 TEASER_HIP_API int32_t teaser_hip_posegraph_create(int32_t device, teaser_hip_posegraph** out);
 TEASER_HIP_API int32_t teaser_hip_posegraph_destroy(teaser_hip_posegraph* posegraph);
 TEASER_HIP_API const char* teaser_hip_posegraph_last_error(const teaser_hip_posegraph* posegraph);
+/* DIAGNOSTIC: fills the handle's scratch and staging buffers with `byte`; see teaser_hip_icp_fill_scratch. */
+TEASER_HIP_API int32_t teaser_hip_posegraph_fill_scratch(teaser_hip_posegraph* posegraph, int32_t byte, int64_t* bytes_out);
 /* The defaults noted beside the fields above. */
 TEASER_HIP_API int32_t teaser_hip_posegraph_option_default(teaser_posegraph_option_c* out);
 /* `batch` graphs as concatenated arrays: n_nodes[b] and poses (16 doubles per node); n_edges[b], edge_source,
@@ -1825,6 +1842,8 @@ typedef struct teaser_hip_ransac teaser_hip_ransac;
 TEASER_HIP_API int32_t teaser_hip_ransac_create(int32_t device, teaser_hip_ransac** out);
 TEASER_HIP_API int32_t teaser_hip_ransac_destroy(teaser_hip_ransac* ransac);
 TEASER_HIP_API const char* teaser_hip_ransac_last_error(const teaser_hip_ransac* ransac);
+/* DIAGNOSTIC: fills the handle's scratch and staging buffers with `byte`; see teaser_hip_icp_fill_scratch. */
+TEASER_HIP_API int32_t teaser_hip_ransac_fill_scratch(teaser_hip_ransac* ransac, int32_t byte, int64_t* bytes_out);
 /* The defaults noted beside the fields above (Open3D's RANSACConvergenceCriteria; both checkers off). */
 TEASER_HIP_API int32_t teaser_hip_ransac_params_default(teaser_ransac_params_c* params);
 /* `batch` independent problems, HOST pointers per problem, borrowed for the call: src[b] n_src[b] x 3, dst[b]
@@ -1939,6 +1958,8 @@ typedef struct teaser_hip_fgr teaser_hip_fgr;
 TEASER_HIP_API int32_t teaser_hip_fgr_create(int32_t device, teaser_hip_fgr** out);
 TEASER_HIP_API int32_t teaser_hip_fgr_destroy(teaser_hip_fgr* fgr);
 TEASER_HIP_API const char* teaser_hip_fgr_last_error(const teaser_hip_fgr* fgr);
+/* DIAGNOSTIC: fills the handle's scratch and staging buffers with `byte`; see teaser_hip_icp_fill_scratch. */
+TEASER_HIP_API int32_t teaser_hip_fgr_fill_scratch(teaser_hip_fgr* fgr, int32_t byte, int64_t* bytes_out);
 /* The defaults noted beside the fields above (Open3D's FastGlobalRegistrationOption). */
 TEASER_HIP_API int32_t teaser_hip_fgr_params_default(teaser_fgr_params_c* params);
 /* `batch` independent problems, HOST pointers per problem, borrowed for the call: src[b] n_src[b] x 3, dst[b]
@@ -2061,6 +2082,8 @@ typedef struct teaser_hip_plane teaser_hip_plane;
 TEASER_HIP_API int32_t teaser_hip_plane_create(int32_t device, teaser_hip_plane** out);
 TEASER_HIP_API int32_t teaser_hip_plane_destroy(teaser_hip_plane* plane);
 TEASER_HIP_API const char* teaser_hip_plane_last_error(const teaser_hip_plane* plane);
+/* DIAGNOSTIC: fills the handle's scratch and staging buffers with `byte`; see teaser_hip_icp_fill_scratch. */
+TEASER_HIP_API int32_t teaser_hip_plane_fill_scratch(teaser_hip_plane* plane, int32_t byte, int64_t* bytes_out);
 /* The defaults noted beside the fields above (Open3D's segment_plane). */
 TEASER_HIP_API int32_t teaser_hip_plane_params_default(teaser_plane_params_c* params);
 /* `batch` independent problems, HOST pointers per problem, borrowed for the call: points[b] n[b] x 3; params and out:
@@ -2246,6 +2269,8 @@ TEASER_HIP_API int32_t teaser_hip_tsdf_volume_default(teaser_tsdf_volume_c* volu
 TEASER_HIP_API int32_t teaser_hip_tsdf_create(const teaser_tsdf_volume_c* volume, int32_t device, teaser_hip_tsdf** out);
 TEASER_HIP_API int32_t teaser_hip_tsdf_destroy(teaser_hip_tsdf* tsdf);
 TEASER_HIP_API const char* teaser_hip_tsdf_last_error(const teaser_hip_tsdf* tsdf);
+/* DIAGNOSTIC: fills the handle's scratch and staging buffers with `byte`; see teaser_hip_icp_fill_scratch. */
+TEASER_HIP_API int32_t teaser_hip_tsdf_fill_scratch(teaser_hip_tsdf* tsdf, int32_t byte, int64_t* bytes_out);
 /* Every voxel back to the state after create. */
 TEASER_HIP_API int32_t teaser_hip_tsdf_reset(teaser_hip_tsdf* tsdf);
 TEASER_HIP_API int32_t teaser_hip_tsdf_integrate_batch(teaser_hip_tsdf* tsdf, int32_t n_frames,

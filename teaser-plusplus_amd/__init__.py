@@ -131,6 +131,7 @@ EXPORTED_SYMBOLS = [
     "teaser_hip_comm_shard", "teaser_hip_comm_unique_id", "teaser_hip_comm_create", "teaser_hip_comm_destroy",
     "teaser_hip_comm_gather_solutions", "teaser_hip_comm_gather_indices", "teaser_hip_comm_last_error",
     "teaser_hip_icp_params_default", "teaser_hip_icp_create", "teaser_hip_icp_destroy", "teaser_hip_icp_last_error",
+    "teaser_hip_icp_fill_scratch",
     "teaser_hip_icp_batch", "teaser_hip_icp_solve", "teaser_hip_icp_estimation_default", "teaser_hip_icp_batch_ex",
     "teaser_hip_icp_solve_ex", "teaser_hip_icp_batch_cov", "teaser_hip_icp_solve_cov",
     "teaser_hip_icp_covariances_batch", "teaser_hip_icp_normals_batch", "teaser_hip_icp_batch_auto",
@@ -146,25 +147,32 @@ EXPORTED_SYMBOLS = [
     "teaser_hip_icp_color_default", "teaser_hip_icp_batch_color", "teaser_hip_icp_solve_color",
     "teaser_hip_icp_color_gradients_batch",
     "teaser_hip_voxel_create", "teaser_hip_voxel_destroy", "teaser_hip_voxel_last_error",
+    "teaser_hip_voxel_fill_scratch",
     "teaser_hip_voxel_down_sample_batch", "teaser_hip_voxel_down_sample",
     "teaser_hip_features_create", "teaser_hip_features_destroy", "teaser_hip_features_last_error",
+    "teaser_hip_features_fill_scratch",
     "teaser_hip_features_set_budgets", "teaser_hip_features_fpfh_batch", "teaser_hip_features_match_batch",
     "teaser_hip_features_correspondences_batch", "teaser_hip_features_knn_batch",
     "teaser_hip_features_match_knn_batch", "teaser_hip_features_correspondences_knn_batch",
     "teaser_hip_features_tuple_test_batch",
     "teaser_hip_posegraph_create", "teaser_hip_posegraph_destroy", "teaser_hip_posegraph_last_error",
+    "teaser_hip_posegraph_fill_scratch",
     "teaser_hip_posegraph_option_default", "teaser_hip_posegraph_optimize_batch", "teaser_hip_posegraph_optimize",
     "teaser_hip_posegraph_linearize_batch", "teaser_hip_posegraph_linearize",
     "teaser_hip_ransac_create", "teaser_hip_ransac_destroy", "teaser_hip_ransac_last_error",
+    "teaser_hip_ransac_fill_scratch",
     "teaser_hip_ransac_params_default", "teaser_hip_ransac_correspondence_batch", "teaser_hip_ransac_correspondence",
     "teaser_hip_ransac_set_option", "teaser_hip_ransac_get_option", "teaser_hip_ransac_trials_batch",
-    "teaser_hip_fgr_create", "teaser_hip_fgr_destroy", "teaser_hip_fgr_last_error", "teaser_hip_fgr_params_default",
+    "teaser_hip_fgr_create", "teaser_hip_fgr_destroy", "teaser_hip_fgr_last_error",
+    "teaser_hip_fgr_fill_scratch", "teaser_hip_fgr_params_default",
     "teaser_hip_fgr_correspondence_batch", "teaser_hip_fgr_correspondence", "teaser_hip_fgr_set_option",
     "teaser_hip_fgr_get_option", "teaser_hip_fgr_iterations_batch",
     "teaser_hip_plane_create", "teaser_hip_plane_destroy", "teaser_hip_plane_last_error",
+    "teaser_hip_plane_fill_scratch",
     "teaser_hip_plane_params_default", "teaser_hip_plane_segment_batch", "teaser_hip_plane_segment",
     "teaser_hip_plane_set_option", "teaser_hip_plane_get_option", "teaser_hip_plane_trials_batch",
     "teaser_hip_tsdf_volume_default", "teaser_hip_tsdf_create", "teaser_hip_tsdf_destroy", "teaser_hip_tsdf_last_error",
+    "teaser_hip_tsdf_fill_scratch",
     "teaser_hip_tsdf_reset", "teaser_hip_tsdf_integrate_batch", "teaser_hip_tsdf_extract_point_cloud",
     "teaser_hip_tsdf_extract_voxel_point_cloud", "teaser_hip_tsdf_download", "teaser_hip_tsdf_upload",
     "teaser_hip_tsdf_extract_triangle_mesh", "teaser_hip_tsdf_mesh_tables", "teaser_hip_tsdf_view_default",
@@ -1181,7 +1189,22 @@ from .odometry import (OdometryOption, RGBDOdometryJacobianFromColorTerm,  # noq
                        RGBDOdometryJacobianFromHybridTerm, RGBDImage, compute_rgbd_odometry,
                        compute_rgbd_odometry_batch, rgbd_odometry_pyramid_batch)
 
-__all__ = ["batched", "FPFHEstimation", "Matcher", "MultiDeviceSolver", "RobustRegistrationSolver", "RegistrationSolution", "RotationEstimationAlgorithm",
+SCRATCH_KINDS = ("icp", "voxel", "features", "posegraph", "ransac", "fgr", "plane")
+
+
+def fill_scratch(kind, byte, device=-1):
+    """DIAGNOSTIC (teaser_hip_<kind>_fill_scratch): sets every byte of the scratch and staging buffers of the cached
+    handle of `kind` (one of SCRATCH_KINDS) on `device` to `byte` (0 .. 255) and returns the device bytes filled.  No
+    result depends on it.  A TSDF volume has its own: UniformTSDFVolume.fill_scratch."""
+    import importlib
+    from . import _handles
+    if kind not in SCRATCH_KINDS:
+        raise ValueError("kind must be one of %s" % (SCRATCH_KINDS,))
+    return _handles._fill_scratch(importlib.import_module("." + kind, __name__)._cache, byte, device)
+
+
+__all__ = ["fill_scratch", "SCRATCH_KINDS",
+           "batched", "FPFHEstimation", "Matcher", "MultiDeviceSolver", "RobustRegistrationSolver", "RegistrationSolution", "RotationEstimationAlgorithm",
            "InlierSelectionMode", "InlierGraphFormulation", "TeaserHipError", "synth_problem",
            "device_count", "build", "lib", "LIB_PATH", "EXPORTED_SYMBOLS", "certifier_warmup", "PinnedArray",
            "ICPConvergenceCriteria", "TransformationEstimationPointToPoint", "RegistrationResult", "registration_icp",

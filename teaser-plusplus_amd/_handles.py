@@ -129,6 +129,14 @@ def _set_option(cache, name, value, device):
     h.call(getattr(h._lib, cache.prefix + "_set_option"), name.encode(), int(value))
 
 
+def _fill_scratch(cache, byte, device):
+    """prefix_fill_scratch(byte) on the cached handle of `device`; the device bytes it filled."""
+    h = cache.get(device)
+    filled = C.c_int64()
+    h.call(getattr(h._lib, cache.prefix + "_fill_scratch"), int(byte), C.byref(filled))
+    return filled.value
+
+
 def _get_option(cache, name, device):
     """prefix_get_option(name) on the cached handle of `device`."""
     h = cache.get(device)

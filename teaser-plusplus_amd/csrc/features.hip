@@ -606,6 +606,14 @@ int32_t teaser_hip_features_destroy(teaser_hip_features* h) { return close_handl
 
 const char* teaser_hip_features_last_error(const teaser_hip_features* h) { return h ? h->err.c_str() : ""; }
 
+int32_t teaser_hip_features_fill_scratch(teaser_hip_features* h, int32_t byte, int64_t* bytes_out) {
+  if (!h) return TEASER_HIP_ERR_BAD_ARG;
+  ScratchSpan spans[B_COUNT_OF_BUFS + H_COUNT_OF_BUFS];
+  for (int k = 0; k < B_COUNT_OF_BUFS; ++k) spans[k] = span_of(h->buf[k]);
+  for (int k = 0; k < H_COUNT_OF_BUFS; ++k) spans[B_COUNT_OF_BUFS + k] = span_of(h->host[k]);
+  return fill_scratch(h, byte, spans, B_COUNT_OF_BUFS + H_COUNT_OF_BUFS, bytes_out);
+}
+
 int32_t teaser_hip_features_set_budgets(teaser_hip_features* h, int64_t list_bytes, int64_t part_bytes) {
   if (!h) return TEASER_HIP_ERR_BAD_ARG;
   h->list_budget = list_bytes > 0 ? list_bytes : kFeatListBudgetBytes;

@@ -230,6 +230,13 @@ int32_t teaser_hip_fgr_create(int32_t device, teaser_hip_fgr** out) { return ope
 int32_t teaser_hip_fgr_destroy(teaser_hip_fgr* h) { return close_handle(h); }
 const char* teaser_hip_fgr_last_error(const teaser_hip_fgr* h) { return h ? h->err.c_str() : ""; }
 
+int32_t teaser_hip_fgr_fill_scratch(teaser_hip_fgr* h, int32_t byte, int64_t* bytes_out) {
+  if (!h) return TEASER_HIP_ERR_BAD_ARG;
+  const ScratchSpan spans[] = {span_of(h->in),  span_of(h->pairs), span_of(h->work), span_of(h->state),
+                               span_of(h->log), span_of(h->stage), span_of(h->back)};
+  return fill_scratch(h, byte, spans, 7, bytes_out);
+}
+
 int32_t teaser_hip_fgr_params_default(teaser_fgr_params_c* params) {
   if (!params) return TEASER_HIP_ERR_BAD_ARG;
   params_default(params);

@@ -1,7 +1,8 @@
 // host_common.h -- what the host sides of the handles share: the members and the error reporting every handle has
 // (HandleBase), the create and destroy sequences (open_handle, close_handle), the one refusal every batched call words
 // the same way (over_batch_limit), the finiteness checks and, for every handle but the solver's, the grow-only buffers
-// (DevBuf, HostBuf), which free themselves when their handle goes.  The cloud calls of the ICP handle build on it in
+// (DevBuf, HostBuf), which free themselves when their handle goes, and the diagnostic fill of those buffers
+// (fill_scratch, behind every teaser_hip_*_fill_scratch).  The cloud calls of the ICP handle build on it in
 // icp_host.h, the packed calls of the RANSAC, plane, FGR and pose-graph handles in packed_call.h.  solver.hip derives its
 // handle from HandleBase and opens it with open_handle, but keeps buffer types of its own under other names (SolverBuf,
 // PinnedBuf: another growth rule, a hipError_t answer with a retry at the exact size, and a view mode) and its own
@@ -10,6 +11,7 @@
 
 #include <hip/hip_runtime.h>
 #include <math.h>
+#include <string.h>
 
 #include <algorithm>
 #include <string>
@@ -92,6 +94,42 @@ inline bool finite_all(const double* p, int64_t n) {
   return true;
 }
 inline bool finite_points(const double* p, int64_t n) { return finite_all(p, 3 * n); }
+
+// One piece of a handle's scratch: `bytes` at p, in device memory or in host memory (page-locked or a std::vector).
+struct ScratchSpan {
+  void* p;
+  size_t bytes;
+  bool on_device;
+};
+inline ScratchSpan span_of(const DevBuf& b) { return {b.p, b.cap, true}; }
+inline ScratchSpan span_of(const HostBuf& b) { return {b.p, b.cap, false}; }
+
+// teaser_hip_*_fill_scratch (diagnostic): sets every byte of the `count` spans to `byte` -- the device ones on the
+// handle's stream, the host ones once the stream has drained, so that no copy still in flight reads or writes them --
+// synchronises, and reports the device bytes.  Allocates and frees nothing; a span without memory counts 0.
+inline int32_t fill_scratch(HandleBase* h, int32_t byte, const ScratchSpan* spans, int count, int64_t* bytes_out) {
+  if (!h) return TEASER_HIP_ERR_BAD_ARG;
+  h->err.clear();
+  if (byte < 0 || byte > 255) return fail(h, TEASER_HIP_ERR_BAD_ARG, "byte must lie in 0..255");
+  if (!bytes_out) return fail(h, TEASER_HIP_ERR_BAD_ARG, "bytes_out must not be NULL");
+  *bytes_out = 0;
+  FCHK(h, hipSetDevice(h->device), "hipSetDevice");
+  FCHK(h, hipStreamSynchronize(h->stream), "hipStreamSynchronize (fill_scratch)");
+  int64_t total = 0;
+  for (int k = 0; k < count; ++k) {
+    const ScratchSpan& s = spans[k];
+    if (!s.p || !s.bytes) continue;
+    if (s.on_device) {
+      FCHK(h, hipMemsetAsync(s.p, byte, s.bytes, h->stream), "hipMemsetAsync (fill_scratch)");
+      total += (int64_t)s.bytes;
+    } else {
+      memset(s.p, byte, s.bytes);
+    }
+  }
+  FCHK(h, hipStreamSynchronize(h->stream), "hipStreamSynchronize (fill_scratch)");
+  *bytes_out = total;
+  return TEASER_HIP_OK;
+}
 
 // teaser_hip_*_create: a handle of type H on `device` (< 0: the current device) with a non-blocking stream.
 template <class H>

@@ -158,6 +158,19 @@ int32_t teaser_hip_icp_destroy(teaser_hip_icp* h) { return close_handle(h); }
 
 const char* teaser_hip_icp_last_error(const teaser_hip_icp* h) { return h ? h->err.c_str() : ""; }
 
+int32_t teaser_hip_icp_fill_scratch(teaser_hip_icp* h, int32_t byte, int64_t* bytes_out) {
+  if (!h) return TEASER_HIP_ERR_BAD_ARG;
+  // every device buffer up to its capacity; the host staging up to its current size.  h_live's four bytes are staging
+  // too: every iteration group copies the live count into them before it reads them.
+  ScratchSpan spans[B_COUNT + 4];
+  for (int k = 0; k < B_COUNT; ++k) spans[k] = span_of(h->buf[k]);
+  spans[B_COUNT] = {h->stage.data(), sizeof(double) * h->stage.size(), false};
+  spans[B_COUNT + 1] = {h->back.data(), sizeof(double) * h->back.size(), false};
+  spans[B_COUNT + 2] = {h->cstage.data(), sizeof(double) * h->cstage.size(), false};
+  spans[B_COUNT + 3] = {h->h_live, sizeof(int32_t), false};
+  return fill_scratch(h, byte, spans, B_COUNT + 4, bytes_out);
+}
+
 int32_t teaser_hip_icp_estimation_default(teaser_icp_estimation_c* est) {
   if (!est) return TEASER_HIP_ERR_BAD_ARG;
   est->method = kIcpMethodPoint;

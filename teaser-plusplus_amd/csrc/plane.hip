@@ -413,6 +413,12 @@ int32_t teaser_hip_plane_create(int32_t device, teaser_hip_plane** out) { return
 int32_t teaser_hip_plane_destroy(teaser_hip_plane* h) { return close_handle(h); }
 const char* teaser_hip_plane_last_error(const teaser_hip_plane* h) { return h ? h->err.c_str() : ""; }
 
+int32_t teaser_hip_plane_fill_scratch(teaser_hip_plane* h, int32_t byte, int64_t* bytes_out) {
+  if (!h) return TEASER_HIP_ERR_BAD_ARG;
+  const ScratchSpan spans[] = {span_of(h->in), span_of(h->work), span_of(h->part), span_of(h->fin), span_of(h->stage)};
+  return fill_scratch(h, byte, spans, 5, bytes_out);
+}
+
 int32_t teaser_hip_plane_params_default(teaser_plane_params_c* params) {
   if (!params) return TEASER_HIP_ERR_BAD_ARG;
   params_default(params);

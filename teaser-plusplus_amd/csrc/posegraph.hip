@@ -362,6 +362,12 @@ int32_t teaser_hip_posegraph_create(int32_t device, teaser_hip_posegraph** out) 
 int32_t teaser_hip_posegraph_destroy(teaser_hip_posegraph* h) { return close_handle(h); }
 const char* teaser_hip_posegraph_last_error(const teaser_hip_posegraph* h) { return h ? h->err.c_str() : ""; }
 
+int32_t teaser_hip_posegraph_fill_scratch(teaser_hip_posegraph* h, int32_t byte, int64_t* bytes_out) {
+  if (!h) return TEASER_HIP_ERR_BAD_ARG;
+  const ScratchSpan spans[] = {span_of(h->in), span_of(h->work), span_of(h->dense), span_of(h->out)};
+  return fill_scratch(h, byte, spans, 4, bytes_out);
+}
+
 int32_t teaser_hip_posegraph_option_default(teaser_posegraph_option_c* out) {
   if (!out) return TEASER_HIP_ERR_BAD_ARG;
   option_default(out);

@@ -409,6 +409,12 @@ int32_t teaser_hip_ransac_create(int32_t device, teaser_hip_ransac** out) { retu
 int32_t teaser_hip_ransac_destroy(teaser_hip_ransac* h) { return close_handle(h); }
 const char* teaser_hip_ransac_last_error(const teaser_hip_ransac* h) { return h ? h->err.c_str() : ""; }
 
+int32_t teaser_hip_ransac_fill_scratch(teaser_hip_ransac* h, int32_t byte, int64_t* bytes_out) {
+  if (!h) return TEASER_HIP_ERR_BAD_ARG;
+  const ScratchSpan spans[] = {span_of(h->in), span_of(h->pairs), span_of(h->work), span_of(h->ctl)};
+  return fill_scratch(h, byte, spans, 4, bytes_out);
+}
+
 int32_t teaser_hip_ransac_params_default(teaser_ransac_params_c* params) {
   if (!params) return TEASER_HIP_ERR_BAD_ARG;
   params_default(params);

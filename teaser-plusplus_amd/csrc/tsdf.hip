@@ -238,6 +238,14 @@ int32_t teaser_hip_tsdf_create(const teaser_tsdf_volume_c* vol, int32_t device, 
 int32_t teaser_hip_tsdf_destroy(teaser_hip_tsdf* h) { return close_handle(h); }
 const char* teaser_hip_tsdf_last_error(const teaser_hip_tsdf* h) { return h ? h->err.c_str() : g_create_error.c_str(); }
 
+int32_t teaser_hip_tsdf_fill_scratch(teaser_hip_tsdf* h, int32_t byte, int64_t* bytes_out) {
+  if (!h) return TEASER_HIP_ERR_BAD_ARG;
+  // not h->volume: the volume is the handle's state
+  const ScratchSpan spans[] = {span_of(h->in),   span_of(h->work),  span_of(h->out),
+                               span_of(h->mesh), span_of(h->stage), span_of(h->back)};
+  return fill_scratch(h, byte, spans, 6, bytes_out);
+}
+
 int32_t teaser_hip_tsdf_reset(teaser_hip_tsdf* h) {
   if (!h) return TEASER_HIP_ERR_BAD_ARG;
   h->err.clear();

@@ -101,6 +101,13 @@ int32_t teaser_hip_voxel_destroy(teaser_hip_voxel* h) { return close_handle(h); 
 
 const char* teaser_hip_voxel_last_error(const teaser_hip_voxel* h) { return h ? h->err.c_str() : ""; }
 
+int32_t teaser_hip_voxel_fill_scratch(teaser_hip_voxel* h, int32_t byte, int64_t* bytes_out) {
+  if (!h) return TEASER_HIP_ERR_BAD_ARG;
+  ScratchSpan spans[B_COUNT_OF_BUFS];
+  for (int k = 0; k < B_COUNT_OF_BUFS; ++k) spans[k] = span_of(h->buf[k]);
+  return fill_scratch(h, byte, spans, B_COUNT_OF_BUFS, bytes_out);
+}
+
 int32_t teaser_hip_voxel_down_sample_batch(teaser_hip_voxel* h, int32_t batch, const double* const* pts,
                                            const int32_t* n, const double* voxel_size, double* const* out,
                                            int64_t* n_out, int32_t* const* counts, int32_t* const* voxel_of_point) {

@@ -28,6 +28,7 @@ def declare(L):
     L.teaser_hip_features_destroy.argtypes = [_vp]
     L.teaser_hip_features_last_error.argtypes = [_vp]
     L.teaser_hip_features_last_error.restype = C.c_char_p
+    L.teaser_hip_features_fill_scratch.argtypes = [_vp, C.c_int32, C.POINTER(C.c_int64)]
     L.teaser_hip_features_set_budgets.argtypes = [_vp, C.c_int64, C.c_int64]
     L.teaser_hip_features_fpfh_batch.argtypes = [_vp, C.c_int32, C.POINTER(_fp), _ip, _dp, _dp, C.POINTER(_fp),
                                                  C.POINTER(_fp)]

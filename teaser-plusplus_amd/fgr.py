@@ -37,6 +37,7 @@ def declare(L):
     L.teaser_hip_fgr_destroy.argtypes = [_vp]
     L.teaser_hip_fgr_last_error.argtypes = [_vp]
     L.teaser_hip_fgr_last_error.restype = C.c_char_p
+    L.teaser_hip_fgr_fill_scratch.argtypes = [_vp, C.c_int32, C.POINTER(C.c_int64)]
     L.teaser_hip_fgr_params_default.argtypes = [C.POINTER(FgrParamsC)]
     problems = [C.POINTER(_dp), _ip, C.POINTER(_dp), _ip, C.POINTER(_ip), _ip, C.POINTER(FgrParamsC)]
     L.teaser_hip_fgr_correspondence_batch.argtypes = [_vp, C.c_int32] + problems + [C.POINTER(FgrResultC)]

@@ -57,6 +57,7 @@ def declare(L):
     L.teaser_hip_icp_destroy.argtypes = [_vp]
     L.teaser_hip_icp_last_error.argtypes = [_vp]
     L.teaser_hip_icp_last_error.restype = C.c_char_p
+    L.teaser_hip_icp_fill_scratch.argtypes = [_vp, C.c_int32, C.POINTER(C.c_int64)]
     L.teaser_hip_icp_batch.argtypes = [_vp, C.c_int32, C.POINTER(_dp), _ip, C.POINTER(_dp), _ip, _dp,
                                        C.POINTER(IcpParamsC), C.POINTER(IcpResultC), C.POINTER(_ip)]
     L.teaser_hip_icp_solve.argtypes = [_vp, _dp, C.c_int32, _dp, C.c_int32, _dp, C.POINTER(IcpParamsC),

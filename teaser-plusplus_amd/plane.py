@@ -35,6 +35,7 @@ def declare(L):
     L.teaser_hip_plane_destroy.argtypes = [_vp]
     L.teaser_hip_plane_last_error.argtypes = [_vp]
     L.teaser_hip_plane_last_error.restype = C.c_char_p
+    L.teaser_hip_plane_fill_scratch.argtypes = [_vp, C.c_int32, C.POINTER(C.c_int64)]
     L.teaser_hip_plane_params_default.argtypes = [C.POINTER(PlaneParamsC)]
     problems = [C.POINTER(_dp), _ip, C.POINTER(PlaneParamsC)]
     L.teaser_hip_plane_segment_batch.argtypes = [_vp, C.c_int32] + problems + [C.POINTER(PlaneResultC), C.POINTER(_ip),

@@ -43,6 +43,7 @@ def declare(L):
     L.teaser_hip_posegraph_destroy.argtypes = [_vp]
     L.teaser_hip_posegraph_last_error.argtypes = [_vp]
     L.teaser_hip_posegraph_last_error.restype = C.c_char_p
+    L.teaser_hip_posegraph_fill_scratch.argtypes = [_vp, C.c_int32, C.POINTER(C.c_int64)]
     L.teaser_hip_posegraph_option_default.argtypes = [C.POINTER(PoseGraphOptionC)]
     graph = [_ip, _dp, _ip, _ip, _ip, _dp, _dp, _u8p, C.POINTER(PoseGraphOptionC)]
     one = [C.c_int32, _dp, C.c_int32, _ip, _ip, _dp, _dp, _u8p, C.POINTER(PoseGraphOptionC)]

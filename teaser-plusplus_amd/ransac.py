@@ -39,6 +39,7 @@ def declare(L):
     L.teaser_hip_ransac_destroy.argtypes = [_vp]
     L.teaser_hip_ransac_last_error.argtypes = [_vp]
     L.teaser_hip_ransac_last_error.restype = C.c_char_p
+    L.teaser_hip_ransac_fill_scratch.argtypes = [_vp, C.c_int32, C.POINTER(C.c_int64)]
     L.teaser_hip_ransac_params_default.argtypes = [C.POINTER(RansacParamsC)]
     problems = [C.POINTER(_dp), _ip, C.POINTER(_dp), _ip, C.POINTER(_ip), _ip, C.POINTER(RansacParamsC)]
     L.teaser_hip_ransac_correspondence_batch.argtypes = [_vp, C.c_int32] + problems + [C.POINTER(RansacResultC),

@@ -57,6 +57,7 @@ def declare(L):
     L.teaser_hip_tsdf_destroy.argtypes = [_vp]
     L.teaser_hip_tsdf_last_error.argtypes = [_vp]
     L.teaser_hip_tsdf_last_error.restype = C.c_char_p
+    L.teaser_hip_tsdf_fill_scratch.argtypes = [_vp, C.c_int32, C.POINTER(C.c_int64)]
     L.teaser_hip_tsdf_reset.argtypes = [_vp]
     L.teaser_hip_tsdf_integrate_batch.argtypes = [_vp, C.c_int32, C.POINTER(TsdfFrameC), C.POINTER(_vp), C.POINTER(_vp)]
     L.teaser_hip_tsdf_extract_point_cloud.argtypes = [_vp, C.c_int64, _dp, _dp, _dp, _i64p]
@@ -203,6 +204,13 @@ class UniformTSDFVolume:
             err = self._lib.teaser_hip_tsdf_last_error(self._h).decode() if rc != 0 else ""
         if rc != 0:
             raise TeaserHipError(rc, err)
+
+    def fill_scratch(self, byte):
+        """DIAGNOSTIC (teaser_hip_tsdf_fill_scratch): sets every byte of the handle's scratch and staging buffers to
+        `byte` (0 .. 255) and returns the device bytes filled.  The volume itself is state and is left alone."""
+        filled = C.c_int64()
+        self._call(self._lib.teaser_hip_tsdf_fill_scratch, int(byte), C.byref(filled))
+        return filled.value
 
     def close(self):
         """Frees the volume; the object is unusable afterwards."""

@@ -22,6 +22,7 @@ def declare(L):
     L.teaser_hip_voxel_destroy.argtypes = [_vp]
     L.teaser_hip_voxel_last_error.argtypes = [_vp]
     L.teaser_hip_voxel_last_error.restype = C.c_char_p
+    L.teaser_hip_voxel_fill_scratch.argtypes = [_vp, C.c_int32, C.POINTER(C.c_int64)]
     L.teaser_hip_voxel_down_sample_batch.argtypes = [_vp, C.c_int32, C.POINTER(_dp), _ip, _dp, C.POINTER(_dp),
                                                      _i64p, C.POINTER(_ip), C.POINTER(_ip)]
     L.teaser_hip_voxel_down_sample.argtypes = [_vp, _dp, C.c_int32, C.c_double, _dp, _i64p, _ip, _ip]

@@ -28,6 +28,27 @@ def test_every_declared_entry_point_is_exported():
     assert L.teaser_hip_abi_version() == 1
 
 
+def test_fill_scratch_is_declared_for_every_handle_kind_but_the_solvers():
+    """The diagnostic teaser_hip_<kind>_fill_scratch(handle, int32 byte, int64* bytes_out): exported, declared in the
+    header with exactly these arguments, and given its ctypes signature where the kind's other entries get theirs."""
+    kinds = ["icp", "voxel", "features", "posegraph", "ransac", "fgr", "plane", "tsdf"]
+    assert sorted(tp.SCRATCH_KINDS + ("tsdf",)) == sorted(kinds)  # a TSDF volume is its own handle: UniformTSDFVolume.fill_scratch
+    text = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "teaser_hip.h")).read(), flags=re.S)
+    L = tp.lib()
+    for kind in kinds:
+        name = "teaser_hip_%s_fill_scratch" % kind
+        assert name in tp.EXPORTED_SYMBOLS
+        assert re.search(r"TEASER_HIP_API int32_t %s\(teaser_hip_%s\* \w+, int32_t byte, int64_t\* bytes_out\);" % (name, kind),
+                         text), name
+        fn = getattr(L, name)
+        assert fn.argtypes == [C.c_void_p, C.c_int32, C.POINTER(C.c_int64)], name
+        filled = C.c_int64(7)
+        assert fn(None, 0, C.byref(filled)) != 0 and filled.value == 7  # no handle: refused, nothing written
+    assert callable(tp.fill_scratch) and callable(tp.UniformTSDFVolume.fill_scratch)
+    with pytest.raises(ValueError):
+        tp.fill_scratch("solver", 0)
+
+
 def test_no_device_is_a_loud_error():
     if tp.device_count() > 0:
         return  # on the GPU box the parity tests cover creation
