@@ -1,8 +1,9 @@
 #!/usr/bin/env python3
 """Static instruction statistics of the K1 kernel from the compiler's own assembly (CPU only, no GPU):
   hipcc --offload-arch=gfx950 <the Makefile's flags for kernels_graph.o> --save-temps -c csrc/kernels_graph.hip
-For EVERY instantiation of tim_graph_mfma3_kernel<PIPE, PLAIN, OCC, CHUNKS> in the object (one in the product build,
-twelve with --lab = -DTEASER_K1_LAB): registers, scratch, LDS, occupancy, and per BASIC BLOCK the instruction mix
+For EVERY instantiation of tim_graph_mfma3_kernel<PIPE, PLAIN, OCC, CHUNKS, LOWER, UW3> in the object (two in the product
+build: LOWER = 1 stores the bitmap's lower triangle, LOWER = 0 leaves it out; more with --lab = -DTEASER_K1_LAB, among
+them UW3 = 1, the three-MFMA formulation): registers, scratch, LDS, occupancy, and per BASIC BLOCK the instruction mix
 (VALU / MFMA / SALU / LDS / VMEM / waits).  The block with the most MFMAs is the steady-state column-tile loop body:
 one iteration covers one 64 x 64 column tile of a wave = 4096 pairs, so VALU per 1024 pairs = VALU / 4.
 usage: k1_isa_stats.py [--lab] [--brief] [<file.s>]"""
@@ -16,6 +17,7 @@ import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PREFIX = "_ZN4thip22tim_graph_mfma3_kernelI"
+MFMA_PER_TILE = 8  # two chained MFMAs per 32 x 32 quarter tile
 
 
 def assembly(lab):
@@ -49,8 +51,8 @@ def classify(op):
 
 
 def template_args(sym):
-    m = re.match(re.escape(PREFIX) + r"Lb([01])ELb([01])ELi(\d+)ELi(\d+)EE", sym)
-    return "<PIPE=%s, PLAIN=%s, OCC=%s, CHUNKS=%s>" % m.groups() if m else sym
+    m = re.match(re.escape(PREFIX) + r"Lb([01])ELb([01])ELi(\d+)ELi(\d+)ELb([01])ELb([01])EE", sym)
+    return "<PIPE=%s, PLAIN=%s, OCC=%s, CHUNKS=%s, LOWER=%s, UW3=%s>" % m.groups() if m else sym
 
 
 def one_kernel(lines, start):
@@ -89,7 +91,7 @@ def one_kernel(lines, start):
     for rank, (nm, c) in enumerate(loops):
         mix = {k: v for k, v in c.items() if not k.startswith("ops:")}
         top = sorted(((k[4:], v) for k, v in c.items() if k.startswith("ops:")), key=lambda kv: -kv[1])[:14]
-        per = 4.0 * max(1, mix.get("mfma", 16) // 16)  # (a block that holds two tiles' MFMAs covers 8192 pairs)
+        per = 4.0 * max(1, mix.get("mfma", MFMA_PER_TILE) // 16)  # (a block with two tiles' MFMAs, 16 or 24, covers 8192 pairs)
         out["loop_body_%d" % rank] = {"label": nm, "mix": mix, "valu_per_1024_pairs": round(mix.get("valu", 0) / per, 1),
                                       "mfma_per_1024_pairs": round(mix.get("mfma", 0) / per, 2), "most_frequent": dict(top)}
     return out

@@ -4,18 +4,18 @@ Writes gpurun_ab/kernels_graph_<name>.hip = csrc/kernels_graph.hip with one ingr
 Variants other than `old` / `touch` produce WRONG bits, so their outputs are forced to zero and their flags dropped
 behind an opaque use (empty graph, no worklist overflow, no fallback: the events time the kernel alone).
   zero      control: outputs zeroed, nothing removed
-  nomfma    no MFMAs (accumulators defined by an empty asm)        halfmfma  the u chain's first link and the w MFMA only
+  nomfma    no MFMAs (accumulators defined by an empty asm)        halfmfma  the chain's first link (X) only
   noepi     no epilogue (sign collection, min |d|, flags)           nofinish  no word assembly / transposes / LDS parking
   noload    no column-operand loads in the loop (operands of the first tile reused)
   sameload  the loop's loads always fetch the wave's first column tile
   load32    buffer_load_dword instead of dwordx4 (same instruction count, a quarter of the bytes)
   ldsload   the loop's operands come from LDS (ds_read_b128 of a constant buffer) instead of global memory
   touch     (correct results) one extra dword load per 64-byte line of the half tile after the next, as a prefetch
-  seq3/seq4 (correct results) ONE accumulator set live at a time (row half 0: 3 MFMAs + epilogue, then row half 1 with the
+  seq3/seq4 (correct results) ONE accumulator set live at a time (row half 0: 2 MFMAs + epilogue, then row half 1 with the
             next half tile's loads behind its MFMAs) at 3 / 4 waves per SIMD: 151 VGPRs / 128 with no scratch access in
             the steady-state loop.  Round 6: 0.606 - 0.612 ms alone against 0.596 - 0.611 for the product (two sets,
             168 VGPRs, 3 waves): the fourth wave buys nothing (profiles/r6b/k1_sequential_accumulators.txt; the
-            figures of that round are the bf16 formulation's: four MFMAs per quarter tile)
+            figures of that round are the bf16 formulation's: four MFMAs per quarter tile, two now)
 usage: make_variants.py [name ...]   then  bash scripts/probe/k1_ab/build.sh <name> ...   (see README.md)"""
 import os
 import sys
@@ -78,11 +78,9 @@ SEQ_BODY = '''  auto body_flat = [&](const int J, auto diag_tag) {
       {
         Acc acc;
         __builtin_amdgcn_s_setprio(2);
-        acc.U = __builtin_amdgcn_mfma_f32_32x32x16_f16(ar[0][0], b0, z, 0, 0, 0);
+        acc.W = __builtin_amdgcn_mfma_f32_32x32x16_f16(ar[0][0], b0, z, 0, 0, 0);
         __builtin_amdgcn_sched_barrier(0);
-        acc.W = __builtin_amdgcn_mfma_f32_32x32x16_f16(ar[0][2], b0, z, 0, 0, 0);
-        __builtin_amdgcn_sched_barrier(0);
-        acc.U = __builtin_amdgcn_mfma_f32_32x32x16_f16(ar[0][1], b1, acc.U, 0, 0, 0);
+        acc.U = __builtin_amdgcn_mfma_f32_32x32x16_f16(ar[0][1], b1, acc.W, 0, 0, 0);
         __builtin_amdgcn_s_setprio(0);
         __builtin_amdgcn_sched_barrier(0);
         tr[ct][0] = epi(acc, DIAG && ct == 0);
@@ -91,13 +89,11 @@ SEQ_BODY = '''  auto body_flat = [&](const int J, auto diag_tag) {
       {
         Acc acc;
         __builtin_amdgcn_s_setprio(2);
-        acc.U = __builtin_amdgcn_mfma_f32_32x32x16_f16(ar[1][0], b0, z, 0, 0, 0);
-        __builtin_amdgcn_sched_barrier(0);
-        acc.W = __builtin_amdgcn_mfma_f32_32x32x16_f16(ar[1][2], b0, z, 0, 0, 0);
+        acc.W = __builtin_amdgcn_mfma_f32_32x32x16_f16(ar[1][0], b0, z, 0, 0, 0);
         __builtin_amdgcn_sched_barrier(0);
         bX[0] = load_op(Jn, 1, gn, 0);
         __builtin_amdgcn_sched_barrier(0);
-        acc.U = __builtin_amdgcn_mfma_f32_32x32x16_f16(ar[1][1], b1, acc.U, 0, 0, 0);
+        acc.U = __builtin_amdgcn_mfma_f32_32x32x16_f16(ar[1][1], b1, acc.W, 0, 0, 0);
         __builtin_amdgcn_sched_barrier(0);
         bX[1] = load_op(Jn, 1, gn, 1);
         __builtin_amdgcn_s_setprio(0);
@@ -122,7 +118,8 @@ VARIANTS = {
     "zero": lambda: zeroed(SRC),
     "nomfma": lambda: in_body(zeroed(SRC), lambda bd: once(no_mfma(bd), LOADS[0],
         '      asm volatile("" : "=v"(acc[0].U), "=v"(acc[0].W), "=v"(acc[1].U), "=v"(acc[1].W) : "v"(b0), "v"(b1));\n' + LOADS[0])),
-    "halfmfma": lambda: in_body(zeroed(SRC), lambda bd: no_mfma(bd, keep=lambda l: "b1, acc" not in l)),
+    "halfmfma": lambda: in_body(zeroed(SRC), lambda bd: once(no_mfma(bd, keep=lambda l: "b1, " not in l), LOADS[0],
+        '      asm volatile("" : "=v"(acc[0].U), "=v"(acc[1].U) : "v"(b1));\n' + LOADS[0])),
     "noepi": lambda: in_body(zeroed(SRC), lambda bd: once(bd, EPI,
         '      for (int rt = 0; rt < 2; ++rt) { asm volatile("" :: "v"(acc[rt].U), "v"(acc[rt].W)); tr[ct][rt] = (unsigned int)lane * 2654435761u + J; }')),
     "nofinish": lambda: in_body(zeroed(SRC), lambda bd: once(bd, "    finish_tile(J, DIAG, tr);",
@@ -131,7 +128,7 @@ VARIANTS = {
     "sameload": lambda: in_body(zeroed(SRC), lambda bd: each_load(bd, lambda m:
         "      (void)Jn; bX[%d] = load_op(Jfirst < T ? Jfirst : T - 1, 1, gn, %d);" % (m, m))),
     "load32": lambda: in_body(zeroed(SRC), lambda bd: each_load(bd, lambda m:
-        "      bX[%d].x = __builtin_amdgcn_raw_buffer_load_b32(q_rsrc, lane * 4, Jn * (int)sizeof(TimOperandTile2) + (int)offsetof(TimOperandTile2, b) + (gn * kTimColOperands + %d) * 1024, 0);" % (m, m))),
+        "      bX[%d].x = __builtin_amdgcn_raw_buffer_load_b32(q_rsrc, lane * 4, Jn * kTileBytes + kColBase + (gn * kTimColOperands + %d) * 1024, 0);" % (m, m))),
     "ldsload": lambda: once(in_body(zeroed(SRC), lambda bd: each_load(bd, lambda m:
         "      (void)Jn; bX[%d] = lds_b[(2 * J + gn) & 1][%d][lane];" % (m, m))),
         "  uint4 bX[kTimColOperands], bY[kTimColOperands];",
@@ -140,7 +137,7 @@ VARIANTS = {
       {
         const int half2 = 2 * J + ct + 2, J2 = min(half2 >> 1, Jend - 1), g2 = half2 & 1;
         asm volatile("" :: "v"(touch[ct]));
-        touch[ct] = __builtin_amdgcn_raw_buffer_load_b32(q_rsrc, lane * 64, J2 * (int)sizeof(TimOperandTile2) + (int)offsetof(TimOperandTile2, b) + g2 * kTimColOperands * 1024, 0);
+        touch[ct] = __builtin_amdgcn_raw_buffer_load_b32(q_rsrc, lane * 64, J2 * kTileBytes + kColBase + g2 * kTimColOperands * 1024, 0);
       }""")), "  uint4 bX[kTimColOperands], bY[kTimColOperands];", "  unsigned int touch[2] = {0u, 0u};\n  uint4 bX[kTimColOperands], bY[kTimColOperands];"),
         "  if (rowvalid)\n    __builtin_amdgcn_raw_ptr_buffer_atomic_add_i32(degacc,",
         '  asm volatile("" :: "v"(touch[0]), "v"(touch[1]));\n  if (rowvalid)\n    __builtin_amdgcn_raw_ptr_buffer_atomic_add_i32(degacc,'),

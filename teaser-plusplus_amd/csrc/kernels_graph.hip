@@ -387,19 +387,22 @@ static_assert(fxr::kChunkTiles == kMfmaColTiles && fxr::kRowTiles == kMfmaRowTil
 // (d = (x^2 - beta^2)(S^2 - beta^2) with x = sqrt B - sqrt A, S = sqrt A + sqrt B).  Both u and w are LINEAR in
 // the Gram terms, so they come straight out of the matrix pipe.  The operands are fp16: 11 significant bits, so TWO
 // round-to-nearest pieces h + m carry an f32 coordinate to 2^-22 relative and only the products h h', h m', m h' are
-// needed -- u over 30 K slots (9 + 9 coordinate products, 6 for the per-point constants m_i - n_i - beta^2 and
-// m_j - n_j in three exact pieces each) = two chained v_mfma_f32_32x32x16_f16, w over 15 slots of the chain's FIRST
-// column operand = one more -- three MFMAs per 32 x 32 tile and two 1-KB column-operand loads per half tile.  (The
-// bf16 formulation this replaces -- three pieces, six products per coordinate, four MFMAs, three loads -- is
-// archived: scripts/probe/experiments/k1_bf16_three_piece.patch.)
+// needed.  The kernel computes the pair (X, Y) = (w / kappa^2, u / kappa), kappa = 4 beta^2, with TWO chained
+// v_mfma_f32_32x32x16_f16 per 32 x 32 tile: the first link sums -A / kappa over 15 K slots (9 coordinate products,
+// the squared norms n_i, n_j in three exact pieces each), the second adds (B - beta^2) / kappa over 16 (9 products,
+// m_i, m_j, beta^2 / kappa = 1/4), and Y^2 + X = d / kappa^2 has the sign of d.  Two row operands per row half, two
+// 1-KB column-operand loads per half tile.  (Archived: the formulation with w as a third MFMA over the chain's first
+// column operand, scripts/probe/experiments/k1_three_mfma_uw.patch, and the bf16 one before it -- three pieces, four
+// MFMAs, three loads -- k1_bf16_three_piece.patch.)
 // The points are centred and scaled per problem by g 2^s: g in (1, sqrt 2] such that kappa = 4 (g beta)^2 is a power
-// of two -- the factor of w is then an exponent shift of the row operands, exact -- and 2^s (k1c::norm_shift, from
-// the bounding boxes) such that the largest half extent lies in [16, 32): fp16 has 5 exponent bits, and in this
-// window every piece stays below 65504 (squared norms <= 8192) while the low pieces keep the precision the budget
-// assumes (a piece below 2^-14 is subnormal and rounds to a multiple of 2^-24: an ABSOLUTE error with its own term).
-// What the window cannot hold -- kappa R > 60000, kappa outside [2^-24, 2^15], R^2 > 8192 -- fails the admission
-// test and runs the FP64 body.  The error budget (eps_u = 500 u R^2 + u (12.1 R + 1), eps_w = kappa 200 u R^2 + ...),
-// the band constants and the admission test are in k1_consts.h, term by term; host programs evaluate the same code.
+// of two -- every factor 1 / kappa is then an exponent shift of the values behind the operand pieces, exact -- and 2^s
+// (k1c::norm_shift, from the bounding boxes) such that the largest half extent lies in [16, 32): fp16 has 5 exponent
+// bits, and in this window every piece stays below 65504 (squared norms <= 8192) while the low pieces keep the
+// precision the budget assumes (a piece below 2^-14 is subnormal and rounds to a multiple of 2^-24: an ABSOLUTE error
+// with its own term).  What the window cannot hold -- kappa outside [2^-17, 2^15], R^2 > 8192 -- fails the admission
+// test and runs the FP64 body.  The error budget (eps_y = (640 u R^2) / kappa + sub_y, eps_x = (200 u R^2) / kappa +
+// sub_y / 2), the band constants and the admission test are in k1_consts.h (consts_xy), term by term, derived in the
+// kappa-multiplied units u = kappa Y, w = kappa^2 X of the lines below; host programs evaluate the same code.
 //   per-value band (admission only): with lam = 2 beta R, eta = eps_u / lam:
 //     |d~ - d*| <= [ (eta + u) |d~| + eta |w~| + K0' ] / (1 - eta), K0' = eps_u lam + eps_u^2 + eps_w (1 + eta);
 //   short pairs: S <= beta implies A, B <= beta^2, hence u* in [-2 beta^2, 0], w* in [-4 beta^4, 0] and |d*| <= 4 beta^4;
@@ -407,17 +410,17 @@ static_assert(fxr::kChunkTiles == kMfmaColTiles && fxr::kRowTiles == kMfmaRowTil
 // ==========================================================================================
 
 // Packed operands of one 64-point tile (tile t of a problem = points 64 t .. 64 t + 63, padded with copies of the
-// problem's last point; tiles are indexed like the bitmap's row words, ProbDesc.w_off + t): 160 B per
-// correspondence, 10 KB per tile.  Laid out so that the 64 lanes of a wave -- lane = (h, c), c = point within a
+// problem's last point; tiles are indexed like the bitmap's row words, ProbDesc.w_off + t): 128 B per
+// correspondence, 8 KB per tile.  Laid out so that the 64 lanes of a wave -- lane = (h, c), c = point within a
 // 32-point group, lane half h holding K slots 8h..8h+7 -- load 1 KB of CONSECUTIVE memory per MFMA operand:
 // [32-point group][MFMA][h][c].  (A first layout with 128 B per point made every such load touch 32 separate
 // 128-B lines: the vector L1 was the kernel's hidden bottleneck.)
 struct TimOperandTile2 {
-  uint4 a[2][3][2][32];  // row side: the u chain's two operands, then the w MFMA's
-  uint4 b[2][2][2][32];  // column side: two operands -- the w MFMA multiplies the u chain's FIRST one again (below)
+  uint4 a[2][2][2][32];  // row side: the chain's two operands (K slots 0..15: X, 16..31: Y - X)
+  uint4 b[2][2][2][32];  // column side: the same slots
 };
 constexpr int kTimColOperands = 2;
-constexpr int kTimRowOperands = 3;
+constexpr int kTimRowOperands = 2;
 
 // fp16 bits of v, round to nearest even, subnormals kept (v_cvt_f16_f32 under the kernel's default denormal mode)
 __device__ __forceinline__ unsigned short f16_bits(float v) { return __builtin_bit_cast(unsigned short, (_Float16)v); }
@@ -446,6 +449,107 @@ __global__ __launch_bounds__(256) void tim_prep_pack2_kernel(const ProbDesc* __r
                                                              const double* __restrict__ dst,
                                                              TimPrep* __restrict__ prep,
                                                              TimOperandTile2* __restrict__ ops,
+                                                             int32_t* __restrict__ deg, double beta) {
+  const ProbDesc d = descs[blockIdx.y];
+  const int ip = blockIdx.x * 256 + threadIdx.x;  // padded point index
+  float mx = 0.f;
+  if (ip < d.W * 64 && d.n > 0) {
+    double g;
+    int kexp;
+    k1c::scale(beta, &g, &kexp);
+    const int i = min(ip, d.n - 1);
+    const TimPrep* pr = prep + blockIdx.y;
+    const int sh = k1c::norm_shift(prep_half_extent(pr));
+    kexp += 2 * sh;  // kappa of the normalised system
+    g *= k1c::pow2_d(sh);
+    const double* a = src + 3 * (d.pt_off + i);
+    const double* b = dst + 3 * (d.pt_off + i);
+    const float sx = (float)((a[0] - prep_centre(pr, 0, 0)) * g), sy = (float)((a[1] - prep_centre(pr, 0, 1)) * g),
+                sz = (float)((a[2] - prep_centre(pr, 0, 2)) * g);
+    const float dx = (float)((b[0] - prep_centre(pr, 1, 0)) * g), dy = (float)((b[1] - prep_centre(pr, 1, 1)) * g),
+                dz = (float)((b[2] - prep_centre(pr, 1, 2)) * g);
+    // squared norms of the f32 points, exact in double up to its own rounding
+    const double na_d = ((double)sx * sx + (double)sy * sy) + (double)sz * sz;
+    const double nb_d = ((double)dx * dx + (double)dy * dy) + (double)dz * dz;
+    const float na = (float)na_d, nb = (float)nb_d;
+    // K slots (k1_consts.h, "The X / Y formulation").  Every slot product carries 2^-kexp = 1 / kappa: the values are
+    // shifted by exact powers of two BEFORE they are split (coordinates 2^-ra on the row side and 2^-rb on the column
+    // side, the squared norms 2^-pa against P = 2^-pb), so the pieces are those of the unshifted value wherever they
+    // stay normal fp16 numbers, and a subnormal piece is rounded once (the budget's absolute terms).
+    //   slot    A (row i)                          B (column j)
+    //   3c+0    h(s_c 2^-ra)                       2 h(s_c 2^-rb)
+    //   3c+1    h(s_c 2^-ra)                       2 m(s_c 2^-rb)
+    //   3c+2    m(s_c 2^-ra)                       2 h(s_c 2^-rb)          c = 0, 1, 2
+    //   9-11    -h, -m, -l (n_i 2^-pa)             P
+    //   12-14   P                                  -h, -m, -l (n_j 2^-pa)
+    //   15      0                                  0                       first link:  X = -A / kappa
+    //   16+3c   h, h, m (d_c 2^-ra)                -2 h, -2 m, -2 h (d_c 2^-rb)
+    //   25-27   h, m, l (m_i 2^-pa)                P
+    //   28-30   P                                  h, m, l (m_j 2^-pa)
+    //   31      -1/4                               1                       second link: Y = X + (B - beta^2) / kappa
+    // (n = |s|^2, m = |d|^2 of the normalised f32 points)
+    int ra, rb, pa, pb;
+    k1c::xy_shifts(kexp, &ra, &rb, &pa, &pb);
+    const float fra = (float)k1c::pow2_d(-ra), frb = (float)k1c::pow2_d(-rb), fpa = (float)k1c::pow2_d(-pa);
+    const unsigned short P = f16_bits((float)k1c::pow2_d(-pb));
+    unsigned short A[32], B[32];
+    for (int k = 0; k < 32; ++k) A[k] = B[k] = 0;
+    const float cs[3] = {sx, sy, sz}, cd[3] = {dx, dy, dz};
+    float h, m, l;
+    for (int c = 0; c < 3; ++c) {
+      f16_split3(cs[c] * fra, &h, &m, &l);  // -A contributes +2 s.s'
+      A[3 * c] = f16_bits(h); A[3 * c + 1] = A[3 * c]; A[3 * c + 2] = f16_bits(m);
+      f16_split3(cs[c] * frb, &h, &m, &l);
+      B[3 * c] = f16_bits(2.0f * h); B[3 * c + 1] = f16_bits(2.0f * m); B[3 * c + 2] = B[3 * c];
+      f16_split3(cd[c] * fra, &h, &m, &l);  // +B contributes -2 d.d'
+      A[16 + 3 * c] = f16_bits(h); A[16 + 3 * c + 1] = A[16 + 3 * c]; A[16 + 3 * c + 2] = f16_bits(m);
+      f16_split3(cd[c] * frb, &h, &m, &l);
+      B[16 + 3 * c] = f16_bits(-2.0f * h); B[16 + 3 * c + 1] = f16_bits(-2.0f * m); B[16 + 3 * c + 2] = B[16 + 3 * c];
+    }
+    f16_split3(na * fpa, &h, &m, &l);
+    A[9] = f16_bits(-h); A[10] = f16_bits(-m); A[11] = f16_bits(-l); B[9] = P; B[10] = P; B[11] = P;
+    B[12] = A[9]; B[13] = A[10]; B[14] = A[11]; A[12] = P; A[13] = P; A[14] = P;
+    f16_split3(nb * fpa, &h, &m, &l);
+    A[25] = f16_bits(h); A[26] = f16_bits(m); A[27] = f16_bits(l); B[25] = P; B[26] = P; B[27] = P;
+    B[28] = A[25]; B[29] = A[26]; B[30] = A[27]; A[28] = P; A[29] = P; A[30] = P;
+    A[31] = 0xb400;  // -1/4 = -beta^2 / kappa
+    B[31] = 0x3c00;  // 1
+    TimOperandTile2* tile = ops + d.w_off + (ip >> 6);
+    const int gq = (ip >> 5) & 1, cc = ip & 31;
+    for (int mf = 0; mf < kTimRowOperands; ++mf)
+      for (int hh = 0; hh < 2; ++hh) {
+        const unsigned short* pa = A + 16 * mf + 8 * hh;
+        tile->a[gq][mf][hh][cc] = make_uint4(pa[0] | ((unsigned int)pa[1] << 16), pa[2] | ((unsigned int)pa[3] << 16),
+                                             pa[4] | ((unsigned int)pa[5] << 16), pa[6] | ((unsigned int)pa[7] << 16));
+        if (mf >= kTimColOperands) continue;
+        const unsigned short* pb = B + 16 * mf + 8 * hh;
+        tile->b[gq][mf][hh][cc] = make_uint4(pb[0] | ((unsigned int)pb[1] << 16), pb[2] | ((unsigned int)pb[3] << 16),
+                                             pb[4] | ((unsigned int)pb[5] << 16), pb[6] | ((unsigned int)pb[7] << 16));
+      }
+    mx = na > nb ? na : nb;
+    if (!(mx == mx)) mx = INFINITY;  // NaN coordinates: force the FP64 path
+    if (ip < d.n) deg[d.pt_off + ip] = 0;
+  }
+  for (int o = 32; o > 0; o >>= 1) {
+    const float t = __shfl_xor(mx, o, 64);
+    mx = t > mx ? t : mx;
+  }
+  if ((threadIdx.x & 63) == 0 && mx > 0.f) atomicMax(&prep[blockIdx.y].r2_bits, __float_as_uint(mx));
+}
+
+#ifdef TEASER_K1_LAB
+// Lab build only: the u / w formulation of rounds 7 - 9 -- w = -kappa A as a THIRD MFMA over the chain's first column
+// operand, kappa-shifted row pieces, constants k1c::consts -- kept as a variant (TEASER_K1_VARIANT + 10000) for A/B runs
+// inside one binary: 160 B per correspondence, three row operands.  The product packs the X / Y operands above.
+struct TimOperandTile3 {
+  uint4 a[2][3][2][32];  // row side: the u chain's two operands, then the w MFMA's
+  uint4 b[2][2][2][32];  // column side: two operands -- the w MFMA multiplies the u chain's FIRST one again
+};
+__global__ __launch_bounds__(256) void tim_prep_pack3_kernel(const ProbDesc* __restrict__ descs,
+                                                             const double* __restrict__ src,
+                                                             const double* __restrict__ dst,
+                                                             TimPrep* __restrict__ prep,
+                                                             TimOperandTile3* __restrict__ ops,
                                                              int32_t* __restrict__ deg, double beta) {
   const ProbDesc d = descs[blockIdx.y];
   const int ip = blockIdx.x * 256 + threadIdx.x;  // padded point index
@@ -514,9 +618,9 @@ __global__ __launch_bounds__(256) void tim_prep_pack2_kernel(const ProbDesc* __r
     A[11] = f16_bits(h); A[12] = f16_bits(m); A[13] = f16_bits(l);
     f16_split3(delta_col, &h, &m, &l);
     A[25] = one; A[26] = one; A[27] = one; B[25] = f16_bits(h); B[26] = f16_bits(m); B[27] = f16_bits(l);
-    TimOperandTile2* tile = ops + d.w_off + (ip >> 6);
+    TimOperandTile3* tile = ops + d.w_off + (ip >> 6);
     const int gq = (ip >> 5) & 1, cc = ip & 31;
-    for (int mf = 0; mf < kTimRowOperands; ++mf)
+    for (int mf = 0; mf < 3; ++mf)
       for (int hh = 0; hh < 2; ++hh) {
         const unsigned short* pa = A + 16 * mf + 8 * hh;
         tile->a[gq][mf][hh][cc] = make_uint4(pa[0] | ((unsigned int)pa[1] << 16), pa[2] | ((unsigned int)pa[3] << 16),
@@ -536,6 +640,7 @@ __global__ __launch_bounds__(256) void tim_prep_pack2_kernel(const ProbDesc* __r
   }
   if ((threadIdx.x & 63) == 0 && mx > 0.f) atomicMax(&prep[blockIdx.y].r2_bits, __float_as_uint(mx));
 }
+#endif  // TEASER_K1_LAB
 
 // ==========================================================================================
 // K1, the matrix-core filter ("min |d|"): the u / w algebra and operands above, with the error band taken off the
@@ -560,14 +665,26 @@ __global__ __launch_bounds__(256) void tim_prep_pack2_kernel(const ProbDesc* __r
 //   Short pairs (S <= beta, the one region where the sign of d misleads) have |d~| <= short_d <= C: always a group.
 // Self pairs (u = -beta^2, w = 0, d = beta^4 <= C) would flag every lane of a diagonal tile: the diagonal column tile
 // of a wave runs a second copy of the loop body that leaves them out of the minimum.
+// The kernel's registers hold Y = u / kappa and X = w / kappa^2 (operands above), its d is Y^2 + X = d / kappa^2 and
+// the band constant it compares with is C / kappa^2 (k1c::consts_xy): the lines above read the same in either unit
+// (short pairs |d| / kappa^2 <= 1/4, self pairs 1/16).
 // ==========================================================================================
 __global__ void tim_prep_consts_kernel(TimPrep* __restrict__ prep, int batch, double beta) {
+  const int p = blockIdx.x * blockDim.x + threadIdx.x;
+  if (p >= batch) return;
+  const k1c::ConstsXY c = k1c::consts_xy(beta, k1c::norm_shift(prep_half_extent(prep + p)), prep[p].r2_bits);
+  prep[p].band_c = c.C;
+  prep[p].use_mfma = c.use_mfma;
+}
+#ifdef TEASER_K1_LAB
+__global__ void tim_prep_consts3_kernel(TimPrep* __restrict__ prep, int batch, double beta) {  // (the UW3 variant's)
   const int p = blockIdx.x * blockDim.x + threadIdx.x;
   if (p >= batch) return;
   const k1c::Consts c = k1c::consts(beta, k1c::norm_shift(prep_half_extent(prep + p)), prep[p].r2_bits);
   prep[p].band_c = c.C;
   prep[p].use_mfma = c.use_mfma;
 }
+#endif
 
 // worklist item: 16 rows of one column and their provisional bits (fixup_item.h; tim_fixup_group_kernel)
 
@@ -576,9 +693,9 @@ constexpr bool kK1Pipe = false, kK1Plain = true;
 constexpr int kK1Chunks = 1, kK1Occ = 3;
 
 // PIPE: software-pipelined schedule.  The wave works on QUARTER tiles (32 x 32) with two accumulator sets: while the
-// matrix pipe runs the three MFMAs of quarter k + 1, the vector ALU runs the epilogue of quarter k -- interleaved
+// matrix pipe runs the two MFMAs of quarter k + 1, the vector ALU runs the epilogue of quarter k -- interleaved
 // inside the one wave (sched_group_barrier: one MFMA, then a share of the epilogue), across the column tiles of the
-// loop as well.  The flat schedule (PIPE = false: 6 MFMAs, then both epilogues) relies on the other two waves of the
+// loop as well.  The flat schedule (PIPE = false: 4 MFMAs, then both epilogues) relies on the other two waves of the
 // SIMD to fill the matrix pipe's shadow.
 // PLAIN: d = fma(u, u, w) as one v_fma_f32 per value instead of one v_pk_fma_f32 per two (MI355X_MICROARCH.md prices
 // a packed f32 instruction beside MFMAs above two plain ones).  Measured (profiles/r5a/k1_lab.jsonl, 64 x 10 k, kernel
@@ -592,10 +709,12 @@ constexpr int kK1Chunks = 1, kK1Occ = 3;
 // counts them for the degrees and issues neither of their stores: a bitmap row r is then valid from word r / 64 on, and
 // what lies in front of it is whatever an earlier batch left there.  The route whose only reader of the bitmap is the
 // degree closure runs so (solver.hip); tim_mirror_lower_kernel rebuilds the lower triangle for whoever else reads it.
-template <bool PIPE, bool PLAIN, int OCC, int CHUNKS, bool LOWER>
+// UW3 (lab build only, flat schedule): the three-MFMA u / w formulation on TimOperandTile3 operands, for A/B runs
+// against the X / Y chain inside one binary; d is then in the units of u^2 + w and the band constant k1c::consts's.
+template <bool PIPE, bool PLAIN, int OCC, int CHUNKS, bool LOWER, bool UW3 = false>
 __global__ __launch_bounds__(256, OCC) void tim_graph_mfma3_kernel(
     const ProbDesc* __restrict__ descs, const double* __restrict__ src,
-    const double* __restrict__ dst, const TimOperandTile2* __restrict__ ops, const TimPrep* __restrict__ prep,
+    const double* __restrict__ dst, const void* __restrict__ ops, const TimPrep* __restrict__ prep,
     uint64_t* __restrict__ bitmap, double beta, int gyr,
     unsigned long long* __restrict__ work, unsigned int* __restrict__ work_count,
     ProbState* __restrict__ states, int32_t* __restrict__ deg, unsigned long long* __restrict__ regions, int Tmax) {
@@ -653,22 +772,26 @@ __global__ __launch_bounds__(256, OCC) void tim_graph_mfma3_kernel(
   // stores on ONE in-order vmcnt)
   __shared__ __attribute__((aligned(16))) uint64_t lds_tr[kMfmaColTiles][64][kMfmaRowTiles];
   // (the operand loads are issued before the band constants are worked out: they are harmless on the FP64 route)
-  const TimOperandTile2* __restrict__ qt = ops + d.w_off;
+  // one operand tile: kRowOps row operands, then kTimColOperands column operands, per 32-point group (TimOperandTile2;
+  // the lab's UW3 variant: TimOperandTile3)
+  constexpr int kRowOps = UW3 ? 3 : kTimRowOperands;
+  constexpr int kTileBytes = 2 * (kRowOps + kTimColOperands) * 1024, kColBase = 2 * kRowOps * 1024;
+  static_assert(UW3 || (kTileBytes == (int)sizeof(TimOperandTile2) && kColBase == (int)offsetof(TimOperandTile2, b)), "tile layout");
+  const char* __restrict__ qt = reinterpret_cast<const char*>(ops) + (size_t)d.w_off * kTileBytes;
   const int h = lane >> 5, c = lane & 31;
   typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
   const __amdgpu_buffer_rsrc_t q_rsrc = __builtin_amdgcn_make_buffer_rsrc(
-      (void*)qt, 0, (int)((unsigned int)T * (unsigned int)sizeof(TimOperandTile2)), 0x00020000);
-  auto load_op = [&](int tile, int side, int g, int m) -> uint4 {  // side 0 = a (rows: m = 0..2), 1 = b (columns: m = 0..1)
-    const int soff = tile * (int)sizeof(TimOperandTile2) +
-                     (side ? (int)offsetof(TimOperandTile2, b) + (g * kTimColOperands + m) * 1024 : (g * kTimRowOperands + m) * 1024);
+      (void*)qt, 0, (int)((unsigned int)T * (unsigned int)kTileBytes), 0x00020000);
+  auto load_op = [&](int tile, int side, int g, int m) -> uint4 {  // side 0 = a (rows), 1 = b (columns): m = 0..1
+    const int soff = tile * kTileBytes + (side ? kColBase + (g * kTimColOperands + m) * 1024 : (g * kRowOps + m) * 1024);
     const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(q_rsrc, lane * 16, soff, 0);
     return make_uint4(v.x, v.y, v.z, v.w);
   };
-  f16x8 ar[2][kTimRowOperands];
+  f16x8 ar[2][kRowOps];
   {
     const int It = min(I, T - 1);
     for (int rt = 0; rt < 2; ++rt)
-      for (int m = 0; m < kTimRowOperands; ++m) ar[rt][m] = __builtin_bit_cast(f16x8, load_op(It, 0, rt, m));
+      for (int m = 0; m < kRowOps; ++m) ar[rt][m] = __builtin_bit_cast(f16x8, load_op(It, 0, rt, m));
   }
   const bool rowvalid = I < T;
   const uint64_t rowmask = !rowvalid ? 0ull : (n - I * 64 >= 64) ? ~0ull : ((1ull << (n - I * 64)) - 1ull);
@@ -707,16 +830,16 @@ __global__ __launch_bounds__(256, OCC) void tim_graph_mfma3_kernel(
   const float thr = pr.band_c;
 
   struct Acc {
-    f32x16 U, W;
+    f32x16 U, W;  // U = Y = u / kappa (the chain's end), W = X = w / kappa^2 (its first link, which stays live)
   };
-  // the three MFMAs of one 32 x 32 quarter tile: u = B - A - beta^2 over 32 K slots (two chained), w = -4 beta^2 A
-  // over 16 (one, over the chain's first column operand again); w sits between the two links of the chain
-  auto mf = [&](Acc& a, const f16x8(&arow)[kTimRowOperands], const uint4(&b)[kTimColOperands]) {
+  // the two chained MFMAs of one 32 x 32 quarter tile: X = -A / kappa over K slots 0..15, Y = X + (B - beta^2) / kappa
+  // over 16..31, written to registers of its own
+  static_assert(!(UW3 && PIPE), "the three-MFMA lab variant has the flat schedule only");
+  auto mf = [&](Acc& a, const f16x8(&arow)[kRowOps], const uint4(&b)[kTimColOperands]) {
     f32x16 z;
     for (int k = 0; k < 16; ++k) z[k] = 0.f;
-    a.U = __builtin_amdgcn_mfma_f32_32x32x16_f16(arow[0], __builtin_bit_cast(f16x8, b[0]), z, 0, 0, 0);
-    a.W = __builtin_amdgcn_mfma_f32_32x32x16_f16(arow[2], __builtin_bit_cast(f16x8, b[0]), z, 0, 0, 0);
-    a.U = __builtin_amdgcn_mfma_f32_32x32x16_f16(arow[1], __builtin_bit_cast(f16x8, b[1]), a.U, 0, 0, 0);
+    a.W = __builtin_amdgcn_mfma_f32_32x32x16_f16(arow[0], __builtin_bit_cast(f16x8, b[0]), z, 0, 0, 0);
+    a.U = __builtin_amdgcn_mfma_f32_32x32x16_f16(arow[1], __builtin_bit_cast(f16x8, b[1]), a.W, 0, 0, 0);
   };
   // epilogue of one quarter tile: the lane's 16 provisional column bits (sign of d = u^2 + w) and the group flag
   auto epi = [&](const Acc& a, bool self_tile) -> unsigned int {
@@ -809,7 +932,7 @@ __global__ __launch_bounds__(256, OCC) void tim_graph_mfma3_kernel(
     lds_tr[(J - Jbase) & (kMfmaColTiles - 1)][lane][wave] = trw_out;
   };
 
-  // flat schedule: per 32-column half the 6 MFMAs of both row halves (chains interleaved by hand), then the epilogues
+  // flat schedule: per 32-column half the 4 MFMAs of both row halves (the two chains interleaved by hand), then the epilogues
   auto body_flat = [&](const int J, auto diag_tag) {
     constexpr bool DIAG = decltype(diag_tag)::value;
     unsigned int tr[2][2];  // [ct][rt]: this lane's 16 column bits
@@ -824,22 +947,28 @@ __global__ __launch_bounds__(256, OCC) void tim_graph_mfma3_kernel(
       // wave's loads win the arbitration against the other waves' vector work (-2 % on the bench step, profiles/r5t;
       // lowering the priority BEFORE the loads, or one level for the whole loop, gains nothing)
       __builtin_amdgcn_s_setprio(2);
-      acc[0].U = __builtin_amdgcn_mfma_f32_32x32x16_f16(ar[0][0], b0, z, 0, 0, 0);
-      __builtin_amdgcn_sched_barrier(0);
-      acc[1].U = __builtin_amdgcn_mfma_f32_32x32x16_f16(ar[1][0], b0, z, 0, 0, 0);
-      __builtin_amdgcn_sched_barrier(0);
-      acc[0].W = __builtin_amdgcn_mfma_f32_32x32x16_f16(ar[0][2], b0, z, 0, 0, 0);
-      __builtin_amdgcn_sched_barrier(0);
-      acc[1].W = __builtin_amdgcn_mfma_f32_32x32x16_f16(ar[1][2], b0, z, 0, 0, 0);
+      if constexpr (UW3) {  // u's first link into U, then w = the third row operand over the same column operand
+        acc[0].U = __builtin_amdgcn_mfma_f32_32x32x16_f16(ar[0][0], b0, z, 0, 0, 0);
+        __builtin_amdgcn_sched_barrier(0);
+        acc[1].U = __builtin_amdgcn_mfma_f32_32x32x16_f16(ar[1][0], b0, z, 0, 0, 0);
+        __builtin_amdgcn_sched_barrier(0);
+        acc[0].W = __builtin_amdgcn_mfma_f32_32x32x16_f16(ar[0][kRowOps - 1], b0, z, 0, 0, 0);
+        __builtin_amdgcn_sched_barrier(0);
+        acc[1].W = __builtin_amdgcn_mfma_f32_32x32x16_f16(ar[1][kRowOps - 1], b0, z, 0, 0, 0);
+      } else {
+        acc[0].W = __builtin_amdgcn_mfma_f32_32x32x16_f16(ar[0][0], b0, z, 0, 0, 0);
+        __builtin_amdgcn_sched_barrier(0);
+        acc[1].W = __builtin_amdgcn_mfma_f32_32x32x16_f16(ar[1][0], b0, z, 0, 0, 0);
+      }
       __builtin_amdgcn_sched_barrier(0);
       // each operand of the next half tile is requested right behind the last MFMA that reads its registers: the
       // load's way into the address unit runs beside the matrix pipe (0.592 -> 0.576 ms alone, -0.6 % on the bench
       // step: profiles/r5t/r5t21)
       bX[0] = load_op(Jn, 1, gn, 0);
       __builtin_amdgcn_sched_barrier(0);
-      acc[0].U = __builtin_amdgcn_mfma_f32_32x32x16_f16(ar[0][1], b1, acc[0].U, 0, 0, 0);
+      acc[0].U = __builtin_amdgcn_mfma_f32_32x32x16_f16(ar[0][1], b1, UW3 ? acc[0].U : acc[0].W, 0, 0, 0);
       __builtin_amdgcn_sched_barrier(0);
-      acc[1].U = __builtin_amdgcn_mfma_f32_32x32x16_f16(ar[1][1], b1, acc[1].U, 0, 0, 0);
+      acc[1].U = __builtin_amdgcn_mfma_f32_32x32x16_f16(ar[1][1], b1, UW3 ? acc[1].U : acc[1].W, 0, 0, 0);
       __builtin_amdgcn_sched_barrier(0);
       bX[1] = load_op(Jn, 1, gn, 1);
       __builtin_amdgcn_s_setprio(0);
@@ -1301,7 +1430,11 @@ void launch_tim_graph(hipStream_t s, const ProbDesc* d_desc, int batch, int max_
 // Host side of the matrix-core K1: buffer sizes, the fix-up worklist's layout, the three launches.
 // ------------------------------------------------------------------------------------------
 int64_t tim_prep_bytes(int batch) { return (int64_t)batch * ((int64_t)sizeof(TimPrep) + 4) + 64; }  // + one worklist counter per problem
+#ifdef TEASER_K1_LAB
+int64_t tim_operand_bytes(int64_t total_tiles) { return total_tiles * (int64_t)sizeof(TimOperandTile3); }  // (the larger)
+#else
 int64_t tim_operand_bytes(int64_t total_tiles) { return total_tiles * (int64_t)sizeof(TimOperandTile2); }
+#endif
 
 // blocks of the matrix-core kernel for a problem of T 64-point tiles: those touching the upper triangle; a block
 // covers 4 row tiles x `chunks` chunks of kMfmaColTiles column tiles
@@ -1366,12 +1499,14 @@ int tim_probe_worklist(const void* d_prep, const void* d_work, int64_t work_cap,
 // Lab build only (scripts/probe/k1_lab): the schedule / geometry of the kernel is picked per launch from
 // TEASER_K1_VARIANT so that a probe can time them side by side.  Every variant produces the same bitmap
 // (scripts/probe/k1_lab/k1_lab.py asserts it).  The product library has ONE instantiation and reads no environment.
-struct K1Variant { int pipe, plain, chunks, occ4; };
+struct K1Variant { int pipe, plain, chunks, occ4, uw3; };
 static K1Variant k1_lab_variant() {
   const char* ev = getenv("TEASER_K1_VARIANT");
   const int v = ev ? atoi(ev) : 0;
-  // v = 1000 * occ4 + 100 * chunks_log2 + 10 * plain + pipe   (occ4: the 128-VGPR build, four workgroups per CU)
+  // v = 10000 * uw3 + 1000 * occ4 + 100 * chunks_log2 + 10 * plain + pipe   (occ4: the 128-VGPR build, four workgroups
+  // per CU; uw3: the three-MFMA u / w formulation with its own operands and constants -- flat schedule, one chunk)
   K1Variant k;
+  k.uw3 = (v / 10000) % 10 != 0;
   k.occ4 = (v / 1000) % 10 != 0;
   k.pipe = v % 10 != 0;
   k.plain = (v / 10) % 10 != 0;
@@ -1424,16 +1559,24 @@ void launch_tim_graph_mfma(hipStream_t s, int phase, const ProbDesc* d_desc, int
     // prep (and the worklist counter behind it) arrive zeroed: part of the solve's header upload
     hipLaunchKernelGGL(tim_prep_bbox_kernel, dim3((max_n + 1023) / 1024, batch), dim3(256), 0, s, d_desc,
                        d_src, d_dst, prep);
+#ifdef TEASER_K1_LAB
+    if (lab.uw3) {
+      hipLaunchKernelGGL(tim_prep_pack3_kernel, dim3((T * 64 + 255) / 256, batch), dim3(256), 0, s, d_desc, d_src,
+                         d_dst, prep, reinterpret_cast<TimOperandTile3*>(d_pk), d_deg, beta);
+      hipLaunchKernelGGL(tim_prep_consts3_kernel, dim3((batch + 63) / 64), dim3(64), 0, s, prep, batch, beta);
+      return;
+    }
+#endif
     hipLaunchKernelGGL(tim_prep_pack2_kernel, dim3((T * 64 + 255) / 256, batch), dim3(256), 0, s, d_desc, d_src,
                        d_dst, prep, reinterpret_cast<TimOperandTile2*>(d_pk), d_deg, beta);
     hipLaunchKernelGGL(tim_prep_consts_kernel, dim3((batch + 63) / 64), dim3(64), 0, s, prep, batch, beta);
   } else if (phase == 1) {
     const int gyr = (T + kMfmaRowTiles - 1) / kMfmaRowTiles;
 #define TIM_K1_LAUNCH(PIPE, PLAIN, CHUNKS) TIM_K1_LAUNCH_OCC(PIPE, PLAIN, kK1Occ, CHUNKS, true)
-#define TIM_K1_LAUNCH_OCC(PIPE, PLAIN, OCC, CHUNKS, LOWER)                                                               \
-  hipLaunchKernelGGL((tim_graph_mfma3_kernel<PIPE, PLAIN, OCC, CHUNKS, LOWER>), dim3(tim_mfma_blocks(T, CHUNKS), batch), \
-                     dim3(256), 0, s, d_desc, d_src, d_dst, reinterpret_cast<const TimOperandTile2*>(d_pk), prep,        \
-                     d_bitmap, beta, gyr, work, work_count, d_state, d_deg, regions, T)
+#define TIM_K1_LAUNCH_OCC(PIPE, PLAIN, OCC, CHUNKS, ...)                                                                       \
+  hipLaunchKernelGGL((tim_graph_mfma3_kernel<PIPE, PLAIN, OCC, CHUNKS, __VA_ARGS__>), dim3(tim_mfma_blocks(T, CHUNKS), batch), \
+                     dim3(256), 0, s, d_desc, d_src, d_dst, (const void*)d_pk, prep, d_bitmap, beta, gyr, work, work_count,    \
+                     d_state, d_deg, regions, T)
 #ifdef TEASER_K1_LAB
 #define TIM_K1_LAB_CASE(PIPE, PLAIN)                             \
   if (lab.pipe == (PIPE ? 1 : 0) && lab.plain == (PLAIN ? 1 : 0)) { \
@@ -1441,7 +1584,9 @@ void launch_tim_graph_mfma(hipStream_t s, int phase, const ProbDesc* d_desc, int
     else if (lab.chunks == 2) { TIM_K1_LAUNCH(PIPE, PLAIN, 2); } \
     else { TIM_K1_LAUNCH(PIPE, PLAIN, 4); }                      \
   }
-    if (lab.occ4) {
+    if (lab.uw3) {
+      if (lab.plain) { TIM_K1_LAUNCH_OCC(false, true, kK1Occ, 1, true, true); } else { TIM_K1_LAUNCH_OCC(false, false, kK1Occ, 1, true, true); }
+    } else if (lab.occ4) {
       if (lab.plain) { TIM_K1_LAUNCH_OCC(false, true, 4, 1, true); } else { TIM_K1_LAUNCH_OCC(false, false, 4, 1, true); }
     } else {
       TIM_K1_LAB_CASE(false, false)
