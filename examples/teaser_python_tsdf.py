@@ -10,9 +10,11 @@ poses (the poses a multiway registration such as examples/teaser_python_multiway
 
 It prints the number of extracted points and the largest distance from an extracted point to the analytic surface (the
 nearer of the wall and the balls' spheres).  With --mesh PATH the triangle mesh is extracted too (extract_triangle_mesh:
-marching cubes on the device) and written to PATH as a PLY file.  Usage:
+marching cubes on the device) and written to PATH as a PLY file.  With --scalable the same frames also go into a
+ScalableTSDFVolume with the same voxels, which needs no cube around the scene: it prints the blocks the frames opened and
+the device bytes they hold beside the dense cube's, and the same two figures for its cloud.  Usage:
 
-    python examples/teaser_python_tsdf.py [--width 320 --height 240] [--resolution 128] [--frames 8] [--mesh PATH]
+    python examples/teaser_python_tsdf.py [--width 320 --height 240] [--resolution 128] [--frames 8] [--mesh PATH] [--scalable]
 """
 import argparse
 import importlib
@@ -70,6 +72,7 @@ def main():
     ap.add_argument("--resolution", type=int, default=128)
     ap.add_argument("--frames", type=int, default=8)
     ap.add_argument("--mesh", default=None, help="also extract the triangle mesh and write it to this PLY file")
+    ap.add_argument("--scalable", action="store_true", help="also fuse the frames in a ScalableTSDFVolume with the same voxels")
     a = ap.parse_args()
     K, depths, extrinsics = scene_frames(a.width, a.height, a.frames)
     length, R, trunc, origin = volume_settings(a.resolution)
@@ -94,6 +97,26 @@ def main():
         print("mesh: %d vertices, %d triangles, %.1f ms; distance to the analytic surface: max %.6f; written to %s"
               % (len(mesh.vertices), len(mesh.triangles), 1e3 * (t5 - t4), dm.max() if len(dm) else 0.0, a.mesh))
     vol.close()
+    if a.scalable:
+        run_scalable(a, K, depths, extrinsics, length / R, trunc, 8 * R ** 3)
+
+
+def run_scalable(a, K, depths, extrinsics, voxel_length, trunc, dense_bytes):
+    """The same frames in blocks of 16^3 voxels: no cube, no origin."""
+    t0 = time.perf_counter()
+    with tp.ScalableTSDFVolume(voxel_length, trunc, tp.TSDFVolumeColorType.NoColor) as vol:
+        vol.integrate_batch(depths, K, extrinsics, depth_scale=1000.0, depth_trunc=6.0)
+        t1 = time.perf_counter()
+        cloud = vol.extract_point_cloud()
+        t2 = time.perf_counter()
+        touched, opened, _ = vol.last_counts
+        held = vol.block_count * vol.block_bytes
+        print("scalable volume: voxels of %.4f in blocks of 16^3, truncation %.4f, every 4th pixel touches" % (voxel_length, trunc))
+        print("scalable integration: %d frames in one call, %.1f ms; %d blocks opened (%d frame-block pairs), "
+              "%d bytes held beside the dense cube's %d" % (len(depths), 1e3 * (t1 - t0), opened, touched, held, dense_bytes))
+        print("scalable extraction: %d points with normals, %.1f ms" % (len(cloud.points), 1e3 * (t2 - t1)))
+        d = distance_to_surface(cloud.points)
+        print("scalable distance to the analytic surface: max %.17g, mean %.6f" % (d.max() if len(d) else 0.0, d.mean() if len(d) else 0.0))
 
 
 if __name__ == "__main__":

@@ -84,5 +84,15 @@ struct LazyTsdf : LazyHandle<teaser_hip_tsdf, teaser_hip_tsdf_destroy> {
   }
 };
 
+// Likewise for the scalable TSDF volume.
+struct LazyStsdf : LazyHandle<teaser_hip_stsdf, teaser_hip_stsdf_destroy> {
+  int32_t create(const teaser_stsdf_volume_c& volume, int32_t device = -1) {
+    if (h_) return TEASER_HIP_OK;
+    const int32_t rc = teaser_hip_stsdf_create(&volume, device, &h_);
+    if (rc != TEASER_HIP_OK) h_ = nullptr;
+    return rc;
+  }
+};
+
 }  // namespace detail
 }  // namespace teaser

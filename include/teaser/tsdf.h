@@ -1,6 +1,6 @@
 // teaser/tsdf.h -- TSDF volume integration on the MI355X with the surface of open3d::pipelines::integration::
 // UniformTSDFVolume: depth frames and their camera poses in, one fused cloud out, over the C ABI (include/teaser_hip.h,
-// "TSDF volume", where the contract is written out).  Header-only.
+// "TSDF volume", where the contract is written out), and of ScalableTSDFVolume ("Scalable TSDF volume").  Header-only.
 //
 // The volume lives on the device as long as the object: frames go up, only the extracted surface comes back.  Images
 // come in as teaser::DepthFrame (teaser/rgbd.h), a view that owns nothing; `extrinsic` is world-to-camera as in Open3D.
@@ -232,6 +232,115 @@ class UniformTSDFVolume {
   int resolution_;
   TSDFVolumeColorType color_type_;
   detail::LazyTsdf h_;
+};
+
+// Open3D's ScalableTSDFVolume: only the blocks of 16^3 voxels that depth frames have come near are stored (include/
+// teaser_hip.h, "Scalable TSDF volume").  extractTriangleMesh and rayCast are not offered here.
+class ScalableTSDFVolume {
+ public:
+  // What the last integrate call reported: (frame, block) pairs touched, blocks opened, and (frame, point) pairs with
+  // a block outside the index range.
+  struct Counts {
+    int64_t touched = 0, opened = 0, out_of_range = 0;
+  };
+
+  ScalableTSDFVolume(double voxel_length, double sdf_trunc, TSDFVolumeColorType color_type, int volume_unit_resolution = 16,
+                     int depth_sampling_stride = 4, int device = -1)
+      : voxel_length_(voxel_length), color_type_(color_type) {
+    teaser_stsdf_volume_c v;
+    teaser_hip_stsdf_volume_default(&v);
+    v.voxel_length = voxel_length, v.sdf_trunc = sdf_trunc, v.color_type = (int32_t)color_type;
+    v.volume_unit_resolution = volume_unit_resolution, v.depth_sampling_stride = depth_sampling_stride;
+    const int32_t rc = h_.create(v, device);
+    if (rc != TEASER_HIP_OK)
+      throw TSDFError(rc, "teaser::ScalableTSDFVolume: teaser_hip_stsdf_create failed (status " + std::to_string(rc) +
+                              (rc == TEASER_HIP_ERR_NO_DEVICE ? ": no MI355X visible, there is no CPU path)"
+                                                              : std::string("): ") + teaser_hip_stsdf_last_error(nullptr)));
+  }
+
+  double voxelLength() const { return voxel_length_; }
+  const Counts& lastCounts() const { return counts_; }
+
+  void integrate(const DepthFrame& frame, const PinholeCameraIntrinsic& intrinsic, const Matrix4& extrinsic,
+                 double depth_scale = 1000.0, double depth_trunc = 3.0) {
+    integrateBatch({frame}, {intrinsic}, {extrinsic}, depth_scale, depth_trunc);
+  }
+
+  // The frames, in the order given, in one call: the blocks end with the bits one integrate() per frame leaves.
+  void integrateBatch(const std::vector<DepthFrame>& frames, const std::vector<PinholeCameraIntrinsic>& intrinsics,
+                      const std::vector<Matrix4>& extrinsics, double depth_scale = 1000.0, double depth_trunc = 3.0) {
+    const size_t b = frames.size();
+    if ((intrinsics.size() != 1 && intrinsics.size() != b) || extrinsics.size() != b)
+      throw std::invalid_argument("teaser::ScalableTSDFVolume: one intrinsic (or one per frame) and one extrinsic per frame");
+    std::vector<teaser_tsdf_frame_c> rec(b);
+    std::vector<const void*> pd(b), pc(b);
+    for (size_t k = 0; k < b; ++k) {
+      const DepthFrame& f = frames[k];
+      const PinholeCameraIntrinsic& K = intrinsics[intrinsics.size() == 1 ? 0 : k];
+      teaser_tsdf_frame_c& r = rec[k];
+      r = teaser_tsdf_frame_c{};
+      r.width = f.width, r.height = f.height, r.depth_format = f.depth_format, r.color_format = f.color_format;
+      r.depth_row_bytes = f.depth_row_bytes, r.color_row_bytes = f.color_row_bytes;
+      r.fx = K.fx, r.fy = K.fy, r.cx = K.cx, r.cy = K.cy;
+      detail::row_major(extrinsics[k], r.extrinsic);
+      r.depth_scale = depth_scale, r.depth_trunc = depth_trunc;
+      pd[k] = f.depth, pc[k] = f.color;
+    }
+    counts_ = Counts();
+    check(teaser_hip_stsdf_integrate_frames(h_, (int32_t)b, rec.data(), pd.data(), pc.data(), &counts_.touched, &counts_.opened,
+                                           &counts_.out_of_range));
+  }
+
+  // Points, normals (unless with_normals is false) and, for a volume with a colour type, colours: blocks in ascending
+  // (bx, by, bz), Open3D's order inside a block.
+  TSDFPointCloud extractPointCloud(bool with_normals = true) {
+    const bool colored = color_type_ != TSDFVolumeColorType::NoColor;
+    int64_t count = 0;
+    check(teaser_hip_stsdf_extract_point_cloud(h_, 0, nullptr, nullptr, nullptr, &count));
+    TSDFPointCloud out;
+    out.points = Matrix3X(3, count);
+    if (with_normals) out.normals = Matrix3X(3, count);
+    if (colored) out.colors = Matrix3X(3, count);
+    if (count > 0)
+      check(teaser_hip_stsdf_extract_point_cloud(h_, count, out.points.data(), with_normals ? out.normals.data() : nullptr,
+                                                 colored ? out.colors.data() : nullptr, &count));
+    return out;
+  }
+
+  TSDFPointCloud extractVoxelPointCloud() {
+    int64_t count = 0;
+    check(teaser_hip_stsdf_extract_voxel_point_cloud(h_, 0, nullptr, nullptr, &count));
+    TSDFPointCloud out;
+    out.points = Matrix3X(3, count);
+    out.colors = Matrix3X(3, count);
+    if (count > 0)
+      check(teaser_hip_stsdf_extract_voxel_point_cloud(h_, count, out.points.data(), out.colors.data(), &count));
+    return out;
+  }
+
+  int64_t blockCount() {
+    int64_t n = 0;
+    check(teaser_hip_stsdf_block_count(h_, &n));
+    return n;
+  }
+  // (bx, by, bz) of every open block, three int32 per block, in ascending order.
+  std::vector<int32_t> blockKeys() {
+    int64_t n = blockCount();
+    std::vector<int32_t> keys(3 * (size_t)n);
+    if (n > 0) check(teaser_hip_stsdf_block_keys(h_, n, keys.data(), &n));
+    return keys;
+  }
+  void reset() { check(teaser_hip_stsdf_reset(h_)); }
+
+ private:
+  void check(int32_t rc) {
+    if (rc != TEASER_HIP_OK)
+      throw TSDFError(rc, "teaser::ScalableTSDFVolume: status " + std::to_string(rc) + ": " + teaser_hip_stsdf_last_error(h_));
+  }
+  double voxel_length_;
+  TSDFVolumeColorType color_type_;
+  Counts counts_;
+  detail::LazyStsdf h_;
 };
 
 }  // namespace teaser

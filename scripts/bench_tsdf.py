@@ -38,7 +38,16 @@ route fills.  The steps every ray takes are counted by the numpy restatement (te
 volume downloaded at R = 64, which must equal the device's maps.  `--profile-workload ray_cast` runs three single-view
 and three 16-view calls for rocprofv3.
 
-    python scripts/bench_tsdf.py --ray-cast --reps 9 --warmup 1 --out profiles/tsdf_raycast/bench_tsdf_raycast.json"""
+    python scripts/bench_tsdf.py --ray-cast --reps 9 --warmup 1 --out profiles/tsdf_raycast/bench_tsdf_raycast.json
+
+`--scalable` measures the scalable volume instead (profiles/tsdf_scalable/): the same 64 frames into a ScalableTSDFVolume
+with the voxels of every size of `--sizes`, without and with RGB8 colour: the time of one call of 64 frames and of 64
+calls, each into an emptied volume (every block is opened again) and into a volume whose blocks are open, per call and
+per frame and split by the library's own clock into touch pass, directory merge and integration; the extractions; the
+blocks opened and the device bytes they hold beside the dense cube's; and the dense volume's times on the same frames in
+the same process, measured in alternation with the scalable ones (that is the comparison: the dense path is unchanged).
+
+    python scripts/bench_tsdf.py --scalable --sizes 512 --reps 9 --warmup 1 --out profiles/tsdf_scalable/bench_tsdf_scalable.json"""
 import argparse
 import ctypes as C
 import importlib
@@ -250,6 +259,64 @@ def ray_cast_restatement(K, d, e, c):
                 steps_histogram_by_8=np.bincount(steps // 8).tolist())
 
 
+def run_scalable(R, colour, K, d, e, c, reps, warmup):
+    cc = c if colour else None
+    length, R, trunc, _ = ex.volume_settings(R)
+    ctype = tp.TSDFVolumeColorType.RGB8 if colour else tp.TSDFVolumeColorType.NoColor
+    res = dict(R=R, colour=bool(colour), voxel_length=length / R, sdf_trunc=trunc, dense_bytes=(32 if colour else 8) * R ** 3)
+    phases = {}
+
+    def fresh_one_call(vol):
+        vol.reset()
+        one_call(vol, K, d, e, cc)
+        phases.setdefault("fresh", []).append(vol.last_phases_ms())
+
+    def warm_one_call(vol):
+        one_call(vol, K, d, e, cc)
+        phases.setdefault("warm", []).append(vol.last_phases_ms())
+
+    def fresh_many_calls(vol):
+        vol.reset()
+        many_calls(vol, K, d, e, cc)
+
+    with tp.ScalableTSDFVolume(length / R, trunc, ctype) as a, tp.ScalableTSDFVolume(length / R, trunc, ctype) as b, make(R, colour) as dense:
+        one_call(a, K, d, e, cc)
+        many_calls(b, K, d, e, cc)
+        res["touched_pairs"], res["blocks"], res["out_of_range"] = a.last_counts[0], a.block_count, a.last_counts[2]
+        res["scalable_bytes"] = a.block_count * a.block_bytes
+        ka, ta, ca = a.extract_blocks()
+        kb, tb, cb = b.extract_blocks()
+        res["same_bits_one_call_and_64_calls"] = bool(ka.tobytes() == kb.tobytes() and ta.tobytes() == tb.tobytes() and
+                                                      (ca is None or ca.tobytes() == cb.tobytes()))
+        del ta, tb, ca, cb
+        pc = a.extract_point_cloud()
+        res["surface_points"] = len(pc.points)
+        res["max_distance_to_surface"] = float(ex.distance_to_surface(pc.points).max())
+        res["voxel_points"] = len(a.extract_voxel_point_cloud().points)
+        # alternating: a scalable measurement, then the dense one of the same kind
+        res["extract_point_cloud"] = timed(lambda: a.extract_point_cloud(), reps, warmup)
+        one_call(dense, K, d, e, cc)
+        res["dense_extract_point_cloud"] = timed(lambda: dense.extract_point_cloud(), reps, warmup)
+        res["dense_surface_points"] = len(dense.extract_point_cloud().points)
+        res["extract_point_cloud_no_normals"] = timed(lambda: a.extract_point_cloud(normals=False), reps, warmup)
+        res["extract_voxel_point_cloud"] = timed(lambda: a.extract_voxel_point_cloud(), reps, warmup)
+        res["dense_extract_voxel_point_cloud"] = timed(lambda: dense.extract_voxel_point_cloud(), reps, warmup)
+        res["integrate_one_call_64_frames_fresh"] = timed(lambda: fresh_one_call(a), reps, warmup)
+        res["dense_integrate_one_call_64_frames"] = timed(lambda: one_call(dense, K, d, e, cc), reps, warmup)
+        res["integrate_one_call_64_frames_warm"] = timed(lambda: warm_one_call(a), reps, warmup)
+        res["integrate_64_calls_fresh"] = timed(lambda: fresh_many_calls(b), reps, warmup)
+        res["dense_integrate_64_calls"] = timed(lambda: many_calls(dense, K, d, e, cc), reps, warmup)
+        res["integrate_64_calls_warm"] = timed(lambda: many_calls(b, K, d, e, cc), reps, warmup)
+    for key in list(res):
+        if "integrate_" in key:
+            res[key]["ms_per_frame"] = res[key]["median_ms"] / FRAMES
+    for kind, rows in phases.items():
+        med = np.median(np.array(rows[warmup:]), axis=0)
+        res["phases_one_call_%s_ms" % kind] = dict(touch_and_readback=float(med[0]), directory_on_host=float(med[1]),
+                                                   zeroing_and_integration=float(med[2]))
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=9)
@@ -261,6 +328,7 @@ def main():
     ap.add_argument("--profile-colour", type=int, default=1)
     ap.add_argument("--mesh", action="store_true", help="measure the triangle mesh instead (profiles/tsdf_mesh/)")
     ap.add_argument("--ray-cast", action="store_true", help="measure the ray cast instead (profiles/tsdf_raycast/)")
+    ap.add_argument("--scalable", action="store_true", help="measure the scalable volume instead (profiles/tsdf_scalable/)")
     a = ap.parse_args()
     if tp.device_count() < 1:
         sys.exit("bench_tsdf.py needs an MI355X: no HIP device visible")
@@ -287,6 +355,17 @@ def main():
                     vol.extract_voxel_point_cloud()
         return
     out = dict(workload=dict(width=W, height=H, frames=FRAMES, poses=POSES, chunk=CHUNK, hbm_peak=HBM_PEAK), settings=[])
+    if a.scalable:
+        for R in a.sizes:
+            for colour in (0, 1):
+                r = run_scalable(R, colour, K, d, e, c, a.reps, a.warmup)
+                print(json.dumps(r), flush=True)
+                out["settings"].append(r)
+        if a.out:
+            os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+            with open(a.out, "w") as f:
+                json.dump(out, f, indent=1)
+        return
     if a.ray_cast:
         for R in a.sizes:
             r = run_ray_cast(R, K, d, e, c, a.reps, a.warmup)

@@ -177,6 +177,10 @@ EXPORTED_SYMBOLS = [
     "teaser_hip_tsdf_extract_voxel_point_cloud", "teaser_hip_tsdf_download", "teaser_hip_tsdf_upload",
     "teaser_hip_tsdf_extract_triangle_mesh", "teaser_hip_tsdf_mesh_tables", "teaser_hip_tsdf_view_default",
     "teaser_hip_tsdf_ray_cast_views",
+    "teaser_hip_stsdf_volume_default", "teaser_hip_stsdf_create", "teaser_hip_stsdf_destroy", "teaser_hip_stsdf_last_error",
+    "teaser_hip_stsdf_fill_scratch", "teaser_hip_stsdf_last_phases", "teaser_hip_stsdf_reset", "teaser_hip_stsdf_integrate_frames",
+    "teaser_hip_stsdf_extract_point_cloud", "teaser_hip_stsdf_extract_voxel_point_cloud", "teaser_hip_stsdf_block_count",
+    "teaser_hip_stsdf_block_keys", "teaser_hip_stsdf_download_blocks", "teaser_hip_stsdf_upload_blocks",
     "teaser_hip_icp_odometry_option_default", "teaser_hip_icp_rgbd_odometry_batch",
     "teaser_hip_icp_rgbd_odometry_pyramid_batch",
 ]
@@ -1183,7 +1187,7 @@ from .fgr import (FastGlobalRegistrationOption, registration_fgr_based_on_corres
                   fgr_iterations_batch, set_fgr_option, get_fgr_option)
 from .plane import (segment_plane, segment_plane_batch, plane_trials_batch, set_plane_option,  # noqa: E402
                     get_plane_option)
-from .tsdf import (UniformTSDFVolume, TSDFVolumeColorType, TSDFPointCloud, TSDFTriangleMesh,  # noqa: E402
+from .tsdf import (UniformTSDFVolume, ScalableTSDFVolume, TSDFVolumeColorType, TSDFPointCloud, TSDFTriangleMesh,  # noqa: E402
                    TSDFRayCastResult, write_triangle_mesh)
 from .odometry import (OdometryOption, RGBDOdometryJacobianFromColorTerm,  # noqa: E402
                        RGBDOdometryJacobianFromHybridTerm, RGBDImage, compute_rgbd_odometry,

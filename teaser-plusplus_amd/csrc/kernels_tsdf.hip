@@ -111,12 +111,16 @@ __global__ __launch_bounds__(kTsdfScanThreads) void tsdf_scan_kernel(const int32
   if (threadIdx.x == kTsdfScanThreads - 1) offsets[n_cols] = s[threadIdx.x];
 }
 
+void launch_tsdf_scan(hipStream_t s, const int32_t* d_counts, int64_t n, int64_t* d_offsets) {
+  hipLaunchKernelGGL(tsdf_scan_kernel, dim3(1), dim3(kTsdfScanThreads), 0, s, d_counts, n, d_offsets);
+}
+
 void launch_tsdf_count(hipStream_t s, const TsdfGrid& g, const TsdfFields& v, int mode, int32_t* d_counts,
                        int64_t* d_offsets) {
   const int64_t plane = (int64_t)g.R * g.R;
   hipLaunchKernelGGL(tsdf_count_kernel, dim3((unsigned)((plane + kTsdfBlock - 1) / kTsdfBlock)), dim3(kTsdfBlock), 0, s, g,
                      v, mode, d_counts);
-  hipLaunchKernelGGL(tsdf_scan_kernel, dim3(1), dim3(kTsdfScanThreads), 0, s, d_counts, plane, d_offsets);
+  launch_tsdf_scan(s, d_counts, plane, d_offsets);
 }
 
 __global__ __launch_bounds__(kTsdfBlock) void tsdf_write_kernel(const TsdfGrid g, const TsdfFields v, const int mode,

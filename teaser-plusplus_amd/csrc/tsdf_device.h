@@ -241,6 +241,9 @@ void launch_tsdf_integrate(hipStream_t s, const TsdfGrid& g, const TsdfChunkArgs
 // counts[x R + y] = the rows of the column, offsets = their exclusive sum with the total at offsets[R R].
 void launch_tsdf_count(hipStream_t s, const TsdfGrid& g, const TsdfFields& v, int mode, int32_t* d_counts,
                        int64_t* d_offsets);
+// The scan alone (one block): offsets = the exclusive sum of n counts with the total at offsets[n].  The scalable volume
+// runs it over its blocks (kernels_stsdf.hip).
+void launch_tsdf_scan(hipStream_t s, const int32_t* d_counts, int64_t n, int64_t* d_offsets);
 // The rows, from every column's offset, unless the total exceeds capacity (then nothing is written).  Any of normals and
 // colors may be NULL.
 void launch_tsdf_write(hipStream_t s, const TsdfGrid& g, const TsdfFields& v, int mode, const int64_t* d_offsets,

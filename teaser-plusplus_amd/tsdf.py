@@ -47,7 +47,15 @@ class TsdfViewC(C.Structure):
                 ("weight_threshold", C.c_double), ("reserved", C.c_int64)]
 
 
+class StsdfVolumeC(C.Structure):
+    """teaser_stsdf_volume_c (include/teaser_hip.h)."""
+    _fields_ = [("voxel_length", C.c_double), ("sdf_trunc", C.c_double), ("color_type", C.c_int32),
+                ("volume_unit_resolution", C.c_int32), ("depth_sampling_stride", C.c_int32), ("initial_blocks", C.c_int32),
+                ("slab_blocks", C.c_int32), ("reserved32", C.c_int32), ("max_blocks", C.c_int64), ("reserved", C.c_int64)]
+
+
 assert C.sizeof(TsdfVolumeC) == 56 and C.sizeof(TsdfFrameC) == 208 and C.sizeof(TsdfViewC) == 200  # as the header asserts
+assert C.sizeof(StsdfVolumeC) == 56
 
 
 def declare(L):
@@ -69,6 +77,22 @@ def declare(L):
     L.teaser_hip_tsdf_view_default.argtypes = [C.POINTER(TsdfViewC)]
     L.teaser_hip_tsdf_ray_cast_views.argtypes = [_vp, C.c_int32, C.POINTER(TsdfViewC), C.POINTER(_fp), C.POINTER(_fp),
                                                  C.POINTER(_fp), C.POINTER(_fp), _i64p]
+    L.teaser_hip_stsdf_volume_default.argtypes = [C.POINTER(StsdfVolumeC)]
+    L.teaser_hip_stsdf_create.argtypes = [C.POINTER(StsdfVolumeC), C.c_int32, C.POINTER(_vp)]
+    L.teaser_hip_stsdf_destroy.argtypes = [_vp]
+    L.teaser_hip_stsdf_last_error.argtypes = [_vp]
+    L.teaser_hip_stsdf_last_error.restype = C.c_char_p
+    L.teaser_hip_stsdf_fill_scratch.argtypes = [_vp, C.c_int32, C.POINTER(C.c_int64)]
+    L.teaser_hip_stsdf_last_phases.argtypes = [_vp, _dp]
+    L.teaser_hip_stsdf_reset.argtypes = [_vp]
+    L.teaser_hip_stsdf_integrate_frames.argtypes = [_vp, C.c_int32, C.POINTER(TsdfFrameC), C.POINTER(_vp), C.POINTER(_vp),
+                                                   _i64p, _i64p, _i64p]
+    L.teaser_hip_stsdf_extract_point_cloud.argtypes = [_vp, C.c_int64, _dp, _dp, _dp, _i64p]
+    L.teaser_hip_stsdf_extract_voxel_point_cloud.argtypes = [_vp, C.c_int64, _dp, _dp, _i64p]
+    L.teaser_hip_stsdf_block_count.argtypes = [_vp, _i64p]
+    L.teaser_hip_stsdf_block_keys.argtypes = [_vp, C.c_int64, _i32p, _i64p]
+    L.teaser_hip_stsdf_download_blocks.argtypes = [_vp, C.c_int64, _fp, _dp, _i64p]
+    L.teaser_hip_stsdf_upload_blocks.argtypes = [_vp, C.c_int64, _i32p, _fp, _dp]
 
 
 class TSDFVolumeColorType:
@@ -161,38 +185,13 @@ def write_triangle_mesh(path, mesh, binary=True):
                 f.write(("3 %d %d %d\n" % (a, b, c)).encode())
 
 
-class UniformTSDFVolume:
-    """Open3D's UniformTSDFVolume(length, resolution, sdf_trunc, color_type, origin): a cube of resolution^3 voxels with
-    its corner at ``origin``, kept on ``device`` (-1: the current one)."""
+class _TSDFHandle:
+    """What the dense and the scalable volume share: the handle (``_prefix`` names its entry points), the frame records,
+    integration and the two point-cloud extractions."""
+    _prefix = "teaser_hip_tsdf"
 
-    def __init__(self, length, resolution, sdf_trunc, color_type=TSDFVolumeColorType.NoColor, origin=(0.0, 0.0, 0.0),
-                 device=-1):
-        from . import TeaserHipError, lib
-        if int(resolution) != resolution or not 1 <= int(resolution) <= 1024:
-            raise ValueError("resolution must be an integer in [1, 1024]")
-        if not (math.isfinite(float(length)) and float(length) > 0):
-            raise ValueError("length must be finite and > 0")
-        if not (math.isfinite(float(sdf_trunc)) and float(sdf_trunc) > 0):
-            raise ValueError("sdf_trunc must be finite and > 0")
-        if color_type not in (0, 1, 2):
-            raise ValueError("color_type must be one of TSDFVolumeColorType.NoColor, RGB8, Gray32")
-        o = np.asarray(origin, dtype=np.float64)
-        if o.shape != (3,) or not np.isfinite(o).all():
-            raise ValueError("origin must be three finite numbers")
-        self.length, self.sdf_trunc, self.color_type = float(length), float(sdf_trunc), int(color_type)
-        self._resolution, self.origin = int(resolution), o.copy()
-        self._lib = lib()
-        rec = TsdfVolumeC()
-        self._lib.teaser_hip_tsdf_volume_default(C.byref(rec))
-        rec.length, rec.sdf_trunc, rec.resolution, rec.color_type = self.length, self.sdf_trunc, self._resolution, self.color_type
-        rec.origin[:] = list(o)
-        self._h = _vp()
-        self._lock = threading.Lock()
-        rc = self._lib.teaser_hip_tsdf_create(C.byref(rec), int(device), C.byref(self._h))
-        if rc != 0:
-            self._h = None
-            msg = self._lib.teaser_hip_tsdf_last_error(None).decode()
-            raise TeaserHipError(rc, "(no MI355X visible: the product has no CPU path)" if rc == 3 else msg)
+    def _fn(self, name):
+        return getattr(self._lib, self._prefix + "_" + name)
 
     # ---- the handle ---------------------------------------------------------------------------------------------
     def _call(self, fn, *args):
@@ -201,22 +200,22 @@ class UniformTSDFVolume:
             raise ValueError("the volume is closed")
         with self._lock:  # the handle serves one call at a time
             rc = fn(self._h, *args)
-            err = self._lib.teaser_hip_tsdf_last_error(self._h).decode() if rc != 0 else ""
+            err = self._fn("last_error")(self._h).decode() if rc != 0 else ""
         if rc != 0:
             raise TeaserHipError(rc, err)
 
     def fill_scratch(self, byte):
-        """DIAGNOSTIC (teaser_hip_tsdf_fill_scratch): sets every byte of the handle's scratch and staging buffers to
+        """DIAGNOSTIC (teaser_hip_*_fill_scratch): sets every byte of the handle's scratch and staging buffers to
         `byte` (0 .. 255) and returns the device bytes filled.  The volume itself is state and is left alone."""
         filled = C.c_int64()
-        self._call(self._lib.teaser_hip_tsdf_fill_scratch, int(byte), C.byref(filled))
+        self._call(self._fn("fill_scratch"), int(byte), C.byref(filled))
         return filled.value
 
     def close(self):
         """Frees the volume; the object is unusable afterwards."""
         h, self._h = getattr(self, "_h", None), None
         if h is not None:
-            self._lib.teaser_hip_tsdf_destroy(h)
+            self._fn("destroy")(h)
 
     def __del__(self):
         try:
@@ -229,14 +228,6 @@ class UniformTSDFVolume:
 
     def __exit__(self, *exc):
         self.close()
-
-    @property
-    def voxel_length(self):
-        return self.length / self._resolution
-
-    @property
-    def resolution(self):
-        return self._resolution
 
     # ---- integration --------------------------------------------------------------------------------------------
     def _frames(self, depths, intrinsic, extrinsics, colors, depth_scale, depth_trunc):
@@ -289,7 +280,7 @@ class UniformTSDFVolume:
 
         def ptrs(arrs):
             return (_vp * b)(*[None if a is None or a.size == 0 else a.ctypes.data_as(_vp) for a in arrs])
-        self._call(self._lib.teaser_hip_tsdf_integrate_batch, b, frames, ptrs(dimg), ptrs(cimg))
+        self._integrate_call(b, frames, ptrs(dimg), ptrs(cimg))
 
     def integrate(self, depth, intrinsic, extrinsic, color=None, depth_scale=1000.0, depth_trunc=3.0):
         """Open3D's integrate(rgbd, intrinsic, extrinsic) with the RGBD image given as its parts: the depth image, and
@@ -313,15 +304,61 @@ class UniformTSDFVolume:
     def extract_point_cloud(self, normals=True):
         """Open3D's extract_point_cloud: the zero crossings between neighbouring voxels in Open3D's order, with their
         normals (unless normals=False) and, for a volume with a colour type, their colours."""
-        pts, (nrm, col) = self._extract(self._lib.teaser_hip_tsdf_extract_point_cloud,
+        pts, (nrm, col) = self._extract(self._fn("extract_point_cloud"),
                                         [bool(normals), self.color_type != TSDFVolumeColorType.NoColor])
         return TSDFPointCloud(pts, nrm, col)
 
     def extract_voxel_point_cloud(self):
         """Open3D's extract_voxel_point_cloud: the centre of every observed voxel with (tsdf + 1) / 2 as its colour."""
-        pts, (col,) = self._extract(self._lib.teaser_hip_tsdf_extract_voxel_point_cloud, [True])
+        pts, (col,) = self._extract(self._fn("extract_voxel_point_cloud"), [True])
         return TSDFPointCloud(pts, None, col)
 
+
+class UniformTSDFVolume(_TSDFHandle):
+    """Open3D's UniformTSDFVolume(length, resolution, sdf_trunc, color_type, origin): a cube of resolution^3 voxels with
+    its corner at ``origin``, kept on ``device`` (-1: the current one)."""
+
+    def __init__(self, length, resolution, sdf_trunc, color_type=TSDFVolumeColorType.NoColor, origin=(0.0, 0.0, 0.0),
+                 device=-1):
+        from . import TeaserHipError, lib
+        if int(resolution) != resolution or not 1 <= int(resolution) <= 1024:
+            raise ValueError("resolution must be an integer in [1, 1024]")
+        if not (math.isfinite(float(length)) and float(length) > 0):
+            raise ValueError("length must be finite and > 0")
+        if not (math.isfinite(float(sdf_trunc)) and float(sdf_trunc) > 0):
+            raise ValueError("sdf_trunc must be finite and > 0")
+        if color_type not in (0, 1, 2):
+            raise ValueError("color_type must be one of TSDFVolumeColorType.NoColor, RGB8, Gray32")
+        o = np.asarray(origin, dtype=np.float64)
+        if o.shape != (3,) or not np.isfinite(o).all():
+            raise ValueError("origin must be three finite numbers")
+        self.length, self.sdf_trunc, self.color_type = float(length), float(sdf_trunc), int(color_type)
+        self._resolution, self.origin = int(resolution), o.copy()
+        self._lib = lib()
+        rec = TsdfVolumeC()
+        self._lib.teaser_hip_tsdf_volume_default(C.byref(rec))
+        rec.length, rec.sdf_trunc, rec.resolution, rec.color_type = self.length, self.sdf_trunc, self._resolution, self.color_type
+        rec.origin[:] = list(o)
+        self._h = _vp()
+        self._lock = threading.Lock()
+        rc = self._lib.teaser_hip_tsdf_create(C.byref(rec), int(device), C.byref(self._h))
+        if rc != 0:
+            self._h = None
+            msg = self._lib.teaser_hip_tsdf_last_error(None).decode()
+            raise TeaserHipError(rc, "(no MI355X visible: the product has no CPU path)" if rc == 3 else msg)
+
+    @property
+    def voxel_length(self):
+        return self.length / self._resolution
+
+    @property
+    def resolution(self):
+        return self._resolution
+
+    def _integrate_call(self, b, frames, depth, color):
+        self._call(self._lib.teaser_hip_tsdf_integrate_batch, b, frames, depth, color)
+
+    # ---- extraction ---------------------------------------------------------------------------------------------
     def extract_triangle_mesh(self, vertex_normals=False):
         """Open3D's extract_triangle_mesh: marching cubes over the observed cubes, vertices and triangles in the order
         of Open3D's loop, with vertex colours for a volume with a colour type.  vertex_normals=True adds the TSDF
@@ -430,5 +467,101 @@ class UniformTSDFVolume:
         self._call(self._lib.teaser_hip_tsdf_reset)
 
 
-__all__ = ["UniformTSDFVolume", "TSDFVolumeColorType", "TSDFPointCloud", "TSDFTriangleMesh", "TSDFRayCastResult",
+class ScalableTSDFVolume(_TSDFHandle):
+    """Open3D's ScalableTSDFVolume(voxel_length, sdf_trunc, color_type, volume_unit_resolution, depth_sampling_stride):
+    only the blocks of 16^3 voxels that depth frames have come near are kept, so the scene needs no bounds.  The rules
+    are written out in include/teaser_hip.h ("Scalable TSDF volume").  initial_blocks, slab_blocks and max_blocks (None:
+    the library's defaults; max_blocks 0: no limit) size the memory the blocks lie in.  ``last_counts`` holds
+    (touched, opened, out_of_range) of the last integrate call.  extract_triangle_mesh and ray casting are not offered."""
+    _prefix = "teaser_hip_stsdf"
+
+    def __init__(self, voxel_length, sdf_trunc, color_type=TSDFVolumeColorType.NoColor, volume_unit_resolution=16,
+                 depth_sampling_stride=4, device=-1, initial_blocks=None, slab_blocks=None, max_blocks=None):
+        from . import TeaserHipError, lib
+        if color_type not in (0, 1, 2):
+            raise ValueError("color_type must be one of TSDFVolumeColorType.NoColor, RGB8, Gray32")
+        self.voxel_length, self.sdf_trunc, self.color_type = float(voxel_length), float(sdf_trunc), int(color_type)
+        self.volume_unit_resolution, self.depth_sampling_stride = int(volume_unit_resolution), int(depth_sampling_stride)
+        self.last_counts = (0, 0, 0)
+        self._lib = lib()
+        rec = StsdfVolumeC()
+        self._lib.teaser_hip_stsdf_volume_default(C.byref(rec))
+        rec.voxel_length, rec.sdf_trunc, rec.color_type = self.voxel_length, self.sdf_trunc, self.color_type
+        rec.volume_unit_resolution, rec.depth_sampling_stride = self.volume_unit_resolution, self.depth_sampling_stride
+        for name, v in (("initial_blocks", initial_blocks), ("slab_blocks", slab_blocks), ("max_blocks", max_blocks)):
+            if v is not None:
+                setattr(rec, name, int(v))
+        self._h = _vp()
+        self._lock = threading.Lock()
+        rc = self._lib.teaser_hip_stsdf_create(C.byref(rec), int(device), C.byref(self._h))
+        if rc != 0:
+            self._h = None
+            msg = self._lib.teaser_hip_stsdf_last_error(None).decode()
+            raise TeaserHipError(rc, "(no MI355X visible: the product has no CPU path)" if rc == 3 else msg)
+
+    def _integrate_call(self, b, frames, depth, color):
+        t, o, r = C.c_int64(0), C.c_int64(0), C.c_int64(0)
+        try:
+            self._call(self._lib.teaser_hip_stsdf_integrate_frames, b, frames, depth, color, C.byref(t), C.byref(o), C.byref(r))
+        finally:
+            self.last_counts = (int(t.value), int(o.value), int(r.value))
+
+    def last_phases_ms(self):
+        """DIAGNOSTIC (teaser_hip_stsdf_last_phases): the host's clock over the last integrate call, in milliseconds:
+        (upload, touch pass and read-back; directory merge; zeroing and integration)."""
+        ms = (C.c_double * 3)()
+        self._call(self._lib.teaser_hip_stsdf_last_phases, ms)
+        return tuple(ms)
+
+    # ---- the blocks ---------------------------------------------------------------------------------------------
+    @property
+    def block_count(self):
+        n = C.c_int64(0)
+        self._call(self._lib.teaser_hip_stsdf_block_count, C.byref(n))
+        return int(n.value)
+
+    @property
+    def block_bytes(self):
+        """Device bytes of one block."""
+        return (32 if self.color_type != TSDFVolumeColorType.NoColor else 8) * self.volume_unit_resolution ** 3
+
+    def block_keys(self):
+        """blocks x 3 int32: (bx, by, bz) of every open block in ascending order."""
+        n = self.block_count
+        keys, cnt = np.empty((n, 3), dtype=np.int32), C.c_int64(0)
+        if n:
+            self._call(self._lib.teaser_hip_stsdf_block_keys, n, keys.ctypes.data_as(_i32p), C.byref(cnt))
+        return keys
+
+    def extract_blocks(self):
+        """(keys, tsdf_weight, color): blocks x 3 int32, blocks x 4096 x 2 float32 (tsdf, weight) and blocks x 4096 x 3
+        float64 (None without a colour type), the blocks in ascending order and Open3D's voxel order inside."""
+        keys = self.block_keys()
+        n, v, cnt = len(keys), self.volume_unit_resolution ** 3, C.c_int64(0)
+        tw = np.empty((n, v, 2), dtype=np.float32)
+        col = np.empty((n, v, 3)) if self.color_type != TSDFVolumeColorType.NoColor else None
+        if n:
+            self._call(self._lib.teaser_hip_stsdf_download_blocks, n, tw.ctypes.data_as(_fp),
+                       None if col is None else col.ctypes.data_as(_dp), C.byref(cnt))
+        return keys, tw, col
+
+    def inject_blocks(self, keys, tsdf_weight=None, color=None):
+        """The voxels of the blocks ``keys`` (n x 3, any order, none twice); a block that is not open is opened first."""
+        k = np.ascontiguousarray(keys, dtype=np.int32).reshape(-1, 3)
+        n, v = len(k), self.volume_unit_resolution ** 3
+        tw = None if tsdf_weight is None else np.ascontiguousarray(tsdf_weight, dtype=np.float32)
+        col = None if color is None else np.ascontiguousarray(color, dtype=np.float64)
+        if tw is not None and tw.shape != (n, v, 2):
+            raise ValueError("tsdf_weight must have shape %d x %d x 2, got %s" % (n, v, tw.shape))
+        if col is not None and col.shape != (n, v, 3):
+            raise ValueError("color must have shape %d x %d x 3, got %s" % (n, v, col.shape))
+        self._call(self._lib.teaser_hip_stsdf_upload_blocks, n, k.ctypes.data_as(_i32p),
+                   None if tw is None else tw.ctypes.data_as(_fp), None if col is None else col.ctypes.data_as(_dp))
+
+    def reset(self):
+        """Closes every block."""
+        self._call(self._lib.teaser_hip_stsdf_reset)
+
+
+__all__ = ["UniformTSDFVolume", "ScalableTSDFVolume", "TSDFVolumeColorType", "TSDFPointCloud", "TSDFTriangleMesh", "TSDFRayCastResult",
            "write_triangle_mesh"]
