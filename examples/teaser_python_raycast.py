@@ -11,9 +11,11 @@ with an intensity that is a function of the surface point, and a camera that mov
 
 It prints how far the model's depth lies from the analytically rendered depth of the same pose, and the pose error of
 frame-to-model odometry beside that of frame-to-frame odometry (the second-to-last camera frame against the last).
+With --scalable the model is a ScalableTSDFVolume with the same voxels and truncation -- only the blocks of 16^3 voxels
+near the surface exist, and the space needs no bounds -- rendered by tp.ray_cast, which serves either volume class.
 Exit code 77: no MI355X visible.  Usage:
 
-    python examples/teaser_python_raycast.py [--width 320 --height 240] [--frames 8] [--resolution 128]
+    python examples/teaser_python_raycast.py [--width 320 --height 240] [--frames 8] [--resolution 128] [--scalable]
 """
 import argparse
 import importlib
@@ -51,6 +53,7 @@ def main():
     ap.add_argument("--height", type=int, default=240)
     ap.add_argument("--frames", type=int, default=8)
     ap.add_argument("--resolution", type=int, default=128)
+    ap.add_argument("--scalable", action="store_true", help="keep the model in a ScalableTSDFVolume with the same voxels")
     a = ap.parse_args()
     if a.frames < 3:
         sys.exit("--frames must be at least 3")
@@ -59,14 +62,22 @@ def main():
         sys.exit(77)
     K, poses, depths, paints = odo.sequence(a.width, a.height, a.frames)
     length, R, trunc, origin = fusion.volume_settings(a.resolution)
-    with tp.UniformTSDFVolume(length, R, trunc, tp.TSDFVolumeColorType.Gray32, origin) as vol:
+    if a.scalable:
+        vol = tp.ScalableTSDFVolume(length / R, trunc, tp.TSDFVolumeColorType.Gray32)
+    else:
+        vol = tp.UniformTSDFVolume(length, R, trunc, tp.TSDFVolumeColorType.Gray32, origin)
+    with vol:
         t0 = time.perf_counter()
         vol.integrate_batch(depths[:-1], K, [np.linalg.inv(p) for p in poses[:-1]], paints[:-1], depth_scale=1000.0, depth_trunc=DEPTH_MAX)
         t1 = time.perf_counter()
-        model = vol.ray_cast(K, np.linalg.inv(poses[-2]), depth_max=DEPTH_MAX, weight_threshold=min(3.0, a.frames - 1.0))
+        model = tp.ray_cast(vol, K, np.linalg.inv(poses[-2]), depth_max=DEPTH_MAX, weight_threshold=min(3.0, a.frames - 1.0))
         t2 = time.perf_counter()
         voxel = vol.voxel_length
-    print("integration: %d frames of %d x %d into %d^3 voxels, %.1f ms" % (a.frames - 1, a.width, a.height, R, 1e3 * (t1 - t0)))
+        blocks = vol.block_count if a.scalable else 0
+    if a.scalable:
+        print("integration: %d frames of %d x %d into %d blocks of 16^3 voxels, %.1f ms" % (a.frames - 1, a.width, a.height, blocks, 1e3 * (t1 - t0)))
+    else:
+        print("integration: %d frames of %d x %d into %d^3 voxels, %.1f ms" % (a.frames - 1, a.width, a.height, R, 1e3 * (t1 - t0)))
     print("ray cast at pose %d: %d of %d pixels hit, %.1f ms" % (a.frames - 2, model.hits, a.width * a.height, 1e3 * (t2 - t1)))
     n, med, p95, worst = depth_error(model.depth, metres(depths[-2]), voxel)
     print("model depth against the analytic depth: %d pixels, median %.17g, 95th percentile %.17g, max %.6f voxels" % (n, med, p95, worst))

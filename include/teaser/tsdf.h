@@ -11,6 +11,7 @@
 #include <cstdint>
 #include <stdexcept>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "teaser/handle.h"
@@ -56,6 +57,52 @@ struct TSDFRayCastResult {
   std::vector<float> depth, vertex_map, normal_map, color;
   int64_t hits = 0;  // the pixels that met a surface
 };
+
+namespace detail {
+
+// The records, results and pointers of one ray-cast call, which both volume classes hand to their entry point.
+struct RayCastCall {
+  std::vector<teaser_tsdf_view_c> rec;
+  std::vector<TSDFRayCastResult> out;
+  std::vector<float*> pd, pv, pn, pc;
+  std::vector<int64_t> hits;
+
+  RayCastCall(const char* who, const std::vector<PinholeCameraIntrinsic>& intrinsics, const std::vector<Matrix4>& extrinsics,
+              const std::vector<int>& widths, const std::vector<int>& heights, const TSDFRayCastOptions& options, bool colored) {
+    const size_t b = extrinsics.size();
+    if ((intrinsics.size() != 1 && intrinsics.size() != b) || (widths.size() != 1 && widths.size() != b) ||
+        (heights.size() != 1 && heights.size() != b))
+      throw std::invalid_argument(std::string(who) + ": one intrinsic, width and height (or one per view)");
+    rec.resize(b), out.resize(b), pd.resize(b), pv.resize(b), pn.resize(b), pc.resize(b), hits.assign(b, 0);
+    for (size_t k = 0; k < b; ++k) {
+      const PinholeCameraIntrinsic& K = intrinsics[intrinsics.size() == 1 ? 0 : k];
+      teaser_tsdf_view_c& r = rec[k];
+      teaser_hip_tsdf_view_default(&r);
+      r.width = widths[widths.size() == 1 ? 0 : k], r.height = heights[heights.size() == 1 ? 0 : k];
+      r.fx = K.fx, r.fy = K.fy, r.cx = K.cx, r.cy = K.cy;
+      row_major(extrinsics[k], r.extrinsic);
+      r.depth_min = options.depth_min, r.depth_max = options.depth_max, r.weight_threshold = options.weight_threshold;
+      TSDFRayCastResult& o = out[k];
+      o.width = r.width, o.height = r.height;
+      const size_t px = r.width > 0 && r.height > 0 ? (size_t)r.width * (size_t)r.height : 0;
+      o.depth.assign(px, 0.0f);
+      if (options.vertex_map) o.vertex_map.assign(3 * px, 0.0f);
+      if (options.normal_map) o.normal_map.assign(3 * px, 0.0f);
+      if (colored) o.color.assign(3 * px, 0.0f);
+      pd[k] = px ? o.depth.data() : nullptr;
+      pv[k] = px && options.vertex_map ? o.vertex_map.data() : nullptr;
+      pn[k] = px && options.normal_map ? o.normal_map.data() : nullptr;
+      pc[k] = px && colored ? o.color.data() : nullptr;
+    }
+  }
+
+  std::vector<TSDFRayCastResult> results() {
+    for (size_t k = 0; k < out.size(); ++k) out[k].hits = hits[k];
+    return std::move(out);
+  }
+};
+
+}  // namespace detail
 
 class UniformTSDFVolume {
  public:
@@ -166,38 +213,11 @@ class UniformTSDFVolume {
                                               const std::vector<Matrix4>& extrinsics, const std::vector<int>& widths,
                                               const std::vector<int>& heights,
                                               const TSDFRayCastOptions& options = TSDFRayCastOptions()) {
-    const size_t b = extrinsics.size();
-    if ((intrinsics.size() != 1 && intrinsics.size() != b) || (widths.size() != 1 && widths.size() != b) ||
-        (heights.size() != 1 && heights.size() != b))
-      throw std::invalid_argument("teaser::UniformTSDFVolume: one intrinsic, width and height (or one per view)");
-    const bool colored = options.color && color_type_ != TSDFVolumeColorType::NoColor;
-    std::vector<teaser_tsdf_view_c> rec(b);
-    std::vector<TSDFRayCastResult> out(b);
-    std::vector<float*> pd(b), pv(b), pn(b), pc(b);
-    std::vector<int64_t> hits(b, 0);
-    for (size_t k = 0; k < b; ++k) {
-      const PinholeCameraIntrinsic& K = intrinsics[intrinsics.size() == 1 ? 0 : k];
-      teaser_tsdf_view_c& r = rec[k];
-      teaser_hip_tsdf_view_default(&r);
-      r.width = widths[widths.size() == 1 ? 0 : k], r.height = heights[heights.size() == 1 ? 0 : k];
-      r.fx = K.fx, r.fy = K.fy, r.cx = K.cx, r.cy = K.cy;
-      detail::row_major(extrinsics[k], r.extrinsic);
-      r.depth_min = options.depth_min, r.depth_max = options.depth_max, r.weight_threshold = options.weight_threshold;
-      TSDFRayCastResult& o = out[k];
-      o.width = r.width, o.height = r.height;
-      const size_t px = r.width > 0 && r.height > 0 ? (size_t)r.width * (size_t)r.height : 0;
-      o.depth.assign(px, 0.0f);
-      if (options.vertex_map) o.vertex_map.assign(3 * px, 0.0f);
-      if (options.normal_map) o.normal_map.assign(3 * px, 0.0f);
-      if (colored) o.color.assign(3 * px, 0.0f);
-      pd[k] = px ? o.depth.data() : nullptr;
-      pv[k] = px && options.vertex_map ? o.vertex_map.data() : nullptr;
-      pn[k] = px && options.normal_map ? o.normal_map.data() : nullptr;
-      pc[k] = px && colored ? o.color.data() : nullptr;
-    }
-    check(teaser_hip_tsdf_ray_cast_views(h_, (int32_t)b, rec.data(), pd.data(), pv.data(), pn.data(), pc.data(), hits.data()));
-    for (size_t k = 0; k < b; ++k) out[k].hits = hits[k];
-    return out;
+    detail::RayCastCall c("teaser::UniformTSDFVolume", intrinsics, extrinsics, widths, heights, options,
+                          options.color && color_type_ != TSDFVolumeColorType::NoColor);
+    check(teaser_hip_tsdf_ray_cast_views(h_, (int32_t)c.rec.size(), c.rec.data(), c.pd.data(), c.pv.data(), c.pn.data(),
+                                         c.pc.data(), c.hits.data()));
+    return c.results();
   }
 
   // resolution^3 x 2 floats (tsdf, weight) in Open3D's voxel order (x R + y) R + z.
@@ -235,7 +255,8 @@ class UniformTSDFVolume {
 };
 
 // Open3D's ScalableTSDFVolume: only the blocks of 16^3 voxels that depth frames have come near are stored (include/
-// teaser_hip.h, "Scalable TSDF volume").  extractTriangleMesh and rayCast are not offered here.
+// teaser_hip.h, "Scalable TSDF volume"), and rayCast / rayCastBatch render them into cameras ("Scalable TSDF ray
+// casting") with the dense class's options and result.  extractTriangleMesh is not offered here.
 class ScalableTSDFVolume {
  public:
   // What the last integrate call reported: (frame, block) pairs touched, blocks opened, and (frame, point) pairs with
@@ -316,6 +337,26 @@ class ScalableTSDFVolume {
     if (count > 0)
       check(teaser_hip_stsdf_extract_voxel_point_cloud(h_, count, out.points.data(), out.colors.data(), &count));
     return out;
+  }
+
+  // The fused model seen from a camera (Open3D's VoxelBlockGrid::RayCast): per pixel the z-depth of the first surface
+  // its ray meets in the open blocks, the world point, the normal and the colour.  The rules: include/teaser_hip.h,
+  // "Scalable TSDF ray casting".
+  TSDFRayCastResult rayCast(const PinholeCameraIntrinsic& intrinsic, const Matrix4& extrinsic, int width, int height,
+                            const TSDFRayCastOptions& options = TSDFRayCastOptions()) {
+    return rayCastBatch({intrinsic}, {extrinsic}, {width}, {height}, options)[0];
+  }
+
+  // All views in one call: one launch, one synchronisation.  intrinsics, widths, heights: one for all or one per view.
+  std::vector<TSDFRayCastResult> rayCastBatch(const std::vector<PinholeCameraIntrinsic>& intrinsics,
+                                              const std::vector<Matrix4>& extrinsics, const std::vector<int>& widths,
+                                              const std::vector<int>& heights,
+                                              const TSDFRayCastOptions& options = TSDFRayCastOptions()) {
+    detail::RayCastCall c("teaser::ScalableTSDFVolume", intrinsics, extrinsics, widths, heights, options,
+                          options.color && color_type_ != TSDFVolumeColorType::NoColor);
+    check(teaser_hip_stsdf_ray_cast_views(h_, (int32_t)c.rec.size(), c.rec.data(), c.pd.data(), c.pv.data(), c.pn.data(),
+                                          c.pc.data(), c.hits.data()));
+    return c.results();
   }
 
   int64_t blockCount() {

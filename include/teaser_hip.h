@@ -2385,7 +2385,7 @@ TEASER_HIP_API int32_t teaser_hip_tsdf_ray_cast_views(teaser_hip_tsdf* tsdf, int
  * memory and fixes what Open3D leaves to an unordered map; Open3D is not run and bit parity with an Open3D binary is NOT
  * claimed.  Every deliberate difference is marked DEPARTURE.  tests/stsdf_reference.py restates this text in numpy and
  * is the parity target of the host and GPU tests.  No product-add is fused and every sum is taken left to right as
- * written.  extract_triangle_mesh and ray casting are not offered on this handle.
+ * written.  Ray casting is "Scalable TSDF ray casting" below; extract_triangle_mesh is not offered on this handle.
  *
  * Parameters.  voxel_length, sdf_trunc, color_type (0 none, 1 RGB8, 2 Gray32) as for "TSDF volume";
  * volume_unit_resolution U (default 16): this version supports ONLY 16 and refuses 4, 8 and 32 by name;
@@ -2502,6 +2502,73 @@ TEASER_HIP_API int32_t teaser_hip_stsdf_download_blocks(teaser_hip_stsdf* stsdf,
                                                         double* color, int64_t* count_out);
 TEASER_HIP_API int32_t teaser_hip_stsdf_upload_blocks(teaser_hip_stsdf* stsdf, int64_t n_blocks, const int32_t* keys,
                                                       const float* tsdf_weight, const double* color);
+
+/* Scalable TSDF ray casting: the open blocks of a scalable TSDF handle rendered into cameras -- per pixel the z-depth,
+ * the world point, the normal and the colour of the first surface a ray meets.  It is the operation of Open3D's
+ * t.geometry.VoxelBlockGrid.ray_cast, restated for the blocks of "Scalable TSDF volume"; Open3D is not run and bit
+ * parity with an Open3D binary is NOT claimed.  The text below IS the contract; tests/stsdf_raycast_reference.py
+ * restates it in numpy and is the parity target of the host and GPU tests.  Every deliberate difference from "TSDF ray
+ * casting" or from Open3D is marked DEPARTURE.  No product-add is fused, every sum is taken left to right as written,
+ * every min and max is written as a comparison (so a NaN's path is stated), float32 divisions are correctly rounded.
+ *
+ * The view is the record teaser_tsdf_view_c of "TSDF ray casting" and is built as there with origin = 0: c_k as there
+ * in double, o_f[k] = (float)c_k (the world coordinates of the centre), Rt_f, fx_f, fy_f, cx_f, cy_f, dmin_f, dmax_f,
+ * wthr_f as there; vl_f = (float)vl, trunc_f = (float)sdf_trunc, ul_f = (float)ul.  There is no box and no clip:
+ * t0 = dmin_f, t1 = dmax_f.  The host forms in double the step cap
+ *   n_cap = min(2^20, floor(((double)dmax_f - (double)dmin_f) / (double)vl_f) + 2).
+ * The ray of pixel (v, u) is that of "TSDF ray casting"; the point at t is o_f + t d and t is the z-depth.
+ *
+ * The march.  t = t0, t_prev = t0, f_prev = -1.0f.  At most n_cap steps; a ray that has taken them all is a MISS (every
+ * step is at least vl_f long, so a ray that ends earlier by the cap than by t1 has met a rounding t + step == t; the cap
+ * exists so that the loop ends whatever the floats do).  Each step, in order:
+ *   1. MISS unless t <= t1  (a NaN misses).
+ *   2. p_k = o_k + t d_k;  g_k = floorf(p_k / vl_f): the voxel of the sample on the global lattice.
+ *   3. MISS when any g_k is NaN or not in [-2^24, 2^24), tested as a float before any conversion (DEPARTURE: out there
+ *      float32 no longer resolves a voxel; the dense ray cast treats the outside of its box as unobserved and goes on).
+ *   4. B_k = floorf(g_k / 16.0f);  l_k = g_k - 16.0f B_k.  Both are exact, B_k lies in [-2^20, 2^20) and l_k in [0, 16).
+ *   5. Block B is OPEN: f = the tsdf and w = the weight of its voxel (l_0, l_1, l_2).  HIT when
+ *      f_prev > 0.0f && w >= wthr_f && f <= 0.0f.  Otherwise t_prev = t, f_prev = f;  delta = f trunc_f;
+ *      t = t + (delta < vl_f ? vl_f : delta).
+ *   6. Block B is NOT open: nothing is observed there, f = w = 0, and the sample is never a hit (DEPARTURE: with
+ *      weight_threshold <= 0 the dense rule ends a ray that leaves its box from a positive voxel; here absent space ends
+ *      no ray).  t_prev = t, f_prev = 0, and the ray skips to the face it leaves the block by: for every axis k = 0, 1, 2
+ *      in turn with d_k != 0.0f,
+ *        face_k = (d_k > 0.0f ? B_k + 1.0f : B_k) ul_f;  e_k = (face_k - o_k) / d_k;
+ *        t_exit = e_k for the first such axis, then t_exit = e_k < t_exit ? e_k : t_exit;
+ *      t_next = t + vl_f;  t = t_exit > t_next ? t_exit : t_next;  with no such axis t = t_next.  The ray always advances
+ *      by at least a voxel, so a rounding that lands it just short of the face costs one more step and no surface.
+ *      (DEPARTURE: Open3D bounds the march of a tile of pixels by the depth range of the blocks projected into it; the
+ *      skip reaches the same blocks ray by ray and needs no second pass.)
+ * As in "TSDF ray casting", a surface met out of unobserved or absent space (f_prev = 0) is not a hit, and a camera that
+ * starts behind a surface sees nothing until its ray has passed an observed positive voxel.  A block is looked up anew
+ * only when B differs from the last sample's; the look-up is a function of B alone, so no bit depends on that.
+ *
+ * A hit.  t* = (t f_prev - t_prev f) / (f_prev - f) in float32;  depth = t*.  In double
+ *   q_k = (double)o_k + (double)t* (double)d_k   (world coordinates);  vertex_k = q_k rounded to float32.
+ * NEAR: every |q_k| <= (2^24 + 2) vl (double; a NaN is not near).  A hit that is not near has the normal and the
+ * colour 0 (DEPARTURE; it keeps an enormous q from being converted to an integer).  Otherwise:
+ *   normal: the normal rule of teaser_hip_stsdf_extract_point_cloud at q -- T on the GLOBAL lattice, a corner in a block
+ *   that is not open has the value 0, g = 0.99 vl, the dense normalisation -- rounded to float32.
+ *   colour (a volume with a colour type): the colour rule of "TSDF ray casting" over the eight corners of q on the
+ *   global lattice, corner g + offset lying in block floor_div(g + offset, 16) at the local index
+ *   (g + offset) - 16 floor_div(g + offset, 16): a corner COUNTS when its block is open and its voxel weight is != 0;
+ *   the same weights, order and division; / 255.0 for RGB8 only; rounded to float32, a NaN (a Gray32 volume) stored as
+ *   the quiet NaN 0x7fc00000.
+ * A missed pixel is 0 in every output.  In a volume with no open block every pixel misses, the maps are zeros and no
+ * voxel address is formed.
+ *
+ * teaser_hip_stsdf_ray_cast_views takes the arguments of teaser_hip_tsdf_ray_cast_views with the scalable handle: the
+ * arrays of n_views host pointers, any of them or any entry NULL, the packed row-major float32 maps, hit_counts.  One
+ * launch covers all pixels of all views of any mix of sizes (blocks of 16 x 16 pixels and a block map), one stream
+ * synchronisation per call; the maps come back through the handle's page-locked buffer and only the requested ones are
+ * computed and copied.  The directory's device copy is uploaded again only when blocks were opened or closed since the
+ * last upload.  The call modifies neither the blocks nor the directory, is stream-ordered after earlier integrations on
+ * the handle, uses no atomic of any kind and gives the same bits run after run and for any grouping of the views into
+ * calls.  The refusals and their texts are those of teaser_hip_tsdf_ray_cast_views. */
+TEASER_HIP_API int32_t teaser_hip_stsdf_ray_cast_views(teaser_hip_stsdf* stsdf, int32_t n_views,
+                                                       const teaser_tsdf_view_c* views, float* const* depth,
+                                                       float* const* vertex, float* const* normal, float* const* color,
+                                                       int64_t* hit_counts);
 
 /* Page-locked host memory from the HIP runtime THIS library runs on.  teaser_hip_submit_batch(..., INPUT_HOST) moves
  * the points with one DMA copy per cloud, at PCIe speed only when the runtime knows the pages are locked.  A buffer

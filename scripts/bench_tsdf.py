@@ -47,7 +47,18 @@ per frame and split by the library's own clock into touch pass, directory merge 
 blocks opened and the device bytes they hold beside the dense cube's; and the dense volume's times on the same frames in
 the same process, measured in alternation with the scalable ones (that is the comparison: the dense path is unchanged).
 
-    python scripts/bench_tsdf.py --scalable --sizes 512 --reps 9 --warmup 1 --out profiles/tsdf_scalable/bench_tsdf_scalable.json"""
+    python scripts/bench_tsdf.py --scalable --sizes 512 --reps 9 --warmup 1 --out profiles/tsdf_scalable/bench_tsdf_scalable.json
+
+`--scalable --ray-cast` measures the ray cast of the scalable volume (profiles/tsdf_scalable_raycast/): the 64 RGB8 frames
+into a ScalableTSDFVolume with the voxels of every size of `--sizes` and, in the same process, into the dense volume; one
+640 x 480 view at the first pose with all maps and with the depth alone and 16 views in one call on both, measured in
+alternation; extract_point_cloud(normals=False) + project_to_depth_image on the scalable volume; and, from the trace of
+the numpy restatement (tests/stsdf_raycast_reference.py) on the very volume that was timed (the first of `--sizes`, all 64
+frames, downloaded) and a 160 x 120 view, which must equal the device's maps: the steps per ray, the share of them in blocks that are not open and
+the directory searches (block changes) per ray.  `--profile-workload scalable_ray_cast` runs three single-view and three
+16-view calls on both volumes for rocprofv3.
+
+    python scripts/bench_tsdf.py --scalable --ray-cast --sizes 512 --reps 9 --warmup 1 --out profiles/tsdf_scalable_raycast/bench_tsdf_scalable_raycast.json"""
 import argparse
 import ctypes as C
 import importlib
@@ -259,6 +270,95 @@ def ray_cast_restatement(K, d, e, c):
                 steps_histogram_by_8=np.bincount(steps // 8).tolist())
 
 
+def make_scalable(R, colour):
+    length, R, trunc, _ = ex.volume_settings(R)
+    return tp.ScalableTSDFVolume(length / R, trunc, tp.TSDFVolumeColorType.RGB8 if colour else tp.TSDFVolumeColorType.NoColor)
+
+
+def run_scalable_ray_cast(R, K, d, e, c, reps, warmup):
+    res = dict(R=R, colour=True, width=W, height=H)
+    views = e[:POSES]
+    kw = dict(depth_max=6.0, weight_threshold=3.0)
+    only = dict(vertex_map=False, normal_map=False, color=False)
+    with make_scalable(R, 1) as vol, make(R, 1) as dense:
+        one_call(vol, K, d, e, c)
+        one_call(dense, K, d, e, c)
+        res["blocks"], res["scalable_bytes"], res["dense_bytes"] = vol.block_count, vol.block_count * vol.block_bytes, 32 * R ** 3
+        full, again, ref = tp.ray_cast(vol, K, views[0], **kw), tp.ray_cast(vol, K, views[0], **kw), dense.ray_cast(K, views[0], **kw)
+        res["hits"], res["filled_share"], res["dense_hits"] = full.hits, full.hits / float(W * H), ref.hits
+        res["same_bits_twice"] = bool(all(getattr(full, n).tobytes() == getattr(again, n).tobytes() for n in ("depth", "vertex_map", "normal_map", "color")))
+        both = (full.depth > 0) & (ref.depth > 0)
+        res["pixels_hit_in_both"] = int(both.sum())
+        res["max_depth_difference_to_dense_in_voxels"] = float(np.abs(full.depth[both] - ref.depth[both]).max() / vol.voxel_length)
+        res["max_distance_to_surface"] = float(ex.distance_to_surface(full.vertex_map[full.depth > 0].astype(np.float64)).max())
+        batch = vol.ray_cast_batch(K, views, **kw)
+        res["batch_equals_single"] = bool(batch[0].depth.tobytes() == full.depth.tobytes() and batch[0].color.tobytes() == full.color.tobytes())
+        # alternating: a scalable measurement, then the dense one of the same kind
+        res["ray_cast_all_maps"] = timed(lambda: tp.ray_cast(vol, K, views[0], **kw), reps, warmup)
+        res["dense_ray_cast_all_maps"] = timed(lambda: dense.ray_cast(K, views[0], **kw), reps, warmup)
+        res["ray_cast_depth_only"] = timed(lambda: tp.ray_cast(vol, K, views[0], **only, **kw), reps, warmup)
+        res["dense_ray_cast_depth_only"] = timed(lambda: dense.ray_cast(K, views[0], **only, **kw), reps, warmup)
+        res["ray_cast_16_views_one_call"] = timed(lambda: vol.ray_cast_batch(K, views, **kw), reps, warmup)
+        res["dense_ray_cast_16_views_one_call"] = timed(lambda: dense.ray_cast_batch(K, views, **kw), reps, warmup)
+        res["ray_cast_16_views_one_call_depth_only"] = timed(lambda: vol.ray_cast_batch(K, views, **only, **kw), reps, warmup)
+        cloud = vol.extract_point_cloud(normals=False)
+        res["surface_points"] = len(cloud.points)
+        img = tp.project_to_depth_image(cloud.points, W, H, K, views[0], depth_scale=1.0, depth_max=6.0)
+        res["projected_filled_share"] = float(np.count_nonzero(img)) / float(W * H)
+        res["extract_then_project"] = timed(lambda: tp.project_to_depth_image(vol.extract_point_cloud(normals=False).points, W, H, K, views[0],
+                                                                              depth_scale=1.0, depth_max=6.0), reps, warmup)
+    return res
+
+
+def scalable_ray_cast_restatement(R, K, d, e):
+    """The numpy restatement on the volume that was timed -- all 64 frames at the voxels of R, fused on the device; the
+    tsdf and the weights do not depend on the colour, so a volume without colour is downloaded -- for a 160 x 120 view at
+    the first pose: equality of the depth, vertex and normal maps and the hit count with the device's, and from the trace
+    the steps, the steps in blocks that are not open and the block changes (directory searches) of every ray."""
+    import stsdf_raycast_reference as SR
+    import stsdf_reference as S
+    import tsdf_reference as T
+    length, R, trunc, _ = ex.volume_settings(R)
+    Ks = tp.PinholeCameraIntrinsic(160, 120, K.fx / 4, K.fy / 4, (K.cx - 1.5) / 4, (K.cy - 1.5) / 4)
+    with make_scalable(R, 0) as g:
+        one_call(g, K, d, e, None)
+        keys, tw, _ = g.extract_blocks()
+        U = S.U
+        # Open3D's voxel order (x U + y) U + z is the restatement's [x, y, z]
+        vol = SR.volume_of_blocks(length / R, trunc, T.NONE, {tuple(int(v) for v in k): (tw[n, :, 0].reshape(U, U, U), tw[n, :, 1].reshape(U, U, U), None)
+                                                             for n, k in enumerate(keys)})
+        lat = SR.Lattice(vol)
+        print("restatement: %d blocks packed, marching" % len(keys), file=sys.stderr, flush=True)
+        trace = []
+        t = time.perf_counter()
+        ref = SR.ray_cast(vol, (Ks.fx, Ks.fy, Ks.cx, Ks.cy), e[0], 160, 120, 0.1, 6.0, 3.0, trace=trace, lat=lat)
+        t1 = time.perf_counter()
+        got = tp.ray_cast(g, Ks, e[0], depth_max=6.0, weight_threshold=3.0)
+    same = (got.hits == ref.hits and got.depth.tobytes() == ref.depth.tobytes() and got.vertex_map.tobytes() == ref.vertex.tobytes()
+            and got.normal_map.tobytes() == ref.normal.tobytes())
+    n = 160 * 120
+    steps, absent, changes, absent_changes = (np.zeros(n, dtype=np.int64) for _ in range(4))
+    last = np.full((n, 3), np.nan, dtype=np.float32)
+    for s in trace:
+        steps += s.active
+        absent += s.active & ~s.open
+        moved = s.active & (s.B != last).any(axis=1)
+        changes += moved
+        absent_changes += moved & ~s.open
+        last[s.active] = s.B[s.active]
+    del trace
+    assert (steps == ref.steps.ravel()).all()
+    print("restatement: %.1f s, marching again without the skip" % (t1 - t), file=sys.stderr, flush=True)
+    slow = SR.ray_cast(vol, (Ks.fx, Ks.fy, Ks.cx, Ks.cy), e[0], 160, 120, 0.1, 6.0, 3.0, skip=False, lat=lat)
+    return dict(R=R, frames=len(d), width=160, height=120, blocks=len(keys), restatement_ms=1e3 * (t1 - t), hits=ref.hits,
+                device_equals_restatement=bool(same), steps_max=int(steps.max()), steps_mean=float(steps.mean()),
+                steps_median=float(np.median(steps)), steps_histogram_by_8=np.bincount(steps // 8).tolist(),
+                steps_in_absent_blocks_mean=float(absent.mean()), share_of_steps_in_absent_blocks=float(absent.sum()) / float(steps.sum()),
+                directory_searches_mean=float(changes.mean()), directory_searches_median=float(np.median(changes)),
+                directory_searches_max=int(changes.max()), directory_searches_that_find_no_block_mean=float(absent_changes.mean()),
+                steps_mean_without_skip=float(slow.steps.mean()), steps_max_without_skip=int(slow.steps.max()), hits_without_skip=slow.hits)
+
+
 def run_scalable(R, colour, K, d, e, c, reps, warmup):
     cc = c if colour else None
     length, R, trunc, _ = ex.volume_settings(R)
@@ -323,7 +423,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--out", default=None)
     ap.add_argument("--sizes", type=int, nargs="+", default=[256, 512])
-    ap.add_argument("--profile-workload", choices=["one_call", "calls", "extract", "mesh", "ray_cast"], default=None)
+    ap.add_argument("--profile-workload", choices=["one_call", "calls", "extract", "mesh", "ray_cast", "scalable_ray_cast"], default=None)
     ap.add_argument("--profile-R", type=int, default=512)
     ap.add_argument("--profile-colour", type=int, default=1)
     ap.add_argument("--mesh", action="store_true", help="measure the triangle mesh instead (profiles/tsdf_mesh/)")
@@ -333,6 +433,15 @@ def main():
     if tp.device_count() < 1:
         sys.exit("bench_tsdf.py needs an MI355X: no HIP device visible")
     K, d, e, c = workload()
+    if a.profile_workload == "scalable_ray_cast":
+        with make_scalable(a.profile_R, 1) as vol, make(a.profile_R, 1) as dense:
+            one_call(vol, K, d, e, c)
+            one_call(dense, K, d, e, c)
+            for rep in range(3):
+                for v in (vol, dense):
+                    tp.ray_cast(v, K, e[0], depth_max=6.0, weight_threshold=3.0)
+                    v.ray_cast_batch(K, e[:POSES], depth_max=6.0, weight_threshold=3.0)
+        return
     if a.profile_workload:
         cc = c if a.profile_colour else None
         with make(a.profile_R, a.profile_colour) as vol:
@@ -355,6 +464,18 @@ def main():
                     vol.extract_voxel_point_cloud()
         return
     out = dict(workload=dict(width=W, height=H, frames=FRAMES, poses=POSES, chunk=CHUNK, hbm_peak=HBM_PEAK), settings=[])
+    if a.scalable and a.ray_cast:
+        for R in a.sizes:
+            r = run_scalable_ray_cast(R, K, d, e, c, a.reps, a.warmup)
+            print(json.dumps(r), flush=True)
+            out["settings"].append(r)
+        out["restatement"] = scalable_ray_cast_restatement(a.sizes[0], K, d, e)
+        print(json.dumps(out["restatement"]), flush=True)
+        if a.out:
+            os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+            with open(a.out, "w") as f:
+                json.dump(out, f, indent=1)
+        return
     if a.scalable:
         for R in a.sizes:
             for colour in (0, 1):

@@ -100,8 +100,11 @@ int32_t open_blocks(teaser_hip_stsdf* h, const std::vector<uint64_t>& fresh) {
   return TEASER_HIP_OK;
 }
 
-// The device copy of the directory: keys, then the blocks' addresses, both in key order.
-int32_t sync_directory(teaser_hip_stsdf* h, StsdfDir* d) {
+}  // namespace
+
+// The device copy of the directory: keys, then the blocks' addresses, both in key order; uploaded only when the
+// directory has changed since the last upload.  stsdf_raycast.hip calls it, too.
+int32_t thip::stsdf_sync_directory(teaser_hip_stsdf* h, StsdfDir* d) {
   const size_t n = h->keys.size();
   const size_t o_base = round_up(sizeof(uint64_t) * std::max<size_t>(n, 1), 256);
   if (h->dir_dirty) {
@@ -120,6 +123,8 @@ int32_t sync_directory(teaser_hip_stsdf* h, StsdfDir* d) {
   d->n = (int32_t)n;
   return TEASER_HIP_OK;
 }
+
+namespace {
 
 int32_t integrate(teaser_hip_stsdf* h, int32_t n_frames, const teaser_tsdf_frame_c* frames, const void* const* depth,
                   const void* const* color, int64_t* touched_out, int64_t* opened_out, int64_t* oor_out) {
@@ -322,7 +327,7 @@ int32_t extract(teaser_hip_stsdf* h, int mode, int64_t capacity, double* points,
   const bool want_n = cap > 0 && normals, want_c = cap > 0 && colors;
   FCHK(h, hipSetDevice(h->device), "hipSetDevice");
   StsdfDir d;
-  const int32_t rc = sync_directory(h, &d);
+  const int32_t rc = stsdf_sync_directory(h, &d);
   if (rc != TEASER_HIP_OK) return rc;
   const size_t o_totals = round_up(sizeof(int64_t) * (size_t)(nb + 1), 256);
   const size_t o_counts = o_totals + round_up(sizeof(int32_t) * (size_t)std::max<int64_t>(nb, 1), 256);
@@ -503,7 +508,7 @@ int32_t teaser_hip_stsdf_download_blocks(teaser_hip_stsdf* h, int64_t capacity, 
   if (n == 0) return TEASER_HIP_OK;
   FCHK(h, hipSetDevice(h->device), "hipSetDevice");
   StsdfDir d;
-  const int32_t rc = sync_directory(h, &d);
+  const int32_t rc = stsdf_sync_directory(h, &d);
   if (rc != TEASER_HIP_OK) return rc;
   const size_t per_tw = 8 * (size_t)kStsdfVoxels, per_c = 24 * (size_t)kStsdfVoxels;
   if (!h->out.ensure((color ? per_c : per_tw) * (size_t)std::min<int64_t>(n, kBatchBlocks)))

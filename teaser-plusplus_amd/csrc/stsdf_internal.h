@@ -41,4 +41,7 @@ inline char* stsdf_block_ptr(const teaser_hip_stsdf* h, int64_t slot) {
   return static_cast<char*>(h->slabs[(size_t)s]) + (size_t)k * h->block_bytes;
 }
 
+// The directory's device copy, brought up to date when blocks were opened or closed since its last upload (stsdf.hip).
+int32_t stsdf_sync_directory(teaser_hip_stsdf* h, StsdfDir* d);
+
 }  // namespace thip

@@ -24,7 +24,7 @@ struct TsdfRayView {
   int32_t width, height;
   int32_t tiles_x;  // blocks across a row of tiles
   int32_t blk0;     // the view's first block
-  int32_t pad;
+  int32_t n_cap;    // the step cap of the scalable volume's march (stsdf_raycast_device.h); 0 and unread in the dense call
   int64_t depth_off, vertex_off, normal_off, color_off;
 };
 

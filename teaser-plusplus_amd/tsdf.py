@@ -93,6 +93,8 @@ def declare(L):
     L.teaser_hip_stsdf_block_keys.argtypes = [_vp, C.c_int64, _i32p, _i64p]
     L.teaser_hip_stsdf_download_blocks.argtypes = [_vp, C.c_int64, _fp, _dp, _i64p]
     L.teaser_hip_stsdf_upload_blocks.argtypes = [_vp, C.c_int64, _i32p, _fp, _dp]
+    L.teaser_hip_stsdf_ray_cast_views.argtypes = [_vp, C.c_int32, C.POINTER(TsdfViewC), C.POINTER(_fp), C.POINTER(_fp),
+                                                  C.POINTER(_fp), C.POINTER(_fp), _i64p]
 
 
 class TSDFVolumeColorType:
@@ -187,7 +189,7 @@ def write_triangle_mesh(path, mesh, binary=True):
 
 class _TSDFHandle:
     """What the dense and the scalable volume share: the handle (``_prefix`` names its entry points), the frame records,
-    integration and the two point-cloud extractions."""
+    integration, the two point-cloud extractions and the ray cast of any number of views."""
     _prefix = "teaser_hip_tsdf"
 
     def _fn(self, name):
@@ -313,6 +315,51 @@ class _TSDFHandle:
         pts, (col,) = self._extract(self._fn("extract_voxel_point_cloud"), [True])
         return TSDFPointCloud(pts, None, col)
 
+    # ---- ray casting --------------------------------------------------------------------------------------------
+    def ray_cast_batch(self, intrinsic, extrinsics, width=None, height=None, depth_min=0.1, depth_max=3.0,
+                       weight_threshold=3.0, vertex_map=True, normal_map=True, color=True):
+        """One TSDFRayCastResult per extrinsic, all views in one call (one launch, one synchronisation).  intrinsic,
+        width, height, depth_min, depth_max, weight_threshold: one for all views or a list with one per view; width
+        and height default to the intrinsic's.  The rules: include/teaser_hip.h, "TSDF ray casting" for the dense volume
+        and "Scalable TSDF ray casting" for the scalable one."""
+        ext = list(extrinsics)
+        b = len(ext)
+        if b == 0:
+            return []
+        intr = _each(intrinsic, b, "intrinsic", _is_intrinsic)
+        K = [_fxfycxcy(k) for k in intr]
+        W, H = _each(width, b, "width", _is_scalar), _each(height, b, "height", _is_scalar)
+        lo, hi = _each(depth_min, b, "depth_min", _is_scalar), _each(depth_max, b, "depth_max", _is_scalar)
+        thr = _each(weight_threshold, b, "weight_threshold", _is_scalar)
+        colored = bool(color) and self.color_type != TSDFVolumeColorType.NoColor
+        views = (TsdfViewC * b)()
+        maps = [[], [], [], []]
+        for k in range(b):
+            v = views[k]
+            self._lib.teaser_hip_tsdf_view_default(C.byref(v))
+            E = np.array(np.eye(4) if ext[k] is None else ext[k], dtype=np.float64)
+            if E.shape != (4, 4):
+                raise ValueError("extrinsic must be a 4 x 4 matrix")
+            w = W[k] if W[k] is not None else getattr(intr[k], "width", None)
+            h = H[k] if H[k] is not None else getattr(intr[k], "height", None)
+            if w is None or h is None:
+                raise ValueError("width and height: the intrinsic carries none, so they must be given")
+            v.width, v.height = int(w), int(h)
+            v.fx, v.fy, v.cx, v.cy = K[k]
+            v.extrinsic[:] = list(E.ravel())
+            v.depth_min, v.depth_max, v.weight_threshold = float(lo[k]), float(hi[k]), float(thr[k])
+            shape = (max(v.height, 0), max(v.width, 0))
+            for m, want in enumerate((True, bool(vertex_map), bool(normal_map), colored)):
+                maps[m].append(np.zeros(shape + ((3,) if m else ()), dtype=np.float32) if want else None)
+
+        def ptrs(arrs):
+            return (_fp * b)(*[None if a is None or a.size == 0 else a.ctypes.data_as(_fp) for a in arrs])
+        hits = (C.c_int64 * b)()
+        self._call(self._fn("ray_cast_views"), b, views, ptrs(maps[0]), ptrs(maps[1]), ptrs(maps[2]),
+                   ptrs(maps[3]), hits)
+        return [TSDFRayCastResult(maps[0][k], maps[1][k], maps[2][k], maps[3][k], int(hits[k]), self.color_type)
+                for k in range(b)]
+
 
 class UniformTSDFVolume(_TSDFHandle):
     """Open3D's UniformTSDFVolume(length, resolution, sdf_trunc, color_type, origin): a cube of resolution^3 voxels with
@@ -377,50 +424,6 @@ class UniformTSDFVolume(_TSDFHandle):
                        C.byref(nt))
         return TSDFTriangleMesh(vert, tri, col, nrm)
 
-    # ---- ray casting --------------------------------------------------------------------------------------------
-    def ray_cast_batch(self, intrinsic, extrinsics, width=None, height=None, depth_min=0.1, depth_max=3.0,
-                       weight_threshold=3.0, vertex_map=True, normal_map=True, color=True):
-        """One TSDFRayCastResult per extrinsic, all views in one call (one launch, one synchronisation).  intrinsic,
-        width, height, depth_min, depth_max, weight_threshold: one for all views or a list with one per view; width
-        and height default to the intrinsic's.  The rules: include/teaser_hip.h, "TSDF ray casting"."""
-        ext = list(extrinsics)
-        b = len(ext)
-        if b == 0:
-            return []
-        intr = _each(intrinsic, b, "intrinsic", _is_intrinsic)
-        K = [_fxfycxcy(k) for k in intr]
-        W, H = _each(width, b, "width", _is_scalar), _each(height, b, "height", _is_scalar)
-        lo, hi = _each(depth_min, b, "depth_min", _is_scalar), _each(depth_max, b, "depth_max", _is_scalar)
-        thr = _each(weight_threshold, b, "weight_threshold", _is_scalar)
-        colored = bool(color) and self.color_type != TSDFVolumeColorType.NoColor
-        views = (TsdfViewC * b)()
-        maps = [[], [], [], []]
-        for k in range(b):
-            v = views[k]
-            self._lib.teaser_hip_tsdf_view_default(C.byref(v))
-            E = np.array(np.eye(4) if ext[k] is None else ext[k], dtype=np.float64)
-            if E.shape != (4, 4):
-                raise ValueError("extrinsic must be a 4 x 4 matrix")
-            w = W[k] if W[k] is not None else getattr(intr[k], "width", None)
-            h = H[k] if H[k] is not None else getattr(intr[k], "height", None)
-            if w is None or h is None:
-                raise ValueError("width and height: the intrinsic carries none, so they must be given")
-            v.width, v.height = int(w), int(h)
-            v.fx, v.fy, v.cx, v.cy = K[k]
-            v.extrinsic[:] = list(E.ravel())
-            v.depth_min, v.depth_max, v.weight_threshold = float(lo[k]), float(hi[k]), float(thr[k])
-            shape = (max(v.height, 0), max(v.width, 0))
-            for m, want in enumerate((True, bool(vertex_map), bool(normal_map), colored)):
-                maps[m].append(np.zeros(shape + ((3,) if m else ()), dtype=np.float32) if want else None)
-
-        def ptrs(arrs):
-            return (_fp * b)(*[None if a is None or a.size == 0 else a.ctypes.data_as(_fp) for a in arrs])
-        hits = (C.c_int64 * b)()
-        self._call(self._lib.teaser_hip_tsdf_ray_cast_views, b, views, ptrs(maps[0]), ptrs(maps[1]), ptrs(maps[2]),
-                   ptrs(maps[3]), hits)
-        return [TSDFRayCastResult(maps[0][k], maps[1][k], maps[2][k], maps[3][k], int(hits[k]), self.color_type)
-                for k in range(b)]
-
     def ray_cast(self, intrinsic, extrinsic, width=None, height=None, depth_min=0.1, depth_max=3.0, weight_threshold=3.0,
                  vertex_map=True, normal_map=True, color=True):
         """The fused model seen from a camera: per pixel the z-depth of the first surface its ray meets (Open3D's
@@ -472,7 +475,10 @@ class ScalableTSDFVolume(_TSDFHandle):
     only the blocks of 16^3 voxels that depth frames have come near are kept, so the scene needs no bounds.  The rules
     are written out in include/teaser_hip.h ("Scalable TSDF volume").  initial_blocks, slab_blocks and max_blocks (None:
     the library's defaults; max_blocks 0: no limit) size the memory the blocks lie in.  ``last_counts`` holds
-    (touched, opened, out_of_range) of the last integrate call.  extract_triangle_mesh and ray casting are not offered."""
+    (touched, opened, out_of_range) of the last integrate call.  ray_cast_batch renders views of the open blocks
+    (include/teaser_hip.h, "Scalable TSDF ray casting"); the single view is the module's ray_cast(volume, ...): Open3D's
+    ScalableTSDFVolume has no method of that name, and this class keeps Open3D's surface.  extract_triangle_mesh is not
+    offered."""
     _prefix = "teaser_hip_stsdf"
 
     def __init__(self, voxel_length, sdf_trunc, color_type=TSDFVolumeColorType.NoColor, volume_unit_resolution=16,
@@ -563,5 +569,20 @@ class ScalableTSDFVolume(_TSDFHandle):
         self._call(self._lib.teaser_hip_stsdf_reset)
 
 
+def ray_cast_batch(volume, intrinsic, extrinsics, width=None, height=None, depth_min=0.1, depth_max=3.0, weight_threshold=3.0,
+                   vertex_map=True, normal_map=True, color=True):
+    """``volume.ray_cast_batch(...)`` for a UniformTSDFVolume or a ScalableTSDFVolume: one TSDFRayCastResult per
+    extrinsic, all views in one call."""
+    return volume.ray_cast_batch(intrinsic, extrinsics, width, height, depth_min, depth_max, weight_threshold, vertex_map,
+                                 normal_map, color)
+
+
+def ray_cast(volume, intrinsic, extrinsic, width=None, height=None, depth_min=0.1, depth_max=3.0, weight_threshold=3.0,
+             vertex_map=True, normal_map=True, color=True):
+    """The fused model of either volume class seen from one camera (UniformTSDFVolume.ray_cast says what comes back)."""
+    return ray_cast_batch(volume, intrinsic, [extrinsic], width, height, depth_min, depth_max, weight_threshold, vertex_map,
+                          normal_map, color)[0]
+
+
 __all__ = ["UniformTSDFVolume", "ScalableTSDFVolume", "TSDFVolumeColorType", "TSDFPointCloud", "TSDFTriangleMesh", "TSDFRayCastResult",
-           "write_triangle_mesh"]
+           "write_triangle_mesh", "ray_cast", "ray_cast_batch"]
