@@ -290,6 +290,13 @@ TEASER_HIP_API int32_t teaser_hip_get_input_ordered_translation_inliers(teaser_h
 TEASER_HIP_API int32_t teaser_hip_get_inlier_graph_bitmap(teaser_hip_solver* h, int32_t problem, uint64_t* buf,
                                            int64_t* len /* words */);
 TEASER_HIP_API int32_t teaser_hip_get_degrees(teaser_hip_solver* h, int32_t problem, int32_t* buf, int64_t* len);
+/* DIAGNOSTIC (tests), on no hot path: the rows of a problem's graph as the device arena holds them -- n rows on a
+ * stride of *stride_words words (ceil(n / 64) rounded up to a multiple of 8: 64 bytes), len = n x stride.  The words
+ * ceil(n / 64) .. stride - 1 of a row are padding and zero.  Unlike teaser_hip_get_inlier_graph_bitmap the call
+ * rebuilds nothing: behind a solve that stored the upper triangle only, the words of row r in front of r / 64 are
+ * whatever an earlier solve left there. */
+TEASER_HIP_API int32_t teaser_hip_get_inlier_graph_rows(teaser_hip_solver* h, int32_t problem, uint64_t* buf,
+                                         int64_t* len /* words */, int32_t* stride_words);
 
 /* Stage entry points (registration.h:584-601), host pointers, 3 x K column-major TIMs/points:
  *   solveForRotation   -> GNCTLSRotationSolver::solveForRotation (registration.cc:764-866);

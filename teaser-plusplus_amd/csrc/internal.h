@@ -31,6 +31,14 @@ struct ProbDesc {
   int64_t bm_off;
   int64_t w_off;
 };
+// Bitmap rows lie on a 64-BYTE STRIDE: row r of a problem with W = ceil(n / 64) words per row starts bm_stride(W) words
+// behind row r - 1, and every bm_off is a multiple of 8 words.  K1 stores a row's words in aligned runs of eight (64
+// bytes); on a stride of W words three runs in four straddled three 32-byte granules instead of two, and the partial
+// granules of neighbouring runs, written by other workgroups at other times, never merged (profiles/r11a).  A row's
+// words W .. bm_stride(W) - 1 are padding: zero on every route that fills a bitmap, read by nobody.  W stays the
+// number of words (and of 64-point tiles) of a row: per-row-word arrays (w_off), LDS rows, compact rows and the
+// public layout (teaser_hip_get_inlier_graph_bitmap: dense n x W) do not know the stride.
+constexpr int bm_stride(int W) { return (W + 7) & ~7; }
 
 // Mutable per-problem device state.
 // The latency-bound tail kernels of a batch run BESIDE the next batch's K1, whose VALU-saturating waves hold

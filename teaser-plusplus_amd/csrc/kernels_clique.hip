@@ -1052,7 +1052,7 @@ __global__ __launch_bounds__(256) void exact_count_kernel(const ProbDesc* __rest
     for (int k = wave; k < xc; k += 4) {
       const int x = xlist[d.pt_off + k];
       if (!((Xb[x >> 6] >> (x & 63)) & 1ull)) continue;
-      const uint64_t* row = bm + (int64_t)x * W;
+      const uint64_t* row = bm + (int64_t)x * bm_stride(W);
       for (int w = lane; w < W; w += 64) {
         const uint64_t v = row[w] & al[w];
         if (v) atomicOr(reinterpret_cast<unsigned long long*>(&Cb[w]), v);
@@ -1208,7 +1208,7 @@ __global__ __launch_bounds__(256) void exact_gather_kernel(const ProbDesc* __res
   const int32_t* order = order_pool + pb.order_off;
   uint64_t* out = bitmap_pool + pb.bm_off;
   for (int i = blockIdx.x * 4 + wave; i < n2; i += gridDim.x * 4) {
-    const uint64_t* row = bitmap + d.bm_off + (int64_t)order[i] * d.W;
+    const uint64_t* row = bitmap + d.bm_off + (int64_t)order[i] * bm_stride(d.W);
     for (int wo = 0; wo < W2; ++wo) {
       const int j = wo * 64 + lane;
       bool e = false;
@@ -1498,7 +1498,7 @@ __global__ __launch_bounds__(64 * kAssignWaves) void colour_assign_kernel(const 
     const int v = list[d.pt_off + it];
     F[lane] = 0ull;  // kColourMaxWords == 64 lanes
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    const uint64_t* row = bitmap + d.bm_off + (int64_t)v * d.W;
+    const uint64_t* row = bitmap + d.bm_off + (int64_t)v * bm_stride(d.W);
     for (int w0 = 0; w0 < d.W; w0 += 64 * kRowWordsPerLane) {
       uint64_t words[kRowWordsPerLane];  // every load of the pass issued before the first use
 #pragma unroll
@@ -1582,7 +1582,7 @@ __global__ __launch_bounds__(64 * kColourWaves) void colour_resolve_kernel(const
     if (consider) {
       const int tv = tn[v];
       const unsigned int pv = colour_hash(v, round, 0xabcdef1u);
-      const uint64_t* row = bitmap + d.bm_off + (int64_t)v * d.W;
+      const uint64_t* row = bitmap + d.bm_off + (int64_t)v * bm_stride(d.W);
       for (int w0 = 0; w0 < d.W; w0 += 64 * kRowWordsPerLane) {
         // rivals: neighbours that bid in this round.  (colbits may already hold winners of this very round -- their
         // bids still count, so it is not used to thin the set; a vertex coloured in an EARLIER round cannot hold tv:
@@ -1777,7 +1777,7 @@ __global__ __launch_bounds__(kPcThreads) void colour_persistent_kernel(
       }
       F[lane] = 0ull;
       __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-      const uint64_t* row = bitmap + d.bm_off + (int64_t)v * d.W;
+      const uint64_t* row = bitmap + d.bm_off + (int64_t)v * bm_stride(d.W);
       for (int w0 = 0; w0 < d.W; w0 += 64 * kRowWordsPerLane) {
         uint64_t words[kRowWordsPerLane];
 #pragma unroll
@@ -1858,7 +1858,7 @@ __global__ __launch_bounds__(kPcThreads) void colour_persistent_kernel(
       if (tv >= 0) {
         const unsigned int mine = 0x8000u | (unsigned int)tv;
         const unsigned int pv = colour_hash(v, r, 0xabcdef1u);
-        const uint64_t* row = bitmap + d.bm_off + (int64_t)v * d.W;
+        const uint64_t* row = bitmap + d.bm_off + (int64_t)v * bm_stride(d.W);
         for (int w0 = 0; w0 < d.W; w0 += 64 * kRowWordsPerLane) {
           uint64_t words[kRowWordsPerLane];
 #pragma unroll
@@ -1985,7 +1985,7 @@ __global__ __launch_bounds__(256) void root_prune_kernel(const ProbDesc* __restr
   for (int root = blockIdx.y; root < xc; root += gridDim.y) {
   const int x = xlist[d.pt_off + root];
   __syncthreads();  // (the previous root's Rx / wsum_ are no longer read)
-  for (int w = threadIdx.x; w < d.W; w += 256) Rx[w] = bm[(int64_t)x * d.W + w] & al[w];
+  for (int w = threadIdx.x; w < d.W; w += 256) Rx[w] = bm[(int64_t)x * bm_stride(d.W) + w] & al[w];
   __syncthreads();
   // this block's slice of x's neighbours: words blockIdx.x*4+wave, stride 4*gridDim.x
   int cnt = 0;
@@ -2000,8 +2000,8 @@ __global__ __launch_bounds__(256) void root_prune_kernel(const ProbDesc* __restr
       const bool two = bits != 0ull;
       const int y1 = two ? w * 64 + __builtin_ctzll(bits) : y0;
       bits &= bits - (two ? 1ull : 0ull);
-      const uint64_t* r0 = bm + (int64_t)y0 * d.W;
-      const uint64_t* r1 = bm + (int64_t)y1 * d.W;
+      const uint64_t* r0 = bm + (int64_t)y0 * bm_stride(d.W);
+      const uint64_t* r1 = bm + (int64_t)y1 * bm_stride(d.W);
       int c0 = 0, c1 = 0;
       for (int k0 = 0; k0 < d.W; k0 += 64 * 8) {
         uint64_t a[8], b[8];
@@ -2164,7 +2164,7 @@ __global__ __launch_bounds__(256) void mis_init_kernel(const ProbDesc* __restric
   uint64_t* nc = mb.nc + (size_t)blockIdx.y * mb.cap * mb.max_W;
   const uint64_t* bm = bitmap + d.bm_off;
   for (int c = blockIdx.x; c < lbc; c += gridDim.x) {
-    const uint64_t* row = bm + (int64_t)cl[c] * d.W;
+    const uint64_t* row = bm + (int64_t)cl[c] * bm_stride(d.W);
     for (int w = threadIdx.x; w < d.W; w += 256) nc[(size_t)c * mb.max_W + w] = row[w];
   }
 }
@@ -2383,7 +2383,7 @@ __global__ __launch_bounds__(256) void mis_accept_kernel(const ProbDesc* __restr
       static_assert(kMisBatch <= 64 && kTpc * kPpt == kMisBatch && kPpt % kGrp == 0, "thread mapping of the adjacency gather");
       const int a = t / kTpc;
       const int ua = a < ncand ? cand[a] : 0;
-      const uint64_t* rowa = bm + (int64_t)ua * W;
+      const uint64_t* rowa = bm + (int64_t)ua * bm_stride(W);
       unsigned long long bits = 0ull;
 #pragma unroll
       for (int g0 = 0; g0 < kPpt; g0 += kGrp) {
@@ -2423,7 +2423,7 @@ __global__ __launch_bounds__(256) void mis_accept_kernel(const ProbDesc* __restr
 #pragma unroll
       for (int q = 0; q < kFly; ++q) {
         if (todo) {
-          rows[q] = bm + (int64_t)cand[__builtin_ctzll(todo)] * W;
+          rows[q] = bm + (int64_t)cand[__builtin_ctzll(todo)] * bm_stride(W);
           todo &= todo - 1ull;
         } else {
           rows[q] = nullptr;
@@ -2500,7 +2500,7 @@ __global__ __launch_bounds__(256) void mis_verify_kernel(const ProbDesc* __restr
     const int cv = col[v];
     if (cv < 0) continue;
     int bad = 0;
-    const uint64_t* row = bitmap + d.bm_off + (int64_t)v * d.W;
+    const uint64_t* row = bitmap + d.bm_off + (int64_t)v * bm_stride(d.W);
     for (int w = lane; w < d.W; w += 64) {
       uint64_t bits = row[w];
       while (bits) {
@@ -2775,7 +2775,7 @@ __global__ __launch_bounds__(kCoreThreads) void kcore_kernel(const ProbDesc* __r
         const int b = __builtin_ctzll(f);
         f &= f - 1;
         if ((ord++ & (kCoreWaves - 1)) != wave) continue;
-        const uint64_t* row = bm + (int64_t)(w * 64 + b) * W;
+        const uint64_t* row = bm + (int64_t)(w * 64 + b) * bm_stride(W);
         for (int x = lane; x < W; x += 64) {
           uint64_t m = row[x] & alive[x];
           while (m) {

@@ -182,7 +182,7 @@ __device__ __forceinline__ void tim_wave_fp64(const double* __restrict__ ps,
                                               const double* __restrict__ pd,
                                               uint64_t* __restrict__ bm, int n, int W, int I,
                                               int Jbase, const EdgeConst& kc, double* cbw) {
-  const int T = W;
+  const int T = W, S = bm_stride(W);  // tiles = words of a row; words between two rows
   const int lane = threadIdx.x & 63;
   const int i = I * 64 + lane;
   const bool vi = i < n;
@@ -234,10 +234,13 @@ __device__ __forceinline__ void tim_wave_fp64(const double* __restrict__ ps,
     const uint64_t colmask = (n - j0 >= 64) ? ~0ull : ((1ull << (n - j0)) - 1ull);
     own &= colmask;
     if (J == I) own &= ~(1ull << lane);
-    if (vi) bm[(int64_t)i * W + J] = own;
+    if (vi) bm[(int64_t)i * S + J] = own;
     if (J != I && j0 + lane < n) {
-      bm[(int64_t)(j0 + lane) * W + I] = trw & rowmask;
+      bm[(int64_t)(j0 + lane) * S + I] = trw & rowmask;
     }
+    // the rows' padding words: zeroed by the wave of the row tile's last column tile (every row tile has one)
+    if (J == T - 1 && vi)
+      for (int w = T; w < S; ++w) bm[(int64_t)i * S + w] = 0ull;
   }
 }
 
@@ -720,7 +723,7 @@ __global__ __launch_bounds__(256, OCC) void tim_graph_mfma3_kernel(
     ProbState* __restrict__ states, int32_t* __restrict__ deg, unsigned long long* __restrict__ regions, int Tmax) {
   const ProbDesc d = descs[blockIdx.y];
   const int n = d.n, W = d.W;
-  const int T = W;
+  const int T = W, S = bm_stride(W);  // tiles = words of a bitmap row; words between two rows
   // block decode: only the blocks that touch the upper triangle are launched (column group X has
   // min(gyr, 2 CHUNKS (X + 1)) row groups; blockIdx.x enumerates them), in an XCD-aware order: workgroups go to the
   // 8 XCDs round robin in dispatch order, so the blocks of one XCD take CONSECUTIVE logical indices -- the four
@@ -821,7 +824,7 @@ __global__ __launch_bounds__(256, OCC) void tim_graph_mfma3_kernel(
   const __amdgpu_buffer_rsrc_t deg_rsrc = __builtin_amdgcn_make_buffer_rsrc(
       (void*)(deg + d.pt_off), 0, (int)((unsigned int)n * 4u), 0x00020000);
   const __amdgpu_buffer_rsrc_t bm_rsrc = __builtin_amdgcn_make_buffer_rsrc(
-      (void*)bm, 0, (int)((unsigned int)n * (unsigned int)W * 8u), 0x00020000);
+      (void*)bm, 0, (int)((unsigned int)n * (unsigned int)S * 8u), 0x00020000);
   int degacc = 0;
   // the value of a diagonal 32 x 32 tile (ct == rt) that is this lane's self pair: row 4h + (q & 3) + 8 (q >> 2) == c
   const int cq = c - 4 * h;
@@ -1068,7 +1071,7 @@ __global__ __launch_bounds__(256, OCC) void tim_graph_mfma3_kernel(
         const uint4 lo = *reinterpret_cast<const uint4*>(&lds_tr[Jr][r][0]);
         const uint4 hi = *reinterpret_cast<const uint4*>(&lds_tr[Jr][r][2]);
         const bool rowok = J < Jc1 && j < n;
-        const unsigned int base = ((unsigned int)j * (unsigned int)W + (unsigned int)I0) * 8u;
+        const unsigned int base = ((unsigned int)j * (unsigned int)S + (unsigned int)I0) * 8u;
         if (Jc0 > I0 + 3 && I0 + 3 < T) {  // (block-uniform) the chunk lies strictly right of all four row tiles
           const int cnt = (__builtin_popcount(lo.x) + __builtin_popcount(lo.y)) + (__builtin_popcount(lo.z) + __builtin_popcount(lo.w)) +
                           (__builtin_popcount(hi.x) + __builtin_popcount(hi.y)) + (__builtin_popcount(hi.z) + __builtin_popcount(hi.w));
@@ -1100,14 +1103,16 @@ __global__ __launch_bounds__(256, OCC) void tim_graph_mfma3_kernel(
     // own words of the chunk: lanes 8r..8r+7 store the (up to) 8 consecutive words of one row
     if (nact > 0) {
       const int kk = lane & 7, J = Jc0 + kk;
-      const bool colok = J >= Ja && J < Jc1;
-      const unsigned int off0 = ((unsigned int)(I * 64 + (lane >> 3)) * (unsigned int)W + (unsigned int)J) * 8u;
+      // (the problem's last chunk ends at the row stride: its words T .. S - 1 are the rows' padding, stored as zeros, so
+      // that this run too covers its whole 64 bytes)
+      const bool pad = J >= T, colok = (J >= Ja && J < Jc1) || pad;
+      const unsigned int off0 = ((unsigned int)(I * 64 + (lane >> 3)) * (unsigned int)S + (unsigned int)J) * 8u;
 #pragma unroll
       for (int it = 0; it < 8; ++it) {
         const int r = it * 8 + (lane >> 3);
-        const uint64_t w = lds_own[wave][r][kk];
+        const uint64_t w = pad ? 0ull : lds_own[wave][r][kk];
         __builtin_amdgcn_raw_buffer_store_b64(u32x2{(unsigned int)w, (unsigned int)(w >> 32)}, bm_rsrc,
-                                              (colok && I * 64 + r < n) ? off0 + (unsigned int)it * 64u * (unsigned int)W : kOobOffset,
+                                              (colok && I * 64 + r < n) ? off0 + (unsigned int)it * 64u * (unsigned int)S : kOobOffset,
                                               0, 0);
       }
     }
@@ -1216,9 +1221,9 @@ __global__ __launch_bounds__(256) void tim_fixup_group_kernel(const ProbDesc* __
   const TimPrep tpr = prep[prob];
   const unsigned int cap = tpr.seg_cap;
   const ProbDesc d = descs[prob];
-  const int n = d.n, W = d.W;
+  const int n = d.n, W = d.W, S = bm_stride(W);
   if (total > cap) {
-    const int64_t words = (int64_t)n * W;
+    const int64_t words = (int64_t)n * S;  // (padding included: zero like everywhere)
     uint64_t* bm = bitmap + d.bm_off;
     for (int64_t w = (int64_t)blockIdx.x * 256 + threadIdx.x; w < words; w += (int64_t)gridDim.x * 256) bm[w] = 0;
     if (blockIdx.x == 0 && threadIdx.x == 0) states[prob].k1_overflow = 1;
@@ -1231,7 +1236,7 @@ __global__ __launch_bounds__(256) void tim_fixup_group_kernel(const ProbDesc* __
     const uint64_t* bm = bitmap + d.bm_off;
     const int lane = threadIdx.x & 63;
     for (int row = blockIdx.x * 4 + (threadIdx.x >> 6); row < n; row += gridDim.x * 4) {
-      const uint64_t* r = bm + (int64_t)row * W;
+      const uint64_t* r = bm + (int64_t)row * S;
       int c = 0;
       for (int w = lane; w < W; w += 64) c += __popcll(r[w]);
       c = wave_sum_i(c);
@@ -1281,7 +1286,7 @@ __global__ __launch_bounds__(256) void tim_fixup_group_kernel(const ProbDesc* __
       cx = ps[3 * col]; cy = ps[3 * col + 1]; cz = ps[3 * col + 2];
       ex = pd[3 * col]; ey = pd[3 * col + 1]; ez = pd[3 * col + 2];
     }
-    unsigned int* wp = bm32 + 2 * ((int64_t)r * W + (col >> 6)) + ((col >> 5) & 1);
+    unsigned int* wp = bm32 + 2 * ((int64_t)r * S + (col >> 6)) + ((col >> 5) & 1);
     const unsigned int bit = 1u << (col & 31);
     bool prov;
     if (STAGED && (r >> 6) != (col >> 6)) {  // (uniform over the 16 lanes of an item)
@@ -1298,7 +1303,7 @@ __global__ __launch_bounds__(256) void tim_fixup_group_kernel(const ProbDesc* __
     atomicXor(wp, bit);
     atomicAdd(dg + r, e ? 1 : -1);
     if ((r >> 6) != (col >> 6)) {  // the transposed copy, where there is one, and the column's degree
-      if (!upper) atomicXor(bm32 + 2 * ((int64_t)col * W + (r >> 6)) + ((r >> 5) & 1), 1u << (r & 31));
+      if (!upper) atomicXor(bm32 + 2 * ((int64_t)col * S + (r >> 6)) + ((r >> 5) & 1), 1u << (r & 31));
       atomicAdd(dg + col, e ? 1 : -1);
     }
   };
@@ -1380,7 +1385,7 @@ __global__ __launch_bounds__(256) void tim_mirror_lower_kernel(const ProbDesc* _
                                                                uint64_t* __restrict__ bitmap,
                                                                const ProbState* __restrict__ states, int skip_closed) {
   const ProbDesc d = descs[blockIdx.y];
-  const int n = d.n, W = d.W, T = W;
+  const int n = d.n, W = d.W, T = W, S = bm_stride(W);
   if (T < 2 || (skip_closed && states[blockIdx.y].deg_closed)) return;
   const int lane = threadIdx.x & 63;
   const int runs = (T + kMirrorRun - 1) / kMirrorRun;  // runs of row tiles per column tile (those at or beyond J: idle)
@@ -1394,7 +1399,7 @@ __global__ __launch_bounds__(256) void tim_mirror_lower_kernel(const ProbDesc* _
       out[k] = 0ull;
       if (Ia + k >= Ib) continue;  // (wave-uniform)
       // row 64 (Ia + k) + lane < 64 J <= n: every lane has a row
-      const uint64_t x = bm[(int64_t)(64 * (Ia + k) + lane) * W + J];
+      const uint64_t x = bm[(int64_t)(64 * (Ia + k) + lane) * S + J];
 #pragma unroll
       for (int c = 0; c < 64; ++c) {  // bit r of the ballot = bit c of row r's word = bit r of column c's word
         const uint64_t m = __builtin_amdgcn_ballot_w64(((x >> c) & 1ull) != 0ull);
@@ -1405,7 +1410,7 @@ __global__ __launch_bounds__(256) void tim_mirror_lower_kernel(const ProbDesc* _
     if (row < n) {
 #pragma unroll
       for (int k = 0; k < kMirrorRun; ++k)
-        if (Ia + k < Ib) bm[(int64_t)row * W + Ia + k] = out[k];
+        if (Ia + k < Ib) bm[(int64_t)row * S + Ia + k] = out[k];
     }
   }
 }
@@ -1625,7 +1630,7 @@ __global__ __launch_bounds__(256) void degree_kernel(const ProbDesc* __restrict_
   const ProbDesc d = descs[blockIdx.y];
   const int lane = threadIdx.x & 63;
   for (int row = blockIdx.x * 4 + (threadIdx.x >> 6); row < d.n; row += gridDim.x * 4) {
-    const uint64_t* r = bitmap + d.bm_off + (int64_t)row * d.W;
+    const uint64_t* r = bitmap + d.bm_off + (int64_t)row * bm_stride(d.W);
     int c = 0;
     for (int w = lane; w < d.W; w += 64) c += __popcll(r[w]);
     c = wave_sum_i(c);

@@ -79,7 +79,7 @@ __device__ __forceinline__ int greedy_one_start(
   if (tr && threadIdx.x == 0) tr[6] = tr[7] = 0;
   stamp(0);
   const ProbDesc d = descs[prob];
-  const int n = d.n, W = d.W;
+  const int n = d.n, W = d.W, S = bm_stride(W);  // words of a bitmap row; words between two rows
   const int Wpad = (W + 1) & ~1;
   uint64_t* P = reinterpret_cast<uint64_t*>(smem);                      // Wpad
   uint64_t* U = P + Wpad;                                               // Wpad (streaming rounds)
@@ -134,7 +134,7 @@ __device__ __forceinline__ int greedy_one_start(
   if (tid == 0) C[0] = v0;
   int pc = 0;
   for (int w = tid; w < W; w += kGreedyThreads) {
-    const uint64_t x = bm[(int64_t)v0 * W + w];
+    const uint64_t x = bm[(int64_t)v0 * S + w];
     P[w] = x;
     pc += __popcll(x);
   }
@@ -181,7 +181,7 @@ __device__ __forceinline__ int greedy_one_start(
       int c = 0;
       __syncthreads();
       for (int w = tid; w < W; w += kGreedyThreads) {
-        const uint64_t x = P[w] & bm[(int64_t)u * W + w];
+        const uint64_t x = P[w] & bm[(int64_t)u * S + w];
         P[w] = x;
         c += __popcll(x);
       }
@@ -261,7 +261,7 @@ __device__ __forceinline__ int greedy_one_start(
         for (int q = 0; q < kStreamRows; ++q) {
           on[q] = i0 + q < pc;
           vv[q] = clist[on[q] ? i0 + q : i0];
-          rr[q] = bm + (int64_t)vv[q] * W;
+          rr[q] = bm + (int64_t)vv[q] * S;
         }
         int cc[kStreamRows];
 #pragma unroll
@@ -314,8 +314,8 @@ __device__ __forceinline__ int greedy_one_start(
         const bool two = bits != 0ull;
         const int b1 = two ? __builtin_ctzll(bits) : b0;
         bits &= bits - (two ? 1ull : 0ull);
-        const uint64_t* r0 = bm + (int64_t)(w * 64 + b0) * W;
-        const uint64_t* r1 = bm + (int64_t)(w * 64 + b1) * W;
+        const uint64_t* r0 = bm + (int64_t)(w * 64 + b0) * S;
+        const uint64_t* r1 = bm + (int64_t)(w * 64 + b1) * S;
         int c0 = 0, c1 = 0;
         for (int x0 = 0; x0 < W; x0 += 64 * 8) {
           uint64_t ra[8], rb[8];
@@ -380,7 +380,7 @@ __device__ __forceinline__ int greedy_one_start(
       ++csize;
       int c = 0;
       for (int w = tid; w < W; w += kGreedyThreads) {
-        const uint64_t x = P[w] & bm[(int64_t)u * W + w];
+        const uint64_t x = P[w] & bm[(int64_t)u * S + w];
         P[w] = x;
         c += __popcll(x);
       }
@@ -459,7 +459,7 @@ __device__ __forceinline__ int greedy_one_start(
       for (int j = 0; j < kRowsInFlight; ++j) {
         const int rj = r + j * kGreedyWaves;
         has[j] = rj < pc;
-        rp[j] = bm32 + 2 * ((int64_t)cand[has[j] ? rj : r] * W);
+        rp[j] = bm32 + 2 * ((int64_t)cand[has[j] ? rj : r] * S);
       }
       unsigned int x[kRowsInFlight][kCapW];
 #pragma unroll
@@ -565,7 +565,7 @@ __device__ __forceinline__ int greedy_one_start(
 // NOT inlined: its 16 loads in flight per lane would add to the greedy kernel's register peak (167 VGPRs: more
 // than 208 and a greedy wave no longer fits where ONE K1 wave has retired).
 template <int kGreedyThreads>
-__device__ __attribute__((noinline)) void closure_round(const uint64_t* __restrict__ bm, int W, const uint64_t* Pa,
+__device__ __attribute__((noinline)) void closure_round(const uint64_t* __restrict__ bm, int W, int S /* row stride */, const uint64_t* Pa,
                                                         uint64_t* Pb, const int* alist, int cnt, int csize, int tid) {
       // One round = the bitmap rows of every alive vertex (~640 x 1.25 KB at N = 10 k, cold in HBM) against the alive
   // bitset.  What bounds it is memory-level parallelism, not bytes: one thread per row, and then 16 lanes per row
@@ -585,7 +585,7 @@ __device__ __attribute__((noinline)) void closure_round(const uint64_t* __restri
     for (int r = 0; r < kRowsPerGroup; ++r) {
       const int k = k0 + gid * kRowsPerGroup + r;
       v[r] = k < cnt ? alist[k] : -1;
-      row[r] = bm + (int64_t)(v[r] < 0 ? 0 : v[r]) * W;
+      row[r] = bm + (int64_t)(v[r] < 0 ? 0 : v[r]) * S;
       c[r] = 0;
     }
 #pragma unroll 1
@@ -898,7 +898,7 @@ __global__ __launch_bounds__(kDegThreads) void degree_closure_rows_kernel(
   const int m = counters[blockIdx.y];
   if (m < 2) return;
   const ProbDesc d = descs[blockIdx.y];
-  const int W = d.W, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int W = d.W, S = bm_stride(W), tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const uint64_t* bm = bitmap + d.bm_off;
   {
     const uint32_t* kin = key_pool + (size_t)blockIdx.y * kCoreCap;
@@ -921,7 +921,7 @@ __global__ __launch_bounds__(kDegThreads) void degree_closure_rows_kernel(
       for (int r = 0; r < kRows; ++r) {
         const int rr = min(rb + r, k1 - 1);
         const int v = (int)(keys[rr] & 0xffffu);
-        rp[r] = bm32 + 2 * ((int64_t)v * W);
+        rp[r] = bm32 + 2 * ((int64_t)v * S);
         rtile[r] = v >> 6;
         myword[r] = 0;
       }
@@ -1421,7 +1421,7 @@ __global__ __launch_bounds__(kGreedyThreads) void greedy_clique_kernel(
         }
       }
       __syncthreads();
-      closure_round<kGreedyThreads>(bm, W, Pa, Pb, alist, cnt, csize, tid);
+      closure_round<kGreedyThreads>(bm, W, bm_stride(W), Pa, Pb, alist, cnt, csize, tid);
       __syncthreads();
       int c2 = 0;
       for (int w = tid; w < W; w += kGreedyThreads) {
@@ -1614,7 +1614,7 @@ __global__ __launch_bounds__(256) void greedy_small_kernel(const ProbDesc* __res
   const ProbDesc d = descs[p];
   ProbState* st = states + p;
   unsigned long long* slot = slots + ((size_t)p * G + blockIdx.x) * kSmallSlotWords;
-  const int n = d.n, W = d.W, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int n = d.n, W = d.W, S = bm_stride(W), tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   if (n < 2 || n > kSmallCap || st->deg_closed) {
     if (tid == 0) slot[0] = 0ull;
     return;
@@ -1637,7 +1637,7 @@ __global__ __launch_bounds__(256) void greedy_small_kernel(const ProbDesc* __res
     __syncthreads();
     for (int v = tid; v < n; v += 256) {
       if (!((alive[v >> 6] >> (v & 63)) & 1ull)) continue;
-      const uint64_t* row = bm + (int64_t)v * W;
+      const uint64_t* row = bm + (int64_t)v * S;
       uint64_t rw[kSmallMaxW];
 #pragma unroll
       for (int x = 0; x < kSmallMaxW; ++x) rw[x] = x < W ? row[x] : 0ull;
@@ -1674,7 +1674,7 @@ __global__ __launch_bounds__(256) void greedy_small_kernel(const ProbDesc* __res
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       const int i = min(i0 + r, m - 1);
-      const uint64_t* row = bm + (int64_t)alist[i] * W;
+      const uint64_t* row = bm + (int64_t)alist[i] * S;
 #pragma unroll
       for (int g = 0; g < kSmallMaxW; ++g) {
         const int c = 64 * g + lane;
@@ -1954,7 +1954,7 @@ __global__ __launch_bounds__(256) void peel_round_kernel(const ProbDesc* __restr
       const uint64_t* bm = bitmap + d.bm_off;
       for (int r = wave; r < 64; r += 4) {
         if (!((aw >> r) & 1ull)) continue;
-        const uint64_t* row = bm + (int64_t)(tile * 64 + r) * d.W;
+        const uint64_t* row = bm + (int64_t)(tile * 64 + r) * bm_stride(d.W);
         int c = 0;
         for (int w = lane; w < d.W; w += 64) c += __popcll(row[w] & cur[w]);
         c = wave_sum_i(c);

@@ -321,6 +321,7 @@ struct teaser_hip_solver : HandleBase {
   // (launch_tim_graph_mfma, kTimMirror / kTimMirrorOpen).  The flag lives with the arena: every lane has its own.
   bool bm_lower_missing = false;
 
+  std::vector<uint64_t> bm_stage;  // teaser_hip_max_clique: the caller's dense rows on the arena's 64-byte stride
   SolverBuf d_desc, d_state, d_src, d_dst, d_bitmap, d_deg, d_clique, d_start_cliques, d_alive_a,
       d_alive_b, d_next_count, d_weights, d_rot_inl, d_trans_inl, d_tls_scratch, d_tim_off,
       d_pk, d_prep, d_work, d_core, d_small;
@@ -1185,7 +1186,7 @@ int32_t layout_batch(teaser_hip_solver* h, const int64_t* pt_off, const int32_t*
   for (int b = 0; b < batch; ++b) {
     if (n[b] < 0) return TEASER_HIP_ERR_BAD_ARG;
     const ProbDesc d = h->descs[(size_t)b] = problem_desc(n[b], pt_off[b], bm, wo);
-    bm += (int64_t)d.n * d.W;
+    bm += (int64_t)d.n * bm_stride(d.W);  // rows on a 64-byte stride (internal.h): every bm_off a multiple of 8 words
     wo += d.W;
     h->tim_off[(size_t)b] = tims;
     const int64_t kt = h->params.rotation_tim_graph == TEASER_TIM_CHAIN ? (int64_t)d.n : (int64_t)d.n * (d.n - 1) / 2;
@@ -2270,7 +2271,39 @@ int32_t teaser_hip_get_inlier_graph_bitmap(teaser_hip_solver* h, int32_t problem
     HIPCHK(h, hipStreamSynchronize(h->stream));
     h->bm_lower_missing = false;
   }
-  return copy_out(h, h->d_bitmap.as<uint64_t>() + d.bm_off, (int64_t)d.n * d.W, buf, len);
+  // the public layout is dense, n x W words: the rows leave the arena's 64-byte stride behind
+  if (!len) return TEASER_HIP_ERR_BAD_ARG;
+  const int64_t cap = *len, count = (int64_t)d.n * d.W;
+  *len = count;
+  if (!buf) return TEASER_HIP_OK;
+  if (cap < count) return TEASER_HIP_ERR_BAD_ARG;
+  const int S = bm_stride(d.W);
+  const uint64_t* rows = h->d_bitmap.as<uint64_t>() + d.bm_off;
+  if (S == d.W) {
+    if (count > 0) HIPCHK(h, hipMemcpy(buf, rows, (size_t)count * 8, hipMemcpyDeviceToHost));
+    return TEASER_HIP_OK;
+  }
+  // blocks of rows through a staging vector (at most ~32 MB), the padding dropped on the way
+  const int64_t blk = std::max<int64_t>(1, ((int64_t)4 << 20) / S);
+  std::vector<uint64_t> stage((size_t)(std::min<int64_t>(blk, d.n) * S));
+  for (int64_t r0 = 0; r0 < d.n; r0 += blk) {
+    const int64_t nr = std::min<int64_t>(blk, d.n - r0);
+    HIPCHK(h, hipMemcpy(stage.data(), rows + r0 * S, (size_t)(nr * S) * 8, hipMemcpyDeviceToHost));
+    for (int64_t r = 0; r < nr; ++r) memcpy(buf + (r0 + r) * d.W, stage.data() + r * S, (size_t)d.W * 8);
+  }
+  return TEASER_HIP_OK;
+}
+
+int32_t teaser_hip_get_inlier_graph_rows(teaser_hip_solver* h, int32_t problem, uint64_t* buf, int64_t* len,
+                                         int32_t* stride_words) {
+  CHECK_PROBLEM(h, problem);
+  const ProbDesc& d = h->descs[(size_t)problem];
+  if (stride_words) *stride_words = bm_stride(d.W);
+  if (!h->have_graph) {
+    if (len) *len = 0;
+    return len ? TEASER_HIP_OK : TEASER_HIP_ERR_BAD_ARG;
+  }
+  return copy_out(h, h->d_bitmap.as<uint64_t>() + d.bm_off, (int64_t)d.n * bm_stride(d.W), buf, len);
 }
 
 int32_t teaser_hip_get_degrees(teaser_hip_solver* h, int32_t problem, int32_t* buf, int64_t* len) {
@@ -2454,7 +2487,7 @@ int32_t teaser_hip_max_clique(teaser_hip_solver* h, const uint64_t* bitmap, int3
   if (!h || !bitmap || n <= 0 || !clique || !clique_size) return TEASER_HIP_ERR_BAD_ARG;
   (void)hipSetDevice(h->device);
   hipStream_t s = h->stream;
-  const int W = (n + 63) / 64;
+  const int W = (n + 63) / 64, S = bm_stride(W);
   const int mode = effective_mode(h->params);
   if (mode == TEASER_INLIER_KCORE_HEU && n > 65536) {  // graph.cc:58-81 (refused before anything is enqueued)
     h->err = "KCORE_HEU supports at most 65536 vertices";
@@ -2470,7 +2503,7 @@ int32_t teaser_hip_max_clique(teaser_hip_solver* h, const uint64_t* bitmap, int3
   ProbState& st = h->states[0];
   HIPCHK(h, h->d_desc.ensure(sizeof(ProbDesc)));
   HIPCHK(h, h->d_state.ensure(sizeof(ProbState)));
-  HIPCHK(h, h->d_bitmap.ensure((size_t)n * W * 8));
+  HIPCHK(h, h->d_bitmap.ensure((size_t)n * S * 8));
   HIPCHK(h, h->d_deg.ensure((size_t)n * 4));
   HIPCHK(h, h->d_clique.ensure((size_t)n * 4));
   HIPCHK(h, h->d_start_cliques.ensure((size_t)n * 4 * kMaxStarts));
@@ -2479,7 +2512,15 @@ int32_t teaser_hip_max_clique(teaser_hip_solver* h, const uint64_t* bitmap, int3
   HIPCHK(h, h->d_next_count.ensure(32));
   HIPCHK(h, hipMemcpyAsync(h->d_desc.p, h->descs.data(), sizeof(ProbDesc), hipMemcpyHostToDevice, s));
   HIPCHK(h, hipMemcpyAsync(h->d_state.p, &st, sizeof(st), hipMemcpyHostToDevice, s));
-  HIPCHK(h, hipMemcpyAsync(h->d_bitmap.p, bitmap, (size_t)n * W * 8, hipMemcpyHostToDevice, s));
+  // the caller's rows are dense (W words); the arena's lie on the 64-byte stride, padding zero
+  // (staged in the handle: the copy may still read it when an early return leaves this function)
+  const uint64_t* up = bitmap;
+  if (S != W) {
+    h->bm_stage.assign((size_t)n * S, 0ull);
+    for (int64_t r = 0; r < n; ++r) memcpy(h->bm_stage.data() + r * S, bitmap + r * W, (size_t)W * 8);
+    up = h->bm_stage.data();
+  }
+  HIPCHK(h, hipMemcpyAsync(h->d_bitmap.p, up, (size_t)n * S * 8, hipMemcpyHostToDevice, s));
   HIPCHK(h, hipMemsetAsync(h->d_next_count.p, 0, 32, s));
   const bool exact = (mode == TEASER_INLIER_PMC_EXACT);
   launch_degrees(s, h->d_desc.as<ProbDesc>(), 1, n, h->d_bitmap.as<uint64_t>(), h->d_deg.as<int32_t>(),
