@@ -12,7 +12,8 @@ It prints the number of extracted points and the largest distance from an extrac
 nearer of the wall and the balls' spheres).  With --mesh PATH the triangle mesh is extracted too (extract_triangle_mesh:
 marching cubes on the device) and written to PATH as a PLY file.  With --scalable the same frames also go into a
 ScalableTSDFVolume with the same voxels, which needs no cube around the scene: it prints the blocks the frames opened and
-the device bytes they hold beside the dense cube's, and the same two figures for its cloud.  Usage:
+the device bytes they hold beside the dense cube's, and the same two figures for its cloud; with --mesh PATH its mesh is
+extracted as well (the same line, and PATH then holds the scalable volume's mesh, not the cube's).  Usage:
 
     python examples/teaser_python_tsdf.py [--width 320 --height 240] [--resolution 128] [--frames 8] [--mesh PATH] [--scalable]
 """
@@ -89,16 +90,21 @@ def main():
     d = distance_to_surface(cloud.points)
     print("distance to the analytic surface: max %.17g, mean %.6f (voxel %.6f)" % (d.max(), d.mean(), vol.voxel_length))
     if a.mesh:
-        t4 = time.perf_counter()
-        mesh = vol.extract_triangle_mesh()
-        t5 = time.perf_counter()
-        tp.write_triangle_mesh(a.mesh, mesh)
-        dm = distance_to_surface(mesh.vertices)
-        print("mesh: %d vertices, %d triangles, %.1f ms; distance to the analytic surface: max %.6f; written to %s"
-              % (len(mesh.vertices), len(mesh.triangles), 1e3 * (t5 - t4), dm.max() if len(dm) else 0.0, a.mesh))
+        report_mesh(vol, a.mesh, "mesh")
     vol.close()
     if a.scalable:
         run_scalable(a, K, depths, extrinsics, length / R, trunc, 8 * R ** 3)
+
+
+def report_mesh(vol, path, label):
+    """The triangle mesh of either volume class (marching cubes on the device), written to `path` as a PLY file."""
+    t0 = time.perf_counter()
+    mesh = tp.extract_triangle_mesh(vol)
+    t1 = time.perf_counter()
+    tp.write_triangle_mesh(path, mesh)
+    dm = distance_to_surface(mesh.vertices)
+    print("%s: %d vertices, %d triangles, %.1f ms; distance to the analytic surface: max %.6f; written to %s"
+          % (label, len(mesh.vertices), len(mesh.triangles), 1e3 * (t1 - t0), dm.max() if len(dm) else 0.0, path))
 
 
 def run_scalable(a, K, depths, extrinsics, voxel_length, trunc, dense_bytes):
@@ -117,6 +123,8 @@ def run_scalable(a, K, depths, extrinsics, voxel_length, trunc, dense_bytes):
         print("scalable extraction: %d points with normals, %.1f ms" % (len(cloud.points), 1e3 * (t2 - t1)))
         d = distance_to_surface(cloud.points)
         print("scalable distance to the analytic surface: max %.17g, mean %.6f" % (d.max() if len(d) else 0.0, d.mean() if len(d) else 0.0))
+        if a.mesh:
+            report_mesh(vol, a.mesh, "scalable mesh")
 
 
 if __name__ == "__main__":

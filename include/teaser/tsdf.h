@@ -256,7 +256,8 @@ class UniformTSDFVolume {
 
 // Open3D's ScalableTSDFVolume: only the blocks of 16^3 voxels that depth frames have come near are stored (include/
 // teaser_hip.h, "Scalable TSDF volume"), and rayCast / rayCastBatch render them into cameras ("Scalable TSDF ray
-// casting") with the dense class's options and result.  extractTriangleMesh is not offered here.
+// casting") with the dense class's options and result.  extractTriangleMesh runs marching cubes over them ("Scalable
+// TSDF triangle mesh").
 class ScalableTSDFVolume {
  public:
   // What the last integrate call reported: (frame, block) pairs touched, blocks opened, and (frame, point) pairs with
@@ -336,6 +337,26 @@ class ScalableTSDFVolume {
     out.colors = Matrix3X(3, count);
     if (count > 0)
       check(teaser_hip_stsdf_extract_voxel_point_cloud(h_, count, out.points.data(), out.colors.data(), &count));
+    return out;
+  }
+
+  // Open3D's ExtractTriangleMesh (marching cubes) over the open blocks and across their faces: blocks in ascending
+  // (bx, by, bz), the cubes of a block in (x, y, z) order, vertex colours for a volume with a colour type.
+  // with_vertex_normals adds the TSDF gradient at every vertex (the normal rule of the point cloud).  A count call, then
+  // a fill call; PLYWriter::writeMesh takes the result as it is.
+  TSDFTriangleMesh extractTriangleMesh(bool with_vertex_normals = false) {
+    const bool colored = color_type_ != TSDFVolumeColorType::NoColor;
+    int64_t nv = 0, nt = 0;
+    check(teaser_hip_stsdf_extract_triangle_mesh(h_, 0, nullptr, nullptr, nullptr, 0, nullptr, &nv, &nt));
+    TSDFTriangleMesh out;
+    out.vertices = Matrix3X(3, nv);
+    if (colored) out.vertex_colors = Matrix3X(3, nv);
+    if (with_vertex_normals) out.vertex_normals = Matrix3X(3, nv);
+    out.triangles.resize(3 * (size_t)nt);
+    if (nv > 0 || nt > 0)
+      check(teaser_hip_stsdf_extract_triangle_mesh(h_, nv, out.vertices.data(), colored ? out.vertex_colors.data() : nullptr,
+                                                   with_vertex_normals ? out.vertex_normals.data() : nullptr, nt,
+                                                   out.triangles.data(), &nv, &nt));
     return out;
   }
 

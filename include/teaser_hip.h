@@ -2392,7 +2392,8 @@ TEASER_HIP_API int32_t teaser_hip_tsdf_ray_cast_views(teaser_hip_tsdf* tsdf, int
  * memory and fixes what Open3D leaves to an unordered map; Open3D is not run and bit parity with an Open3D binary is NOT
  * claimed.  Every deliberate difference is marked DEPARTURE.  tests/stsdf_reference.py restates this text in numpy and
  * is the parity target of the host and GPU tests.  No product-add is fused and every sum is taken left to right as
- * written.  Ray casting is "Scalable TSDF ray casting" below; extract_triangle_mesh is not offered on this handle.
+ * written.  Ray casting is "Scalable TSDF ray casting" below; extract_triangle_mesh is not offered in this section:
+ * the mesh is "Scalable TSDF triangle mesh" below.
  *
  * Parameters.  voxel_length, sdf_trunc, color_type (0 none, 1 RGB8, 2 Gray32) as for "TSDF volume";
  * volume_unit_resolution U (default 16): this version supports ONLY 16 and refuses 4, 8 and 32 by name;
@@ -2576,6 +2577,67 @@ TEASER_HIP_API int32_t teaser_hip_stsdf_ray_cast_views(teaser_hip_stsdf* stsdf, 
                                                        const teaser_tsdf_view_c* views, float* const* depth,
                                                        float* const* vertex, float* const* normal, float* const* color,
                                                        int64_t* hit_counts);
+
+/* Scalable TSDF triangle mesh: Open3D's ScalableTSDFVolume::ExtractTriangleMesh (marching cubes over the open blocks)
+ * on a scalable TSDF handle.  The text below IS the contract.  It restates Open3D from memory; Open3D is not run and bit
+ * parity with an Open3D binary is NOT claimed.  Every deliberate difference is marked DEPARTURE.
+ * tests/stsdf_mesh_reference.py restates this text as Open3D's loop with a dict and is the parity target of the host and
+ * GPU tests.  Everything is double arithmetic, no product-add is fused, every sum is taken left to right as written.
+ *
+ * Reused word for word from "TSDF volume" (the triangle mesh): shift, edge_shift, edge_to_vert, the tables (the same
+ * SHA-256, the same teaser_hip_tsdf_mesh_tables), the ACTIVE rule, the triangle row (v[T[t]], v[T[t + 2]], v[T[t + 1]]),
+ * int32 indices, coincident vertices with distinct indices and kept degenerate triangles.
+ *
+ * Lattice.  The global voxel is g = 16 b + l for the voxel l of block b.  A voxel of a block that is not open has
+ * tsdf 0 and weight 0, so a cube with a corner in such a block is never ACTIVE.  Cube g is considered only when the
+ * block of its base voxel g is open: Open3D never visits the others.  Corner i of cube g is voxel g + shift[i], wherever
+ * that lies: a cube with a local index of 15 on some axis reads voxel 0 of the next block, and a cube may have its
+ * corners in eight blocks.  There is no R - 1 rule.
+ *
+ * Visiting order (DEPARTURE: Open3D walks an unordered map of blocks, so its order differs from run to run).  Blocks are
+ * visited in ascending (bx, by, bz), the order of the directory; inside a block the cubes in ascending (lx, ly, lz), x
+ * outermost.  rank(cube) = (directory rank of its block, (lx 16 + ly) 16 + lz), compared lexicographically.
+ *
+ * Vertices.  The lattice edge with base voxel h along axis a carries a vertex when at least one of the four cubes
+ * h - du e_u - dv e_v (u < v the other two axes, du, dv in {0, 1}) is ACTIVE and its end voxels differ in sign
+ * (tsdf < 0.0f).  Its CREATOR is the ACTIVE cube of smallest rank among the four, its slot the edge's number inside the
+ * creator.  Vertices are numbered in ascending (rank(creator), slot): the order in which the loop first meets them.
+ *   The creator is NOT the dense rule carried over.  Take an x-edge whose base voxel has local y != 0 and local z = 0,
+ *   and its cubes A = h - e_y - e_z, B = h - e_y, C = h - e_z, D = h.  Globally A < B < C < D, but A and C lie in block
+ *   bz - 1 and come before B and D: by rank A < C < B < D.  With A inactive and B, C ACTIVE the dense rule names B and
+ *   this contract names C.
+ *   Position, with a, b = edge_to_vert[slot] in the creator: f0 = |(double)tsdf(a)|, f1 = |(double)tsdf(b)|;
+ *   p_k = half + vl (double)h_k with h the GLOBAL base voxel of the edge (exact: |h_k| < 2^24) and half = vl 0.5;
+ *   p_axis = p_axis + (f0 vl) / (f0 + f1).  The vertex is p: there is no origin, and this is NOT the point cloud's
+ *   (half + vl x) + b ul -- Open3D forms the mesh vertex from the global edge index.
+ *   Colour (a volume with a colour type): the dense mesh's rule -- c0, c1 the end voxels' colours, each / 255.0 first for
+ *   RGB8; (f1 c0 + f0 c1) / (f0 + f1) per component; a NaN colour of a Gray32 volume is the quiet NaN.
+ *   Vertex normals (the same EXTENSION as the dense mesh): when vertex_normals is given, the normal rule of the scalable
+ *   point cloud evaluated at p: T on the global lattice, 0 in a block that is not open, g = 0.99 vl, the same
+ *   normalisation.
+ *
+ * Triangles.  For every ACTIVE cube in rank order the dense rows, v[e] being the index of the vertex on the cube's edge e.
+ *
+ * The call follows teaser_hip_tsdf_extract_triangle_mesh.  vertex_count_out and triangle_count_out (both required)
+ * receive the counts.  Both capacities 0 with vertices and triangles NULL returns the counts alone.  Otherwise vertices
+ * has room for vertex_capacity x 3 doubles, vertex_colors (only for a volume with a colour type) and vertex_normals are
+ * NULL or as large, triangles has room for triangle_capacity x 3 int32.  A capacity below its count is
+ * TEASER_HIP_ERR_BAD_ARG: the message names both counts, both outputs hold them, and no row of either array is written.
+ * Rows behind the counts are not written.  A vertex count above 2^31 - 1 is TEASER_HIP_ERR_BAD_ARG with the count in the
+ * message.  A volume with no open block answers 0 / 0.  Scratch: 5 bytes per voxel of the open blocks (a byte and a
+ * 32-bit record per cube) plus 8 bytes per column and 24 per block, sized from the block count the host holds, kept on
+ * the handle and grown when the directory has grown; teaser_hip_stsdf_fill_scratch reaches it; a failed allocation is
+ * TEASER_HIP_ERR_OOM and leaves the blocks and the directory intact.  One stream synchronisation per call.  Launches:
+ * with no open block the two scans of the block totals alone; else cubes, count and the two scans -- four launches for
+ * the counts -- and one more for each array with a capacity above 0.  The launch count depends on the data only through
+ * whether a block is open.  There is no atomic of any kind: the same bits run after run, and the same bits whatever
+ * order the blocks were opened in -- slots differ, ranks do not.  The call modifies neither the blocks nor the
+ * directory. */
+TEASER_HIP_API int32_t teaser_hip_stsdf_extract_triangle_mesh(teaser_hip_stsdf* stsdf, int64_t vertex_capacity,
+                                                              double* vertices, double* vertex_colors,
+                                                              double* vertex_normals, int64_t triangle_capacity,
+                                                              int32_t* triangles, int64_t* vertex_count_out,
+                                                              int64_t* triangle_count_out);
 
 /* Page-locked host memory from the HIP runtime THIS library runs on.  teaser_hip_submit_batch(..., INPUT_HOST) moves
  * the points with one DMA copy per cloud, at PCIe speed only when the runtime knows the pages are locked.  A buffer

@@ -58,7 +58,17 @@ frames, downloaded) and a 160 x 120 view, which must equal the device's maps: th
 the directory searches (block changes) per ray.  `--profile-workload scalable_ray_cast` runs three single-view and three
 16-view calls on both volumes for rocprofv3.
 
-    python scripts/bench_tsdf.py --scalable --ray-cast --sizes 512 --reps 9 --warmup 1 --out profiles/tsdf_scalable_raycast/bench_tsdf_scalable_raycast.json"""
+    python scripts/bench_tsdf.py --scalable --ray-cast --sizes 512 --reps 9 --warmup 1 --out profiles/tsdf_scalable_raycast/bench_tsdf_scalable_raycast.json
+
+`--scalable --mesh` measures the triangle mesh of the scalable volume (profiles/tsdf_scalable_mesh/): the 64 RGB8 frames
+into a ScalableTSDFVolume with the voxels of every size of `--sizes` and, in the same process, into the dense volume;
+extract_mesh (a count call and a fill call) with and without vertex normals, the counts-only call and the scalable
+extract_point_cloud beside the dense extract_triangle_mesh on the same frames, measured in alternation; and the Python
+restatement of the mesh (tests/stsdf_mesh_reference.py) on the blocks downloaded at the voxels of R = 64, which must
+equal the device's mesh.  `--profile-workload scalable_mesh` runs three mesh extractions with normals on both volumes
+for rocprofv3.
+
+    python scripts/bench_tsdf.py --scalable --mesh --sizes 512 --reps 9 --warmup 1 --out profiles/tsdf_scalable_mesh/bench_tsdf_scalable_mesh.json"""
 import argparse
 import ctypes as C
 import importlib
@@ -359,6 +369,66 @@ def scalable_ray_cast_restatement(R, K, d, e):
                 steps_mean_without_skip=float(slow.steps.mean()), steps_max_without_skip=int(slow.steps.max()), hits_without_skip=slow.hits)
 
 
+def run_scalable_mesh(R, K, d, e, c, reps, warmup):
+    res = dict(R=R, colour=True)
+    with make_scalable(R, 1) as vol, make(R, 1) as dense:
+        one_call(vol, K, d, e, c)
+        one_call(dense, K, d, e, c)
+        res["blocks"], res["scalable_bytes"], res["dense_bytes"] = vol.block_count, vol.block_count * vol.block_bytes, 32 * R ** 3
+        res["voxels_of_open_blocks"], res["dense_voxels"] = vol.block_count * 4096, R ** 3
+        mesh = vol.extract_mesh(vertex_normals=True)
+        res["vertices"], res["triangles"] = len(mesh.vertices), len(mesh.triangles)
+        res["output_bytes"] = int(mesh.vertices.nbytes * 3 + mesh.triangles.nbytes)
+        res["max_distance_to_surface"] = float(ex.distance_to_surface(mesh.vertices).max())
+        again = vol.extract_mesh(vertex_normals=True)
+        res["same_bits_twice"] = bool(again.vertices.tobytes() == mesh.vertices.tobytes() and again.triangles.tobytes() == mesh.triangles.tobytes()
+                                      and again.vertex_normals.tobytes() == mesh.vertex_normals.tobytes())
+        ref = dense.extract_triangle_mesh()
+        res["dense_vertices"], res["dense_triangles"] = len(ref.vertices), len(ref.triangles)
+        del mesh, again, ref
+        nv, nt = C.c_int64(0), C.c_int64(0)
+        # alternating: a scalable measurement, then the dense one of the same kind
+        res["extract_mesh"] = timed(lambda: vol.extract_mesh(), reps, warmup)
+        res["dense_extract_triangle_mesh"] = timed(lambda: dense.extract_triangle_mesh(), reps, warmup)
+        res["extract_mesh_with_normals"] = timed(lambda: vol.extract_mesh(vertex_normals=True), reps, warmup)
+        res["dense_extract_triangle_mesh_with_normals"] = timed(lambda: dense.extract_triangle_mesh(vertex_normals=True), reps, warmup)
+        res["counts_only_call"] = timed(lambda: vol._call(tp.lib().teaser_hip_stsdf_extract_triangle_mesh, 0, None, None, None, 0, None,
+                                                          C.byref(nv), C.byref(nt)), reps, warmup)
+        res["dense_counts_only_call"] = timed(lambda: dense._call(tp.lib().teaser_hip_tsdf_extract_triangle_mesh, 0, None, None, None, 0, None,
+                                                                  C.byref(nv), C.byref(nt)), reps, warmup)
+        res["surface_points"] = len(vol.extract_point_cloud().points)
+        res["extract_point_cloud"] = timed(lambda: vol.extract_point_cloud(), reps, warmup)
+        res["extract_point_cloud_no_normals"] = timed(lambda: vol.extract_point_cloud(normals=False), reps, warmup)
+    return res
+
+
+def scalable_mesh_restatement(K, d, e, c):
+    """The Python loop on the host at the voxels of R = 64 (8 frames), on the blocks the device integrated."""
+    import stsdf_mesh_reference as SM
+    import stsdf_raycast_reference as SR
+    import stsdf_reference as S
+    import tsdf_reference as T
+    length, R, trunc, _ = ex.volume_settings(64)
+    U = S.U
+    with make_scalable(64, 1) as g:
+        one_call(g, K, d[:CHUNK], e[:CHUNK], c[:CHUNK])
+        keys, tw, col = g.extract_blocks()
+        # Open3D's voxel order (x U + y) U + z is the restatement's [x, y, z]
+        vol = SR.volume_of_blocks(length / R, trunc, T.RGB8, {tuple(int(v) for v in k): (tw[n, :, 0].reshape(U, U, U), tw[n, :, 1].reshape(U, U, U),
+                                                                                       col[n].reshape(U, U, U, 3)) for n, k in enumerate(keys)})
+        t = time.perf_counter()
+        ref = SM.extract_triangle_mesh(vol, normals=True)
+        t1 = time.perf_counter()
+        mesh = g.extract_mesh(vertex_normals=True)
+        t2 = time.perf_counter()
+    blocks, cubes, crossing, differ = SM.face_statistics(vol)
+    same = (mesh.vertices.tobytes() == ref.vertices.tobytes() and mesh.triangles.tobytes() == ref.triangles.tobytes()
+            and mesh.vertex_colors.tobytes() == ref.colors.tobytes() and mesh.vertex_normals.tobytes() == ref.normals.tobytes())
+    return dict(R=64, frames=CHUNK, blocks=blocks, active_cubes=cubes, active_cubes_with_a_local_index_of_15=crossing,
+                edges_whose_creator_is_not_the_dense_one=differ, restatement_ms=1e3 * (t1 - t), device_ms_one_untimed_call=1e3 * (t2 - t1),
+                vertices=len(ref.vertices), triangles=len(ref.triangles), device_equals_restatement=bool(same))
+
+
 def run_scalable(R, colour, K, d, e, c, reps, warmup):
     cc = c if colour else None
     length, R, trunc, _ = ex.volume_settings(R)
@@ -423,7 +493,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--out", default=None)
     ap.add_argument("--sizes", type=int, nargs="+", default=[256, 512])
-    ap.add_argument("--profile-workload", choices=["one_call", "calls", "extract", "mesh", "ray_cast", "scalable_ray_cast"], default=None)
+    ap.add_argument("--profile-workload", choices=["one_call", "calls", "extract", "mesh", "ray_cast", "scalable_ray_cast", "scalable_mesh"], default=None)
     ap.add_argument("--profile-R", type=int, default=512)
     ap.add_argument("--profile-colour", type=int, default=1)
     ap.add_argument("--mesh", action="store_true", help="measure the triangle mesh instead (profiles/tsdf_mesh/)")
@@ -441,6 +511,14 @@ def main():
                 for v in (vol, dense):
                     tp.ray_cast(v, K, e[0], depth_max=6.0, weight_threshold=3.0)
                     v.ray_cast_batch(K, e[:POSES], depth_max=6.0, weight_threshold=3.0)
+        return
+    if a.profile_workload == "scalable_mesh":
+        with make_scalable(a.profile_R, 1) as vol, make(a.profile_R, 1) as dense:
+            one_call(vol, K, d, e, c)
+            one_call(dense, K, d, e, c)
+            for rep in range(3):
+                vol.extract_mesh(vertex_normals=True)
+                dense.extract_triangle_mesh(vertex_normals=True)
         return
     if a.profile_workload:
         cc = c if a.profile_colour else None
@@ -470,6 +548,18 @@ def main():
             print(json.dumps(r), flush=True)
             out["settings"].append(r)
         out["restatement"] = scalable_ray_cast_restatement(a.sizes[0], K, d, e)
+        print(json.dumps(out["restatement"]), flush=True)
+        if a.out:
+            os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+            with open(a.out, "w") as f:
+                json.dump(out, f, indent=1)
+        return
+    if a.scalable and a.mesh:
+        for R in a.sizes:
+            r = run_scalable_mesh(R, K, d, e, c, a.reps, a.warmup)
+            print(json.dumps(r), flush=True)
+            out["settings"].append(r)
+        out["restatement"] = scalable_mesh_restatement(K, d, e, c)
         print(json.dumps(out["restatement"]), flush=True)
         if a.out:
             os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)

@@ -181,7 +181,7 @@ EXPORTED_SYMBOLS = [
     "teaser_hip_stsdf_fill_scratch", "teaser_hip_stsdf_last_phases", "teaser_hip_stsdf_reset", "teaser_hip_stsdf_integrate_frames",
     "teaser_hip_stsdf_extract_point_cloud", "teaser_hip_stsdf_extract_voxel_point_cloud", "teaser_hip_stsdf_block_count",
     "teaser_hip_stsdf_block_keys", "teaser_hip_stsdf_download_blocks", "teaser_hip_stsdf_upload_blocks",
-    "teaser_hip_stsdf_ray_cast_views",
+    "teaser_hip_stsdf_ray_cast_views", "teaser_hip_stsdf_extract_triangle_mesh",
     "teaser_hip_icp_odometry_option_default", "teaser_hip_icp_rgbd_odometry_batch",
     "teaser_hip_icp_rgbd_odometry_pyramid_batch",
 ]
@@ -1190,7 +1190,7 @@ from .fgr import (FastGlobalRegistrationOption, registration_fgr_based_on_corres
 from .plane import (segment_plane, segment_plane_batch, plane_trials_batch, set_plane_option,  # noqa: E402
                     get_plane_option)
 from .tsdf import (UniformTSDFVolume, ScalableTSDFVolume, TSDFVolumeColorType, TSDFPointCloud, TSDFTriangleMesh,  # noqa: E402
-                   TSDFRayCastResult, write_triangle_mesh, ray_cast, ray_cast_batch)
+                   TSDFRayCastResult, write_triangle_mesh, ray_cast, ray_cast_batch, extract_triangle_mesh)
 from .odometry import (OdometryOption, RGBDOdometryJacobianFromColorTerm,  # noqa: E402
                        RGBDOdometryJacobianFromHybridTerm, RGBDImage, compute_rgbd_odometry,
                        compute_rgbd_odometry_batch, rgbd_odometry_pyramid_batch)
@@ -1252,6 +1252,6 @@ __all__ = ["fill_scratch", "SCRATCH_KINDS",
            "fgr_iterations_batch", "set_fgr_option", "get_fgr_option",
            "segment_plane", "segment_plane_batch", "plane_trials_batch", "set_plane_option", "get_plane_option",
            "UniformTSDFVolume", "TSDFVolumeColorType", "TSDFPointCloud", "TSDFTriangleMesh", "TSDFRayCastResult",
-           "write_triangle_mesh", "ray_cast", "ray_cast_batch",
+           "write_triangle_mesh", "ray_cast", "ray_cast_batch", "extract_triangle_mesh",
            "OdometryOption", "RGBDOdometryJacobianFromColorTerm", "RGBDOdometryJacobianFromHybridTerm", "RGBDImage",
            "compute_rgbd_odometry", "compute_rgbd_odometry_batch", "rgbd_odometry_pyramid_batch"]

@@ -433,9 +433,9 @@ const char* teaser_hip_stsdf_last_error(const teaser_hip_stsdf* h) {
 int32_t teaser_hip_stsdf_fill_scratch(teaser_hip_stsdf* h, int32_t byte, int64_t* bytes_out) {
   if (!h) return TEASER_HIP_ERR_BAD_ARG;
   // not the slabs and not h->dir: the blocks and the directory are the handle's state
-  const ScratchSpan spans[] = {span_of(h->in),    span_of(h->work), span_of(h->out),   span_of(h->items),
-                               span_of(h->stage), span_of(h->back), span_of(h->istage)};
-  return fill_scratch(h, byte, spans, 7, bytes_out);
+  const ScratchSpan spans[] = {span_of(h->in),    span_of(h->work), span_of(h->out),    span_of(h->items),
+                               span_of(h->stage), span_of(h->back), span_of(h->istage), span_of(h->mesh)};
+  return fill_scratch(h, byte, spans, 8, bytes_out);
 }
 
 int32_t teaser_hip_stsdf_last_phases(const teaser_hip_stsdf* h, double* ms) {

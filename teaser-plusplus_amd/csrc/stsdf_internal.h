@@ -20,6 +20,7 @@ struct teaser_hip_stsdf : thip::HandleBase {
   double phase_ms[3] = {0.0, 0.0, 0.0};  // teaser_hip_stsdf_last_phases: the host's clock over the last integrate call
   bool dir_dirty = true;     // the device copy of the directory (dir) is behind keys / slots
   thip::DevBuf in, work, out, items, dir;
+  thip::DevBuf mesh;  // the cube bytes, records and offsets of the triangle mesh (stsdf_mesh.hip): grown with the directory
   thip::HostBuf stage, back, istage;
   ~teaser_hip_stsdf() {
     for (void* p : slabs)

@@ -95,6 +95,7 @@ def declare(L):
     L.teaser_hip_stsdf_upload_blocks.argtypes = [_vp, C.c_int64, _i32p, _fp, _dp]
     L.teaser_hip_stsdf_ray_cast_views.argtypes = [_vp, C.c_int32, C.POINTER(TsdfViewC), C.POINTER(_fp), C.POINTER(_fp),
                                                   C.POINTER(_fp), C.POINTER(_fp), _i64p]
+    L.teaser_hip_stsdf_extract_triangle_mesh.argtypes = [_vp, C.c_int64, _dp, _dp, _dp, C.c_int64, _i32p, _i64p, _i64p]
 
 
 class TSDFVolumeColorType:
@@ -315,6 +316,22 @@ class _TSDFHandle:
         pts, (col,) = self._extract(self._fn("extract_voxel_point_cloud"), [True])
         return TSDFPointCloud(pts, None, col)
 
+    def _extract_mesh(self, vertex_normals):
+        """The counts first, then the rows into arrays of exactly that size."""
+        nv, nt = C.c_int64(0), C.c_int64(0)
+        fn = self._fn("extract_triangle_mesh")
+        self._call(fn, 0, None, None, None, 0, None, C.byref(nv), C.byref(nt))
+        n, m = int(nv.value), int(nt.value)
+        colored = self.color_type != TSDFVolumeColorType.NoColor
+        vert, tri = np.empty((n, 3)), np.empty((m, 3), dtype=np.int32)
+        col = np.empty((n, 3)) if colored else None
+        nrm = np.empty((n, 3)) if vertex_normals else None
+        if n or m:
+            self._call(fn, n, vert.ctypes.data_as(_dp), None if col is None else col.ctypes.data_as(_dp),
+                       None if nrm is None else nrm.ctypes.data_as(_dp), m, tri.ctypes.data_as(_i32p), C.byref(nv),
+                       C.byref(nt))
+        return TSDFTriangleMesh(vert, tri, col, nrm)
+
     # ---- ray casting --------------------------------------------------------------------------------------------
     def ray_cast_batch(self, intrinsic, extrinsics, width=None, height=None, depth_min=0.1, depth_max=3.0,
                        weight_threshold=3.0, vertex_map=True, normal_map=True, color=True):
@@ -410,19 +427,7 @@ class UniformTSDFVolume(_TSDFHandle):
         """Open3D's extract_triangle_mesh: marching cubes over the observed cubes, vertices and triangles in the order
         of Open3D's loop, with vertex colours for a volume with a colour type.  vertex_normals=True adds the TSDF
         gradient at every vertex (the normal rule of the point cloud), which Open3D's call does not give."""
-        nv, nt = C.c_int64(0), C.c_int64(0)
-        fn = self._lib.teaser_hip_tsdf_extract_triangle_mesh
-        self._call(fn, 0, None, None, None, 0, None, C.byref(nv), C.byref(nt))
-        n, m = int(nv.value), int(nt.value)
-        colored = self.color_type != TSDFVolumeColorType.NoColor
-        vert, tri = np.empty((n, 3)), np.empty((m, 3), dtype=np.int32)
-        col = np.empty((n, 3)) if colored else None
-        nrm = np.empty((n, 3)) if vertex_normals else None
-        if n or m:
-            self._call(fn, n, vert.ctypes.data_as(_dp), None if col is None else col.ctypes.data_as(_dp),
-                       None if nrm is None else nrm.ctypes.data_as(_dp), m, tri.ctypes.data_as(_i32p), C.byref(nv),
-                       C.byref(nt))
-        return TSDFTriangleMesh(vert, tri, col, nrm)
+        return self._extract_mesh(vertex_normals)
 
     def ray_cast(self, intrinsic, extrinsic, width=None, height=None, depth_min=0.1, depth_max=3.0, weight_threshold=3.0,
                  vertex_map=True, normal_map=True, color=True):
@@ -477,8 +482,9 @@ class ScalableTSDFVolume(_TSDFHandle):
     the library's defaults; max_blocks 0: no limit) size the memory the blocks lie in.  ``last_counts`` holds
     (touched, opened, out_of_range) of the last integrate call.  ray_cast_batch renders views of the open blocks
     (include/teaser_hip.h, "Scalable TSDF ray casting"); the single view is the module's ray_cast(volume, ...): Open3D's
-    ScalableTSDFVolume has no method of that name, and this class keeps Open3D's surface.  extract_triangle_mesh is not
-    offered."""
+    ScalableTSDFVolume has no method of that name, and this class keeps Open3D's surface.  The triangle mesh
+    (include/teaser_hip.h, "Scalable TSDF triangle mesh") is extract_mesh(), or the module's
+    extract_triangle_mesh(volume, ...), which serves either volume class."""
     _prefix = "teaser_hip_stsdf"
 
     def __init__(self, voxel_length, sdf_trunc, color_type=TSDFVolumeColorType.NoColor, volume_unit_resolution=16,
@@ -564,6 +570,14 @@ class ScalableTSDFVolume(_TSDFHandle):
         self._call(self._lib.teaser_hip_stsdf_upload_blocks, n, k.ctypes.data_as(_i32p),
                    None if tw is None else tw.ctypes.data_as(_fp), None if col is None else col.ctypes.data_as(_dp))
 
+    # ---- extraction ---------------------------------------------------------------------------------------------
+    def extract_mesh(self, vertex_normals=False):
+        """Open3D's ScalableTSDFVolume.extract_triangle_mesh: marching cubes over the open blocks, across their faces,
+        blocks in ascending (bx, by, bz) and cubes in (x, y, z) order inside, with vertex colours for a volume with a
+        colour type.  vertex_normals=True adds the TSDF gradient at every vertex (the normal rule of the point cloud).
+        Returns a TSDFTriangleMesh."""
+        return self._extract_mesh(vertex_normals)
+
     def reset(self):
         """Closes every block."""
         self._call(self._lib.teaser_hip_stsdf_reset)
@@ -584,5 +598,12 @@ def ray_cast(volume, intrinsic, extrinsic, width=None, height=None, depth_min=0.
                           normal_map, color)[0]
 
 
+def extract_triangle_mesh(volume, vertex_normals=False):
+    """The triangle mesh of either volume class: ``volume.extract_triangle_mesh(...)`` of a UniformTSDFVolume,
+    ``volume.extract_mesh(...)`` of a ScalableTSDFVolume."""
+    fn = getattr(volume, "extract_triangle_mesh", None)
+    return (fn if fn is not None else volume.extract_mesh)(vertex_normals)
+
+
 __all__ = ["UniformTSDFVolume", "ScalableTSDFVolume", "TSDFVolumeColorType", "TSDFPointCloud", "TSDFTriangleMesh", "TSDFRayCastResult",
-           "write_triangle_mesh", "ray_cast", "ray_cast_batch"]
+           "write_triangle_mesh", "ray_cast", "ray_cast_batch", "extract_triangle_mesh"]
