@@ -293,10 +293,18 @@ TEASER_HIP_API int32_t teaser_hip_get_degrees(teaser_hip_solver* h, int32_t prob
 /* DIAGNOSTIC (tests), on no hot path: the rows of a problem's graph as the device arena holds them -- n rows on a
  * stride of *stride_words words (ceil(n / 64) rounded up to a multiple of 8: 64 bytes), len = n x stride.  The words
  * ceil(n / 64) .. stride - 1 of a row are padding and zero.  Unlike teaser_hip_get_inlier_graph_bitmap the call
- * rebuilds nothing: behind a solve that stored the upper triangle only, the words of row r in front of r / 64 are
- * whatever an earlier solve left there. */
+ * mirrors nothing: behind a solve that stored the upper triangle only, the words of row r in front of r / 64 are
+ * whatever an earlier solve left there.  Behind a solve whose K1 stored no row at all (teaser_hip_get_graph_route: 2)
+ * it does what that getter does: every row of the batch is rebuilt first, once, both halves and the padding.
+ * Both getters rebuild from the handle's own arenas: the caller's point arrays are not read again and need not
+ * outlive the solve. */
 TEASER_HIP_API int32_t teaser_hip_get_inlier_graph_rows(teaser_hip_solver* h, int32_t problem, uint64_t* buf,
                                          int64_t* len /* words */, int32_t* stride_words);
+/* DIAGNOSTIC (tests): how the last solve's K1 stored the graph of the batch `problem` belongs to -- 0: both halves,
+ * 1: the upper triangle (the lower one is mirrored on demand), 2: nothing (the degree closure worked from the points;
+ * rows are rebuilt on demand) -- and how many problems rebuilds have covered since that solve.  Which route a solve
+ * takes is not observable in any result.  Either pointer may be NULL. */
+TEASER_HIP_API int32_t teaser_hip_get_graph_route(teaser_hip_solver* h, int32_t problem, int32_t* route, int64_t* rebuilt);
 
 /* Stage entry points (registration.h:584-601), host pointers, 3 x K column-major TIMs/points:
  *   solveForRotation   -> GNCTLSRotationSolver::solveForRotation (registration.cc:764-866);

@@ -1,9 +1,10 @@
 #!/usr/bin/env python3
 """Static instruction statistics of the K1 kernel from the compiler's own assembly (CPU only, no GPU):
   hipcc --offload-arch=gfx950 <the Makefile's flags for kernels_graph.o> --save-temps -c csrc/kernels_graph.hip
-For EVERY instantiation of tim_graph_mfma3_kernel<PIPE, PLAIN, OCC, CHUNKS, LOWER, UW3> in the object (two in the product
-build: LOWER = 1 stores the bitmap's lower triangle, LOWER = 0 leaves it out; more with --lab = -DTEASER_K1_LAB, among
-them UW3 = 1, the three-MFMA formulation): registers, scratch, LDS, occupancy, and per BASIC BLOCK the instruction mix
+For EVERY instantiation of tim_graph_mfma3_kernel<PIPE, PLAIN, OCC, CHUNKS, LOWER, UW3, NS> in the object (four in the
+product build: LOWER = 1 stores the bitmap's lower triangle, LOWER = 0 leaves it out, NS = 1 stores no row, NS = 2 is
+the rebuild of such a batch's rows; more with --lab = -DTEASER_K1_LAB, among them UW3 = 1, the three-MFMA
+formulation): registers, scratch, LDS, occupancy, and per BASIC BLOCK the instruction mix
 (VALU / MFMA / SALU / LDS / VMEM / waits).  The block with the most MFMAs is the steady-state column-tile loop body:
 one iteration covers one 64 x 64 column tile of a wave = 4096 pairs, so VALU per 1024 pairs = VALU / 4.
 usage: k1_isa_stats.py [--lab] [--brief] [<file.s>]"""
@@ -51,8 +52,8 @@ def classify(op):
 
 
 def template_args(sym):
-    m = re.match(re.escape(PREFIX) + r"Lb([01])ELb([01])ELi(\d+)ELi(\d+)ELb([01])ELb([01])EE", sym)
-    return "<PIPE=%s, PLAIN=%s, OCC=%s, CHUNKS=%s, LOWER=%s, UW3=%s>" % m.groups() if m else sym
+    m = re.match(re.escape(PREFIX) + r"Lb([01])ELb([01])ELi(\d+)ELi(\d+)ELb([01])ELb([01])ELi(\d+)EE", sym)
+    return "<PIPE=%s, PLAIN=%s, OCC=%s, CHUNKS=%s, LOWER=%s, UW3=%s, NS=%s>" % m.groups() if m else sym
 
 
 def one_kernel(lines, start):

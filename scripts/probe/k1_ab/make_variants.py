@@ -40,8 +40,8 @@ def each_load(bd, f):
 
 
 def zeroed(s):
-    s = once(s, "    lds_own[wave][lane][(J - Jbase) & (kMfmaColTiles - 1)] = ownw;\n",
-             '    asm volatile("" :: "v"(ownw)); ownw = 0;\n    lds_own[wave][lane][(J - Jbase) & (kMfmaColTiles - 1)] = ownw;\n')
+    s = once(s, "    if (NS != kK1NoStore || diag) lds_own[wave][lane][(J - Jbase) & (kMfmaColTiles - 1)] = ownw;",
+             '    asm volatile("" :: "v"(ownw)); ownw = 0;\n    if (NS != kK1NoStore || diag) lds_own[wave][lane][(J - Jbase) & (kMfmaColTiles - 1)] = ownw;')
     s = once(s, "    lds_tr[(J - Jbase) & (kMfmaColTiles - 1)][lane][wave] = trw_out;\n",
              '    asm volatile("" :: "v"(trw_out));\n    lds_tr[(J - Jbase) & (kMfmaColTiles - 1)][lane][wave] = 0ull;\n')
     return once(s, "      unsigned int vf = flags;\n", '      asm volatile("" :: "v"(flags));\n      unsigned int vf = 0;\n')

@@ -4,7 +4,12 @@
 //     mode "k1"   : per variant in [variants] (comma separated; "fp64" = the all-FP64 route through
 //                   teaser_hip_set_option, "default" = the library's kernel, a NUMBER = TEASER_K1_VARIANT of the LAB
 //                   build, scripts/probe/k1_lab: 100 * log2(chunks) + 10 * plain + pipe): K1 ms per launch (HIP
-//                   events), step ms (synchronous API), FNV hash of two bitmaps (must agree across variants)
+//                   events), step ms (synchronous API), FNV hash of two bitmaps (must agree across variants).
+//                   Behind the two warm-up solves the handle of "default" is on the NO-STORE route (the closure decides
+//                   the bench workload): every timed K1 is the instantiation that stores no row, which is what a
+//                   counter pass (rocprofv3 --pmc, a run of its own) of mode "one" then sees under that kernel name.
+//                   "store" = the product library with a fresh handle per timed step: the storing (upper-triangle) K1,
+//                   for the comparison inside one binary (step ms then includes the handle's creation)
 //     mode "pipe" : registrations/s through teaser_hip_submit_batch / teaser_hip_wait for depth 1..4,
 //                   K1 staggering on and off
 //     (K1_PROBE_TAIL_SKIP=<mask> in the environment: the library's tail_skip setting -- stages not enqueued -- switched
@@ -195,7 +200,7 @@ int main(int argc, char** argv) {
   if (mode == "k1" || mode == "one") {
     for (const std::string& v : vs) {
       CK(teaser_hip_set_option(nullptr, "k1_fp64", v == "fp64" ? 1 : 0));
-      if (v != "fp64" && v != "default") setenv("TEASER_K1_VARIANT", v.c_str(), 1);  // (read by the lab build only)
+      if (v != "fp64" && v != "default" && v != "store") setenv("TEASER_K1_VARIANT", v.c_str(), 1);  // (read by the lab build only)
       teaser_hip_solver* h = nullptr;
       CK(teaser_hip_solver_create(&prm, 0, &h));
       for (int w = 0; w < 2; ++w)
@@ -207,6 +212,11 @@ int main(int argc, char** argv) {
       CK(hipDeviceSynchronize());
       const double t0 = now_ms();
       for (int it = 0; it < iters; ++it) {
+        if (v == "store") {  // a fresh handle per step: its first solve stores the upper triangle
+          teaser_hip_solver_destroy(h);
+          CK(teaser_hip_solver_create(&prm, 0, &h));
+          CK(teaser_hip_set_profiling(h, 2));
+        }
         CK(teaser_hip_solve_batch_device(h, P.d_src[it % 4], P.d_dst[it % 4], P.off.data(), P.n.data(), B, out.data()));
         teaser_profile_c pf;
         teaser_hip_get_profile(h, &pf);

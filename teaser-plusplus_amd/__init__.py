@@ -117,7 +117,7 @@ EXPORTED_SYMBOLS = [
     "teaser_hip_solve_device", "teaser_hip_solve_correspondences", "teaser_hip_solve_batch",
     "teaser_hip_solve_batch_device", "teaser_hip_get_max_clique", "teaser_hip_get_rotation_inliers",
     "teaser_hip_get_translation_inliers", "teaser_hip_get_input_ordered_translation_inliers",
-    "teaser_hip_get_inlier_graph_bitmap", "teaser_hip_get_inlier_graph_rows", "teaser_hip_get_degrees", "teaser_hip_solve_for_rotation",
+    "teaser_hip_get_inlier_graph_bitmap", "teaser_hip_get_inlier_graph_rows", "teaser_hip_get_graph_route", "teaser_hip_get_degrees", "teaser_hip_solve_for_rotation",
     "teaser_hip_solve_for_translation", "teaser_hip_scalar_tls", "teaser_hip_max_clique",
     "teaser_hip_set_profiling", "teaser_hip_set_option", "teaser_hip_get_option", "teaser_hip_get_profile", "teaser_hip_get_stream",
     "teaser_hip_last_error", "teaser_hip_abi_version", "teaser_hip_device_count", "teaser_hip_host_alloc",
@@ -236,6 +236,7 @@ def lib():
         getattr(L, nm).argtypes = [_vp, C.c_int32, _ip, _i64p]
     L.teaser_hip_get_inlier_graph_bitmap.argtypes = [_vp, C.c_int32, _u64p, _i64p]
     L.teaser_hip_get_inlier_graph_rows.argtypes = [_vp, C.c_int32, _u64p, _i64p, _ip]
+    L.teaser_hip_get_graph_route.argtypes = [_vp, C.c_int32, _ip, _i64p]
     L.teaser_hip_solve_for_rotation.argtypes = [_vp, _dp, _dp, C.c_int32, C.c_double, _dp, _u8p, _dp, _ip]
     L.teaser_hip_solve_for_translation.argtypes = [_vp, _dp, _dp, C.c_int32, _dp, _u8p]
     L.teaser_hip_scalar_tls.argtypes = [_vp, _dp, _dp, C.c_int32, _dp, _u8p]

@@ -714,16 +714,41 @@ constexpr int kK1Chunks = 1, kK1Occ = 3;
 // degree closure runs so (solver.hip); tim_mirror_lower_kernel rebuilds the lower triangle for whoever else reads it.
 // UW3 (lab build only, flat schedule): the three-MFMA u / w formulation on TimOperandTile3 operands, for A/B runs
 // against the X / Y chain inside one binary; d is then in the units of u^2 + w and the band constant k1c::consts's.
-template <bool PIPE, bool PLAIN, int OCC, int CHUNKS, bool LOWER, bool UW3 = false>
+// NS (the third store mode; with LOWER = false): kK1NoStore -- no row is stored at all.  The loop, the transposes and
+// the degree counting are the storing kernel's; the flush stores the one own word of the wave's DIAGONAL tile (both
+// directions of its 64 x 64 pairs: the fix-up reads the provisional bits of that tile's items there, K1 parks zero
+// for them), no other own word, no padding, no transposed word.  The route behind it (solver.hip) is the one on which
+// the closure evaluates the pairs of its candidate set itself (tim_closure_pairs_kernel) and nobody reads a row.
+// kK1Rebuild (with LOWER = true) -- the rows of such a batch rebuilt on demand from the handle's own operand arena:
+// the full store, nothing written to the regions, the segment counters or the states, the degrees added into a
+// scratch array nobody reads; problems on the FP64 body (their rows are in place) and, with rb_open, problems the
+// closure has decided are skipped, and a block walks the logical blocks lb, lb + gridDim.x, .. of the nlb_arg a
+// problem has: the open-only launch is then 64 workgroups per problem, not K1's grid.  Measured (profiles/r12a): on
+// K1's own grid the workgroups of an all-closed batch leave at once and cost 14 us alone, but each still needs a K1-sized
+// slot (144 VGPRs x 4 waves, 34 KB of LDS), and in the two-lane pipeline those slots are held by the OTHER lane's K1 --
+// the launch then ends with that K1 and the lane's tail behind it: the bench fell 1.4 % BELOW the parent, against
+// + 7.9 % with the small grid.  tim_fixup_replay_kernel puts the fix-up's recorded answers on top.
+constexpr int kK1NoStore = 1, kK1Rebuild = 2;
+template <bool PIPE, bool PLAIN, int OCC, int CHUNKS, bool LOWER, bool UW3 = false, int NS = 0>
 __global__ __launch_bounds__(256, OCC) void tim_graph_mfma3_kernel(
     const ProbDesc* __restrict__ descs, const double* __restrict__ src,
     const double* __restrict__ dst, const void* __restrict__ ops, const TimPrep* __restrict__ prep,
     uint64_t* __restrict__ bitmap, double beta, int gyr,
     unsigned long long* __restrict__ work, unsigned int* __restrict__ work_count,
-    ProbState* __restrict__ states, int32_t* __restrict__ deg, unsigned long long* __restrict__ regions, int Tmax) {
+    ProbState* __restrict__ states, int32_t* __restrict__ deg, unsigned long long* __restrict__ regions, int Tmax,
+    int rb_open, int nlb_arg) {
+  static_assert(NS == 0 || (NS == kK1NoStore && !LOWER) || (NS == kK1Rebuild && LOWER), "store modes");
+  if constexpr (NS == kK1Rebuild) {  // (uniform over the block)
+    if ((rb_open && states[blockIdx.y].deg_closed) || !prep[blockIdx.y].use_mfma) return;
+  }
   const ProbDesc d = descs[blockIdx.y];
   const int n = d.n, W = d.W;
   const int T = W, S = bm_stride(W);  // tiles = words of a bitmap row; words between two rows
+  // One pass per logical block.  Every instantiation but the rebuild's makes exactly one (lb = blockIdx.x; the loop's
+  // condition is constant false and `continue` is its early exit), so the body below is not indented for it.
+  int lb = (int)blockIdx.x;
+  const int nlb = NS == kK1Rebuild ? nlb_arg : (int)gridDim.x;
+  do {
   // block decode: only the blocks that touch the upper triangle are launched (column group X has
   // min(gyr, 2 CHUNKS (X + 1)) row groups; blockIdx.x enumerates them), in an XCD-aware order: workgroups go to the
   // 8 XCDs round robin in dispatch order, so the blocks of one XCD take CONSECUTIVE logical indices -- the four
@@ -731,7 +756,7 @@ __global__ __launch_bounds__(256, OCC) void tim_graph_mfma3_kernel(
   // about the same time and merge in that L2, and a column group's operands are fetched into one L2 instead of eight
   // (fxr::decode_block, fixup_regions.h: the host test of the region arena runs the same decode)
   int Ig, X;
-  fxr::decode_block((int)blockIdx.x, (int)gridDim.x, gyr, CHUNKS, &Ig, &X);
+  fxr::decode_block(lb, nlb, gyr, CHUNKS, &Ig, &X);
   // a block = 4 row tiles x CHUNKS chunks of kMfmaColTiles column tiles, walked chunk after chunk by the same four
   // waves: a wave's set-up (descriptors, band constants, row operands: three dependent memory round trips) and its
   // wind-down (the last stores' acknowledgement) took 40 % of its lifetime when it lived for 8 column tiles only
@@ -743,6 +768,7 @@ __global__ __launch_bounds__(256, OCC) void tim_graph_mfma3_kernel(
   // regions of a row tile as one run.  Cells exist in the upper triangle of the batch's largest problem (Tmax tiles)
   // only; every cell a wave owns gets a count word on every path, also on the early exits (the arena is not cleared).
   auto region_of = [&](int wv, int chunk) -> unsigned long long* {
+    if constexpr (NS == kK1Rebuild) return nullptr;  // (the arena keeps the items the fix-up has recorded its answers in)
     const int Iw = I0 + wv, Xc = X * CHUNKS + chunk;
     return fxr::is_cell(Iw, Xc, Tmax) ? regions + fxr::region_offset((int)blockIdx.y, Tmax, Iw, Xc) : nullptr;
   };
@@ -754,7 +780,7 @@ __global__ __launch_bounds__(256, OCC) void tim_graph_mfma3_kernel(
   };
   if (I0 >= T || Jbase >= T || Jbase + kBlockColTiles - 1 < I0) {  // outside / below the diagonal
     zero_regions();
-    return;
+    continue;
   }
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -819,7 +845,7 @@ __global__ __launch_bounds__(256, OCC) void tim_graph_mfma3_kernel(
         if (!(jb + kColTilesPerWave - 1 < I || jb >= T))
           tim_wave_fp64<0>(ps, pd, bm, n, W, I, jb, kc, reinterpret_cast<double*>(&lds_own[wave][0][0]));
     zero_regions();
-    return;
+    continue;
   }
   const __amdgpu_buffer_rsrc_t deg_rsrc = __builtin_amdgcn_make_buffer_rsrc(
       (void*)(deg + d.pt_off), 0, (int)((unsigned int)n * 4u), 0x00020000);
@@ -928,7 +954,7 @@ __global__ __launch_bounds__(256, OCC) void tim_graph_mfma3_kernel(
     const uint64_t colmask = (n - j0 >= 64) ? ~0ull : ((1ull << (n - j0)) - 1ull);
     ownw &= colmask;
     if (diag) ownw &= ~(1ull << lane);
-    lds_own[wave][lane][(J - Jbase) & (kMfmaColTiles - 1)] = ownw;
+    if (NS != kK1NoStore || diag) lds_own[wave][lane][(J - Jbase) & (kMfmaColTiles - 1)] = ownw;  // (nobody reads the others back)
     degacc += __builtin_popcountll(ownw);
     // rows beyond n hold no bits (clamped: the padding repeats the last point); the diagonal tile has no transposed copy
     const uint64_t trw_out = diag ? 0ull : (trw & rowmask);  // (columns beyond n: the flush stores no such row)
@@ -1101,7 +1127,15 @@ __global__ __launch_bounds__(256, OCC) void tim_graph_mfma3_kernel(
       if (CHUNKS > 1) __syncthreads();  // (the next chunk rewrites lds_tr)
     }
     // own words of the chunk: lanes 8r..8r+7 store the (up to) 8 consecutive words of one row
-    if (nact > 0) {
+    if (NS == kK1NoStore) {
+      // ... of which this mode stores one: word I of the wave's 64 rows, where the chunk holds its diagonal tile
+      if (Ja == I && Ja < Jc1) {
+        const uint64_t w = lds_own[wave][lane][(I - Jbase) & (kMfmaColTiles - 1)];
+        __builtin_amdgcn_raw_buffer_store_b64(u32x2{(unsigned int)w, (unsigned int)(w >> 32)}, bm_rsrc,
+                                              I * 64 + lane < n ? ((unsigned int)(I * 64 + lane) * (unsigned int)S + (unsigned int)I) * 8u : kOobOffset,
+                                              0, 0);
+      }
+    } else if (nact > 0) {
       const int kk = lane & 7, J = Jc0 + kk;
       // (the problem's last chunk ends at the row stride: its words T .. S - 1 are the rows' padding, stored as zeros, so
       // that this run too covers its whole 64 bytes)
@@ -1120,7 +1154,7 @@ __global__ __launch_bounds__(256, OCC) void tim_graph_mfma3_kernel(
     // wave's LDS slice (the own words are on their way), then the wave's OWN region of the worklist (plain stores, no
     // atomic); only a wave with more items sends the rest through the problem's counted segment.
     int wcount = 0;  // wave-uniform
-    {
+    if constexpr (NS != kK1Rebuild) {
       // flags: 4 bits per active column tile, the OLDEST tile in the highest nibble; bit 3: (ct 0, rt 0), 2: (0, 1),
       // 1: (1, 0), 0: (1, 1).  Lane-tiles beyond n (padding: copies of the last point) are dropped: rows only in the
       // problem's last row tile, columns only in its last column tile.
@@ -1165,7 +1199,7 @@ __global__ __launch_bounds__(256, OCC) void tim_graph_mfma3_kernel(
       }
     }
     flags = 0;
-    {
+    if constexpr (NS != kK1Rebuild) {
       // (a wave has items only where its row tile reaches the chunk's columns, i.e. in a cell: region != null then)
       const int nreg = !region ? 0 : (wcount < kRegionItems ? wcount : kRegionItems);
       if (lane == 0 && region) region[0] = (unsigned long long)nreg;
@@ -1187,6 +1221,7 @@ __global__ __launch_bounds__(256, OCC) void tim_graph_mfma3_kernel(
   }
   if (rowvalid)
     __builtin_amdgcn_raw_ptr_buffer_atomic_add_i32(degacc, deg_rsrc, (unsigned int)(I * 64 + lane) * 4u, 0, 0);
+  } while (NS == kK1Rebuild && (__syncthreads(), (lb += (int)gridDim.x) < nlb));  // (the next pass rewrites the LDS arrays)
 }
 
 // FP64 resolution of the filter's GROUP items: 16 lanes per item, lane q owns the pair
@@ -1204,18 +1239,30 @@ __global__ __launch_bounds__(256, OCC) void tim_graph_mfma3_kernel(
 // Overflow (the problem's counted segment was too small): its bitmap is cleared instead (the stages enqueued behind
 // K1 see an empty graph, not unresolved, possibly asymmetric bits), the problem is flagged and the host reruns the
 // batch on the FP64 kernel.
+// mode: kFixUpper -- K1 left the lower triangle out.  NOSTORE -- K1 stored nothing but the diagonal tiles' words
+// (kK1NoStore): outside a diagonal tile the provisional bits come with the item on both paths, the staged one and the
+// counted segment's, no bitmap bit is flipped and only the two degrees follow; and every item gets the 16 EXACT bits
+// of its pairs written back into its own word (one ballot per step, one lane per item).  The worklist arena lives
+// until the handle's next solve, so it then holds the reference predicate's answer for every pair the filter could
+// not decide: what tim_fixup_replay_kernel puts on top of a rebuilt bitmap without looking at a point.
+// NOSTORE is a template parameter, mode carries kFixUpper only: the storing routes' fix-up is then the code it was
+// (66 VGPRs, 28 KB of LDS; with a runtime flag every route paid the write-back's 84 VGPRs and the queue's home indices).
+constexpr int kFixUpper = 1;
+template <bool NOSTORE>
 __global__ __launch_bounds__(256) void tim_fixup_group_kernel(const ProbDesc* __restrict__ descs, int batch,
                                                               const double* __restrict__ src,
                                                               const double* __restrict__ dst,
                                                               uint64_t* __restrict__ bitmap, double beta,
-                                                              const unsigned long long* __restrict__ work,
+                                                              unsigned long long* __restrict__ work,
                                                               const unsigned int* __restrict__ work_count,
                                                               ProbState* __restrict__ states,
                                                               int32_t* __restrict__ deg,
-                                                              const unsigned long long* __restrict__ regions,
+                                                              unsigned long long* __restrict__ regions,
                                                               int Tmax,
-                                                              const TimPrep* __restrict__ prep, int upper) {
+                                                              const TimPrep* __restrict__ prep, int mode) {
   TAIL_WAVE_PRIO();
+  constexpr bool nostore = NOSTORE;
+  const bool upper = nostore || (mode & kFixUpper) != 0;
   const int prob = blockIdx.y;
   const unsigned int total = work_count[prob];
   const TimPrep tpr = prep[prob];
@@ -1267,8 +1314,9 @@ __global__ __launch_bounds__(256) void tim_fixup_group_kernel(const ProbDesc* __
   // 64 x 10 k batch, two thirds of what K1 itself issues, and on a step bound by the board's power limit the fix-up's
   // energy -- 0.1 J of 1.1 -- is paid for in K1's clock: profiles/r6v, r6w.)
   __shared__ __attribute__((aligned(16))) double col_pts[4][64][6];
-  auto resolve = [&](unsigned long long it, bool valid, auto staged, int tile, int slot) {
+  auto resolve = [&](unsigned long long it, bool valid, auto staged, int tile, int slot, unsigned long long* home) {
     constexpr bool STAGED = decltype(staged)::value;
+    const bool live = valid;  // (the item exists: `valid` goes on to mean this lane's pair)
     int r = fxi::row0(it) + rq, col = fxi::col(it);
     valid = valid && r < n && col < n && r != col;
     r = valid ? r : (STAGED ? tile * 64 : 0);
@@ -1288,8 +1336,9 @@ __global__ __launch_bounds__(256) void tim_fixup_group_kernel(const ProbDesc* __
     }
     unsigned int* wp = bm32 + 2 * ((int64_t)r * S + (col >> 6)) + ((col >> 5) & 1);
     const unsigned int bit = 1u << (col & 31);
+    const bool offdiag = (r >> 6) != (col >> 6);
     bool prov;
-    if (STAGED && (r >> 6) != (col >> 6)) {  // (uniform over the 16 lanes of an item)
+    if ((STAGED || nostore) && offdiag) {  // (uniform over the valid lanes of an item)
       prov = fxi::bit(it, q);
     } else {
       prov = (*wp & bit) != 0u;
@@ -1299,10 +1348,14 @@ __global__ __launch_bounds__(256) void tim_fixup_group_kernel(const ProbDesc* __
     bool e = tim_edge_fast(ax, ay, az, bx, by, bz, kc, &unc, &shortp);
     e |= shortp;
     if (unc) e = tim_edge_exact(ax, ay, az, bx, by, bz, beta);
+    if constexpr (nostore) {  // the item's word takes its pairs' exact bits: lanes 16 sub .. 16 sub + 15 of the ballot
+      const uint64_t em = __builtin_amdgcn_ballot_w64(valid && e);
+      if (q == 0 && live) *home = fxi::pack((unsigned int)fxi::row0(it), (unsigned int)fxi::col(it), (unsigned int)(em >> (16 * sub)) & 0xffffu);
+    }
     if (!valid || prov == e) return;
-    atomicXor(wp, bit);
+    if (!nostore || !offdiag) atomicXor(wp, bit);
     atomicAdd(dg + r, e ? 1 : -1);
-    if ((r >> 6) != (col >> 6)) {  // the transposed copy, where there is one, and the column's degree
+    if (offdiag) {  // the transposed copy, where there is one, and the column's degree
       if (!upper) atomicXor(bm32 + 2 * ((int64_t)col * S + (r >> 6)) + ((r >> 5) & 1), 1u << (r & 31));
       atomicAdd(dg + col, e ? 1 : -1);
     }
@@ -1310,9 +1363,12 @@ __global__ __launch_bounds__(256) void tim_fixup_group_kernel(const ProbDesc* __
   // The per-wave item queue: a region adds at most 63 items to fewer than 64 pending ones.
   __shared__ unsigned long long queue[4][2 * kRegionWords];
   static_assert(kRegionWords == 64, "one region = one 64-lane load");
+  // (NOSTORE) where a queued item came from: its word's index in the row tile's run of regions (< 2^16: at most
+  // 128 chunks of 64 words)
+  __shared__ unsigned short qsrc[nostore ? 4 : 1][nostore ? 2 * kRegionWords : 1];
   const int T = W, nch = fxr::n_chunks(T);
-  // one round: the first `cnt` (<= 64) items of the queue, all of row tile `tile`
-  auto round = [&](int cnt, int tile) {
+  // one round: the first `cnt` (<= 64) items of the queue, all of row tile `tile`, whose regions begin at `run`
+  auto round = [&](int cnt, int tile, unsigned long long* run) {
     if (lane < cnt) {  // item `lane`: its column point
       const int col = min(fxi::col(queue[wave][lane]), n - 1);
       double* cp = col_pts[wave][lane];
@@ -1324,7 +1380,7 @@ __global__ __launch_bounds__(256) void tim_fixup_group_kernel(const ProbDesc* __
 #pragma nounroll
     for (int base = 0; base < cnt; base += 4) {
       const int k = base + sub;
-      resolve(queue[wave][k], k < cnt, std::true_type(), tile, k);
+      resolve(queue[wave][k], k < cnt, std::true_type(), tile, k, nostore ? run + qsrc[nostore ? wave : 0][nostore ? k : 0] : nullptr);
     }
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");  // (the next round overwrites the slices)
   };
@@ -1343,7 +1399,7 @@ __global__ __launch_bounds__(256) void tim_fixup_group_kernel(const ProbDesc* __
         rp[3] = pd[3 * pr]; rp[4] = pd[3 * pr + 1]; rp[5] = pd[3 * pr + 2];
       }
       const int Xc0 = fxr::first_chunk(tile);
-      const unsigned long long* reg = regions + fxr::region_offset(prob, Tmax, tile, Xc0);
+      unsigned long long* reg = regions + fxr::region_offset(prob, Tmax, tile, Xc0);
       int qn = 0;  // queued items (wave-uniform), < 64 between regions
       unsigned long long mine = reg[lane];
       for (int Xc = Xc0; Xc < nch; ++Xc) {
@@ -1352,26 +1408,154 @@ __global__ __launch_bounds__(256) void tim_fixup_group_kernel(const ProbDesc* __
         const int cnt = min((int)__builtin_amdgcn_readfirstlane((unsigned int)cur), kRegionItems);
         if (cnt <= 0) continue;
         // append: the valid lanes are 1 .. cnt, so the exclusive prefix of the valid flags is lane - 1
-        if (lane >= 1 && lane <= cnt) queue[wave][qn + lane - 1] = cur;
+        if (lane >= 1 && lane <= cnt) {
+          queue[wave][qn + lane - 1] = cur;
+          if constexpr (nostore) qsrc[wave][qn + lane - 1] = (unsigned short)((Xc - Xc0) * kRegionWords + lane);
+        }
         qn += cnt;
         if (qn >= kRegionWords) {
           __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-          round(kRegionWords, tile);
+          round(kRegionWords, tile, reg);
           qn -= kRegionWords;
           const unsigned long long moved = queue[wave][kRegionWords + lane];  // (every lane reads before any writes)
+          unsigned short moved_src = 0;
+          if constexpr (nostore) moved_src = qsrc[wave][kRegionWords + lane];
           __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-          if (lane < qn) queue[wave][lane] = moved;
+          if (lane < qn) {
+            queue[wave][lane] = moved;
+            if constexpr (nostore) qsrc[wave][lane] = moved_src;
+          }
         }
       }
       if (qn > 0) {
         __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-        round(qn, tile);
+        round(qn, tile, reg);
+      }
+    }
+  }
+  unsigned long long* seg = work + (((size_t)tpr.seg_off_hi << 32) | (size_t)tpr.seg_off_lo);
+  const unsigned int ngrp = gridDim.x * 16;
+  for (unsigned int w = (blockIdx.x * 256 + threadIdx.x) >> 4; w < total; w += ngrp) resolve(seg[w], true, std::false_type(), 0, 0, seg + w);
+}
+
+// The recorded answers of a no-store batch's fix-up put on top of the rows K1 has just rebuilt (kK1Rebuild): 16 lanes
+// per item; for every pair of an item the recorded bit is the reference predicate's answer and the bit in the bitmap
+// the filter's, stored a launch ago; where they differ both copies are flipped (a diagonal tile's pair has one: its
+// mirror image is a pair of its own).  No point is loaded, nothing is evaluated, no degree is touched.  A wave takes a
+// row tile's run of regions, region after region; the counted segment follows.  open_only: as in K1.
+__global__ __launch_bounds__(256) void tim_fixup_replay_kernel(const ProbDesc* __restrict__ descs,
+                                                               uint64_t* __restrict__ bitmap,
+                                                               const unsigned long long* __restrict__ work,
+                                                               const unsigned int* __restrict__ work_count,
+                                                               const ProbState* __restrict__ states,
+                                                               const unsigned long long* __restrict__ regions,
+                                                               int Tmax, const TimPrep* __restrict__ prep, int open_only) {
+  const int prob = blockIdx.y;
+  const TimPrep tpr = prep[prob];
+  const unsigned int total = work_count[prob];
+  if (!tpr.use_mfma || total > tpr.seg_cap || (open_only && states[prob].deg_closed)) return;
+  const ProbDesc d = descs[prob];
+  const int n = d.n, W = d.W, S = bm_stride(W), T = W, nch = fxr::n_chunks(T);
+  unsigned int* bm32 = reinterpret_cast<unsigned int*>(bitmap + d.bm_off);
+  const int lane = threadIdx.x & 63, q = lane & 15, sub = lane >> 4;
+  const int rq = fxi::row_of(q);
+  auto replay = [&](unsigned long long it, bool live) {
+    const int r = fxi::row0(it) + rq, col = fxi::col(it);
+    if (!live || r >= n || col >= n || r == col) return;
+    unsigned int* wp = bm32 + 2 * ((int64_t)r * S + (col >> 6)) + ((col >> 5) & 1);
+    const unsigned int bit = 1u << (col & 31);
+    if (((*wp & bit) != 0u) == fxi::bit(it, q)) return;
+    atomicXor(wp, bit);
+    if ((r >> 6) != (col >> 6)) atomicXor(bm32 + 2 * ((int64_t)col * S + (r >> 6)) + ((r >> 5) & 1), 1u << (r & 31));
+  };
+  const int wv = blockIdx.x * 4 + (int)(threadIdx.x >> 6), nwv = gridDim.x * 4;
+  for (int tile = wv; tile < T; tile += nwv) {
+    const int Xc0 = fxr::first_chunk(tile);
+    const unsigned long long* reg = regions + fxr::region_offset(prob, Tmax, tile, Xc0);
+    for (int Xc = Xc0; Xc < nch; ++Xc) {
+      const unsigned long long cur = reg[(size_t)(Xc - Xc0) * kRegionWords + lane];  // lane 0: the count, lane k: item k
+      const int cnt = min((int)__builtin_amdgcn_readfirstlane((unsigned int)cur), kRegionItems);
+      for (int base = 0; base < cnt; base += 4) {
+        const int k = base + sub;  // item k sits in lane k + 1
+        const unsigned long long it = __shfl(cur, min(k + 1, 63));
+        replay(it, k < cnt);
       }
     }
   }
   const unsigned long long* seg = work + (((size_t)tpr.seg_off_hi << 32) | (size_t)tpr.seg_off_lo);
   const unsigned int ngrp = gridDim.x * 16;
-  for (unsigned int w = (blockIdx.x * 256 + threadIdx.x) >> 4; w < total; w += ngrp) resolve(seg[w], true, std::false_type(), 0, 0);
+  for (unsigned int w = (blockIdx.x * 256 + threadIdx.x) >> 4; w < total; w += ngrp) replay(seg[w], true);
+}
+
+// Launch 2 of the degree closure where K1 has stored no row (kTimNoStore): the partial compact rows of the candidate
+// set R straight from the points.  Keys: degree << 16 | vertex by rank, as the order launch leaves them; for every
+// rank pair a < b the predicate is evaluated ONCE, with the two-step expression of the fix-up's resolve() (the FP64
+// fast path with its guard band, the reference expression inside it: the bit a stored row would hold), and lands in
+// word (a, b / 64) of the partial pool; the diagonal bit and everything at or below it are zero.  The symmetrise
+// launch ORs every partial row with the transpose of the pool, so covering every unordered pair once is enough, and
+// this rule leaves the blocks below the diagonal without work.  A wave takes a 64 x 64 block (A, B >= A) of rank
+// pairs: the 64 row points staged in its LDS slice (a broadcast read per row), lane l's column point (rank 64 B + l)
+// in registers, one ballot per row.  The points of R are gathered through the keys -- 2 x 64 points per block, from
+// the L2 that holds the problem's 48 n bytes; |R| ~ 900 at N = 10 k is ~120 blocks, ~0.5 M pairs per problem.
+__global__ __launch_bounds__(256) void tim_closure_pairs_kernel(const ProbDesc* __restrict__ descs,
+                                                                const double* __restrict__ src,
+                                                                const double* __restrict__ dst,
+                                                                uint64_t* __restrict__ part_pool /* [batch][kCoreCap][kCoreWords] */,
+                                                                const uint32_t* __restrict__ key_pool /* [batch][kCoreCap] */,
+                                                                const int32_t* __restrict__ counters, double beta) {
+  TAIL_WAVE_PRIO();
+  const int m = counters[blockIdx.y];
+  if (m < 2) return;
+  const ProbDesc d = descs[blockIdx.y];
+  const double* ps = src + 3 * d.pt_off;
+  const double* pd = dst + 3 * d.pt_off;
+  const uint32_t* keys = key_pool + (size_t)blockIdx.y * kCoreCap;
+  uint64_t* part = part_pool + (size_t)blockIdx.y * kCoreCap * kCoreWords;
+  EdgeConst kc;
+  kc.beta = beta;
+  kc.beta2 = beta * beta;
+  kc.m2beta2 = -2.0 * kc.beta2;
+  kc.beta4 = kc.beta2 * kc.beta2;
+  kc.s_hat = 1.0;
+  __shared__ double row_pts[4][64][6];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int ng = (m + 63) >> 6, units = ng * (ng + 1) / 2;
+  for (int u = blockIdx.x * 4 + wave; u < units; u += gridDim.x * 4) {
+    int A = 0, rem = u;  // row block A has the ng - A blocks A .. ng - 1
+    while (rem >= ng - A) {
+      rem -= ng - A;
+      ++A;
+    }
+    const int B = A + rem, ra = 64 * A + lane, rb = 64 * B + lane;
+    {
+      const int v = (int)(keys[min(ra, m - 1)] & 0xffffu);
+      double* rp = row_pts[wave][lane];
+      rp[0] = ps[3 * v]; rp[1] = ps[3 * v + 1]; rp[2] = ps[3 * v + 2];
+      rp[3] = pd[3 * v]; rp[4] = pd[3 * v + 1]; rp[5] = pd[3 * v + 2];
+    }
+    const int vb = (int)(keys[min(rb, m - 1)] & 0xffffu);
+    const double cx = ps[3 * vb], cy = ps[3 * vb + 1], cz = ps[3 * vb + 2];
+    const double ex = pd[3 * vb], ey = pd[3 * vb + 1], ez = pd[3 * vb + 2];
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");  // wave-private slice: same-wave ordering suffices
+    uint64_t word = 0ull;
+    const int rows = min(64, m - 64 * A);
+    for (int r = 0; r < rows; ++r) {
+      const double* rp = row_pts[wave][r];
+      const double ax = cx - rp[0], ay = cy - rp[1], az = cz - rp[2], bx = ex - rp[3], by = ey - rp[4], bz = ez - rp[5];
+      bool unc, shortp;
+      bool e = tim_edge_fast(ax, ay, az, bx, by, bz, kc, &unc, &shortp);
+      e |= shortp;
+      if (unc) e = tim_edge_exact(ax, ay, az, bx, by, bz, beta);
+      const uint64_t mk = __builtin_amdgcn_ballot_w64(e && rb < m && 64 * A + r < rb);
+      word = lane == r ? mk : word;
+    }
+    if (ra < m) {
+      part[(size_t)ra * kCoreWords + B] = word;
+      if (A == B)  // (the row's words in front of its diagonal block: no pair of theirs is evaluated from this side)
+        for (int Bz = 0; Bz < A; ++Bz) part[(size_t)ra * kCoreWords + Bz] = 0ull;
+    }
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");  // (the next block overwrites the slice)
+  }
 }
 
 // The lower triangle of a bitmap whose K1 stored the upper one only (LOWER = false), rebuilt on demand: per problem and
@@ -1524,7 +1708,8 @@ static K1Variant k1_lab_variant() {
 // + degrees), 2 FP64 fix-up of the worklist (+ overflow clear).  Three calls so that the profiling span
 // of phase 1 is that kernel alone.  Phases 1 and 2 with kTimUpperOnly added: K1 stores the upper triangle only and the
 // fix-up flips no transposed bit.  kTimMirror / kTimMirrorOpen: the lower triangle rebuilt from the upper one, for
-// every problem / for the problems the degree closure left open (only d_desc, batch, max_n, d_bitmap, d_state are read).  d_pk: total_tiles TimOperandTile2, total_tiles = sum of the problems' W;
+// every problem / for the problems the degree closure left open (only d_desc, batch, max_n, d_bitmap, d_state are read).
+// kTimNoStore on phases 1 and 2, kTimClosurePairs, kTimRebuild / kTimRebuildOpen: the route without stores (internal.h).  d_pk: total_tiles TimOperandTile2, total_tiles = sum of the problems' W;
 // d_prep: tim_prep_bytes(batch), zero except the segment fields (tim_prep_fill_segments), part of the header upload;
 // work_cap = tim_work_items(n, batch).
 void launch_tim_graph_mfma(hipStream_t s, int phase, const ProbDesc* d_desc, int batch, int max_n,
@@ -1544,13 +1729,25 @@ void launch_tim_graph_mfma(hipStream_t s, int phase, const ProbDesc* d_desc, int
                        d_bitmap, d_state, phase == kTimMirrorOpen ? 1 : 0);
     return;
   }
+  const double beta = 2 * noise_bound * sqrt(cbar2);  // registration.cc:438
+  if (phase == kTimClosurePairs) {  // d_pk: the closure's scratch, d_prep: its counters (2 * batch ints, zero on entry)
+    int32_t* counters = reinterpret_cast<int32_t*>(d_prep);
+    launch_degree_closure_order(s, d_desc, batch, d_deg, d_state, d_pk, counters);
+    const ClosurePools cp = degree_closure_pools(d_pk, batch);
+    hipLaunchKernelGGL(tim_closure_pairs_kernel, dim3(degree_closure_wgs(batch), batch), dim3(256), 0, s, d_desc, d_src, d_dst,
+                       cp.part, cp.keys, counters, beta);
+    return;
+  }
 #ifdef TEASER_K1_LAB
-  const bool upper = false;  // the lab instantiations keep the full store, and the fix-up its transposed flips with them
+  // the lab instantiations keep the full store, and the fix-up its flips of both copies with them: a rebuild then finds
+  // every row in place
+  const bool upper = false, nostore = false;
+  if (phase == kTimRebuild || phase == kTimRebuildOpen) return;
 #else
   const bool upper = (phase & kTimUpperOnly) != 0;
+  const bool nostore = (phase & kTimNoStore) != 0;
 #endif
-  phase &= ~kTimUpperOnly;
-  const double beta = 2 * noise_bound * sqrt(cbar2);  // registration.cc:438
+  phase &= ~(kTimUpperOnly | kTimNoStore);
   TimPrep* prep = reinterpret_cast<TimPrep*>(d_prep);
   unsigned long long* work = reinterpret_cast<unsigned long long*>(d_work);
   unsigned int* work_count = reinterpret_cast<unsigned int*>(reinterpret_cast<char*>(d_prep) +
@@ -1581,7 +1778,7 @@ void launch_tim_graph_mfma(hipStream_t s, int phase, const ProbDesc* d_desc, int
 #define TIM_K1_LAUNCH_OCC(PIPE, PLAIN, OCC, CHUNKS, ...)                                                                       \
   hipLaunchKernelGGL((tim_graph_mfma3_kernel<PIPE, PLAIN, OCC, CHUNKS, __VA_ARGS__>), dim3(tim_mfma_blocks(T, CHUNKS), batch), \
                      dim3(256), 0, s, d_desc, d_src, d_dst, (const void*)d_pk, prep, d_bitmap, beta, gyr, work, work_count,    \
-                     d_state, d_deg, regions, T)
+                     d_state, d_deg, regions, T, 0, 0)
 #ifdef TEASER_K1_LAB
 #define TIM_K1_LAB_CASE(PIPE, PLAIN)                             \
   if (lab.pipe == (PIPE ? 1 : 0) && lab.plain == (PLAIN ? 1 : 0)) { \
@@ -1601,7 +1798,9 @@ void launch_tim_graph_mfma(hipStream_t s, int phase, const ProbDesc* d_desc, int
     }
 #undef TIM_K1_LAB_CASE
 #else
-    if (upper) {
+    if (nostore) {
+      TIM_K1_LAUNCH_OCC(kK1Pipe, kK1Plain, kK1Occ, kK1Chunks, false, false, kK1NoStore);
+    } else if (upper) {
       TIM_K1_LAUNCH_OCC(kK1Pipe, kK1Plain, kK1Occ, kK1Chunks, false);
     } else {
       TIM_K1_LAUNCH(kK1Pipe, kK1Plain, kK1Chunks);
@@ -1609,15 +1808,33 @@ void launch_tim_graph_mfma(hipStream_t s, int phase, const ProbDesc* d_desc, int
 #endif
 #undef TIM_K1_LAUNCH
 #undef TIM_K1_LAUNCH_OCC
+#ifndef TEASER_K1_LAB
+  } else if (phase == kTimRebuild || phase == kTimRebuildOpen) {
+    // K1's full store once more (no worklist, the degrees into d_deg: a scratch array), then the recorded answers on
+    // top.  Behind the closure most or all problems are skipped: the open-only launch is sized like the mirror launch
+    // (a block walks its share of a problem's logical blocks), the launch for the getters has K1's own grid.
+    const int gyr = (T + kMfmaRowTiles - 1) / kMfmaRowTiles, nlb = tim_mfma_blocks(T, kK1Chunks);
+    const int open_only = phase == kTimRebuildOpen ? 1 : 0;
+    // (two workgroups per CU: the pass loop keeps ~24 more registers live than one pass, and at three the kernel spills)
+    hipLaunchKernelGGL((tim_graph_mfma3_kernel<kK1Pipe, kK1Plain, 2, kK1Chunks, true, false, kK1Rebuild>),
+                       dim3(open_only ? std::min(64, nlb) : nlb, batch), dim3(256), 0, s, d_desc, d_src, d_dst,
+                       (const void*)d_pk, prep, d_bitmap, beta, gyr, work, work_count, d_state, d_deg, regions, T, open_only, nlb);
+    hipLaunchKernelGGL(tim_fixup_replay_kernel, dim3((unsigned)std::max(4, ((T + 3) / 4 + 1) / 2), batch), dim3(256), 0, s,
+                       d_desc, d_bitmap, work, work_count, d_state, regions, T, prep, open_only);
+#endif
   } else {
     // a wave per PAIR of row tiles (p, T - 1 - p) of the largest problem, four pairs per workgroup; S_FIXUP_WGS forces
     // the workgroups per problem (the waves stride over the pairs).  The kernel also counts the degrees of the
     // problems that ran the FP64 body inside K1 (no degree atomics there)
     const int64_t forced_wgs = setting(S_FIXUP_WGS);
     const int64_t fix_wgs = forced_wgs > 0 ? forced_wgs : ((T + 1) / 2 + 3) / 4;
-    hipLaunchKernelGGL(tim_fixup_group_kernel, dim3((unsigned)std::max<int64_t>(4, fix_wgs), batch),
-                       dim3(256), 0, s, d_desc, batch, d_src, d_dst, d_bitmap, beta, work, work_count, d_state, d_deg,
-                       regions, T, prep, upper ? 1 : 0);
+    const dim3 fix_grid((unsigned)std::max<int64_t>(4, fix_wgs), batch);
+    if (nostore)
+      hipLaunchKernelGGL(tim_fixup_group_kernel<true>, fix_grid, dim3(256), 0, s, d_desc, batch, d_src, d_dst, d_bitmap, beta,
+                         work, work_count, d_state, d_deg, regions, T, prep, 0);
+    else
+      hipLaunchKernelGGL(tim_fixup_group_kernel<false>, fix_grid, dim3(256), 0, s, d_desc, batch, d_src, d_dst, d_bitmap, beta,
+                         work, work_count, d_state, d_deg, regions, T, prep, upper ? kFixUpper : 0);
   }
 }
 

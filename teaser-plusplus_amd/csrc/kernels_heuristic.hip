@@ -645,8 +645,7 @@ __device__ __attribute__((noinline)) void closure_round(const uint64_t* __restri
 // symmetrise + H launch, and the verdict from the H values and the compact matrix (one workgroup per problem): h1, the
 // core peel, the clique in ascending order, the problem state.
 // ------------------------------------------------------------------------------------------
-constexpr int kCoreCap = 2048;     // |R|
-constexpr int kCoreWords = kCoreCap / 64;
+// (kCoreCap = |R| and kCoreWords: internal.h -- the no-store route's pair kernel in kernels_graph.hip fills the partial pool)
 constexpr int kDegBins = kCoreCap; // histogram bins (the last one clamps): a threshold t >= kCoreCap cannot be certified anyway
 constexpr int kDegMaxW = 1024;     // n <= 65536
 constexpr int kDegThreads = 256;
@@ -1303,20 +1302,42 @@ int64_t degree_closure_scratch_bytes(int batch) {
   return (int64_t)std::max(batch, 1) * (2 * (int64_t)kCoreCap * kCoreWords * 8 /* partial + full rows */ + (int64_t)kCoreCap * 8);
 }
 
+int degree_closure_wgs(int batch) {
+  const int forced = (int)setting(S_DEG_CLOSURE_WGS);
+  return forced > 0 ? std::min(forced, 64) : std::max(1, std::min(16, 1024 / std::max(batch, 1)));
+}
+
+ClosurePools degree_closure_pools(void* d_scratch, int batch) {
+  ClosurePools cp;
+  cp.comp = reinterpret_cast<uint64_t*>(d_scratch);
+  cp.part = cp.comp + (size_t)batch * kCoreCap * kCoreWords;
+  cp.h = reinterpret_cast<int32_t*>(cp.part + (size_t)batch * kCoreCap * kCoreWords);
+  cp.keys = reinterpret_cast<uint32_t*>(cp.h + (size_t)batch * kCoreCap);
+  return cp;
+}
+
+void launch_degree_closure_order(hipStream_t s, const ProbDesc* d_desc, int batch, const int32_t* d_deg, ProbState* d_state,
+                                 void* d_scratch, int32_t* d_counters) {
+  hipLaunchKernelGGL(degree_closure_order_kernel, dim3(1, batch), dim3(kDegThreads), 0, s, d_desc, d_deg, d_state,
+                     degree_closure_pools(d_scratch, batch).keys, d_counters, batch);
+}
+
 void launch_degree_closure(hipStream_t s, const ProbDesc* d_desc, int batch, const uint64_t* d_bitmap,
                            const int32_t* d_deg, ProbState* d_state, int32_t* d_clique, void* d_scratch,
                            int32_t* d_counters) {
   if (batch <= 0) return;
-  const int forced = (int)setting(S_DEG_CLOSURE_WGS);
-  const int G = forced > 0 ? std::min(forced, 64) : std::max(1, std::min(16, 1024 / batch));
-  uint64_t* comp = reinterpret_cast<uint64_t*>(d_scratch);
-  uint64_t* part = comp + (size_t)batch * kCoreCap * kCoreWords;
-  int32_t* hp = reinterpret_cast<int32_t*>(part + (size_t)batch * kCoreCap * kCoreWords);
-  uint32_t* kp = reinterpret_cast<uint32_t*>(hp + (size_t)batch * kCoreCap);
-  hipLaunchKernelGGL(degree_closure_order_kernel, dim3(1, batch), dim3(kDegThreads), 0, s, d_desc, d_deg, d_state, kp,
-                     d_counters, batch);
-  hipLaunchKernelGGL(degree_closure_rows_kernel, dim3(G, batch), dim3(kDegThreads), 0, s, d_desc, d_bitmap, part, kp,
-                     d_counters, batch);
+  const int G = degree_closure_wgs(batch);
+  const ClosurePools cp = degree_closure_pools(d_scratch, batch);
+  uint64_t *comp = cp.comp, *part = cp.part;
+  int32_t* hp = cp.h;
+  uint32_t* kp = cp.keys;
+  // d_bitmap == nullptr: launches 1 and 2 have run already -- the order through launch_degree_closure_order, the
+  // partial rows from the points (kernels_graph.hip, tim_closure_pairs_kernel: the route whose K1 stores no row)
+  if (d_bitmap) {
+    launch_degree_closure_order(s, d_desc, batch, d_deg, d_state, d_scratch, d_counters);
+    hipLaunchKernelGGL(degree_closure_rows_kernel, dim3(G, batch), dim3(kDegThreads), 0, s, d_desc, d_bitmap, part, kp,
+                       d_counters, batch);
+  }
   hipLaunchKernelGGL(degree_closure_symmetrise_kernel, dim3(std::min(G, 8), batch), dim3(kDegThreads), 0, s, part, comp, hp, kp,
                      d_counters, batch);
   hipLaunchKernelGGL(degree_closure_verdict_kernel, dim3(batch), dim3(kDegThreads), 0, s, d_desc, d_state, d_clique, comp, hp,

@@ -320,11 +320,19 @@ struct teaser_hip_solver : HandleBase {
   // whose one reader is the degree closure.  Whoever else reads the arena runs the mirror kernel first
   // (launch_tim_graph_mfma, kTimMirror / kTimMirrorOpen).  The flag lives with the arena: every lane has its own.
   bool bm_lower_missing = false;
+  // ... or no row at all (the diagonal tiles' words only): K1 ran without stores (kTimNoStore), the closure worked from
+  // the points, and whoever else reads the arena runs a rebuild first (kTimRebuild / kTimRebuildOpen: K1's full store
+  // from d_pk plus a replay of the answers the fix-up recorded in d_work -- nothing of the caller's is read, so the
+  // getters need no rule about how long device-resident inputs stay valid).  Lives with the arena, like the flag above.
+  bool bm_rows_missing = false;
+  int64_t work_cap = 0;        // tim_work_items of the last matrix-core K1 (the rebuild's launcher argument)
+  int graph_route = 0;         // diagnostics: how the last solve's K1 stored the graph (0 full, 1 upper triangle, 2 nothing)
+  int64_t rebuilt = 0;         // diagnostics: problems rebuild launches have covered since that solve
 
   std::vector<uint64_t> bm_stage;  // teaser_hip_max_clique: the caller's dense rows on the arena's 64-byte stride
   SolverBuf d_desc, d_state, d_src, d_dst, d_bitmap, d_deg, d_clique, d_start_cliques, d_alive_a,
       d_alive_b, d_next_count, d_weights, d_rot_inl, d_trans_inl, d_tls_scratch, d_tim_off,
-      d_pk, d_prep, d_work, d_core, d_small;
+      d_pk, d_prep, d_work, d_core, d_small, d_deg_scratch;
   // colouring bound
   SolverBuf c_sel, c_colour, c_tent, c_xlist, c_list_a, c_list_b, c_counts, c_bits, c_class, c_mis;
   std::vector<int32_t> colour_x;  // |X| per problem of the last solve (-1: stage not run)
@@ -357,6 +365,7 @@ struct teaser_hip_solver : HandleBase {
   // the path of the next-but-one K1 in one batch out of two of the headline, profiles/r6a/timeline).
   bool skip_heuristic_next = false;
   int closure_open_prev = 0;   // problems the closure left open in this handle's previous batch
+  int closure_batch_prev = 0;  // ... out of this many (0: no batch of this handle has finished on a closure route yet)
   int heu_blocks = 0;          // workgroups per problem of the current batch's greedy launch (= ProbState.next_start)
   int heu_rows = 0;            // its grid rows: 0 = one per problem; behind the closure a few, shared by the open problems
 
@@ -1088,6 +1097,15 @@ int32_t enqueue_estimators(teaser_hip_solver* h) {
   return TEASER_HIP_OK;
 }
 
+// The rows of a batch whose K1 stored none (bm_rows_missing), for every problem (kTimRebuild) or for those the degree
+// closure left open (kTimRebuildOpen), from the handle's own arenas: the operands in d_pk, the band constants in d_prep
+// and the fix-up's recorded answers in d_work all live until the handle's next solve.
+void enqueue_graph_rebuild(teaser_hip_solver* h, int phase) {
+  launch_tim_graph_mfma(h->stream, phase, h->d_desc.as<ProbDesc>(), h->batch, h->max_n, h->total_w, nullptr, nullptr, h->d_pk.p,
+                        h->d_prep.p, h->d_work.p, h->work_cap, h->d_bitmap.as<uint64_t>(), h->d_state.as<ProbState>(),
+                        h->d_deg_scratch.as<int32_t>(), h->params.noise_bound, h->params.cbar2);
+}
+
 // K3 + selection (+ the peel in PMC_EXACT mode) of the current batch; every kernel skips the problems the degree
 // closure has decided.
 int32_t enqueue_heuristic_stage(teaser_hip_solver* h, int batch, int mode, bool record_stagger) {
@@ -1104,6 +1122,8 @@ int32_t enqueue_heuristic_stage(teaser_hip_solver* h, int batch, int mode, bool 
     if (h->bm_lower_missing)
       launch_tim_graph_mfma(s, kTimMirrorOpen, dd, batch, h->max_n, 0, nullptr, nullptr, nullptr, nullptr, nullptr, 0,
                             h->d_bitmap.as<uint64_t>(), ds, nullptr, 0.0, 0.0);
+    // K1 stored no row: the open problems' rows are rebuilt whole (the same place, the same rule for the flag)
+    if (h->bm_rows_missing) enqueue_graph_rebuild(h, kTimRebuildOpen);
     int32_t* heu_trace = nullptr;
     if (setting(S_K4_DEBUG) && batch <= 4) {  // diagnostics only: per-start phase clocks of the greedy kernel
       HIPCHK(h, h->s_e.ensure(sizeof(long long) * 8 * kMaxStarts * (size_t)batch));
@@ -1278,8 +1298,20 @@ int32_t solve_packed_enqueue(teaser_hip_solver* h, const double* d_src, const do
   // then does not store the lower one (every other route keeps the full store).
   const bool closure = need_graph && mode == TEASER_INLIER_PMC_EXACT && max_n <= 65536 && setting(S_DEG_CLOSURE) != 0 &&
                        !(setting(S_TAIL_SKIP) & 2);
-  const bool upper_k1 = mfma_k1 && closure;
-  if (need_graph) h->bm_lower_missing = upper_k1;
+  // ... and once this handle has seen the closure decide (nearly) everything -- its previous batch finished on a closure
+  // route with at most 1/32 of its problems left open -- K1 stores no row at all: the closure evaluates the pairs of its
+  // candidate set from the points, and a problem it leaves open pays a second K1 (the rebuild at the head of the
+  // heuristic stage).  Break-even: DESIGN.md, section 4.  A fresh handle's first solve, and any workload the closure
+  // does not decide, stay on the upper-triangle route.
+  const bool nostore_k1 = mfma_k1 && closure && h->closure_batch_prev > 0 && h->closure_open_prev * 32 <= h->closure_batch_prev;
+  const bool upper_k1 = mfma_k1 && closure && !nostore_k1;
+  if (need_graph) {
+    h->bm_lower_missing = upper_k1;
+    h->bm_rows_missing = nostore_k1;
+    h->graph_route = nostore_k1 ? 2 : upper_k1 ? 1 : 0;
+    h->rebuilt = 0;
+    if (nostore_k1) HIPCHK(h, h->d_deg_scratch.ensure(4 * (size_t)total_n));
+  }
   const bool k1_only = mfma_k1 && h->is_lane && h->k1_stream && h->k1_kernel_only;
   if (mfma_k1 && h->is_lane && h->k1_stream && !k1_only) {
     s1 = h->k1_stream;
@@ -1317,7 +1349,7 @@ int32_t solve_packed_enqueue(teaser_hip_solver* h, const double* d_src, const do
       launch_tim_graph(s, dd, batch, max_n, d_src, d_dst, h->d_bitmap.as<uint64_t>(), P.noise_bound,
                        P.cbar2, P.estimate_scaling ? 1 : 0, ds);
     } else {
-      const int64_t cap = tim_work_items(n, batch);
+      const int64_t cap = h->work_cap = tim_work_items(n, batch);
       const int64_t tail_skip = setting(S_TAIL_SKIP);  // (timing probes only)
       for (int phase = 0; phase < 3; ++phase) {
         if ((phase == 2 && (tail_skip & 1)) || (phase == 0 && (tail_skip & 16))) continue;
@@ -1337,7 +1369,8 @@ int32_t solve_packed_enqueue(teaser_hip_solver* h, const double* d_src, const do
         }
         {
           StageScope sc(h, phase == 1 ? ST_TIM : ST_TIMAUX, sp);
-          launch_tim_graph_mfma(sp, (upper_k1 && phase > 0) ? (phase | kTimUpperOnly) : phase, dd, batch, max_n, wo, d_src, d_dst, h->d_pk.p, h->d_prep.p,
+          const int store_flag = phase == 0 ? 0 : nostore_k1 ? kTimNoStore : upper_k1 ? kTimUpperOnly : 0;
+          launch_tim_graph_mfma(sp, phase | store_flag, dd, batch, max_n, wo, d_src, d_dst, h->d_pk.p, h->d_prep.p,
                                 h->d_work.p, cap, h->d_bitmap.as<uint64_t>(), ds, h->d_deg.as<int32_t>(),
                                 P.noise_bound, P.cbar2);
         }
@@ -1371,7 +1404,13 @@ int32_t solve_packed_enqueue(teaser_hip_solver* h, const double* d_src, const do
     if (closure) {
       StageScope sc(h, ST_HEU);
       HIPCHK(h, h->d_core.ensure((size_t)degree_closure_scratch_bytes(batch)));
-      launch_degree_closure(s, dd, batch, h->d_bitmap.as<uint64_t>(), h->d_deg.as<int32_t>(), ds,
+      // (no rows to gather from: the order launch and the pairs of the candidate set from the points, then the
+      // symmetrise and verdict launches as they are)
+      if (nostore_k1)
+        launch_tim_graph_mfma(s, kTimClosurePairs, dd, batch, max_n, wo, d_src, d_dst, h->d_core.p,
+                              h->d_next_count.as<int32_t>() + 2 * (size_t)batch, nullptr, 0, nullptr, ds, h->d_deg.as<int32_t>(),
+                              P.noise_bound, P.cbar2);
+      launch_degree_closure(s, dd, batch, nostore_k1 ? nullptr : h->d_bitmap.as<uint64_t>(), h->d_deg.as<int32_t>(), ds,
                             h->d_clique.as<int32_t>(), h->d_core.p, h->d_next_count.as<int32_t>() + 2 * (size_t)batch);
     }
     h->pend.closure = closure;
@@ -1443,6 +1482,8 @@ int32_t solve_packed_finish(teaser_hip_solver* h, teaser_solution_c* out, bool* 
     }
     h->skip_heuristic_next = open == 0;
     h->closure_open_prev = open;
+    h->closure_batch_prev = batch;
+    if (h->bm_rows_missing) h->rebuilt += open;  // (the heuristic stage's rebuild, behind the closure or just now)
   }
   for (int b = 0; b < batch; ++b) h->heu_size[(size_t)b] = h->states[(size_t)b].lb;
   if (setting(S_K4_DEBUG) && batch <= 4)  // diagnostics only: what the greedy starts found
@@ -2255,6 +2296,17 @@ int32_t teaser_hip_get_input_ordered_translation_inliers(teaser_hip_solver* h, i
   return TEASER_HIP_OK;
 }
 
+// The last solve's K1 stored no row: all of them are rebuilt, once, before a getter's first copy.
+static int32_t ensure_graph_rows(teaser_hip_solver* h) {
+  if (!h->bm_rows_missing) return TEASER_HIP_OK;
+  enqueue_graph_rebuild(h, kTimRebuild);
+  HIPCHK(h, hipGetLastError());
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  h->bm_rows_missing = false;
+  h->rebuilt += h->batch;
+  return TEASER_HIP_OK;
+}
+
 int32_t teaser_hip_get_inlier_graph_bitmap(teaser_hip_solver* h, int32_t problem, uint64_t* buf,
                                            int64_t* len) {
   CHECK_PROBLEM(h, problem);
@@ -2263,6 +2315,10 @@ int32_t teaser_hip_get_inlier_graph_bitmap(teaser_hip_solver* h, int32_t problem
     return len ? TEASER_HIP_OK : TEASER_HIP_ERR_BAD_ARG;
   }
   const ProbDesc& d = h->descs[(size_t)problem];
+  if (buf) {
+    const int32_t rc = ensure_graph_rows(h);
+    if (rc != TEASER_HIP_OK) return rc;
+  }
   if (buf && h->bm_lower_missing) {
     // the solve's K1 stored the upper triangle only: rebuild the lower one for every problem of the batch, once
     launch_tim_graph_mfma(h->stream, kTimMirror, h->d_desc.as<ProbDesc>(), h->batch, h->max_n, 0, nullptr, nullptr, nullptr,
@@ -2303,7 +2359,21 @@ int32_t teaser_hip_get_inlier_graph_rows(teaser_hip_solver* h, int32_t problem, 
     if (len) *len = 0;
     return len ? TEASER_HIP_OK : TEASER_HIP_ERR_BAD_ARG;
   }
+  if (buf) {  // (a K1 that stored no row: rebuilt first, both halves and the padding)
+    const int32_t rc = ensure_graph_rows(h);
+    if (rc != TEASER_HIP_OK) return rc;
+  }
   return copy_out(h, h->d_bitmap.as<uint64_t>() + d.bm_off, (int64_t)d.n * bm_stride(d.W), buf, len);
+}
+
+// DIAGNOSTIC, for tests (declared in teaser_hip.h beside teaser_hip_get_inlier_graph_rows): how the K1 of the last
+// solve of the handle that holds `problem` stored the graph -- 0 both halves, 1 the upper triangle, 2 nothing (the
+// rows are rebuilt on demand) -- and how many problems rebuild launches have covered since.
+int32_t teaser_hip_get_graph_route(teaser_hip_solver* h, int32_t problem, int32_t* route, int64_t* rebuilt) {
+  CHECK_PROBLEM(h, problem);
+  if (route) *route = h->have_graph ? h->graph_route : 0;
+  if (rebuilt) *rebuilt = h->have_graph ? h->rebuilt : 0;
+  return TEASER_HIP_OK;
 }
 
 int32_t teaser_hip_get_degrees(teaser_hip_solver* h, int32_t problem, int32_t* buf, int64_t* len) {
@@ -2499,7 +2569,8 @@ int32_t teaser_hip_max_clique(teaser_hip_solver* h, const uint64_t* bitmap, int3
   if (rc != TEASER_HIP_OK) return rc;
   h->batch = 0;  // getters of a previous solve are invalidated
   h->pend.spec_bounds = false;  // (a previous solve's speculative bound results are not this graph's)
-  h->bm_lower_missing = false;  // (the arena takes the caller's bitmap, both halves)
+  h->bm_lower_missing = h->bm_rows_missing = false;  // (the arena takes the caller's bitmap, both halves)
+  h->graph_route = 0;
   ProbState& st = h->states[0];
   HIPCHK(h, h->d_desc.ensure(sizeof(ProbDesc)));
   HIPCHK(h, h->d_state.ensure(sizeof(ProbState)));
