@@ -691,9 +691,45 @@ __global__ void tim_prep_consts3_kernel(TimPrep* __restrict__ prep, int batch, d
 
 // worklist item: 16 rows of one column and their provisional bits (fixup_item.h; tim_fixup_group_kernel)
 
+// The open-only rebuild's search for its problem (tim_graph_mfma3_kernel with NS = kK1Rebuild): the ord-th problem of
+// the batch that the closure left open and that ran the matrix-core body, or -1.  Every wave of the workgroup scans
+// the states itself, one ballot per 64 problems: no list, no buffer, no launch in front.
+__device__ __forceinline__ int k1_rebuild_find_open(const ProbState* __restrict__ states, const TimPrep* __restrict__ prep,
+                                                    const int batch, int ord) {
+  const int ln = (int)(threadIdx.x & 63);
+  for (int base = 0; base < batch; base += 64) {
+    const int b = base + ln;
+    const bool open = b < batch && !states[b].deg_closed && prep[b].use_mfma;
+    uint64_t m = __builtin_amdgcn_ballot_w64(open);
+    const int cnt = __builtin_popcountll(m);
+    if (ord < cnt) {
+      for (int k = 0; k < ord; ++k) m &= m - 1ull;  // (wave-uniform)
+      return base + (int)__builtin_ctzll(m);
+    }
+    ord -= cnt;
+  }
+  return -1;
+}
+// the rebuild's next pass: the workgroup's next logical block of its problem, then (open-only) its next problem
+__device__ __forceinline__ bool k1_rebuild_next(int& lb, const int nlb, int& ord, unsigned int& pb, const int rb_open,
+                                                const ProbState* __restrict__ states, const TimPrep* __restrict__ prep,
+                                                const ProbDesc* __restrict__ descs, ProbDesc& d, int& n, int& W, int& T, int& S) {
+  if ((lb += (int)gridDim.x) < nlb) return true;
+  if (!rb_open) return false;
+  ord += (int)gridDim.y;
+  const int found = k1_rebuild_find_open(states, prep, rb_open, ord);
+  if (found < 0) return false;
+  pb = (unsigned int)found;
+  lb = (int)blockIdx.x;
+  d = descs[pb];
+  n = d.n, W = d.W, T = W, S = bm_stride(W);
+  return true;
+}
+
 // The product's instantiation (launch_tim_graph_mfma); the lab build (scripts/probe/k1_lab) times the others.
 constexpr bool kK1Pipe = false, kK1Plain = true;
 constexpr int kK1Chunks = 1, kK1Occ = 3;
+constexpr int kRebuildOpenSlots = 2;  // the open-only rebuild's grid: open problems served side by side
 
 // PIPE: software-pipelined schedule.  The wave works on QUARTER tiles (32 x 32) with two accumulator sets: while the
 // matrix pipe runs the two MFMAs of quarter k + 1, the vector ALU runs the epilogue of quarter k -- interleaved
@@ -723,11 +759,14 @@ constexpr int kK1Chunks = 1, kK1Occ = 3;
 // the full store, nothing written to the regions, the segment counters or the states, the degrees added into a
 // scratch array nobody reads; problems on the FP64 body (their rows are in place) and, with rb_open, problems the
 // closure has decided are skipped, and a block walks the logical blocks lb, lb + gridDim.x, .. of the nlb_arg a
-// problem has: the open-only launch is then 64 workgroups per problem, not K1's grid.  Measured (profiles/r12a): on
-// K1's own grid the workgroups of an all-closed batch leave at once and cost 14 us alone, but each still needs a K1-sized
-// slot (144 VGPRs x 4 waves, 34 KB of LDS), and in the two-lane pipeline those slots are held by the OTHER lane's K1 --
-// the launch then ends with that K1 and the lane's tail behind it: the bench fell 1.4 % BELOW the parent, against
-// + 7.9 % with the small grid.  tim_fixup_replay_kernel puts the fix-up's recorded answers on top.
+// problem has.  The open-only launch has the grid of ONE problem x kRebuildOpenSlots slots, whatever the batch's size:
+// a workgroup finds the open problems itself (k1_rebuild_find_open) and serves every kRebuildOpenSlots-th of them.
+// Measured (profiles/r12a, r13a): on K1's own grid x batch the workgroups of an all-closed batch leave at once and
+// cost 14 us alone, but each still needs a K1-sized slot (144 VGPRs x 4 waves, 34 KB of LDS), and in the two-lane
+// pipeline those slots are held by the OTHER lane's K1 -- the launch then ends with that K1 and the lane's tail behind
+// it: the bench fell 1.4 % BELOW the parent.  64 workgroups x batch (the form up to r12a) walked one open problem's 420
+// blocks in 7 passes, up to 245 us; 128 and 210 x batch lost 1.7 % and 6 % against it; one problem x 2 slots gained
+// 3.0 %.  tim_fixup_replay_kernel puts the fix-up's recorded answers on top.
 constexpr int kK1NoStore = 1, kK1Rebuild = 2;
 template <bool PIPE, bool PLAIN, int OCC, int CHUNKS, bool LOWER, bool UW3 = false, int NS = 0>
 __global__ __launch_bounds__(256, OCC) void tim_graph_mfma3_kernel(
@@ -738,12 +777,23 @@ __global__ __launch_bounds__(256, OCC) void tim_graph_mfma3_kernel(
     ProbState* __restrict__ states, int32_t* __restrict__ deg, unsigned long long* __restrict__ regions, int Tmax,
     int rb_open, int nlb_arg) {
   static_assert(NS == 0 || (NS == kK1NoStore && !LOWER) || (NS == kK1Rebuild && LOWER), "store modes");
+  // The problem: blockIdx.y, except in the open-only rebuild (rb_open = the batch's size), whose grid is the size of
+  // ONE problem times gridDim.y slots: workgroup (x, y) serves the y-th, (y + gridDim.y)-th, .. open problem of the
+  // batch and finds it by scanning the batch's states itself (k1_rebuild_find_open); without one it leaves at once.
+  unsigned int pb = blockIdx.y;
+  int ord = (int)blockIdx.y;
   if constexpr (NS == kK1Rebuild) {  // (uniform over the block)
-    if ((rb_open && states[blockIdx.y].deg_closed) || !prep[blockIdx.y].use_mfma) return;
+    if (rb_open) {
+      const int found = k1_rebuild_find_open(states, prep, rb_open, ord);
+      if (found < 0) return;
+      pb = (unsigned int)found;
+    } else if (!prep[pb].use_mfma) {
+      return;
+    }
   }
-  const ProbDesc d = descs[blockIdx.y];
-  const int n = d.n, W = d.W;
-  const int T = W, S = bm_stride(W);  // tiles = words of a bitmap row; words between two rows
+  ProbDesc d = descs[pb];
+  int n = d.n, W = d.W;
+  int T = W, S = bm_stride(W);  // tiles = words of a bitmap row; words between two rows
   // One pass per logical block.  Every instantiation but the rebuild's makes exactly one (lb = blockIdx.x; the loop's
   // condition is constant false and `continue` is its early exit), so the body below is not indented for it.
   int lb = (int)blockIdx.x;
@@ -770,7 +820,7 @@ __global__ __launch_bounds__(256, OCC) void tim_graph_mfma3_kernel(
   auto region_of = [&](int wv, int chunk) -> unsigned long long* {
     if constexpr (NS == kK1Rebuild) return nullptr;  // (the arena keeps the items the fix-up has recorded its answers in)
     const int Iw = I0 + wv, Xc = X * CHUNKS + chunk;
-    return fxr::is_cell(Iw, Xc, Tmax) ? regions + fxr::region_offset((int)blockIdx.y, Tmax, Iw, Xc) : nullptr;
+    return fxr::is_cell(Iw, Xc, Tmax) ? regions + fxr::region_offset((int)pb, Tmax, Iw, Xc) : nullptr;
   };
   auto zero_regions = [&]() {
     if ((threadIdx.x & 63) < CHUNKS) {
@@ -832,7 +882,7 @@ __global__ __launch_bounds__(256, OCC) void tim_graph_mfma3_kernel(
     if (PIPE)
       for (int m = 0; m < kTimColOperands; ++m) bY[m] = load_op(Jf, 1, 1, m);
   }
-  const TimPrep pr = prep[blockIdx.y];  // (uniform address: scalar loads)
+  const TimPrep pr = prep[pb];  // (uniform address: scalar loads)
   if (!pr.use_mfma) {  // per problem: uniform over the block
     EdgeConst kc;
     kc.beta = beta;
@@ -1177,7 +1227,7 @@ __global__ __launch_bounds__(256, OCC) void tim_graph_mfma3_kernel(
           total += __builtin_popcountll(m) << bit;
         }
         if (total > kWorkBuf) {  // adversarial geometry: the host reruns the batch on the FP64 kernel
-          if (lane == 0) states[blockIdx.y].k1_overflow = 1;
+          if (lane == 0) states[pb].k1_overflow = 1;
         } else {
           int kk = base;
 #pragma nounroll
@@ -1207,10 +1257,10 @@ __global__ __launch_bounds__(256, OCC) void tim_graph_mfma3_kernel(
       if (wcount > nreg) {
         const int extra = wcount - nreg;
         unsigned int base = 0;
-        if (lane == 0) base = atomicAdd(work_count + blockIdx.y, (unsigned int)extra);
+        if (lane == 0) base = atomicAdd(work_count + pb, (unsigned int)extra);
         base = __builtin_amdgcn_readfirstlane(base);
         if (base + (unsigned int)extra > pr.seg_cap) {
-          if (lane == 0) states[blockIdx.y].k1_overflow = 1;
+          if (lane == 0) states[pb].k1_overflow = 1;
         } else {
           unsigned long long* seg = work + (((size_t)pr.seg_off_hi << 32) | (size_t)pr.seg_off_lo);
 #pragma nounroll
@@ -1221,7 +1271,8 @@ __global__ __launch_bounds__(256, OCC) void tim_graph_mfma3_kernel(
   }
   if (rowvalid)
     __builtin_amdgcn_raw_ptr_buffer_atomic_add_i32(degacc, deg_rsrc, (unsigned int)(I * 64 + lane) * 4u, 0, 0);
-  } while (NS == kK1Rebuild && (__syncthreads(), (lb += (int)gridDim.x) < nlb));  // (the next pass rewrites the LDS arrays)
+  } while (NS == kK1Rebuild &&  // (`continue` lands here too; the next pass rewrites the LDS arrays)
+           (__syncthreads(), k1_rebuild_next(lb, nlb, ord, pb, rb_open, states, prep, descs, d, n, W, T, S)));
 }
 
 // FP64 resolution of the filter's GROUP items: 16 lanes per item, lane q owns the pair
@@ -1815,10 +1866,14 @@ void launch_tim_graph_mfma(hipStream_t s, int phase, const ProbDesc* d_desc, int
     // (a block walks its share of a problem's logical blocks), the launch for the getters has K1's own grid.
     const int gyr = (T + kMfmaRowTiles - 1) / kMfmaRowTiles, nlb = tim_mfma_blocks(T, kK1Chunks);
     const int open_only = phase == kTimRebuildOpen ? 1 : 0;
+    // open-only: one problem's logical blocks x kRebuildOpenSlots slots, whatever the batch's size (the kernel finds
+    // the open problems itself); the batch's size travels in rb_open
+    const dim3 rb_grid = open_only ? dim3(nlb, kRebuildOpenSlots) : dim3(nlb, batch);
     // (two workgroups per CU: the pass loop keeps ~24 more registers live than one pass, and at three the kernel spills)
     hipLaunchKernelGGL((tim_graph_mfma3_kernel<kK1Pipe, kK1Plain, 2, kK1Chunks, true, false, kK1Rebuild>),
-                       dim3(open_only ? std::min(64, nlb) : nlb, batch), dim3(256), 0, s, d_desc, d_src, d_dst,
-                       (const void*)d_pk, prep, d_bitmap, beta, gyr, work, work_count, d_state, d_deg, regions, T, open_only, nlb);
+                       rb_grid, dim3(256), 0, s, d_desc, d_src, d_dst,
+                       (const void*)d_pk, prep, d_bitmap, beta, gyr, work, work_count, d_state, d_deg, regions, T,
+                       open_only ? batch : 0, nlb);
     hipLaunchKernelGGL(tim_fixup_replay_kernel, dim3((unsigned)std::max(4, ((T + 3) / 4 + 1) / 2), batch), dim3(256), 0, s,
                        d_desc, d_bitmap, work, work_count, d_state, regions, T, prep, open_only);
 #endif
