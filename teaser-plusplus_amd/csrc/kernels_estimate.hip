@@ -791,7 +791,10 @@ void launch_tls_translation(hipStream_t s, const ProbDesc* d_desc, int batch, co
 //     come from prefix sums, and each lane finds the merged position of its endpoints by two binary searches.
 //     First minimum in endpoint order, NaN never wins -- as :77-78.  Endpoint ties (an opening and a closing of
 //     exactly equal value) are unpinned in the reference (std::sort); here the opening goes first.  Window sums
-//     associate differently from the sequential sweep (~1e-16 relative).
+//     associate differently from the sequential sweep (~1e-16 relative) -- except for a window of ONE value, which is
+//     evaluated exactly (x_hat = the value, residual 0, cost beta (K - 1)): where consensus sets do not overlap the
+//     sweep's running sums return to exactly 0 and all singletons tie, so the first (smallest) value wins there; a
+//     prefix difference (a + b) - a would let an arbitrary one win by 1e-17.
 //   GENERAL route (FGR / QUATRO / COMPLETE TIMs / larger cliques): the block functions of the separate kernels,
 //   the three axes one after the other.
 // ------------------------------------------------------------------------------------------
@@ -1108,8 +1111,12 @@ __global__ __launch_bounds__(256) void estimate_fused_kernel(
       auto consider = [&](int lo, int hi, int pos) {
         const double card = (double)(hi - lo);
         const double s1 = p1[hi] - p1[lo], s2 = p2[hi] - p2[lo];
-        const double x_hat = s1 / card;  // (weights 1 / beta^2 cancel)
-        const double residual = card * x_hat * x_hat + s2 - 2 * s1 * x_hat;
+        double x_hat = s1 / card;  // (weights 1 / beta^2 cancel)
+        double residual = card * x_hat * x_hat + s2 - 2 * s1 * x_hat;
+        if (hi - lo == 1) {  // one value: (a + b) - a is not b -- the sweep's sums are exact here, residual 0
+          x_hat = sx[lo];
+          residual = 0;
+        }
         const double c = residual + beta * (double)(K - (hi - lo));
         if (c < bcost || (c == bcost && pos < bpos)) {  // first minimum; NaN (empty window) never wins
           bcost = c;

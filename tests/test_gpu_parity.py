@@ -1721,7 +1721,9 @@ def test_fused_estimators_match_the_separate_kernels():
     separate launches (option fused_estimators = 0): the GNC-TLS arithmetic is ordered identically, so R, the GNC cost, the
     iteration count and the rotation inliers are bit-identical; the translation comes from the window form of the scalar
     TLS (sorted values + prefix sums instead of the endpoint sweep): same estimate to ~1e-15, same inlier list.  Cliques of
-    2 .. 512 vertices take the fast route, larger ones (and FGR / QUATRO / COMPLETE) the general route inside the kernel."""
+    2 .. 512 vertices take the fast route, larger ones (and FGR / QUATRO / COMPLETE) the general route inside the kernel.
+    The cliques here have roughly 5, 64, 150, 250, 360, 513 and 576 vertices; the size edges of both routes (2, 3, 255 ..
+    258, 511, 512, 513, 1024, 1025) are in tests/test_gpu_estimator_edges.py, against the oracle too."""
     cases = [(300, 0.5, 31), (1200, 0.7, 32), (2500, 0.9, 33), (640, 0.1, 34), (9, 0.4, 35), (64, 0.0, 36), (513, 0.0, 37)]
     probs = [tp.synth_problem(9000 + seed, n, rho, 0.01) for n, rho, seed in cases]
     try:
