@@ -178,7 +178,7 @@ int64_t tim_prep_fill_segments(void* host_prep, const int32_t* n, int batch);
 // other reader.
 constexpr int kTimUpperOnly = 8, kTimMirror = 3, kTimMirrorOpen = 4;
 // kTimNoStore on top of phases 1 and 2: K1 stores no row at all (the diagonal tiles' words only) and the fix-up follows
-// with the degrees alone, recording its answers in the worklist items.  The closure then gets its partial rows from
+// with the degrees alone, recording its answers in the worklist items.  The closure then gets its full rows from
 // kTimClosurePairs (the order launch + one evaluation of every pair of the candidate set from the points; d_pk: the
 // closure's scratch, d_prep: its counters -- launch_degree_closure with d_bitmap == nullptr finishes), and whoever else
 // reads the arena runs kTimRebuild (every problem) / kTimRebuildOpen (those the closure left open) first: K1's full
@@ -211,15 +211,17 @@ int launch_greedy_small(hipStream_t s, const ProbDesc* d_desc, int batch, int ma
 // degrees and the rows of the ~10^3 vertices of largest degree are closed (clique written, state proven,
 // deg_closed = 1); the others are left untouched.  d_scratch: degree_closure_scratch_bytes(batch);
 // d_counters: 2 * batch ints, zero on entry
-// d_bitmap == nullptr: the symmetrise and verdict launches only -- the order and the partial rows are there already
-// (launch_tim_graph_mfma, kTimClosurePairs).
+// d_bitmap == nullptr: the verdict launch alone -- the order and the FULL rows are there already (launch_tim_graph_mfma,
+// kTimClosurePairs) and the verdict computes H from them (closure_h.h): order, pairs, verdict.
 int64_t degree_closure_scratch_bytes(int batch);
 void launch_degree_closure(hipStream_t s, const ProbDesc* d_desc, int batch, const uint64_t* d_bitmap,
                            const int32_t* d_deg, ProbState* d_state, int32_t* d_clique, void* d_scratch,
                            int32_t* d_counters);
 // The closure's scratch as its launches and kernels_graph.hip's pair kernel see it: the candidate set R holds at most
 // kCoreCap vertices; per problem kCoreCap compact rows of kCoreWords words, full and partial, the H values and the
-// keys (degree << 16 | vertex, by rank).  launch_degree_closure_order: launch 1 alone (|R| into d_counters[problem]).
+// keys (degree << 16 | vertex, by rank).  launch_degree_closure_order: launch 1 alone (|R| into d_counters[problem]);
+// with d_src / d_dst it also stages the points of R in rank order (six doubles per rank: src xyz, dst xyz) for the pair
+// kernel, in pts -- the room of the partial rows, which that route does not write; null: no staging.
 constexpr int kCoreCap = 2048;
 constexpr int kCoreWords = kCoreCap / 64;
 struct ClosurePools {
@@ -227,11 +229,13 @@ struct ClosurePools {
   uint64_t* part;
   int32_t* h;
   uint32_t* keys;
+  double* pts;  // [batch][kCoreCap][6], aliases part
 };
+static_assert(6 <= kCoreWords, "the staged points fit in the partial rows' room");
 ClosurePools degree_closure_pools(void* d_scratch, int batch);
 int degree_closure_wgs(int batch);  // workgroups per problem of launch 2
 void launch_degree_closure_order(hipStream_t s, const ProbDesc* d_desc, int batch, const int32_t* d_deg, ProbState* d_state,
-                                 void* d_scratch, int32_t* d_counters);
+                                 void* d_scratch, int32_t* d_counters, const double* d_src, const double* d_dst);
 // k-core style peel at threshold lb
 void launch_peel(hipStream_t s, const ProbDesc* d_desc, int batch, int max_n, int max_W,
                  const uint64_t* d_bitmap, const int32_t* d_deg, ProbState* d_state,

@@ -1538,30 +1538,27 @@ __global__ __launch_bounds__(256) void tim_fixup_replay_kernel(const ProbDesc* _
   for (unsigned int w = (blockIdx.x * 256 + threadIdx.x) >> 4; w < total; w += ngrp) replay(seg[w], true);
 }
 
-// Launch 2 of the degree closure where K1 has stored no row (kTimNoStore): the partial compact rows of the candidate
-// set R straight from the points.  Keys: degree << 16 | vertex by rank, as the order launch leaves them; for every
-// rank pair a < b the predicate is evaluated ONCE, with the two-step expression of the fix-up's resolve() (the FP64
-// fast path with its guard band, the reference expression inside it: the bit a stored row would hold), and lands in
-// word (a, b / 64) of the partial pool; the diagonal bit and everything at or below it are zero.  The symmetrise
-// launch ORs every partial row with the transpose of the pool, so covering every unordered pair once is enough, and
-// this rule leaves the blocks below the diagonal without work.  A wave takes a 64 x 64 block (A, B >= A) of rank
-// pairs: the 64 row points staged in its LDS slice (a broadcast read per row), lane l's column point (rank 64 B + l)
-// in registers, one ballot per row.  The points of R are gathered through the keys -- 2 x 64 points per block, from
-// the L2 that holds the problem's 48 n bytes; |R| ~ 900 at N = 10 k is ~120 blocks, ~0.5 M pairs per problem.
-__global__ __launch_bounds__(256) void tim_closure_pairs_kernel(const ProbDesc* __restrict__ descs,
-                                                                const double* __restrict__ src,
-                                                                const double* __restrict__ dst,
-                                                                uint64_t* __restrict__ part_pool /* [batch][kCoreCap][kCoreWords] */,
-                                                                const uint32_t* __restrict__ key_pool /* [batch][kCoreCap] */,
+// Launch 2 of the degree closure where K1 has stored no row (kTimNoStore): the FULL compact rows of the candidate set
+// R straight from the points.  For every rank pair a < b the predicate is evaluated ONCE, with the two-step expression
+// of the fix-up's resolve() (the FP64 fast path with its guard band, the reference expression inside it: the bit a
+// stored row would hold).  A wave takes a 64 x 64 block (A, B >= A) of rank pairs -- the blocks below the diagonal are
+// without work -- with the 64 row points staged in its LDS slice (a broadcast read per row) and lane l's column point
+// (rank 64 B + l) in registers, and leaves BOTH words of the block: one ballot per row is the row-side word
+// (64 A + r, B), and the 64 predicate values lane l sees over the row loop are, bit for bit, the mirrored word
+// (64 B + l, A) -- one OR per row.  Off the diagonal lane l stores its row word to comp[64 A + l][B] and its column word
+// to comp[64 B + l][A]; the diagonal block stores the OR of the two to comp[64 A + l][A] (zero diagonal).  So every word
+// (row < m, block < ng) of the pool is written exactly once per launch, whatever the grid: the verdict launch reads
+// full rows and there is neither a zero fill nor a symmetrise launch behind this one.  The points come from the pool
+// the order launch staged in rank order (six doubles per rank): contiguous loads, no key is read.  |R| ~ 900 at
+// N = 10 k is ~120 blocks, ~0.5 M pairs per problem.
+__global__ __launch_bounds__(256) void tim_closure_pairs_kernel(uint64_t* __restrict__ comp_pool /* [batch][kCoreCap][kCoreWords] */,
+                                                                const double* __restrict__ pts_pool /* [batch][kCoreCap][6] */,
                                                                 const int32_t* __restrict__ counters, double beta) {
   TAIL_WAVE_PRIO();
   const int m = counters[blockIdx.y];
   if (m < 2) return;
-  const ProbDesc d = descs[blockIdx.y];
-  const double* ps = src + 3 * d.pt_off;
-  const double* pd = dst + 3 * d.pt_off;
-  const uint32_t* keys = key_pool + (size_t)blockIdx.y * kCoreCap;
-  uint64_t* part = part_pool + (size_t)blockIdx.y * kCoreCap * kCoreWords;
+  const double* pts = pts_pool + (size_t)blockIdx.y * kCoreCap * 6;
+  uint64_t* comp = comp_pool + (size_t)blockIdx.y * kCoreCap * kCoreWords;
   EdgeConst kc;
   kc.beta = beta;
   kc.beta2 = beta * beta;
@@ -1578,17 +1575,17 @@ __global__ __launch_bounds__(256) void tim_closure_pairs_kernel(const ProbDesc* 
       ++A;
     }
     const int B = A + rem, ra = 64 * A + lane, rb = 64 * B + lane;
-    {
-      const int v = (int)(keys[min(ra, m - 1)] & 0xffffu);
+    {  // (ranks beyond m: the last rank's point, masked below -- the pool holds nothing there)
+      const double* pa = pts + 6 * min(ra, m - 1);
       double* rp = row_pts[wave][lane];
-      rp[0] = ps[3 * v]; rp[1] = ps[3 * v + 1]; rp[2] = ps[3 * v + 2];
-      rp[3] = pd[3 * v]; rp[4] = pd[3 * v + 1]; rp[5] = pd[3 * v + 2];
+      rp[0] = pa[0]; rp[1] = pa[1]; rp[2] = pa[2];
+      rp[3] = pa[3]; rp[4] = pa[4]; rp[5] = pa[5];
     }
-    const int vb = (int)(keys[min(rb, m - 1)] & 0xffffu);
-    const double cx = ps[3 * vb], cy = ps[3 * vb + 1], cz = ps[3 * vb + 2];
-    const double ex = pd[3 * vb], ey = pd[3 * vb + 1], ez = pd[3 * vb + 2];
+    const double* pb = pts + 6 * min(rb, m - 1);
+    const double cx = pb[0], cy = pb[1], cz = pb[2];
+    const double ex = pb[3], ey = pb[4], ez = pb[5];
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");  // wave-private slice: same-wave ordering suffices
-    uint64_t word = 0ull;
+    uint64_t word = 0ull, colw = 0ull;
     const int rows = min(64, m - 64 * A);
     for (int r = 0; r < rows; ++r) {
       const double* rp = row_pts[wave][r];
@@ -1597,13 +1594,17 @@ __global__ __launch_bounds__(256) void tim_closure_pairs_kernel(const ProbDesc* 
       bool e = tim_edge_fast(ax, ay, az, bx, by, bz, kc, &unc, &shortp);
       e |= shortp;
       if (unc) e = tim_edge_exact(ax, ay, az, bx, by, bz, beta);
-      const uint64_t mk = __builtin_amdgcn_ballot_w64(e && rb < m && 64 * A + r < rb);
+      const bool valid = rb < m && 64 * A + r < rb;
+      const uint64_t mk = __builtin_amdgcn_ballot_w64(e && valid);
       word = lane == r ? mk : word;
+      colw |= (uint64_t)(e && valid) << r;
     }
-    if (ra < m) {
-      part[(size_t)ra * kCoreWords + B] = word;
-      if (A == B)  // (the row's words in front of its diagonal block: no pair of theirs is evaluated from this side)
-        for (int Bz = 0; Bz < A; ++Bz) part[(size_t)ra * kCoreWords + Bz] = 0ull;
+    // (ranks >= m: no row is stored for them, and the mask leaves their bits zero in every word that is)
+    if (A == B) {
+      if (ra < m) comp[(size_t)ra * kCoreWords + A] = word | colw;
+    } else {
+      if (ra < m) comp[(size_t)ra * kCoreWords + B] = word;
+      if (rb < m) comp[(size_t)rb * kCoreWords + A] = colw;
     }
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");  // (the next block overwrites the slice)
   }
@@ -1783,10 +1784,10 @@ void launch_tim_graph_mfma(hipStream_t s, int phase, const ProbDesc* d_desc, int
   const double beta = 2 * noise_bound * sqrt(cbar2);  // registration.cc:438
   if (phase == kTimClosurePairs) {  // d_pk: the closure's scratch, d_prep: its counters (2 * batch ints, zero on entry)
     int32_t* counters = reinterpret_cast<int32_t*>(d_prep);
-    launch_degree_closure_order(s, d_desc, batch, d_deg, d_state, d_pk, counters);
+    launch_degree_closure_order(s, d_desc, batch, d_deg, d_state, d_pk, counters, d_src, d_dst);
     const ClosurePools cp = degree_closure_pools(d_pk, batch);
-    hipLaunchKernelGGL(tim_closure_pairs_kernel, dim3(degree_closure_wgs(batch), batch), dim3(256), 0, s, d_desc, d_src, d_dst,
-                       cp.part, cp.keys, counters, beta);
+    hipLaunchKernelGGL(tim_closure_pairs_kernel, dim3(degree_closure_wgs(batch), batch), dim3(256), 0, s, cp.comp, cp.pts,
+                       counters, beta);
     return;
   }
 #ifdef TEASER_K1_LAB

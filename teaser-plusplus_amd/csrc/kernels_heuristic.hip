@@ -10,6 +10,7 @@
 #include <cstdlib>
 
 #include "internal.h"
+#include "closure_h.h"
 #include "wave_utils.h"
 
 namespace thip {
@@ -731,7 +732,9 @@ __device__ __forceinline__ void suffix_counts(const int* hist, int* above, int t
 __global__ __launch_bounds__(kDegThreads) void degree_closure_order_kernel(
     const ProbDesc* __restrict__ descs, const int32_t* __restrict__ deg, ProbState* __restrict__ states,
     uint32_t* __restrict__ key_pool /* [batch][kCoreCap] */,
-    int32_t* __restrict__ counters /* [batch] |R|, [batch] t; zero on entry (|R| = 0: the closure declined) */, int batch) {
+    int32_t* __restrict__ counters /* [batch] |R|, [batch] t; zero on entry (|R| = 0: the closure declined) */, int batch,
+    const double* __restrict__ src, const double* __restrict__ dst /* null: nothing is staged */,
+    double* __restrict__ pts_pool /* [batch][kCoreCap][6]: src xyz, dst xyz by rank */) {
   TAIL_WAVE_PRIO();
   __shared__ uint64_t Pa[kDegMaxW];          // { deg >= t } over the vertices
   __shared__ int hist[kDegBins + 1];         // degree histogram -> slot cursors
@@ -872,6 +875,30 @@ __global__ __launch_bounds__(kDegThreads) void degree_closure_order_kernel(
     if (tid == 0) {
       counters[blockIdx.y] = m;
       counters[batch + blockIdx.y] = t;
+    }
+    // the route whose K1 stores no row: the pair kernel reads R's points in rank order, as contiguous loads
+    if (src) {
+      const double* ps = src + 3 * d.pt_off;
+      const double* pd = dst + 3 * d.pt_off;
+      double* pout = pts_pool + (size_t)blockIdx.y * kCoreCap * 6;
+      constexpr int kRanks = 4;  // ranks per thread and pass: their 24 loads are independent
+      for (int r0 = tid; r0 < m; r0 += kRanks * kDegThreads) {
+        double p[kRanks][6];
+#pragma unroll
+        for (int q = 0; q < kRanks; ++q) {
+          const int v = (int)(keys[min(r0 + q * kDegThreads, m - 1)] & 0xffffu);
+#pragma unroll
+          for (int c = 0; c < 3; ++c) {
+            p[q][c] = ps[3 * v + c];
+            p[q][3 + c] = pd[3 * v + c];
+          }
+        }
+#pragma unroll
+        for (int q = 0; q < kRanks; ++q)
+          if (r0 + q * kDegThreads < m)
+#pragma unroll
+            for (int c = 0; c < 6; ++c) pout[6 * (size_t)(r0 + q * kDegThreads) + c] = p[q][c];
+      }
     }
   }
 }
@@ -1072,6 +1099,11 @@ constexpr int kCoverMax = 4;   // a core of up to k + kCoverMax vertices is stil
 constexpr int kMissCap = 64;   // ... when it misses at most this many edges
 // Launch 4 of the closure, one workgroup per problem: h1 from the H values, the core peel inside the compact graph
 // (its rows come from launch 3: plain loads behind a kernel boundary), the clique in ascending order, the state.
+// kHFromRows (the three-launch route behind a K1 that stores no row: order, pairs, verdict): the pool holds FULL rows
+// already -- the pair kernel writes both words of every block -- and no launch has left H values: every thread computes
+// the H of its rows from their words by the rule of closure_h.h (the symmetrise launch's, with a bisection in the one
+// block where a row's P crosses d), then the histogram as before.  h_pool is not read.
+template <bool kHFromRows>
 __global__ __launch_bounds__(kDegThreads) void degree_closure_verdict_kernel(
     const ProbDesc* __restrict__ descs, ProbState* __restrict__ states, int32_t* __restrict__ clique,
     const uint64_t* __restrict__ comp_pool, const int32_t* __restrict__ h_pool, const uint32_t* __restrict__ key_pool,
@@ -1096,11 +1128,38 @@ __global__ __launch_bounds__(kDegThreads) void degree_closure_verdict_kernel(
   const uint32_t* keys = key_pool + (size_t)blockIdx.x * kCoreCap;
   constexpr int kHBins = kCoreCap;  // H <= |R| - 1
   for (int i = tid; i <= kHBins; i += kDegThreads) hist[i] = 0;
-  __syncthreads();
-  for (int r = tid; r < m; r += kDegThreads) {
-    const int hv = hout[r];
-    hval[r] = hv;
-    atomicAdd(&hist[hv < kHBins ? hv : kHBins], 1);
+  if constexpr (kHFromRows) {
+    // degree by rank, clamped to kCoreCap (closure_h.h; as the symmetrise launch does)
+    __shared__ unsigned short cdeg[kCoreCap];
+    static_assert(kCoreCap <= 65535 && kDegBins >= kCoreCap, "clamped degrees fit and stay ordered");
+    for (int r = tid; r < m; r += kDegThreads) cdeg[r] = (unsigned short)min(keys[r] >> 16, (uint32_t)kCoreCap);
+    __syncthreads();
+    for (int r = tid; r < m; r += kDegThreads) {
+      const uint64_t* rowp = comp + (size_t)r * kCoreWords;
+      int base = 0, hv = 0;
+      constexpr int kGrp = 16;  // independent loads at a time: one round trip per row at |R| <= 1024
+      for (int g0 = 0; g0 < ng; g0 += kGrp) {
+        uint64_t row[kGrp];
+#pragma unroll
+        for (int u = 0; u < kGrp; ++u) row[u] = g0 + u < ng ? rowp[g0 + u] : 0ull;
+#pragma unroll
+        for (int u = 0; u < kGrp; ++u) {
+          if (g0 + u >= ng) break;
+          const int B = g0 + u;
+          hv = clh::block(row[u], base, min(64, m - 64 * B), &cdeg[64 * B], hv);
+          base += __popcll(row[u]);
+        }
+      }
+      hval[r] = hv;
+      atomicAdd(&hist[hv < kHBins ? hv : kHBins], 1);
+    }
+  } else {
+    __syncthreads();
+    for (int r = tid; r < m; r += kDegThreads) {
+      const int hv = hout[r];
+      hval[r] = hv;
+      atomicAdd(&hist[hv < kHBins ? hv : kHBins], 1);
+    }
   }
   __syncthreads();
   suffix_counts<kHBins>(hist, csum, tid);
@@ -1313,13 +1372,15 @@ ClosurePools degree_closure_pools(void* d_scratch, int batch) {
   cp.part = cp.comp + (size_t)batch * kCoreCap * kCoreWords;
   cp.h = reinterpret_cast<int32_t*>(cp.part + (size_t)batch * kCoreCap * kCoreWords);
   cp.keys = reinterpret_cast<uint32_t*>(cp.h + (size_t)batch * kCoreCap);
+  cp.pts = reinterpret_cast<double*>(cp.part);  // (the three-launch route writes no partial row)
   return cp;
 }
 
 void launch_degree_closure_order(hipStream_t s, const ProbDesc* d_desc, int batch, const int32_t* d_deg, ProbState* d_state,
-                                 void* d_scratch, int32_t* d_counters) {
-  hipLaunchKernelGGL(degree_closure_order_kernel, dim3(1, batch), dim3(kDegThreads), 0, s, d_desc, d_deg, d_state,
-                     degree_closure_pools(d_scratch, batch).keys, d_counters, batch);
+                                 void* d_scratch, int32_t* d_counters, const double* d_src, const double* d_dst) {
+  const ClosurePools cp = degree_closure_pools(d_scratch, batch);
+  hipLaunchKernelGGL(degree_closure_order_kernel, dim3(1, batch), dim3(kDegThreads), 0, s, d_desc, d_deg, d_state, cp.keys,
+                     d_counters, batch, d_src, d_dst, cp.pts);
 }
 
 void launch_degree_closure(hipStream_t s, const ProbDesc* d_desc, int batch, const uint64_t* d_bitmap,
@@ -1331,17 +1392,21 @@ void launch_degree_closure(hipStream_t s, const ProbDesc* d_desc, int batch, con
   uint64_t *comp = cp.comp, *part = cp.part;
   int32_t* hp = cp.h;
   uint32_t* kp = cp.keys;
-  // d_bitmap == nullptr: launches 1 and 2 have run already -- the order through launch_degree_closure_order, the
-  // partial rows from the points (kernels_graph.hip, tim_closure_pairs_kernel: the route whose K1 stores no row)
-  if (d_bitmap) {
-    launch_degree_closure_order(s, d_desc, batch, d_deg, d_state, d_scratch, d_counters);
-    hipLaunchKernelGGL(degree_closure_rows_kernel, dim3(G, batch), dim3(kDegThreads), 0, s, d_desc, d_bitmap, part, kp,
-                       d_counters, batch);
+  // d_bitmap == nullptr: launches 1 and 2 have run already -- the order through launch_degree_closure_order, the FULL
+  // rows from the points (kernels_graph.hip, tim_closure_pairs_kernel: the route whose K1 stores no row) -- and the
+  // verdict launch finds H itself: three launches, no symmetrise
+  if (!d_bitmap) {
+    hipLaunchKernelGGL(degree_closure_verdict_kernel<true>, dim3(batch), dim3(kDegThreads), 0, s, d_desc, d_state, d_clique,
+                       comp, hp, kp, d_counters, batch);
+    return;
   }
+  launch_degree_closure_order(s, d_desc, batch, d_deg, d_state, d_scratch, d_counters, nullptr, nullptr);
+  hipLaunchKernelGGL(degree_closure_rows_kernel, dim3(G, batch), dim3(kDegThreads), 0, s, d_desc, d_bitmap, part, kp,
+                     d_counters, batch);
   hipLaunchKernelGGL(degree_closure_symmetrise_kernel, dim3(std::min(G, 8), batch), dim3(kDegThreads), 0, s, part, comp, hp, kp,
                      d_counters, batch);
-  hipLaunchKernelGGL(degree_closure_verdict_kernel, dim3(batch), dim3(kDegThreads), 0, s, d_desc, d_state, d_clique, comp, hp,
-                     kp, d_counters, batch);
+  hipLaunchKernelGGL(degree_closure_verdict_kernel<false>, dim3(batch), dim3(kDegThreads), 0, s, d_desc, d_state, d_clique, comp,
+                     hp, kp, d_counters, batch);
 }
 
 // Grid (B, batch): B workgroups per problem share the kMaxStarts starts.  Workgroup x begins with start x;

@@ -1404,8 +1404,8 @@ int32_t solve_packed_enqueue(teaser_hip_solver* h, const double* d_src, const do
     if (closure) {
       StageScope sc(h, ST_HEU);
       HIPCHK(h, h->d_core.ensure((size_t)degree_closure_scratch_bytes(batch)));
-      // (no rows to gather from: the order launch and the pairs of the candidate set from the points, then the
-      // symmetrise and verdict launches as they are)
+      // (no rows to gather from: the order launch and the full rows of the candidate set from the points, then the
+      // verdict launch alone)
       if (nostore_k1)
         launch_tim_graph_mfma(s, kTimClosurePairs, dd, batch, max_n, wo, d_src, d_dst, h->d_core.p,
                               h->d_next_count.as<int32_t>() + 2 * (size_t)batch, nullptr, 0, nullptr, ds, h->d_deg.as<int32_t>(),
