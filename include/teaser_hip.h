@@ -1278,6 +1278,148 @@ TEASER_HIP_API int32_t teaser_hip_icp_rgbd_odometry_pyramid_batch(teaser_hip_icp
                                                                   const void* const* target_depth,
                                                                   const void* const* target_color,
                                                                   float* const* images_out);
+/* Depth odometry (Open3D's t.pipelines.odometry.rgbd_odometry_multi_scale with Method.PointToPlane, the tracker of its
+ * dense-SLAM loop, t.pipelines.slam.Model.track_frame_to_model), batched, on the ICP handle: the motion between two
+ * DEPTH frames, source to target, by projective data association on vertex maps with a point-to-plane residual against
+ * the target's normal map (KinectFusion), and its 6 x 6 information matrix.  No colour is read.  The text below IS the
+ * contract; it restates Open3D from knowledge and fixes what Open3D leaves loose.  tests/depth_odometry_reference.py
+ * restates this text; bit parity with an Open3D binary is NOT claimed.  The arithmetic follows "RGB-D odometry" above:
+ * no product-add is fused; every sum is taken left to right as written; "float32" operations round to float32 after
+ * every operation, everything else is FP64; every float32 NaN that is stored in an image is 0x7fc00000, every double NaN
+ * that is handed out 0x7ff8000000000000.
+ *
+ * Per pair one record teaser_icp_depth_odometry_pair_c and two depth images of one size and format (uint16 or float32).
+ * Rows may be padded; only the first width samples of a row are read.  One record teaser_icp_depth_odometry_option_c
+ * serves the call: n_levels L in 1 .. 8 and iterations[0 .. L - 1], iterations[0] belonging to the COARSEST level.
+ *
+ * Images.  Level l of a pair has w_l = width >> l columns, h_l = height >> l rows, n_l = w_l h_l pixels and eleven
+ * float32 planes, row-major: 0 D_s, 1 D_t (depth of source, target), 2 .. 4 the source vertex map (X, Y, Z), 5 .. 7 the
+ * target vertex map, 8 .. 10 the target normal map.  Level intrinsics: fx_l = fx 2^-l, and so fy_l, cx_l, cy_l.
+ *   1 convert   level 0, both images.  uint16: zf = (float)d / (float)depth_scale; float32: zf = the sample.  NaN when zf
+ *               is not finite, (double)zf <= depth_min or (double)zf > depth_max.
+ *   2 pyramid   level l + 1 from level l, both images.  c = D(2y, 2x); a NaN c gives NaN.  Otherwise with
+ *               k = (0.0625, 0.25, 0.375, 0.25, 0.0625), thr = (float)(2.0 depth_outlier_trunc), float32 s = 0, ws = 0:
+ *               for dy = -2 .. 2 (outer), dx = -2 .. 2 (inner): the neighbour (2y + dy, 2x + dx) counts when it lies
+ *               inside the image (one outside is skipped, not clamped), its value v is not a NaN and
+ *               fabsf(v - c) < thr;  then wgt = k[dy + 2] k[dx + 2];  s = s + wgt v;  ws = ws + wgt.   out = s / ws.
+ *   3 vertex    every level, both images, z = D(y, x).  A NaN z gives three NaNs.  Otherwise
+ *               X = (float)((((double)x - cx_l) (double)z) (1.0 / fx_l)),  Y likewise from y, cy_l, fy_l,  Z = z.
+ *   4 normal    every level, the target.  NaN unless x + 1 < w_l, y + 1 < h_l and the vertices V(y, x), V(y, x + 1),
+ *               V(y + 1, x) are free of NaN.  a = V(y, x + 1) - V(y, x), b = V(y + 1, x) - V(y, x), componentwise in
+ *               float32.  In FP64 m = b x a:  m0 = b1 a2 - b2 a1;  m1 = b2 a0 - b0 a2;  m2 = b0 a1 - b1 a0;
+ *               len = sqrt((m0 m0 + m1 m1) + m2 m2).  NaN if len is zero or not finite, else N_i = (float)(m_i / len).
+ *               The normal points towards the camera; its sign cancels in every sum below.
+ *
+ * 5 One iteration at level l, pose T = [R | t] (row-major 4 x 4, source to target).  For source pixel s = v w_l + u whose
+ * vertex P is free of NaN, in doubles:
+ *   p_r = ((R[r][0] P_0 + R[r][1] P_1) + R[r][2] P_2) + t_r;  skipped unless p_2 > 0
+ *   x = ((fx_l p_0) / p_2 + cx_l) + 0.5, y likewise;  skipped unless both are finite, >= 0 and < 2^31
+ *   ut = (int)x, vt = (int)y;  skipped unless ut < w_l and vt < h_l
+ *   Q = the target vertex, N = the target normal at (vt, ut);  skipped if any of the six is a NaN
+ *   r = ((p_0 - Q_0) N_0 + (p_1 - Q_1) N_1) + (p_2 - Q_2) N_2;  skipped unless |r| <= depth_outlier_trunc
+ *   J = ((-p_2) N_1 + p_1 N_2,  p_2 N_0 - p_0 N_2,  (-p_1) N_0 + p_0 N_1,  N_0, N_1, N_2)
+ *   Huber, delta = depth_huber_delta:  |r| < delta:  dh = r, lh = (0.5 r) r;  otherwise dh = delta with the sign of r,
+ *   lh = delta (|r| - 0.5 delta)
+ *   the pixel's 29 values: J_i J_j for i <= j by rows (21), J_i dh (6), lh, and 1.0.  A skipped pixel contributes +0.0.
+ * Summation order: that of "RGB-D odometry" (blocks of TEASER_HIP_ODOMETRY_BLOCK, the tree inside a run of 64, groups of
+ * TEASER_HIP_ODOMETRY_GROUP), taken over the level's n_l SOURCE pixels s.  The sums give A, g, e and the count.
+ * Solve: the LDL^T of "RGB-D odometry" with its three failure rules.  Update: T = U(x) T as there, with fdet_sincos_d.
+ * Measures, after the update: fitness_k = (double)count / (double)n_l, rmse_k = sqrt(e / (double)count).
+ * Convergence: the level is converged behind this iteration if it is not the level's first iteration and
+ *   |fitness_k - fitness_{k-1}| <= relative_fitness fitness_k  and  |rmse_k - rmse_{k-1}| <= relative_rmse rmse_k
+ * (k - 1: the level's previous iteration), so a negative threshold never converges.  The level's remaining iterations
+ * are then not executed: their trace records have executed = 0 and are zero otherwise, like the records behind a
+ * failure.  Levels run from L - 1 down to 0, level l for at most iterations[L - 1 - l] iterations (an entry may be 0),
+ * starting from init.  A pair that FAILS is reported as in "RGB-D odometry": success = 0, transformation = the identity,
+ * information = zero, count = the count of the failing iteration; fitness = inlier_rmse = 0.
+ *
+ * 6 Information matrix of a pair that has not failed, at level 0 and the final pose: over the source pixels with the
+ * projection of step 5; Q must be free of NaN (the normal is not looked at); skipped unless
+ * ((p_0 - Q_0)^2 + (p_1 - Q_1)^2) + (p_2 - Q_2)^2 <= depth_outlier_trunc depth_outlier_trunc.  The rows G_0 .. G_2 of
+ * "RGB-D odometry" from (x, y, z) = Q as doubles; the 21 values per pixel summed in the summation order.
+ * Result: count, fitness, inlier_rmse = those of the last executed iteration (0 when none was executed); iterations =
+ * the executed ones; converged_levels: bit l is set when level l converged.
+ *
+ * teaser_hip_icp_depth_odometry_pairs: results[b] per pair.  trace_out: NULL, or per pair NULL or room for N = SUM
+ * iterations[] records teaser_icp_depth_odometry_trace_c, one per iteration in launch order: level, executed, count,
+ * failed, converged (1 in the record of the iteration behind which the level converged), e, A (21), g (6) and the pose
+ * after the update (the identity when the iteration failed).
+ * teaser_hip_icp_depth_odometry_pyramid_pairs: steps 1 .. 4 alone, run by the same kernels.  images_out[b] takes
+ * 11 SUM_l n_l float32: level l begins at 11 SUM_{k < l} n_k, plane p of it n_l p further on.
+ * Both calls: batch = 0 does nothing.  The launch sequence depends on the options and the image sizes alone, never on
+ * the data (the blocks of a pair that has failed or converged return at once); one stream synchronisation per call.
+ * Every output of a pair is a function of that pair alone: the same bits alone, at any position of any batch, run after
+ * run, whatever the handle's buffers held before.
+ * TEASER_HIP_ERR_BAD_ARG (argument and pair named, before the device is asked for; the handle stays usable): NULL where
+ * something is required; depth_format outside {0, 1}; reserved != 0; n_levels outside 1 .. 8; a negative iteration
+ * count; fx or fy not finite or not > 0; cx, cy, init, depth_scale, depth_min or depth_max not finite; depth_scale <= 0;
+ * depth_min < 0; depth_outlier_trunc or depth_huber_delta not finite or not > 0; relative_rmse or relative_fitness not
+ * finite; width or height below 2^(n_levels - 1) (a level without a pixel) or above 16384; row bytes below a row's size;
+ * more than 2^31 - 1 pixels in one call. */
+typedef struct teaser_icp_depth_odometry_option_c {
+  int32_t n_levels;            /* default 3 */
+  int32_t iterations[8];       /* default {10, 5, 3}: the first entry is the coarsest level's */
+  int32_t reserved[3];         /* must be 0 */
+  double depth_outlier_trunc;  /* default 0.07 */
+  double depth_huber_delta;    /* default 0.05 */
+  double depth_min;            /* default 0.0 */
+  double depth_max;            /* default 3.0 */
+  double relative_rmse;        /* default 1e-6 */
+  double relative_fitness;     /* default 1e-6 */
+  double reserved2[2];         /* must be 0 */
+} teaser_icp_depth_odometry_option_c;
+typedef struct teaser_icp_depth_odometry_pair_c {
+  int32_t width, height;       /* of both images */
+  int32_t depth_format;        /* 0 uint16, 1 float32 (both images) */
+  int32_t reserved;            /* must be 0 */
+  int64_t source_depth_row_bytes, target_depth_row_bytes;
+  double fx, fy, cx, cy;
+  double init[16];             /* row-major, source to target; row 3 must be finite and counts as (0, 0, 0, 1) */
+  double depth_scale;          /* uint16 depth only */
+  double reserved2;            /* must be 0 */
+} teaser_icp_depth_odometry_pair_c;
+typedef struct teaser_icp_depth_odometry_result_c {
+  int32_t success;
+  int32_t count;               /* of the last executed iteration */
+  int32_t iterations;          /* iterations executed */
+  int32_t converged_levels;    /* bit l: level l converged */
+  double fitness, inlier_rmse; /* of the last executed iteration */
+  double transformation[16];
+  double information[36];
+} teaser_icp_depth_odometry_result_c;
+typedef struct teaser_icp_depth_odometry_trace_c {
+  int32_t level, executed, count, failed, converged, reserved;
+  double e;
+  double A[21];
+  double g[6];
+  double pose[16];
+  double reserved2;
+} teaser_icp_depth_odometry_trace_c;
+#ifdef __cplusplus
+static_assert(sizeof(teaser_icp_depth_odometry_option_c) == 112, "teaser_icp_depth_odometry_option_c is 112 bytes");
+static_assert(sizeof(teaser_icp_depth_odometry_pair_c) == 208, "teaser_icp_depth_odometry_pair_c is 208 bytes");
+static_assert(sizeof(teaser_icp_depth_odometry_result_c) == 448, "teaser_icp_depth_odometry_result_c is 448 bytes");
+static_assert(sizeof(teaser_icp_depth_odometry_trace_c) == 384, "teaser_icp_depth_odometry_trace_c is 384 bytes");
+#else
+_Static_assert(sizeof(teaser_icp_depth_odometry_option_c) == 112, "teaser_icp_depth_odometry_option_c is 112 bytes");
+_Static_assert(sizeof(teaser_icp_depth_odometry_pair_c) == 208, "teaser_icp_depth_odometry_pair_c is 208 bytes");
+_Static_assert(sizeof(teaser_icp_depth_odometry_result_c) == 448, "teaser_icp_depth_odometry_result_c is 448 bytes");
+_Static_assert(sizeof(teaser_icp_depth_odometry_trace_c) == 384, "teaser_icp_depth_odometry_trace_c is 384 bytes");
+#endif
+TEASER_HIP_API int32_t teaser_hip_icp_depth_odometry_option_default(teaser_icp_depth_odometry_option_c* option);
+TEASER_HIP_API int32_t teaser_hip_icp_depth_odometry_pairs(teaser_hip_icp* icp, int32_t batch,
+                                                           const teaser_icp_depth_odometry_pair_c* pairs,
+                                                           const teaser_icp_depth_odometry_option_c* option,
+                                                           const void* const* source_depth,
+                                                           const void* const* target_depth,
+                                                           teaser_icp_depth_odometry_result_c* results,
+                                                           teaser_icp_depth_odometry_trace_c* const* trace_out);
+TEASER_HIP_API int32_t teaser_hip_icp_depth_odometry_pyramid_pairs(teaser_hip_icp* icp, int32_t batch,
+                                                                   const teaser_icp_depth_odometry_pair_c* pairs,
+                                                                   const teaser_icp_depth_odometry_option_c* option,
+                                                                   const void* const* source_depth,
+                                                                   const void* const* target_depth,
+                                                                   float* const* images_out);
 /* Outlier removal: statistical (Open3D's remove_statistical_outlier), on the ICP handle.  Per cloud, with
  * nb_neighbors in [1, TEASER_HIP_ICP_KNN_MAX] and std_ratio finite and > 0:
  *   avg[i]    = (sum of sqrt(d2) over point i's m = min(nb_neighbors, n) nearest of self k-NN, the point itself

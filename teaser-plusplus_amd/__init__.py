@@ -184,6 +184,8 @@ EXPORTED_SYMBOLS = [
     "teaser_hip_stsdf_ray_cast_views", "teaser_hip_stsdf_extract_triangle_mesh",
     "teaser_hip_icp_odometry_option_default", "teaser_hip_icp_rgbd_odometry_batch",
     "teaser_hip_icp_rgbd_odometry_pyramid_batch",
+    "teaser_hip_icp_depth_odometry_option_default", "teaser_hip_icp_depth_odometry_pairs",
+    "teaser_hip_icp_depth_odometry_pyramid_pairs",
 ]
 
 
@@ -303,6 +305,7 @@ def lib():
     _tsdf.declare(L)
     from . import odometry as _odometry
     _odometry.declare(L)
+    _odometry.declare_depth(L)
     _lib = L
     return L
 
@@ -1194,7 +1197,10 @@ from .tsdf import (UniformTSDFVolume, ScalableTSDFVolume, TSDFVolumeColorType, T
                    TSDFRayCastResult, write_triangle_mesh, ray_cast, ray_cast_batch, extract_triangle_mesh)
 from .odometry import (OdometryOption, RGBDOdometryJacobianFromColorTerm,  # noqa: E402
                        RGBDOdometryJacobianFromHybridTerm, RGBDImage, compute_rgbd_odometry,
-                       compute_rgbd_odometry_batch, rgbd_odometry_pyramid_batch)
+                       compute_rgbd_odometry_batch, rgbd_odometry_pyramid_batch,
+                       OdometryConvergenceCriteria, OdometryLossParams, DepthOdometryOption,
+                       compute_depth_odometry, compute_depth_odometry_batch, depth_odometry_pyramid_batch,
+                       track_frame_to_model)
 
 SCRATCH_KINDS = ("icp", "voxel", "features", "posegraph", "ransac", "fgr", "plane")
 
@@ -1255,4 +1261,6 @@ __all__ = ["fill_scratch", "SCRATCH_KINDS",
            "UniformTSDFVolume", "TSDFVolumeColorType", "TSDFPointCloud", "TSDFTriangleMesh", "TSDFRayCastResult",
            "write_triangle_mesh", "ray_cast", "ray_cast_batch", "extract_triangle_mesh",
            "OdometryOption", "RGBDOdometryJacobianFromColorTerm", "RGBDOdometryJacobianFromHybridTerm", "RGBDImage",
-           "compute_rgbd_odometry", "compute_rgbd_odometry_batch", "rgbd_odometry_pyramid_batch"]
+           "compute_rgbd_odometry", "compute_rgbd_odometry_batch", "rgbd_odometry_pyramid_batch",
+           "OdometryConvergenceCriteria", "OdometryLossParams", "DepthOdometryOption", "compute_depth_odometry",
+           "compute_depth_odometry_batch", "depth_odometry_pyramid_batch", "track_frame_to_model"]
