@@ -2789,6 +2789,130 @@ TEASER_HIP_API int32_t teaser_hip_stsdf_extract_triangle_mesh(teaser_hip_stsdf* 
                                                               int32_t* triangles, int64_t* vertex_count_out,
                                                               int64_t* triangle_count_out);
 
+/* Ray casting scene: triangle meshes as the TARGET of queries -- the first surface a ray meets, whether anything lies
+ * between two parameters of a ray, and the closest point of the surface to a point.  The interface follows Open3D's
+ * t.geometry.RaycastingScene (add_triangles, cast_rays, test_occlusions, compute_closest_points, compute_distance,
+ * create_rays_pinhole).  It restates Open3D from memory; Open3D and Embree are not run and bit parity with an Open3D or
+ * Embree binary is NOT claimed.  The text below IS the contract; tests/scene_reference.py restates it in numpy, by
+ * brute force over all triangles, and is the parity target of the host and GPU tests.
+ *
+ * Geometries.  teaser_hip_scene_add_triangles takes vertices (n_vertices x 3 float32) and triangles (n_triangles x 3
+ * uint32 indices into them) and answers the geometry id 0, 1, 2, ... in geometry_id_out (may be NULL).  The GLOBAL INDEX g
+ * of a triangle counts the triangles of all geometries in the order added, inside a geometry in the order given.  The
+ * call makes the scene uncommitted and may follow queries; teaser_hip_scene_commit builds the search structure; a query
+ * on an uncommitted scene builds first.  An empty mesh is a geometry without triangles.
+ *
+ * Arithmetic.  Everything below is in double on the float32 inputs.  No product-add is fused.  Every three-term sum is
+ * (a + b) + c.  A cross product a x b is (a1 b2 - a2 b1, a2 b0 - a0 b2, a0 b1 - a1 b0), both products of a component
+ * rounded; a dot product is (a0 b0 + a1 b1) + a2 b2.
+ *
+ * The triangle.  e1 = v1 - v0;  e2 = v2 - v0;  n = e1 x e2.  The triangle is DEAD when n == (0, 0, 0): it is never
+ * hit and never closest.
+ *
+ * Ray-triangle test.  A ray is (ox oy oz dx dy dz), d used as given (not normalised), so t counts in units of |d|.
+ *   p = d x e2;  det = e1 . p;                         det == 0: miss
+ *   inv = 1.0 / det;  s = o - v0;
+ *   u = (s . p) inv;                                   miss unless u >= 0 && u <= 1
+ *   q = s x e1;  v = (d . q) inv;                      miss unless v >= 0 && u + v <= 1
+ *   t = (e2 . q) inv;                                  miss unless t >= 0 && t < +inf
+ * The comparisons are written so that a NaN misses.  Both faces are hit; nothing is culled by orientation.  A ray with
+ * d == (0, 0, 0) or a non-finite component misses everything; that is an outcome, not an error.
+ *
+ * teaser_hip_scene_cast_rays.  The winner of a ray is the minimum of (t, g), t compared in double.  On a hit:
+ *   t_hit = (float)t;  primitive_uvs = ((float)u, (float)v);  primitive_normals = (float)(n_k / sqrt(n . n));
+ *   geometry_ids = the winner's geometry;  primitive_ids = its index inside that geometry.
+ * On a miss: t_hit = +inf, both ids 0xFFFFFFFF, uv and normal 0.  Every output pointer may be NULL.
+ *
+ * teaser_hip_scene_test_occlusions.  occluded[i] = 1 iff some triangle passes the test with tnear <= t && t <= tfar,
+ * else 0.
+ *
+ * teaser_hip_scene_closest_points.  Per triangle Ericson, Real-Time Collision Detection 5.1.5,
+ * ClosestPtPointTriangle, with a = v0, b = v1, c = v2, ab = e1, ac = e2, in the order of the book:
+ *   ap = p - a;  d1 = ab . ap;  d2 = ac . ap;          d1 <= 0 && d2 <= 0:                  c* = a             (v, w) = (0, 0)
+ *   bp = p - b;  d3 = ab . bp;  d4 = ac . bp;          d3 >= 0 && d4 <= d3:                 c* = b             (1, 0)
+ *   vc = d1 d4 - d3 d2;            vc <= 0 && d1 >= 0 && d3 <= 0:  v = d1 / (d1 - d3);      c* = a + v ab      (v, 0)
+ *   cp = p - c;  d5 = ab . cp;  d6 = ac . cp;          d6 >= 0 && d5 <= d6:                 c* = c             (0, 1)
+ *   vb = d5 d2 - d1 d6;            vb <= 0 && d2 >= 0 && d6 <= 0:  w = d2 / (d2 - d6);      c* = a + w ac      (0, w)
+ *   va = d3 d6 - d5 d4;            va <= 0 && d4 - d3 >= 0 && d5 - d6 >= 0:
+ *                                  w = (d4 - d3) / ((d4 - d3) + (d5 - d6));                 c* = b + w (c - b) (1 - w, w)
+ *   otherwise  denom = 1.0 / ((va + vb) + vc);  v = vb denom;  w = vc denom;               c* = (a + ab v) + ac w
+ * the first rule that applies decides.  d2* = ((cx - px)^2 + (cy - py)^2) + (cz - pz)^2 with cx = c*_x - p_x formed
+ * first.  A DEAD triangle and a triangle whose d2* is not < +inf are skipped.  The winner is the minimum of (d2*, g).
+ *   distance = (float)sqrt(d2*);  closest = (float)c*;  primitive_uvs = ((float)v, (float)w), the weights of v1 and
+ *   v2 as for rays;  primitive_normals and the ids as for rays.
+ * Without a winner (no live triangle, or a point with a non-finite component): distance = +inf, both ids 0xFFFFFFFF,
+ * everything else 0.
+ *
+ * Views.  One record teaser_scene_view_c per view; E = extrinsic, row-major 4 x 4 world to camera as in "TSDF ray
+ * casting".  The ray of pixel (row v, column u), in double:
+ *   a = (((double)u + pixel_offset) - cx) / fx;   b = (((double)v + pixel_offset) - cy) / fy;
+ *   d_k = (E[0][k] a + E[1][k] b) + E[2][k];      o_k = c_k = -((E[0][k] E[0][3] + E[1][k] E[1][3]) + E[2][k] E[2][3])
+ * (the centre exactly as "TSDF ray casting" forms it), both rounded to float32.  These float32 rays then go through the
+ * ray contract above, so t_hit is the z-depth in the camera.  teaser_hip_scene_cast_views EQUALS
+ * teaser_hip_scene_cast_rays on the rays these formulas give, bit for bit.  Each output is an array of n_views host
+ * pointers; a whole array or any entry may be NULL.  The maps of a view are packed height x width (t_hit, the ids),
+ * height x width x 2 (uv) and height x width x 3 (normals).  Views of any mix of sizes go into one call: one launch
+ * covers all pixels of all views (blocks of 16 x 16 pixels and a block map); only the requested maps are computed and
+ * copied.  A view with width or height 0 is legal.  pixel_offset 0.5 (the default, Open3D's create_rays_pinhole) looks
+ * through pixel centres; 0 is the convention of "Depth frames".
+ *
+ * The search structure is NOT part of the contract.  Every output EQUALS what the definitions above give over ALL
+ * triangles; the results are the same bits for any grouping of rays, points and views into calls, for any order of
+ * queries, and run after run.  No floating-point atomic is used.  (How the structure keeps that promise, and the one
+ * condition its argument needs -- a ray that lies within about 1e-8 rad of a triangle's plane, where the test above
+ * divides rounding noise by rounding noise -- is DESIGN.md section 41.)  One stream synchronisation per query; a query
+ * that has to build adds the build's.
+ *
+ * TEASER_HIP_ERR_BAD_ARG (the message names the argument; the handle stays usable): a NULL handle; a negative count; NULL
+ * where a count is positive (vertices, triangles, rays, points, views, occluded); a non-finite vertex; a triangle index
+ * >= n_vertices; more than 2^30 triangles in a scene; tnear or tfar NaN; of a view: width or height negative or above
+ * 16384, fx or fy zero or not finite, cx, cy, the extrinsic or pixel_offset not finite, reserved != 0, more than
+ * 2^31 - 1 blocks in one call.  Empty meshes, zero rays, zero points and zero views are legal.
+ * TEASER_HIP_ERR_HIP with "visit cap": a traversal did not end within 4 n + 64 node visits (it cannot on a tree this
+ * library built; the cap exists so that damaged memory ends in an error, not in a hang).
+ *
+ * Not offered: signed distance and occupancy, count_intersections / list_intersections, lines and other primitives,
+ * refitting after vertex motion, a device-side hand-over to the odometry, mesh sampling. */
+typedef struct teaser_scene_view_c {
+  int32_t width, height;
+  double fx, fy, cx, cy;
+  double extrinsic[16]; /* row-major, world to camera */
+  double pixel_offset;  /* default 0.5 */
+  int64_t reserved;     /* must be 0 */
+} teaser_scene_view_c;
+#ifdef __cplusplus
+static_assert(sizeof(teaser_scene_view_c) == 184, "teaser_scene_view_c is 184 bytes");
+#else
+_Static_assert(sizeof(teaser_scene_view_c) == 184, "teaser_scene_view_c is 184 bytes");
+#endif
+typedef struct teaser_hip_scene teaser_hip_scene;
+/* device < 0: the current HIP device.  TEASER_HIP_ERR_NO_DEVICE without a GPU: there is no CPU path. */
+TEASER_HIP_API int32_t teaser_hip_scene_create(int32_t device, teaser_hip_scene** out);
+TEASER_HIP_API int32_t teaser_hip_scene_destroy(teaser_hip_scene* scene);
+TEASER_HIP_API const char* teaser_hip_scene_last_error(const teaser_hip_scene* scene);
+/* DIAGNOSTIC, as teaser_hip_icp_fill_scratch: every scratch and staging buffer; the triangles and the tree are state. */
+TEASER_HIP_API int32_t teaser_hip_scene_fill_scratch(teaser_hip_scene* scene, int32_t byte, int64_t* bytes_out);
+TEASER_HIP_API int32_t teaser_hip_scene_add_triangles(teaser_hip_scene* scene, const float* vertices, int64_t n_vertices,
+                                                      const uint32_t* triangles, int64_t n_triangles,
+                                                      uint32_t* geometry_id_out);
+TEASER_HIP_API int32_t teaser_hip_scene_commit(teaser_hip_scene* scene);
+TEASER_HIP_API int32_t teaser_hip_scene_triangle_count(const teaser_hip_scene* scene, int64_t* count_out);
+TEASER_HIP_API int32_t teaser_hip_scene_cast_rays(teaser_hip_scene* scene, const float* rays, int64_t n, float* t_hit,
+                                                  uint32_t* geometry_ids, uint32_t* primitive_ids, float* primitive_uvs,
+                                                  float* primitive_normals);
+TEASER_HIP_API int32_t teaser_hip_scene_test_occlusions(teaser_hip_scene* scene, const float* rays, int64_t n, double tnear,
+                                                        double tfar, uint8_t* occluded);
+TEASER_HIP_API int32_t teaser_hip_scene_closest_points(teaser_hip_scene* scene, const float* points, int64_t n,
+                                                       float* closest, float* distance, uint32_t* geometry_ids,
+                                                       uint32_t* primitive_ids, float* primitive_uvs,
+                                                       float* primitive_normals);
+/* Zeroes the record, sets the identity extrinsic and pixel_offset = 0.5. */
+TEASER_HIP_API int32_t teaser_hip_scene_view_default(teaser_scene_view_c* view);
+TEASER_HIP_API int32_t teaser_hip_scene_cast_views(teaser_hip_scene* scene, const teaser_scene_view_c* views,
+                                                   int32_t n_views, float* const* t_hit, uint32_t* const* geometry_ids,
+                                                   uint32_t* const* primitive_ids, float* const* primitive_uvs,
+                                                   float* const* primitive_normals);
+
 /* Page-locked host memory from the HIP runtime THIS library runs on.  teaser_hip_submit_batch(..., INPUT_HOST) moves
  * the points with one DMA copy per cloud, at PCIe speed only when the runtime knows the pages are locked.  A buffer
  * pinned by another HIP runtime instance in the same process (e.g. the one a Python framework bundles) is pageable

@@ -186,6 +186,10 @@ EXPORTED_SYMBOLS = [
     "teaser_hip_icp_rgbd_odometry_pyramid_batch",
     "teaser_hip_icp_depth_odometry_option_default", "teaser_hip_icp_depth_odometry_pairs",
     "teaser_hip_icp_depth_odometry_pyramid_pairs",
+    "teaser_hip_scene_create", "teaser_hip_scene_destroy", "teaser_hip_scene_last_error", "teaser_hip_scene_fill_scratch",
+    "teaser_hip_scene_add_triangles", "teaser_hip_scene_commit", "teaser_hip_scene_triangle_count",
+    "teaser_hip_scene_cast_rays", "teaser_hip_scene_test_occlusions", "teaser_hip_scene_closest_points",
+    "teaser_hip_scene_view_default", "teaser_hip_scene_cast_views",
 ]
 
 
@@ -306,6 +310,8 @@ def lib():
     from . import odometry as _odometry
     _odometry.declare(L)
     _odometry.declare_depth(L)
+    from . import scene as _scene
+    _scene.declare(L)
     _lib = L
     return L
 
@@ -1202,6 +1208,8 @@ from .odometry import (OdometryOption, RGBDOdometryJacobianFromColorTerm,  # noq
                        compute_depth_odometry, compute_depth_odometry_batch, depth_odometry_pyramid_batch,
                        track_frame_to_model)
 
+from .scene import RaycastingScene, create_rays_pinhole  # noqa: E402
+
 SCRATCH_KINDS = ("icp", "voxel", "features", "posegraph", "ransac", "fgr", "plane")
 
 
@@ -1263,4 +1271,5 @@ __all__ = ["fill_scratch", "SCRATCH_KINDS",
            "OdometryOption", "RGBDOdometryJacobianFromColorTerm", "RGBDOdometryJacobianFromHybridTerm", "RGBDImage",
            "compute_rgbd_odometry", "compute_rgbd_odometry_batch", "rgbd_odometry_pyramid_batch",
            "OdometryConvergenceCriteria", "OdometryLossParams", "DepthOdometryOption", "compute_depth_odometry",
-           "compute_depth_odometry_batch", "depth_odometry_pyramid_batch", "track_frame_to_model"]
+           "compute_depth_odometry_batch", "depth_odometry_pyramid_batch", "track_frame_to_model",
+           "RaycastingScene", "create_rays_pinhole"]
